@@ -5,22 +5,25 @@ Workload (BASELINE.json config 3, the one the metric is quoted on): the determin
 stand-in scene (500 k triangles, seed 0; the real PS5 ISF is not in the reference) in the
 FRAMING OF THE REFERENCE'S OWN RENDER (readme/ps5_b5_s128.png: 38.8 % of its 8x8 pixel blocks are
 sky; generator flag 8, host/scene_gen.cpp), 1920x1080, 128 spp, 5 bounces, Cook–Torrance, FILMIC.
-The line also carries `config.legacy_framing`: the same measurement on the framing rounds 1-3
+With --full the line also carries `config.legacy_framing`: the same measurement on the framing rounds 1-3
 reported (52.5 % sky blocks), taken in the same run.  A "step" is one complete render of that frame:
 every rank renders its interleaved 32x32 tiles (global pixel index in the seed formula, so
 the image is bit-identical for any N), then — for N > 1 — one RCCL all-gather of the packed
 u8 framebuffer slices and a scatter into the row-major image on every rank.  The scene, KD-tree,
 origin grids and textures are resident in HBM before the timed region starts.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` without a launcher starts the N ranks itself (one process per GPU,
 torch.distributed.run, RCCL) before this process makes any GPU call, and exits with their status.
 
-Rank 0 prints ONE JSON line (contract in the task statement) carrying `roofline` (dominant
-kernel, HIP-event timed inside the timed region) and, at N=1, `cpu_baseline` (the CPU oracle —
-a port, all host cores — on a bounded sample of the same workload).
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run sets up, warms up, times
+the K steps and prints the headline; `roofline` (dominant kernel, HIP-event timed inside the timed
+region, plus a counters run and a copy-bandwidth run of its own), `config.legacy_framing` and, at
+N=1, `cpu_baseline` (the CPU oracle — a port, all host cores — on a bounded sample of the same
+workload) come with --full and are null without it.  --dump-outputs DIR writes what the last timed
+step computed (rank 0's frame and accumulation buffer) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -60,6 +63,26 @@ def kernel_source_sha16():
             h.update(f.name.encode())
             h.update(f.read_bytes())
     return h.hexdigest()[:16]
+
+
+DUMP_BYTES = 60 << 20   # --dump-outputs: under 64 MB in all, .npy headers included
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each [rows, k] device tensor of `arrays` as out_dir/<name>.npy in float32.  An array larger than its share of
+    DUMP_BYTES is cut to a fixed sample of rows (seed 0, ascending), whose row numbers go to <name>_rows.npy (float64)."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.cpu().numpy().astype(np.float32)
+        if a.nbytes > share:
+            keep = share // (a.itemsize * a.shape[1] + 8)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            np.save(out_dir / f"{name}_rows.npy", rows.astype(np.float64))
+            a = a[rows]
+        np.save(out_dir / f"{name}.npy", a)
 
 
 def count_gpus():
@@ -113,16 +136,23 @@ def main():
     ap.add_argument("--scene-flags", type=int, default=8,
                     help="generator flags: 1 = translucent shells (config 5), 2 = textures, 4 = closed room, 8 = the framing of "
                          "the reference's PS5 render (default; 0 = the framing of rounds 1-3)")
-    ap.add_argument("--no-legacy", action="store_true", help="skip the second measurement on the rounds 1-3 framing")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the counters run and roofline, the legacy framing, "
+                         "the CPU baseline (--no-counters / --no-legacy / --cpu-seconds 0 drop one of them again)")
+    ap.add_argument("--no-legacy", action="store_true", help="--full: skip the second measurement on the rounds 1-3 framing")
     ap.add_argument("--opt-flags", type=int, default=0, help="extra pt_opts.flags (4 = PT_FLAG_NO_GRIDS: KD-tree only)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline budget (0 = skip)")
-    ap.add_argument("--no-counters", action="store_true")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: CPU baseline budget (0 = skip)")
+    ap.add_argument("--no-counters", action="store_true", help="--full: skip the counters run and the roofline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32; rank 0)")
     ap.add_argument("--save-png", default=None)
     ap.add_argument("--backend", default="nccl", help="collective backend for N > 1 (nccl = RCCL; gloo only to rehearse "
                     "the N > 1 path with several ranks on ONE GPU: set PT_BENCH_DEVICE=0)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
 
@@ -263,6 +293,13 @@ def main():
     total_samples = npix * args.spp * args.steps
     value = total_samples / elapsed / 1e6
 
+    # ---- what the last timed step computed, before any later render reuses the buffers: the u8 frame (N > 1: the assembled
+    # image) and this rank's f32 accumulation buffer, [pixels, 3] each in the order pt_render returns them
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {
+            "rgb8": (image if world > 1 else rgb_local[: n_local * 3]).view(-1, 3),
+            "accum": acc_local[: n_local * 3].view(-1, 3)})
+
     # ---- roofline of the dominant kernel, this rank's shard.  Algorithmic bytes are SURVEY §8-d's per-unit terms for
     # the work the kernel does: 160 B per path segment (64 B ray + 16 B hit record, written and read), 104 B per shadow
     # ray, 8 B per KD node visited, 36 B per primitive tested, 160 B per shaded hit (96 B vertex attributes + 64 B
@@ -271,7 +308,7 @@ def main():
     # the camera-grid cull of the timed frames (rank 0's tiles): blocks whose samples are the background without RNG or cast
     cull_blocks, cull_empty = gscene.cull_stats()
     counters = None
-    if not args.no_counters:
+    if args.full and not args.no_counters:
         copts = pta.Opts.make(flags=pta.PT_FLAG_COUNTERS | args.opt_flags, device=local_rank, shard_rank=rank,
                               shard_count=world, tile_w=tile, tile_h=tile)
         gscene.render_device(prof, copts, rgb_local.data_ptr(), acc_local.data_ptr(), stream)
@@ -437,7 +474,7 @@ def main():
 
     # ---- CPU baseline: the oracle on a bounded sample of the same workload (rank 0, N = 1 only)
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         oracle = entry.load_oracle()
         osc = oracle.OracleScene(scene.desc, oracle.PTO_BVH)
         rows_per_band = 2
@@ -474,7 +511,7 @@ def main():
     # ---- the same measurement on the framing rounds 1-3 reported (generator flags 0: 52.5 % of the pixel blocks are sky), so
     # that the two lines of numbers stay comparable across rounds
     legacy = None
-    if rank == 0 and world == 1 and args.scene_flags == 8 and not args.no_legacy:
+    if args.full and rank == 0 and world == 1 and args.scene_flags == 8 and not args.no_legacy:
         gscene.close()
         scene0 = pta.HostScene.generate_ps5(args.tris, 0, 0)
         g0 = pta.GpuScene(scene0, device=local_rank)

@@ -1,5 +1,6 @@
 import sys
-sys.path.insert(0,'/root/repo')
+from pathlib import Path
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import torch; torch.zeros(1,device='cuda')
 import __graft_entry__ as e
 pta=e.load_package()

@@ -194,6 +194,21 @@ typedef struct pt_scene pt_scene;
 int pt_scene_create(const pt_scene_desc* desc, int device, pt_scene** out);
 void pt_scene_destroy(pt_scene* scene);
 
+/* Give a scene another camera.  Afterwards every render entry point (pt_render, pt_render_device, pt_render_gathered,
+ * sharded calls), pt_debug_render and the grid / escape-mask test hooks behave exactly as on a scene that pt_scene_create
+ * made with this camera: the same images bit for bit.  Accepts the cameras pt_scene_create accepts; a null argument is
+ * PT_ERR_INVALID.  Works on scenes made by pt_scene_create_from_prep, also after pt_prep_destroy (the scene keeps what the
+ * camera grid needs, in host memory).
+ * The call synchronises the scene's device before it replaces anything: a frame already queued by pt_render_device
+ * completes with the old camera.  The caller must not enqueue work on the scene from another thread during the call.
+ * The camera grid is rebuilt on the device; without the memory for it the camera goes without one (camera rays take
+ * the KD-tree, as on a fresh scene in that situation) and the call succeeds.  Any other device failure returns
+ * PT_ERR_DEVICE and leaves the scene rendering the OLD camera.  With PT_OG_HOST=1 (grids built on the host) a moved
+ * camera goes without a camera grid.  Every later frame runs as the first frame of its configuration (no frame plan
+ * carries over); the escape masks are kept where they still prove their misses, otherwise rebuilt on the schedule of a
+ * fresh scene (PT_ESCAPE_AFTER). */
+int pt_scene_set_camera(pt_scene* scene, const pt_camera* camera);
+
 /* The host half of pt_scene_create (validation, KD build, origin grids) as an object of its own: build it ONCE
  * and upload it to every device of a multi-GPU render instead of repeating seconds of CPU work per device. */
 typedef struct pt_prep pt_prep;

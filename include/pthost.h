@@ -29,6 +29,15 @@ int pth_scene_load_isf(const char* path, pth_scene** out);
 void pth_scene_free(pth_scene* s);
 const pt_scene_desc* pth_scene_desc(const pth_scene* s);
 
+/* Replace the scene's camera (a host-side copy of a scene with a moved camera: baselines, oracle scenes). */
+int pth_scene_set_camera(pth_scene* s, const pt_camera* camera);
+
+/* A camera path (`path-tracer render --camera-path`): a JSON array of ISF camera objects ("transform", "fov", "zfar",
+ * "znear", as the "camera" of a scene; the ISF loader's messages for a missing field).  An empty array or anything but
+ * an array is PT_ERR_PARSE.  *out is malloc'd: free with pth_camera_path_free. */
+int pth_camera_path_load(const char* path, pt_camera** out, uint32_t* n);
+void pth_camera_path_free(pt_camera* cameras);
+
 /* Deterministic synthetic stand-in for the (unpublished) PS5 scene
  * (SURVEY §8-d): ground quad + two tessellated curved shells + an emissive
  * strip + one point light, black background, fov 0.6911112.

@@ -172,9 +172,9 @@ HOST_SYMBOLS = ["pth_scene_load_isf", "pth_scene_free", "pth_scene_desc", "pth_s
                 "pth_scene_save_isf", "pth_convert_gltf", "pth_profile_load", "pth_profile_parse", "pth_png_read",
                 "pth_png_decode", "pth_png_write_rgb8", "pth_free", "pth_prim_count", "pth_kd_build",
                 "pth_kd_free", "pth_origin_grid_build", "pth_ortho_grid_build", "pth_origin_grid_auto_resolution", "pth_origin_grid_free",
-                "pth_last_error"]
+                "pth_last_error", "pth_scene_set_camera", "pth_camera_path_load", "pth_camera_path_free"]
 # Every symbol include/ptgpu.h declares.
-GPU_SYMBOLS = ["pt_scene_create", "pt_scene_destroy", "pt_prep_create", "pt_prep_destroy", "pt_scene_create_from_prep",
+GPU_SYMBOLS = ["pt_scene_create", "pt_scene_destroy", "pt_scene_set_camera", "pt_prep_create", "pt_prep_destroy", "pt_scene_create_from_prep",
                "pt_comm_unique_id", "pt_comm_create", "pt_comm_create_all", "pt_comm_destroy", "pt_gather_tiles", "pt_render_gathered", "pt_local_pixel_count", "pt_local_pixel_map",
                "pt_render", "pt_render_device", "pt_debug_render", "pt_assemble_tiles", "pt_get_timing", "pt_get_counters",
                "pt_scene_get_info", "pt_scene_set_cu_mask", "pt_stream_create_cu_mask", "pt_stream_destroy", "pt_get_cull_stats", "pt_scene_escape_copy", "pt_scene_grid_header", "pt_scene_grid_copy", "pt_trace_rays", "pt_trace_rays_wavefront",
@@ -219,6 +219,10 @@ def host_lib():
         L.pth_origin_grid_free.argtypes = [C.POINTER(OriginGridC)]
         L.pth_origin_grid_free.restype = None
         L.pth_last_error.restype = C.c_char_p
+        L.pth_scene_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
+        L.pth_camera_path_load.argtypes = [C.c_char_p, C.POINTER(C.POINTER(Camera)), C.POINTER(C.c_uint32)]
+        L.pth_camera_path_free.argtypes = [C.POINTER(Camera)]
+        L.pth_camera_path_free.restype = None
         _host = L
     return _host
 
@@ -240,6 +244,7 @@ def gpu_lib():
         L.pt_prep_destroy.argtypes = [vp]
         L.pt_prep_destroy.restype = None
         L.pt_scene_create_from_prep.argtypes = [vp, C.c_int, C.POINTER(vp)]
+        L.pt_scene_set_camera.argtypes = [vp, C.POINTER(Camera)]
         L.pt_comm_unique_id.argtypes = [vp]
         L.pt_comm_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
         L.pt_comm_create_all.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
@@ -289,6 +294,40 @@ def check_gpu(rc):
         raise PtError(rc, gpu_lib().pt_last_error().decode(errors="replace"))
 
 
+def make_camera(camera):
+    """A Camera from a Camera (copied) or a dict in ISF form ({"transform": 4 columns of 4, "fov", "zfar", "znear"}, the
+    numbers narrowed to f32 as the ISF loader does).  None is passed on as a null pointer (the C ABI rejects it)."""
+    if camera is None:
+        return None
+    if isinstance(camera, Camera):
+        c = Camera()
+        C.memmove(C.byref(c), C.byref(camera), C.sizeof(Camera))
+        return c
+    cols = camera["transform"]
+    if len(cols) != 4 or any(len(col) != 4 for col in cols):
+        raise ValueError("camera transform: 4 columns of 4 numbers expected")
+    return Camera((C.c_float * 16)(*[float(v) for col in cols for v in col]), float(camera["fov"]),
+                  float(camera["zfar"]), float(camera["znear"]))
+
+
+def camera_to_dict(camera):
+    """The ISF form of a Camera (f32 values as Python floats: they round-trip exactly)."""
+    t = list(camera.transform)
+    return {"transform": [t[4 * k:4 * k + 4] for k in range(4)], "fov": camera.fov, "zfar": camera.zfar,
+            "znear": camera.znear}
+
+
+def load_camera_path(path):
+    """`--camera-path` file (pth_camera_path_load): a JSON array of ISF camera objects -> list of Camera."""
+    ptr = C.POINTER(Camera)()
+    n = C.c_uint32(0)
+    check_host(host_lib().pth_camera_path_load(os.fsencode(str(path)), C.byref(ptr), C.byref(n)))
+    try:
+        return [make_camera(ptr[i]) for i in range(n.value)]
+    finally:
+        host_lib().pth_camera_path_free(ptr)
+
+
 class HostScene:
     """Owned pth_scene handle (ISF file or generated)."""
 
@@ -314,6 +353,16 @@ class HostScene:
     @property
     def n_triangles(self):
         return int(self.desc.contents.n_triangles)
+
+    @property
+    def camera(self):
+        """A copy of the scene's camera."""
+        return make_camera(self.desc.contents.camera)
+
+    def set_camera(self, camera):
+        """pth_scene_set_camera: camera is a Camera or a dict in ISF form."""
+        c = make_camera(camera)
+        check_host(host_lib().pth_scene_set_camera(self.handle, C.byref(c) if c is not None else None))
 
     @property
     def n_prims(self):
@@ -513,6 +562,11 @@ class GpuScene:
         i = SceneInfo()
         check_gpu(self.lib.pt_scene_get_info(self.handle, C.byref(i)))
         return i
+
+    def set_camera(self, camera):
+        """pt_scene_set_camera: camera is a Camera or a dict in ISF form; None raises PtError (PT_ERR_INVALID)."""
+        c = make_camera(camera)
+        check_gpu(self.lib.pt_scene_set_camera(self.handle, C.byref(c) if c is not None else None))
 
     def render(self, profile, opts=None):
         """Host-buffer render: returns (rgb8 [n,3] uint8, accum [n,3] float32)."""

@@ -483,6 +483,20 @@ struct DeviceBuffer {
 
 }  // namespace
 
+// What pt_scene_set_camera needs to give a scene the camera grid pt_scene_create would have made for a new camera, without
+// the caller's pt_scene_desc or the prep: the primitives' geometry as the grid footprints take it (9 floats: three
+// positions, or centre + radius) with the id | sphere-bit word, the positions of the triangles no model owns (og_params_point's
+// extent scans every triangle of the description), and the resolution rule.  Shared by a prep and the scenes made from it
+// (host memory: 40 B per primitive).
+struct CamGridSource {
+    std::vector<float> og_geom;
+    std::vector<uint32_t> og_words;
+    std::vector<float> unowned;   // 9 floats per triangle outside every model's range
+    bool device_grids = false;    // false: PT_OG_HOST=1 (a moved camera goes without a grid)
+    uint32_t cam_res = 0;         // resolution of a camera grid; 0: none whatever the camera (PT_OG=0, no primitives, budget)
+    double budget = 0;            // PT_OG_BUDGET_GIB in bytes
+};
+
 struct pt_scene {
     int device = 0;
     DevScene dev{};
@@ -491,6 +505,8 @@ struct pt_scene {
     bool ortho_light_grids = false;   // some light grid is orthographic (a directional light): kernel variants DIRL
     std::vector<uint32_t> host_prim_entry;
     std::vector<pth_origin_grid> grid_headers;   // device-built grids: [0] camera, [1 + i] light i (enabled = 0: none)
+    std::shared_ptr<const CamGridSource> cam_src;   // (pt_scene_set_camera)
+    uint64_t cam_grid_bytes = 0, cam_grid_refs = 0;   // device bytes / list entries of the camera grid
     std::vector<DevGrid> host_light_grids;
     struct BuiltGrids {   // what grids_on_device() produced for this scene (possibly while the KD-tree was still being built)
         bool done = false, all_lights = false, ortho = false;
@@ -541,6 +557,7 @@ struct pt_scene {
     // escape masks: wanted (PT_ESCAPE), built when the scene has rendered `escape_after` frames of the default pipeline
     bool escape_wanted = false, escape_tried = false;
     uint32_t escape_after = 2;
+    float escape_delta = 0.f;   // the delta_in the masks were built with (pt_scene_set_camera keeps them while a camera needs no more)
     mutable uint32_t frames_rendered = 0;
     mutable int trace_blocks = 0, shadow_blocks = 0, n_cu = 0;
     // (experiment, pt_scene_set_cu_mask: the scene's own streams confined to these CUs, grids sized for their number)
@@ -631,8 +648,7 @@ struct pt_prep {
     bool device_grids = false;
     GridJob cam_job;
     std::vector<GridJob> light_jobs;
-    std::vector<float> og_geom;
-    std::vector<uint32_t> og_words;
+    std::shared_ptr<CamGridSource> src = std::make_shared<CamGridSource>();   // og_geom, og_words (+ what a camera change needs)
     double og_budget = 0;
 };
 
@@ -678,8 +694,8 @@ void prep_create(const pt_scene_desc& d, pt_prep& P, pt_scene* early = nullptr, 
     std::vector<float4>&attr = P.attr, &pos = P.pos;
     attr.resize(n_prims * 4);
     pos.resize(n_prims * 3);
-    P.og_geom.resize(n_prims * 9);
-    P.og_words.resize(n_prims);
+    P.src->og_geom.resize(n_prims * 9);
+    P.src->og_words.resize(n_prims);
     P.model_mat.resize(d.n_models);
     bool translucent = false;
     uint64_t prim = 0;
@@ -705,11 +721,11 @@ void prep_create(const pt_scene_desc& d, pt_prep& P, pt_scene* early = nullptr, 
                 pos[prim * 3 + 0] = make_float4(a[0], a[1], a[2], pbits);
                 pos[prim * 3 + 1] = make_float4(e1[0], e1[1], e1[2], e2[0]);
                 pos[prim * 3 + 2] = make_float4(e2[1], e2[2], 0.f, 0.f);
-                float* og = &P.og_geom[prim * 9];
+                float* og = &P.src->og_geom[prim * 9];
                 og[0] = a[0]; og[1] = a[1]; og[2] = a[2];
                 og[3] = b[0]; og[4] = b[1]; og[5] = b[2];
                 og[6] = c[0]; og[7] = c[1]; og[8] = c[2];
-                P.og_words[prim] = pid;
+                P.src->og_words[prim] = pid;
             }
         } else {
             attr[prim * 4 + 0] = make_float4(mo.center[0], mo.center[1], mo.center[2], mo.radius);
@@ -721,12 +737,23 @@ void prep_create(const pt_scene_desc& d, pt_prep& P, pt_scene* early = nullptr, 
             pos[prim * 3 + 0] = make_float4(mo.center[0], mo.center[1], mo.center[2], pbits);
             pos[prim * 3 + 1] = make_float4(mo.radius, 0, 0, 0);
             pos[prim * 3 + 2] = make_float4(0, 0, 0, 0);
-            float* og = &P.og_geom[prim * 9];
+            float* og = &P.src->og_geom[prim * 9];
             og[0] = mo.center[0]; og[1] = mo.center[1]; og[2] = mo.center[2]; og[3] = mo.radius;
             og[4] = og[5] = og[6] = og[7] = og[8] = 0.f;
-            P.og_words[prim] = pid;
+            P.src->og_words[prim] = pid;
             ++prim;
         }
+    }
+    // ---- the triangles no model owns (pt_scene_set_camera: the extent of a camera grid includes them, as og_params_point's does)
+    {
+        std::vector<uint8_t> owned(d.n_triangles, 0);
+        for (uint32_t m = 0; m < d.n_models; ++m)
+            if (d.models[m].kind == PT_MODEL_MESH)
+                std::fill(owned.begin() + d.models[m].tri_first, owned.begin() + d.models[m].tri_first + d.models[m].tri_count, (uint8_t)1);
+        for (uint64_t t = 0; t < d.n_triangles; ++t)
+            if (!owned[t])
+                for (int k = 0; k < 3; ++k)
+                    for (int a = 0; a < 3; ++a) P.src->unowned.push_back(d.triangles[t * 24 + k * 8 + a]);
     }
     // ---- kdtree-ray's slab test (scene_slab, pt_integrator.h): the exact bounding box of the scene - the union of
     // Model::bound() (model.rs:76-86: the positions' bounds for a mesh, centre -+ radius for a sphere).  A cast whose origin
@@ -807,6 +834,9 @@ void prep_create(const pt_scene_desc& d, pt_prep& P, pt_scene* early = nullptr, 
             const char* e = getenv("PT_OG_HOST");
             return e && *e && atoi(e) != 0;
         }();
+        P.src->cam_res = grids_on && n_prims > 0 && estimate(res) <= budget ? res : 0u;
+        P.src->budget = budget;
+        P.src->device_grids = !host_grids;
         if (!host_grids) {   // the device builds them at upload time: only the parameters are derived here
             P.device_grids = true;
             P.og_budget = budget;
@@ -1218,15 +1248,15 @@ void grids_on_device(const pt_prep& P, pt_scene& s) {
     for (auto& g : B.lights) memset(&g, 0, sizeof g);
     memset(&B.cam, 0, sizeof B.cam);
     s.grid_headers.assign(1 + std::max(n_lights, (size_t)0), pth_origin_grid{});
-    const uint32_t n_prims = (uint32_t)P.og_words.size();
+    const uint32_t n_prims = (uint32_t)P.src->og_words.size();
     float* d_geom = nullptr;
     uint32_t* d_words = nullptr;
     double used = 0;
-    if ((P.cam_job.valid || n_lights) && n_prims > 0 && hipMalloc((void**)&d_geom, P.og_geom.size() * 4) == hipSuccess &&
-        hipMalloc((void**)&d_words, P.og_words.size() * 4) == hipSuccess) {
-        bool copied = hipMemcpy(d_geom, P.og_geom.data(), P.og_geom.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
-                      hipMemcpy(d_words, P.og_words.data(), P.og_words.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-        if (copied && device_grid_build(s, P.cam_job, d_geom, d_words, n_prims, P.og_words, used, P.og_budget, B.cam, s.grid_headers[0], B.bytes)) {
+    if ((P.cam_job.valid || n_lights) && n_prims > 0 && hipMalloc((void**)&d_geom, P.src->og_geom.size() * 4) == hipSuccess &&
+        hipMalloc((void**)&d_words, P.src->og_words.size() * 4) == hipSuccess) {
+        bool copied = hipMemcpy(d_geom, P.src->og_geom.data(), P.src->og_geom.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                      hipMemcpy(d_words, P.src->og_words.data(), P.src->og_words.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+        if (copied && device_grid_build(s, P.cam_job, d_geom, d_words, n_prims, P.src->og_words, used, P.og_budget, B.cam, s.grid_headers[0], B.bytes)) {
             B.cam_res = s.grid_headers[0].res;
             B.refs += s.grid_headers[0].n_refs;
         }
@@ -1236,7 +1266,7 @@ void grids_on_device(const pt_prep& P, pt_scene& s) {
         const uint64_t bytes_mark = B.bytes;
         uint64_t light_refs = 0;
         for (size_t i = 0; i < n_lights && all; ++i) {
-            if (!device_grid_build(s, P.light_jobs[i], d_geom, d_words, n_prims, P.og_words, used, P.og_budget, B.lights[i], s.grid_headers[1 + i], B.bytes))
+            if (!device_grid_build(s, P.light_jobs[i], d_geom, d_words, n_prims, P.src->og_words, used, P.og_budget, B.lights[i], s.grid_headers[1 + i], B.bytes))
                 all = false;
             else {
                 light_refs += s.grid_headers[1 + i].n_refs;
@@ -1265,6 +1295,21 @@ void grids_on_device(const pt_prep& P, pt_scene& s) {
     B.done = true;
 }
 
+// The delta_in of the escape masks of a scene (EscBuildParams): PT_SLACK_K x the largest distance a ray of the scene covers
+// before it hits anything - the box diagonal, or camera to far corner - plus the rounding of the largest coordinate.
+float escape_delta_in(const DevScene& D) {
+    double diag2 = 0, cam2 = 0, amax = 0;
+    for (int a = 0; a < 3; ++a) {
+        const double w = (double)D.bounds_max[a] - D.bounds_min[a], c = D.cam_c3[a];
+        const double far = std::max(std::fabs(c - D.bounds_min[a]), std::fabs(c - D.bounds_max[a]));
+        diag2 += w * w;
+        cam2 += far * far;
+        amax = std::max({amax, std::fabs((double)D.bounds_min[a]), std::fabs((double)D.bounds_max[a]), std::fabs(c)});
+    }
+    const double reach = std::sqrt(std::max(diag2, cam2));
+    return (float)((double)PT_SLACK_K * reach + 4.0 * 5.9604645e-8 * amax);
+}
+
 // Copy a prepared scene to `device`.
 // The escape masks of a scene (pt_escape.h), built on its device from the uploaded arrays: one wavefront per primitive.  Blocks
 // until they are there (every frame in flight has completed by then).  A device without the memory for them goes without.
@@ -1284,18 +1329,8 @@ void escape_masks_build(pt_scene& s) {
         uint32_t* d_stats = nullptr;
         HIP_CHECK(hipMalloc((void**)&d_stats, 16));
         HIP_CHECK(hipMemset(d_stats, 0, 16));
-        // the largest distance a ray of this scene covers before it hits anything: the box diagonal, or camera to far corner
-        double diag2 = 0, cam2 = 0, amax = 0;
-        for (int a = 0; a < 3; ++a) {
-            const double w = (double)D.bounds_max[a] - D.bounds_min[a], c = D.cam_c3[a];
-            const double far = std::max(std::fabs(c - D.bounds_min[a]), std::fabs(c - D.bounds_max[a]));
-            diag2 += w * w;
-            cam2 += far * far;
-            amax = std::max({amax, std::fabs((double)D.bounds_min[a]), std::fabs((double)D.bounds_max[a]), std::fabs(c)});
-        }
-        const double reach = std::sqrt(std::max(diag2, cam2));
         EscBuildParams E{};
-        E.delta_in = (float)((double)PT_SLACK_K * reach + 4.0 * 5.9604645e-8 * amax);
+        E.delta_in = escape_delta_in(D);
         E.slop_far = E.delta_in;
         E.alpha_stop = [] { const char* e = getenv("PT_ESCAPE_ALPHA"); return e && *e ? (float)atof(e) : 0.04f; }();
         E.r_near_scale = 2.0f;
@@ -1307,6 +1342,7 @@ void escape_masks_build(pt_scene& s) {
         HIP_CHECK(hipMemcpy(st, d_stats, 16, hipMemcpyDeviceToHost));
         (void)hipFree(d_stats);
         D.escape = (const float4*)buf;
+        s.escape_delta = E.delta_in;
         s.info.escape_prims = st[0];
         s.info.escape_clear_fraction = st[0] ? (float)((double)st[1] / (384.0 * st[0])) : 0.f;
     } catch (const GpuError&) {   // (no memory for them: the casts are simply made)
@@ -1342,6 +1378,7 @@ void scene_upload(const pt_prep& P, int device, pt_scene& s) {
     D.entry_lists = s.upload(P.entry_lists.data(), P.entry_lists.size());
     D.prim_entry = s.upload(P.prim_entry.data(), P.prim_entry.size());
     s.host_prim_entry = P.prim_entry;   // (test hook pt_trace_rays_wavefront)
+    s.cam_src = P.src;
     D.materials = s.upload(P.model_mat.data(), P.model_mat.size());
     D.textures = s.upload(P.textures.data(), P.textures.size());
     D.texels = s.upload(P.texels.data(), P.texels.size());
@@ -1393,6 +1430,9 @@ void scene_upload(const pt_prep& P, int device, pt_scene& s) {
         s.info.grid_build_seconds += B.seconds;
         s.host_light_grids = lgrids;
         D.light_grids = s.upload(lgrids.data(), lgrids.size());
+        const pth_origin_grid& ch = s.grid_headers[0];
+        s.cam_grid_bytes = ch.enabled ? (ch.n_cells + 2) * 4 + 8 * std::max<uint64_t>(1, ch.n_refs) : 0;   // (device_grid_build)
+        s.cam_grid_refs = ch.enabled ? ch.n_refs : 0;
         s.info.upload_seconds = std::chrono::duration<float>(std::chrono::steady_clock::now() - t_up).count();
         return;
     }
@@ -1410,6 +1450,8 @@ void scene_upload(const pt_prep& P, int device, pt_scene& s) {
         const uint64_t bytes_mark = s.info.device_bytes;
         try {
             upload_grid(P.cam_grid->g, D.cam_grid);
+            s.cam_grid_bytes = s.info.device_bytes - bytes_mark;
+            s.cam_grid_refs = P.cam_grid->g.enabled ? P.cam_grid->g.n_refs : 0;
         } catch (const GpuError&) {
             drop_allocations_from(mark, bytes_mark);
             memset(&D.cam_grid, 0, sizeof D.cam_grid);
@@ -1438,6 +1480,132 @@ void scene_upload(const pt_prep& P, int device, pt_scene& s) {
     }
     D.light_grids = s.upload(lgrids.data(), lgrids.size());
     s.info.upload_seconds = std::chrono::duration<float>(std::chrono::steady_clock::now() - t_up).count();
+}
+
+// pt_scene_set_camera (include/ptgpu.h has the contract, DESIGN.md "Camera updates" the state it touches row by row).  Everything
+// that can fail comes first - the new camera grid is built beside the old one - and the scene is changed only afterwards.
+void scene_set_camera(pt_scene& s, const pt_camera& cam) {
+    HIP_CHECK(hipSetDevice(s.device));
+    HIP_CHECK(hipDeviceSynchronize());   // the frames in flight finish with the old camera (and its grid)
+    DevScene D = s.dev;
+    const float* M = cam.transform;
+    memcpy(D.cam_c0, M, 12);   // (as prep_create)
+    memcpy(D.cam_c1, M + 4, 12);
+    memcpy(D.cam_c2, M + 8, 12);
+    memcpy(D.cam_c3, M + 12, 12);
+    D.tan_half_fov = tanf(cam.fov / 2.f);
+
+    // ---- the camera grid a fresh scene would have: prep_create's rule (resolution, fro < 64, fro * 1.001, budget), its
+    // parameters with the extent reduced on the device from the footprints, the device build of grids_on_device.  PT_OG_HOST=1
+    // (host-built grids): the moved camera goes without.  No memory for it: without, as a fresh scene on that device.
+    const CamGridSource& src = *s.cam_src;
+    DevGrid grid;
+    memset(&grid, 0, sizeof grid);
+    pth_origin_grid hdr{};
+    uint64_t grid_bytes = 0;
+    double fro = 0;
+    for (int k = 0; k < 3; ++k)
+        for (int r = 0; r < 3; ++r) fro += (double)M[4 * k + r] * M[4 * k + r];
+    fro = std::sqrt(fro);
+    const uint32_t n_prims = (uint32_t)src.og_words.size();
+    if (src.device_grids && src.cam_res && n_prims > 0 && fro > 0 && fro < 64.0) {
+        float* d_geom = nullptr;
+        uint32_t* d_words = nullptr;
+        unsigned long long* d_ext = nullptr;
+        struct Scratch {   // (freed on every way out)
+            float*& g;
+            uint32_t*& w;
+            unsigned long long*& e;
+            ~Scratch() {
+                for (void* q : {(void*)g, (void*)w, (void*)e})
+                    if (q) (void)hipFree(q);
+            }
+        } scratch{d_geom, d_words, d_ext};
+        bool built = false;
+        try {
+            if (hipMalloc((void**)&d_geom, src.og_geom.size() * 4) == hipSuccess && hipMalloc((void**)&d_words, src.og_words.size() * 4) == hipSuccess &&
+                hipMalloc((void**)&d_ext, 8) == hipSuccess) {
+                HIP_CHECK(hipMemcpy(d_geom, src.og_geom.data(), src.og_geom.size() * 4, hipMemcpyHostToDevice));
+                HIP_CHECK(hipMemcpy(d_words, src.og_words.data(), src.og_words.size() * 4, hipMemcpyHostToDevice));
+                HIP_CHECK(hipMemset(d_ext, 0, 8));
+                const uint32_t blocks = std::min<uint32_t>((n_prims + 255u) / 256u, 4096u);
+                hipLaunchKernelGGL(ogb::k_og_extent, dim3(blocks), dim3(256), 0, 0, (const float*)d_geom, (const uint32_t*)d_words, n_prims,
+                                   (double)M[12], (double)M[13], (double)M[14], d_ext);
+                HIP_CHECK(hipGetLastError());
+                unsigned long long bits = 0;
+                HIP_CHECK(hipMemcpy(&bits, d_ext, 8, hipMemcpyDeviceToHost));
+                double ext;
+                memcpy(&ext, &bits, 8);
+                for (size_t i = 0; i < src.unowned.size(); ++i) {   // (triangles no model owns: rare, on the host)
+                    const double v = std::fabs((double)src.unowned[i] - M[12 + i % 3]);
+                    if (std::isfinite(v)) ext = std::max(ext, v);
+                }
+                pt_prep::GridJob job;
+                job.valid = pth::og_params_point_ext(M + 12, src.cam_res, 0.f, (float)(fro * 1.001), ext, job.params, job.hdr);
+                double used = 0;
+                built = device_grid_build(s, job, d_geom, d_words, n_prims, src.og_words, used, src.budget, grid, hdr, grid_bytes);
+            } else {
+                (void)hipGetLastError();   // (out of memory: no grid)
+            }
+            // device_grid_build gives up on any failure; what is not a lack of memory is sticky and shows here
+            HIP_CHECK(hipDeviceSynchronize());
+        } catch (...) {
+            if (built) {
+                for (const void* q : {(const void*)grid.cell_off, (const void*)grid.refs}) {
+                    auto it = std::find(s.allocations.begin(), s.allocations.end(), q);
+                    if (it != s.allocations.end()) s.allocations.erase(it);
+                    (void)hipFree(const_cast<void*>(q));
+                }
+            }
+            throw;
+        }
+        if (!built) {
+            memset(&grid, 0, sizeof grid);
+            hdr = pth_origin_grid{};
+            grid_bytes = 0;
+        }
+    }
+
+    // ---- from here on nothing fails: the scene takes the new camera
+    auto release = [&s](const void* q) {
+        if (!q) return;
+        auto it = std::find(s.allocations.begin(), s.allocations.end(), q);
+        if (it != s.allocations.end()) s.allocations.erase(it);
+        (void)hipFree(const_cast<void*>(q));
+    };
+    release(s.dev.cam_grid.cell_off);
+    release(s.dev.cam_grid.refs);
+    D.cam_grid = grid;
+    s.built.cam = grid;
+    s.built.cam_res = hdr.enabled ? hdr.res : 0u;
+    if (!s.grid_headers.empty()) s.grid_headers[0] = hdr;
+    s.info.device_bytes = s.info.device_bytes - s.cam_grid_bytes + grid_bytes;
+    s.info.grid_refs = s.info.grid_refs - s.cam_grid_refs + (hdr.enabled ? hdr.n_refs : 0);
+    s.info.cam_grid_res = hdr.enabled ? hdr.res : 0u;
+    s.cam_grid_bytes = grid_bytes;
+    s.cam_grid_refs = hdr.enabled ? hdr.n_refs : 0;
+    // ---- escape masks: built with a delta_in at least the new camera's, they stay a proof; otherwise they go, and the
+    // PT_ESCAPE_AFTER schedule starts again (a scene whose attempt found no memory tries again too)
+    if (D.escape && escape_delta_in(D) > s.escape_delta) {
+        release(D.escape);
+        s.info.device_bytes -= (uint64_t)D.n_prims * 80u;
+        D.escape = nullptr;
+        s.escape_tried = false;
+        s.frames_rendered = 0;
+        s.info.escape_build_seconds = 0.f;
+        s.info.escape_prims = 0;
+        s.info.escape_clear_fraction = 0.f;
+    } else if (!D.escape && s.escape_tried) {
+        s.escape_tried = false;
+        s.frames_rendered = 0;
+    }
+    s.dev = D;
+    // ---- what earlier frames left: their counts (a plan sized from another camera's counts may overflow), the captured
+    // graphs (they hold the old DevScene as kernel arguments), the cull table of the last frame
+    s.frame_stats.clear();
+    for (auto& g : s.graphs) (void)hipGraphExecDestroy(g.second);
+    s.graphs.clear();
+    s.last_mask_blocks = 0;
 }
 
 hipEvent_t get_event(const pt_scene& s, size_t i) {
@@ -2622,6 +2790,13 @@ int pt_scene_create_from_prep(const pt_prep* prep, int device, pt_scene** out) {
 }
 
 void pt_scene_destroy(pt_scene* scene) { delete scene; }
+
+int pt_scene_set_camera(pt_scene* scene, const pt_camera* camera) {
+    return guarded([&] {
+        if (!scene || !camera) fail(PT_ERR_INVALID, "pt_scene_set_camera: null argument");
+        scene_set_camera(*scene, *camera);
+    });
+}
 
 uint64_t pt_local_pixel_count(const pt_profile* profile, const pt_opts* opts) {
     uint64_t n = 0;

@@ -66,6 +66,35 @@ __global__ __launch_bounds__(256) void k_og_raster(GridParams P, const float* __
     }, lane, 64u);
 }
 
+// The scene extent around a grid's origin (og_params_point: the absolute slack of the stored distances) from the uploaded
+// footprints, for pt_scene_set_camera: per axis the largest |vertex - origin| of a triangle and |centre - origin| + |radius|
+// of a sphere, in f64, non-finite terms skipped - the host's terms exactly (IEEE subtraction, absolute value, addition).
+// The values are >= 0, so their f64 bit patterns order as unsigned integers: one atomicMax per wavefront on the bits.  A
+// max is independent of the order of its terms, so the result is the host's value bit for bit.
+__global__ __launch_bounds__(256) void k_og_extent(const float* __restrict__ geom, const uint32_t* __restrict__ words, uint32_t n_prims,
+                                                   double ox, double oy, double oz, unsigned long long* __restrict__ out) {
+    double m = 0.0;
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n_prims; p += gridDim.x * blockDim.x) {
+        const float* g = geom + (size_t)p * 9;
+        const double o[3] = {ox, oy, oz};
+        if (words[p] & 0x80000000u) {   // sphere: (centre, radius)
+            const double r = fabs((double)g[3]);
+            for (int a = 0; a < 3; ++a) {
+                const double v = fabs((double)g[a] - o[a]) + r;
+                if (isfinite(v)) m = fmax(m, v);
+            }
+        } else {
+            for (int k = 0; k < 3; ++k)
+                for (int a = 0; a < 3; ++a) {
+                    const double v = fabs((double)g[k * 3 + a] - o[a]);
+                    if (isfinite(v)) m = fmax(m, v);
+                }
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off, 64));
+    if ((threadIdx.x & 63u) == 0u) atomicMax(out, (unsigned long long)__double_as_longlong(m));
+}
+
 #define OG_SCAN_BLOCK 1024u   // cells per block (256 threads x 4)
 
 // (summed in 64 bits and SATURATED: 1024 cells that every one of several million large primitives overlaps hold more than

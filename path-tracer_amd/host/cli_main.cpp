@@ -2,7 +2,7 @@
 // render path (src/main.rs:14-57, src/config/mod.rs:10-52, README.md:28-60):
 //
 //   path-tracer render <INPUT> [-o/--output <OUTPUT>] [-q/--quiet] [-v/--viewer]
-//                              [--debug-textures] [-p/--profile <PROFILE>]
+//                              [--debug-textures] [-p/--profile <PROFILE>] [--camera-path <CAMERAS>]
 //       env OUTPUT (default render.png), env PROFILE
 //   path-tracer convert <INPUT> <OUTPUT>      (glTF 2.0 -> ISF, host/gltf_convert.cpp)
 //
@@ -11,7 +11,9 @@
 // there is no CPU fallback.  Extras (not in the reference): --device N,
 // --devices A,B,... (one host thread per GPU, each rendering its share of interleaved 32x32 tiles: the
 // sharding of SURVEY 8-e inside one process; the KD-tree and the origin grids are built once and uploaded to every
-// device, the slices are exchanged by one RCCL all-gather), --stats (one JSON line with timings on stderr).
+// device, the slices are exchanged by one RCCL all-gather), --stats (one JSON line with timings on stderr),
+// --camera-path cams.json (a JSON array of ISF cameras: the scene is uploaded once and rendered from every camera in
+// turn through pt_scene_set_camera; frame i goes to OUTPUT with i substituted for its one %d / %0Nd field).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -47,6 +49,8 @@ void usage_render(FILE* f) {
           "      --device <N>         HIP device ordinal [default: 0]\n"
           "      --devices <A,B,..>   Render on several GPUs (interleaved tiles, one thread per device)\n"
           "      --stats              Print timing statistics as JSON on stderr\n"
+          "      --camera-path <CAMERAS>  Render one frame per camera of a JSON array of ISF cameras; the OUTPUT name\n"
+          "                           takes the frame index in its %d / %0Nd field (e.g. out/frame_%04d.png)\n"
           "  -h, --help               Print help\n",
           f);
 }
@@ -80,6 +84,31 @@ void on_preview(const uint8_t* rgb8, uint64_t n_pixels, uint32_t, uint32_t, void
     if (n_pixels == (uint64_t)v->width * v->height) pth_png_write_rgb8(v->path.c_str(), v->width, v->height, rgb8);
 }
 
+// The one %d / %0Nd field of an output name: (prefix, zero-pad width, suffix).  false: no field; a malformed or second
+// field is an error.
+bool frame_pattern(const std::string& out, std::string& pre, int& width, std::string& post) {
+    size_t at = std::string::npos;
+    for (size_t i = 0; i < out.size(); ++i) {
+        if (out[i] != '%') continue;
+        if (at != std::string::npos) die("error: the output name '" + out + "' has more than one % field (one %d or %0Nd expected)");
+        at = i;
+    }
+    if (at == std::string::npos) return false;
+    size_t j = at + 1;
+    width = 0;
+    if (j < out.size() && out[j] == '0') {
+        ++j;
+        size_t k = j;
+        while (j < out.size() && isdigit((unsigned char)out[j])) ++j;
+        if (j == k) die("error: the output name '" + out + "' has a malformed % field (%d or %0Nd expected)");
+        width = atoi(out.substr(k, j - k).c_str());
+    }
+    if (j >= out.size() || out[j] != 'd' || width > 32) die("error: the output name '" + out + "' has a malformed % field (%d or %0Nd expected)");
+    pre = out.substr(0, at);
+    post = out.substr(j + 1);
+    return true;
+}
+
 void on_progress(uint32_t done, uint32_t total, void* user) {
     Progress* p = (Progress*)user;
     if (p->quiet) return;
@@ -92,7 +121,9 @@ void on_progress(uint32_t done, uint32_t total, void* user) {
 
 int run_render(int argc, char** argv) {
     std::string input, output, profile_path;
+    std::string camera_path;
     bool have_output = false, have_profile = false, quiet = false, debug_textures = false, stats = false, viewer = false;
+    bool have_camera_path = false;
     int device = 0;
     std::vector<int> devices;
     for (int i = 0; i < argc; ++i) {
@@ -123,6 +154,10 @@ int run_render(int argc, char** argv) {
         else if (a == "-qv" || a == "-vq") quiet = viewer = true;
         else if (a == "--debug-textures") debug_textures = true;
         else if (a == "--stats") stats = true;
+        else if (a == "--camera-path" || a.rfind("--camera-path=", 0) == 0) {
+            camera_path = value("--camera-path <CAMERAS>");
+            have_camera_path = true;
+        }
         else if (a == "--devices" || a.rfind("--devices=", 0) == 0) {
             std::string list = value("--devices <A,B,..>");
             devices.clear();
@@ -156,9 +191,38 @@ int run_render(int argc, char** argv) {
     pt_profile profile;
     if (pth_profile_load(have_profile ? profile_path.c_str() : nullptr, &profile) != PT_OK) die(pth_last_error());
 
+    // --camera-path: everything it can get wrong is found before any GPU work
+    std::vector<pt_camera> cameras;
+    std::string out_pre, out_post;
+    int out_width = 0;
+    bool out_field = false;
+    if (have_camera_path) {
+        if (debug_textures) die("error: the argument '--debug-textures' cannot be used with '--camera-path <CAMERAS>'");
+        pt_camera* cams = nullptr;
+        uint32_t n_cams = 0;
+        if (pth_camera_path_load(camera_path.c_str(), &cams, &n_cams) != PT_OK) die(pth_last_error());
+        cameras.assign(cams, cams + n_cams);
+        pth_camera_path_free(cams);
+        out_field = frame_pattern(output, out_pre, out_width, out_post);
+        if (cameras.size() > 1 && !out_field)
+            die("error: --camera-path has " + std::to_string(cameras.size()) + " cameras but the output name '" + output +
+                "' has no %d / %0Nd field for the frame index");
+        size_t dot = output.find_last_of('.');
+        std::string ext = dot == std::string::npos ? "" : output.substr(dot + 1);
+        for (char& c : ext) c = (char)tolower(c);
+        if (ext != "png") die("The image format could not be determined (only .png output is supported): " + output);
+    }
+    auto frame_name = [&](size_t f) {
+        if (!out_field) return output;
+        char num[48];
+        snprintf(num, sizeof num, "%0*zu", out_width, f);
+        return out_pre + num + out_post;
+    };
+
     auto t0 = std::chrono::steady_clock::now();
     pth_scene* hscene = nullptr;  // load_internal (main.rs:38)
     if (pth_scene_load_isf(input.c_str(), &hscene) != PT_OK) die(pth_last_error());
+    if (!cameras.empty() && pth_scene_set_camera(hscene, &cameras[0]) != PT_OK) die(pth_last_error());   // (frame 0: no grid rebuild)
     auto t1 = std::chrono::steady_clock::now();
 
     if (devices.size() == 1 || (debug_textures && !devices.empty())) {
@@ -215,10 +279,11 @@ int run_render(int argc, char** argv) {
             opts[k].tile_w = opts[k].tile_h = 32;
             slice_pixels = std::max<uint64_t>(slice_pixels, pt_local_pixel_count(&profile, &opts[k]));
         }
-        std::vector<std::vector<uint8_t>> part(n);
+        const size_t n_frames = cameras.empty() ? 1 : cameras.size();   // (--camera-path: every scene takes every camera)
+        std::vector<std::vector<std::vector<uint8_t>>> part(n, std::vector<std::vector<uint8_t>>(n_frames));
         std::vector<std::vector<uint32_t>> map(n);
         std::vector<std::string> error(n);
-        std::vector<uint8_t> rgb((size_t)profile.width * profile.height * 3);
+        std::vector<std::vector<uint8_t>> frames(n_frames, std::vector<uint8_t>((size_t)profile.width * profile.height * 3));
         std::mutex bar_mutex;
         std::condition_variable bar_cv;
         uint32_t arrived = 0, failed = 0;
@@ -235,19 +300,21 @@ int run_render(int argc, char** argv) {
                 if (++arrived == n) bar_cv.notify_all();
                 else bar_cv.wait(lock, [&] { return arrived == n; });
             }
-            if (up && failed == 0) {
+            for (size_t f = 0; f < n_frames && up && failed == 0 && error[k].empty(); ++f) {
                 if (distinct) {
-                    if (!check(pt_render_gathered(sc, comms[k], &profile, &opts[k], slice_pixels, k == 0 ? rgb.data() : nullptr))) {
+                    if ((f > 0 && !check(pt_scene_set_camera(sc, &cameras[f]))) ||
+                        !check(pt_render_gathered(sc, comms[k], &profile, &opts[k], slice_pixels, k == 0 ? frames[f].data() : nullptr))) {
                         fprintf(stderr, "Error: %s\n", error[k].c_str());   // (the peers may be inside the all-gather: do not join them)
                         fflush(stderr);
                         _exit(2);
                     }
                 } else {
+                    if (f > 0 && !check(pt_scene_set_camera(sc, &cameras[f]))) break;
                     uint64_t count = pt_local_pixel_count(&profile, &opts[k]);
                     map[k].resize(count);
-                    part[k].resize(count * 3);
+                    part[k][f].resize(count * 3);
                     if (check(pt_local_pixel_map(&profile, &opts[k], map[k].data())))
-                        check(pt_render(sc, &profile, &opts[k], part[k].data(), nullptr));
+                        check(pt_render(sc, &profile, &opts[k], part[k][f].data(), nullptr));
                 }
             }
             if (sc) pt_scene_destroy(sc);
@@ -260,8 +327,9 @@ int run_render(int argc, char** argv) {
         for (uint32_t k = 0; k < n; ++k)
             if (!error[k].empty()) die(error[k]);
         if (!distinct)
-            for (uint32_t k = 0; k < n; ++k)
-                for (size_t i = 0; i < map[k].size(); ++i) memcpy(&rgb[(size_t)map[k][i] * 3], &part[k][i * 3], 3);
+            for (size_t f = 0; f < n_frames; ++f)
+                for (uint32_t k = 0; k < n; ++k)
+                    for (size_t i = 0; i < map[k].size(); ++i) memcpy(&frames[f][(size_t)map[k][i] * 3], &part[k][f][i * 3], 3);
         auto t3 = std::chrono::steady_clock::now();
         if (!quiet)
             fprintf(stderr, "Done: %llds\n", (long long)std::chrono::duration_cast<std::chrono::seconds>(t3 - t2).count());
@@ -269,7 +337,8 @@ int run_render(int argc, char** argv) {
         std::string ext = dot == std::string::npos ? "" : output.substr(dot + 1);
         for (char& c : ext) c = (char)tolower(c);
         if (ext != "png") die("The image format could not be determined (only .png output is supported): " + output);
-        if (pth_png_write_rgb8(output.c_str(), profile.width, profile.height, rgb.data()) != PT_OK) die(pth_last_error());
+        for (size_t f = 0; f < n_frames; ++f)
+            if (pth_png_write_rgb8(frame_name(f).c_str(), profile.width, profile.height, frames[f].data()) != PT_OK) die(pth_last_error());
         if (stats) {
             double sec = std::chrono::duration<double>(t3 - t2).count();
             fprintf(stderr, "{\"devices\": %u, \"gather\": \"%s\", \"render_s\": %.3f, \"msamples_per_s\": %.2f}\n", n,
@@ -300,18 +369,24 @@ int run_render(int argc, char** argv) {
         }
     }
     std::vector<uint8_t> rgb((size_t)profile.width * profile.height * 3);
-    if (pt_render(scene, &profile, &opts, rgb.data(), nullptr) != PT_OK) die(pt_last_error());
-    auto t3 = std::chrono::steady_clock::now();
-    if (!quiet)
-        fprintf(stderr, "\nDone: %llds\n", (long long)std::chrono::duration_cast<std::chrono::seconds>(t3 - t2).count());
+    const size_t n_frames = cameras.empty() ? 1 : cameras.size();   // (--camera-path: one frame per camera, the scene kept)
+    auto t3 = t2, t4 = t2;
+    for (size_t f = 0; f < n_frames; ++f) {
+        if (f > 0 && pt_scene_set_camera(scene, &cameras[f]) != PT_OK) die(pt_last_error());
+        pv.path = frame_name(f);
+        if (pt_render(scene, &profile, &opts, rgb.data(), nullptr) != PT_OK) die(pt_last_error());
+        t3 = std::chrono::steady_clock::now();
+        if (!quiet)
+            fprintf(stderr, "\nDone: %llds\n", (long long)std::chrono::duration_cast<std::chrono::seconds>(t3 - t2).count());
 
-    // rendered_image.save(output) (main.rs:50); the format follows the extension, PNG only here
-    size_t dot = output.find_last_of('.');
-    std::string ext = dot == std::string::npos ? "" : output.substr(dot + 1);
-    for (char& c : ext) c = (char)tolower(c);
-    if (ext != "png") die("The image format could not be determined (only .png output is supported): " + output);
-    if (pth_png_write_rgb8(output.c_str(), profile.width, profile.height, rgb.data()) != PT_OK) die(pth_last_error());
-    auto t4 = std::chrono::steady_clock::now();
+        // rendered_image.save(output) (main.rs:50); the format follows the extension, PNG only here
+        size_t dot = output.find_last_of('.');
+        std::string ext = dot == std::string::npos ? "" : output.substr(dot + 1);
+        for (char& c : ext) c = (char)tolower(c);
+        if (ext != "png") die("The image format could not be determined (only .png output is supported): " + output);
+        if (pth_png_write_rgb8(frame_name(f).c_str(), profile.width, profile.height, rgb.data()) != PT_OK) die(pth_last_error());
+        t4 = std::chrono::steady_clock::now();
+    }
 
     if (stats) {
         pt_timing tm{};
@@ -319,7 +394,7 @@ int run_render(int argc, char** argv) {
         pt_get_timing(scene, &tm);
         pt_scene_get_info(scene, &info);
         auto sec = [](auto a, auto b) { return std::chrono::duration<double>(b - a).count(); };
-        double samples = (double)profile.width * profile.height * profile.samples;
+        double samples = (double)profile.width * profile.height * profile.samples * n_frames;
         fprintf(stderr,
                 // load = ISF + textures; build = pt_scene_create (KD-tree and origin grids side by side on the host, upload);
                 // render = pt_render (kernels + the copy back); png = the output file

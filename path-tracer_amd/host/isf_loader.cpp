@@ -542,6 +542,26 @@ void parse_camera(JsonReader& r, pt_camera& c) {
 
 }  // namespace
 
+// A camera path: a JSON array of ISF camera objects (parse_camera: the same fields, the same messages), at least one.
+static void load_camera_path(const char* path, std::vector<pt_camera>& out) {
+    std::ifstream f(path, std::ios::binary);
+    if (!f) fail(PT_ERR_IO, "%s: %s", path, strerror(errno));
+    std::string text((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    JsonReader r(text.data(), text.data() + text.size());
+    if (r.peek() != '[') r.error("expected an array of cameras");
+    r.expect('[');
+    if (!r.consume(']')) {
+        do {
+            pt_camera c{};
+            parse_camera(r, c);
+            out.push_back(c);
+        } while (r.consume(','));
+        r.expect(']');
+    }
+    r.end_of_input();
+    if (out.empty()) fail(PT_ERR_PARSE, "%s: the camera path holds no camera", path);
+}
+
 static void load_isf(const char* path, pth_scene& s) {
     std::ifstream f(path, std::ios::binary);
     if (!f) fail(PT_ERR_IO, "%s: %s", path, strerror(errno));
@@ -602,6 +622,29 @@ int pth_scene_load_isf(const char* path, pth_scene** out) {
 }
 
 void pth_scene_free(pth_scene* s) { delete s; }
+
+int pth_scene_set_camera(pth_scene* s, const pt_camera* camera) {
+    return pth::guarded([&] {
+        if (!s || !camera) pth::fail(PT_ERR_INVALID, "pth_scene_set_camera: null argument");
+        s->desc.camera = *camera;
+    });
+}
+
+int pth_camera_path_load(const char* path, pt_camera** out, uint32_t* n) {
+    return pth::guarded([&] {
+        if (!path || !out || !n) pth::fail(PT_ERR_INVALID, "pth_camera_path_load: null argument");
+        std::vector<pt_camera> cams;
+        pth::load_camera_path(path, cams);
+        if (cams.size() > 0xffffffffu) pth::fail(PT_ERR_INVALID, "%s: too many cameras", path);
+        pt_camera* buf = (pt_camera*)malloc(cams.size() * sizeof(pt_camera));
+        if (!buf) throw std::bad_alloc();
+        memcpy(buf, cams.data(), cams.size() * sizeof(pt_camera));
+        *out = buf;
+        *n = (uint32_t)cams.size();
+    });
+}
+
+void pth_camera_path_free(pt_camera* cameras) { free(cameras); }
 
 const pt_scene_desc* pth_scene_desc(const pth_scene* s) { return s ? &s->desc : nullptr; }
 

@@ -396,4 +396,9 @@ OG_HD inline void rasterize(const GridParams& P, const Footprint& fp, Emit&& emi
 bool og_params_point(const pt_scene_desc& d, const float origin[3], uint32_t res, float ray_offset, float max_dir_len,
                      og::GridParams& P, ::pth_origin_grid& g);
 bool og_params_ortho(const pt_scene_desc& d, const float direction[3], uint32_t res, og::GridParams& P, ::pth_origin_grid& g);
+// The same as og_params_point for a scene extent `ext` computed elsewhere (og_point_extent, or the device's reduction over the
+// footprints: pt_scene_set_camera); res must be given (> 0).
+bool og_params_point_ext(const float origin[3], uint32_t res, float ray_offset, float max_dir_len, double ext, og::GridParams& P,
+                         ::pth_origin_grid& g);
+double og_point_extent(const pt_scene_desc& d, const float origin[3]);
 }  // namespace pth

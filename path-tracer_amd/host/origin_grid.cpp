@@ -261,19 +261,10 @@ void fill_lists(const pt_scene_desc& d, const GridParams& P, pth_origin_grid& g,
     g.build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
-bool params_point(const pt_scene_desc& d, const float origin[3], uint32_t res, float ray_offset, float max_dir_len,
-                  GridParams& P, pth_origin_grid& g) {
-    memset(&g, 0, sizeof g);
-    memcpy(g.origin, origin, 12);
-    const uint64_t n_prims = pth_prim_count(&d);
-    if (res == 0) res = auto_resolution(n_prims);
-    if (res > 8192) fail(PT_ERR_INVALID, "origin grid: resolution %u too large", res);
-    g.res = res;
-    g.n_cells = 6ull * res * res;
-    g.ray_offset = ray_offset;
-    if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2])) return false;  // enabled = 0
-
-    // scene extent (for the absolute slack of the stored distances)
+// The scene extent around `origin` (the absolute slack of the stored distances): the largest |coordinate - origin| of any
+// vertex, and |centre - origin| + |radius| of any sphere, per axis, non-finite terms skipped.  A max: the device's
+// reduction over the footprints (pt_scene_set_camera) finds the same value whatever its order.
+double point_extent(const pt_scene_desc& d, const float origin[3]) {
     double ext = 0;
     for (uint64_t t = 0; t < d.n_triangles; ++t)
         for (int k = 0; k < 3; ++k)
@@ -287,6 +278,18 @@ bool params_point(const pt_scene_desc& d, const float origin[3], uint32_t res, f
                 double v = std::fabs((double)d.models[m].center[a] - origin[a]) + std::fabs((double)d.models[m].radius);
                 if (std::isfinite(v)) ext = std::max(ext, v);
             }
+    return ext;
+}
+
+bool params_point_ext(const float origin[3], uint32_t res, float ray_offset, float max_dir_len, double ext, GridParams& P,
+                      pth_origin_grid& g) {
+    memset(&g, 0, sizeof g);
+    memcpy(g.origin, origin, 12);
+    if (res > 8192) fail(PT_ERR_INVALID, "origin grid: resolution %u too large", res);
+    g.res = res;
+    g.n_cells = 6ull * res * res;
+    g.ray_offset = ray_offset;
+    if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2])) return false;  // enabled = 0
     P = GridParams();
     P.origin = Vec{origin[0], origin[1], origin[2]};
     P.res = res;
@@ -301,6 +304,14 @@ bool params_point(const pt_scene_desc& d, const float origin[3], uint32_t res, f
     P.near_radius = std::max(1e-5 * ext, P.ray_offset > 0 ? 3.0 * P.ray_offset / (0.125 * 2.0 / res) : 0.0);
 
     return true;
+}
+
+bool params_point(const pt_scene_desc& d, const float origin[3], uint32_t res, float ray_offset, float max_dir_len,
+                  GridParams& P, pth_origin_grid& g) {
+    if (res == 0) res = auto_resolution(pth_prim_count(&d));
+    if (res > 8192) fail(PT_ERR_INVALID, "origin grid: resolution %u too large", res);
+    const bool finite = std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2]);
+    return params_point_ext(origin, res, ray_offset, max_dir_len, finite ? point_extent(d, origin) : 0.0, P, g);
 }
 
 void build(const pt_scene_desc& d, const float origin[3], uint32_t res, float ray_offset, float max_dir_len,
@@ -395,6 +406,11 @@ bool og_params_point(const pt_scene_desc& d, const float origin[3], uint32_t res
                      og::GridParams& P, pth_origin_grid& g) {
     return params_point(d, origin, res, ray_offset, max_dir_len, P, g);
 }
+bool og_params_point_ext(const float origin[3], uint32_t res, float ray_offset, float max_dir_len, double ext, og::GridParams& P,
+                         pth_origin_grid& g) {
+    return params_point_ext(origin, res, ray_offset, max_dir_len, ext, P, g);
+}
+double og_point_extent(const pt_scene_desc& d, const float origin[3]) { return point_extent(d, origin); }
 bool og_params_ortho(const pt_scene_desc& d, const float direction[3], uint32_t res, og::GridParams& P, pth_origin_grid& g) {
     return params_ortho(d, direction, res, P, g);
 }

@@ -209,6 +209,24 @@ void pt_scene_destroy(pt_scene* scene);
  * fresh scene (PT_ESCAPE_AFTER). */
 int pt_scene_set_camera(pt_scene* scene, const pt_camera* camera);
 
+/* Replace ALL lights of a scene (n_lights may differ from the count it was made with; 0 is allowed, lights may be NULL only
+ * then), or its material table (n_materials must equal the n_materials of the description the scene was made from; the
+ * model -> material assignment and the textures are kept; a texture index must be -1 or name one of the scene's textures
+ * with the channel count pt_scene_create demands).  Afterwards every entry point behaves exactly as on a scene that
+ * pt_scene_create made from the edited description, with the same contract as pt_scene_set_camera: the device is
+ * synchronised first (a frame already queued by pt_render_device completes with the old lights / materials), works on
+ * scenes of pt_scene_create_from_prep also after pt_prep_destroy (scenes of one prep are edited independently), and no
+ * frame plan or captured graph carries over.  A null pointer with a count > 0, a wrong material count, a light kind other
+ * than PT_LIGHT_*, a texture index out of range or with the wrong channel count are PT_ERR_INVALID; any other device
+ * failure is PT_ERR_DEVICE; in both cases the scene keeps rendering its old state bit for bit.
+ * set_lights rebuilds the light origin grids on the device (all or none, as pt_scene_create: a light whose grid is not to
+ * be had sends every shadow ray through the KD-tree) and the camera grid only if the new light count changes its
+ * resolution (PT_OG_BUDGET_GIB).  With PT_OG_HOST=1 (grids built on the host) the edited scene goes without light grids.
+ * set_materials replaces the per-model materials the device reads and re-evaluates has_translucent (the ALPHA variants).
+ * The escape masks are kept by both: they depend on the geometry and the camera only. */
+int pt_scene_set_lights(pt_scene* scene, const pt_light* lights, uint32_t n_lights);
+int pt_scene_set_materials(pt_scene* scene, const pt_material* materials, uint32_t n_materials);
+
 /* The host half of pt_scene_create (validation, KD build, origin grids) as an object of its own: build it ONCE
  * and upload it to every device of a multi-GPU render instead of repeating seconds of CPU work per device. */
 typedef struct pt_prep pt_prep;

@@ -38,6 +38,53 @@ int pth_scene_set_camera(pth_scene* s, const pt_camera* camera);
 int pth_camera_path_load(const char* path, pt_camera** out, uint32_t* n);
 void pth_camera_path_free(pt_camera* cameras);
 
+/* Replace all lights (n_lights may be 0; lights may be NULL only then) or the material table (n_materials must equal the
+ * scene's; texture indices -1 or an existing texture with the channel count pt_scene_create demands) of a host scene, with
+ * the checks and messages of pt_scene_set_lights / pt_scene_set_materials (PT_ERR_INVALID; the scene is unchanged then).
+ * In a scene loaded from ISF, material i is model i's.  pth_scene_save_isf writes the edited state. */
+int pth_scene_set_lights(pth_scene* s, const pt_light* lights, uint32_t n_lights);
+int pth_scene_set_materials(pth_scene* s, const pt_material* materials, uint32_t n_materials);
+
+/* Keyframes (`path-tracer render --keyframes`): a JSON array of frame objects, at least one.  A frame holds any of
+ *   "camera"     an ISF camera (the fields and messages of a scene's "camera"),
+ *   "lights"     an array of ISF lights: ALL lights of the frame (the fields and messages of a scene's "lights"),
+ *   "materials"  an object from a material index (a decimal string: the order of pt_scene_desc.materials) to a partial
+ *                ISF material: channels "albedo", "emissive", "opacity", "metalness", "roughness" with "factor" only, and
+ *                "ior".  Fields left out keep their value; a texture keeps multiplying its new factor.
+ * and applies on top of the frame before it ({} renders the current state again).  Anything else - an unknown key, a
+ * "texture", a file that is not an array or an empty one - is PT_ERR_PARSE with a line and column.  *out is one malloc'd
+ * block (the lights and edits of every frame inside it): free with pth_keyframes_free. */
+enum {
+    PTH_MAT_ALBEDO = 1,
+    PTH_MAT_EMISSIVE = 2,
+    PTH_MAT_OPACITY = 4,
+    PTH_MAT_METALNESS = 8,
+    PTH_MAT_ROUGHNESS = 16,
+    PTH_MAT_IOR = 32
+};
+typedef struct pth_material_edit {
+    uint32_t index;     /* into pt_scene_desc.materials */
+    uint32_t fields;    /* PTH_MAT_*: the values given */
+    float albedo[3];
+    float emissive[3];
+    float opacity, metalness, roughness, ior;
+} pth_material_edit;
+typedef struct pth_keyframe {
+    uint32_t has_camera;
+    pt_camera camera;
+    uint32_t has_lights;        /* 1: lights[0 .. n_lights) replace every light (n_lights may be 0) */
+    uint32_t n_lights;
+    const pt_light* lights;
+    uint32_t n_materials;       /* material edits, applied in order */
+    uint32_t _pad;
+    const pth_material_edit* materials;
+} pth_keyframe;
+int pth_keyframes_load(const char* path, pth_keyframe** out, uint32_t* n);
+void pth_keyframes_free(pth_keyframe* frames);
+/* Apply one frame to a host scene: camera, lights, materials, in that order.  A material index out of range is
+ * PT_ERR_INVALID and changes nothing. */
+int pth_keyframe_apply(pth_scene* s, const pth_keyframe* frame);
+
 /* Deterministic synthetic stand-in for the (unpublished) PS5 scene
  * (SURVEY §8-d): ground quad + two tessellated curved shells + an emissive
  * strip + one point light, black background, fov 0.6911112.

@@ -16,6 +16,7 @@ PKG_DIR = Path(__file__).resolve().parent
 ROOT = PKG_DIR.parent
 
 PT_OK = 0
+PT_ERR_INVALID, PT_ERR_IO, PT_ERR_PARSE, PT_ERR_DEVICE, PT_ERR_NUMERIC, PT_ERR_UNSUPPORTED = -1, -2, -3, -4, -5, -6
 PT_MODEL_MESH, PT_MODEL_SPHERE = 0, 1
 PT_LIGHT_POINT, PT_LIGHT_DIRECTIONAL = 0, 1
 PT_TONEMAP_REINHARD, PT_TONEMAP_FILMIC, PT_TONEMAP_ACES = 0, 1, 2
@@ -47,6 +48,22 @@ class Light(C.Structure):
 
 class Camera(C.Structure):
     _fields_ = [("transform", C.c_float * 16), ("fov", C.c_float), ("zfar", C.c_float), ("znear", C.c_float)]
+
+
+class MaterialEdit(C.Structure):
+    """pth_material_edit: one material's factors in a keyframe (fields: the PTH_MAT_* bits of what is given)."""
+    _fields_ = [("index", C.c_uint32), ("fields", C.c_uint32), ("albedo", C.c_float * 3), ("emissive", C.c_float * 3),
+                ("opacity", C.c_float), ("metalness", C.c_float), ("roughness", C.c_float), ("ior", C.c_float)]
+
+
+class Keyframe(C.Structure):
+    """pth_keyframe: one frame of a keyframe file (pth_keyframes_load)."""
+    _fields_ = [("has_camera", C.c_uint32), ("camera", Camera), ("has_lights", C.c_uint32), ("n_lights", C.c_uint32),
+                ("lights", C.POINTER(Light)), ("n_materials", C.c_uint32), ("_pad", C.c_uint32),
+                ("materials", C.POINTER(MaterialEdit))]
+
+
+PTH_MAT_ALBEDO, PTH_MAT_EMISSIVE, PTH_MAT_OPACITY, PTH_MAT_METALNESS, PTH_MAT_ROUGHNESS, PTH_MAT_IOR = 1, 2, 4, 8, 16, 32
 
 
 class SceneDesc(C.Structure):
@@ -172,9 +189,10 @@ HOST_SYMBOLS = ["pth_scene_load_isf", "pth_scene_free", "pth_scene_desc", "pth_s
                 "pth_scene_save_isf", "pth_convert_gltf", "pth_profile_load", "pth_profile_parse", "pth_png_read",
                 "pth_png_decode", "pth_png_write_rgb8", "pth_free", "pth_prim_count", "pth_kd_build",
                 "pth_kd_free", "pth_origin_grid_build", "pth_ortho_grid_build", "pth_origin_grid_auto_resolution", "pth_origin_grid_free",
-                "pth_last_error", "pth_scene_set_camera", "pth_camera_path_load", "pth_camera_path_free"]
+                "pth_last_error", "pth_scene_set_camera", "pth_camera_path_load", "pth_camera_path_free",
+                "pth_scene_set_lights", "pth_scene_set_materials", "pth_keyframes_load", "pth_keyframes_free", "pth_keyframe_apply"]
 # Every symbol include/ptgpu.h declares.
-GPU_SYMBOLS = ["pt_scene_create", "pt_scene_destroy", "pt_scene_set_camera", "pt_prep_create", "pt_prep_destroy", "pt_scene_create_from_prep",
+GPU_SYMBOLS = ["pt_scene_create", "pt_scene_destroy", "pt_scene_set_camera", "pt_scene_set_lights", "pt_scene_set_materials", "pt_prep_create", "pt_prep_destroy", "pt_scene_create_from_prep",
                "pt_comm_unique_id", "pt_comm_create", "pt_comm_create_all", "pt_comm_destroy", "pt_gather_tiles", "pt_render_gathered", "pt_local_pixel_count", "pt_local_pixel_map",
                "pt_render", "pt_render_device", "pt_debug_render", "pt_assemble_tiles", "pt_get_timing", "pt_get_counters",
                "pt_scene_get_info", "pt_scene_set_cu_mask", "pt_stream_create_cu_mask", "pt_stream_destroy", "pt_get_cull_stats", "pt_scene_escape_copy", "pt_scene_grid_header", "pt_scene_grid_copy", "pt_trace_rays", "pt_trace_rays_wavefront",
@@ -223,6 +241,12 @@ def host_lib():
         L.pth_camera_path_load.argtypes = [C.c_char_p, C.POINTER(C.POINTER(Camera)), C.POINTER(C.c_uint32)]
         L.pth_camera_path_free.argtypes = [C.POINTER(Camera)]
         L.pth_camera_path_free.restype = None
+        L.pth_scene_set_lights.argtypes = [C.c_void_p, C.POINTER(Light), C.c_uint32]
+        L.pth_scene_set_materials.argtypes = [C.c_void_p, C.POINTER(Material), C.c_uint32]
+        L.pth_keyframes_load.argtypes = [C.c_char_p, C.POINTER(C.POINTER(Keyframe)), C.POINTER(C.c_uint32)]
+        L.pth_keyframes_free.argtypes = [C.POINTER(Keyframe)]
+        L.pth_keyframes_free.restype = None
+        L.pth_keyframe_apply.argtypes = [C.c_void_p, C.POINTER(Keyframe)]
         _host = L
     return _host
 
@@ -245,6 +269,8 @@ def gpu_lib():
         L.pt_prep_destroy.restype = None
         L.pt_scene_create_from_prep.argtypes = [vp, C.c_int, C.POINTER(vp)]
         L.pt_scene_set_camera.argtypes = [vp, C.POINTER(Camera)]
+        L.pt_scene_set_lights.argtypes = [vp, C.POINTER(Light), C.c_uint32]
+        L.pt_scene_set_materials.argtypes = [vp, C.POINTER(Material), C.c_uint32]
         L.pt_comm_unique_id.argtypes = [vp]
         L.pt_comm_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
         L.pt_comm_create_all.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
@@ -328,6 +354,71 @@ def load_camera_path(path):
         host_lib().pth_camera_path_free(ptr)
 
 
+def _table(cls, items, n):
+    """(array, count) for a C table of `cls` from a list of structures (copied); items None: a null pointer with count n or 0."""
+    if items is None:
+        return None, (0 if n is None else n)
+    items = list(items)
+    arr = (cls * max(1, len(items)))()
+    for i, it in enumerate(items):
+        C.memmove(C.byref(arr, i * C.sizeof(cls)), C.byref(it), C.sizeof(cls))
+    return arr, (len(items) if n is None else n)
+
+
+class Keyframes:
+    """A keyframe file (pth_keyframes_load, `render --keyframes`): a list of Keyframe structures, valid while this object
+    lives.  Apply frame i with HostScene.apply_keyframe / GpuScene.apply_keyframe."""
+
+    def __init__(self, path):
+        self._ptr = C.POINTER(Keyframe)()
+        n = C.c_uint32(0)
+        check_host(host_lib().pth_keyframes_load(os.fsencode(str(path)), C.byref(self._ptr), C.byref(n)))
+        self._n = n.value
+
+    def __len__(self):
+        return self._n
+
+    def __getitem__(self, i):
+        if not 0 <= i < self._n:
+            raise IndexError(i)
+        return self._ptr[i]
+
+    def __iter__(self):
+        return (self[i] for i in range(self._n))
+
+    @staticmethod
+    def lights(frame):
+        """The lights a frame sets (copies), or None if it keeps them."""
+        return [_copy(Light, frame.lights[i]) for i in range(frame.n_lights)] if frame.has_lights else None
+
+    @staticmethod
+    def material_edits(frame):
+        return [_copy(MaterialEdit, frame.materials[i]) for i in range(frame.n_materials)]
+
+    def close(self):
+        if self._ptr:
+            host_lib().pth_keyframes_free(self._ptr)
+            self._ptr = C.POINTER(Keyframe)()
+            self._n = 0
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _copy(cls, s):
+    c = cls()
+    C.memmove(C.byref(c), C.byref(s), C.sizeof(cls))
+    return c
+
+
+def load_keyframes(path):
+    """`--keyframes` file (pth_keyframes_load) -> Keyframes."""
+    return Keyframes(path)
+
+
 class HostScene:
     """Owned pth_scene handle (ISF file or generated)."""
 
@@ -363,6 +454,32 @@ class HostScene:
         """pth_scene_set_camera: camera is a Camera or a dict in ISF form."""
         c = make_camera(camera)
         check_host(host_lib().pth_scene_set_camera(self.handle, C.byref(c) if c is not None else None))
+
+    @property
+    def lights(self):
+        """Copies of the scene's lights."""
+        d = self.desc.contents
+        return [_copy(Light, d.lights[i]) for i in range(d.n_lights)]
+
+    @property
+    def materials(self):
+        """Copies of the scene's materials (pt_scene_desc.materials: in an ISF scene material i is model i's)."""
+        d = self.desc.contents
+        return [_copy(Material, d.materials[i]) for i in range(d.n_materials)]
+
+    def set_lights(self, lights, n=None):
+        """pth_scene_set_lights: lights is a list of Light (all of them); None passes a null pointer (with count n)."""
+        arr, cnt = _table(Light, lights, n)
+        check_host(host_lib().pth_scene_set_lights(self.handle, arr, cnt))
+
+    def set_materials(self, materials, n=None):
+        """pth_scene_set_materials: the whole material table, a list of Material; None passes a null pointer."""
+        arr, cnt = _table(Material, materials, n)
+        check_host(host_lib().pth_scene_set_materials(self.handle, arr, cnt))
+
+    def apply_keyframe(self, frame):
+        """pth_keyframe_apply: one Keyframe of a Keyframes (camera, lights, materials, in that order)."""
+        check_host(host_lib().pth_keyframe_apply(self.handle, C.byref(frame)))
 
     @property
     def n_prims(self):
@@ -567,6 +684,28 @@ class GpuScene:
         """pt_scene_set_camera: camera is a Camera or a dict in ISF form; None raises PtError (PT_ERR_INVALID)."""
         c = make_camera(camera)
         check_gpu(self.lib.pt_scene_set_camera(self.handle, C.byref(c) if c is not None else None))
+
+    def set_lights(self, lights, n=None):
+        """pt_scene_set_lights: lights is a list of Light (all of them; [] removes every light); None passes a null pointer
+        with count n (PT_ERR_INVALID for n > 0)."""
+        arr, cnt = _table(Light, lights, n)
+        check_gpu(self.lib.pt_scene_set_lights(self.handle, arr, cnt))
+
+    def set_materials(self, materials, n=None):
+        """pt_scene_set_materials: the whole material table (as many as the scene was made with), a list of Material."""
+        arr, cnt = _table(Material, materials, n)
+        check_gpu(self.lib.pt_scene_set_materials(self.handle, arr, cnt))
+
+    def apply_keyframe(self, frame, host_scene):
+        """What `render --keyframes` does for a frame after the first: host_scene (the description this scene renders) takes
+        the frame, then this scene takes its camera, lights and materials - those the frame names."""
+        host_scene.apply_keyframe(frame)
+        if frame.has_camera:
+            self.set_camera(host_scene.camera)
+        if frame.has_lights:
+            self.set_lights(host_scene.lights)
+        if frame.n_materials:
+            self.set_materials(host_scene.materials)
 
     def render(self, profile, opts=None):
         """Host-buffer render: returns (rgb8 [n,3] uint8, accum [n,3] float32)."""

@@ -41,6 +41,7 @@
 #include "pt_escape_build.h"
 #include "pt_grid_build.h"
 #include "pthost.h"
+#include "../host/scene_check.h"
 
 // ------------------------------------------------------------------ errors
 namespace {
@@ -483,18 +484,24 @@ struct DeviceBuffer {
 
 }  // namespace
 
-// What pt_scene_set_camera needs to give a scene the camera grid pt_scene_create would have made for a new camera, without
-// the caller's pt_scene_desc or the prep: the primitives' geometry as the grid footprints take it (9 floats: three
-// positions, or centre + radius) with the id | sphere-bit word, the positions of the triangles no model owns (og_params_point's
-// extent scans every triangle of the description), and the resolution rule.  Shared by a prep and the scenes made from it
-// (host memory: 40 B per primitive).
+// What pt_scene_set_camera / _set_lights / _set_materials need to give a scene the grids and tables pt_scene_create would
+// have made for an edited description, without the caller's pt_scene_desc or the prep: the primitives' geometry as the grid
+// footprints take it (9 floats: three positions, or centre + radius) with the id | sphere-bit word, the positions of the
+// triangles no model owns (og_params_point's and params_ortho's extents scan every triangle of the description), the inputs
+// of the grids' resolution rule (grid_rule), and the model -> material indices with the texture table a new material table
+// is checked against.  Shared by a prep and the scenes made from it (host memory: 40 B per primitive).
 struct CamGridSource {
     std::vector<float> og_geom;
     std::vector<uint32_t> og_words;
     std::vector<float> unowned;   // 9 floats per triangle outside every model's range
-    bool device_grids = false;    // false: PT_OG_HOST=1 (a moved camera goes without a grid)
+    bool device_grids = false;    // false: PT_OG_HOST=1 (a moved camera, edited lights go without grids)
+    bool grids_on = false;        // PT_OG
     uint32_t cam_res = 0;         // resolution of a camera grid; 0: none whatever the camera (PT_OG=0, no primitives, budget)
     double budget = 0;            // PT_OG_BUDGET_GIB in bytes
+    std::vector<int32_t> model_material;   // pt_model.material of every model
+    uint32_t n_materials = 0;
+    std::vector<pt_texture> textures;
+    uint64_t n_texel_bytes = 0;
 };
 
 struct pt_scene {
@@ -505,8 +512,10 @@ struct pt_scene {
     bool ortho_light_grids = false;   // some light grid is orthographic (a directional light): kernel variants DIRL
     std::vector<uint32_t> host_prim_entry;
     std::vector<pth_origin_grid> grid_headers;   // device-built grids: [0] camera, [1 + i] light i (enabled = 0: none)
-    std::shared_ptr<const CamGridSource> cam_src;   // (pt_scene_set_camera)
+    std::shared_ptr<const CamGridSource> cam_src;   // (pt_scene_set_camera, _set_lights, _set_materials)
+    uint32_t cam_res = 0;                             // the camera grid's resolution rule for the scene's light count (grid_rule)
     uint64_t cam_grid_bytes = 0, cam_grid_refs = 0;   // device bytes / list entries of the camera grid
+    uint64_t light_grid_bytes = 0, light_grid_refs = 0;   // device bytes / list entries of the light grids
     std::vector<DevGrid> host_light_grids;
     struct BuiltGrids {   // what grids_on_device() produced for this scene (possibly while the KD-tree was still being built)
         bool done = false, all_lights = false, ortho = false;
@@ -587,6 +596,13 @@ struct pt_scene {
         if (pipe.side) (void)hipStreamDestroy(pipe.side);
         if (pipe.side_wide) (void)hipStreamDestroy(pipe.side_wide);
     }
+    // Free one of the scene's device allocations (nullptr: nothing).
+    void release(const void* q) {
+        if (!q) return;
+        auto it = std::find(allocations.begin(), allocations.end(), q);
+        if (it != allocations.end()) allocations.erase(it);
+        (void)hipFree(const_cast<void*>(q));
+    }
     template <class T>
     const T* upload(const T* host, size_t count) {
         size_t bytes = std::max<size_t>(16, count * sizeof(T));
@@ -656,6 +672,54 @@ namespace {
 
 void grids_on_device(const pt_prep& P, pt_scene& s);
 
+// A light as the device reads it (tame: every colour component finite and below 1e30).
+DevLight dev_light(const pt_light& l) {
+    DevLight o{};
+    o.kind = l.kind;
+    memcpy(o.vec, l.vec, 12);
+    memcpy(o.color, l.color, 12);
+    o.tame = 1u;
+    for (int k = 0; k < 3; ++k)
+        if (!(fabsf(l.color[k]) < 1e30f)) o.tame = 0u;  // also catches NaN
+    return o;
+}
+
+// Byte budget over ALL grids of the scene (PT_OG_BUDGET_GIB, default 48 of the 288 GB): the grids are an optional
+// accelerator in front of the KD-tree, one per camera and per light, 6 res^2 cells of 4 B plus ~1.5x that in list
+// entries each (8192^2: ~4 GB a grid) - a scene with many lights must not run the host or the device out of
+// memory over them.  The resolution is halved (down to 512) until the estimate fits; if it still does not, or
+// the grids as built exceed the budget, the lights go without (their shadow rays take the KD-tree).  Evaluated by
+// prep_create, and again by pt_scene_set_lights for the new light count.
+struct GridRule {
+    uint32_t res = 0;         // the camera grid's resolution
+    uint32_t light_res = 0;   // the light grids' (PT_OG_RES_LIGHT: experiments - a resolution of their own)
+    bool cam_fits = false;    // the camera grid's estimate fits the budget
+    bool lights_fit = false;  // every grid's estimate at `res` fits the budget
+    uint32_t cam_res = 0;     // res if a camera grid is to be had at all (PT_OG, primitives, budget), else 0
+    bool lights = false;      // the lights get grids (if every one of them can have one)
+};
+double grid_estimate(uint32_t r) { return 6.0 * r * r * 4.0 * 2.5; }
+GridRule grid_rule(uint64_t n_prims, uint32_t n_lights, double budget, bool grids_on) {
+    GridRule R;
+    uint32_t res = pth_origin_grid_auto_resolution(n_prims);
+    const double n_grids = 1.0 + n_lights;
+    while (res > 512u && grid_estimate(res) * n_grids > budget) res >>= 1;
+    R.lights_fit = grid_estimate(res) * n_grids <= budget;
+    R.light_res = [&] {
+        const char* e = getenv("PT_OG_RES_LIGHT");
+        return e && *e && atoi(e) >= 32 ? (uint32_t)atoi(e) : res;
+    }();
+    if (!R.lights_fit) {   // the camera grid alone, at the resolution it is worth having
+        res = pth_origin_grid_auto_resolution(n_prims);
+        while (res > 512u && grid_estimate(res) > budget) res >>= 1;
+    }
+    R.res = res;
+    R.cam_fits = grid_estimate(res) <= budget;
+    R.cam_res = grids_on && n_prims > 0 && R.cam_fits ? res : 0u;
+    R.lights = grids_on && n_prims > 0 && R.lights_fit;
+    return R;
+}
+
 // `early` / `early_device`: the scene this prep is made for, when there is exactly one (pt_scene_create): its origin grids
 // are then built on the device by the grid thread WHILE the KD-tree is being built on the host.
 void prep_create(const pt_scene_desc& d, pt_prep& P, pt_scene* early = nullptr, int early_device = -1) {
@@ -675,19 +739,13 @@ void prep_create(const pt_scene_desc& d, pt_prep& P, pt_scene* early = nullptr, 
             fail(PT_ERR_INVALID, "model %u: triangle range out of bounds", m);
         if (mo.kind != PT_MODEL_MESH && mo.kind != PT_MODEL_SPHERE) fail(PT_ERR_INVALID, "model %u: bad kind", m);
     }
-    for (uint32_t m = 0; m < d.n_materials; ++m) {
-        const pt_material& ma = d.materials[m];
-        const int32_t tx[6] = {ma.tex_albedo, ma.tex_emissive, ma.tex_opacity, ma.tex_metalness, ma.tex_roughness, ma.tex_normal};
-        const uint32_t ch[6] = {3, 3, 1, 1, 1, 3};
-        for (int k = 0; k < 6; ++k) {
-            if (tx[k] < 0) continue;
-            if ((uint32_t)tx[k] >= d.n_textures) fail(PT_ERR_INVALID, "material %u: texture index out of range", m);
-            const pt_texture& t = d.textures[tx[k]];
-            if (t.channels != ch[k]) fail(PT_ERR_INVALID, "material %u: texture %d has %u channels, expected %u", m, tx[k], t.channels, ch[k]);
-            if (t.width == 0 || t.height == 0 || t.offset + (uint64_t)t.width * t.height * t.channels > d.n_texel_bytes)
-                fail(PT_ERR_INVALID, "texture %d: bad extent", tx[k]);
-        }
-    }
+    pth::check_materials(d.materials, d.n_materials, d.textures, d.n_textures, d.n_texel_bytes);
+    // (what pt_scene_set_materials checks a new table against and resolves it through)
+    P.src->model_material.resize(d.n_models);
+    for (uint32_t m = 0; m < d.n_models; ++m) P.src->model_material[m] = d.models[m].material;
+    P.src->n_materials = d.n_materials;
+    P.src->textures.assign(d.textures, d.textures + d.n_textures);
+    P.src->n_texel_bytes = d.n_texel_bytes;
 
     // ---- per-primitive arrays
     uint64_t n_prims = pth_prim_count(&d);
@@ -805,36 +863,23 @@ void prep_create(const pt_scene_desc& d, pt_prep& P, pt_scene* early = nullptr, 
         for (int k = 0; k < 3; ++k)
             for (int r = 0; r < 3; ++r) fro += (double)M[4 * k + r] * M[4 * k + r];
         fro = std::sqrt(fro);
-        // Byte budget over ALL grids of the scene (PT_OG_BUDGET_GIB, default 48 of the 288 GB): the grids are an optional
-        // accelerator in front of the KD-tree, one per camera and per light, 6 res^2 cells of 4 B plus ~1.5x that in list
-        // entries each (8192^2: ~4 GB a grid) - a scene with many lights must not run the host or the device out of
-        // memory over them.  The resolution is halved (down to 512) until the estimate fits; if it still does not, or
-        // the grids as built exceed the budget, the lights go without (their shadow rays take the KD-tree).
+        // the byte budget over all grids of the scene and the resolutions it leaves (grid_rule)
         static const double budget = [] {
             const char* e = getenv("PT_OG_BUDGET_GIB");
             const double g = e && *e ? atof(e) : 48.0;
             return (g > 0 ? g : 48.0) * 1073741824.0;
         }();
-        auto estimate = [](uint32_t r) { return 6.0 * r * r * 4.0 * 2.5; };
-        uint32_t res = pth_origin_grid_auto_resolution(n_prims);
-        const double n_grids = 1.0 + d.n_lights;
-        while (res > 512u && estimate(res) * n_grids > budget) res >>= 1;
-        bool lights_fit = estimate(res) * n_grids <= budget;
-        // (PT_OG_RES_LIGHT: experiments - the light grids at a resolution of their own)
-        const uint32_t light_res = [&] {
-            const char* e = getenv("PT_OG_RES_LIGHT");
-            return e && *e && atoi(e) >= 32 ? (uint32_t)atoi(e) : res;
-        }();
-        if (!lights_fit) {   // the camera grid alone, at the resolution it is worth having
-            res = pth_origin_grid_auto_resolution(n_prims);
-            while (res > 512u && estimate(res) > budget) res >>= 1;
-        }
+        auto estimate = grid_estimate;
+        const GridRule rule = grid_rule(n_prims, d.n_lights, budget, grids_on);
+        const uint32_t res = rule.res, light_res = rule.light_res;
+        const bool lights_fit = rule.lights_fit;
         double grid_bytes = 0;
         static const bool host_grids = [] {
             const char* e = getenv("PT_OG_HOST");
             return e && *e && atoi(e) != 0;
         }();
-        P.src->cam_res = grids_on && n_prims > 0 && estimate(res) <= budget ? res : 0u;
+        P.src->cam_res = rule.cam_res;
+        P.src->grids_on = grids_on;
         P.src->budget = budget;
         P.src->device_grids = !host_grids;
         if (!host_grids) {   // the device builds them at upload time: only the parameters are derived here
@@ -944,14 +989,7 @@ void prep_create(const pt_scene_desc& d, pt_prep& P, pt_scene* early = nullptr, 
     // sRGB -> linear table: (c as f32 / 255.0).powf(2.2) with the host libm (material.rs:137-141)
     for (int c = 0; c < 256; ++c) P.lut[c] = powf((float)c / 255.0f, 2.2f);
     P.lights.resize(d.n_lights);
-    for (uint32_t i = 0; i < d.n_lights; ++i) {
-        P.lights[i].kind = d.lights[i].kind;
-        memcpy(P.lights[i].vec, d.lights[i].vec, 12);
-        memcpy(P.lights[i].color, d.lights[i].color, 12);
-        P.lights[i].tame = 1u;
-        for (int k = 0; k < 3; ++k)
-            if (!(fabsf(d.lights[i].color[k]) < 1e30f)) P.lights[i].tame = 0u;  // also catches NaN
-    }
+    for (uint32_t i = 0; i < d.n_lights; ++i) P.lights[i] = dev_light(d.lights[i]);
     P.textures.assign(d.textures, d.textures + d.n_textures);
     P.texels.assign(d.texels, d.texels + d.n_texel_bytes);
 
@@ -1379,6 +1417,7 @@ void scene_upload(const pt_prep& P, int device, pt_scene& s) {
     D.prim_entry = s.upload(P.prim_entry.data(), P.prim_entry.size());
     s.host_prim_entry = P.prim_entry;   // (test hook pt_trace_rays_wavefront)
     s.cam_src = P.src;
+    s.cam_res = P.src->cam_res;
     D.materials = s.upload(P.model_mat.data(), P.model_mat.size());
     D.textures = s.upload(P.textures.data(), P.textures.size());
     D.texels = s.upload(P.texels.data(), P.texels.size());
@@ -1433,6 +1472,8 @@ void scene_upload(const pt_prep& P, int device, pt_scene& s) {
         const pth_origin_grid& ch = s.grid_headers[0];
         s.cam_grid_bytes = ch.enabled ? (ch.n_cells + 2) * 4 + 8 * std::max<uint64_t>(1, ch.n_refs) : 0;   // (device_grid_build)
         s.cam_grid_refs = ch.enabled ? ch.n_refs : 0;
+        s.light_grid_bytes = B.bytes - s.cam_grid_bytes;
+        s.light_grid_refs = B.refs - s.cam_grid_refs;
         s.info.upload_seconds = std::chrono::duration<float>(std::chrono::steady_clock::now() - t_up).count();
         return;
     }
@@ -1469,6 +1510,8 @@ void scene_upload(const pt_prep& P, int device, pt_scene& s) {
                 upload_grid(P.light_grids[i]->g, lgrids[i]);
                 if (P.light_grids[i]->g.kind != 0) s.ortho_light_grids = true;
             }
+            s.light_grid_bytes = s.info.device_bytes - bytes_mark;
+            for (auto& g : P.light_grids) s.light_grid_refs += g->g.n_refs;
         } catch (const GpuError&) {
             drop_allocations_from(mark, bytes_mark);
             for (auto& g : lgrids) memset(&g, 0, sizeof g);
@@ -1482,8 +1525,134 @@ void scene_upload(const pt_prep& P, int device, pt_scene& s) {
     s.info.upload_seconds = std::chrono::duration<float>(std::chrono::steady_clock::now() - t_up).count();
 }
 
-// pt_scene_set_camera (include/ptgpu.h has the contract, DESIGN.md "Camera updates" the state it touches row by row).  Everything
-// that can fail comes first - the new camera grid is built beside the old one - and the scene is changed only afterwards.
+// ---- live edits of a scene: pt_scene_set_camera, pt_scene_set_lights, pt_scene_set_materials (include/ptgpu.h has the
+// contract, DESIGN.md 4c / 4d the state they touch row by row).  Everything that can fail comes first - new grids and tables
+// are built beside the old ones - and the scene is changed only afterwards.
+
+// Every device allocation the scene makes after construction is freed again unless `done` is set (an edit that failed).
+struct EditRollback {
+    pt_scene& s;
+    size_t mark;
+    uint64_t bytes;
+    bool done = false;
+    explicit EditRollback(pt_scene& sc) : s(sc), mark(sc.allocations.size()), bytes(sc.info.device_bytes) {}
+    ~EditRollback() {
+        if (done) return;
+        while (s.allocations.size() > mark) {
+            (void)hipFree(s.allocations.back());
+            s.allocations.pop_back();
+        }
+        s.info.device_bytes = bytes;
+    }
+};
+
+// The primitives' footprints (CamGridSource) on the scene's device for the grid builds of an edit, uploaded on first use
+// and freed on every way out, with room for the extent reductions.
+struct EditFootprints {
+    float* geom = nullptr;
+    uint32_t* words = nullptr;
+    unsigned long long* ext = nullptr;   // 12 words
+    bool tried = false, ok = false;
+    ~EditFootprints() {
+        for (void* q : {(void*)geom, (void*)words, (void*)ext})
+            if (q) (void)hipFree(q);
+    }
+    // false: no memory for them (the grids that need them are not to be had, as on a fresh scene in that situation)
+    bool ready(const CamGridSource& src) {
+        if (tried) return ok;
+        tried = true;
+        if (hipMalloc((void**)&geom, src.og_geom.size() * 4) != hipSuccess || hipMalloc((void**)&words, src.og_words.size() * 4) != hipSuccess ||
+            hipMalloc((void**)&ext, 12 * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+        HIP_CHECK(hipMemcpy(geom, src.og_geom.data(), src.og_geom.size() * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(words, src.og_words.data(), src.og_words.size() * 4, hipMemcpyHostToDevice));
+        ok = true;
+        return true;
+    }
+    static uint32_t blocks(uint32_t n_prims) { return std::min<uint32_t>((n_prims + 255u) / 256u, 4096u); }
+
+    // og_point_extent about `o`: the device's reduction over the footprints (k_og_extent), the unowned triangles on the host
+    double point_extent(const CamGridSource& src, const float o[3]) {
+        const uint32_t n_prims = (uint32_t)src.og_words.size();
+        HIP_CHECK(hipMemset(ext, 0, 8));
+        hipLaunchKernelGGL(ogb::k_og_extent, dim3(blocks(n_prims)), dim3(256), 0, 0, (const float*)geom, (const uint32_t*)words, n_prims,
+                           (double)o[0], (double)o[1], (double)o[2], ext);
+        HIP_CHECK(hipGetLastError());
+        unsigned long long bits = 0;
+        HIP_CHECK(hipMemcpy(&bits, ext, 8, hipMemcpyDeviceToHost));
+        double e;
+        memcpy(&e, &bits, 8);
+        for (size_t i = 0; i < src.unowned.size(); ++i) {   // (triangles no model owns: rare, on the host)
+            const double v = std::fabs((double)src.unowned[i] - o[i % 3]);
+            if (std::isfinite(v)) e = std::max(e, v);
+        }
+        return e;
+    }
+
+    // params_ortho's extent along the axes of P (k_og_ortho_extent), the unowned triangles on the host
+    pth::og::OrthoExtent ortho_extent(const CamGridSource& src, const pth::og::GridParams& P) {
+        const uint32_t n_prims = (uint32_t)src.og_words.size();
+        HIP_CHECK(hipMemset(ext, 0, 12 * 8));
+        hipLaunchKernelGGL(ogb::k_og_ortho_extent, dim3(blocks(n_prims)), dim3(256), 0, 0, (const float*)geom, (const uint32_t*)words, n_prims,
+                           P.axis_u, P.axis_v, P.axis_w, ext);
+        HIP_CHECK(hipGetLastError());
+        unsigned long long key[12];
+        HIP_CHECK(hipMemcpy(key, ext, sizeof key, hipMemcpyDeviceToHost));
+        double m[12];
+        for (int i = 0; i < 12; ++i) {   // (og_order_key inverted; 0: no value)
+            const unsigned long long b = key[i] == 0 ? 0xfff0000000000000ull : (key[i] >> 63) ? key[i] & 0x7fffffffffffffffull : ~key[i];
+            memcpy(&m[i], &b, 8);
+        }
+        pth::og::OrthoExtent e;
+        for (int k = 0; k < 3; ++k) {
+            e.lo[k] = -m[k];
+            e.hi[k] = m[3 + k];
+            e.bmin[k] = -m[6 + k];
+            e.bmax[k] = m[9 + k];
+        }
+        for (size_t i = 0; i + 2 < src.unowned.size(); i += 3)
+            pth::og::ortho_extent_grow(e, P.axis_u, P.axis_v, P.axis_w, pth::og::Vec{src.unowned[i], src.unowned[i + 1], src.unowned[i + 2]}, 0.0);
+        return e;
+    }
+};
+
+// The camera grid pt_scene_create would build for camera transform M at resolution cam_res (0: none): prep_create's rule
+// (fro < 64, fro * 1.001, the budget), the extent reduced on the device, the device build of grids_on_device.  False: no
+// grid, also when the device has no memory for it.  A device failure of another kind throws.
+bool camera_grid_build(pt_scene& s, EditFootprints& F, const float* M, uint32_t cam_res, double& used, DevGrid& grid,
+                       pth_origin_grid& hdr, uint64_t& bytes) {
+    const CamGridSource& src = *s.cam_src;
+    memset(&grid, 0, sizeof grid);
+    hdr = pth_origin_grid{};
+    bytes = 0;
+    double fro = 0;
+    for (int k = 0; k < 3; ++k)
+        for (int r = 0; r < 3; ++r) fro += (double)M[4 * k + r] * M[4 * k + r];
+    fro = std::sqrt(fro);
+    const uint32_t n_prims = (uint32_t)src.og_words.size();
+    if (!(src.device_grids && cam_res && n_prims > 0 && fro > 0 && fro < 64.0) || !F.ready(src)) return false;
+    pt_prep::GridJob job;
+    job.valid = pth::og_params_point_ext(M + 12, cam_res, 0.f, (float)(fro * 1.001), F.point_extent(src, M + 12), job.params, job.hdr);
+    const bool built = device_grid_build(s, job, F.geom, F.words, n_prims, src.og_words, used, src.budget, grid, hdr, bytes);
+    if (!built) {
+        memset(&grid, 0, sizeof grid);
+        hdr = pth_origin_grid{};
+        bytes = 0;
+    }
+    return built;
+}
+
+// What earlier frames left: their counts (a plan sized from another camera's, light's or material's counts may overflow),
+// the captured graphs (they hold the old DevScene as kernel arguments), the cull table of the last frame.
+void drop_frame_state(pt_scene& s) {
+    s.frame_stats.clear();
+    for (auto& g : s.graphs) (void)hipGraphExecDestroy(g.second);
+    s.graphs.clear();
+    s.last_mask_blocks = 0;
+}
+
 void scene_set_camera(pt_scene& s, const pt_camera& cam) {
     HIP_CHECK(hipSetDevice(s.device));
     HIP_CHECK(hipDeviceSynchronize());   // the frames in flight finish with the old camera (and its grid)
@@ -1495,86 +1664,23 @@ void scene_set_camera(pt_scene& s, const pt_camera& cam) {
     memcpy(D.cam_c3, M + 12, 12);
     D.tan_half_fov = tanf(cam.fov / 2.f);
 
-    // ---- the camera grid a fresh scene would have: prep_create's rule (resolution, fro < 64, fro * 1.001, budget), its
-    // parameters with the extent reduced on the device from the footprints, the device build of grids_on_device.  PT_OG_HOST=1
-    // (host-built grids): the moved camera goes without.  No memory for it: without, as a fresh scene on that device.
-    const CamGridSource& src = *s.cam_src;
+    // ---- the camera grid a fresh scene would have.  PT_OG_HOST=1 (host-built grids): the moved camera goes without.
+    EditRollback rb(s);
     DevGrid grid;
-    memset(&grid, 0, sizeof grid);
     pth_origin_grid hdr{};
     uint64_t grid_bytes = 0;
-    double fro = 0;
-    for (int k = 0; k < 3; ++k)
-        for (int r = 0; r < 3; ++r) fro += (double)M[4 * k + r] * M[4 * k + r];
-    fro = std::sqrt(fro);
-    const uint32_t n_prims = (uint32_t)src.og_words.size();
-    if (src.device_grids && src.cam_res && n_prims > 0 && fro > 0 && fro < 64.0) {
-        float* d_geom = nullptr;
-        uint32_t* d_words = nullptr;
-        unsigned long long* d_ext = nullptr;
-        struct Scratch {   // (freed on every way out)
-            float*& g;
-            uint32_t*& w;
-            unsigned long long*& e;
-            ~Scratch() {
-                for (void* q : {(void*)g, (void*)w, (void*)e})
-                    if (q) (void)hipFree(q);
-            }
-        } scratch{d_geom, d_words, d_ext};
-        bool built = false;
-        try {
-            if (hipMalloc((void**)&d_geom, src.og_geom.size() * 4) == hipSuccess && hipMalloc((void**)&d_words, src.og_words.size() * 4) == hipSuccess &&
-                hipMalloc((void**)&d_ext, 8) == hipSuccess) {
-                HIP_CHECK(hipMemcpy(d_geom, src.og_geom.data(), src.og_geom.size() * 4, hipMemcpyHostToDevice));
-                HIP_CHECK(hipMemcpy(d_words, src.og_words.data(), src.og_words.size() * 4, hipMemcpyHostToDevice));
-                HIP_CHECK(hipMemset(d_ext, 0, 8));
-                const uint32_t blocks = std::min<uint32_t>((n_prims + 255u) / 256u, 4096u);
-                hipLaunchKernelGGL(ogb::k_og_extent, dim3(blocks), dim3(256), 0, 0, (const float*)d_geom, (const uint32_t*)d_words, n_prims,
-                                   (double)M[12], (double)M[13], (double)M[14], d_ext);
-                HIP_CHECK(hipGetLastError());
-                unsigned long long bits = 0;
-                HIP_CHECK(hipMemcpy(&bits, d_ext, 8, hipMemcpyDeviceToHost));
-                double ext;
-                memcpy(&ext, &bits, 8);
-                for (size_t i = 0; i < src.unowned.size(); ++i) {   // (triangles no model owns: rare, on the host)
-                    const double v = std::fabs((double)src.unowned[i] - M[12 + i % 3]);
-                    if (std::isfinite(v)) ext = std::max(ext, v);
-                }
-                pt_prep::GridJob job;
-                job.valid = pth::og_params_point_ext(M + 12, src.cam_res, 0.f, (float)(fro * 1.001), ext, job.params, job.hdr);
-                double used = 0;
-                built = device_grid_build(s, job, d_geom, d_words, n_prims, src.og_words, used, src.budget, grid, hdr, grid_bytes);
-            } else {
-                (void)hipGetLastError();   // (out of memory: no grid)
-            }
-            // device_grid_build gives up on any failure; what is not a lack of memory is sticky and shows here
-            HIP_CHECK(hipDeviceSynchronize());
-        } catch (...) {
-            if (built) {
-                for (const void* q : {(const void*)grid.cell_off, (const void*)grid.refs}) {
-                    auto it = std::find(s.allocations.begin(), s.allocations.end(), q);
-                    if (it != s.allocations.end()) s.allocations.erase(it);
-                    (void)hipFree(const_cast<void*>(q));
-                }
-            }
-            throw;
-        }
-        if (!built) {
-            memset(&grid, 0, sizeof grid);
-            hdr = pth_origin_grid{};
-            grid_bytes = 0;
-        }
+    {
+        EditFootprints F;
+        double used = 0;
+        camera_grid_build(s, F, M, s.cam_res, used, grid, hdr, grid_bytes);
+        // device_grid_build gives up on any failure; what is not a lack of memory is sticky and shows here
+        HIP_CHECK(hipDeviceSynchronize());
     }
 
     // ---- from here on nothing fails: the scene takes the new camera
-    auto release = [&s](const void* q) {
-        if (!q) return;
-        auto it = std::find(s.allocations.begin(), s.allocations.end(), q);
-        if (it != s.allocations.end()) s.allocations.erase(it);
-        (void)hipFree(const_cast<void*>(q));
-    };
-    release(s.dev.cam_grid.cell_off);
-    release(s.dev.cam_grid.refs);
+    rb.done = true;
+    s.release(s.dev.cam_grid.cell_off);
+    s.release(s.dev.cam_grid.refs);
     D.cam_grid = grid;
     s.built.cam = grid;
     s.built.cam_res = hdr.enabled ? hdr.res : 0u;
@@ -1587,7 +1693,7 @@ void scene_set_camera(pt_scene& s, const pt_camera& cam) {
     // ---- escape masks: built with a delta_in at least the new camera's, they stay a proof; otherwise they go, and the
     // PT_ESCAPE_AFTER schedule starts again (a scene whose attempt found no memory tries again too)
     if (D.escape && escape_delta_in(D) > s.escape_delta) {
-        release(D.escape);
+        s.release(D.escape);
         s.info.device_bytes -= (uint64_t)D.n_prims * 80u;
         D.escape = nullptr;
         s.escape_tried = false;
@@ -1600,12 +1706,157 @@ void scene_set_camera(pt_scene& s, const pt_camera& cam) {
         s.frames_rendered = 0;
     }
     s.dev = D;
-    // ---- what earlier frames left: their counts (a plan sized from another camera's counts may overflow), the captured
-    // graphs (they hold the old DevScene as kernel arguments), the cull table of the last frame
-    s.frame_stats.clear();
-    for (auto& g : s.graphs) (void)hipGraphExecDestroy(g.second);
-    s.graphs.clear();
-    s.last_mask_blocks = 0;
+    drop_frame_state(s);
+}
+
+// pt_scene_set_lights.  The light grids are those grids_on_device builds for the new lights (all or none), their parameters
+// from extents reduced on the device; the camera grid is rebuilt only if the new light count changes its resolution.  The
+// escape masks stay: they depend on the geometry and the camera only (pt_escape.h).
+void scene_set_lights(pt_scene& s, const pt_light* lights, uint32_t n) {
+    pth::check_lights(lights, n);
+    HIP_CHECK(hipSetDevice(s.device));
+    HIP_CHECK(hipDeviceSynchronize());   // the frames in flight finish with the old lights (and their grids)
+    const CamGridSource& src = *s.cam_src;
+    const uint32_t n_prims = (uint32_t)src.og_words.size();
+    const GridRule rule = grid_rule(n_prims, n, src.budget, src.grids_on);
+    std::vector<DevLight> dl(n);
+    for (uint32_t i = 0; i < n; ++i) dl[i] = dev_light(lights[i]);
+    DevScene D = s.dev;
+
+    EditRollback rb(s);
+    EditFootprints F;
+    // ---- the camera grid, if a fresh scene with n lights has another resolution for it
+    const bool new_cam = src.device_grids && rule.cam_res != s.cam_res;
+    DevGrid cam_grid = D.cam_grid;
+    pth_origin_grid cam_hdr = s.grid_headers.empty() ? pth_origin_grid{} : s.grid_headers[0];
+    uint64_t cam_bytes = s.cam_grid_bytes;
+    double used = (double)s.cam_grid_bytes;   // (grids_on_device: the light grids come after the camera's in the budget)
+    if (new_cam) {
+        float M[16] = {};
+        memcpy(M, D.cam_c0, 12);
+        memcpy(M + 4, D.cam_c1, 12);
+        memcpy(M + 8, D.cam_c2, 12);
+        memcpy(M + 12, D.cam_c3, 12);
+        used = 0;
+        camera_grid_build(s, F, M, rule.cam_res, used, cam_grid, cam_hdr, cam_bytes);
+    }
+    // ---- the light grids: all or none (the shadow queue is consumed by ONE kernel); PT_OG_HOST=1: none
+    std::vector<DevGrid> lg(n);
+    for (auto& g : lg) memset(&g, 0, sizeof g);
+    std::vector<pth_origin_grid> lh(n);
+    bool all = rule.lights, ortho = false;
+    uint64_t l_bytes = 0, l_refs = 0;
+    if (n > 0) {
+        all = all && src.device_grids;
+        const size_t mark = s.allocations.size();
+        const float max_normal = 1.5f;   // (prep_create)
+        for (uint32_t i = 0; i < n && all; ++i) {
+            pt_prep::GridJob job;
+            if (lights[i].kind == PT_LIGHT_POINT) {
+                const float* o = lights[i].vec;
+                const bool finite = std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]);
+                if (F.ready(src))
+                    job.valid = pth::og_params_point_ext(o, rule.light_res, 1.05e-5f * max_normal, 1.001f, finite ? F.point_extent(src, o) : 0.0,
+                                                         job.params, job.hdr);
+            } else {   // the shadow rays run along -direction (mod.rs:291)
+                const float sd[3] = {-1.f * lights[i].vec[0], -1.f * lights[i].vec[1], -1.f * lights[i].vec[2]};
+                pth::og::GridParams axes;
+                if (F.ready(src) && pth::og_ortho_axes(sd, axes))
+                    job.valid = pth::og_params_ortho_ext(sd, rule.light_res, F.ortho_extent(src, axes), job.params, job.hdr);
+            }
+            if (!device_grid_build(s, job, F.geom, F.words, n_prims, src.og_words, used, src.budget, lg[i], lh[i], l_bytes)) {
+                all = false;
+            } else {
+                l_refs += lh[i].n_refs;
+                if (lg[i].kind != 0) ortho = true;
+            }
+        }
+        if (!all) {   // drop whatever light grids were built
+            while (s.allocations.size() > mark) {
+                (void)hipFree(s.allocations.back());
+                s.allocations.pop_back();
+            }
+            for (auto& g : lg) memset(&g, 0, sizeof g);
+            for (auto& h : lh) h = pth_origin_grid{};
+            l_bytes = l_refs = 0;
+            ortho = false;
+        }
+    }
+    HIP_CHECK(hipDeviceSynchronize());   // (device_grid_build gives up on any failure: what is not a lack of memory shows here)
+    const DevLight* d_lights = s.upload(dl.data(), dl.size());
+    const DevGrid* d_grids = s.upload(lg.data(), lg.size());
+
+    // ---- from here on nothing fails: the scene takes the new lights
+    rb.done = true;
+    const uint64_t n_old = D.n_lights;
+    for (const DevGrid& g : s.host_light_grids) {
+        s.release(g.cell_off);
+        s.release(g.refs);
+    }
+    s.release(D.lights);
+    s.release(D.light_grids);
+    s.info.device_bytes = s.info.device_bytes - s.light_grid_bytes + l_bytes - std::max<uint64_t>(16, n_old * sizeof(DevLight)) -
+                          std::max<uint64_t>(16, n_old * sizeof(DevGrid));
+    s.info.grid_refs = s.info.grid_refs - s.light_grid_refs + l_refs;
+    s.light_grid_bytes = l_bytes;
+    s.light_grid_refs = l_refs;
+    if (new_cam) {
+        s.release(D.cam_grid.cell_off);
+        s.release(D.cam_grid.refs);
+        D.cam_grid = cam_grid;
+        s.built.cam = cam_grid;
+        s.built.cam_res = cam_hdr.enabled ? cam_hdr.res : 0u;
+        if (!s.grid_headers.empty()) s.grid_headers[0] = cam_hdr;
+        s.info.device_bytes = s.info.device_bytes - s.cam_grid_bytes + cam_bytes;
+        s.info.grid_refs = s.info.grid_refs - s.cam_grid_refs + (cam_hdr.enabled ? cam_hdr.n_refs : 0);
+        s.info.cam_grid_res = cam_hdr.enabled ? cam_hdr.res : 0u;
+        s.cam_grid_bytes = cam_bytes;
+        s.cam_grid_refs = cam_hdr.enabled ? cam_hdr.n_refs : 0;
+    }
+    s.cam_res = rule.cam_res;
+    D.lights = d_lights;
+    D.light_grids = d_grids;
+    D.n_lights = n;
+    D.all_lights_gridded = all ? 1u : 0u;
+    s.host_light_grids = lg;
+    s.ortho_light_grids = ortho;
+    s.built.lights = lg;
+    s.built.all_lights = all;
+    s.built.ortho = ortho;
+    s.built.light_grids = all ? n : 0u;
+    s.info.light_grids = all ? n : 0u;
+    if (!s.grid_headers.empty()) {
+        s.grid_headers.resize(1 + n);
+        for (uint32_t i = 0; i < n; ++i) s.grid_headers[1 + i] = lh[i];
+    }
+    s.dev = D;
+    drop_frame_state(s);
+}
+
+// pt_scene_set_materials: the model -> material indices of the description resolve the new table into the per-model copies
+// the device reads, in a new buffer; has_translucent selects the ALPHA kernel variants.  Nothing else depends on materials.
+void scene_set_materials(pt_scene& s, const pt_material* materials, uint32_t n) {
+    const CamGridSource& src = *s.cam_src;
+    if (n != src.n_materials) fail(PT_ERR_INVALID, "pt_scene_set_materials: %u materials, the scene has %u", n, src.n_materials);
+    pth::check_materials(materials, n, src.textures.data(), (uint32_t)src.textures.size(), src.n_texel_bytes);
+    HIP_CHECK(hipSetDevice(s.device));
+    HIP_CHECK(hipDeviceSynchronize());   // the frames in flight finish with the old materials
+    const size_t n_models = src.model_material.size();
+    std::vector<pt_material> mm(n_models);
+    bool translucent = false;
+    for (size_t m = 0; m < n_models; ++m) {   // (as prep_create)
+        mm[m] = materials[src.model_material[m]];
+        if (mm[m].opacity != 1.0f || mm[m].tex_opacity >= 0) translucent = true;
+    }
+    EditRollback rb(s);
+    const pt_material* d_mat = s.upload(mm.data(), mm.size());
+    rb.done = true;
+    s.release(s.dev.materials);
+    s.info.device_bytes -= std::max<uint64_t>(16, n_models * sizeof(pt_material));
+    s.dev.materials = d_mat;
+    s.dev.has_translucent = translucent ? 1u : 0u;
+    s.info.has_translucent = translucent;
+    drop_frame_state(s);
 }
 
 hipEvent_t get_event(const pt_scene& s, size_t i) {
@@ -2795,6 +3046,20 @@ int pt_scene_set_camera(pt_scene* scene, const pt_camera* camera) {
     return guarded([&] {
         if (!scene || !camera) fail(PT_ERR_INVALID, "pt_scene_set_camera: null argument");
         scene_set_camera(*scene, *camera);
+    });
+}
+
+int pt_scene_set_lights(pt_scene* scene, const pt_light* lights, uint32_t n_lights) {
+    return guarded([&] {
+        if (!scene || (!lights && n_lights > 0)) fail(PT_ERR_INVALID, "pt_scene_set_lights: null argument");
+        scene_set_lights(*scene, lights, n_lights);
+    });
+}
+
+int pt_scene_set_materials(pt_scene* scene, const pt_material* materials, uint32_t n_materials) {
+    return guarded([&] {
+        if (!scene || !materials) fail(PT_ERR_INVALID, "pt_scene_set_materials: null argument");
+        scene_set_materials(*scene, materials, n_materials);
     });
 }
 

@@ -95,6 +95,50 @@ __global__ __launch_bounds__(256) void k_og_extent(const float* __restrict__ geo
     if ((threadIdx.x & 63u) == 0u) atomicMax(out, (unsigned long long)__double_as_longlong(m));
 }
 
+// An order-preserving 64-bit key of a double (for atomicMax): non-negative values get the sign bit set, negative ones all
+// bits flipped, so that key(a) < key(b) exactly when a < b (-0 < +0).  Key 0 is below every finite value: "no value yet".
+__device__ inline unsigned long long og_order_key(double x) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+// The extent of an orthographic grid along (u, v, w) from the uploaded footprints, for pt_scene_set_lights: the twelve values
+// of pth::og::OrthoExtent (lo / hi along the axes, bmin / bmax of the coordinates) over every vertex of a triangle and every
+// sphere, in one pass.  Each lane grows its own extent with the host's ortho_extent_grow (the same f64 terms in the same
+// operand order), the wavefront reduces it with shuffles, and one lane folds it into out[12] with one atomicMax per value on
+// og_order_key - of the value for a maximum, of its negation for a minimum.  A max or min does not depend on the order of
+// its terms, so the result is the host's (up to the sign of a zero, which no grid parameter depends on).
+__global__ __launch_bounds__(256) void k_og_ortho_extent(const float* __restrict__ geom, const uint32_t* __restrict__ words, uint32_t n_prims,
+                                                         pth::og::Vec u, pth::og::Vec v, pth::og::Vec w,
+                                                         unsigned long long* __restrict__ out) {
+    using namespace pth::og;
+    OrthoExtent e;
+    ortho_extent_init(e);
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n_prims; p += gridDim.x * blockDim.x) {
+        const float* g = geom + (size_t)p * 9;
+        if (words[p] & 0x80000000u) {   // sphere: (centre, radius)
+            ortho_extent_grow(e, u, v, w, Vec{g[0], g[1], g[2]}, fabs((double)g[3]));
+        } else {
+            for (int k = 0; k < 3; ++k) ortho_extent_grow(e, u, v, w, Vec{g[k * 3], g[k * 3 + 1], g[k * 3 + 2]}, 0.0);
+        }
+    }
+    double m[12];   // all as maxima: -lo, hi, -bmin, bmax
+    for (int k = 0; k < 3; ++k) {
+        m[k] = -e.lo[k];
+        m[3 + k] = e.hi[k];
+        m[6 + k] = -e.bmin[k];
+        m[9 + k] = e.bmax[k];
+    }
+    for (int i = 0; i < 12; ++i) {
+        double x = m[i];
+        for (int off = 32; off > 0; off >>= 1) x = og_max(x, __shfl_xor(x, off, 64));
+        m[i] = x;
+    }
+    if ((threadIdx.x & 63u) == 0u)
+        for (int i = 0; i < 12; ++i)
+            if (m[i] > -INFINITY) atomicMax(out + i, og_order_key(m[i]));
+}
+
 #define OG_SCAN_BLOCK 1024u   // cells per block (256 threads x 4)
 
 // (summed in 64 bits and SATURATED: 1024 cells that every one of several million large primitives overlaps hold more than

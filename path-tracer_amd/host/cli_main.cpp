@@ -3,6 +3,7 @@
 //
 //   path-tracer render <INPUT> [-o/--output <OUTPUT>] [-q/--quiet] [-v/--viewer]
 //                              [--debug-textures] [-p/--profile <PROFILE>] [--camera-path <CAMERAS>]
+//                              [--keyframes <FRAMES>]
 //       env OUTPUT (default render.png), env PROFILE
 //   path-tracer convert <INPUT> <OUTPUT>      (glTF 2.0 -> ISF, host/gltf_convert.cpp)
 //
@@ -13,7 +14,10 @@
 // sharding of SURVEY 8-e inside one process; the KD-tree and the origin grids are built once and uploaded to every
 // device, the slices are exchanged by one RCCL all-gather), --stats (one JSON line with timings on stderr),
 // --camera-path cams.json (a JSON array of ISF cameras: the scene is uploaded once and rendered from every camera in
-// turn through pt_scene_set_camera; frame i goes to OUTPUT with i substituted for its one %d / %0Nd field).
+// turn through pt_scene_set_camera; frame i goes to OUTPUT with i substituted for its one %d / %0Nd field),
+// --keyframes frames.json (a JSON array of frames, each with any of a camera, all lights, material factor edits: the scene
+// is uploaded once, frame i's edits are applied on top of frame i - 1's through pt_scene_set_camera / _set_lights /
+// _set_materials, and frame i is written as with --camera-path).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -51,6 +55,8 @@ void usage_render(FILE* f) {
           "      --stats              Print timing statistics as JSON on stderr\n"
           "      --camera-path <CAMERAS>  Render one frame per camera of a JSON array of ISF cameras; the OUTPUT name\n"
           "                           takes the frame index in its %d / %0Nd field (e.g. out/frame_%04d.png)\n"
+          "      --keyframes <FRAMES>  Render one frame per object of a JSON array of keyframes (\"camera\", \"lights\",\n"
+          "                           \"materials\" edits, each frame on top of the last); OUTPUT as with --camera-path\n"
           "  -h, --help               Print help\n",
           f);
 }
@@ -121,9 +127,9 @@ void on_progress(uint32_t done, uint32_t total, void* user) {
 
 int run_render(int argc, char** argv) {
     std::string input, output, profile_path;
-    std::string camera_path;
+    std::string camera_path, keyframes_path;
     bool have_output = false, have_profile = false, quiet = false, debug_textures = false, stats = false, viewer = false;
-    bool have_camera_path = false;
+    bool have_camera_path = false, have_keyframes = false;
     int device = 0;
     std::vector<int> devices;
     for (int i = 0; i < argc; ++i) {
@@ -157,6 +163,9 @@ int run_render(int argc, char** argv) {
         else if (a == "--camera-path" || a.rfind("--camera-path=", 0) == 0) {
             camera_path = value("--camera-path <CAMERAS>");
             have_camera_path = true;
+        } else if (a == "--keyframes" || a.rfind("--keyframes=", 0) == 0) {
+            keyframes_path = value("--keyframes <FRAMES>");
+            have_keyframes = true;
         }
         else if (a == "--devices" || a.rfind("--devices=", 0) == 0) {
             std::string list = value("--devices <A,B,..>");
@@ -191,22 +200,33 @@ int run_render(int argc, char** argv) {
     pt_profile profile;
     if (pth_profile_load(have_profile ? profile_path.c_str() : nullptr, &profile) != PT_OK) die(pth_last_error());
 
-    // --camera-path: everything it can get wrong is found before any GPU work
+    // --camera-path / --keyframes: everything they can get wrong is found before any GPU work
     std::vector<pt_camera> cameras;
+    pth_keyframe* keyframes = nullptr;
+    uint32_t n_keyframes = 0;
     std::string out_pre, out_post;
     int out_width = 0;
     bool out_field = false;
-    if (have_camera_path) {
-        if (debug_textures) die("error: the argument '--debug-textures' cannot be used with '--camera-path <CAMERAS>'");
-        pt_camera* cams = nullptr;
-        uint32_t n_cams = 0;
-        if (pth_camera_path_load(camera_path.c_str(), &cams, &n_cams) != PT_OK) die(pth_last_error());
-        cameras.assign(cams, cams + n_cams);
-        pth_camera_path_free(cams);
+    if (have_camera_path && have_keyframes) die("error: the argument '--keyframes <FRAMES>' cannot be used with '--camera-path <CAMERAS>'");
+    if (have_camera_path || have_keyframes) {
+        const char* opt = have_camera_path ? "--camera-path <CAMERAS>" : "--keyframes <FRAMES>";
+        if (debug_textures) die(std::string("error: the argument '--debug-textures' cannot be used with '") + opt + "'");
+        size_t n_frames = 0;
+        if (have_camera_path) {
+            pt_camera* cams = nullptr;
+            uint32_t n_cams = 0;
+            if (pth_camera_path_load(camera_path.c_str(), &cams, &n_cams) != PT_OK) die(pth_last_error());
+            cameras.assign(cams, cams + n_cams);
+            pth_camera_path_free(cams);
+            n_frames = cameras.size();
+        } else {
+            if (pth_keyframes_load(keyframes_path.c_str(), &keyframes, &n_keyframes) != PT_OK) die(pth_last_error());
+            n_frames = n_keyframes;
+        }
         out_field = frame_pattern(output, out_pre, out_width, out_post);
-        if (cameras.size() > 1 && !out_field)
-            die("error: --camera-path has " + std::to_string(cameras.size()) + " cameras but the output name '" + output +
-                "' has no %d / %0Nd field for the frame index");
+        if (n_frames > 1 && !out_field)
+            die(std::string("error: ") + (have_camera_path ? "--camera-path" : "--keyframes") + " has " + std::to_string(n_frames) +
+                (have_camera_path ? " cameras" : " frames") + " but the output name '" + output + "' has no %d / %0Nd field for the frame index");
         size_t dot = output.find_last_of('.');
         std::string ext = dot == std::string::npos ? "" : output.substr(dot + 1);
         for (char& c : ext) c = (char)tolower(c);
@@ -222,7 +242,55 @@ int run_render(int argc, char** argv) {
     auto t0 = std::chrono::steady_clock::now();
     pth_scene* hscene = nullptr;  // load_internal (main.rs:38)
     if (pth_scene_load_isf(input.c_str(), &hscene) != PT_OK) die(pth_last_error());
-    if (!cameras.empty() && pth_scene_set_camera(hscene, &cameras[0]) != PT_OK) die(pth_last_error());   // (frame 0: no grid rebuild)
+    // What every frame after the first changes (--camera-path: its camera; --keyframes: the state its edits leave), found
+    // by applying the frames to the host scene in turn - a material index out of range ends the run here, before any GPU
+    // work - and the host scene left in frame 0's state for pt_scene_create (frame 0: no grid rebuild).
+    struct FrameEdit {
+        bool camera = false, lights = false, materials = false;
+        pt_camera cam{};
+        std::vector<pt_light> light;
+        std::vector<pt_material> material;
+    };
+    std::vector<FrameEdit> edits;
+    for (const pt_camera& c : cameras) {
+        edits.emplace_back();
+        edits.back().camera = true;
+        edits.back().cam = c;
+    }
+    if (keyframes) {
+        auto snapshot = [&](FrameEdit& e) {
+            const pt_scene_desc* d = pth_scene_desc(hscene);
+            e.cam = d->camera;
+            e.light.assign(d->lights, d->lights + d->n_lights);
+            e.material.assign(d->materials, d->materials + d->n_materials);
+        };
+        for (uint32_t f = 0; f < n_keyframes; ++f) {
+            if (pth_keyframe_apply(hscene, &keyframes[f]) != PT_OK) die(std::string("frame ") + std::to_string(f) + ": " + pth_last_error());
+            edits.emplace_back();
+            FrameEdit& e = edits.back();
+            e.camera = keyframes[f].has_camera != 0;
+            e.lights = keyframes[f].has_lights != 0;
+            e.materials = keyframes[f].n_materials > 0;
+            snapshot(e);
+        }
+        const FrameEdit& e0 = edits[0];
+        if (pth_scene_set_camera(hscene, &e0.cam) != PT_OK || pth_scene_set_lights(hscene, e0.light.data(), (uint32_t)e0.light.size()) != PT_OK ||
+            pth_scene_set_materials(hscene, e0.material.data(), (uint32_t)e0.material.size()) != PT_OK)
+            die(pth_last_error());
+        pth_keyframes_free(keyframes);
+        keyframes = nullptr;
+    } else if (!cameras.empty() && pth_scene_set_camera(hscene, &cameras[0]) != PT_OK) {
+        die(pth_last_error());
+    }
+    // frame f's edits on a device's scene (f > 0)
+    auto apply_frame = [&](pt_scene* sc, size_t f) {
+        const FrameEdit& e = edits[f];
+        int rc = PT_OK;
+        if (e.camera) rc = pt_scene_set_camera(sc, &e.cam);
+        if (rc == PT_OK && e.lights) rc = pt_scene_set_lights(sc, e.light.data(), (uint32_t)e.light.size());
+        if (rc == PT_OK && e.materials) rc = pt_scene_set_materials(sc, e.material.data(), (uint32_t)e.material.size());
+        return rc;
+    };
     auto t1 = std::chrono::steady_clock::now();
 
     if (devices.size() == 1 || (debug_textures && !devices.empty())) {
@@ -279,7 +347,7 @@ int run_render(int argc, char** argv) {
             opts[k].tile_w = opts[k].tile_h = 32;
             slice_pixels = std::max<uint64_t>(slice_pixels, pt_local_pixel_count(&profile, &opts[k]));
         }
-        const size_t n_frames = cameras.empty() ? 1 : cameras.size();   // (--camera-path: every scene takes every camera)
+        const size_t n_frames = edits.empty() ? 1 : edits.size();   // (--camera-path / --keyframes: every scene takes every frame)
         std::vector<std::vector<std::vector<uint8_t>>> part(n, std::vector<std::vector<uint8_t>>(n_frames));
         std::vector<std::vector<uint32_t>> map(n);
         std::vector<std::string> error(n);
@@ -302,14 +370,14 @@ int run_render(int argc, char** argv) {
             }
             for (size_t f = 0; f < n_frames && up && failed == 0 && error[k].empty(); ++f) {
                 if (distinct) {
-                    if ((f > 0 && !check(pt_scene_set_camera(sc, &cameras[f]))) ||
+                    if ((f > 0 && !check(apply_frame(sc, f))) ||
                         !check(pt_render_gathered(sc, comms[k], &profile, &opts[k], slice_pixels, k == 0 ? frames[f].data() : nullptr))) {
                         fprintf(stderr, "Error: %s\n", error[k].c_str());   // (the peers may be inside the all-gather: do not join them)
                         fflush(stderr);
                         _exit(2);
                     }
                 } else {
-                    if (f > 0 && !check(pt_scene_set_camera(sc, &cameras[f]))) break;
+                    if (f > 0 && !check(apply_frame(sc, f))) break;
                     uint64_t count = pt_local_pixel_count(&profile, &opts[k]);
                     map[k].resize(count);
                     part[k][f].resize(count * 3);
@@ -369,10 +437,10 @@ int run_render(int argc, char** argv) {
         }
     }
     std::vector<uint8_t> rgb((size_t)profile.width * profile.height * 3);
-    const size_t n_frames = cameras.empty() ? 1 : cameras.size();   // (--camera-path: one frame per camera, the scene kept)
+    const size_t n_frames = edits.empty() ? 1 : edits.size();   // (--camera-path / --keyframes: one frame each, the scene kept)
     auto t3 = t2, t4 = t2;
     for (size_t f = 0; f < n_frames; ++f) {
-        if (f > 0 && pt_scene_set_camera(scene, &cameras[f]) != PT_OK) die(pt_last_error());
+        if (f > 0 && apply_frame(scene, f) != PT_OK) die(pt_last_error());
         pv.path = frame_name(f);
         if (pt_render(scene, &profile, &opts, rgb.data(), nullptr) != PT_OK) die(pt_last_error());
         t3 = std::chrono::steady_clock::now();

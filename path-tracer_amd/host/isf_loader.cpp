@@ -33,11 +33,34 @@
 #include <sstream>
 
 #include "host_common.hpp"
+#include "scene_check.h"
 
 namespace pth {
 
 static thread_local std::string g_last_error;
 void set_last_error(const std::string& msg) { g_last_error = msg; }
+
+void check_materials(const pt_material* materials, uint32_t n_materials, const pt_texture* textures, uint32_t n_textures,
+                     uint64_t n_texel_bytes) {
+    for (uint32_t m = 0; m < n_materials; ++m) {
+        const pt_material& ma = materials[m];
+        const int32_t tx[6] = {ma.tex_albedo, ma.tex_emissive, ma.tex_opacity, ma.tex_metalness, ma.tex_roughness, ma.tex_normal};
+        const uint32_t ch[6] = {3, 3, 1, 1, 1, 3};
+        for (int k = 0; k < 6; ++k) {
+            if (tx[k] < 0) continue;
+            if ((uint32_t)tx[k] >= n_textures) fail(PT_ERR_INVALID, "material %u: texture index out of range", m);
+            const pt_texture& t = textures[tx[k]];
+            if (t.channels != ch[k]) fail(PT_ERR_INVALID, "material %u: texture %d has %u channels, expected %u", m, tx[k], t.channels, ch[k]);
+            if (t.width == 0 || t.height == 0 || t.offset + (uint64_t)t.width * t.height * t.channels > n_texel_bytes)
+                fail(PT_ERR_INVALID, "texture %d: bad extent", tx[k]);
+        }
+    }
+}
+
+void check_lights(const pt_light* lights, uint32_t n_lights) {
+    for (uint32_t i = 0; i < n_lights; ++i)
+        if (lights[i].kind != PT_LIGHT_POINT && lights[i].kind != PT_LIGHT_DIRECTIONAL) fail(PT_ERR_INVALID, "light %u: bad kind", i);
+}
 
 namespace {
 
@@ -562,6 +585,111 @@ static void load_camera_path(const char* path, std::vector<pt_camera>& out) {
     if (out.empty()) fail(PT_ERR_PARSE, "%s: the camera path holds no camera", path);
 }
 
+// One frame of a keyframe file: the edits it makes, lights and material edits in storage of its own.
+struct Keyframe {
+    bool has_camera = false, has_lights = false;
+    pt_camera camera{};
+    pth_scene lights;   // (parse_light appends to a scene's lights)
+    std::vector<pth_material_edit> materials;
+};
+
+// A partial ISF channel of a material edit: "factor" and nothing else (textures cannot change).
+template <size_t N>
+void parse_edit_channel(JsonReader& r, float* out) {
+    bool hf = false;
+    r.object([&](const std::string& key) {
+        if (key == "factor") {
+            float f[N];
+            if constexpr (N == 1) f[0] = r.f32();
+            else r.f32_array(f);
+            memcpy(out, f, sizeof f);
+            hf = true;
+        } else if (key == "texture") {
+            r.error("a material edit cannot change a texture (`texture`)");
+        } else {
+            r.error(("unknown field `" + key + "`, expected `factor`").c_str());
+        }
+    });
+    if (!hf) r.error("missing field `factor`");
+}
+
+// "materials": {"<index>": {partial ISF material}, ...}
+void parse_material_edits(JsonReader& r, std::vector<pth_material_edit>& out) {
+    r.object([&](const std::string& key) {
+        bool digits = !key.empty() && key.size() <= 10;
+        for (char c : key) digits = digits && c >= '0' && c <= '9';
+        if (!digits || std::stoull(key) > 0xffffffffull) r.error(("material index `" + key + "` is not a decimal number").c_str());
+        pth_material_edit e{};
+        e.index = (uint32_t)std::stoull(key);
+        r.object([&](const std::string& field) {
+            if (field == "albedo") parse_edit_channel<3>(r, e.albedo), e.fields |= PTH_MAT_ALBEDO;
+            else if (field == "emissive") parse_edit_channel<3>(r, e.emissive), e.fields |= PTH_MAT_EMISSIVE;
+            else if (field == "opacity") parse_edit_channel<1>(r, &e.opacity), e.fields |= PTH_MAT_OPACITY;
+            else if (field == "metalness") parse_edit_channel<1>(r, &e.metalness), e.fields |= PTH_MAT_METALNESS;
+            else if (field == "roughness") parse_edit_channel<1>(r, &e.roughness), e.fields |= PTH_MAT_ROUGHNESS;
+            else if (field == "ior") e.ior = r.f32(), e.fields |= PTH_MAT_IOR;
+            else if (field == "normal_texture") r.error("a material edit cannot change a texture (`normal_texture`)");
+            else r.error(("unknown field `" + field + "`, expected `albedo`, `emissive`, `opacity`, `metalness`, `roughness` or `ior`").c_str());
+        });
+        out.push_back(e);
+    });
+}
+
+// A keyframe file: a JSON array of frame objects with any of "camera" (an ISF camera), "lights" (an array of ISF lights:
+// all of them) and "materials" (edits of material factors by index), at least one frame.
+static void load_keyframes(const char* path, std::vector<Keyframe>& out) {
+    std::ifstream f(path, std::ios::binary);
+    if (!f) fail(PT_ERR_IO, "%s: %s", path, strerror(errno));
+    std::string text((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    JsonReader r(text.data(), text.data() + text.size());
+    if (r.peek() != '[') r.error("expected an array of keyframes");
+    r.expect('[');
+    if (r.peek() == ']') r.error("the keyframe file holds no frame");
+    do {
+        out.emplace_back();
+        Keyframe& k = out.back();
+        r.object([&](const std::string& key) {
+            if (key == "camera") {
+                parse_camera(r, k.camera);
+                k.has_camera = true;
+            } else if (key == "lights") {
+                k.lights.lights.clear();
+                r.expect('[');
+                if (!r.consume(']')) {
+                    do parse_light(r, k.lights);
+                    while (r.consume(','));
+                    r.expect(']');
+                }
+                k.has_lights = true;
+            } else if (key == "materials") {
+                parse_material_edits(r, k.materials);
+            } else {
+                r.error(("unknown field `" + key + "`, expected `camera`, `lights` or `materials`").c_str());
+            }
+        });
+    } while (r.consume(','));
+    r.expect(']');
+    r.end_of_input();
+}
+
+// The material table of `s` with the edits of one frame applied (fields left out keep their value; a texture keeps
+// multiplying its new factor); an index out of range is PT_ERR_INVALID.
+static std::vector<pt_material> edited_materials(const pth_scene& s, const pth_material_edit* edits, uint32_t n) {
+    std::vector<pt_material> m = s.materials;
+    for (uint32_t i = 0; i < n; ++i) {
+        const pth_material_edit& e = edits[i];
+        if (e.index >= m.size()) fail(PT_ERR_INVALID, "keyframe: material %u out of range (the scene has %zu)", e.index, m.size());
+        pt_material& t = m[e.index];
+        if (e.fields & PTH_MAT_ALBEDO) memcpy(t.albedo, e.albedo, 12);
+        if (e.fields & PTH_MAT_EMISSIVE) memcpy(t.emissive, e.emissive, 12);
+        if (e.fields & PTH_MAT_OPACITY) t.opacity = e.opacity;
+        if (e.fields & PTH_MAT_METALNESS) t.metalness = e.metalness;
+        if (e.fields & PTH_MAT_ROUGHNESS) t.roughness = e.roughness;
+        if (e.fields & PTH_MAT_IOR) t.ior = e.ior;
+    }
+    return m;
+}
+
 static void load_isf(const char* path, pth_scene& s) {
     std::ifstream f(path, std::ios::binary);
     if (!f) fail(PT_ERR_IO, "%s: %s", path, strerror(errno));
@@ -645,6 +773,81 @@ int pth_camera_path_load(const char* path, pt_camera** out, uint32_t* n) {
 }
 
 void pth_camera_path_free(pt_camera* cameras) { free(cameras); }
+
+int pth_scene_set_lights(pth_scene* s, const pt_light* lights, uint32_t n_lights) {
+    return pth::guarded([&] {
+        if (!s || (!lights && n_lights > 0)) pth::fail(PT_ERR_INVALID, "pth_scene_set_lights: null argument");
+        pth::check_lights(lights, n_lights);
+        s->lights.assign(lights, lights + n_lights);
+        s->finalize();
+    });
+}
+
+int pth_scene_set_materials(pth_scene* s, const pt_material* materials, uint32_t n_materials) {
+    return pth::guarded([&] {
+        if (!s || !materials) pth::fail(PT_ERR_INVALID, "pth_scene_set_materials: null argument");
+        if (n_materials != s->materials.size())
+            pth::fail(PT_ERR_INVALID, "pth_scene_set_materials: %u materials, the scene has %zu", n_materials, s->materials.size());
+        pth::check_materials(materials, n_materials, s->textures.data(), (uint32_t)s->textures.size(), s->texels.size());
+        s->materials.assign(materials, materials + n_materials);
+        s->finalize();
+    });
+}
+
+int pth_keyframes_load(const char* path, pth_keyframe** out, uint32_t* n) {
+    return pth::guarded([&] {
+        if (!path || !out || !n) pth::fail(PT_ERR_INVALID, "pth_keyframes_load: null argument");
+        std::vector<pth::Keyframe> frames;
+        pth::load_keyframes(path, frames);
+        if (frames.size() > 0xffffffffu) pth::fail(PT_ERR_INVALID, "%s: too many frames", path);
+        // one allocation: the frames, then every frame's lights, then every frame's material edits
+        size_t n_lights = 0, n_edits = 0;
+        for (const auto& k : frames) {
+            n_lights += k.lights.lights.size();
+            n_edits += k.materials.size();
+        }
+        const size_t bytes = frames.size() * sizeof(pth_keyframe) + n_lights * sizeof(pt_light) + n_edits * sizeof(pth_material_edit);
+        char* buf = (char*)calloc(1, bytes);
+        if (!buf) throw std::bad_alloc();
+        pth_keyframe* kf = (pth_keyframe*)buf;
+        pt_light* lp = (pt_light*)(buf + frames.size() * sizeof(pth_keyframe));
+        pth_material_edit* mp = (pth_material_edit*)((char*)lp + n_lights * sizeof(pt_light));
+        for (size_t i = 0; i < frames.size(); ++i) {
+            const pth::Keyframe& k = frames[i];
+            kf[i].has_camera = k.has_camera;
+            kf[i].camera = k.camera;
+            kf[i].has_lights = k.has_lights;
+            kf[i].n_lights = (uint32_t)k.lights.lights.size();
+            kf[i].lights = kf[i].n_lights ? lp : nullptr;
+            if (kf[i].n_lights) memcpy(lp, k.lights.lights.data(), kf[i].n_lights * sizeof(pt_light));
+            lp += kf[i].n_lights;
+            kf[i].n_materials = (uint32_t)k.materials.size();
+            kf[i].materials = kf[i].n_materials ? mp : nullptr;
+            if (kf[i].n_materials) memcpy(mp, k.materials.data(), kf[i].n_materials * sizeof(pth_material_edit));
+            mp += kf[i].n_materials;
+        }
+        *out = kf;
+        *n = (uint32_t)frames.size();
+    });
+}
+
+void pth_keyframes_free(pth_keyframe* frames) { free(frames); }
+
+int pth_keyframe_apply(pth_scene* s, const pth_keyframe* frame) {
+    return pth::guarded([&] {
+        if (!s || !frame) pth::fail(PT_ERR_INVALID, "pth_keyframe_apply: null argument");
+        if (frame->has_lights && !frame->lights && frame->n_lights > 0) pth::fail(PT_ERR_INVALID, "pth_keyframe_apply: null lights");
+        if (!frame->materials && frame->n_materials > 0) pth::fail(PT_ERR_INVALID, "pth_keyframe_apply: null material edits");
+        // every check first: a frame that fails changes nothing
+        std::vector<pt_material> mats = pth::edited_materials(*s, frame->materials, frame->n_materials);
+        pth::check_materials(mats.data(), (uint32_t)mats.size(), s->textures.data(), (uint32_t)s->textures.size(), s->texels.size());
+        if (frame->has_lights) pth::check_lights(frame->lights, frame->n_lights);
+        if (frame->has_camera) s->desc.camera = frame->camera;
+        if (frame->has_lights) s->lights.assign(frame->lights, frame->lights + frame->n_lights);
+        s->materials = std::move(mats);
+        s->finalize();
+    });
+}
 
 const pt_scene_desc* pth_scene_desc(const pth_scene* s) { return s ? &s->desc : nullptr; }
 

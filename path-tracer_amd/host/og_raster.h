@@ -49,6 +49,31 @@ OG_HD inline double oct_sin(int k) {
     return t[k];
 }
 
+// The extent of an orthographic grid (params_ortho): per grid axis the range of p . axis -+ r, per coordinate the range of
+// p -+ r, over every point whose length and radius are finite (a vertex: r = 0; a sphere: its centre, r = |radius|).  One
+// function for the host's scan and the device's reduction (csrc/pt_grid_build.h k_og_ortho_extent): both evaluate the same
+// terms in the same operand order.
+struct OrthoExtent {
+    double lo[3], hi[3], bmin[3], bmax[3];
+};
+OG_HD inline void ortho_extent_init(OrthoExtent& e) {
+    for (int k = 0; k < 3; ++k) {
+        e.lo[k] = e.bmin[k] = INFINITY;
+        e.hi[k] = e.bmax[k] = -INFINITY;
+    }
+}
+OG_HD inline void ortho_extent_grow(OrthoExtent& e, Vec u, Vec v, Vec w, Vec p, double r) {
+    if (!og_finite(len(p)) || !og_finite(r)) return;
+    const double c[3] = {dot(p, u), dot(p, v), dot(p, w)};
+    const double q[3] = {p.x, p.y, p.z};
+    for (int k = 0; k < 3; ++k) {
+        e.lo[k] = og_min(e.lo[k], c[k] - r);
+        e.hi[k] = og_max(e.hi[k], c[k] + r);
+        e.bmin[k] = og_min(e.bmin[k], q[k] - r);
+        e.bmax[k] = og_max(e.bmax[k], q[k] + r);
+    }
+}
+
 // Distance from the origin to triangle (a, b, c) (Ericson, Real-Time Collision Detection 5.1.5).
 OG_HD inline double origin_triangle_distance(Vec a, Vec b, Vec c) {
     const Vec p{0, 0, 0};
@@ -396,6 +421,10 @@ OG_HD inline void rasterize(const GridParams& P, const Footprint& fp, Emit&& emi
 bool og_params_point(const pt_scene_desc& d, const float origin[3], uint32_t res, float ray_offset, float max_dir_len,
                      og::GridParams& P, ::pth_origin_grid& g);
 bool og_params_ortho(const pt_scene_desc& d, const float direction[3], uint32_t res, og::GridParams& P, ::pth_origin_grid& g);
+// og_params_ortho in two halves (pt_scene_set_lights reduces the extent on the device): the grid's axes for `direction` (false:
+// no grid), and the parameters from an extent computed elsewhere with those axes; res must be given (> 0).
+bool og_ortho_axes(const float direction[3], og::GridParams& P);
+bool og_params_ortho_ext(const float direction[3], uint32_t res, const og::OrthoExtent& e, og::GridParams& P, ::pth_origin_grid& g);
 // The same as og_params_point for a scene extent `ext` computed elsewhere (og_point_extent, or the device's reduction over the
 // footprints: pt_scene_set_camera); res must be given (> 0).
 bool og_params_point_ext(const float origin[3], uint32_t res, float ray_offset, float max_dir_len, double ext, og::GridParams& P,

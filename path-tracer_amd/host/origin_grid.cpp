@@ -321,17 +321,11 @@ void build(const pt_scene_desc& d, const float origin[3], uint32_t res, float ra
     if (params_point(d, origin, res, ray_offset, max_dir_len, P, g)) fill_lists(d, P, g, t0);
 }
 
-bool params_ortho(const pt_scene_desc& d, const float direction[3], uint32_t res, GridParams& P, pth_origin_grid& g) {
-    memset(&g, 0, sizeof g);
-    g.kind = 1;
-    const uint64_t n_prims = pth_prim_count(&d);
-    if (res == 0) res = auto_resolution(n_prims);
-    if (res > 8192) fail(PT_ERR_INVALID, "origin grid: resolution %u too large", res);
-    g.res = res;
-    g.n_cells = (uint64_t)res * res;
+// The axes of an orthographic grid along `direction`, as the device will use them (f32 images); false: no grid.
+bool ortho_axes(const float direction[3], GridParams& P) {
     Vec w{direction[0], direction[1], direction[2]};
     const double wl = len(w);
-    if (!std::isfinite(wl) || !(wl > 0) || wl > 1e6) return false;   // enabled = 0
+    if (!std::isfinite(wl) || !(wl > 0) || wl > 1e6) return false;
     P = GridParams();
     P.ortho = true;
     P.ray_len = wl * (1.0 + 1e-6);
@@ -345,25 +339,40 @@ bool params_ortho(const pt_scene_desc& d, const float direction[3], uint32_t res
     P.axis_u = f32v(P.axis_u);
     P.axis_v = f32v(P.axis_v);
     P.axis_w = f32v(P.axis_w);
-    // bounds of the scene in (u, v) and its diameter
-    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    double bmin[3] = {INFINITY, INFINITY, INFINITY}, bmax[3] = {-INFINITY, -INFINITY, -INFINITY};
-    auto grow = [&](Vec p, double r) {
-        if (!std::isfinite(len(p)) || !std::isfinite(r)) return;
-        const double c[3] = {dot(p, P.axis_u), dot(p, P.axis_v), dot(p, P.axis_w)};
-        const double q[3] = {p.x, p.y, p.z};
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = std::min(lo[k], c[k] - r);
-            hi[k] = std::max(hi[k], c[k] + r);
-            bmin[k] = std::min(bmin[k], q[k] - r);
-            bmax[k] = std::max(bmax[k], q[k] + r);
-        }
-    };
+    return true;
+}
+
+// bounds of the scene in (u, v, w) and in x, y, z: every triangle vertex of the description and every sphere
+void ortho_extent(const pt_scene_desc& d, const GridParams& P, OrthoExtent& e) {
+    ortho_extent_init(e);
     for (uint64_t tr = 0; tr < d.n_triangles; ++tr)
-        for (int k = 0; k < 3; ++k) grow(Vec{d.triangles[tr * 24 + k * 8], d.triangles[tr * 24 + k * 8 + 1], d.triangles[tr * 24 + k * 8 + 2]}, 0.0);
+        for (int k = 0; k < 3; ++k)
+            ortho_extent_grow(e, P.axis_u, P.axis_v, P.axis_w,
+                              Vec{d.triangles[tr * 24 + k * 8], d.triangles[tr * 24 + k * 8 + 1], d.triangles[tr * 24 + k * 8 + 2]}, 0.0);
     for (uint32_t m = 0; m < d.n_models; ++m)
         if (d.models[m].kind == PT_MODEL_SPHERE)
-            grow(Vec{d.models[m].center[0], d.models[m].center[1], d.models[m].center[2]}, std::fabs((double)d.models[m].radius));
+            ortho_extent_grow(e, P.axis_u, P.axis_v, P.axis_w, Vec{d.models[m].center[0], d.models[m].center[1], d.models[m].center[2]},
+                              std::fabs((double)d.models[m].radius));
+}
+
+// The parameters of an orthographic grid from the scene's extent along its axes (ortho_extent, or the device's reduction).
+// `e` == nullptr: the scene is scanned here.
+bool params_ortho_from(const pt_scene_desc* d, const float direction[3], uint32_t res, const OrthoExtent* e_in, GridParams& P,
+                       pth_origin_grid& g) {
+    memset(&g, 0, sizeof g);
+    g.kind = 1;
+    if (res == 0) {
+        if (!d) fail(PT_ERR_INVALID, "origin grid: no resolution given");
+        res = auto_resolution(pth_prim_count(d));
+    }
+    if (res > 8192) fail(PT_ERR_INVALID, "origin grid: resolution %u too large", res);
+    g.res = res;
+    g.n_cells = (uint64_t)res * res;
+    if (!ortho_axes(direction, P)) return false;   // enabled = 0
+    OrthoExtent scanned;
+    if (!e_in) ortho_extent(*d, P, scanned);
+    const OrthoExtent& e = e_in ? *e_in : scanned;
+    const double *lo = e.lo, *hi = e.hi, *bmin = e.bmin, *bmax = e.bmax;
     if (!(hi[0] >= lo[0])) return false;   // nothing finite in the scene: enabled = 0
     const double diag = std::sqrt((bmax[0] - bmin[0]) * (bmax[0] - bmin[0]) + (bmax[1] - bmin[1]) * (bmax[1] - bmin[1]) +
                                   (bmax[2] - bmin[2]) * (bmax[2] - bmin[2]));
@@ -374,7 +383,7 @@ bool params_ortho(const pt_scene_desc& d, const float direction[3], uint32_t res
     P.v0 = lo[1] - 1.0 / P.cells_per_unit;
     P.base_margin = 0.125 + 8.0 * kEps32 * (std::fabs(lo[0]) + std::fabs(hi[0]) + std::fabs(lo[1]) + std::fabs(hi[1])) * P.cells_per_unit;
     P.max_margin = 128.0;
-    if (const char* e = getenv("PT_OG_MAX_MARGIN")) P.max_margin = std::max(0.5, atof(e));
+    if (const char* ev = getenv("PT_OG_MAX_MARGIN")) P.max_margin = std::max(0.5, atof(ev));
     P.max_dir_len = P.ray_len;
     P.ray_offset = 0.0;
     P.reach_max = diag * 1.01 + 1e-4;   // rays start on surfaces of the scene (+ normal * 1e-5)
@@ -392,6 +401,10 @@ bool params_ortho(const pt_scene_desc& d, const float direction[3], uint32_t res
     P.v0 = g.v0;
     P.cells_per_unit = g.cells_per_unit;
     return true;
+}
+
+bool params_ortho(const pt_scene_desc& d, const float direction[3], uint32_t res, GridParams& P, pth_origin_grid& g) {
+    return params_ortho_from(&d, direction, res, nullptr, P, g);
 }
 
 void build_ortho(const pt_scene_desc& d, const float direction[3], uint32_t res, pth_origin_grid& g) {
@@ -413,6 +426,10 @@ bool og_params_point_ext(const float origin[3], uint32_t res, float ray_offset, 
 double og_point_extent(const pt_scene_desc& d, const float origin[3]) { return point_extent(d, origin); }
 bool og_params_ortho(const pt_scene_desc& d, const float direction[3], uint32_t res, og::GridParams& P, pth_origin_grid& g) {
     return params_ortho(d, direction, res, P, g);
+}
+bool og_ortho_axes(const float direction[3], og::GridParams& P) { return ortho_axes(direction, P); }
+bool og_params_ortho_ext(const float direction[3], uint32_t res, const og::OrthoExtent& e, og::GridParams& P, pth_origin_grid& g) {
+    return params_ortho_from(nullptr, direction, res, &e, P, g);
 }
 }  // namespace pth
 

@@ -1,0 +1,359 @@
+"""pt_scene_set_lights / pt_scene_set_materials: a scene whose lights or materials were replaced renders exactly what a scene
+created from the edited description renders - images, accumulators, light and camera grids, debug planes, shards, the oracle
+- keeps its escape masks, and no state of the old lights or materials survives (frame plans, graphs)."""
+import ctypes as C
+import json
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ROOT = Path(__file__).resolve().parent.parent
+SCENES = ROOT / "tests" / "golden" / "scenes"
+EXE = ROOT / "path-tracer_amd" / "path-tracer"
+FLAG_SETS = (0, 4, 8)   # default, PT_FLAG_NO_GRIDS, PT_FLAG_MEGAKERNEL
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def same(a, b):
+    return np.array_equal(a[0], b[0]) and np.array_equal(bits(a[1]), bits(b[1]))
+
+
+def load(pta, name):
+    if name == "ps5":
+        return pta.HostScene.generate_ps5(30000, seed=1, flags=8)
+    return pta.HostScene.load_isf(SCENES / name / "scene.isf")
+
+
+def copy(pta, s):
+    return type(s).from_buffer_copy(bytes(C.string_at(C.addressof(s), C.sizeof(s))))
+
+
+def light(pta, kind, vec, color):
+    return pta.Light(kind, (C.c_float * 3)(*[float(v) for v in vec]), (C.c_float * 3)(*[float(v) for v in color]), 0.1)
+
+
+def scene_centre(host):
+    d = host.desc.contents
+    if d.n_triangles:
+        v = np.ctypeslib.as_array(d.triangles, (int(d.n_triangles) * 24,)).reshape(-1, 8)[:, :3]
+    else:
+        v = np.array([list(d.models[m].center) for m in range(d.n_models)], np.float64)
+    return 0.5 * (v.min(axis=0) + v.max(axis=0)), float(np.linalg.norm(v.max(axis=0) - v.min(axis=0)))
+
+
+def light_edits(pta, host):
+    """The edits of the tests, each a complete light list: a moved point light, a point light turned directional and a
+    directional one turned point, one light added, all lights removed, and a light whose grid a fresh scene rejects (a
+    directional light longer than 1e6: params_ortho gives up, every shadow ray takes the KD-tree)."""
+    base = host.lights
+    centre, size = scene_centre(host)
+    P, D = pta.PT_LIGHT_POINT, pta.PT_LIGHT_DIRECTIONAL
+    pi = next((i for i, l in enumerate(base) if l.kind == P), None)
+    di = next((i for i, l in enumerate(base) if l.kind == D), None)
+    out = {}
+    if pi is not None:
+        moved = [copy(pta, l) for l in base]
+        p = np.array(list(moved[pi].vec), np.float64)
+        q = centre + np.array([[0.8, 0.0, -0.6], [0.6, 0.0, 0.8], [0.0, 1.0, 0.0]]) @ (p - centre)   # (about the centre)
+        moved[pi] = light(pta, P, q, list(base[pi].color))
+        out["moved"] = moved
+        to_d = [copy(pta, l) for l in base]
+        d = centre - p
+        to_d[pi] = light(pta, D, d / np.linalg.norm(d), list(base[pi].color))
+        out["to_directional"] = to_d
+    if di is not None:
+        to_p = [copy(pta, l) for l in base]
+        to_p[di] = light(pta, P, centre - 0.75 * size * np.array(list(base[di].vec)), [3.0, 3.0, 3.0])
+        out["to_point"] = to_p
+    out["added"] = [copy(pta, l) for l in base] + [light(pta, P, centre + np.array([0.2, 0.6, 0.3]) * size, [2.0, 1.5, 1.0])]
+    out["none"] = []
+    out["rejected"] = [copy(pta, l) for l in base] + [light(pta, D, [0.0, -2e6, 1e5], [1e-12, 1e-12, 1e-12])]
+    return out
+
+
+def fresh(pta, name, lights=None, materials=None, **kw):
+    h = load(pta, name)
+    if lights is not None:
+        h.set_lights(lights)
+    if materials is not None:
+        h.set_materials(materials)
+    return h, pta.GpuScene(h, **kw)
+
+
+def profile(pta, name, spp=4):
+    return pta.Profile.make(160, 120, spp, 0 if name == "white_furnace_direct" else 3)
+
+
+@pytest.mark.parametrize("name", ["cube", "head", "reflection", "white_furnace_direct", "ps5"])
+def test_set_lights_equals_a_fresh_scene(pta, name):
+    prof = profile(pta, name)
+    host = load(pta, name)
+    g = pta.GpuScene(host)
+    for f in FLAG_SETS:   # (frames of the first lights: plans, masks, the cull table exist when the lights change)
+        g.render(prof, pta.Opts.make(flags=f))
+    g.render(prof)
+    edits = light_edits(pta, host)
+    assert {"added", "none", "rejected"} <= set(edits)
+    for label, lights in edits.items():
+        _, ref = fresh(pta, name, lights=lights)
+        g.set_lights(lights)
+        gi, ri = g.info(), ref.info()
+        assert (gi.light_grids, gi.grid_refs, gi.cam_grid_res) == (ri.light_grids, ri.grid_refs, ri.cam_grid_res), (name, label)
+        if label == "rejected":
+            assert ri.light_grids == 0
+        for f in FLAG_SETS:
+            got, want = g.render(prof, pta.Opts.make(flags=f)), ref.render(prof, pta.Opts.make(flags=f))
+            assert same(got, want), (name, label, f)
+        ref.close()
+
+
+def assert_grids_equal(a, b, what):
+    for k in ("res", "n_cells", "n_refs", "n_global", "enabled", "max_cell_refs", "kind", "u0", "v0", "cells_per_unit"):
+        assert getattr(a.c, k) == getattr(b.c, k), (what, k)
+    for k in ("origin", "axis_u", "axis_v", "axis_w"):
+        assert bits(np.array(list(getattr(a.c, k)), np.float32)).tolist() == bits(np.array(list(getattr(b.c, k)), np.float32)).tolist(), (what, k)
+    if a.enabled:
+        assert np.array_equal(a.cell_off, b.cell_off), what
+        assert np.array_equal(a.ref_prim[:a.n_refs], b.ref_prim[:b.n_refs]), what
+        assert np.array_equal(bits(a.ref_mindist[:a.n_refs]), bits(b.ref_mindist[:b.n_refs])), what
+
+
+@pytest.mark.parametrize("name", ["head", "ps5"])
+def test_light_grids_equal_a_fresh_scene_and_the_host_builder(pta, name):
+    host = load(pta, name)
+    g = pta.GpuScene(host)
+    for label, lights in light_edits(pta, host).items():
+        h2, ref = fresh(pta, name, lights=lights)
+        g.set_lights(lights)
+        assert g.info().light_grids == ref.info().light_grids and g.info().grid_refs == ref.info().grid_refs, label
+        assert_grids_equal(pta.OriginGrid.from_device(g, 0), pta.OriginGrid.from_device(ref, 0), (name, label, "camera"))
+        for i, l in enumerate(lights):
+            got, want = pta.OriginGrid.from_device(g, 1 + i), pta.OriginGrid.from_device(ref, 1 + i)
+            assert_grids_equal(got, want, (name, label, i))
+            if not want.enabled:
+                continue
+            if l.kind == pta.PT_LIGHT_POINT:
+                hg = pta.OriginGrid(h2, origin=list(l.vec), res=want.res, ray_offset=float(np.float32(1.05e-5) * np.float32(1.5)),
+                                    max_dir_len=1.001)
+            else:
+                hg = pta.OriginGrid(h2, direction=[float(np.float32(-1.0) * np.float32(v)) for v in l.vec], res=want.res)
+            assert_grids_equal(got, hg, (name, label, i, "host"))
+        # (no grid beyond the last light)
+        assert not pta.OriginGrid.from_device(g, 1 + len(lights)).enabled
+        ref.close()
+
+
+def material_edits(pta, name, host):
+    mats = [copy(pta, m) for m in host.materials]
+    if name == "cube":   # opaque -> translucent
+        mats[0].opacity = 0.5
+    elif name == "alpha_transparency":   # translucent -> opaque
+        for m in mats:
+            m.opacity, m.tex_opacity = 1.0, -1
+    else:   # emissive, roughness, metalness
+        mats[0].emissive[0], mats[0].emissive[1], mats[0].emissive[2] = 0.5, 0.25, 0.125
+        mats[-1].roughness, mats[-1].metalness = 0.15, 0.6
+    return mats
+
+
+@pytest.mark.parametrize("name", ["cube", "alpha_transparency", "reflection"])
+def test_set_materials_equals_a_fresh_scene(pta, name):
+    prof = profile(pta, name)
+    host = load(pta, name)
+    g = pta.GpuScene(host)
+    for f in FLAG_SETS:
+        g.render(prof, pta.Opts.make(flags=f))
+    was = g.info().has_translucent
+    mats = material_edits(pta, name, host)
+    _, ref = fresh(pta, name, materials=mats)
+    g.set_materials(mats)
+    assert g.info().has_translucent == ref.info().has_translucent
+    if name == "cube":
+        assert (was, g.info().has_translucent) == (0, 1)   # (the ALPHA variants run from here on)
+    if name == "alpha_transparency":
+        assert (was, g.info().has_translucent) == (1, 0)
+    for f in FLAG_SETS:
+        assert same(g.render(prof, pta.Opts.make(flags=f)), ref.render(prof, pta.Opts.make(flags=f))), (name, f)
+    d_got, d_want = g.debug_render(160, 120), ref.debug_render(160, 120)
+    assert d_got.keys() == d_want.keys() and all(np.array_equal(d_got[k], d_want[k]) for k in d_want)
+
+
+def test_escape_masks_untouched(pta):
+    host = load(pta, "head")
+    g = pta.GpuScene(host)
+    before = [np.asarray(m).view(np.uint8).copy() for m in g.escape_masks()]
+    g.set_lights(light_edits(pta, host)["added"])
+    g.set_materials(material_edits(pta, "head", host))
+    after = [np.asarray(m).view(np.uint8) for m in g.escape_masks()]
+    assert len(before) == len(after) and all(np.array_equal(u, v) for u, v in zip(before, after))
+    assert g.info().escape_prims > 0
+
+
+def test_no_stale_frame_plan(pta):
+    prof = pta.Profile.make(160, 120, 4, 4)
+    host = load(pta, "ps5")
+    lights_b = light_edits(pta, host)["added"]
+    mats_c = material_edits(pta, "ps5", host)
+    _, ref_b = fresh(pta, "ps5", lights=lights_b)
+    _, ref_c = fresh(pta, "ps5", lights=lights_b, materials=mats_c)
+    want_b, want_c = ref_b.render(prof), ref_c.render(prof)
+    g = pta.GpuScene(host)
+    for _ in range(3):
+        g.render(prof)
+    assert g.info().frame_planned == 1
+    g.set_lights(lights_b)
+    assert same(g.render(prof), want_b) and g.info().frame_planned == 0
+    for _ in range(2):
+        assert same(g.render(prof), want_b) and g.info().frame_planned == 1
+    g.set_materials(mats_c)
+    assert same(g.render(prof), want_c) and g.info().frame_planned == 0
+    for _ in range(2):
+        assert same(g.render(prof), want_c)
+
+
+def test_frame_in_flight_finishes_with_the_old_lights(pta):
+    import torch
+    prof = pta.Profile.make(160, 120, 8, 4)
+    host = load(pta, "head")
+    lights_b = light_edits(pta, host)["moved"]
+    _, ref_b = fresh(pta, "head", lights=lights_b)
+    want_a, want_b = pta.GpuScene(host).render(prof), ref_b.render(prof)
+    assert not same(want_a, want_b)
+    g = pta.GpuScene(host)
+    n = 160 * 120
+    outs = [(torch.empty(n * 3, dtype=torch.uint8, device="cuda"), torch.empty(n * 3, dtype=torch.float32, device="cuda")) for _ in range(2)]
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        g.render_device(prof, pta.Opts.make(), outs[0][0].data_ptr(), outs[0][1].data_ptr(), stream.cuda_stream)
+        g.set_lights(lights_b)   # (no synchronisation by the caller)
+        g.render_device(prof, pta.Opts.make(), outs[1][0].data_ptr(), outs[1][1].data_ptr(), stream.cuda_stream)
+    stream.synchronize()
+    for (rgb, acc), want in zip(outs, (want_a, want_b)):
+        assert same((rgb.cpu().numpy().reshape(-1, 3), acc.cpu().numpy().reshape(-1, 3)), want)
+
+
+def test_edited_scene_matches_the_oracle(pta, oracle):
+    prof = pta.Profile.make(160, 120, 8, 3)
+    host = load(pta, "head")
+    lights = light_edits(pta, host)["to_point"]
+    mats = material_edits(pta, "head", host)
+    g = pta.GpuScene(host)
+    g.render(prof)
+    g.set_lights(lights)
+    g.set_materials(mats)
+    rgb, acc = g.render(prof)
+    h2 = load(pta, "head")
+    h2.set_lights(lights)
+    h2.set_materials(mats)
+    o = oracle.OracleScene(h2.desc, oracle.PTO_BRUTE_FORCE)
+    for row in (40, 77):
+        o_rgb, o_acc, _ = o.render(prof, row * 160, (row + 1) * 160)
+        assert np.array_equal(rgb[row * 160:(row + 1) * 160], o_rgb)
+        assert np.array_equal(bits(acc[row * 160:(row + 1) * 160]), bits(o_acc))
+
+
+def test_errors_change_nothing(pta):
+    prof = pta.Profile.make(160, 120, 4, 3)
+    host = load(pta, "head")
+    g = pta.GpuScene(host)
+    want = g.render(prof)
+    mats = host.materials
+    bad_tex = [copy(pta, m) for m in mats]
+    bad_tex[0].tex_albedo = host.desc.contents.n_textures
+    bad_chan = [copy(pta, m) for m in mats]
+    bad_chan[0].tex_albedo = mats[0].tex_opacity   # (1 channel where 3 are demanded)
+    bad_kind = [copy(pta, l) for l in host.lights]
+    bad_kind[0].kind = 5
+    calls = [lambda: g.set_lights(None, n=1), lambda: g.set_lights(bad_kind), lambda: g.set_materials(mats + mats),
+             lambda: g.set_materials(None, n=len(mats)), lambda: g.set_materials(bad_tex), lambda: g.set_materials(bad_chan)]
+    for i, call in enumerate(calls):
+        with pytest.raises(pta.PtError) as e:
+            call()
+        assert e.value.code == pta.PT_ERR_INVALID, i
+        assert same(g.render(prof), want), i
+
+
+def test_shards_and_prep_after_edits(pta):
+    prof = pta.Profile.make(160, 120, 4, 3)
+    host = load(pta, "head")
+    edits = light_edits(pta, host)
+    lights_a, lights_b = edits["to_point"], edits["added"]
+    mats_b = material_edits(pta, "head", host)
+    _, ref_a = fresh(pta, "head", lights=lights_a)
+    _, ref_b = fresh(pta, "head", lights=lights_b, materials=mats_b)
+    want_a, want_b = ref_a.render(prof), ref_b.render(prof)
+    # three shards of a live edited scene
+    g = pta.GpuScene(host)
+    g.render(prof)
+    g.set_lights(lights_b)
+    g.set_materials(mats_b)
+    rgb = np.zeros((160 * 120, 3), np.uint8)
+    acc = np.zeros((160 * 120, 3), np.float32)
+    for r in range(3):
+        o = pta.Opts.make(shard_rank=r, shard_count=3, tile_w=32, tile_h=32)
+        pr, pa = g.render(prof, o)
+        m = pta.local_pixel_map(prof, o)
+        rgb[m], acc[m] = pr, pa
+    assert same((rgb, acc), want_b)
+    # two scenes of one prep, edited differently after the prep is gone
+    prep = pta.Prep(host)
+    s_a, s_b = [pta.GpuScene(host, prep=prep) for _ in range(2)]
+    prep.close()
+    s_a.set_lights(lights_a)
+    s_b.set_lights(lights_b)
+    s_b.set_materials(mats_b)
+    assert same(s_a.render(prof), want_a)
+    assert same(s_b.render(prof), want_b)
+
+
+def test_cli_keyframes(pta, tmp_path):
+    from PIL import Image
+    scene_path = SCENES / "head" / "scene.isf"
+    host = load(pta, "head")
+    cam = json.loads(scene_path.read_text())["camera"]
+    cam["transform"][3][0] += 0.3
+    frames = [{"camera": cam},
+              {"lights": [{"type": "Point", "position": [2.0, 3.0, 2.5], "color": [30.0, 25.0, 20.0], "size": 0.1},
+                          {"type": "Directional", "direction": [0.2, -1.0, -0.3], "color": [1.5, 1.5, 1.5]}]},
+              {"materials": {"0": {"albedo": {"factor": [0.9, 0.5, 0.3]}}}}]
+    path = tmp_path / "frames.json"
+    path.write_text(json.dumps(frames))
+    prof = tmp_path / "p.yml"
+    prof.write_text("resolution:\n  width: 96\n  height: 64\nsamples: 4\nbounces: 2\n")
+    want = []
+    h = load(pta, "head")
+    for k in pta.load_keyframes(path):   # (each state as a fresh scene of the edited description)
+        h.apply_keyframe(k)
+        s = pta.GpuScene(h)
+        want.append(s.render(pta.Profile.make(96, 64, 4, 2))[0])
+        s.close()
+    assert not np.array_equal(want[0], want[1]) and not np.array_equal(want[1], want[2])
+    for sub, extra in (("one", []), ("two", ["--devices", "0,0"])):
+        out = tmp_path / sub
+        out.mkdir()
+        r = subprocess.run([str(EXE), "render", str(scene_path), "-q", "-p", str(prof), "--keyframes", str(path),
+                            "-o", str(out / "frame_%02d.png"), *extra], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr
+        assert sorted(p.name for p in out.iterdir()) == [f"frame_{i:02d}.png" for i in range(3)]
+        for i in range(3):
+            assert np.array_equal(np.asarray(Image.open(out / f"frame_{i:02d}.png")).reshape(-1, 3), want[i]), (sub, i)
+    # a bad file and --keyframes with --camera-path: exit code 2, no image
+    bad = tmp_path / "bad.json"
+    bad.write_text('[{"materials": {"7": {"ior": 1.5}}}]')
+    cams = tmp_path / "cams.json"
+    cams.write_text(json.dumps([cam]))
+    for sub, args in (("bad", ["--keyframes", str(bad)]), ("both", ["--keyframes", str(path), "--camera-path", str(cams)])):
+        out = tmp_path / sub
+        out.mkdir()
+        r = subprocess.run([str(EXE), "render", str(scene_path), "-q", "-p", str(prof), *args, "-o", str(out / "f_%d.png")],
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 2, (sub, r.stderr)
+        assert not list(out.iterdir())
+    assert host.n_lights == 2

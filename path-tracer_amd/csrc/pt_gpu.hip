@@ -32,6 +32,7 @@
 #include <mutex>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -215,7 +216,7 @@ __global__ __launch_bounds__(256) void k_assemble(const uint8_t* __restrict__ ga
     for (uint32_t b = 0; b < elem_bytes; ++b) d[b] = s[b];
 }
 
-// The counts of one chunk, gathered into one line of the frame's statistics (render_device, frame plan).
+// The counts of one chunk, gathered into one line of the frame's statistics (frame_plan, render_chunk).
 __global__ void k_wf_stats(const WfCounters* __restrict__ ctr, uint32_t levels, uint32_t* __restrict__ out) {
     const uint32_t b = threadIdx.x;
     if (b >= levels) return;
@@ -525,9 +526,9 @@ struct pt_scene {
         uint64_t refs = 0, bytes = 0;
         float seconds = 0.f;
     } built;
-    mutable pt_timing timing{};
-    mutable pt_counters counters{};
-    mutable DeviceBuffer accum_scratch, counter_buf, staging_buf;
+    pt_timing timing{};
+    pt_counters counters{};
+    DeviceBuffer accum_scratch, counter_buf, staging_buf;
     // The queues of the chunk of work items in flight.  The shadow casts of bounce b run on a side stream
     // beside the trace of bounce b+1, so the tail of one persistent launch is filled by the other's head.
     struct WfPipe {
@@ -536,11 +537,11 @@ struct pt_scene {
         hipEvent_t ev_shade = nullptr, ev_shadow = nullptr, ev_rng = nullptr, ev_chunk = nullptr, ev_trace = nullptr, ev_wide = nullptr,
                    ev_exact = nullptr, ev_exact_go = nullptr;
     };
-    mutable WfPipe pipe;
+    WfPipe pipe;
     // What a frame of one configuration produced: records per queue and bounce, per chunk of work items.  A frame is a pure
     // function of (scene, profile, options) - the seeds are the pixels' - so the counts of one frame are those of every later
     // one: the FIRST frame of a configuration runs in chunks small enough for a fixed budget with every queue as long as the
-    // chunk, the later ones get queues as long as the records that exist (render_device, "frame plan").
+    // chunk, the later ones get queues as long as the records that exist (frame_plan).
     struct FrameStats {
         uint32_t cap_items = 0, n_slots = 0, levels = 0;   // the chunking the numbers were taken with; (batch, chunk) slots; bounces + 2
         uint32_t* host = nullptr;                         // pinned: n_slots x levels x 4 words (queue, shadow, exact, offgrid | overflow)
@@ -559,35 +560,32 @@ struct pt_scene {
             if (done) (void)hipEventDestroy(done);
         }
     };
-    mutable std::map<std::vector<uint64_t>, std::unique_ptr<FrameStats>> frame_stats;
-    mutable DeviceBuffer stats_dev;
-    mutable uint64_t queue_bytes_last = 0;   // bytes of the path queues of the last frame (pt_scene_get_info)
-    mutable uint32_t queue_chunk_last = 0, frame_planned_last = 0;
+    // What earlier frames left that an edit of the scene invalidates (drop_frame_state): the counts of every configuration
+    // (a plan sized from another camera's, light's or material's counts may overflow) and the size of the last frame's
+    // camera-grid cull table
+    struct FrameState {
+        std::map<std::vector<uint64_t>, std::unique_ptr<FrameStats>> stats;
+        uint32_t mask_blocks = 0;   // blocks of the last frame's camera-grid cull table (0: no cull in that frame)
+    } frame_state;
+    DeviceBuffer stats_dev;
+    uint64_t queue_bytes_last = 0;   // bytes of the path queues of the last frame (pt_scene_get_info)
+    uint32_t queue_chunk_last = 0, frame_planned_last = 0;
     // escape masks: wanted (PT_ESCAPE), built when the scene has rendered `escape_after` frames of the default pipeline
     bool escape_wanted = false, escape_tried = false;
     uint32_t escape_after = 2;
     float escape_delta = 0.f;   // the delta_in the masks were built with (pt_scene_set_camera keeps them while a camera needs no more)
-    mutable uint32_t frames_rendered = 0;
-    mutable int trace_blocks = 0, shadow_blocks = 0, n_cu = 0;
-    // (experiment, pt_scene_set_cu_mask: the scene's own streams confined to these CUs, grids sized for their number)
-    std::vector<uint32_t> cu_mask;
-    mutable uint32_t last_mask_blocks = 0;   // blocks of the last frame's camera-grid cull table (0: no cull in that frame)
-    mutable uint32_t wf_cap_ok = 0;   // largest queue capacity the device provided so far (0: not tried)
+    uint32_t frames_rendered = 0;
+    int trace_blocks = 0, shadow_blocks = 0, n_cu = 0;
+    uint32_t wf_cap_ok = 0;   // largest queue capacity the device provided so far (0: not tried)
     // tile tables of the sharded renders, one per configuration (image size, rank, count, tile size) and never rewritten:
     // pt_render_device is asynchronous, two calls for different ranks may be in flight on the caller's streams at once
     typedef std::tuple<uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t> TileKey;
-    mutable std::map<TileKey, std::unique_ptr<DeviceBuffer>> tile_tables;
-    mutable std::vector<hipEvent_t> events;
-    // One frame's launches as an instantiated hipGraph, per configuration (profile, options, output and queue addresses):
-    // the ~35 launches, memsets and cross-stream waits of a frame are captured once and replayed with ONE hipGraphLaunch
-    mutable std::map<std::vector<uint64_t>, hipGraphExec_t> graphs;
-    mutable hipStream_t capture_stream = nullptr;
+    std::map<TileKey, std::unique_ptr<DeviceBuffer>> tile_tables;
+    std::vector<hipEvent_t> events;
 
     ~pt_scene() {
         (void)hipSetDevice(device);
-        frame_stats.clear();
-        for (auto& g : graphs) (void)hipGraphExecDestroy(g.second);
-        if (capture_stream) (void)hipStreamDestroy(capture_stream);
+        frame_state.stats.clear();
         for (void* p : allocations) (void)hipFree(p);
         for (hipEvent_t e : events) (void)hipEventDestroy(e);
         for (hipEvent_t e : {pipe.ev_shade, pipe.ev_shadow, pipe.ev_rng, pipe.ev_chunk, pipe.ev_trace, pipe.ev_wide, pipe.ev_exact, pipe.ev_exact_go})
@@ -1393,7 +1391,7 @@ void escape_masks_build(pt_scene& s) {
     }
     s.info.escape_build_seconds = std::chrono::duration<float>(std::chrono::steady_clock::now() - t_esc).count();
     // the counts of the frames rendered so far are upper bounds now (the masks end paths): the next frame counts again
-    for (auto& kv : s.frame_stats) {
+    for (auto& kv : s.frame_state.stats) {
         pt_scene::FrameStats& f = *kv.second;
         f.pending = f.valid = f.planned = f.plan_failed = false;
     }
@@ -1644,14 +1642,8 @@ bool camera_grid_build(pt_scene& s, EditFootprints& F, const float* M, uint32_t 
     return built;
 }
 
-// What earlier frames left: their counts (a plan sized from another camera's, light's or material's counts may overflow),
-// the captured graphs (they hold the old DevScene as kernel arguments), the cull table of the last frame.
-void drop_frame_state(pt_scene& s) {
-    s.frame_stats.clear();
-    for (auto& g : s.graphs) (void)hipGraphExecDestroy(g.second);
-    s.graphs.clear();
-    s.last_mask_blocks = 0;
-}
+// What earlier frames left (pt_scene::FrameState).
+void drop_frame_state(pt_scene& s) { s.frame_state = pt_scene::FrameState{}; }
 
 void scene_set_camera(pt_scene& s, const pt_camera& cam) {
     HIP_CHECK(hipSetDevice(s.device));
@@ -1859,7 +1851,7 @@ void scene_set_materials(pt_scene& s, const pt_material* materials, uint32_t n) 
     drop_frame_state(s);
 }
 
-hipEvent_t get_event(const pt_scene& s, size_t i) {
+hipEvent_t get_event(pt_scene& s, size_t i) {
     while (s.events.size() <= i) {
         hipEvent_t e;
         HIP_CHECK(hipEventCreate(&e));
@@ -1868,98 +1860,256 @@ hipEvent_t get_event(const pt_scene& s, size_t i) {
     return s.events[i];
 }
 
-#ifndef PT_GRAPH_DEFAULT
-// PT_GRAPH=1: frames replayed from a captured hipGraph (render_device).  Measured (MI355X, ROCm 7.2; config 3): a whole
-// frame 34.47 -> 34.40 ms, one shard of eight 5.49 -> 5.60 ms - the replay of the ~35 nodes on three streams is no faster
-// than their launches (the host is 30 frames ahead of the device either way; the 7 us between dependent kernels stay): off.
-#define PT_GRAPH_DEFAULT false
-#endif
-void render_device(const pt_scene& s, const pt_profile& p, const pt_opts* opts_in, void* d_rgb8, void* d_accum,
-                   hipStream_t stream, bool allow_preview = false) {
-    pt_opts o;
+// ------------------------------------------------------------------ render options
+// The render path's environment knobs (runtime knobs).  One parser per type: unset or empty gives the default.
+double env_num(const char* e, double def) { return e && *e ? atof(e) : def; }
+int env_int(const char* e, int def) { return e && *e ? atoi(e) : def; }
+bool env_bool(const char* e, bool def) { return e && *e ? atoi(e) != 0 : def; }
+
+// Read once per process (render_env).
+struct RenderEnv {
+    // PT_TILE_ORDER=morton: the wavefront integrator visits the local tiles along a Z curve over the tile grid instead of row by row
+    bool morton;
+    uint64_t staging_bytes;   // PT_STAGING_GIB: staging budget (radiance 12 B + RNG block 64 B per work item [+ queues]); 32 GiB of 288 GB
+    // PT_WF_CHUNK: the most work items one pass over the bounces may take, whatever the budgets of the frame plan allow
+    // (every extra chunk repeats the ~13 persistent launches and their drain phases: 60.9 ms against 63.0 ms for two chunks
+    // of 128 Mi - round 2)
+    uint32_t wf_chunk;
+    bool overlap;   // PT_WF_OVERLAP: shadow(b) on a side stream beside trace(b+1); 0 serialises
+    // PT_WF_REFILL: idle lanes that trigger a refill of a persistent wavefront.  Round 3, after the split shade pass and the
+    // slack change (config 3, trace stage): 2 / 4 / 6 / 8 / 12 / 16 / 24 / 32 -> 13.36 / 13.31 / 13.32 / 13.31 / 13.41 /
+    // 13.57 / 13.98 / 14.63 ms (16 was round 1's optimum)
+    uint32_t refill;
+    // PT_WF_WALK: node steps per walking phase; 0 = default: 20 for the coherent camera rays (bounce 0 on the KD-tree), 16
+    // for the incoherent rays of the later bounces (render_chunk)
+    uint32_t walk;
+    // PT_WF_SPLIT: the shade pass of bounces >= 1 runs beside k_wf_trace_wide (trace_stage).  Measured (MI355X, config 3;
+    // profiles/r03_experiments.txt item 6): frame 34.26 -> 34.14 ms, one shard of eight 5.85 -> 5.69 ms - the two kernels
+    // slow each other down (beside the 4 workgroups per CU of k_wf_trace_wide a SIMD has registers for one shade wavefront
+    // instead of four), so only part of the shorter one is hidden.
+    bool split;
+    // PT_WF_EXACT (clamped to 0..2): k_wf_trace / k_wf_shadow hand the rays their walker's slack does not cover to
+    // k_wf_trace_exact / k_og_shadow_offgrid (csrc/pt_integrator.h, slop model).  0 is for A/B measurements of what that
+    // costs only: the capped walk.  1: k_wf_trace lists them when it fetches them, k_wf_trace_exact runs behind it (beside
+    // the shade pass over the queue); 2: k_wf_shade lists them when it makes the rays, k_wf_trace_exact runs beside k_wf_trace.
+    uint32_t exact;
+    uint32_t exact_blocks;   // PT_WF_EXACT_BLOCKS: workgroups per 8 CUs of k_wf_trace_exact beside k_wf_trace (PT_WF_EXACT=2)
+    uint32_t defer;          // PT_WF_DEFER: k_wf_trace: age (loop iterations) at which a cast leaves a drained wavefront
+    // PT_WF_SORT: coherence sorting of the survivors by direction octant: measured (MI355X, config 3) trace of bounce 1
+    // 9.50 -> 9.25 ms, but the bounce-0 kernel 19.0 -> 20.2 ms: off by default
+    uint32_t sort;
+    // PT_WF_ENTRY=1: casts of bounces >= 1 start at the home node of the primitive their ray leaves (trav_enter).
+    // Measured (profiles/r03_experiments.txt item 2): 31 % fewer node visits, the same time - off by default
+    uint32_t entry;
+    uint32_t refill_shadow, walk_shadow;   // PT_WF_REFILL_SHADOW, PT_WF_WALK_SHADOW: k_wf_shadow's (0: k_wf_trace's)
+    bool side_priority;   // PT_WF_SIDE_PRIORITY=0: the streams of k_wf_trace_wide and k_wf_trace_exact at default priority
+    // PT_SHADE_BLOCKS_B0, PT_SHADE_BLOCKS: k_wf_shade's workgroups per CU in the grid.  The kernel's loops are grid-stride,
+    // but a grid of just the resident workgroups (3 per CU) keeps the whole chip on ONE window of the image at a time -
+    // everybody in the ChaCha-bound background together, then everybody waiting for casts into the model together.  Many
+    // more workgroups than are resident, each with a short loop, mix the two (and balance the end): bounce-0 kernel of
+    // config 3, 3 / 16 / 64 / 256 / 1024 / 4096 workgroups per CU: 20.9 / 17.3 / 16.1 / 15.5 / 15.4 / 16.4 ms; the later
+    // bounces (queues of unknown, shrinking length: every extra workgroup is a dispatch that may find nothing) are best at 32
+    // (16 / 32 / 64 / 128: frame 37.6 / 36.2 / 36.2 / 36.2 ms, one shard of eight 5.97 / 5.92 / 6.03 / 6.13 ms).
+    uint32_t shade_blocks_b0, shade_blocks;
+    bool fuse_rng;   // PT_OG_FUSE_RNG: the fused bounce-0 kernel computes the ChaCha block itself (GRID 3)
+    // PT_OG_INLINE_ALL: shadow casts inside the shade kernel at every bounce (bounces >= 1 otherwise keep the shade kernel
+    // lean and cast their shadow rays in k_og_shadow: measured faster)
+    bool inline_all;
+    // PT_OG_INLINE_AUTO: ... and at the bounces where the frame plan found (nearly) every ray reaching a lit surface
+    // (PT_OG_INLINE_ALL=1 in the closed room: +6.6 %; in an open scene: -6 %)
+    bool inline_auto;
+    uint32_t ogs_blocks;   // PT_OGS_BLOCKS: workgroups per CU of k_og_shadow's grid-stride launch
+    bool plan_skip;        // PT_PLAN_SKIP=0: the bounces behind a chunk's last ray are launched too
+    bool cam_cull;         // PT_CAM_CULL=0: no camera-grid cull (camera_cull)
+    bool plan_debug;       // PT_PLAN_DEBUG: the frame plan on stderr when it is made
+    bool debug_times, debug_hist, debug_stamps;   // PT_DEBUG_TIMES, PT_DEBUG_HIST, PT_DEBUG_STAMPS: set (even empty) = on
+};
+
+const RenderEnv& render_env() {
+    static const RenderEnv env = [] {
+        RenderEnv r;
+        const char* order = getenv("PT_TILE_ORDER");
+        r.morton = order && !strcmp(order, "morton");
+        r.staging_bytes = (uint64_t)(env_num(getenv("PT_STAGING_GIB"), 32.0) * 1024.0 * 1024.0 * 1024.0);
+        r.wf_chunk = (uint32_t)env_num(getenv("PT_WF_CHUNK"), 320.0 * 1024 * 1024);
+        r.overlap = env_bool(getenv("PT_WF_OVERLAP"), true);
+        r.refill = (uint32_t)env_int(getenv("PT_WF_REFILL"), 8);
+        r.walk = (uint32_t)env_int(getenv("PT_WF_WALK"), 0);
+        r.split = env_bool(getenv("PT_WF_SPLIT"), true);
+        r.exact = (uint32_t)std::min(2, std::max(0, env_int(getenv("PT_WF_EXACT"), 1)));
+        r.exact_blocks = (uint32_t)env_int(getenv("PT_WF_EXACT_BLOCKS"), 4);
+        r.defer = (uint32_t)env_int(getenv("PT_WF_DEFER"), 16);
+        r.sort = (uint32_t)env_int(getenv("PT_WF_SORT"), 0);
+        r.entry = env_bool(getenv("PT_WF_ENTRY"), false) ? 1u : 0u;
+        r.refill_shadow = (uint32_t)env_int(getenv("PT_WF_REFILL_SHADOW"), 0);
+        r.walk_shadow = (uint32_t)env_int(getenv("PT_WF_WALK_SHADOW"), 12);
+        r.side_priority = env_bool(getenv("PT_WF_SIDE_PRIORITY"), true);
+        r.shade_blocks_b0 = (uint32_t)env_int(getenv("PT_SHADE_BLOCKS_B0"), 256);
+        r.shade_blocks = (uint32_t)env_int(getenv("PT_SHADE_BLOCKS"), 32);
+        r.fuse_rng = env_bool(getenv("PT_OG_FUSE_RNG"), true);
+        r.inline_all = env_int(getenv("PT_OG_INLINE_ALL"), 0) != 0;
+        r.inline_auto = env_bool(getenv("PT_OG_INLINE_AUTO"), true);
+        r.ogs_blocks = (uint32_t)env_int(getenv("PT_OGS_BLOCKS"), 16);
+        r.plan_skip = env_bool(getenv("PT_PLAN_SKIP"), true);
+        r.cam_cull = env_bool(getenv("PT_CAM_CULL"), true);
+        r.plan_debug = env_bool(getenv("PT_PLAN_DEBUG"), false);
+        r.debug_times = getenv("PT_DEBUG_TIMES") != nullptr;
+        r.debug_hist = getenv("PT_DEBUG_HIST") != nullptr;
+        r.debug_stamps = getenv("PT_DEBUG_STAMPS") != nullptr;
+        return r;
+    }();
+    return env;
+}
+
+// The frame plan's budgets, read per call: tests/test_frame_plan.py and tools/stress_paths.py change them between frames
+// of one scene.  First frame 8 GiB: what the CLI pays for in allocation time (path-tracer render of the 500 k-triangle
+// scene, 1080p x 128 spp, render_s with 2 / 4 / 8 / 16 / 64 GiB: 0.121 / 0.095 / 0.080 / 0.136-0.29 / 1.69 s - the frame
+// itself is 0.04-0.05 s).  Later frames: what their records need, up to 32 GiB - config 3 takes 14.1 GiB (one pass), the
+// closed room 31.4 GiB in 2 passes (170.2 ms in 5 passes of 12.7 GiB, 165.8 in 2, 164.5 in one of 51.7 GiB), the KD-tree
+// pipeline of config 3 29.7 GiB.
+struct QueueEnv {
+    double first_gib;      // PT_QUEUE_GIB
+    double steady_gib;     // PT_QUEUE_STEADY_GIB (default: the larger of PT_QUEUE_GIB and 32)
+    // PT_QUEUE_ONE_PASS_GIB: a batch that fits it as ONE chunk takes it (every extra pass repeats the persistent launches
+    // and their drains - the KD-tree pipeline of config 3, 29.7 GiB in one pass: 62.4 ms, in three passes of 16 GiB 75.3 ms)
+    double one_pass_gib;
+    // PT_QUEUE_RESERVE_GIB: what the queues must leave free (the runtime allocates the kernels' scratch - up to 592 B per
+    // lane of every wave slot of the device, per hardware queue: ~1.2 GB - when they are first launched, and dies if it cannot)
+    double reserve_gib;
+    double test_shrink;    // PT_PLAN_TEST_SHRINK, clamped to 0.01..1 (0: unset)
+};
+
+QueueEnv queue_env() {
+    QueueEnv q;
+    q.first_gib = env_num(getenv("PT_QUEUE_GIB"), 8.0);
+    q.steady_gib = env_num(getenv("PT_QUEUE_STEADY_GIB"), std::max(q.first_gib, 32.0));
+    q.one_pass_gib = env_num(getenv("PT_QUEUE_ONE_PASS_GIB"), 32.0);
+    q.reserve_gib = env_num(getenv("PT_QUEUE_RESERVE_GIB"), 2.0);
+    const char* shrink = getenv("PT_PLAN_TEST_SHRINK");
+    q.test_shrink = shrink && *shrink ? std::min(1.0, std::max(0.01, atof(shrink))) : 0.0;
+    return q;
+}
+
+// ------------------------------------------------------------------ one frame (render_device and its stages)
+// Runtime switches to template arguments: fn(std::integral_constant<bool, b>...) for the values b of `on`, in order.
+template <class F>
+void dispatch(F&& fn) {
+    fn();
+}
+template <class F, class... B>
+void dispatch(F&& fn, bool on, B... rest) {
+    if (on) dispatch([&](auto... t) { fn(std::true_type{}, t...); }, rest...);
+    else dispatch([&](auto... t) { fn(std::false_type{}, t...); }, rest...);
+}
+
+// What frame_setup derives from the profile, the options and the scene.
+struct Frame {
+    const RenderEnv& env = render_env();
+    pt_profile p{};
+    pt_opts o{};
+    TileMap tm;
+    DevScene dev{};   // the scene as this frame's kernels see it
+    const uint32_t* d_tiles = nullptr;
+    float* accum = nullptr;
+    RenderParams P{};
+    bool timing = false, counting = false, exit_times = false;
+    DevCounters* gctr = nullptr;   // (counting or exit_times)
+    bool wavefront = true;         // the integrator: wavefront (default), or the one-lane-per-pixel megakernel
+    bool use_cam_grid = false, use_light_grids = false, alpha = false;
+    // bounce 0 as ONE kernel (k_wf_shade<GRID >= 2>: camera cast through the camera grid, shadow casts through the light grids).
+    // The camera-grid cull belongs to that kernel: its mask is computed, its wavefronts skip empty blocks and k_accumulate
+    // adds the background for their pixels under this one condition (round-3 advisory: three places derived it separately).
+    bool bounce0_fused = false;
+    uint32_t blocks64 = 0;   // 8x8 pixel blocks of the local tiles
+    uint32_t batch = 0;      // samples per pass over the image
+};
+
+// The tile table of a sharded or Morton-ordered frame (cached per configuration: no host sync in steady state): the packed
+// offset of every local tile, their global tile numbers (tile_k_base), then - PT_TILE_ORDER=morton - the order in which
+// the wavefront integrator visits the local tiles
+const uint32_t* tile_table(pt_scene& s, const pt_profile& p, const pt_opts& o, const TileMap& tm, bool morton) {
+    auto key = std::make_tuple(p.width, p.height, o.shard_rank, o.shard_count, o.tile_w, o.tile_h);
+    auto found = s.tile_tables.find(key);
+    if (found == s.tile_tables.end()) {
+        if (s.tile_tables.size() >= 256) {   // (a caller cycling through hundreds of configurations: start over, idle)
+            HIP_CHECK(hipDeviceSynchronize());
+            s.tile_tables.clear();
+        }
+        std::vector<uint32_t> table(tm.offsets);
+        table.insert(table.end(), tm.tiles.begin(), tm.tiles.end());
+        if (morton) {
+            auto spread = [](uint32_t v) {   // bits of v to the even positions
+                uint64_t x = v;
+                x = (x | (x << 16)) & 0x0000ffff0000ffffull;
+                x = (x | (x << 8)) & 0x00ff00ff00ff00ffull;
+                x = (x | (x << 4)) & 0x0f0f0f0f0f0f0f0full;
+                x = (x | (x << 2)) & 0x3333333333333333ull;
+                x = (x | (x << 1)) & 0x5555555555555555ull;
+                return x;
+            };
+            std::vector<std::pair<uint64_t, uint32_t>> order(tm.n_local_tiles);
+            for (uint32_t lt = 0; lt < tm.n_local_tiles; ++lt) {
+                const uint32_t k = tm.tiles[lt];
+                order[lt] = {spread(k % tm.tiles_x) | (spread(k / tm.tiles_x) << 1), lt};
+            }
+            std::sort(order.begin(), order.end());
+            for (auto& e : order) table.push_back(e.second);
+        }
+        auto buf = std::make_unique<DeviceBuffer>();
+        buf->ensure(table.size() * 4);
+        HIP_CHECK(hipMemcpy(buf->p, table.data(), table.size() * 4, hipMemcpyHostToDevice));   // (a fresh buffer: nobody reads it yet)
+        found = s.tile_tables.emplace(key, std::move(buf)).first;
+    }
+    return (const uint32_t*)found->second->p;
+}
+
+// Validation, the tile map, the escape masks, the counters, RenderParams, the pipeline, the sample batch and its staging
+// area.  false: this rank has no pixels.
+bool frame_setup(pt_scene& s, const pt_profile& p, const pt_opts* opts_in, void* d_accum, hipStream_t stream, Frame& f) {
+    pt_opts& o = f.o;
     normalise_opts(p, opts_in, o);
     if (p.samples == 0) fail(PT_ERR_INVALID, "profile.samples must be > 0");
     if (p.brdf != PT_BRDF_COOK_TORRANCE) fail(PT_ERR_INVALID, "unknown brdf %d", p.brdf);
     if (p.tonemap < 0 || p.tonemap > 2) fail(PT_ERR_INVALID, "unknown tonemap %d", p.tonemap);
     HIP_CHECK(hipSetDevice(s.device));
-    TileMap tm = make_tile_map(p, o, o.shard_rank);
-    if (tm.n_local == 0) return;
+    f.p = p;
+    f.tm = make_tile_map(p, o, o.shard_rank);
+    const TileMap& tm = f.tm;
+    if (tm.n_local == 0) return false;
     // escape masks: from the scene's (escape_after + 1)th frame of the default pipeline on (scene_upload has the reason)
     if (s.escape_wanted && !s.escape_tried && !(o.flags & (PT_FLAG_NO_GRIDS | PT_FLAG_MEGAKERNEL))) {
-        if (s.frames_rendered >= s.escape_after) escape_masks_build(const_cast<pt_scene&>(s));
+        if (s.frames_rendered >= s.escape_after) escape_masks_build(s);
         ++s.frames_rendered;
     }
-    // the scene as the kernels of THIS frame see it: the KD-tree pipeline (PT_FLAG_NO_GRIDS) - the cross-check of the parity
-    // tests - knows no escape masks either
-    DevScene dev = s.dev;
-    if (o.flags & PT_FLAG_NO_GRIDS) dev.escape = nullptr;
-
-    // tile tables (cached per configuration: no host sync in steady state): the packed offset of every local tile
-    // (sharded renders), then - PT_TILE_ORDER=morton - the order in which the wavefront integrator visits the local
-    // tiles: along a Z curve over the tile grid instead of row by row
-    static const bool morton = [] {
-        const char* e = getenv("PT_TILE_ORDER");
-        return e && !strcmp(e, "morton");
-    }();
-    const uint32_t* d_tiles = nullptr;
+    // the KD-tree pipeline (PT_FLAG_NO_GRIDS) - the cross-check of the parity tests - knows no escape masks either
+    f.dev = s.dev;
+    if (o.flags & PT_FLAG_NO_GRIDS) f.dev.escape = nullptr;
     uint32_t tile_order_base = 0, tile_k_base = 0;
-    if (o.shard_count > 1 || morton) {
-        auto key = std::make_tuple(p.width, p.height, o.shard_rank, o.shard_count, o.tile_w, o.tile_h);
-        auto found = s.tile_tables.find(key);
-        if (found == s.tile_tables.end()) {
-            if (s.tile_tables.size() >= 256) {   // (a caller cycling through hundreds of configurations: start over, idle)
-                HIP_CHECK(hipDeviceSynchronize());
-                s.tile_tables.clear();
-            }
-            std::vector<uint32_t> table(tm.offsets);
-            table.insert(table.end(), tm.tiles.begin(), tm.tiles.end());   // global tile numbers (tile_k_base)
-            if (morton) {
-                auto spread = [](uint32_t v) {   // bits of v to the even positions
-                    uint64_t x = v;
-                    x = (x | (x << 16)) & 0x0000ffff0000ffffull;
-                    x = (x | (x << 8)) & 0x00ff00ff00ff00ffull;
-                    x = (x | (x << 4)) & 0x0f0f0f0f0f0f0f0full;
-                    x = (x | (x << 2)) & 0x3333333333333333ull;
-                    x = (x | (x << 1)) & 0x5555555555555555ull;
-                    return x;
-                };
-                std::vector<std::pair<uint64_t, uint32_t>> order(tm.n_local_tiles);
-                for (uint32_t lt = 0; lt < tm.n_local_tiles; ++lt) {
-                    const uint32_t k = tm.tiles[lt];
-                    order[lt] = {spread(k % tm.tiles_x) | (spread(k / tm.tiles_x) << 1), lt};
-                }
-                std::sort(order.begin(), order.end());
-                for (auto& e : order) table.push_back(e.second);
-            }
-            auto buf = std::make_unique<DeviceBuffer>();
-            buf->ensure(table.size() * 4);
-            HIP_CHECK(hipMemcpy(buf->p, table.data(), table.size() * 4, hipMemcpyHostToDevice));   // (a fresh buffer: nobody reads it yet)
-            found = s.tile_tables.emplace(key, std::move(buf)).first;
-        }
-        d_tiles = (const uint32_t*)found->second->p;
+    if (o.shard_count > 1 || f.env.morton) {
+        f.d_tiles = tile_table(s, p, o, tm, f.env.morton);
         tile_k_base = (uint32_t)tm.offsets.size();
-        if (morton) tile_order_base = (uint32_t)(tm.offsets.size() + tm.tiles.size());
+        if (f.env.morton) tile_order_base = (uint32_t)(tm.offsets.size() + tm.tiles.size());
     }
-    float* accum = (float*)d_accum;
-    if (!accum) {
+    f.accum = (float*)d_accum;
+    if (!f.accum) {
         s.accum_scratch.ensure(tm.n_local * 12);
-        accum = (float*)s.accum_scratch.p;
+        f.accum = (float*)s.accum_scratch.p;
     }
-    const bool timing = o.flags & PT_FLAG_TIMING, counting = o.flags & PT_FLAG_COUNTERS;
+    f.timing = o.flags & PT_FLAG_TIMING;
+    f.counting = o.flags & PT_FLAG_COUNTERS;
 #ifdef WF_EXIT_TIMES
-    const bool exit_times = true;    // diagnostic build: the stamps are taken by the plain (non-counting) kernels too
-#else
-    const bool exit_times = false;
+    f.exit_times = true;    // diagnostic build: the stamps are taken by the plain (non-counting) kernels too
 #endif
-    if (counting || exit_times) {
+    if (f.counting || f.exit_times) {
         s.counter_buf.ensure(sizeof(DevCounters));
         HIP_CHECK(hipMemsetAsync(s.counter_buf.p, 0, sizeof(DevCounters), stream));
 #ifdef WF_EXIT_TIMES
         HIP_CHECK(hipMemsetAsync(&((DevCounters*)s.counter_buf.p)->launch_start, 0xff, sizeof(((DevCounters*)nullptr)->launch_start), stream));
 #endif
+        f.gctr = (DevCounters*)s.counter_buf.p;
     }
 
-    RenderParams P{};
+    RenderParams& P = f.P;
     P.width = p.width;
     P.height = p.height;
     P.samples = p.samples;
@@ -1978,966 +2128,704 @@ void render_device(const pt_scene& s, const pt_profile& p, const pt_opts* opts_i
     pt_fastdiv_make(o.tile_w >> 3, P.div_tile_cols);
     pt_fastdiv_make(tm.tiles_x, P.div_tiles_x);
 
-    // ---- integrator selection: wavefront (default, mode 2), or the one-lane-per-pixel megakernel (mode 0)
-    const int mode = (o.flags & PT_FLAG_MEGAKERNEL) ? 0 : 2;
+    f.wavefront = !(o.flags & PT_FLAG_MEGAKERNEL);
     // the 16-bit draw index / bounce fields of the queue records, the per-bounce counter table
     if (p.bounces > 4096u) fail(PT_ERR_INVALID, "profile.bounces %u is out of range (at most 4096)", p.bounces);
-    const bool use_cam_grid = !(o.flags & PT_FLAG_NO_GRIDS) && s.dev.cam_grid.res != 0;
-    const bool use_light_grids = !(o.flags & PT_FLAG_NO_GRIDS) && s.dev.all_lights_gridded != 0;
-    // bounce 0 as ONE kernel (k_wf_shade<GRID >= 2>: camera cast through the camera grid, shadow casts through the light grids).
-    // The camera-grid cull belongs to that kernel: its mask is computed, its wavefronts skip empty blocks and k_accumulate
-    // adds the background for their pixels under this one condition (round-3 advisory: three places derived it separately).
-    const bool bounce0_fused = use_cam_grid && use_light_grids;
-    const uint32_t blocks64 = tm.n_local_tiles * (o.tile_w / 8u) * (o.tile_h / 8u);
-    // staging budget (radiance 12 B + RNG block 64 B per work item [+ queues]); default 32 GiB of 288 GB
-    static const uint64_t budget = [] {
-        const char* e = getenv("PT_STAGING_GIB");
-        return (uint64_t)((e && *e ? atof(e) : 32.0) * 1024.0 * 1024.0 * 1024.0);
-    }();
-    static const uint32_t wf_cap = [] {
-        const char* e = getenv("PT_WF_CHUNK");
-        // the most work items one pass over the bounces may take, whatever the budgets of the frame plan below allow
-        // (every extra chunk repeats the ~13 persistent launches and their drain phases: 60.9 ms against 63.0 ms for
-        // two chunks of 128 Mi - round 2)
-        return (uint32_t)(e && *e ? atof(e) : 320.0 * 1024 * 1024);
-    }();
-    static const bool wf_overlap = [] {    // shadow(b) on a side stream beside trace(b+1); PT_WF_OVERLAP=0 serialises
-        const char* e = getenv("PT_WF_OVERLAP");
-        return e && *e ? atoi(e) != 0 : true;
-    }();
-    static const uint32_t wf_refill = [] {
-        // idle lanes that trigger a refill of a persistent wavefront.  Round 3, after the split shade pass and the slack
-        // change (config 3, trace stage): 2 / 4 / 6 / 8 / 12 / 16 / 24 / 32 -> 13.36 / 13.31 / 13.32 / 13.31 / 13.41 / 13.57 /
-        // 13.98 / 14.63 ms (16 was round 1's optimum)
-        const char* e = getenv("PT_WF_REFILL");
-        return (uint32_t)(e && *e ? atoi(e) : 8);
-    }();
-    static const uint32_t wf_walk = [] {
-        const char* e = getenv("PT_WF_WALK");
-        // 0 = default: 20 for the coherent camera rays (bounce 0 on the KD-tree), 12 for the incoherent rays of the
-        // later bounces (7.9 against 8.2 ms per 64 spp, MI355X, config 3)
-        return (uint32_t)(e && *e ? atoi(e) : 0);
-    }();
-    // The shade pass of bounces >= 1 runs beside k_wf_trace_wide (see the launch below).  Measured (MI355X, config 3;
-    // profiles/r03_experiments.txt item 6): frame 34.26 -> 34.14 ms, one shard of eight 5.85 -> 5.69 ms - the two kernels
-    // slow each other down (beside the 4 workgroups per CU of k_wf_trace_wide a SIMD has registers for one shade wavefront
-    // instead of four), so only part of the shorter one is hidden.
-    static const bool wf_split = [] {
-        const char* e = getenv("PT_WF_SPLIT");
-        return e && *e ? atoi(e) != 0 : true;
-    }();
-    static const bool wf_allwide = [] {   // experiment: every cast of the bounces >= 1 of an opaque scene through k_wf_trace_wide
-        const char* e = getenv("PT_WF_ALLWIDE");
-        return e && *e ? atoi(e) != 0 : false;
-    }();
-    // k_wf_trace / k_wf_shadow hand the rays their walker's slack does not cover to k_wf_trace_exact / k_og_shadow_offgrid
-    // (csrc/pt_integrator.h, slop model).  PT_WF_EXACT=0 is for A/B measurements of what that costs only: the capped walk.
-    // 1: k_wf_trace lists them when it fetches them, k_wf_trace_exact runs behind it (beside the shade pass over the queue);
-    // 2: k_wf_shade lists them when it makes the rays, k_wf_trace_exact runs beside k_wf_trace.
-    static const uint32_t wf_exact = [] {
-        const char* e = getenv("PT_WF_EXACT");
-        return (uint32_t)(e && *e ? std::min(2, std::max(0, atoi(e))) : 1);
-    }();
-    static const uint32_t wf_defer = [] {   // k_wf_trace: age (loop iterations) at which a cast leaves a drained wavefront
-        const char* e = getenv("PT_WF_DEFER");
-        return (uint32_t)(e && *e ? atoi(e) : 16);
-    }();
-    // k_wf_shade: workgroups per CU in the grid.  The kernel's loops are grid-stride, but a grid of just the resident
-    // workgroups (3 per CU) keeps the whole chip on ONE window of the image at a time - everybody in the ChaCha-bound
-    // background together, then everybody waiting for casts into the model together.  Many more workgroups than are
-    // resident, each with a short loop, mix the two (and balance the end): bounce-0 kernel of config 3, 3 / 16 / 64 /
-    // 256 / 1024 / 4096 workgroups per CU: 20.9 / 17.3 / 16.1 / 15.5 / 15.4 / 16.4 ms; the later bounces (queues of
-    // unknown, shrinking length: every extra workgroup is a dispatch that may find nothing) are best at 32
-    // (16 / 32 / 64 / 128: frame 37.6 / 36.2 / 36.2 / 36.2 ms, one shard of eight 5.97 / 5.92 / 6.03 / 6.13 ms).
-    static const uint32_t shade_blocks_b0 = [] {
-        const char* e = getenv("PT_SHADE_BLOCKS_B0");
-        return (uint32_t)(e && *e ? atoi(e) : 256);
-    }();
-    static const uint32_t shade_blocks_later = [] {
-        const char* e = getenv("PT_SHADE_BLOCKS");
-        return (uint32_t)(e && *e ? atoi(e) : 32);
-    }();
-    static const uint32_t wf_refill_shadow = [] {
-        const char* e = getenv("PT_WF_REFILL_SHADOW");
-        return (uint32_t)(e && *e ? atoi(e) : 0);
-    }();
-    static const uint32_t wf_walk_shadow = [] {
-        const char* e = getenv("PT_WF_WALK_SHADOW");
-        return (uint32_t)(e && *e ? atoi(e) : 12);
-    }();
-    if (s.n_cu == 0) {
-        HIP_CHECK(hipDeviceGetAttribute(&s.n_cu, hipDeviceAttributeMultiprocessorCount, s.device));
-        if (!s.cu_mask.empty()) {
-            int bits = 0;
-            for (uint32_t w : s.cu_mask) bits += __builtin_popcount(w);
-            s.n_cu = std::max(1, std::min(s.n_cu, bits));
-        }
-    }
-    auto side_stream = [&s](hipStream_t* st, int priority) {
-        if (!s.cu_mask.empty()) HIP_CHECK(hipExtStreamCreateWithCUMask(st, (uint32_t)s.cu_mask.size(), s.cu_mask.data()));
-        else HIP_CHECK(hipStreamCreateWithPriority(st, hipStreamNonBlocking, priority));
-    };
-    uint32_t batch = o.sample_batch ? o.sample_batch : p.samples;
-    const bool alpha = s.dev.has_translucent != 0;
-    if (mode >= 1) {
+    f.use_cam_grid = !(o.flags & PT_FLAG_NO_GRIDS) && s.dev.cam_grid.res != 0;
+    f.use_light_grids = !(o.flags & PT_FLAG_NO_GRIDS) && s.dev.all_lights_gridded != 0;
+    f.bounce0_fused = f.use_cam_grid && f.use_light_grids;
+    f.blocks64 = tm.n_local_tiles * (o.tile_w / 8u) * (o.tile_h / 8u);
+    if (s.n_cu == 0) HIP_CHECK(hipDeviceGetAttribute(&s.n_cu, hipDeviceAttributeMultiprocessorCount, s.device));
+    f.batch = o.sample_batch ? o.sample_batch : p.samples;
+    f.alpha = s.dev.has_translucent != 0;
+    if (f.wavefront) {
         uint64_t per_sample = tm.n_local * 12u;
-        uint64_t max_batch = std::max<uint64_t>(1, budget / std::max<uint64_t>(1, per_sample));
-        max_batch = std::min<uint64_t>(max_batch, 0x7fffffffull / ((uint64_t)blocks64 * 64u));
+        uint64_t max_batch = std::max<uint64_t>(1, f.env.staging_bytes / std::max<uint64_t>(1, per_sample));
+        max_batch = std::min<uint64_t>(max_batch, 0x7fffffffull / ((uint64_t)f.blocks64 * 64u));
         if (max_batch == 0) fail(PT_ERR_UNSUPPORTED, "image too large for one sample batch");
-        batch = (uint32_t)std::min<uint64_t>(batch, max_batch);
-        s.staging_buf.ensure((size_t)batch * tm.n_local * 12);
+        f.batch = (uint32_t)std::min<uint64_t>(f.batch, max_batch);
+        s.staging_buf.ensure((size_t)f.batch * tm.n_local * 12);
     }
-    uint32_t cap = 0;
-    // capacities (records) of what is indexed by a queue position: the two path queues, the hit records (+ the alpha walk's draw
-    // counts), the shadow records (+ contrib planes, off-grid list), the exact lists
+    return true;
+}
+
+// The wavefront integrator's chunking and queues for one frame.
+struct WfFrame {
+    pt_scene::FrameStats* fs = nullptr;   // the statistics (and plan) of this frame's configuration
+    uint64_t items_per_batch = 0;         // work items of a whole sample batch
+    uint32_t max_items = 0;               // the most work items of one chunk (PT_WF_CHUNK)
+    size_t lights = 1;
+    bool rng_one_plane = false;   // the fused bounce-0 kernel keeps words 0-3 of the items' ChaCha blocks in registers
+    uint64_t per_item = 0;        // bytes per work item when nothing is known (every queue as long as the chunk)
+    uint32_t cap_a = 0;           // the chunk of the first frame: what fits the first-frame budget
+    uint32_t cap = 0;             // work items per chunk
+    // capacities (records) of what is indexed by a queue position: the two path queues, the hit records (+ the alpha walk's
+    // draw counts), the shadow records (+ contrib planes, off-grid list), the exact lists
     uint32_t cap_q[2] = {0, 0}, cap_h = 0, cap_s = 0, cap_e = 0;
-    std::vector<uint8_t> inline_at(p.bounces + 2, 0);   // bounces >= 1 whose shadow casts run inside the shade kernel
-    pt_scene::FrameStats* fs = nullptr;
-    bool multi_chunk = false, rng_one_plane = false, skip_dead = false;
-    uint32_t stats_slots = 0;
-    if (mode == 2) {
-        uint64_t items_per_batch = (uint64_t)blocks64 * 64u * batch;
-        if (s.trace_blocks == 0) {
-            int a = 0, b = 0, c = 0, d = 0;
-            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_wf_trace<false, false, false>, WF_THREADS, 0));
-            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_wf_trace<true, false, false>, WF_THREADS, 0));
-            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&c, k_wf_shadow<false, false>, WF_THREADS, 0));
-            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&d, k_wf_shadow<true, false>, WF_THREADS, 0));
-            s.trace_blocks = std::max(1, alpha ? b : a) * s.n_cu;
-            s.shadow_blocks = std::max(1, alpha ? d : c) * s.n_cu;
-            if (const char* e = getenv("PT_WF_BLOCKS_PER_CU")) {  // experiments: fewer resident workgroups
-                int k = atoi(e);
-                if (k > 0) {
-                    s.trace_blocks = std::min(s.trace_blocks, k * s.n_cu);
-                    s.shadow_blocks = std::min(s.shadow_blocks, k * s.n_cu);
+    std::vector<uint8_t> inline_at;   // bounces >= 1 whose shadow casts run inside the shade kernel
+    bool planned = false;             // the capacities are the plan's (false: a first frame's)
+    bool multi_chunk = false;
+    uint32_t stats_slots = 0;   // lines of this frame's statistics (0: none taken)
+    // per chunk of the plan: the last bounce that has a ray (later ones are not launched); nullptr: every bounce
+    const std::vector<uint32_t>* plan_last = nullptr;
+    const uint32_t* block_empty = nullptr;     // the camera-grid cull table (nullptr: no cull in this frame)
+    uint32_t stats_line = 0, chunk_slot = 0;   // the frame's progress through its chunks
+};
+
+// Counts per (batch, chunk of fs.cap_items items) -> the plan: m consecutive chunks become one, every buffer as long as the
+// largest group's counts need; the largest m whose buffers fit the steady budget
+bool make_plan(pt_scene::FrameStats& fs, const Frame& f, const WfFrame& wf, const QueueEnv& qe) {
+    const uint32_t ca = fs.cap_items, lv = fs.levels;
+    const uint64_t items_per_batch = wf.items_per_batch;
+    std::vector<std::vector<uint32_t>> batches;   // slots of each batch, in order
+    for (uint32_t k = 0; k < fs.n_slots; ++k) {
+        if (fs.first_item_of_slot[k] == 0u) batches.emplace_back();
+        if (batches.empty()) return false;
+        batches.back().push_back(k);
+    }
+    if (batches.empty() || ca == 0) return false;
+    uint32_t m_max = 1;
+    for (auto& bt : batches) m_max = std::max<uint32_t>(m_max, (uint32_t)bt.size());
+    // (PT_WF_CHUNK caps a chunk; a batch that may be one chunk needs no multiple of ca)
+    m_max = std::min<uint32_t>(m_max, (uint64_t)wf.max_items >= items_per_batch ? (uint32_t)((items_per_batch + ca - 1u) / ca) : std::max(1u, wf.max_items / ca));
+    // by the number of passes over a batch: m = the fewest first-frame chunks per pass that make that many passes, so the
+    // passes come out even (nine chunks in three passes: 3 + 3 + 3, not 4 + 4 + 1 at a third more memory)
+    uint32_t s_max = 1;
+    for (auto& bt : batches) s_max = std::max<uint32_t>(s_max, (uint32_t)bt.size());
+    uint32_t m_prev = 0;
+    for (uint32_t n_pass = 1; n_pass <= s_max; ++n_pass) {
+        const uint32_t m = (s_max + n_pass - 1u) / n_pass;
+        if (m > m_max || m == m_prev) continue;
+        m_prev = m;
+        uint64_t q1 = 0, q0 = 0, hh = 0, ss = 0, ee = 0;
+        std::vector<uint64_t> tot_q(lv, 0), tot_s(lv, 0);
+        std::vector<uint32_t> last;
+        for (auto& bt : batches)
+            for (size_t g0 = 0; g0 < bt.size(); g0 += m) {
+                last.push_back(0u);
+                for (uint32_t b = 0; b < lv; ++b) {
+                    uint64_t nq = 0, ns = 0, ne = 0;
+                    for (size_t k = g0; k < std::min(bt.size(), g0 + m); ++k) {
+                        const uint32_t* row = fs.host + ((size_t)bt[k] * lv + b) * 4;
+                        nq += row[0];
+                        ns += row[1];
+                        ne += row[2];
+                    }
+                    tot_q[b] += nq;
+                    tot_s[b] += ns;
+                    if (b >= 1 && nq != 0) last.back() = b;
+                    if (b >= 1) {   // (queue b lives in queue[b & 1]; the hits of its casts by queue position)
+                        uint64_t& q = (b & 1u) ? q1 : q0;
+                        q = std::max(q, nq);
+                        hh = std::max(hh, nq);
+                    }
+                    ss = std::max(ss, ns);
+                    ee = std::max(ee, ne);
                 }
             }
-        }
-        pt_scene::WfPipe& w = s.pipe;
-        const uint32_t levels = p.bounces + 3;
-        w.ctr.ensure(sizeof(WfCounters) * levels);
-        const size_t lights = std::max(1u, s.dev.n_lights);
-        static const bool fuse_rng_env = [] {
-            const char* e = getenv("PT_OG_FUSE_RNG");
-            return e && *e ? atoi(e) != 0 : true;
-        }();
-        // (the fused bounce-0 kernel keeps words 0-3 of the items' ChaCha blocks in registers: one 16-byte plane per item)
-        rng_one_plane = fuse_rng_env && bounce0_fused;
-        // ---- The frame plan.  Bytes per work item when nothing is known (every queue as long as the chunk): two path queues of
-        // 64 B (+ the entry word), 20 B hit, 64 B shadow record + 16 B per light, the RNG plane(s), draws, off-grid and exact lists.
-        const uint64_t per_item = 68u * 2u + 20u + 64u + 16u * lights + (rng_one_plane ? 16u : 32u) + (alpha ? 4u : 0u) + 4u + 16u;
-        // (read per frame: the tests change them)
-        // First frame 8 GiB: what the CLI pays for in allocation time (path-tracer render of the 500 k-triangle scene, 1080p x 128 spp,
-        // render_s with 2 / 4 / 8 / 16 / 64 GiB: 0.121 / 0.095 / 0.080 / 0.136-0.29 / 1.69 s - the frame itself is 0.04-0.05 s).
-        // Later frames: what their records need, up to 32 GiB - config 3 takes 14.1 GiB (one pass), the closed room 31.4 GiB in 2
-        // passes (170.2 ms in 5 passes of 12.7 GiB, 165.8 in 2, 164.5 in one of 51.7 GiB), the KD-tree pipeline of config 3 29.7 GiB.
-        const double first_gib = [] { const char* e = getenv("PT_QUEUE_GIB"); return e && *e ? atof(e) : 8.0; }();
-        const double one_pass_gib = [] { const char* e = getenv("PT_QUEUE_ONE_PASS_GIB"); return e && *e ? atof(e) : 32.0; }();
-        const double steady_gib = [first_gib] { const char* e = getenv("PT_QUEUE_STEADY_GIB"); return e && *e ? atof(e) : std::max(first_gib, 32.0); }();
-        static const bool skip_dead_env = [] { const char* e = getenv("PT_PLAN_SKIP"); return !(e && *e && atoi(e) == 0); }();
-        skip_dead = skip_dead_env;
-        static const bool inline_auto = [] { const char* e = getenv("PT_OG_INLINE_AUTO"); return !(e && *e && atoi(e) == 0); }();
-        const uint32_t max_items = (uint32_t)std::min<uint64_t>(items_per_batch, std::max<uint32_t>(64u, wf_cap & ~63u));
-        std::vector<uint64_t> stat_key = {p.width, p.height, p.samples, p.bounces, (uint64_t)p.brdf,
-                                          o.flags & (PT_FLAG_NO_GRIDS | PT_FLAG_MEGAKERNEL | PT_FLAG_COUNTERS), (uint64_t)bounce0_fused, o.shard_rank, o.shard_count, o.tile_w, o.tile_h, batch, (uint64_t)max_items};
-        static const bool graphs_on = [] {   // (frames replayed from a captured graph keep the first frame's chunking: no plan)
-            const char* e = getenv("PT_GRAPH");
-            return e && *e ? atoi(e) != 0 : PT_GRAPH_DEFAULT;
-        }();
-        // the chunk of the first frame: what fits the first-frame budget
-        uint32_t cap_a = (uint32_t)std::min<uint64_t>(max_items, std::max<uint64_t>(1u << 20, (uint64_t)(first_gib * 1073741824.0) / per_item) & ~63ull);
-        if (s.wf_cap_ok) cap_a = std::min(cap_a, s.wf_cap_ok);
-        // counts per (batch, chunk of fs->cap_items items) -> the plan: m consecutive chunks become one, every buffer as long as
-        // the largest group's counts need; the largest m whose buffers fit the steady budget
-        auto make_plan = [&](pt_scene::FrameStats& f) {
-            const uint32_t ca = f.cap_items, lv = f.levels;
-            std::vector<std::vector<uint32_t>> batches;   // slots of each batch, in order
-            for (uint32_t k = 0; k < f.n_slots; ++k) {
-                if (f.first_item_of_slot[k] == 0u) batches.emplace_back();
-                if (batches.empty()) return false;
-                batches.back().push_back(k);
+        const uint64_t items = std::min<uint64_t>((uint64_t)ca * m, items_per_batch);
+        if (!f.bounce0_fused) hh = std::max(hh, items);   // the casts of bounce 0 too: hits and draw counts by work item
+        auto pad = [](uint64_t n) { return (std::max<uint64_t>(n, 1024) + 1023) & ~1023ull; };
+        q0 = pad(q0), q1 = pad(q1), hh = pad(hh), ss = pad(ss), ee = pad(ee);
+        const uint64_t bytes = 68u * (q0 + q1) + 20u * hh + (f.alpha ? 4u * hh : 0u) + (64u + 16u * wf.lights + 4u) * ss + 16u * ee +
+                               (wf.rng_one_plane ? 16u : (f.env.overlap && items < items_per_batch) ? 64u : 32u) * items;   // (two copies: the next chunk's are made ahead)
+        const bool fits = bytes <= (uint64_t)(qe.steady_gib * 1073741824.0) ||
+                          (items >= items_per_batch && bytes <= (uint64_t)(qe.one_pass_gib * 1073741824.0));
+        if ((fits || m == 1) && std::max({q0, q1, hh, ss, ee, items}) < 0xffffffffull) {
+            fs.plan_cap = (uint32_t)items;
+            fs.plan_q[0] = (uint32_t)q0;
+            fs.plan_q[1] = (uint32_t)q1;
+            fs.plan_h = (uint32_t)hh;
+            fs.plan_s = (uint32_t)ss;
+            fs.plan_e = (uint32_t)ee;
+            // shadow casts inside the shade kernel where (nearly) every ray of a bounce reaches a lit surface
+            fs.plan_inline.assign(f.p.bounces + 2, 0);
+            if (f.env.inline_auto && f.use_light_grids)
+                for (uint32_t b = 1; b < lv && b < fs.plan_inline.size(); ++b) fs.plan_inline[b] = tot_q[b] > 0 && tot_s[b] * 10 >= tot_q[b] * 6;
+            fs.plan_last = last;
+            fs.plan_fresh = true;
+            if (f.env.plan_debug) {
+                fprintf(stderr, "[ptgpu] frame plan: %u chunks of %u -> 1 of %llu items; queues %llu / %llu, hits %llu, shadow %llu, exact %llu records; %.3f GiB\n",
+                        m, ca, (unsigned long long)items, (unsigned long long)q0, (unsigned long long)q1, (unsigned long long)hh,
+                        (unsigned long long)ss, (unsigned long long)ee, bytes / 1073741824.0);
+                for (uint32_t b = 0; b < lv; ++b)
+                    fprintf(stderr, "[ptgpu]   bounce %u: %llu rays, %llu shadow records%s\n", b, (unsigned long long)tot_q[b],
+                            (unsigned long long)tot_s[b], b < fs.plan_inline.size() && fs.plan_inline[b] ? " (inline)" : "");
             }
-            if (batches.empty() || ca == 0) return false;
-            uint32_t m_max = 1;
-            for (auto& bt : batches) m_max = std::max<uint32_t>(m_max, (uint32_t)bt.size());
-            // (PT_WF_CHUNK caps a chunk; a batch that may be one chunk needs no multiple of ca)
-            m_max = std::min<uint32_t>(m_max, (uint64_t)max_items >= items_per_batch ? (uint32_t)((items_per_batch + ca - 1u) / ca) : std::max(1u, max_items / ca));
-            // by the number of passes over a batch: m = the fewest first-frame chunks per pass that make that many passes, so the
-            // passes come out even (nine chunks in three passes: 3 + 3 + 3, not 4 + 4 + 1 at a third more memory)
-            uint32_t s_max = 1;
-            for (auto& bt : batches) s_max = std::max<uint32_t>(s_max, (uint32_t)bt.size());
-            uint32_t m_prev = 0;
-            for (uint32_t n_pass = 1; n_pass <= s_max; ++n_pass) {
-                const uint32_t m = (s_max + n_pass - 1u) / n_pass;
-                if (m > m_max || m == m_prev) continue;
-                m_prev = m;
-                uint64_t q1 = 0, q0 = 0, hh = 0, ss = 0, ee = 0;
-                std::vector<uint64_t> tot_q(lv, 0), tot_s(lv, 0);
-                std::vector<uint32_t> last;
-                for (auto& bt : batches)
-                    for (size_t g0 = 0; g0 < bt.size(); g0 += m) {
-                        last.push_back(0u);
-                        for (uint32_t b = 0; b < lv; ++b) {
-                            uint64_t nq = 0, ns = 0, ne = 0;
-                            for (size_t k = g0; k < std::min(bt.size(), g0 + m); ++k) {
-                                const uint32_t* row = f.host + ((size_t)bt[k] * lv + b) * 4;
-                                nq += row[0];
-                                ns += row[1];
-                                ne += row[2];
-                            }
-                            tot_q[b] += nq;
-                            tot_s[b] += ns;
-                            if (b >= 1 && nq != 0) last.back() = b;
-                            if (b >= 1) {   // (queue b lives in queue[b & 1]; the hits of its casts by queue position)
-                                uint64_t& q = (b & 1u) ? q1 : q0;
-                                q = std::max(q, nq);
-                                hh = std::max(hh, nq);
-                            }
-                            ss = std::max(ss, ns);
-                            ee = std::max(ee, ne);
-                        }
-                    }
-                const uint64_t items = std::min<uint64_t>((uint64_t)ca * m, items_per_batch);
-                if (!bounce0_fused) hh = std::max(hh, items);   // the casts of bounce 0 too: hits and draw counts by work item
-                auto pad = [](uint64_t n) { return (std::max<uint64_t>(n, 1024) + 1023) & ~1023ull; };
-                q0 = pad(q0), q1 = pad(q1), hh = pad(hh), ss = pad(ss), ee = pad(ee);
-                const uint64_t bytes = 68u * (q0 + q1) + 20u * hh + (alpha ? 4u * hh : 0u) + (64u + 16u * lights + 4u) * ss + 16u * ee +
-                                       (rng_one_plane ? 16u : (wf_overlap && items < items_per_batch) ? 64u : 32u) * items;   // (two copies: the next chunk's are made ahead)
-                // (a batch that fits `one_pass_gib` as ONE chunk takes it: every extra pass repeats the persistent launches and their
-                // drains - the KD-tree pipeline of config 3, 29.7 GiB in one pass: 62.4 ms, in three passes of 16 GiB 75.3 ms)
-                const bool fits = bytes <= (uint64_t)(steady_gib * 1073741824.0) ||
-                                  (items >= items_per_batch && bytes <= (uint64_t)(one_pass_gib * 1073741824.0));
-                if ((fits || m == 1) && std::max({q0, q1, hh, ss, ee, items}) < 0xffffffffull) {
-                    f.plan_cap = (uint32_t)items;
-                    f.plan_q[0] = (uint32_t)q0;
-                    f.plan_q[1] = (uint32_t)q1;
-                    f.plan_h = (uint32_t)hh;
-                    f.plan_s = (uint32_t)ss;
-                    f.plan_e = (uint32_t)ee;
-                    // shadow casts inside the shade kernel where (nearly) every ray of a bounce reaches a lit surface
-                    // (PT_OG_INLINE_ALL=1 in the closed room: +6.6 %; in an open scene: -6 %)
-                    f.plan_inline.assign(p.bounces + 2, 0);
-                    if (inline_auto && use_light_grids)
-                        for (uint32_t b = 1; b < lv && b < f.plan_inline.size(); ++b) f.plan_inline[b] = tot_q[b] > 0 && tot_s[b] * 10 >= tot_q[b] * 6;
-                    f.plan_last = last;
-                    f.plan_fresh = true;
-                    if (const char* e = getenv("PT_PLAN_DEBUG"); e && *e && atoi(e)) {
-                        fprintf(stderr, "[ptgpu] frame plan: %u chunks of %u -> 1 of %llu items; queues %llu / %llu, hits %llu, shadow %llu, exact %llu records; %.3f GiB\n",
-                                m, ca, (unsigned long long)items, (unsigned long long)q0, (unsigned long long)q1, (unsigned long long)hh,
-                                (unsigned long long)ss, (unsigned long long)ee, bytes / 1073741824.0);
-                        for (uint32_t b = 0; b < lv; ++b)
-                            fprintf(stderr, "[ptgpu]   bounce %u: %llu rays, %llu shadow records%s\n", b, (unsigned long long)tot_q[b],
-                                    (unsigned long long)tot_s[b], b < f.plan_inline.size() && f.plan_inline[b] ? " (inline)" : "");
-                    }
-                    return true;
-                }
-            }
-            return false;
-        };
-        if (!graphs_on) {
-            auto& slot = s.frame_stats[stat_key];
-            if (!slot) {
-                if (s.frame_stats.size() > 64) {   // (a caller cycling through configurations: start over)
-                    HIP_CHECK(hipDeviceSynchronize());
-                    s.frame_stats.clear();
-                }
-                s.frame_stats[stat_key] = std::make_unique<pt_scene::FrameStats>();
-            }
-            fs = s.frame_stats[stat_key].get();
-            if (fs->pending) {
-                const hipError_t q = hipEventQuery(fs->done);
-                (void)hipGetLastError();   // (hipErrorNotReady is no error)
-                if (q == hipSuccess) {
-                    fs->pending = false;
-                    bool overflow = false;
-                    for (uint32_t k = 0; k < fs->n_slots; ++k) {
-                        overflow = overflow || fs->host[(size_t)k * fs->levels * 4 + 3] != 0u;
-                        if (fs->planned && fs->stats_planned && k < fs->plan_last.size())   // (a ray at a bounce the plan did not launch)
-                            for (uint32_t b = fs->plan_last[k] + 1u; b < fs->levels; ++b)
-                                overflow = overflow || fs->host[((size_t)k * fs->levels + b) * 4] != 0u;
-                    }
-                    if (overflow) {
-                        // cannot happen (the counts of a configuration do not change): a queue sized from them ran full
-                        fs->valid = fs->planned = false;
-                        fail(PT_ERR_DEVICE, "internal error: a path queue sized from an earlier frame's counts ran full; the previous frame of "
-                                            "this configuration is not to be trusted");
-                    }
-                    if (!fs->planned) {
-                        fs->valid = true;
-                        fs->planned = make_plan(*fs);
-                    }
-                }
-            }
-        }
-        bool exact = fs && fs->planned && !fs->plan_failed;
-        if (exact) {
-            cap = fs->plan_cap;
-            cap_q[0] = fs->plan_q[0], cap_q[1] = fs->plan_q[1], cap_h = fs->plan_h, cap_s = fs->plan_s, cap_e = fs->plan_e;
-            inline_at = fs->plan_inline;
-            inline_at.resize(p.bounces + 2, 0);
-            // test hook (tests/test_frame_plan.py): a plan that is WRONG - every array shorter than its records - so that what
-            // cannot happen does: the kernels must drop the records that do not fit without writing past an array, flag the
-            // frame, and the next call of the configuration must say so
-            if (const char* e = getenv("PT_PLAN_TEST_SHRINK"); e && *e) {
-                const double f = std::min(1.0, std::max(0.01, atof(e)));
-                for (uint32_t* c : {&cap_q[0], &cap_q[1], &cap_s, &cap_e}) *c = std::max<uint32_t>(64u, (uint32_t)(*c * f));
-                cap_h = std::max({(uint32_t)(cap_h * f), cap_q[0], cap_q[1]});
-            }
-        }
-        if (!exact) {
-            cap = cap_a;
-            cap_q[0] = cap_q[1] = cap_h = cap_s = cap_e = cap;
-        }
-        // allocation; a device that cannot provide the buffers (shared GPU) gets half-size chunks with every queue as long as
-        // the chunk, and so on, down to 1 Mi items
-        const bool give_back = exact && fs->plan_fresh;   // (a new plan gives memory back, once)
-        bool grew = false;
-        auto fit = [give_back, &grew](DeviceBuffer& b, size_t n) {
-            if (give_back && b.bytes > n + n / 4 + (64u << 20)) b.release();
-            grew = grew || b.bytes < n;
-            return b.try_ensure(n);
-        };
-        // (what the queues must leave free: the runtime allocates the kernels' scratch - up to 592 B per lane of every wave slot
-        // of the device, per hardware queue: ~1.2 GB - when they are first launched, and dies if it cannot)
-        const double reserve_gib = [] { const char* e = getenv("PT_QUEUE_RESERVE_GIB"); return e && *e ? atof(e) : 2.0; }();
-        while (true) {
-            multi_chunk = (uint64_t)cap < items_per_batch;
-            const bool two_rng = !rng_one_plane && multi_chunk && wf_overlap;
-            bool ok = fit(w.queue[0], (size_t)cap_q[0] * 68u) && fit(w.queue[1], (size_t)cap_q[1] * 68u) &&   // (64 B + the entry word)
-                      fit(w.hits, (size_t)cap_h * 20u) && fit(w.shadow, (size_t)cap_s * 64u) &&
-                      fit(w.contrib, (size_t)cap_s * 16u * lights) && fit(w.rng[0], (size_t)cap * (rng_one_plane ? 16u : 32u)) &&
-                      (!two_rng || fit(w.rng[1], (size_t)cap * 32u)) &&
-                      (!alpha || fit(w.draws, (size_t)cap_h * 4u)) &&   // RNG draw index of the alpha walk
-                      fit(w.offgrid, (size_t)cap_s * 4u) &&   // shadow jobs left to k_og_shadow_offgrid (long normals; rays the wavefront walker does not take)
-                      fit(w.exact[0], (size_t)cap_e * 8u) && fit(w.exact[1], (size_t)cap_e * 8u) &&   // casts left to k_wf_trace_exact: queue index + hit word
-                      (!bounce0_fused || w.block_mask.try_ensure((size_t)blocks64 * 4u + 4u + tm.n_local)) &&
-                      // casts left to k_wf_trace_wide: at most one per lane in flight when the queue runs dry
-                      // (4 B the queue index + 20 B a hit + 4 B the progress of the walk: wf_list_* in pt_wavefront.h)
-                      (!wf_defer ||
-                       w.deferred.try_ensure((wf_allwide && !alpha ? (size_t)std::max(cap_q[0], cap_q[1]) : (size_t)s.trace_blocks * WF_THREADS) * 4u *
-                                             (alpha ? WF_LIST_WORDS_ALPHA : WF_LIST_WORDS_OPAQUE)));
-            if (ok && grew && cap > (1u << 20)) {
-                size_t free_b = 0, total_b = 0;
-                if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (double)free_b < reserve_gib * 1073741824.0) ok = false;
-                grew = false;
-            }
-            if (ok) {
-                if (exact) fs->plan_fresh = false;
-                break;
-            }
-            for (DeviceBuffer* b : {&w.queue[0], &w.queue[1], &w.hits, &w.shadow, &w.contrib, &w.rng[0], &w.rng[1], &w.draws, &w.offgrid, &w.deferred, &w.exact[0], &w.exact[1], &w.block_mask})
-                b->release();
-            if (exact) {   // (no room for the planned sizes: as a first frame)
-                exact = false;
-                fs->plan_failed = true;
-                cap = cap_a;
-            } else {
-                if (cap <= (1u << 20))
-                    fail(PT_ERR_DEVICE, "out of device memory: the path queues need %zu bytes for %u work items", (size_t)cap * per_item, cap);
-                cap = std::max<uint32_t>(1u << 20, (cap / 2u) & ~63u);
-                s.wf_cap_ok = cap;
-            }
-            cap_q[0] = cap_q[1] = cap_h = cap_s = cap_e = cap;
-            std::fill(inline_at.begin(), inline_at.end(), 0);
-        }
-        s.queue_bytes_last = w.queue[0].bytes + w.queue[1].bytes + w.hits.bytes + w.shadow.bytes + w.contrib.bytes + w.rng[0].bytes +
-                             w.rng[1].bytes + w.draws.bytes + w.offgrid.bytes + w.exact[0].bytes + w.exact[1].bytes + w.deferred.bytes;
-        s.queue_chunk_last = cap;
-        s.frame_planned_last = exact ? 1u : 0u;
-        if (fs) {
-            // this frame's counts, one line per (batch, chunk): taken every frame (a few KB) - the first frame's feed the plan,
-            // the later ones only say whether a queue ran full
-            stats_slots = 0;
-            for (uint32_t s0 = 0; s0 < p.samples; s0 += batch) {
-                const uint64_t tot = (uint64_t)blocks64 * 64u * std::min(batch, p.samples - s0);
-                stats_slots += (uint32_t)((tot + cap - 1u) / cap);
-            }
-            if (!fs->pending) {
-                if (fs->n_slots != stats_slots || fs->levels != levels || !fs->host) {
-                    if (fs->host) (void)hipHostFree(fs->host);
-                    fs->host = nullptr;
-                    HIP_CHECK(hipHostMalloc((void**)&fs->host, (size_t)stats_slots * levels * 16u));
-                    fs->n_slots = stats_slots;
-                    fs->levels = levels;
-                }
-                if (!fs->done) HIP_CHECK(hipEventCreateWithFlags(&fs->done, hipEventDisableTiming));
-                fs->cap_items = cap;
-                fs->stats_planned = exact;
-                fs->first_item_of_slot.assign(stats_slots, 0u);
-                s.stats_dev.ensure((size_t)stats_slots * levels * 16u);
-            } else {
-                stats_slots = 0;   // (an earlier frame's line is still on its way)
-            }
-        }
-        // (the next chunk's RNG planes are produced on the SHADOW stream, idle while a chunk's bounce 0 is traced - not on a stream
-        // of their own: a FIFTH stream - the caller's, shadow, wide, exact and that one - makes two of them share one of the
-        // device's four hardware queues (ROCm's default), and every launch of the frame then waits ~45 us longer for its turn:
-        // config 3, 40.3 -> 41.8 ms a frame with the stream merely existing, config 5 465 -> 508 ms)
-        if (multi_chunk && wf_overlap && !rng_one_plane && !w.ev_rng) {
-            HIP_CHECK(hipEventCreateWithFlags(&w.ev_rng, hipEventDisableTiming));
-            HIP_CHECK(hipEventCreateWithFlags(&w.ev_chunk, hipEventDisableTiming));
-        }
-        if (wf_overlap && !w.side) {
-            side_stream(&w.side, 0);
-            HIP_CHECK(hipEventCreateWithFlags(&w.ev_shade, hipEventDisableTiming));
-            HIP_CHECK(hipEventCreateWithFlags(&w.ev_shadow, hipEventDisableTiming));
-        }
-        if (wf_overlap && !w.side_wide) {
-            // (high priority: their few workgroups - the long casts of the drain, the casts the wavefront walker does not take -
-            // run beside the shade pass over the queue, whose thousands of short workgroups would otherwise take every slot
-            // that comes free before them; PT_WF_SIDE_PRIORITY=0: default priority)
-            int prio_lo = 0, prio_hi = 0;
-            HIP_CHECK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-            const char* pe = getenv("PT_WF_SIDE_PRIORITY");
-            const int prio = (pe && *pe && atoi(pe) == 0) ? prio_lo : prio_hi;
-            side_stream(&w.side_wide, prio);
-            side_stream(&w.side_exact, prio);
-            HIP_CHECK(hipEventCreateWithFlags(&w.ev_trace, hipEventDisableTiming));
-            HIP_CHECK(hipEventCreateWithFlags(&w.ev_wide, hipEventDisableTiming));
-            HIP_CHECK(hipEventCreateWithFlags(&w.ev_exact, hipEventDisableTiming));
-            HIP_CHECK(hipEventCreateWithFlags(&w.ev_exact_go, hipEventDisableTiming));
+            return true;
         }
     }
-    uint32_t blocks = tm.n_local_tiles * (o.tile_w * o.tile_h / 256u);
+    return false;
+}
+
+// The frame plan.  A frame is a pure function of (scene, profile, options) - the seeds are the pixels' - so the counts of
+// a configuration's first frame are those of every later one: the first frame runs in chunks small enough for a fixed
+// budget with every queue as long as the chunk, the later ones get queues as long as the records that exist.  Collects
+// the counts of an earlier frame if they have arrived and returns this frame's chunking and capacities.
+WfFrame frame_plan(pt_scene& s, const Frame& f, const QueueEnv& qe) {
+    const pt_profile& p = f.p;
+    const pt_opts& o = f.o;
+    WfFrame wf;
+    wf.items_per_batch = (uint64_t)f.blocks64 * 64u * f.batch;
+    if (s.trace_blocks == 0) {
+        int a = 0, b = 0, c = 0, d = 0;
+        HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_wf_trace<false, false, false>, WF_THREADS, 0));
+        HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_wf_trace<true, false, false>, WF_THREADS, 0));
+        HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&c, k_wf_shadow<false, false>, WF_THREADS, 0));
+        HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&d, k_wf_shadow<true, false>, WF_THREADS, 0));
+        s.trace_blocks = std::max(1, f.alpha ? b : a) * s.n_cu;
+        s.shadow_blocks = std::max(1, f.alpha ? d : c) * s.n_cu;
+    }
+    s.pipe.ctr.ensure(sizeof(WfCounters) * (p.bounces + 3));
+    wf.lights = std::max(1u, s.dev.n_lights);
+    wf.rng_one_plane = f.env.fuse_rng && f.bounce0_fused;
+    // two path queues of 64 B (+ the entry word), 20 B hit, 64 B shadow record + 16 B per light, the RNG plane(s), draws,
+    // off-grid and exact lists
+    wf.per_item = 68u * 2u + 20u + 64u + 16u * wf.lights + (wf.rng_one_plane ? 16u : 32u) + (f.alpha ? 4u : 0u) + 4u + 16u;
+    wf.max_items = (uint32_t)std::min<uint64_t>(wf.items_per_batch, std::max<uint32_t>(64u, f.env.wf_chunk & ~63u));
+    const std::vector<uint64_t> stat_key = {p.width, p.height, p.samples, p.bounces, (uint64_t)p.brdf,
+                                            o.flags & (PT_FLAG_NO_GRIDS | PT_FLAG_MEGAKERNEL | PT_FLAG_COUNTERS), (uint64_t)f.bounce0_fused, o.shard_rank, o.shard_count, o.tile_w, o.tile_h, f.batch, (uint64_t)wf.max_items};
+    wf.cap_a = (uint32_t)std::min<uint64_t>(wf.max_items, std::max<uint64_t>(1u << 20, (uint64_t)(qe.first_gib * 1073741824.0) / wf.per_item) & ~63ull);
+    if (s.wf_cap_ok) wf.cap_a = std::min(wf.cap_a, s.wf_cap_ok);
+    auto& stats = s.frame_state.stats;
+    if (!stats[stat_key]) {
+        if (stats.size() > 64) {   // (a caller cycling through configurations: start over)
+            HIP_CHECK(hipDeviceSynchronize());
+            stats.clear();
+        }
+        stats[stat_key] = std::make_unique<pt_scene::FrameStats>();
+    }
+    pt_scene::FrameStats* fs = wf.fs = stats[stat_key].get();
+    if (fs->pending) {
+        const hipError_t q = hipEventQuery(fs->done);
+        (void)hipGetLastError();   // (hipErrorNotReady is no error)
+        if (q == hipSuccess) {
+            fs->pending = false;
+            bool overflow = false;
+            for (uint32_t k = 0; k < fs->n_slots; ++k) {
+                overflow = overflow || fs->host[(size_t)k * fs->levels * 4 + 3] != 0u;
+                if (fs->planned && fs->stats_planned && k < fs->plan_last.size())   // (a ray at a bounce the plan did not launch)
+                    for (uint32_t b = fs->plan_last[k] + 1u; b < fs->levels; ++b)
+                        overflow = overflow || fs->host[((size_t)k * fs->levels + b) * 4] != 0u;
+            }
+            if (overflow) {
+                // cannot happen (the counts of a configuration do not change): a queue sized from them ran full
+                fs->valid = fs->planned = false;
+                fail(PT_ERR_DEVICE, "internal error: a path queue sized from an earlier frame's counts ran full; the previous frame of "
+                                    "this configuration is not to be trusted");
+            }
+            if (!fs->planned) {
+                fs->valid = true;
+                fs->planned = make_plan(*fs, f, wf, qe);
+            }
+        }
+    }
+    wf.planned = fs->planned && !fs->plan_failed;
+    wf.inline_at.assign(p.bounces + 2, 0);
+    if (wf.planned) {
+        wf.cap = fs->plan_cap;
+        wf.cap_q[0] = fs->plan_q[0], wf.cap_q[1] = fs->plan_q[1], wf.cap_h = fs->plan_h, wf.cap_s = fs->plan_s, wf.cap_e = fs->plan_e;
+        wf.inline_at = fs->plan_inline;
+        wf.inline_at.resize(p.bounces + 2, 0);
+        // test hook (tests/test_frame_plan.py): a plan that is WRONG - every array shorter than its records - so that what
+        // cannot happen does: the kernels must drop the records that do not fit without writing past an array, flag the
+        // frame, and the next call of the configuration must say so
+        if (qe.test_shrink > 0) {
+            const double k = qe.test_shrink;
+            for (uint32_t* c : {&wf.cap_q[0], &wf.cap_q[1], &wf.cap_s, &wf.cap_e}) *c = std::max<uint32_t>(64u, (uint32_t)(*c * k));
+            wf.cap_h = std::max({(uint32_t)(wf.cap_h * k), wf.cap_q[0], wf.cap_q[1]});
+        }
+    } else {
+        wf.cap = wf.cap_a;
+        wf.cap_q[0] = wf.cap_q[1] = wf.cap_h = wf.cap_s = wf.cap_e = wf.cap;
+    }
+    return wf;
+}
+
+// The buffers of wf's capacities.  A device that cannot provide them (shared GPU) gets half-size chunks with every queue as
+// long as the chunk, and so on, down to 1 Mi items.
+void queue_buffers(pt_scene& s, const Frame& f, const QueueEnv& qe, WfFrame& wf) {
+    pt_scene::WfPipe& w = s.pipe;
+    const bool alpha = f.alpha;
+    const size_t lights = wf.lights;
+    const bool give_back = wf.planned && wf.fs->plan_fresh;   // (a new plan gives memory back, once)
+    bool grew = false;
+    auto fit = [give_back, &grew](DeviceBuffer& b, size_t n) {
+        if (give_back && b.bytes > n + n / 4 + (64u << 20)) b.release();
+        grew = grew || b.bytes < n;
+        return b.try_ensure(n);
+    };
+    while (true) {
+        wf.multi_chunk = (uint64_t)wf.cap < wf.items_per_batch;
+        const bool two_rng = !wf.rng_one_plane && wf.multi_chunk && f.env.overlap;
+        bool ok = fit(w.queue[0], (size_t)wf.cap_q[0] * 68u) && fit(w.queue[1], (size_t)wf.cap_q[1] * 68u) &&   // (64 B + the entry word)
+                  fit(w.hits, (size_t)wf.cap_h * 20u) && fit(w.shadow, (size_t)wf.cap_s * 64u) &&
+                  fit(w.contrib, (size_t)wf.cap_s * 16u * lights) && fit(w.rng[0], (size_t)wf.cap * (wf.rng_one_plane ? 16u : 32u)) &&
+                  (!two_rng || fit(w.rng[1], (size_t)wf.cap * 32u)) &&
+                  (!alpha || fit(w.draws, (size_t)wf.cap_h * 4u)) &&   // RNG draw index of the alpha walk
+                  fit(w.offgrid, (size_t)wf.cap_s * 4u) &&   // shadow jobs left to k_og_shadow_offgrid (long normals; rays the wavefront walker does not take)
+                  fit(w.exact[0], (size_t)wf.cap_e * 8u) && fit(w.exact[1], (size_t)wf.cap_e * 8u) &&   // casts left to k_wf_trace_exact: queue index + hit word
+                  (!f.bounce0_fused || w.block_mask.try_ensure((size_t)f.blocks64 * 4u + 4u + f.tm.n_local)) &&
+                  // casts left to k_wf_trace_wide: at most one per lane in flight when the queue runs dry
+                  // (4 B the queue index + 20 B a hit + 4 B the progress of the walk: wf_list_* in pt_wavefront.h)
+                  (!f.env.defer ||
+                   w.deferred.try_ensure((size_t)s.trace_blocks * WF_THREADS * 4u * (alpha ? WF_LIST_WORDS_ALPHA : WF_LIST_WORDS_OPAQUE)));
+        if (ok && grew && wf.cap > (1u << 20)) {
+            size_t free_b = 0, total_b = 0;
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (double)free_b < qe.reserve_gib * 1073741824.0) ok = false;
+            grew = false;
+        }
+        if (ok) {
+            if (wf.planned) wf.fs->plan_fresh = false;
+            break;
+        }
+        for (DeviceBuffer* b : {&w.queue[0], &w.queue[1], &w.hits, &w.shadow, &w.contrib, &w.rng[0], &w.rng[1], &w.draws, &w.offgrid, &w.deferred, &w.exact[0], &w.exact[1], &w.block_mask})
+            b->release();
+        if (wf.planned) {   // (no room for the planned sizes: as a first frame)
+            wf.planned = false;
+            wf.fs->plan_failed = true;
+            wf.cap = wf.cap_a;
+        } else {
+            if (wf.cap <= (1u << 20))
+                fail(PT_ERR_DEVICE, "out of device memory: the path queues need %zu bytes for %u work items", (size_t)wf.cap * wf.per_item, wf.cap);
+            wf.cap = std::max<uint32_t>(1u << 20, (wf.cap / 2u) & ~63u);
+            s.wf_cap_ok = wf.cap;
+        }
+        wf.cap_q[0] = wf.cap_q[1] = wf.cap_h = wf.cap_s = wf.cap_e = wf.cap;
+        std::fill(wf.inline_at.begin(), wf.inline_at.end(), 0);
+    }
+    s.queue_bytes_last = w.queue[0].bytes + w.queue[1].bytes + w.hits.bytes + w.shadow.bytes + w.contrib.bytes + w.rng[0].bytes +
+                         w.rng[1].bytes + w.draws.bytes + w.offgrid.bytes + w.exact[0].bytes + w.exact[1].bytes + w.deferred.bytes;
+    s.queue_chunk_last = wf.cap;
+    s.frame_planned_last = wf.planned ? 1u : 0u;
+}
+
+// This frame's counts, one line per (batch, chunk): taken every frame (a few KB) - the first frame's feed the plan, the
+// later ones only say whether a queue ran full.  None while an earlier frame's line is still on its way.
+void stats_slots(pt_scene& s, const Frame& f, WfFrame& wf) {
+    pt_scene::FrameStats* fs = wf.fs;
+    const uint32_t levels = f.p.bounces + 3;
+    uint32_t n = 0;
+    for (uint32_t s0 = 0; s0 < f.p.samples; s0 += f.batch) {
+        const uint64_t tot = (uint64_t)f.blocks64 * 64u * std::min(f.batch, f.p.samples - s0);
+        n += (uint32_t)((tot + wf.cap - 1u) / wf.cap);
+    }
+    if (fs->pending) return;
+    if (fs->n_slots != n || fs->levels != levels || !fs->host) {
+        if (fs->host) (void)hipHostFree(fs->host);
+        fs->host = nullptr;
+        HIP_CHECK(hipHostMalloc((void**)&fs->host, (size_t)n * levels * 16u));
+        fs->n_slots = n;
+        fs->levels = levels;
+    }
+    if (!fs->done) HIP_CHECK(hipEventCreateWithFlags(&fs->done, hipEventDisableTiming));
+    fs->cap_items = wf.cap;
+    fs->stats_planned = wf.planned;
+    fs->first_item_of_slot.assign(n, 0u);
+    s.stats_dev.ensure((size_t)n * levels * 16u);
+    wf.stats_slots = n;
+}
+
+// The side streams and the events between them, made by the first frame that needs them.
+void side_streams(pt_scene& s, const Frame& f, const WfFrame& wf) {
+    pt_scene::WfPipe& w = s.pipe;
+    // (the next chunk's RNG planes are produced on the SHADOW stream, idle while a chunk's bounce 0 is traced - not on a stream
+    // of their own: a FIFTH stream - the caller's, shadow, wide, exact and that one - makes two of them share one of the
+    // device's four hardware queues (ROCm's default), and every launch of the frame then waits ~45 us longer for its turn:
+    // config 3, 40.3 -> 41.8 ms a frame with the stream merely existing, config 5 465 -> 508 ms)
+    if (wf.multi_chunk && f.env.overlap && !wf.rng_one_plane && !w.ev_rng) {
+        HIP_CHECK(hipEventCreateWithFlags(&w.ev_rng, hipEventDisableTiming));
+        HIP_CHECK(hipEventCreateWithFlags(&w.ev_chunk, hipEventDisableTiming));
+    }
+    if (f.env.overlap && !w.side) {
+        HIP_CHECK(hipStreamCreateWithPriority(&w.side, hipStreamNonBlocking, 0));
+        HIP_CHECK(hipEventCreateWithFlags(&w.ev_shade, hipEventDisableTiming));
+        HIP_CHECK(hipEventCreateWithFlags(&w.ev_shadow, hipEventDisableTiming));
+    }
+    if (f.env.overlap && !w.side_wide) {
+        // (high priority: their few workgroups - the long casts of the drain, the casts the wavefront walker does not take -
+        // run beside the shade pass over the queue, whose thousands of short workgroups would otherwise take every slot
+        // that comes free before them; PT_WF_SIDE_PRIORITY=0: default priority)
+        int prio_lo = 0, prio_hi = 0;
+        HIP_CHECK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+        const int prio = f.env.side_priority ? prio_hi : prio_lo;
+        HIP_CHECK(hipStreamCreateWithPriority(&w.side_wide, hipStreamNonBlocking, prio));
+        HIP_CHECK(hipStreamCreateWithPriority(&w.side_exact, hipStreamNonBlocking, prio));
+        HIP_CHECK(hipEventCreateWithFlags(&w.ev_trace, hipEventDisableTiming));
+        HIP_CHECK(hipEventCreateWithFlags(&w.ev_wide, hipEventDisableTiming));
+        HIP_CHECK(hipEventCreateWithFlags(&w.ev_exact, hipEventDisableTiming));
+        HIP_CHECK(hipEventCreateWithFlags(&w.ev_exact_go, hipEventDisableTiming));
+    }
+}
+
+// The timing events of one frame (PT_FLAG_TIMING): (stage id, first event index) of every timed launch - 0 generate
+// 1 trace 2 shade 3 shadow 4 accumulate 5 fused - and the first event index of every fused bounce-0 launch (k_wf_shade<GRID >= 2>).
+struct Timeline {
+    pt_scene& s;
+    bool on;
+    hipStream_t stream;   // where the events of the next stage are recorded
     size_t ev = 0;
     uint32_t launches = 0, stage_launches = 0;
-    // (stage id, first event index) of every timed launch: 0 generate 1 trace 2 shade 3 shadow 4 accumulate 5 fused
     std::vector<std::pair<int, size_t>> marks;
-    std::vector<size_t> fused_marks;   // first event index of every fused bounce-0 launch (k_wf_shade<GRID >= 2>)
-    hipStream_t stage_stream = stream;
-    auto stage_begin = [&](int stage) {
-        if (!timing) return;
+    std::vector<size_t> fused_marks;
+    void begin(int stage) {
+        if (!on) return;
         marks.emplace_back(stage, ev);
-        HIP_CHECK(hipEventRecord(get_event(s, ev++), stage_stream));
-    };
-    auto stage_end = [&]() {
-        ++stage_launches;
-        if (timing) HIP_CHECK(hipEventRecord(get_event(s, ev++), stage_stream));
-    };
-    DevCounters* gctr = (counting || exit_times) ? (DevCounters*)s.counter_buf.p : nullptr;
-    // ---- hipGraph: a plain frame (no timing events, counters, callbacks) is captured once per configuration - on a
-    // stream of the scene's own, the caller's may be the null stream - and replayed on the caller's stream afterwards.
-    // Everything the launches below depend on is in the key; the side streams join the capture through the events they
-    // wait for and are joined again before it ends.
-    static const bool wf_graph = [] {
-        const char* e = getenv("PT_GRAPH");
-        return e && *e ? atoi(e) != 0 : PT_GRAPH_DEFAULT;
-    }();
-    const hipStream_t user_stream = stream;
-    struct CaptureGuard {   // (an exception between begin and end must not leave the stream capturing)
-        hipStream_t st = nullptr;
-        ~CaptureGuard() {
-            if (!st) return;
-            hipGraph_t g = nullptr;
-            (void)hipStreamEndCapture(st, &g);
-            if (g) (void)hipGraphDestroy(g);
-            (void)hipGetLastError();
-        }
-    } capture;
-    std::vector<uint64_t> graph_key;
-    if (wf_graph && mode == 2 && !timing && !counting && !exit_times && !o.progress && !(allow_preview && o.preview)) {
-        const pt_scene::WfPipe& w = s.pipe;
-        graph_key = {p.width, p.height, p.samples, p.bounces, (uint64_t)p.tonemap, o.flags, o.shard_rank, o.shard_count, o.tile_w,
-                     o.tile_h, o.sample_batch, (uint64_t)d_rgb8, (uint64_t)accum, (uint64_t)d_tiles, cap, cap_q[0], cap_q[1], cap_h, cap_s, cap_e, batch,
-                     (uint64_t)s.staging_buf.p, (uint64_t)w.queue[0].p, (uint64_t)w.queue[1].p, (uint64_t)w.hits.p,
-                     (uint64_t)w.shadow.p, (uint64_t)w.contrib.p, (uint64_t)w.ctr.p, (uint64_t)w.rng[0].p, (uint64_t)w.rng[1].p,
-                     (uint64_t)w.draws.p, (uint64_t)w.offgrid.p, (uint64_t)w.deferred.p, (uint64_t)w.exact[0].p, (uint64_t)w.exact[1].p, (uint64_t)s.trace_blocks,
-                     (uint64_t)s.shadow_blocks, (uint64_t)tm.n_local, (uint64_t)tm.n_local_tiles, (uint64_t)w.block_mask.p};
-        auto hit = s.graphs.find(graph_key);
-        if (hit != s.graphs.end()) {
-            HIP_CHECK(hipGraphLaunch(hit->second, user_stream));
-            return;
-        }
-        if (!s.capture_stream) HIP_CHECK(hipStreamCreateWithFlags(&s.capture_stream, hipStreamNonBlocking));
-        stream = s.capture_stream;
-        stage_stream = stream;
-        HIP_CHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-        capture.st = stream;
+        HIP_CHECK(hipEventRecord(get_event(s, ev++), stream));
     }
-    // bounce 0 through the camera grid: the 8x8 pixel blocks no camera ray can hit anything in (k_cam_block_mask) are
-    // found once per frame; their wavefronts write the background without a ChaCha block or a cast.  PT_CAM_CULL=0: off
-    static const bool cam_cull = [] {
-        const char* e = getenv("PT_CAM_CULL");
-        return e && *e ? atoi(e) != 0 : true;
-    }();
+    void end() {
+        ++stage_launches;
+        if (on) HIP_CHECK(hipEventRecord(get_event(s, ev++), stream));
+    }
+};
+
+// Bounce 0 through the camera grid: the 8x8 pixel blocks no camera ray can hit anything in (k_cam_block_mask) are found
+// once per frame; their wavefronts write the background without a ChaCha block or a cast.  PT_CAM_CULL=0: off.
+// Returns the table (nullptr: no cull in this frame).
+const uint32_t* camera_cull(pt_scene& s, const Frame& f, hipStream_t stream) {
     const uint32_t* block_empty = nullptr;
-    if (cam_cull && mode == 2 && bounce0_fused && !counting) {
-        RenderParams P1 = P;
+    if (f.env.cam_cull && f.wavefront && f.bounce0_fused && !f.counting) {
+        RenderParams P1 = f.P;
         P1.sample_begin = 0;
         P1.sample_end = 1;
         pt_fastdiv_make(1u, P1.div_batch);
-        HIP_CHECK(hipMemsetAsync((uint32_t*)s.pipe.block_mask.p + blocks64, 0, 4, stream));
-        hipLaunchKernelGGL(k_cam_block_mask, dim3((blocks64 * 64u + 255u) / 256u), dim3(256), 0, stream, dev, P1, d_tiles, blocks64,
-                           (uint32_t*)s.pipe.block_mask.p, (uint8_t*)((uint32_t*)s.pipe.block_mask.p + blocks64 + 1u));
+        HIP_CHECK(hipMemsetAsync((uint32_t*)s.pipe.block_mask.p + f.blocks64, 0, 4, stream));
+        hipLaunchKernelGGL(k_cam_block_mask, dim3((f.blocks64 * 64u + 255u) / 256u), dim3(256), 0, stream, f.dev, P1, f.d_tiles, f.blocks64,
+                           (uint32_t*)s.pipe.block_mask.p, (uint8_t*)((uint32_t*)s.pipe.block_mask.p + f.blocks64 + 1u));
         HIP_CHECK(hipGetLastError());
         block_empty = (const uint32_t*)s.pipe.block_mask.p;
     }
-    s.last_mask_blocks = block_empty ? blocks64 : 0u;
-    uint32_t stats_line = 0, chunk_slot = 0;
-    const std::vector<uint32_t>* plan_last = (fs && s.frame_planned_last && skip_dead) ? &fs->plan_last : nullptr;
-    for (uint32_t s0 = 0; s0 < p.samples; s0 += batch) {
-        P.sample_begin = s0;
-        P.sample_end = std::min(p.samples, s0 + batch);
-        uint32_t nb = P.sample_end - P.sample_begin;
-        pt_fastdiv_make(nb, P.div_batch);
-        if (mode == 0) {
-            stage_begin(5);
-            if (counting)
-                hipLaunchKernelGGL(k_render<true>, dim3(blocks), dim3(256), 0, stream, dev, P, d_tiles, accum, gctr);
-            else
-                hipLaunchKernelGGL(k_render<false>, dim3(blocks), dim3(256), 0, stream, dev, P, d_tiles, accum, gctr);
-            HIP_CHECK(hipGetLastError());
-            stage_end();
-            ++launches;
-        } else {
-            uint32_t total_items = blocks64 * 64u * nb;
-            const pt_scene::WfPipe& pipe = s.pipe;
-            hipStream_t st_main = stream;
-            hipStream_t st_shadow = wf_overlap ? pipe.side : st_main;   // (not const: see the shadow stage)
-            // opaque scenes, several chunks: the RNG planes of chunk c+1 are produced on their own stream while
-            // chunk c runs its bounces (k_wf_rng is pure integer ALU work; the traversal kernels leave ~40 % of
-            // the issue slots idle and end in a drain phase)
-            // both kinds of grid: the bounce-0 kernel computes the ChaCha block itself (GRID 3)
-            const bool fused_rng = rng_one_plane;   // (PT_OG_FUSE_RNG=0: off)
-            const bool rng_ahead = !fused_rng && wf_overlap && total_items > cap && pipe.side != nullptr && pipe.ev_rng != nullptr;
-            uint32_t chunk_no = 0;
-            for (uint32_t base = 0; base < total_items; base += cap, ++chunk_no) {
-                WfParams W{};
-                W.P = P;
-                W.item_base = base;
-                W.n_items = std::min(cap, total_items - base);
-                W.cap = cap;
-                W.hcap = cap_h;
-                W.scap = cap_s;
-                W.ecap = cap_e;
-                W.qcap_in = cap_q[0];
-                W.qcap_out = cap_q[1];
-                W.rng_first_plane = rng_one_plane ? 1u : 0u;
-                W.n_mask_blocks = blocks64;
-                uint4* rng_planes = (uint4*)pipe.rng[rng_ahead ? (chunk_no & 1u) : 0u].p;
-                // coherence sorting of the survivors by direction octant: measured (MI355X, config 3) trace of bounce 1
-                // 9.50 -> 9.25 ms, but the bounce-0 kernel 19.0 -> 20.2 ms: off by default
-                static const uint32_t wf_sort = [] {
-                    const char* e = getenv("PT_WF_SORT");
-                    return (uint32_t)(e && *e ? atoi(e) : 0);
-                }();
-                W.sort_octants = wf_sort;
-                // PT_WF_ENTRY=1: casts of bounces >= 1 start at the home node of the primitive their ray leaves (trav_enter).
-                // Measured (profiles/r03_experiments.txt item 2): 31 % fewer node visits, the same time - off by default
-                static const uint32_t wf_entry = [] {
-                    const char* e = getenv("PT_WF_ENTRY");
-                    return (uint32_t)(e && *e ? atoi(e) != 0 : 0);
-                }();
-                W.use_entry = wf_entry;
-                W.exact_handover = wf_exact ? 1u : 0u;   // (per bounce below: 1 k_wf_trace lists, 2 k_wf_shade listed)
-                W.exact_shade_lists = wf_exact == 2u ? 1u : 0u;
+    s.frame_state.mask_blocks = block_empty ? f.blocks64 : 0u;
+    return block_empty;
+}
 
-                W.refill_min = std::max(1u, std::min(64u, wf_refill));
-                W.walk_steps = wf_walk ? wf_walk : 20u;
-                WfCounters* wctr = (WfCounters*)pipe.ctr.p;
-                HIP_CHECK(hipMemsetAsync(wctr, 0, sizeof(WfCounters) * (p.bounces + 3), st_main));
-                // bounce 0 derives the camera rays in place from the staged screen positions (no queue[0])
-                const bool fused_primary = true;
-                if (fused_rng) {
-                    // (no k_wf_rng launch)
-                } else if (!rng_ahead || chunk_no == 0) {
-                    stage_begin(0);
-                    hipLaunchKernelGGL(k_wf_rng, dim3((W.n_items + 255u) / 256u), dim3(256), 0, st_main, dev, W, d_tiles,
-                                       rng_planes);
-                    HIP_CHECK(hipGetLastError());
-                    stage_end();
-                } else {
-                    HIP_CHECK(hipStreamWaitEvent(st_main, pipe.ev_rng, 0));  // produced underneath the previous chunk
-                }
-                if (rng_ahead && base + cap < total_items) {
-                    // the other copy was last read by chunk c-1, which has completed on st_main by now
-                    WfParams Wn = W;
-                    Wn.item_base = base + cap;
-                    Wn.n_items = std::min(cap, total_items - Wn.item_base);
-                    HIP_CHECK(hipEventRecord(pipe.ev_chunk, st_main));
-                    HIP_CHECK(hipStreamWaitEvent(pipe.side, pipe.ev_chunk, 0));
-                    stage_stream = pipe.side;
-                    stage_begin(0);
-                    hipLaunchKernelGGL(k_wf_rng, dim3((Wn.n_items + 255u) / 256u), dim3(256), 0, pipe.side, dev, Wn,
-                                       d_tiles, (uint4*)pipe.rng[(chunk_no + 1u) & 1u].p);
-                    HIP_CHECK(hipGetLastError());
-                    stage_end();
-                    stage_stream = st_main;
-                    HIP_CHECK(hipEventRecord(pipe.ev_rng, pipe.side));
-                }
-                // (the plan knows where this chunk's last ray ends: the launches of the bounces behind it - ~85 us each for nothing -
-                // are not made; PT_PLAN_SKIP=0: all of them)
-                const uint32_t b_end = (plan_last && chunk_slot < plan_last->size()) ? std::min(p.bounces, (*plan_last)[chunk_slot]) : p.bounces;
-                ++chunk_slot;
-                for (uint32_t b = 0; b <= b_end; ++b) {
-                    W.bounce = b;
-                    W.qcap_in = cap_q[b & 1u];          // (queue b lives in pipe.queue[b & 1])
-                    W.qcap_out = cap_q[(b + 1u) & 1u];
-                    // (node steps per walking phase: 12 until the escape masks took the short casts out of the queues; re-swept on the rays that
-                    // are left - 12 / 14 / 16 / 18: config 3 40.3-40.8 / 40.3-40.4 / 39.7-39.8 / 39.8-40.0 ms, closed room 173.9 -> 171.4)
-                    W.walk_steps = wf_walk ? wf_walk : (b == 0 ? 20u : 16u);
-                    float4* q_in = (float4*)pipe.queue[b & 1].p;
-                    float4* q_out = (float4*)pipe.queue[(b + 1) & 1].p;
-                    const bool prim = fused_primary && b == 0;
-                    // origin grids (pt_grid.h): 2 = camera cast + shadow casts inside the shade kernel (bounce 0, both
-                    // kinds of grid), 1 = shadow casts inside the shade kernel, 0 = none
-                    // (bounces >= 1 keep the shade kernel lean and cast their shadow rays in k_og_shadow: measured faster)
-                    static const int inline_later = [] {
-                        const char* e = getenv("PT_OG_INLINE_ALL");
-                        return e && *e ? atoi(e) : 0;
-                    }();
-                    // (... or where the frame plan found (nearly) every ray of the bounce reaching a lit surface)
-                    const int grid_mode = (prim && bounce0_fused) ? (fused_rng ? 3 : 2)
-                                                                  : (use_light_grids && (inline_later || (b < inline_at.size() && inline_at[b])) ? 1 : 0);
-#define PT_LAUNCH_ACP(kernel, grid, threads, ...)                                                                                      \
-    do {                                                                                                                               \
-        if (prim && alpha && counting)                                                                                                  \
-            hipLaunchKernelGGL((kernel<true, true, true>), dim3(grid), dim3(threads), 0, st_main, __VA_ARGS__);                        \
-        else if (prim && alpha) hipLaunchKernelGGL((kernel<true, false, true>), dim3(grid), dim3(threads), 0, st_main, __VA_ARGS__);   \
-        else if (prim && counting) hipLaunchKernelGGL((kernel<false, true, true>), dim3(grid), dim3(threads), 0, st_main, __VA_ARGS__); \
-        else if (prim) hipLaunchKernelGGL((kernel<false, false, true>), dim3(grid), dim3(threads), 0, st_main, __VA_ARGS__);           \
-        else if (alpha && counting) hipLaunchKernelGGL((kernel<true, true, false>), dim3(grid), dim3(threads), 0, st_main, __VA_ARGS__); \
-        else if (alpha) hipLaunchKernelGGL((kernel<true, false, false>), dim3(grid), dim3(threads), 0, st_main, __VA_ARGS__);          \
-        else if (counting) hipLaunchKernelGGL((kernel<false, true, false>), dim3(grid), dim3(threads), 0, st_main, __VA_ARGS__);       \
-        else hipLaunchKernelGGL((kernel<false, false, false>), dim3(grid), dim3(threads), 0, st_main, __VA_ARGS__);                    \
-        HIP_CHECK(hipGetLastError());                                                                                                  \
-    } while (0)
-#define PT_LAUNCH_AC(kernel, grid, ...)                                                                                  \
-    do {                                                                                                                 \
-        if (alpha && counting) hipLaunchKernelGGL((kernel<true, true>), dim3(grid), dim3(WF_THREADS), 0, st_shadow, __VA_ARGS__); \
-        else if (alpha) hipLaunchKernelGGL((kernel<true, false>), dim3(grid), dim3(WF_THREADS), 0, st_shadow, __VA_ARGS__);       \
-        else if (counting) hipLaunchKernelGGL((kernel<false, true>), dim3(grid), dim3(WF_THREADS), 0, st_shadow, __VA_ARGS__);    \
-        else hipLaunchKernelGGL((kernel<false, false>), dim3(grid), dim3(WF_THREADS), 0, st_shadow, __VA_ARGS__);                 \
-        HIP_CHECK(hipGetLastError());                                                                                    \
-    } while (0)
-// k_wf_shade<ALPHA, COUNT, PRIMARY, GRID>
-#define PT_SHADE_ARGS                                                                                                         \
-    dev, W, d_tiles, (const float4*)q_in, shade_hits, (const uint4*)rng_planes, (const uint32_t*)pipe.draws.p, \
-        q_out, (float4*)pipe.shadow.p, (float4*)pipe.contrib.p, (float*)s.staging_buf.p, shade_list,                 \
-        (const uint32_t*)pipe.exact[b & 1].p, (const uint4*)pipe.hits.p, (uint32_t*)pipe.exact[(b + 1) & 1].p,      \
-        (grid_mode >= 2 ? block_empty : (const uint32_t*)nullptr), wctr, gctr
-#define PT_LAUNCH_SHADE(A, C, P, G)                                                                                    \
-    hipLaunchKernelGGL((k_wf_shade<A, C, P, G>), dim3(shade_grid), dim3(WF_SHADE_THREADS), 0, st_main, PT_SHADE_ARGS)
-#define PT_LAUNCH_SHADE_G(G)                                                   \
-    do {                                                                       \
-        if (prim && alpha && counting) PT_LAUNCH_SHADE(true, true, true, G);   \
-        else if (prim && alpha) PT_LAUNCH_SHADE(true, false, true, G);         \
-        else if (prim && counting) PT_LAUNCH_SHADE(false, true, true, G);      \
-        else if (prim) PT_LAUNCH_SHADE(false, false, true, G);                 \
-        else if (alpha && counting) PT_LAUNCH_SHADE(true, true, false, G);     \
-        else if (alpha) PT_LAUNCH_SHADE(true, false, false, G);                \
-        else if (counting) PT_LAUNCH_SHADE(false, true, false, G);             \
-        else PT_LAUNCH_SHADE(false, false, false, G);                          \
-    } while (0)
-#define PT_LAUNCH_SHADE_P(G)                                            \
-    do {                                                                \
-        if (alpha && counting) PT_LAUNCH_SHADE(true, true, true, G);    \
-        else if (alpha) PT_LAUNCH_SHADE(true, false, true, G);          \
-        else if (counting) PT_LAUNCH_SHADE(false, true, true, G);       \
-        else PT_LAUNCH_SHADE(false, false, true, G);                    \
-    } while (0)
-                    bool split_shade = false;
-                    if (grid_mode < 2) {   // (grid_mode >= 2: k_wf_shade casts the camera rays itself)
-                        stage_begin(1);
-                        if (prim && use_cam_grid) {   // camera rays: one grid lookup instead of a KD walk (pt_grid_kernels.h)
-                            const dim3 g((W.n_items + 255u) / 256u);
-#define PT_LAUNCH_OGP(A, C)                                                                                                   \
-    hipLaunchKernelGGL((k_og_primary<A, C>), g, dim3(256), 0, st_main, dev, W, d_tiles, (uint4*)pipe.hits.p, \
-                       (const uint4*)rng_planes, (uint32_t*)pipe.draws.p, gctr)
-                            if (alpha && counting) PT_LAUNCH_OGP(true, true);
-                            else if (alpha) PT_LAUNCH_OGP(true, false);
-                            else if (counting) PT_LAUNCH_OGP(false, true);
-                            else PT_LAUNCH_OGP(false, false);
-#undef PT_LAUNCH_OGP
-                            HIP_CHECK(hipGetLastError());
-                        } else {
-                            W.defer_age = prim ? 0u : wf_defer;
-                            // the hand-over list: queue indices, then (split shade pass) the plane of their hits
-                            const uint32_t list_cap = (uint32_t)s.trace_blocks * WF_THREADS;
-                            uint4* list_hits = (uint4*)((uint32_t*)pipe.deferred.p + list_cap);
-                            split_shade = wf_split && W.defer_age != 0u && pipe.side_wide != nullptr;
-                            W.list_cap = list_cap;
-                            W.split_deferred = split_shade ? 1u : 0u;
-                            const bool allwide = wf_allwide && !alpha && W.defer_age != 0u;
-                            if (allwide) {
-                                split_shade = false;
-                                W.list_cap = std::max(cap_q[0], cap_q[1]);
-                                W.split_deferred = 0u;
-                            }
-                            // The casts the wavefront walker does not take (slack_is_capped): one lane each on the grown-box walker.
-                            // Bounces >= 1: k_wf_shade listed them when it made the rays, so the launch goes out BEFORE the
-                            // persistent kernel, on a stream of its own, and runs beside it (its few hundred workgroups take
-                            // their slots first; the persistent grid's last workgroups start as those free up).  Camera rays of
-                            // the KD-tree pipeline: k_wf_trace lists them, the launch follows it.
-                            W.exact_handover = (wf_exact && !allwide) ? (prim ? 1u : wf_exact) : 0u;
-                            // (beside the persistent kernel: a SMALL grid - every workgroup of it takes a slot from k_wf_trace for as
-                            // long as it runs, and 2048 workgroups held most of the chip for milliseconds: closed room 185 -> 199 ms.
-                            // PT_WF_EXACT_BLOCKS: workgroups per 8 CUs)
-                            static const uint32_t exact_blocks = [] {
-                                const char* e = getenv("PT_WF_EXACT_BLOCKS");
-                                return (uint32_t)(e && *e ? atoi(e) : 4);
-                            }();
-                            auto launch_exact = [&](hipStream_t st_exact) {
-                                const dim3 eg(W.exact_handover == 2u ? std::max(1u, (uint32_t)s.n_cu * exact_blocks / 8u) : (uint32_t)s.n_cu * 16u);
-#define PT_LAUNCH_EXACT(C, A, P)                                                                                               \
-    hipLaunchKernelGGL((k_wf_trace_exact<C, A, P>), eg, dim3(WF_EXACT_THREADS), 0, st_exact, dev, W, d_tiles, (const float4*)q_in, \
-                       (uint4*)pipe.hits.p, (const uint4*)rng_planes, (uint32_t*)pipe.draws.p, (uint32_t*)pipe.exact[b & 1].p, \
-                       (const WfCounters*)wctr, gctr)
-                                if (prim) {
-                                    if (alpha && counting) PT_LAUNCH_EXACT(true, true, true);
-                                    else if (alpha) PT_LAUNCH_EXACT(false, true, true);
-                                    else if (counting) PT_LAUNCH_EXACT(true, false, true);
-                                    else PT_LAUNCH_EXACT(false, false, true);
-                                } else {
-                                    if (alpha && counting) PT_LAUNCH_EXACT(true, true, false);
-                                    else if (alpha) PT_LAUNCH_EXACT(false, true, false);
-                                    else if (counting) PT_LAUNCH_EXACT(true, false, false);
-                                    else PT_LAUNCH_EXACT(false, false, false);
-                                }
-#undef PT_LAUNCH_EXACT
-                                HIP_CHECK(hipGetLastError());
-                            };
-                            if (W.exact_handover == 2u) {
-                                if (split_shade) {
-                                    HIP_CHECK(hipEventRecord(pipe.ev_exact_go, st_main));   // (the shade pass that listed them is done)
-                                    HIP_CHECK(hipStreamWaitEvent(pipe.side_exact, pipe.ev_exact_go, 0));
-                                    launch_exact(pipe.side_exact);
-                                    HIP_CHECK(hipEventRecord(pipe.ev_exact, pipe.side_exact));
-                                } else {
-                                    launch_exact(st_main);
-                                }
-                            }
-                            if (allwide) {
-                                hipLaunchKernelGGL(k_wf_list_identity, dim3((uint32_t)s.n_cu * 8u), dim3(256), 0, st_main,
-                                                   (uint32_t*)pipe.deferred.p, W.list_cap, wctr, b);
-                                HIP_CHECK(hipGetLastError());
-                            } else {
-                                PT_LAUNCH_ACP(k_wf_trace, s.trace_blocks, WF_THREADS, dev, W, d_tiles, q_in, (uint4*)pipe.hits.p,
-                                              (const uint4*)rng_planes, (uint32_t*)pipe.draws.p, (uint32_t*)pipe.deferred.p,
-                                              (uint32_t*)pipe.exact[b & 1].p, wctr, gctr);
-                            }
-                            if (W.exact_handover == 1u) {   // behind k_wf_trace: beside the shade pass over the queue if that is split off
-                                if (split_shade) {
-                                    HIP_CHECK(hipEventRecord(pipe.ev_exact_go, st_main));
-                                    HIP_CHECK(hipStreamWaitEvent(pipe.side_exact, pipe.ev_exact_go, 0));
-                                    launch_exact(pipe.side_exact);
-                                    HIP_CHECK(hipEventRecord(pipe.ev_exact, pipe.side_exact));
-                                } else {
-                                    launch_exact(st_main);
-                                }
-                            }
-                            if (W.defer_age) {   // the casts the drained wavefronts handed over (pt_wavefront.h)
-                                // split shade pass: on a stream of its own, underneath k_wf_shade's pass over the queue
-                                hipStream_t st_wide = split_shade ? pipe.side_wide : st_main;
-                                // (16 Ki casts per pass; a workgroup without a cast returns at once)
-                                const uint32_t wide_grid = allwide ? (uint32_t)s.trace_blocks * 4u
-                                                                   : (uint32_t)s.n_cu * 4u * (WF_WIDE_LANES / 16u > 0u ? WF_WIDE_LANES / 16u : 1u);
-                                uint4* wide_hits = split_shade ? list_hits : (uint4*)pipe.hits.p;
-                                if (split_shade) {
-                                    HIP_CHECK(hipEventRecord(pipe.ev_trace, st_main));
-                                    HIP_CHECK(hipStreamWaitEvent(st_wide, pipe.ev_trace, 0));
-                                }
-#define PT_LAUNCH_WIDE(C, A)                                                                                                  \
-    hipLaunchKernelGGL((k_wf_trace_wide<C, A>), dim3(wide_grid), dim3(WF_THREADS), 0, st_wide, dev, W, d_tiles, (const float4*)q_in, \
-                       wide_hits, (const uint4*)rng_planes, (uint32_t*)pipe.draws.p, (const uint32_t*)pipe.deferred.p,             \
-                       (const WfCounters*)wctr, gctr)
-                                if (alpha && counting) PT_LAUNCH_WIDE(true, true);
-                                else if (alpha) PT_LAUNCH_WIDE(false, true);
-                                else if (counting) PT_LAUNCH_WIDE(true, false);
-                                else PT_LAUNCH_WIDE(false, false);
-#undef PT_LAUNCH_WIDE
-                                HIP_CHECK(hipGetLastError());
-                            }
-                            if (split_shade) HIP_CHECK(hipEventRecord(pipe.ev_wide, pipe.side_wide));
-                        }
-                        stage_end();
-                        ++launches;
-                    }
-                    // shade(b) reads the colours shadow(b-1) patched and refills the shadow queue it consumed
-                    if (st_shadow != st_main && b > 0) HIP_CHECK(hipStreamWaitEvent(st_main, pipe.ev_shadow, 0));
-                    // (no more workgroups than the chunk has 256-entry steps)
-                    uint32_t shade_grid = std::max(1u, std::min((uint32_t)s.n_cu * (prim ? shade_blocks_b0 : shade_blocks_later),
-                                                                (W.n_items + WF_SHADE_THREADS - 1u) / WF_SHADE_THREADS));
-                    if (timing && grid_mode >= 2) fused_marks.push_back(ev);
-                    stage_begin(2);
-                    // (+4: the variants with the orthographic branch for directional lights compiled in)
-                    const bool dirl = s.ortho_light_grids;
-                    const uint4* shade_hits = (const uint4*)pipe.hits.p;
-                    const uint32_t* shade_list = nullptr;
-                    auto launch_shade = [&]() {
-                        if (grid_mode == 3) {
-                            if (dirl) PT_LAUNCH_SHADE_P(7);
-                            else PT_LAUNCH_SHADE_P(3);
-                        } else if (grid_mode == 2) {
-                            if (dirl) PT_LAUNCH_SHADE_P(6);
-                            else PT_LAUNCH_SHADE_P(2);
-                        } else if (grid_mode == 1) {
-                            if (dirl) PT_LAUNCH_SHADE_G(5);
-                            else PT_LAUNCH_SHADE_G(1);
-                        } else {
-                            PT_LAUNCH_SHADE_G(0);
-                        }
-                        HIP_CHECK(hipGetLastError());
-                    };
-                    launch_shade();
-                    if (split_shade) {
-                        // ... and the casts that were with k_wf_trace_wide meanwhile: the hand-over list (at most one entry per
-                        // lane of the trace grid; usually a few thousand - a launch that finds an empty list returns)
-                        HIP_CHECK(hipStreamWaitEvent(st_main, pipe.ev_wide, 0));
-                        if (W.exact_handover) HIP_CHECK(hipStreamWaitEvent(st_main, pipe.ev_exact, 0));
-                        shade_hits = (const uint4*)((const uint32_t*)pipe.deferred.p + W.list_cap);
-                        shade_list = (const uint32_t*)pipe.deferred.p;
-                        shade_grid = std::min(shade_grid, (uint32_t)s.n_cu);
-                        launch_shade();
-                    }
-                    HIP_CHECK(hipGetLastError());
-                    stage_end();
-                    // (inline casts leave at most a few records in the shadow queue: that launch stays on the main stream,
-                    // behind a persistent trace grid on another stream it would wait milliseconds for a free slot)
-                    hipStream_t st_shadow_main = st_shadow;
-                    if (grid_mode != 0) st_shadow = st_main;
-                    if (st_shadow != st_main) {
-                        HIP_CHECK(hipEventRecord(pipe.ev_shade, st_main));
-                        HIP_CHECK(hipStreamWaitEvent(st_shadow, pipe.ev_shade, 0));
-                    }
-                    stage_stream = st_shadow;
-                    stage_begin(3);
-                    WfParams Ws = W;
-                    if (wf_refill_shadow) Ws.refill_min = std::min(64u, wf_refill_shadow);
-                    if (wf_walk_shadow) Ws.walk_steps = wf_walk_shadow;
-#define PT_OGS_ARGS                                                                                                    \
-    dev, Ws, (const float4*)pipe.shadow.p, (const float4*)pipe.contrib.p, q_out, (float*)s.staging_buf.p, \
-        (uint32_t*)pipe.offgrid.p, wctr, gctr
-                    if (grid_mode != 0) {
-                        // what is left in the shadow queue: surfaces with a normal too long for the grids' margin
-                        // (normally none: the launch finds an empty queue and returns)
-                        if (counting) hipLaunchKernelGGL((k_og_shadow_offgrid<true, false>), dim3((uint32_t)s.n_cu), dim3(256), 0, st_shadow, PT_OGS_ARGS);
-                        else hipLaunchKernelGGL((k_og_shadow_offgrid<false, false>), dim3((uint32_t)s.n_cu), dim3(256), 0, st_shadow, PT_OGS_ARGS);
-                        HIP_CHECK(hipGetLastError());
-                    } else if (use_light_grids) {   // every light a point light with a grid: plain grid-stride kernel
-                        static const uint32_t ogs_blocks = [] {   // workgroups per CU of k_og_shadow's grid-stride launch
-                            const char* e = getenv("PT_OGS_BLOCKS");
-                            return (uint32_t)(e && *e ? atoi(e) : 16);
-                        }();
-                        const dim3 g((uint32_t)s.n_cu * std::max(1u, ogs_blocks));
-#define PT_LAUNCH_OGSH(A, C)                                                                                   \
-    do {                                                                                                       \
-        if (s.ortho_light_grids) hipLaunchKernelGGL((k_og_shadow<A, C, true>), g, dim3(256), 0, st_shadow, PT_OGS_ARGS); \
-        else hipLaunchKernelGGL((k_og_shadow<A, C, false>), g, dim3(256), 0, st_shadow, PT_OGS_ARGS);          \
-    } while (0)
-                        if (alpha && counting) PT_LAUNCH_OGSH(true, true);
-                        else if (alpha) PT_LAUNCH_OGSH(true, false);
-                        else if (counting) PT_LAUNCH_OGSH(false, true);
-                        else PT_LAUNCH_OGSH(false, false);
-#undef PT_LAUNCH_OGSH
-                        HIP_CHECK(hipGetLastError());
-                        if (counting) hipLaunchKernelGGL((k_og_shadow_offgrid<true, true>), dim3((uint32_t)s.n_cu), dim3(256), 0, st_shadow, PT_OGS_ARGS);
-                        else hipLaunchKernelGGL((k_og_shadow_offgrid<false, true>), dim3((uint32_t)s.n_cu), dim3(256), 0, st_shadow, PT_OGS_ARGS);
-                        HIP_CHECK(hipGetLastError());
-                    } else {
-                        PT_LAUNCH_AC(k_wf_shadow, s.shadow_blocks, dev, Ws, (float4*)pipe.shadow.p,
-                                     (const float4*)pipe.contrib.p, q_out, (float*)s.staging_buf.p, (uint32_t*)pipe.offgrid.p, wctr, gctr);
-                        // ... and the jobs it set aside: a shadow ray the wavefront walker does not take (normally a few per mille)
-                        if (Ws.exact_handover) {
-                            if (counting) hipLaunchKernelGGL((k_og_shadow_offgrid<true, true>), dim3((uint32_t)s.n_cu * 4u), dim3(256), 0, st_shadow, PT_OGS_ARGS);
-                            else hipLaunchKernelGGL((k_og_shadow_offgrid<false, true>), dim3((uint32_t)s.n_cu * 4u), dim3(256), 0, st_shadow, PT_OGS_ARGS);
-                            HIP_CHECK(hipGetLastError());
-                        }
-                    }
-                    stage_end();
-                    stage_stream = st_main;
-                    if (st_shadow != st_main) HIP_CHECK(hipEventRecord(pipe.ev_shadow, st_shadow));
-                    else if (st_shadow_main != st_main) HIP_CHECK(hipEventRecord(pipe.ev_shadow, st_main));   // (keeps the waits below valid)
-                    st_shadow = st_shadow_main;
-#undef PT_OGS_ARGS
-#undef PT_LAUNCH_ACP
-#undef PT_LAUNCH_AC
-#undef PT_LAUNCH_SHADE_P
-#undef PT_LAUNCH_SHADE_G
-#undef PT_LAUNCH_SHADE
-#undef PT_SHADE_ARGS
-                }
-                // the next chunk clears the counters and reuses the queues, accumulate reads the staging area:
-                // join the side stream
-                if (st_shadow != st_main) HIP_CHECK(hipStreamWaitEvent(st_main, pipe.ev_shadow, 0));
-                if (fs && stats_slots && stats_line < stats_slots) {   // this chunk's counts: one line of the frame's statistics
-                    hipLaunchKernelGGL(k_wf_stats, dim3(1), dim3(64u * ((p.bounces + 3u + 63u) / 64u)), 0, st_main, (const WfCounters*)wctr,
-                                       p.bounces + 3u, (uint32_t*)s.stats_dev.p + (size_t)stats_line * (p.bounces + 3u) * 4u);
-                    HIP_CHECK(hipGetLastError());
-                    fs->first_item_of_slot[stats_line] = base;
-                    ++stats_line;
-                }
+// What the stages of one bounce of a chunk launch with.
+struct Chunk {
+    WfParams W{};
+    hipStream_t st_main = nullptr, st_shadow = nullptr;
+    uint4* rng_planes = nullptr;
+    WfCounters* wctr = nullptr;
+    uint32_t b = 0;      // the bounce
+    bool prim = false;   // bounce 0: the camera rays, derived in place from the staged screen positions (no queue[0])
+    // origin grids (pt_grid.h): 3 / 2 = camera cast + shadow casts inside the shade kernel (bounce 0, both kinds of grid;
+    // 3: the kernel computes the ChaCha block itself), 1 = shadow casts inside the shade kernel, 0 = none
+    int grid_mode = 0;
+    float4 *q_in = nullptr, *q_out = nullptr;
+    bool split_shade = false;   // the shade pass in two launches (PT_WF_SPLIT)
+};
+
+// The casts of a bounce: the camera rays through the camera grid (k_og_primary), or k_wf_trace with its hand-overs to
+// k_wf_trace_exact and k_wf_trace_wide.
+void trace_stage(pt_scene& s, const Frame& f, Chunk& c, Timeline& tl) {
+    const pt_scene::WfPipe& pipe = s.pipe;
+    WfParams& W = c.W;
+    const uint32_t b = c.b;
+    tl.begin(1);
+    if (c.prim && f.use_cam_grid) {   // camera rays: one grid lookup instead of a KD walk (pt_grid_kernels.h)
+        dispatch([&](auto alpha, auto count) {
+            hipLaunchKernelGGL((k_og_primary<alpha, count>), dim3((W.n_items + 255u) / 256u), dim3(256), 0, c.st_main, f.dev, W, f.d_tiles,
+                               (uint4*)pipe.hits.p, (const uint4*)c.rng_planes, (uint32_t*)pipe.draws.p, f.gctr);
+        }, f.alpha, f.counting);
+        HIP_CHECK(hipGetLastError());
+    } else {
+        W.defer_age = c.prim ? 0u : f.env.defer;
+        // the hand-over list: queue indices, then (split shade pass) the plane of their hits
+        const uint32_t list_cap = (uint32_t)s.trace_blocks * WF_THREADS;
+        uint4* list_hits = (uint4*)((uint32_t*)pipe.deferred.p + list_cap);
+        c.split_shade = f.env.split && W.defer_age != 0u && pipe.side_wide != nullptr;
+        W.list_cap = list_cap;
+        W.split_deferred = c.split_shade ? 1u : 0u;
+        // The casts the wavefront walker does not take (slack_is_capped): one lane each on the grown-box walker.
+        // Bounces >= 1: k_wf_shade listed them when it made the rays, so the launch goes out BEFORE the
+        // persistent kernel, on a stream of its own, and runs beside it (its few hundred workgroups take
+        // their slots first; the persistent grid's last workgroups start as those free up).  Camera rays of
+        // the KD-tree pipeline: k_wf_trace lists them, the launch follows it.
+        W.exact_handover = f.env.exact ? (c.prim ? 1u : f.env.exact) : 0u;
+        // (beside the persistent kernel: a SMALL grid - every workgroup of it takes a slot from k_wf_trace for as
+        // long as it runs, and 2048 workgroups held most of the chip for milliseconds: closed room 185 -> 199 ms.
+        // PT_WF_EXACT_BLOCKS: workgroups per 8 CUs)
+        auto launch_exact = [&](hipStream_t st_exact) {
+            const dim3 eg(W.exact_handover == 2u ? std::max(1u, (uint32_t)s.n_cu * f.env.exact_blocks / 8u) : (uint32_t)s.n_cu * 16u);
+            dispatch([&](auto count, auto alpha, auto prim) {
+                hipLaunchKernelGGL((k_wf_trace_exact<count, alpha, prim>), eg, dim3(WF_EXACT_THREADS), 0, st_exact, f.dev, W, f.d_tiles,
+                                   (const float4*)c.q_in, (uint4*)pipe.hits.p, (const uint4*)c.rng_planes, (uint32_t*)pipe.draws.p,
+                                   (uint32_t*)pipe.exact[b & 1].p, (const WfCounters*)c.wctr, f.gctr);
+            }, f.counting, f.alpha, c.prim);
+            HIP_CHECK(hipGetLastError());
+        };
+        auto exact_pass = [&] {   // beside the shade pass over the queue if that is split off
+            if (c.split_shade) {
+                HIP_CHECK(hipEventRecord(pipe.ev_exact_go, c.st_main));   // (the shade pass that listed them is done)
+                HIP_CHECK(hipStreamWaitEvent(pipe.side_exact, pipe.ev_exact_go, 0));
+                launch_exact(pipe.side_exact);
+                HIP_CHECK(hipEventRecord(pipe.ev_exact, pipe.side_exact));
+            } else {
+                launch_exact(c.st_main);
             }
-        }
-        if (mode >= 1) {
-            stage_begin(4);
-            hipLaunchKernelGGL(k_accumulate, dim3(((uint32_t)tm.n_local + 255u) / 256u), dim3(256), 0, stream,
-                               (const float*)s.staging_buf.p, accum, (uint32_t)tm.n_local, nb, s0 == 0 ? 1 : 0,
-                               block_empty ? (const uint8_t*)(block_empty + blocks64 + 1u) : (const uint8_t*)nullptr,
-                               s.dev.background[0], s.dev.background[1], s.dev.background[2]);
+        };
+        if (W.exact_handover == 2u) exact_pass();
+        dispatch([&](auto alpha, auto count, auto prim) {
+            hipLaunchKernelGGL((k_wf_trace<alpha, count, prim>), dim3(s.trace_blocks), dim3(WF_THREADS), 0, c.st_main, f.dev, W, f.d_tiles,
+                               c.q_in, (uint4*)pipe.hits.p, (const uint4*)c.rng_planes, (uint32_t*)pipe.draws.p, (uint32_t*)pipe.deferred.p,
+                               (uint32_t*)pipe.exact[b & 1].p, c.wctr, f.gctr);
+        }, f.alpha, f.counting, c.prim);
+        HIP_CHECK(hipGetLastError());
+        if (W.exact_handover == 1u) exact_pass();   // behind k_wf_trace
+        if (W.defer_age) {   // the casts the drained wavefronts handed over (pt_wavefront.h)
+            // split shade pass: on a stream of its own, underneath k_wf_shade's pass over the queue
+            hipStream_t st_wide = c.split_shade ? pipe.side_wide : c.st_main;
+            // (16 Ki casts per pass; a workgroup without a cast returns at once)
+            const uint32_t wide_grid = (uint32_t)s.n_cu * 4u * (WF_WIDE_LANES / 16u > 0u ? WF_WIDE_LANES / 16u : 1u);
+            uint4* wide_hits = c.split_shade ? list_hits : (uint4*)pipe.hits.p;
+            if (c.split_shade) {
+                HIP_CHECK(hipEventRecord(pipe.ev_trace, c.st_main));
+                HIP_CHECK(hipStreamWaitEvent(st_wide, pipe.ev_trace, 0));
+            }
+            dispatch([&](auto count, auto alpha) {
+                hipLaunchKernelGGL((k_wf_trace_wide<count, alpha>), dim3(wide_grid), dim3(WF_THREADS), 0, st_wide, f.dev, W, f.d_tiles,
+                                   (const float4*)c.q_in, wide_hits, (const uint4*)c.rng_planes, (uint32_t*)pipe.draws.p,
+                                   (const uint32_t*)pipe.deferred.p, (const WfCounters*)c.wctr, f.gctr);
+            }, f.counting, f.alpha);
             HIP_CHECK(hipGetLastError());
-            stage_end();
         }
-        if (allow_preview && o.preview && d_rgb8) {
-            // viewer feed (mod.rs:133-141): post_processing(pixel / current_sample) of the samples so far
-            hipLaunchKernelGGL(k_postprocess, dim3(((uint32_t)tm.n_local + 255u) / 256u), dim3(256), 0, stream, accum,
-                               (uint8_t*)d_rgb8, (uint32_t)tm.n_local, P.sample_end, p.tonemap);
-            HIP_CHECK(hipGetLastError());
-            std::vector<uint8_t> host(tm.n_local * 3);
-            HIP_CHECK(hipMemcpyAsync(host.data(), d_rgb8, host.size(), hipMemcpyDeviceToHost, stream));
-            HIP_CHECK(hipStreamSynchronize(stream));
-            o.preview(host.data(), tm.n_local, P.sample_end, p.samples, o.preview_user);
-        }
-        if (o.progress) {
-            HIP_CHECK(hipStreamSynchronize(stream));
-            o.progress(P.sample_end, p.samples, o.progress_user);
-        }
+        if (c.split_shade) HIP_CHECK(hipEventRecord(pipe.ev_wide, pipe.side_wide));
     }
-    if (fs && stats_slots && stats_line == stats_slots) {   // the frame's counts on their way to the host (read when the next frame is planned)
-        HIP_CHECK(hipMemcpyAsync(fs->host, s.stats_dev.p, (size_t)stats_slots * (p.bounces + 3u) * 16u, hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipEventRecord(fs->done, stream));
-        fs->pending = true;
+    tl.end();
+    ++tl.launches;
+}
+
+// k_wf_shade over the bounce's queue (split shade pass: then over the casts k_wf_trace_wide took meanwhile).
+void shade_stage(pt_scene& s, const Frame& f, const WfFrame& wf, const Chunk& c, Timeline& tl) {
+    const pt_scene::WfPipe& pipe = s.pipe;
+    const WfParams& W = c.W;
+    const uint32_t b = c.b;
+    // shade(b) reads the colours shadow(b-1) patched and refills the shadow queue it consumed
+    if (c.st_shadow != c.st_main && b > 0) HIP_CHECK(hipStreamWaitEvent(c.st_main, pipe.ev_shadow, 0));
+    // (no more workgroups than the chunk has 256-entry steps)
+    uint32_t shade_grid = std::max(1u, std::min((uint32_t)s.n_cu * (c.prim ? f.env.shade_blocks_b0 : f.env.shade_blocks),
+                                                (W.n_items + WF_SHADE_THREADS - 1u) / WF_SHADE_THREADS));
+    if (tl.on && c.grid_mode >= 2) tl.fused_marks.push_back(tl.ev);
+    tl.begin(2);
+    const uint4* shade_hits = (const uint4*)pipe.hits.p;
+    const uint32_t* shade_list = nullptr;
+    const uint32_t* block_empty = c.grid_mode >= 2 ? wf.block_empty : nullptr;
+    // k_wf_shade<ALPHA, COUNT, PRIMARY, GRID>; GRID + 4: the variants with the orthographic branch for directional lights
+    // compiled in.  GRID 2 and 3 cast the camera rays: they exist for PRIMARY only.
+    auto launch = [&](auto grid) {
+        constexpr int G = decltype(grid)::value;
+        auto go = [&](auto alpha, auto count, auto prim) {
+            hipLaunchKernelGGL((k_wf_shade<alpha, count, prim, G>), dim3(shade_grid), dim3(WF_SHADE_THREADS), 0, c.st_main, f.dev, W,
+                               f.d_tiles, (const float4*)c.q_in, shade_hits, (const uint4*)c.rng_planes, (const uint32_t*)pipe.draws.p,
+                               c.q_out, (float4*)pipe.shadow.p, (float4*)pipe.contrib.p, (float*)s.staging_buf.p, shade_list,
+                               (const uint32_t*)pipe.exact[b & 1].p, (const uint4*)pipe.hits.p, (uint32_t*)pipe.exact[(b + 1) & 1].p,
+                               block_empty, c.wctr, f.gctr);
+        };
+        if constexpr ((G & 3) >= 2) dispatch([&](auto alpha, auto count) { go(alpha, count, std::true_type{}); }, f.alpha, f.counting);
+        else dispatch(go, f.alpha, f.counting, c.prim);
+        HIP_CHECK(hipGetLastError());
+    };
+    auto launch_shade = [&] {
+        switch (c.grid_mode == 0 ? 0 : c.grid_mode + (s.ortho_light_grids ? 4 : 0)) {
+        case 0: launch(std::integral_constant<int, 0>{}); break;
+        case 1: launch(std::integral_constant<int, 1>{}); break;
+        case 2: launch(std::integral_constant<int, 2>{}); break;
+        case 3: launch(std::integral_constant<int, 3>{}); break;
+        case 5: launch(std::integral_constant<int, 5>{}); break;
+        case 6: launch(std::integral_constant<int, 6>{}); break;
+        default: launch(std::integral_constant<int, 7>{}); break;
+        }
+    };
+    launch_shade();
+    if (c.split_shade) {
+        // ... and the casts that were with k_wf_trace_wide meanwhile: the hand-over list (at most one entry per
+        // lane of the trace grid; usually a few thousand - a launch that finds an empty list returns)
+        HIP_CHECK(hipStreamWaitEvent(c.st_main, pipe.ev_wide, 0));
+        if (W.exact_handover) HIP_CHECK(hipStreamWaitEvent(c.st_main, pipe.ev_exact, 0));
+        shade_hits = (const uint4*)((const uint32_t*)pipe.deferred.p + W.list_cap);
+        shade_list = (const uint32_t*)pipe.deferred.p;
+        shade_grid = std::min(shade_grid, (uint32_t)s.n_cu);
+        launch_shade();
     }
-    const size_t ev_post = ev;
-    if (timing) HIP_CHECK(hipEventRecord(get_event(s, ev++), stream));
+    tl.end();
+}
+
+// The shadow casts the shade pass left in the shadow queue: on the side stream, beside the next bounce's trace.
+void shadow_stage(pt_scene& s, const Frame& f, const Chunk& c, Timeline& tl) {
+    const pt_scene::WfPipe& pipe = s.pipe;
+    // (inline casts leave at most a few records in the shadow queue: that launch stays on the main stream,
+    // behind a persistent trace grid on another stream it would wait milliseconds for a free slot)
+    const hipStream_t st_shadow = c.grid_mode != 0 ? c.st_main : c.st_shadow;
+    if (st_shadow != c.st_main) {
+        HIP_CHECK(hipEventRecord(pipe.ev_shade, c.st_main));
+        HIP_CHECK(hipStreamWaitEvent(st_shadow, pipe.ev_shade, 0));
+    }
+    tl.stream = st_shadow;
+    tl.begin(3);
+    WfParams Ws = c.W;
+    if (f.env.refill_shadow) Ws.refill_min = std::min(64u, f.env.refill_shadow);
+    if (f.env.walk_shadow) Ws.walk_steps = f.env.walk_shadow;
+    // what is left to k_og_shadow_offgrid: surfaces with a normal too long for the grids' margin, the rays the wavefront
+    // walker does not take (normally none, or a few per mille: the launch finds an empty queue and returns)
+    auto offgrid = [&](auto list, uint32_t grid) {
+        constexpr bool LIST = decltype(list)::value;
+        dispatch([&](auto count) {
+            hipLaunchKernelGGL((k_og_shadow_offgrid<count, LIST>), dim3(grid), dim3(256), 0, st_shadow, f.dev, Ws, (const float4*)pipe.shadow.p,
+                               (const float4*)pipe.contrib.p, c.q_out, (float*)s.staging_buf.p, (uint32_t*)pipe.offgrid.p, c.wctr, f.gctr);
+        }, f.counting);
+        HIP_CHECK(hipGetLastError());
+    };
+    if (c.grid_mode != 0) {
+        offgrid(std::false_type{}, (uint32_t)s.n_cu);
+    } else if (f.use_light_grids) {   // every light a point light with a grid: plain grid-stride kernel
+        const dim3 g((uint32_t)s.n_cu * std::max(1u, f.env.ogs_blocks));
+        dispatch([&](auto alpha, auto count, auto dirl) {
+            hipLaunchKernelGGL((k_og_shadow<alpha, count, dirl>), g, dim3(256), 0, st_shadow, f.dev, Ws, (const float4*)pipe.shadow.p,
+                               (const float4*)pipe.contrib.p, c.q_out, (float*)s.staging_buf.p, (uint32_t*)pipe.offgrid.p, c.wctr, f.gctr);
+        }, f.alpha, f.counting, s.ortho_light_grids);
+        HIP_CHECK(hipGetLastError());
+        offgrid(std::true_type{}, (uint32_t)s.n_cu);
+    } else {
+        dispatch([&](auto alpha, auto count) {
+            hipLaunchKernelGGL((k_wf_shadow<alpha, count>), dim3(s.shadow_blocks), dim3(WF_THREADS), 0, st_shadow, f.dev, Ws, (float4*)pipe.shadow.p,
+                               (const float4*)pipe.contrib.p, c.q_out, (float*)s.staging_buf.p, (uint32_t*)pipe.offgrid.p, c.wctr, f.gctr);
+        }, f.alpha, f.counting);
+        HIP_CHECK(hipGetLastError());
+        if (Ws.exact_handover) offgrid(std::true_type{}, (uint32_t)s.n_cu * 4u);   // ... and the jobs k_wf_shadow set aside
+    }
+    tl.end();
+    tl.stream = c.st_main;
+    if (st_shadow != c.st_main) HIP_CHECK(hipEventRecord(pipe.ev_shadow, st_shadow));
+    else if (c.st_shadow != c.st_main) HIP_CHECK(hipEventRecord(pipe.ev_shadow, c.st_main));   // (keeps the waits below valid)
+}
+
+// Work items [base, base + cap) of a sample batch: their RNG planes, then per bounce the trace, shade and shadow stages.
+void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const RenderParams& P, hipStream_t stream,
+                  uint32_t base, uint32_t total_items, uint32_t chunk_no) {
+    const pt_scene::WfPipe& pipe = s.pipe;
+    Chunk c;
+    c.st_main = stream;
+    c.st_shadow = f.env.overlap ? pipe.side : stream;
+    // opaque scenes, several chunks: the RNG planes of chunk c+1 are produced on their own stream while
+    // chunk c runs its bounces (k_wf_rng is pure integer ALU work; the traversal kernels leave ~40 % of
+    // the issue slots idle and end in a drain phase)
+    // both kinds of grid: the bounce-0 kernel computes the ChaCha block itself (GRID 3; PT_OG_FUSE_RNG=0: off)
+    const bool fused_rng = wf.rng_one_plane;
+    const bool rng_ahead = !fused_rng && f.env.overlap && total_items > wf.cap && pipe.side != nullptr && pipe.ev_rng != nullptr;
+    WfParams& W = c.W;
+    W.P = P;
+    W.item_base = base;
+    W.n_items = std::min(wf.cap, total_items - base);
+    W.cap = wf.cap;
+    W.hcap = wf.cap_h;
+    W.scap = wf.cap_s;
+    W.ecap = wf.cap_e;
+    W.qcap_in = wf.cap_q[0];
+    W.qcap_out = wf.cap_q[1];
+    W.rng_first_plane = wf.rng_one_plane ? 1u : 0u;
+    W.n_mask_blocks = f.blocks64;
+    c.rng_planes = (uint4*)pipe.rng[rng_ahead ? (chunk_no & 1u) : 0u].p;
+    W.sort_octants = f.env.sort;
+    W.use_entry = f.env.entry;
+    W.exact_handover = f.env.exact ? 1u : 0u;   // (per bounce in trace_stage: 1 k_wf_trace lists, 2 k_wf_shade listed)
+    W.exact_shade_lists = f.env.exact == 2u ? 1u : 0u;
+    W.refill_min = std::max(1u, std::min(64u, f.env.refill));
+    W.walk_steps = f.env.walk ? f.env.walk : 20u;
+    c.wctr = (WfCounters*)pipe.ctr.p;
+    HIP_CHECK(hipMemsetAsync(c.wctr, 0, sizeof(WfCounters) * (f.p.bounces + 3), c.st_main));
+    if (fused_rng) {
+        // (no k_wf_rng launch)
+    } else if (!rng_ahead || chunk_no == 0) {
+        tl.begin(0);
+        hipLaunchKernelGGL(k_wf_rng, dim3((W.n_items + 255u) / 256u), dim3(256), 0, c.st_main, f.dev, W, f.d_tiles, c.rng_planes);
+        HIP_CHECK(hipGetLastError());
+        tl.end();
+    } else {
+        HIP_CHECK(hipStreamWaitEvent(c.st_main, pipe.ev_rng, 0));  // produced underneath the previous chunk
+    }
+    if (rng_ahead && base + wf.cap < total_items) {
+        // the other copy was last read by chunk c-1, which has completed on st_main by now
+        WfParams Wn = W;
+        Wn.item_base = base + wf.cap;
+        Wn.n_items = std::min(wf.cap, total_items - Wn.item_base);
+        HIP_CHECK(hipEventRecord(pipe.ev_chunk, c.st_main));
+        HIP_CHECK(hipStreamWaitEvent(pipe.side, pipe.ev_chunk, 0));
+        tl.stream = pipe.side;
+        tl.begin(0);
+        hipLaunchKernelGGL(k_wf_rng, dim3((Wn.n_items + 255u) / 256u), dim3(256), 0, pipe.side, f.dev, Wn, f.d_tiles,
+                           (uint4*)pipe.rng[(chunk_no + 1u) & 1u].p);
+        HIP_CHECK(hipGetLastError());
+        tl.end();
+        tl.stream = c.st_main;
+        HIP_CHECK(hipEventRecord(pipe.ev_rng, pipe.side));
+    }
+    // (the plan knows where this chunk's last ray ends: the launches of the bounces behind it - ~85 us each for nothing -
+    // are not made; PT_PLAN_SKIP=0: all of them)
+    const uint32_t b_end = (wf.plan_last && wf.chunk_slot < wf.plan_last->size()) ? std::min(f.p.bounces, (*wf.plan_last)[wf.chunk_slot]) : f.p.bounces;
+    ++wf.chunk_slot;
+    for (uint32_t b = 0; b <= b_end; ++b) {
+        W.bounce = b;
+        W.qcap_in = wf.cap_q[b & 1u];          // (queue b lives in pipe.queue[b & 1])
+        W.qcap_out = wf.cap_q[(b + 1u) & 1u];
+        // (node steps per walking phase: 12 until the escape masks took the short casts out of the queues; re-swept on the rays that
+        // are left - 12 / 14 / 16 / 18: config 3 40.3-40.8 / 40.3-40.4 / 39.7-39.8 / 39.8-40.0 ms, closed room 173.9 -> 171.4)
+        W.walk_steps = f.env.walk ? f.env.walk : (b == 0 ? 20u : 16u);
+        c.b = b;
+        c.q_in = (float4*)pipe.queue[b & 1].p;
+        c.q_out = (float4*)pipe.queue[(b + 1) & 1].p;
+        c.prim = b == 0;
+        // (bounces >= 1: shadow casts inline with PT_OG_INLINE_ALL, or where the frame plan found (nearly) every ray of the
+        // bounce reaching a lit surface)
+        c.grid_mode = (c.prim && f.bounce0_fused) ? (fused_rng ? 3 : 2)
+                                                  : (f.use_light_grids && (f.env.inline_all || (b < wf.inline_at.size() && wf.inline_at[b])) ? 1 : 0);
+        c.split_shade = false;
+        if (c.grid_mode < 2) trace_stage(s, f, c, tl);   // (grid_mode >= 2: k_wf_shade casts the camera rays itself)
+        shade_stage(s, f, wf, c, tl);
+        shadow_stage(s, f, c, tl);
+    }
+    // the next chunk clears the counters and reuses the queues, accumulate reads the staging area:
+    // join the side stream
+    if (c.st_shadow != c.st_main) HIP_CHECK(hipStreamWaitEvent(c.st_main, pipe.ev_shadow, 0));
+    if (wf.stats_slots && wf.stats_line < wf.stats_slots) {   // this chunk's counts: one line of the frame's statistics
+        hipLaunchKernelGGL(k_wf_stats, dim3(1), dim3(64u * ((f.p.bounces + 3u + 63u) / 64u)), 0, c.st_main, (const WfCounters*)c.wctr,
+                           f.p.bounces + 3u, (uint32_t*)s.stats_dev.p + (size_t)wf.stats_line * (f.p.bounces + 3u) * 4u);
+        HIP_CHECK(hipGetLastError());
+        wf.fs->first_item_of_slot[wf.stats_line] = base;
+        ++wf.stats_line;
+    }
+}
+
+// After the frame's launches: its counts on their way to the host (read when the next frame is planned), the
+// post-processing, timing and counters.
+void frame_readout(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, void* d_rgb8, hipStream_t stream) {
+    const pt_profile& p = f.p;
+    if (wf.stats_slots && wf.stats_line == wf.stats_slots) {
+        HIP_CHECK(hipMemcpyAsync(wf.fs->host, s.stats_dev.p, (size_t)wf.stats_slots * (p.bounces + 3u) * 16u, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipEventRecord(wf.fs->done, stream));
+        wf.fs->pending = true;
+    }
+    const size_t ev_post = tl.ev;
+    if (f.timing) HIP_CHECK(hipEventRecord(get_event(s, tl.ev++), stream));
     if (d_rgb8) {
-        hipLaunchKernelGGL(k_postprocess, dim3(((uint32_t)tm.n_local + 255u) / 256u), dim3(256), 0, stream, accum,
-                           (uint8_t*)d_rgb8, (uint32_t)tm.n_local, p.samples, p.tonemap);
+        hipLaunchKernelGGL(k_postprocess, dim3(((uint32_t)f.tm.n_local + 255u) / 256u), dim3(256), 0, stream, f.accum,
+                           (uint8_t*)d_rgb8, (uint32_t)f.tm.n_local, p.samples, p.tonemap);
         HIP_CHECK(hipGetLastError());
     }
-    if (timing) HIP_CHECK(hipEventRecord(get_event(s, ev++), stream));
-    if (capture.st) {
-        hipGraph_t graph = nullptr;
-        capture.st = nullptr;
-        HIP_CHECK(hipStreamEndCapture(stream, &graph));
-        hipGraphExec_t exec = nullptr;
-        const hipError_t rc = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        HIP_CHECK(rc);
-        if (s.graphs.size() >= 16) {   // (configurations come and go with the caller's buffers: start over)
-            for (auto& g : s.graphs) (void)hipGraphExecDestroy(g.second);
-            s.graphs.clear();
-        }
-        s.graphs.emplace(std::move(graph_key), exec);
-        HIP_CHECK(hipGraphLaunch(exec, user_stream));
-        return;
-    }
+    if (f.timing) HIP_CHECK(hipEventRecord(get_event(s, tl.ev++), stream));
 
-    if (timing || counting || exit_times) HIP_CHECK(hipStreamSynchronize(stream));
-    if (timing) {
+    if (f.timing || f.counting || f.exit_times) HIP_CHECK(hipStreamSynchronize(stream));
+    if (f.timing) {
         pt_timing t{};
-        t.launches = launches;
-        t.stage_launches = stage_launches;
+        t.launches = tl.launches;
+        t.stage_launches = tl.stage_launches;
         float* slot[6] = {&t.generate_ms, &t.trace_ms, &t.shade_ms, &t.shadow_ms, &t.accumulate_ms, &t.integrate_ms};
-        static const bool dump = getenv("PT_DEBUG_TIMES") != nullptr;
-        for (auto& m : marks) {
+        for (auto& m : tl.marks) {
             float ms = 0;
             HIP_CHECK(hipEventElapsedTime(&ms, s.events[m.second], s.events[m.second + 1]));
             *slot[m.first] += ms;
-            if (dump) fprintf(stderr, "[pt] stage %d  %.3f ms\n", m.first, ms);
+            if (f.env.debug_times) fprintf(stderr, "[pt] stage %d  %.3f ms\n", m.first, ms);
         }
-        if (mode == 2) t.integrate_ms = t.trace_ms;  // k_wf_trace launches of the wavefront integrator
-        for (size_t m : fused_marks) {
+        if (f.wavefront) t.integrate_ms = t.trace_ms;  // k_wf_trace launches of the wavefront integrator
+        for (size_t m : tl.fused_marks) {
             float ms = 0;
             HIP_CHECK(hipEventElapsedTime(&ms, s.events[m], s.events[m + 1]));
             t.bounce0_ms += ms;
@@ -2967,26 +2855,94 @@ void render_device(const pt_scene& s, const pt_profile& p, const pt_opts* opts_i
         }
     }
 #endif
-    if (counting) {
+    if (f.counting) {
         DevCounters c;
         HIP_CHECK(hipMemcpy(&c, s.counter_buf.p, sizeof c, hipMemcpyDeviceToHost));
         s.counters = pt_counters{c.samples, c.segments, c.shadow_rays, c.nodes_visited, c.tris_tested, c.shaded_hits,
                                  c.rng_draws, c.restarts, c.max_nodes_per_cast, c.casts_over_1k_nodes,
                                  c.trace_nodes, c.trace_tris, c.shadow_skipped, c.bounce0_hits, c.bounce0_shadow_rays,
                                  c.bounce0_tris, c.grid_tris, c.bounce0_cam_tris, c.deferred_casts, c.exact_casts, c.masked_casts, c.bounce0_masked};
-        if (getenv("PT_DEBUG_HIST")) {   // casts of k_wf_trace by length (bins of 64 node visits; bin 0 not counted)
+        if (f.env.debug_hist) {   // casts of k_wf_trace by length (bins of 64 node visits; bin 0 not counted)
             fprintf(stderr, "[pt] cast length histogram (x64 nodes):");
             for (int b = 1; b < 16; ++b) fprintf(stderr, " %llu", c.cast_hist[b]);
             fprintf(stderr, "\n[pt] wide casts %llu: rounds total %llu max %llu | node steps %llu | time per cast (us): mean %.1f max %.1f\n",
                     c.deferred_casts, c.stamps[0], c.stamps[1], c.stamps[3],
                     c.deferred_casts ? (double)c.stamps[5] / 100.0 / (double)c.deferred_casts : 0.0, (double)c.stamps[4] / 100.0);
         }
-        if (getenv("PT_DEBUG_STAMPS"))
+        if (f.env.debug_stamps)
             fprintf(stderr, "[pt] trace stamps: refill %llu walk %llu leaf %llu complete %llu cycles | walk lanes/step %.1f (%llu steps) | leaf lanes/run %.1f (%llu runs)\n",
                     c.stamps[0], c.stamps[1], c.stamps[2], c.stamps[3], c.stamps[5] ? (double)c.stamps[4] / c.stamps[5] : 0.0,
                     c.stamps[5], c.stamps[7] ? (double)c.stamps[6] / c.stamps[7] : 0.0, c.stamps[7]);
     }
 }
+
+// One frame of pt_render, pt_render_device and pt_render_gathered.
+void render_device(pt_scene& s, const pt_profile& p, const pt_opts* opts_in, void* d_rgb8, void* d_accum,
+                   hipStream_t stream, bool allow_preview = false) {
+    Frame f;
+    if (!frame_setup(s, p, opts_in, d_accum, stream, f)) return;
+    const pt_opts& o = f.o;
+    WfFrame wf;
+    if (f.wavefront) {
+        const QueueEnv qe = queue_env();
+        wf = frame_plan(s, f, qe);
+        queue_buffers(s, f, qe, wf);
+        stats_slots(s, f, wf);
+        side_streams(s, f, wf);
+        wf.plan_last = (wf.planned && f.env.plan_skip) ? &wf.fs->plan_last : nullptr;
+    }
+    Timeline tl{s, f.timing, stream};
+    wf.block_empty = camera_cull(s, f, stream);
+    RenderParams P = f.P;
+    for (uint32_t s0 = 0; s0 < p.samples; s0 += f.batch) {
+        P.sample_begin = s0;
+        P.sample_end = std::min(p.samples, s0 + f.batch);
+        const uint32_t nb = P.sample_end - P.sample_begin;
+        pt_fastdiv_make(nb, P.div_batch);
+        if (!f.wavefront) {
+            const uint32_t blocks = f.tm.n_local_tiles * (o.tile_w * o.tile_h / 256u);
+            tl.begin(5);
+            dispatch([&](auto count) {
+                hipLaunchKernelGGL((k_render<count>), dim3(blocks), dim3(256), 0, stream, f.dev, P, f.d_tiles, f.accum, f.gctr);
+            }, f.counting);
+            HIP_CHECK(hipGetLastError());
+            tl.end();
+            ++tl.launches;
+        } else {
+            const uint32_t total_items = f.blocks64 * 64u * nb;
+            uint32_t chunk_no = 0;
+            for (uint32_t base = 0; base < total_items; base += wf.cap, ++chunk_no)
+                render_chunk(s, f, wf, tl, P, stream, base, total_items, chunk_no);
+            tl.begin(4);
+            hipLaunchKernelGGL(k_accumulate, dim3(((uint32_t)f.tm.n_local + 255u) / 256u), dim3(256), 0, stream,
+                               (const float*)s.staging_buf.p, f.accum, (uint32_t)f.tm.n_local, nb, s0 == 0 ? 1 : 0,
+                               wf.block_empty ? (const uint8_t*)(wf.block_empty + f.blocks64 + 1u) : (const uint8_t*)nullptr,
+                               s.dev.background[0], s.dev.background[1], s.dev.background[2]);
+            HIP_CHECK(hipGetLastError());
+            tl.end();
+        }
+        if (allow_preview && o.preview && d_rgb8) {
+            // viewer feed (mod.rs:133-141): post_processing(pixel / current_sample) of the samples so far
+            hipLaunchKernelGGL(k_postprocess, dim3(((uint32_t)f.tm.n_local + 255u) / 256u), dim3(256), 0, stream, f.accum,
+                               (uint8_t*)d_rgb8, (uint32_t)f.tm.n_local, P.sample_end, p.tonemap);
+            HIP_CHECK(hipGetLastError());
+            std::vector<uint8_t> host(f.tm.n_local * 3);
+            HIP_CHECK(hipMemcpyAsync(host.data(), d_rgb8, host.size(), hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipStreamSynchronize(stream));
+            o.preview(host.data(), f.tm.n_local, P.sample_end, p.samples, o.preview_user);
+        }
+        if (o.progress) {
+            HIP_CHECK(hipStreamSynchronize(stream));
+            o.progress(P.sample_end, p.samples, o.progress_user);
+        }
+    }
+    frame_readout(s, f, wf, tl, d_rgb8, stream);
+}
+
+// The render entry points and pt_scene_escape_copy take the scene as const - the C ABI's promise that rendering changes
+// nothing a caller described - but a frame fills the scene's caches (buffers, streams, frame statistics, tile tables) and
+// builds its escape masks lazily: the one place the const goes.
+pt_scene& render_state(const pt_scene* scene) { return const_cast<pt_scene&>(*scene); }
 
 template <class T>
 struct Staged {  // host -> device copy of a test-hook input, freed on scope exit
@@ -3100,7 +3056,7 @@ int pt_render_device(const pt_scene* scene, const pt_profile* profile, const pt_
                      void* d_accum, void* hip_stream) {
     return guarded([&] {
         if (!scene || !profile) fail(PT_ERR_INVALID, "pt_render_device: null argument");
-        render_device(*scene, *profile, opts, d_rgb8, d_accum, (hipStream_t)hip_stream);
+        render_device(render_state(scene), *profile, opts, d_rgb8, d_accum, (hipStream_t)hip_stream);
     });
 }
 
@@ -3113,7 +3069,7 @@ int pt_render(const pt_scene* scene, const pt_profile* profile, const pt_opts* o
         uint64_t n = make_tile_map(*profile, o, o.shard_rank).n_local;
         Staged<uint8_t> d_rgb(nullptr, n * 3);
         Staged<float> d_acc(nullptr, n * 3);
-        render_device(*scene, *profile, opts, d_rgb.d, d_acc.d, nullptr, true);
+        render_device(render_state(scene), *profile, opts, d_rgb.d, d_acc.d, nullptr, true);
         HIP_CHECK(hipDeviceSynchronize());
         if (rgb8) d_rgb.fetch(rgb8, n * 3);
         if (accum) d_acc.fetch(accum, n * 3);
@@ -3334,7 +3290,7 @@ int pt_render_gathered(const pt_scene* scene, pt_comm* comm, const pt_profile* p
         const size_t npix = (size_t)profile->width * profile->height;
         Staged<uint8_t> d_local(nullptr, slice_pixels * 3), d_gathered(nullptr, slice_pixels * 3 * comm->size), d_image(nullptr, npix * 3);
         HIP_CHECK(hipMemset(d_local.d, 0, slice_pixels * 3));   // the padding of the slice
-        render_device(*scene, *profile, opts, d_local.d, nullptr, nullptr);
+        render_device(render_state(scene), *profile, opts, d_local.d, nullptr, nullptr);
         int rc = pt_gather_tiles(comm, profile, o.tile_w, o.tile_h, slice_pixels, 3, d_local.d, d_gathered.d, d_image.d, nullptr);
         if (rc != PT_OK) throw GpuError{rc, g_err};
         HIP_CHECK(hipDeviceSynchronize());
@@ -3355,41 +3311,17 @@ int pt_get_counters(const pt_scene* scene, pt_counters* out) {
 int pt_get_cull_stats(const pt_scene* scene, uint32_t* n_blocks, uint32_t* n_empty) {
     return guarded([&] {
         if (!scene || !n_blocks || !n_empty) fail(PT_ERR_INVALID, "pt_get_cull_stats: null argument");
-        *n_blocks = scene->last_mask_blocks;
+        *n_blocks = scene->frame_state.mask_blocks;
         *n_empty = 0;
-        if (scene->last_mask_blocks) {
+        if (scene->frame_state.mask_blocks) {
             HIP_CHECK(hipSetDevice(scene->device));
             HIP_CHECK(hipDeviceSynchronize());
-            std::vector<uint32_t> mask(scene->last_mask_blocks);
+            std::vector<uint32_t> mask(scene->frame_state.mask_blocks);
             HIP_CHECK(hipMemcpy(mask.data(), scene->pipe.block_mask.p, mask.size() * 4, hipMemcpyDeviceToHost));
             for (uint32_t m : mask) *n_empty += m != 0u;
         }
     });
 }
-int pt_scene_set_cu_mask(pt_scene* scene, const uint32_t* mask, uint32_t n_words) {
-    return guarded([&] {
-        if (!scene || (n_words && !mask)) fail(PT_ERR_INVALID, "pt_scene_set_cu_mask: null argument");
-        if (scene->pipe.side || scene->n_cu) fail(PT_ERR_INVALID, "pt_scene_set_cu_mask: the scene has rendered already");
-        scene->cu_mask.assign(mask, mask + n_words);
-    });
-}
-
-int pt_stream_create_cu_mask(int device, const uint32_t* mask, uint32_t n_words, void** out) {
-    return guarded([&] {
-        if (!mask || !n_words || !out) fail(PT_ERR_INVALID, "pt_stream_create_cu_mask: null argument");
-        HIP_CHECK(hipSetDevice(device));
-        hipStream_t st = nullptr;
-        HIP_CHECK(hipExtStreamCreateWithCUMask(&st, n_words, mask));
-        *out = (void*)st;
-    });
-}
-
-int pt_stream_destroy(void* stream) {
-    return guarded([&] {
-        if (stream) HIP_CHECK(hipStreamDestroy((hipStream_t)stream));
-    });
-}
-
 int pt_scene_get_info(const pt_scene* scene, pt_scene_info* out) {
     if (!scene || !out) return PT_ERR_INVALID;
     *out = scene->info;
@@ -3504,7 +3436,7 @@ int pt_trace_rays_wavefront(const pt_scene* scene, const float* rays, const uint
 int pt_scene_escape_copy(const pt_scene* scene, void* out, uint64_t bytes) {
     return guarded([&] {
         if (!scene || !out) fail(PT_ERR_INVALID, "pt_scene_escape_copy: null argument");
-        if (!scene->dev.escape && scene->escape_wanted && !scene->escape_tried) escape_masks_build(const_cast<pt_scene&>(*scene));
+        if (!scene->dev.escape && scene->escape_wanted && !scene->escape_tried) escape_masks_build(render_state(scene));
         if (!scene->dev.escape) fail(PT_ERR_INVALID, "pt_scene_escape_copy: the scene has no escape masks");
         if (bytes != (uint64_t)scene->dev.n_prims * 80u) fail(PT_ERR_INVALID, "pt_scene_escape_copy: %llu bytes expected", (unsigned long long)scene->dev.n_prims * 80ull);
         HIP_CHECK(hipSetDevice(scene->device));

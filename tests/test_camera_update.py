@@ -1,6 +1,6 @@
 """pt_scene_set_camera: a scene whose camera was replaced renders exactly what a scene created with that camera renders -
 images, accumulators, grids, escape masks, debug planes, shards - and no state of an earlier camera survives (frame plans,
-graphs, the camera grid)."""
+the cull table, the camera grid)."""
 import json
 import os
 import subprocess

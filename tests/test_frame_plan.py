@@ -1,4 +1,4 @@
-"""The frame plan (csrc/pt_gpu.hip, render_device): queues sized by what a frame is known to produce.
+"""The frame plan (csrc/pt_gpu.hip, frame_plan): queues sized by what a frame is known to produce.
 
 A frame is a pure function of (scene, profile, options) - the reference seeds every pixel's generator from the pixel's
 index (renderer/mod.rs:110-112) - so the number of records each bounce puts into each queue is the same in every frame of

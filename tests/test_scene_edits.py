@@ -1,6 +1,6 @@
 """pt_scene_set_lights / pt_scene_set_materials: a scene whose lights or materials were replaced renders exactly what a scene
 created from the edited description renders - images, accumulators, light and camera grids, debug planes, shards, the oracle
-- keeps its escape masks, and no state of the old lights or materials survives (frame plans, graphs)."""
+- keeps its escape masks, and no state of the old lights or materials survives (frame plans, the cull table)."""
 import ctypes as C
 import json
 import subprocess

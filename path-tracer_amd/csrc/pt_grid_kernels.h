@@ -69,8 +69,11 @@ __global__ __launch_bounds__(256) void k_og_primary(DevScene S, WfParams W, cons
     }
 }
 
-// A finished shadow job: the sample is complete (staging) or the colour of the path's next record is patched.
-PT_D void og_retire(f3 color, uint32_t next_idx, uint32_t out_slot, float4* __restrict__ queue_next, uint32_t cap,
+// A finished shadow job: the sample is complete (staging), or the colour of the path's next record is patched - that colour
+// is final now, so the sample's result for the case that the record's cast misses is staged with it (wf_prestage_miss; the
+// record's throughput, written by k_wf_shade of this bounce, is fetched here, after the shadow casts: it costs the lean
+// kernel no register while they run).
+PT_D void og_retire(const DevScene& S, f3 color, uint32_t next_idx, uint32_t out_slot, float4* __restrict__ queue_next, uint32_t cap,
                     float* __restrict__ staging) {
     if (next_idx == 0xffffffffu) {
         float* out = staging + (size_t)out_slot * 3;
@@ -78,7 +81,10 @@ PT_D void og_retire(f3 color, uint32_t next_idx, uint32_t out_slot, float4* __re
         out[1] = color.y;
         out[2] = color.z;
     } else {
-        wf_path_rec(queue_next, cap, next_idx)[1] = make_float4(color.x, color.y, color.z, 0.f);
+        float4* qp = wf_path_rec(queue_next, cap, next_idx);
+        const float4 thr = qp[0];
+        qp[1] = make_float4(color.x, color.y, color.z, 0.f);
+        wf_prestage_miss(staging, out_slot, color, mk3(thr.x, thr.y, thr.z), ld3(S.background));
     }
 }
 
@@ -124,7 +130,7 @@ __global__ __launch_bounds__(256, (!ALPHA && !COUNT && !DIRL) ? 8 : 1) void k_og
             const f3 rad = og_light_radiance<ALPHA, COUNT, DIRL>(S, li, pos, gn, uv, sphere, lc);
             if (!(rad.x == 0.f && rad.y == 0.f && rad.z == 0.f)) color = color + mul_ew(term, rad);
         }
-        og_retire(color, __float_as_uint(s2.w), __float_as_uint(s3.x), queue_next, W.qcap_out, staging);
+        og_retire(S, color, __float_as_uint(s2.w), __float_as_uint(s3.x), queue_next, W.qcap_out, staging);
     }
     if (COUNT) {
         atomicAdd(&gctr->shadow_rays, (unsigned long long)lc.shadow_rays);
@@ -180,7 +186,7 @@ __global__ __launch_bounds__(256) void k_og_shadow_offgrid(DevScene S, WfParams 
             light_radiance<COUNT, true>(S, L, sf, rad, ldir, lc);
             if (!(rad.x == 0.f && rad.y == 0.f && rad.z == 0.f)) color = color + mul_ew(term, rad);
         }
-        og_retire(color, __float_as_uint(s2.w), __float_as_uint(s3.x), queue_next, W.qcap_out, staging);
+        og_retire(S, color, __float_as_uint(s2.w), __float_as_uint(s3.x), queue_next, W.qcap_out, staging);
     }
     if (COUNT) {
         atomicAdd(&gctr->shadow_rays, (unsigned long long)lc.shadow_rays);

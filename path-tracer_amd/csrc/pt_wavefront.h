@@ -110,6 +110,18 @@ PT_D const uint32_t* wf_entry_plane(const float4* q, uint32_t cap) { return (con
 PT_D uint32_t* wf_entry_plane(float4* q, uint32_t cap) { return (uint32_t*)(q + (size_t)cap * 4); }
 PT_D const float4* wf_path_rec(const float4* q, uint32_t cap, uint32_t i) { return q + ((size_t)cap + i) * 2; }
 PT_D float4* wf_path_rec(float4* q, uint32_t cap, uint32_t i) { return q + ((size_t)cap + i) * 2; }
+// The sample's result should the NEXT cast of a path that goes on find nothing (mod.rs:184-186: colour + throughput x
+// background, the reference's two f32 operations in its order), staged by the kernel that makes the colour of the path's
+// record final: k_wf_shade for a survivor no shadow kernel will patch, the shadow kernels where they patch.  The shade pass
+// of the next bounce then does nothing at all for a miss; a path that hits there has its slot overwritten by whichever
+// kernel ends it - every such kernel is ordered behind this one ("Pre-staged misses").
+PT_D void wf_prestage_miss(float* __restrict__ staging, uint32_t out_slot, f3 color, f3 thr, f3 background) {
+    const f3 c = color + mul_ew(thr, background);
+    float* out = staging + (size_t)out_slot * 3;
+    out[0] = c.x;
+    out[1] = c.y;
+    out[2] = c.z;
+}
 
 #ifndef WF_CURSORS
 #define WF_CURSORS 8u   // fetch cursors per queue (a power of two)
@@ -1954,6 +1966,7 @@ PT_D bool wf_light_is_moot(const DevLight& L, f3 term, f3 surface_pos) {
 #ifndef WF_SHADE_AGGREGATE
 #define WF_SHADE_AGGREGATE 1  // bounces >= 1: retire the misses first, shade the hits 256 at a time (see the kernel)
 #endif
+#define WF_SHADE_SWEEP 4      // hit words per thread and step of the aggregation's sweep over the queue (one uint4)
 #ifndef WF_SHADE_GRID_WAVES
 // ... for the variants that cast through origin grids inline: 3 (170 registers).  At 4 the fused bounce-0 kernel keeps
 // 132 B of its state per lane in scratch: 18.66 ms against 17.09 ms at 3 (and 21.3 ms at 2) on config 3.
@@ -2127,7 +2140,9 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, GRIDX ? (ALPHA ? WF_SHADE_GRID_WA
     f3 term0 = mk3(0.f, 0.f, 0.f);
     Surface surf;
     f3 next_o = o, next_d = d, next_thr = thr;
-    if (live && !hit) {  // background (mod.rs:184-186): the path ends here
+    // background (mod.rs:184-186): the path ends here.  Bounce 0 only: a miss of a later bounce never gets here - its
+    // result was staged by the kernel that finished the record's colour (wf_prestage_miss)
+    if (PRIMARY && live && !hit) {
         color = color + mul_ew(thr, ld3(S.background));
         float* out = staging + (size_t)out_slot * 3;
         out[0] = color.x;
@@ -2281,6 +2296,9 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, GRIDX ? (ALPHA ? WF_SHADE_GRID_WA
         qr[1] = make_float4(next_d.y, next_d.z, __uint_as_float(item), __uint_as_float((draw & 0xffffu) | ((bounce + 1) << 16)));
         qp[0] = make_float4(next_thr.x, next_thr.y, next_thr.z, __uint_as_float(out_slot));
         qp[1] = make_float4(color.x, color.y, color.z, 0.f);  // colour is patched by the shadow kernels
+        // ... and where none will (lights added inline, or none can contribute) it is final here: stage the path's result
+        // for the case that its next cast misses
+        if (!to_shadow) wf_prestage_miss(staging, out_slot, color, next_thr, ld3(S.background));
         if (W.use_entry) wf_entry_plane(queue_out, W.qcap_out)[next_idx] = S.prim_entry[PT_PRIM_INDEX(h.pid)];
     }
     if (to_shadow) {
@@ -2318,7 +2336,11 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, GRIDX ? (ALPHA ? WF_SHADE_GRID_WA
         const bool cull = PRIMARY && GRID >= 2 && !COUNT && block_empty != nullptr && block_empty[W.n_mask_blocks] != 0u;
         for (uint32_t base = blockIdx.x * WF_SHADE_THREADS; base < n; base += gridDim.x * WF_SHADE_THREADS) {
             const uint32_t e = base + threadIdx.x;
-            bool live = e < n && (PRIMARY || entry_word(e) != WF_HIT_PENDING);
+            bool live = e < n;
+            if (!PRIMARY && live) {   // bounces >= 1: the hits only (a miss was staged when its record's colour became final)
+                const uint32_t word = entry_word(e);
+                live = word != WF_HIT_PENDING && word != 0xffffffffu;
+            }
             if (cull) {   // a step whose four wavefronts are all empty skips the compaction's barriers as well
                 const uint32_t g0 = (W.item_base + base) >> 6;
                 bool step_empty = true;
@@ -2336,45 +2358,58 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, GRIDX ? (ALPHA ? WF_SHADE_GRID_WA
         // Hit aggregation (bounces >= 1).  Three of four secondary rays of an open scene leave into the background:
         // shaded in queue order, 23 % of the lanes would carry the material fetch, the BRDF and the GGX sample while
         // the others wait (27.7 of 64 lanes active per vector instruction, profiles/r02_a_pmc.json).  So a first
-        // pass over a step's 256 entries retires the misses (background term, mod.rs:184-186: 48 of the 64 record
-        // bytes) and collects the indices of the hits in LDS; whenever 256 are waiting - or the queue has ended -
-        // they are shaded together.  The order in which paths are shaded is free (results are keyed by out_slot),
-        // so no bit changes.
-        __shared__ uint32_t agg[2 * WF_SHADE_THREADS];
+        // pass over a step's 256 entries reads the hit words only and collects the indices of the hits in LDS; whenever
+        // 256 are waiting - or the queue has ended - they are shaded together.  A miss costs its 4-byte word and nothing
+        // else: its result (background term, mod.rs:184-186) was staged when the record's colour became final
+        // (wf_prestage_miss).  The order in which paths are shaded is free (results are keyed by out_slot), so no bit
+        // changes.
+        // The pass over the queue sweeps WF_SHADE_SWEEP words per thread and step (one 16-byte load): the sweep is a chain of
+        // load -> ballots -> barrier -> LDS -> barrier per step, and a step of 256 words finds ~90 hits.  The lists of the second
+        // launch (scattered words, a few thousand entries) keep one word per thread.
+        __shared__ uint32_t agg[(1 + WF_SHADE_SWEEP) * WF_SHADE_THREADS];
         __shared__ uint32_t agg_cnt[WF_SHADE_THREADS / 64];
-        uint32_t have = 0;   // waiting hits (the same value in every thread)
-        uint32_t base = blockIdx.x * WF_SHADE_THREADS;
+        const uint32_t per = list_pass ? 1u : (uint32_t)WF_SHADE_SWEEP;
+        uint32_t have = 0;   // waiting hits (the same value in every thread; at most 255 + 256 * WF_SHADE_SWEEP)
+        uint32_t base = blockIdx.x * WF_SHADE_THREADS * per;
         while (true) {
             while (have < WF_SHADE_THREADS && base < n) {
-                const uint32_t e = base + threadIdx.x;
-                const uint32_t i = e < n ? entry_index(e) : e;   // (queue record; the hit is stored by e)
-                base += gridDim.x * WF_SHADE_THREADS;
-                bool is_hit = false;
-                const uint32_t word = e < n ? entry_word(e) : WF_HIT_PENDING;
-                if (word != WF_HIT_PENDING) {
-                    is_hit = word != 0xffffffffu;
-                    if (!is_hit) {
-                        const float4* qp = wf_path_rec(queue_in, W.qcap_in, i);
-                        const float4 q2 = qp[0], q3 = qp[1];
-                        const uint32_t slot = __float_as_uint(q2.w);
-                        if (slot != 0xffffffffu) {
-                            const f3 c = mk3(q3.x, q3.y, q3.z) + mul_ew(mk3(q2.x, q2.y, q2.z), ld3(S.background));
-                            float* out = staging + (size_t)slot * 3;
-                            out[0] = c.x;
-                            out[1] = c.y;
-                            out[2] = c.z;
-                        }
-                    }
+                const uint32_t e0 = base + threadIdx.x * per;
+                base += gridDim.x * WF_SHADE_THREADS * per;
+                uint32_t word[WF_SHADE_SWEEP];
+#pragma unroll
+                for (uint32_t j = 0; j < WF_SHADE_SWEEP; ++j) word[j] = WF_HIT_PENDING;
+                static_assert(WF_SHADE_SWEEP == 4, "the sweep loads the words as one uint4");
+                if (!list_pass && e0 + WF_SHADE_SWEEP <= n) {   // (e0 is a multiple of four: one aligned load of the words' plane)
+                    const uint4 w4 = hits[e0 >> 2];
+                    word[0] = w4.x, word[1] = w4.y, word[2] = w4.z, word[3] = w4.w;
+                } else {
+                    for (uint32_t j = 0; j < per; ++j)
+                        if (e0 + j < n) word[j] = entry_word(e0 + j);
                 }
-                const unsigned long long m = __ballot(is_hit);
-                if ((threadIdx.x & 63u) == 0) agg_cnt[wave] = (uint32_t)__popcll(m);
+                // (a miss: nothing to do, see above)  The hits keep their queue order - lane after lane, a lane's words in
+                // order -: the exclusive prefix of the lanes' hit counts (0..4) comes from one ballot per bit of the count.
+                // (Ranked word by word instead, neighbours in the queue land in different batches of 256: the frame lost
+                // what the pre-staged misses had gained, profiles/r05_experiments.txt item 3.)
+                uint32_t mine_n = 0;
+#pragma unroll
+                for (uint32_t j = 0; j < WF_SHADE_SWEEP; ++j) mine_n += (word[j] != WF_HIT_PENDING && word[j] != 0xffffffffu) ? 1u : 0u;
+                uint32_t before = 0, in_wave = 0;
+#pragma unroll
+                for (uint32_t b = 0; b < 3u; ++b) {
+                    const unsigned long long m = __ballot((mine_n >> b) & 1u);
+                    before += wf_lane_rank(m) << b;
+                    in_wave += (uint32_t)__popcll(m) << b;
+                }
+                if ((threadIdx.x & 63u) == 0) agg_cnt[wave] = in_wave;
                 __syncthreads();
-                uint32_t pos = have + wf_lane_rank(m), total = 0;
+                uint32_t pos = have + before, total = 0;
                 for (uint32_t k = 0; k < WF_SHADE_THREADS / 64; ++k) {
                     if (k < wave) pos += agg_cnt[k];
                     total += agg_cnt[k];
                 }
-                if (is_hit) agg[pos] = e;
+#pragma unroll
+                for (uint32_t j = 0; j < WF_SHADE_SWEEP; ++j)
+                    if (word[j] != WF_HIT_PENDING && word[j] != 0xffffffffu) agg[pos++] = e0 + j;
                 have += total;
                 __syncthreads();
             }
@@ -2546,8 +2581,11 @@ __global__ __launch_bounds__(WF_THREADS, (!COUNT && !ALPHA) ? WF_PRIMARY_WAVES :
             out[0] = color.x;
             out[1] = color.y;
             out[2] = color.z;
-        } else {
-            wf_path_rec(queue_next, W.qcap_out, next_idx)[1] = make_float4(color.x, color.y, color.z, 0.f);
+        } else {   // the patched colour is final: stage the result of a miss of the record's cast with it (wf_prestage_miss)
+            float4* qp = wf_path_rec(queue_next, W.qcap_out, next_idx);
+            const float4 thr = qp[0];
+            qp[1] = make_float4(color.x, color.y, color.z, 0.f);
+            wf_prestage_miss(staging, out_slot, color, mk3(thr.x, thr.y, thr.z), ld3(S.background));
         }
         active = false;
     };

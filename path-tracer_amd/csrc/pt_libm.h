@@ -11,7 +11,11 @@
 // container's libm.so.6, see tools/libm_probe.cpp and profiles/r01_libm_exhaustive.txt):
 //   sinf, cosf  glibc sysdeps/ieee754/flt-32/s_sinf.c, s_cosf.c, s_sincosf.h, s_sincosf_data.c
 //               (ARM optimized-routines): double-precision reduction by pi/2 and two degree-7/8
-//               polynomials.  0 mismatches on every float in [0, 7].
+//               polynomials.  0 mismatches on every float with |y| < 120, both signs - with the
+//               reduction x - n * pi/2 fused, as x86-64 glibc's FMA build has it: unfused, 6 sinf
+//               and 11 cosf arguments per sign, where the difference cancels (the smallest
+//               17.2787 and 53.4225), come out one ulp off - none in [0, 7], where the integrator
+//               calls.
 //   acosf       glibc sysdeps/ieee754/flt-32/e_acosf.c (fdlibm, pure f32).  0 mismatches on
 //               every float in [-1, 1].
 //   powf        glibc sysdeps/ieee754/flt-32/e_powf.c + e_powf_log2_data.c + e_exp2f_data.c:
@@ -20,7 +24,7 @@
 //               that is observable is r = fma(z, invc, -1) (found by searching all 512
 //               placements): with it, 0 mismatches on every positive float for y = 1/2.2f and
 //               for y = 2.2f on [0, 1].
-// The file is compiled with -ffp-contract=off; the single fused operation is written explicitly.
+// The file is compiled with -ffp-contract=off; the two fused operations are written explicitly.
 #pragma once
 
 PT_D uint32_t ptm_asuint(float f) { return __float_as_uint(f); }
@@ -56,11 +60,12 @@ PT_D float ptm_sinf_poly(double x, double x2, bool neg, int n) {
     return (float)(c + x6 * p2);
 }
 
-// reduce_fast: x - n*pi/2 with n = round(x * 2/pi) taken from a 2^24-scaled product
+// reduce_fast: x - n*pi/2 with n = round(x * 2/pi) taken from a 2^24-scaled product.  One fused operation, like
+// glibc's FMA build: where the difference cancels, the rounding of the product n * pi/2 shows in it.
 PT_D double ptm_reduce_fast(double x, int& n) {
     double r = x * 0x1.45F306DC9C883p+23;
     n = ((int32_t)r + 0x800000) >> 24;
-    return x - (double)n * 0x1.921FB54442D18p0;
+    return __builtin_fma(-(double)n, 0x1.921FB54442D18p0, x);
 }
 
 // |y| < 120 only (the integrator passes theta in [0, pi/2] and phi in [0, 2 pi)); larger

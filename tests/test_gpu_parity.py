@@ -118,8 +118,14 @@ def gpu_math(pta, fn, x):
                                            ("cos", 3, 0.0, 7.0)])
 def test_device_libm_is_bit_exact(pta, oracle, name, fn, lo, hi):
     """csrc/pt_libm.h restates glibc's powf/acosf/sinf/cosf; the GPU results must equal the host libm bit for bit
-    (exhaustive CPU-side proof of the algorithms: profiles/r01_libm_exhaustive.txt)."""
+    (exhaustive CPU-side proof of the algorithms: profiles/r01_libm_exhaustive.txt).  [lo, hi] is where the integrator
+    itself calls the function; the header claims more, and that is held too: powf(x, 1/2.2f) on every positive float (a strided
+    sweep of all positive bit patterns, subnormals included - post-processing without a compressing tone map passes whatever
+    radiance a pixel has) and on +inf, NaN, -0 and negative values; sin / cos on glibc's reduce_fast path up to |y| < 120, both
+    signs; acos just outside [-1, 1] (NaN).  From |y| = 120 on the device returns NaN by contract (no reduce_large path): that is
+    asserted as such and not compared with glibc."""
     rng = np.random.default_rng(fn)
+    f32 = np.float32
     x = rng.uniform(lo, hi, 3_000_000).astype(np.float32)
     # every float in a few binades + denormals, zeros, ones, the domain ends
     dense = np.arange(0x3f000000, 0x3f000000 + 400_000, dtype=np.uint32).view(np.float32)
@@ -128,9 +134,45 @@ def test_device_libm_is_bit_exact(pta, oracle, name, fn, lo, hi):
                         np.nextafter(np.float32(1), np.float32(0)), 0.25, 0.75, 1e-30, 3e-39], np.float32)
     xs = np.concatenate([x, dense, tiny, special])
     xs = xs[(xs >= lo) & (xs <= hi)]
+    beyond = np.zeros(0, f32)
+    if name == "pow_inv_gamma":
+        sweep = np.arange(1, 0x7f800000, 1021, dtype=np.uint32).view(f32)          # every 1021st positive bit pattern: 2.1 M
+        ends = np.array([0x00000001, 0x007fffff, 0x00800000, 0x7f7fffff], np.uint32).view(f32)   # subnormal ends, FLT_MIN, FLT_MAX
+        odd = np.array([np.inf, np.nan, -0.0, -1e-45, -1e-30, -0.5, -1.0, -4.0, -3e38, -np.inf], f32)
+        assert len(sweep) > 2_000_000
+        xs = np.concatenate([xs, sweep, ends, odd])
+    elif name in ("sin", "cos"):
+        wide = rng.uniform(7.0, 120.0, 2_000_000).astype(f32)
+        below = np.arange(0x42f00000 - 200_000, 0x42f00000, dtype=np.uint32).view(f32)   # the last 200 000 floats below 120
+        k = np.arange(0, 77)                                                          # around every multiple of pi / 2 up to 120
+        near = ((k * (np.pi / 2)).astype(f32).view(np.uint32)[:, None] + np.arange(-40, 41)[None, :]).astype(np.uint32).view(f32).reshape(-1)
+        pos = np.concatenate([wide, below, near])
+        pos = pos[(pos >= 0) & (pos < f32(120.0))]
+        xs = np.concatenate([xs, pos, -pos, -xs])
+        beyond = np.array([120.0, np.nextafter(f32(120.0), f32(np.inf)), 127.99999, 128.0, 1e3, 1e10, 3e38, np.inf, np.nan], f32)
+        beyond = np.concatenate([beyond, -beyond])
+    elif name == "acos":
+        out = np.array([np.nextafter(f32(1), f32(2)), 1.0000002, 1.5, 2.0, 3e38, np.inf, np.nan], f32)
+        xs = np.concatenate([xs, out, -out])
     got, ref = gpu_math(pta, fn, xs), oracle.eval_math(name, xs)
     same = (got.view(np.uint32) == ref.view(np.uint32)) | (np.isnan(got) & np.isnan(ref))
     assert same.all(), (name, xs[~same][:5], got[~same][:5], ref[~same][:5])
+    if name == "acos":
+        assert np.isnan(got[-14:]).all()     # |x| > 1: NaN, both signs
+    if len(beyond):
+        assert np.isnan(gpu_math(pta, fn, beyond)).all(), name
+
+
+def test_sin_cos_reduction_is_fused_next_to_multiples_of_half_pi(pta, oracle):
+    """Found by test_device_libm_is_bit_exact when its inputs grew beyond [0, 7]: cosf(0x1.1475b6p+4) - 17.2787, 2.2e-5 from
+    11 pi / 2 - and sinf(0x1.ab6152p+5) - 53.4225, 0.015 from 17 pi - came out one ulp off glibc (-2.1572892e-05 for
+    -2.1572894e-05), the smallest of 11 and 6 such arguments per sign below 120.  Where x - n * pi/2 cancels, the rounding
+    of the product n * pi/2 shows in the difference; glibc's build fuses the two operations and csrc/pt_libm.h
+    ptm_reduce_fast does now (exhaustive on the host: profiles/r01_libm_exhaustive.txt)."""
+    x = np.array([float.fromhex(v) for v in ("0x1.1475b6p+4", "0x1.ab6152p+5", "-0x1.1475b6p+4", "-0x1.ab6152p+5")], np.float32)
+    for name, fn in (("sin", 2), ("cos", 3)):
+        assert np.array_equal(gpu_math(pta, fn, x).view(np.uint32), oracle.eval_math(name, x).view(np.uint32)), name
+    assert gpu_math(pta, 3, x[:1])[0] == np.float32(-2.1572894e-05)
 
 
 def compare_render(pta, oracle, scene, gscene, prof, opts=None):

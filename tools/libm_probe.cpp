@@ -4,8 +4,9 @@
 #include <vector>
 int main(){
   struct T{const char*name; uint32_t lo,hi; int fn;};
-  // float bit ranges: [0,1] -> 0..0x3f800000 ; [0, 2pi] -> up to 0x40c90fdb ; negatives for sin/cos not needed
-  T tests[]={{"acosf [0,1]",0,0x3f800000u,1},{"acosf [-1,0)",0x80000000u,0xbf800000u,1},{"sinf [0,7]",0,0x40e00000u,2},{"cosf [0,7]",0,0x40e00000u,3},
+  // float bit ranges: [0,1] -> 0..0x3f800000 ; |y| < 120 -> 0..0x42efffff, and the same with the sign bit
+  T tests[]={{"acosf [0,1]",0,0x3f800000u,1},{"acosf [-1,0)",0x80000000u,0xbf800000u,1},{"sinf [0,120)",0,0x42efffffu,2},{"cosf [0,120)",0,0x42efffffu,3},
+             {"sinf (-120,-0]",0x80000000u,0xc2efffffu,2},{"cosf (-120,-0]",0x80000000u,0xc2efffffu,3},
              {"powf(x,1/2.2f) [0,2]",0,0x40000000u,0},{"powf(x,1/2.2f) (2,inf]",0x40000001u,0x7f800000u,0},{"powf(x,2.2f) [0,1]",0,0x3f800000u,4}};
   const float ig=1.f/2.2f;
   for(auto&t:tests){

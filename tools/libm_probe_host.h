@@ -24,7 +24,7 @@ static inline float sinf_poly(double x,double x2,const sincos_t*p,int n){
   if((n&1)==0){ x3=x*x2; s1=p->s2+x2*p->s3; x7=x3*x2; s=x+x3*p->s1; return (float)(s+x7*s1);}
   else { x4=x2*x2; c2=p->c3+x2*p->c4; c1=p->c0+x2*p->c1; x6=x4*x2; c=c1+x4*p->c2; return (float)(c+x6*c2);} }
 static inline double reduce_fast(double x,const sincos_t*p,int*np){
-  double r=x*p->hpi_inv; int n=((int32_t)r+0x800000)>>24; *np=n; return x-n*p->hpi; }
+  double r=x*p->hpi_inv; int n=((int32_t)r+0x800000)>>24; *np=n; return __builtin_fma(-(double)n, p->hpi, x); }
 static inline float pt_sinf_host(float y){
   double x=y,s; int n; const sincos_t*p=&sincosf_table[0];
   if(abstop12(y)<abstop12(0x1.921FB6p-1f)){ s=x*x; if(abstop12(y)<abstop12(0x1p-12f)) return y; return sinf_poly(x,s,p,0);}

@@ -296,6 +296,75 @@ enum { PT_DEBUG_PLANES = 7 };
 int pt_debug_render(const pt_scene* scene, uint32_t width, uint32_t height, uint8_t* planes, int* any_hit);
 
 /* ------------------------------------------------------------------ */
+/* denoised previews (no reference counterpart)             */
+/* ------------------------------------------------------------------ */
+
+/* Guide planes: the first hit of the pixel-centre ray at float precision (what pt_debug_render quantises to u8).
+ * Per pixel i = x + y*W, 8 f32: [0..2] shading normal exactly as the debug pass computes it (NOT normalised for
+ * triangles, flipped on back faces), [3] depth = the `dist` pt_trace_rays reports for the first entry of ray_cast() of the
+ * pixel-centre ray (r1 = r2 = 0.5), [4..6] MaterialSample albedo, [7] the global primitive index (pt_hit.prim) as int32 bits.
+ * A pixel whose ray hits nothing: floats 0, depth -1.0f, prim -1.  Translucent first surfaces are reported as they are.
+ * Follows pt_scene_set_camera and the scene edits like pt_debug_render.  d_guides: 16-byte aligned device memory. */
+enum { PT_GUIDE_FLOATS = 8 };
+int pt_render_guides(const pt_scene* scene, uint32_t width, uint32_t height, float* guides /* host */);
+int pt_render_guides_device(const pt_scene* scene, uint32_t width, uint32_t height, void* d_guides, void* hip_stream);
+
+/* Edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over the accumulator, steered by the guides.  All f32, one
+ * IEEE operation per step in the order written, no transcendental function (tests/denoise_model.py restates it bit for bit):
+ *   prep    valid = depth >= 0;  c = accum / (float)samples;  an invalid pixel outputs c and is never a tap.
+ *           u = normalize(n) (0 when n.n is 0 or not finite);  d = albedo + 0.01 (1 with NO_DEMODULATE);  x = c / d;
+ *           gx = min(|z(x+1) - z|, |z - z(x-1)|) over the valid in-image neighbours (one: that difference; none: 0), gy alike.
+ *   pass i  s = 2^i.  acc = 0, wsum = 0; dy = -2..2 outer, dx = -2..2 inner, q = p + s*(dx, dy) in the image and valid:
+ *           k = h[|dx|] * h[|dy|], h = {3/8, 1/4, 1/16};  centre tap: w = k;  any other tap:
+ *             wn = max(0, u_p.u_q) squared normal_power_log2 times
+ *             den = sigma_depth * (gx_p * (float)(s*|dx|) + gy_p * (float)(s*|dy|)) + 1e-4f * z_p;  wz = wexp(|z_p - z_q| / den)
+ *             sc = sigma_color * 2^-i;  wc = sigma_color == 0 ? 1 : wexp(|x_p - x_q|^2 / (sc * sc))  (x of this pass's input)
+ *             w = ((k * wn) * wz) * wc
+ *           acc += x_q * w, wsum += w;  the pass writes acc / wsum.
+ *           wexp(e): r = max(0, 1 - e * 0.125f), squared three times (compact-support stand-in for exp(-e); NaN / inf: 0)
+ *   finish  out = x * d (x with NO_DEMODULATE);  rgb8 = as_u8(pow(tonemap(out), 1/2.2) * 255) like pt_render.
+ * iterations = 0: out = c for every pixel (no demodulation round trip): out_rgb8 equals pt_render's rgb8 bit for bit.
+ * Non-finite accumulator values are outside the contract (a NaN sample spreads to the pixels whose taps reach it). */
+enum { PT_DENOISE_NO_DEMODULATE = 1 };
+typedef struct pt_denoise_params {
+    uint32_t iterations;         /* a-trous passes, pass i has step 2^i; 0..8; 0 = no filtering at all */
+    uint32_t flags;              /* PT_DENOISE_NO_DEMODULATE = 1 */
+    uint32_t normal_power_log2;  /* normal weight = max(0, n_p.n_q)^(2^this); 0..10 */
+    int32_t  tonemap;            /* PT_TONEMAP_* for the rgb8 output */
+    float sigma_color;           /* 0 = colour weight off */
+    float sigma_depth;           /* > 0 */
+} pt_denoise_params;
+/* The defaults: the best of the grid tools/measure_denoise_gain.py searched (tests/golden/denoise_gain.json), FILMIC. */
+#define PT_DENOISE_DEFAULT_ITERATIONS 1
+#define PT_DENOISE_DEFAULT_NORMAL_POWER_LOG2 3
+#define PT_DENOISE_DEFAULT_SIGMA_COLOR 0.5f
+#define PT_DENOISE_DEFAULT_SIGMA_DEPTH 0.5f
+void pt_denoise_params_default(pt_denoise_params* params);
+
+uint64_t pt_denoise_scratch_bytes(uint32_t width, uint32_t height);
+/* accum: W*H*3 f32 SUM of samples (pt_render's accum, row-major, unsharded); guides: W*H*8 f32 as above;
+ * out_color: W*H*3 f32 mean radiance [may be NULL]; out_rgb8: W*H*3 [may be NULL].  The host form allocates its own scratch
+ * and blocks; the device form takes the caller's scratch (pt_denoise_scratch_bytes, 256-byte aligned), allocates nothing and
+ * is asynchronous on hip_stream.  device: HIP ordinal, -1 = current.  PT_ERR_INVALID: a null required pointer,
+ * width * height == 0, samples == 0, a parameter outside its range, sigma_depth not positive and finite, sigma_color negative
+ * or not finite. */
+int pt_denoise(int device, uint32_t width, uint32_t height, uint32_t samples, const pt_denoise_params* params,
+               const float* accum, const float* guides, float* out_color, uint8_t* out_rgb8);
+int pt_denoise_device(int device, uint32_t width, uint32_t height, uint32_t samples, const pt_denoise_params* params,
+                      const void* d_accum, const void* d_guides, void* d_out_color, void* d_out_rgb8,
+                      void* d_scratch, void* hip_stream);
+/* pt_render + guides + denoise without leaving the device; rgb8 / color are host pointers, either may be NULL.  The preview
+ * callback of opts receives the RAW frames.  shard_count > 1 is PT_ERR_UNSUPPORTED (the filter needs the whole image). */
+int pt_render_denoised(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts,
+                       const pt_denoise_params* params, uint8_t* rgb8, float* color);
+/* Measurement: pt_denoise_device on the null stream with HIP events between its kernels; blocks.  ms[0] = prep,
+ * ms[1 + i] = pass i, ms[9] = finish; stages that did not run are 0. */
+enum { PT_DENOISE_STAGES = 10 };
+int pt_denoise_stage_times(int device, uint32_t width, uint32_t height, uint32_t samples, const pt_denoise_params* params,
+                           const void* d_accum, const void* d_guides, void* d_out_color, void* d_out_rgb8,
+                           void* d_scratch, float* ms);
+
+/* ------------------------------------------------------------------ */
 /* measurement                                                         */
 /* ------------------------------------------------------------------ */
 

@@ -104,6 +104,28 @@ class Opts(C.Structure):
         return o
 
 
+PT_GUIDE_FLOATS = 8
+PT_DENOISE_NO_DEMODULATE = 1
+PT_DENOISE_STAGES = 10
+
+
+class DenoiseParams(C.Structure):
+    """pt_denoise_params: the a-trous filter's settings (include/ptgpu.h)."""
+    _fields_ = [("iterations", C.c_uint32), ("flags", C.c_uint32), ("normal_power_log2", C.c_uint32),
+                ("tonemap", C.c_int32), ("sigma_color", C.c_float), ("sigma_depth", C.c_float)]
+
+    @classmethod
+    def default(cls, **changes):
+        """pt_denoise_params_default, with fields replaced by keyword."""
+        p = cls()
+        gpu_lib().pt_denoise_params_default(C.byref(p))
+        for k, v in changes.items():
+            if k not in dict(cls._fields_):
+                raise TypeError(f"pt_denoise_params has no field {k!r}")
+            setattr(p, k, TONEMAPS[v] if k == "tonemap" and isinstance(v, str) else v)
+        return p
+
+
 class Hit(C.Structure):
     _fields_ = [("prim", C.c_int32), ("flags", C.c_int32), ("dist", C.c_float), ("u", C.c_float),
                 ("v", C.c_float)]
@@ -198,7 +220,8 @@ GPU_SYMBOLS = ["pt_scene_create", "pt_scene_destroy", "pt_scene_set_camera", "pt
                "pt_scene_get_info", "pt_get_cull_stats", "pt_scene_escape_copy", "pt_scene_grid_header", "pt_scene_grid_copy", "pt_trace_rays", "pt_trace_rays_wavefront",
                "pt_trace_rays_all", "pt_intersect_triangles",
                "pt_rng_words", "pt_eval_math", "pt_measure_copy_bandwidth", "pt_measure_gather_rate", "pt_last_error",
-               "pt_version"]
+               "pt_version", "pt_render_guides", "pt_render_guides_device", "pt_denoise_params_default", "pt_denoise_scratch_bytes",
+               "pt_denoise", "pt_denoise_device", "pt_render_denoised", "pt_denoise_stage_times"]
 
 
 def host_lib():
@@ -301,6 +324,17 @@ def gpu_lib():
         L.pt_eval_math.argtypes = [C.c_int, C.c_int, vp, C.c_uint64, vp]
         L.pt_measure_copy_bandwidth.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]
         L.pt_measure_gather_rate.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]
+        dp = C.POINTER(DenoiseParams)
+        L.pt_render_guides.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
+        L.pt_render_guides_device.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp]
+        L.pt_denoise_params_default.argtypes = [dp]
+        L.pt_denoise_params_default.restype = None
+        L.pt_denoise_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
+        L.pt_denoise_scratch_bytes.restype = C.c_uint64
+        L.pt_denoise.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, dp, vp, vp, vp, vp]
+        L.pt_denoise_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, dp, vp, vp, vp, vp, vp, vp]
+        L.pt_render_denoised.argtypes = [vp, C.POINTER(Profile), C.POINTER(Opts), dp, vp, vp]
+        L.pt_denoise_stage_times.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, dp, vp, vp, vp, vp, vp, vp]
         L.pt_last_error.restype = C.c_char_p
         L.pt_version.restype = C.c_char_p
         _gpu = L
@@ -727,6 +761,26 @@ class GpuScene:
             return {}
         return dict(zip(DEBUG_PLANES, planes))
 
+    def render_guides(self, width, height):
+        """pt_render_guides: [H*W, 8] float32 - normal3, depth, albedo3, primitive index as int32 bits (view(np.int32))."""
+        import numpy as np
+        g = np.empty((width * height, PT_GUIDE_FLOATS), np.float32)
+        check_gpu(self.lib.pt_render_guides(self.handle, width, height, g.ctypes.data))
+        return g
+
+    def render_guides_device(self, width, height, d_guides, stream=0):
+        check_gpu(self.lib.pt_render_guides_device(self.handle, width, height, d_guides, stream))
+
+    def render_denoised(self, profile, params, opts=None):
+        """pt_render_denoised: (rgb8 [H*W, 3] uint8, color [H*W, 3] float32 mean radiance) of the filtered frame."""
+        import numpy as np
+        n = profile.width * profile.height
+        rgb = np.empty((n, 3), np.uint8)
+        col = np.empty((n, 3), np.float32)
+        check_gpu(self.lib.pt_render_denoised(self.handle, C.byref(profile), C.byref(opts) if opts is not None else None,
+                                              C.byref(params) if params is not None else None, rgb.ctypes.data, col.ctypes.data))
+        return rgb, col
+
     def timing(self):
         t = Timing()
         check_gpu(self.lib.pt_get_timing(self.handle, C.byref(t)))
@@ -798,6 +852,26 @@ try:
     HIT_DTYPE = _np.dtype([("prim", "<i4"), ("flags", "<i4"), ("dist", "<f4"), ("u", "<f4"), ("v", "<f4")])
 except Exception:  # pragma: no cover
     HIT_DTYPE = None
+
+
+def denoise(width, height, samples, params, accum, guides, device=0):
+    """pt_denoise on host arrays: accum [H*W, 3] float32 SUM of samples, guides [H*W, 8] float32 (GpuScene.render_guides);
+    returns (color [H*W, 3] float32 mean radiance, rgb8 [H*W, 3] uint8)."""
+    import numpy as np
+    n = width * height
+    accum = np.ascontiguousarray(accum, np.float32)
+    guides = np.ascontiguousarray(guides, np.float32)
+    if accum.size != n * 3 or guides.size != n * PT_GUIDE_FLOATS:
+        raise ValueError("denoise: accum must hold width*height*3 and guides width*height*8 floats")
+    col = np.empty((n, 3), np.float32)
+    rgb = np.empty((n, 3), np.uint8)
+    check_gpu(gpu_lib().pt_denoise(device, width, height, samples, C.byref(params) if params is not None else None,
+                                   accum.ctypes.data, guides.ctypes.data, col.ctypes.data, rgb.ctypes.data))
+    return col, rgb
+
+
+def denoise_scratch_bytes(width, height):
+    return int(gpu_lib().pt_denoise_scratch_bytes(width, height))
 
 
 def local_pixel_map(profile, opts):

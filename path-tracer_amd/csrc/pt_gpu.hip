@@ -13,6 +13,7 @@
 //   k_postprocess     Renderer::post_processing (mod.rs:335-353)
 //   k_assemble        scatter all-gathered packed tiles into a row-major image
 //   k_debug           --debug-textures G-buffer pass (debug_renderer.rs:64-105)
+//   k_guides, k_dn_*  pt_denoise.h: first-hit guide planes and the a-trous filter of denoised previews
 //   k_stream_copy     achievable-HBM yardstick of the roofline (pt_measure_copy_bandwidth)
 //   k_trace / k_trace_all / k_isect / k_rng / k_math   parity-test hooks
 #include <hip/hip_runtime.h>
@@ -41,6 +42,7 @@
 #include "pt_grid_kernels.h"
 #include "pt_escape_build.h"
 #include "pt_grid_build.h"
+#include "pt_denoise.h"
 #include "pthost.h"
 #include "../host/scene_check.h"
 
@@ -2957,6 +2959,96 @@ struct Staged {  // host -> device copy of a test-hook input, freed on scope exi
     void fetch(T* host, size_t count) { HIP_CHECK(hipMemcpy(host, d, count * sizeof(T), hipMemcpyDeviceToHost)); }
 };
 
+// ------------------------------------------------------------------ denoised previews (pt_denoise.h)
+struct DnScratch {   // the planes of pt_denoise_scratch_bytes, each on a 256-byte boundary
+    uint64_t xa, xb, u, g, d, total;
+};
+DnScratch dn_scratch_layout(uint64_t n) {
+    auto up = [](uint64_t v) { return (v + 255u) & ~(uint64_t)255u; };
+    DnScratch L;
+    L.xa = 0;
+    L.xb = L.xa + up(16u * n);
+    L.u = L.xb + up(16u * n);
+    L.g = L.u + up(16u * n);
+    L.d = L.g + up(8u * n);
+    L.total = L.d + up(12u * n);
+    return L;
+}
+
+void dn_check_size(const char* who, uint32_t width, uint32_t height) {
+    if (!width || !height) fail(PT_ERR_INVALID, "%s: width * height is 0", who);
+    if ((uint64_t)width * height >= (1ull << 31)) fail(PT_ERR_INVALID, "%s: image too large", who);
+}
+
+void dn_check_params(const char* who, const pt_denoise_params* p) {
+    if (!p) fail(PT_ERR_INVALID, "%s: null parameters", who);
+    if (p->iterations > 8u) fail(PT_ERR_INVALID, "%s: iterations %u outside 0..8", who, p->iterations);
+    if (p->flags & ~(uint32_t)PT_DENOISE_NO_DEMODULATE) fail(PT_ERR_INVALID, "%s: unknown flags 0x%x", who, p->flags);
+    if (p->normal_power_log2 > 10u) fail(PT_ERR_INVALID, "%s: normal_power_log2 %u outside 0..10", who, p->normal_power_log2);
+    if (p->tonemap < PT_TONEMAP_REINHARD || p->tonemap > PT_TONEMAP_ACES) fail(PT_ERR_INVALID, "%s: unknown tonemap %d", who, p->tonemap);
+    if (!(p->sigma_depth > 0.f) || !std::isfinite(p->sigma_depth)) fail(PT_ERR_INVALID, "%s: sigma_depth must be positive and finite", who);
+    if (!(p->sigma_color >= 0.f) || !std::isfinite(p->sigma_color)) fail(PT_ERR_INVALID, "%s: sigma_color must be finite and not negative", who);
+}
+
+// The passes of step 1 and 2 gather from an LDS tile with a halo (k_dn_pass<1>, <2>): a fifth faster than global gathers at
+// 1080p.  PT_DN_LDS=0: every pass from global memory (A/B measurements; the bits are the same).
+bool dn_use_lds() {
+    const char* e = getenv("PT_DN_LDS");
+    return !(e && *e == '0');
+}
+
+// prep, the passes and finish on `stream`; ev (measurement only): 2 + iterations + 1 events recorded between the stages
+void denoise_launch(uint32_t width, uint32_t height, uint32_t samples, const pt_denoise_params& p, const float* d_accum,
+                    const float4* d_guides, float* d_out_color, uint8_t* d_out_rgb8, uint8_t* d_scratch, hipStream_t stream,
+                    hipEvent_t* ev = nullptr) {
+    const uint32_t n = width * height, blocks = (n + 255u) / 256u;
+    const uint32_t no_demod = p.flags & PT_DENOISE_NO_DEMODULATE;
+    size_t e = 0;
+    if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
+    if (p.iterations == 0) {
+        hipLaunchKernelGGL(k_dn_finish, dim3(blocks), dim3(256), 0, stream, (const float4*)nullptr, (const float*)nullptr, d_accum,
+                           samples, n, no_demod, p.tonemap, d_out_color, d_out_rgb8);
+        HIP_CHECK(hipGetLastError());
+        if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
+        return;
+    }
+    const DnScratch L = dn_scratch_layout(n);
+    float4* X = (float4*)(d_scratch + L.xa);
+    float4* Y = (float4*)(d_scratch + L.xb);
+    float4* U = (float4*)(d_scratch + L.u);
+    float2* G = (float2*)(d_scratch + L.g);
+    float* D = (float*)(d_scratch + L.d);
+    hipLaunchKernelGGL(k_dn_prep, dim3(blocks), dim3(256), 0, stream, d_accum, d_guides, width, height, samples, no_demod, X, U, G, D);
+    HIP_CHECK(hipGetLastError());
+    if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
+    const dim3 grid((width + DN_TILE_W - 1u) / DN_TILE_W, (height + DN_TILE_H - 1u) / DN_TILE_H);
+    const bool lds = dn_use_lds();
+    for (uint32_t i = 0; i < p.iterations; ++i) {
+        DnParams P;
+        P.sigma_depth = p.sigma_depth;
+        const float sc = p.sigma_color * (1.0f / (float)(1u << i));
+        P.sc2 = sc * sc;
+        P.npow = p.normal_power_log2;
+        P.color_on = p.sigma_color != 0.f;
+        const int step = 1 << i;
+        if (lds && i == 0) hipLaunchKernelGGL(k_dn_pass<1>, grid, dim3(256), 0, stream, (const float4*)X, (const float4*)U, (const float2*)G, Y, (int)width, (int)height, step, P);
+        else if (lds && i == 1) hipLaunchKernelGGL(k_dn_pass<2>, grid, dim3(256), 0, stream, (const float4*)X, (const float4*)U, (const float2*)G, Y, (int)width, (int)height, step, P);
+        else hipLaunchKernelGGL(k_dn_pass<0>, grid, dim3(256), 0, stream, (const float4*)X, (const float4*)U, (const float2*)G, Y, (int)width, (int)height, step, P);
+        HIP_CHECK(hipGetLastError());
+        if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
+        std::swap(X, Y);
+    }
+    hipLaunchKernelGGL(k_dn_finish, dim3(blocks), dim3(256), 0, stream, (const float4*)X, (const float*)D, d_accum, samples, n, no_demod,
+                       p.tonemap, d_out_color, d_out_rgb8);
+    HIP_CHECK(hipGetLastError());
+    if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
+}
+
+void guides_launch(const pt_scene& s, uint32_t width, uint32_t height, float4* d_guides, hipStream_t stream) {
+    hipLaunchKernelGGL(k_guides, dim3((width * height + 255u) / 256u), dim3(256), 0, stream, s.dev, width, height, d_guides);
+    HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace
 
 // ==================================================================== C ABI
@@ -3092,6 +3184,136 @@ int pt_debug_render(const pt_scene* scene, uint32_t width, uint32_t height, uint
         HIP_CHECK(hipDeviceSynchronize());
         d_planes.fetch(planes, bytes);
         d_flag.fetch(any_hit, 1);
+    });
+}
+
+int pt_render_guides_device(const pt_scene* scene, uint32_t width, uint32_t height, void* d_guides, void* hip_stream) {
+    return guarded([&] {
+        if (!scene || !d_guides) fail(PT_ERR_INVALID, "pt_render_guides_device: null argument");
+        dn_check_size("pt_render_guides_device", width, height);
+        HIP_CHECK(hipSetDevice(scene->device));
+        guides_launch(*scene, width, height, (float4*)d_guides, (hipStream_t)hip_stream);
+    });
+}
+
+int pt_render_guides(const pt_scene* scene, uint32_t width, uint32_t height, float* guides) {
+    return guarded([&] {
+        if (!scene || !guides) fail(PT_ERR_INVALID, "pt_render_guides: null argument");
+        dn_check_size("pt_render_guides", width, height);
+        HIP_CHECK(hipSetDevice(scene->device));
+        const size_t n = (size_t)width * height;
+        Staged<float4> d_guides(nullptr, n * 2);
+        guides_launch(*scene, width, height, d_guides.d, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        d_guides.fetch((float4*)guides, n * 2);
+    });
+}
+
+void pt_denoise_params_default(pt_denoise_params* p) {
+    if (!p) return;
+    // the winner of tools/measure_denoise_gain.py (tests/golden/denoise_gain.json)
+    p->iterations = PT_DENOISE_DEFAULT_ITERATIONS;
+    p->flags = 0;
+    p->normal_power_log2 = PT_DENOISE_DEFAULT_NORMAL_POWER_LOG2;
+    p->tonemap = PT_TONEMAP_FILMIC;
+    p->sigma_color = PT_DENOISE_DEFAULT_SIGMA_COLOR;
+    p->sigma_depth = PT_DENOISE_DEFAULT_SIGMA_DEPTH;
+}
+
+uint64_t pt_denoise_scratch_bytes(uint32_t width, uint32_t height) {
+    const uint64_t n = (uint64_t)width * height;
+    return n ? dn_scratch_layout(n).total : 0;
+}
+
+int pt_denoise_device(int device, uint32_t width, uint32_t height, uint32_t samples, const pt_denoise_params* params,
+                      const void* d_accum, const void* d_guides, void* d_out_color, void* d_out_rgb8, void* d_scratch,
+                      void* hip_stream) {
+    return guarded([&] {
+        dn_check_params("pt_denoise_device", params);
+        if (!d_accum || !d_guides || (!d_scratch && params->iterations)) fail(PT_ERR_INVALID, "pt_denoise_device: null argument");
+        dn_check_size("pt_denoise_device", width, height);
+        if (!samples) fail(PT_ERR_INVALID, "pt_denoise_device: samples is 0");
+        if (device >= 0) HIP_CHECK(hipSetDevice(device));
+        denoise_launch(width, height, samples, *params, (const float*)d_accum, (const float4*)d_guides, (float*)d_out_color,
+                       (uint8_t*)d_out_rgb8, (uint8_t*)d_scratch, (hipStream_t)hip_stream);
+    });
+}
+
+int pt_denoise(int device, uint32_t width, uint32_t height, uint32_t samples, const pt_denoise_params* params,
+               const float* accum, const float* guides, float* out_color, uint8_t* out_rgb8) {
+    return guarded([&] {
+        dn_check_params("pt_denoise", params);
+        if (!accum || !guides) fail(PT_ERR_INVALID, "pt_denoise: null argument");
+        dn_check_size("pt_denoise", width, height);
+        if (!samples) fail(PT_ERR_INVALID, "pt_denoise: samples is 0");
+        if (device >= 0) HIP_CHECK(hipSetDevice(device));
+        const size_t n = (size_t)width * height;
+        Staged<float> d_acc(accum, n * 3), d_color(nullptr, n * 3);
+        Staged<float4> d_guides((const float4*)guides, n * 2);
+        Staged<uint8_t> d_rgb(nullptr, n * 3), d_scratch(nullptr, pt_denoise_scratch_bytes(width, height));
+        denoise_launch(width, height, samples, *params, d_acc.d, d_guides.d, d_color.d, d_rgb.d, d_scratch.d, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        if (out_color) d_color.fetch(out_color, n * 3);
+        if (out_rgb8) d_rgb.fetch(out_rgb8, n * 3);
+    });
+}
+
+int pt_denoise_stage_times(int device, uint32_t width, uint32_t height, uint32_t samples, const pt_denoise_params* params,
+                           const void* d_accum, const void* d_guides, void* d_out_color, void* d_out_rgb8, void* d_scratch,
+                           float* ms) {
+    return guarded([&] {
+        dn_check_params("pt_denoise_stage_times", params);
+        if (!d_accum || !d_guides || !ms || (!d_scratch && params->iterations)) fail(PT_ERR_INVALID, "pt_denoise_stage_times: null argument");
+        dn_check_size("pt_denoise_stage_times", width, height);
+        if (!samples) fail(PT_ERR_INVALID, "pt_denoise_stage_times: samples is 0");
+        if (device >= 0) HIP_CHECK(hipSetDevice(device));
+        const size_t n_ev = params->iterations ? params->iterations + 3u : 2u;
+        std::vector<hipEvent_t> ev(n_ev, nullptr);
+        struct Free {
+            std::vector<hipEvent_t>& e;
+            ~Free() {
+                for (hipEvent_t x : e)
+                    if (x) (void)hipEventDestroy(x);
+            }
+        } guard{ev};
+        for (hipEvent_t& x : ev) HIP_CHECK(hipEventCreate(&x));
+        denoise_launch(width, height, samples, *params, (const float*)d_accum, (const float4*)d_guides, (float*)d_out_color,
+                       (uint8_t*)d_out_rgb8, (uint8_t*)d_scratch, nullptr, ev.data());
+        HIP_CHECK(hipDeviceSynchronize());
+        for (int k = 0; k < PT_DENOISE_STAGES; ++k) ms[k] = 0.f;
+        if (params->iterations == 0) {
+            HIP_CHECK(hipEventElapsedTime(&ms[PT_DENOISE_STAGES - 1], ev[0], ev[1]));
+            return;
+        }
+        HIP_CHECK(hipEventElapsedTime(&ms[0], ev[0], ev[1]));
+        for (uint32_t i = 0; i < params->iterations; ++i) HIP_CHECK(hipEventElapsedTime(&ms[1 + i], ev[1 + i], ev[2 + i]));
+        HIP_CHECK(hipEventElapsedTime(&ms[PT_DENOISE_STAGES - 1], ev[1 + params->iterations], ev[2 + params->iterations]));
+    });
+}
+
+int pt_render_denoised(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, const pt_denoise_params* params,
+                       uint8_t* rgb8, float* color) {
+    return guarded([&] {
+        if (!scene || !profile) fail(PT_ERR_INVALID, "pt_render_denoised: null argument");
+        dn_check_params("pt_render_denoised", params);
+        pt_opts o;
+        normalise_opts(*profile, opts, o);
+        if (o.shard_count > 1) fail(PT_ERR_UNSUPPORTED, "pt_render_denoised: the filter needs the whole image (shard_count %u)", o.shard_count);
+        if (!profile->samples) fail(PT_ERR_INVALID, "pt_render_denoised: samples is 0");
+        HIP_CHECK(hipSetDevice(scene->device));
+        const uint32_t w = profile->width, h = profile->height;
+        const size_t n = (size_t)w * h;
+        Staged<uint8_t> d_rgb(nullptr, n * 3), d_scratch(nullptr, pt_denoise_scratch_bytes(w, h));
+        Staged<float> d_acc(nullptr, n * 3), d_color(nullptr, n * 3);
+        Staged<float4> d_guides(nullptr, n * 2);
+        // the raw frame (its rgb8 feeds the preview callback only), then guides and filter behind it on the same stream
+        render_device(render_state(scene), *profile, opts, d_rgb.d, d_acc.d, nullptr, true);
+        guides_launch(*scene, w, h, d_guides.d, nullptr);
+        denoise_launch(w, h, profile->samples, *params, d_acc.d, d_guides.d, color ? d_color.d : nullptr, rgb8 ? d_rgb.d : nullptr,
+                       d_scratch.d, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        if (rgb8) d_rgb.fetch(rgb8, n * 3);
+        if (color) d_color.fetch(color, n * 3);
     });
 }
 

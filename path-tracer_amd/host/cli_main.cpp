@@ -57,6 +57,9 @@ void usage_render(FILE* f) {
           "                           takes the frame index in its %d / %0Nd field (e.g. out/frame_%04d.png)\n"
           "      --keyframes <FRAMES>  Render one frame per object of a JSON array of keyframes (\"camera\", \"lights\",\n"
           "                           \"materials\" edits, each frame on top of the last); OUTPUT as with --camera-path\n"
+          "      --denoise            Write the frame filtered by the edge-avoiding a-trous denoiser (first-hit normal, depth and\n"
+          "                           albedo guides); one device only, -v previews stay raw\n"
+          "      --denoise-iterations <N>  Filter passes of --denoise, pass i has step 2^i [0..8, default: the library's]\n"
           "  -h, --help               Print help\n",
           f);
 }
@@ -130,6 +133,8 @@ int run_render(int argc, char** argv) {
     std::string camera_path, keyframes_path;
     bool have_output = false, have_profile = false, quiet = false, debug_textures = false, stats = false, viewer = false;
     bool have_camera_path = false, have_keyframes = false;
+    bool denoise = false;
+    int denoise_iterations = -1;
     int device = 0;
     std::vector<int> devices;
     for (int i = 0; i < argc; ++i) {
@@ -160,6 +165,13 @@ int run_render(int argc, char** argv) {
         else if (a == "-qv" || a == "-vq") quiet = viewer = true;
         else if (a == "--debug-textures") debug_textures = true;
         else if (a == "--stats") stats = true;
+        else if (a == "--denoise") denoise = true;
+        else if (a == "--denoise-iterations" || a.rfind("--denoise-iterations=", 0) == 0) {
+            std::string v = value("--denoise-iterations <N>");
+            if (v.empty() || v.size() > 1 || !isdigit((unsigned char)v[0]) || v[0] > '8')
+                die("error: invalid value '" + v + "' for '--denoise-iterations <N>': 0..8 expected");
+            denoise_iterations = v[0] - '0';
+        }
         else if (a == "--camera-path" || a.rfind("--camera-path=", 0) == 0) {
             camera_path = value("--camera-path <CAMERAS>");
             have_camera_path = true;
@@ -195,6 +207,11 @@ int run_render(int argc, char** argv) {
             have_profile = true;
         }
     }
+
+    if (denoise_iterations >= 0 && !denoise) die("error: '--denoise-iterations <N>' needs '--denoise'");
+    if (denoise && devices.size() > 1)
+        die("error: the argument '--denoise' cannot be used with more than one device in '--devices <A,B,..>' (the gathered "
+            "multi-GPU frame is u8 only; the filter needs the f32 frame on one device)");
 
     // Profile::load / Default (main.rs:33-36)
     pt_profile profile;
@@ -437,12 +454,18 @@ int run_render(int argc, char** argv) {
         }
     }
     std::vector<uint8_t> rgb((size_t)profile.width * profile.height * 3);
+    pt_denoise_params dn;
+    pt_denoise_params_default(&dn);
+    dn.tonemap = profile.tonemap;
+    if (denoise_iterations >= 0) dn.iterations = (uint32_t)denoise_iterations;
     const size_t n_frames = edits.empty() ? 1 : edits.size();   // (--camera-path / --keyframes: one frame each, the scene kept)
     auto t3 = t2, t4 = t2;
     for (size_t f = 0; f < n_frames; ++f) {
         if (f > 0 && apply_frame(scene, f) != PT_OK) die(pt_last_error());
         pv.path = frame_name(f);
-        if (pt_render(scene, &profile, &opts, rgb.data(), nullptr) != PT_OK) die(pt_last_error());
+        if ((denoise ? pt_render_denoised(scene, &profile, &opts, &dn, rgb.data(), nullptr)
+                     : pt_render(scene, &profile, &opts, rgb.data(), nullptr)) != PT_OK)
+            die(pt_last_error());
         t3 = std::chrono::steady_clock::now();
         if (!quiet)
             fprintf(stderr, "\nDone: %llds\n", (long long)std::chrono::duration_cast<std::chrono::seconds>(t3 - t2).count());

@@ -365,6 +365,70 @@ int pt_denoise_stage_times(int device, uint32_t width, uint32_t height, uint32_t
                            void* d_scratch, float* ms);
 
 /* ------------------------------------------------------------------ */
+/* sample moments and the variance-guided filter           */
+/* ------------------------------------------------------------------ */
+
+/* pt_render / pt_render_device that also report the first two moments of every pixel's sample LUMINANCE,
+ *     lum(a) = (0.2126f*a.r + 0.7152f*a.g) + 0.0722f*a.b.
+ * moments: n_local x 2 f32 in the packed local order of accum (shards as in pt_render): [0] = m1, [1] = m2.  Both start at 0.f
+ * and are built in sample order s = 0..N-1 from the radiance c_s of the sample (the value that is added to accum):
+ *     L = lum(c_s);  m1 = m1 + L;  m2 = m2 + L*L        (each step one f32 operation, in this order)
+ * A pixel of a block the camera-grid cull found empty uses the background value that accum gets for it, once per sample.
+ * rgb8 and accum [either may be NULL] equal pt_render's bit for bit; moments is required.  The device form has the contract of
+ * pt_render_device (d_moments: 8-byte aligned).  The frame runs the same launches on the same queues as pt_render's (one
+ * kernel, k_accumulate_moments, takes the place of k_accumulate), so later frames - planned ones included - are unchanged.
+ * Pipelines that stage no samples (PT_FLAG_MEGAKERNEL) return PT_ERR_UNSUPPORTED before any device work. */
+int pt_render_moments(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts,
+                      uint8_t* rgb8, float* accum, float* moments);
+int pt_render_moments_device(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts,
+                             void* d_rgb8, void* d_accum, void* d_moments, void* hip_stream);
+/* Test hook: the radiance of every sample on its own.  samples (HOST): profile.samples x n_local x 3 f32, sample s of packed
+ * pixel p at (s*n_local + p)*3; pixels of culled blocks hold the background value.  Summed in sample order they give accum;
+ * the moments above are held to a restatement over these planes bit for bit.  PT_ERR_INVALID when the planes would exceed
+ * 256 MiB, PT_ERR_UNSUPPORTED as for pt_render_moments. */
+int pt_render_samples(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, float* samples /* host */);
+
+/* The a-trous filter of pt_denoise with a colour weight steered by the per-pixel variance of the mean (SVGF's guide, Schied et
+ * al. 2017, without its temporal part).  All f32, one IEEE operation per step in the order written (IEEE divide and sqrt;
+ * tests/denoise_var_model.py restates it bit for bit):
+ *   prep    valid, c, u, d, x, gx, gy exactly as pt_denoise's prep.
+ *           N = (float)samples;  mu = m1 / N;  e2 = m2 / N;  s2 = max(0, e2 - mu*mu);  vL = s2 / (float)(samples - 1)
+ *           v = vL / (lum(d) * lum(d))   (NO_DEMODULATE: v = vL);  an invalid pixel: v = 0
+ *   pass i  s = 2^i.  Variance blur at UNIT spacing: b = 0, bs = 0; dy = -1..1 outer, dx = -1..1 inner, q = p + (dx, dy) in the
+ *           image and valid: g = {1/4, 1/8, 1/16}[|dx| + |dy|];  b += v_q * g;  bs += g.   vb = b / bs
+ *           lden = sigma_color * sqrt(vb) + 1e-6f
+ *           taps, k, wn, wz, the skipping of invalid / out-of-image taps and the tap order as in pt_denoise's pass i;
+ *           wl = wexp(|lum(x_p) - lum(x_q)| / lden);  centre tap w = k, any other w = ((k * wn) * wz) * wl
+ *           acc += x_q * w;  wsum += w;  vacc += v_q * (w * w)
+ *           the pass writes x = acc / wsum and v = vacc / (wsum * wsum)   (x and v of this pass's INPUT on the right-hand sides)
+ *   finish  as pt_denoise.   iterations = 0: as pt_denoise with iterations = 0.
+ * The functions take pt_denoise_params; for them sigma_color is the LUMINANCE sigma in standard deviations of the pixel mean
+ * and must be positive and finite.  moments: W*H*2 f32 (pt_render_moments', row-major, unsharded), after accum.  samples >= 2,
+ * otherwise PT_ERR_INVALID; every other argument rule, the scratch and the stage times are pt_denoise's.  Non-finite accumulator
+ * or moment values are outside the contract. */
+/* The defaults: the best of the grid tools/measure_denoise_var_gain.py searched (tests/golden/denoise_var_gain.json), FILMIC. */
+#define PT_DENOISE_VAR_DEFAULT_ITERATIONS 1
+#define PT_DENOISE_VAR_DEFAULT_FLAGS PT_DENOISE_NO_DEMODULATE
+#define PT_DENOISE_VAR_DEFAULT_NORMAL_POWER_LOG2 3
+#define PT_DENOISE_VAR_DEFAULT_SIGMA_COLOR 4.0f
+#define PT_DENOISE_VAR_DEFAULT_SIGMA_DEPTH 4.0f
+void pt_denoise_var_params_default(pt_denoise_params* params);
+uint64_t pt_denoise_var_scratch_bytes(uint32_t width, uint32_t height);
+int pt_denoise_var(int device, uint32_t width, uint32_t height, uint32_t samples, const pt_denoise_params* params,
+                   const float* accum, const float* moments, const float* guides, float* out_color, uint8_t* out_rgb8);
+int pt_denoise_var_device(int device, uint32_t width, uint32_t height, uint32_t samples, const pt_denoise_params* params,
+                          const void* d_accum, const void* d_moments, const void* d_guides, void* d_out_color,
+                          void* d_out_rgb8, void* d_scratch, void* hip_stream);
+/* pt_render_moments + guides + pt_denoise_var without leaving the device, like pt_render_denoised (same outputs, the preview
+ * callback receives the RAW frames, shard_count > 1 is PT_ERR_UNSUPPORTED). */
+int pt_render_denoised_var(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts,
+                           const pt_denoise_params* params, uint8_t* rgb8, float* color);
+/* Measurement, as pt_denoise_stage_times: ms[0] = prep, ms[1 + i] = pass i, ms[9] = finish. */
+int pt_denoise_var_stage_times(int device, uint32_t width, uint32_t height, uint32_t samples, const pt_denoise_params* params,
+                               const void* d_accum, const void* d_moments, const void* d_guides, void* d_out_color,
+                               void* d_out_rgb8, void* d_scratch, float* ms);
+
+/* ------------------------------------------------------------------ */
 /* measurement                                                         */
 /* ------------------------------------------------------------------ */
 

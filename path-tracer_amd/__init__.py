@@ -117,8 +117,17 @@ class DenoiseParams(C.Structure):
     @classmethod
     def default(cls, **changes):
         """pt_denoise_params_default, with fields replaced by keyword."""
+        return cls._from(gpu_lib().pt_denoise_params_default, changes)
+
+    @classmethod
+    def default_var(cls, **changes):
+        """pt_denoise_var_params_default (the variance-guided filter's settings), with fields replaced by keyword."""
+        return cls._from(gpu_lib().pt_denoise_var_params_default, changes)
+
+    @classmethod
+    def _from(cls, fill, changes):
         p = cls()
-        gpu_lib().pt_denoise_params_default(C.byref(p))
+        fill(C.byref(p))
         for k, v in changes.items():
             if k not in dict(cls._fields_):
                 raise TypeError(f"pt_denoise_params has no field {k!r}")
@@ -221,7 +230,10 @@ GPU_SYMBOLS = ["pt_scene_create", "pt_scene_destroy", "pt_scene_set_camera", "pt
                "pt_trace_rays_all", "pt_intersect_triangles",
                "pt_rng_words", "pt_eval_math", "pt_measure_copy_bandwidth", "pt_measure_gather_rate", "pt_last_error",
                "pt_version", "pt_render_guides", "pt_render_guides_device", "pt_denoise_params_default", "pt_denoise_scratch_bytes",
-               "pt_denoise", "pt_denoise_device", "pt_render_denoised", "pt_denoise_stage_times"]
+               "pt_denoise", "pt_denoise_device", "pt_render_denoised", "pt_denoise_stage_times",
+               "pt_render_moments", "pt_render_moments_device", "pt_render_samples", "pt_denoise_var_params_default",
+               "pt_denoise_var_scratch_bytes", "pt_denoise_var", "pt_denoise_var_device", "pt_render_denoised_var",
+               "pt_denoise_var_stage_times"]
 
 
 def host_lib():
@@ -335,6 +347,17 @@ def gpu_lib():
         L.pt_denoise_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, dp, vp, vp, vp, vp, vp, vp]
         L.pt_render_denoised.argtypes = [vp, C.POINTER(Profile), C.POINTER(Opts), dp, vp, vp]
         L.pt_denoise_stage_times.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, dp, vp, vp, vp, vp, vp, vp]
+        L.pt_render_moments.argtypes = [vp, C.POINTER(Profile), C.POINTER(Opts), vp, vp, vp]
+        L.pt_render_moments_device.argtypes = [vp, C.POINTER(Profile), C.POINTER(Opts), vp, vp, vp, vp]
+        L.pt_render_samples.argtypes = [vp, C.POINTER(Profile), C.POINTER(Opts), vp]
+        L.pt_denoise_var_params_default.argtypes = [dp]
+        L.pt_denoise_var_params_default.restype = None
+        L.pt_denoise_var_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
+        L.pt_denoise_var_scratch_bytes.restype = C.c_uint64
+        L.pt_denoise_var.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, dp, vp, vp, vp, vp, vp]
+        L.pt_denoise_var_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, dp, vp, vp, vp, vp, vp, vp, vp]
+        L.pt_render_denoised_var.argtypes = [vp, C.POINTER(Profile), C.POINTER(Opts), dp, vp, vp]
+        L.pt_denoise_var_stage_times.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, dp, vp, vp, vp, vp, vp, vp, vp]
         L.pt_last_error.restype = C.c_char_p
         L.pt_version.restype = C.c_char_p
         _gpu = L
@@ -781,6 +804,44 @@ class GpuScene:
                                               C.byref(params) if params is not None else None, rgb.ctypes.data, col.ctypes.data))
         return rgb, col
 
+    def render_moments(self, profile, opts=None):
+        """pt_render_moments: (rgb8 [n, 3] uint8, accum [n, 3] float32, moments [n, 2] float32 = sum and sum of squares of
+        the samples' luminance)."""
+        import numpy as np
+        opts = opts or Opts.make()
+        n = int(self.lib.pt_local_pixel_count(C.byref(profile), C.byref(opts)))
+        rgb = np.empty((n, 3), np.uint8)
+        acc = np.empty((n, 3), np.float32)
+        mom = np.empty((n, 2), np.float32)
+        check_gpu(self.lib.pt_render_moments(self.handle, C.byref(profile), C.byref(opts), rgb.ctypes.data, acc.ctypes.data,
+                                             mom.ctypes.data))
+        return rgb, acc, mom
+
+    def render_moments_device(self, profile, opts, d_rgb8, d_accum, d_moments, stream=0):
+        check_gpu(self.lib.pt_render_moments_device(self.handle, C.byref(profile), C.byref(opts), d_rgb8, d_accum, d_moments, stream))
+
+    def render_samples(self, profile, opts=None):
+        """pt_render_samples (test hook): [samples, n, 3] float32, the radiance of every sample of every packed pixel."""
+        import numpy as np
+        opts = opts or Opts.make()
+        n = int(self.lib.pt_local_pixel_count(C.byref(profile), C.byref(opts)))
+        if profile.samples * n * 12 > 256 << 20:
+            raise PtError(PT_ERR_INVALID, "render_samples: the sample planes would exceed 256 MiB")
+        out = np.empty((profile.samples, n, 3), np.float32)
+        check_gpu(self.lib.pt_render_samples(self.handle, C.byref(profile), C.byref(opts), out.ctypes.data))
+        return out
+
+    def render_denoised_var(self, profile, params, opts=None):
+        """pt_render_denoised_var: (rgb8 [H*W, 3] uint8, color [H*W, 3] float32 mean radiance) of the frame filtered with
+        its own per-pixel variance."""
+        import numpy as np
+        n = profile.width * profile.height
+        rgb = np.empty((n, 3), np.uint8)
+        col = np.empty((n, 3), np.float32)
+        check_gpu(self.lib.pt_render_denoised_var(self.handle, C.byref(profile), C.byref(opts) if opts is not None else None,
+                                                  C.byref(params) if params is not None else None, rgb.ctypes.data, col.ctypes.data))
+        return rgb, col
+
     def timing(self):
         t = Timing()
         check_gpu(self.lib.pt_get_timing(self.handle, C.byref(t)))
@@ -872,6 +933,28 @@ def denoise(width, height, samples, params, accum, guides, device=0):
 
 def denoise_scratch_bytes(width, height):
     return int(gpu_lib().pt_denoise_scratch_bytes(width, height))
+
+
+def denoise_var(width, height, samples, params, accum, moments, guides, device=0):
+    """pt_denoise_var on host arrays: denoise() plus moments [H*W, 2] float32 (GpuScene.render_moments); returns
+    (color [H*W, 3] float32 mean radiance, rgb8 [H*W, 3] uint8)."""
+    import numpy as np
+    n = width * height
+    accum = np.ascontiguousarray(accum, np.float32)
+    moments = np.ascontiguousarray(moments, np.float32)
+    guides = np.ascontiguousarray(guides, np.float32)
+    if accum.size != n * 3 or moments.size != n * 2 or guides.size != n * PT_GUIDE_FLOATS:
+        raise ValueError("denoise_var: accum must hold width*height*3, moments width*height*2 and guides width*height*8 floats")
+    col = np.empty((n, 3), np.float32)
+    rgb = np.empty((n, 3), np.uint8)
+    check_gpu(gpu_lib().pt_denoise_var(device, width, height, samples, C.byref(params) if params is not None else None,
+                                       accum.ctypes.data, moments.ctypes.data, guides.ctypes.data, col.ctypes.data,
+                                       rgb.ctypes.data))
+    return col, rgb
+
+
+def denoise_var_scratch_bytes(width, height):
+    return int(gpu_lib().pt_denoise_var_scratch_bytes(width, height))
 
 
 def local_pixel_map(profile, opts):

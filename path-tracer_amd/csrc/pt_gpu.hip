@@ -14,6 +14,7 @@
 //   k_assemble        scatter all-gathered packed tiles into a row-major image
 //   k_debug           --debug-textures G-buffer pass (debug_renderer.rs:64-105)
 //   k_guides, k_dn_*  pt_denoise.h: first-hit guide planes and the a-trous filter of denoised previews
+//   k_accumulate_moments, k_dnv_*  pt_variance.h: per-pixel sample moments and the variance-guided form of that filter
 //   k_stream_copy     achievable-HBM yardstick of the roofline (pt_measure_copy_bandwidth)
 //   k_trace / k_trace_all / k_isect / k_rng / k_math   parity-test hooks
 #include <hip/hip_runtime.h>
@@ -43,6 +44,7 @@
 #include "pt_escape_build.h"
 #include "pt_grid_build.h"
 #include "pt_denoise.h"
+#include "pt_variance.h"
 #include "pthost.h"
 #include "../host/scene_check.h"
 
@@ -2878,11 +2880,19 @@ void frame_readout(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, void*
     }
 }
 
-// One frame of pt_render, pt_render_device and pt_render_gathered.
+// What a frame of the wavefront integrator can hand out besides accum (pt_variance.h): the luminance moments of every
+// pixel's samples (n_local x 2 f32) and, for the tests, the staged samples themselves (samples x n_local x 3 f32).
+struct FrameTaps {
+    float2* moments = nullptr;
+    float* samples = nullptr;
+};
+
+// One frame of pt_render, pt_render_device and pt_render_gathered; taps: of pt_render_moments and pt_render_samples.
 void render_device(pt_scene& s, const pt_profile& p, const pt_opts* opts_in, void* d_rgb8, void* d_accum,
-                   hipStream_t stream, bool allow_preview = false) {
+                   hipStream_t stream, bool allow_preview = false, const FrameTaps* taps = nullptr) {
     Frame f;
     if (!frame_setup(s, p, opts_in, d_accum, stream, f)) return;
+    if (taps && !f.wavefront) fail(PT_ERR_UNSUPPORTED, "this pipeline stages no samples");
     const pt_opts& o = f.o;
     WfFrame wf;
     if (f.wavefront) {
@@ -2915,13 +2925,25 @@ void render_device(pt_scene& s, const pt_profile& p, const pt_opts* opts_in, voi
             uint32_t chunk_no = 0;
             for (uint32_t base = 0; base < total_items; base += wf.cap, ++chunk_no)
                 render_chunk(s, f, wf, tl, P, stream, base, total_items, chunk_no);
+            const dim3 acc_grid(((uint32_t)f.tm.n_local + 255u) / 256u);
+            const uint8_t* pixel_empty = wf.block_empty ? (const uint8_t*)(wf.block_empty + f.blocks64 + 1u) : (const uint8_t*)nullptr;
             tl.begin(4);
-            hipLaunchKernelGGL(k_accumulate, dim3(((uint32_t)f.tm.n_local + 255u) / 256u), dim3(256), 0, stream,
-                               (const float*)s.staging_buf.p, f.accum, (uint32_t)f.tm.n_local, nb, s0 == 0 ? 1 : 0,
-                               wf.block_empty ? (const uint8_t*)(wf.block_empty + f.blocks64 + 1u) : (const uint8_t*)nullptr,
-                               s.dev.background[0], s.dev.background[1], s.dev.background[2]);
+            if (taps && taps->moments)
+                hipLaunchKernelGGL(k_accumulate_moments, acc_grid, dim3(256), 0, stream, (const float*)s.staging_buf.p, f.accum,
+                                   taps->moments, (uint32_t)f.tm.n_local, nb, s0 == 0 ? 1 : 0, pixel_empty,
+                                   s.dev.background[0], s.dev.background[1], s.dev.background[2]);
+            else
+                hipLaunchKernelGGL(k_accumulate, acc_grid, dim3(256), 0, stream,
+                                   (const float*)s.staging_buf.p, f.accum, (uint32_t)f.tm.n_local, nb, s0 == 0 ? 1 : 0,
+                                   pixel_empty, s.dev.background[0], s.dev.background[1], s.dev.background[2]);
             HIP_CHECK(hipGetLastError());
             tl.end();
+            if (taps && taps->samples) {
+                hipLaunchKernelGGL(k_samples_copy, acc_grid, dim3(256), 0, stream, (const float*)s.staging_buf.p, taps->samples,
+                                   (uint32_t)f.tm.n_local, nb, s0, pixel_empty, s.dev.background[0], s.dev.background[1],
+                                   s.dev.background[2]);
+                HIP_CHECK(hipGetLastError());
+            }
         }
         if (allow_preview && o.preview && d_rgb8) {
             // viewer feed (mod.rs:133-141): post_processing(pixel / current_sample) of the samples so far
@@ -3042,6 +3064,63 @@ void denoise_launch(uint32_t width, uint32_t height, uint32_t samples, const pt_
                        p.tonemap, d_out_color, d_out_rgb8);
     HIP_CHECK(hipGetLastError());
     if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
+}
+
+// The variance-guided filter (pt_variance.h) on the planes of dn_scratch_layout: X / Y carry (x, v), U carries (u, z).
+void denoise_var_launch(uint32_t width, uint32_t height, uint32_t samples, const pt_denoise_params& p, const float* d_accum,
+                        const float2* d_moments, const float4* d_guides, float* d_out_color, uint8_t* d_out_rgb8,
+                        uint8_t* d_scratch, hipStream_t stream, hipEvent_t* ev = nullptr) {
+    const uint32_t n = width * height, blocks = (n + 255u) / 256u;
+    const uint32_t no_demod = p.flags & PT_DENOISE_NO_DEMODULATE;
+    size_t e = 0;
+    if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
+    if (p.iterations == 0) {
+        hipLaunchKernelGGL(k_dn_finish, dim3(blocks), dim3(256), 0, stream, (const float4*)nullptr, (const float*)nullptr, d_accum,
+                           samples, n, no_demod, p.tonemap, d_out_color, d_out_rgb8);
+        HIP_CHECK(hipGetLastError());
+        if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
+        return;
+    }
+    const DnScratch L = dn_scratch_layout(n);
+    float4* X = (float4*)(d_scratch + L.xa);
+    float4* Y = (float4*)(d_scratch + L.xb);
+    float4* U = (float4*)(d_scratch + L.u);
+    float2* G = (float2*)(d_scratch + L.g);
+    float* D = (float*)(d_scratch + L.d);
+    hipLaunchKernelGGL(k_dnv_prep, dim3(blocks), dim3(256), 0, stream, d_accum, d_moments, d_guides, width, height, samples,
+                       no_demod, X, U, G, D);
+    HIP_CHECK(hipGetLastError());
+    if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
+    const dim3 grid((width + DN_TILE_W - 1u) / DN_TILE_W, (height + DN_TILE_H - 1u) / DN_TILE_H);
+    DnvParams P;
+    P.sigma_depth = p.sigma_depth;
+    P.sigma_lum = p.sigma_color;
+    P.npow = p.normal_power_log2;
+    for (uint32_t i = 0; i < p.iterations; ++i) {
+        hipLaunchKernelGGL(k_dnv_pass, grid, dim3(256), 0, stream, (const float4*)X, (const float4*)U, (const float2*)G, Y,
+                           (int)width, (int)height, 1 << i, P);
+        HIP_CHECK(hipGetLastError());
+        if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
+        std::swap(X, Y);
+    }
+    // (an invalid pixel carries v = -1 in X.w: k_dn_finish's validity test)
+    hipLaunchKernelGGL(k_dn_finish, dim3(blocks), dim3(256), 0, stream, (const float4*)X, (const float*)D, d_accum, samples, n, no_demod,
+                       p.tonemap, d_out_color, d_out_rgb8);
+    HIP_CHECK(hipGetLastError());
+    if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
+}
+
+// The argument rules of the pt_denoise_var family beyond dn_check_params.
+void dnv_check(const char* who, const pt_denoise_params* p, uint32_t width, uint32_t height, uint32_t samples) {
+    dn_check_params(who, p);
+    if (!(p->sigma_color > 0.f)) fail(PT_ERR_INVALID, "%s: sigma_color (the luminance sigma) must be positive and finite", who);
+    dn_check_size(who, width, height);
+    if (samples < 2u) fail(PT_ERR_INVALID, "%s: a sample variance needs samples >= 2 (got %u)", who, samples);
+}
+
+// Pipelines that stage no samples have no moments: refused before any device work.
+void moments_check_opts(const char* who, const pt_opts* opts) {
+    if (opts && (opts->flags & PT_FLAG_MEGAKERNEL)) fail(PT_ERR_UNSUPPORTED, "%s: PT_FLAG_MEGAKERNEL stages no samples", who);
 }
 
 void guides_launch(const pt_scene& s, uint32_t width, uint32_t height, float4* d_guides, hipStream_t stream) {
@@ -3311,6 +3390,161 @@ int pt_render_denoised(const pt_scene* scene, const pt_profile* profile, const p
         guides_launch(*scene, w, h, d_guides.d, nullptr);
         denoise_launch(w, h, profile->samples, *params, d_acc.d, d_guides.d, color ? d_color.d : nullptr, rgb8 ? d_rgb.d : nullptr,
                        d_scratch.d, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        if (rgb8) d_rgb.fetch(rgb8, n * 3);
+        if (color) d_color.fetch(color, n * 3);
+    });
+}
+
+int pt_render_moments_device(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, void* d_rgb8,
+                             void* d_accum, void* d_moments, void* hip_stream) {
+    return guarded([&] {
+        if (!scene || !profile || !d_moments) fail(PT_ERR_INVALID, "pt_render_moments_device: null argument");
+        moments_check_opts("pt_render_moments_device", opts);
+        FrameTaps taps;
+        taps.moments = (float2*)d_moments;
+        render_device(render_state(scene), *profile, opts, d_rgb8, d_accum, (hipStream_t)hip_stream, false, &taps);
+    });
+}
+
+int pt_render_moments(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, uint8_t* rgb8, float* accum,
+                      float* moments) {
+    return guarded([&] {
+        if (!scene || !profile || !moments) fail(PT_ERR_INVALID, "pt_render_moments: null argument");
+        moments_check_opts("pt_render_moments", opts);
+        HIP_CHECK(hipSetDevice(scene->device));
+        pt_opts o;
+        normalise_opts(*profile, opts, o);
+        uint64_t n = make_tile_map(*profile, o, o.shard_rank).n_local;
+        Staged<uint8_t> d_rgb(nullptr, n * 3);
+        Staged<float> d_acc(nullptr, n * 3);
+        Staged<float2> d_mom(nullptr, n);
+        FrameTaps taps;
+        taps.moments = d_mom.d;
+        render_device(render_state(scene), *profile, opts, d_rgb.d, d_acc.d, nullptr, true, &taps);
+        HIP_CHECK(hipDeviceSynchronize());
+        if (rgb8) d_rgb.fetch(rgb8, n * 3);
+        if (accum) d_acc.fetch(accum, n * 3);
+        d_mom.fetch((float2*)moments, n);
+    });
+}
+
+int pt_render_samples(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, float* samples) {
+    return guarded([&] {
+        if (!scene || !profile || !samples) fail(PT_ERR_INVALID, "pt_render_samples: null argument");
+        moments_check_opts("pt_render_samples", opts);
+        pt_opts o;
+        normalise_opts(*profile, opts, o);
+        const uint64_t n = make_tile_map(*profile, o, o.shard_rank).n_local;
+        if (n && (uint64_t)profile->samples > (256ull << 20) / (n * 12u))
+            fail(PT_ERR_INVALID, "pt_render_samples: %u planes of %llu pixels exceed 256 MiB", profile->samples, (unsigned long long)n);
+        HIP_CHECK(hipSetDevice(scene->device));
+        Staged<float> d_samples(nullptr, (size_t)profile->samples * n * 3);
+        FrameTaps taps;
+        taps.samples = d_samples.d;
+        render_device(render_state(scene), *profile, opts, nullptr, nullptr, nullptr, false, &taps);
+        HIP_CHECK(hipDeviceSynchronize());
+        d_samples.fetch(samples, (size_t)profile->samples * n * 3);
+    });
+}
+
+void pt_denoise_var_params_default(pt_denoise_params* p) {
+    if (!p) return;
+    // the winner of tools/measure_denoise_var_gain.py (tests/golden/denoise_var_gain.json)
+    p->iterations = PT_DENOISE_VAR_DEFAULT_ITERATIONS;
+    p->flags = PT_DENOISE_VAR_DEFAULT_FLAGS;
+    p->normal_power_log2 = PT_DENOISE_VAR_DEFAULT_NORMAL_POWER_LOG2;
+    p->tonemap = PT_TONEMAP_FILMIC;
+    p->sigma_color = PT_DENOISE_VAR_DEFAULT_SIGMA_COLOR;
+    p->sigma_depth = PT_DENOISE_VAR_DEFAULT_SIGMA_DEPTH;
+}
+
+uint64_t pt_denoise_var_scratch_bytes(uint32_t width, uint32_t height) { return pt_denoise_scratch_bytes(width, height); }
+
+int pt_denoise_var_device(int device, uint32_t width, uint32_t height, uint32_t samples, const pt_denoise_params* params,
+                          const void* d_accum, const void* d_moments, const void* d_guides, void* d_out_color,
+                          void* d_out_rgb8, void* d_scratch, void* hip_stream) {
+    return guarded([&] {
+        dnv_check("pt_denoise_var_device", params, width, height, samples);
+        if (!d_accum || !d_moments || !d_guides || (!d_scratch && params->iterations)) fail(PT_ERR_INVALID, "pt_denoise_var_device: null argument");
+        if (device >= 0) HIP_CHECK(hipSetDevice(device));
+        denoise_var_launch(width, height, samples, *params, (const float*)d_accum, (const float2*)d_moments, (const float4*)d_guides,
+                           (float*)d_out_color, (uint8_t*)d_out_rgb8, (uint8_t*)d_scratch, (hipStream_t)hip_stream);
+    });
+}
+
+int pt_denoise_var(int device, uint32_t width, uint32_t height, uint32_t samples, const pt_denoise_params* params,
+                   const float* accum, const float* moments, const float* guides, float* out_color, uint8_t* out_rgb8) {
+    return guarded([&] {
+        dnv_check("pt_denoise_var", params, width, height, samples);
+        if (!accum || !moments || !guides) fail(PT_ERR_INVALID, "pt_denoise_var: null argument");
+        if (device >= 0) HIP_CHECK(hipSetDevice(device));
+        const size_t n = (size_t)width * height;
+        Staged<float> d_acc(accum, n * 3), d_color(nullptr, n * 3);
+        Staged<float2> d_mom((const float2*)moments, n);
+        Staged<float4> d_guides((const float4*)guides, n * 2);
+        Staged<uint8_t> d_rgb(nullptr, n * 3), d_scratch(nullptr, pt_denoise_var_scratch_bytes(width, height));
+        denoise_var_launch(width, height, samples, *params, d_acc.d, d_mom.d, d_guides.d, d_color.d, d_rgb.d, d_scratch.d, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        if (out_color) d_color.fetch(out_color, n * 3);
+        if (out_rgb8) d_rgb.fetch(out_rgb8, n * 3);
+    });
+}
+
+int pt_denoise_var_stage_times(int device, uint32_t width, uint32_t height, uint32_t samples, const pt_denoise_params* params,
+                               const void* d_accum, const void* d_moments, const void* d_guides, void* d_out_color,
+                               void* d_out_rgb8, void* d_scratch, float* ms) {
+    return guarded([&] {
+        dnv_check("pt_denoise_var_stage_times", params, width, height, samples);
+        if (!d_accum || !d_moments || !d_guides || !ms || (!d_scratch && params->iterations)) fail(PT_ERR_INVALID, "pt_denoise_var_stage_times: null argument");
+        if (device >= 0) HIP_CHECK(hipSetDevice(device));
+        const size_t n_ev = params->iterations ? params->iterations + 3u : 2u;
+        std::vector<hipEvent_t> ev(n_ev, nullptr);
+        struct Free {
+            std::vector<hipEvent_t>& e;
+            ~Free() {
+                for (hipEvent_t x : e)
+                    if (x) (void)hipEventDestroy(x);
+            }
+        } guard{ev};
+        for (hipEvent_t& x : ev) HIP_CHECK(hipEventCreate(&x));
+        denoise_var_launch(width, height, samples, *params, (const float*)d_accum, (const float2*)d_moments, (const float4*)d_guides,
+                           (float*)d_out_color, (uint8_t*)d_out_rgb8, (uint8_t*)d_scratch, nullptr, ev.data());
+        HIP_CHECK(hipDeviceSynchronize());
+        for (int k = 0; k < PT_DENOISE_STAGES; ++k) ms[k] = 0.f;
+        if (params->iterations == 0) {
+            HIP_CHECK(hipEventElapsedTime(&ms[PT_DENOISE_STAGES - 1], ev[0], ev[1]));
+            return;
+        }
+        HIP_CHECK(hipEventElapsedTime(&ms[0], ev[0], ev[1]));
+        for (uint32_t i = 0; i < params->iterations; ++i) HIP_CHECK(hipEventElapsedTime(&ms[1 + i], ev[1 + i], ev[2 + i]));
+        HIP_CHECK(hipEventElapsedTime(&ms[PT_DENOISE_STAGES - 1], ev[1 + params->iterations], ev[2 + params->iterations]));
+    });
+}
+
+int pt_render_denoised_var(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, const pt_denoise_params* params,
+                           uint8_t* rgb8, float* color) {
+    return guarded([&] {
+        if (!scene || !profile) fail(PT_ERR_INVALID, "pt_render_denoised_var: null argument");
+        dnv_check("pt_render_denoised_var", params, profile->width, profile->height, profile->samples);
+        moments_check_opts("pt_render_denoised_var", opts);
+        pt_opts o;
+        normalise_opts(*profile, opts, o);
+        if (o.shard_count > 1) fail(PT_ERR_UNSUPPORTED, "pt_render_denoised_var: the filter needs the whole image (shard_count %u)", o.shard_count);
+        HIP_CHECK(hipSetDevice(scene->device));
+        const uint32_t w = profile->width, h = profile->height;
+        const size_t n = (size_t)w * h;
+        Staged<uint8_t> d_rgb(nullptr, n * 3), d_scratch(nullptr, pt_denoise_var_scratch_bytes(w, h));
+        Staged<float> d_acc(nullptr, n * 3), d_color(nullptr, n * 3);
+        Staged<float2> d_mom(nullptr, n);
+        Staged<float4> d_guides(nullptr, n * 2);
+        FrameTaps taps;
+        taps.moments = d_mom.d;
+        // the raw frame with its moments (its rgb8 feeds the preview callback only), then guides and filter on the same stream
+        render_device(render_state(scene), *profile, opts, d_rgb.d, d_acc.d, nullptr, true, &taps);
+        guides_launch(*scene, w, h, d_guides.d, nullptr);
+        denoise_var_launch(w, h, profile->samples, *params, d_acc.d, d_mom.d, d_guides.d, color ? d_color.d : nullptr,
+                           rgb8 ? d_rgb.d : nullptr, d_scratch.d, nullptr);
         HIP_CHECK(hipDeviceSynchronize());
         if (rgb8) d_rgb.fetch(rgb8, n * 3);
         if (color) d_color.fetch(color, n * 3);

@@ -60,6 +60,8 @@ void usage_render(FILE* f) {
           "      --denoise            Write the frame filtered by the edge-avoiding a-trous denoiser (first-hit normal, depth and\n"
           "                           albedo guides); one device only, -v previews stay raw\n"
           "      --denoise-iterations <N>  Filter passes of --denoise, pass i has step 2^i [0..8, default: the library's]\n"
+          "      --denoise-variance   With --denoise: steer the filter's colour weight by the per-pixel variance of the frame's own\n"
+          "                           samples (needs samples >= 2 in the profile)\n"
           "  -h, --help               Print help\n",
           f);
 }
@@ -133,7 +135,7 @@ int run_render(int argc, char** argv) {
     std::string camera_path, keyframes_path;
     bool have_output = false, have_profile = false, quiet = false, debug_textures = false, stats = false, viewer = false;
     bool have_camera_path = false, have_keyframes = false;
-    bool denoise = false;
+    bool denoise = false, denoise_variance = false;
     int denoise_iterations = -1;
     int device = 0;
     std::vector<int> devices;
@@ -166,6 +168,7 @@ int run_render(int argc, char** argv) {
         else if (a == "--debug-textures") debug_textures = true;
         else if (a == "--stats") stats = true;
         else if (a == "--denoise") denoise = true;
+        else if (a == "--denoise-variance") denoise_variance = true;
         else if (a == "--denoise-iterations" || a.rfind("--denoise-iterations=", 0) == 0) {
             std::string v = value("--denoise-iterations <N>");
             if (v.empty() || v.size() > 1 || !isdigit((unsigned char)v[0]) || v[0] > '8')
@@ -209,6 +212,7 @@ int run_render(int argc, char** argv) {
     }
 
     if (denoise_iterations >= 0 && !denoise) die("error: '--denoise-iterations <N>' needs '--denoise'");
+    if (denoise_variance && !denoise) die("error: '--denoise-variance' needs '--denoise'");
     if (denoise && devices.size() > 1)
         die("error: the argument '--denoise' cannot be used with more than one device in '--devices <A,B,..>' (the gathered "
             "multi-GPU frame is u8 only; the filter needs the f32 frame on one device)");
@@ -216,6 +220,9 @@ int run_render(int argc, char** argv) {
     // Profile::load / Default (main.rs:33-36)
     pt_profile profile;
     if (pth_profile_load(have_profile ? profile_path.c_str() : nullptr, &profile) != PT_OK) die(pth_last_error());
+    if (denoise_variance && profile.samples < 2)
+        die("error: '--denoise-variance' needs a profile with samples >= 2 (a sample variance of " + std::to_string(profile.samples) +
+            " sample does not exist)");
 
     // --camera-path / --keyframes: everything they can get wrong is found before any GPU work
     std::vector<pt_camera> cameras;
@@ -455,7 +462,8 @@ int run_render(int argc, char** argv) {
     }
     std::vector<uint8_t> rgb((size_t)profile.width * profile.height * 3);
     pt_denoise_params dn;
-    pt_denoise_params_default(&dn);
+    if (denoise_variance) pt_denoise_var_params_default(&dn);
+    else pt_denoise_params_default(&dn);
     dn.tonemap = profile.tonemap;
     if (denoise_iterations >= 0) dn.iterations = (uint32_t)denoise_iterations;
     const size_t n_frames = edits.empty() ? 1 : edits.size();   // (--camera-path / --keyframes: one frame each, the scene kept)
@@ -463,8 +471,9 @@ int run_render(int argc, char** argv) {
     for (size_t f = 0; f < n_frames; ++f) {
         if (f > 0 && apply_frame(scene, f) != PT_OK) die(pt_last_error());
         pv.path = frame_name(f);
-        if ((denoise ? pt_render_denoised(scene, &profile, &opts, &dn, rgb.data(), nullptr)
-                     : pt_render(scene, &profile, &opts, rgb.data(), nullptr)) != PT_OK)
+        if ((denoise_variance ? pt_render_denoised_var(scene, &profile, &opts, &dn, rgb.data(), nullptr)
+             : denoise        ? pt_render_denoised(scene, &profile, &opts, &dn, rgb.data(), nullptr)
+                              : pt_render(scene, &profile, &opts, rgb.data(), nullptr)) != PT_OK)
             die(pt_last_error());
         t3 = std::chrono::steady_clock::now();
         if (!quiet)

@@ -486,6 +486,13 @@ int pt_get_counters(const pt_scene* scene, pt_counters* out);
  * (Renderer::render's miss branch, renderer/mod.rs:184-186) without an RNG block or a cast.  0 blocks: no cull ran
  * (no camera grid, PT_FLAG_NO_GRIDS / PT_FLAG_MEGAKERNEL / PT_FLAG_COUNTERS, PT_CAM_CULL=0). */
 int pt_get_cull_stats(const pt_scene* scene, uint32_t* n_blocks, uint32_t* n_empty);
+/* The scene's cache of ChaCha words (words 0-7 of block 0 of every work item; they depend on the item enumeration -
+ * image size, samples, shard, tiling, sample batch - and on nothing else, so consecutive frames of one enumeration share
+ * them): its device bytes, the work items of the enumeration it is keyed to (0: none - it is keyed when a frame directly
+ * follows another of the same enumeration), how many of them are cached so far, and the fill launches since the scene
+ * was made.  PT_RNG_CACHE=0 switches the cache off, PT_RNG_CACHE_GIB (16) is its budget; both are read per frame.  The
+ * bytes are not part of pt_scene_info's queue_bytes or device_bytes. */
+int pt_get_rng_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* fills);
 
 /* Scene statistics after the KD build. */
 typedef struct pt_scene_info {

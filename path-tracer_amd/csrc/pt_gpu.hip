@@ -572,6 +572,21 @@ struct pt_scene {
         uint32_t mask_blocks = 0;   // blocks of the last frame's camera-grid cull table (0: no cull in that frame)
     } frame_state;
     DeviceBuffer stats_dev;
+    // Words 0-7 of ChaCha block 0 of every work item of ONE item enumeration (rng_cache_frame): a sample's seed is
+    // sample + pixel x samples - the enumeration alone, not the scene, the camera, the lights, the materials or the
+    // bounces - so the frames of a camera path, of live edits or of a steady state read them instead of deriving them
+    // again.  Two planes of `stride` uint4 (words 0-3, words 4-7) by frame-global item g = batch x items per batch + item,
+    // filled as a prefix [0, mark) in frame order.  Not an edit's to drop (drop_frame_state) and not part of queue_bytes.
+    struct RngCache {
+        DeviceBuffer buf;
+        std::vector<uint64_t> key, last_key;   // the enumeration the words are of; that of the scene's last wavefront frame
+        uint64_t items = 0;                    // work items of the keyed enumeration
+        uint64_t stride = 0;                   // of them, those the budget has room for (PT_RNG_CACHE_GIB)
+        uint64_t mark = 0, fills = 0;          // items filled so far; fill launches since the scene was made
+        hipEvent_t ev_fill = nullptr;          // behind the last fill launch
+        hipStream_t fill_stream = nullptr;
+        bool recorded = false, failed = false;   // (failed: the device could not provide the planes: no cache for this scene)
+    } rng_cache;
     uint64_t queue_bytes_last = 0;   // bytes of the path queues of the last frame (pt_scene_get_info)
     uint32_t queue_chunk_last = 0, frame_planned_last = 0;
     // escape masks: wanted (PT_ESCAPE), built when the scene has rendered `escape_after` frames of the default pipeline
@@ -594,6 +609,7 @@ struct pt_scene {
         for (hipEvent_t e : events) (void)hipEventDestroy(e);
         for (hipEvent_t e : {pipe.ev_shade, pipe.ev_shadow, pipe.ev_rng, pipe.ev_chunk, pipe.ev_trace, pipe.ev_wide, pipe.ev_exact, pipe.ev_exact_go})
             if (e) (void)hipEventDestroy(e);
+        if (rng_cache.ev_fill) (void)hipEventDestroy(rng_cache.ev_fill);
         if (pipe.side_exact) (void)hipStreamDestroy(pipe.side_exact);
         if (pipe.side) (void)hipStreamDestroy(pipe.side);
         if (pipe.side_wide) (void)hipStreamDestroy(pipe.side_wide);
@@ -2173,6 +2189,7 @@ struct WfFrame {
     // per chunk of the plan: the last bounce that has a ray (later ones are not launched); nullptr: every bounce
     const std::vector<uint32_t>* plan_last = nullptr;
     const uint32_t* block_empty = nullptr;     // the camera-grid cull table (nullptr: no cull in this frame)
+    pt_scene::RngCache* rng_cache = nullptr;   // the scene's word cache, keyed to this frame's enumeration (nullptr: not in use)
     uint32_t stats_line = 0, chunk_slot = 0;   // the frame's progress through its chunks
 };
 
@@ -2362,9 +2379,12 @@ void queue_buffers(pt_scene& s, const Frame& f, const QueueEnv& qe, WfFrame& wf)
     while (true) {
         wf.multi_chunk = (uint64_t)wf.cap < wf.items_per_batch;
         const bool two_rng = !wf.rng_one_plane && wf.multi_chunk && f.env.overlap;
+        // (a frame whose every item has room in the word cache needs no plane of its own: render_chunk allocates it should a
+        // chunk run uncached after all)
+        const bool words_cached = wf.rng_cache && wf.rng_cache->stride == wf.rng_cache->items;
         bool ok = fit(w.queue[0], (size_t)wf.cap_q[0] * 68u) && fit(w.queue[1], (size_t)wf.cap_q[1] * 68u) &&   // (64 B + the entry word)
                   fit(w.hits, (size_t)wf.cap_h * 20u) && fit(w.shadow, (size_t)wf.cap_s * 64u) &&
-                  fit(w.contrib, (size_t)wf.cap_s * 16u * lights) && fit(w.rng[0], (size_t)wf.cap * (wf.rng_one_plane ? 16u : 32u)) &&
+                  fit(w.contrib, (size_t)wf.cap_s * 16u * lights) && (words_cached || fit(w.rng[0], (size_t)wf.cap * (wf.rng_one_plane ? 16u : 32u))) &&
                   (!two_rng || fit(w.rng[1], (size_t)wf.cap * 32u)) &&
                   (!alpha || fit(w.draws, (size_t)wf.cap_h * 4u)) &&   // RNG draw index of the alpha walk
                   fit(w.offgrid, (size_t)wf.cap_s * 4u) &&   // shadow jobs left to k_og_shadow_offgrid (long normals; rays the wavefront walker does not take)
@@ -2402,6 +2422,52 @@ void queue_buffers(pt_scene& s, const Frame& f, const QueueEnv& qe, WfFrame& wf)
                          w.rng[1].bytes + w.draws.bytes + w.offgrid.bytes + w.exact[0].bytes + w.exact[1].bytes + w.deferred.bytes;
     s.queue_chunk_last = wf.cap;
     s.frame_planned_last = wf.planned ? 1u : 0u;
+}
+
+// The scene's word cache and this frame (pt_scene::RngCache).  The cache is keyed to an enumeration - everything
+// decode_item and the batch order read - when a frame of that enumeration directly follows another of the same: a
+// one-shot render never pays for the planes, a caller alternating two profiles never thrashes them.  PT_RNG_CACHE=0:
+// off; PT_RNG_CACHE_GIB: the budget (16) - both read per frame, the tests switch them.  Frames of the KD-tree pipeline
+// and instrumented frames (PT_FLAG_COUNTERS) derive their words as before and leave the cache alone.
+void rng_cache_frame(pt_scene& s, const Frame& f, WfFrame& wf, hipStream_t stream) {
+    pt_scene::RngCache& rc = s.rng_cache;
+    const std::vector<uint64_t> key = {f.p.width, f.p.height, f.p.samples, f.o.shard_rank, f.o.shard_count, f.o.tile_w, f.o.tile_h,
+                                       (uint64_t)f.env.morton, f.batch};
+    const bool follows_same = key == rc.last_key;
+    rc.last_key = key;
+    const double gib = env_num(getenv("PT_RNG_CACHE_GIB"), 16.0);
+    if (!env_bool(getenv("PT_RNG_CACHE"), true) || !(gib > 0.0)) {
+        if (rc.buf.p) {
+            HIP_CHECK(hipDeviceSynchronize());   // (frames in flight may still read the planes)
+            rc.buf.release();
+        }
+        rc.key.clear();
+        rc.items = rc.stride = rc.mark = 0;
+        return;
+    }
+    if (rc.failed || !wf.rng_one_plane || f.counting) return;
+    const uint64_t items = (uint64_t)f.blocks64 * 64u * f.p.samples;
+    const uint64_t stride = std::min<uint64_t>(items, (uint64_t)(gib * 1073741824.0) / 32u) & ~63ull;
+    if (key != rc.key || stride != rc.stride) {
+        // (W.cap carries the stride: 32 bits)
+        if (!follows_same || items >= (1ull << 32) || stride == 0) return;
+        HIP_CHECK(hipDeviceSynchronize());   // the frames in flight finish with the old words
+        if (rc.buf.bytes < stride * 32u || rc.buf.bytes > stride * 32u + (64u << 20)) rc.buf.release();
+        rc.key.clear();
+        rc.items = rc.stride = rc.mark = 0;
+        if (!rc.buf.try_ensure((size_t)stride * 32u)) {
+            rc.failed = true;
+            return;
+        }
+        if (!rc.ev_fill) HIP_CHECK(hipEventCreateWithFlags(&rc.ev_fill, hipEventDisableTiming));
+        rc.key = key;
+        rc.items = items;
+        rc.stride = stride;
+    }
+    wf.rng_cache = &rc;
+    // a frame on another stream than the one that filled last waits for that fill (one event: the caller orders the frames
+    // of a scene - they share its queues - so the earlier fills are behind it)
+    if (rc.recorded && rc.fill_stream != stream) HIP_CHECK(hipStreamWaitEvent(stream, rc.ev_fill, 0));
 }
 
 // This frame's counts, one line per (batch, chunk): taken every frame (a few KB) - the first frame's feed the plan, the
@@ -2514,6 +2580,7 @@ struct Chunk {
     // origin grids (pt_grid.h): 3 / 2 = camera cast + shadow casts inside the shade kernel (bounce 0, both kinds of grid;
     // 3: the kernel computes the ChaCha block itself), 1 = shadow casts inside the shade kernel, 0 = none
     int grid_mode = 0;
+    bool cached = false;   // the chunk's words are in the scene's word cache (rng_planes points there): GRID 3 reads them
     float4 *q_in = nullptr, *q_out = nullptr;
     bool split_shade = false;   // the shade pass in two launches (PT_WF_SPLIT)
 };
@@ -2624,18 +2691,21 @@ void shade_stage(pt_scene& s, const Frame& f, const WfFrame& wf, const Chunk& c,
                                (const uint32_t*)pipe.exact[b & 1].p, (const uint4*)pipe.hits.p, (uint32_t*)pipe.exact[(b + 1) & 1].p,
                                block_empty, c.wctr, f.gctr);
         };
-        if constexpr ((G & 3) >= 2) dispatch([&](auto alpha, auto count) { go(alpha, count, std::true_type{}); }, f.alpha, f.counting);
+        if constexpr (G >= 8) dispatch([&](auto alpha) { go(alpha, std::false_type{}, std::true_type{}); }, f.alpha);
+        else if constexpr ((G & 3) >= 2) dispatch([&](auto alpha, auto count) { go(alpha, count, std::true_type{}); }, f.alpha, f.counting);
         else dispatch(go, f.alpha, f.counting, c.prim);
         HIP_CHECK(hipGetLastError());
     };
     auto launch_shade = [&] {
-        switch (c.grid_mode == 0 ? 0 : c.grid_mode + (s.ortho_light_grids ? 4 : 0)) {
+        switch (c.grid_mode == 0 ? 0 : c.grid_mode + (s.ortho_light_grids ? 4 : 0) + ((c.grid_mode == 3 && c.cached) ? 8 : 0)) {
         case 0: launch(std::integral_constant<int, 0>{}); break;
         case 1: launch(std::integral_constant<int, 1>{}); break;
         case 2: launch(std::integral_constant<int, 2>{}); break;
         case 3: launch(std::integral_constant<int, 3>{}); break;
         case 5: launch(std::integral_constant<int, 5>{}); break;
         case 6: launch(std::integral_constant<int, 6>{}); break;
+        case 11: launch(std::integral_constant<int, 11>{}); break;
+        case 15: launch(std::integral_constant<int, 15>{}); break;
         default: launch(std::integral_constant<int, 7>{}); break;
         }
     };
@@ -2736,6 +2806,37 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
     W.walk_steps = f.env.walk ? f.env.walk : 20u;
     c.wctr = (WfCounters*)pipe.ctr.p;
     HIP_CHECK(hipMemsetAsync(c.wctr, 0, sizeof(WfCounters) * (f.p.bounces + 3), c.st_main));
+    if (fused_rng && wf.rng_cache) {
+        // The scene's word cache: a chunk below its high-water mark reads it, the chunk next above the mark - if the
+        // budget has room for it - is filled first, here on the frame's stream.  (Chunk boundaries differ between a first
+        // frame and a planned one: the prefix does not care.)
+        pt_scene::RngCache& rc = *wf.rng_cache;
+        const uint64_t g0 = (uint64_t)(P.sample_begin / f.batch) * wf.items_per_batch + base, g1 = g0 + W.n_items;
+        if (g1 <= rc.stride && g0 <= rc.mark) {
+            uint4* planes = (uint4*)rc.buf.p + g0;
+            if (g1 > rc.mark) {
+                const uint32_t first = (uint32_t)(rc.mark - g0), n = (uint32_t)(g1 - rc.mark);
+                tl.begin(0);
+                hipLaunchKernelGGL(k_wf_rng_fill, dim3((n + 255u) / 256u), dim3(256), 0, c.st_main, W, f.d_tiles, first, n, planes,
+                                   (uint32_t)rc.stride);
+                HIP_CHECK(hipGetLastError());
+                tl.end();
+                HIP_CHECK(hipEventRecord(rc.ev_fill, c.st_main));
+                rc.recorded = true;
+                rc.fill_stream = c.st_main;
+                rc.mark = g1;
+                ++rc.fills;
+            }
+            c.cached = true;
+            c.rng_planes = planes;
+            W.cap = (uint32_t)rc.stride;
+            W.rng_first_plane = 0u;
+        }
+    }
+    if (fused_rng && !c.cached && pipe.rng[0].bytes < (size_t)wf.cap * 16u) {   // (queue_buffers left the plane out)
+        s.pipe.rng[0].ensure((size_t)wf.cap * 16u);
+        c.rng_planes = (uint4*)pipe.rng[0].p;
+    }
     if (fused_rng) {
         // (no k_wf_rng launch)
     } else if (!rng_ahead || chunk_no == 0) {
@@ -2898,6 +2999,7 @@ void render_device(pt_scene& s, const pt_profile& p, const pt_opts* opts_in, voi
     if (f.wavefront) {
         const QueueEnv qe = queue_env();
         wf = frame_plan(s, f, qe);
+        rng_cache_frame(s, f, wf, stream);
         queue_buffers(s, f, qe, wf);
         stats_slots(s, f, wf);
         side_streams(s, f, wf);
@@ -3777,6 +3879,15 @@ int pt_get_cull_stats(const pt_scene* scene, uint32_t* n_blocks, uint32_t* n_emp
             for (uint32_t m : mask) *n_empty += m != 0u;
         }
     });
+}
+int pt_get_rng_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* fills) {
+    if (!scene || !bytes || !items || !items_cached || !fills) return PT_ERR_INVALID;
+    const pt_scene::RngCache& rc = scene->rng_cache;
+    *bytes = rc.buf.bytes;
+    *items = rc.items;
+    *items_cached = rc.mark;
+    *fills = rc.fills;
+    return PT_OK;
 }
 int pt_scene_get_info(const pt_scene* scene, pt_scene_info* out) {
     if (!scene || !out) return PT_ERR_INVALID;

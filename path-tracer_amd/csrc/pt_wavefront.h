@@ -71,7 +71,8 @@ struct WfParams {
     RenderParams P;
     uint32_t item_base;   // first absolute work item of this chunk
     uint32_t n_items;     // items in this chunk
-    uint32_t cap;         // work items per chunk: the stride of the RNG planes (and, when nothing smaller is known, of everything)
+    uint32_t cap;         // work items per chunk: the stride of the RNG planes (and, when nothing smaller is known, of everything);
+                          // a chunk that reads the scene's word cache: the cache's stride
     // capacities of what is indexed by a QUEUE position instead of a work item (the host sizes them by the records that can
     // exist - a frame's counts are known exactly once it has been rendered once, pt_gpu.hip FramePlan):
     uint32_t qcap_in;     //   the queue this bounce reads (ray plane, path plane at 2 x qcap_in, entry plane at 4 x qcap_in)
@@ -831,6 +832,21 @@ __global__ __launch_bounds__(256) void k_wf_rng(DevScene S, WfParams W, const ui
     primary_screen(S, it.x, it.y, W.P.width, W.P.height, wf_rng_float(w[0]), wf_rng_float(w[1]), sx, sy);
     rng_planes[rel] = make_uint4(__float_as_uint(sx), __float_as_uint(sy), w[2], w[3]);
     rng_planes[(size_t)W.cap + rel] = make_uint4(w[4], w[5], w[6], w[7]);
+}
+
+// The same block for the scene's word cache (pt_gpu.hip RngCache): items [first, first + n) of the chunk, the RAW words
+// 0-3 and 4-7 at planes[rel] and planes[stride + rel] (planes: the chunk's first item in the cache).  Items outside the
+// image get the words of whatever pixel index they decode to: nobody reads them.
+__global__ __launch_bounds__(256) void k_wf_rng_fill(WfParams W, const uint32_t* __restrict__ tile_offsets, uint32_t first, uint32_t n,
+                                                     uint4* __restrict__ planes, uint32_t stride) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= n) return;
+    const uint32_t rel = first + t;
+    ItemRef it = decode_item(W.P, tile_offsets, W.item_base + rel);
+    uint32_t w[16];
+    pt_chacha12_block((uint64_t)it.sample + (uint64_t)it.global_index * (uint64_t)W.P.samples, 0u, w);
+    planes[rel] = make_uint4(w[0], w[1], w[2], w[3]);
+    planes[(size_t)stride + rel] = make_uint4(w[4], w[5], w[6], w[7]);
 }
 
 // rng.gen::<f32>() number idx of the path that started as work item `item` of the chunk: words 0-7 come
@@ -1975,6 +1991,10 @@ PT_D bool wf_light_is_moot(const DevLight& L, f3 term, f3 surface_pos) {
 #ifndef WF_SHADE_GRID_WAVES_ALPHA
 #define WF_SHADE_GRID_WAVES_ALPHA WF_SHADE_GRID_WAVES   // (translucent scenes, 88 B of scratch at 3: 2 waves measured worse, item 17)
 #endif
+#ifndef WF_SHADE_CACHED_WAVES
+// ... for the opaque bounce-0 variant that READS its ChaCha words (CACHED below): no block, no `later_words` to hold
+#define WF_SHADE_CACHED_WAVES 3
+#endif
 // GRID (origin grids, pt_grid.h): 0 - none: direct light goes through the shadow queue and k_wf_shadow / k_og_shadow;
 // 1 - every light is a point light with a grid: get_light_info (mod.rs:281-333) is evaluated HERE, light after
 //     light, so a surface costs no shadow record, no contrib entries and no colour patch (190 B of queue traffic
@@ -1984,9 +2004,12 @@ PT_D bool wf_light_is_moot(const DevLight& L, f3 term, f3 surface_pos) {
 // 3 - (bounce 0) 2 + the item's ChaCha12 block is computed HERE instead of by k_wf_rng: the ~800 integer
 //     instructions per item run underneath the memory latency of the casts, and only the paths that go on write
 //     the words of bounces 1 and 2 (plane 1 of the RNG planes; a path has made at least four draws by then).
-// GRIDX = GRID + 4 * DIRL; DIRL: some light is directional (orthographic grid branch of og_light_radiance compiled in).
+// GRIDX = GRID + 4 * DIRL + 8 * CACHED; DIRL: some light is directional (orthographic grid branch of og_light_radiance
+// compiled in).  CACHED (GRID 3 only): words 0-7 of the item's block are READ from the scene's word cache (pt_gpu.hip
+// RngCache: rng_planes points at the chunk's first item there, W.cap is the cache's stride, W.rng_first_plane 0) - the raw
+// words, not the screen position: that depends on the camera, the words on the item enumeration alone.
 template <bool ALPHA, bool COUNT, bool PRIMARY, int GRIDX>
-__global__ __launch_bounds__(WF_SHADE_THREADS, GRIDX ? (ALPHA ? WF_SHADE_GRID_WAVES_ALPHA : WF_SHADE_GRID_WAVES) : WF_SHADE_WAVES) void k_wf_shade(DevScene S, WfParams W,
+__global__ __launch_bounds__(WF_SHADE_THREADS, GRIDX ? (ALPHA ? WF_SHADE_GRID_WAVES_ALPHA : GRIDX >= 8 ? WF_SHADE_CACHED_WAVES : WF_SHADE_GRID_WAVES) : WF_SHADE_WAVES) void k_wf_shade(DevScene S, WfParams W,
                                                   const uint32_t* __restrict__ tile_offsets,
                                                   const float4* __restrict__ queue_in, const uint4* __restrict__ hits,
                                                   const uint4* rng_planes,
@@ -2007,8 +2030,10 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, GRIDX ? (ALPHA ? WF_SHADE_GRID_WA
     // wavefront walker will not take (slack_is_capped) is listed here, where the ray is made, so that k_wf_trace_exact can
     // walk it while k_wf_trace is busy with the rest of the queue.
     constexpr int GRID = GRIDX & 3;
-    constexpr bool DIRL = GRIDX >= 4;
+    constexpr bool DIRL = (GRIDX & 4) != 0;
+    constexpr bool CACHED = GRIDX >= 8;
     static_assert(GRIDX != 4, "DIRL needs a grid mode");
+    static_assert(!CACHED || (GRID == 3 && !COUNT), "the word cache serves the fused bounce-0 kernel");
     uint4* rng_planes_out = const_cast<uint4*>(rng_planes);   // GRID == 3 writes plane 1 (nobody reads it before bounce 1)
     static_assert(GRID < 2 || PRIMARY, "the camera grid serves bounce 0");
     const bool list_pass = !PRIMARY && index_list != nullptr;
@@ -2051,7 +2076,7 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, GRIDX ? (ALPHA ? WF_SHADE_GRID_WA
     // rng.gen::<f32>() number idx (>= 2) of the path at bounce 0, GRID == 3: from the block in registers; beyond
     // word 7 (more than three alpha draws) the block is derived again by wf_rng_draw
     auto draw_b0 = [&](uint32_t idx) -> float {
-        if (idx >= WF_RNG_STAGED) return wf_rng_draw(rng, W, tile_offsets, rng_planes, item, idx);
+        if (idx >= (CACHED ? 4u : WF_RNG_STAGED)) return wf_rng_draw(rng, W, tile_offsets, rng_planes, item, idx);   // (CACHED: plane 1 of the cache)
         uint32_t word = word2;
         word = idx == 3u ? word3 : word;
         word = idx == 4u ? later_words.x : word;
@@ -2069,7 +2094,14 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, GRIDX ? (ALPHA ? WF_SHADE_GRID_WA
             color = mk3(0.f, 0.f, 0.f);
             out_slot = (it.sample - 1u - W.P.sample_begin) * W.P.n_local + it.out_index;
             if (GRID >= 2) {   // ray_cast + alpha walk of the camera ray (mod.rs:182-205) through the camera grid
-                if (GRID == 3) {   // StdRng::seed_from_u64(sample + i * samples), jitter x then y (mod.rs:110-120)
+                if (GRID == 3 && CACHED) {   // the same words, made once per item enumeration: one dense 16-byte load
+                    const uint4 w03 = rng_planes[i];
+                    float sx, sy;
+                    primary_screen(S, it.x, it.y, W.P.width, W.P.height, wf_rng_float(w03.x), wf_rng_float(w03.y), sx, sy);
+                    primary_from_screen(S, sx, sy, o, d);
+                    word2 = w03.z;
+                    word3 = w03.w;
+                } else if (GRID == 3) {   // StdRng::seed_from_u64(sample + i * samples), jitter x then y (mod.rs:110-120)
                     uint32_t w[16];
                     pt_chacha12_block((uint64_t)it.sample + (uint64_t)it.global_index * (uint64_t)W.P.samples, 0u, w);
                     float sx, sy;
@@ -2280,7 +2312,7 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, GRIDX ? (ALPHA ? WF_SHADE_GRID_WA
         survive = false;
         to_shadow = false;
     }
-    if (GRID == 3 && survive) rng_planes_out[(size_t)(1u - W.rng_first_plane) * W.cap + item] = later_words;   // draws 4-7 of the path
+    if (GRID == 3 && !CACHED && survive) rng_planes_out[(size_t)(1u - W.rng_first_plane) * W.cap + item] = later_words;   // draws 4-7 of the path
     if (W.exact_shade_lists) {   // (wave-uniform; 0.24 % of random directions)
         const bool listed = survive && slack_is_capped(__builtin_amdgcn_rcpf(next_d.x), __builtin_amdgcn_rcpf(next_d.y), __builtin_amdgcn_rcpf(next_d.z));
         if (wf_any(listed)) {

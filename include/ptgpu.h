@@ -493,6 +493,10 @@ int pt_get_cull_stats(const pt_scene* scene, uint32_t* n_blocks, uint32_t* n_emp
  * was made.  PT_RNG_CACHE=0 switches the cache off, PT_RNG_CACHE_GIB (16) is its budget; both are read per frame.  The
  * bytes are not part of pt_scene_info's queue_bytes or device_bytes. */
 int pt_get_rng_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* fills);
+/* Workgroups of the fused bounce-0 kernel of opaque scenes that the runtime places on one compute unit of `device`
+ * (hipOccupancyMaxActiveBlocksPerMultiprocessor at the kernel's workgroup size): which = 0 the variant that computes
+ * its ChaCha words, 1 the variant that reads them from the word cache.  One workgroup is one wave per SIMD. */
+int pt_kernel_occupancy(int device, int which, int* blocks_per_cu);
 
 /* Scene statistics after the KD build. */
 typedef struct pt_scene_info {

@@ -3889,6 +3889,16 @@ int pt_get_rng_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* ite
     *fills = rc.fills;
     return PT_OK;
 }
+int pt_kernel_occupancy(int device, int which, int* blocks_per_cu) {
+    return guarded([&] {
+        if (!blocks_per_cu || which < 0 || which > 1) fail(PT_ERR_INVALID, "pt_kernel_occupancy: bad argument");
+        HIP_CHECK(hipSetDevice(device));
+        if (which == 0)
+            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_wf_shade<false, false, true, 3>, WF_SHADE_THREADS, 0));
+        else
+            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_wf_shade<false, false, true, 11>, WF_SHADE_THREADS, 0));
+    });
+}
 int pt_scene_get_info(const pt_scene* scene, pt_scene_info* out) {
     if (!scene || !out) return PT_ERR_INVALID;
     *out = scene->info;

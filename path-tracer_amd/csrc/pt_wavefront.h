@@ -27,6 +27,8 @@
 #include "pt_grid.h"
 #include "pt_escape.h"
 
+#include <type_traits>
+
 // Work item -> pixel / sample (see the item numbering in pt_gpu.hip).
 struct ItemRef {
     uint32_t x, y, global_index, out_index, sample;  // sample is 1-based (mod.rs:105)
@@ -1992,9 +1994,33 @@ PT_D bool wf_light_is_moot(const DevLight& L, f3 term, f3 surface_pos) {
 #define WF_SHADE_GRID_WAVES_ALPHA WF_SHADE_GRID_WAVES   // (translucent scenes, 88 B of scratch at 3: 2 waves measured worse, item 17)
 #endif
 #ifndef WF_SHADE_CACHED_WAVES
-// ... for the opaque bounce-0 variant that READS its ChaCha words (CACHED below): no block, no `later_words` to hold
-#define WF_SHADE_CACHED_WAVES 3
+// ... for the opaque bounce-0 variant that READS its ChaCha words (CACHED below): no block, no `later_words` to hold.
+// 4: 128 registers and 8 B of scratch with the state that is cold across the shadow casts parked in LDS (WF_SHADE_PARK)
+// and the arguments read through an opaque pointer (wf_opaque_arg); by launch bounds alone it was 180 B of scratch.
+#define WF_SHADE_CACHED_WAVES 4
 #endif
+#ifndef WF_SHADE_PARK
+#define WF_SHADE_PARK (WF_SHADE_CACHED_WAVES >= 4)
+#endif
+// A by-value kernel argument, read through the kernarg segment pointer (explicit arguments lie there in order, each at its
+// alignment) after an empty asm has made that pointer opaque: loads through it cannot leave the loop the asm stands in.
+template <class T>
+PT_D const T& wf_opaque_arg(uint32_t offset) {
+    const __attribute__((address_space(4))) char* p = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *(const T*)(p + offset);
+}
+// (k_wf_shade checks at compile time that these two ARE its first two parameters)
+template <class F> struct wf_leading_args;
+template <class R, class A, class B, class... Rest> struct wf_leading_args<R (*)(A, B, Rest...)> {
+    static constexpr bool scene_then_params = std::is_same<A, DevScene>::value && std::is_same<B, WfParams>::value;
+};
+constexpr uint32_t WF_ARG_OFFSET_W = (uint32_t)((sizeof(DevScene) + alignof(WfParams) - 1u) / alignof(WfParams) * alignof(WfParams));   // k_wf_shade(DevScene, WfParams, ...)
+// LDS parking slots of that variant at four waves (one dword per thread each; the kernel's sh_park).  Four workgroups must
+// fit a CU's 160 KiB beside the compaction's 296 B each: 39 slots (39 KiB) at the most, forty would not.
+enum : uint32_t { PK_BRDF = 0, PK_NORMAL = 11, PK_VIEW = 14, PK_UV = 17, PK_PID = 19, PK_OUT_SLOT = 20, PK_WORD2 = 21, PK_C = 23,
+                  PK_COLOR = 26, PK_TERM0 = 29, WF_PARK_SLOTS = 32 };
+static_assert(WF_PARK_SLOTS <= 39, "four workgroups of the bounce-0 kernel must fit a CU's LDS");
 // GRID (origin grids, pt_grid.h): 0 - none: direct light goes through the shadow queue and k_wf_shadow / k_og_shadow;
 // 1 - every light is a point light with a grid: get_light_info (mod.rs:281-333) is evaluated HERE, light after
 //     light, so a surface costs no shadow record, no contrib entries and no colour patch (190 B of queue traffic
@@ -2008,6 +2034,7 @@ PT_D bool wf_light_is_moot(const DevLight& L, f3 term, f3 surface_pos) {
 // compiled in).  CACHED (GRID 3 only): words 0-7 of the item's block are READ from the scene's word cache (pt_gpu.hip
 // RngCache: rng_planes points at the chunk's first item there, W.cap is the cache's stride, W.rng_first_plane 0) - the raw
 // words, not the screen position: that depends on the camera, the words on the item enumeration alone.
+// (S and W FIRST, in this order: the PARK variants read them again through the kernarg segment, wf_opaque_arg)
 template <bool ALPHA, bool COUNT, bool PRIMARY, int GRIDX>
 __global__ __launch_bounds__(WF_SHADE_THREADS, GRIDX ? (ALPHA ? WF_SHADE_GRID_WAVES_ALPHA : GRIDX >= 8 ? WF_SHADE_CACHED_WAVES : WF_SHADE_GRID_WAVES) : WF_SHADE_WAVES) void k_wf_shade(DevScene S, WfParams W,
                                                   const uint32_t* __restrict__ tile_offsets,
@@ -2058,12 +2085,36 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, GRIDX ? (ALPHA ? WF_SHADE_GRID_WA
     __shared__ uint32_t sh_base[2];
     __shared__ uint32_t sh_oct[8][WF_SHADE_THREADS / 64], sh_oct_off[8][WF_SHADE_THREADS / 64];
     const uint32_t wave = threadIdx.x >> 6;
+    // LDS parking (PARK: the cached opaque bounce-0 variant at four waves per SIMD): per-lane state that is cold across an
+    // inline shadow cast waits in LDS, slot-major (sh_park[slot][thread]: conflict-free dwords, every slot private to its
+    // thread - no barrier).  The accesses are volatile: a plain store would be forwarded to its load and the register kept.
+    constexpr bool PARK = CACHED && !ALPHA && WF_SHADE_PARK;
+    // wf_opaque_arg reads S at offset 0 of the kernarg segment and W right behind it: they must stay this kernel's first two
+    // parameters, in this order (anything may follow them)
+    static_assert(wf_leading_args<decltype(&k_wf_shade<ALPHA, COUNT, PRIMARY, GRIDX>)>::scene_then_params,
+                  "wf_opaque_arg: DevScene and WfParams must be the first two parameters of k_wf_shade");
+    __shared__ uint32_t sh_park[PARK ? WF_PARK_SLOTS : 1][WF_SHADE_THREADS];
+    // (an LDS pointer by type: a volatile access through a generic pointer stays a flat access, one 64-bit address per slot)
+    volatile __attribute__((address_space(3))) uint32_t* const park = (volatile __attribute__((address_space(3))) uint32_t*)&sh_park[0][threadIdx.x];
+    auto park_u = [&](uint32_t slot, uint32_t v) { park[slot * WF_SHADE_THREADS] = v; };
+    auto park_f = [&](uint32_t slot, float v) { park[slot * WF_SHADE_THREADS] = __float_as_uint(v); };
+    auto park_3 = [&](uint32_t slot, f3 v) { park_f(slot, v.x), park_f(slot + 1u, v.y), park_f(slot + 2u, v.z); };
+    auto unpark_u = [&](uint32_t slot) -> uint32_t { return park[slot * WF_SHADE_THREADS]; };
+    auto unpark_f = [&](uint32_t slot) -> float { return __uint_as_float(park[slot * WF_SHADE_THREADS]); };
+    auto unpark_3 = [&](uint32_t slot) -> f3 { const float x = unpark_f(slot), y = unpark_f(slot + 1u); return mk3(x, y, unpark_f(slot + 2u)); };
     // (Bounce 0 needs no hit aggregation like the later bounces' below: a wavefront is one 8x8 pixel block of one sample,
     // so its camera rays hit or miss together - collecting the hits of 256 items in LDS and shading them 256 at a time left
     // the instruction count and the 52 active lanes per instruction unchanged, profiles/r02_experiments.txt item 13.)
     // One workgroup-wide step: thread t shades queue entry i (live = it has one).  Every thread of the workgroup
     // calls this together: the compaction at the end has barriers.
+    // (PARK) The arguments again, read through a kernarg pointer made opaque inside the grid-stride loop: what is derived from
+    // them (float copies of scalars, item-decoding terms, addresses) can then not be hoisted out of that loop into vector
+    // registers that stay occupied - and spilled - through every cast; the fields are fetched by scalar loads where they are used.
+    auto scene_arg = [&]() -> const DevScene& { return PARK ? wf_opaque_arg<DevScene>(0u) : S; };
+    auto params_arg = [&]() -> const WfParams& { return PARK ? wf_opaque_arg<WfParams>(WF_ARG_OFFSET_W) : W; };
     auto shade_one = [&](const uint32_t e, bool live) {   // e: position in the queue / in the lists
+    const DevScene& S = scene_arg();
+    const WfParams& W = params_arg();
     const uint32_t i = (list_pass && live) ? entry_index(e) : e;
     f3 o = mk3(0, 0, 0), d = mk3(0, 0, 1), thr = mk3(0, 0, 0), color = mk3(0, 0, 0);
     uint32_t item = i, draw = 0, out_slot = 0;
@@ -2198,6 +2249,22 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, GRIDX ? (ALPHA ? WF_SHADE_GRID_WA
         // visibility factor is applied by the shadow kernel: the first light's term stays in registers, the others
         // are recomputed when the record is written.
         const bool inline_lights = GRID != 0 && dot3(surf.normal, surf.normal) <= S.light_grid_max_normal2;
+        // (PARK) what no cast changes is parked once, what a light changes right before its cast; all of it comes back after
+        auto park_fixed = [&] {
+            park_f(PK_BRDF, brdf.metalness), park_f(PK_BRDF + 1u, brdf.roughness);
+            park_3(PK_BRDF + 2u, brdf.albedo), park_3(PK_BRDF + 5u, brdf.emissive), park_3(PK_BRDF + 8u, brdf.f0);
+            park_3(PK_NORMAL, normal), park_3(PK_VIEW, view);
+            park_f(PK_UV, surf.uv.x), park_f(PK_UV + 1u, surf.uv.y);
+            park_u(PK_PID, h.pid), park_u(PK_OUT_SLOT, out_slot), park_u(PK_WORD2, word2), park_u(PK_WORD2 + 1u, word3);
+        };
+        auto unpark_fixed = [&] {
+            brdf.metalness = unpark_f(PK_BRDF), brdf.roughness = unpark_f(PK_BRDF + 1u);
+            brdf.albedo = unpark_3(PK_BRDF + 2u), brdf.emissive = unpark_3(PK_BRDF + 5u), brdf.f0 = unpark_3(PK_BRDF + 8u);
+            normal = unpark_3(PK_NORMAL), view = unpark_3(PK_VIEW);
+            surf.uv.x = unpark_f(PK_UV), surf.uv.y = unpark_f(PK_UV + 1u);
+            h.pid = unpark_u(PK_PID), out_slot = unpark_u(PK_OUT_SLOT), word2 = unpark_u(PK_WORD2), word3 = unpark_u(PK_WORD2 + 1u);
+        };
+        if (PARK) park_fixed();
         for (uint32_t li = 0; li < S.n_lights; ++li) {
             const DevLight& L = S.lights[li];
             f3 ldir = L.kind == PT_LIGHT_POINT ? normalize3(surf.pos - ld3(L.vec)) : ld3(L.vec);
@@ -2208,7 +2275,12 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, GRIDX ? (ALPHA ? WF_SHADE_GRID_WA
                 if (moot) {
                     if (COUNT) n_moot++;
                 } else {
+                    if (PARK) park_3(PK_C, c), park_3(PK_COLOR, color), park_3(PK_TERM0, term0);
                     const f3 rad = og_light_radiance<ALPHA, COUNT, DIRL>(S, li, surf.pos, surf.normal, surf.uv, surf.sphere, lc);
+                    if (PARK) {
+                        c = unpark_3(PK_C), color = unpark_3(PK_COLOR), term0 = unpark_3(PK_TERM0);
+                        unpark_fixed();
+                    }
                     if (!(rad.x == 0.f && rad.y == 0.f && rad.z == 0.f)) color = color + mul_ew(c, rad);
                 }
             } else if (!moot) {
@@ -2341,6 +2413,11 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, GRIDX ? (ALPHA ? WF_SHADE_GRID_WA
         sq[3] = make_float4(__uint_as_float(out_slot), __uint_as_float(surf.sphere ? WF_FLAG_SPHERE : 0u), 0.f, 0.f);
         contrib[sh_idx] = make_float4(term0.x, term0.y, term0.z, 0.f);
         for (uint32_t li = 1; li < S.n_lights; ++li) {
+            // (PARK: one light per trip - two at a time in packed f32 made this rarely taken loop the kernel's register peak.
+            // An empty asm, not `#pragma clang loop vectorize(disable)`: a pragma cannot depend on PARK, and on the one loop
+            // all variants share it changes the code of every other variant; tests/test_bounce0_four_waves.py holds the
+            // register count should a compiler stop honouring it.)
+            if (PARK) asm volatile("");
             const DevLight& L = S.lights[li];
             f3 ldir = L.kind == PT_LIGHT_POINT ? normalize3(surf.pos - ld3(L.vec)) : ld3(L.vec);
             f3 c = mul_ew(thr, ct_eval_direct(brdf, normal, view, -1.f * ldir));

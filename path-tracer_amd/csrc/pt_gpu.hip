@@ -509,27 +509,42 @@ struct CamGridSource {
     uint64_t n_texel_bytes = 0;
 };
 
+// One origin grid of a scene: what the kernels read of it, its header (enabled = 0: no grid) and the bytes of its two arrays.
+struct GridSlot {
+    DevGrid dev{};
+    pth_origin_grid hdr{};
+    uint64_t bytes = 0;
+};
+
+// The origin grids of a scene, said once.  grids_on_device makes one (PT_OG_HOST=1: upload_host_grids, from the prep's), an
+// edit makes the part it replaces, and install_camera_grid / install_light_grids hand it to the scene - with what DevScene
+// restates of it.  What pt_scene_get_info reports of the grids is read from here when it is asked for (grid_facts).
+struct SceneGrids {
+    GridSlot cam;
+    std::vector<GridSlot> lights;   // one per light of the scene
+    bool all_lights = false;        // every light has a grid: the shadow rays take them (no lights at all: vacuously)
+    bool ortho = false;             // some light grid is orthographic (a directional light): kernel variants DIRL
+    bool headers = false;           // built on the device: pt_scene_grid_header / _copy show them (host-built grids: all zero)
+    float seconds = 0.f;            // what building them on the device took
+    void lights_done(bool all) {    // the light slots stand, all of them, or none does (emptied)
+        if (!all) lights.assign(lights.size(), GridSlot{});
+        all_lights = all;
+        ortho = std::any_of(lights.begin(), lights.end(), [](const GridSlot& g) { return g.dev.kind != 0; });
+    }
+    const GridSlot* slot(uint32_t which) const {   // 0: the camera's, 1 + i: light i's; nullptr: no such light
+        return which == 0 ? &cam : which - 1 < lights.size() ? &lights[which - 1] : nullptr;
+    }
+};
+
 struct pt_scene {
     int device = 0;
     DevScene dev{};
     std::vector<void*> allocations;
-    pt_scene_info info{};
-    bool ortho_light_grids = false;   // some light grid is orthographic (a directional light): kernel variants DIRL
+    pt_scene_info info{};   // (device_bytes: every allocation but the grids' arrays; the grids' rows: grid_facts)
+    SceneGrids grids;
     std::vector<uint32_t> host_prim_entry;
-    std::vector<pth_origin_grid> grid_headers;   // device-built grids: [0] camera, [1 + i] light i (enabled = 0: none)
     std::shared_ptr<const CamGridSource> cam_src;   // (pt_scene_set_camera, _set_lights, _set_materials)
     uint32_t cam_res = 0;                             // the camera grid's resolution rule for the scene's light count (grid_rule)
-    uint64_t cam_grid_bytes = 0, cam_grid_refs = 0;   // device bytes / list entries of the camera grid
-    uint64_t light_grid_bytes = 0, light_grid_refs = 0;   // device bytes / list entries of the light grids
-    std::vector<DevGrid> host_light_grids;
-    struct BuiltGrids {   // what grids_on_device() produced for this scene (possibly while the KD-tree was still being built)
-        bool done = false, all_lights = false, ortho = false;
-        DevGrid cam{};
-        std::vector<DevGrid> lights;
-        uint32_t cam_res = 0, light_grids = 0;
-        uint64_t refs = 0, bytes = 0;
-        float seconds = 0.f;
-    } built;
     pt_timing timing{};
     pt_counters counters{};
     DeviceBuffer accum_scratch, counter_buf, staging_buf;
@@ -679,16 +694,23 @@ struct pt_prep {
         pth_origin_grid hdr{};
         bool valid = false;
     };
-    bool device_grids = false;
     GridJob cam_job;
     std::vector<GridJob> light_jobs;
-    std::shared_ptr<CamGridSource> src = std::make_shared<CamGridSource>();   // og_geom, og_words (+ what a camera change needs)
-    double og_budget = 0;
+    std::shared_ptr<CamGridSource> src = std::make_shared<CamGridSource>();   // og_geom, og_words (+ what an edit needs)
 };
 
 namespace {
 
-void grids_on_device(const pt_prep& P, pt_scene& s);
+// pt_scene_create makes its prep for exactly one scene: the prep's grid thread then builds that scene's grids on the device
+// WHILE the KD-tree is being built on the host, and scene_upload finds them here.
+struct EarlyGrids {
+    pt_scene& scene;
+    int device;
+    SceneGrids grids;
+    bool built = false;
+};
+
+SceneGrids grids_on_device(const pt_prep& P, pt_scene& s);
 
 // A light as the device reads it (tame: every colour component finite and below 1e30).
 DevLight dev_light(const pt_light& l) {
@@ -700,6 +722,16 @@ DevLight dev_light(const pt_light& l) {
     for (int k = 0; k < 3; ++k)
         if (!(fabsf(l.color[k]) < 1e30f)) o.tame = 0u;  // also catches NaN
     return o;
+}
+
+// A camera as the device reads it: the columns of its transform, Rad::tan(fov / 2.) (mod.rs:116,120) with the host libm.
+void dev_camera(const pt_camera& cam, DevScene& D) {
+    const float* M = cam.transform;
+    memcpy(D.cam_c0, M, 12);
+    memcpy(D.cam_c1, M + 4, 12);
+    memcpy(D.cam_c2, M + 8, 12);
+    memcpy(D.cam_c3, M + 12, 12);
+    D.tan_half_fov = tanf(cam.fov / 2.f);
 }
 
 // Byte budget over ALL grids of the scene (PT_OG_BUDGET_GIB, default 48 of the 288 GB): the grids are an optional
@@ -738,18 +770,77 @@ GridRule grid_rule(uint64_t n_prims, uint32_t n_lights, double budget, bool grid
     return R;
 }
 
-// `early` / `early_device`: the scene this prep is made for, when there is exactly one (pt_scene_create): its origin grids
-// are then built on the device by the grid thread WHILE the KD-tree is being built on the host.
-void prep_create(const pt_scene_desc& d, pt_prep& P, pt_scene* early = nullptr, int early_device = -1) {
-    const bool dbg_setup = getenv("PT_DEBUG_SETUP") != nullptr;
-    auto t_sec = std::chrono::steady_clock::now();
-    auto section = [&](const char* name) {
-        if (!dbg_setup) return;
-        auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[prep] %-28s %.3f s\n", name, std::chrono::duration<double>(now - t_sec).count());
-        t_sec = now;
-    };
-    // ---- validate
+// ---- the grid of the camera and of a light, each said once.  `ext` is where the scene's extent about the grid comes from,
+// and with it what becomes of the parameters: the description, scanned on the host (DescJobs: the jobs of a fresh scene's
+// device build; HostBuilt: the host builder, PT_OG_HOST=1), or the footprints, reduced on the device (EditFootprints: the
+// edits).  The numbers are the same; a path's source decides what its setup time overlaps with.
+
+// A point light's shadow ray starts n * 1e-5 off the line through the light (mod.rs:319): the grids' margin covers
+// |n| <= max_normal, longer normals take the KD-tree per surface (DevScene.light_grid_max_normal2).
+constexpr float max_normal = 1.5f;
+
+// A cube map around a point light; an orthographic grid along a directional light's shadow rays, which run along
+// -direction (mod.rs:291), as it is.
+template <class Ext>
+auto light_grid(uint32_t kind, const float vec[3], uint32_t light_res, Ext&& ext) {
+    if (kind == PT_LIGHT_POINT) return ext.point(vec, light_res, 1.05e-5f * max_normal, 1.001f);
+    const float sd[3] = {-1.f * vec[0], -1.f * vec[1], -1.f * vec[2]};
+    return ext.ortho(sd, light_res);
+}
+
+// A cube map around the camera of transform M, for directions as long as a camera ray's can be: |M dir| <= ||M||_F for the
+// unit vector dir (mod.rs:122-123).  A norm that is not in (0, 64): no grid (what `ext` gives by default).
+template <class Ext>
+auto camera_grid(const float* M, uint32_t res, Ext&& ext) -> decltype(ext.point(M, res, 0.f, 0.f)) {
+    double fro = 0;
+    for (int k = 0; k < 3; ++k)
+        for (int r = 0; r < 3; ++r) fro += (double)M[4 * k + r] * M[4 * k + r];
+    fro = std::sqrt(fro);
+    if (!(fro > 0 && fro < 64.0)) return {};
+    return ext.point(M + 12, res, 0.f, (float)(fro * 1.001));
+}
+
+struct DescJobs {
+    const pt_scene_desc& d;
+    pt_prep::GridJob point(const float o[3], uint32_t res, float ray_offset, float max_dir_len) const {
+        pt_prep::GridJob job;
+        job.valid = pth::og_params_point(d, o, res, ray_offset, max_dir_len, job.params, job.hdr);
+        return job;
+    }
+    pt_prep::GridJob ortho(const float sd[3], uint32_t res) const {
+        pt_prep::GridJob job;
+        job.valid = pth::og_params_ortho(d, sd, res, job.params, job.hdr);
+        return job;
+    }
+};
+
+struct HostBuilt {
+    const pt_scene_desc& d;
+    std::string what;   // (of the error message)
+    void check(int rc) const {
+        if (rc != PT_OK) fail(PT_ERR_INVALID, "origin grid (%s): %s", what.c_str(), pth_last_error());
+    }
+    std::unique_ptr<pt_prep::Grid> point(const float o[3], uint32_t res, float ray_offset, float max_dir_len) const {
+        auto g = std::make_unique<pt_prep::Grid>();
+        check(pth_origin_grid_build(&d, o, res, ray_offset, max_dir_len, &g->g));
+        return g;
+    }
+    std::unique_ptr<pt_prep::Grid> ortho(const float sd[3], uint32_t res) const {
+        auto g = std::make_unique<pt_prep::Grid>();
+        check(pth_ortho_grid_build(&d, sd, res, &g->g));
+        return g;
+    }
+};
+
+struct Join {   // (an exception on the way out must not leave the thread behind)
+    std::future<void>& f;
+    ~Join() { if (f.valid()) f.wait(); }
+};
+
+// ---- prep_create, stage by stage
+
+// validation, and what pt_scene_set_materials checks a new table against and resolves it through
+void prep_tables(const pt_scene_desc& d, pt_prep& P) {
     for (uint32_t m = 0; m < d.n_models; ++m) {
         const pt_model& mo = d.models[m];
         if (mo.material < 0 || (uint32_t)mo.material >= d.n_materials) fail(PT_ERR_INVALID, "model %u: bad material index", m);
@@ -758,15 +849,16 @@ void prep_create(const pt_scene_desc& d, pt_prep& P, pt_scene* early = nullptr, 
         if (mo.kind != PT_MODEL_MESH && mo.kind != PT_MODEL_SPHERE) fail(PT_ERR_INVALID, "model %u: bad kind", m);
     }
     pth::check_materials(d.materials, d.n_materials, d.textures, d.n_textures, d.n_texel_bytes);
-    // (what pt_scene_set_materials checks a new table against and resolves it through)
     P.src->model_material.resize(d.n_models);
     for (uint32_t m = 0; m < d.n_models; ++m) P.src->model_material[m] = d.models[m].material;
     P.src->n_materials = d.n_materials;
     P.src->textures.assign(d.textures, d.textures + d.n_textures);
     P.src->n_texel_bytes = d.n_texel_bytes;
+}
 
-    // ---- per-primitive arrays
-    uint64_t n_prims = pth_prim_count(&d);
+// The per-primitive arrays (attributes, positions, the grids' footprints) and the per-model materials; true: some material
+// is translucent.
+bool prep_primitives(const pt_scene_desc& d, uint64_t n_prims, pt_prep& P) {
     std::vector<float4>&attr = P.attr, &pos = P.pos;
     attr.resize(n_prims * 4);
     pos.resize(n_prims * 3);
@@ -820,183 +912,131 @@ void prep_create(const pt_scene_desc& d, pt_prep& P, pt_scene* early = nullptr, 
             ++prim;
         }
     }
-    // ---- the triangles no model owns (pt_scene_set_camera: the extent of a camera grid includes them, as og_params_point's does)
-    {
-        std::vector<uint8_t> owned(d.n_triangles, 0);
-        for (uint32_t m = 0; m < d.n_models; ++m)
-            if (d.models[m].kind == PT_MODEL_MESH)
-                std::fill(owned.begin() + d.models[m].tri_first, owned.begin() + d.models[m].tri_first + d.models[m].tri_count, (uint8_t)1);
-        for (uint64_t t = 0; t < d.n_triangles; ++t)
-            if (!owned[t])
-                for (int k = 0; k < 3; ++k)
-                    for (int a = 0; a < 3; ++a) P.src->unowned.push_back(d.triangles[t * 24 + k * 8 + a]);
-    }
-    // ---- kdtree-ray's slab test (scene_slab, pt_integrator.h): the exact bounding box of the scene - the union of
-    // Model::bound() (model.rs:76-86: the positions' bounds for a mesh, centre -+ radius for a sphere).  A cast whose origin
-    // is not strictly inside it runs the test once, at its end (hit_passes_slab).
-    {
-        DevScene& D = P.dev;
-        for (int a = 0; a < 3; ++a) {
-            D.slab_min[a] = INFINITY;
-            D.slab_max[a] = -INFINITY;
-        }
-        for (uint32_t m = 0; m < d.n_models; ++m) {
-            const pt_model& mo = d.models[m];
-            const uint32_t cnt = mo.kind == PT_MODEL_MESH ? mo.tri_count : 1u;
-            for (uint32_t t = 0; t < cnt; ++t) {
-                for (int a = 0; a < 3; ++a) {
-                    float lo, hi;
-                    if (mo.kind == PT_MODEL_MESH) {
-                        const float* v = d.triangles + (size_t)(mo.tri_first + t) * 24;
-                        lo = fminf(fminf(v[a], v[8 + a]), v[16 + a]);
-                        hi = fmaxf(fmaxf(v[a], v[8 + a]), v[16 + a]);
-                    } else {
-                        lo = mo.center[a] - mo.radius;
-                        hi = mo.center[a] + mo.radius;
-                    }
-                    D.slab_min[a] = fminf(D.slab_min[a], lo);
-                    D.slab_max[a] = fmaxf(D.slab_max[a], hi);
-                }
-            }
-        }
-        if (n_prims >= (1ull << 28)) fail(PT_ERR_UNSUPPORTED, "more than 2^28 primitives");   // (pack_hit's index bits)
-    }
-    section("primitive arrays, scene box");
-    const uint64_t n_prims_early = pth_prim_count(&d);
-    // ---- origin grids (host/origin_grid.cpp, csrc/pt_grid.h): camera rays, shadow rays of point lights.  They depend on the
-    // scene description only, not on the KD-tree: built on a thread of their own BESIDE the KD build (both are seconds of
-    // multi-threaded host work; setup of config 3: 3.2 -> 2.3 s).
-    auto build_grids = [&P, &d, n_prims_early, early, early_device]() {
-        const uint64_t n_prims = n_prims_early;
-        const float* M = d.camera.transform;
-        DevScene& D = P.dev;
+    return translucent;
+}
 
-        auto t_grid = std::chrono::steady_clock::now();
-        static const bool grids_on = [] {
-            const char* e = getenv("PT_OG");
-            return !(e && *e && atoi(e) == 0);
-        }();
-        // longest camera-ray direction: |M dir| <= ||M||_F for the unit vector dir (mod.rs:122-123)
-        double fro = 0;
-        for (int k = 0; k < 3; ++k)
-            for (int r = 0; r < 3; ++r) fro += (double)M[4 * k + r] * M[4 * k + r];
-        fro = std::sqrt(fro);
-        // the byte budget over all grids of the scene and the resolutions it leaves (grid_rule)
-        static const double budget = [] {
-            const char* e = getenv("PT_OG_BUDGET_GIB");
-            const double g = e && *e ? atof(e) : 48.0;
-            return (g > 0 ? g : 48.0) * 1073741824.0;
-        }();
-        auto estimate = grid_estimate;
-        const GridRule rule = grid_rule(n_prims, d.n_lights, budget, grids_on);
-        const uint32_t res = rule.res, light_res = rule.light_res;
-        const bool lights_fit = rule.lights_fit;
-        double grid_bytes = 0;
-        static const bool host_grids = [] {
-            const char* e = getenv("PT_OG_HOST");
-            return e && *e && atoi(e) != 0;
-        }();
-        P.src->cam_res = rule.cam_res;
-        P.src->grids_on = grids_on;
-        P.src->budget = budget;
-        P.src->device_grids = !host_grids;
-        if (!host_grids) {   // the device builds them at upload time: only the parameters are derived here
-            P.device_grids = true;
-            P.og_budget = budget;
-            const float max_normal = 1.5f;
-            if (grids_on && n_prims > 0 && fro > 0 && fro < 64.0 && estimate(res) <= budget)
-                P.cam_job.valid = pth::og_params_point(d, M + 12, res, 0.f, (float)(fro * 1.001), P.cam_job.params, P.cam_job.hdr);
-            bool all = grids_on && n_prims > 0 && lights_fit;
-            for (uint32_t i = 0; i < d.n_lights && all; ++i) {
-                pt_prep::GridJob job;
-                if (d.lights[i].kind == PT_LIGHT_POINT) {
-                    job.valid = pth::og_params_point(d, d.lights[i].vec, light_res, 1.05e-5f * max_normal, 1.001f, job.params, job.hdr);
+// The triangles no model owns (pt_scene_set_camera: the extent of a camera grid includes them, as og_params_point's does).
+void prep_unowned(const pt_scene_desc& d, pt_prep& P) {
+    std::vector<uint8_t> owned(d.n_triangles, 0);
+    for (uint32_t m = 0; m < d.n_models; ++m)
+        if (d.models[m].kind == PT_MODEL_MESH)
+            std::fill(owned.begin() + d.models[m].tri_first, owned.begin() + d.models[m].tri_first + d.models[m].tri_count, (uint8_t)1);
+    for (uint64_t t = 0; t < d.n_triangles; ++t)
+        if (!owned[t])
+            for (int k = 0; k < 3; ++k)
+                for (int a = 0; a < 3; ++a) P.src->unowned.push_back(d.triangles[t * 24 + k * 8 + a]);
+}
+
+// kdtree-ray's slab test (scene_slab, pt_integrator.h): the exact bounding box of the scene - the union of
+// Model::bound() (model.rs:76-86: the positions' bounds for a mesh, centre -+ radius for a sphere).  A cast whose origin
+// is not strictly inside it runs the test once, at its end (hit_passes_slab).
+void prep_slab_box(const pt_scene_desc& d, DevScene& D) {
+    for (int a = 0; a < 3; ++a) {
+        D.slab_min[a] = INFINITY;
+        D.slab_max[a] = -INFINITY;
+    }
+    for (uint32_t m = 0; m < d.n_models; ++m) {
+        const pt_model& mo = d.models[m];
+        const uint32_t cnt = mo.kind == PT_MODEL_MESH ? mo.tri_count : 1u;
+        for (uint32_t t = 0; t < cnt; ++t) {
+            for (int a = 0; a < 3; ++a) {
+                float lo, hi;
+                if (mo.kind == PT_MODEL_MESH) {
+                    const float* v = d.triangles + (size_t)(mo.tri_first + t) * 24;
+                    lo = fminf(fminf(v[a], v[8 + a]), v[16 + a]);
+                    hi = fmaxf(fmaxf(v[a], v[8 + a]), v[16 + a]);
                 } else {
-                    const float sd[3] = {-1.f * d.lights[i].vec[0], -1.f * d.lights[i].vec[1], -1.f * d.lights[i].vec[2]};
-                    job.valid = pth::og_params_ortho(d, sd, light_res, job.params, job.hdr);
+                    lo = mo.center[a] - mo.radius;
+                    hi = mo.center[a] + mo.radius;
                 }
-                if (!job.valid) all = false;
-                P.light_jobs.push_back(job);
-            }
-            if (!all) P.light_jobs.clear();
-            P.all_lights_gridded = all;
-            D.all_lights_gridded = all ? 1u : 0u;
-            D.light_grid_max_normal2 = max_normal * max_normal;
-            P.info.grid_build_seconds = std::chrono::duration<float>(std::chrono::steady_clock::now() - t_grid).count();
-            if (early) {
-                select_device(early_device);
-                int cur = 0;
-                HIP_CHECK(hipGetDevice(&cur));
-                early->device = cur;
-                grids_on_device(P, *early);
-            }
-            return;
-        }
-        // (the camera grid on a thread of its own beside the light grids: every grid is its own count / scan / fill / sort)
-        std::future<void> cam_done;
-        if (grids_on && n_prims > 0 && fro > 0 && fro < 64.0 && estimate(res) <= budget) {
-            P.cam_grid = std::make_unique<pt_prep::Grid>();
-            cam_done = std::async(std::launch::async, [&P, &d, M, res, fro] {
-                if (pth_origin_grid_build(&d, M + 12, res, 0.f, (float)(fro * 1.001), &P.cam_grid->g) != PT_OK)
-                    fail(PT_ERR_INVALID, "origin grid (camera): %s", pth_last_error());
-            });
-        }
-        struct JoinCam {
-            std::future<void>& f;
-            ~JoinCam() { if (f.valid()) f.wait(); }
-        } join_cam{cam_done};
-        // lights: the shadow queue is consumed by ONE kernel, so the grids serve the shadow rays only when EVERY
-        // light has one - a cube map around a point light, an orthographic grid along a directional light.  A
-        // point light's shadow ray starts n * 1e-5 off the line through the light (mod.rs:319): the grids' margin
-        // covers |n| <= 1.5, longer normals take the KD-tree per surface.
-        bool all = grids_on && n_prims > 0 && lights_fit;   // (no lights at all: vacuously)
-        const float max_normal = 1.5f;
-        for (uint32_t i = 0; i < d.n_lights && all; ++i) {
-            P.light_grids.push_back(std::make_unique<pt_prep::Grid>());
-            int rc;
-            if (d.lights[i].kind == PT_LIGHT_POINT) {
-                rc = pth_origin_grid_build(&d, d.lights[i].vec, light_res, 1.05e-5f * max_normal, 1.001f, &P.light_grids.back()->g);
-            } else {   // the shadow rays run along -direction (mod.rs:291), as it is
-                const float sd[3] = {-1.f * d.lights[i].vec[0], -1.f * d.lights[i].vec[1], -1.f * d.lights[i].vec[2]};
-                rc = pth_ortho_grid_build(&d, sd, light_res, &P.light_grids.back()->g);
-            }
-            if (rc != PT_OK) fail(PT_ERR_INVALID, "origin grid (light %u): %s", i, pth_last_error());
-            if (!P.light_grids.back()->g.enabled) all = false;
-            grid_bytes += 4.0 * P.light_grids.back()->g.n_cells + 8.0 * P.light_grids.back()->g.n_refs;
-            if (grid_bytes > budget) all = false;   // (the lists came out longer than estimated)
-        }
-        if (cam_done.valid()) {
-            cam_done.get();
-            if (P.cam_grid->g.enabled) {
-                P.info.cam_grid_res = P.cam_grid->g.res;
-                P.info.grid_refs += P.cam_grid->g.n_refs;
-                grid_bytes += 4.0 * P.cam_grid->g.n_cells + 8.0 * P.cam_grid->g.n_refs;
-                if (grid_bytes > budget) all = false;
+                D.slab_min[a] = fminf(D.slab_min[a], lo);
+                D.slab_max[a] = fmaxf(D.slab_max[a], hi);
             }
         }
-        if (!all) P.light_grids.clear();
-        for (auto& g : P.light_grids) P.info.grid_refs += g->g.n_refs;
-        P.all_lights_gridded = all;
-        D.all_lights_gridded = all ? 1u : 0u;
-        D.light_grid_max_normal2 = max_normal * max_normal;
-        P.info.light_grids = all ? d.n_lights : 0u;
-        P.info.grid_build_seconds = std::chrono::duration<float>(std::chrono::steady_clock::now() - t_grid).count();
-    };
-    std::future<void> grids_done = std::async(std::launch::async, build_grids);
-    struct JoinGrids {   // (an exception on the way out must not leave the thread behind)
-        std::future<void>& f;
-        ~JoinGrids() { if (f.valid()) f.wait(); }
-    } join_grids{grids_done};
+    }
+}
 
-    // ---- KD-tree
-    pth_kdtree kd;
-    if (pth_kd_build(&d, &kd) != PT_OK) fail(PT_ERR_INVALID, "KD build failed: %s", pth_last_error());
-    std::unique_ptr<pth_kdtree, void (*)(pth_kdtree*)> kd_guard(&kd, pth_kd_free);
-    if (kd.depth >= PT_KD_STACK) fail(PT_ERR_UNSUPPORTED, "KD-tree depth %u exceeds the traversal stack", kd.depth);
+// The grid jobs of a scene whose grids the device builds at upload time: only their parameters are derived here.
+void prep_grid_jobs(const pt_scene_desc& d, const GridRule& rule, pt_prep& P) {
+    if (rule.cam_res) P.cam_job = camera_grid(d.camera.transform, rule.cam_res, DescJobs{d});
+    bool all = rule.lights;   // (no lights at all: vacuously)
+    for (uint32_t i = 0; i < d.n_lights && all; ++i) {
+        P.light_jobs.push_back(light_grid(d.lights[i].kind, d.lights[i].vec, rule.light_res, DescJobs{d}));
+        all = P.light_jobs.back().valid;
+    }
+    if (!all) P.light_jobs.clear();
+    P.all_lights_gridded = all;
+}
 
-    section("KD build");
-    section("slab box + edge marks");
-    // leaf records in leaf-reference order
+// PT_OG_HOST=1: the grids built here, by the host builder.
+void prep_host_grids(const pt_scene_desc& d, const GridRule& rule, pt_prep& P) {
+    // (the camera grid on a thread of its own beside the light grids: every grid is its own count / scan / fill / sort)
+    std::future<void> cam_done;
+    if (rule.cam_res)
+        cam_done = std::async(std::launch::async, [&P, &d, &rule] { P.cam_grid = camera_grid(d.camera.transform, rule.cam_res, HostBuilt{d, "camera"}); });
+    Join join_cam{cam_done};
+    // lights: all or none (light_grids_build), within the budget as built too
+    const double budget = P.src->budget;
+    double grid_bytes = 0;
+    bool all = rule.lights;   // (no lights at all: vacuously)
+    for (uint32_t i = 0; i < d.n_lights && all; ++i) {
+        P.light_grids.push_back(light_grid(d.lights[i].kind, d.lights[i].vec, rule.light_res, HostBuilt{d, "light " + std::to_string(i)}));
+        const pth_origin_grid& g = P.light_grids.back()->g;
+        if (!g.enabled) all = false;
+        grid_bytes += 4.0 * g.n_cells + 8.0 * g.n_refs;
+        if (grid_bytes > budget) all = false;   // (the lists came out longer than estimated)
+    }
+    if (cam_done.valid()) {
+        cam_done.get();
+        if (P.cam_grid && P.cam_grid->g.enabled) {
+            grid_bytes += 4.0 * P.cam_grid->g.n_cells + 8.0 * P.cam_grid->g.n_refs;
+            if (grid_bytes > budget) all = false;
+        }
+    }
+    if (!all) P.light_grids.clear();
+    P.all_lights_gridded = all;
+}
+
+// ---- origin grids (host/origin_grid.cpp, csrc/pt_grid.h): camera rays, shadow rays of the lights.  They depend on the
+// scene description only, not on the KD-tree: prep_create runs this on a thread of its own BESIDE the KD build (both are
+// seconds of multi-threaded host work; setup of config 3: 3.2 -> 2.3 s).  For the one scene of pt_scene_create (`early`) the
+// device build follows at once, on this thread.
+void prep_grids(const pt_scene_desc& d, uint64_t n_prims, pt_prep& P, EarlyGrids* early) {
+    auto t_grid = std::chrono::steady_clock::now();
+    static const bool grids_on = [] {
+        const char* e = getenv("PT_OG");
+        return !(e && *e && atoi(e) == 0);
+    }();
+    // the byte budget over all grids of the scene and the resolutions it leaves (grid_rule)
+    static const double budget = [] {
+        const char* e = getenv("PT_OG_BUDGET_GIB");
+        const double g = e && *e ? atof(e) : 48.0;
+        return (g > 0 ? g : 48.0) * 1073741824.0;
+    }();
+    static const bool host_grids = [] {
+        const char* e = getenv("PT_OG_HOST");
+        return e && *e && atoi(e) != 0;
+    }();
+    const GridRule rule = grid_rule(n_prims, d.n_lights, budget, grids_on);
+    P.src->cam_res = rule.cam_res;
+    P.src->grids_on = grids_on;
+    P.src->budget = budget;
+    P.src->device_grids = !host_grids;
+    host_grids ? prep_host_grids(d, rule, P) : prep_grid_jobs(d, rule, P);
+    P.info.grid_build_seconds = std::chrono::duration<float>(std::chrono::steady_clock::now() - t_grid).count();
+    if (early && !host_grids) {
+        select_device(early->device);
+        int cur = 0;
+        HIP_CHECK(hipGetDevice(&cur));
+        early->scene.device = cur;
+        early->grids = grids_on_device(P, early->scene);
+        early->built = true;
+    }
+}
+
+// The leaf records in leaf-reference order and the small tables.
+void prep_leaf_tables(const pt_scene_desc& d, const pth_kdtree& kd, pt_prep& P) {
+    const std::vector<float4>& pos = P.pos;
     P.leaf.resize(kd.n_refs * 3);
     for (uint64_t r = 0; r < kd.n_refs; ++r) {
         uint32_t p = kd.refs[r];
@@ -1010,68 +1050,71 @@ void prep_create(const pt_scene_desc& d, pt_prep& P, pt_scene* early = nullptr, 
     for (uint32_t i = 0; i < d.n_lights; ++i) P.lights[i] = dev_light(d.lights[i]);
     P.textures.assign(d.textures, d.textures + d.n_textures);
     P.texels.assign(d.texels, d.texels + d.n_texel_bytes);
+}
 
-    section("leaf records, tables");
-    // ---- device node layout.  The builder emits DFS order (below child = next node); on the GPU the
-    // walk is bound by cache-line round trips (a wave waits for the slowest of ~43 scattered node
-    // fetches), so the nodes are re-laid out in treelets: sibling PAIRS are adjacent (children of a
-    // node = pair, pair + 1) and the pairs of a 4-level subtree are packed consecutively, so that
-    // one 128-byte line serves up to four steps of a walk.  Node words: interior (split,
-    // pair << 2 | axis), leaf (first record, n << 2 | 3) as before.
+// The device node layout.  The builder emits DFS order (below child = next node); on the GPU the
+// walk is bound by cache-line round trips (a wave waits for the slowest of ~43 scattered node
+// fetches), so the nodes are re-laid out in treelets: sibling PAIRS are adjacent (children of a
+// node = pair, pair + 1) and the pairs of a 4-level subtree are packed consecutively, so that
+// one 128-byte line serves up to four steps of a walk.  Node words: interior (split,
+// pair << 2 | axis), leaf (first record, n << 2 | 3) as before.
+// Returns the device slot of every builder (DFS) node number.
+std::vector<uint32_t> prep_treelets(const pth_kdtree& kd, pt_prep& P) {
     std::vector<pth_kd_node>& tre = P.nodes;
     tre.assign(std::max<uint64_t>(kd.n_nodes, 1) + 1, pth_kd_node{0u, 0u});
     std::vector<uint32_t> new_index(kd.n_nodes, 0xffffffffu);   // builder (DFS) node number -> device slot
-    {
-        const pth_kd_node* N = kd.nodes;
-        const int H = 4;  // treelet height: 2 + 4 + 8 = 14 nodes = 112 B below the treelet root pair
-        if (kd.n_nodes == 0) {
-            tre[0] = pth_kd_node{0u, 3u};
-        } else {
-            new_index[0] = 0;
-            uint32_t next = 2;  // pairs start at even indices; slot 1 pads the root
-            std::vector<uint32_t> cluster_roots{0}, frontier, level;
-            size_t cr = 0;
-            while (cr < cluster_roots.size()) {
-                level.assign(1, cluster_roots[cr++]);
-                for (int depth = 0; depth < H && !level.empty(); ++depth) {
-                    frontier.clear();
-                    for (uint32_t n : level) {
-                        if ((N[n].w1 & 3u) == 3u) continue;
-                        uint32_t below = n + 1, above = N[n].w1 >> 2;
-                        new_index[below] = next;
-                        new_index[above] = next + 1;
-                        next += 2;
-                        frontier.push_back(below);
-                        frontier.push_back(above);
-                    }
-                    level.swap(frontier);
+    const pth_kd_node* N = kd.nodes;
+    const int H = 4;  // treelet height: 2 + 4 + 8 = 14 nodes = 112 B below the treelet root pair
+    if (kd.n_nodes == 0) {
+        tre[0] = pth_kd_node{0u, 3u};
+    } else {
+        new_index[0] = 0;
+        uint32_t next = 2;  // pairs start at even indices; slot 1 pads the root
+        std::vector<uint32_t> cluster_roots{0}, frontier, level;
+        size_t cr = 0;
+        while (cr < cluster_roots.size()) {
+            level.assign(1, cluster_roots[cr++]);
+            for (int depth = 0; depth < H && !level.empty(); ++depth) {
+                frontier.clear();
+                for (uint32_t n : level) {
+                    if ((N[n].w1 & 3u) == 3u) continue;
+                    uint32_t below = n + 1, above = N[n].w1 >> 2;
+                    new_index[below] = next;
+                    new_index[above] = next + 1;
+                    next += 2;
+                    frontier.push_back(below);
+                    frontier.push_back(above);
                 }
-                // whatever is left at the bottom of this treelet starts new treelets
-                for (uint32_t n : level)
-                    if ((N[n].w1 & 3u) != 3u) cluster_roots.push_back(n);
+                level.swap(frontier);
             }
-            if (next > tre.size()) tre.resize(next);
-            if (next >= (1u << 29)) fail(PT_ERR_UNSUPPORTED, "KD-tree has too many nodes");
-            for (uint64_t n = 0; n < kd.n_nodes; ++n) {
-                pth_kd_node nd = N[n];
-                if ((nd.w1 & 3u) != 3u) nd.w1 = (new_index[n + 1] << 2) | (nd.w1 & 3u);
-                tre[new_index[n]] = nd;
-            }
-            tre[1] = pth_kd_node{0u, 3u};
+            // whatever is left at the bottom of this treelet starts new treelets
+            for (uint32_t n : level)
+                if ((N[n].w1 & 3u) != 3u) cluster_roots.push_back(n);
         }
+        if (next > tre.size()) tre.resize(next);
+        if (next >= (1u << 29)) fail(PT_ERR_UNSUPPORTED, "KD-tree has too many nodes");
+        for (uint64_t n = 0; n < kd.n_nodes; ++n) {
+            pth_kd_node nd = N[n];
+            if ((nd.w1 & 3u) != 3u) nd.w1 = (new_index[n + 1] << 2) | (nd.w1 & 3u);
+            tre[new_index[n]] = nd;
+        }
+        tre[1] = pth_kd_node{0u, 3u};
     }
-    section("treelet layout");
-    // ---- entry lists (trav_enter, csrc/pt_wavefront.h).  A path's next ray starts ON the primitive it just hit
-    // (origin = hit point + interpolated normal * 1e-5, mod.rs:266-268), deep inside the tree: of the ~23 nodes such a
-    // cast visits, the first ~15 are the descent from the root to the small node around its origin - a chain of
-    // dependent 8-byte fetches during which nothing is decided that the origin's whereabouts do not already say, except
-    // which far children the ray will come back to.  So every primitive gets its HOME NODE - the deepest node whose box
-    // holds every origin a hit on the primitive can produce - and the list of the home node's ancestors, root first:
-    // (split, far child << 3 | near child is the below child << 2 | axis).  The cast reads that list (contiguous, all
-    // loads in flight together), pushes the far children its ray reaches, and starts walking at the home node.  The
-    // lists are shared by the primitives of a home node (a few MB in all).  Nothing here is load-bearing for
-    // correctness: the cast checks that its origin lies on the near side of every listed plane and starts at the root
-    // otherwise, so the region below is an estimate that only has to be right most of the time.
+    return new_index;
+}
+
+// The entry lists (trav_enter, csrc/pt_wavefront.h).  A path's next ray starts ON the primitive it just hit
+// (origin = hit point + interpolated normal * 1e-5, mod.rs:266-268), deep inside the tree: of the ~23 nodes such a
+// cast visits, the first ~15 are the descent from the root to the small node around its origin - a chain of
+// dependent 8-byte fetches during which nothing is decided that the origin's whereabouts do not already say, except
+// which far children the ray will come back to.  So every primitive gets its HOME NODE - the deepest node whose box
+// holds every origin a hit on the primitive can produce - and the list of the home node's ancestors, root first:
+// (split, far child << 3 | near child is the below child << 2 | axis).  The cast reads that list (contiguous, all
+// loads in flight together), pushes the far children its ray reaches, and starts walking at the home node.  The
+// lists are shared by the primitives of a home node (a few MB in all).  Nothing here is load-bearing for
+// correctness: the cast checks that its origin lies on the near side of every listed plane and starts at the root
+// otherwise, so the region below is an estimate that only has to be right most of the time.
+void prep_entry_lists(const pt_scene_desc& d, const pth_kdtree& kd, const std::vector<uint32_t>& new_index, uint64_t n_prims, pt_prep& P) {
     P.prim_entry.assign(n_prims, 0u);
     P.entry_lists.clear();
     if (kd.n_nodes > 0 && n_prims > 0) {
@@ -1136,29 +1179,24 @@ void prep_create(const pt_scene_desc& d, pt_prep& P, pt_scene* early = nullptr, 
     }
     if (P.entry_lists.size() & 1u) P.entry_lists.push_back(make_uint2(0u, 0u));
     for (int k = 0; k < 8; ++k) P.entry_lists.push_back(make_uint2(0u, 0u));   // (the batched loads of trav_enter read up to 8 entries past a list's start)
+}
+
+// The DevScene scalars (the pointers are set per device) and the prep's rows of pt_scene_info.
+void prep_scalars(const pt_scene_desc& d, const pth_kdtree& kd, uint64_t n_prims, bool translucent, pt_prep& P) {
     DevScene& D = P.dev;
     D.n_lights = d.n_lights;
     D.n_prims = (uint32_t)n_prims;
     D.n_nodes = (uint32_t)kd.n_nodes;
-    D.n_node_slots = (uint32_t)tre.size();
+    D.n_node_slots = (uint32_t)P.nodes.size();
     D.has_translucent = translucent ? 1u : 0u;
     for (int a = 0; a < 3; ++a) {
         float pad = 1e-4f * std::max(fabsf(kd.bounds_min[a]), fabsf(kd.bounds_max[a])) + 1e-5f;
         D.bounds_min[a] = kd.bounds_min[a] - pad;
         D.bounds_max[a] = kd.bounds_max[a] + pad;
     }
-    const float* M = d.camera.transform;
-    memcpy(D.cam_c0, M, 12);
-    memcpy(D.cam_c1, M + 4, 12);
-    memcpy(D.cam_c2, M + 8, 12);
-    memcpy(D.cam_c3, M + 12, 12);
-    D.tan_half_fov = tanf(d.camera.fov / 2.f);  // Rad::tan(fov / 2.) (mod.rs:116,120)
+    dev_camera(d.camera, D);
     memcpy(D.background, d.background, 12);
-
-
-    section("entry lists");
-    grids_done.get();   // (rethrows what the grid thread threw)
-    section("waiting for the grids");
+    D.light_grid_max_normal2 = max_normal * max_normal;
     P.info.n_prims = n_prims;
     P.info.n_kd_nodes = kd.n_nodes;
     P.info.n_kd_leaves = kd.n_leaves;
@@ -1168,14 +1206,100 @@ void prep_create(const pt_scene_desc& d, pt_prep& P, pt_scene* early = nullptr, 
     P.info.kd_build_seconds = (float)kd.build_seconds;
 }
 
-// One origin grid built on the device (csrc/pt_grid_build.h) from the parameters / header prep_create derived.  Returns
-// false when the grid is not to be had - too many primitives every ray would have to test, more than 2^32 list entries,
-// the byte budget of the scene's grids exceeded, or the device out of memory: the casts it would have served take the
-// KD-tree.  On success the two arrays belong to the scene (s.allocations).
-bool device_grid_build(pt_scene& s, const pt_prep::GridJob& job, const float* d_geom, const uint32_t* d_words, uint32_t n_prims,
-                       const std::vector<uint32_t>& words, double& bytes_used, double budget, DevGrid& out, pth_origin_grid& hdr_out,
-                       uint64_t& dev_bytes) {
-    memset(&out, 0, sizeof out);
+// `early`: the scene this prep is made for, when there is exactly one (pt_scene_create, EarlyGrids).
+void prep_create(const pt_scene_desc& d, pt_prep& P, EarlyGrids* early = nullptr) {
+    const bool dbg_setup = getenv("PT_DEBUG_SETUP") != nullptr;
+    auto t_sec = std::chrono::steady_clock::now();
+    auto section = [&](const char* name) {
+        if (!dbg_setup) return;
+        auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[prep] %-28s %.3f s\n", name, std::chrono::duration<double>(now - t_sec).count());
+        t_sec = now;
+    };
+    prep_tables(d, P);
+    const uint64_t n_prims = pth_prim_count(&d);
+    const bool translucent = prep_primitives(d, n_prims, P);
+    prep_unowned(d, P);
+    prep_slab_box(d, P.dev);
+    if (n_prims >= (1ull << 28)) fail(PT_ERR_UNSUPPORTED, "more than 2^28 primitives");   // (pack_hit's index bits)
+    section("primitive arrays, scene box");
+    std::future<void> grids_done = std::async(std::launch::async, [&d, &P, n_prims, early] { prep_grids(d, n_prims, P, early); });
+    Join join_grids{grids_done};
+
+    // ---- KD-tree
+    pth_kdtree kd;
+    if (pth_kd_build(&d, &kd) != PT_OK) fail(PT_ERR_INVALID, "KD build failed: %s", pth_last_error());
+    std::unique_ptr<pth_kdtree, void (*)(pth_kdtree*)> kd_guard(&kd, pth_kd_free);
+    if (kd.depth >= PT_KD_STACK) fail(PT_ERR_UNSUPPORTED, "KD-tree depth %u exceeds the traversal stack", kd.depth);
+
+    section("KD build");
+    prep_leaf_tables(d, kd, P);
+    section("leaf records, tables");
+    const std::vector<uint32_t> new_index = prep_treelets(kd, P);
+    section("treelet layout");
+    prep_entry_lists(d, kd, new_index, n_prims, P);
+    prep_scalars(d, kd, n_prims, translucent, P);
+    section("entry lists");
+    grids_done.get();   // (rethrows what the grid thread threw)
+    section("waiting for the grids");
+}
+
+// A mark in the scene's device allocations.  Unless it is released, its destructor frees what the scene has allocated since
+// and gives info.device_bytes its value back: a grid that is not to be had, an edit that failed.
+struct AllocMark {
+    pt_scene& s;
+    size_t mark;
+    uint64_t bytes;
+    bool released = false;
+    explicit AllocMark(pt_scene& sc) : s(sc), mark(sc.allocations.size()), bytes(sc.info.device_bytes) {}
+    void release() { released = true; }
+    ~AllocMark() {
+        if (released) return;
+        while (s.allocations.size() > mark) {
+            (void)hipFree(s.allocations.back());
+            s.allocations.pop_back();
+        }
+        s.info.device_bytes = bytes;
+    }
+};
+
+// The primitives' footprints (CamGridSource: og_geom, og_words) on a device for its grid builds, freed on every way out.
+struct Footprints {
+    float* geom = nullptr;
+    uint32_t* words = nullptr;
+    ~Footprints() {
+        for (void* q : {(void*)geom, (void*)words})
+            if (q) (void)hipFree(q);
+    }
+};
+
+// What the kernels read of the grid of header `hdr` whose arrays are on the device.
+DevGrid dev_grid_from(const pth_origin_grid& hdr, const uint32_t* cell_off, const uint2* refs) {
+    DevGrid out{};
+    out.cell_off = cell_off;
+    out.refs = refs;
+    out.res = hdr.res;
+    out.n_global = hdr.n_global;
+    out.half_res = 0.5f * (float)hdr.res;
+    out.kind = hdr.kind;
+    memcpy(out.axis_u, hdr.axis_u, 12);
+    memcpy(out.axis_v, hdr.axis_v, 12);
+    memcpy(out.axis_w, hdr.axis_w, 12);
+    out.u0 = hdr.u0;
+    out.v0 = hdr.v0;
+    out.cells_per_unit = hdr.cells_per_unit;
+    return out;
+}
+
+// One origin grid built on the device (csrc/pt_grid_build.h) from the parameters / header of `job`, over the footprints F.
+// Returns false, and an empty slot, when the grid is not to be had - too many primitives every ray would have to test, more
+// than 2^32 list entries, the byte budget of the scene's grids exceeded (`bytes_used`: what the grids before it took), or the
+// device out of memory: the casts it would have served take the KD-tree.  On success the two arrays belong to the scene
+// (s.allocations).
+bool device_grid_build(pt_scene& s, const pt_prep::GridJob& job, const Footprints& F, const CamGridSource& src, double& bytes_used,
+                       GridSlot& out) {
+    out = GridSlot{};
+    const uint32_t n_prims = (uint32_t)src.og_words.size();
     if (!job.valid || n_prims == 0) return false;
     static const uint32_t max_global = [] {
         const char* e = getenv("PT_OG_MAX_GLOBAL");
@@ -1202,7 +1326,7 @@ bool device_grid_build(pt_scene& s, const pt_prep::GridJob& job, const float* d_
     };
     try {
         const size_t off_bytes = (n_cells + 2) * 4;
-        if (bytes_used + (double)off_bytes > budget) return false;
+        if (bytes_used + (double)off_bytes > src.budget) return false;
         HIP_CHECK(hipMalloc((void**)&cnt_base, off_bytes));
         HIP_CHECK(hipMemsetAsync(cnt_base, 0, off_bytes, 0));
         const uint32_t glob_cap = max_global + 1u;
@@ -1210,7 +1334,7 @@ bool device_grid_build(pt_scene& s, const pt_prep::GridJob& job, const float* d_
         HIP_CHECK(hipMemsetAsync(d_glob, 0, (glob_cap + 2u) * 4, 0));
         phase("alloc");
         const dim3 pg((n_prims + 3u) / 4u);   // a wavefront per primitive
-        hipLaunchKernelGGL((ogb::k_og_raster<0>), pg, dim3(256), 0, 0, G, d_geom, d_words, n_prims, cnt_base + 1, (uint2*)nullptr,
+        hipLaunchKernelGGL((ogb::k_og_raster<0>), pg, dim3(256), 0, 0, G, F.geom, F.words, n_prims, cnt_base + 1, (uint2*)nullptr,
                            d_glob + 2, d_glob, glob_cap);
         HIP_CHECK(hipGetLastError());
         phase("count");
@@ -1235,7 +1359,7 @@ bool device_grid_build(pt_scene& s, const pt_prep::GridJob& job, const float* d_
             run += v == 0xffffffffu ? 0x100000000ull : v;   // (a saturated block sum: the grid is given up below)
         }
         const uint64_t total = run;
-        if (total > 0xffffffffull || bytes_used + (double)off_bytes + 8.0 * (double)total > budget) {
+        if (total > 0xffffffffull || bytes_used + (double)off_bytes + 8.0 * (double)total > src.budget) {
             cleanup();
             return false;
         }
@@ -1248,10 +1372,10 @@ bool device_grid_build(pt_scene& s, const pt_prep::GridJob& job, const float* d_
             std::vector<uint32_t> g(glob.begin() + 2, glob.begin() + 2 + n_global);
             std::sort(g.begin(), g.end());
             std::vector<uint2> front(n_global);
-            for (uint32_t i = 0; i < n_global; ++i) front[i] = make_uint2(words[g[i]], 0u);
+            for (uint32_t i = 0; i < n_global; ++i) front[i] = make_uint2(src.og_words[g[i]], 0u);
             HIP_CHECK(hipMemcpy(d_refs, front.data(), (size_t)n_global * 8, hipMemcpyHostToDevice));
         }
-        hipLaunchKernelGGL((ogb::k_og_raster<1>), pg, dim3(256), 0, 0, G, d_geom, d_words, n_prims, cnt_base + 1, d_refs, d_glob + 2,
+        hipLaunchKernelGGL((ogb::k_og_raster<1>), pg, dim3(256), 0, 0, G, F.geom, F.words, n_prims, cnt_base + 1, d_refs, d_glob + 2,
                            d_glob, glob_cap);
         HIP_CHECK(hipGetLastError());
         phase("fill");
@@ -1267,88 +1391,63 @@ bool device_grid_build(pt_scene& s, const pt_prep::GridJob& job, const float* d_
         s.allocations.push_back(cnt_base);
         s.allocations.push_back(d_refs);
         const double bytes = (double)off_bytes + 8.0 * (double)std::max<uint64_t>(1, total);
-        dev_bytes += (uint64_t)bytes;
         bytes_used += bytes;
         hdr.n_refs = total;
         hdr.enabled = 1;
-        out.cell_off = cnt_base;
-        out.refs = d_refs;
-        out.res = hdr.res;
-        out.n_global = n_global;
-        out.half_res = 0.5f * (float)hdr.res;
-        out.kind = hdr.kind;
-        memcpy(out.axis_u, hdr.axis_u, 12);
-        memcpy(out.axis_v, hdr.axis_v, 12);
-        memcpy(out.axis_w, hdr.axis_w, 12);
-        out.u0 = hdr.u0;
-        out.v0 = hdr.v0;
-        out.cells_per_unit = hdr.cells_per_unit;
-        hdr_out = hdr;
+        out.dev = dev_grid_from(hdr, cnt_base, d_refs);
+        out.hdr = hdr;
+        out.bytes = (uint64_t)bytes;
         return true;
     } catch (const GpuError&) {
         cleanup();
-        memset(&out, 0, sizeof out);
         return false;
     }
 }
 
-// Every origin grid of the scene, built on the device the calling thread has selected, into s.built (the arrays go to
+// The light grids of a scene, built on its device into G: all or none - the shadow queue is consumed by ONE kernel, so the
+// grids serve the shadow rays only when EVERY light has one (no lights at all: vacuously).  job(i) gives the parameters of
+// light i of n; `all`: whether the lights are to have grids at all; `used`: what the camera grid took of the budget (it
+// comes first).  At the first grid that is not to be had, those built are dropped.
+template <class Job>
+void light_grids_build(pt_scene& s, SceneGrids& G, size_t n, bool all, Job&& job, const Footprints& F, const CamGridSource& src,
+                       double used) {
+    G.lights.assign(n, GridSlot{});
+    AllocMark mark(s);
+    for (size_t i = 0; i < n && all; ++i) {
+        const pt_prep::GridJob& j = job(i);
+        all = device_grid_build(s, j, F, src, used, G.lights[i]);
+    }
+    if (all) mark.release();
+    G.lights_done(all);
+}
+
+// Every origin grid of a scene of the prep, built on the device the calling thread has selected (the arrays go to
 // s.allocations).  Needs of the prep only what prep_create has ready BEFORE the KD build: the grid jobs and the
 // primitives' geometry - so pt_scene_create runs it on a thread of its own beside the KD build.
-void grids_on_device(const pt_prep& P, pt_scene& s) {
+SceneGrids grids_on_device(const pt_prep& P, pt_scene& s) {
     auto t_grid = std::chrono::steady_clock::now();
-    pt_scene::BuiltGrids& B = s.built;
-    const size_t n_lights = P.light_jobs.size();
-    B = pt_scene::BuiltGrids();
-    B.lights.assign(n_lights, DevGrid{});
-    for (auto& g : B.lights) memset(&g, 0, sizeof g);
-    memset(&B.cam, 0, sizeof B.cam);
-    s.grid_headers.assign(1 + std::max(n_lights, (size_t)0), pth_origin_grid{});
-    const uint32_t n_prims = (uint32_t)P.src->og_words.size();
-    float* d_geom = nullptr;
-    uint32_t* d_words = nullptr;
-    double used = 0;
-    if ((P.cam_job.valid || n_lights) && n_prims > 0 && hipMalloc((void**)&d_geom, P.src->og_geom.size() * 4) == hipSuccess &&
-        hipMalloc((void**)&d_words, P.src->og_words.size() * 4) == hipSuccess) {
-        bool copied = hipMemcpy(d_geom, P.src->og_geom.data(), P.src->og_geom.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
-                      hipMemcpy(d_words, P.src->og_words.data(), P.src->og_words.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-        if (copied && device_grid_build(s, P.cam_job, d_geom, d_words, n_prims, P.src->og_words, used, P.og_budget, B.cam, s.grid_headers[0], B.bytes)) {
-            B.cam_res = s.grid_headers[0].res;
-            B.refs += s.grid_headers[0].n_refs;
+    const CamGridSource& src = *P.src;
+    SceneGrids G;
+    G.headers = true;
+    const size_t n_lights = P.light_jobs.size();   // (all of the scene's lights, or none: scene_upload has the slots of a scene without)
+    G.lights.assign(n_lights, GridSlot{});
+    {
+        Footprints F;
+        if ((P.cam_job.valid || n_lights) && !src.og_words.empty() && hipMalloc((void**)&F.geom, src.og_geom.size() * 4) == hipSuccess &&
+            hipMalloc((void**)&F.words, src.og_words.size() * 4) == hipSuccess) {
+            const bool copied = hipMemcpy(F.geom, src.og_geom.data(), src.og_geom.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                                hipMemcpy(F.words, src.og_words.data(), src.og_words.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+            double used = 0;
+            if (copied) device_grid_build(s, P.cam_job, F, src, used, G.cam);
+            light_grids_build(s, G, n_lights, copied && P.all_lights_gridded,
+                              [&P](size_t i) -> const pt_prep::GridJob& { return P.light_jobs[i]; }, F, src, used);
+        } else {
+            (void)hipGetLastError();
+            G.lights_done(n_lights == 0 && P.all_lights_gridded);   // (no lights at all: vacuously)
         }
-        // the lights: all or none (the shadow queue is consumed by ONE kernel)
-        bool all = copied && P.all_lights_gridded;
-        const size_t mark = s.allocations.size();
-        const uint64_t bytes_mark = B.bytes;
-        uint64_t light_refs = 0;
-        for (size_t i = 0; i < n_lights && all; ++i) {
-            if (!device_grid_build(s, P.light_jobs[i], d_geom, d_words, n_prims, P.src->og_words, used, P.og_budget, B.lights[i], s.grid_headers[1 + i], B.bytes))
-                all = false;
-            else {
-                light_refs += s.grid_headers[1 + i].n_refs;
-                if (B.lights[i].kind != 0) B.ortho = true;
-            }
-        }
-        if (!all) {   // drop whatever light grids were built
-            for (size_t k = mark; k < s.allocations.size(); ++k) (void)hipFree(s.allocations[k]);
-            s.allocations.resize(mark);
-            B.bytes = bytes_mark;
-            for (auto& g : B.lights) memset(&g, 0, sizeof g);
-            for (size_t i = 1; i < s.grid_headers.size(); ++i) s.grid_headers[i] = pth_origin_grid{};
-            B.ortho = false;
-            light_refs = 0;
-        }
-        B.all_lights = all;
-        B.light_grids = all ? (uint32_t)n_lights : 0u;
-        B.refs += light_refs;
-    } else {
-        (void)hipGetLastError();
-        B.all_lights = n_lights == 0 && P.all_lights_gridded;   // (no lights at all: vacuously)
     }
-    if (d_geom) (void)hipFree(d_geom);
-    if (d_words) (void)hipFree(d_words);
-    B.seconds = std::chrono::duration<float>(std::chrono::steady_clock::now() - t_grid).count();
-    B.done = true;
+    G.seconds = std::chrono::duration<float>(std::chrono::steady_clock::now() - t_grid).count();
+    return G;
 }
 
 // The delta_in of the escape masks of a scene (EscBuildParams): PT_SLACK_K x the largest distance a ray of the scene covers
@@ -1366,7 +1465,6 @@ float escape_delta_in(const DevScene& D) {
     return (float)((double)PT_SLACK_K * reach + 4.0 * 5.9604645e-8 * amax);
 }
 
-// Copy a prepared scene to `device`.
 // The escape masks of a scene (pt_escape.h), built on its device from the uploaded arrays: one wavefront per primitive.  Blocks
 // until they are there (every frame in flight has completed by then).  A device without the memory for them goes without.
 void escape_masks_build(pt_scene& s) {
@@ -1374,9 +1472,8 @@ void escape_masks_build(pt_scene& s) {
     DevScene& D = s.dev;
     const uint64_t n_prims = D.n_prims;
     auto t_esc = std::chrono::steady_clock::now();
-    const size_t mark = s.allocations.size();
-    const uint64_t bytes_mark = s.info.device_bytes;
     try {
+        AllocMark mark(s);
         HIP_CHECK(hipSetDevice(s.device));
         void* buf = nullptr;
         HIP_CHECK(hipMalloc(&buf, n_prims * 80));
@@ -1401,12 +1498,8 @@ void escape_masks_build(pt_scene& s) {
         s.escape_delta = E.delta_in;
         s.info.escape_prims = st[0];
         s.info.escape_clear_fraction = st[0] ? (float)((double)st[1] / (384.0 * st[0])) : 0.f;
+        mark.release();
     } catch (const GpuError&) {   // (no memory for them: the casts are simply made)
-        while (s.allocations.size() > mark) {
-            (void)hipFree(s.allocations.back());
-            s.allocations.pop_back();
-        }
-        s.info.device_bytes = bytes_mark;
         D.escape = nullptr;
     }
     s.info.escape_build_seconds = std::chrono::duration<float>(std::chrono::steady_clock::now() - t_esc).count();
@@ -1417,7 +1510,95 @@ void escape_masks_build(pt_scene& s) {
     }
 }
 
-void scene_upload(const pt_prep& P, int device, pt_scene& s) {
+// What pt_scene_get_info reports of the grids, on top of an `out` that counts every other allocation.
+void grid_facts(const SceneGrids& G, pt_scene_info& out) {
+    out.cam_grid_res = G.cam.hdr.enabled ? G.cam.hdr.res : 0u;
+    out.light_grids = G.all_lights ? (uint32_t)G.lights.size() : 0u;
+    out.grid_refs = G.cam.hdr.enabled ? G.cam.hdr.n_refs : 0;
+    out.device_bytes += G.cam.bytes;
+    for (const GridSlot& g : G.lights) {
+        out.grid_refs += g.hdr.enabled ? g.hdr.n_refs : 0;
+        out.device_bytes += g.bytes;
+    }
+}
+
+// The scene takes another camera grid / other light grids (an empty slot: none): the old arrays are freed, s.grids and what
+// DevScene restates of it change together.  `table`: the new light slots' DevGrid[] on the device (light_grid_table) - the
+// edits upload it while they still may fail.  Nothing here fails.
+void install_camera_grid(pt_scene& s, const GridSlot& slot) {
+    s.release(s.grids.cam.dev.cell_off);
+    s.release(s.grids.cam.dev.refs);
+    s.grids.cam = slot;
+    s.dev.cam_grid = slot.dev;
+}
+
+const DevGrid* light_grid_table(pt_scene& s, const std::vector<GridSlot>& lights) {
+    std::vector<DevGrid> table(lights.size());
+    for (size_t i = 0; i < lights.size(); ++i) table[i] = lights[i].dev;
+    return s.upload(table.data(), table.size());
+}
+
+void install_light_grids(pt_scene& s, const SceneGrids& from, const DevGrid* table) {
+    for (const GridSlot& g : s.grids.lights) {
+        s.release(g.dev.cell_off);
+        s.release(g.dev.refs);
+    }
+    if (s.dev.light_grids) {
+        s.release(s.dev.light_grids);
+        s.info.device_bytes -= std::max<uint64_t>(16, s.grids.lights.size() * sizeof(DevGrid));
+    }
+    s.grids.lights = from.lights;
+    s.grids.all_lights = from.all_lights;
+    s.grids.ortho = from.ortho;
+    s.dev.light_grids = table;
+    s.dev.all_lights_gridded = from.all_lights ? 1u : 0u;
+}
+
+// A grid the host built, copied to the scene's device.
+GridSlot upload_grid(pt_scene& s, const pth_origin_grid& g) {
+    GridSlot out;
+    if (!g.enabled) return out;
+    const uint64_t before = s.info.device_bytes;
+    const uint32_t* cell_off = s.upload(g.cell_off, g.n_cells + 1);
+    const uint2* refs = (const uint2*)s.upload(g.refs, std::max<uint64_t>(1, g.n_refs));
+    out.bytes = s.info.device_bytes - before;
+    s.info.device_bytes = before;   // (the slot has them: grid_facts)
+    out.dev = dev_grid_from(g, cell_off, refs);
+    out.hdr = g;
+    out.hdr.cell_off = nullptr;
+    out.hdr.refs = nullptr;
+    return out;
+}
+
+// PT_OG_HOST=1: the grids of the prep.  They are optional: a device that cannot hold them renders through the KD-tree (the
+// light grids go first, then the camera grid) instead of failing the scene.
+SceneGrids upload_host_grids(const pt_prep& P, pt_scene& s) {
+    SceneGrids G;
+    G.lights.assign(P.lights.size(), GridSlot{});
+    if (P.cam_grid) {
+        try {
+            AllocMark mark(s);
+            G.cam = upload_grid(s, P.cam_grid->g);
+            mark.release();
+        } catch (const GpuError&) {
+            (void)hipGetLastError();
+        }
+    }
+    bool all = P.all_lights_gridded;
+    try {
+        AllocMark mark(s);
+        for (size_t i = 0; i < P.light_grids.size(); ++i) G.lights[i] = upload_grid(s, P.light_grids[i]->g);
+        mark.release();
+    } catch (const GpuError&) {
+        (void)hipGetLastError();
+        all = false;
+    }
+    G.lights_done(all);
+    return G;
+}
+
+// Copy a prepared scene to `device`.  `early`: its grids, where pt_scene_create has had them built already.
+void scene_upload(const pt_prep& P, int device, pt_scene& s, SceneGrids* early = nullptr) {
     select_device(device);
     int cur = 0;
     HIP_CHECK(hipGetDevice(&cur));
@@ -1456,90 +1637,13 @@ void scene_upload(const pt_prep& P, int device, pt_scene& s) {
         const char* after = getenv("PT_ESCAPE_AFTER");   // frames a scene renders without them (0: built for the first frame)
         s.escape_after = after && *after ? (uint32_t)atoi(after) : 2u;
     }
-    auto upload_grid = [&](const pth_origin_grid& g, DevGrid& out) {
-        memset(&out, 0, sizeof out);
-        if (!g.enabled) return;
-        out.cell_off = s.upload(g.cell_off, g.n_cells + 1);
-        out.refs = (const uint2*)s.upload(g.refs, std::max<uint64_t>(1, g.n_refs));
-        out.res = g.res;
-        out.n_global = g.n_global;
-        out.half_res = 0.5f * (float)g.res;
-        out.kind = g.kind;
-        memcpy(out.axis_u, g.axis_u, 12);
-        memcpy(out.axis_v, g.axis_v, 12);
-        memcpy(out.axis_w, g.axis_w, 12);
-        out.u0 = g.u0;
-        out.v0 = g.v0;
-        out.cells_per_unit = g.cells_per_unit;
-    };
-    if (P.device_grids) {   // built on this device (a prep is shared by the devices of a multi-GPU host: each builds its own)
-        if (!s.built.done) grids_on_device(P, s);   // (pt_scene_create has them built beside the KD-tree already)
-        const pt_scene::BuiltGrids& B = s.built;
-        D.cam_grid = B.cam;
-        std::vector<DevGrid> lgrids = B.lights;
-        lgrids.resize(P.lights.size());
-        D.all_lights_gridded = B.all_lights ? 1u : 0u;
-        s.ortho_light_grids = B.ortho;
-        s.info.cam_grid_res = B.cam_res;
-        s.info.light_grids = B.light_grids;
-        s.info.grid_refs = B.refs;
-        s.info.device_bytes += B.bytes;
-        s.info.grid_build_seconds += B.seconds;
-        s.host_light_grids = lgrids;
-        D.light_grids = s.upload(lgrids.data(), lgrids.size());
-        const pth_origin_grid& ch = s.grid_headers[0];
-        s.cam_grid_bytes = ch.enabled ? (ch.n_cells + 2) * 4 + 8 * std::max<uint64_t>(1, ch.n_refs) : 0;   // (device_grid_build)
-        s.cam_grid_refs = ch.enabled ? ch.n_refs : 0;
-        s.light_grid_bytes = B.bytes - s.cam_grid_bytes;
-        s.light_grid_refs = B.refs - s.cam_grid_refs;
-        s.info.upload_seconds = std::chrono::duration<float>(std::chrono::steady_clock::now() - t_up).count();
-        return;
-    }
-    // The grids are optional: a device that cannot hold them renders through the KD-tree (the light grids go first,
-    // then the camera grid) instead of failing the scene.
-    auto drop_allocations_from = [&](size_t mark, uint64_t bytes_mark) {
-        for (size_t k = mark; k < s.allocations.size(); ++k) (void)hipFree(s.allocations[k]);
-        s.allocations.resize(mark);
-        s.info.device_bytes = bytes_mark;
-        (void)hipGetLastError();
-    };
-    memset(&D.cam_grid, 0, sizeof D.cam_grid);
-    if (P.cam_grid) {
-        const size_t mark = s.allocations.size();
-        const uint64_t bytes_mark = s.info.device_bytes;
-        try {
-            upload_grid(P.cam_grid->g, D.cam_grid);
-            s.cam_grid_bytes = s.info.device_bytes - bytes_mark;
-            s.cam_grid_refs = P.cam_grid->g.enabled ? P.cam_grid->g.n_refs : 0;
-        } catch (const GpuError&) {
-            drop_allocations_from(mark, bytes_mark);
-            memset(&D.cam_grid, 0, sizeof D.cam_grid);
-            s.info.grid_refs -= P.cam_grid->g.enabled ? P.cam_grid->g.n_refs : 0;
-            s.info.cam_grid_res = 0;
-        }
-    }
-    std::vector<DevGrid> lgrids(P.lights.size());
-    for (auto& g : lgrids) memset(&g, 0, sizeof g);
-    {
-        const size_t mark = s.allocations.size();
-        const uint64_t bytes_mark = s.info.device_bytes;
-        try {
-            for (size_t i = 0; i < P.light_grids.size(); ++i) {
-                upload_grid(P.light_grids[i]->g, lgrids[i]);
-                if (P.light_grids[i]->g.kind != 0) s.ortho_light_grids = true;
-            }
-            s.light_grid_bytes = s.info.device_bytes - bytes_mark;
-            for (auto& g : P.light_grids) s.light_grid_refs += g->g.n_refs;
-        } catch (const GpuError&) {
-            drop_allocations_from(mark, bytes_mark);
-            for (auto& g : lgrids) memset(&g, 0, sizeof g);
-            for (auto& g : P.light_grids) s.info.grid_refs -= g->g.n_refs;
-            s.ortho_light_grids = false;
-            D.all_lights_gridded = 0u;
-            s.info.light_grids = 0;
-        }
-    }
-    D.light_grids = s.upload(lgrids.data(), lgrids.size());
+    // (built on this device - a prep is shared by the devices of a multi-GPU host, each builds its own - or uploaded)
+    SceneGrids G = early ? std::move(*early) : P.src->device_grids ? grids_on_device(P, s) : upload_host_grids(P, s);
+    G.lights.resize(P.lights.size());
+    s.grids.headers = G.headers;
+    s.info.grid_build_seconds += G.seconds;
+    install_camera_grid(s, G.cam);
+    install_light_grids(s, G, light_grid_table(s, G.lights));
     s.info.upload_seconds = std::chrono::duration<float>(std::chrono::steady_clock::now() - t_up).count();
 }
 
@@ -1547,36 +1651,18 @@ void scene_upload(const pt_prep& P, int device, pt_scene& s) {
 // contract, DESIGN.md 4c / 4d the state they touch row by row).  Everything that can fail comes first - new grids and tables
 // are built beside the old ones - and the scene is changed only afterwards.
 
-// Every device allocation the scene makes after construction is freed again unless `done` is set (an edit that failed).
-struct EditRollback {
-    pt_scene& s;
-    size_t mark;
-    uint64_t bytes;
-    bool done = false;
-    explicit EditRollback(pt_scene& sc) : s(sc), mark(sc.allocations.size()), bytes(sc.info.device_bytes) {}
-    ~EditRollback() {
-        if (done) return;
-        while (s.allocations.size() > mark) {
-            (void)hipFree(s.allocations.back());
-            s.allocations.pop_back();
-        }
-        s.info.device_bytes = bytes;
-    }
-};
-
-// The primitives' footprints (CamGridSource) on the scene's device for the grid builds of an edit, uploaded on first use
-// and freed on every way out, with room for the extent reductions.
-struct EditFootprints {
-    float* geom = nullptr;
-    uint32_t* words = nullptr;
+// The footprints on the scene's device for the grid builds of an edit, uploaded on first use, with room for the extent
+// reductions: the extent source of an edit's grids (light_grid, camera_grid).
+struct EditFootprints : Footprints {
+    const CamGridSource& src;
     unsigned long long* ext = nullptr;   // 12 words
     bool tried = false, ok = false;
+    explicit EditFootprints(const CamGridSource& source) : src(source) {}
     ~EditFootprints() {
-        for (void* q : {(void*)geom, (void*)words, (void*)ext})
-            if (q) (void)hipFree(q);
+        if (ext) (void)hipFree(ext);
     }
     // false: no memory for them (the grids that need them are not to be had, as on a fresh scene in that situation)
-    bool ready(const CamGridSource& src) {
+    bool ready() {
         if (tried) return ok;
         tried = true;
         if (hipMalloc((void**)&geom, src.og_geom.size() * 4) != hipSuccess || hipMalloc((void**)&words, src.og_words.size() * 4) != hipSuccess ||
@@ -1591,8 +1677,21 @@ struct EditFootprints {
     }
     static uint32_t blocks(uint32_t n_prims) { return std::min<uint32_t>((n_prims + 255u) / 256u, 4096u); }
 
+    pt_prep::GridJob point(const float o[3], uint32_t res, float ray_offset, float max_dir_len) {
+        pt_prep::GridJob job;
+        const bool finite = std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]);
+        if (ready()) job.valid = pth::og_params_point_ext(o, res, ray_offset, max_dir_len, finite ? point_extent(o) : 0.0, job.params, job.hdr);
+        return job;
+    }
+    pt_prep::GridJob ortho(const float sd[3], uint32_t res) {
+        pt_prep::GridJob job;
+        pth::og::GridParams axes;
+        if (ready() && pth::og_ortho_axes(sd, axes)) job.valid = pth::og_params_ortho_ext(sd, res, ortho_extent(axes), job.params, job.hdr);
+        return job;
+    }
+
     // og_point_extent about `o`: the device's reduction over the footprints (k_og_extent), the unowned triangles on the host
-    double point_extent(const CamGridSource& src, const float o[3]) {
+    double point_extent(const float o[3]) {
         const uint32_t n_prims = (uint32_t)src.og_words.size();
         HIP_CHECK(hipMemset(ext, 0, 8));
         hipLaunchKernelGGL(ogb::k_og_extent, dim3(blocks(n_prims)), dim3(256), 0, 0, (const float*)geom, (const uint32_t*)words, n_prims,
@@ -1610,7 +1709,7 @@ struct EditFootprints {
     }
 
     // params_ortho's extent along the axes of P (k_og_ortho_extent), the unowned triangles on the host
-    pth::og::OrthoExtent ortho_extent(const CamGridSource& src, const pth::og::GridParams& P) {
+    pth::og::OrthoExtent ortho_extent(const pth::og::GridParams& P) {
         const uint32_t n_prims = (uint32_t)src.og_words.size();
         HIP_CHECK(hipMemset(ext, 0, 12 * 8));
         hipLaunchKernelGGL(ogb::k_og_ortho_extent, dim3(blocks(n_prims)), dim3(256), 0, 0, (const float*)geom, (const uint32_t*)words, n_prims,
@@ -1636,30 +1735,14 @@ struct EditFootprints {
     }
 };
 
-// The camera grid pt_scene_create would build for camera transform M at resolution cam_res (0: none): prep_create's rule
-// (fro < 64, fro * 1.001, the budget), the extent reduced on the device, the device build of grids_on_device.  False: no
-// grid, also when the device has no memory for it.  A device failure of another kind throws.
-bool camera_grid_build(pt_scene& s, EditFootprints& F, const float* M, uint32_t cam_res, double& used, DevGrid& grid,
-                       pth_origin_grid& hdr, uint64_t& bytes) {
+// The camera grid pt_scene_create would build for camera transform M at resolution cam_res (0: none): camera_grid's rule
+// with the extent reduced on the device, the device build of grids_on_device.  An empty slot: no grid, also when the device
+// has no memory for it.  A device failure of another kind throws.
+GridSlot camera_grid_build(pt_scene& s, EditFootprints& F, const float* M, uint32_t cam_res, double& used) {
     const CamGridSource& src = *s.cam_src;
-    memset(&grid, 0, sizeof grid);
-    hdr = pth_origin_grid{};
-    bytes = 0;
-    double fro = 0;
-    for (int k = 0; k < 3; ++k)
-        for (int r = 0; r < 3; ++r) fro += (double)M[4 * k + r] * M[4 * k + r];
-    fro = std::sqrt(fro);
-    const uint32_t n_prims = (uint32_t)src.og_words.size();
-    if (!(src.device_grids && cam_res && n_prims > 0 && fro > 0 && fro < 64.0) || !F.ready(src)) return false;
-    pt_prep::GridJob job;
-    job.valid = pth::og_params_point_ext(M + 12, cam_res, 0.f, (float)(fro * 1.001), F.point_extent(src, M + 12), job.params, job.hdr);
-    const bool built = device_grid_build(s, job, F.geom, F.words, n_prims, src.og_words, used, src.budget, grid, hdr, bytes);
-    if (!built) {
-        memset(&grid, 0, sizeof grid);
-        hdr = pth_origin_grid{};
-        bytes = 0;
-    }
-    return built;
+    GridSlot slot;
+    if (src.device_grids && cam_res && !src.og_words.empty()) device_grid_build(s, camera_grid(M, cam_res, F), F, src, used, slot);
+    return slot;
 }
 
 // What earlier frames left (pt_scene::FrameState).
@@ -1668,40 +1751,24 @@ void drop_frame_state(pt_scene& s) { s.frame_state = pt_scene::FrameState{}; }
 void scene_set_camera(pt_scene& s, const pt_camera& cam) {
     HIP_CHECK(hipSetDevice(s.device));
     HIP_CHECK(hipDeviceSynchronize());   // the frames in flight finish with the old camera (and its grid)
-    DevScene D = s.dev;
     const float* M = cam.transform;
-    memcpy(D.cam_c0, M, 12);   // (as prep_create)
-    memcpy(D.cam_c1, M + 4, 12);
-    memcpy(D.cam_c2, M + 8, 12);
-    memcpy(D.cam_c3, M + 12, 12);
-    D.tan_half_fov = tanf(cam.fov / 2.f);
 
     // ---- the camera grid a fresh scene would have.  PT_OG_HOST=1 (host-built grids): the moved camera goes without.
-    EditRollback rb(s);
-    DevGrid grid;
-    pth_origin_grid hdr{};
-    uint64_t grid_bytes = 0;
+    AllocMark mark(s);
+    GridSlot grid;
     {
-        EditFootprints F;
+        EditFootprints F(*s.cam_src);
         double used = 0;
-        camera_grid_build(s, F, M, s.cam_res, used, grid, hdr, grid_bytes);
+        grid = camera_grid_build(s, F, M, s.cam_res, used);
         // device_grid_build gives up on any failure; what is not a lack of memory is sticky and shows here
         HIP_CHECK(hipDeviceSynchronize());
     }
 
     // ---- from here on nothing fails: the scene takes the new camera
-    rb.done = true;
-    s.release(s.dev.cam_grid.cell_off);
-    s.release(s.dev.cam_grid.refs);
-    D.cam_grid = grid;
-    s.built.cam = grid;
-    s.built.cam_res = hdr.enabled ? hdr.res : 0u;
-    if (!s.grid_headers.empty()) s.grid_headers[0] = hdr;
-    s.info.device_bytes = s.info.device_bytes - s.cam_grid_bytes + grid_bytes;
-    s.info.grid_refs = s.info.grid_refs - s.cam_grid_refs + (hdr.enabled ? hdr.n_refs : 0);
-    s.info.cam_grid_res = hdr.enabled ? hdr.res : 0u;
-    s.cam_grid_bytes = grid_bytes;
-    s.cam_grid_refs = hdr.enabled ? hdr.n_refs : 0;
+    mark.release();
+    install_camera_grid(s, grid);
+    DevScene& D = s.dev;
+    dev_camera(cam, D);
     // ---- escape masks: built with a delta_in at least the new camera's, they stay a proof; otherwise they go, and the
     // PT_ESCAPE_AFTER schedule starts again (a scene whose attempt found no memory tries again too)
     if (D.escape && escape_delta_in(D) > s.escape_delta) {
@@ -1717,7 +1784,6 @@ void scene_set_camera(pt_scene& s, const pt_camera& cam) {
         s.escape_tried = false;
         s.frames_rendered = 0;
     }
-    s.dev = D;
     drop_frame_state(s);
 }
 
@@ -1733,115 +1799,39 @@ void scene_set_lights(pt_scene& s, const pt_light* lights, uint32_t n) {
     const GridRule rule = grid_rule(n_prims, n, src.budget, src.grids_on);
     std::vector<DevLight> dl(n);
     for (uint32_t i = 0; i < n; ++i) dl[i] = dev_light(lights[i]);
-    DevScene D = s.dev;
 
-    EditRollback rb(s);
-    EditFootprints F;
+    AllocMark mark(s);
+    EditFootprints F(src);
+    SceneGrids G;   // the grids of the new lights, and the camera's if they change it
     // ---- the camera grid, if a fresh scene with n lights has another resolution for it
     const bool new_cam = src.device_grids && rule.cam_res != s.cam_res;
-    DevGrid cam_grid = D.cam_grid;
-    pth_origin_grid cam_hdr = s.grid_headers.empty() ? pth_origin_grid{} : s.grid_headers[0];
-    uint64_t cam_bytes = s.cam_grid_bytes;
-    double used = (double)s.cam_grid_bytes;   // (grids_on_device: the light grids come after the camera's in the budget)
+    double used = (double)s.grids.cam.bytes;   // (grids_on_device: the light grids come after the camera's in the budget)
     if (new_cam) {
+        const DevScene& D = s.dev;
         float M[16] = {};
         memcpy(M, D.cam_c0, 12);
         memcpy(M + 4, D.cam_c1, 12);
         memcpy(M + 8, D.cam_c2, 12);
         memcpy(M + 12, D.cam_c3, 12);
         used = 0;
-        camera_grid_build(s, F, M, rule.cam_res, used, cam_grid, cam_hdr, cam_bytes);
+        G.cam = camera_grid_build(s, F, M, rule.cam_res, used);
     }
-    // ---- the light grids: all or none (the shadow queue is consumed by ONE kernel); PT_OG_HOST=1: none
-    std::vector<DevGrid> lg(n);
-    for (auto& g : lg) memset(&g, 0, sizeof g);
-    std::vector<pth_origin_grid> lh(n);
-    bool all = rule.lights, ortho = false;
-    uint64_t l_bytes = 0, l_refs = 0;
-    if (n > 0) {
-        all = all && src.device_grids;
-        const size_t mark = s.allocations.size();
-        const float max_normal = 1.5f;   // (prep_create)
-        for (uint32_t i = 0; i < n && all; ++i) {
-            pt_prep::GridJob job;
-            if (lights[i].kind == PT_LIGHT_POINT) {
-                const float* o = lights[i].vec;
-                const bool finite = std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]);
-                if (F.ready(src))
-                    job.valid = pth::og_params_point_ext(o, rule.light_res, 1.05e-5f * max_normal, 1.001f, finite ? F.point_extent(src, o) : 0.0,
-                                                         job.params, job.hdr);
-            } else {   // the shadow rays run along -direction (mod.rs:291)
-                const float sd[3] = {-1.f * lights[i].vec[0], -1.f * lights[i].vec[1], -1.f * lights[i].vec[2]};
-                pth::og::GridParams axes;
-                if (F.ready(src) && pth::og_ortho_axes(sd, axes))
-                    job.valid = pth::og_params_ortho_ext(sd, rule.light_res, F.ortho_extent(src, axes), job.params, job.hdr);
-            }
-            if (!device_grid_build(s, job, F.geom, F.words, n_prims, src.og_words, used, src.budget, lg[i], lh[i], l_bytes)) {
-                all = false;
-            } else {
-                l_refs += lh[i].n_refs;
-                if (lg[i].kind != 0) ortho = true;
-            }
-        }
-        if (!all) {   // drop whatever light grids were built
-            while (s.allocations.size() > mark) {
-                (void)hipFree(s.allocations.back());
-                s.allocations.pop_back();
-            }
-            for (auto& g : lg) memset(&g, 0, sizeof g);
-            for (auto& h : lh) h = pth_origin_grid{};
-            l_bytes = l_refs = 0;
-            ortho = false;
-        }
-    }
+    // ---- the light grids; PT_OG_HOST=1: none
+    light_grids_build(s, G, n, rule.lights && (n == 0 || src.device_grids),
+                      [&](size_t i) { return light_grid(lights[i].kind, lights[i].vec, rule.light_res, F); }, F, src, used);
     HIP_CHECK(hipDeviceSynchronize());   // (device_grid_build gives up on any failure: what is not a lack of memory shows here)
     const DevLight* d_lights = s.upload(dl.data(), dl.size());
-    const DevGrid* d_grids = s.upload(lg.data(), lg.size());
+    const DevGrid* d_grids = light_grid_table(s, G.lights);
 
     // ---- from here on nothing fails: the scene takes the new lights
-    rb.done = true;
-    const uint64_t n_old = D.n_lights;
-    for (const DevGrid& g : s.host_light_grids) {
-        s.release(g.cell_off);
-        s.release(g.refs);
-    }
-    s.release(D.lights);
-    s.release(D.light_grids);
-    s.info.device_bytes = s.info.device_bytes - s.light_grid_bytes + l_bytes - std::max<uint64_t>(16, n_old * sizeof(DevLight)) -
-                          std::max<uint64_t>(16, n_old * sizeof(DevGrid));
-    s.info.grid_refs = s.info.grid_refs - s.light_grid_refs + l_refs;
-    s.light_grid_bytes = l_bytes;
-    s.light_grid_refs = l_refs;
-    if (new_cam) {
-        s.release(D.cam_grid.cell_off);
-        s.release(D.cam_grid.refs);
-        D.cam_grid = cam_grid;
-        s.built.cam = cam_grid;
-        s.built.cam_res = cam_hdr.enabled ? cam_hdr.res : 0u;
-        if (!s.grid_headers.empty()) s.grid_headers[0] = cam_hdr;
-        s.info.device_bytes = s.info.device_bytes - s.cam_grid_bytes + cam_bytes;
-        s.info.grid_refs = s.info.grid_refs - s.cam_grid_refs + (cam_hdr.enabled ? cam_hdr.n_refs : 0);
-        s.info.cam_grid_res = cam_hdr.enabled ? cam_hdr.res : 0u;
-        s.cam_grid_bytes = cam_bytes;
-        s.cam_grid_refs = cam_hdr.enabled ? cam_hdr.n_refs : 0;
-    }
+    mark.release();
+    s.release(s.dev.lights);
+    s.info.device_bytes -= std::max<uint64_t>(16, (uint64_t)s.dev.n_lights * sizeof(DevLight));
+    install_light_grids(s, G, d_grids);
+    if (new_cam) install_camera_grid(s, G.cam);
     s.cam_res = rule.cam_res;
-    D.lights = d_lights;
-    D.light_grids = d_grids;
-    D.n_lights = n;
-    D.all_lights_gridded = all ? 1u : 0u;
-    s.host_light_grids = lg;
-    s.ortho_light_grids = ortho;
-    s.built.lights = lg;
-    s.built.all_lights = all;
-    s.built.ortho = ortho;
-    s.built.light_grids = all ? n : 0u;
-    s.info.light_grids = all ? n : 0u;
-    if (!s.grid_headers.empty()) {
-        s.grid_headers.resize(1 + n);
-        for (uint32_t i = 0; i < n; ++i) s.grid_headers[1 + i] = lh[i];
-    }
-    s.dev = D;
+    s.dev.lights = d_lights;
+    s.dev.n_lights = n;
     drop_frame_state(s);
 }
 
@@ -1860,9 +1850,9 @@ void scene_set_materials(pt_scene& s, const pt_material* materials, uint32_t n) 
         mm[m] = materials[src.model_material[m]];
         if (mm[m].opacity != 1.0f || mm[m].tex_opacity >= 0) translucent = true;
     }
-    EditRollback rb(s);
+    AllocMark mark(s);
     const pt_material* d_mat = s.upload(mm.data(), mm.size());
-    rb.done = true;
+    mark.release();
     s.release(s.dev.materials);
     s.info.device_bytes -= std::max<uint64_t>(16, n_models * sizeof(pt_material));
     s.dev.materials = d_mat;
@@ -2697,7 +2687,7 @@ void shade_stage(pt_scene& s, const Frame& f, const WfFrame& wf, const Chunk& c,
         HIP_CHECK(hipGetLastError());
     };
     auto launch_shade = [&] {
-        switch (c.grid_mode == 0 ? 0 : c.grid_mode + (s.ortho_light_grids ? 4 : 0) + ((c.grid_mode == 3 && c.cached) ? 8 : 0)) {
+        switch (c.grid_mode == 0 ? 0 : c.grid_mode + (s.grids.ortho ? 4 : 0) + ((c.grid_mode == 3 && c.cached) ? 8 : 0)) {
         case 0: launch(std::integral_constant<int, 0>{}); break;
         case 1: launch(std::integral_constant<int, 1>{}); break;
         case 2: launch(std::integral_constant<int, 2>{}); break;
@@ -2755,7 +2745,7 @@ void shadow_stage(pt_scene& s, const Frame& f, const Chunk& c, Timeline& tl) {
         dispatch([&](auto alpha, auto count, auto dirl) {
             hipLaunchKernelGGL((k_og_shadow<alpha, count, dirl>), g, dim3(256), 0, st_shadow, f.dev, Ws, (const float4*)pipe.shadow.p,
                                (const float4*)pipe.contrib.p, c.q_out, (float*)s.staging_buf.p, (uint32_t*)pipe.offgrid.p, c.wctr, f.gctr);
-        }, f.alpha, f.counting, s.ortho_light_grids);
+        }, f.alpha, f.counting, s.grids.ortho);
         HIP_CHECK(hipGetLastError());
         offgrid(std::true_type{}, (uint32_t)s.n_cu);
     } else {
@@ -3243,8 +3233,9 @@ int pt_scene_create(const pt_scene_desc* desc, int device, pt_scene** out) {
         if (!desc || !out) fail(PT_ERR_INVALID, "pt_scene_create: null argument");
         pt_prep prep;
         auto s = std::make_unique<pt_scene>();
-        prep_create(*desc, prep, s.get(), device);
-        scene_upload(prep, device, *s);
+        EarlyGrids early{*s, device};
+        prep_create(*desc, prep, &early);
+        scene_upload(prep, device, *s, early.built ? &early.grids : nullptr);
         *out = s.release();
     });
 }
@@ -3902,6 +3893,7 @@ int pt_kernel_occupancy(int device, int which, int* blocks_per_cu) {
 int pt_scene_get_info(const pt_scene* scene, pt_scene_info* out) {
     if (!scene || !out) return PT_ERR_INVALID;
     *out = scene->info;
+    grid_facts(scene->grids, *out);
     out->queue_bytes = scene->queue_bytes_last;
     out->queue_chunk_items = scene->queue_chunk_last;
     out->frame_planned = scene->frame_planned_last;
@@ -4025,7 +4017,8 @@ int pt_scene_grid_header(const pt_scene* scene, uint32_t which, pth_origin_grid*
     return guarded([&] {
         if (!scene || !out) fail(PT_ERR_INVALID, "pt_scene_grid_header: null argument");
         memset(out, 0, sizeof *out);
-        if (which < scene->grid_headers.size()) *out = scene->grid_headers[which];
+        const GridSlot* slot = scene->grids.slot(which);
+        if (scene->grids.headers && slot) *out = slot->hdr;
         out->cell_off = nullptr;
         out->refs = nullptr;
     });
@@ -4034,9 +4027,10 @@ int pt_scene_grid_header(const pt_scene* scene, uint32_t which, pth_origin_grid*
 int pt_scene_grid_copy(const pt_scene* scene, uint32_t which, uint32_t* cell_off, pth_grid_ref* refs) {
     return guarded([&] {
         if (!scene || !cell_off || !refs) fail(PT_ERR_INVALID, "pt_scene_grid_copy: null argument");
-        if (which >= scene->grid_headers.size() || !scene->grid_headers[which].enabled) fail(PT_ERR_INVALID, "pt_scene_grid_copy: no such grid");
-        const pth_origin_grid& h = scene->grid_headers[which];
-        const DevGrid& g = which == 0 ? scene->dev.cam_grid : scene->host_light_grids[which - 1];
+        const GridSlot* slot = scene->grids.slot(which);
+        if (!scene->grids.headers || !slot || !slot->hdr.enabled) fail(PT_ERR_INVALID, "pt_scene_grid_copy: no such grid");
+        const pth_origin_grid& h = slot->hdr;
+        const DevGrid& g = slot->dev;
         HIP_CHECK(hipSetDevice(scene->device));
         HIP_CHECK(hipMemcpy(cell_off, g.cell_off, (h.n_cells + 1) * 4, hipMemcpyDeviceToHost));
         if (h.n_refs) HIP_CHECK(hipMemcpy(refs, g.refs, h.n_refs * 8, hipMemcpyDeviceToHost));

@@ -493,9 +493,21 @@ int pt_get_cull_stats(const pt_scene* scene, uint32_t* n_blocks, uint32_t* n_emp
  * was made.  PT_RNG_CACHE=0 switches the cache off, PT_RNG_CACHE_GIB (16) is its budget; both are read per frame.  The
  * bytes are not part of pt_scene_info's queue_bytes or device_bytes. */
 int pt_get_rng_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* fills);
+/* The scene's cache of camera hits (the closest hit of every work item's camera ray, 16 B per item; it depends on the
+ * item enumeration, the camera and the geometry - not on the lights, the bounce count or, in an opaque scene, the
+ * materials - so the frames of light and material edits and of a steady state read it instead of casting): its device
+ * bytes, the work items of the view it is keyed to (0: none - it is keyed when a frame directly follows another of the
+ * same enumeration and camera), how many of them are cached so far, and the launches of the storing and of the loading
+ * variant of the bounce-0 kernel since the scene was made.  Only opaque, uninstrumented frames of the default pipeline
+ * whose words come from the word cache use it; pt_scene_set_camera empties it (the allocation stays), a camera path
+ * never stores and never allocates.  PT_HIT_CACHE=0 switches the cache off, PT_HIT_CACHE_GIB (8) is its budget; both are
+ * read per frame.  The bytes are not part of pt_scene_info's queue_bytes or device_bytes. */
+int pt_get_hit_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* stores,
+                           uint64_t* loads);
 /* Workgroups of the fused bounce-0 kernel of opaque scenes that the runtime places on one compute unit of `device`
  * (hipOccupancyMaxActiveBlocksPerMultiprocessor at the kernel's workgroup size): which = 0 the variant that computes
- * its ChaCha words, 1 the variant that reads them from the word cache.  One workgroup is one wave per SIMD. */
+ * its ChaCha words, 1 the variant that reads them from the word cache, 2 and 3 the variants of 1 that store and that
+ * load the camera hits.  One workgroup is one wave per SIMD. */
 int pt_kernel_occupancy(int device, int which, int* blocks_per_cu);
 
 /* Scene statistics after the KD build. */

@@ -226,7 +226,7 @@ HOST_SYMBOLS = ["pth_scene_load_isf", "pth_scene_free", "pth_scene_desc", "pth_s
 GPU_SYMBOLS = ["pt_scene_create", "pt_scene_destroy", "pt_scene_set_camera", "pt_scene_set_lights", "pt_scene_set_materials", "pt_prep_create", "pt_prep_destroy", "pt_scene_create_from_prep",
                "pt_comm_unique_id", "pt_comm_create", "pt_comm_create_all", "pt_comm_destroy", "pt_gather_tiles", "pt_render_gathered", "pt_local_pixel_count", "pt_local_pixel_map",
                "pt_render", "pt_render_device", "pt_debug_render", "pt_assemble_tiles", "pt_get_timing", "pt_get_counters",
-               "pt_scene_get_info", "pt_get_cull_stats", "pt_get_rng_cache_stats", "pt_kernel_occupancy", "pt_scene_escape_copy", "pt_scene_grid_header", "pt_scene_grid_copy", "pt_trace_rays", "pt_trace_rays_wavefront",
+               "pt_scene_get_info", "pt_get_cull_stats", "pt_get_rng_cache_stats", "pt_get_hit_cache_stats", "pt_kernel_occupancy", "pt_scene_escape_copy", "pt_scene_grid_header", "pt_scene_grid_copy", "pt_trace_rays", "pt_trace_rays_wavefront",
                "pt_trace_rays_all", "pt_intersect_triangles",
                "pt_rng_words", "pt_eval_math", "pt_measure_copy_bandwidth", "pt_measure_gather_rate", "pt_last_error",
                "pt_version", "pt_render_guides", "pt_render_guides_device", "pt_denoise_params_default", "pt_denoise_scratch_bytes",
@@ -331,6 +331,8 @@ def gpu_lib():
         L.pt_get_cull_stats.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         if hasattr(L, "pt_get_rng_cache_stats"):   # (an A/B library of an earlier commit, PT_GPU_LIB, has none)
             L.pt_get_rng_cache_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 4
+        if hasattr(L, "pt_get_hit_cache_stats"):
+            L.pt_get_hit_cache_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 5
         if hasattr(L, "pt_kernel_occupancy"):
             L.pt_kernel_occupancy.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.pt_scene_grid_copy.argtypes = [vp, C.c_uint32, vp, vp]
@@ -369,7 +371,8 @@ def gpu_lib():
 
 
 def kernel_occupancy(which, device=0):
-    """Workgroups of the fused bounce-0 kernel per compute unit (0: the variant computing its ChaCha words, 1: the cached one)."""
+    """Workgroups of the fused bounce-0 kernel per compute unit (0: the variant computing its ChaCha words, 1: the cached one,
+    2 / 3: the cached one storing / loading the camera hits)."""
     n = C.c_int()
     check_gpu(gpu_lib().pt_kernel_occupancy(device, which, C.byref(n)))
     return n.value
@@ -868,6 +871,13 @@ class GpuScene:
         """The scene's cache of ChaCha words: (device bytes, work items of the keyed enumeration, items cached, fill launches)."""
         v = [C.c_uint64() for _ in range(4)]
         check_gpu(self.lib.pt_get_rng_cache_stats(self.handle, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def hit_cache_stats(self):
+        """The scene's cache of camera hits: (device bytes, work items of the keyed view, items cached, storing launches,
+        loading launches)."""
+        v = [C.c_uint64() for _ in range(5)]
+        check_gpu(self.lib.pt_get_hit_cache_stats(self.handle, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
     def counters(self):

@@ -602,6 +602,23 @@ struct pt_scene {
         hipStream_t fill_stream = nullptr;
         bool recorded = false, failed = false;   // (failed: the device could not provide the planes: no cache for this scene)
     } rng_cache;
+    // The camera rays' closest hits of ONE view (hit_cache_frame): the hit of a camera ray depends on the item enumeration
+    // (the jitter words), the camera and the geometry - not on the lights, the bounces or, in an opaque scene, the
+    // materials - so the frames of light and material edits and of a steady state read it instead of casting again.  One
+    // plane of uint4 (pack_hit) by frame-global item g, indexed like the word cache and filled as a prefix [0, mark) by the
+    // storing variant of the bounce-0 kernel.  Keyed to the word cache's key + the camera generation + the camera grid's
+    // resolution: a camera move resets the mark (the allocation stays), no other edit touches it (drop_frame_state).  Not
+    // part of queue_bytes / device_bytes.
+    struct HitCache {
+        DeviceBuffer buf;
+        std::vector<uint64_t> key, last_key;   // the view the records are of; that of the scene's last wavefront frame
+        uint64_t items = 0, stride = 0, mark = 0;   // as RngCache's (the budget: PT_HIT_CACHE_GIB)
+        uint64_t stores = 0, loads = 0;             // launches of the storing / loading variants since the scene was made
+        hipEvent_t ev_store = nullptr;              // behind the last storing launch
+        hipStream_t store_stream = nullptr;
+        bool recorded = false, failed = false;
+    } hit_cache;
+    uint64_t camera_generation = 0;   // bumped by pt_scene_set_camera
     uint64_t queue_bytes_last = 0;   // bytes of the path queues of the last frame (pt_scene_get_info)
     uint32_t queue_chunk_last = 0, frame_planned_last = 0;
     // escape masks: wanted (PT_ESCAPE), built when the scene has rendered `escape_after` frames of the default pipeline
@@ -625,6 +642,7 @@ struct pt_scene {
         for (hipEvent_t e : {pipe.ev_shade, pipe.ev_shadow, pipe.ev_rng, pipe.ev_chunk, pipe.ev_trace, pipe.ev_wide, pipe.ev_exact, pipe.ev_exact_go})
             if (e) (void)hipEventDestroy(e);
         if (rng_cache.ev_fill) (void)hipEventDestroy(rng_cache.ev_fill);
+        if (hit_cache.ev_store) (void)hipEventDestroy(hit_cache.ev_store);
         if (pipe.side_exact) (void)hipStreamDestroy(pipe.side_exact);
         if (pipe.side) (void)hipStreamDestroy(pipe.side);
         if (pipe.side_wide) (void)hipStreamDestroy(pipe.side_wide);
@@ -1785,6 +1803,9 @@ void scene_set_camera(pt_scene& s, const pt_camera& cam) {
         s.frames_rendered = 0;
     }
     drop_frame_state(s);
+    // the camera-hit cache was this camera's: the next view starts at an empty prefix (the allocation stays)
+    ++s.camera_generation;
+    s.hit_cache.mark = 0;
 }
 
 // pt_scene_set_lights.  The light grids are those grids_on_device builds for the new lights (all or none), their parameters
@@ -2180,6 +2201,7 @@ struct WfFrame {
     const std::vector<uint32_t>* plan_last = nullptr;
     const uint32_t* block_empty = nullptr;     // the camera-grid cull table (nullptr: no cull in this frame)
     pt_scene::RngCache* rng_cache = nullptr;   // the scene's word cache, keyed to this frame's enumeration (nullptr: not in use)
+    pt_scene::HitCache* hit_cache = nullptr;   // the scene's camera-hit cache, keyed to this frame's view (nullptr: not in use)
     uint32_t stats_line = 0, chunk_slot = 0;   // the frame's progress through its chunks
 };
 
@@ -2460,6 +2482,52 @@ void rng_cache_frame(pt_scene& s, const Frame& f, WfFrame& wf, hipStream_t strea
     if (rc.recorded && rc.fill_stream != stream) HIP_CHECK(hipStreamWaitEvent(stream, rc.ev_fill, 0));
 }
 
+// The scene's camera-hit cache and this frame (pt_scene::HitCache), after rng_cache_frame.  The key is the word cache's -
+// the enumeration - plus the camera generation and the camera grid's resolution (a new light COUNT may rebuild the grid at
+// another resolution, and with it the cull table that decides which wavefronts store): the cache is keyed to a view when a
+// frame of that view directly follows another, so the first frame of a view never stores, a camera path never stores and
+// never allocates.  Eligible: opaque, uninstrumented frames of the fused pipeline that read the word cache; any other
+// frame leaves the records alone - those of a scene that turned translucent are still the opaque cast's for that camera.
+// PT_HIT_CACHE=0: off; PT_HIT_CACHE_GIB: the budget (8) - both read per frame.
+void hit_cache_frame(pt_scene& s, const Frame& f, WfFrame& wf, hipStream_t stream) {
+    pt_scene::HitCache& hc = s.hit_cache;
+    const std::vector<uint64_t> key = {f.p.width, f.p.height, f.p.samples, f.o.shard_rank, f.o.shard_count, f.o.tile_w, f.o.tile_h,
+                                       (uint64_t)f.env.morton, f.batch, s.camera_generation, s.cam_res};
+    const bool follows_same = key == hc.last_key;
+    hc.last_key = key;
+    const double gib = env_num(getenv("PT_HIT_CACHE_GIB"), 8.0);
+    if (!env_bool(getenv("PT_HIT_CACHE"), true) || !(gib > 0.0)) {
+        if (hc.buf.p) {
+            HIP_CHECK(hipDeviceSynchronize());   // (frames in flight may still read the plane)
+            hc.buf.release();
+        }
+        hc.key.clear();
+        hc.items = hc.stride = hc.mark = 0;
+        return;
+    }
+    if (hc.failed || !wf.rng_cache || !f.bounce0_fused || f.alpha || f.counting) return;
+    const uint64_t items = (uint64_t)f.blocks64 * 64u * f.p.samples;
+    const uint64_t stride = std::min<uint64_t>(items, (uint64_t)(gib * 1073741824.0) / 16u) & ~63ull;
+    if (key != hc.key || stride != hc.stride) {
+        if (!follows_same || stride == 0) return;
+        HIP_CHECK(hipDeviceSynchronize());   // the frames in flight finish with the old records
+        if (hc.buf.bytes < stride * 16u || hc.buf.bytes > stride * 16u + (64u << 20)) hc.buf.release();
+        hc.key.clear();
+        hc.items = hc.stride = hc.mark = 0;
+        if (!hc.buf.try_ensure((size_t)stride * 16u)) {
+            hc.failed = true;
+            return;
+        }
+        if (!hc.ev_store) HIP_CHECK(hipEventCreateWithFlags(&hc.ev_store, hipEventDisableTiming));
+        hc.key = key;
+        hc.items = items;
+        hc.stride = stride;
+    }
+    wf.hit_cache = &hc;
+    // a frame on another stream than the one that stored last waits for that launch (as the word cache's fill)
+    if (hc.recorded && hc.store_stream != stream) HIP_CHECK(hipStreamWaitEvent(stream, hc.ev_store, 0));
+}
+
 // This frame's counts, one line per (batch, chunk): taken every frame (a few KB) - the first frame's feed the plan, the
 // later ones only say whether a queue ran full.  None while an earlier frame's line is still on its way.
 void stats_slots(pt_scene& s, const Frame& f, WfFrame& wf) {
@@ -2571,6 +2639,10 @@ struct Chunk {
     // 3: the kernel computes the ChaCha block itself), 1 = shadow casts inside the shade kernel, 0 = none
     int grid_mode = 0;
     bool cached = false;   // the chunk's words are in the scene's word cache (rng_planes points there): GRID 3 reads them
+    // the scene's camera-hit cache (cached chunks only): 16 - the bounce-0 kernel stores the chunk's camera hits at hit_plane,
+    // 32 - it loads them instead of casting, 0 - neither
+    int hit_mode = 0;
+    uint4* hit_plane = nullptr;
     float4 *q_in = nullptr, *q_out = nullptr;
     bool split_shade = false;   // the shade pass in two launches (PT_WF_SPLIT)
 };
@@ -2686,7 +2758,24 @@ void shade_stage(pt_scene& s, const Frame& f, const WfFrame& wf, const Chunk& c,
         else dispatch(go, f.alpha, f.counting, c.prim);
         HIP_CHECK(hipGetLastError());
     };
+    // the cached opaque bounce-0 kernel with the camera-hit cache (k_wf_shade_hits): stores the chunk's hits or loads them
+    auto launch_hits = [&](auto grid) {
+        constexpr int G = decltype(grid)::value;
+        hipLaunchKernelGGL((k_wf_shade_hits<G>), dim3(shade_grid), dim3(WF_SHADE_THREADS), 0, c.st_main, f.dev, W, f.d_tiles,
+                           (const uint4*)c.rng_planes, c.hit_plane, c.q_out, (float4*)pipe.shadow.p, (float4*)pipe.contrib.p,
+                           (float*)s.staging_buf.p, (uint32_t*)pipe.exact[(b + 1) & 1].p, block_empty, c.wctr);
+        HIP_CHECK(hipGetLastError());
+    };
     auto launch_shade = [&] {
+        if (c.grid_mode == 3 && c.cached && c.hit_mode) {
+            switch ((s.grids.ortho ? 15 : 11) | c.hit_mode) {
+            case 11 | 16: launch_hits(std::integral_constant<int, (11 | 16)>{}); break;
+            case 11 | 32: launch_hits(std::integral_constant<int, (11 | 32)>{}); break;
+            case 15 | 16: launch_hits(std::integral_constant<int, (15 | 16)>{}); break;
+            default: launch_hits(std::integral_constant<int, (15 | 32)>{}); break;
+            }
+            return;
+        }
         switch (c.grid_mode == 0 ? 0 : c.grid_mode + (s.grids.ortho ? 4 : 0) + ((c.grid_mode == 3 && c.cached) ? 8 : 0)) {
         case 0: launch(std::integral_constant<int, 0>{}); break;
         case 1: launch(std::integral_constant<int, 1>{}); break;
@@ -2823,6 +2912,15 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
             W.rng_first_plane = 0u;
         }
     }
+    if (c.cached && wf.hit_cache) {
+        // The camera-hit cache, the same prefix in g: a chunk wholly below the mark loads its hits, the chunk next above the
+        // mark - if the budget has room for all of it - stores them; anything else casts as before.
+        pt_scene::HitCache& hc = *wf.hit_cache;
+        const uint64_t g0 = (uint64_t)(P.sample_begin / f.batch) * wf.items_per_batch + base, g1 = g0 + W.n_items;
+        if (g1 <= hc.mark) c.hit_mode = 32;
+        else if (g1 <= hc.stride && g0 <= hc.mark) c.hit_mode = 16;
+        if (c.hit_mode) c.hit_plane = (uint4*)hc.buf.p + g0;
+    }
     if (fused_rng && !c.cached && pipe.rng[0].bytes < (size_t)wf.cap * 16u) {   // (queue_buffers left the plane out)
         s.pipe.rng[0].ensure((size_t)wf.cap * 16u);
         c.rng_planes = (uint4*)pipe.rng[0].p;
@@ -2875,6 +2973,16 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
         c.split_shade = false;
         if (c.grid_mode < 2) trace_stage(s, f, c, tl);   // (grid_mode >= 2: k_wf_shade casts the camera rays itself)
         shade_stage(s, f, wf, c, tl);
+        if (c.prim && c.hit_mode == 16) {   // the records are behind this launch: the prefix grows by the chunk
+            pt_scene::HitCache& hc = *wf.hit_cache;
+            HIP_CHECK(hipEventRecord(hc.ev_store, c.st_main));
+            hc.recorded = true;
+            hc.store_stream = c.st_main;
+            hc.mark = (uint64_t)(c.hit_plane - (uint4*)hc.buf.p) + W.n_items;
+            ++hc.stores;
+        } else if (c.prim && c.hit_mode == 32) {
+            ++wf.hit_cache->loads;
+        }
         shadow_stage(s, f, c, tl);
     }
     // the next chunk clears the counters and reuses the queues, accumulate reads the staging area:
@@ -2990,6 +3098,7 @@ void render_device(pt_scene& s, const pt_profile& p, const pt_opts* opts_in, voi
         const QueueEnv qe = queue_env();
         wf = frame_plan(s, f, qe);
         rng_cache_frame(s, f, wf, stream);
+        hit_cache_frame(s, f, wf, stream);
         queue_buffers(s, f, qe, wf);
         stats_slots(s, f, wf);
         side_streams(s, f, wf);
@@ -3880,12 +3989,26 @@ int pt_get_rng_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* ite
     *fills = rc.fills;
     return PT_OK;
 }
+int pt_get_hit_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* stores, uint64_t* loads) {
+    if (!scene || !bytes || !items || !items_cached || !stores || !loads) return PT_ERR_INVALID;
+    const pt_scene::HitCache& hc = scene->hit_cache;
+    *bytes = hc.buf.bytes;
+    *items = hc.items;
+    *items_cached = hc.mark;
+    *stores = hc.stores;
+    *loads = hc.loads;
+    return PT_OK;
+}
 int pt_kernel_occupancy(int device, int which, int* blocks_per_cu) {
     return guarded([&] {
-        if (!blocks_per_cu || which < 0 || which > 1) fail(PT_ERR_INVALID, "pt_kernel_occupancy: bad argument");
+        if (!blocks_per_cu || which < 0 || which > 3) fail(PT_ERR_INVALID, "pt_kernel_occupancy: bad argument");
         HIP_CHECK(hipSetDevice(device));
         if (which == 0)
             HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_wf_shade<false, false, true, 3>, WF_SHADE_THREADS, 0));
+        else if (which == 2)
+            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_wf_shade_hits<(11 | 16)>, WF_SHADE_THREADS, 0));
+        else if (which == 3)
+            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_wf_shade_hits<(11 | 32)>, WF_SHADE_THREADS, 0));
         else
             HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_wf_shade<false, false, true, 11>, WF_SHADE_THREADS, 0));
     });

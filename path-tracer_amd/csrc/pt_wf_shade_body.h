@@ -1,0 +1,552 @@
+// The body of k_wf_shade and of k_wf_shade_hits (pt_wavefront.h), included inside both kernels: a function the two call would
+// be the plainer form, but inlined it compiles the existing variants to other code than the kernel's own text does (scratch
+// of eight variants moved by 4-8 B; profiles/r09_experiments.txt item 0), and those variants are tuned to the byte.
+// In scope: the template parameters ALPHA, COUNT, PRIMARY, GRIDX (as constants in k_wf_shade_hits) and the kernel's
+// parameters - S, W, tile_offsets, queue_in, hits, rng_planes, draws, queue_out, shadow_q, contrib, staging, index_list,
+// exact_list, chunk_hits, exact_next, block_empty, ctr, gctr - and hit_plane.
+    // index_list (bounces >= 1): null - the whole queue, entries marked WF_HIT_PENDING left out; else the entries to shade:
+    // the hand-over list of k_wf_trace, whose casts k_wf_trace_wide has finished by now - `hits` is then that list's
+    // own plane (W.list_cap records, by list position).  The pass over the queue runs WHILE k_wf_trace_wide walks
+    // those few long casts (WF_WIDE_LANES = 32 lanes each, a launch bound by its longest cast).  Behind that list, in the same launch, the
+    // exact list (k_wf_trace_exact, pt_wavefront.h wf_exact_words): word by list position, the rest of the hit in the chunk's
+    // own plane (chunk_hits) at the queue index.  exact_next: the exact list of the NEXT bounce - a survivor whose new ray the
+    // wavefront walker will not take (slack_is_capped) is listed here, where the ray is made, so that k_wf_trace_exact can
+    // walk it while k_wf_trace is busy with the rest of the queue.
+    constexpr int GRID = GRIDX & 3;
+    constexpr bool DIRL = (GRIDX & 4) != 0;
+    constexpr bool CACHED = (GRIDX & 8) != 0;
+    constexpr bool STORE = (GRIDX & 16) != 0, LOAD = (GRIDX & 32) != 0;
+    static_assert(GRIDX != 4, "DIRL needs a grid mode");
+    static_assert(!(STORE || LOAD) || (CACHED && !ALPHA && !COUNT && PRIMARY), "the camera-hit cache serves the cached opaque bounce-0 kernel");
+    static_assert(!(STORE && LOAD), "a launch stores the camera hits or loads them");
+    static_assert(!CACHED || (GRID == 3 && !COUNT), "the word cache serves the fused bounce-0 kernel");
+    uint4* rng_planes_out = const_cast<uint4*>(rng_planes);   // GRID == 3 writes plane 1 (nobody reads it before bounce 1)
+    static_assert(GRID < 2 || PRIMARY, "the camera grid serves bounce 0");
+    const bool list_pass = !PRIMARY && index_list != nullptr;
+    const uint32_t n_def = list_pass ? ctr[W.bounce].deferred_count : 0u;
+    const uint32_t n = PRIMARY ? W.n_items : list_pass ? n_def + (exact_list ? min(ctr[W.bounce].exact_count, W.ecap) : 0u) : min(ctr[W.bounce].queue_count, W.qcap_in);
+    // entry e of this launch: its queue record, the word of its hit, the hit
+    auto entry_index = [&](uint32_t e) -> uint32_t { return !list_pass ? e : e < n_def ? index_list[e] : exact_list[e - n_def]; };
+    auto entry_word = [&](uint32_t e) -> uint32_t {
+        return (!list_pass || e < n_def) ? wf_hit_word(hits, e) : wf_exact_words(exact_list, W.ecap)[e - n_def];
+    };
+    auto entry_hit = [&](uint32_t e, uint32_t i, RawHit& h) -> bool {
+        if (!list_pass) return wf_load_hit(hits, W.hcap, e, h);
+        if (e < n_def) return wf_load_hit(hits, W.list_cap, e, h);
+        const uint32_t x = wf_exact_words(exact_list, W.ecap)[e - n_def];
+        if (x == 0xffffffffu) return false;
+        const uint4 k = ((const uint4*)((const uint32_t*)chunk_hits + W.hcap))[i];
+        return unpack_hit(make_uint4(x, k.x, k.y, k.z), h);
+    };
+    uint32_t n_draws = 0, n_new = 0, n_moot = 0, n_hits = 0, n_cam_tris = 0, n_masked = 0;
+    LocalCtr lc = {0, 0, 0, 0, 0, 0};   // (GRID: casts made here)
+    __shared__ uint32_t sh_cnt[2][WF_SHADE_THREADS / 64];
+    __shared__ uint32_t sh_base[2];
+    __shared__ uint32_t sh_oct[8][WF_SHADE_THREADS / 64], sh_oct_off[8][WF_SHADE_THREADS / 64];
+    const uint32_t wave = threadIdx.x >> 6;
+    // LDS parking (PARK: the cached opaque bounce-0 variant at four waves per SIMD): per-lane state that is cold across an
+    // inline shadow cast waits in LDS, slot-major (sh_park[slot][thread]: conflict-free dwords, every slot private to its
+    // thread - no barrier).  The accesses are volatile: a plain store would be forwarded to its load and the register kept.
+    constexpr bool PARK = CACHED && !ALPHA && WF_SHADE_PARK;
+    // (wf_opaque_arg reads S at offset 0 of the kernarg segment and W right behind it: the kernels below check that)
+    __shared__ uint32_t sh_park[PARK ? WF_PARK_SLOTS : 1][WF_SHADE_THREADS];
+    // (an LDS pointer by type: a volatile access through a generic pointer stays a flat access, one 64-bit address per slot)
+    volatile __attribute__((address_space(3))) uint32_t* const park = (volatile __attribute__((address_space(3))) uint32_t*)&sh_park[0][threadIdx.x];
+    auto park_u = [&](uint32_t slot, uint32_t v) { park[slot * WF_SHADE_THREADS] = v; };
+    auto park_f = [&](uint32_t slot, float v) { park[slot * WF_SHADE_THREADS] = __float_as_uint(v); };
+    auto park_3 = [&](uint32_t slot, f3 v) { park_f(slot, v.x), park_f(slot + 1u, v.y), park_f(slot + 2u, v.z); };
+    auto unpark_u = [&](uint32_t slot) -> uint32_t { return park[slot * WF_SHADE_THREADS]; };
+    auto unpark_f = [&](uint32_t slot) -> float { return __uint_as_float(park[slot * WF_SHADE_THREADS]); };
+    auto unpark_3 = [&](uint32_t slot) -> f3 { const float x = unpark_f(slot), y = unpark_f(slot + 1u); return mk3(x, y, unpark_f(slot + 2u)); };
+    // (Bounce 0 needs no hit aggregation like the later bounces' below: a wavefront is one 8x8 pixel block of one sample,
+    // so its camera rays hit or miss together - collecting the hits of 256 items in LDS and shading them 256 at a time left
+    // the instruction count and the 52 active lanes per instruction unchanged, profiles/r02_experiments.txt item 13.)
+    // One workgroup-wide step: thread t shades queue entry i (live = it has one).  Every thread of the workgroup
+    // calls this together: the compaction at the end has barriers.
+    // (PARK) The arguments again, read through a kernarg pointer made opaque inside the grid-stride loop: what is derived from
+    // them (float copies of scalars, item-decoding terms, addresses) can then not be hoisted out of that loop into vector
+    // registers that stay occupied - and spilled - through every cast; the fields are fetched by scalar loads where they are used.
+    auto scene_arg = [&]() -> const DevScene& { return PARK ? wf_opaque_arg<DevScene>(0u) : S; };
+    auto params_arg = [&]() -> const WfParams& { return PARK ? wf_opaque_arg<WfParams>(WF_ARG_OFFSET_W) : W; };
+    auto shade_one = [&](const uint32_t e, bool live) {   // e: position in the queue / in the lists
+    const DevScene& S = scene_arg();
+    const WfParams& W = params_arg();
+    const uint32_t i = (list_pass && live) ? entry_index(e) : e;
+    f3 o = mk3(0, 0, 0), d = mk3(0, 0, 1), thr = mk3(0, 0, 0), color = mk3(0, 0, 0);
+    uint32_t item = i, draw = 0, out_slot = 0;
+    RawHit h;
+    bool hit = false;
+    WfRng rng;
+    rng.block = 0xffffffffu;
+    uint32_t word2 = 0, word3 = 0;                      // GRID == 3: words 2 and 3 of the item's ChaCha block
+    uint4 later_words = make_uint4(0u, 0u, 0u, 0u);     //            words 4-7 (bounces 1 and 2; the alpha walk of bounce 0)
+    // rng.gen::<f32>() number idx (>= 2) of the path at bounce 0, GRID == 3: from the block in registers; beyond
+    // word 7 (more than three alpha draws) the block is derived again by wf_rng_draw
+    auto draw_b0 = [&](uint32_t idx) -> float {
+        if (idx >= (CACHED ? 4u : WF_RNG_STAGED)) return wf_rng_draw(rng, W, tile_offsets, rng_planes, item, idx);   // (CACHED: plane 1 of the cache)
+        uint32_t word = word2;
+        word = idx == 3u ? word3 : word;
+        word = idx == 4u ? later_words.x : word;
+        word = idx == 5u ? later_words.y : word;
+        word = idx == 6u ? later_words.z : word;
+        word = idx == 7u ? later_words.w : word;
+        return wf_rng_float(word);
+    };
+    // (LOAD) the item's camera hit: a dense load that depends on nothing - its latency runs under decode_item and the ray set-up
+    uint4 cam_rec = make_uint4(0xffffffffu, 0u, 0u, 0u);
+    if (LOAD && PRIMARY && live) cam_rec = hit_plane[i];
+    if (PRIMARY && live) {  // entry i is work item i: the initial path state, built in place
+        ItemRef it = decode_item(W.P, tile_offsets, W.item_base + i);
+        if (!it.valid) {
+            live = false;
+        } else {
+            thr = mk3(1.f, 1.f, 1.f);
+            color = mk3(0.f, 0.f, 0.f);
+            out_slot = (it.sample - 1u - W.P.sample_begin) * W.P.n_local + it.out_index;
+            if (GRID >= 2) {   // ray_cast + alpha walk of the camera ray (mod.rs:182-205) through the camera grid
+                if (GRID == 3 && CACHED) {   // the same words, made once per item enumeration: one dense 16-byte load
+                    const uint4 w03 = rng_planes[i];
+                    float sx, sy;
+                    primary_screen(S, it.x, it.y, W.P.width, W.P.height, wf_rng_float(w03.x), wf_rng_float(w03.y), sx, sy);
+                    primary_from_screen(S, sx, sy, o, d);
+                    word2 = w03.z;
+                    word3 = w03.w;
+                } else if (GRID == 3) {   // StdRng::seed_from_u64(sample + i * samples), jitter x then y (mod.rs:110-120)
+                    uint32_t w[16];
+                    pt_chacha12_block((uint64_t)it.sample + (uint64_t)it.global_index * (uint64_t)W.P.samples, 0u, w);
+                    float sx, sy;
+                    primary_screen(S, it.x, it.y, W.P.width, W.P.height, wf_rng_float(w[0]), wf_rng_float(w[1]), sx, sy);
+                    primary_from_screen(S, sx, sy, o, d);
+                    word2 = w[2];
+                    word3 = w[3];
+                    later_words = make_uint4(w[4], w[5], w[6], w[7]);
+                } else {
+                    const uint2 sc = *(const uint2*)(rng_planes + i);  // jittered screen position (k_wf_rng)
+                    primary_from_screen(S, __uint_as_float(sc.x), __uint_as_float(sc.y), o, d);
+                }
+                if (LOAD) {   // the cast's result as an earlier frame of this view stored it
+                    draw = 2u;
+                    hit = unpack_hit(cam_rec, h);
+                } else {
+                    const uint32_t cell = og_cell(S.cam_grid, d);
+                    const float dlen = mag3(d);
+                    const float kmax = (dlen > 1.0f ? dlen : 1.0f) * 1.00002f;
+                    draw = 2u;   // the pixel jitter
+                    if (COUNT) lc.segments++;
+                    const uint32_t tris_before = lc.tris;
+                    hit = og_next_hit<COUNT>(S, S.cam_grid, cell, o, d, kmax, INFINITY, -INFINITY, 0u, h, lc);
+                    if (STORE) hit_plane[i] = pack_hit(h, hit);
+                    if (ALPHA) {
+                        RawHit kept = h;
+                        bool have_kept = false;
+                        while (hit) {
+                            const float opacity = hit_opacity(S, o, d, h);
+                            if (COUNT) lc.shaded++;
+                            bool stop = opacity >= 1.f;
+                            if (!stop && opacity > 0.001f)
+                                stop = (GRID == 3 ? draw_b0(draw++) : wf_rng_draw(rng, W, tile_offsets, rng_planes, item, draw++)) < opacity;
+                            if (stop) break;
+                            kept = h;   // skipped: remember it, look for the next entry of the list
+                            have_kept = true;
+                            if (COUNT) lc.restarts++;
+                            hit = og_next_hit<COUNT>(S, S.cam_grid, cell, o, d, kmax, INFINITY, kept.key, kept.ord, h, lc);
+                        }
+                        if (!hit && have_kept) {   // every hit skipped: the last one is shaded
+                            h = kept;
+                            hit = true;
+                        }
+                    }
+                    if (COUNT) n_cam_tris += lc.tris - tris_before;
+                }
+            } else {
+                draw = ALPHA ? draws[i] : 2u;   // 2 = the pixel jitter (+ the draws of the alpha walk)
+                hit = wf_load_hit(hits, W.hcap, i, h);
+                if (hit) {  // (a missed cast only adds the background: no ray, no normalisation)
+                    const uint2 sc = *(const uint2*)(rng_planes + i);  // jittered screen position (k_wf_rng)
+                    primary_from_screen(S, __uint_as_float(sc.x), __uint_as_float(sc.y), o, d);
+                }
+            }
+            if (COUNT) n_new++;
+        }
+    }
+    if (!PRIMARY && live) {
+        const float4* qr = wf_ray_rec(queue_in, i);
+        const float4* qp = wf_path_rec(queue_in, W.qcap_in, i);
+        float4 q0 = qr[0], q1 = qr[1], q2 = qp[0], q3 = qp[1];
+        o = mk3(q0.x, q0.y, q0.z);
+        d = mk3(q0.w, q1.x, q1.y);
+        thr = mk3(q2.x, q2.y, q2.z);
+        color = mk3(q3.x, q3.y, q3.z);
+        item = __float_as_uint(q1.z);
+        draw = ALPHA ? draws[i] : (__float_as_uint(q1.w) & 0xffffu);
+        out_slot = __float_as_uint(q2.w);
+        hit = entry_hit(e, i, h);
+        if (out_slot == 0xffffffffu) live = false;  // (records of items outside the image; none since bounce 0 is fused)
+    }
+    const uint32_t bounce = PRIMARY ? 0u : W.bounce, bounces = W.P.bounces;   // (PRIMARY: no Russian roulette code at all)
+    bool to_shadow = false, survive = false;
+    f3 term0 = mk3(0.f, 0.f, 0.f);
+    Surface surf;
+    f3 next_o = o, next_d = d, next_thr = thr;
+    // background (mod.rs:184-186): the path ends here.  Bounce 0 only: a miss of a later bounce never gets here - its
+    // result was staged by the kernel that finished the record's colour (wf_prestage_miss)
+    if (PRIMARY && live && !hit) {
+        color = color + mul_ew(thr, ld3(S.background));
+        float* out = staging + (size_t)out_slot * 3;
+        out[0] = color.x;
+        out[1] = color.y;
+        out[2] = color.z;
+    }
+    Brdf brdf;
+    f3 normal = mk3(0, 0, 0), view = mk3(0, 0, 0);
+    if (live && hit) {
+        if (COUNT) n_hits++;
+        make_surface(S, o, d, h, surf);
+        MatSample ms;
+        material_sample(S, surf.model, surf.sphere, surf.uv, ms);
+        normal = shading_normal(S, surf);
+        if (COUNT && !ALPHA) atomicAdd(&gctr->shaded_hits, 1ull);
+        view = -1.f * d;
+        ct_init(brdf, ms);
+        color = color + mul_ew(thr, ms.emissive);
+        // (thr ⊙ eval_direct) per light.  GRID: the light's visibility is looked up here and the light added at
+        // once, in light order (mod.rs:248-262).  Otherwise (and for a normal too long for the grids' margin) the
+        // visibility factor is applied by the shadow kernel: the first light's term stays in registers, the others
+        // are recomputed when the record is written.
+        const bool inline_lights = GRID != 0 && dot3(surf.normal, surf.normal) <= S.light_grid_max_normal2;
+        // (PARK) what no cast changes is parked once, what a light changes right before its cast; all of it comes back after
+        auto park_fixed = [&] {
+            park_f(PK_BRDF, brdf.metalness), park_f(PK_BRDF + 1u, brdf.roughness);
+            park_3(PK_BRDF + 2u, brdf.albedo), park_3(PK_BRDF + 5u, brdf.emissive), park_3(PK_BRDF + 8u, brdf.f0);
+            park_3(PK_NORMAL, normal), park_3(PK_VIEW, view);
+            park_f(PK_UV, surf.uv.x), park_f(PK_UV + 1u, surf.uv.y);
+            park_u(PK_PID, h.pid), park_u(PK_OUT_SLOT, out_slot), park_u(PK_WORD2, word2), park_u(PK_WORD2 + 1u, word3);
+        };
+        auto unpark_fixed = [&] {
+            brdf.metalness = unpark_f(PK_BRDF), brdf.roughness = unpark_f(PK_BRDF + 1u);
+            brdf.albedo = unpark_3(PK_BRDF + 2u), brdf.emissive = unpark_3(PK_BRDF + 5u), brdf.f0 = unpark_3(PK_BRDF + 8u);
+            normal = unpark_3(PK_NORMAL), view = unpark_3(PK_VIEW);
+            surf.uv.x = unpark_f(PK_UV), surf.uv.y = unpark_f(PK_UV + 1u);
+            h.pid = unpark_u(PK_PID), out_slot = unpark_u(PK_OUT_SLOT), word2 = unpark_u(PK_WORD2), word3 = unpark_u(PK_WORD2 + 1u);
+        };
+        if (PARK) park_fixed();
+        for (uint32_t li = 0; li < S.n_lights; ++li) {
+            const DevLight& L = S.lights[li];
+            f3 ldir = L.kind == PT_LIGHT_POINT ? normalize3(surf.pos - ld3(L.vec)) : ld3(L.vec);
+            f3 c = mul_ew(thr, ct_eval_direct(brdf, normal, view, -1.f * ldir));
+            if (li == 0) term0 = c;
+            const bool moot = wf_light_is_moot(L, c, surf.pos);
+            if (GRID != 0 && inline_lights) {
+                if (moot) {
+                    if (COUNT) n_moot++;
+                } else {
+                    if (PARK) park_3(PK_C, c), park_3(PK_COLOR, color), park_3(PK_TERM0, term0);
+                    const f3 rad = og_light_radiance<ALPHA, COUNT, DIRL>(S, li, surf.pos, surf.normal, surf.uv, surf.sphere, lc);
+                    if (PARK) {
+                        c = unpark_3(PK_C), color = unpark_3(PK_COLOR), term0 = unpark_3(PK_TERM0);
+                        unpark_fixed();
+                    }
+                    if (!(rad.x == 0.f && rad.y == 0.f && rad.z == 0.f)) color = color + mul_ew(c, rad);
+                }
+            } else if (!moot) {
+                to_shadow = true;
+            }
+        }
+        if (COUNT && !inline_lights && !to_shadow) n_moot += S.n_lights;
+        bool ended = false;
+        if (bounce < bounces) {
+            next_o = surf.pos + surf.normal * 0.00001f;
+            float r1, r2;
+            if (GRID == 3 && ALPHA) {
+                r1 = draw_b0(draw++);
+                r2 = draw_b0(draw++);
+            } else if (GRID == 3) {
+                r1 = wf_rng_float(word2);
+                r2 = wf_rng_float(word3);
+                draw += 2u;
+            } else if (PRIMARY && !ALPHA) {   // draws 2 and 3 of the item: staged next to the screen position (k_wf_rng)
+                const uint2 w23 = *(const uint2*)((const uint32_t*)(rng_planes + item) + 2);
+                r1 = wf_rng_float(w23.x);
+                r2 = wf_rng_float(w23.y);
+                draw += 2u;
+            } else {
+                r1 = wf_rng_draw(rng, W, tile_offsets, rng_planes, item, draw++);
+                r2 = wf_rng_draw(rng, W, tile_offsets, rng_planes, item, draw++);
+            }
+            next_d = ct_sample(brdf, normal, view, r1, r2);
+            f3 wgt = ct_eval_indirect(brdf, normal, view, next_d) / 1.0f;
+            next_thr = mul_ew(thr, wgt);
+        }
+        if (dot3(next_thr, next_thr) < 0.00001f) ended = true;
+        if (!ended && bounce > 3) {
+            float p = max_rs(max_rs(next_thr.x, next_thr.y), next_thr.z);
+            next_thr = next_thr * (1.f / p);
+            if (wf_rng_draw(rng, W, tile_offsets, rng_planes, item, draw++) > p) ended = true;
+        }
+        survive = !ended && bounce + 1 <= bounces;
+        // Escape mask of the primitive the ray leaves (pt_escape.h): a clear bit proves that the next ray_cast is empty, i.e.
+        // that the path ends with `colour + throughput x background` (mod.rs:184-186) - no record, no cast.  The background
+        // term must be added AFTER this bounce's lights (mod.rs:248-262 come first): here if the lights are added here
+        // (inline) or none can contribute; through the shadow queue only if the term is exactly zero (a black background).
+        if (survive && S.escape != nullptr && !surf.sphere && escape_proves_miss(S, PT_PRIM_INDEX(h.pid), next_o, next_d)) {
+            const f3 bg = mul_ew(next_thr, ld3(S.background));
+            const bool zero = bg.x == 0.f && bg.y == 0.f && bg.z == 0.f;
+            if (zero || !to_shadow) {
+                if (!zero) color = color + bg;
+                survive = false;
+                if (COUNT) n_masked++;
+            }
+        }
+    }
+    // ---- compaction: survivors -> queue[b+1], surface hits -> shadow queue.  One atomic per
+    // workgroup and queue (wave ballots -> LDS -> one lane), not one per wavefront: the counter
+    // word would otherwise cap the kernel at ~88 M wave-atomics per second.
+    // Coherence sorting (W.sort_octants): the survivors of a workgroup step - paths that started in the same few
+    // 8x8 pixel blocks - are placed in the workgroup's slice of the queue by the OCTANT of their new direction
+    // (ballot per octant, mbcnt rank, prefix over octants and waves in LDS), so that the 64 consecutive records a
+    // wavefront of the next k_wf_trace launch fetches walk the tree in the same child order.  The position of a
+    // record in a queue is free (results are keyed by out_slot), so no bit of the image changes.
+    unsigned long long m_next = __ballot(survive), m_sh = __ballot(to_shadow);
+    uint32_t oct = 0, oct_rank = 0;
+    if (W.sort_octants & 1u) {
+        oct = (next_d.x < 0.f ? 1u : 0u) | (next_d.y < 0.f ? 2u : 0u) | (next_d.z < 0.f ? 4u : 0u);
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; ++k) {
+            const unsigned long long m = __ballot(survive && oct == k);
+            if ((threadIdx.x & 63u) == 0) sh_oct[k][wave] = (uint32_t)__popcll(m);
+            if (oct == k) oct_rank = wf_lane_rank(m);
+        }
+    }
+    if ((threadIdx.x & 63u) == 0) {
+        sh_cnt[0][wave] = (uint32_t)__popcll(m_next);
+        sh_cnt[1][wave] = (uint32_t)__popcll(m_sh);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        uint32_t total = 0;
+        for (uint32_t k = 0; k < WF_SHADE_THREADS / 64; ++k) total += sh_cnt[threadIdx.x][k];
+        uint32_t* counter = threadIdx.x == 0 ? &ctr[bounce + 1].queue_count : &ctr[bounce].shadow_count;
+        sh_base[threadIdx.x] = total ? atomicAdd(counter, total) : 0u;
+    } else if ((W.sort_octants & 1u) && threadIdx.x >= 64u && threadIdx.x < 64u + 8u * (WF_SHADE_THREADS / 64)) {
+        // exclusive prefix of the (octant, wave) counts, octant-major
+        const uint32_t e = threadIdx.x - 64u;
+        uint32_t before = 0;
+        for (uint32_t j = 0; j < e; ++j) before += sh_oct[j / (WF_SHADE_THREADS / 64)][j % (WF_SHADE_THREADS / 64)];
+        sh_oct_off[e / (WF_SHADE_THREADS / 64)][e % (WF_SHADE_THREADS / 64)] = before;
+    }
+    __syncthreads();
+    uint32_t next_idx = sh_base[0] + wf_lane_rank(m_next), sh_idx = sh_base[1] + wf_lane_rank(m_sh);
+    for (uint32_t k = 0; k < wave; ++k) {
+        next_idx += sh_cnt[0][k];
+        sh_idx += sh_cnt[1][k];
+    }
+    if (W.sort_octants & 1u) next_idx = sh_base[0] + sh_oct_off[oct][wave] + oct_rank;
+    __syncthreads();  // sh_cnt / sh_base are rewritten by the next step
+    // (the queues are sized by the records this very frame is known to produce, pt_gpu.hip FramePlan: a record beyond its
+    // queue's end means that knowledge was wrong - nothing is written, the frame is flagged and rendered again with room)
+    if ((survive && next_idx >= W.qcap_out) || (to_shadow && sh_idx >= W.scap)) {
+        ctr[0].overflow = 1u;
+        survive = false;
+        to_shadow = false;
+    }
+    if (GRID == 3 && !CACHED && survive) rng_planes_out[(size_t)(1u - W.rng_first_plane) * W.cap + item] = later_words;   // draws 4-7 of the path
+    if (W.exact_shade_lists) {   // (wave-uniform; 0.24 % of random directions)
+        const bool listed = survive && slack_is_capped(__builtin_amdgcn_rcpf(next_d.x), __builtin_amdgcn_rcpf(next_d.y), __builtin_amdgcn_rcpf(next_d.z));
+        if (wf_any(listed)) {
+            const uint32_t slot = wf_reserve(&ctr[bounce + 1].exact_count, listed);
+            if (listed && slot < W.ecap) exact_next[slot] = next_idx;
+            else if (listed) ctr[0].overflow = 1u;
+        }
+    }
+    if (survive) {
+        float4* qr = wf_ray_rec(queue_out, next_idx);
+        float4* qp = wf_path_rec(queue_out, W.qcap_out, next_idx);
+        qr[0] = make_float4(next_o.x, next_o.y, next_o.z, next_d.x);
+        qr[1] = make_float4(next_d.y, next_d.z, __uint_as_float(item), __uint_as_float((draw & 0xffffu) | ((bounce + 1) << 16)));
+        qp[0] = make_float4(next_thr.x, next_thr.y, next_thr.z, __uint_as_float(out_slot));
+        qp[1] = make_float4(color.x, color.y, color.z, 0.f);  // colour is patched by the shadow kernels
+        // ... and where none will (lights added inline, or none can contribute) it is final here: stage the path's result
+        // for the case that its next cast misses
+        if (!to_shadow) wf_prestage_miss(staging, out_slot, color, next_thr, ld3(S.background));
+        if (W.use_entry) wf_entry_plane(queue_out, W.qcap_out)[next_idx] = S.prim_entry[PT_PRIM_INDEX(h.pid)];
+    }
+    if (to_shadow) {
+        float4* sq = shadow_q + (size_t)sh_idx * 4;
+        sq[0] = make_float4(surf.pos.x, surf.pos.y, surf.pos.z, surf.normal.x);
+        sq[1] = make_float4(surf.normal.y, surf.normal.z, surf.uv.x, surf.uv.y);
+        sq[2] = make_float4(color.x, color.y, color.z, __uint_as_float(survive ? next_idx : 0xffffffffu));
+        sq[3] = make_float4(__uint_as_float(out_slot), __uint_as_float(surf.sphere ? WF_FLAG_SPHERE : 0u), 0.f, 0.f);
+        contrib[sh_idx] = make_float4(term0.x, term0.y, term0.z, 0.f);
+        for (uint32_t li = 1; li < S.n_lights; ++li) {
+            // (PARK: one light per trip - two at a time in packed f32 made this rarely taken loop the kernel's register peak.
+            // An empty asm, not `#pragma clang loop vectorize(disable)`: a pragma cannot depend on PARK, and on the one loop
+            // all variants share it changes the code of every other variant; tests/test_bounce0_four_waves.py holds the
+            // register count should a compiler stop honouring it.)
+            if (PARK) asm volatile("");
+            const DevLight& L = S.lights[li];
+            f3 ldir = L.kind == PT_LIGHT_POINT ? normalize3(surf.pos - ld3(L.vec)) : ld3(L.vec);
+            f3 c = mul_ew(thr, ct_eval_direct(brdf, normal, view, -1.f * ldir));
+            contrib[(size_t)li * W.scap + sh_idx] = make_float4(c.x, c.y, c.z, 0.f);
+        }
+    } else if (live && hit && !survive) {  // no light can contribute and the path ends: the sample is complete
+        float* out = staging + (size_t)out_slot * 3;
+        out[0] = color.x;
+        out[1] = color.y;
+        out[2] = color.z;
+    }
+    // draws made HERE (the alpha walk counts its own): since the value this kernel started from, plus the jitter
+    if (COUNT && live)
+        n_draws += GRID >= 2 ? draw
+                             : draw - (ALPHA ? draws[i] : PRIMARY ? 0u : (__float_as_uint(wf_ray_rec(queue_in, i)[1].w) & 0xffffu)) +
+                                   ((ALPHA && PRIMARY) ? 2u : 0u);
+    };  // shade_one
+    if (PRIMARY || !WF_SHADE_AGGREGATE) {
+        // grid-stride over the queue, one workgroup-wide step at a time (the loop bound is uniform in the workgroup)
+        // Camera-grid cull (k_cam_block_mask): no camera ray of an EMPTY 8x8 pixel block can hit anything, so its samples
+        // are the background - no ChaCha block, no cast (the instrumented variant counts them the long way).  A wavefront
+        // is one block of one sample; chunks and queues are whole wavefronts.  Nothing is staged for them: k_accumulate
+        // adds the background for the pixels of an empty block itself, once per sample.
+        // (word W.n_mask_blocks of the table: non-zero if any block is empty - a frame without one pays nothing here)
+        const bool cull = PRIMARY && GRID >= 2 && !COUNT && block_empty != nullptr && block_empty[W.n_mask_blocks] != 0u;
+        for (uint32_t base = blockIdx.x * WF_SHADE_THREADS; base < n; base += gridDim.x * WF_SHADE_THREADS) {
+            const uint32_t e = base + threadIdx.x;
+            bool live = e < n;
+            if (!PRIMARY && live) {   // bounces >= 1: the hits only (a miss was staged when its record's colour became final)
+                const uint32_t word = entry_word(e);
+                live = word != WF_HIT_PENDING && word != 0xffffffffu;
+            }
+            if (cull) {   // a step whose four wavefronts are all empty skips the compaction's barriers as well
+                const uint32_t g0 = (W.item_base + base) >> 6;
+                bool step_empty = true;
+#pragma unroll
+                for (uint32_t k = 0; k < WF_SHADE_THREADS / 64; ++k) {
+                    const bool em = base + 64u * k >= n || block_empty[pt_fastdiv(g0 + k, W.P.div_batch)] != 0u;
+                    step_empty = step_empty && em;
+                    live = (k == wave && em) ? false : live;
+                }
+                if (step_empty) continue;   // (the same answer in every thread of the workgroup)
+            }
+            shade_one(e, live);
+        }
+    } else {
+        // Hit aggregation (bounces >= 1).  Three of four secondary rays of an open scene leave into the background:
+        // shaded in queue order, 23 % of the lanes would carry the material fetch, the BRDF and the GGX sample while
+        // the others wait (27.7 of 64 lanes active per vector instruction, profiles/r02_a_pmc.json).  So a first
+        // pass over a step's 256 entries reads the hit words only and collects the indices of the hits in LDS; whenever
+        // 256 are waiting - or the queue has ended - they are shaded together.  A miss costs its 4-byte word and nothing
+        // else: its result (background term, mod.rs:184-186) was staged when the record's colour became final
+        // (wf_prestage_miss).  The order in which paths are shaded is free (results are keyed by out_slot), so no bit
+        // changes.
+        // The pass over the queue sweeps WF_SHADE_SWEEP words per thread and step (one 16-byte load): the sweep is a chain of
+        // load -> ballots -> barrier -> LDS -> barrier per step, and a step of 256 words finds ~90 hits.  The lists of the second
+        // launch (scattered words, a few thousand entries) keep one word per thread.
+        __shared__ uint32_t agg[(1 + WF_SHADE_SWEEP) * WF_SHADE_THREADS];
+        __shared__ uint32_t agg_cnt[WF_SHADE_THREADS / 64];
+        const uint32_t per = list_pass ? 1u : (uint32_t)WF_SHADE_SWEEP;
+        uint32_t have = 0;   // waiting hits (the same value in every thread; at most 255 + 256 * WF_SHADE_SWEEP)
+        uint32_t base = blockIdx.x * WF_SHADE_THREADS * per;
+        while (true) {
+            while (have < WF_SHADE_THREADS && base < n) {
+                const uint32_t e0 = base + threadIdx.x * per;
+                base += gridDim.x * WF_SHADE_THREADS * per;
+                uint32_t word[WF_SHADE_SWEEP];
+#pragma unroll
+                for (uint32_t j = 0; j < WF_SHADE_SWEEP; ++j) word[j] = WF_HIT_PENDING;
+                static_assert(WF_SHADE_SWEEP == 4, "the sweep loads the words as one uint4");
+                if (!list_pass && e0 + WF_SHADE_SWEEP <= n) {   // (e0 is a multiple of four: one aligned load of the words' plane)
+                    const uint4 w4 = hits[e0 >> 2];
+                    word[0] = w4.x, word[1] = w4.y, word[2] = w4.z, word[3] = w4.w;
+                } else {
+                    for (uint32_t j = 0; j < per; ++j)
+                        if (e0 + j < n) word[j] = entry_word(e0 + j);
+                }
+                // (a miss: nothing to do, see above)  The hits keep their queue order - lane after lane, a lane's words in
+                // order -: the exclusive prefix of the lanes' hit counts (0..4) comes from one ballot per bit of the count.
+                // (Ranked word by word instead, neighbours in the queue land in different batches of 256: the frame lost
+                // what the pre-staged misses had gained, profiles/r05_experiments.txt item 3.)
+                uint32_t mine_n = 0;
+#pragma unroll
+                for (uint32_t j = 0; j < WF_SHADE_SWEEP; ++j) mine_n += (word[j] != WF_HIT_PENDING && word[j] != 0xffffffffu) ? 1u : 0u;
+                uint32_t before = 0, in_wave = 0;
+#pragma unroll
+                for (uint32_t b = 0; b < 3u; ++b) {
+                    const unsigned long long m = __ballot((mine_n >> b) & 1u);
+                    before += wf_lane_rank(m) << b;
+                    in_wave += (uint32_t)__popcll(m) << b;
+                }
+                if ((threadIdx.x & 63u) == 0) agg_cnt[wave] = in_wave;
+                __syncthreads();
+                uint32_t pos = have + before, total = 0;
+                for (uint32_t k = 0; k < WF_SHADE_THREADS / 64; ++k) {
+                    if (k < wave) pos += agg_cnt[k];
+                    total += agg_cnt[k];
+                }
+#pragma unroll
+                for (uint32_t j = 0; j < WF_SHADE_SWEEP; ++j)
+                    if (word[j] != WF_HIT_PENDING && word[j] != 0xffffffffu) agg[pos++] = e0 + j;
+                have += total;
+                __syncthreads();
+            }
+            if (have == 0) break;
+            const uint32_t take = have < WF_SHADE_THREADS ? have : (uint32_t)WF_SHADE_THREADS;
+            have -= take;
+            uint32_t mine = threadIdx.x < take ? agg[have + threadIdx.x] : 0u;
+            __syncthreads();
+            if (W.sort_octants & 2u) {
+                // Material sorting (measured option, PT_WF_SORT=2): the 256 hits of a step are ordered by the model -
+                // i.e. the material - of the primitive they hit (8 classes, stable counting sort: ballot per class,
+                // mbcnt rank, prefix over classes and waves in LDS), so that a wavefront shades one material's
+                // texture set.  The order in which paths are shaded is free: no bit changes.
+                __shared__ uint32_t agg_sorted[WF_SHADE_THREADS];
+                uint32_t key = 8u, rank = 0u;
+                if (threadIdx.x < take) {
+                    const uint32_t prim = entry_word(mine) & 0x0fffffffu;
+                    key = __float_as_uint(S.prim_attr[(size_t)prim * 4 + 3].w) & 7u;
+                }
+#pragma unroll
+                for (uint32_t k = 0; k < 8u; ++k) {
+                    const unsigned long long m = __ballot(key == k);
+                    if ((threadIdx.x & 63u) == 0) sh_oct[k][wave] = (uint32_t)__popcll(m);
+                    if (key == k) rank = wf_lane_rank(m);
+                }
+                __syncthreads();
+                if (threadIdx.x < 8u * (WF_SHADE_THREADS / 64)) {
+                    uint32_t before = 0;
+                    for (uint32_t j = 0; j < threadIdx.x; ++j) before += sh_oct[j / (WF_SHADE_THREADS / 64)][j % (WF_SHADE_THREADS / 64)];
+                    sh_oct_off[threadIdx.x / (WF_SHADE_THREADS / 64)][threadIdx.x % (WF_SHADE_THREADS / 64)] = before;
+                }
+                __syncthreads();
+                if (threadIdx.x < take) agg_sorted[sh_oct_off[key][wave] + rank] = mine;
+                __syncthreads();
+                mine = threadIdx.x < take ? agg_sorted[threadIdx.x] : 0u;
+                __syncthreads();
+            }
+            shade_one(mine, threadIdx.x < take);
+        }
+    }
+    if (COUNT && n_draws) atomicAdd(&gctr->rng_draws, (unsigned long long)n_draws);
+    if (COUNT && n_new) atomicAdd(&gctr->samples, (unsigned long long)n_new);
+    if (COUNT && n_moot) {
+        atomicAdd(&gctr->shadow_rays, (unsigned long long)n_moot);
+        atomicAdd(&gctr->shadow_skipped, (unsigned long long)n_moot);
+    }
+    if (COUNT && PRIMARY && n_hits) atomicAdd(&gctr->bounce0_hits, (unsigned long long)n_hits);
+    if (COUNT && n_masked) {   // (ray_cast calls the reference makes and this pipeline proves empty)
+        atomicAdd(&gctr->segments, (unsigned long long)n_masked);
+        atomicAdd(&gctr->masked_casts, (unsigned long long)n_masked);
+        if (PRIMARY) atomicAdd(&gctr->bounce0_masked, (unsigned long long)n_masked);
+    }
+    if (COUNT && GRID != 0) {
+        atomicAdd(&gctr->segments, (unsigned long long)lc.segments);
+        atomicAdd(&gctr->shadow_rays, (unsigned long long)lc.shadow_rays);
+        atomicAdd(&gctr->tris_tested, (unsigned long long)lc.tris);
+        atomicAdd(&gctr->grid_tris, (unsigned long long)lc.tris);
+        atomicAdd(&gctr->restarts, (unsigned long long)lc.restarts);
+        if (GRID >= 2) {
+            atomicAdd(&gctr->trace_tris, (unsigned long long)n_cam_tris);
+            atomicAdd(&gctr->bounce0_cam_tris, (unsigned long long)n_cam_tris);
+            atomicAdd(&gctr->bounce0_tris, (unsigned long long)lc.tris);
+            atomicAdd(&gctr->bounce0_shadow_rays, (unsigned long long)lc.shadow_rays);
+        }
+        if (ALPHA) atomicAdd(&gctr->shaded_hits, (unsigned long long)lc.shaded);
+    }

@@ -54,6 +54,8 @@ for _ in range(4):   # (first frames, escape masks, the plan of the scene camera
 steady = [frame() for _ in range(a.steady)]
 cams = make_orbit.orbit(host, a.moves + 1)[1:]
 set_ms, first_ms = [], []
+has_hits = hasattr(g.lib, "pt_get_hit_cache_stats")   # (an A/B library of an earlier commit, PT_GPU_LIB, has none)
+stores_before = g.hit_cache_stats()[3] if has_hits else None
 for cam in cams:
     torch.cuda.synchronize()
     t = time.perf_counter()
@@ -66,4 +68,6 @@ print(json.dumps({"tris": a.tris, "prims": int(info["n_prims"]), "image": f"{a.w
                   "set_camera_ms_median": round(statistics.median(set_ms), 2), "set_camera_ms": [round(v, 1) for v in set_ms],
                   "first_frame_after_move_ms_median": round(statistics.median(first_ms), 2),
                   "steady_planned_frame_ms_median": round(statistics.median(steady), 2),
-                  "cam_grid_res": int(info["cam_grid_res"])}))
+                  "cam_grid_res": int(info["cam_grid_res"]),
+                  # the camera-hit cache stores at a view's second frame: a camera path must never store
+                  "hit_cache_stores_during_moves": g.hit_cache_stats()[3] - stores_before if has_hits else None}))

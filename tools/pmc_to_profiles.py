@@ -36,6 +36,8 @@ for path in sorted(glob.glob(f"{src}/pass*/**/*counter_collection.csv", recursiv
             targs = k.split("<", 1)[1].split(">", 1)[0].split(",")
             if len(targs) >= 4 and int(targs[3]) >= 2:
                 name = "k_wf_shade<GRID=%d>" % int(targs[3])
+        if name == "k_wf_shade_hits":   # k_wf_shade_hits<GRIDX>: the storing and the loading variant are rows of their own
+            name = "k_wf_shade_hits<GRID=%d>" % int(k.split("<", 1)[1].split(">", 1)[0])
         acc[name][r["Counter_Name"]] += float(r["Counter_Value"])
         if r["Counter_Name"] == "FETCH_SIZE":
             fetch_of[name][r["Dispatch_Id"]] = fetch_of[name].get(r["Dispatch_Id"], 0.0) + float(r["Counter_Value"])

@@ -504,10 +504,22 @@ int pt_get_rng_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* ite
  * read per frame.  The bytes are not part of pt_scene_info's queue_bytes or device_bytes. */
 int pt_get_hit_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* stores,
                            uint64_t* loads);
+/* The scene's cache of bounce-0 shadow visibility (one byte per work item: two bits per light - unknown, not blocked,
+ * blocked; in an opaque scene that answer depends on the camera hit, the light's kind and position and the geometry -
+ * not on the materials, the light's colour or the bounce count - so the frames of material and light-colour edits and of
+ * a steady state read it instead of casting): its device bytes, the work items of the view and lights it is keyed to
+ * (0: none - it is keyed, and zeroed, when a frame directly follows another of the same view and light positions), how
+ * often it was zeroed, and the launches of the bounce-0 variant that reads it and fills in what is unknown, since the
+ * scene was made.  Only frames that load their camera hits, of scenes with one to four lights, use it; a moved light or
+ * camera re-keys it (the allocation stays), a light orbit or camera path never zeroes and never allocates.
+ * PT_VIS_CACHE=0 switches the cache off, PT_VIS_CACHE_GIB (1) is its budget; both are read per frame.  The bytes are
+ * not part of pt_scene_info's queue_bytes or device_bytes. */
+int pt_get_vis_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* resets, uint64_t* launches);
 /* Workgroups of the fused bounce-0 kernel of opaque scenes that the runtime places on one compute unit of `device`
  * (hipOccupancyMaxActiveBlocksPerMultiprocessor at the kernel's workgroup size): which = 0 the variant that computes
  * its ChaCha words, 1 the variant that reads them from the word cache, 2 and 3 the variants of 1 that store and that
- * load the camera hits.  One workgroup is one wave per SIMD. */
+ * load the camera hits, 4 the variant of 3 with the shadow-visibility cache and 5 that variant of scenes with a
+ * directional light.  One workgroup is one wave per SIMD. */
 int pt_kernel_occupancy(int device, int which, int* blocks_per_cu);
 
 /* Scene statistics after the KD build. */

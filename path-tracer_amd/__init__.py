@@ -226,7 +226,7 @@ HOST_SYMBOLS = ["pth_scene_load_isf", "pth_scene_free", "pth_scene_desc", "pth_s
 GPU_SYMBOLS = ["pt_scene_create", "pt_scene_destroy", "pt_scene_set_camera", "pt_scene_set_lights", "pt_scene_set_materials", "pt_prep_create", "pt_prep_destroy", "pt_scene_create_from_prep",
                "pt_comm_unique_id", "pt_comm_create", "pt_comm_create_all", "pt_comm_destroy", "pt_gather_tiles", "pt_render_gathered", "pt_local_pixel_count", "pt_local_pixel_map",
                "pt_render", "pt_render_device", "pt_debug_render", "pt_assemble_tiles", "pt_get_timing", "pt_get_counters",
-               "pt_scene_get_info", "pt_get_cull_stats", "pt_get_rng_cache_stats", "pt_get_hit_cache_stats", "pt_kernel_occupancy", "pt_scene_escape_copy", "pt_scene_grid_header", "pt_scene_grid_copy", "pt_trace_rays", "pt_trace_rays_wavefront",
+               "pt_scene_get_info", "pt_get_cull_stats", "pt_get_rng_cache_stats", "pt_get_hit_cache_stats", "pt_get_vis_cache_stats", "pt_kernel_occupancy", "pt_scene_escape_copy", "pt_scene_grid_header", "pt_scene_grid_copy", "pt_trace_rays", "pt_trace_rays_wavefront",
                "pt_trace_rays_all", "pt_intersect_triangles",
                "pt_rng_words", "pt_eval_math", "pt_measure_copy_bandwidth", "pt_measure_gather_rate", "pt_last_error",
                "pt_version", "pt_render_guides", "pt_render_guides_device", "pt_denoise_params_default", "pt_denoise_scratch_bytes",
@@ -333,6 +333,8 @@ def gpu_lib():
             L.pt_get_rng_cache_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 4
         if hasattr(L, "pt_get_hit_cache_stats"):
             L.pt_get_hit_cache_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 5
+        if hasattr(L, "pt_get_vis_cache_stats"):
+            L.pt_get_vis_cache_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 4
         if hasattr(L, "pt_kernel_occupancy"):
             L.pt_kernel_occupancy.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.pt_scene_grid_copy.argtypes = [vp, C.c_uint32, vp, vp]
@@ -372,7 +374,8 @@ def gpu_lib():
 
 def kernel_occupancy(which, device=0):
     """Workgroups of the fused bounce-0 kernel per compute unit (0: the variant computing its ChaCha words, 1: the cached one,
-    2 / 3: the cached one storing / loading the camera hits)."""
+    2 / 3: the cached one storing / loading the camera hits, 4 / 5: the loading one with the shadow-visibility cache, for
+    point lights / with a directional light)."""
     n = C.c_int()
     check_gpu(gpu_lib().pt_kernel_occupancy(device, which, C.byref(n)))
     return n.value
@@ -878,6 +881,13 @@ class GpuScene:
         loading launches)."""
         v = [C.c_uint64() for _ in range(5)]
         check_gpu(self.lib.pt_get_hit_cache_stats(self.handle, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def vis_cache_stats(self):
+        """The scene's cache of bounce-0 shadow visibility: (device bytes, work items of the keyed view and lights, times the
+        plane was zeroed, launches of the variant that reads and fills it)."""
+        v = [C.c_uint64() for _ in range(4)]
+        check_gpu(self.lib.pt_get_vis_cache_stats(self.handle, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
     def counters(self):

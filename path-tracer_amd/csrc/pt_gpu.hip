@@ -618,6 +618,25 @@ struct pt_scene {
         hipStream_t store_stream = nullptr;
         bool recorded = false, failed = false;
     } hit_cache;
+    // The answers of the bounce-0 shadow casts of ONE view and ONE set of light positions (vis_cache_frame): in an opaque scene
+    // og_blocked for an item and a light depends on the item's camera hit, the light's kind and position and the geometry -
+    // not on the materials, the light's colour or the bounces - so the frames of material and colour edits and of a steady
+    // state read it instead of casting again.  One byte by frame-global item g, indexed like the hit cache's plane: two
+    // bits per light (scenes of at most four), 0 unknown / 1 not blocked / 2 blocked.  No high-water mark: zero is
+    // "unknown", and the kernel that reads the plane casts for what it finds unknown and writes the answer back
+    // (k_wf_shade_hits<.. | 64>).  Keyed to the hit cache's key + the light count + every light's kind and position: a moved
+    // light or camera makes a new key (one memset, the allocation stays), no other edit touches the plane
+    // (drop_frame_state).  Not part of queue_bytes / device_bytes.
+    struct VisCache {
+        DeviceBuffer buf;
+        std::vector<uint64_t> key, last_key;   // what the bits are of; that of the scene's last wavefront frame
+        uint64_t items = 0, stride = 0;        // as HitCache's (the budget: PT_VIS_CACHE_GIB)
+        uint64_t resets = 0, launches = 0;     // times the plane was zeroed / launches of the variant since the scene was made
+        hipEvent_t ev_write = nullptr;         // behind the last launch of the variant (any of them may write)
+        hipStream_t write_stream = nullptr;
+        bool recorded = false, failed = false;
+    } vis_cache;
+    std::vector<DevLight> host_lights;   // the lights as the device has them (the visibility cache's key)
     uint64_t camera_generation = 0;   // bumped by pt_scene_set_camera
     uint64_t queue_bytes_last = 0;   // bytes of the path queues of the last frame (pt_scene_get_info)
     uint32_t queue_chunk_last = 0, frame_planned_last = 0;
@@ -643,6 +662,7 @@ struct pt_scene {
             if (e) (void)hipEventDestroy(e);
         if (rng_cache.ev_fill) (void)hipEventDestroy(rng_cache.ev_fill);
         if (hit_cache.ev_store) (void)hipEventDestroy(hit_cache.ev_store);
+        if (vis_cache.ev_write) (void)hipEventDestroy(vis_cache.ev_write);
         if (pipe.side_exact) (void)hipStreamDestroy(pipe.side_exact);
         if (pipe.side) (void)hipStreamDestroy(pipe.side);
         if (pipe.side_wide) (void)hipStreamDestroy(pipe.side_wide);
@@ -1640,6 +1660,7 @@ void scene_upload(const pt_prep& P, int device, pt_scene& s, SceneGrids* early =
     D.texels = s.upload(P.texels.data(), P.texels.size());
     D.srgb_lut = s.upload(P.lut, 256);
     D.lights = s.upload(P.lights.data(), P.lights.size());
+    s.host_lights = P.lights;
     // ---- escape masks (pt_escape.h): built on the device from these arrays - not here: when the scene is about to render its
     // THIRD frame (escape_masks_build below).  They take 0.14 s for the 0.5 M primitives of config 3 and 1.3 s for the 4 M of
     // config 5 and return 3 ms and ~0.1 s per frame: a one-shot render (the CLI) is better off without them.
@@ -1853,6 +1874,7 @@ void scene_set_lights(pt_scene& s, const pt_light* lights, uint32_t n) {
     s.cam_res = rule.cam_res;
     s.dev.lights = d_lights;
     s.dev.n_lights = n;
+    s.host_lights = dl;
     drop_frame_state(s);
 }
 
@@ -2201,6 +2223,7 @@ struct WfFrame {
     const std::vector<uint32_t>* plan_last = nullptr;
     const uint32_t* block_empty = nullptr;     // the camera-grid cull table (nullptr: no cull in this frame)
     pt_scene::RngCache* rng_cache = nullptr;   // the scene's word cache, keyed to this frame's enumeration (nullptr: not in use)
+    pt_scene::VisCache* vis_cache = nullptr;   // the scene's shadow-visibility cache, keyed to this frame's view and lights (nullptr: not in use)
     pt_scene::HitCache* hit_cache = nullptr;   // the scene's camera-hit cache, keyed to this frame's view (nullptr: not in use)
     uint32_t stats_line = 0, chunk_slot = 0;   // the frame's progress through its chunks
 };
@@ -2528,6 +2551,69 @@ void hit_cache_frame(pt_scene& s, const Frame& f, WfFrame& wf, hipStream_t strea
     if (hc.recorded && hc.store_stream != stream) HIP_CHECK(hipStreamWaitEvent(stream, hc.ev_store, 0));
 }
 
+// The scene's shadow-visibility cache and this frame (pt_scene::VisCache), after hit_cache_frame.  The key is the hit
+// cache's plus the light count and every light's kind and position, bit for bit - not its colour or `tame`, not the
+// materials, not the bounces.  As the hit cache, the plane is keyed when a frame's key equals that of the frame before: the
+// first frame after a moved light or camera does nothing new, a light orbit or a camera path never zeroes and never
+// allocates.  Keying is one memset on the frame's stream; from then on every chunk that LOADs its hits and lies below the
+// plane's stride runs the variant that reads the plane and fills in what is unknown.  Eligible: the frames the hit cache
+// serves, with one to four lights; any other frame leaves the bits alone - those of a scene that turned translucent are
+// still the opaque geometry's.  PT_VIS_CACHE=0: off; PT_VIS_CACHE_GIB: the budget (1) - both read per frame.
+void vis_cache_frame(pt_scene& s, const Frame& f, WfFrame& wf, hipStream_t stream) {
+    pt_scene::VisCache& vc = s.vis_cache;
+    std::vector<uint64_t> key = {f.p.width, f.p.height, f.p.samples, f.o.shard_rank, f.o.shard_count, f.o.tile_w, f.o.tile_h,
+                                 (uint64_t)f.env.morton, f.batch, s.camera_generation, s.cam_res, s.host_lights.size()};
+    for (const DevLight& L : s.host_lights) {
+        uint32_t w[4];
+        memcpy(w, &L.kind, 4);
+        memcpy(w + 1, L.vec, 12);
+        key.push_back((uint64_t)w[0] << 32 | w[1]);
+        key.push_back((uint64_t)w[2] << 32 | w[3]);
+    }
+    const bool follows_same = key == vc.last_key;
+    vc.last_key = key;
+    const double gib = env_num(getenv("PT_VIS_CACHE_GIB"), 1.0);
+    if (!env_bool(getenv("PT_VIS_CACHE"), true) || !(gib > 0.0)) {
+        if (vc.buf.p) {
+            HIP_CHECK(hipDeviceSynchronize());   // (frames in flight may still read the plane)
+            vc.buf.release();
+        }
+        vc.key.clear();
+        vc.items = vc.stride = 0;
+        return;
+    }
+    if (vc.failed || !wf.hit_cache || s.host_lights.empty() || s.host_lights.size() > 4u) return;
+    const uint64_t items = (uint64_t)f.blocks64 * 64u * f.p.samples;
+    const uint64_t stride = std::min<uint64_t>(items, (uint64_t)(gib * 1073741824.0)) & ~63ull;
+    if (key != vc.key || stride != vc.stride) {
+        if (!follows_same || stride == 0) return;
+        vc.key.clear();
+        vc.items = vc.stride = 0;
+        if (vc.buf.bytes < stride || vc.buf.bytes > stride + (64u << 20)) {
+            if (vc.buf.p) HIP_CHECK(hipDeviceSynchronize());   // (frames in flight may still use the plane)
+            vc.buf.release();
+            if (!vc.buf.try_ensure((size_t)stride)) {
+                vc.failed = true;
+                return;
+            }
+        }
+        if (!vc.ev_write) HIP_CHECK(hipEventCreateWithFlags(&vc.ev_write, hipEventDisableTiming));
+        // the launches of the old key on another stream are done with the plane before it is zeroed
+        if (vc.recorded && vc.write_stream != stream) HIP_CHECK(hipStreamWaitEvent(stream, vc.ev_write, 0));
+        HIP_CHECK(hipMemsetAsync(vc.buf.p, 0, (size_t)stride, stream));
+        HIP_CHECK(hipEventRecord(vc.ev_write, stream));
+        vc.recorded = true;
+        vc.write_stream = stream;
+        ++vc.resets;
+        vc.key = key;
+        vc.items = items;
+        vc.stride = stride;
+    }
+    wf.vis_cache = &vc;
+    // a frame on another stream than the one that wrote last waits for that launch (as the hit cache's ev_store)
+    if (vc.recorded && vc.write_stream != stream) HIP_CHECK(hipStreamWaitEvent(stream, vc.ev_write, 0));
+}
+
 // This frame's counts, one line per (batch, chunk): taken every frame (a few KB) - the first frame's feed the plan, the
 // later ones only say whether a queue ran full.  None while an earlier frame's line is still on its way.
 void stats_slots(pt_scene& s, const Frame& f, WfFrame& wf) {
@@ -2643,6 +2729,7 @@ struct Chunk {
     // 32 - it loads them instead of casting, 0 - neither
     int hit_mode = 0;
     uint4* hit_plane = nullptr;
+    uint8_t* vis_plane = nullptr;   // the scene's shadow-visibility cache (chunks that load their hits only): the chunk's bytes, or null
     float4 *q_in = nullptr, *q_out = nullptr;
     bool split_shade = false;   // the shade pass in two launches (PT_WF_SPLIT)
 };
@@ -2766,7 +2853,20 @@ void shade_stage(pt_scene& s, const Frame& f, const WfFrame& wf, const Chunk& c,
                            (float*)s.staging_buf.p, (uint32_t*)pipe.exact[(b + 1) & 1].p, block_empty, c.wctr);
         HIP_CHECK(hipGetLastError());
     };
+    // ... and with the shadow-visibility cache: loads the hits, reads the chunk's visibility bytes and fills in the unknown
+    auto launch_vis = [&](auto grid) {
+        constexpr int G = decltype(grid)::value;
+        hipLaunchKernelGGL((k_wf_shade_hits<G>), dim3(shade_grid), dim3(WF_SHADE_THREADS), 0, c.st_main, f.dev, W, f.d_tiles,
+                           (const uint4*)c.rng_planes, c.hit_plane, c.q_out, (float4*)pipe.shadow.p, (float4*)pipe.contrib.p,
+                           (float*)s.staging_buf.p, (uint32_t*)pipe.exact[(b + 1) & 1].p, block_empty, c.wctr, c.vis_plane);
+        HIP_CHECK(hipGetLastError());
+    };
     auto launch_shade = [&] {
+        if (c.grid_mode == 3 && c.cached && c.hit_mode == 32 && c.vis_plane) {
+            if (s.grids.ortho) launch_vis(std::integral_constant<int, (15 | 32 | 64)>{});
+            else launch_vis(std::integral_constant<int, (11 | 32 | 64)>{});
+            return;
+        }
         if (c.grid_mode == 3 && c.cached && c.hit_mode) {
             switch ((s.grids.ortho ? 15 : 11) | c.hit_mode) {
             case 11 | 16: launch_hits(std::integral_constant<int, (11 | 16)>{}); break;
@@ -2920,6 +3020,8 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
         if (g1 <= hc.mark) c.hit_mode = 32;
         else if (g1 <= hc.stride && g0 <= hc.mark) c.hit_mode = 16;
         if (c.hit_mode) c.hit_plane = (uint4*)hc.buf.p + g0;
+        // the shadow-visibility cache: a chunk that loads its hits and lies wholly below the plane's stride
+        if (c.hit_mode == 32 && wf.vis_cache && g1 <= wf.vis_cache->stride) c.vis_plane = (uint8_t*)wf.vis_cache->buf.p + g0;
     }
     if (fused_rng && !c.cached && pipe.rng[0].bytes < (size_t)wf.cap * 16u) {   // (queue_buffers left the plane out)
         s.pipe.rng[0].ensure((size_t)wf.cap * 16u);
@@ -2982,6 +3084,13 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
             ++hc.stores;
         } else if (c.prim && c.hit_mode == 32) {
             ++wf.hit_cache->loads;
+            if (c.vis_plane) {   // (any such launch may write the plane)
+                pt_scene::VisCache& vc = *wf.vis_cache;
+                HIP_CHECK(hipEventRecord(vc.ev_write, c.st_main));
+                vc.recorded = true;
+                vc.write_stream = c.st_main;
+                ++vc.launches;
+            }
         }
         shadow_stage(s, f, c, tl);
     }
@@ -3099,6 +3208,7 @@ void render_device(pt_scene& s, const pt_profile& p, const pt_opts* opts_in, voi
         wf = frame_plan(s, f, qe);
         rng_cache_frame(s, f, wf, stream);
         hit_cache_frame(s, f, wf, stream);
+        vis_cache_frame(s, f, wf, stream);
         queue_buffers(s, f, qe, wf);
         stats_slots(s, f, wf);
         side_streams(s, f, wf);
@@ -3999,16 +4109,29 @@ int pt_get_hit_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* ite
     *loads = hc.loads;
     return PT_OK;
 }
+int pt_get_vis_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* resets, uint64_t* launches) {
+    if (!scene || !bytes || !items || !resets || !launches) return PT_ERR_INVALID;
+    const pt_scene::VisCache& vc = scene->vis_cache;
+    *bytes = vc.buf.bytes;
+    *items = vc.items;
+    *resets = vc.resets;
+    *launches = vc.launches;
+    return PT_OK;
+}
 int pt_kernel_occupancy(int device, int which, int* blocks_per_cu) {
     return guarded([&] {
-        if (!blocks_per_cu || which < 0 || which > 3) fail(PT_ERR_INVALID, "pt_kernel_occupancy: bad argument");
+        if (!blocks_per_cu || which < 0 || which > 5) fail(PT_ERR_INVALID, "pt_kernel_occupancy: bad argument");
         HIP_CHECK(hipSetDevice(device));
         if (which == 0)
             HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_wf_shade<false, false, true, 3>, WF_SHADE_THREADS, 0));
         else if (which == 2)
-            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_wf_shade_hits<(11 | 16)>, WF_SHADE_THREADS, 0));
+            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, (WfShadeHitsKernel)k_wf_shade_hits<(11 | 16)>, WF_SHADE_THREADS, 0));
         else if (which == 3)
-            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_wf_shade_hits<(11 | 32)>, WF_SHADE_THREADS, 0));
+            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, (WfShadeHitsKernel)k_wf_shade_hits<(11 | 32)>, WF_SHADE_THREADS, 0));
+        else if (which == 4)
+            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, (WfShadeVisKernel)k_wf_shade_hits<(11 | 32 | 64)>, WF_SHADE_THREADS, 0));
+        else if (which == 5)
+            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, (WfShadeVisKernel)k_wf_shade_hits<(15 | 32 | 64)>, WF_SHADE_THREADS, 0));
         else
             HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_wf_shade<false, false, true, 11>, WF_SHADE_THREADS, 0));
     });

@@ -215,3 +215,34 @@ PT_D f3 og_light_radiance(const DevScene& S, uint32_t li, f3 pos, f3 gn, f2 uv, 
     }
     return rad;
 }
+
+// og_light_radiance of an OPAQUE scene in its two halves, for the caller that keeps the visibility (the shadow-visibility
+// cache of the bounce-0 kernel, pt_wavefront.h VIS): the radiance before the visibility factor - the expressions of
+// og_light_radiance, operand for operand - and the cast whose answer is that factor.  rad * 0.0f where blocked stays the
+// caller's, as there.
+template <bool DIRL>
+PT_D f3 og_light_unshadowed(const DevScene& S, uint32_t li, f3 pos) {
+    const DevLight& L = S.lights[li];
+    if (DIRL && L.kind != PT_LIGHT_POINT) return ld3(L.color);
+    const f3 direction = pos - ld3(L.vec);
+    const float ldist = mag3(direction);
+    return ld3(L.color) / (4.f * PT_PI * ldist * ldist);
+}
+template <bool DIRL>
+PT_D bool og_light_blocked(const DevScene& S, uint32_t li, f3 pos, f3 gn, LocalCtr& lc) {
+    const DevLight& L = S.lights[li];
+    const DevGrid& G = S.light_grids[li];
+    const f3 so = pos + gn * 0.00001f;   // NORMAL_BIAS (mod.rs:58)
+    if (DIRL && L.kind != PT_LIGHT_POINT) {
+        const f3 sd = -1.f * ld3(L.vec);
+        const uint32_t cell = og_cell_ortho(G, so);
+        const float limit = -dot3(so, ld3(G.axis_w));
+        return og_blocked<false, false>(S, G, cell, so, sd, pos, limit, lc);
+    }
+    f3 direction = pos - ld3(L.vec);
+    const uint32_t cell = og_cell(G, direction);
+    const float ldist = mag3(direction);
+    direction = normalize3(direction);
+    const f3 sd = -1.f * direction;
+    return og_blocked<false, true>(S, G, cell, so, sd, pos, ldist, lc);
+}

@@ -2019,8 +2019,8 @@ constexpr uint32_t WF_ARG_OFFSET_W = (uint32_t)((sizeof(DevScene) + alignof(WfPa
 // LDS parking slots of that variant at four waves (one dword per thread each; the kernel's sh_park).  Four workgroups must
 // fit a CU's 160 KiB beside the compaction's 296 B each: 39 slots (39 KiB) at the most, forty would not.
 enum : uint32_t { PK_BRDF = 0, PK_NORMAL = 11, PK_VIEW = 14, PK_UV = 17, PK_PID = 19, PK_OUT_SLOT = 20, PK_WORD2 = 21, PK_C = 23,
-                  PK_COLOR = 26, PK_TERM0 = 29, WF_PARK_SLOTS = 32 };
-static_assert(WF_PARK_SLOTS <= 39, "four workgroups of the bounce-0 kernel must fit a CU's LDS");
+                  PK_COLOR = 26, PK_TERM0 = 29, WF_PARK_SLOTS = 32, PK_VIS = 32 };   // (PK_VIS: the VIS variants' one slot more)
+static_assert(WF_PARK_SLOTS + 1u <= 39, "four workgroups of the bounce-0 kernel must fit a CU's LDS");
 // GRID (origin grids, pt_grid.h): 0 - none: direct light goes through the shadow queue and k_wf_shadow / k_og_shadow;
 // 1 - every light is a point light with a grid: get_light_info (mod.rs:281-333) is evaluated HERE, light after
 //     light, so a surface costs no shadow record, no contrib entries and no colour patch (190 B of queue traffic
@@ -2039,6 +2039,8 @@ static_assert(WF_PARK_SLOTS <= 39, "four workgroups of the bounce-0 kernel must 
 // enumeration, the camera and the geometry - not on the lights, the bounces or, in an opaque scene, the materials - so
 // STORE writes pack_hit of the cast's result for every item, and LOAD reads that record instead of casting: no og_cell on
 // the camera grid, no og_next_hit.  The ray itself is still derived: shading needs o and d.
+// + 64 * VIS (LOAD only; the second k_wf_shade_hits below): the scene's shadow-visibility cache (pt_gpu.hip VisCache;
+// vis_plane points at the chunk's first item there) - a light whose bits are known is not cast for.
 // (S and W FIRST, in this order: the PARK variants read them again through the kernarg segment, wf_opaque_arg)
 template <bool ALPHA, bool COUNT, bool PRIMARY, int GRIDX>
 __global__ __launch_bounds__(WF_SHADE_THREADS, GRIDX ? (ALPHA ? WF_SHADE_GRID_WAVES_ALPHA : GRIDX >= 8 ? WF_SHADE_CACHED_WAVES : WF_SHADE_GRID_WAVES) : WF_SHADE_WAVES) void k_wf_shade(DevScene S, WfParams W,
@@ -2059,6 +2061,7 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, GRIDX ? (ALPHA ? WF_SHADE_GRID_WA
     static_assert(wf_leading_args<decltype(&k_wf_shade<ALPHA, COUNT, PRIMARY, GRIDX>)>::scene_then_params,
                   "wf_opaque_arg: DevScene and WfParams must be the first two parameters of k_wf_shade");
     uint4* const hit_plane = nullptr;   // (k_wf_shade_hits has one)
+    uint8_t* const vis_plane = nullptr;
 #include "pt_wf_shade_body.h"
 }
 
@@ -2078,6 +2081,39 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_
                   "wf_opaque_arg: DevScene and WfParams must be the first two parameters of k_wf_shade_hits");
     constexpr bool ALPHA = false, COUNT = false, PRIMARY = true;
     // (what bounce 0 does not read)
+    const float4* const queue_in = nullptr;
+    const uint4 *const hits = nullptr, *const chunk_hits = nullptr;
+    const uint32_t *const draws = nullptr, *const index_list = nullptr, *const exact_list = nullptr;
+    DevCounters* const gctr = nullptr;
+    uint8_t* const vis_plane = nullptr;   // (the overload below has one)
+#include "pt_wf_shade_body.h"
+}
+
+// ... and with the scene's shadow-visibility cache (pt_gpu.hip VisCache): GRIDX = 11 or 15, + 32 (LOAD) + 64 (VIS).  In an
+// opaque scene the answer of a bounce-0 shadow cast - og_blocked for one item and one light - depends on the camera hit,
+// the light's kind and position and the geometry: not on the materials, the light's colour or the bounces.  vis_plane
+// holds it, one byte per item of the chunk (two bits per light, zero: unknown); a lane casts for the lights it does not
+// know yet and writes its byte back, so the launch that fills the plane and those that read it are one kernel.  An
+// overload of its own, by the one parameter more: the kernels above keep their arguments, and their code, as they were.
+// (The two overloads by their types: `k_wf_shade_hits<G>` alone names both where nothing is called.)
+typedef void (*WfShadeHitsKernel)(DevScene, WfParams, const uint32_t*, const uint4*, uint4*, float4*, float4*, float4*, float*, uint32_t*,
+                                  const uint32_t*, WfCounters*);
+typedef void (*WfShadeVisKernel)(DevScene, WfParams, const uint32_t*, const uint4*, uint4*, float4*, float4*, float4*, float*, uint32_t*,
+                                 const uint32_t*, WfCounters*, uint8_t*);
+template <int GRIDX>
+__global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_shade_hits(DevScene S, WfParams W,
+                                                  const uint32_t* __restrict__ tile_offsets, const uint4* rng_planes,
+                                                  uint4* __restrict__ hit_plane,
+                                                  float4* __restrict__ queue_out, float4* __restrict__ shadow_q,
+                                                  float4* __restrict__ contrib, float* __restrict__ staging,
+                                                  uint32_t* __restrict__ exact_next,
+                                                  const uint32_t* __restrict__ block_empty,
+                                                  WfCounters* __restrict__ ctr, uint8_t* __restrict__ vis_plane) {
+    static_assert(GRIDX == (11 | 32 | 64) || GRIDX == (15 | 32 | 64), "LOAD and VIS of the cached opaque variants");
+    // (S and W first: wf_opaque_arg, as above)
+    static_assert(wf_leading_args<WfShadeVisKernel>::scene_then_params,
+                  "wf_opaque_arg: DevScene and WfParams must be the first two parameters of k_wf_shade_hits");
+    constexpr bool ALPHA = false, COUNT = false, PRIMARY = true;
     const float4* const queue_in = nullptr;
     const uint4 *const hits = nullptr, *const chunk_hits = nullptr;
     const uint32_t *const draws = nullptr, *const index_list = nullptr, *const exact_list = nullptr;

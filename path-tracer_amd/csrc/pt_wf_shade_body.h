@@ -3,7 +3,7 @@
 // of eight variants moved by 4-8 B; profiles/r09_experiments.txt item 0), and those variants are tuned to the byte.
 // In scope: the template parameters ALPHA, COUNT, PRIMARY, GRIDX (as constants in k_wf_shade_hits) and the kernel's
 // parameters - S, W, tile_offsets, queue_in, hits, rng_planes, draws, queue_out, shadow_q, contrib, staging, index_list,
-// exact_list, chunk_hits, exact_next, block_empty, ctr, gctr - and hit_plane.
+// exact_list, chunk_hits, exact_next, block_empty, ctr, gctr - and hit_plane, vis_plane.
     // index_list (bounces >= 1): null - the whole queue, entries marked WF_HIT_PENDING left out; else the entries to shade:
     // the hand-over list of k_wf_trace, whose casts k_wf_trace_wide has finished by now - `hits` is then that list's
     // own plane (W.list_cap records, by list position).  The pass over the queue runs WHILE k_wf_trace_wide walks
@@ -19,6 +19,8 @@
     static_assert(GRIDX != 4, "DIRL needs a grid mode");
     static_assert(!(STORE || LOAD) || (CACHED && !ALPHA && !COUNT && PRIMARY), "the camera-hit cache serves the cached opaque bounce-0 kernel");
     static_assert(!(STORE && LOAD), "a launch stores the camera hits or loads them");
+    constexpr bool VIS = (GRIDX & 64) != 0;
+    static_assert(!VIS || LOAD, "the shadow-visibility cache serves the launches that load their camera hits");
     static_assert(!CACHED || (GRID == 3 && !COUNT), "the word cache serves the fused bounce-0 kernel");
     uint4* rng_planes_out = const_cast<uint4*>(rng_planes);   // GRID == 3 writes plane 1 (nobody reads it before bounce 1)
     static_assert(GRID < 2 || PRIMARY, "the camera grid serves bounce 0");
@@ -49,7 +51,7 @@
     // thread - no barrier).  The accesses are volatile: a plain store would be forwarded to its load and the register kept.
     constexpr bool PARK = CACHED && !ALPHA && WF_SHADE_PARK;
     // (wf_opaque_arg reads S at offset 0 of the kernarg segment and W right behind it: the kernels below check that)
-    __shared__ uint32_t sh_park[PARK ? WF_PARK_SLOTS : 1][WF_SHADE_THREADS];
+    __shared__ uint32_t sh_park[PARK ? WF_PARK_SLOTS + (VIS ? 1u : 0u) : 1][WF_SHADE_THREADS];   // (VIS: + PK_VIS)
     // (an LDS pointer by type: a volatile access through a generic pointer stays a flat access, one 64-bit address per slot)
     volatile __attribute__((address_space(3))) uint32_t* const park = (volatile __attribute__((address_space(3))) uint32_t*)&sh_park[0][threadIdx.x];
     auto park_u = [&](uint32_t slot, uint32_t v) { park[slot * WF_SHADE_THREADS] = v; };
@@ -95,6 +97,12 @@
     // (LOAD) the item's camera hit: a dense load that depends on nothing - its latency runs under decode_item and the ray set-up
     uint4 cam_rec = make_uint4(0xffffffffu, 0u, 0u, 0u);
     if (LOAD && PRIMARY && live) cam_rec = hit_plane[i];
+    // (VIS) the item's visibility byte, as dense and as independent: two bits per light - 0 unknown, 1 not blocked, 2 blocked
+    // (og_blocked of the item's surface and that light).  Bit 8, in the register only: this launch found one of them out.
+    uint32_t vis = 0u;
+    if constexpr (VIS) {
+        if (live) vis = vis_plane[i];
+    }
     if (PRIMARY && live) {  // entry i is work item i: the initial path state, built in place
         ItemRef it = decode_item(W.P, tile_offsets, W.item_base + i);
         if (!it.valid) {
@@ -229,7 +237,7 @@
             surf.uv.x = unpark_f(PK_UV), surf.uv.y = unpark_f(PK_UV + 1u);
             h.pid = unpark_u(PK_PID), out_slot = unpark_u(PK_OUT_SLOT), word2 = unpark_u(PK_WORD2), word3 = unpark_u(PK_WORD2 + 1u);
         };
-        if (PARK) park_fixed();
+        if (PARK && !VIS) park_fixed();   // (VIS: around the casts that are still made)
         for (uint32_t li = 0; li < S.n_lights; ++li) {
             const DevLight& L = S.lights[li];
             f3 ldir = L.kind == PT_LIGHT_POINT ? normalize3(surf.pos - ld3(L.vec)) : ld3(L.vec);
@@ -239,6 +247,25 @@
             if (GRID != 0 && inline_lights) {
                 if (moot) {
                     if (COUNT) n_moot++;
+                } else if constexpr (VIS) {
+                    // og_light_radiance with the cast's answer kept: a light whose bits are known costs the radiance alone - no
+                    // grid cell, no list, no primitive, no slab test.  The cast and all the parking around it sit behind
+                    // this branch: a wavefront none of whose lanes has an unknown light skips it, and once the plane is
+                    // full no LDS parking instruction is issued at all.
+                    const uint32_t known = (vis >> (2u * li)) & 3u;
+                    bool blocked = known == 2u;
+                    if (known == 0u) {
+                        if (PARK) park_fixed(), park_3(PK_C, c), park_3(PK_COLOR, color), park_3(PK_TERM0, term0), park_u(PK_VIS, vis);
+                        blocked = og_light_blocked<DIRL>(S, li, surf.pos, surf.normal, lc);
+                        if (PARK) {
+                            c = unpark_3(PK_C), color = unpark_3(PK_COLOR), term0 = unpark_3(PK_TERM0), vis = unpark_u(PK_VIS);
+                            unpark_fixed();
+                        }
+                        vis |= ((blocked ? 2u : 1u) << (2u * li)) | 0x100u;
+                    }
+                    f3 rad = og_light_unshadowed<DIRL>(S, li, surf.pos);
+                    if (blocked) rad = rad * 0.0f;
+                    if (!(rad.x == 0.f && rad.y == 0.f && rad.z == 0.f)) color = color + mul_ew(c, rad);
                 } else {
                     if (PARK) park_3(PK_C, c), park_3(PK_COLOR, color), park_3(PK_TERM0, term0);
                     const f3 rad = og_light_radiance<ALPHA, COUNT, DIRL>(S, li, surf.pos, surf.normal, surf.uv, surf.sphere, lc);
@@ -253,6 +280,9 @@
             }
         }
         if (COUNT && !inline_lights && !to_shadow) n_moot += S.n_lights;
+        if constexpr (VIS) {   // what this launch found out: one byte store per lane that cast; none once the plane is full
+            if (vis & 0x100u) vis_plane[i] = (uint8_t)vis;
+        }
         bool ended = false;
         if (bounce < bounces) {
             next_o = surf.pos + surf.normal * 0.00001f;

@@ -589,6 +589,13 @@ int pt_trace_rays_wavefront(const pt_scene* scene, const float* rays, const uint
  * hit").  For the tests, which aim rays through clear cells and require brute force to find nothing. */
 int pt_scene_escape_copy(const pt_scene* scene, void* out, uint64_t bytes);
 
+/* The lookup the shade kernel makes before it casts a bounce ray (escape_proves_miss, csrc/pt_escape.h), run on the device for
+ * n queries: proven[i] = 1 where the mask of primitive prims[i] proves that the ray rays[i] (origin3, direction3) hits nothing -
+ * the height of the origin above the primitive's plane within [5e-6, 1e-3] and the direction's cell clear - else 0.  HOST
+ * pointers.  Builds the masks if the scene has none yet, as pt_scene_escape_copy does.  PT_ERR_INVALID: a null pointer, a
+ * primitive index >= n_prims (checked before anything runs on the device), a scene that cannot have masks. */
+int pt_escape_query(const pt_scene* scene, const uint32_t* prims, const float* rays /* n x 6 */, uint64_t n, uint8_t* proven);
+
 struct pth_origin_grid;
 struct pth_grid_ref;
 int pt_scene_grid_header(const pt_scene* scene, uint32_t which, struct pth_origin_grid* out);

@@ -226,7 +226,7 @@ HOST_SYMBOLS = ["pth_scene_load_isf", "pth_scene_free", "pth_scene_desc", "pth_s
 GPU_SYMBOLS = ["pt_scene_create", "pt_scene_destroy", "pt_scene_set_camera", "pt_scene_set_lights", "pt_scene_set_materials", "pt_prep_create", "pt_prep_destroy", "pt_scene_create_from_prep",
                "pt_comm_unique_id", "pt_comm_create", "pt_comm_create_all", "pt_comm_destroy", "pt_gather_tiles", "pt_render_gathered", "pt_local_pixel_count", "pt_local_pixel_map",
                "pt_render", "pt_render_device", "pt_debug_render", "pt_assemble_tiles", "pt_get_timing", "pt_get_counters",
-               "pt_scene_get_info", "pt_get_cull_stats", "pt_get_rng_cache_stats", "pt_get_hit_cache_stats", "pt_get_vis_cache_stats", "pt_kernel_occupancy", "pt_scene_escape_copy", "pt_scene_grid_header", "pt_scene_grid_copy", "pt_trace_rays", "pt_trace_rays_wavefront",
+               "pt_scene_get_info", "pt_get_cull_stats", "pt_get_rng_cache_stats", "pt_get_hit_cache_stats", "pt_get_vis_cache_stats", "pt_kernel_occupancy", "pt_scene_escape_copy", "pt_escape_query", "pt_scene_grid_header", "pt_scene_grid_copy", "pt_trace_rays", "pt_trace_rays_wavefront",
                "pt_trace_rays_all", "pt_intersect_triangles",
                "pt_rng_words", "pt_eval_math", "pt_measure_copy_bandwidth", "pt_measure_gather_rate", "pt_last_error",
                "pt_version", "pt_render_guides", "pt_render_guides_device", "pt_denoise_params_default", "pt_denoise_scratch_bytes",
@@ -328,6 +328,8 @@ def gpu_lib():
         L.pt_trace_rays_wavefront.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, vp]
         L.pt_scene_grid_header.argtypes = [vp, C.c_uint32, vp]
         L.pt_scene_escape_copy.argtypes = [vp, vp, C.c_uint64]
+        if hasattr(L, "pt_escape_query"):
+            L.pt_escape_query.argtypes = [vp, vp, vp, C.c_uint64, vp]
         L.pt_get_cull_stats.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         if hasattr(L, "pt_get_rng_cache_stats"):   # (an A/B library of an earlier commit, PT_GPU_LIB, has none)
             L.pt_get_rng_cache_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 4
@@ -913,6 +915,18 @@ class GpuScene:
         words = raw[:, 8:20].reshape(n, 6, 2)
         bits = ((words[:, :, :, None] >> np.arange(32, dtype=np.uint32)) & 1).astype(bool).reshape(n, 6, 64)
         return normals, v0, bits
+
+    def escape_query(self, prims, rays):
+        """bool [n]: does the mask of prims[i] prove that rays[i] (origin3, direction3) hits nothing - the kernels' own lookup
+        (escape_proves_miss) run on the device, the height check of the origin included."""
+        import numpy as np
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        prims = np.ascontiguousarray(prims, np.uint32).reshape(-1)
+        if len(prims) != len(rays):
+            raise ValueError("escape_query: one primitive per ray")
+        out = np.zeros(len(rays), np.uint8)
+        check_gpu(self.lib.pt_escape_query(self.handle, prims.ctypes.data, rays.ctypes.data, len(rays), out.ctypes.data))
+        return out.astype(bool)
 
     def trace_wavefront(self, rays, start_prims=None, mode=0):
         """Closest hits through k_wf_trace itself (mode bit 0: entry lists from start_prims, bit 1: k_wf_trace_wide)."""

@@ -16,7 +16,7 @@
 //   k_guides, k_dn_*  pt_denoise.h: first-hit guide planes and the a-trous filter of denoised previews
 //   k_accumulate_moments, k_dnv_*  pt_variance.h: per-pixel sample moments and the variance-guided form of that filter
 //   k_stream_copy     achievable-HBM yardstick of the roofline (pt_measure_copy_bandwidth)
-//   k_trace / k_trace_all / k_isect / k_rng / k_math   parity-test hooks
+//   k_trace / k_trace_all / k_escape_query / k_isect / k_rng / k_math   parity-test hooks
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
@@ -270,6 +270,17 @@ __global__ __launch_bounds__(256) void k_trace_all(DevScene S, const float* __re
     }
     counts[i] = cnt;
     for (uint32_t j = cnt; j < max_hits; ++j) out[i * max_hits + j] = pt_hit{-1, 0, 0.f, 0.f, 0.f};
+}
+
+// The lookup k_wf_shade makes when it has sampled a bounce direction, one query per lane: the function itself, so that a test
+// asks the device which cell it reads for a direction on a border instead of restating it.  prims are checked on the host.
+__global__ __launch_bounds__(256) void k_escape_query(DevScene S, const uint32_t* __restrict__ prims, const float* __restrict__ rays,
+                                                      uint64_t n, uint8_t* __restrict__ proven) {
+    uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    f3 o = mk3(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]);
+    f3 d = mk3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
+    proven[i] = escape_proves_miss(S, prims[i], o, d) ? 1 : 0;
 }
 
 // render_debug_pixels (src/renderer/debug_renderer.rs:64-105): first hit of the pixel-centre ray
@@ -4256,6 +4267,26 @@ int pt_scene_escape_copy(const pt_scene* scene, void* out, uint64_t bytes) {
         if (bytes != (uint64_t)scene->dev.n_prims * 80u) fail(PT_ERR_INVALID, "pt_scene_escape_copy: %llu bytes expected", (unsigned long long)scene->dev.n_prims * 80ull);
         HIP_CHECK(hipSetDevice(scene->device));
         HIP_CHECK(hipMemcpy(out, scene->dev.escape, bytes, hipMemcpyDeviceToHost));
+    });
+}
+
+int pt_escape_query(const pt_scene* scene, const uint32_t* prims, const float* rays, uint64_t n, uint8_t* proven) {
+    return guarded([&] {
+        if (!scene || !prims || !rays || !proven) fail(PT_ERR_INVALID, "pt_escape_query: null argument");
+        if (!scene->dev.escape && scene->escape_wanted && !scene->escape_tried) escape_masks_build(render_state(scene));
+        if (!scene->dev.escape) fail(PT_ERR_INVALID, "pt_escape_query: the scene has no escape masks");
+        for (uint64_t i = 0; i < n; ++i)   // (before anything is launched: the kernel indexes the records with them)
+            if (prims[i] >= scene->dev.n_prims) fail(PT_ERR_INVALID, "pt_escape_query: primitive %u out of range", prims[i]);
+        if (n == 0) return;
+        if (n >= (1ull << 31)) fail(PT_ERR_INVALID, "pt_escape_query: too many queries");
+        HIP_CHECK(hipSetDevice(scene->device));
+        Staged<uint32_t> d_prims(prims, n);
+        Staged<float> d_rays(rays, n * 6);
+        Staged<uint8_t> d_out(nullptr, n);
+        hipLaunchKernelGGL(k_escape_query, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, 0, scene->dev, d_prims.d, d_rays.d, n, d_out.d);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        d_out.fetch(proven, n);
     });
 }
 

@@ -872,25 +872,25 @@ class GpuScene:
         check_gpu(self.lib.pt_get_cull_stats(self.handle, C.byref(n), C.byref(e)))
         return n.value, e.value
 
+    def _cache_stats(self, getter, n):
+        """The n uint64 values one of the frame caches' getters writes."""
+        v = [C.c_uint64() for _ in range(n)]
+        check_gpu(getter(self.handle, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
     def rng_cache_stats(self):
         """The scene's cache of ChaCha words: (device bytes, work items of the keyed enumeration, items cached, fill launches)."""
-        v = [C.c_uint64() for _ in range(4)]
-        check_gpu(self.lib.pt_get_rng_cache_stats(self.handle, *[C.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._cache_stats(self.lib.pt_get_rng_cache_stats, 4)
 
     def hit_cache_stats(self):
         """The scene's cache of camera hits: (device bytes, work items of the keyed view, items cached, storing launches,
         loading launches)."""
-        v = [C.c_uint64() for _ in range(5)]
-        check_gpu(self.lib.pt_get_hit_cache_stats(self.handle, *[C.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._cache_stats(self.lib.pt_get_hit_cache_stats, 5)
 
     def vis_cache_stats(self):
         """The scene's cache of bounce-0 shadow visibility: (device bytes, work items of the keyed view and lights, times the
         plane was zeroed, launches of the variant that reads and fills it)."""
-        v = [C.c_uint64() for _ in range(4)]
-        check_gpu(self.lib.pt_get_vis_cache_stats(self.handle, *[C.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._cache_stats(self.lib.pt_get_vis_cache_stats, 4)
 
     def counters(self):
         c = Counters()

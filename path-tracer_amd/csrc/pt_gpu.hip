@@ -598,55 +598,57 @@ struct pt_scene {
         uint32_t mask_blocks = 0;   // blocks of the last frame's camera-grid cull table (0: no cull in that frame)
     } frame_state;
     DeviceBuffer stats_dev;
-    // Words 0-7 of ChaCha block 0 of every work item of ONE item enumeration (rng_cache_frame): a sample's seed is
-    // sample + pixel x samples - the enumeration alone, not the scene, the camera, the lights, the materials or the
-    // bounces - so the frames of a camera path, of live edits or of a steady state read them instead of deriving them
-    // again.  Two planes of `stride` uint4 (words 0-3, words 4-7) by frame-global item g = batch x items per batch + item,
-    // filled as a prefix [0, mark) in frame order.  Not an edit's to drop (drop_frame_state) and not part of queue_bytes.
-    struct RngCache {
+    // A frame cache: one value per work item that later frames of the same key read instead of computing it again.  The
+    // mechanics the three share (frame_cache_frame, render_chunk): the plane is indexed by frame-global item g = batch x
+    // items per batch + item and - words and hits - filled as a prefix [0, mark) in frame order, whatever the chunking; it is
+    // keyed to a key in the SECOND consecutive frame of that key, so a one-shot render never pays for it and a caller
+    // alternating two keys never thrashes it; it is not an edit's to drop (drop_frame_state: an edit that matters changes the
+    // key) and not part of queue_bytes / device_bytes.  One event, behind the last launch that wrote the plane (the
+    // visibility plane: that may have written), is what a frame on another stream waits for: the caller orders the frames
+    // of a scene - they share its queues - so the earlier writes are behind it.
+    struct FrameCache {
         DeviceBuffer buf;
-        std::vector<uint64_t> key, last_key;   // the enumeration the words are of; that of the scene's last wavefront frame
-        uint64_t items = 0;                    // work items of the keyed enumeration
-        uint64_t stride = 0;                   // of them, those the budget has room for (PT_RNG_CACHE_GIB)
-        uint64_t mark = 0, fills = 0;          // items filled so far; fill launches since the scene was made
-        hipEvent_t ev_fill = nullptr;          // behind the last fill launch
-        hipStream_t fill_stream = nullptr;
-        bool recorded = false, failed = false;   // (failed: the device could not provide the planes: no cache for this scene)
-    } rng_cache;
-    // The camera rays' closest hits of ONE view (hit_cache_frame): the hit of a camera ray depends on the item enumeration
-    // (the jitter words), the camera and the geometry - not on the lights, the bounces or, in an opaque scene, the
-    // materials - so the frames of light and material edits and of a steady state read it instead of casting again.  One
-    // plane of uint4 (pack_hit) by frame-global item g, indexed like the word cache and filled as a prefix [0, mark) by the
-    // storing variant of the bounce-0 kernel.  Keyed to the word cache's key + the camera generation + the camera grid's
-    // resolution: a camera move resets the mark (the allocation stays), no other edit touches it (drop_frame_state).  Not
-    // part of queue_bytes / device_bytes.
-    struct HitCache {
-        DeviceBuffer buf;
-        std::vector<uint64_t> key, last_key;   // the view the records are of; that of the scene's last wavefront frame
-        uint64_t items = 0, stride = 0, mark = 0;   // as RngCache's (the budget: PT_HIT_CACHE_GIB)
-        uint64_t stores = 0, loads = 0;             // launches of the storing / loading variants since the scene was made
-        hipEvent_t ev_store = nullptr;              // behind the last storing launch
-        hipStream_t store_stream = nullptr;
-        bool recorded = false, failed = false;
-    } hit_cache;
-    // The answers of the bounce-0 shadow casts of ONE view and ONE set of light positions (vis_cache_frame): in an opaque scene
-    // og_blocked for an item and a light depends on the item's camera hit, the light's kind and position and the geometry -
-    // not on the materials, the light's colour or the bounces - so the frames of material and colour edits and of a steady
-    // state read it instead of casting again.  One byte by frame-global item g, indexed like the hit cache's plane: two
-    // bits per light (scenes of at most four), 0 unknown / 1 not blocked / 2 blocked.  No high-water mark: zero is
-    // "unknown", and the kernel that reads the plane casts for what it finds unknown and writes the answer back
-    // (k_wf_shade_hits<.. | 64>).  Keyed to the hit cache's key + the light count + every light's kind and position: a moved
-    // light or camera makes a new key (one memset, the allocation stays), no other edit touches the plane
-    // (drop_frame_state).  Not part of queue_bytes / device_bytes.
-    struct VisCache {
-        DeviceBuffer buf;
-        std::vector<uint64_t> key, last_key;   // what the bits are of; that of the scene's last wavefront frame
-        uint64_t items = 0, stride = 0;        // as HitCache's (the budget: PT_VIS_CACHE_GIB)
-        uint64_t resets = 0, launches = 0;     // times the plane was zeroed / launches of the variant since the scene was made
-        hipEvent_t ev_write = nullptr;         // behind the last launch of the variant (any of them may write)
-        hipStream_t write_stream = nullptr;
-        bool recorded = false, failed = false;
-    } vis_cache;
+        std::vector<uint64_t> key, last_key;   // what the contents are of; the key of the scene's last wavefront frame
+        uint64_t items = 0;                    // work items of the keyed frame
+        uint64_t stride = 0;                   // of them, those the budget has room for
+        uint64_t mark = 0;                     // items of the prefix written so far
+        uint64_t counter[2] = {0, 0};          // since the scene was made (pt_get_*_cache_stats name them)
+        hipEvent_t ev = nullptr;
+        hipStream_t stream = nullptr;          // the one `ev` was last recorded on
+        bool recorded = false, failed = false;   // (failed: the device could not provide the plane: no such cache for this scene)
+        ~FrameCache() {
+            if (ev) (void)hipEventDestroy(ev);
+        }
+        // a launch on `st` touched the plane
+        void touched(hipStream_t st) {
+            HIP_CHECK(hipEventRecord(ev, st));
+            recorded = true;
+            stream = st;
+        }
+        // `st` goes on behind the last launch that touched the plane
+        void wait_on(hipStream_t st) const {
+            if (recorded && stream != st) HIP_CHECK(hipStreamWaitEvent(st, ev, 0));
+        }
+    };
+    // Words 0-7 of ChaCha block 0 of every work item of ONE item enumeration: a sample's seed is sample + pixel x samples -
+    // the enumeration alone, not the scene, the camera, the lights, the materials or the bounces - so the frames of a
+    // camera path, of live edits or of a steady state read them instead of deriving them again.  Two planes of `stride`
+    // uint4 (words 0-3, words 4-7).  counter[0]: fill launches.
+    FrameCache rng_cache;
+    // The camera rays' closest hits of ONE view: the hit of a camera ray depends on the item enumeration (the jitter
+    // words), the camera and the geometry - not on the lights, the bounces or, in an opaque scene, the materials - so the
+    // frames of light and material edits and of a steady state read it instead of casting again.  One plane of uint4
+    // (pack_hit), written by the storing variant of the bounce-0 kernel.  A camera move resets the mark (the allocation
+    // stays).  counter[0], [1]: launches of the storing / loading variants.
+    FrameCache hit_cache;
+    // The answers of the bounce-0 shadow casts of ONE view and ONE set of light positions: in an opaque scene og_blocked
+    // for an item and a light depends on the item's camera hit, the light's kind and position and the geometry - not on the
+    // materials, the light's colour or the bounces - so the frames of material and colour edits and of a steady state read
+    // it instead of casting again.  One byte per item: two bits per light (scenes of at most four), 0 unknown / 1 not
+    // blocked / 2 blocked.  No high-water mark: zero is "unknown", and the kernel that reads the plane casts for what it
+    // finds unknown and writes the answer back (k_wf_shade_hits<.. | 64>); a moved light or camera makes a new key (one
+    // memset, the allocation stays).  counter[0], [1]: times the plane was zeroed / launches of the variant.
+    FrameCache vis_cache;
     std::vector<DevLight> host_lights;   // the lights as the device has them (the visibility cache's key)
     uint64_t camera_generation = 0;   // bumped by pt_scene_set_camera
     uint64_t queue_bytes_last = 0;   // bytes of the path queues of the last frame (pt_scene_get_info)
@@ -671,9 +673,6 @@ struct pt_scene {
         for (hipEvent_t e : events) (void)hipEventDestroy(e);
         for (hipEvent_t e : {pipe.ev_shade, pipe.ev_shadow, pipe.ev_rng, pipe.ev_chunk, pipe.ev_trace, pipe.ev_wide, pipe.ev_exact, pipe.ev_exact_go})
             if (e) (void)hipEventDestroy(e);
-        if (rng_cache.ev_fill) (void)hipEventDestroy(rng_cache.ev_fill);
-        if (hit_cache.ev_store) (void)hipEventDestroy(hit_cache.ev_store);
-        if (vis_cache.ev_write) (void)hipEventDestroy(vis_cache.ev_write);
         if (pipe.side_exact) (void)hipStreamDestroy(pipe.side_exact);
         if (pipe.side) (void)hipStreamDestroy(pipe.side);
         if (pipe.side_wide) (void)hipStreamDestroy(pipe.side_wide);
@@ -2233,9 +2232,9 @@ struct WfFrame {
     // per chunk of the plan: the last bounce that has a ray (later ones are not launched); nullptr: every bounce
     const std::vector<uint32_t>* plan_last = nullptr;
     const uint32_t* block_empty = nullptr;     // the camera-grid cull table (nullptr: no cull in this frame)
-    pt_scene::RngCache* rng_cache = nullptr;   // the scene's word cache, keyed to this frame's enumeration (nullptr: not in use)
-    pt_scene::VisCache* vis_cache = nullptr;   // the scene's shadow-visibility cache, keyed to this frame's view and lights (nullptr: not in use)
-    pt_scene::HitCache* hit_cache = nullptr;   // the scene's camera-hit cache, keyed to this frame's view (nullptr: not in use)
+    // the scene's frame caches this frame uses (frame_caches; nullptr: not in use): the words, keyed to this frame's
+    // enumeration, the camera hits, keyed to its view, the shadow visibility, keyed to its view and lights
+    pt_scene::FrameCache *rng_cache = nullptr, *hit_cache = nullptr, *vis_cache = nullptr;
     uint32_t stats_line = 0, chunk_slot = 0;   // the frame's progress through its chunks
 };
 
@@ -2470,110 +2469,90 @@ void queue_buffers(pt_scene& s, const Frame& f, const QueueEnv& qe, WfFrame& wf)
     s.frame_planned_last = wf.planned ? 1u : 0u;
 }
 
-// The scene's word cache and this frame (pt_scene::RngCache).  The cache is keyed to an enumeration - everything
-// decode_item and the batch order read - when a frame of that enumeration directly follows another of the same: a
-// one-shot render never pays for the planes, a caller alternating two profiles never thrashes them.  PT_RNG_CACHE=0:
-// off; PT_RNG_CACHE_GIB: the budget (16) - both read per frame, the tests switch them.  Frames of the KD-tree pipeline
-// and instrumented frames (PT_FLAG_COUNTERS) derive their words as before and leave the cache alone.
-void rng_cache_frame(pt_scene& s, const Frame& f, WfFrame& wf, hipStream_t stream) {
-    pt_scene::RngCache& rc = s.rng_cache;
-    const std::vector<uint64_t> key = {f.p.width, f.p.height, f.p.samples, f.o.shard_rank, f.o.shard_count, f.o.tile_w, f.o.tile_h,
-                                       (uint64_t)f.env.morton, f.batch};
-    const bool follows_same = key == rc.last_key;
-    rc.last_key = key;
-    const double gib = env_num(getenv("PT_RNG_CACHE_GIB"), 16.0);
-    if (!env_bool(getenv("PT_RNG_CACHE"), true) || !(gib > 0.0)) {
-        if (rc.buf.p) {
-            HIP_CHECK(hipDeviceSynchronize());   // (frames in flight may still read the planes)
-            rc.buf.release();
+// What differs between the scene's three frame caches, apart from their keys and the frames they serve (frame_caches).
+struct FrameCacheKind {
+    const char *env_switch, *env_gib;   // "0": off; the budget in GiB - both read per frame, the tests switch them
+    double default_gib;
+    uint32_t item_bytes;
+    uint64_t max_items;   // an enumeration of this many items or more is never keyed
+    // false: the contents are a prefix written in frame order - a new key starts an empty one once the frames in flight have
+    // finished with the old (device sync).  true: the plane is zeroed for a new key, by a memset in stream order behind the
+    // last launch that touched it - a device sync only where the allocation changes.  counter[0] counts the memsets.
+    bool zeroed;
+};
+constexpr FrameCacheKind RNG_CACHE = {"PT_RNG_CACHE", "PT_RNG_CACHE_GIB", 16.0, 32u, 1ull << 32, false};   // (W.cap carries the stride: 32 bits)
+constexpr FrameCacheKind HIT_CACHE = {"PT_HIT_CACHE", "PT_HIT_CACHE_GIB", 8.0, 16u, ~0ull, false};
+constexpr FrameCacheKind VIS_CACHE = {"PT_VIS_CACHE", "PT_VIS_CACHE_GIB", 1.0, 1u, ~0ull, true};
+
+// One frame cache and this frame, of `items` work items and key `key`: the cache if the frame uses it, keyed to `key`.
+// Keying happens when a frame of a key directly follows another of the same - also one that was switched off or not
+// eligible - and the budget has room for a stride other than the keyed one.  A frame that is not eligible leaves the
+// contents alone.
+pt_scene::FrameCache* frame_cache_frame(pt_scene::FrameCache& fc, const FrameCacheKind& kind, const std::vector<uint64_t>& key,
+                                        uint64_t items, bool eligible, hipStream_t stream) {
+    const bool follows_same = key == fc.last_key;
+    fc.last_key = key;
+    const double gib = env_num(getenv(kind.env_gib), kind.default_gib);
+    if (!env_bool(getenv(kind.env_switch), true) || !(gib > 0.0)) {
+        if (fc.buf.p) {
+            HIP_CHECK(hipDeviceSynchronize());   // (frames in flight may still use the plane)
+            fc.buf.release();
         }
-        rc.key.clear();
-        rc.items = rc.stride = rc.mark = 0;
-        return;
+        fc.key.clear();
+        fc.items = fc.stride = fc.mark = 0;
+        return nullptr;
     }
-    if (rc.failed || !wf.rng_one_plane || f.counting) return;
-    const uint64_t items = (uint64_t)f.blocks64 * 64u * f.p.samples;
-    const uint64_t stride = std::min<uint64_t>(items, (uint64_t)(gib * 1073741824.0) / 32u) & ~63ull;
-    if (key != rc.key || stride != rc.stride) {
-        // (W.cap carries the stride: 32 bits)
-        if (!follows_same || items >= (1ull << 32) || stride == 0) return;
-        HIP_CHECK(hipDeviceSynchronize());   // the frames in flight finish with the old words
-        if (rc.buf.bytes < stride * 32u || rc.buf.bytes > stride * 32u + (64u << 20)) rc.buf.release();
-        rc.key.clear();
-        rc.items = rc.stride = rc.mark = 0;
-        if (!rc.buf.try_ensure((size_t)stride * 32u)) {
-            rc.failed = true;
-            return;
+    if (fc.failed || !eligible) return nullptr;
+    const uint64_t stride = std::min<uint64_t>(items, (uint64_t)(gib * 1073741824.0) / kind.item_bytes) & ~63ull;
+    if (key != fc.key || stride != fc.stride) {
+        if (!follows_same || items >= kind.max_items || stride == 0) return nullptr;
+        const size_t bytes = (size_t)stride * kind.item_bytes;
+        const bool refit = fc.buf.bytes < bytes || fc.buf.bytes > bytes + (64u << 20);
+        if (!kind.zeroed || (refit && fc.buf.p)) HIP_CHECK(hipDeviceSynchronize());   // the frames in flight finish with the old contents
+        if (refit) fc.buf.release();
+        fc.key.clear();
+        fc.items = fc.stride = fc.mark = 0;
+        if (!fc.buf.try_ensure(bytes)) {
+            fc.failed = true;
+            return nullptr;
         }
-        if (!rc.ev_fill) HIP_CHECK(hipEventCreateWithFlags(&rc.ev_fill, hipEventDisableTiming));
-        rc.key = key;
-        rc.items = items;
-        rc.stride = stride;
+        if (!fc.ev) HIP_CHECK(hipEventCreateWithFlags(&fc.ev, hipEventDisableTiming));
+        if (kind.zeroed) {
+            fc.wait_on(stream);   // the launches of the old key on another stream are done with the plane before it is zeroed
+            HIP_CHECK(hipMemsetAsync(fc.buf.p, 0, bytes, stream));
+            fc.touched(stream);
+            ++fc.counter[0];
+        }
+        fc.key = key;
+        fc.items = items;
+        fc.stride = stride;
     }
-    wf.rng_cache = &rc;
-    // a frame on another stream than the one that filled last waits for that fill (one event: the caller orders the frames
-    // of a scene - they share its queues - so the earlier fills are behind it)
-    if (rc.recorded && rc.fill_stream != stream) HIP_CHECK(hipStreamWaitEvent(stream, rc.ev_fill, 0));
+    fc.wait_on(stream);   // a frame on another stream than the last launch that touched the plane
+    return &fc;
 }
 
-// The scene's camera-hit cache and this frame (pt_scene::HitCache), after rng_cache_frame.  The key is the word cache's -
-// the enumeration - plus the camera generation and the camera grid's resolution (a new light COUNT may rebuild the grid at
-// another resolution, and with it the cull table that decides which wavefronts store): the cache is keyed to a view when a
-// frame of that view directly follows another, so the first frame of a view never stores, a camera path never stores and
-// never allocates.  Eligible: opaque, uninstrumented frames of the fused pipeline that read the word cache; any other
-// frame leaves the records alone - those of a scene that turned translucent are still the opaque cast's for that camera.
-// PT_HIT_CACHE=0: off; PT_HIT_CACHE_GIB: the budget (8) - both read per frame.
-void hit_cache_frame(pt_scene& s, const Frame& f, WfFrame& wf, hipStream_t stream) {
-    pt_scene::HitCache& hc = s.hit_cache;
-    const std::vector<uint64_t> key = {f.p.width, f.p.height, f.p.samples, f.o.shard_rank, f.o.shard_count, f.o.tile_w, f.o.tile_h,
-                                       (uint64_t)f.env.morton, f.batch, s.camera_generation, s.cam_res};
-    const bool follows_same = key == hc.last_key;
-    hc.last_key = key;
-    const double gib = env_num(getenv("PT_HIT_CACHE_GIB"), 8.0);
-    if (!env_bool(getenv("PT_HIT_CACHE"), true) || !(gib > 0.0)) {
-        if (hc.buf.p) {
-            HIP_CHECK(hipDeviceSynchronize());   // (frames in flight may still read the plane)
-            hc.buf.release();
-        }
-        hc.key.clear();
-        hc.items = hc.stride = hc.mark = 0;
-        return;
-    }
-    if (hc.failed || !wf.rng_cache || !f.bounce0_fused || f.alpha || f.counting) return;
+// The scene's frame caches and this frame: one key, extended from cache to cache, and the frames each serves.
+void frame_caches(pt_scene& s, const Frame& f, WfFrame& wf, hipStream_t stream) {
     const uint64_t items = (uint64_t)f.blocks64 * 64u * f.p.samples;
-    const uint64_t stride = std::min<uint64_t>(items, (uint64_t)(gib * 1073741824.0) / 16u) & ~63ull;
-    if (key != hc.key || stride != hc.stride) {
-        if (!follows_same || stride == 0) return;
-        HIP_CHECK(hipDeviceSynchronize());   // the frames in flight finish with the old records
-        if (hc.buf.bytes < stride * 16u || hc.buf.bytes > stride * 16u + (64u << 20)) hc.buf.release();
-        hc.key.clear();
-        hc.items = hc.stride = hc.mark = 0;
-        if (!hc.buf.try_ensure((size_t)stride * 16u)) {
-            hc.failed = true;
-            return;
-        }
-        if (!hc.ev_store) HIP_CHECK(hipEventCreateWithFlags(&hc.ev_store, hipEventDisableTiming));
-        hc.key = key;
-        hc.items = items;
-        hc.stride = stride;
-    }
-    wf.hit_cache = &hc;
-    // a frame on another stream than the one that stored last waits for that launch (as the word cache's fill)
-    if (hc.recorded && hc.store_stream != stream) HIP_CHECK(hipStreamWaitEvent(stream, hc.ev_store, 0));
-}
-
-// The scene's shadow-visibility cache and this frame (pt_scene::VisCache), after hit_cache_frame.  The key is the hit
-// cache's plus the light count and every light's kind and position, bit for bit - not its colour or `tame`, not the
-// materials, not the bounces.  As the hit cache, the plane is keyed when a frame's key equals that of the frame before: the
-// first frame after a moved light or camera does nothing new, a light orbit or a camera path never zeroes and never
-// allocates.  Keying is one memset on the frame's stream; from then on every chunk that LOADs its hits and lies below the
-// plane's stride runs the variant that reads the plane and fills in what is unknown.  Eligible: the frames the hit cache
-// serves, with one to four lights; any other frame leaves the bits alone - those of a scene that turned translucent are
-// still the opaque geometry's.  PT_VIS_CACHE=0: off; PT_VIS_CACHE_GIB: the budget (1) - both read per frame.
-void vis_cache_frame(pt_scene& s, const Frame& f, WfFrame& wf, hipStream_t stream) {
-    pt_scene::VisCache& vc = s.vis_cache;
+    // The words: keyed to an enumeration - everything decode_item and the batch order read.  Frames of the KD-tree pipeline
+    // and instrumented frames (PT_FLAG_COUNTERS) derive their words as before and leave the cache alone.
     std::vector<uint64_t> key = {f.p.width, f.p.height, f.p.samples, f.o.shard_rank, f.o.shard_count, f.o.tile_w, f.o.tile_h,
-                                 (uint64_t)f.env.morton, f.batch, s.camera_generation, s.cam_res, s.host_lights.size()};
+                                 (uint64_t)f.env.morton, f.batch};
+    wf.rng_cache = frame_cache_frame(s.rng_cache, RNG_CACHE, key, items, wf.rng_one_plane && !f.counting, stream);
+    // The camera hits: the enumeration plus the camera generation and the camera grid's resolution (a new light COUNT may
+    // rebuild the grid at another resolution, and with it the cull table that decides which wavefronts store).  The first
+    // frame of a view never stores, a camera path never stores and never allocates.  Eligible: opaque, uninstrumented
+    // frames of the fused pipeline that read the word cache; any other frame leaves the records alone - those of a scene
+    // that turned translucent are still the opaque cast's for that camera.
+    key.insert(key.end(), {s.camera_generation, (uint64_t)s.cam_res});
+    wf.hit_cache = frame_cache_frame(s.hit_cache, HIT_CACHE, key, items, wf.rng_cache && f.bounce0_fused && !f.alpha && !f.counting, stream);
+    // The shadow visibility: the hits' key plus the light count and every light's kind and position, bit for bit - not its
+    // colour or `tame`, not the materials, not the bounces.  The first frame after a moved light or camera does nothing
+    // new, a light orbit or a camera path never zeroes and never allocates; from the keying frame's memset on, every chunk
+    // that LOADs its hits and lies below the plane's stride runs the variant that reads the plane and fills in what is
+    // unknown.  Eligible: the frames the hit cache serves, with one to four lights; any other frame leaves the bits alone -
+    // those of a scene that turned translucent are still the opaque geometry's.
+    key.push_back(s.host_lights.size());
     for (const DevLight& L : s.host_lights) {
         uint32_t w[4];
         memcpy(w, &L.kind, 4);
@@ -2581,48 +2560,7 @@ void vis_cache_frame(pt_scene& s, const Frame& f, WfFrame& wf, hipStream_t strea
         key.push_back((uint64_t)w[0] << 32 | w[1]);
         key.push_back((uint64_t)w[2] << 32 | w[3]);
     }
-    const bool follows_same = key == vc.last_key;
-    vc.last_key = key;
-    const double gib = env_num(getenv("PT_VIS_CACHE_GIB"), 1.0);
-    if (!env_bool(getenv("PT_VIS_CACHE"), true) || !(gib > 0.0)) {
-        if (vc.buf.p) {
-            HIP_CHECK(hipDeviceSynchronize());   // (frames in flight may still read the plane)
-            vc.buf.release();
-        }
-        vc.key.clear();
-        vc.items = vc.stride = 0;
-        return;
-    }
-    if (vc.failed || !wf.hit_cache || s.host_lights.empty() || s.host_lights.size() > 4u) return;
-    const uint64_t items = (uint64_t)f.blocks64 * 64u * f.p.samples;
-    const uint64_t stride = std::min<uint64_t>(items, (uint64_t)(gib * 1073741824.0)) & ~63ull;
-    if (key != vc.key || stride != vc.stride) {
-        if (!follows_same || stride == 0) return;
-        vc.key.clear();
-        vc.items = vc.stride = 0;
-        if (vc.buf.bytes < stride || vc.buf.bytes > stride + (64u << 20)) {
-            if (vc.buf.p) HIP_CHECK(hipDeviceSynchronize());   // (frames in flight may still use the plane)
-            vc.buf.release();
-            if (!vc.buf.try_ensure((size_t)stride)) {
-                vc.failed = true;
-                return;
-            }
-        }
-        if (!vc.ev_write) HIP_CHECK(hipEventCreateWithFlags(&vc.ev_write, hipEventDisableTiming));
-        // the launches of the old key on another stream are done with the plane before it is zeroed
-        if (vc.recorded && vc.write_stream != stream) HIP_CHECK(hipStreamWaitEvent(stream, vc.ev_write, 0));
-        HIP_CHECK(hipMemsetAsync(vc.buf.p, 0, (size_t)stride, stream));
-        HIP_CHECK(hipEventRecord(vc.ev_write, stream));
-        vc.recorded = true;
-        vc.write_stream = stream;
-        ++vc.resets;
-        vc.key = key;
-        vc.items = items;
-        vc.stride = stride;
-    }
-    wf.vis_cache = &vc;
-    // a frame on another stream than the one that wrote last waits for that launch (as the hit cache's ev_store)
-    if (vc.recorded && vc.write_stream != stream) HIP_CHECK(hipStreamWaitEvent(stream, vc.ev_write, 0));
+    wf.vis_cache = frame_cache_frame(s.vis_cache, VIS_CACHE, key, items, wf.hit_cache && !s.host_lights.empty() && s.host_lights.size() <= 4u, stream);
 }
 
 // This frame's counts, one line per (batch, chunk): taken every frame (a few KB) - the first frame's feed the plan, the
@@ -2856,34 +2794,30 @@ void shade_stage(pt_scene& s, const Frame& f, const WfFrame& wf, const Chunk& c,
         else dispatch(go, f.alpha, f.counting, c.prim);
         HIP_CHECK(hipGetLastError());
     };
-    // the cached opaque bounce-0 kernel with the camera-hit cache (k_wf_shade_hits): stores the chunk's hits or loads them
+    // the cached opaque bounce-0 kernel with the camera-hit cache (k_wf_shade_hits): stores the chunk's hits or loads them;
+    // | 64, with the shadow-visibility cache (an overload with one parameter more): loads the hits, reads the chunk's
+    // visibility bytes and fills in the unknown
     auto launch_hits = [&](auto grid) {
         constexpr int G = decltype(grid)::value;
-        hipLaunchKernelGGL((k_wf_shade_hits<G>), dim3(shade_grid), dim3(WF_SHADE_THREADS), 0, c.st_main, f.dev, W, f.d_tiles,
-                           (const uint4*)c.rng_planes, c.hit_plane, c.q_out, (float4*)pipe.shadow.p, (float4*)pipe.contrib.p,
-                           (float*)s.staging_buf.p, (uint32_t*)pipe.exact[(b + 1) & 1].p, block_empty, c.wctr);
-        HIP_CHECK(hipGetLastError());
-    };
-    // ... and with the shadow-visibility cache: loads the hits, reads the chunk's visibility bytes and fills in the unknown
-    auto launch_vis = [&](auto grid) {
-        constexpr int G = decltype(grid)::value;
-        hipLaunchKernelGGL((k_wf_shade_hits<G>), dim3(shade_grid), dim3(WF_SHADE_THREADS), 0, c.st_main, f.dev, W, f.d_tiles,
-                           (const uint4*)c.rng_planes, c.hit_plane, c.q_out, (float4*)pipe.shadow.p, (float4*)pipe.contrib.p,
-                           (float*)s.staging_buf.p, (uint32_t*)pipe.exact[(b + 1) & 1].p, block_empty, c.wctr, c.vis_plane);
+        auto go = [&](auto... vis_plane) {
+            hipLaunchKernelGGL((k_wf_shade_hits<G>), dim3(shade_grid), dim3(WF_SHADE_THREADS), 0, c.st_main, f.dev, W, f.d_tiles,
+                               (const uint4*)c.rng_planes, c.hit_plane, c.q_out, (float4*)pipe.shadow.p, (float4*)pipe.contrib.p,
+                               (float*)s.staging_buf.p, (uint32_t*)pipe.exact[(b + 1) & 1].p, block_empty, c.wctr, vis_plane...);
+        };
+        if constexpr (G & 64) go(c.vis_plane);
+        else go();
         HIP_CHECK(hipGetLastError());
     };
     auto launch_shade = [&] {
-        if (c.grid_mode == 3 && c.cached && c.hit_mode == 32 && c.vis_plane) {
-            if (s.grids.ortho) launch_vis(std::integral_constant<int, (15 | 32 | 64)>{});
-            else launch_vis(std::integral_constant<int, (11 | 32 | 64)>{});
-            return;
-        }
         if (c.grid_mode == 3 && c.cached && c.hit_mode) {
-            switch ((s.grids.ortho ? 15 : 11) | c.hit_mode) {
-            case 11 | 16: launch_hits(std::integral_constant<int, (11 | 16)>{}); break;
-            case 11 | 32: launch_hits(std::integral_constant<int, (11 | 32)>{}); break;
-            case 15 | 16: launch_hits(std::integral_constant<int, (15 | 16)>{}); break;
-            default: launch_hits(std::integral_constant<int, (15 | 32)>{}); break;
+            // GRIDX: 11 / 15 (orthographic branch) + 16 STORE / 32 LOAD + 64 VIS (LOAD only)
+            switch ((s.grids.ortho ? 15 : 11) | c.hit_mode | (c.hit_mode == 32 && c.vis_plane ? 64 : 0)) {
+            case 27: launch_hits(std::integral_constant<int, 27>{}); break;
+            case 43: launch_hits(std::integral_constant<int, 43>{}); break;
+            case 31: launch_hits(std::integral_constant<int, 31>{}); break;
+            case 47: launch_hits(std::integral_constant<int, 47>{}); break;
+            case 107: launch_hits(std::integral_constant<int, 107>{}); break;
+            default: launch_hits(std::integral_constant<int, 111>{}); break;
             }
             return;
         }
@@ -2996,42 +2930,37 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
     W.walk_steps = f.env.walk ? f.env.walk : 20u;
     c.wctr = (WfCounters*)pipe.ctr.p;
     HIP_CHECK(hipMemsetAsync(c.wctr, 0, sizeof(WfCounters) * (f.p.bounces + 3), c.st_main));
-    if (fused_rng && wf.rng_cache) {
-        // The scene's word cache: a chunk below its high-water mark reads it, the chunk next above the mark - if the
-        // budget has room for it - is filled first, here on the frame's stream.  (Chunk boundaries differ between a first
-        // frame and a planned one: the prefix does not care.)
-        pt_scene::RngCache& rc = *wf.rng_cache;
-        const uint64_t g0 = (uint64_t)(P.sample_begin / f.batch) * wf.items_per_batch + base, g1 = g0 + W.n_items;
-        if (g1 <= rc.stride && g0 <= rc.mark) {
-            uint4* planes = (uint4*)rc.buf.p + g0;
-            if (g1 > rc.mark) {
-                const uint32_t first = (uint32_t)(rc.mark - g0), n = (uint32_t)(g1 - rc.mark);
-                tl.begin(0);
-                hipLaunchKernelGGL(k_wf_rng_fill, dim3((n + 255u) / 256u), dim3(256), 0, c.st_main, W, f.d_tiles, first, n, planes,
-                                   (uint32_t)rc.stride);
-                HIP_CHECK(hipGetLastError());
-                tl.end();
-                HIP_CHECK(hipEventRecord(rc.ev_fill, c.st_main));
-                rc.recorded = true;
-                rc.fill_stream = c.st_main;
-                rc.mark = g1;
-                ++rc.fills;
-            }
-            c.cached = true;
-            c.rng_planes = planes;
-            W.cap = (uint32_t)rc.stride;
-            W.rng_first_plane = 0u;
+    // The scene's frame caches, one prefix in the frame-global item g (chunk boundaries differ between a first frame and a
+    // planned one: the prefix does not care); this chunk is [g0, g1)
+    const uint64_t g0 = (uint64_t)(P.sample_begin / f.batch) * wf.items_per_batch + base, g1 = g0 + W.n_items;
+    // does the chunk read the prefix (wholly below the mark), or extend it (next above the mark, the budget has room for all of it)?
+    auto reads = [&](const pt_scene::FrameCache* fc) { return fc && g1 <= fc->mark; };
+    auto extends = [&](const pt_scene::FrameCache* fc) { return fc && g1 > fc->mark && g1 <= fc->stride && g0 <= fc->mark; };
+    if (fused_rng && (reads(wf.rng_cache) || extends(wf.rng_cache))) {
+        // the words: read from the cache, filled first - here on the frame's stream - by the chunk that extends the prefix
+        pt_scene::FrameCache& rc = *wf.rng_cache;
+        uint4* planes = (uint4*)rc.buf.p + g0;
+        if (extends(&rc)) {
+            const uint32_t first = (uint32_t)(rc.mark - g0), n = (uint32_t)(g1 - rc.mark);
+            tl.begin(0);
+            hipLaunchKernelGGL(k_wf_rng_fill, dim3((n + 255u) / 256u), dim3(256), 0, c.st_main, W, f.d_tiles, first, n, planes,
+                               (uint32_t)rc.stride);
+            HIP_CHECK(hipGetLastError());
+            tl.end();
+            rc.touched(c.st_main);
+            rc.mark = g1;
+            ++rc.counter[0];
         }
+        c.cached = true;
+        c.rng_planes = planes;
+        W.cap = (uint32_t)rc.stride;
+        W.rng_first_plane = 0u;
     }
-    if (c.cached && wf.hit_cache) {
-        // The camera-hit cache, the same prefix in g: a chunk wholly below the mark loads its hits, the chunk next above the
-        // mark - if the budget has room for all of it - stores them; anything else casts as before.
-        pt_scene::HitCache& hc = *wf.hit_cache;
-        const uint64_t g0 = (uint64_t)(P.sample_begin / f.batch) * wf.items_per_batch + base, g1 = g0 + W.n_items;
-        if (g1 <= hc.mark) c.hit_mode = 32;
-        else if (g1 <= hc.stride && g0 <= hc.mark) c.hit_mode = 16;
-        if (c.hit_mode) c.hit_plane = (uint4*)hc.buf.p + g0;
-        // the shadow-visibility cache: a chunk that loads its hits and lies wholly below the plane's stride
+    if (c.cached) {
+        // the camera hits: loaded by the bounce-0 kernel, or stored by it; anything else casts as before.  The shadow
+        // visibility: a chunk that loads its hits and lies wholly below the plane's stride
+        c.hit_mode = reads(wf.hit_cache) ? 32 : extends(wf.hit_cache) ? 16 : 0;
+        if (c.hit_mode) c.hit_plane = (uint4*)wf.hit_cache->buf.p + g0;
         if (c.hit_mode == 32 && wf.vis_cache && g1 <= wf.vis_cache->stride) c.vis_plane = (uint8_t*)wf.vis_cache->buf.p + g0;
     }
     if (fused_rng && !c.cached && pipe.rng[0].bytes < (size_t)wf.cap * 16u) {   // (queue_buffers left the plane out)
@@ -3087,20 +3016,14 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
         if (c.grid_mode < 2) trace_stage(s, f, c, tl);   // (grid_mode >= 2: k_wf_shade casts the camera rays itself)
         shade_stage(s, f, wf, c, tl);
         if (c.prim && c.hit_mode == 16) {   // the records are behind this launch: the prefix grows by the chunk
-            pt_scene::HitCache& hc = *wf.hit_cache;
-            HIP_CHECK(hipEventRecord(hc.ev_store, c.st_main));
-            hc.recorded = true;
-            hc.store_stream = c.st_main;
-            hc.mark = (uint64_t)(c.hit_plane - (uint4*)hc.buf.p) + W.n_items;
-            ++hc.stores;
+            wf.hit_cache->touched(c.st_main);
+            wf.hit_cache->mark = g1;
+            ++wf.hit_cache->counter[0];
         } else if (c.prim && c.hit_mode == 32) {
-            ++wf.hit_cache->loads;
+            ++wf.hit_cache->counter[1];
             if (c.vis_plane) {   // (any such launch may write the plane)
-                pt_scene::VisCache& vc = *wf.vis_cache;
-                HIP_CHECK(hipEventRecord(vc.ev_write, c.st_main));
-                vc.recorded = true;
-                vc.write_stream = c.st_main;
-                ++vc.launches;
+                wf.vis_cache->touched(c.st_main);
+                ++wf.vis_cache->counter[1];
             }
         }
         shadow_stage(s, f, c, tl);
@@ -3217,9 +3140,7 @@ void render_device(pt_scene& s, const pt_profile& p, const pt_opts* opts_in, voi
     if (f.wavefront) {
         const QueueEnv qe = queue_env();
         wf = frame_plan(s, f, qe);
-        rng_cache_frame(s, f, wf, stream);
-        hit_cache_frame(s, f, wf, stream);
-        vis_cache_frame(s, f, wf, stream);
+        frame_caches(s, f, wf, stream);
         queue_buffers(s, f, qe, wf);
         stats_slots(s, f, wf);
         side_streams(s, f, wf);
@@ -3981,6 +3902,14 @@ Rccl& rccl() {
         int _e = (expr);                                                                                           \
         if (_e != 0) fail(PT_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, rccl().GetErrorString(_e), __FILE__, __LINE__); \
     } while (0)
+
+// pt_get_*_cache_stats: each value to the caller's variable; nothing is written unless every pointer is given.
+int cache_stats(std::initializer_list<std::pair<uint64_t*, uint64_t>> out) {
+    for (const auto& o : out)
+        if (!o.first) return PT_ERR_INVALID;
+    for (const auto& o : out) *o.first = o.second;
+    return PT_OK;
+}
 }  // namespace
 
 struct pt_comm {
@@ -4102,32 +4031,19 @@ int pt_get_cull_stats(const pt_scene* scene, uint32_t* n_blocks, uint32_t* n_emp
     });
 }
 int pt_get_rng_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* fills) {
-    if (!scene || !bytes || !items || !items_cached || !fills) return PT_ERR_INVALID;
-    const pt_scene::RngCache& rc = scene->rng_cache;
-    *bytes = rc.buf.bytes;
-    *items = rc.items;
-    *items_cached = rc.mark;
-    *fills = rc.fills;
-    return PT_OK;
+    if (!scene) return PT_ERR_INVALID;
+    const pt_scene::FrameCache& fc = scene->rng_cache;
+    return cache_stats({{bytes, fc.buf.bytes}, {items, fc.items}, {items_cached, fc.mark}, {fills, fc.counter[0]}});
 }
 int pt_get_hit_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* stores, uint64_t* loads) {
-    if (!scene || !bytes || !items || !items_cached || !stores || !loads) return PT_ERR_INVALID;
-    const pt_scene::HitCache& hc = scene->hit_cache;
-    *bytes = hc.buf.bytes;
-    *items = hc.items;
-    *items_cached = hc.mark;
-    *stores = hc.stores;
-    *loads = hc.loads;
-    return PT_OK;
+    if (!scene) return PT_ERR_INVALID;
+    const pt_scene::FrameCache& fc = scene->hit_cache;
+    return cache_stats({{bytes, fc.buf.bytes}, {items, fc.items}, {items_cached, fc.mark}, {stores, fc.counter[0]}, {loads, fc.counter[1]}});
 }
 int pt_get_vis_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* resets, uint64_t* launches) {
-    if (!scene || !bytes || !items || !resets || !launches) return PT_ERR_INVALID;
-    const pt_scene::VisCache& vc = scene->vis_cache;
-    *bytes = vc.buf.bytes;
-    *items = vc.items;
-    *resets = vc.resets;
-    *launches = vc.launches;
-    return PT_OK;
+    if (!scene) return PT_ERR_INVALID;
+    const pt_scene::FrameCache& fc = scene->vis_cache;
+    return cache_stats({{bytes, fc.buf.bytes}, {items, fc.items}, {resets, fc.counter[0]}, {launches, fc.counter[1]}});
 }
 int pt_kernel_occupancy(int device, int which, int* blocks_per_cu) {
     return guarded([&] {

@@ -836,7 +836,7 @@ __global__ __launch_bounds__(256) void k_wf_rng(DevScene S, WfParams W, const ui
     rng_planes[(size_t)W.cap + rel] = make_uint4(w[4], w[5], w[6], w[7]);
 }
 
-// The same block for the scene's word cache (pt_gpu.hip RngCache): items [first, first + n) of the chunk, the RAW words
+// The same block for the scene's word cache (pt_gpu.hip FrameCache rng_cache): items [first, first + n) of the chunk, the RAW words
 // 0-3 and 4-7 at planes[rel] and planes[stride + rel] (planes: the chunk's first item in the cache).  Items outside the
 // image get the words of whatever pixel index they decode to: nobody reads them.
 __global__ __launch_bounds__(256) void k_wf_rng_fill(WfParams W, const uint32_t* __restrict__ tile_offsets, uint32_t first, uint32_t n,
@@ -2032,14 +2032,14 @@ static_assert(WF_PARK_SLOTS + 1u <= 39, "four workgroups of the bounce-0 kernel 
 //     the words of bounces 1 and 2 (plane 1 of the RNG planes; a path has made at least four draws by then).
 // GRIDX = GRID + 4 * DIRL + 8 * CACHED; DIRL: some light is directional (orthographic grid branch of og_light_radiance
 // compiled in).  CACHED (GRID 3 only): words 0-7 of the item's block are READ from the scene's word cache (pt_gpu.hip
-// RngCache: rng_planes points at the chunk's first item there, W.cap is the cache's stride, W.rng_first_plane 0) - the raw
+// FrameCache rng_cache: rng_planes points at the chunk's first item there, W.cap is the cache's stride, W.rng_first_plane 0) - the raw
 // words, not the screen position: that depends on the camera, the words on the item enumeration alone.
 // + 16 * STORE + 32 * LOAD (CACHED, opaque, bounce 0 only; k_wf_shade_hits below): the scene's camera-hit cache (pt_gpu.hip
-// HitCache; hit_plane points at the chunk's first item there).  The closest hit of a camera ray depends on the item
+// FrameCache hit_cache; hit_plane points at the chunk's first item there).  The closest hit of a camera ray depends on the item
 // enumeration, the camera and the geometry - not on the lights, the bounces or, in an opaque scene, the materials - so
 // STORE writes pack_hit of the cast's result for every item, and LOAD reads that record instead of casting: no og_cell on
 // the camera grid, no og_next_hit.  The ray itself is still derived: shading needs o and d.
-// + 64 * VIS (LOAD only; the second k_wf_shade_hits below): the scene's shadow-visibility cache (pt_gpu.hip VisCache;
+// + 64 * VIS (LOAD only; the second k_wf_shade_hits below): the scene's shadow-visibility cache (pt_gpu.hip FrameCache vis_cache;
 // vis_plane points at the chunk's first item there) - a light whose bits are known is not cast for.
 // (S and W FIRST, in this order: the PARK variants read them again through the kernarg segment, wf_opaque_arg)
 template <bool ALPHA, bool COUNT, bool PRIMARY, int GRIDX>
@@ -2089,7 +2089,7 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_
 #include "pt_wf_shade_body.h"
 }
 
-// ... and with the scene's shadow-visibility cache (pt_gpu.hip VisCache): GRIDX = 11 or 15, + 32 (LOAD) + 64 (VIS).  In an
+// ... and with the scene's shadow-visibility cache (pt_gpu.hip FrameCache vis_cache): GRIDX = 11 or 15, + 32 (LOAD) + 64 (VIS).  In an
 // opaque scene the answer of a bounce-0 shadow cast - og_blocked for one item and one light - depends on the camera hit,
 // the light's kind and position and the geometry: not on the materials, the light's colour or the bounces.  vis_plane
 // holds it, one byte per item of the chunk (two bits per light, zero: unknown); a lane casts for the lights it does not

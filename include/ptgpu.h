@@ -515,6 +515,18 @@ int pt_get_hit_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* ite
  * PT_VIS_CACHE=0 switches the cache off, PT_VIS_CACHE_GIB (1) is its budget; both are read per frame.  The bytes are
  * not part of pt_scene_info's queue_bytes or device_bytes. */
 int pt_get_vis_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* resets, uint64_t* launches);
+/* The scene's cache of bounce-1 hits (the closest hit of every work item's bounce-1 ray, 16 B per item; in an opaque scene
+ * that ray is made from the camera hit, the material there and the item's random words - not from a light's position,
+ * kind, colour or count, nor from the bounce count - so the frames of light edits and of a steady state read its hit
+ * instead of casting): its device bytes, the work items of the view and material table it is keyed to (0: none - it is
+ * keyed, and zeroed, when a frame directly follows another of the same view and materials), how many of them are cached
+ * so far, how often it was zeroed, the storing and the loading launches, and the casts the loading launches found no
+ * record for and left to the exact walker, since the scene was made.  Only frames that use the camera-hit cache and have
+ * at least one bounce use it; pt_scene_set_materials and pt_scene_set_camera re-key it (the allocation stays), light
+ * edits keep it.  PT_HIT1_CACHE=0 switches the cache off, PT_HIT1_CACHE_GIB (8) is its budget; both are read per frame.
+ * The call waits for the device.  The bytes are not part of pt_scene_info's queue_bytes or device_bytes. */
+int pt_get_hit1_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* resets,
+                            uint64_t* stores, uint64_t* loads, uint64_t* unknown_casts);
 /* Workgroups of the fused bounce-0 kernel of opaque scenes that the runtime places on one compute unit of `device`
  * (hipOccupancyMaxActiveBlocksPerMultiprocessor at the kernel's workgroup size): which = 0 the variant that computes
  * its ChaCha words, 1 the variant that reads them from the word cache, 2 and 3 the variants of 1 that store and that

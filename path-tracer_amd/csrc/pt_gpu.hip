@@ -578,6 +578,9 @@ struct pt_scene {
         hipEvent_t done = nullptr;
         bool pending = false, valid = false, planned = false;
         bool stats_planned = false;   // the counts on their way were taken by a frame that ran the plan
+        // the counts (on their way / the plan's) are of a frame whose bounce 1 loaded its hits (hit1_cache): its bounce-0 kernel
+        // listed no ray for k_wf_trace_exact, so the exact count of bounce 1 is lower than a frame that casts would have
+        bool stats_hit1_loads = false, plan_hit1_loads = false;
         std::vector<uint32_t> first_item_of_slot;         // (which chunk a slot was)
         // the plan made from them: work items per chunk, records per queue / hit / shadow / exact array, the bounces whose
         // shadow casts go inline; fresh until its buffers have been allocated once (buffers much larger are given back then)
@@ -612,7 +615,7 @@ struct pt_scene {
         uint64_t items = 0;                    // work items of the keyed frame
         uint64_t stride = 0;                   // of them, those the budget has room for
         uint64_t mark = 0;                     // items of the prefix written so far
-        uint64_t counter[2] = {0, 0};          // since the scene was made (pt_get_*_cache_stats name them)
+        uint64_t counter[3] = {0, 0, 0};       // since the scene was made (pt_get_*_cache_stats name them)
         hipEvent_t ev = nullptr;
         hipStream_t stream = nullptr;          // the one `ev` was last recorded on
         bool recorded = false, failed = false;   // (failed: the device could not provide the plane: no such cache for this scene)
@@ -649,8 +652,20 @@ struct pt_scene {
     // finds unknown and writes the answer back (k_wf_shade_hits<.. | 64>); a moved light or camera makes a new key (one
     // memset, the allocation stays).  counter[0], [1]: times the plane was zeroed / launches of the variant.
     FrameCache vis_cache;
+    // The closest hits of the bounce-1 rays of ONE view and ONE material table: in an opaque scene that ray is made from the
+    // item's camera hit, the material record there and words 2-3 of its ChaCha block - not from a light's position, kind,
+    // colour or count, nor from the bounces - so the frames of light edits and of a steady state read its hit instead of
+    // casting again.  One plane of uint4 (pack_hit, bit 28 of the word flipped: zero is "never written"), zeroed when it is
+    // keyed AND filled as a prefix: which items reach bounce 1 may differ between frames of one key (escape masks, surfaces
+    // lit through the shadow queue), so a chunk below the mark may still meet an item without a record, and casts for it
+    // (k_wf_hits_store / k_wf_hits_load in pt_wavefront.h).  A camera move resets the mark.  counter[0], [1], [2]: times
+    // the plane was zeroed / storing launches / loading launches; hit1_unknown: the casts the loading launches left to
+    // k_wf_trace_exact (one uint64 on the device).
+    FrameCache hit1_cache;
+    DeviceBuffer hit1_unknown;
     std::vector<DevLight> host_lights;   // the lights as the device has them (the visibility cache's key)
     uint64_t camera_generation = 0;   // bumped by pt_scene_set_camera
+    uint64_t material_generation = 0;   // bumped by pt_scene_set_materials
     uint64_t queue_bytes_last = 0;   // bytes of the path queues of the last frame (pt_scene_get_info)
     uint32_t queue_chunk_last = 0, frame_planned_last = 0;
     // escape masks: wanted (PT_ESCAPE), built when the scene has rendered `escape_after` frames of the default pipeline
@@ -1837,6 +1852,7 @@ void scene_set_camera(pt_scene& s, const pt_camera& cam) {
     // the camera-hit cache was this camera's: the next view starts at an empty prefix (the allocation stays)
     ++s.camera_generation;
     s.hit_cache.mark = 0;
+    s.hit1_cache.mark = 0;
 }
 
 // pt_scene_set_lights.  The light grids are those grids_on_device builds for the new lights (all or none), their parameters
@@ -1911,6 +1927,7 @@ void scene_set_materials(pt_scene& s, const pt_material* materials, uint32_t n) 
     s.dev.materials = d_mat;
     s.dev.has_translucent = translucent ? 1u : 0u;
     s.info.has_translucent = translucent;
+    ++s.material_generation;
     drop_frame_state(s);
 }
 
@@ -2235,6 +2252,8 @@ struct WfFrame {
     // the scene's frame caches this frame uses (frame_caches; nullptr: not in use): the words, keyed to this frame's
     // enumeration, the camera hits, keyed to its view, the shadow visibility, keyed to its view and lights
     pt_scene::FrameCache *rng_cache = nullptr, *hit_cache = nullptr, *vis_cache = nullptr;
+    pt_scene::FrameCache* hit1_cache = nullptr;   // the bounce-1 hits, keyed to the frame's view and material table
+    uint32_t hit1_holes = 0;                      // PT_HIT1_CACHE_HOLES (a study switch, read per frame)
     uint32_t stats_line = 0, chunk_slot = 0;   // the frame's progress through its chunks
 };
 
@@ -2383,6 +2402,7 @@ WfFrame frame_plan(pt_scene& s, const Frame& f, const QueueEnv& qe) {
             if (!fs->planned) {
                 fs->valid = true;
                 fs->planned = make_plan(*fs, f, wf, qe);
+                fs->plan_hit1_loads = fs->stats_hit1_loads;
             }
         }
     }
@@ -2469,7 +2489,7 @@ void queue_buffers(pt_scene& s, const Frame& f, const QueueEnv& qe, WfFrame& wf)
     s.frame_planned_last = wf.planned ? 1u : 0u;
 }
 
-// What differs between the scene's three frame caches, apart from their keys and the frames they serve (frame_caches).
+// What differs between the scene's four frame caches, apart from their keys and the frames they serve (frame_caches).
 struct FrameCacheKind {
     const char *env_switch, *env_gib;   // "0": off; the budget in GiB - both read per frame, the tests switch them
     double default_gib;
@@ -2483,6 +2503,9 @@ struct FrameCacheKind {
 constexpr FrameCacheKind RNG_CACHE = {"PT_RNG_CACHE", "PT_RNG_CACHE_GIB", 16.0, 32u, 1ull << 32, false};   // (W.cap carries the stride: 32 bits)
 constexpr FrameCacheKind HIT_CACHE = {"PT_HIT_CACHE", "PT_HIT_CACHE_GIB", 8.0, 16u, ~0ull, false};
 constexpr FrameCacheKind VIS_CACHE = {"PT_VIS_CACHE", "PT_VIS_CACHE_GIB", 1.0, 1u, ~0ull, true};
+// (zeroed AND a prefix: the memset of a new key also starts an empty prefix - frame_cache_frame resets the mark either way -
+// and, there being no device sync, every launch that reads the plane records the event too, not only those that write)
+constexpr FrameCacheKind HIT1_CACHE = {"PT_HIT1_CACHE", "PT_HIT1_CACHE_GIB", 8.0, 16u, ~0ull, true};
 
 // One frame cache and this frame, of `items` work items and key `key`: the cache if the frame uses it, keyed to `key`.
 // Keying happens when a frame of a key directly follows another of the same - also one that was switched off or not
@@ -2546,6 +2569,25 @@ void frame_caches(pt_scene& s, const Frame& f, WfFrame& wf, hipStream_t stream) 
     // that turned translucent are still the opaque cast's for that camera.
     key.insert(key.end(), {s.camera_generation, (uint64_t)s.cam_res});
     wf.hit_cache = frame_cache_frame(s.hit_cache, HIT_CACHE, key, items, wf.rng_cache && f.bounce0_fused && !f.alpha && !f.counting, stream);
+    // The bounce-1 hits: the camera hits' key plus the material generation - the BRDF at the camera hit makes the ray - and
+    // NOT the lights or the bounces.  The first frame after a material edit or a camera move neither loads nor stores, the
+    // second zeroes the plane and stores, the third loads; a light orbit loads throughout.  Eligible: the frames the hit
+    // cache serves that have a bounce 1; any other frame leaves the records alone.
+    {
+        std::vector<uint64_t> key1 = key;
+        key1.push_back(s.material_generation);
+        wf.hit1_cache = frame_cache_frame(s.hit1_cache, HIT1_CACHE, key1, items, wf.hit_cache && f.p.bounces >= 1u, stream);
+        if (wf.hit1_cache && !s.hit1_unknown.p) {
+            s.hit1_unknown.ensure(8);
+            HIP_CHECK(hipMemset(s.hit1_unknown.p, 0, 8));
+        }
+        wf.hit1_holes = wf.hit1_cache ? (uint32_t)env_num(getenv("PT_HIT1_CACHE_HOLES"), 0.0) : 0u;
+        // The exact list as long as the queue it indexes where the plan's count of it does not cover this frame: the study
+        // switch makes every N-th cast of the queue unknown; a plan counted in a frame that loaded (bounce 0 listed nothing for
+        // bounce 1 then) does not know the rays a frame that casts lists - a cache switched off or over budget since.
+        const bool loads_all = wf.hit1_cache && wf.hit1_cache->mark >= items;
+        if (wf.hit1_holes || (wf.planned && wf.fs->plan_hit1_loads && !loads_all)) wf.cap_e = std::max({wf.cap_e, wf.cap_q[0], wf.cap_q[1]});
+    }
     // The shadow visibility: the hits' key plus the light count and every light's kind and position, bit for bit - not its
     // colour or `tame`, not the materials, not the bounces.  The first frame after a moved light or camera does nothing
     // new, a light orbit or a camera path never zeroes and never allocates; from the keying frame's memset on, every chunk
@@ -2584,6 +2626,7 @@ void stats_slots(pt_scene& s, const Frame& f, WfFrame& wf) {
     if (!fs->done) HIP_CHECK(hipEventCreateWithFlags(&fs->done, hipEventDisableTiming));
     fs->cap_items = wf.cap;
     fs->stats_planned = wf.planned;
+    fs->stats_hit1_loads = false;
     fs->first_item_of_slot.assign(n, 0u);
     s.stats_dev.ensure((size_t)n * levels * 16u);
     wf.stats_slots = n;
@@ -2679,6 +2722,10 @@ struct Chunk {
     int hit_mode = 0;
     uint4* hit_plane = nullptr;
     uint8_t* vis_plane = nullptr;   // the scene's shadow-visibility cache (chunks that load their hits only): the chunk's bytes, or null
+    // the scene's bounce-1 hit cache: 16 - k_wf_hits_store behind bounce 1 writes the chunk's records at hit1_plane, 32 -
+    // k_wf_hits_load takes the place of bounce 1's casts, 0 - neither
+    int hit1_mode = 0;
+    uint4* hit1_plane = nullptr;
     float4 *q_in = nullptr, *q_out = nullptr;
     bool split_shade = false;   // the shade pass in two launches (PT_WF_SPLIT)
 };
@@ -2761,6 +2808,49 @@ void trace_stage(pt_scene& s, const Frame& f, Chunk& c, Timeline& tl) {
     }
     tl.end();
     ++tl.launches;
+}
+
+// Bounce 1 of a chunk whose hits the scene's bounce-1 hit cache holds (Chunk::hit1_mode 32), in place of trace_stage:
+// k_wf_hits_load instead of k_wf_trace and k_wf_trace_wide, then k_wf_trace_exact for the items without a record (normally
+// none: the launch finds an empty list and returns).  All on the main stream, the shade pass behind them unsplit: nothing
+// is left that a second launch could run beside.  The bounce-0 kernel of such a chunk listed no ray for k_wf_trace_exact
+// (render_chunk), so the list holds the unknown casts alone.
+void hits_load_stage(pt_scene& s, const Frame& f, Chunk& c, Timeline& tl) {
+    const pt_scene::WfPipe& pipe = s.pipe;
+    WfParams& W = c.W;
+    const uint32_t b = c.b;
+    tl.begin(1);
+    W.defer_age = 0u;
+    W.list_cap = (uint32_t)s.trace_blocks * WF_THREADS;
+    W.split_deferred = 0u;
+    W.exact_handover = f.env.exact;
+    c.split_shade = false;
+    const uint32_t grid = std::max(1u, std::min((uint32_t)s.n_cu * 16u, (W.qcap_in + 255u) / 256u));
+    hipLaunchKernelGGL(k_wf_hits_load, dim3(grid), dim3(256), 0, c.st_main, W, (const float4*)c.q_in, (uint4*)pipe.hits.p,
+                       (uint32_t*)pipe.exact[b & 1].p, c.wctr, (const uint4*)c.hit1_plane, (unsigned long long*)s.hit1_unknown.p);
+    HIP_CHECK(hipGetLastError());
+    const dim3 eg(f.env.exact == 2u ? std::max(1u, (uint32_t)s.n_cu * f.env.exact_blocks / 8u) : (uint32_t)s.n_cu * 16u);
+    hipLaunchKernelGGL((k_wf_trace_exact<false, false, false>), eg, dim3(WF_EXACT_THREADS), 0, c.st_main, f.dev, W, f.d_tiles,
+                       (const float4*)c.q_in, (uint4*)pipe.hits.p, (const uint4*)c.rng_planes, (uint32_t*)pipe.draws.p,
+                       (uint32_t*)pipe.exact[b & 1].p, (const WfCounters*)c.wctr, f.gctr);
+    HIP_CHECK(hipGetLastError());
+    tl.end();
+    ++tl.launches;
+}
+
+// Behind bounce 1 of a chunk that extends the prefix of the scene's bounce-1 hit cache (Chunk::hit1_mode 16): the final hits
+// of the bounce's queue to the plane.  On the main stream, before the next bounce's casts rewrite the chunk's hit plane, the
+// hand-over list and this bounce's exact list.
+void hits_store_stage(pt_scene& s, const Frame& f, const Chunk& c, Timeline& tl, uint32_t holes, uint64_t g0) {
+    const pt_scene::WfPipe& pipe = s.pipe;
+    const WfParams& W = c.W;
+    tl.begin(1);
+    const uint32_t grid = std::max(1u, std::min((uint32_t)s.n_cu * 16u, (W.qcap_in + 255u) / 256u));
+    hipLaunchKernelGGL(k_wf_hits_store, dim3(grid), dim3(256), 0, c.st_main, W, (const float4*)c.q_in, (const uint4*)pipe.hits.p,
+                       (const uint32_t*)pipe.deferred.p, (const uint32_t*)pipe.exact[c.b & 1].p, (const WfCounters*)c.wctr, c.hit1_plane,
+                       holes, holes ? (uint32_t)(g0 % holes) : 0u);
+    HIP_CHECK(hipGetLastError());
+    tl.end();
 }
 
 // k_wf_shade over the bounce's queue (split shade pass: then over the casts k_wf_trace_wide took meanwhile).
@@ -2963,6 +3053,10 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
         if (c.hit_mode) c.hit_plane = (uint4*)wf.hit_cache->buf.p + g0;
         if (c.hit_mode == 32 && wf.vis_cache && g1 <= wf.vis_cache->stride) c.vis_plane = (uint8_t*)wf.vis_cache->buf.p + g0;
     }
+    // the bounce-1 hits: loaded in place of bounce 1's casts, or stored behind them; anything else casts as before
+    c.hit1_mode = reads(wf.hit1_cache) ? 32 : extends(wf.hit1_cache) ? 16 : 0;
+    if (c.hit1_mode) c.hit1_plane = (uint4*)wf.hit1_cache->buf.p + g0;
+    if (c.hit1_mode == 32 && wf.stats_slots && wf.stats_line < wf.stats_slots) wf.fs->stats_hit1_loads = true;
     if (fused_rng && !c.cached && pipe.rng[0].bytes < (size_t)wf.cap * 16u) {   // (queue_buffers left the plane out)
         s.pipe.rng[0].ensure((size_t)wf.cap * 16u);
         c.rng_planes = (uint4*)pipe.rng[0].p;
@@ -3013,7 +3107,16 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
         c.grid_mode = (c.prim && f.bounce0_fused) ? (fused_rng ? 3 : 2)
                                                   : (f.use_light_grids && (f.env.inline_all || (b < wf.inline_at.size() && wf.inline_at[b])) ? 1 : 0);
         c.split_shade = false;
-        if (c.grid_mode < 2) trace_stage(s, f, c, tl);   // (grid_mode >= 2: k_wf_shade casts the camera rays itself)
+        // (a chunk that loads its bounce-1 hits: the rays k_wf_trace would leave to k_wf_trace_exact have records like any
+        // other, so bounce 0 lists none of them - the exact list of bounce 1 is k_wf_hits_load's, for the items without one)
+        W.exact_shade_lists = (f.env.exact == 2u && !(b == 0u && c.hit1_mode == 32)) ? 1u : 0u;
+        if (b == 1u && c.hit1_mode == 32) {
+            hits_load_stage(s, f, c, tl);
+            wf.hit1_cache->touched(c.st_main);   // (no device sync before the plane is zeroed for a new key: the readers count)
+            ++wf.hit1_cache->counter[2];
+        } else if (c.grid_mode < 2) {
+            trace_stage(s, f, c, tl);   // (grid_mode >= 2: k_wf_shade casts the camera rays itself)
+        }
         shade_stage(s, f, wf, c, tl);
         if (c.prim && c.hit_mode == 16) {   // the records are behind this launch: the prefix grows by the chunk
             wf.hit_cache->touched(c.st_main);
@@ -3027,7 +3130,14 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
             }
         }
         shadow_stage(s, f, c, tl);
+        if (b == 1u && c.hit1_mode == 16) {   // the records are behind this launch: the prefix grows by the chunk
+            hits_store_stage(s, f, c, tl, wf.hit1_holes, g0);
+            wf.hit1_cache->touched(c.st_main);
+            wf.hit1_cache->mark = g1;
+            ++wf.hit1_cache->counter[1];
+        }
     }
+    if (c.hit1_mode == 16 && b_end < 1u) wf.hit1_cache->mark = g1;   // (a chunk without a bounce-1 ray: nothing to store)
     // the next chunk clears the counters and reuses the queues, accumulate reads the staging area:
     // join the side stream
     if (c.st_shadow != c.st_main) HIP_CHECK(hipStreamWaitEvent(c.st_main, pipe.ev_shadow, 0));
@@ -4039,6 +4149,22 @@ int pt_get_hit_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* ite
     if (!scene) return PT_ERR_INVALID;
     const pt_scene::FrameCache& fc = scene->hit_cache;
     return cache_stats({{bytes, fc.buf.bytes}, {items, fc.items}, {items_cached, fc.mark}, {stores, fc.counter[0]}, {loads, fc.counter[1]}});
+}
+int pt_get_hit1_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* resets,
+                            uint64_t* stores, uint64_t* loads, uint64_t* unknown_casts) {
+    if (!scene) return PT_ERR_INVALID;
+    return guarded([&] {
+        const pt_scene::FrameCache& fc = scene->hit1_cache;
+        uint64_t unknown = 0;
+        if (scene->hit1_unknown.p) {   // (synchronises, like pt_get_cull_stats)
+            HIP_CHECK(hipSetDevice(scene->device));
+            HIP_CHECK(hipDeviceSynchronize());
+            HIP_CHECK(hipMemcpy(&unknown, scene->hit1_unknown.p, 8, hipMemcpyDeviceToHost));
+        }
+        if (cache_stats({{bytes, fc.buf.bytes}, {items, fc.items}, {items_cached, fc.mark}, {resets, fc.counter[0]}, {stores, fc.counter[1]},
+                         {loads, fc.counter[2]}, {unknown_casts, unknown}}) != PT_OK)
+            fail(PT_ERR_INVALID, "pt_get_hit1_cache_stats: null argument");
+    });
 }
 int pt_get_vis_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* resets, uint64_t* launches) {
     if (!scene) return PT_ERR_INVALID;

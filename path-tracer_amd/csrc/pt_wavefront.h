@@ -2376,3 +2376,90 @@ __global__ __launch_bounds__(WF_THREADS, (!COUNT && !ALPHA) ? WF_PRIMARY_WAVES :
         atomicAdd(&gctr->restarts, (unsigned long long)lc.restarts);
     }
 }
+
+// ---------------------------------------------------------------------------
+// The bounce-1 hit cache (pt_gpu.hip FrameCache hit1_cache): the closest hit of a work item's bounce-1 ray, one record per
+// item of the frame.  In an opaque scene that ray is made from the camera hit, the material record there and words 2-3 of
+// the item's ChaCha block (pt_wf_shade_body.h: next_o, next_d) - no light enters - so the frames of one view and one
+// material table cast it once.  `plane` points at the chunk's first item; a record is pack_hit's with bit 28 of the word
+// flipped (pack_hit always leaves it clear, the miss word has it set): no record is all-zero, and the plane is zeroed when
+// it is keyed, so a zero word says "never written".  Which items reach bounce 1 may differ between frames of one key
+// (escape masks, surfaces lit through the shadow queue): an item without a record is cast, by k_wf_trace_exact.
+// ---------------------------------------------------------------------------
+#define WF_HIT1_FLIP 0x10000000u
+PT_D uint32_t wf_queue_item(const float4* queue, uint32_t i) { return __float_as_uint(wf_ray_rec(queue, i)[1].z); }
+
+// Behind the casts and the shade passes of bounce 1 in a chunk that fills the plane: the final hit of every entry of the
+// bounce's queue, resolved as the shade passes resolve it - the chunk's hit plane, or, where the word there is
+// WF_HIT_PENDING (split shade pass), the hand-over list's own plane by list position or the exact list's words with the
+// chunk's (key, u, v) at the queue index - to plane[item].  holes (PT_HIT1_CACHE_HOLES, a study switch): the records of
+// the items whose frame-global number is a multiple of it are left out.
+__global__ __launch_bounds__(256) void k_wf_hits_store(WfParams W, const float4* __restrict__ queue, const uint4* __restrict__ hits,
+                                                       const uint32_t* __restrict__ deferred, const uint32_t* __restrict__ exact_list,
+                                                       const WfCounters* __restrict__ ctr, uint4* __restrict__ plane,
+                                                       uint32_t holes, uint32_t hole_phase) {
+    const uint32_t n_queue = min(ctr[W.bounce].queue_count, W.qcap_in);
+    const uint32_t n_def = W.split_deferred ? min(ctr[W.bounce].deferred_count, W.list_cap) : 0u;
+    const uint32_t n_exact = W.split_deferred ? min(ctr[W.bounce].exact_count, W.ecap) : 0u;
+    const uint32_t n = n_queue + n_def + n_exact, stride = gridDim.x * blockDim.x;
+    const uint4* list_hits = wf_list_hits(deferred, W.list_cap);
+    for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
+        uint32_t i, word;
+        uint4 k = make_uint4(0u, 0u, 0u, 0u);
+        if (e < n_queue) {
+            i = e;
+            word = wf_hit_word(hits, i);
+            if (word == WF_HIT_PENDING) continue;   // (in one of the lists below)
+            if (word != 0xffffffffu) k = ((const uint4*)((const uint32_t*)hits + W.hcap))[i];
+        } else if (e < n_queue + n_def) {
+            const uint32_t l = e - n_queue;
+            i = deferred[l];
+            word = wf_hit_word(list_hits, l);
+            if (word != 0xffffffffu) k = ((const uint4*)((const uint32_t*)list_hits + W.list_cap))[l];
+        } else {
+            const uint32_t l = e - n_queue - n_def;
+            i = exact_list[l];
+            word = wf_exact_words(exact_list, W.ecap)[l];
+            if (i < n_queue && word != 0xffffffffu) k = ((const uint4*)((const uint32_t*)hits + W.hcap))[i];
+        }
+        if (i >= n_queue || word == WF_HIT_PENDING) continue;
+        const uint32_t item = wf_queue_item(queue, i);
+        if (item >= W.n_items) continue;
+        if (holes != 0u && (hole_phase + item % holes) % holes == 0u) continue;
+        plane[item] = make_uint4(word ^ WF_HIT1_FLIP, k.x, k.y, k.z);
+    }
+}
+
+// In place of the casts of bounce 1 in a chunk whose items all lie below the plane's mark: every queue entry gets its item's
+// record as wf_store_hit would have written it.  An item without a record goes to the bounce's exact list - marked the way
+// k_wf_trace marks a cast it leaves to k_wf_trace_exact - and is counted in *unknown_casts.
+__global__ __launch_bounds__(256) void k_wf_hits_load(WfParams W, const float4* __restrict__ queue, uint4* __restrict__ hits,
+                                                      uint32_t* __restrict__ exact_list, WfCounters* __restrict__ ctr,
+                                                      const uint4* __restrict__ plane, unsigned long long* __restrict__ unknown_casts) {
+    const uint32_t n = min(ctr[W.bounce].queue_count, W.qcap_in), stride = gridDim.x * blockDim.x;
+    for (uint32_t base = blockIdx.x * blockDim.x; base < n; base += stride) {   // (uniform in the wavefront: wf_reserve)
+        const uint32_t i = base + threadIdx.x;
+        const bool live = i < n;
+        uint4 rec = make_uint4(0u, 0u, 0u, 0u);
+        if (live) {
+            const uint32_t item = wf_queue_item(queue, i);
+            if (item < W.n_items) rec = plane[item];
+        }
+        const bool unknown = live && rec.x == 0u;
+        if (live && !unknown) {
+            const uint32_t word = rec.x ^ WF_HIT1_FLIP;
+            ((uint32_t*)hits)[i] = word;
+            if (word != 0xffffffffu) ((uint4*)((uint32_t*)hits + W.hcap))[i] = make_uint4(rec.y, rec.z, rec.w, 0u);
+        }
+        if (wf_any(unknown)) {
+            const uint32_t slot = wf_reserve(&ctr[W.bounce].exact_count, unknown);
+            if (unknown) {
+                if (slot < W.ecap) exact_list[slot] = i;
+                else ctr[0].overflow = 1u;
+                if (W.split_deferred) ((uint32_t*)hits)[i] = WF_HIT_PENDING;
+            }
+            const unsigned long long m = __ballot(unknown);
+            if (unknown && wf_lane_rank(m) == 0u) atomicAdd(unknown_casts, (unsigned long long)__popcll(m));
+        }
+    }
+}

@@ -2,7 +2,7 @@
 1920x1080, 128 spp, 5 bounces, FILMIC): the case the camera-hit cache is for (DESIGN section 4 "The camera-hit cache").  One
 JSON line with the scene's first frames one by one (the second is the one that fills the word cache and stores the camera
 hits), the median steady frame, the frame after each of `--moves` moves of the first point light along a circle about the
-vertical axis, and the cache's numbers where the library has them (an A/B library of an earlier commit, PT_GPU_LIB, has none).
+vertical axis, and the numbers of the camera-hit and bounce-1 hit caches where the library has them (an A/B library of an earlier commit, PT_GPU_LIB, has none).
     timeout -k 10 600 python tools/light_orbit_times.py [--tris 500000] [--moves 8] [--steady 8]
 Needs the GPU; every step below is bounded by the caller's time limit."""
 import argparse
@@ -50,7 +50,9 @@ g = pta.GpuScene(host, device=0)
 frame = lambda: timed(lambda: g.render_device(prof, pta.Opts.make(), rgb.data_ptr(), acc.data_ptr(), 0))
 has_stats = hasattr(g.lib, "pt_get_hit_cache_stats")
 stats = lambda: dict(zip(("bytes", "items", "cached", "stores", "loads"), g.hit_cache_stats())) if has_stats else None
-first = [frame() for _ in range(4)]   # (the first frame, the filling and storing frame, escape masks, the plan)
+has_hit1 = hasattr(g.lib, "pt_get_hit1_cache_stats")
+hit1 = lambda: dict(zip(("bytes", "items", "cached", "resets", "stores", "loads", "unknown_casts"), g.hit1_cache_stats())) if has_hit1 else None
+first = [frame() for _ in range(5)]   # (the first frame, the filling and storing frame, escape masks, the plan, a steady one)
 after_first = stats()
 steady = [frame() for _ in range(a.steady)]
 base = host.lights
@@ -67,5 +69,6 @@ print(json.dumps({"image": f"{a.width}x{a.height}", "spp": a.spp, "bounces": a.b
                   "first_frames_ms": [round(v, 2) for v in first], "hit_cache_after_first_frames": after_first,
                   "steady_frame_ms_median": round(statistics.median(steady), 2),
                   "frame_after_light_move_ms": [round(v, 2) for v in moved],
-                  "frame_after_light_move_ms_median": round(statistics.median(moved), 2), "hit_cache": stats()}))
+                  "frame_after_light_move_ms_median": round(statistics.median(moved), 2), "hit_cache": stats(),
+                  "hit1_cache": hit1()}))
 g.close()

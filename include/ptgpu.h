@@ -527,6 +527,24 @@ int pt_get_vis_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* ite
  * The call waits for the device.  The bytes are not part of pt_scene_info's queue_bytes or device_bytes. */
 int pt_get_hit1_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* resets,
                             uint64_t* stores, uint64_t* loads, uint64_t* unknown_casts);
+/* The scene's cache of bounce-2 hits: the bounce-1 hit cache one bounce later - the bounce-2 ray is made from the bounce-1
+ * hit, the material there and the item's random words, so it has the same key (view and material table, no light, no
+ * bounce count) and the same rules, values and meaning of every field.  Only frames that use the bounce-1 hit cache and
+ * have at least two bounces use it; both planes are keyed, zeroed and stored by the same frame.  PT_HIT2_CACHE=0 switches
+ * the cache off (PT_HIT1_CACHE=0 takes it out of use too), PT_HIT2_CACHE_GIB (8) is its budget; both are read per frame.
+ * The call waits for the device.  The bytes are not part of pt_scene_info's queue_bytes or device_bytes. */
+int pt_get_hit2_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* resets,
+                            uint64_t* stores, uint64_t* loads, uint64_t* unknown_casts);
+/* The scene's cache of bounce-1 shadow visibility (one byte per work item, the encoding of the bounce-0 one; the answer
+ * of a shadow cast from a bounce-1 hit depends on that hit - the view, the material table, the item's words - and on the
+ * light's kind and position, not on its colour or intensity): the fields of pt_get_vis_cache_stats - device bytes, work
+ * items of the view, materials and lights it is keyed to, how often it was zeroed, launches of the shadow kernel that reads
+ * it and fills in what is unknown.  Only frames that use the bounce-1 hit cache, of scenes with one to four lights that
+ * all have a light grid, use it, for the sample batches that lie below its budget and whose bounce-1 shadow casts are a
+ * launch of their own; a moved light, a new light count, a material edit and a camera move re-key it (the allocation
+ * stays), colour and intensity edits keep it.  PT_VIS1_CACHE=0 switches the cache off, PT_VIS1_CACHE_GIB (1) is its
+ * budget; both are read per frame.  The bytes are not part of pt_scene_info's queue_bytes or device_bytes. */
+int pt_get_vis1_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* resets, uint64_t* launches);
 /* Workgroups of the fused bounce-0 kernel of opaque scenes that the runtime places on one compute unit of `device`
  * (hipOccupancyMaxActiveBlocksPerMultiprocessor at the kernel's workgroup size): which = 0 the variant that computes
  * its ChaCha words, 1 the variant that reads them from the word cache, 2 and 3 the variants of 1 that store and that

@@ -578,9 +578,10 @@ struct pt_scene {
         hipEvent_t done = nullptr;
         bool pending = false, valid = false, planned = false;
         bool stats_planned = false;   // the counts on their way were taken by a frame that ran the plan
-        // the counts (on their way / the plan's) are of a frame whose bounce 1 loaded its hits (hit1_cache): its bounce-0 kernel
-        // listed no ray for k_wf_trace_exact, so the exact count of bounce 1 is lower than a frame that casts would have
-        bool stats_hit1_loads = false, plan_hit1_loads = false;
+        // the counts (on their way / the plan's) are of a frame that loaded the hits of these bounces (bit b; hit1_cache,
+        // hit2_cache): the shade pass before listed no ray for k_wf_trace_exact, so the exact count of that bounce is lower than
+        // a frame that casts would have
+        uint32_t stats_hit_loads = 0, plan_hit_loads = 0;
         std::vector<uint32_t> first_item_of_slot;         // (which chunk a slot was)
         // the plan made from them: work items per chunk, records per queue / hit / shadow / exact array, the bounces whose
         // shadow casts go inline; fresh until its buffers have been allocated once (buffers much larger are given back then)
@@ -602,7 +603,7 @@ struct pt_scene {
     } frame_state;
     DeviceBuffer stats_dev;
     // A frame cache: one value per work item that later frames of the same key read instead of computing it again.  The
-    // mechanics the three share (frame_cache_frame, render_chunk): the plane is indexed by frame-global item g = batch x
+    // mechanics they all share (frame_cache_frame, render_chunk): the plane is indexed by frame-global item g = batch x
     // items per batch + item and - words and hits - filled as a prefix [0, mark) in frame order, whatever the chunking; it is
     // keyed to a key in the SECOND consecutive frame of that key, so a one-shot render never pays for it and a caller
     // alternating two keys never thrashes it; it is not an edit's to drop (drop_frame_state: an edit that matters changes the
@@ -663,6 +664,19 @@ struct pt_scene {
     // k_wf_trace_exact (one uint64 on the device).
     FrameCache hit1_cache;
     DeviceBuffer hit1_unknown;
+    // The closest hits of the bounce-2 rays, same key: that ray is made from the bounce-1 hit, the material there and the
+    // item's words - again no light, and the Russian roulette starts behind it - so what holds for bounce 1 holds one bounce
+    // later.  In use in the frames hit1_cache serves that have a bounce 2; the record, the zeroing, the prefix, the counters
+    // and hit2_unknown as for hit1_cache (render_chunk drives both from one table, WfFrame::bounce_hits).
+    FrameCache hit2_cache;
+    DeviceBuffer hit2_unknown;
+    // The answers of the bounce-1 shadow casts of ONE view, ONE material table and ONE set of light positions: the casts
+    // k_og_shadow makes for the surfaces bounce 1 reached - those depend on what hit1_cache's key holds - towards lights whose
+    // kind and position are in the key, colour and intensity not.  One byte per item in vis_cache's encoding, indexed by the
+    // sample's slot in its batch's staging area (the shadow record carries that, not the item: a bijection onto the batch's
+    // valid items that the enumeration fixes), no mark; k_og_shadow_vis reads a record's byte, casts for what is unknown
+    // and writes the byte back.  counter[0], [1]: times the plane was zeroed / launches of the variant.
+    FrameCache vis1_cache;
     std::vector<DevLight> host_lights;   // the lights as the device has them (the visibility cache's key)
     uint64_t camera_generation = 0;   // bumped by pt_scene_set_camera
     uint64_t material_generation = 0;   // bumped by pt_scene_set_materials
@@ -1853,6 +1867,7 @@ void scene_set_camera(pt_scene& s, const pt_camera& cam) {
     ++s.camera_generation;
     s.hit_cache.mark = 0;
     s.hit1_cache.mark = 0;
+    s.hit2_cache.mark = 0;
 }
 
 // pt_scene_set_lights.  The light grids are those grids_on_device builds for the new lights (all or none), their parameters
@@ -2252,8 +2267,16 @@ struct WfFrame {
     // the scene's frame caches this frame uses (frame_caches; nullptr: not in use): the words, keyed to this frame's
     // enumeration, the camera hits, keyed to its view, the shadow visibility, keyed to its view and lights
     pt_scene::FrameCache *rng_cache = nullptr, *hit_cache = nullptr, *vis_cache = nullptr;
-    pt_scene::FrameCache* hit1_cache = nullptr;   // the bounce-1 hits, keyed to the frame's view and material table
-    uint32_t hit1_holes = 0;                      // PT_HIT1_CACHE_HOLES (a study switch, read per frame)
+    // the hits of the bounces that have a cache of them (hit1_cache, hit2_cache), keyed to the frame's view and material
+    // table: by bounce (entry 0 stays empty - the camera hits are the bounce-0 kernel's).  A third bounce is a third entry.
+    struct BounceHits {
+        pt_scene::FrameCache* cache = nullptr;
+        uint32_t holes = 0;                      // PT_HIT1_CACHE_HOLES / PT_HIT2_CACHE_HOLES (study switches, read per frame)
+        unsigned long long* unknown = nullptr;   // the casts the loading launches left to k_wf_trace_exact (on the device)
+    };
+    static constexpr uint32_t HIT_BOUNCES = 3;
+    BounceHits bounce_hits[HIT_BOUNCES];
+    pt_scene::FrameCache* vis1_cache = nullptr;   // the bounce-1 shadow visibility, keyed to view, material table and lights
     uint32_t stats_line = 0, chunk_slot = 0;   // the frame's progress through its chunks
 };
 
@@ -2402,7 +2425,7 @@ WfFrame frame_plan(pt_scene& s, const Frame& f, const QueueEnv& qe) {
             if (!fs->planned) {
                 fs->valid = true;
                 fs->planned = make_plan(*fs, f, wf, qe);
-                fs->plan_hit1_loads = fs->stats_hit1_loads;
+                fs->plan_hit_loads = fs->stats_hit_loads;
             }
         }
     }
@@ -2489,7 +2512,7 @@ void queue_buffers(pt_scene& s, const Frame& f, const QueueEnv& qe, WfFrame& wf)
     s.frame_planned_last = wf.planned ? 1u : 0u;
 }
 
-// What differs between the scene's four frame caches, apart from their keys and the frames they serve (frame_caches).
+// What differs between the scene's six frame caches, apart from their keys and the frames they serve (frame_caches).
 struct FrameCacheKind {
     const char *env_switch, *env_gib;   // "0": off; the budget in GiB - both read per frame, the tests switch them
     double default_gib;
@@ -2506,6 +2529,8 @@ constexpr FrameCacheKind VIS_CACHE = {"PT_VIS_CACHE", "PT_VIS_CACHE_GIB", 1.0, 1
 // (zeroed AND a prefix: the memset of a new key also starts an empty prefix - frame_cache_frame resets the mark either way -
 // and, there being no device sync, every launch that reads the plane records the event too, not only those that write)
 constexpr FrameCacheKind HIT1_CACHE = {"PT_HIT1_CACHE", "PT_HIT1_CACHE_GIB", 8.0, 16u, ~0ull, true};
+constexpr FrameCacheKind HIT2_CACHE = {"PT_HIT2_CACHE", "PT_HIT2_CACHE_GIB", 8.0, 16u, ~0ull, true};
+constexpr FrameCacheKind VIS1_CACHE = {"PT_VIS1_CACHE", "PT_VIS1_CACHE_GIB", 1.0, 1u, ~0ull, true};
 
 // One frame cache and this frame, of `items` work items and key `key`: the cache if the frame uses it, keyed to `key`.
 // Keying happens when a frame of a key directly follows another of the same - also one that was switched off or not
@@ -2573,20 +2598,39 @@ void frame_caches(pt_scene& s, const Frame& f, WfFrame& wf, hipStream_t stream) 
     // NOT the lights or the bounces.  The first frame after a material edit or a camera move neither loads nor stores, the
     // second zeroes the plane and stores, the third loads; a light orbit loads throughout.  Eligible: the frames the hit
     // cache serves that have a bounce 1; any other frame leaves the records alone.
+    // The bounce-2 hits: the same key, the same rules, one bounce later - in use where the bounce-1 hits are and the frame
+    // has a bounce 2.  Both planes are keyed, zeroed and stored by the same frame.
+    std::vector<uint64_t> key1 = key;
+    key1.push_back(s.material_generation);
     {
-        std::vector<uint64_t> key1 = key;
-        key1.push_back(s.material_generation);
-        wf.hit1_cache = frame_cache_frame(s.hit1_cache, HIT1_CACHE, key1, items, wf.hit_cache && f.p.bounces >= 1u, stream);
-        if (wf.hit1_cache && !s.hit1_unknown.p) {
-            s.hit1_unknown.ensure(8);
-            HIP_CHECK(hipMemset(s.hit1_unknown.p, 0, 8));
+        struct Entry {
+            uint32_t bounce;
+            pt_scene::FrameCache& fc;
+            const FrameCacheKind& kind;
+            DeviceBuffer& unknown;
+            const char* env_holes;
+        } table[] = {{1u, s.hit1_cache, HIT1_CACHE, s.hit1_unknown, "PT_HIT1_CACHE_HOLES"},
+                     {2u, s.hit2_cache, HIT2_CACHE, s.hit2_unknown, "PT_HIT2_CACHE_HOLES"}};
+        bool before = wf.hit_cache != nullptr, holes = false;
+        uint32_t loads_all = 0;   // bit b: every item of the frame loads bounce b
+        for (Entry& e : table) {
+            WfFrame::BounceHits& bh = wf.bounce_hits[e.bounce];
+            bh.cache = frame_cache_frame(e.fc, e.kind, key1, items, before && f.p.bounces >= e.bounce, stream);
+            if (bh.cache && !e.unknown.p) {
+                e.unknown.ensure(8);
+                HIP_CHECK(hipMemset(e.unknown.p, 0, 8));
+            }
+            bh.unknown = (unsigned long long*)e.unknown.p;
+            bh.holes = bh.cache ? (uint32_t)env_num(getenv(e.env_holes), 0.0) : 0u;
+            holes = holes || bh.holes != 0u;
+            if (bh.cache && bh.cache->mark >= items) loads_all |= 1u << e.bounce;
+            before = bh.cache != nullptr;
         }
-        wf.hit1_holes = wf.hit1_cache ? (uint32_t)env_num(getenv("PT_HIT1_CACHE_HOLES"), 0.0) : 0u;
         // The exact list as long as the queue it indexes where the plan's count of it does not cover this frame: the study
-        // switch makes every N-th cast of the queue unknown; a plan counted in a frame that loaded (bounce 0 listed nothing for
-        // bounce 1 then) does not know the rays a frame that casts lists - a cache switched off or over budget since.
-        const bool loads_all = wf.hit1_cache && wf.hit1_cache->mark >= items;
-        if (wf.hit1_holes || (wf.planned && wf.fs->plan_hit1_loads && !loads_all)) wf.cap_e = std::max({wf.cap_e, wf.cap_q[0], wf.cap_q[1]});
+        // switches make every N-th cast of the queue unknown; a plan counted in a frame that loaded a bounce (the shade pass
+        // before it listed nothing for that bounce then) does not know the rays a frame that casts it lists - a cache switched
+        // off or over budget since.
+        if (holes || (wf.planned && (wf.fs->plan_hit_loads & ~loads_all) != 0u)) wf.cap_e = std::max({wf.cap_e, wf.cap_q[0], wf.cap_q[1]});
     }
     // The shadow visibility: the hits' key plus the light count and every light's kind and position, bit for bit - not its
     // colour or `tame`, not the materials, not the bounces.  The first frame after a moved light or camera does nothing
@@ -2594,6 +2638,7 @@ void frame_caches(pt_scene& s, const Frame& f, WfFrame& wf, hipStream_t stream) 
     // that LOADs its hits and lies below the plane's stride runs the variant that reads the plane and fills in what is
     // unknown.  Eligible: the frames the hit cache serves, with one to four lights; any other frame leaves the bits alone -
     // those of a scene that turned translucent are still the opaque geometry's.
+    const size_t light_words = key.size();
     key.push_back(s.host_lights.size());
     for (const DevLight& L : s.host_lights) {
         uint32_t w[4];
@@ -2602,7 +2647,15 @@ void frame_caches(pt_scene& s, const Frame& f, WfFrame& wf, hipStream_t stream) 
         key.push_back((uint64_t)w[0] << 32 | w[1]);
         key.push_back((uint64_t)w[2] << 32 | w[3]);
     }
-    wf.vis_cache = frame_cache_frame(s.vis_cache, VIS_CACHE, key, items, wf.hit_cache && !s.host_lights.empty() && s.host_lights.size() <= 4u, stream);
+    const bool few_lights = !s.host_lights.empty() && s.host_lights.size() <= 4u;
+    wf.vis_cache = frame_cache_frame(s.vis_cache, VIS_CACHE, key, items, wf.hit_cache && few_lights, stream);
+    // The bounce-1 shadow visibility: the bounce-1 hits' key plus the same light words.  The first frame after a moved
+    // light, a material edit or a camera move does nothing new; from the keying frame's memset on, every chunk whose sample
+    // batch lies below the plane's stride and whose bounce-1 shadow records go through k_og_shadow runs the variant that
+    // reads the plane and fills in what is unknown (render_chunk).  Eligible: the frames the bounce-1 hit cache serves, with
+    // one to four lights, every light with a grid.
+    key1.insert(key1.end(), key.begin() + light_words, key.end());
+    wf.vis1_cache = frame_cache_frame(s.vis1_cache, VIS1_CACHE, key1, items, wf.bounce_hits[1].cache && few_lights && f.use_light_grids, stream);
 }
 
 // This frame's counts, one line per (batch, chunk): taken every frame (a few KB) - the first frame's feed the plan, the
@@ -2626,7 +2679,7 @@ void stats_slots(pt_scene& s, const Frame& f, WfFrame& wf) {
     if (!fs->done) HIP_CHECK(hipEventCreateWithFlags(&fs->done, hipEventDisableTiming));
     fs->cap_items = wf.cap;
     fs->stats_planned = wf.planned;
-    fs->stats_hit1_loads = false;
+    fs->stats_hit_loads = 0;
     fs->first_item_of_slot.assign(n, 0u);
     s.stats_dev.ensure((size_t)n * levels * 16u);
     wf.stats_slots = n;
@@ -2722,10 +2775,15 @@ struct Chunk {
     int hit_mode = 0;
     uint4* hit_plane = nullptr;
     uint8_t* vis_plane = nullptr;   // the scene's shadow-visibility cache (chunks that load their hits only): the chunk's bytes, or null
-    // the scene's bounce-1 hit cache: 16 - k_wf_hits_store behind bounce 1 writes the chunk's records at hit1_plane, 32 -
-    // k_wf_hits_load takes the place of bounce 1's casts, 0 - neither
-    int hit1_mode = 0;
-    uint4* hit1_plane = nullptr;
+    // the scene's caches of later bounces' hits, by bounce (WfFrame::bounce_hits): 16 - k_wf_hits_store behind the bounce
+    // writes the chunk's records at `plane`, 32 - k_wf_hits_load takes the place of the bounce's casts, 0 - neither
+    struct BounceHits {
+        int mode = 0;
+        uint4* plane = nullptr;
+    } bounce_hits[WfFrame::HIT_BOUNCES];
+    int hits_mode(uint32_t bounce) const { return bounce < WfFrame::HIT_BOUNCES ? bounce_hits[bounce].mode : 0; }
+    // the scene's bounce-1 shadow-visibility cache: the bytes of the chunk's sample batch, or null (k_og_shadow_vis)
+    uint8_t* vis1_plane = nullptr;
     float4 *q_in = nullptr, *q_out = nullptr;
     bool split_shade = false;   // the shade pass in two launches (PT_WF_SPLIT)
 };
@@ -2810,12 +2868,12 @@ void trace_stage(pt_scene& s, const Frame& f, Chunk& c, Timeline& tl) {
     ++tl.launches;
 }
 
-// Bounce 1 of a chunk whose hits the scene's bounce-1 hit cache holds (Chunk::hit1_mode 32), in place of trace_stage:
-// k_wf_hits_load instead of k_wf_trace and k_wf_trace_wide, then k_wf_trace_exact for the items without a record (normally
-// none: the launch finds an empty list and returns).  All on the main stream, the shade pass behind them unsplit: nothing
-// is left that a second launch could run beside.  The bounce-0 kernel of such a chunk listed no ray for k_wf_trace_exact
-// (render_chunk), so the list holds the unknown casts alone.
-void hits_load_stage(pt_scene& s, const Frame& f, Chunk& c, Timeline& tl) {
+// A bounce of a chunk whose hits one of the scene's hit caches holds (Chunk::bounce_hits, mode 32; `unknown`: that cache's
+// counter), in place of trace_stage: k_wf_hits_load instead of k_wf_trace and k_wf_trace_wide, then k_wf_trace_exact for the
+// items without a record (normally none: the launch finds an empty list and returns).  All on the main stream, the shade pass
+// behind them unsplit: nothing is left that a second launch could run beside.  The shade pass before such a bounce listed no
+// ray for k_wf_trace_exact (render_chunk), so the list holds the unknown casts alone.
+void hits_load_stage(pt_scene& s, const Frame& f, Chunk& c, Timeline& tl, unsigned long long* unknown) {
     const pt_scene::WfPipe& pipe = s.pipe;
     WfParams& W = c.W;
     const uint32_t b = c.b;
@@ -2827,7 +2885,7 @@ void hits_load_stage(pt_scene& s, const Frame& f, Chunk& c, Timeline& tl) {
     c.split_shade = false;
     const uint32_t grid = std::max(1u, std::min((uint32_t)s.n_cu * 16u, (W.qcap_in + 255u) / 256u));
     hipLaunchKernelGGL(k_wf_hits_load, dim3(grid), dim3(256), 0, c.st_main, W, (const float4*)c.q_in, (uint4*)pipe.hits.p,
-                       (uint32_t*)pipe.exact[b & 1].p, c.wctr, (const uint4*)c.hit1_plane, (unsigned long long*)s.hit1_unknown.p);
+                       (uint32_t*)pipe.exact[b & 1].p, c.wctr, (const uint4*)c.bounce_hits[b].plane, unknown);
     HIP_CHECK(hipGetLastError());
     const dim3 eg(f.env.exact == 2u ? std::max(1u, (uint32_t)s.n_cu * f.env.exact_blocks / 8u) : (uint32_t)s.n_cu * 16u);
     hipLaunchKernelGGL((k_wf_trace_exact<false, false, false>), eg, dim3(WF_EXACT_THREADS), 0, c.st_main, f.dev, W, f.d_tiles,
@@ -2838,19 +2896,20 @@ void hits_load_stage(pt_scene& s, const Frame& f, Chunk& c, Timeline& tl) {
     ++tl.launches;
 }
 
-// Behind bounce 1 of a chunk that extends the prefix of the scene's bounce-1 hit cache (Chunk::hit1_mode 16): the final hits
-// of the bounce's queue to the plane.  On the main stream, before the next bounce's casts rewrite the chunk's hit plane, the
-// hand-over list and this bounce's exact list.
-void hits_store_stage(pt_scene& s, const Frame& f, const Chunk& c, Timeline& tl, uint32_t holes, uint64_t g0) {
+// Behind a bounce of a chunk that extends the prefix of one of the scene's hit caches (Chunk::bounce_hits, mode 16): the final
+// hits of the bounce's queue to the plane.  On the main stream, before the next bounce's casts rewrite the chunk's hit plane,
+// the hand-over list and this bounce's exact list.  Only a chunk's first store is a stage of the timeline (PT_FLAG_TIMING): a
+// storing frame comes once per key, and its stage count stays one above a plain frame's whatever the number of planes.
+void hits_store_stage(pt_scene& s, const Frame& f, const Chunk& c, Timeline& tl, uint32_t holes, uint64_t g0, bool first) {
     const pt_scene::WfPipe& pipe = s.pipe;
     const WfParams& W = c.W;
-    tl.begin(1);
+    if (first) tl.begin(1);
     const uint32_t grid = std::max(1u, std::min((uint32_t)s.n_cu * 16u, (W.qcap_in + 255u) / 256u));
     hipLaunchKernelGGL(k_wf_hits_store, dim3(grid), dim3(256), 0, c.st_main, W, (const float4*)c.q_in, (const uint4*)pipe.hits.p,
-                       (const uint32_t*)pipe.deferred.p, (const uint32_t*)pipe.exact[c.b & 1].p, (const WfCounters*)c.wctr, c.hit1_plane,
-                       holes, holes ? (uint32_t)(g0 % holes) : 0u);
+                       (const uint32_t*)pipe.deferred.p, (const uint32_t*)pipe.exact[c.b & 1].p, (const WfCounters*)c.wctr,
+                       c.bounce_hits[c.b].plane, holes, holes ? (uint32_t)(g0 % holes) : 0u);
     HIP_CHECK(hipGetLastError());
-    tl.end();
+    if (first) tl.end();
 }
 
 // k_wf_shade over the bounce's queue (split shade pass: then over the casts k_wf_trace_wide took meanwhile).
@@ -2966,10 +3025,18 @@ void shadow_stage(pt_scene& s, const Frame& f, const Chunk& c, Timeline& tl) {
         offgrid(std::false_type{}, (uint32_t)s.n_cu);
     } else if (f.use_light_grids) {   // every light a point light with a grid: plain grid-stride kernel
         const dim3 g((uint32_t)s.n_cu * std::max(1u, f.env.ogs_blocks));
-        dispatch([&](auto alpha, auto count, auto dirl) {
-            hipLaunchKernelGGL((k_og_shadow<alpha, count, dirl>), g, dim3(256), 0, st_shadow, f.dev, Ws, (const float4*)pipe.shadow.p,
-                               (const float4*)pipe.contrib.p, c.q_out, (float*)s.staging_buf.p, (uint32_t*)pipe.offgrid.p, c.wctr, f.gctr);
-        }, f.alpha, f.counting, s.grids.ortho);
+        if (c.vis1_plane && c.b == 1u) {   // the scene's bounce-1 shadow-visibility cache (opaque, uninstrumented frames)
+            dispatch([&](auto dirl) {
+                hipLaunchKernelGGL((k_og_shadow_vis<dirl>), g, dim3(256), 0, st_shadow, f.dev, Ws, (const float4*)pipe.shadow.p,
+                                   (const float4*)pipe.contrib.p, c.q_out, (float*)s.staging_buf.p, (uint32_t*)pipe.offgrid.p, c.wctr,
+                                   c.vis1_plane);
+            }, s.grids.ortho);
+        } else {
+            dispatch([&](auto alpha, auto count, auto dirl) {
+                hipLaunchKernelGGL((k_og_shadow<alpha, count, dirl>), g, dim3(256), 0, st_shadow, f.dev, Ws, (const float4*)pipe.shadow.p,
+                                   (const float4*)pipe.contrib.p, c.q_out, (float*)s.staging_buf.p, (uint32_t*)pipe.offgrid.p, c.wctr, f.gctr);
+            }, f.alpha, f.counting, s.grids.ortho);
+        }
         HIP_CHECK(hipGetLastError());
         offgrid(std::true_type{}, (uint32_t)s.n_cu);
     } else {
@@ -3053,10 +3120,21 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
         if (c.hit_mode) c.hit_plane = (uint4*)wf.hit_cache->buf.p + g0;
         if (c.hit_mode == 32 && wf.vis_cache && g1 <= wf.vis_cache->stride) c.vis_plane = (uint8_t*)wf.vis_cache->buf.p + g0;
     }
-    // the bounce-1 hits: loaded in place of bounce 1's casts, or stored behind them; anything else casts as before
-    c.hit1_mode = reads(wf.hit1_cache) ? 32 : extends(wf.hit1_cache) ? 16 : 0;
-    if (c.hit1_mode) c.hit1_plane = (uint4*)wf.hit1_cache->buf.p + g0;
-    if (c.hit1_mode == 32 && wf.stats_slots && wf.stats_line < wf.stats_slots) wf.fs->stats_hit1_loads = true;
+    // the later bounces' hits: loaded in place of the bounce's casts, or stored behind them; anything else casts as before
+    for (uint32_t b = 1; b < WfFrame::HIT_BOUNCES; ++b) {
+        const pt_scene::FrameCache* fc = wf.bounce_hits[b].cache;
+        Chunk::BounceHits& bh = c.bounce_hits[b];
+        bh.mode = reads(fc) ? 32 : extends(fc) ? 16 : 0;
+        if (bh.mode) bh.plane = (uint4*)fc->buf.p + g0;
+        if (bh.mode == 32 && wf.stats_slots && wf.stats_line < wf.stats_slots) wf.fs->stats_hit_loads |= 1u << b;
+    }
+    // the bounce-1 shadow visibility: indexed by the sample's slot in its batch's staging area, which any chunk of the batch
+    // may hold - so the whole batch lies below the plane's stride, not the chunk alone
+    if (wf.vis1_cache) {
+        const uint64_t batch0 = (uint64_t)(P.sample_begin / f.batch) * wf.items_per_batch;
+        const uint64_t batch1 = batch0 + (uint64_t)f.blocks64 * 64u * (P.sample_end - P.sample_begin);
+        if (batch1 <= wf.vis1_cache->stride) c.vis1_plane = (uint8_t*)wf.vis1_cache->buf.p + batch0;
+    }
     if (fused_rng && !c.cached && pipe.rng[0].bytes < (size_t)wf.cap * 16u) {   // (queue_buffers left the plane out)
         s.pipe.rng[0].ensure((size_t)wf.cap * 16u);
         c.rng_planes = (uint4*)pipe.rng[0].p;
@@ -3091,6 +3169,7 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
     // are not made; PT_PLAN_SKIP=0: all of them)
     const uint32_t b_end = (wf.plan_last && wf.chunk_slot < wf.plan_last->size()) ? std::min(f.p.bounces, (*wf.plan_last)[wf.chunk_slot]) : f.p.bounces;
     ++wf.chunk_slot;
+    bool stored = false;   // a store of this chunk has been launched
     for (uint32_t b = 0; b <= b_end; ++b) {
         W.bounce = b;
         W.qcap_in = wf.cap_q[b & 1u];          // (queue b lives in pipe.queue[b & 1])
@@ -3107,13 +3186,15 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
         c.grid_mode = (c.prim && f.bounce0_fused) ? (fused_rng ? 3 : 2)
                                                   : (f.use_light_grids && (f.env.inline_all || (b < wf.inline_at.size() && wf.inline_at[b])) ? 1 : 0);
         c.split_shade = false;
-        // (a chunk that loads its bounce-1 hits: the rays k_wf_trace would leave to k_wf_trace_exact have records like any
-        // other, so bounce 0 lists none of them - the exact list of bounce 1 is k_wf_hits_load's, for the items without one)
-        W.exact_shade_lists = (f.env.exact == 2u && !(b == 0u && c.hit1_mode == 32)) ? 1u : 0u;
-        if (b == 1u && c.hit1_mode == 32) {
-            hits_load_stage(s, f, c, tl);
-            wf.hit1_cache->touched(c.st_main);   // (no device sync before the plane is zeroed for a new key: the readers count)
-            ++wf.hit1_cache->counter[2];
+        // (a chunk that loads the next bounce's hits: the rays k_wf_trace would leave to k_wf_trace_exact have records like any
+        // other, so this bounce's shade pass lists none of them - the exact list of the next bounce is k_wf_hits_load's, for
+        // the items without one)
+        W.exact_shade_lists = (f.env.exact == 2u && c.hits_mode(b + 1u) != 32) ? 1u : 0u;
+        const int hits_mode = c.hits_mode(b);
+        if (hits_mode == 32) {
+            hits_load_stage(s, f, c, tl, wf.bounce_hits[b].unknown);
+            wf.bounce_hits[b].cache->touched(c.st_main);   // (no device sync before the plane is zeroed for a new key: the readers count)
+            ++wf.bounce_hits[b].cache->counter[2];
         } else if (c.grid_mode < 2) {
             trace_stage(s, f, c, tl);   // (grid_mode >= 2: k_wf_shade casts the camera rays itself)
         }
@@ -3130,14 +3211,20 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
             }
         }
         shadow_stage(s, f, c, tl);
-        if (b == 1u && c.hit1_mode == 16) {   // the records are behind this launch: the prefix grows by the chunk
-            hits_store_stage(s, f, c, tl, wf.hit1_holes, g0);
-            wf.hit1_cache->touched(c.st_main);
-            wf.hit1_cache->mark = g1;
-            ++wf.hit1_cache->counter[1];
+        if (c.vis1_plane && b == 1u && c.grid_mode == 0) {   // (k_og_shadow_vis, on the side stream; any such launch may write the plane)
+            wf.vis1_cache->touched(c.st_shadow);
+            ++wf.vis1_cache->counter[1];
+        }
+        if (hits_mode == 16) {   // the records are behind this launch: the prefix grows by the chunk
+            hits_store_stage(s, f, c, tl, wf.bounce_hits[b].holes, g0, !stored);
+            stored = true;
+            wf.bounce_hits[b].cache->touched(c.st_main);
+            wf.bounce_hits[b].cache->mark = g1;
+            ++wf.bounce_hits[b].cache->counter[1];
         }
     }
-    if (c.hit1_mode == 16 && b_end < 1u) wf.hit1_cache->mark = g1;   // (a chunk without a bounce-1 ray: nothing to store)
+    for (uint32_t b = b_end + 1u; b < WfFrame::HIT_BOUNCES; ++b)   // (a chunk without a ray at that bounce: nothing to store)
+        if (c.bounce_hits[b].mode == 16) wf.bounce_hits[b].cache->mark = g1;
     // the next chunk clears the counters and reuses the queues, accumulate reads the staging area:
     // join the side stream
     if (c.st_shadow != c.st_main) HIP_CHECK(hipStreamWaitEvent(c.st_main, pipe.ev_shadow, 0));
@@ -4020,6 +4107,22 @@ int cache_stats(std::initializer_list<std::pair<uint64_t*, uint64_t>> out) {
     for (const auto& o : out) *o.first = o.second;
     return PT_OK;
 }
+// pt_get_hit1_cache_stats / pt_get_hit2_cache_stats: the cache's numbers and its counter of unknown casts from the device
+int bounce_hits_stats(const pt_scene* scene, const pt_scene::FrameCache& fc, const DeviceBuffer& unknown_casts_dev, const char* who,
+                      uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* resets, uint64_t* stores, uint64_t* loads,
+                      uint64_t* unknown_casts) {
+    return guarded([&] {
+        uint64_t unknown = 0;
+        if (unknown_casts_dev.p) {   // (synchronises, like pt_get_cull_stats)
+            HIP_CHECK(hipSetDevice(scene->device));
+            HIP_CHECK(hipDeviceSynchronize());
+            HIP_CHECK(hipMemcpy(&unknown, unknown_casts_dev.p, 8, hipMemcpyDeviceToHost));
+        }
+        if (cache_stats({{bytes, fc.buf.bytes}, {items, fc.items}, {items_cached, fc.mark}, {resets, fc.counter[0]}, {stores, fc.counter[1]},
+                         {loads, fc.counter[2]}, {unknown_casts, unknown}}) != PT_OK)
+            fail(PT_ERR_INVALID, "%s: null argument", who);
+    });
+}
 }  // namespace
 
 struct pt_comm {
@@ -4153,22 +4256,23 @@ int pt_get_hit_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* ite
 int pt_get_hit1_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* resets,
                             uint64_t* stores, uint64_t* loads, uint64_t* unknown_casts) {
     if (!scene) return PT_ERR_INVALID;
-    return guarded([&] {
-        const pt_scene::FrameCache& fc = scene->hit1_cache;
-        uint64_t unknown = 0;
-        if (scene->hit1_unknown.p) {   // (synchronises, like pt_get_cull_stats)
-            HIP_CHECK(hipSetDevice(scene->device));
-            HIP_CHECK(hipDeviceSynchronize());
-            HIP_CHECK(hipMemcpy(&unknown, scene->hit1_unknown.p, 8, hipMemcpyDeviceToHost));
-        }
-        if (cache_stats({{bytes, fc.buf.bytes}, {items, fc.items}, {items_cached, fc.mark}, {resets, fc.counter[0]}, {stores, fc.counter[1]},
-                         {loads, fc.counter[2]}, {unknown_casts, unknown}}) != PT_OK)
-            fail(PT_ERR_INVALID, "pt_get_hit1_cache_stats: null argument");
-    });
+    return bounce_hits_stats(scene, scene->hit1_cache, scene->hit1_unknown, "pt_get_hit1_cache_stats", bytes, items, items_cached, resets,
+                             stores, loads, unknown_casts);
+}
+int pt_get_hit2_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* resets,
+                            uint64_t* stores, uint64_t* loads, uint64_t* unknown_casts) {
+    if (!scene) return PT_ERR_INVALID;
+    return bounce_hits_stats(scene, scene->hit2_cache, scene->hit2_unknown, "pt_get_hit2_cache_stats", bytes, items, items_cached, resets,
+                             stores, loads, unknown_casts);
 }
 int pt_get_vis_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* resets, uint64_t* launches) {
     if (!scene) return PT_ERR_INVALID;
     const pt_scene::FrameCache& fc = scene->vis_cache;
+    return cache_stats({{bytes, fc.buf.bytes}, {items, fc.items}, {resets, fc.counter[0]}, {launches, fc.counter[1]}});
+}
+int pt_get_vis1_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* resets, uint64_t* launches) {
+    if (!scene) return PT_ERR_INVALID;
+    const pt_scene::FrameCache& fc = scene->vis1_cache;
     return cache_stats({{bytes, fc.buf.bytes}, {items, fc.items}, {resets, fc.counter[0]}, {launches, fc.counter[1]}});
 }
 int pt_kernel_occupancy(int device, int which, int* blocks_per_cu) {

@@ -142,6 +142,72 @@ __global__ __launch_bounds__(256, (!ALPHA && !COUNT && !DIRL) ? 8 : 1) void k_og
 }
 
 // ---------------------------------------------------------------------------
+// k_og_shadow of an opaque, uninstrumented frame with the scene's bounce-1 shadow-visibility cache (pt_gpu.hip FrameCache
+// vis1_cache): the answer of og_blocked for a record and a light is kept in the record's byte of `vis_plane` - two bits
+// per light, 0 unknown / 1 not blocked / 2 blocked, scenes of at most four lights - so the frames of one view, material
+// table and set of light positions cast once.  The byte is found by the record's out_slot, the sample's place in its batch's
+// staging area: the shadow record does not carry the item, and out_slot = (sample in the batch) x pixels + pixel is a
+// bijection onto the batch's valid items that the enumeration alone fixes - `vis_plane` points at the batch's first byte.
+// The byte is loaded with the record, dependent on nothing but s3.  Per light: moot is skipped as in k_og_shadow and its
+// bits stay unknown; known bits cost og_light_unshadowed and rad * 0.0f where blocked; unknown bits cast
+// (og_light_blocked) and the answer goes into the byte - the arithmetic and the order of the additions are
+// og_light_radiance's, as in the VIS branch of the shade body.  One byte store if the byte changed.  Long normals go to
+// `offgrid` as before, their bytes untouched.
+// Registers: written plainly the kernel takes 70, a wave per SIMD fewer than k_og_shadow's 64.  What a cast does not need
+// is therefore not held across it: the colour so far and the byte wait in LDS (four dwords per thread), the light's term
+// and the record's slot and next index are fetched again behind it (og_again) - 64 registers, no scratch; the parking
+// and the term's second fetch sit in the branch of the cast, which a wavefront that finds its bits known skips.  No minimum of blocks in the launch bounds: asking for 8 takes
+// scalar registers away, and their spills then cost vector registers and scratch.
+// ---------------------------------------------------------------------------
+// v, as a value the compiler knows nothing about: a load through it is a new load, not the register of an earlier one
+PT_D uint32_t og_again(uint32_t v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+template <bool DIRL>
+__global__ __launch_bounds__(256) void k_og_shadow_vis(DevScene S, WfParams W, const float4* __restrict__ shadow_q,
+                                                       const float4* __restrict__ contrib, float4* __restrict__ queue_next,
+                                                       float* __restrict__ staging, uint32_t* __restrict__ offgrid,
+                                                       WfCounters* __restrict__ ctr, uint8_t* __restrict__ vis_plane) {
+    const uint32_t n = min(ctr[W.bounce].shadow_count, W.scap);
+    LocalCtr lc = {0, 0, 0, 0, 0, 0};
+    // (slot-major, every slot private to its thread, volatile: as sh_park of the shade kernels, pt_wf_shade_body.h)
+    __shared__ uint32_t sh_park[4][256];
+    volatile __attribute__((address_space(3))) uint32_t* const park = (volatile __attribute__((address_space(3))) uint32_t*)&sh_park[0][threadIdx.x];
+    for (uint32_t idx = blockIdx.x * 256u + threadIdx.x; idx < n; idx += gridDim.x * 256u) {
+        const float4* sq = shadow_q + (size_t)idx * 4;
+        uint32_t vis = vis_plane[__float_as_uint(sq[3].x)];
+        const float4 s0 = sq[0], s1 = sq[1], s2 = sq[2];
+        const f3 pos = mk3(s0.x, s0.y, s0.z), gn = mk3(s0.w, s1.x, s1.y);
+        f3 color = mk3(s2.x, s2.y, s2.z);
+        if (!(dot3(gn, gn) <= S.light_grid_max_normal2)) {   // (rare: one atomic per surface is fine)
+            offgrid[atomicAdd(&ctr[W.bounce].offgrid_count, 1u)] = idx;
+            continue;
+        }
+        for (uint32_t li = 0; li < S.n_lights; ++li) {
+            float4 c = contrib[(size_t)li * W.scap + idx];
+            if (S.n_lights > 1 && wf_light_is_moot(S.lights[li], mk3(c.x, c.y, c.z), pos)) continue;   // (a single light was already filtered by k_wf_shade)
+            const uint32_t known = (vis >> (2u * li)) & 3u;
+            bool blocked = known == 2u;
+            if (known == 0u) {
+                park[0] = __float_as_uint(color.x), park[256] = __float_as_uint(color.y), park[512] = __float_as_uint(color.z), park[768] = vis;
+                blocked = og_light_blocked<DIRL>(S, li, pos, gn, lc);
+                color = mk3(__uint_as_float(park[0]), __uint_as_float(park[256]), __uint_as_float(park[512]));
+                vis = park[768] | ((blocked ? 2u : 1u) << (2u * li)) | 0x100u;
+                c = contrib[(size_t)li * W.scap + og_again(idx)];
+            }
+            f3 rad = og_light_unshadowed<DIRL>(S, li, pos);
+            if (blocked) rad = rad * 0.0f;
+            if (!(rad.x == 0.f && rad.y == 0.f && rad.z == 0.f)) color = color + mul_ew(mk3(c.x, c.y, c.z), rad);
+        }
+        const float4* sq_again = shadow_q + (size_t)og_again(idx) * 4;
+        const uint32_t out_slot = __float_as_uint(sq_again[3].x);
+        if (vis & 0x100u) vis_plane[out_slot] = (uint8_t)vis;
+        og_retire(S, color, __float_as_uint(sq_again[2].w), out_slot, queue_next, W.qcap_out, staging);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Surfaces whose normal is too long for the light grids' margin: get_light_info on the KD-tree (light_radiance,
 // pt_integrator.h) for all their lights, then the path is retired like k_wf_shadow does.  LIST: the records
 // k_og_shadow set aside (offgrid[0 .. offgrid_count)); otherwise the whole shadow queue - what k_wf_shade<GRID>

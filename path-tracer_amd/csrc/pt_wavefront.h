@@ -2385,6 +2385,8 @@ __global__ __launch_bounds__(WF_THREADS, (!COUNT && !ALPHA) ? WF_PRIMARY_WAVES :
 // flipped (pack_hit always leaves it clear, the miss word has it set): no record is all-zero, and the plane is zeroed when
 // it is keyed, so a zero word says "never written".  Which items reach bounce 1 may differ between frames of one key
 // (escape masks, surfaces lit through the shadow queue): an item without a record is cast, by k_wf_trace_exact.
+// The bounce-2 hit cache (hit2_cache) is the same one bounce later - the bounce-2 ray is made from the bounce-1 hit, the
+// material there and the item's words - with a plane of its own: both kernels work from W.bounce and serve either.
 // ---------------------------------------------------------------------------
 #define WF_HIT1_FLIP 0x10000000u
 PT_D uint32_t wf_queue_item(const float4* queue, uint32_t i) { return __float_as_uint(wf_ray_rec(queue, i)[1].z); }

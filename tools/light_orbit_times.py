@@ -2,7 +2,7 @@
 1920x1080, 128 spp, 5 bounces, FILMIC): the case the camera-hit cache is for (DESIGN section 4 "The camera-hit cache").  One
 JSON line with the scene's first frames one by one (the second is the one that fills the word cache and stores the camera
 hits), the median steady frame, the frame after each of `--moves` moves of the first point light along a circle about the
-vertical axis, and the numbers of the camera-hit and bounce-1 hit caches where the library has them (an A/B library of an earlier commit, PT_GPU_LIB, has none).
+vertical axis, and the numbers of the camera-hit, bounce-1 hit, bounce-2 hit and bounce-1 visibility caches where the library has them (an A/B library of an earlier commit, PT_GPU_LIB, has none).
     timeout -k 10 600 python tools/light_orbit_times.py [--tris 500000] [--moves 8] [--steady 8]
 Needs the GPU; every step below is bounded by the caller's time limit."""
 import argparse
@@ -52,6 +52,10 @@ has_stats = hasattr(g.lib, "pt_get_hit_cache_stats")
 stats = lambda: dict(zip(("bytes", "items", "cached", "stores", "loads"), g.hit_cache_stats())) if has_stats else None
 has_hit1 = hasattr(g.lib, "pt_get_hit1_cache_stats")
 hit1 = lambda: dict(zip(("bytes", "items", "cached", "resets", "stores", "loads", "unknown_casts"), g.hit1_cache_stats())) if has_hit1 else None
+has_hit2 = hasattr(g.lib, "pt_get_hit2_cache_stats")
+hit2 = lambda: dict(zip(("bytes", "items", "cached", "resets", "stores", "loads", "unknown_casts"), g.hit2_cache_stats())) if has_hit2 else None
+has_vis1 = hasattr(g.lib, "pt_get_vis1_cache_stats")
+vis1 = lambda: dict(zip(("bytes", "items", "resets", "launches"), g.vis1_cache_stats())) if has_vis1 else None
 first = [frame() for _ in range(5)]   # (the first frame, the filling and storing frame, escape masks, the plan, a steady one)
 after_first = stats()
 steady = [frame() for _ in range(a.steady)]
@@ -70,5 +74,5 @@ print(json.dumps({"image": f"{a.width}x{a.height}", "spp": a.spp, "bounces": a.b
                   "steady_frame_ms_median": round(statistics.median(steady), 2),
                   "frame_after_light_move_ms": [round(v, 2) for v in moved],
                   "frame_after_light_move_ms_median": round(statistics.median(moved), 2), "hit_cache": stats(),
-                  "hit1_cache": hit1()}))
+                  "hit1_cache": hit1(), "hit2_cache": hit2(), "vis1_cache": vis1()}))
 g.close()

@@ -4,7 +4,7 @@ is for (DESIGN section 4 "The shadow-visibility cache").  One JSON line with the
 second stores the camera hits and zeroes the visibility plane, the third fills it), the median steady frame, the frame after
 each of `--edits` material edits (every albedo scaled), after each of as many colour-only edits of the first light, and - the
 control - after each of as many MOVES of that light, with the planes zeroed and the launches of the visibility variant
-during the moves (both must be zero), where the library has the numbers (an A/B library of an earlier commit, PT_GPU_LIB,
+during the moves (both must be zero), and the numbers of the bounce-2 hit and bounce-1 visibility caches, where the library has the numbers (an A/B library of an earlier commit, PT_GPU_LIB,
 has none).
     timeout -k 10 600 python tools/material_edit_times.py [--tris 500000] [--edits 8] [--steady 8]
 Needs the GPU; every step below is bounded by the caller's time limit."""
@@ -53,6 +53,10 @@ g = pta.GpuScene(host, device=0)
 frame = lambda: timed(lambda: g.render_device(prof, pta.Opts.make(), rgb.data_ptr(), acc.data_ptr(), 0))
 has_stats = hasattr(g.lib, "pt_get_vis_cache_stats")
 stats = lambda: dict(zip(("bytes", "items", "resets", "launches"), g.vis_cache_stats())) if has_stats else None
+has_hit2 = hasattr(g.lib, "pt_get_hit2_cache_stats")
+hit2 = lambda: dict(zip(("bytes", "items", "cached", "resets", "stores", "loads", "unknown_casts"), g.hit2_cache_stats())) if has_hit2 else None
+has_vis1 = hasattr(g.lib, "pt_get_vis1_cache_stats")
+vis1 = lambda: dict(zip(("bytes", "items", "resets", "launches"), g.vis1_cache_stats())) if has_vis1 else None
 first = [frame() for _ in range(5)]
 after_first = stats()
 steady = [frame() for _ in range(a.steady)]
@@ -100,5 +104,5 @@ print(json.dumps({"image": f"{a.width}x{a.height}", "spp": a.spp, "bounces": a.b
                   "frame_after_light_move_ms_median": round(statistics.median(after_move), 2),
                   "resets_during_moves": end["resets"] - before_moves["resets"] if has_stats else None,
                   "launches_during_moves": end["launches"] - before_moves["launches"] if has_stats else None,
-                  "vis_cache": end}))
+                  "vis_cache": end, "hit2_cache": hit2(), "vis1_cache": vis1()}))
 g.close()

@@ -527,6 +527,14 @@ int pt_get_vis_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* ite
  * The call waits for the device.  The bytes are not part of pt_scene_info's queue_bytes or device_bytes. */
 int pt_get_hit1_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* resets,
                             uint64_t* stores, uint64_t* loads, uint64_t* unknown_casts);
+/* The bounce-0 launches that read the cache of bounce-1 hits themselves (a chunk that loads its camera hits, its bounce-0
+ * shadow visibility and its bounce-1 hits: the kernel that makes the bounce-1 ray looks its hit up where the ray is made,
+ * and a path whose ray is known to miss, behind a colour that is final, ends there without a queue record), since the scene
+ * was made: those launches, the bounce-1 queue records they wrote with a known hit or miss, the records they did not write
+ * (elided), and the records they wrote for items the cache has no record of (unknown; part of pt_get_hit1_cache_stats'
+ * unknown_casts as well).  written + elided + unknown is what a frame that casts writes.  PT_HIT1_FUSED=0 (read per frame)
+ * switches these launches off: bounce 1 then loads its hits in a launch of its own.  The call waits for the device. */
+int pt_get_hit1_fused_stats(const pt_scene* scene, uint64_t* launches, uint64_t* written, uint64_t* elided, uint64_t* unknown);
 /* The scene's cache of bounce-2 hits: the bounce-1 hit cache one bounce later - the bounce-2 ray is made from the bounce-1
  * hit, the material there and the item's random words, so it has the same key (view and material table, no light, no
  * bounce count) and the same rules, values and meaning of every field.  Only frames that use the bounce-1 hit cache and

@@ -224,7 +224,9 @@ __global__ __launch_bounds__(256) void k_assemble(const uint8_t* __restrict__ ga
 __global__ void k_wf_stats(const WfCounters* __restrict__ ctr, uint32_t levels, uint32_t* __restrict__ out) {
     const uint32_t b = threadIdx.x;
     if (b >= levels) return;
-    out[4 * b + 0] = ctr[b].queue_count;
+    // (+ the records the bounce-0 kernel elided for the bounce-1 hit cache: the plan sizes queues, counts rays for the inline
+    // rule and finds a chunk's last bounce as a frame that casts would - a plan outlives the frames that elide)
+    out[4 * b + 0] = ctr[b].queue_count + ctr[b].elided_count;
     out[4 * b + 1] = ctr[b].shadow_count;
     out[4 * b + 2] = ctr[b].exact_count;
     out[4 * b + 3] = b == 0 ? ctr[0].overflow : ctr[b].offgrid_count;
@@ -662,8 +664,12 @@ struct pt_scene {
     // (k_wf_hits_store / k_wf_hits_load in pt_wavefront.h).  A camera move resets the mark.  counter[0], [1], [2]: times
     // the plane was zeroed / storing launches / loading launches; hit1_unknown: the casts the loading launches left to
     // k_wf_trace_exact (one uint64 on the device).
+    // (hit1_unknown: four uint64 - behind the counter of unknown casts, what the bounce-0 launches that read the plane
+    // themselves counted: records written, records elided, unknown; hit1_fused_launches: those launches.
+    // pt_get_hit1_fused_stats)
     FrameCache hit1_cache;
     DeviceBuffer hit1_unknown;
+    uint64_t hit1_fused_launches = 0;
     // The closest hits of the bounce-2 rays, same key: that ray is made from the bounce-1 hit, the material there and the
     // item's words - again no light, and the Russian roulette starts behind it - so what holds for bounce 1 holds one bounce
     // later.  In use in the frames hit1_cache serves that have a bounce 2; the record, the zeroing, the prefix, the counters
@@ -2276,6 +2282,9 @@ struct WfFrame {
     };
     static constexpr uint32_t HIT_BOUNCES = 3;
     BounceHits bounce_hits[HIT_BOUNCES];
+    // PT_HIT1_FUSED (read per frame; 0: off): the bounce-0 kernel of a chunk that loads camera hits, visibility and bounce-1
+    // hits reads the bounce-1 plane itself (k_wf_shade_hits<.. | 128>) - no k_wf_hits_load at bounce 1
+    bool hit1_fused = true;
     pt_scene::FrameCache* vis1_cache = nullptr;   // the bounce-1 shadow visibility, keyed to view, material table and lights
     uint32_t stats_line = 0, chunk_slot = 0;   // the frame's progress through its chunks
 };
@@ -2617,8 +2626,8 @@ void frame_caches(pt_scene& s, const Frame& f, WfFrame& wf, hipStream_t stream) 
             WfFrame::BounceHits& bh = wf.bounce_hits[e.bounce];
             bh.cache = frame_cache_frame(e.fc, e.kind, key1, items, before && f.p.bounces >= e.bounce, stream);
             if (bh.cache && !e.unknown.p) {
-                e.unknown.ensure(8);
-                HIP_CHECK(hipMemset(e.unknown.p, 0, 8));
+                e.unknown.ensure(32);   // (hit1_unknown: + the three counts of the fused launches)
+                HIP_CHECK(hipMemset(e.unknown.p, 0, 32));
             }
             bh.unknown = (unsigned long long*)e.unknown.p;
             bh.holes = bh.cache ? (uint32_t)env_num(getenv(e.env_holes), 0.0) : 0u;
@@ -2631,6 +2640,7 @@ void frame_caches(pt_scene& s, const Frame& f, WfFrame& wf, hipStream_t stream) 
         // before it listed nothing for that bounce then) does not know the rays a frame that casts it lists - a cache switched
         // off or over budget since.
         if (holes || (wf.planned && (wf.fs->plan_hit_loads & ~loads_all) != 0u)) wf.cap_e = std::max({wf.cap_e, wf.cap_q[0], wf.cap_q[1]});
+        wf.hit1_fused = env_bool(getenv("PT_HIT1_FUSED"), true);
     }
     // The shadow visibility: the hits' key plus the light count and every light's kind and position, bit for bit - not its
     // colour or `tame`, not the materials, not the bounces.  The first frame after a moved light or camera does nothing
@@ -2782,6 +2792,10 @@ struct Chunk {
         uint4* plane = nullptr;
     } bounce_hits[WfFrame::HIT_BOUNCES];
     int hits_mode(uint32_t bounce) const { return bounce < WfFrame::HIT_BOUNCES ? bounce_hits[bounce].mode : 0; }
+    // the bounce-0 kernel answers the bounce-1 casts from bounce_hits[1].plane itself (k_wf_shade_hits<.. | 128>): bounce 1
+    // launches no k_wf_hits_load.  next_ctr: the cache's device counters (pt_scene::hit1_unknown)
+    bool hit1_fused = false;
+    unsigned long long* next_ctr = nullptr;
     // the scene's bounce-1 shadow-visibility cache: the bytes of the chunk's sample batch, or null (k_og_shadow_vis)
     uint8_t* vis1_plane = nullptr;
     float4 *q_in = nullptr, *q_out = nullptr;
@@ -2872,7 +2886,8 @@ void trace_stage(pt_scene& s, const Frame& f, Chunk& c, Timeline& tl) {
 // counter), in place of trace_stage: k_wf_hits_load instead of k_wf_trace and k_wf_trace_wide, then k_wf_trace_exact for the
 // items without a record (normally none: the launch finds an empty list and returns).  All on the main stream, the shade pass
 // behind them unsplit: nothing is left that a second launch could run beside.  The shade pass before such a bounce listed no
-// ray for k_wf_trace_exact (render_chunk), so the list holds the unknown casts alone.
+// ray for k_wf_trace_exact (render_chunk), so the list holds the unknown casts alone.  A chunk whose bounce-0 kernel read the
+// plane itself (Chunk::hit1_fused, bounce 1): that kernel wrote the words, the hits and the list - k_wf_trace_exact alone.
 void hits_load_stage(pt_scene& s, const Frame& f, Chunk& c, Timeline& tl, unsigned long long* unknown) {
     const pt_scene::WfPipe& pipe = s.pipe;
     WfParams& W = c.W;
@@ -2883,10 +2898,12 @@ void hits_load_stage(pt_scene& s, const Frame& f, Chunk& c, Timeline& tl, unsign
     W.split_deferred = 0u;
     W.exact_handover = f.env.exact;
     c.split_shade = false;
-    const uint32_t grid = std::max(1u, std::min((uint32_t)s.n_cu * 16u, (W.qcap_in + 255u) / 256u));
-    hipLaunchKernelGGL(k_wf_hits_load, dim3(grid), dim3(256), 0, c.st_main, W, (const float4*)c.q_in, (uint4*)pipe.hits.p,
-                       (uint32_t*)pipe.exact[b & 1].p, c.wctr, (const uint4*)c.bounce_hits[b].plane, unknown);
-    HIP_CHECK(hipGetLastError());
+    if (!(c.hit1_fused && b == 1u)) {
+        const uint32_t grid = std::max(1u, std::min((uint32_t)s.n_cu * 16u, (W.qcap_in + 255u) / 256u));
+        hipLaunchKernelGGL(k_wf_hits_load, dim3(grid), dim3(256), 0, c.st_main, W, (const float4*)c.q_in, (uint4*)pipe.hits.p,
+                           (uint32_t*)pipe.exact[b & 1].p, c.wctr, (const uint4*)c.bounce_hits[b].plane, unknown);
+        HIP_CHECK(hipGetLastError());
+    }
     const dim3 eg(f.env.exact == 2u ? std::max(1u, (uint32_t)s.n_cu * f.env.exact_blocks / 8u) : (uint32_t)s.n_cu * 16u);
     hipLaunchKernelGGL((k_wf_trace_exact<false, false, false>), eg, dim3(WF_EXACT_THREADS), 0, c.st_main, f.dev, W, f.d_tiles,
                        (const float4*)c.q_in, (uint4*)pipe.hits.p, (const uint4*)c.rng_planes, (uint32_t*)pipe.draws.p,
@@ -2945,28 +2962,32 @@ void shade_stage(pt_scene& s, const Frame& f, const WfFrame& wf, const Chunk& c,
     };
     // the cached opaque bounce-0 kernel with the camera-hit cache (k_wf_shade_hits): stores the chunk's hits or loads them;
     // | 64, with the shadow-visibility cache (an overload with one parameter more): loads the hits, reads the chunk's
-    // visibility bytes and fills in the unknown
+    // visibility bytes and fills in the unknown; | 128, with the bounce-1 hit cache (three parameters more): answers the
+    // survivors' next casts from the chunk's records there
     auto launch_hits = [&](auto grid) {
         constexpr int G = decltype(grid)::value;
-        auto go = [&](auto... vis_plane) {
+        auto go = [&](auto... planes) {
             hipLaunchKernelGGL((k_wf_shade_hits<G>), dim3(shade_grid), dim3(WF_SHADE_THREADS), 0, c.st_main, f.dev, W, f.d_tiles,
                                (const uint4*)c.rng_planes, c.hit_plane, c.q_out, (float4*)pipe.shadow.p, (float4*)pipe.contrib.p,
-                               (float*)s.staging_buf.p, (uint32_t*)pipe.exact[(b + 1) & 1].p, block_empty, c.wctr, vis_plane...);
+                               (float*)s.staging_buf.p, (uint32_t*)pipe.exact[(b + 1) & 1].p, block_empty, c.wctr, planes...);
         };
-        if constexpr (G & 64) go(c.vis_plane);
+        if constexpr (G & 128) go(c.vis_plane, (const uint4*)c.bounce_hits[1].plane, (uint4*)pipe.hits.p, c.next_ctr);
+        else if constexpr (G & 64) go(c.vis_plane);
         else go();
         HIP_CHECK(hipGetLastError());
     };
     auto launch_shade = [&] {
         if (c.grid_mode == 3 && c.cached && c.hit_mode) {
-            // GRIDX: 11 / 15 (orthographic branch) + 16 STORE / 32 LOAD + 64 VIS (LOAD only)
-            switch ((s.grids.ortho ? 15 : 11) | c.hit_mode | (c.hit_mode == 32 && c.vis_plane ? 64 : 0)) {
+            // GRIDX: 11 / 15 (orthographic branch) + 16 STORE / 32 LOAD + 64 VIS (LOAD only) + 128 NEXT (LOAD and VIS only)
+            switch ((s.grids.ortho ? 15 : 11) | c.hit_mode | (c.hit_mode == 32 && c.vis_plane ? 64 : 0) | (c.hit1_fused ? 128 : 0)) {
             case 27: launch_hits(std::integral_constant<int, 27>{}); break;
             case 43: launch_hits(std::integral_constant<int, 43>{}); break;
             case 31: launch_hits(std::integral_constant<int, 31>{}); break;
             case 47: launch_hits(std::integral_constant<int, 47>{}); break;
             case 107: launch_hits(std::integral_constant<int, 107>{}); break;
-            default: launch_hits(std::integral_constant<int, 111>{}); break;
+            case 111: launch_hits(std::integral_constant<int, 111>{}); break;
+            case 235: launch_hits(std::integral_constant<int, 235>{}); break;
+            default: launch_hits(std::integral_constant<int, 239>{}); break;
             }
             return;
         }
@@ -3128,6 +3149,9 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
         if (bh.mode) bh.plane = (uint4*)fc->buf.p + g0;
         if (bh.mode == 32 && wf.stats_slots && wf.stats_line < wf.stats_slots) wf.fs->stats_hit_loads |= 1u << b;
     }
+    // ... and the bounce-1 hits by the bounce-0 kernel itself, where that loads the camera hits and the visibility too
+    c.hit1_fused = wf.hit1_fused && c.hit_mode == 32 && c.vis_plane != nullptr && c.hits_mode(1u) == 32;
+    c.next_ctr = wf.bounce_hits[1].unknown;
     // the bounce-1 shadow visibility: indexed by the sample's slot in its batch's staging area, which any chunk of the batch
     // may hold - so the whole batch lies below the plane's stride, not the chunk alone
     if (wf.vis1_cache) {
@@ -3205,6 +3229,10 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
             ++wf.hit_cache->counter[0];
         } else if (c.prim && c.hit_mode == 32) {
             ++wf.hit_cache->counter[1];
+            if (c.hit1_fused) {   // (the bounce-1 plane is read here: its event and its count of loads follow at bounce 1)
+                wf.bounce_hits[1].cache->touched(c.st_main);
+                ++s.hit1_fused_launches;
+            }
             if (c.vis_plane) {   // (any such launch may write the plane)
                 wf.vis_cache->touched(c.st_main);
                 ++wf.vis_cache->counter[1];
@@ -4258,6 +4286,19 @@ int pt_get_hit1_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* it
     if (!scene) return PT_ERR_INVALID;
     return bounce_hits_stats(scene, scene->hit1_cache, scene->hit1_unknown, "pt_get_hit1_cache_stats", bytes, items, items_cached, resets,
                              stores, loads, unknown_casts);
+}
+int pt_get_hit1_fused_stats(const pt_scene* scene, uint64_t* launches, uint64_t* written, uint64_t* elided, uint64_t* unknown) {
+    if (!scene) return PT_ERR_INVALID;
+    return guarded([&] {
+        uint64_t n[4] = {0, 0, 0, 0};   // (pt_scene::hit1_unknown)
+        if (scene->hit1_unknown.p) {    // (synchronises, like pt_get_hit1_cache_stats)
+            HIP_CHECK(hipSetDevice(scene->device));
+            HIP_CHECK(hipDeviceSynchronize());
+            HIP_CHECK(hipMemcpy(n, scene->hit1_unknown.p, sizeof n, hipMemcpyDeviceToHost));
+        }
+        if (cache_stats({{launches, scene->hit1_fused_launches}, {written, n[1] - n[3]}, {elided, n[2]}, {unknown, n[3]}}) != PT_OK)
+            fail(PT_ERR_INVALID, "pt_get_hit1_fused_stats: null argument");
+    });
 }
 int pt_get_hit2_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* resets,
                             uint64_t* stores, uint64_t* loads, uint64_t* unknown_casts) {

@@ -141,6 +141,9 @@ struct WfCounters {  // one set per bounce level, zeroed once per chunk
     uint32_t offgrid_count;  // shadow records k_og_shadow left to k_og_shadow_offgrid (pt_grid_kernels.h)
     uint32_t deferred_count; // casts k_wf_trace left to k_wf_trace_wide in its drain phase
     uint32_t exact_count;    // casts k_wf_trace left to k_wf_trace_exact when it fetched them (slack_is_capped)
+    // records of queue[b] that were never written: the bounce-0 kernel that reads the bounce-1 hit cache found the record's
+    // cast a miss behind a final colour (k_wf_shade_hits<.. | 128>).  A frame that casts writes queue_count + elided_count.
+    uint32_t elided_count;
 };
 
 #define WF_FLAG_TERMINATED 1u
@@ -2019,8 +2022,9 @@ constexpr uint32_t WF_ARG_OFFSET_W = (uint32_t)((sizeof(DevScene) + alignof(WfPa
 // LDS parking slots of that variant at four waves (one dword per thread each; the kernel's sh_park).  Four workgroups must
 // fit a CU's 160 KiB beside the compaction's 296 B each: 39 slots (39 KiB) at the most, forty would not.
 enum : uint32_t { PK_BRDF = 0, PK_NORMAL = 11, PK_VIEW = 14, PK_UV = 17, PK_PID = 19, PK_OUT_SLOT = 20, PK_WORD2 = 21, PK_C = 23,
-                  PK_COLOR = 26, PK_TERM0 = 29, WF_PARK_SLOTS = 32, PK_VIS = 32 };   // (PK_VIS: the VIS variants' one slot more)
-static_assert(WF_PARK_SLOTS + 1u <= 39, "four workgroups of the bounce-0 kernel must fit a CU's LDS");
+                  PK_COLOR = 26, PK_TERM0 = 29, WF_PARK_SLOTS = 32, PK_VIS = 32,   // (PK_VIS: the VIS variants' one slot more)
+                  PK_NEXT = 33 };   // (PK_NEXT: the NEXT variants' four more - the item's bounce-1 hit record)
+static_assert(WF_PARK_SLOTS + 1u + 4u <= 39, "four workgroups of the bounce-0 kernel must fit a CU's LDS");
 // GRID (origin grids, pt_grid.h): 0 - none: direct light goes through the shadow queue and k_wf_shadow / k_og_shadow;
 // 1 - every light is a point light with a grid: get_light_info (mod.rs:281-333) is evaluated HERE, light after
 //     light, so a surface costs no shadow record, no contrib entries and no colour patch (190 B of queue traffic
@@ -2041,7 +2045,10 @@ static_assert(WF_PARK_SLOTS + 1u <= 39, "four workgroups of the bounce-0 kernel 
 // the camera grid, no og_next_hit.  The ray itself is still derived: shading needs o and d.
 // + 64 * VIS (LOAD only; the second k_wf_shade_hits below): the scene's shadow-visibility cache (pt_gpu.hip FrameCache vis_cache;
 // vis_plane points at the chunk's first item there) - a light whose bits are known is not cast for.
+// + 128 * NEXT (LOAD and VIS only; the third k_wf_shade_hits below): the scene's bounce-1 hit cache (pt_gpu.hip FrameCache
+// hit1_cache; next_plane points at the chunk's first item there) - the survivors' next casts are answered here.
 // (S and W FIRST, in this order: the PARK variants read them again through the kernarg segment, wf_opaque_arg)
+#define WF_HIT1_FLIP 0x10000000u   // bit 28 of a record's word in the later bounces' hit caches ("The bounce-1 hit cache" below)
 template <bool ALPHA, bool COUNT, bool PRIMARY, int GRIDX>
 __global__ __launch_bounds__(WF_SHADE_THREADS, GRIDX ? (ALPHA ? WF_SHADE_GRID_WAVES_ALPHA : GRIDX >= 8 ? WF_SHADE_CACHED_WAVES : WF_SHADE_GRID_WAVES) : WF_SHADE_WAVES) void k_wf_shade(DevScene S, WfParams W,
                                                   const uint32_t* __restrict__ tile_offsets,
@@ -2062,6 +2069,9 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, GRIDX ? (ALPHA ? WF_SHADE_GRID_WA
                   "wf_opaque_arg: DevScene and WfParams must be the first two parameters of k_wf_shade");
     uint4* const hit_plane = nullptr;   // (k_wf_shade_hits has one)
     uint8_t* const vis_plane = nullptr;
+    const uint4* const next_plane = nullptr;   // (the third k_wf_shade_hits has these)
+    uint4* const next_hits = nullptr;
+    unsigned long long* const next_ctr = nullptr;
 #include "pt_wf_shade_body.h"
 }
 
@@ -2086,6 +2096,9 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_
     const uint32_t *const draws = nullptr, *const index_list = nullptr, *const exact_list = nullptr;
     DevCounters* const gctr = nullptr;
     uint8_t* const vis_plane = nullptr;   // (the overload below has one)
+    const uint4* const next_plane = nullptr;   // (the third overload has these)
+    uint4* const next_hits = nullptr;
+    unsigned long long* const next_ctr = nullptr;
 #include "pt_wf_shade_body.h"
 }
 
@@ -2112,6 +2125,45 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_
     static_assert(GRIDX == (11 | 32 | 64) || GRIDX == (15 | 32 | 64), "LOAD and VIS of the cached opaque variants");
     // (S and W first: wf_opaque_arg, as above)
     static_assert(wf_leading_args<WfShadeVisKernel>::scene_then_params,
+                  "wf_opaque_arg: DevScene and WfParams must be the first two parameters of k_wf_shade_hits");
+    constexpr bool ALPHA = false, COUNT = false, PRIMARY = true;
+    const float4* const queue_in = nullptr;
+    const uint4 *const hits = nullptr, *const chunk_hits = nullptr;
+    const uint32_t *const draws = nullptr, *const index_list = nullptr, *const exact_list = nullptr;
+    DevCounters* const gctr = nullptr;
+    const uint4* const next_plane = nullptr;   // (the overload below has these)
+    uint4* const next_hits = nullptr;
+    unsigned long long* const next_ctr = nullptr;
+#include "pt_wf_shade_body.h"
+}
+
+// ... and with the scene's bounce-1 hit cache (pt_gpu.hip FrameCache hit1_cache): GRIDX = 11 or 15, + 32 (LOAD) + 64 (VIS) + 128
+// (NEXT), for a chunk that lies wholly below that cache's mark.  The kernel that makes the bounce-1 ray has the item's index in
+// a register, and next_plane[i] is as dense a load as hit_plane[i]: it answers the cast where the ray is made.  A survivor
+// whose record says miss and whose colour is final (no shadow record) ENDS here - what wf_prestage_miss stages is its
+// sample, so it gets no queue record and no slot, and is counted in WfCounters::elided_count of the next bounce.  Every other
+// survivor gets its record as before and, at the same queue position, what k_wf_hits_load would have copied there: the hit
+// word and (key, u, v) in the chunk's hit plane (next_hits), or - an item without a record - an entry of the next bounce's
+// exact list.  k_wf_hits_load is not launched for such a chunk, and the bounce-1 shade pass sweeps a queue of hits (and the
+// few unknown) only.  next_ctr: four uint64 on the device - [0] the cache's counter of unknown casts (k_wf_hits_load's), and
+// of these launches alone [1] records written, unknown included, [2] records elided, [3] unknown.
+// An overload again, by its three parameters more: the kernels above keep their arguments, and their code, as they were.
+typedef void (*WfShadeNextKernel)(DevScene, WfParams, const uint32_t*, const uint4*, uint4*, float4*, float4*, float4*, float*, uint32_t*,
+                                  const uint32_t*, WfCounters*, uint8_t*, const uint4*, uint4*, unsigned long long*);
+template <int GRIDX>
+__global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_shade_hits(DevScene S, WfParams W,
+                                                  const uint32_t* __restrict__ tile_offsets, const uint4* rng_planes,
+                                                  uint4* __restrict__ hit_plane,
+                                                  float4* __restrict__ queue_out, float4* __restrict__ shadow_q,
+                                                  float4* __restrict__ contrib, float* __restrict__ staging,
+                                                  uint32_t* __restrict__ exact_next,
+                                                  const uint32_t* __restrict__ block_empty,
+                                                  WfCounters* __restrict__ ctr, uint8_t* __restrict__ vis_plane,
+                                                  const uint4* __restrict__ next_plane, uint4* __restrict__ next_hits,
+                                                  unsigned long long* __restrict__ next_ctr) {
+    static_assert(GRIDX == (11 | 32 | 64 | 128) || GRIDX == (15 | 32 | 64 | 128), "LOAD, VIS and NEXT of the cached opaque variants");
+    // (S and W first: wf_opaque_arg, as above)
+    static_assert(wf_leading_args<WfShadeNextKernel>::scene_then_params,
                   "wf_opaque_arg: DevScene and WfParams must be the first two parameters of k_wf_shade_hits");
     constexpr bool ALPHA = false, COUNT = false, PRIMARY = true;
     const float4* const queue_in = nullptr;
@@ -2388,7 +2440,6 @@ __global__ __launch_bounds__(WF_THREADS, (!COUNT && !ALPHA) ? WF_PRIMARY_WAVES :
 // The bounce-2 hit cache (hit2_cache) is the same one bounce later - the bounce-2 ray is made from the bounce-1 hit, the
 // material there and the item's words - with a plane of its own: both kernels work from W.bounce and serve either.
 // ---------------------------------------------------------------------------
-#define WF_HIT1_FLIP 0x10000000u
 PT_D uint32_t wf_queue_item(const float4* queue, uint32_t i) { return __float_as_uint(wf_ray_rec(queue, i)[1].z); }
 
 // Behind the casts and the shade passes of bounce 1 in a chunk that fills the plane: the final hit of every entry of the

@@ -3,7 +3,7 @@
 // of eight variants moved by 4-8 B; profiles/r09_experiments.txt item 0), and those variants are tuned to the byte.
 // In scope: the template parameters ALPHA, COUNT, PRIMARY, GRIDX (as constants in k_wf_shade_hits) and the kernel's
 // parameters - S, W, tile_offsets, queue_in, hits, rng_planes, draws, queue_out, shadow_q, contrib, staging, index_list,
-// exact_list, chunk_hits, exact_next, block_empty, ctr, gctr - and hit_plane, vis_plane.
+// exact_list, chunk_hits, exact_next, block_empty, ctr, gctr - and hit_plane, vis_plane, next_plane, next_hits, next_ctr.
     // index_list (bounces >= 1): null - the whole queue, entries marked WF_HIT_PENDING left out; else the entries to shade:
     // the hand-over list of k_wf_trace, whose casts k_wf_trace_wide has finished by now - `hits` is then that list's
     // own plane (W.list_cap records, by list position).  The pass over the queue runs WHILE k_wf_trace_wide walks
@@ -21,6 +21,10 @@
     static_assert(!(STORE && LOAD), "a launch stores the camera hits or loads them");
     constexpr bool VIS = (GRIDX & 64) != 0;
     static_assert(!VIS || LOAD, "the shadow-visibility cache serves the launches that load their camera hits");
+    // NEXT: the launch reads the bounce-1 hit cache as well (next_plane: the chunk's records there) - a survivor whose record
+    // says miss and whose colour is final ends here, the others get the word and the hit k_wf_hits_load would have copied
+    constexpr bool NEXT = (GRIDX & 128) != 0;
+    static_assert(!NEXT || (LOAD && VIS), "the bounce-1 hits are consumed by the launches that load camera hits and visibility");
     static_assert(!CACHED || (GRID == 3 && !COUNT), "the word cache serves the fused bounce-0 kernel");
     uint4* rng_planes_out = const_cast<uint4*>(rng_planes);   // GRID == 3 writes plane 1 (nobody reads it before bounce 1)
     static_assert(GRID < 2 || PRIMARY, "the camera grid serves bounce 0");
@@ -42,7 +46,11 @@
     };
     uint32_t n_draws = 0, n_new = 0, n_moot = 0, n_hits = 0, n_cam_tris = 0, n_masked = 0;
     LocalCtr lc = {0, 0, 0, 0, 0, 0};   // (GRID: casts made here)
-    __shared__ uint32_t sh_cnt[2][WF_SHADE_THREADS / 64];
+    // (NEXT: [2] the elided of a step; [3][0], [3][2] what threads 0 and 2 counted over the launch's steps - records written,
+    // records elided -, each its own thread's word, added to the device's counters once, at the end: an atomic per step
+    // would stand, with its round trip, in front of the compaction's barrier)
+    __shared__ uint32_t sh_cnt[NEXT ? 4 : 2][WF_SHADE_THREADS / 64];
+    if (NEXT && threadIdx.x < WF_SHADE_THREADS / 64) sh_cnt[NEXT ? 3 : 0][threadIdx.x] = 0u;
     __shared__ uint32_t sh_base[2];
     __shared__ uint32_t sh_oct[8][WF_SHADE_THREADS / 64], sh_oct_off[8][WF_SHADE_THREADS / 64];
     const uint32_t wave = threadIdx.x >> 6;
@@ -51,7 +59,7 @@
     // thread - no barrier).  The accesses are volatile: a plain store would be forwarded to its load and the register kept.
     constexpr bool PARK = CACHED && !ALPHA && WF_SHADE_PARK;
     // (wf_opaque_arg reads S at offset 0 of the kernarg segment and W right behind it: the kernels below check that)
-    __shared__ uint32_t sh_park[PARK ? WF_PARK_SLOTS + (VIS ? 1u : 0u) : 1][WF_SHADE_THREADS];   // (VIS: + PK_VIS)
+    __shared__ uint32_t sh_park[PARK ? WF_PARK_SLOTS + (VIS ? 1u : 0u) + (NEXT ? 4u : 0u) : 1][WF_SHADE_THREADS];   // (VIS: + PK_VIS; NEXT: + PK_NEXT)
     // (an LDS pointer by type: a volatile access through a generic pointer stays a flat access, one 64-bit address per slot)
     volatile __attribute__((address_space(3))) uint32_t* const park = (volatile __attribute__((address_space(3))) uint32_t*)&sh_park[0][threadIdx.x];
     auto park_u = [&](uint32_t slot, uint32_t v) { park[slot * WF_SHADE_THREADS] = v; };
@@ -102,6 +110,19 @@
     uint32_t vis = 0u;
     if constexpr (VIS) {
         if (live) vis = vis_plane[i];
+    }
+    // (NEXT) the record of the item's bounce-1 cast, as dense and as independent: read for every item, used by the survivors.
+    // (Issued behind the lights, where only the survivors would load it, its latency stood in front of the compaction's
+    // barriers in every step: the launch took 13.9 ms for the 8.1 ms of the kernel without it.)
+    // NEXT_WORD (the variant with the orthographic branch): the word alone, (key, u, v) read again where a hit is written - the
+    // whole record held through the lights is 20 B of scratch there (8 B this way); without that branch it is none, and the
+    // second read cost the launch 0.16 ms (8.29 against 8.13 ms).
+    constexpr bool NEXT_WORD = NEXT && DIRL;
+    uint4 next_rec = make_uint4(0u, 0u, 0u, 0u);
+    if constexpr (NEXT_WORD) {
+        if (live) next_rec.x = ((const uint32_t*)next_plane)[4u * (size_t)i];
+    } else if constexpr (NEXT) {
+        if (live) next_rec = next_plane[i];
     }
     if (PRIMARY && live) {  // entry i is work item i: the initial path state, built in place
         ItemRef it = decode_item(W.P, tile_offsets, W.item_base + i);
@@ -256,9 +277,11 @@
                     bool blocked = known == 2u;
                     if (known == 0u) {
                         if (PARK) park_fixed(), park_3(PK_C, c), park_3(PK_COLOR, color), park_3(PK_TERM0, term0), park_u(PK_VIS, vis);
+                        if (PARK && NEXT) park_u(PK_NEXT, next_rec.x), park_u(PK_NEXT + 1u, next_rec.y), park_u(PK_NEXT + 2u, next_rec.z), park_u(PK_NEXT + 3u, next_rec.w);
                         blocked = og_light_blocked<DIRL>(S, li, surf.pos, surf.normal, lc);
                         if (PARK) {
                             c = unpark_3(PK_C), color = unpark_3(PK_COLOR), term0 = unpark_3(PK_TERM0), vis = unpark_u(PK_VIS);
+                            if (NEXT) next_rec = make_uint4(unpark_u(PK_NEXT), unpark_u(PK_NEXT + 1u), unpark_u(PK_NEXT + 2u), unpark_u(PK_NEXT + 3u));
                             unpark_fixed();
                         }
                         vis |= ((blocked ? 2u : 1u) << (2u * li)) | 0x100u;
@@ -328,6 +351,14 @@
             }
         }
     }
+    // (NEXT) A survivor whose next cast is known to miss, behind a colour that is final: what wf_prestage_miss stages for it
+    // (below, with the other stores) IS the sample - no record, no slot, nothing for bounce 1 to read.  A to_shadow survivor
+    // keeps its record whatever the cast found: the shadow kernel patches the colour and stages the miss.
+    bool elided = false;
+    if constexpr (NEXT) {
+        elided = survive && !to_shadow && next_rec.x == (0xffffffffu ^ WF_HIT1_FLIP);
+        if (elided) survive = false;
+    }
     // ---- compaction: survivors -> queue[b+1], surface hits -> shadow queue.  One atomic per
     // workgroup and queue (wave ballots -> LDS -> one lane), not one per wavefront: the counter
     // word would otherwise cap the kernel at ~88 M wave-atomics per second.
@@ -337,6 +368,7 @@
     // wavefront of the next k_wf_trace launch fetches walk the tree in the same child order.  The position of a
     // record in a queue is free (results are keyed by out_slot), so no bit of the image changes.
     unsigned long long m_next = __ballot(survive), m_sh = __ballot(to_shadow);
+    const unsigned long long m_elided = NEXT ? __ballot(elided) : 0ull;
     uint32_t oct = 0, oct_rank = 0;
     if (W.sort_octants & 1u) {
         oct = (next_d.x < 0.f ? 1u : 0u) | (next_d.y < 0.f ? 2u : 0u) | (next_d.z < 0.f ? 4u : 0u);
@@ -350,13 +382,19 @@
     if ((threadIdx.x & 63u) == 0) {
         sh_cnt[0][wave] = (uint32_t)__popcll(m_next);
         sh_cnt[1][wave] = (uint32_t)__popcll(m_sh);
+        if constexpr (NEXT) sh_cnt[2][wave] = (uint32_t)__popcll(m_elided);
     }
     __syncthreads();
-    if (threadIdx.x < 2) {
+    if (NEXT && threadIdx.x == 2) {
+        uint32_t total = 0;
+        for (uint32_t k = 0; k < WF_SHADE_THREADS / 64; ++k) total += sh_cnt[2][k];
+        sh_cnt[NEXT ? 3 : 0][2] += total;
+    } else if (threadIdx.x < 2) {
         uint32_t total = 0;
         for (uint32_t k = 0; k < WF_SHADE_THREADS / 64; ++k) total += sh_cnt[threadIdx.x][k];
         uint32_t* counter = threadIdx.x == 0 ? &ctr[bounce + 1].queue_count : &ctr[bounce].shadow_count;
         sh_base[threadIdx.x] = total ? atomicAdd(counter, total) : 0u;
+        if (NEXT && threadIdx.x == 0) sh_cnt[NEXT ? 3 : 0][0] += total;
     } else if ((W.sort_octants & 1u) && threadIdx.x >= 64u && threadIdx.x < 64u + 8u * (WF_SHADE_THREADS / 64)) {
         // exclusive prefix of the (octant, wave) counts, octant-major
         const uint32_t e = threadIdx.x - 64u;
@@ -380,7 +418,30 @@
         to_shadow = false;
     }
     if (GRID == 3 && !CACHED && survive) rng_planes_out[(size_t)(1u - W.rng_first_plane) * W.cap + item] = later_words;   // draws 4-7 of the path
-    if (W.exact_shade_lists) {   // (wave-uniform; 0.24 % of random directions)
+    if constexpr (NEXT) {
+        // as k_wf_hits_load: the word and the hit to the chunk's hit plane at the record's queue position; an item without a
+        // record to the next bounce's exact list (whose pass over the queue is unsplit: no WF_HIT_PENDING), and counted
+        const bool unknown = survive && next_rec.x == 0u;
+        if (survive && !unknown) {
+            const uint32_t word = next_rec.x ^ WF_HIT1_FLIP;
+            ((uint32_t*)next_hits)[next_idx] = word;
+            if (NEXT_WORD && word != 0xffffffffu) {   // (volatile: a plain load is merged with the word's, and the record held)
+                const volatile uint32_t* rest = (const volatile uint32_t*)next_plane + 4u * (size_t)i;
+                next_rec.y = rest[1], next_rec.z = rest[2], next_rec.w = rest[3];
+            }
+            if (word != 0xffffffffu) ((uint4*)((uint32_t*)next_hits + W.hcap))[next_idx] = make_uint4(next_rec.y, next_rec.z, next_rec.w, 0u);
+        }
+        if (wf_any(unknown)) {
+            const uint32_t slot = wf_reserve(&ctr[bounce + 1].exact_count, unknown);
+            if (unknown && slot < W.ecap) exact_next[slot] = next_idx;
+            else if (unknown) ctr[0].overflow = 1u;
+            const unsigned long long m = __ballot(unknown);
+            if (unknown && wf_lane_rank(m) == 0u) {
+                atomicAdd(next_ctr, (unsigned long long)__popcll(m));
+                atomicAdd(next_ctr + 3, (unsigned long long)__popcll(m));
+            }
+        }
+    } else if (W.exact_shade_lists) {   // (wave-uniform; 0.24 % of random directions)
         const bool listed = survive && slack_is_capped(__builtin_amdgcn_rcpf(next_d.x), __builtin_amdgcn_rcpf(next_d.y), __builtin_amdgcn_rcpf(next_d.z));
         if (wf_any(listed)) {
             const uint32_t slot = wf_reserve(&ctr[bounce + 1].exact_count, listed);
@@ -418,6 +479,8 @@
             f3 c = mul_ew(thr, ct_eval_direct(brdf, normal, view, -1.f * ldir));
             contrib[(size_t)li * W.scap + sh_idx] = make_float4(c.x, c.y, c.z, 0.f);
         }
+    } else if (NEXT && elided) {   // the sample of a path whose next cast is known to miss
+        wf_prestage_miss(staging, out_slot, color, next_thr, ld3(S.background));
     } else if (live && hit && !survive) {  // no light can contribute and the path ends: the sample is complete
         float* out = staging + (size_t)out_slot * 3;
         out[0] = color.x;
@@ -553,6 +616,14 @@
             }
             shade_one(mine, threadIdx.x < take);
         }
+    }
+    if constexpr (NEXT) {   // (threads 0 and 2: the words they alone wrote)
+        // the elided count as records of the next queue: the frame plan sizes by written + elided
+        if (threadIdx.x == 2 && sh_cnt[3][2]) {
+            atomicAdd(&ctr[W.bounce + 1].elided_count, sh_cnt[3][2]);
+            atomicAdd(next_ctr + 2, (unsigned long long)sh_cnt[3][2]);
+        }
+        if (threadIdx.x == 0 && sh_cnt[3][0]) atomicAdd(next_ctr + 1, (unsigned long long)sh_cnt[3][0]);
     }
     if (COUNT && n_draws) atomicAdd(&gctr->rng_draws, (unsigned long long)n_draws);
     if (COUNT && n_new) atomicAdd(&gctr->samples, (unsigned long long)n_new);

@@ -543,6 +543,19 @@ int pt_get_hit1_fused_stats(const pt_scene* scene, uint64_t* launches, uint64_t*
  * The call waits for the device.  The bytes are not part of pt_scene_info's queue_bytes or device_bytes. */
 int pt_get_hit2_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* resets,
                             uint64_t* stores, uint64_t* loads, uint64_t* unknown_casts);
+/* The bounce-1 shade launches that read the bounce-1 shadow-visibility bytes themselves, and - where the chunk loads its
+ * bounce-2 hits - the bounce-2 hit cache too, since the scene was made: chunks that took that kernel (launches), the
+ * records whose lights it added itself because every live light's visibility was known (inlined: no shadow record), the
+ * records it left to the shadow queue whole - an unknown bit, or a normal too long for the light grids - (deferred), the
+ * bounce-2 records it wrote with a known hit word (next_written), the survivors that got no bounce-2 record because their
+ * colour was final and their next cast is known to miss - from the plane or from the escape masks - (next_elided), and
+ * the records it wrote for items the bounce-2 cache has no record of (next_unknown; part of pt_get_hit2_cache_stats'
+ * unknown_casts as well).  PT_VIS1_FUSED (default 1) and PT_HIT2_FUSED (default 0: measured slower), read per frame, switch the
+ * two steps: with the first off the launches are k_wf_shade's, with the second off bounce 2 loads its hits in a launch of
+ * its own and next_written and next_unknown stay zero.  Scenes with a
+ * directional light's orthographic grid never take the kernel.  The call waits for the device. */
+int pt_get_bounce1_fused_stats(const pt_scene* scene, uint64_t* launches, uint64_t* inlined, uint64_t* deferred, uint64_t* next_written,
+                               uint64_t* next_elided, uint64_t* next_unknown);
 /* The scene's cache of bounce-1 shadow visibility (one byte per work item, the encoding of the bounce-0 one; the answer
  * of a shadow cast from a bounce-1 hit depends on that hit - the view, the material table, the item's words - and on the
  * light's kind and position, not on its colour or intensity): the fields of pt_get_vis_cache_stats - device bytes, work

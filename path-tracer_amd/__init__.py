@@ -226,7 +226,7 @@ HOST_SYMBOLS = ["pth_scene_load_isf", "pth_scene_free", "pth_scene_desc", "pth_s
 GPU_SYMBOLS = ["pt_scene_create", "pt_scene_destroy", "pt_scene_set_camera", "pt_scene_set_lights", "pt_scene_set_materials", "pt_prep_create", "pt_prep_destroy", "pt_scene_create_from_prep",
                "pt_comm_unique_id", "pt_comm_create", "pt_comm_create_all", "pt_comm_destroy", "pt_gather_tiles", "pt_render_gathered", "pt_local_pixel_count", "pt_local_pixel_map",
                "pt_render", "pt_render_device", "pt_debug_render", "pt_assemble_tiles", "pt_get_timing", "pt_get_counters",
-               "pt_scene_get_info", "pt_get_cull_stats", "pt_get_rng_cache_stats", "pt_get_hit_cache_stats", "pt_get_vis_cache_stats", "pt_get_hit1_cache_stats", "pt_get_hit1_fused_stats", "pt_get_hit2_cache_stats", "pt_get_vis1_cache_stats", "pt_kernel_occupancy", "pt_scene_escape_copy", "pt_escape_query", "pt_scene_grid_header", "pt_scene_grid_copy", "pt_trace_rays", "pt_trace_rays_wavefront",
+               "pt_scene_get_info", "pt_get_cull_stats", "pt_get_rng_cache_stats", "pt_get_hit_cache_stats", "pt_get_vis_cache_stats", "pt_get_hit1_cache_stats", "pt_get_hit1_fused_stats", "pt_get_hit2_cache_stats", "pt_get_vis1_cache_stats", "pt_get_bounce1_fused_stats", "pt_kernel_occupancy", "pt_scene_escape_copy", "pt_escape_query", "pt_scene_grid_header", "pt_scene_grid_copy", "pt_trace_rays", "pt_trace_rays_wavefront",
                "pt_trace_rays_all", "pt_intersect_triangles",
                "pt_rng_words", "pt_eval_math", "pt_measure_copy_bandwidth", "pt_measure_gather_rate", "pt_last_error",
                "pt_version", "pt_render_guides", "pt_render_guides_device", "pt_denoise_params_default", "pt_denoise_scratch_bytes",
@@ -345,6 +345,8 @@ def gpu_lib():
             L.pt_get_hit2_cache_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 7
         if hasattr(L, "pt_get_vis1_cache_stats"):
             L.pt_get_vis1_cache_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 4
+        if hasattr(L, "pt_get_bounce1_fused_stats"):
+            L.pt_get_bounce1_fused_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 6
         if hasattr(L, "pt_kernel_occupancy"):
             L.pt_kernel_occupancy.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.pt_scene_grid_copy.argtypes = [vp, C.c_uint32, vp, vp]
@@ -920,6 +922,13 @@ class GpuScene:
         """The scene's cache of bounce-1 shadow visibility: (device bytes, work items of the keyed view, materials and lights,
         times the plane was zeroed, launches of the shadow kernel that reads and fills it)."""
         return self._cache_stats(self.lib.pt_get_vis1_cache_stats, 4)
+
+    def bounce1_fused_stats(self):
+        """The bounce-1 shade launches that read the bounce-1 shadow visibility (and the bounce-2 hits) themselves: (chunks that
+        took the kernel, records whose lights it added itself, records it left to the shadow queue, bounce-2 records written
+        with a known hit, survivors that got no bounce-2 record - final colour, next cast known to miss -, records written
+        for items without a cached hit).  PT_VIS1_FUSED=0 / PT_HIT2_FUSED=0 switch the steps off.  Waits for the device."""
+        return self._cache_stats(self.lib.pt_get_bounce1_fused_stats, 6)
 
     def counters(self):
         c = Counters()

@@ -226,9 +226,11 @@ __global__ void k_wf_stats(const WfCounters* __restrict__ ctr, uint32_t levels, 
     if (b >= levels) return;
     // (+ the records the bounce-0 kernel elided for the bounce-1 hit cache: the plan sizes queues, counts rays for the inline
     // rule and finds a chunk's last bounce as a frame that casts would - a plan outlives the frames that elide)
+    // (+ what the bounce-1 shade pass that adds the known lights itself left unwritten: shadow records, and the list entries
+    // of the survivors that ended there - the same rule, k_wf_shade_fused)
     out[4 * b + 0] = ctr[b].queue_count + ctr[b].elided_count;
-    out[4 * b + 1] = ctr[b].shadow_count;
-    out[4 * b + 2] = ctr[b].exact_count;
+    out[4 * b + 1] = ctr[b].shadow_count + ctr[b].inlined_count;
+    out[4 * b + 2] = ctr[b].exact_count + ctr[b].exact_elided;
     out[4 * b + 3] = b == 0 ? ctr[0].overflow : ctr[b].offgrid_count;
 }
 
@@ -565,6 +567,9 @@ struct pt_scene {
     // beside the trace of bounce b+1, so the tail of one persistent launch is filled by the other's head.
     struct WfPipe {
         DeviceBuffer queue[2], hits, shadow, contrib, ctr, rng[2], draws, offgrid, deferred, exact[2], block_mask;
+        // the hits of queue 2 where the bounce-1 shade pass answers its survivors' casts from the bounce-2 hit cache itself: that
+        // launch is still reading `hits`.  As long as queue 2 (20 B per record); like the cache it serves, not part of queue_bytes
+        DeviceBuffer hits_next;
         hipStream_t side = nullptr, side_wide = nullptr, side_exact = nullptr;
         hipEvent_t ev_shade = nullptr, ev_shadow = nullptr, ev_rng = nullptr, ev_chunk = nullptr, ev_trace = nullptr, ev_wide = nullptr,
                    ev_exact = nullptr, ev_exact_go = nullptr;
@@ -674,8 +679,12 @@ struct pt_scene {
     // item's words - again no light, and the Russian roulette starts behind it - so what holds for bounce 1 holds one bounce
     // later.  In use in the frames hit1_cache serves that have a bounce 2; the record, the zeroing, the prefix, the counters
     // and hit2_unknown as for hit1_cache (render_chunk drives both from one table, WfFrame::bounce_hits).
+    // (hit2_unknown: eight uint64 - behind the counter of unknown casts, what the bounce-1 shade launches that read the
+    // bounce-1 visibility and this plane themselves counted, k_wf_shade_fused in pt_wavefront.h; b1_fused_launches: the
+    // chunks that took that kernel.  pt_get_bounce1_fused_stats.  Allocated with either cache.)
     FrameCache hit2_cache;
     DeviceBuffer hit2_unknown;
+    uint64_t b1_fused_launches = 0;
     // The answers of the bounce-1 shadow casts of ONE view, ONE material table and ONE set of light positions: the casts
     // k_og_shadow makes for the surfaces bounce 1 reached - those depend on what hit1_cache's key holds - towards lights whose
     // kind and position are in the key, colour and intensity not.  One byte per item in vis_cache's encoding, indexed by the
@@ -2286,6 +2295,11 @@ struct WfFrame {
     // hits reads the bounce-1 plane itself (k_wf_shade_hits<.. | 128>) - no k_wf_hits_load at bounce 1
     bool hit1_fused = true;
     pt_scene::FrameCache* vis1_cache = nullptr;   // the bounce-1 shadow visibility, keyed to view, material table and lights
+    // PT_VIS1_FUSED (default 1), PT_HIT2_FUSED (default 0; both read per frame): the bounce-1 shade pass of a chunk whose batch has visibility bytes
+    // adds the lights of known visibility itself (k_wf_shade_fused<256>); ... and, where the chunk loads its bounce-2 hits, reads
+    // that plane itself too (<256 | 512>, the first switch on as well) - no k_wf_hits_load at bounce 2.  hits_next_wanted: this
+    // frame may take the second, so queue_buffers provides WfPipe::hits_next
+    bool vis1_fused = true, hit2_fused = false, hits_next_wanted = false;
     uint32_t stats_line = 0, chunk_slot = 0;   // the frame's progress through its chunks
 };
 
@@ -2486,6 +2500,7 @@ void queue_buffers(pt_scene& s, const Frame& f, const QueueEnv& qe, WfFrame& wf)
                   (!alpha || fit(w.draws, (size_t)wf.cap_h * 4u)) &&   // RNG draw index of the alpha walk
                   fit(w.offgrid, (size_t)wf.cap_s * 4u) &&   // shadow jobs left to k_og_shadow_offgrid (long normals; rays the wavefront walker does not take)
                   fit(w.exact[0], (size_t)wf.cap_e * 8u) && fit(w.exact[1], (size_t)wf.cap_e * 8u) &&   // casts left to k_wf_trace_exact: queue index + hit word
+                  (!wf.hits_next_wanted || fit(w.hits_next, (size_t)wf.cap_q[0] * 20u)) &&   // (queue 2 lives in queue[0])
                   (!f.bounce0_fused || w.block_mask.try_ensure((size_t)f.blocks64 * 4u + 4u + f.tm.n_local)) &&
                   // casts left to k_wf_trace_wide: at most one per lane in flight when the queue runs dry
                   // (4 B the queue index + 20 B a hit + 4 B the progress of the walk: wf_list_* in pt_wavefront.h)
@@ -2500,7 +2515,7 @@ void queue_buffers(pt_scene& s, const Frame& f, const QueueEnv& qe, WfFrame& wf)
             if (wf.planned) wf.fs->plan_fresh = false;
             break;
         }
-        for (DeviceBuffer* b : {&w.queue[0], &w.queue[1], &w.hits, &w.shadow, &w.contrib, &w.rng[0], &w.rng[1], &w.draws, &w.offgrid, &w.deferred, &w.exact[0], &w.exact[1], &w.block_mask})
+        for (DeviceBuffer* b : {&w.queue[0], &w.queue[1], &w.hits, &w.shadow, &w.contrib, &w.rng[0], &w.rng[1], &w.draws, &w.offgrid, &w.deferred, &w.exact[0], &w.exact[1], &w.block_mask, &w.hits_next})
             b->release();
         if (wf.planned) {   // (no room for the planned sizes: as a first frame)
             wf.planned = false;
@@ -2626,8 +2641,8 @@ void frame_caches(pt_scene& s, const Frame& f, WfFrame& wf, hipStream_t stream) 
             WfFrame::BounceHits& bh = wf.bounce_hits[e.bounce];
             bh.cache = frame_cache_frame(e.fc, e.kind, key1, items, before && f.p.bounces >= e.bounce, stream);
             if (bh.cache && !e.unknown.p) {
-                e.unknown.ensure(32);   // (hit1_unknown: + the three counts of the fused launches)
-                HIP_CHECK(hipMemset(e.unknown.p, 0, 32));
+                e.unknown.ensure(64);   // (+ the counts of the launches that read the plane themselves: three, hit2_unknown five)
+                HIP_CHECK(hipMemset(e.unknown.p, 0, 64));
             }
             bh.unknown = (unsigned long long*)e.unknown.p;
             bh.holes = bh.cache ? (uint32_t)env_num(getenv(e.env_holes), 0.0) : 0u;
@@ -2666,6 +2681,16 @@ void frame_caches(pt_scene& s, const Frame& f, WfFrame& wf, hipStream_t stream) 
     // one to four lights, every light with a grid.
     key1.insert(key1.end(), key.begin() + light_words, key.end());
     wf.vis1_cache = frame_cache_frame(s.vis1_cache, VIS1_CACHE, key1, items, wf.bounce_hits[1].cache && few_lights && f.use_light_grids, stream);
+    // The bounce-1 shade pass that reads these bytes, and the bounce-2 records, itself (render_chunk): its counters live behind
+    // the bounce-2 cache's counter of unknown casts, whether or not that cache is in use
+    wf.vis1_fused = env_bool(getenv("PT_VIS1_FUSED"), true);
+    wf.hit2_fused = env_bool(getenv("PT_HIT2_FUSED"), false);   // (measured 0.08 ms slower than the first step alone: off)
+    if (wf.vis1_cache && !s.hit2_unknown.p) {
+        s.hit2_unknown.ensure(64);
+        HIP_CHECK(hipMemset(s.hit2_unknown.p, 0, 64));
+    }
+    wf.bounce_hits[2].unknown = (unsigned long long*)s.hit2_unknown.p;
+    wf.hits_next_wanted = wf.vis1_fused && wf.hit2_fused && wf.vis1_cache && wf.bounce_hits[2].cache && !s.grids.ortho;
 }
 
 // This frame's counts, one line per (batch, chunk): taken every frame (a few KB) - the first frame's feed the plan, the
@@ -2798,6 +2823,10 @@ struct Chunk {
     unsigned long long* next_ctr = nullptr;
     // the scene's bounce-1 shadow-visibility cache: the bytes of the chunk's sample batch, or null (k_og_shadow_vis)
     uint8_t* vis1_plane = nullptr;
+    // the bounce-1 shade pass reads vis1_plane itself (k_wf_shade_fused<256>), and bounce_hits[2].plane too (| 512): then bounce 2
+    // launches no k_wf_hits_load and finds its hits in WfPipe::hits_next.  0: k_wf_shade.  Set at bounce 1, kept for bounce 2
+    int b1_fused = 0;
+    uint4* hits = nullptr;   // the hit plane of this bounce's queue (WfPipe::hits; hits_next: see above), W.hcap records long
     float4 *q_in = nullptr, *q_out = nullptr;
     bool split_shade = false;   // the shade pass in two launches (PT_WF_SPLIT)
 };
@@ -2898,15 +2927,15 @@ void hits_load_stage(pt_scene& s, const Frame& f, Chunk& c, Timeline& tl, unsign
     W.split_deferred = 0u;
     W.exact_handover = f.env.exact;
     c.split_shade = false;
-    if (!(c.hit1_fused && b == 1u)) {
+    if (!(c.hit1_fused && b == 1u) && !((c.b1_fused & 512) && b == 2u)) {   // (... or whose bounce-1 shade pass did, bounce 2)
         const uint32_t grid = std::max(1u, std::min((uint32_t)s.n_cu * 16u, (W.qcap_in + 255u) / 256u));
-        hipLaunchKernelGGL(k_wf_hits_load, dim3(grid), dim3(256), 0, c.st_main, W, (const float4*)c.q_in, (uint4*)pipe.hits.p,
+        hipLaunchKernelGGL(k_wf_hits_load, dim3(grid), dim3(256), 0, c.st_main, W, (const float4*)c.q_in, c.hits,
                            (uint32_t*)pipe.exact[b & 1].p, c.wctr, (const uint4*)c.bounce_hits[b].plane, unknown);
         HIP_CHECK(hipGetLastError());
     }
     const dim3 eg(f.env.exact == 2u ? std::max(1u, (uint32_t)s.n_cu * f.env.exact_blocks / 8u) : (uint32_t)s.n_cu * 16u);
     hipLaunchKernelGGL((k_wf_trace_exact<false, false, false>), eg, dim3(WF_EXACT_THREADS), 0, c.st_main, f.dev, W, f.d_tiles,
-                       (const float4*)c.q_in, (uint4*)pipe.hits.p, (const uint4*)c.rng_planes, (uint32_t*)pipe.draws.p,
+                       (const float4*)c.q_in, c.hits, (const uint4*)c.rng_planes, (uint32_t*)pipe.draws.p,
                        (uint32_t*)pipe.exact[b & 1].p, (const WfCounters*)c.wctr, f.gctr);
     HIP_CHECK(hipGetLastError());
     tl.end();
@@ -2941,7 +2970,7 @@ void shade_stage(pt_scene& s, const Frame& f, const WfFrame& wf, const Chunk& c,
                                                 (W.n_items + WF_SHADE_THREADS - 1u) / WF_SHADE_THREADS));
     if (tl.on && c.grid_mode >= 2) tl.fused_marks.push_back(tl.ev);
     tl.begin(2);
-    const uint4* shade_hits = (const uint4*)pipe.hits.p;
+    const uint4* shade_hits = (const uint4*)c.hits;
     const uint32_t* shade_list = nullptr;
     const uint32_t* block_empty = c.grid_mode >= 2 ? wf.block_empty : nullptr;
     // k_wf_shade<ALPHA, COUNT, PRIMARY, GRID>; GRID + 4: the variants with the orthographic branch for directional lights
@@ -2952,7 +2981,7 @@ void shade_stage(pt_scene& s, const Frame& f, const WfFrame& wf, const Chunk& c,
             hipLaunchKernelGGL((k_wf_shade<alpha, count, prim, G>), dim3(shade_grid), dim3(WF_SHADE_THREADS), 0, c.st_main, f.dev, W,
                                f.d_tiles, (const float4*)c.q_in, shade_hits, (const uint4*)c.rng_planes, (const uint32_t*)pipe.draws.p,
                                c.q_out, (float4*)pipe.shadow.p, (float4*)pipe.contrib.p, (float*)s.staging_buf.p, shade_list,
-                               (const uint32_t*)pipe.exact[b & 1].p, (const uint4*)pipe.hits.p, (uint32_t*)pipe.exact[(b + 1) & 1].p,
+                               (const uint32_t*)pipe.exact[b & 1].p, (const uint4*)c.hits, (uint32_t*)pipe.exact[(b + 1) & 1].p,
                                block_empty, c.wctr, f.gctr);
         };
         if constexpr (G >= 8) dispatch([&](auto alpha) { go(alpha, std::false_type{}, std::true_type{}); }, f.alpha);
@@ -2976,7 +3005,26 @@ void shade_stage(pt_scene& s, const Frame& f, const WfFrame& wf, const Chunk& c,
         else go();
         HIP_CHECK(hipGetLastError());
     };
+    // the bounce-1 shade pass that reads the bounce-1 visibility itself, | 512: and the bounce-2 hits (k_wf_shade_fused).  Stream
+    // order: the bytes it reads on the main stream were written on the side stream by k_og_shadow_vis of an earlier chunk -
+    // the chunk-end join of render_chunk put that behind this launch - or of an earlier frame, which the frame order (and, for a
+    // frame on another stream, the cache's event) put there; chunks of one batch touch disjoint slots, and this launch
+    // never writes the plane.  Its own k_og_shadow_vis follows it on the side stream (ev_shade) and records the cache's event.
+    auto launch_fused = [&](auto grid) {
+        constexpr int G = decltype(grid)::value;
+        hipLaunchKernelGGL((k_wf_shade_fused<G>), dim3(shade_grid), dim3(WF_SHADE_THREADS), 0, c.st_main, f.dev, W, f.d_tiles,
+                           (const float4*)c.q_in, shade_hits, (const uint4*)c.rng_planes, c.q_out, (float4*)pipe.shadow.p,
+                           (float4*)pipe.contrib.p, (float*)s.staging_buf.p, shade_list, (const uint32_t*)pipe.exact[b & 1].p,
+                           (const uint4*)c.hits, (uint32_t*)pipe.exact[(b + 1) & 1].p, c.wctr, (const uint8_t*)c.vis1_plane,
+                           (const uint4*)c.bounce_hits[2].plane, (uint4*)pipe.hits_next.p, wf.bounce_hits[2].unknown);
+        HIP_CHECK(hipGetLastError());
+    };
     auto launch_shade = [&] {
+        if (b == 1u && c.b1_fused) {
+            if (c.b1_fused & 512) launch_fused(std::integral_constant<int, 256 | 512>{});
+            else launch_fused(std::integral_constant<int, 256>{});
+            return;
+        }
         if (c.grid_mode == 3 && c.cached && c.hit_mode) {
             // GRIDX: 11 / 15 (orthographic branch) + 16 STORE / 32 LOAD + 64 VIS (LOAD only) + 128 NEXT (LOAD and VIS only)
             switch ((s.grids.ortho ? 15 : 11) | c.hit_mode | (c.hit_mode == 32 && c.vis_plane ? 64 : 0) | (c.hit1_fused ? 128 : 0)) {
@@ -3210,6 +3258,16 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
         c.grid_mode = (c.prim && f.bounce0_fused) ? (fused_rng ? 3 : 2)
                                                   : (f.use_light_grids && (f.env.inline_all || (b < wf.inline_at.size() && wf.inline_at[b])) ? 1 : 0);
         c.split_shade = false;
+        // Bounce 1 of a chunk whose batch has visibility bytes, its shadow records going through k_og_shadow_vis (an opaque,
+        // uninstrumented frame with light grids: the cache serves no other): the shade pass adds the lights whose bits are
+        // known itself; ... and, where the chunk loads its bounce-2 hits, answers its survivors' casts from that plane.  A
+        // scene with the orthographic branch takes k_wf_shade, and so does a frame with a sorting option (PT_WF_SORT): the
+        // kernel keeps its counts in the LDS row those options write.
+        if (b == 1u && wf.vis1_fused && c.vis1_plane && c.grid_mode == 0 && f.use_light_grids && !f.alpha && !f.counting && !s.grids.ortho && f.env.sort == 0u)
+            c.b1_fused = 256 | ((wf.hit2_fused && c.hits_mode(2u) == 32 && pipe.hits_next.bytes >= (size_t)W.qcap_out * 20u) ? 512 : 0);
+        // (the hits of bounce 2 in such a chunk: a plane of their own, as long as the queue)
+        c.hits = (b == 2u && (c.b1_fused & 512)) ? (uint4*)pipe.hits_next.p : (uint4*)pipe.hits.p;
+        W.hcap = (b == 2u && (c.b1_fused & 512)) ? W.qcap_in : wf.cap_h;
         // (a chunk that loads the next bounce's hits: the rays k_wf_trace would leave to k_wf_trace_exact have records like any
         // other, so this bounce's shade pass lists none of them - the exact list of the next bounce is k_wf_hits_load's, for
         // the items without one)
@@ -3237,6 +3295,10 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
                 wf.vis_cache->touched(c.st_main);
                 ++wf.vis_cache->counter[1];
             }
+        }
+        if (b == 1u && c.b1_fused) {
+            ++s.b1_fused_launches;
+            if (c.b1_fused & 512) wf.bounce_hits[2].cache->touched(c.st_main);   // (read here: its count of loads follows at bounce 2)
         }
         shadow_stage(s, f, c, tl);
         if (c.vis1_plane && b == 1u && c.grid_mode == 0) {   // (k_og_shadow_vis, on the side stream; any such launch may write the plane)
@@ -4305,6 +4367,21 @@ int pt_get_hit2_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* it
     if (!scene) return PT_ERR_INVALID;
     return bounce_hits_stats(scene, scene->hit2_cache, scene->hit2_unknown, "pt_get_hit2_cache_stats", bytes, items, items_cached, resets,
                              stores, loads, unknown_casts);
+}
+int pt_get_bounce1_fused_stats(const pt_scene* scene, uint64_t* launches, uint64_t* inlined, uint64_t* deferred, uint64_t* next_written,
+                               uint64_t* next_elided, uint64_t* next_unknown) {
+    if (!scene) return PT_ERR_INVALID;
+    return guarded([&] {
+        uint64_t n[6] = {0, 0, 0, 0, 0, 0};   // (pt_scene::hit2_unknown)
+        if (scene->hit2_unknown.p) {          // (synchronises, like pt_get_hit2_cache_stats)
+            HIP_CHECK(hipSetDevice(scene->device));
+            HIP_CHECK(hipDeviceSynchronize());
+            HIP_CHECK(hipMemcpy(n, scene->hit2_unknown.p, sizeof n, hipMemcpyDeviceToHost));
+        }
+        if (cache_stats({{launches, scene->b1_fused_launches}, {inlined, n[4]}, {deferred, n[5]}, {next_written, n[1] - n[3]},
+                         {next_elided, n[2]}, {next_unknown, n[3]}}) != PT_OK)
+            fail(PT_ERR_INVALID, "pt_get_bounce1_fused_stats: null argument");
+    });
 }
 int pt_get_vis_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* resets, uint64_t* launches) {
     if (!scene) return PT_ERR_INVALID;

@@ -144,6 +144,11 @@ struct WfCounters {  // one set per bounce level, zeroed once per chunk
     // records of queue[b] that were never written: the bounce-0 kernel that reads the bounce-1 hit cache found the record's
     // cast a miss behind a final colour (k_wf_shade_hits<.. | 128>).  A frame that casts writes queue_count + elided_count.
     uint32_t elided_count;
+    // ... and what the bounce-1 shade pass that adds the known lights itself (k_wf_shade_fused) did not write: the survivors it
+    // ended or elided count in elided_count of the next bounce; inlined_count - records of this bounce's shadow queue; of
+    // the survivors it ended, exact_elided - entries of the next bounce's exact list.  The frame plan reads the sums.
+    uint32_t inlined_count;
+    uint32_t exact_elided;
 };
 
 #define WF_FLAG_TERMINATED 1u
@@ -2170,6 +2175,48 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_
     const uint4 *const hits = nullptr, *const chunk_hits = nullptr;
     const uint32_t *const draws = nullptr, *const index_list = nullptr, *const exact_list = nullptr;
     DevCounters* const gctr = nullptr;
+#include "pt_wf_shade_body.h"
+}
+
+// The bounce-1 shade pass of an opaque, uninstrumented frame that reads the scene's bounce-1 shadow-visibility cache itself
+// (pt_gpu.hip FrameCache vis1_cache; GRIDX = 256, VIS1), and the bounce-2 hit cache as well (hit2_cache; GRIDX = 256 + 512,
+// NEXT1): k_wf_shade<false, false, false, 0> with three parameters more, for a chunk whose sample batch lies below the
+// visibility plane's stride (and, NEXT1, whose items all lie below the hit plane's mark), in a scene without the
+// orthographic branch.  Once the plane is full k_og_shadow_vis casts nothing: per record it reads what this kernel wrote
+// a moment before, looks up a byte this kernel can look up - the record's out_slot is in the queue record -, applies the
+// factor and patches a colour.  So a hit whose live lights all have known bits gets them added HERE - in light order, the
+// operands of k_og_shadow_vis: og_light_unshadowed, rad * 0.0f where blocked, the same test against zero, colour + c x rad -
+// and writes no shadow record and no contribution record: its colour is final, its miss is staged here, and the escape-mask
+// rule ends it here where the mask proves the next cast empty.  A hit with an unknown bit or a normal too long for the
+// grids goes to the shadow queue whole, as before: k_og_shadow_vis is still launched, on that queue, casts, fills the byte
+// and retires.  This kernel never casts and never writes the plane.
+// NEXT1: the item's record in the bounce-2 plane answers the survivor's next cast where the ray is made, as the bounce-0 kernel
+// does one bounce earlier (the third k_wf_shade_hits above): a miss behind a final colour ends here, a hit gets its word and
+// (key, u, v) at the record's queue position, an item without a record goes to the next bounce's exact list.  next_hits is NOT
+// the chunk's hit plane - this launch is reading that one - but a plane of the next queue's own, W.qcap_out records long.
+// next_ctr (pt_scene::hit2_unknown): six uint64 on the device - [0] the cache's counter of unknown casts, and of these launches
+// alone [1] next-bounce records written, unknown included (NEXT1), [2] survivors ended or elided here, [3] unknown, [4] records
+// whose lights were added here, [5] records deferred to the shadow queue.  What the launch leaves unwritten the frame plan
+// must still count: WfCounters::elided_count of the next bounce, inlined_count and exact_elided.
+template <int GRIDX>
+__global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES) void k_wf_shade_fused(DevScene S, WfParams W,
+                                                  const uint32_t* __restrict__ tile_offsets,
+                                                  const float4* __restrict__ queue_in, const uint4* __restrict__ hits,
+                                                  const uint4* rng_planes,
+                                                  float4* __restrict__ queue_out, float4* __restrict__ shadow_q,
+                                                  float4* __restrict__ contrib, float* __restrict__ staging,
+                                                  const uint32_t* __restrict__ index_list,
+                                                  const uint32_t* __restrict__ exact_list, const uint4* __restrict__ chunk_hits,
+                                                  uint32_t* __restrict__ exact_next, WfCounters* __restrict__ ctr,
+                                                  const uint8_t* __restrict__ vis_bytes, const uint4* __restrict__ next_plane,
+                                                  uint4* __restrict__ next_hits, unsigned long long* __restrict__ next_ctr) {
+    static_assert(GRIDX == 256 || GRIDX == (256 | 512), "VIS1, or VIS1 and NEXT1");
+    constexpr bool ALPHA = false, COUNT = false, PRIMARY = false;
+    // (what this pass does not read)
+    const uint32_t *const draws = nullptr, *const block_empty = nullptr;
+    DevCounters* const gctr = nullptr;
+    uint4* const hit_plane = nullptr;
+    uint8_t* const vis_plane = const_cast<uint8_t*>(vis_bytes);   // (the body's name for it; VIS1 only reads)
 #include "pt_wf_shade_body.h"
 }
 

@@ -26,6 +26,14 @@
     constexpr bool NEXT = (GRIDX & 128) != 0;
     static_assert(!NEXT || (LOAD && VIS), "the bounce-1 hits are consumed by the launches that load camera hits and visibility");
     static_assert(!CACHED || (GRID == 3 && !COUNT), "the word cache serves the fused bounce-0 kernel");
+    // VIS1, NEXT1 (k_wf_shade_fused: the opaque bounce-1 pass of a scene without the orthographic branch).  VIS1: the launch reads
+    // the bounce-1 shadow-visibility bytes (vis_plane, by out_slot, never written here) - a hit whose live lights all have
+    // known bits gets them added here, in light order, with the operands of k_og_shadow_vis, and writes no shadow record;
+    // any other goes to the shadow queue whole.  NEXT1: the launch reads the bounce-2 hit cache as well (next_plane, by item),
+    // as NEXT does one bounce earlier.
+    constexpr bool VIS1 = (GRIDX & 256) != 0, NEXT1 = (GRIDX & 512) != 0;
+    static_assert(!VIS1 || ((GRIDX & 255) == 0 && !ALPHA && !COUNT && !PRIMARY), "the bounce-1 visibility is read by the plain opaque later-bounce pass");
+    static_assert(!NEXT1 || VIS1, "the bounce-2 hits are consumed by the launch that adds the lights itself");
     uint4* rng_planes_out = const_cast<uint4*>(rng_planes);   // GRID == 3 writes plane 1 (nobody reads it before bounce 1)
     static_assert(GRID < 2 || PRIMARY, "the camera grid serves bounce 0");
     const bool list_pass = !PRIMARY && index_list != nullptr;
@@ -53,6 +61,12 @@
     if (NEXT && threadIdx.x < WF_SHADE_THREADS / 64) sh_cnt[NEXT ? 3 : 0][threadIdx.x] = 0u;
     __shared__ uint32_t sh_base[2];
     __shared__ uint32_t sh_oct[8][WF_SHADE_THREADS / 64], sh_oct_off[8][WF_SHADE_THREADS / 64];
+    // (VIS1: what threads 0-3 counted over the launch's steps, each its own word - next-bounce records written, shadow records
+    // written, survivors ended or elided here, records whose lights were added here -, added to the device's counters once,
+    // at the end.  The kernel has no LDS to spare and a register more is scratch: the words are sh_oct_off's last row, which
+    // only the sorting options write - render_chunk takes this kernel for unsorted frames, PT_WF_SORT=0, only.)
+    uint32_t* const fused_acc = &sh_oct_off[7][0];
+    if (VIS1 && threadIdx.x < WF_SHADE_THREADS / 64) fused_acc[threadIdx.x] = 0u;
     const uint32_t wave = threadIdx.x >> 6;
     // LDS parking (PARK: the cached opaque bounce-0 variant at four waves per SIMD): per-lane state that is cold across an
     // inline shadow cast waits in LDS, slot-major (sh_park[slot][thread]: conflict-free dwords, every slot private to its
@@ -211,9 +225,18 @@
         out_slot = __float_as_uint(q2.w);
         hit = entry_hit(e, i, h);
         if (out_slot == 0xffffffffu) live = false;  // (records of items outside the image; none since bounce 0 is fused)
+        // (VIS1) the record's visibility byte, as soon as its slot is there, and (NEXT1) the item's bounce-2 record, as soon as
+        // the item is: their latency runs under make_surface and material_sample
+        if constexpr (VIS1) {
+            if (live) vis = vis_plane[out_slot];
+        }
+        if constexpr (NEXT1) {
+            if (live && item < W.n_items) next_rec = next_plane[item];
+        }
     }
     const uint32_t bounce = PRIMARY ? 0u : W.bounce, bounces = W.P.bounces;   // (PRIMARY: no Russian roulette code at all)
     bool to_shadow = false, survive = false;
+    bool inlined = false, ended_inline = false;   // (VIS1: the lights were added here; ... and the path ended for it)
     f3 term0 = mk3(0.f, 0.f, 0.f);
     Surface surf;
     f3 next_o = o, next_d = d, next_thr = thr;
@@ -238,6 +261,7 @@
         view = -1.f * d;
         ct_init(brdf, ms);
         color = color + mul_ew(thr, ms.emissive);
+        f3 lit = color;   // (VIS1: ... with the lights)
         // (thr ⊙ eval_direct) per light.  GRID: the light's visibility is looked up here and the light added at
         // once, in light order (mod.rs:248-262).  Otherwise (and for a normal too long for the grids' margin) the
         // visibility factor is applied by the shadow kernel: the first light's term stays in registers, the others
@@ -300,6 +324,24 @@
                 }
             } else if (!moot) {
                 to_shadow = true;
+                if constexpr (VIS1) {
+                    // the light as k_og_shadow_vis would add it, should every live light of the record turn out known (bit 8,
+                    // in the register only: one of them is not)
+                    const uint32_t known = (vis >> (2u * li)) & 3u;
+                    if (known == 0u) vis |= 0x100u;
+                    f3 rad = og_light_unshadowed<false>(S, li, surf.pos);
+                    if (known == 2u) rad = rad * 0.0f;
+                    if (!(rad.x == 0.f && rad.y == 0.f && rad.z == 0.f)) lit = lit + mul_ew(c, rad);
+                }
+            }
+        }
+        if constexpr (VIS1) {
+            // all of the record's lights, or none: a partly added record would change the order of the additions.  A normal too
+            // long for the grids' margin, or an unknown bit: the record goes to the shadow queue whole, as in k_wf_shade.
+            if (to_shadow && !(vis & 0x100u) && dot3(surf.normal, surf.normal) <= S.light_grid_max_normal2) {
+                color = lit;
+                to_shadow = false;
+                inlined = true;
             }
         }
         if (COUNT && !inline_lights && !to_shadow) n_moot += S.n_lights;
@@ -348,6 +390,8 @@
                 if (!zero) color = color + bg;
                 survive = false;
                 if (COUNT) n_masked++;
+                // (VIS1: k_wf_shade would have kept this path - a record of the next queue whose cast misses)
+                if (VIS1 && !zero && inlined) ended_inline = true;
             }
         }
     }
@@ -356,6 +400,10 @@
     // keeps its record whatever the cast found: the shadow kernel patches the colour and stages the miss.
     bool elided = false;
     if constexpr (NEXT) {
+        elided = survive && !to_shadow && next_rec.x == (0xffffffffu ^ WF_HIT1_FLIP);
+        if (elided) survive = false;
+    }
+    if constexpr (NEXT1) {   // the same one bounce later
         elided = survive && !to_shadow && next_rec.x == (0xffffffffu ^ WF_HIT1_FLIP);
         if (elided) survive = false;
     }
@@ -369,6 +417,7 @@
     // record in a queue is free (results are keyed by out_slot), so no bit of the image changes.
     unsigned long long m_next = __ballot(survive), m_sh = __ballot(to_shadow);
     const unsigned long long m_elided = NEXT ? __ballot(elided) : 0ull;
+    const unsigned long long m_gone = VIS1 ? __ballot(elided || ended_inline) : 0ull, m_inlined = VIS1 ? __ballot(inlined) : 0ull;
     uint32_t oct = 0, oct_rank = 0;
     if (W.sort_octants & 1u) {
         oct = (next_d.x < 0.f ? 1u : 0u) | (next_d.y < 0.f ? 2u : 0u) | (next_d.z < 0.f ? 4u : 0u);
@@ -383,6 +432,8 @@
         sh_cnt[0][wave] = (uint32_t)__popcll(m_next);
         sh_cnt[1][wave] = (uint32_t)__popcll(m_sh);
         if constexpr (NEXT) sh_cnt[2][wave] = (uint32_t)__popcll(m_elided);
+        // (VIS1: three counts of at most 64 in the one word - the sum over the waves stays below 10 bits a field)
+        if constexpr (VIS1) sh_cnt[1][wave] = (uint32_t)__popcll(m_sh) | ((uint32_t)__popcll(m_gone) << 10) | ((uint32_t)__popcll(m_inlined) << 20);
     }
     __syncthreads();
     if (NEXT && threadIdx.x == 2) {
@@ -392,9 +443,15 @@
     } else if (threadIdx.x < 2) {
         uint32_t total = 0;
         for (uint32_t k = 0; k < WF_SHADE_THREADS / 64; ++k) total += sh_cnt[threadIdx.x][k];
+        if (VIS1 && threadIdx.x == 1) total &= 0x3ffu;
         uint32_t* counter = threadIdx.x == 0 ? &ctr[bounce + 1].queue_count : &ctr[bounce].shadow_count;
         sh_base[threadIdx.x] = total ? atomicAdd(counter, total) : 0u;
         if (NEXT && threadIdx.x == 0) sh_cnt[NEXT ? 3 : 0][0] += total;
+        if (VIS1) fused_acc[threadIdx.x] += total;
+    } else if (VIS1 && threadIdx.x < 4) {   // thread 2: the ended and the elided, thread 3: the records with their lights added here
+        uint32_t total = 0;
+        for (uint32_t k = 0; k < WF_SHADE_THREADS / 64; ++k) total += sh_cnt[1][k];
+        fused_acc[threadIdx.x] += (total >> (10u * (threadIdx.x - 1u))) & 0x3ffu;
     } else if ((W.sort_octants & 1u) && threadIdx.x >= 64u && threadIdx.x < 64u + 8u * (WF_SHADE_THREADS / 64)) {
         // exclusive prefix of the (octant, wave) counts, octant-major
         const uint32_t e = threadIdx.x - 64u;
@@ -406,7 +463,7 @@
     uint32_t next_idx = sh_base[0] + wf_lane_rank(m_next), sh_idx = sh_base[1] + wf_lane_rank(m_sh);
     for (uint32_t k = 0; k < wave; ++k) {
         next_idx += sh_cnt[0][k];
-        sh_idx += sh_cnt[1][k];
+        sh_idx += VIS1 ? (sh_cnt[1][k] & 0x3ffu) : sh_cnt[1][k];
     }
     if (W.sort_octants & 1u) next_idx = sh_base[0] + sh_oct_off[oct][wave] + oct_rank;
     __syncthreads();  // sh_cnt / sh_base are rewritten by the next step
@@ -418,9 +475,12 @@
         to_shadow = false;
     }
     if (GRID == 3 && !CACHED && survive) rng_planes_out[(size_t)(1u - W.rng_first_plane) * W.cap + item] = later_words;   // draws 4-7 of the path
-    if constexpr (NEXT) {
+    if constexpr (NEXT || NEXT1) {
         // as k_wf_hits_load: the word and the hit to the chunk's hit plane at the record's queue position; an item without a
         // record to the next bounce's exact list (whose pass over the queue is unsplit: no WF_HIT_PENDING), and counted
+        // (NEXT1: this launch is still reading the chunk's hit plane - next_hits is a plane of the next queue's own, as long
+        // as that queue)
+        const uint32_t next_hcap = NEXT1 ? W.qcap_out : W.hcap;
         const bool unknown = survive && next_rec.x == 0u;
         if (survive && !unknown) {
             const uint32_t word = next_rec.x ^ WF_HIT1_FLIP;
@@ -429,7 +489,7 @@
                 const volatile uint32_t* rest = (const volatile uint32_t*)next_plane + 4u * (size_t)i;
                 next_rec.y = rest[1], next_rec.z = rest[2], next_rec.w = rest[3];
             }
-            if (word != 0xffffffffu) ((uint4*)((uint32_t*)next_hits + W.hcap))[next_idx] = make_uint4(next_rec.y, next_rec.z, next_rec.w, 0u);
+            if (word != 0xffffffffu) ((uint4*)((uint32_t*)next_hits + next_hcap))[next_idx] = make_uint4(next_rec.y, next_rec.z, next_rec.w, 0u);
         }
         if (wf_any(unknown)) {
             const uint32_t slot = wf_reserve(&ctr[bounce + 1].exact_count, unknown);
@@ -447,6 +507,11 @@
             const uint32_t slot = wf_reserve(&ctr[bounce + 1].exact_count, listed);
             if (listed && slot < W.ecap) exact_next[slot] = next_idx;
             else if (listed) ctr[0].overflow = 1u;
+        }
+        if constexpr (VIS1) {   // the entries of the paths that ended here instead (a handful per launch): counted for the frame plan
+            const bool unlisted = ended_inline && slack_is_capped(__builtin_amdgcn_rcpf(next_d.x), __builtin_amdgcn_rcpf(next_d.y), __builtin_amdgcn_rcpf(next_d.z));
+            const unsigned long long m = __ballot(unlisted);
+            if (unlisted && wf_lane_rank(m) == 0u) atomicAdd(&ctr[bounce + 1].exact_elided, (uint32_t)__popcll(m));
         }
     }
     if (survive) {
@@ -479,7 +544,7 @@
             f3 c = mul_ew(thr, ct_eval_direct(brdf, normal, view, -1.f * ldir));
             contrib[(size_t)li * W.scap + sh_idx] = make_float4(c.x, c.y, c.z, 0.f);
         }
-    } else if (NEXT && elided) {   // the sample of a path whose next cast is known to miss
+    } else if ((NEXT || NEXT1) && elided) {   // the sample of a path whose next cast is known to miss
         wf_prestage_miss(staging, out_slot, color, next_thr, ld3(S.background));
     } else if (live && hit && !survive) {  // no light can contribute and the path ends: the sample is complete
         float* out = staging + (size_t)out_slot * 3;
@@ -624,6 +689,19 @@
             atomicAdd(next_ctr + 2, (unsigned long long)sh_cnt[3][2]);
         }
         if (threadIdx.x == 0 && sh_cnt[3][0]) atomicAdd(next_ctr + 1, (unsigned long long)sh_cnt[3][0]);
+    }
+    if constexpr (VIS1) {   // (threads 0-3: the words they alone wrote; next_ctr: pt_scene::hit2_unknown)
+        const uint32_t mine_acc = threadIdx.x < 4u ? fused_acc[threadIdx.x] : 0u;
+        if (threadIdx.x == 0 && NEXT1 && mine_acc) atomicAdd(next_ctr + 1, (unsigned long long)mine_acc);
+        if (threadIdx.x == 1 && mine_acc) atomicAdd(next_ctr + 5, (unsigned long long)mine_acc);
+        if (threadIdx.x == 2 && mine_acc) {   // as records of the next queue: the frame plan sizes by written + elided
+            atomicAdd(&ctr[W.bounce + 1].elided_count, mine_acc);
+            atomicAdd(next_ctr + 2, (unsigned long long)mine_acc);
+        }
+        if (threadIdx.x == 3 && mine_acc) {   // ... and as records of this bounce's shadow queue
+            atomicAdd(&ctr[W.bounce].inlined_count, mine_acc);
+            atomicAdd(next_ctr + 4, (unsigned long long)mine_acc);
+        }
     }
     if (COUNT && n_draws) atomicAdd(&gctr->rng_draws, (unsigned long long)n_draws);
     if (COUNT && n_new) atomicAdd(&gctr->samples, (unsigned long long)n_new);

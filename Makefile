@@ -23,7 +23,8 @@ oracle: oracle/libptoracle.so
 gpu: $(PKG)/libptgpu.so
 cli: $(PKG)/path-tracer
 
-$(BUILD)/host/%.o: $(PKG)/host/%.cpp include/ptgpu.h include/pthost.h $(PKG)/host/host_common.hpp
+HOST_HDR  := include/ptgpu.h include/pthost.h $(wildcard $(PKG)/host/*.h) $(wildcard $(PKG)/host/*.hpp)
+$(BUILD)/host/%.o: $(PKG)/host/%.cpp $(HOST_HDR)
 	@mkdir -p $(dir $@)
 	$(CXX) $(CXXFLAGS) -c $< -o $@
 
@@ -34,7 +35,8 @@ oracle/libptoracle.so: oracle/pt_oracle.cpp oracle/pt_oracle.h include/ptgpu.h
 	$(CXX) $(ORACLE_FLAGS) -shared -o $@ oracle/pt_oracle.cpp
 
 GPU_SRC := $(wildcard $(PKG)/csrc/*.hip)
-GPU_HDR := $(wildcard $(PKG)/csrc/*.h) $(wildcard $(PKG)/csrc/*.hpp) include/ptgpu.h include/pthost.h
+# (the device builder of the origin grids compiles host/og_raster.h)
+GPU_HDR := $(wildcard $(PKG)/csrc/*.h) $(wildcard $(PKG)/csrc/*.hpp) $(HOST_HDR)
 GPU_OBJ := $(patsubst $(PKG)/csrc/%.hip,$(BUILD)/gpu/%.o,$(GPU_SRC))
 $(BUILD)/gpu/%.o: $(PKG)/csrc/%.hip $(GPU_HDR)
 	@mkdir -p $(dir $@)

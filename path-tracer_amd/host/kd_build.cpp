@@ -442,6 +442,42 @@ static void kd_build(const pt_scene_desc& d, pth_kdtree& out) {
     if (n == 0)
         for (int a = 0; a < 3; ++a) root.mn[a] = root.mx[a] = 0.f;
 
+    // Spheres the f32 quadratic reports in FRONT of their surface.  Model::intersect (model.rs:26-64) forms
+    // c = |o - centre|^2 - r^2 and b^2 - 4ac at magnitude D^2 (D = |o - centre|), so the entry distance comes out as low as
+    // D - sqrt(r^2 + 21 eps D^2) - 64 eps D (the rounding analysis is in host/og_raster.h sphere_footprint): a sphere with
+    // r << 1.1e-3 D is reported up to 1.1e-3 D before its own box.  The walk ends where the next node starts behind the
+    // best hit, so a wall that hides such a sphere by less than that ended it, and the reference's first hit - the sphere -
+    // was never tested (tests/test_origin_grid_adversarial.py, the speck 300 away: 63 pixels of 6144).  The sphere therefore
+    // enters the tree with its box grown by that undershoot, inside the root box, which stays the exact one.  D is not known
+    // here: rays start at the camera and on surfaces, so it is at most the distance from the centre to the farthest corner
+    // of the root box or to the camera of the description; twice that is taken, which leaves pt_scene_set_camera room to
+    // move the camera twice as far from any sphere before the bound stops holding.  (r = 1 at D = 10: 6e-5.)
+    {
+        size_t prim = 0;
+        for (uint32_t m = 0; m < d.n_models; ++m) {
+            const pt_model& mo = d.models[m];
+            if (mo.kind == PT_MODEL_MESH) {
+                prim += mo.tri_count;
+                continue;
+            }
+            double far2 = 0, cam2 = 0;
+            for (int a = 0; a < 3; ++a) {
+                const double c = mo.center[a];
+                const double f = std::max(std::fabs(c - root.mn[a]), std::fabs(c - root.mx[a]));
+                far2 += f * f;
+                cam2 += (c - d.camera.transform[12 + a]) * (c - d.camera.transform[12 + a]);
+            }
+            const double D = 2.0 * std::sqrt(std::max(far2, cam2)), r = std::fabs((double)mo.radius), eps = 5.9604644775390625e-8;
+            const double grow = std::sqrt(r * r + 21.0 * eps * D * D) - r + 64.0 * eps * D;
+            if (std::isfinite(grow))
+                for (int a = 0; a < 3; ++a) {
+                    boxes[prim].mn[a] = std::max(root.mn[a], std::nextafterf((float)(boxes[prim].mn[a] - grow), -INFINITY));
+                    boxes[prim].mx[a] = std::min(root.mx[a], std::nextafterf((float)(boxes[prim].mx[a] + grow), INFINITY));
+                }
+            ++prim;
+        }
+    }
+
     std::vector<PrimGeom> geom(n);
     {
         size_t prim = 0;

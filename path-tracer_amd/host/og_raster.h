@@ -300,7 +300,26 @@ OG_HD inline Footprint sphere_footprint(const GridParams& P, const pt_model& mo)
         fp.poly[k] = c + u * (rad * oct_cos(k)) + w * (rad * oct_sin(k));
     }
     fp.margin = margin;
-    fp.mindist = round_down((dmin - P.ray_offset - P.abs_slack - 64.0 * kEps32 * D) * (1.0 - 1e-5));
+    // ---- distance bound: error model of the f32 quadratic (model.rs:26-64) for a ray from o, |o - O| <= ray_offset, whose
+    // entry distance |o + d t1 - o| is the sphere's sorting key.  With D' = |o - centre| <= D + ray_offset, everything
+    // divided by a = |d|^2 (whose own rounding enters as a relative error, so max_dir_len drops out):
+    //   beta = -b / (2 |d|),  q = disc / (4 a) = beta^2 - c,  key = beta - sqrt(q);  exactly q = r^2 - p^2 (p: the centre's
+    //   distance from the ray's line) and beta = sqrt(D'^2 - p^2).
+    // First-order roundings (eps = 2^-24), all at magnitude D'^2 whatever r is:
+    //   c = fl(oc . oc) - fl(r r):  2 (oc's components) + 3 (dot product) + 1 (r r, r < D') + 1 (difference)     7 eps D'^2
+    //   b^2:  2 beta x 4 eps D' (oc's components 1 + dot product 3) + 1 (the square)                              9 eps D'^2
+    //   4 a c:  3 (a = d . d) + 1 (the product) on |c| <= D'^2                                                    4 eps D'^2
+    //   the difference b^2 - 4ac: eps q (below the others)
+    // so the computed q <= r^2 - p^2 + 20 eps D'^2 (21 with the second-order terms), and the computed key is at least
+    // sqrt(D'^2 - p^2) - sqrt(r^2 + E - p^2) minus the linear terms below, E = 21 eps D'^2; that grows with p (r^2 + E < D'^2),
+    // so its minimum is at p = 0:  D' - sqrt(r^2 + E) - a small sphere far away loses sqrt(E) ~ 1.1e-3 D, not r.
+    // Linear terms: beta 4 eps D', the square root 1, t1's difference, 2a and quotient 6, the hit point o + d t1 and its
+    // distance from o 6.5 (17.5 eps D' in all: 64 eps D covers them with the second order), and the hit point's own
+    // coordinates are rounded at THEIR magnitude, <= |O| + D': eps |O| more (2 eps |O| taken).
+    const double Dp = D + P.ray_offset;
+    const double r_eff = sqrt(r * r + 21.0 * kEps32 * Dp * Dp);
+    const Vec O = P.origin;
+    fp.mindist = round_down((D - r_eff - P.ray_offset - P.abs_slack - 64.0 * kEps32 * D - 2.0 * kEps32 * len(O)) * (1.0 - 1e-5));
     return fp;
 }
 

@@ -300,8 +300,14 @@ bool params_point_ext(const float origin[3], uint32_t res, float ray_offset, flo
     // (the f32 rounding of the normalised shadow-ray direction moves the far end of the ray by ~1e-7 of its length)
     P.ray_offset = ray_offset > 0 ? ray_offset + 4e-7 * ext : 0.0;
     P.abs_slack = 1e-6 * ext + 1e-30;
-    // a ray that misses O by ray_offset deviates by ray_offset / distance: at most 1/8 cell beyond near_radius
-    P.near_radius = std::max(1e-5 * ext, P.ray_offset > 0 ? 3.0 * P.ray_offset / (0.125 * 2.0 / res) : 0.0);
+    // a ray that misses O by ray_offset deviates by asin(ray_offset / distance); every footprint's margin carries that angle
+    // as 3 ray_offset / reach (og_raster.h), so near_radius is no matter of correctness: it caps what the term may cost, at 8
+    // cells.  Up to there x = ray_offset / reach <= 8 cell angles / 3, and the arcsine exceeds x by x^3 / 6: in cells
+    // 9.5 (2 / res)^2, i.e. 0.037 at res 32 (the smallest automatic resolution) - inside the 1/8 cell of base_margin; a
+    // coarser grid keeps the 1/8 cell this cap used to be everywhere.  (With 1/8 cell a light 0.02 above a floor of 2e-3
+    // triangles sent 202 of them to the global list and its grid was not built.)
+    const double near_cells = res >= 32 ? 8.0 : 0.125;
+    P.near_radius = std::max(1e-5 * ext, P.ray_offset > 0 ? 3.0 * P.ray_offset / (near_cells * 2.0 / res) : 0.0);
 
     return true;
 }

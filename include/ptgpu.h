@@ -566,6 +566,31 @@ int pt_get_bounce1_fused_stats(const pt_scene* scene, uint64_t* launches, uint64
  * stays), colour and intensity edits keep it.  PT_VIS1_CACHE=0 switches the cache off, PT_VIS1_CACHE_GIB (1) is its
  * budget; both are read per frame.  The bytes are not part of pt_scene_info's queue_bytes or device_bytes. */
 int pt_get_vis1_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* resets, uint64_t* launches);
+/* The same caches by bounce.  Besides bounces 1 and 2 (above; they answer here too, with the same numbers) a scene keeps the
+ * closest hits of bounces 3, 4 and 5 and the shadow visibility of bounces 2, 3 and 4: no light enters a later bounce's ray,
+ * and the roulette of bounces 4+ draws from the item's words, so every later bounce's hits have the bounce-1 hits' key and
+ * the visibility at bounce b that key plus the lights' kinds and positions.  A hit plane is in use where the plane one
+ * bounce earlier is and the frame has that bounce; a visibility plane where that bounce's hit plane is, under
+ * pt_get_vis1_cache_stats' conditions.  All hit planes are keyed, zeroed and stored by the same frame; a frame with more
+ * than 5 bounces casts bounces 6+.
+ *   pt_get_bounce_hits_cache_stats: bounce 1-5, the fields of pt_get_hit1_cache_stats (unknown_casts: that bounce's own).
+ *   pt_get_bounce_vis_cache_stats:  bounce 1-4, the fields of pt_get_vis1_cache_stats.
+ *   pt_get_bounce_fused_stats:      bounce 1-4, the fields of pt_get_bounce1_fused_stats for the shade launches of that
+ *                                   bounce that add the lights of known visibility themselves; next_written and
+ *                                   next_unknown are bounce 1's alone (PT_HIT2_FUSED).
+ * Any other bounce: PT_ERR_INVALID.  The first and third wait for the device.
+ * Switches, read per frame: PT_TAIL_HIT_CACHE (default 1) and PT_TAIL_HIT_CACHE_GIB (8, PER PLANE) for the hit planes of
+ * bounces 3-5 as a group; PT_TAIL_VIS_CACHE (1) and PT_TAIL_VIS_CACHE_GIB (1, per plane) for the visibility planes of
+ * bounces 2-4; PT_TAIL_VIS_FUSED for the shade pass of bounces 2-4.  A plane is 16 bytes (hits) or 1 byte (visibility)
+ * per work item of the frame, however few items reach the bounce; a plane the device cannot provide is switched off for
+ * the scene, and with it the planes of the bounces behind it.  The bytes are not part of pt_scene_info's queue_bytes or
+ * device_bytes. */
+int pt_get_bounce_hits_cache_stats(const pt_scene* scene, uint32_t bounce, uint64_t* bytes, uint64_t* items, uint64_t* items_cached,
+                                   uint64_t* resets, uint64_t* stores, uint64_t* loads, uint64_t* unknown_casts);
+int pt_get_bounce_vis_cache_stats(const pt_scene* scene, uint32_t bounce, uint64_t* bytes, uint64_t* items, uint64_t* resets,
+                                  uint64_t* launches);
+int pt_get_bounce_fused_stats(const pt_scene* scene, uint32_t bounce, uint64_t* launches, uint64_t* inlined, uint64_t* deferred,
+                              uint64_t* next_written, uint64_t* next_elided, uint64_t* next_unknown);
 /* Workgroups of the fused bounce-0 kernel of opaque scenes that the runtime places on one compute unit of `device`
  * (hipOccupancyMaxActiveBlocksPerMultiprocessor at the kernel's workgroup size): which = 0 the variant that computes
  * its ChaCha words, 1 the variant that reads them from the word cache, 2 and 3 the variants of 1 that store and that

@@ -226,7 +226,7 @@ HOST_SYMBOLS = ["pth_scene_load_isf", "pth_scene_free", "pth_scene_desc", "pth_s
 GPU_SYMBOLS = ["pt_scene_create", "pt_scene_destroy", "pt_scene_set_camera", "pt_scene_set_lights", "pt_scene_set_materials", "pt_prep_create", "pt_prep_destroy", "pt_scene_create_from_prep",
                "pt_comm_unique_id", "pt_comm_create", "pt_comm_create_all", "pt_comm_destroy", "pt_gather_tiles", "pt_render_gathered", "pt_local_pixel_count", "pt_local_pixel_map",
                "pt_render", "pt_render_device", "pt_debug_render", "pt_assemble_tiles", "pt_get_timing", "pt_get_counters",
-               "pt_scene_get_info", "pt_get_cull_stats", "pt_get_rng_cache_stats", "pt_get_hit_cache_stats", "pt_get_vis_cache_stats", "pt_get_hit1_cache_stats", "pt_get_hit1_fused_stats", "pt_get_hit2_cache_stats", "pt_get_vis1_cache_stats", "pt_get_bounce1_fused_stats", "pt_kernel_occupancy", "pt_scene_escape_copy", "pt_escape_query", "pt_scene_grid_header", "pt_scene_grid_copy", "pt_trace_rays", "pt_trace_rays_wavefront",
+               "pt_scene_get_info", "pt_get_cull_stats", "pt_get_rng_cache_stats", "pt_get_hit_cache_stats", "pt_get_vis_cache_stats", "pt_get_hit1_cache_stats", "pt_get_hit1_fused_stats", "pt_get_hit2_cache_stats", "pt_get_vis1_cache_stats", "pt_get_bounce1_fused_stats", "pt_get_bounce_hits_cache_stats", "pt_get_bounce_vis_cache_stats", "pt_get_bounce_fused_stats", "pt_kernel_occupancy", "pt_scene_escape_copy", "pt_escape_query", "pt_scene_grid_header", "pt_scene_grid_copy", "pt_trace_rays", "pt_trace_rays_wavefront",
                "pt_trace_rays_all", "pt_intersect_triangles",
                "pt_rng_words", "pt_eval_math", "pt_measure_copy_bandwidth", "pt_measure_gather_rate", "pt_last_error",
                "pt_version", "pt_render_guides", "pt_render_guides_device", "pt_denoise_params_default", "pt_denoise_scratch_bytes",
@@ -347,6 +347,9 @@ def gpu_lib():
             L.pt_get_vis1_cache_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 4
         if hasattr(L, "pt_get_bounce1_fused_stats"):
             L.pt_get_bounce1_fused_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 6
+        for name, n in (("pt_get_bounce_hits_cache_stats", 7), ("pt_get_bounce_vis_cache_stats", 4), ("pt_get_bounce_fused_stats", 6)):
+            if hasattr(L, name):
+                getattr(L, name).argtypes = [vp, C.c_uint32] + [C.POINTER(C.c_uint64)] * n
         if hasattr(L, "pt_kernel_occupancy"):
             L.pt_kernel_occupancy.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.pt_scene_grid_copy.argtypes = [vp, C.c_uint32, vp, vp]
@@ -929,6 +932,25 @@ class GpuScene:
         with a known hit, survivors that got no bounce-2 record - final colour, next cast known to miss -, records written
         for items without a cached hit).  PT_VIS1_FUSED=0 / PT_HIT2_FUSED=0 switch the steps off.  Waits for the device."""
         return self._cache_stats(self.lib.pt_get_bounce1_fused_stats, 6)
+
+    def _bounce_stats(self, getter, bounce, n):
+        return self._cache_stats(lambda handle, *out: getter(handle, C.c_uint32(bounce), *out), n)
+
+    def bounce_hits_cache_stats(self, bounce):
+        """The scene's cache of the hits of `bounce` (1-5): the fields of hit1_cache_stats.  Bounces 3-5 are switched as a group,
+        PT_TAIL_HIT_CACHE=0 / PT_TAIL_HIT_CACHE_GIB (per plane).  Waits for the device."""
+        return self._bounce_stats(self.lib.pt_get_bounce_hits_cache_stats, bounce, 7)
+
+    def bounce_vis_cache_stats(self, bounce):
+        """The scene's cache of the shadow visibility of `bounce` (1-4): the fields of vis1_cache_stats.  Bounces 2-4 are
+        switched as a group, PT_TAIL_VIS_CACHE=0 / PT_TAIL_VIS_CACHE_GIB (per plane)."""
+        return self._bounce_stats(self.lib.pt_get_bounce_vis_cache_stats, bounce, 4)
+
+    def bounce_fused_stats(self, bounce):
+        """The shade launches of `bounce` (1-4) that read that bounce's shadow visibility themselves: the fields of
+        bounce1_fused_stats (the last three are bounce 1's alone).  Bounces 2-4: PT_TAIL_VIS_FUSED=0 switches them off.
+        Waits for the device."""
+        return self._bounce_stats(self.lib.pt_get_bounce_fused_stats, bounce, 6)
 
     def counters(self):
         c = Counters()

@@ -692,7 +692,26 @@ struct pt_scene {
     // valid items that the enumeration fixes), no mark; k_og_shadow_vis reads a record's byte, casts for what is unknown
     // and writes the byte back.  counter[0], [1]: times the plane was zeroed / launches of the variant.
     FrameCache vis1_cache;
-    std::vector<DevLight> host_lights;   // the lights as the device has them (the visibility cache's key)
+    // The same pairing for the bounces behind them, by bounce: the closest hits of the rays of bounces 3-5 (tail_hits[b - 3];
+    // the roulette of bounces 4+ draws from the item's words, so the bounce-1 hits' key holds for every later bounce) and the
+    // shadow visibility of bounces 2-4 (tail_vis[b - 2]; vis1_cache's key, encoding and index).  One plane, one event and one
+    // block of device counters each.  hits_unknown(b): eight uint64 - [0] the casts the loading launches of bounce b left to
+    // k_wf_trace_exact, [1..5] what the shade launches of bounce b - 1 that read that bounce's visibility themselves counted
+    // (k_wf_shade_fused; hit2_unknown above is hits_unknown(2)); fused_launches(b): the chunks whose bounce-b shade pass took
+    // that kernel.  hits_cache(b), vis_cache_of(b): the table by bounce, bounces 1 and 2 included (pt_get_bounce_*_stats).
+    static constexpr uint32_t HIT_BOUNCES = 6;   // bounces 1-5 have a hit cache, bounces 1-4 a visibility cache
+    FrameCache tail_hits[HIT_BOUNCES - 3], tail_vis[HIT_BOUNCES - 3];
+    DeviceBuffer tail_unknown[HIT_BOUNCES - 3];
+    uint64_t tail_fused_launches[HIT_BOUNCES - 3] = {0, 0, 0};
+    FrameCache& hits_cache(uint32_t b) { return b == 1u ? hit1_cache : b == 2u ? hit2_cache : tail_hits[b - 3u]; }
+    const FrameCache& hits_cache(uint32_t b) const { return const_cast<pt_scene*>(this)->hits_cache(b); }
+    DeviceBuffer& hits_unknown(uint32_t b) { return b == 1u ? hit1_unknown : b == 2u ? hit2_unknown : tail_unknown[b - 3u]; }
+    const DeviceBuffer& hits_unknown(uint32_t b) const { return const_cast<pt_scene*>(this)->hits_unknown(b); }
+    FrameCache& vis_cache_of(uint32_t b) { return b == 1u ? vis1_cache : tail_vis[b - 2u]; }
+    const FrameCache& vis_cache_of(uint32_t b) const { return const_cast<pt_scene*>(this)->vis_cache_of(b); }
+    uint64_t& fused_launches(uint32_t b) { return b == 1u ? b1_fused_launches : tail_fused_launches[b - 2u]; }
+    uint64_t fused_launches(uint32_t b) const { return b == 1u ? b1_fused_launches : tail_fused_launches[b - 2u]; }
+    std::vector<DevLight> host_lights;  // the lights as the device has them (the visibility cache's key)
     uint64_t camera_generation = 0;   // bumped by pt_scene_set_camera
     uint64_t material_generation = 0;   // bumped by pt_scene_set_materials
     uint64_t queue_bytes_last = 0;   // bytes of the path queues of the last frame (pt_scene_get_info)
@@ -1883,6 +1902,7 @@ void scene_set_camera(pt_scene& s, const pt_camera& cam) {
     s.hit_cache.mark = 0;
     s.hit1_cache.mark = 0;
     s.hit2_cache.mark = 0;
+    for (pt_scene::FrameCache& fc : s.tail_hits) fc.mark = 0;
 }
 
 // pt_scene_set_lights.  The light grids are those grids_on_device builds for the new lights (all or none), their parameters
@@ -2283,23 +2303,28 @@ struct WfFrame {
     // enumeration, the camera hits, keyed to its view, the shadow visibility, keyed to its view and lights
     pt_scene::FrameCache *rng_cache = nullptr, *hit_cache = nullptr, *vis_cache = nullptr;
     // the hits of the bounces that have a cache of them (hit1_cache, hit2_cache), keyed to the frame's view and material
-    // table: by bounce (entry 0 stays empty - the camera hits are the bounce-0 kernel's).  A third bounce is a third entry.
+    // table: by bounce (entry 0 stays empty - the camera hits are the bounce-0 kernel's).  Bounces 3-5: pt_scene::tail_hits.
     struct BounceHits {
         pt_scene::FrameCache* cache = nullptr;
-        uint32_t holes = 0;                      // PT_HIT1_CACHE_HOLES / PT_HIT2_CACHE_HOLES (study switches, read per frame)
+        uint32_t holes = 0;                      // PT_HIT1_CACHE_HOLES / PT_HIT2_CACHE_HOLES / PT_TAIL_HIT_CACHE_HOLES (study switches, read per frame)
         unsigned long long* unknown = nullptr;   // the casts the loading launches left to k_wf_trace_exact (on the device)
     };
-    static constexpr uint32_t HIT_BOUNCES = 3;
+    static constexpr uint32_t HIT_BOUNCES = pt_scene::HIT_BOUNCES;
     BounceHits bounce_hits[HIT_BOUNCES];
+    // the shadow visibility of the bounces that have a cache of it, by bounce (entry 1: pt_scene::vis1_cache; 2-4: pt_scene::tail_vis),
+    // and whether that bounce's shade pass adds the lights of known visibility itself (PT_VIS1_FUSED; 2-4: PT_TAIL_VIS_FUSED)
+    pt_scene::FrameCache* bounce_vis[HIT_BOUNCES] = {};
+    bool vis_fused[HIT_BOUNCES] = {};
+    // the device counters of the fused shade launches of bounce b: behind the next bounce's counter of unknown casts
+    unsigned long long* fused_ctr(uint32_t b) const { return b + 1u < HIT_BOUNCES ? bounce_hits[b + 1u].unknown : nullptr; }
     // PT_HIT1_FUSED (read per frame; 0: off): the bounce-0 kernel of a chunk that loads camera hits, visibility and bounce-1
     // hits reads the bounce-1 plane itself (k_wf_shade_hits<.. | 128>) - no k_wf_hits_load at bounce 1
     bool hit1_fused = true;
-    pt_scene::FrameCache* vis1_cache = nullptr;   // the bounce-1 shadow visibility, keyed to view, material table and lights
     // PT_VIS1_FUSED (default 1), PT_HIT2_FUSED (default 0; both read per frame): the bounce-1 shade pass of a chunk whose batch has visibility bytes
     // adds the lights of known visibility itself (k_wf_shade_fused<256>); ... and, where the chunk loads its bounce-2 hits, reads
     // that plane itself too (<256 | 512>, the first switch on as well) - no k_wf_hits_load at bounce 2.  hits_next_wanted: this
     // frame may take the second, so queue_buffers provides WfPipe::hits_next
-    bool vis1_fused = true, hit2_fused = false, hits_next_wanted = false;
+    bool hit2_fused = false, hits_next_wanted = false;   // (PT_VIS1_FUSED: vis_fused[1])
     uint32_t stats_line = 0, chunk_slot = 0;   // the frame's progress through its chunks
 };
 
@@ -2555,6 +2580,9 @@ constexpr FrameCacheKind VIS_CACHE = {"PT_VIS_CACHE", "PT_VIS_CACHE_GIB", 1.0, 1
 constexpr FrameCacheKind HIT1_CACHE = {"PT_HIT1_CACHE", "PT_HIT1_CACHE_GIB", 8.0, 16u, ~0ull, true};
 constexpr FrameCacheKind HIT2_CACHE = {"PT_HIT2_CACHE", "PT_HIT2_CACHE_GIB", 8.0, 16u, ~0ull, true};
 constexpr FrameCacheKind VIS1_CACHE = {"PT_VIS1_CACHE", "PT_VIS1_CACHE_GIB", 1.0, 1u, ~0ull, true};
+// (the planes of bounces 3-5 and 2-4: one switch and one budget PER PLANE for each group)
+constexpr FrameCacheKind TAIL_HIT_CACHE = {"PT_TAIL_HIT_CACHE", "PT_TAIL_HIT_CACHE_GIB", 8.0, 16u, ~0ull, true};
+constexpr FrameCacheKind TAIL_VIS_CACHE = {"PT_TAIL_VIS_CACHE", "PT_TAIL_VIS_CACHE_GIB", 1.0, 1u, ~0ull, true};
 
 // One frame cache and this frame, of `items` work items and key `key`: the cache if the frame uses it, keyed to `key`.
 // Keying happens when a frame of a key directly follows another of the same - also one that was switched off or not
@@ -2623,31 +2651,30 @@ void frame_caches(pt_scene& s, const Frame& f, WfFrame& wf, hipStream_t stream) 
     // second zeroes the plane and stores, the third loads; a light orbit loads throughout.  Eligible: the frames the hit
     // cache serves that have a bounce 1; any other frame leaves the records alone.
     // The bounce-2 hits: the same key, the same rules, one bounce later - in use where the bounce-1 hits are and the frame
-    // has a bounce 2.  Both planes are keyed, zeroed and stored by the same frame.
+    // has a bounce 2.  Bounces 3-5 (pt_scene::tail_hits; PT_TAIL_HIT_CACHE, one budget per plane): the same again, each in
+    // use where the bounce before it is - a plane switched off, over budget or not to be had takes those behind it out of
+    // use.  All planes are keyed, zeroed and stored by the same frame; a frame with more bounces casts bounces >= 6.
     std::vector<uint64_t> key1 = key;
     key1.push_back(s.material_generation);
+    // (a counter block: the cache's unknown casts + the counts of the launches that read the plane themselves, pt_scene::hits_unknown)
+    auto counter_block = [](DeviceBuffer& b) {
+        if (b.p) return;
+        b.ensure(64);
+        HIP_CHECK(hipMemset(b.p, 0, 64));
+    };
     {
-        struct Entry {
-            uint32_t bounce;
-            pt_scene::FrameCache& fc;
-            const FrameCacheKind& kind;
-            DeviceBuffer& unknown;
-            const char* env_holes;
-        } table[] = {{1u, s.hit1_cache, HIT1_CACHE, s.hit1_unknown, "PT_HIT1_CACHE_HOLES"},
-                     {2u, s.hit2_cache, HIT2_CACHE, s.hit2_unknown, "PT_HIT2_CACHE_HOLES"}};
         bool before = wf.hit_cache != nullptr, holes = false;
         uint32_t loads_all = 0;   // bit b: every item of the frame loads bounce b
-        for (Entry& e : table) {
-            WfFrame::BounceHits& bh = wf.bounce_hits[e.bounce];
-            bh.cache = frame_cache_frame(e.fc, e.kind, key1, items, before && f.p.bounces >= e.bounce, stream);
-            if (bh.cache && !e.unknown.p) {
-                e.unknown.ensure(64);   // (+ the counts of the launches that read the plane themselves: three, hit2_unknown five)
-                HIP_CHECK(hipMemset(e.unknown.p, 0, 64));
-            }
-            bh.unknown = (unsigned long long*)e.unknown.p;
-            bh.holes = bh.cache ? (uint32_t)env_num(getenv(e.env_holes), 0.0) : 0u;
+        for (uint32_t b = 1; b < WfFrame::HIT_BOUNCES; ++b) {
+            const FrameCacheKind& kind = b == 1u ? HIT1_CACHE : b == 2u ? HIT2_CACHE : TAIL_HIT_CACHE;
+            const char* env_holes = b == 1u ? "PT_HIT1_CACHE_HOLES" : b == 2u ? "PT_HIT2_CACHE_HOLES" : "PT_TAIL_HIT_CACHE_HOLES";
+            WfFrame::BounceHits& bh = wf.bounce_hits[b];
+            bh.cache = frame_cache_frame(s.hits_cache(b), kind, key1, items, before && f.p.bounces >= b, stream);
+            if (bh.cache) counter_block(s.hits_unknown(b));
+            bh.unknown = (unsigned long long*)s.hits_unknown(b).p;
+            bh.holes = bh.cache ? (uint32_t)env_num(getenv(env_holes), 0.0) : 0u;
             holes = holes || bh.holes != 0u;
-            if (bh.cache && bh.cache->mark >= items) loads_all |= 1u << e.bounce;
+            if (bh.cache && bh.cache->mark >= items) loads_all |= 1u << b;
             before = bh.cache != nullptr;
         }
         // The exact list as long as the queue it indexes where the plan's count of it does not cover this frame: the study
@@ -2679,18 +2706,21 @@ void frame_caches(pt_scene& s, const Frame& f, WfFrame& wf, hipStream_t stream) 
     // batch lies below the plane's stride and whose bounce-1 shadow records go through k_og_shadow runs the variant that
     // reads the plane and fills in what is unknown (render_chunk).  Eligible: the frames the bounce-1 hit cache serves, with
     // one to four lights, every light with a grid.
+    // The shadow visibility of bounces 2-4 (pt_scene::tail_vis; PT_TAIL_VIS_CACHE, one budget per plane): the same key, each
+    // plane eligible where that bounce's hit cache is in use.
+    // The shade pass of such a bounce that reads these bytes itself (render_chunk; bounce 1: and the bounce-2 records): its
+    // counters live behind the next bounce's counter of unknown casts, whether or not that cache is in use
     key1.insert(key1.end(), key.begin() + light_words, key.end());
-    wf.vis1_cache = frame_cache_frame(s.vis1_cache, VIS1_CACHE, key1, items, wf.bounce_hits[1].cache && few_lights && f.use_light_grids, stream);
-    // The bounce-1 shade pass that reads these bytes, and the bounce-2 records, itself (render_chunk): its counters live behind
-    // the bounce-2 cache's counter of unknown casts, whether or not that cache is in use
-    wf.vis1_fused = env_bool(getenv("PT_VIS1_FUSED"), true);
-    wf.hit2_fused = env_bool(getenv("PT_HIT2_FUSED"), false);   // (measured 0.08 ms slower than the first step alone: off)
-    if (wf.vis1_cache && !s.hit2_unknown.p) {
-        s.hit2_unknown.ensure(64);
-        HIP_CHECK(hipMemset(s.hit2_unknown.p, 0, 64));
+    const bool tail_fused = env_bool(getenv("PT_TAIL_VIS_FUSED"), true);
+    for (uint32_t b = 1; b + 1u < WfFrame::HIT_BOUNCES; ++b) {
+        wf.bounce_vis[b] = frame_cache_frame(s.vis_cache_of(b), b == 1u ? VIS1_CACHE : TAIL_VIS_CACHE, key1, items,
+                                             wf.bounce_hits[b].cache && few_lights && f.use_light_grids, stream);
+        wf.vis_fused[b] = b == 1u ? env_bool(getenv("PT_VIS1_FUSED"), true) : tail_fused;
+        if (wf.bounce_vis[b]) counter_block(s.hits_unknown(b + 1u));
+        wf.bounce_hits[b + 1u].unknown = (unsigned long long*)s.hits_unknown(b + 1u).p;
     }
-    wf.bounce_hits[2].unknown = (unsigned long long*)s.hit2_unknown.p;
-    wf.hits_next_wanted = wf.vis1_fused && wf.hit2_fused && wf.vis1_cache && wf.bounce_hits[2].cache && !s.grids.ortho;
+    wf.hit2_fused = env_bool(getenv("PT_HIT2_FUSED"), false);   // (measured 0.08 ms slower than the first step alone: off)
+    wf.hits_next_wanted = wf.vis_fused[1] && wf.hit2_fused && wf.bounce_vis[1] && wf.bounce_hits[2].cache && !s.grids.ortho;
 }
 
 // This frame's counts, one line per (batch, chunk): taken every frame (a few KB) - the first frame's feed the plan, the
@@ -2821,11 +2851,14 @@ struct Chunk {
     // launches no k_wf_hits_load.  next_ctr: the cache's device counters (pt_scene::hit1_unknown)
     bool hit1_fused = false;
     unsigned long long* next_ctr = nullptr;
-    // the scene's bounce-1 shadow-visibility cache: the bytes of the chunk's sample batch, or null (k_og_shadow_vis)
-    uint8_t* vis1_plane = nullptr;
-    // the bounce-1 shade pass reads vis1_plane itself (k_wf_shade_fused<256>), and bounce_hits[2].plane too (| 512): then bounce 2
+    // the scene's shadow-visibility caches of bounces 1-4, by bounce: the bytes of the chunk's sample batch, or null (k_og_shadow_vis)
+    uint8_t* bounce_vis_plane[WfFrame::HIT_BOUNCES] = {};
+    uint8_t* vis_plane_of(uint32_t bounce) const { return bounce < WfFrame::HIT_BOUNCES ? bounce_vis_plane[bounce] : nullptr; }
+    // the bounce-1 shade pass reads bounce_vis_plane[1] itself (k_wf_shade_fused<256>), and bounce_hits[2].plane too (| 512): then bounce 2
     // launches no k_wf_hits_load and finds its hits in WfPipe::hits_next.  0: k_wf_shade.  Set at bounce 1, kept for bounce 2
     int b1_fused = 0;
+    // this bounce's shade pass is k_wf_shade_fused (bounce 1: b1_fused; bounces 2-4: 256, with that bounce's plane); 0: k_wf_shade
+    int fused = 0;
     uint4* hits = nullptr;   // the hit plane of this bounce's queue (WfPipe::hits; hits_next: see above), W.hcap records long
     float4 *q_in = nullptr, *q_out = nullptr;
     bool split_shade = false;   // the shade pass in two launches (PT_WF_SPLIT)
@@ -3015,13 +3048,13 @@ void shade_stage(pt_scene& s, const Frame& f, const WfFrame& wf, const Chunk& c,
         hipLaunchKernelGGL((k_wf_shade_fused<G>), dim3(shade_grid), dim3(WF_SHADE_THREADS), 0, c.st_main, f.dev, W, f.d_tiles,
                            (const float4*)c.q_in, shade_hits, (const uint4*)c.rng_planes, c.q_out, (float4*)pipe.shadow.p,
                            (float4*)pipe.contrib.p, (float*)s.staging_buf.p, shade_list, (const uint32_t*)pipe.exact[b & 1].p,
-                           (const uint4*)c.hits, (uint32_t*)pipe.exact[(b + 1) & 1].p, c.wctr, (const uint8_t*)c.vis1_plane,
-                           (const uint4*)c.bounce_hits[2].plane, (uint4*)pipe.hits_next.p, wf.bounce_hits[2].unknown);
+                           (const uint4*)c.hits, (uint32_t*)pipe.exact[(b + 1) & 1].p, c.wctr, (const uint8_t*)c.bounce_vis_plane[b],
+                           (const uint4*)c.bounce_hits[2].plane, (uint4*)pipe.hits_next.p, wf.fused_ctr(b));   // (the planes of | 512: bounce 1 only)
         HIP_CHECK(hipGetLastError());
     };
     auto launch_shade = [&] {
-        if (b == 1u && c.b1_fused) {
-            if (c.b1_fused & 512) launch_fused(std::integral_constant<int, 256 | 512>{});
+        if (c.fused) {   // (bounces 1-4 of a chunk whose batch has that bounce's visibility bytes: render_chunk)
+            if (c.fused & 512) launch_fused(std::integral_constant<int, 256 | 512>{});
             else launch_fused(std::integral_constant<int, 256>{});
             return;
         }
@@ -3094,11 +3127,11 @@ void shadow_stage(pt_scene& s, const Frame& f, const Chunk& c, Timeline& tl) {
         offgrid(std::false_type{}, (uint32_t)s.n_cu);
     } else if (f.use_light_grids) {   // every light a point light with a grid: plain grid-stride kernel
         const dim3 g((uint32_t)s.n_cu * std::max(1u, f.env.ogs_blocks));
-        if (c.vis1_plane && c.b == 1u) {   // the scene's bounce-1 shadow-visibility cache (opaque, uninstrumented frames)
+        if (c.vis_plane_of(c.b)) {  // the scene's shadow-visibility cache of this bounce (opaque, uninstrumented frames)
             dispatch([&](auto dirl) {
                 hipLaunchKernelGGL((k_og_shadow_vis<dirl>), g, dim3(256), 0, st_shadow, f.dev, Ws, (const float4*)pipe.shadow.p,
                                    (const float4*)pipe.contrib.p, c.q_out, (float*)s.staging_buf.p, (uint32_t*)pipe.offgrid.p, c.wctr,
-                                   c.vis1_plane);
+                                   c.bounce_vis_plane[c.b]);
             }, s.grids.ortho);
         } else {
             dispatch([&](auto alpha, auto count, auto dirl) {
@@ -3200,12 +3233,14 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
     // ... and the bounce-1 hits by the bounce-0 kernel itself, where that loads the camera hits and the visibility too
     c.hit1_fused = wf.hit1_fused && c.hit_mode == 32 && c.vis_plane != nullptr && c.hits_mode(1u) == 32;
     c.next_ctr = wf.bounce_hits[1].unknown;
-    // the bounce-1 shadow visibility: indexed by the sample's slot in its batch's staging area, which any chunk of the batch
-    // may hold - so the whole batch lies below the plane's stride, not the chunk alone
-    if (wf.vis1_cache) {
+    // the shadow visibility of bounces 1-4: indexed by the sample's slot in its batch's staging area, which any chunk of the
+    // batch may hold - so the whole batch lies below the plane's stride, not the chunk alone
+    for (uint32_t b = 1; b < WfFrame::HIT_BOUNCES; ++b) {
+        const pt_scene::FrameCache* vc = wf.bounce_vis[b];
+        if (!vc) continue;
         const uint64_t batch0 = (uint64_t)(P.sample_begin / f.batch) * wf.items_per_batch;
         const uint64_t batch1 = batch0 + (uint64_t)f.blocks64 * 64u * (P.sample_end - P.sample_begin);
-        if (batch1 <= wf.vis1_cache->stride) c.vis1_plane = (uint8_t*)wf.vis1_cache->buf.p + batch0;
+        if (batch1 <= vc->stride) c.bounce_vis_plane[b] = (uint8_t*)vc->buf.p + batch0;
     }
     if (fused_rng && !c.cached && pipe.rng[0].bytes < (size_t)wf.cap * 16u) {   // (queue_buffers left the plane out)
         s.pipe.rng[0].ensure((size_t)wf.cap * 16u);
@@ -3263,8 +3298,12 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
         // known itself; ... and, where the chunk loads its bounce-2 hits, answers its survivors' casts from that plane.  A
         // scene with the orthographic branch takes k_wf_shade, and so does a frame with a sorting option (PT_WF_SORT): the
         // kernel keeps its counts in the LDS row those options write.
-        if (b == 1u && wf.vis1_fused && c.vis1_plane && c.grid_mode == 0 && f.use_light_grids && !f.alpha && !f.counting && !s.grids.ortho && f.env.sort == 0u)
-            c.b1_fused = 256 | ((wf.hit2_fused && c.hits_mode(2u) == 32 && pipe.hits_next.bytes >= (size_t)W.qcap_out * 20u) ? 512 : 0);
+        // Bounces 2-4 with a plane of their own: the same pass (256 alone: the next hits are k_wf_hits_load's), with that
+        // bounce's bytes and a counter block of that bounce's own (WfFrame::fused_ctr).
+        c.fused = 0;
+        if (b < WfFrame::HIT_BOUNCES && wf.vis_fused[b] && c.vis_plane_of(b) && c.grid_mode == 0 && f.use_light_grids && !f.alpha && !f.counting && !s.grids.ortho && f.env.sort == 0u)
+            c.fused = 256 | ((b == 1u && wf.hit2_fused && c.hits_mode(2u) == 32 && pipe.hits_next.bytes >= (size_t)W.qcap_out * 20u) ? 512 : 0);
+        if (b == 1u) c.b1_fused = c.fused;
         // (the hits of bounce 2 in such a chunk: a plane of their own, as long as the queue)
         c.hits = (b == 2u && (c.b1_fused & 512)) ? (uint4*)pipe.hits_next.p : (uint4*)pipe.hits.p;
         W.hcap = (b == 2u && (c.b1_fused & 512)) ? W.qcap_in : wf.cap_h;
@@ -3296,14 +3335,14 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
                 ++wf.vis_cache->counter[1];
             }
         }
-        if (b == 1u && c.b1_fused) {
-            ++s.b1_fused_launches;
-            if (c.b1_fused & 512) wf.bounce_hits[2].cache->touched(c.st_main);   // (read here: its count of loads follows at bounce 2)
+        if (c.fused) {
+            ++s.fused_launches(b);   // (by bounce: b1_fused_launches counts bounce 1's alone)
+            if (c.fused & 512) wf.bounce_hits[2].cache->touched(c.st_main);   // (read here: its count of loads follows at bounce 2)
         }
         shadow_stage(s, f, c, tl);
-        if (c.vis1_plane && b == 1u && c.grid_mode == 0) {   // (k_og_shadow_vis, on the side stream; any such launch may write the plane)
-            wf.vis1_cache->touched(c.st_shadow);
-            ++wf.vis1_cache->counter[1];
+        if (c.vis_plane_of(b) && c.grid_mode == 0) {   // (k_og_shadow_vis, on the side stream; any such launch may write the plane)
+            wf.bounce_vis[b]->touched(c.st_shadow);
+            ++wf.bounce_vis[b]->counter[1];
         }
         if (hits_mode == 16) {   // the records are behind this launch: the prefix grows by the chunk
             hits_store_stage(s, f, c, tl, wf.bounce_hits[b].holes, g0, !stored);
@@ -4392,6 +4431,34 @@ int pt_get_vis1_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* it
     if (!scene) return PT_ERR_INVALID;
     const pt_scene::FrameCache& fc = scene->vis1_cache;
     return cache_stats({{bytes, fc.buf.bytes}, {items, fc.items}, {resets, fc.counter[0]}, {launches, fc.counter[1]}});
+}
+// The same numbers by bounce (pt_scene::hits_cache, vis_cache_of, hits_unknown): hits 1-5, visibility and fused passes 1-4.
+int pt_get_bounce_hits_cache_stats(const pt_scene* scene, uint32_t bounce, uint64_t* bytes, uint64_t* items, uint64_t* items_cached,
+                                   uint64_t* resets, uint64_t* stores, uint64_t* loads, uint64_t* unknown_casts) {
+    if (!scene || bounce < 1u || bounce >= pt_scene::HIT_BOUNCES) return PT_ERR_INVALID;
+    return bounce_hits_stats(scene, scene->hits_cache(bounce), scene->hits_unknown(bounce), "pt_get_bounce_hits_cache_stats", bytes, items,
+                             items_cached, resets, stores, loads, unknown_casts);
+}
+int pt_get_bounce_vis_cache_stats(const pt_scene* scene, uint32_t bounce, uint64_t* bytes, uint64_t* items, uint64_t* resets, uint64_t* launches) {
+    if (!scene || bounce < 1u || bounce + 1u >= pt_scene::HIT_BOUNCES) return PT_ERR_INVALID;
+    const pt_scene::FrameCache& fc = scene->vis_cache_of(bounce);
+    return cache_stats({{bytes, fc.buf.bytes}, {items, fc.items}, {resets, fc.counter[0]}, {launches, fc.counter[1]}});
+}
+int pt_get_bounce_fused_stats(const pt_scene* scene, uint32_t bounce, uint64_t* launches, uint64_t* inlined, uint64_t* deferred,
+                              uint64_t* next_written, uint64_t* next_elided, uint64_t* next_unknown) {
+    if (!scene || bounce < 1u || bounce + 1u >= pt_scene::HIT_BOUNCES) return PT_ERR_INVALID;
+    return guarded([&] {
+        uint64_t n[6] = {0, 0, 0, 0, 0, 0};
+        const DeviceBuffer& block = scene->hits_unknown(bounce + 1u);   // (behind the next bounce's counter of unknown casts)
+        if (block.p) {                                                  // (synchronises, like pt_get_bounce1_fused_stats)
+            HIP_CHECK(hipSetDevice(scene->device));
+            HIP_CHECK(hipDeviceSynchronize());
+            HIP_CHECK(hipMemcpy(n, block.p, sizeof n, hipMemcpyDeviceToHost));
+        }
+        if (cache_stats({{launches, scene->fused_launches(bounce)}, {inlined, n[4]}, {deferred, n[5]},
+                         {next_written, n[1] - n[3]}, {next_elided, n[2]}, {next_unknown, n[3]}}) != PT_OK)
+            fail(PT_ERR_INVALID, "pt_get_bounce_fused_stats: null argument");
+    });
 }
 int pt_kernel_occupancy(int device, int which, int* blocks_per_cu) {
     return guarded([&] {

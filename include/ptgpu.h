@@ -535,6 +535,20 @@ int pt_get_hit1_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* it
  * unknown_casts as well).  written + elided + unknown is what a frame that casts writes.  PT_HIT1_FUSED=0 (read per frame)
  * switches these launches off: bounce 1 then loads its hits in a launch of its own.  The call waits for the device. */
 int pt_get_hit1_fused_stats(const pt_scene* scene, uint64_t* launches, uint64_t* written, uint64_t* elided, uint64_t* unknown);
+/* The scene's cache of bounce-0 continuations (the direction the BRDF samples at every work item's camera hit and the
+ * throughput behind it: 32 B per item in two planes; they are made from the camera hit, the material there and the item's
+ * random words - the key of the bounce-1 hits - so the launches that look the bounce-1 hit up in the bounce-0 kernel load
+ * them instead of sampling): its device bytes, the work items of the view and material table it is keyed to, how many of
+ * them are cached so far, how often the planes were zeroed, the storing and the loading launches, and the hit lanes a
+ * loading launch found without a record (missing: never, by construction - a check), since the scene was made.  The frame
+ * that stores the bounce-1 hits stores it, from the bounce-0 kernel that frame runs anyway; only frames that use the
+ * bounce-1 hit cache use it; pt_scene_set_materials and pt_scene_set_camera re-key it (the allocation stays), light edits
+ * keep it.  PT_CONT_CACHE=0 switches the cache off, PT_CONT_CACHE_GIB (8) is its budget; PT_CONT_ESCAPE=1 (default 0) lets the
+ * loading launches take the escape-mask test's answer from the record too, where the scene's masks are those the records were
+ * stored under; all three are read per frame.  The call
+ * waits for the device.  The bytes are not part of pt_scene_info's queue_bytes or device_bytes. */
+int pt_get_cont_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* resets,
+                            uint64_t* stores, uint64_t* loads, uint64_t* missing);
 /* The scene's cache of bounce-2 hits: the bounce-1 hit cache one bounce later - the bounce-2 ray is made from the bounce-1
  * hit, the material there and the item's random words, so it has the same key (view and material table, no light, no
  * bounce count) and the same rules, values and meaning of every field.  Only frames that use the bounce-1 hit cache and
@@ -594,8 +608,9 @@ int pt_get_bounce_fused_stats(const pt_scene* scene, uint32_t bounce, uint64_t* 
 /* Workgroups of the fused bounce-0 kernel of opaque scenes that the runtime places on one compute unit of `device`
  * (hipOccupancyMaxActiveBlocksPerMultiprocessor at the kernel's workgroup size): which = 0 the variant that computes
  * its ChaCha words, 1 the variant that reads them from the word cache, 2 and 3 the variants of 1 that store and that
- * load the camera hits, 4 the variant of 3 with the shadow-visibility cache and 5 that variant of scenes with a
- * directional light.  One workgroup is one wave per SIMD. */
+ * load the camera hits, 4 the variant of 3 with the shadow-visibility cache, 5 that variant of scenes with a
+ * directional light and 6 the variant that also reads the bounce-1 hits and loads the bounce-0 continuation.  One
+ * workgroup is one wave per SIMD. */
 int pt_kernel_occupancy(int device, int which, int* blocks_per_cu);
 
 /* Scene statistics after the KD build. */

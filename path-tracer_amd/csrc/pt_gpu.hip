@@ -675,6 +675,17 @@ struct pt_scene {
     FrameCache hit1_cache;
     DeviceBuffer hit1_unknown;
     uint64_t hit1_fused_launches = 0;
+    // The bounce-0 continuations of ONE view and ONE material table - the direction the BRDF samples at the camera hit and the
+    // throughput behind it: made from what the bounce-1 hits' key holds, so that key, its eligibility and its re-keying are
+    // theirs.  Two planes of `stride` uint4 (pt_wf_shade_body.h CONT_STORE / CONT_LOAD), zeroed when they are keyed and filled
+    // as a prefix with a mark of its own: by the bounce-0 launches of the chunks whose bounce-1 hits are stored in that frame
+    // (k_wf_shade_hits<.. | 1024>), read by the launches that read the bounce-1 hits themselves (<.. | 2048>).  A camera move
+    // resets the mark.  counter[0], [1], [2]: times the planes were zeroed / storing launches / loading launches; the hit
+    // lanes a loading launch found without a record (none, ever) are word 6 of hit1_unknown.  pt_get_cont_cache_stats
+    // (the escape test's answer in the records, PT_CONT_ESCAPE: escape_generation is bumped wherever the masks are built, dropped
+    // or rebuilt; cont_escape_generation is the one the records were stored under - 0: none, or stored under more than one)
+    FrameCache cont_cache;
+    uint64_t escape_generation = 1, cont_escape_generation = 0;
     // The closest hits of the bounce-2 rays, same key: that ray is made from the bounce-1 hit, the material there and the
     // item's words - again no light, and the Russian roulette starts behind it - so what holds for bounce 1 holds one bounce
     // later.  In use in the frames hit1_cache serves that have a bounce 2; the record, the zeroing, the prefix, the counters
@@ -1606,6 +1617,7 @@ void escape_masks_build(pt_scene& s) {
         HIP_CHECK(hipMemcpy(st, d_stats, 16, hipMemcpyDeviceToHost));
         (void)hipFree(d_stats);
         D.escape = (const float4*)buf;
+        ++s.escape_generation;
         s.escape_delta = E.delta_in;
         s.info.escape_prims = st[0];
         s.info.escape_clear_fraction = st[0] ? (float)((double)st[1] / (384.0 * st[0])) : 0.f;
@@ -1887,6 +1899,7 @@ void scene_set_camera(pt_scene& s, const pt_camera& cam) {
         s.release(D.escape);
         s.info.device_bytes -= (uint64_t)D.n_prims * 80u;
         D.escape = nullptr;
+        ++s.escape_generation;
         s.escape_tried = false;
         s.frames_rendered = 0;
         s.info.escape_build_seconds = 0.f;
@@ -1901,6 +1914,7 @@ void scene_set_camera(pt_scene& s, const pt_camera& cam) {
     ++s.camera_generation;
     s.hit_cache.mark = 0;
     s.hit1_cache.mark = 0;
+    s.cont_cache.mark = 0;
     s.hit2_cache.mark = 0;
     for (pt_scene::FrameCache& fc : s.tail_hits) fc.mark = 0;
 }
@@ -2320,6 +2334,11 @@ struct WfFrame {
     // PT_HIT1_FUSED (read per frame; 0: off): the bounce-0 kernel of a chunk that loads camera hits, visibility and bounce-1
     // hits reads the bounce-1 plane itself (k_wf_shade_hits<.. | 128>) - no k_wf_hits_load at bounce 1
     bool hit1_fused = true;
+    // the bounce-0 continuations (pt_scene::cont_cache), keyed like the bounce-1 hits; nullptr: not in use
+    pt_scene::FrameCache* cont_cache = nullptr;
+    // PT_CONT_ESCAPE (read per frame): the loading launches use the escape test's recorded answer where the scene's masks are
+    // those the records were stored under
+    bool cont_escape = false;
     // PT_VIS1_FUSED (default 1), PT_HIT2_FUSED (default 0; both read per frame): the bounce-1 shade pass of a chunk whose batch has visibility bytes
     // adds the lights of known visibility itself (k_wf_shade_fused<256>); ... and, where the chunk loads its bounce-2 hits, reads
     // that plane itself too (<256 | 512>, the first switch on as well) - no k_wf_hits_load at bounce 2.  hits_next_wanted: this
@@ -2561,7 +2580,7 @@ void queue_buffers(pt_scene& s, const Frame& f, const QueueEnv& qe, WfFrame& wf)
     s.frame_planned_last = wf.planned ? 1u : 0u;
 }
 
-// What differs between the scene's six frame caches, apart from their keys and the frames they serve (frame_caches).
+// What differs between the scene's frame caches, apart from their keys and the frames they serve (frame_caches).
 struct FrameCacheKind {
     const char *env_switch, *env_gib;   // "0": off; the budget in GiB - both read per frame, the tests switch them
     double default_gib;
@@ -2578,6 +2597,10 @@ constexpr FrameCacheKind VIS_CACHE = {"PT_VIS_CACHE", "PT_VIS_CACHE_GIB", 1.0, 1
 // (zeroed AND a prefix: the memset of a new key also starts an empty prefix - frame_cache_frame resets the mark either way -
 // and, there being no device sync, every launch that reads the plane records the event too, not only those that write)
 constexpr FrameCacheKind HIT1_CACHE = {"PT_HIT1_CACHE", "PT_HIT1_CACHE_GIB", 8.0, 16u, ~0ull, true};
+#ifndef PT_CONT_ESCAPE_DEFAULT
+#define PT_CONT_ESCAPE_DEFAULT false   // (measured against the cache alone: profiles/r19_experiments.txt item 8)
+#endif
+constexpr FrameCacheKind CONT_CACHE = {"PT_CONT_CACHE", "PT_CONT_CACHE_GIB", 8.0, 32u, ~0ull, true};   // (two planes of 16 B)
 constexpr FrameCacheKind HIT2_CACHE = {"PT_HIT2_CACHE", "PT_HIT2_CACHE_GIB", 8.0, 16u, ~0ull, true};
 constexpr FrameCacheKind VIS1_CACHE = {"PT_VIS1_CACHE", "PT_VIS1_CACHE_GIB", 1.0, 1u, ~0ull, true};
 // (the planes of bounces 3-5 and 2-4: one switch and one budget PER PLANE for each group)
@@ -2684,6 +2707,10 @@ void frame_caches(pt_scene& s, const Frame& f, WfFrame& wf, hipStream_t stream) 
         if (holes || (wf.planned && (wf.fs->plan_hit_loads & ~loads_all) != 0u)) wf.cap_e = std::max({wf.cap_e, wf.cap_q[0], wf.cap_q[1]});
         wf.hit1_fused = env_bool(getenv("PT_HIT1_FUSED"), true);
     }
+    // The bounce-0 continuations: the bounce-1 hits' key, in use in the frames that cache serves - stored by the frame that
+    // stores those hits, loaded by the launches that read them in the bounce-0 kernel.  Light edits leave it alone.
+    wf.cont_cache = frame_cache_frame(s.cont_cache, CONT_CACHE, key1, items, wf.bounce_hits[1].cache != nullptr, stream);
+    wf.cont_escape = env_bool(getenv("PT_CONT_ESCAPE"), PT_CONT_ESCAPE_DEFAULT);
     // The shadow visibility: the hits' key plus the light count and every light's kind and position, bit for bit - not its
     // colour or `tame`, not the materials, not the bounces.  The first frame after a moved light or camera does nothing
     // new, a light orbit or a camera path never zeroes and never allocates; from the keying frame's memset on, every chunk
@@ -2851,6 +2878,12 @@ struct Chunk {
     // launches no k_wf_hits_load.  next_ctr: the cache's device counters (pt_scene::hit1_unknown)
     bool hit1_fused = false;
     unsigned long long* next_ctr = nullptr;
+    // the scene's cache of bounce-0 continuations: 1024 - the bounce-0 kernel stores the chunk's records at cont_plane (plane 1:
+    // cont_stride records behind), 2048 - it loads them instead of sampling the BRDF, 0 - neither
+    int cont_mode = 0;
+    uint4* cont_plane = nullptr;
+    size_t cont_stride = 0;
+    uint32_t cont_flags = 0;   // bit 0: the records' escape answers hold for the scene's masks (the loading variant's flag argument)
     // the scene's shadow-visibility caches of bounces 1-4, by bounce: the bytes of the chunk's sample batch, or null (k_og_shadow_vis)
     uint8_t* bounce_vis_plane[WfFrame::HIT_BOUNCES] = {};
     uint8_t* vis_plane_of(uint32_t bounce) const { return bounce < WfFrame::HIT_BOUNCES ? bounce_vis_plane[bounce] : nullptr; }
@@ -3025,7 +3058,8 @@ void shade_stage(pt_scene& s, const Frame& f, const WfFrame& wf, const Chunk& c,
     // the cached opaque bounce-0 kernel with the camera-hit cache (k_wf_shade_hits): stores the chunk's hits or loads them;
     // | 64, with the shadow-visibility cache (an overload with one parameter more): loads the hits, reads the chunk's
     // visibility bytes and fills in the unknown; | 128, with the bounce-1 hit cache (three parameters more): answers the
-    // survivors' next casts from the chunk's records there
+    // survivors' next casts from the chunk's records there; | 1024 / | 2048, with the continuation cache (two parameters
+    // more): stores the sampled direction and the throughput / loads them
     auto launch_hits = [&](auto grid) {
         constexpr int G = decltype(grid)::value;
         auto go = [&](auto... planes) {
@@ -3033,7 +3067,10 @@ void shade_stage(pt_scene& s, const Frame& f, const WfFrame& wf, const Chunk& c,
                                (const uint4*)c.rng_planes, c.hit_plane, c.q_out, (float4*)pipe.shadow.p, (float4*)pipe.contrib.p,
                                (float*)s.staging_buf.p, (uint32_t*)pipe.exact[(b + 1) & 1].p, block_empty, c.wctr, planes...);
         };
-        if constexpr (G & 128) go(c.vis_plane, (const uint4*)c.bounce_hits[1].plane, (uint4*)pipe.hits.p, c.next_ctr);
+        if constexpr (G & 2048) go(c.vis_plane, (const uint4*)c.bounce_hits[1].plane, (uint4*)pipe.hits.p, c.next_ctr, c.cont_plane, c.cont_stride, c.cont_flags);
+        else if constexpr ((G & 1024) && (G & 64)) go(c.vis_plane, c.cont_plane, c.cont_stride);
+        else if constexpr (G & 1024) go(c.cont_plane, c.cont_stride);
+        else if constexpr (G & 128) go(c.vis_plane, (const uint4*)c.bounce_hits[1].plane, (uint4*)pipe.hits.p, c.next_ctr);
         else if constexpr (G & 64) go(c.vis_plane);
         else go();
         HIP_CHECK(hipGetLastError());
@@ -3060,7 +3097,14 @@ void shade_stage(pt_scene& s, const Frame& f, const WfFrame& wf, const Chunk& c,
         }
         if (c.grid_mode == 3 && c.cached && c.hit_mode) {
             // GRIDX: 11 / 15 (orthographic branch) + 16 STORE / 32 LOAD + 64 VIS (LOAD only) + 128 NEXT (LOAD and VIS only)
-            switch ((s.grids.ortho ? 15 : 11) | c.hit_mode | (c.hit_mode == 32 && c.vis_plane ? 64 : 0) | (c.hit1_fused ? 128 : 0)) {
+            // + 1024 CONT_STORE (STORE, or LOAD and VIS) / 2048 CONT_LOAD (NEXT only)
+            switch ((s.grids.ortho ? 15 : 11) | c.hit_mode | (c.hit_mode == 32 && c.vis_plane ? 64 : 0) | (c.hit1_fused ? 128 : 0) | c.cont_mode) {
+            case 27 | 1024: launch_hits(std::integral_constant<int, 27 | 1024>{}); break;
+            case 31 | 1024: launch_hits(std::integral_constant<int, 31 | 1024>{}); break;
+            case 107 | 1024: launch_hits(std::integral_constant<int, 107 | 1024>{}); break;
+            case 111 | 1024: launch_hits(std::integral_constant<int, 111 | 1024>{}); break;
+            case 235 | 2048: launch_hits(std::integral_constant<int, 235 | 2048>{}); break;
+            case 239 | 2048: launch_hits(std::integral_constant<int, 239 | 2048>{}); break;
             case 27: launch_hits(std::integral_constant<int, 27>{}); break;
             case 43: launch_hits(std::integral_constant<int, 43>{}); break;
             case 31: launch_hits(std::integral_constant<int, 31>{}); break;
@@ -3233,6 +3277,16 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
     // ... and the bounce-1 hits by the bounce-0 kernel itself, where that loads the camera hits and the visibility too
     c.hit1_fused = wf.hit1_fused && c.hit_mode == 32 && c.vis_plane != nullptr && c.hits_mode(1u) == 32;
     c.next_ctr = wf.bounce_hits[1].unknown;
+    // the continuations: loaded by the launch that reads the bounce-1 hits itself where the chunk lies below their mark too;
+    // stored by the bounce-0 launch of a chunk whose bounce-1 hits are stored in this frame - one that stores its camera hits,
+    // or loads them with the visibility - where the chunk is next above the mark and the budget has room for it
+    if (c.hit1_fused && reads(wf.cont_cache)) c.cont_mode = 2048;
+    else if (c.hits_mode(1u) == 16 && extends(wf.cont_cache) && (c.hit_mode == 16 || (c.hit_mode == 32 && c.vis_plane))) c.cont_mode = 1024;
+    if (c.cont_mode) {
+        c.cont_plane = (uint4*)wf.cont_cache->buf.p + g0;
+        c.cont_stride = (size_t)wf.cont_cache->stride;
+    }
+    if (c.cont_mode == 2048 && wf.cont_escape && f.dev.escape && s.cont_escape_generation == s.escape_generation) c.cont_flags = 1u;
     // the shadow visibility of bounces 1-4: indexed by the sample's slot in its batch's staging area, which any chunk of the
     // batch may hold - so the whole batch lies below the plane's stride, not the chunk alone
     for (uint32_t b = 1; b < WfFrame::HIT_BOUNCES; ++b) {
@@ -3334,6 +3388,16 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
                 wf.vis_cache->touched(c.st_main);
                 ++wf.vis_cache->counter[1];
             }
+        }
+        if (c.prim && c.cont_mode == 1024) {   // the records are behind this launch: the prefix grows by the chunk
+            wf.cont_cache->touched(c.st_main);
+            // (the masks this launch evaluated the escape test with: one generation for the whole prefix, or none)
+            s.cont_escape_generation = (wf.cont_cache->mark == 0 || s.cont_escape_generation == s.escape_generation) ? s.escape_generation : 0;
+            wf.cont_cache->mark = g1;
+            ++wf.cont_cache->counter[1];
+        } else if (c.prim && c.cont_mode == 2048) {   // (no device sync before the planes are zeroed for a new key: the readers count)
+            wf.cont_cache->touched(c.st_main);
+            ++wf.cont_cache->counter[2];
         }
         if (c.fused) {
             ++s.fused_launches(b);   // (by bounce: b1_fused_launches counts bounce 1's alone)
@@ -4401,6 +4465,22 @@ int pt_get_hit1_fused_stats(const pt_scene* scene, uint64_t* launches, uint64_t*
             fail(PT_ERR_INVALID, "pt_get_hit1_fused_stats: null argument");
     });
 }
+int pt_get_cont_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* resets,
+                            uint64_t* stores, uint64_t* loads, uint64_t* missing) {
+    if (!scene) return PT_ERR_INVALID;
+    return guarded([&] {
+        uint64_t n[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // (pt_scene::hit1_unknown: word 6)
+        if (scene->hit1_unknown.p) {                // (synchronises, like pt_get_hit1_cache_stats)
+            HIP_CHECK(hipSetDevice(scene->device));
+            HIP_CHECK(hipDeviceSynchronize());
+            HIP_CHECK(hipMemcpy(n, scene->hit1_unknown.p, sizeof n, hipMemcpyDeviceToHost));
+        }
+        const pt_scene::FrameCache& fc = scene->cont_cache;
+        if (cache_stats({{bytes, fc.buf.bytes}, {items, fc.items}, {items_cached, fc.mark}, {resets, fc.counter[0]}, {stores, fc.counter[1]},
+                         {loads, fc.counter[2]}, {missing, n[6]}}) != PT_OK)
+            fail(PT_ERR_INVALID, "pt_get_cont_cache_stats: null argument");
+    });
+}
 int pt_get_hit2_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* resets,
                             uint64_t* stores, uint64_t* loads, uint64_t* unknown_casts) {
     if (!scene) return PT_ERR_INVALID;
@@ -4462,7 +4542,7 @@ int pt_get_bounce_fused_stats(const pt_scene* scene, uint32_t bounce, uint64_t* 
 }
 int pt_kernel_occupancy(int device, int which, int* blocks_per_cu) {
     return guarded([&] {
-        if (!blocks_per_cu || which < 0 || which > 5) fail(PT_ERR_INVALID, "pt_kernel_occupancy: bad argument");
+        if (!blocks_per_cu || which < 0 || which > 6) fail(PT_ERR_INVALID, "pt_kernel_occupancy: bad argument");
         HIP_CHECK(hipSetDevice(device));
         if (which == 0)
             HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_wf_shade<false, false, true, 3>, WF_SHADE_THREADS, 0));
@@ -4472,6 +4552,8 @@ int pt_kernel_occupancy(int device, int which, int* blocks_per_cu) {
             HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, (WfShadeHitsKernel)k_wf_shade_hits<(11 | 32)>, WF_SHADE_THREADS, 0));
         else if (which == 4)
             HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, (WfShadeVisKernel)k_wf_shade_hits<(11 | 32 | 64)>, WF_SHADE_THREADS, 0));
+        else if (which == 6)
+            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, (WfShadeContLoadKernel)k_wf_shade_hits<(11 | 32 | 64 | 128 | 2048)>, WF_SHADE_THREADS, 0));
         else if (which == 5)
             HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, (WfShadeVisKernel)k_wf_shade_hits<(15 | 32 | 64)>, WF_SHADE_THREADS, 0));
         else

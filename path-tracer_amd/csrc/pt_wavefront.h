@@ -2052,6 +2052,9 @@ static_assert(WF_PARK_SLOTS + 1u + 4u <= 39, "four workgroups of the bounce-0 ke
 // vis_plane points at the chunk's first item there) - a light whose bits are known is not cast for.
 // + 128 * NEXT (LOAD and VIS only; the third k_wf_shade_hits below): the scene's bounce-1 hit cache (pt_gpu.hip FrameCache
 // hit1_cache; next_plane points at the chunk's first item there) - the survivors' next casts are answered here.
+// + 1024 * CONT_STORE (STORE, or LOAD and VIS, without NEXT) / + 2048 * CONT_LOAD (NEXT only; the last three k_wf_shade_hits
+// below): the scene's cache of bounce-0 continuations (pt_gpu.hip FrameCache cont_cache) - the sampled direction and the
+// throughput of the bounce-1 ray are written once per view and material table and read afterwards, not computed.
 // (S and W FIRST, in this order: the PARK variants read them again through the kernarg segment, wf_opaque_arg)
 #define WF_HIT1_FLIP 0x10000000u   // bit 28 of a record's word in the later bounces' hit caches ("The bounce-1 hit cache" below)
 template <bool ALPHA, bool COUNT, bool PRIMARY, int GRIDX>
@@ -2077,6 +2080,9 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, GRIDX ? (ALPHA ? WF_SHADE_GRID_WA
     const uint4* const next_plane = nullptr;   // (the third k_wf_shade_hits has these)
     uint4* const next_hits = nullptr;
     unsigned long long* const next_ctr = nullptr;
+    uint4* const cont_plane = nullptr;   // (the overloads with the continuation cache have these)
+    const size_t cont_stride = 0;
+    const uint32_t cont_flags = 0u;
 #include "pt_wf_shade_body.h"
 }
 
@@ -2104,6 +2110,9 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_
     const uint4* const next_plane = nullptr;   // (the third overload has these)
     uint4* const next_hits = nullptr;
     unsigned long long* const next_ctr = nullptr;
+    uint4* const cont_plane = nullptr;   // (the overloads with the continuation cache have these)
+    const size_t cont_stride = 0;
+    const uint32_t cont_flags = 0u;
 #include "pt_wf_shade_body.h"
 }
 
@@ -2139,6 +2148,9 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_
     const uint4* const next_plane = nullptr;   // (the overload below has these)
     uint4* const next_hits = nullptr;
     unsigned long long* const next_ctr = nullptr;
+    uint4* const cont_plane = nullptr;   // (the overloads with the continuation cache have these)
+    const size_t cont_stride = 0;
+    const uint32_t cont_flags = 0u;
 #include "pt_wf_shade_body.h"
 }
 
@@ -2169,6 +2181,103 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_
     static_assert(GRIDX == (11 | 32 | 64 | 128) || GRIDX == (15 | 32 | 64 | 128), "LOAD, VIS and NEXT of the cached opaque variants");
     // (S and W first: wf_opaque_arg, as above)
     static_assert(wf_leading_args<WfShadeNextKernel>::scene_then_params,
+                  "wf_opaque_arg: DevScene and WfParams must be the first two parameters of k_wf_shade_hits");
+    constexpr bool ALPHA = false, COUNT = false, PRIMARY = true;
+    const float4* const queue_in = nullptr;
+    const uint4 *const hits = nullptr, *const chunk_hits = nullptr;
+    const uint32_t *const draws = nullptr, *const index_list = nullptr, *const exact_list = nullptr;
+    DevCounters* const gctr = nullptr;
+    uint4* const cont_plane = nullptr;   // (the overloads with the continuation cache have these)
+    const size_t cont_stride = 0;
+    const uint32_t cont_flags = 0u;
+#include "pt_wf_shade_body.h"
+}
+
+// ... and with the scene's cache of bounce-0 continuations (pt_gpu.hip FrameCache cont_cache).  What the kernels above compute
+// for every hit lane behind the lights - ct_sample, with its double-precision acos, sines and cosines, and ct_eval_indirect -
+// depends on the camera hit, the material record there and words 2-3 of the item's block: not on a light.  That is the key
+// of the bounce-1 hits, and the launches of one key compute it again and again only to look its cast up in next_plane.  Two
+// planes of uint4 by item keep it: the raw bits of next_d and a state word, the raw bits of next_thr (pt_wf_shade_body.h,
+// CONT_STORE / CONT_LOAD).  next_o is not kept: three multiply-adds on values the lights need anyway.
+// Storing, GRIDX | 1024: the bounce-0 kernel of a chunk whose bounce-1 hits are stored in this frame - the first two
+// overloads above, GRIDX 11 / 15 + 16 (a fresh view: the frame also stores its camera hits) or + 32 + 64 (a view whose
+// materials were edited), with the planes as two parameters more.
+// Loading, GRIDX | 2048: the third overload above with the same two parameters more, for a chunk that also lies below the
+// continuation planes' mark.  A hit lane whose state word is zero cannot occur there; it is counted in next_ctr[6].
+// The escape test's answer (PT_CONT_ESCAPE): the storing launch records it where the scene has masks (bits 1 and 2 of the state
+// word); the loading launch uses it where cont_flags bit 0 says that the scene's masks are still those - a flag argument, set by
+// the host from the scene's mask generation - and the record has one, and runs the test itself for any other lane.
+// Overloads again, by their parameters: the kernels above keep their arguments, and their code, as they were.
+typedef void (*WfShadeContStoreKernel)(DevScene, WfParams, const uint32_t*, const uint4*, uint4*, float4*, float4*, float4*, float*, uint32_t*,
+                                       const uint32_t*, WfCounters*, uint4*, size_t);
+typedef void (*WfShadeContStoreVisKernel)(DevScene, WfParams, const uint32_t*, const uint4*, uint4*, float4*, float4*, float4*, float*,
+                                          uint32_t*, const uint32_t*, WfCounters*, uint8_t*, uint4*, size_t);
+typedef void (*WfShadeContLoadKernel)(DevScene, WfParams, const uint32_t*, const uint4*, uint4*, float4*, float4*, float4*, float*, uint32_t*,
+                                      const uint32_t*, WfCounters*, uint8_t*, const uint4*, uint4*, unsigned long long*, uint4*, size_t, uint32_t);
+template <int GRIDX>
+__global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_shade_hits(DevScene S, WfParams W,
+                                                  const uint32_t* __restrict__ tile_offsets, const uint4* rng_planes,
+                                                  uint4* __restrict__ hit_plane,
+                                                  float4* __restrict__ queue_out, float4* __restrict__ shadow_q,
+                                                  float4* __restrict__ contrib, float* __restrict__ staging,
+                                                  uint32_t* __restrict__ exact_next,
+                                                  const uint32_t* __restrict__ block_empty,
+                                                  WfCounters* __restrict__ ctr, uint4* __restrict__ cont_plane, size_t cont_stride) {
+    static_assert(GRIDX == (11 | 16 | 1024) || GRIDX == (15 | 16 | 1024), "STORE and CONT_STORE of the cached opaque variants");
+    const uint32_t cont_flags = 0u;   // (the loading variant has them)
+    // (S and W first: wf_opaque_arg, as above)
+    static_assert(wf_leading_args<WfShadeContStoreKernel>::scene_then_params,
+                  "wf_opaque_arg: DevScene and WfParams must be the first two parameters of k_wf_shade_hits");
+    constexpr bool ALPHA = false, COUNT = false, PRIMARY = true;
+    const float4* const queue_in = nullptr;
+    const uint4 *const hits = nullptr, *const chunk_hits = nullptr;
+    const uint32_t *const draws = nullptr, *const index_list = nullptr, *const exact_list = nullptr;
+    DevCounters* const gctr = nullptr;
+    uint8_t* const vis_plane = nullptr;
+    const uint4* const next_plane = nullptr;
+    uint4* const next_hits = nullptr;
+    unsigned long long* const next_ctr = nullptr;
+#include "pt_wf_shade_body.h"
+}
+template <int GRIDX>
+__global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_shade_hits(DevScene S, WfParams W,
+                                                  const uint32_t* __restrict__ tile_offsets, const uint4* rng_planes,
+                                                  uint4* __restrict__ hit_plane,
+                                                  float4* __restrict__ queue_out, float4* __restrict__ shadow_q,
+                                                  float4* __restrict__ contrib, float* __restrict__ staging,
+                                                  uint32_t* __restrict__ exact_next,
+                                                  const uint32_t* __restrict__ block_empty,
+                                                  WfCounters* __restrict__ ctr, uint8_t* __restrict__ vis_plane,
+                                                  uint4* __restrict__ cont_plane, size_t cont_stride) {
+    static_assert(GRIDX == (11 | 32 | 64 | 1024) || GRIDX == (15 | 32 | 64 | 1024), "LOAD, VIS and CONT_STORE of the cached opaque variants");
+    const uint32_t cont_flags = 0u;   // (the loading variant has them)
+    static_assert(wf_leading_args<WfShadeContStoreVisKernel>::scene_then_params,
+                  "wf_opaque_arg: DevScene and WfParams must be the first two parameters of k_wf_shade_hits");
+    constexpr bool ALPHA = false, COUNT = false, PRIMARY = true;
+    const float4* const queue_in = nullptr;
+    const uint4 *const hits = nullptr, *const chunk_hits = nullptr;
+    const uint32_t *const draws = nullptr, *const index_list = nullptr, *const exact_list = nullptr;
+    DevCounters* const gctr = nullptr;
+    const uint4* const next_plane = nullptr;
+    uint4* const next_hits = nullptr;
+    unsigned long long* const next_ctr = nullptr;
+#include "pt_wf_shade_body.h"
+}
+// (cont_plane: read only in this launch; not const, as the body's one name for it serves the storing variants too)
+template <int GRIDX>
+__global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_shade_hits(DevScene S, WfParams W,
+                                                  const uint32_t* __restrict__ tile_offsets, const uint4* rng_planes,
+                                                  uint4* __restrict__ hit_plane,
+                                                  float4* __restrict__ queue_out, float4* __restrict__ shadow_q,
+                                                  float4* __restrict__ contrib, float* __restrict__ staging,
+                                                  uint32_t* __restrict__ exact_next,
+                                                  const uint32_t* __restrict__ block_empty,
+                                                  WfCounters* __restrict__ ctr, uint8_t* __restrict__ vis_plane,
+                                                  const uint4* __restrict__ next_plane, uint4* __restrict__ next_hits,
+                                                  unsigned long long* __restrict__ next_ctr,
+                                                  uint4* __restrict__ cont_plane, size_t cont_stride, uint32_t cont_flags) {
+    static_assert(GRIDX == (11 | 32 | 64 | 128 | 2048) || GRIDX == (15 | 32 | 64 | 128 | 2048), "LOAD, VIS, NEXT and CONT_LOAD of the cached opaque variants");
+    static_assert(wf_leading_args<WfShadeContLoadKernel>::scene_then_params,
                   "wf_opaque_arg: DevScene and WfParams must be the first two parameters of k_wf_shade_hits");
     constexpr bool ALPHA = false, COUNT = false, PRIMARY = true;
     const float4* const queue_in = nullptr;
@@ -2217,6 +2326,9 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES) void k_wf_shade_f
     DevCounters* const gctr = nullptr;
     uint4* const hit_plane = nullptr;
     uint8_t* const vis_plane = const_cast<uint8_t*>(vis_bytes);   // (the body's name for it; VIS1 only reads)
+    uint4* const cont_plane = nullptr;   // (the overloads with the continuation cache have these)
+    const size_t cont_stride = 0;
+    const uint32_t cont_flags = 0u;
 #include "pt_wf_shade_body.h"
 }
 

@@ -3,7 +3,8 @@
 // of eight variants moved by 4-8 B; profiles/r09_experiments.txt item 0), and those variants are tuned to the byte.
 // In scope: the template parameters ALPHA, COUNT, PRIMARY, GRIDX (as constants in k_wf_shade_hits) and the kernel's
 // parameters - S, W, tile_offsets, queue_in, hits, rng_planes, draws, queue_out, shadow_q, contrib, staging, index_list,
-// exact_list, chunk_hits, exact_next, block_empty, ctr, gctr - and hit_plane, vis_plane, next_plane, next_hits, next_ctr.
+// exact_list, chunk_hits, exact_next, block_empty, ctr, gctr - and hit_plane, vis_plane, next_plane, next_hits, next_ctr,
+// cont_plane, cont_stride, cont_flags.
     // index_list (bounces >= 1): null - the whole queue, entries marked WF_HIT_PENDING left out; else the entries to shade:
     // the hand-over list of k_wf_trace, whose casts k_wf_trace_wide has finished by now - `hits` is then that list's
     // own plane (W.list_cap records, by list position).  The pass over the queue runs WHILE k_wf_trace_wide walks
@@ -34,6 +35,16 @@
     constexpr bool VIS1 = (GRIDX & 256) != 0, NEXT1 = (GRIDX & 512) != 0;
     static_assert(!VIS1 || ((GRIDX & 255) == 0 && !ALPHA && !COUNT && !PRIMARY), "the bounce-1 visibility is read by the plain opaque later-bounce pass");
     static_assert(!NEXT1 || VIS1, "the bounce-2 hits are consumed by the launch that adds the lights itself");
+    // CONT_STORE, CONT_LOAD (k_wf_shade_hits: the scene's cache of bounce-0 continuations, pt_gpu.hip FrameCache cont_cache;
+    // cont_plane points at the chunk's first item of plane 0, plane 1 lies cont_stride records behind it).  Plane 0: the raw
+    // bits of next_d and a state word (0: never written - the planes are zeroed when they are keyed; bit 0: written; bit 1:
+    // escape_proves_miss was evaluated for the item with the masks that existed then; bit 2: its answer), plane 1: the raw bits of next_thr.  CONT_STORE: every hit lane writes
+    // its two records behind ct_eval_indirect.  CONT_LOAD: the records are read at the top of the step, beside cam_rec, vis
+    // and next_rec, and the launch contains no ct_sample, no ct_eval_indirect and no use of words 2 and 3.
+    constexpr bool CONT_STORE = (GRIDX & 1024) != 0, CONT_LOAD = (GRIDX & 2048) != 0;
+    static_assert(!CONT_STORE || ((STORE || (LOAD && VIS)) && !NEXT), "the continuation is stored by the launch that runs while the bounce-1 hits are stored");
+    static_assert(!CONT_LOAD || NEXT, "the continuation is loaded by the launches that read the bounce-1 hits themselves");
+    static_assert(!(CONT_STORE && CONT_LOAD), "a launch stores the continuation or loads it");
     uint4* rng_planes_out = const_cast<uint4*>(rng_planes);   // GRID == 3 writes plane 1 (nobody reads it before bounce 1)
     static_assert(GRID < 2 || PRIMARY, "the camera grid serves bounce 0");
     const bool list_pass = !PRIMARY && index_list != nullptr;
@@ -137,6 +148,13 @@
         if (live) next_rec.x = ((const uint32_t*)next_plane)[4u * (size_t)i];
     } else if constexpr (NEXT) {
         if (live) next_rec = next_plane[i];
+    }
+    // (CONT_LOAD) the item's continuation, as dense and as independent: read for every item, used by the hit lanes.  (For the
+    // lanes whose camera record is a hit only, and with nontemporal loads: 0.04 and 0.09 ms of a 12.2 ms frame, inside the
+    // spread of the runs, the second at 8 B of scratch - profiles/r19_experiments.txt item 3.)
+    uint4 cont_d = make_uint4(0u, 0u, 0u, 0u), cont_thr = make_uint4(0u, 0u, 0u, 0u);
+    if constexpr (CONT_LOAD) {
+        if (live) cont_d = cont_plane[i], cont_thr = cont_plane[cont_stride + i];
     }
     if (PRIMARY && live) {  // entry i is work item i: the initial path state, built in place
         ItemRef it = decode_item(W.P, tile_offsets, W.item_base + i);
@@ -308,6 +326,15 @@
                             if (NEXT) next_rec = make_uint4(unpark_u(PK_NEXT), unpark_u(PK_NEXT + 1u), unpark_u(PK_NEXT + 2u), unpark_u(PK_NEXT + 3u));
                             unpark_fixed();
                         }
+                        if constexpr (CONT_LOAD) {
+                            // the continuation across the cast: six slots more would cost the fourth workgroup per CU, and the
+                            // planes are read-only in this launch - the lanes that cast read their records again
+                            // (volatile: a plain load is merged with the one at the top of the step, and the records held)
+                            const volatile uint32_t* again = (const volatile uint32_t*)(cont_plane + i);
+                            cont_d = make_uint4(again[0], again[1], again[2], again[3]);
+                            again = (const volatile uint32_t*)(cont_plane + cont_stride + i);
+                            cont_thr.x = again[0], cont_thr.y = again[1], cont_thr.z = again[2];
+                        }
                         vis |= ((blocked ? 2u : 1u) << (2u * li)) | 0x100u;
                     }
                     f3 rad = og_light_unshadowed<DIRL>(S, li, surf.pos);
@@ -349,7 +376,21 @@
             if (vis & 0x100u) vis_plane[i] = (uint8_t)vis;
         }
         bool ended = false;
-        if (bounce < bounces) {
+        uint32_t esc_state = 0u;   // (CONT_STORE) bits 1 and 2 of the record's state word
+        if constexpr (CONT_LOAD) {
+            if (bounce < bounces) {   // what the storing launch computed here, bit for bit
+                next_o = surf.pos + surf.normal * 0.00001f;
+                draw += 2u;
+                next_d = mk3(__uint_as_float(cont_d.x), __uint_as_float(cont_d.y), __uint_as_float(cont_d.z));
+                next_thr = mk3(__uint_as_float(cont_thr.x), __uint_as_float(cont_thr.y), __uint_as_float(cont_thr.z));
+                // a hit lane without a record cannot occur below the mark: counted (next_ctr[6]; its zero throughput ends the path)
+                const bool missing = (cont_d.w & 1u) == 0u;
+                if (wf_any(missing)) {
+                    const unsigned long long m = __ballot(missing);
+                    if (missing && wf_lane_rank(m) == 0u) atomicAdd(next_ctr + 6, (unsigned long long)__popcll(m));
+                }
+            }
+        } else if (bounce < bounces) {
             next_o = surf.pos + surf.normal * 0.00001f;
             float r1, r2;
             if (GRID == 3 && ALPHA) {
@@ -371,6 +412,14 @@
             next_d = ct_sample(brdf, normal, view, r1, r2);
             f3 wgt = ct_eval_indirect(brdf, normal, view, next_d) / 1.0f;
             next_thr = mul_ew(thr, wgt);
+            if constexpr (CONT_STORE) {
+                // the escape test's answer for the lanes that will ask for it (not ended, a triangle, masks there): bit 1 - it
+                // was evaluated, with the masks that exist now -, bit 2 - the answer; the test below reads it from here
+                if (!(dot3(next_thr, next_thr) < 0.00001f) && S.escape != nullptr && !surf.sphere)
+                    esc_state = 2u | (escape_proves_miss(S, PT_PRIM_INDEX(h.pid), next_o, next_d) ? 4u : 0u);
+                cont_plane[i] = make_uint4(__float_as_uint(next_d.x), __float_as_uint(next_d.y), __float_as_uint(next_d.z), 1u | esc_state);
+                cont_plane[cont_stride + i] = make_uint4(__float_as_uint(next_thr.x), __float_as_uint(next_thr.y), __float_as_uint(next_thr.z), 0u);
+            }
         }
         if (dot3(next_thr, next_thr) < 0.00001f) ended = true;
         if (!ended && bounce > 3) {
@@ -383,6 +432,33 @@
         // that the path ends with `colour + throughput x background` (mod.rs:184-186) - no record, no cast.  The background
         // term must be added AFTER this bounce's lights (mod.rs:248-262 come first): here if the lights are added here
         // (inline) or none can contribute; through the shadow queue only if the term is exactly zero (a black background).
+        if constexpr (CONT_LOAD || CONT_STORE) {
+            // The same with the answer from the record (the statement below is kept as it is for every other kernel: written
+            // as one, the two forms changed the code of 57 of them).  CONT_STORE: evaluated above, where it was recorded.
+            // CONT_LOAD: the recorded answer where the launch was told that the scene's masks are those the records were made
+            // with - cont_flags bit 0 - and the record has one; any other lane runs the test itself, behind a branch that a
+            // wavefront with no such lane skips.
+            bool proven = false;
+            if (survive && S.escape != nullptr && !surf.sphere) {
+                if constexpr (CONT_STORE) {
+                    proven = (esc_state & 4u) != 0u;
+                } else {
+                    const bool known = (cont_flags & 1u) != 0u && (cont_d.w & 2u) != 0u;
+                    proven = known && (cont_d.w & 4u) != 0u;
+                    if (wf_any(!known)) {
+                        if (!known) proven = escape_proves_miss(S, PT_PRIM_INDEX(h.pid), next_o, next_d);
+                    }
+                }
+            }
+            if (proven) {
+                const f3 bg = mul_ew(next_thr, ld3(S.background));
+                const bool zero = bg.x == 0.f && bg.y == 0.f && bg.z == 0.f;
+                if (zero || !to_shadow) {
+                    if (!zero) color = color + bg;
+                    survive = false;
+                }
+            }
+        } else
         if (survive && S.escape != nullptr && !surf.sphere && escape_proves_miss(S, PT_PRIM_INDEX(h.pid), next_o, next_d)) {
             const f3 bg = mul_ew(next_thr, ld3(S.background));
             const bool zero = bg.x == 0.f && bg.y == 0.f && bg.z == 0.f;

@@ -56,6 +56,8 @@ has_hit2 = hasattr(g.lib, "pt_get_hit2_cache_stats")
 hit2 = lambda: dict(zip(("bytes", "items", "cached", "resets", "stores", "loads", "unknown_casts"), g.hit2_cache_stats())) if has_hit2 else None
 has_vis1 = hasattr(g.lib, "pt_get_vis1_cache_stats")
 vis1 = lambda: dict(zip(("bytes", "items", "resets", "launches"), g.vis1_cache_stats())) if has_vis1 else None
+has_cont = hasattr(g.lib, "pt_get_cont_cache_stats")
+cont = lambda: dict(zip(("bytes", "items", "cached", "resets", "stores", "loads", "missing"), g.cont_cache_stats())) if has_cont else None
 first = [frame() for _ in range(5)]   # (the first frame, the filling and storing frame, escape masks, the plan, a steady one)
 after_first = stats()
 steady = [frame() for _ in range(a.steady)]
@@ -74,5 +76,5 @@ print(json.dumps({"image": f"{a.width}x{a.height}", "spp": a.spp, "bounces": a.b
                   "steady_frame_ms_median": round(statistics.median(steady), 2),
                   "frame_after_light_move_ms": [round(v, 2) for v in moved],
                   "frame_after_light_move_ms_median": round(statistics.median(moved), 2), "hit_cache": stats(),
-                  "hit1_cache": hit1(), "hit2_cache": hit2(), "vis1_cache": vis1()}))
+                  "hit1_cache": hit1(), "hit2_cache": hit2(), "vis1_cache": vis1(), "cont_cache": cont()}))
 g.close()

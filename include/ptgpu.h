@@ -429,6 +429,67 @@ int pt_denoise_var_stage_times(int device, uint32_t width, uint32_t height, uint
                                void* d_out_rgb8, void* d_scratch, float* ms);
 
 /* ------------------------------------------------------------------ */
+/* light mixer (no reference counterpart)                   */
+/* ------------------------------------------------------------------ */
+
+/* A frame is linear in every light's colour: lights are not sampled stochastically, Russian roulette and the throughput
+ * cut-off look at the BRDF throughput only, and the tone map comes after the accumulation.  So, per channel,
+ *     accum(colours) = E + sum_l colour_l * T_l
+ * with E the frame with every light black and T_l the transport of light l at unit colour.  A pt_lightmix holds these
+ * n_lights + 1 planes for ONE (view, geometry, materials, light kinds / positions, profile, opts); every colour, intensity,
+ * mute or solo edit of that view is then one streaming kernel instead of a render.
+ *
+ * pt_lightmix_capture renders the n_lights + 1 accumulators of (profile, opts) with the scene's own frames (any flags, any
+ * sharding; the planes are in the packed local order of pt_render; the progress and preview callbacks are not invoked):
+ *   plane 0      E: every light's colour (0,0,0), kind, position and size kept
+ *   unit[l]      m_l = the largest channel of light l's current colour, or 1.0f if that is 0
+ *   plane 1 + l  D_l = F_l - E, one f32 subtraction per float; F_l = the frame with light l at (m_l, m_l, m_l), the others black
+ * (the basis is taken at the light's own magnitude: a unit-white basis of a light of colour 1000 would amplify E's rounding
+ * by that factor).  During the call the scene's lights change COLOUR only - the state change of pt_scene_set_lights (the
+ * device is synchronised, no frame plan carries over) without its grid rebuild, and the position-keyed visibility planes are
+ * kept; the caller must not use the scene from another thread meanwhile.  Afterwards - and after any failure, in which case
+ * no object is returned - the scene has its original lights and renders the bits it rendered before.  More than
+ * PT_LIGHTMIX_MAX_LIGHTS lights: PT_ERR_UNSUPPORTED; a null pointer, samples == 0, a rank without pixels or a light colour
+ * that is not finite: PT_ERR_INVALID; both before any device work.
+ * The object owns its planes (device memory on the scene's device) and outlives the scene.  It does not watch the scene: after
+ * any edit other than light colours the caller captures again.
+ *
+ * pt_lightmix_create_from_planes makes the object from host planes ((n_lights + 1) x n_local x 3 f32, plane 0 = E, then D_l)
+ * and units (finite, not 0) - for tests and for planes kept on disk.  device: HIP ordinal, -1 = current.
+ *
+ * pt_lightmix_apply: all f32, one IEEE operation per step in the order written, uncontracted (tests/lightmix_model.py
+ * restates it bit for bit):
+ *   host       f[l][ch] = colors[l][ch] / unit[l]
+ *   per float k of a plane, ch = k mod 3:   a = E[k];  for l = 0 .. n_lights-1 in order:  a = a + f[l][ch] * D_l[k]
+ *   accum[k] = a          (n_local x 3 f32: what pt_render's accum is for the edited lights, within rounding)
+ *   rgb8[k]  = as_u8(pow(tonemap(a / (float)samples), 1/2.2) * 255), pt_render's post-processing of a
+ * With 0 lights a = E[k].  A null object, null colors (with n_lights > 0), a colors entry that is not finite, an unknown tone
+ * map, or rgb8 and accum both null: PT_ERR_INVALID before any device work.  The host form blocks; the device form is
+ * asynchronous on hip_stream, allocates nothing, and wants d_rgb8 4-byte and d_accum 16-byte aligned (PT_ERR_INVALID otherwise);
+ * colors is a HOST pointer in both (the factors travel in the kernel arguments).
+ * pt_lightmix_basis copies plane `plane` (0 .. n_lights) to the host. */
+enum { PT_LIGHTMIX_MAX_LIGHTS = 16 };
+typedef struct pt_lightmix pt_lightmix;
+typedef struct pt_lightmix_info {
+    uint32_t n_lights, samples;
+    uint64_t n_local;                       /* pixels, packed local order of (profile, opts) */
+    uint64_t device_bytes;
+    float unit[PT_LIGHTMIX_MAX_LIGHTS];     /* m_l */
+} pt_lightmix_info;
+
+int  pt_lightmix_capture(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, pt_lightmix** out);
+int  pt_lightmix_create_from_planes(int device, uint32_t n_lights, uint32_t samples, uint64_t n_local,
+                                    const float* unit, const float* planes /* host, (n_lights+1) x n_local x 3 */,
+                                    pt_lightmix** out);
+void pt_lightmix_destroy(pt_lightmix* mix);
+int  pt_lightmix_get_info(const pt_lightmix* mix, pt_lightmix_info* info);
+int  pt_lightmix_basis(const pt_lightmix* mix, uint32_t plane, float* host /* n_local x 3 */);
+int  pt_lightmix_apply(const pt_lightmix* mix, const float* colors /* host, n_lights x 3 */, int tonemap,
+                       uint8_t* rgb8, float* accum);                       /* host, either may be NULL */
+int  pt_lightmix_apply_device(const pt_lightmix* mix, const float* colors /* host */, int tonemap,
+                              void* d_rgb8, void* d_accum, void* hip_stream);   /* asynchronous, allocates nothing */
+
+/* ------------------------------------------------------------------ */
 /* measurement                                                         */
 /* ------------------------------------------------------------------ */
 

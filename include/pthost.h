@@ -84,6 +84,10 @@ void pth_keyframes_free(pth_keyframe* frames);
 /* Apply one frame to a host scene: camera, lights, materials, in that order.  A material index out of range is
  * PT_ERR_INVALID and changes nothing. */
 int pth_keyframe_apply(pth_scene* s, const pth_keyframe* frame);
+/* 1 when two light tables are equal in count and, light by light, in kind, vec and size BIT FOR BIT (-0.0 differs from 0.0, a
+ * NaN equals itself) - they differ in colour at most, which is what a pt_lightmix capture survives (`render --light-mixer`) -
+ * else 0.  Two empty tables are equal; a null table with a count > 0 equals nothing. */
+int pth_lights_differ_in_color_only(const pt_light* a, uint32_t n_a, const pt_light* b, uint32_t n_b);
 
 /* Deterministic synthetic stand-in for the (unpublished) PS5 scene
  * (SURVEY §8-d): ground quad + two tessellated curved shells + an emissive

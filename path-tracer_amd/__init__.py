@@ -135,6 +135,14 @@ class DenoiseParams(C.Structure):
         return p
 
 
+PT_LIGHTMIX_MAX_LIGHTS = 16
+
+
+class LightMixInfo(C.Structure):
+    _fields_ = [("n_lights", C.c_uint32), ("samples", C.c_uint32), ("n_local", C.c_uint64), ("device_bytes", C.c_uint64),
+                ("unit", C.c_float * PT_LIGHTMIX_MAX_LIGHTS)]
+
+
 class Hit(C.Structure):
     _fields_ = [("prim", C.c_int32), ("flags", C.c_int32), ("dist", C.c_float), ("u", C.c_float),
                 ("v", C.c_float)]
@@ -221,7 +229,8 @@ HOST_SYMBOLS = ["pth_scene_load_isf", "pth_scene_free", "pth_scene_desc", "pth_s
                 "pth_png_decode", "pth_png_write_rgb8", "pth_free", "pth_prim_count", "pth_kd_build",
                 "pth_kd_free", "pth_origin_grid_build", "pth_ortho_grid_build", "pth_origin_grid_auto_resolution", "pth_origin_grid_free",
                 "pth_last_error", "pth_scene_set_camera", "pth_camera_path_load", "pth_camera_path_free",
-                "pth_scene_set_lights", "pth_scene_set_materials", "pth_keyframes_load", "pth_keyframes_free", "pth_keyframe_apply"]
+                "pth_scene_set_lights", "pth_scene_set_materials", "pth_keyframes_load", "pth_keyframes_free", "pth_keyframe_apply",
+                "pth_lights_differ_in_color_only"]
 # Every symbol include/ptgpu.h declares.
 GPU_SYMBOLS = ["pt_scene_create", "pt_scene_destroy", "pt_scene_set_camera", "pt_scene_set_lights", "pt_scene_set_materials", "pt_prep_create", "pt_prep_destroy", "pt_scene_create_from_prep",
                "pt_comm_unique_id", "pt_comm_create", "pt_comm_create_all", "pt_comm_destroy", "pt_gather_tiles", "pt_render_gathered", "pt_local_pixel_count", "pt_local_pixel_map",
@@ -233,7 +242,9 @@ GPU_SYMBOLS = ["pt_scene_create", "pt_scene_destroy", "pt_scene_set_camera", "pt
                "pt_denoise", "pt_denoise_device", "pt_render_denoised", "pt_denoise_stage_times",
                "pt_render_moments", "pt_render_moments_device", "pt_render_samples", "pt_denoise_var_params_default",
                "pt_denoise_var_scratch_bytes", "pt_denoise_var", "pt_denoise_var_device", "pt_render_denoised_var",
-               "pt_denoise_var_stage_times"]
+               "pt_denoise_var_stage_times",
+               "pt_lightmix_capture", "pt_lightmix_create_from_planes", "pt_lightmix_destroy", "pt_lightmix_get_info",
+               "pt_lightmix_basis", "pt_lightmix_apply", "pt_lightmix_apply_device"]
 
 
 def host_lib():
@@ -282,6 +293,7 @@ def host_lib():
         L.pth_keyframes_free.argtypes = [C.POINTER(Keyframe)]
         L.pth_keyframes_free.restype = None
         L.pth_keyframe_apply.argtypes = [C.c_void_p, C.POINTER(Keyframe)]
+        L.pth_lights_differ_in_color_only.argtypes = [C.POINTER(Light), C.c_uint32, C.POINTER(Light), C.c_uint32]
         _host = L
     return _host
 
@@ -383,6 +395,15 @@ def gpu_lib():
         L.pt_denoise_var_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, dp, vp, vp, vp, vp, vp, vp, vp]
         L.pt_render_denoised_var.argtypes = [vp, C.POINTER(Profile), C.POINTER(Opts), dp, vp, vp]
         L.pt_denoise_var_stage_times.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, dp, vp, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "pt_lightmix_capture"):   # (an A/B library of an earlier commit has no light mixer)
+            L.pt_lightmix_capture.argtypes = [vp, C.POINTER(Profile), C.POINTER(Opts), C.POINTER(vp)]
+            L.pt_lightmix_create_from_planes.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, vp, vp, C.POINTER(vp)]
+            L.pt_lightmix_destroy.argtypes = [vp]
+            L.pt_lightmix_destroy.restype = None
+            L.pt_lightmix_get_info.argtypes = [vp, C.POINTER(LightMixInfo)]
+            L.pt_lightmix_basis.argtypes = [vp, C.c_uint32, vp]
+            L.pt_lightmix_apply.argtypes = [vp, vp, C.c_int, vp, vp]
+            L.pt_lightmix_apply_device.argtypes = [vp, vp, C.c_int, vp, vp, vp]
         L.pt_last_error.restype = C.c_char_p
         L.pt_version.restype = C.c_char_p
         _gpu = L
@@ -876,6 +897,13 @@ class GpuScene:
                                                   C.byref(params) if params is not None else None, rgb.ctypes.data, col.ctypes.data))
         return rgb, col
 
+    def lightmix_capture(self, profile, opts=None):
+        """pt_lightmix_capture: the light-mixer planes of this scene's view for (profile, opts), as a LightMix."""
+        handle = C.c_void_p()
+        check_gpu(self.lib.pt_lightmix_capture(self.handle, C.byref(profile), C.byref(opts) if opts is not None else None,
+                                               C.byref(handle)))
+        return LightMix(handle)
+
     def timing(self):
         t = Timing()
         check_gpu(self.lib.pt_get_timing(self.handle, C.byref(t)))
@@ -1033,6 +1061,75 @@ try:
     HIT_DTYPE = _np.dtype([("prim", "<i4"), ("flags", "<i4"), ("dist", "<f4"), ("u", "<f4"), ("v", "<f4")])
 except Exception:  # pragma: no cover
     HIT_DTYPE = None
+
+
+class LightMix:
+    """The planes of one captured view (pt_lightmix): E and one difference plane per light.  Owns device memory; outlives the
+    scene it was captured from."""
+
+    def __init__(self, handle):
+        self.lib = gpu_lib()
+        self.handle = handle
+
+    @classmethod
+    def from_planes(cls, planes, unit, samples, device=0):
+        """pt_lightmix_create_from_planes: planes [n_lights + 1, n_local, 3] float32 (E, then D_l), unit [n_lights]."""
+        import numpy as np
+        planes = np.ascontiguousarray(planes, np.float32)
+        unit = np.ascontiguousarray(unit, np.float32).reshape(-1)
+        if planes.ndim != 3 or planes.shape[2] != 3 or planes.shape[0] != len(unit) + 1:
+            raise PtError(PT_ERR_INVALID, "LightMix.from_planes: planes must be [n_lights + 1, n_local, 3] for n_lights units")
+        handle = C.c_void_p()
+        check_gpu(gpu_lib().pt_lightmix_create_from_planes(device, len(unit), samples, planes.shape[1], unit.ctypes.data,
+                                                           planes.ctypes.data, C.byref(handle)))
+        return cls(handle)
+
+    @property
+    def info(self):
+        i = LightMixInfo()
+        check_gpu(self.lib.pt_lightmix_get_info(self.handle, C.byref(i)))
+        return i
+
+    def basis(self, i):
+        """Plane i (0: E, 1 + l: D_l) as [n_local, 3] float32."""
+        import numpy as np
+        out = np.empty((self.info.n_local, 3), np.float32)
+        check_gpu(self.lib.pt_lightmix_basis(self.handle, i, out.ctypes.data))
+        return out
+
+    @staticmethod
+    def _colors(colors):
+        import numpy as np
+        return np.ascontiguousarray(colors, np.float32).reshape(-1, 3)
+
+    def apply(self, colors, tonemap=None, want_accum=False):
+        """pt_lightmix_apply: rgb8 [n_local, 3] uint8 of the view with light colours `colors` [n_lights, 3] (tonemap: a name or
+        number, default FILMIC); with want_accum (rgb8, accum [n_local, 3] float32)."""
+        import numpy as np
+        c = self._colors(colors)
+        tm = TONEMAPS["FILMIC"] if tonemap is None else TONEMAPS.get(tonemap, tonemap)
+        n = self.info.n_local
+        rgb = np.empty((n, 3), np.uint8)
+        acc = np.empty((n, 3), np.float32) if want_accum else None
+        check_gpu(self.lib.pt_lightmix_apply(self.handle, c.ctypes.data, tm, rgb.ctypes.data, acc.ctypes.data if want_accum else None))
+        return (rgb, acc) if want_accum else rgb
+
+    def apply_device(self, colors, tonemap, d_rgb8, d_accum, stream=0):
+        """pt_lightmix_apply_device: device pointers (either may be 0 / None), asynchronous on `stream`."""
+        c = self._colors(colors)
+        tm = TONEMAPS["FILMIC"] if tonemap is None else TONEMAPS.get(tonemap, tonemap)
+        check_gpu(self.lib.pt_lightmix_apply_device(self.handle, c.ctypes.data, tm, d_rgb8 or None, d_accum or None, stream))
+
+    def close(self):
+        if self.handle:
+            self.lib.pt_lightmix_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def denoise(width, height, samples, params, accum, guides, device=0):

@@ -45,6 +45,7 @@
 #include "pt_grid_build.h"
 #include "pt_denoise.h"
 #include "pt_variance.h"
+#include "pt_lightmix.h"
 #include "pthost.h"
 #include "../host/scene_check.h"
 
@@ -1968,6 +1969,23 @@ void scene_set_lights(pt_scene& s, const pt_light* lights, uint32_t n) {
     drop_frame_state(s);
 }
 
+// The colour-only form of scene_set_lights, for pt_lightmix_capture: dl is the scene's light table with other colours - the
+// same count, kinds and vectors.  Grids, camera-grid resolution and the visibility planes depend on those alone (grid_rule,
+// light_grid; the planes' key is made of kind and vector, frame_caches), so only the DevLight table is replaced; everything
+// else is scene_set_lights' state change: the device is synchronised first and no frame plan carries over.
+void scene_set_light_colors(pt_scene& s, const std::vector<DevLight>& dl) {
+    HIP_CHECK(hipSetDevice(s.device));
+    HIP_CHECK(hipDeviceSynchronize());
+    AllocMark mark(s);
+    const DevLight* d_lights = s.upload(dl.data(), dl.size());
+    mark.release();
+    s.release(s.dev.lights);
+    s.info.device_bytes -= std::max<uint64_t>(16, (uint64_t)s.dev.n_lights * sizeof(DevLight));
+    s.dev.lights = d_lights;
+    s.host_lights = dl;
+    drop_frame_state(s);
+}
+
 // pt_scene_set_materials: the model -> material indices of the description resolve the new table into the per-model copies
 // the device reads, in a new buffer; has_translucent selects the ALPHA kernel variants.  Nothing else depends on materials.
 void scene_set_materials(pt_scene& s, const pt_material* materials, uint32_t n) {
@@ -3763,6 +3781,119 @@ void guides_launch(const pt_scene& s, uint32_t width, uint32_t height, float4* d
 
 }  // namespace
 
+// ------------------------------------------------------------------ light mixer (pt_lightmix.h)
+// The planes of one captured view: plane 0 = E, plane 1 + l = D_l, `stride` floats apart on the device.  cudaMalloc-style
+// allocations are 256-byte aligned and the stride is a multiple of 64 floats, so every plane starts on a 256-byte boundary.
+struct pt_lightmix {
+    int device = 0;
+    uint32_t n_lights = 0, samples = 0;
+    uint64_t n_local = 0, stride = 0, bytes = 0;
+    float* planes = nullptr;
+    float unit[PT_LIGHTMIX_MAX_LIGHTS] = {};
+    ~pt_lightmix() {
+        if (planes) (void)hipFree(planes);
+    }
+    float* plane(uint32_t i) const { return planes + (uint64_t)i * stride; }
+};
+
+namespace {
+
+std::unique_ptr<pt_lightmix> lightmix_alloc(int device, uint32_t n_lights, uint32_t samples, uint64_t n_local) {
+    auto m = std::make_unique<pt_lightmix>();
+    m->device = device;
+    m->n_lights = n_lights;
+    m->samples = samples;
+    m->n_local = n_local;
+    m->stride = (3u * n_local + 63u) & ~(uint64_t)63u;
+    m->bytes = (uint64_t)(n_lights + 1u) * m->stride * sizeof(float);
+    HIP_CHECK(hipMalloc((void**)&m->planes, m->bytes));
+    HIP_CHECK(hipMemset(m->planes, 0, m->bytes));   // (the padding behind every plane stays zero)
+    return m;
+}
+
+uint32_t lightmix_blocks(uint64_t n4) { return (uint32_t)std::min<uint64_t>((n4 + 255u) / 256u, LM_MAX_BLOCKS); }
+
+// Everything pt_lightmix_apply / _device can refuse, before any device work; the factors f[l][ch] = colors[l][ch] / unit[l].
+LmFactors lightmix_factors(const char* who, const pt_lightmix* m, const float* colors, int tonemap_type, const void* rgb8,
+                           const void* accum) {
+    if (!m || (!colors && m->n_lights) || (!rgb8 && !accum)) fail(PT_ERR_INVALID, "%s: null argument", who);
+    if (tonemap_type < PT_TONEMAP_REINHARD || tonemap_type > PT_TONEMAP_ACES) fail(PT_ERR_INVALID, "%s: unknown tonemap %d", who, tonemap_type);
+    LmFactors F{};
+    for (uint32_t l = 0; l < m->n_lights; ++l)
+        for (int ch = 0; ch < 3; ++ch) {
+            if (!std::isfinite(colors[3 * l + ch])) fail(PT_ERR_INVALID, "%s: colour %d of light %u is not finite", who, ch, l);
+            F.f[l][ch] = colors[3 * l + ch] / m->unit[l];
+        }
+    return F;
+}
+
+void lightmix_launch(const pt_lightmix& m, const LmFactors& F, int tonemap_type, uint8_t* d_rgb8, float* d_accum, hipStream_t stream) {
+    const uint64_t n_floats = 3u * m.n_local, n4 = (n_floats + 3u) / 4u;
+    hipLaunchKernelGGL(k_lightmix_apply, dim3(lightmix_blocks(n4)), dim3(256), 0, stream, (const float*)m.planes, m.stride, m.n_lights,
+                       F, n_floats, m.samples, tonemap_type, d_accum, d_rgb8);
+    HIP_CHECK(hipGetLastError());
+}
+
+// pt_lightmix_capture.  The scene's lights change colour n_lights + 1 times and get their own colours back on every way
+// out (scene_set_light_colors: positions, grids and visibility planes are never touched).
+std::unique_ptr<pt_lightmix> lightmix_capture(pt_scene& s, const pt_profile& p, const pt_opts* opts_in) {
+    pt_opts o;
+    normalise_opts(p, opts_in, o);
+    o.progress = nullptr;
+    o.preview = nullptr;
+    if (p.samples == 0) fail(PT_ERR_INVALID, "pt_lightmix_capture: profile.samples must be > 0");
+    const std::vector<DevLight> own = s.host_lights;
+    const uint32_t n = (uint32_t)own.size();
+    if (n > (uint32_t)PT_LIGHTMIX_MAX_LIGHTS) fail(PT_ERR_UNSUPPORTED, "pt_lightmix_capture: %u lights, at most %d", n, (int)PT_LIGHTMIX_MAX_LIGHTS);
+    const uint64_t n_local = make_tile_map(p, o, o.shard_rank).n_local;
+    if (n_local == 0) fail(PT_ERR_INVALID, "pt_lightmix_capture: this rank has no pixels");
+    float unit[PT_LIGHTMIX_MAX_LIGHTS] = {};
+    for (uint32_t l = 0; l < n; ++l) {
+        const float* c = own[l].color;
+        float m = c[0];
+        if (c[1] > m) m = c[1];
+        if (c[2] > m) m = c[2];
+        if (m == 0.f) m = 1.0f;
+        if (!std::isfinite(m)) fail(PT_ERR_INVALID, "pt_lightmix_capture: the colour of light %u is not finite", l);
+        unit[l] = m;
+    }
+    HIP_CHECK(hipSetDevice(s.device));
+    auto m = lightmix_alloc(s.device, n, p.samples, n_local);
+    memcpy(m->unit, unit, sizeof unit);
+    struct Restore {   // the scene's own lights, also when a frame fails (a failing restore cannot be reported twice)
+        pt_scene& s;
+        const std::vector<DevLight>& own;
+        bool armed = true;
+        ~Restore() {
+            if (!armed) return;
+            try {
+                scene_set_light_colors(s, own);
+            } catch (const GpuError&) {
+            }
+        }
+    } restore{s, own};
+    for (uint32_t plane = 0; plane <= n; ++plane) {
+        std::vector<DevLight> dl = own;
+        for (uint32_t l = 0; l < n; ++l) {
+            const float v = (plane == l + 1u) ? unit[l] : 0.f;
+            dl[l].color[0] = dl[l].color[1] = dl[l].color[2] = v;
+            dl[l].tame = fabsf(v) < 1e30f ? 1u : 0u;   // (dev_light)
+        }
+        scene_set_light_colors(s, dl);
+        render_device(s, p, &o, nullptr, m->plane(plane), nullptr);
+    }
+    const uint64_t n4 = m->stride / 4u;
+    for (uint32_t l = 0; l < n; ++l)
+        hipLaunchKernelGGL(k_lightmix_diff, dim3(lightmix_blocks(n4)), dim3(256), 0, 0, (float4*)m->plane(l + 1u), (const float4*)m->plane(0), n4);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    restore.armed = false;
+    scene_set_light_colors(s, own);   // (on this way out a failure is reported: no object then)
+    return m;
+}
+
+}  // namespace
+
 // ==================================================================== C ABI
 extern "C" {
 
@@ -4027,6 +4158,80 @@ int pt_render_denoised(const pt_scene* scene, const pt_profile* profile, const p
         HIP_CHECK(hipDeviceSynchronize());
         if (rgb8) d_rgb.fetch(rgb8, n * 3);
         if (color) d_color.fetch(color, n * 3);
+    });
+}
+
+int pt_lightmix_capture(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, pt_lightmix** out) {
+    return guarded([&] {
+        if (!scene || !profile || !out) fail(PT_ERR_INVALID, "pt_lightmix_capture: null argument");
+        *out = lightmix_capture(render_state(scene), *profile, opts).release();
+    });
+}
+
+int pt_lightmix_create_from_planes(int device, uint32_t n_lights, uint32_t samples, uint64_t n_local, const float* unit,
+                                   const float* planes, pt_lightmix** out) {
+    return guarded([&] {
+        if (!planes || !out || (!unit && n_lights)) fail(PT_ERR_INVALID, "pt_lightmix_create_from_planes: null argument");
+        if (n_lights > (uint32_t)PT_LIGHTMIX_MAX_LIGHTS)
+            fail(PT_ERR_UNSUPPORTED, "pt_lightmix_create_from_planes: %u lights, at most %d", n_lights, (int)PT_LIGHTMIX_MAX_LIGHTS);
+        if (!samples) fail(PT_ERR_INVALID, "pt_lightmix_create_from_planes: samples is 0");
+        if (!n_local || n_local >= (1ull << 31)) fail(PT_ERR_INVALID, "pt_lightmix_create_from_planes: n_local must be in 1 .. 2^31 - 1");
+        for (uint32_t l = 0; l < n_lights; ++l)
+            if (!std::isfinite(unit[l]) || unit[l] == 0.f) fail(PT_ERR_INVALID, "pt_lightmix_create_from_planes: unit %u must be finite and not 0", l);
+        if (device >= 0) HIP_CHECK(hipSetDevice(device));
+        else HIP_CHECK(hipGetDevice(&device));
+        auto m = lightmix_alloc(device, n_lights, samples, n_local);
+        for (uint32_t l = 0; l < n_lights; ++l) m->unit[l] = unit[l];
+        for (uint32_t i = 0; i <= n_lights; ++i)
+            HIP_CHECK(hipMemcpy(m->plane(i), planes + (uint64_t)i * n_local * 3u, n_local * 12u, hipMemcpyHostToDevice));
+        *out = m.release();
+    });
+}
+
+void pt_lightmix_destroy(pt_lightmix* mix) { delete mix; }
+
+int pt_lightmix_get_info(const pt_lightmix* mix, pt_lightmix_info* info) {
+    return guarded([&] {
+        if (!mix || !info) fail(PT_ERR_INVALID, "pt_lightmix_get_info: null argument");
+        memset(info, 0, sizeof *info);
+        info->n_lights = mix->n_lights;
+        info->samples = mix->samples;
+        info->n_local = mix->n_local;
+        info->device_bytes = mix->bytes;
+        memcpy(info->unit, mix->unit, sizeof mix->unit);
+    });
+}
+
+int pt_lightmix_basis(const pt_lightmix* mix, uint32_t plane, float* host) {
+    return guarded([&] {
+        if (!mix || !host) fail(PT_ERR_INVALID, "pt_lightmix_basis: null argument");
+        if (plane > mix->n_lights) fail(PT_ERR_INVALID, "pt_lightmix_basis: plane %u of %u", plane, mix->n_lights + 1u);
+        HIP_CHECK(hipSetDevice(mix->device));
+        HIP_CHECK(hipMemcpy(host, mix->plane(plane), mix->n_local * 12u, hipMemcpyDeviceToHost));
+    });
+}
+
+int pt_lightmix_apply_device(const pt_lightmix* mix, const float* colors, int tonemap, void* d_rgb8, void* d_accum, void* hip_stream) {
+    return guarded([&] {
+        const LmFactors F = lightmix_factors("pt_lightmix_apply_device", mix, colors, tonemap, d_rgb8, d_accum);
+        if (((uintptr_t)d_rgb8 & 3u) || ((uintptr_t)d_accum & 15u))
+            fail(PT_ERR_INVALID, "pt_lightmix_apply_device: d_rgb8 must be 4-byte and d_accum 16-byte aligned");
+        HIP_CHECK(hipSetDevice(mix->device));
+        lightmix_launch(*mix, F, tonemap, (uint8_t*)d_rgb8, (float*)d_accum, (hipStream_t)hip_stream);
+    });
+}
+
+int pt_lightmix_apply(const pt_lightmix* mix, const float* colors, int tonemap, uint8_t* rgb8, float* accum) {
+    return guarded([&] {
+        const LmFactors F = lightmix_factors("pt_lightmix_apply", mix, colors, tonemap, rgb8, accum);
+        HIP_CHECK(hipSetDevice(mix->device));
+        const size_t n = (size_t)mix->n_local * 3u;
+        Staged<uint8_t> d_rgb(nullptr, n);
+        Staged<float> d_acc(nullptr, n);
+        lightmix_launch(*mix, F, tonemap, rgb8 ? d_rgb.d : nullptr, accum ? d_acc.d : nullptr, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        if (rgb8) d_rgb.fetch(rgb8, n);
+        if (accum) d_acc.fetch(accum, n);
     });
 }
 

@@ -3,7 +3,7 @@
 //
 //   path-tracer render <INPUT> [-o/--output <OUTPUT>] [-q/--quiet] [-v/--viewer]
 //                              [--debug-textures] [-p/--profile <PROFILE>] [--camera-path <CAMERAS>]
-//                              [--keyframes <FRAMES>]
+//                              [--keyframes <FRAMES> [--light-mixer]]
 //       env OUTPUT (default render.png), env PROFILE
 //   path-tracer convert <INPUT> <OUTPUT>      (glTF 2.0 -> ISF, host/gltf_convert.cpp)
 //
@@ -17,7 +17,8 @@
 // turn through pt_scene_set_camera; frame i goes to OUTPUT with i substituted for its one %d / %0Nd field),
 // --keyframes frames.json (a JSON array of frames, each with any of a camera, all lights, material factor edits: the scene
 // is uploaded once, frame i's edits are applied on top of frame i - 1's through pt_scene_set_camera / _set_lights /
-// _set_materials, and frame i is written as with --camera-path).
+// _set_materials, and frame i is written as with --camera-path), --light-mixer (with --keyframes: frames whose only edit
+// is the colour of lights are mixed from the planes of one pt_lightmix capture instead of rendered).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -57,6 +58,8 @@ void usage_render(FILE* f) {
           "                           takes the frame index in its %d / %0Nd field (e.g. out/frame_%04d.png)\n"
           "      --keyframes <FRAMES>  Render one frame per object of a JSON array of keyframes (\"camera\", \"lights\",\n"
           "                           \"materials\" edits, each frame on top of the last); OUTPUT as with --camera-path\n"
+          "      --light-mixer        With --keyframes: capture light-mixer planes where the next frame changes light colours only\n"
+          "                           and mix such frames from them instead of rendering (one device, not with --denoise)\n"
           "      --denoise            Write the frame filtered by the edge-avoiding a-trous denoiser (first-hit normal, depth and\n"
           "                           albedo guides); one device only, -v previews stay raw\n"
           "      --denoise-iterations <N>  Filter passes of --denoise, pass i has step 2^i [0..8, default: the library's]\n"
@@ -135,7 +138,7 @@ int run_render(int argc, char** argv) {
     std::string camera_path, keyframes_path;
     bool have_output = false, have_profile = false, quiet = false, debug_textures = false, stats = false, viewer = false;
     bool have_camera_path = false, have_keyframes = false;
-    bool denoise = false, denoise_variance = false;
+    bool denoise = false, denoise_variance = false, light_mixer = false;
     int denoise_iterations = -1;
     int device = 0;
     std::vector<int> devices;
@@ -168,6 +171,7 @@ int run_render(int argc, char** argv) {
         else if (a == "--debug-textures") debug_textures = true;
         else if (a == "--stats") stats = true;
         else if (a == "--denoise") denoise = true;
+        else if (a == "--light-mixer") light_mixer = true;
         else if (a == "--denoise-variance") denoise_variance = true;
         else if (a == "--denoise-iterations" || a.rfind("--denoise-iterations=", 0) == 0) {
             std::string v = value("--denoise-iterations <N>");
@@ -216,6 +220,11 @@ int run_render(int argc, char** argv) {
     if (denoise && devices.size() > 1)
         die("error: the argument '--denoise' cannot be used with more than one device in '--devices <A,B,..>' (the gathered "
             "multi-GPU frame is u8 only; the filter needs the f32 frame on one device)");
+    if (light_mixer && !have_keyframes) die("error: '--light-mixer' needs '--keyframes <FRAMES>'");
+    if (light_mixer && denoise) die("error: the argument '--light-mixer' cannot be used with '--denoise' (mixed frames are not filtered)");
+    if (light_mixer && devices.size() > 1)
+        die("error: the argument '--light-mixer' cannot be used with more than one device in '--devices <A,B,..>' (mixed frames "
+            "are not gathered)");
 
     // Profile::load / Default (main.rs:33-36)
     pt_profile profile;
@@ -468,13 +477,51 @@ int run_render(int argc, char** argv) {
     if (denoise_iterations >= 0) dn.iterations = (uint32_t)denoise_iterations;
     const size_t n_frames = edits.empty() ? 1 : edits.size();   // (--camera-path / --keyframes: one frame each, the scene kept)
     auto t3 = t2, t4 = t2;
+    // --light-mixer: frame f is colour-only when its keyframe has no camera and no materials and its lights are the previous
+    // state's in count, kind, vec and size.  A capture lives until the first frame that is not; while it lives the scene is
+    // not told about the colours (lights_of: the frame whose lights it has), so a mixed frame costs no grid rebuild.
+    auto colour_only = [&](size_t f) {
+        return f > 0 && f < n_frames && !edits[f].camera && !edits[f].materials &&
+               pth_lights_differ_in_color_only(edits[f - 1].light.data(), (uint32_t)edits[f - 1].light.size(), edits[f].light.data(),
+                                               (uint32_t)edits[f].light.size());
+    };
+    pt_lightmix* mix = nullptr;
+    bool mixer_on = light_mixer;
+    size_t lights_of = 0, captures = 0, mixed = 0, rendered = 0;
     for (size_t f = 0; f < n_frames; ++f) {
-        if (f > 0 && apply_frame(scene, f) != PT_OK) die(pt_last_error());
+        bool use_mix = false;
+        if (light_mixer) {
+            if (mix && !colour_only(f)) {
+                pt_lightmix_destroy(mix);
+                mix = nullptr;
+            }
+            if (f > 0 && !mix) {   // the scene takes the frame; its lights also when earlier mixed frames held them back
+                FrameEdit& e = edits[f];
+                e.lights = e.lights || lights_of != f - 1;
+                if (apply_frame(scene, f) != PT_OK) die(pt_last_error());
+                lights_of = f;
+            }
+            if (!mix && mixer_on && colour_only(f + 1)) {
+                const int rc = pt_lightmix_capture(scene, &profile, &opts, &mix);
+                if (rc == PT_ERR_UNSUPPORTED) mixer_on = false;   // (more lights than a capture takes: every frame is rendered)
+                else if (rc != PT_OK) die(pt_last_error());
+                else ++captures;
+            }
+            use_mix = mix != nullptr;
+        } else if (f > 0 && apply_frame(scene, f) != PT_OK) die(pt_last_error());
         pv.path = frame_name(f);
-        if ((denoise_variance ? pt_render_denoised_var(scene, &profile, &opts, &dn, rgb.data(), nullptr)
-             : denoise        ? pt_render_denoised(scene, &profile, &opts, &dn, rgb.data(), nullptr)
-                              : pt_render(scene, &profile, &opts, rgb.data(), nullptr)) != PT_OK)
-            die(pt_last_error());
+        if (use_mix) {
+            std::vector<float> colors;
+            for (const pt_light& l : edits[f].light) colors.insert(colors.end(), l.color, l.color + 3);
+            if (pt_lightmix_apply(mix, colors.data(), profile.tonemap, rgb.data(), nullptr) != PT_OK) die(pt_last_error());
+            ++mixed;
+        } else {
+            if ((denoise_variance ? pt_render_denoised_var(scene, &profile, &opts, &dn, rgb.data(), nullptr)
+                 : denoise        ? pt_render_denoised(scene, &profile, &opts, &dn, rgb.data(), nullptr)
+                                  : pt_render(scene, &profile, &opts, rgb.data(), nullptr)) != PT_OK)
+                die(pt_last_error());
+            ++rendered;
+        }
         t3 = std::chrono::steady_clock::now();
         if (!quiet)
             fprintf(stderr, "\nDone: %llds\n", (long long)std::chrono::duration_cast<std::chrono::seconds>(t3 - t2).count());
@@ -487,6 +534,9 @@ int run_render(int argc, char** argv) {
         if (pth_png_write_rgb8(frame_name(f).c_str(), profile.width, profile.height, rgb.data()) != PT_OK) die(pth_last_error());
         t4 = std::chrono::steady_clock::now();
     }
+
+    if (mix) pt_lightmix_destroy(mix);
+    if (light_mixer) fprintf(stderr, "light mixer: %zu captures, %zu mixed frames, %zu rendered frames\n", captures, mixed, rendered);
 
     if (stats) {
         pt_timing tm{};

@@ -849,6 +849,14 @@ int pth_keyframe_apply(pth_scene* s, const pth_keyframe* frame) {
     });
 }
 
+int pth_lights_differ_in_color_only(const pt_light* a, uint32_t n_a, const pt_light* b, uint32_t n_b) {
+    if (n_a != n_b || ((!a || !b) && n_a > 0)) return 0;
+    for (uint32_t i = 0; i < n_a; ++i)
+        if (a[i].kind != b[i].kind || memcmp(a[i].vec, b[i].vec, sizeof a[i].vec) != 0 || memcmp(&a[i].size, &b[i].size, sizeof a[i].size) != 0)
+            return 0;
+    return 1;
+}
+
 const pt_scene_desc* pth_scene_desc(const pth_scene* s) { return s ? &s->desc : nullptr; }
 
 uint64_t pth_prim_count(const pt_scene_desc* d) {

@@ -490,6 +490,110 @@ int  pt_lightmix_apply_device(const pt_lightmix* mix, const float* colors /* hos
                               void* d_rgb8, void* d_accum, void* hip_stream);   /* asynchronous, allocates nothing */
 
 /* ------------------------------------------------------------------ */
+/* progressive film (no reference counterpart)              */
+/* ------------------------------------------------------------------ */
+
+/* A film adds whole frames of ONE view (profile, opts) until the image is clean enough: it holds the sum of their accumulators
+ * (n_local x 3 f32) and of their luminance moments (n_local x 2 f32, pt_render_moments), in the packed local order of pt_render
+ * for (profile, opts), and makes a noise figure from the moments.  It is an add-on like the denoiser and the light mixer:
+ * every pass is an ordinary frame with the moments tap, exactly what pt_render_moments_device launches.
+ *
+ * What a pass is.  The seed of sample s of global pixel i in a frame of `samples` samples is s + i * samples
+ * (renderer/mod.rs:110-112), so two frames of the same `samples` are the same frame.  A pass is therefore a whole frame whose
+ * `samples` is AT LEAST TWICE the pass's before it.  Pixel i of a pass of a samples uses the seeds [i*a, i*a + a); for passes a
+ * and b >= 2a the ranges of one pixel overlap only for i < a / (b - a) <= 1:
+ *   - global pixel 0 is the only pixel that ever sees a seed twice (the first a samples of its larger pass repeat the smaller
+ *     pass).  Its mean stays unbiased; only its variance estimate is slightly off.
+ *   - seeds ARE shared between different pixels of different passes (pixel j of pass b and pixel ~ j*b/a of pass a).  That
+ *     correlates the noise of two distant pixels and biases nothing.
+ * No sample is rendered twice, so the doubling costs nothing.  Every pass is the first frame of its configuration (a new
+ * `samples`): unplanned, no frame cache is keyed - the situation of a camera path.
+ *
+ * pt_film_create copies profile (its samples is ignored) and opts (the progress and preview callbacks are dropped) and allocates
+ * on `device` (HIP ordinal, -1 = current): the film's accum and moments, pass buffers of the same size, one err plane (n_local
+ * f32) and the block arrays.  PT_FLAG_MEGAKERNEL (no staged samples): PT_ERR_UNSUPPORTED; a null pointer, a rank without pixels
+ * or an option pt_render refuses: PT_ERR_INVALID.  pt_film_create_from_planes makes a film from host planes (accum n_local x 3,
+ * moments n_local x 2; samples = their total, 1 .. PT_FILM_MAX_SAMPLES; last_pass_samples in 1 .. samples; n_local in
+ * 1 .. 2^31 - 1) - for tests and for planes kept on disk.  Such a film counts one pass and has no profile (info: width =
+ * height = 0): pt_film_add_pass and pt_film_render_until on it are PT_ERR_INVALID.
+ * pt_film_reset: back to zero passes and zero planes, the allocations stay.  pt_film_read: host copies, either pointer may be
+ * NULL.  pt_film_planes_device: the device planes (256-byte aligned), for pt_denoise_device / pt_denoise_var_device with
+ * samples = info.samples (unsharded films; the planes are the film's, valid until pt_film_destroy, and change with every pass).
+ *
+ * pt_film_add_pass renders the frame (profile with `samples`, opts) of `scene` into the pass buffers, waits for it and only
+ * then merges, per float of accum and of moments alike:   film = film + pass   (one f32 addition; a film of one pass holds that
+ * frame's bits).  PT_ERR_INVALID before any device work: a null pointer, a film without a profile, samples < 1,
+ * samples < 2 * last_pass_samples when a pass exists, a total above PT_FILM_MAX_SAMPLES, a scene on another device than the
+ * film's.  Any failure before the merge leaves the film's planes and counters as they were.  The film does not watch the scene:
+ * edits between passes are the caller's business, as with pt_lightmix.  The call blocks.
+ * pt_film_add_planes merges a pass that was rendered elsewhere or earlier (host planes of pt_render_moments for the film's
+ * view: accum n_local x 3, moments n_local x 2, `samples` theirs) with the same kernel, under the same rules for `samples`; it
+ * works on every film.
+ *
+ * pt_film_noise: all f32, one IEEE operation per step in this order, uncontracted, IEEE divide and sqrt
+ * (tests/film_model.py restates it bit for bit); n = the film's total samples, (m1, m2) = the film's moments of the pixel:
+ *   per pixel p   N = (float)n;  mu = m1 / N;  e2 = m2 / N;  s2 = max(0, e2 - mu*mu);  vL = s2 / (float)(n - 1);
+ *                 se = sqrt(vL);  den = max(mu, lum_floor);  err = se / den
+ *                 (the standard error of the pixel's mean luminance relative to that mean; a pixel darker than lum_floor is
+ *                 judged as if it had that brightness)
+ *   per block b   the packed pixels [256 b, 256 b + 256):  v[i] = err of pixel 256 b + i, or 0.f beyond n_local;
+ *                 for stride = 128, 64, 32, 16, 8, 4, 2, 1:  for i < stride:  v[i] = v[i] + v[i + stride]
+ *                 block_sum[b] = v[0];  block_max[b] = the largest err of the block's pixels
+ *   on the host, in f64, b ascending:   S = S + (double)block_sum[b];   mean_b = (double)block_sum[b] / pixels_in_block(b)
+ *                 mean_error = S / n_local;  max_block_error = the largest mean_b;  fraction_over = (blocks with
+ *                 mean_b > target) / n_blocks;  converged = mean_error <= target
+ * err_host (n_local f32), block_sum_host and block_max_host (n_blocks f32 each, n_blocks = ceil(n_local / 256)) may be NULL.
+ * PT_ERR_INVALID: a null film or out, a total n < 2, lum_floor not positive and finite, target negative or not finite.
+ * Non-finite planes are outside the contract.  PT_FILM_MAX_SAMPLES keeps (float)n exact.
+ *
+ * pt_film_resolve: color = accum / (float)n per float [n_local x 3 f32]; rgb8 = pt_render's post-processing of accum with
+ * samples = n [n_local x 3].  Either output may be NULL, not both (PT_ERR_INVALID, as n = 0 and an unknown tone map).  The host
+ * form blocks; the device form is asynchronous on hip_stream and allocates nothing.
+ *
+ * pt_film_render_until adds passes until the noise target is met: the next pass has first_pass_samples on an empty film and
+ * 2 * last_pass_samples otherwise.  It adds the pass, computes the noise (lum_floor, target), calls on_pass(info, noise, user) if
+ * set, and goes on; it stops when the noise has converged or when the total plus the next pass would exceed max_samples (or
+ * PT_FILM_MAX_SAMPLES).  out = the last noise; out->converged tells why it stopped.  A film that can take no pass at all gets
+ * the noise of what it holds.  PT_ERR_INVALID before any device work: what pt_film_add_pass and pt_film_noise refuse,
+ * first_pass_samples < 2, an empty film with first_pass_samples > max_samples. */
+typedef struct pt_film pt_film;
+typedef struct pt_film_info {
+    uint32_t width, height, passes, last_pass_samples;
+    uint64_t n_local, samples /* total */, device_bytes;
+} pt_film_info;
+typedef struct pt_film_noise_stats {
+    double mean_error;        /* sum of the block sums / n_local                                   */
+    double max_block_error;   /* largest block_sum[b] / pixels_in_block(b)                         */
+    double fraction_over;     /* share of blocks whose mean error exceeds target                   */
+    uint64_t samples;         /* total samples the figures are for                                 */
+    uint32_t n_blocks, converged /* mean_error <= target */;
+} pt_film_noise_stats;
+enum { PT_FILM_MAX_SAMPLES = 1u << 24 };   /* (float)n stays exact */
+#define PT_FILM_DEFAULT_LUM_FLOOR 0.01f
+typedef void (*pt_film_pass_fn)(const pt_film_info* info, const pt_film_noise_stats* noise, void* user);
+
+int  pt_film_create(int device, const pt_profile* profile, const pt_opts* opts, pt_film** out);
+int  pt_film_create_from_planes(int device, uint64_t n_local, uint64_t samples, uint32_t last_pass_samples,
+                                const float* accum /* host */, const float* moments /* host */, pt_film** out);
+void pt_film_destroy(pt_film* film);
+int  pt_film_reset(pt_film* film);
+int  pt_film_get_info(const pt_film* film, pt_film_info* info);
+int  pt_film_read(const pt_film* film, float* accum, float* moments);                  /* host, either may be NULL */
+int  pt_film_planes_device(const pt_film* film, void** d_accum, void** d_moments);
+int  pt_film_add_pass(pt_film* film, const pt_scene* scene, uint32_t samples);
+int  pt_film_add_planes(pt_film* film, uint32_t samples, const float* accum /* host */, const float* moments /* host */);
+int  pt_film_noise(const pt_film* film, float lum_floor, double target, pt_film_noise_stats* out, float* err_host,
+                   float* block_sum_host, float* block_max_host);
+int  pt_film_resolve(const pt_film* film, int tonemap, uint8_t* rgb8, float* color);   /* host */
+int  pt_film_resolve_device(const pt_film* film, int tonemap, void* d_rgb8, void* d_color, void* hip_stream);
+int  pt_film_render_until(pt_film* film, const pt_scene* scene, uint32_t first_pass_samples, uint64_t max_samples,
+                          float lum_floor, double target, pt_film_pass_fn on_pass, void* user, pt_film_noise_stats* out);
+/* Measurement: the two kernels between HIP events on the null stream, `reps` times each (blocks): ms_merge[r] = k_film_merge
+ * adding the film's planes to its PASS buffers (scratch between passes; the film is unchanged), ms_noise[r] = k_film_noise
+ * (lum_floor, with the err plane written when with_err is not 0).  The film's total must be >= 2. */
+int  pt_film_kernel_times(const pt_film* film, float lum_floor, int with_err, uint32_t reps, float* ms_merge, float* ms_noise);
+
+/* ------------------------------------------------------------------ */
 /* measurement                                                         */
 /* ------------------------------------------------------------------ */
 

@@ -143,6 +143,28 @@ class LightMixInfo(C.Structure):
                 ("unit", C.c_float * PT_LIGHTMIX_MAX_LIGHTS)]
 
 
+PT_FILM_MAX_SAMPLES = 1 << 24
+PT_FILM_DEFAULT_LUM_FLOOR = 0.01
+
+
+class FilmInfo(C.Structure):
+    """pt_film_info."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("passes", C.c_uint32), ("last_pass_samples", C.c_uint32),
+                ("n_local", C.c_uint64), ("samples", C.c_uint64), ("device_bytes", C.c_uint64)]
+
+
+class FilmNoise(C.Structure):
+    """pt_film_noise_stats: what pt_film_noise makes of the film's moments."""
+    _fields_ = [("mean_error", C.c_double), ("max_block_error", C.c_double), ("fraction_over", C.c_double),
+                ("samples", C.c_uint64), ("n_blocks", C.c_uint32), ("converged", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+FILM_PASS_FN = C.CFUNCTYPE(None, C.POINTER(FilmInfo), C.POINTER(FilmNoise), C.c_void_p)
+
+
 class Hit(C.Structure):
     _fields_ = [("prim", C.c_int32), ("flags", C.c_int32), ("dist", C.c_float), ("u", C.c_float),
                 ("v", C.c_float)]
@@ -244,7 +266,10 @@ GPU_SYMBOLS = ["pt_scene_create", "pt_scene_destroy", "pt_scene_set_camera", "pt
                "pt_denoise_var_scratch_bytes", "pt_denoise_var", "pt_denoise_var_device", "pt_render_denoised_var",
                "pt_denoise_var_stage_times",
                "pt_lightmix_capture", "pt_lightmix_create_from_planes", "pt_lightmix_destroy", "pt_lightmix_get_info",
-               "pt_lightmix_basis", "pt_lightmix_apply", "pt_lightmix_apply_device"]
+               "pt_lightmix_basis", "pt_lightmix_apply", "pt_lightmix_apply_device",
+               "pt_film_create", "pt_film_create_from_planes", "pt_film_destroy", "pt_film_reset", "pt_film_get_info",
+               "pt_film_read", "pt_film_planes_device", "pt_film_add_pass", "pt_film_add_planes", "pt_film_noise", "pt_film_resolve",
+               "pt_film_resolve_device", "pt_film_render_until", "pt_film_kernel_times"]
 
 
 def host_lib():
@@ -404,6 +429,23 @@ def gpu_lib():
             L.pt_lightmix_basis.argtypes = [vp, C.c_uint32, vp]
             L.pt_lightmix_apply.argtypes = [vp, vp, C.c_int, vp, vp]
             L.pt_lightmix_apply_device.argtypes = [vp, vp, C.c_int, vp, vp, vp]
+        if hasattr(L, "pt_film_create"):   # (an A/B library of an earlier commit has no film)
+            L.pt_film_create.argtypes = [C.c_int, C.POINTER(Profile), C.POINTER(Opts), C.POINTER(vp)]
+            L.pt_film_create_from_planes.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp, C.POINTER(vp)]
+            L.pt_film_destroy.argtypes = [vp]
+            L.pt_film_destroy.restype = None
+            L.pt_film_reset.argtypes = [vp]
+            L.pt_film_get_info.argtypes = [vp, C.POINTER(FilmInfo)]
+            L.pt_film_read.argtypes = [vp, vp, vp]
+            L.pt_film_planes_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+            L.pt_film_add_pass.argtypes = [vp, vp, C.c_uint32]
+            L.pt_film_add_planes.argtypes = [vp, C.c_uint32, vp, vp]
+            L.pt_film_noise.argtypes = [vp, C.c_float, C.c_double, C.POINTER(FilmNoise), vp, vp, vp]
+            L.pt_film_resolve.argtypes = [vp, C.c_int, vp, vp]
+            L.pt_film_resolve_device.argtypes = [vp, C.c_int, vp, vp, vp]
+            L.pt_film_render_until.argtypes = [vp, vp, C.c_uint32, C.c_uint64, C.c_float, C.c_double, FILM_PASS_FN, vp,
+                                               C.POINTER(FilmNoise)]
+            L.pt_film_kernel_times.argtypes = [vp, C.c_float, C.c_int, C.c_uint32, vp, vp]
         L.pt_last_error.restype = C.c_char_p
         L.pt_version.restype = C.c_char_p
         _gpu = L
@@ -1123,6 +1165,141 @@ class LightMix:
     def close(self):
         if self.handle:
             self.lib.pt_lightmix_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Film:
+    """pt_film: the sum of several whole frames of one view (accum and luminance moments) and the noise figure of its
+    moments.  Every pass has at least twice the samples of the pass before it (include/ptgpu.h).  Owns device memory."""
+
+    def __init__(self, profile, opts=None, device=0):
+        self.lib = gpu_lib()
+        self.handle = C.c_void_p()
+        self.tonemap = profile.tonemap if profile is not None else TONEMAPS["FILMIC"]
+        check_gpu(self.lib.pt_film_create(device, C.byref(profile) if profile is not None else None,
+                                          C.byref(opts) if opts is not None else None, C.byref(self.handle)))
+
+    @classmethod
+    def from_planes(cls, accum, moments, samples, last_pass_samples=None, device=0):
+        """pt_film_create_from_planes: accum [n_local, 3] and moments [n_local, 2] float32, `samples` their total."""
+        import numpy as np
+        accum = np.ascontiguousarray(accum, np.float32)
+        moments = np.ascontiguousarray(moments, np.float32)
+        if accum.ndim != 2 or accum.shape[1] != 3 or moments.shape != (accum.shape[0], 2):
+            raise PtError(PT_ERR_INVALID, "Film.from_planes: accum must be [n_local, 3] and moments [n_local, 2]")
+        self = cls.__new__(cls)
+        self.lib = gpu_lib()
+        self.handle = C.c_void_p()
+        self.tonemap = TONEMAPS["FILMIC"]
+        check_gpu(self.lib.pt_film_create_from_planes(device, accum.shape[0], samples,
+                                                      samples if last_pass_samples is None else last_pass_samples,
+                                                      accum.ctypes.data, moments.ctypes.data, C.byref(self.handle)))
+        return self
+
+    @property
+    def info(self):
+        i = FilmInfo()
+        check_gpu(self.lib.pt_film_get_info(self.handle, C.byref(i)))
+        return i
+
+    def add_pass(self, scene, samples):
+        """pt_film_add_pass: one more frame of `samples` samples (at least twice the last pass's) of a GpuScene."""
+        check_gpu(self.lib.pt_film_add_pass(self.handle, scene.handle, samples))
+
+    def add_planes(self, accum, moments, samples):
+        """pt_film_add_planes: a pass rendered elsewhere (pt_render_moments' accum [n_local, 3] and moments [n_local, 2])."""
+        import numpy as np
+        accum = np.ascontiguousarray(accum, np.float32)
+        moments = np.ascontiguousarray(moments, np.float32)
+        n = int(self.info.n_local)
+        if accum.shape != (n, 3) or moments.shape != (n, 2):
+            raise PtError(PT_ERR_INVALID, "Film.add_planes: accum must be [n_local, 3] and moments [n_local, 2]")
+        check_gpu(self.lib.pt_film_add_planes(self.handle, samples, accum.ctypes.data, moments.ctypes.data))
+
+    def render_until(self, scene, first, max_samples, target, lum_floor=PT_FILM_DEFAULT_LUM_FLOOR, on_pass=None):
+        """pt_film_render_until: passes of first, 2 * first, ... samples until the mean error is <= target or the next pass
+        would take the total above max_samples; on_pass(FilmInfo, FilmNoise) after every pass (copies).  Returns the last
+        FilmNoise."""
+        out = FilmNoise()
+        failure = []
+
+        def trampoline(info, noise, _user):
+            try:
+                on_pass(_copy(FilmInfo, info.contents), _copy(FilmNoise, noise.contents))
+            except BaseException as e:   # (an exception cannot cross the C frames: raised after the call)
+                failure.append(e)
+        cb = FILM_PASS_FN(trampoline) if on_pass is not None else C.cast(None, FILM_PASS_FN)
+        check_gpu(self.lib.pt_film_render_until(self.handle, scene.handle, first, max_samples, lum_floor, target, cb, None,
+                                                C.byref(out)))
+        if failure:
+            raise failure[0]
+        return out
+
+    def noise(self, target, lum_floor=PT_FILM_DEFAULT_LUM_FLOOR, want_planes=False):
+        """pt_film_noise: FilmNoise; with want_planes (FilmNoise, err [n_local], block_sum [n_blocks], block_max [n_blocks])."""
+        import numpy as np
+        out = FilmNoise()
+        if not want_planes:
+            check_gpu(self.lib.pt_film_noise(self.handle, lum_floor, target, C.byref(out), None, None, None))
+            return out
+        n = int(self.info.n_local)
+        nb = (n + 255) // 256
+        err, bsum, bmax = np.empty(n, np.float32), np.empty(nb, np.float32), np.empty(nb, np.float32)
+        check_gpu(self.lib.pt_film_noise(self.handle, lum_floor, target, C.byref(out), err.ctypes.data, bsum.ctypes.data,
+                                         bmax.ctypes.data))
+        return out, err, bsum, bmax
+
+    def read(self):
+        """pt_film_read: (accum [n_local, 3], moments [n_local, 2]) float32."""
+        import numpy as np
+        n = int(self.info.n_local)
+        acc, mom = np.empty((n, 3), np.float32), np.empty((n, 2), np.float32)
+        check_gpu(self.lib.pt_film_read(self.handle, acc.ctypes.data, mom.ctypes.data))
+        return acc, mom
+
+    def _tonemap(self, tonemap):
+        return self.tonemap if tonemap is None else TONEMAPS.get(tonemap, tonemap)
+
+    def resolve(self, tonemap=None, want_color=False):
+        """pt_film_resolve: rgb8 [n_local, 3] uint8 (tonemap: a name or number, default the profile's - FILMIC for a film from
+        planes); with want_color (rgb8, color [n_local, 3] float32 = accum / samples)."""
+        import numpy as np
+        n = int(self.info.n_local)
+        rgb = np.empty((n, 3), np.uint8)
+        col = np.empty((n, 3), np.float32) if want_color else None
+        check_gpu(self.lib.pt_film_resolve(self.handle, self._tonemap(tonemap), rgb.ctypes.data,
+                                           col.ctypes.data if want_color else None))
+        return (rgb, col) if want_color else rgb
+
+    def resolve_device(self, tonemap, d_rgb8, d_color, stream=0):
+        """pt_film_resolve_device: device pointers (either may be 0 / None), asynchronous on `stream`."""
+        check_gpu(self.lib.pt_film_resolve_device(self.handle, self._tonemap(tonemap), d_rgb8 or None, d_color or None, stream))
+
+    def planes_device(self):
+        """pt_film_planes_device: the device addresses (accum, moments) of the film's planes."""
+        a, m = C.c_void_p(), C.c_void_p()
+        check_gpu(self.lib.pt_film_planes_device(self.handle, C.byref(a), C.byref(m)))
+        return a.value, m.value
+
+    def kernel_times(self, lum_floor=PT_FILM_DEFAULT_LUM_FLOOR, with_err=False, reps=20):
+        """pt_film_kernel_times: (ms of k_film_merge [reps], ms of k_film_noise [reps])."""
+        import numpy as np
+        a, b = np.zeros(reps, np.float32), np.zeros(reps, np.float32)
+        check_gpu(self.lib.pt_film_kernel_times(self.handle, lum_floor, int(with_err), reps, a.ctypes.data, b.ctypes.data))
+        return a, b
+
+    def reset(self):
+        check_gpu(self.lib.pt_film_reset(self.handle))
+
+    def close(self):
+        if self.handle:
+            self.lib.pt_film_destroy(self.handle)
             self.handle = C.c_void_p()
 
     def __del__(self):

@@ -15,6 +15,7 @@
 //   k_debug           --debug-textures G-buffer pass (debug_renderer.rs:64-105)
 //   k_guides, k_dn_*  pt_denoise.h: first-hit guide planes and the a-trous filter of denoised previews
 //   k_accumulate_moments, k_dnv_*  pt_variance.h: per-pixel sample moments and the variance-guided form of that filter
+//   k_film_*          pt_film.h: the progressive film - merging passes, the noise figure of its moments
 //   k_stream_copy     achievable-HBM yardstick of the roofline (pt_measure_copy_bandwidth)
 //   k_trace / k_trace_all / k_escape_query / k_isect / k_rng / k_math   parity-test hooks
 #include <hip/hip_runtime.h>
@@ -46,6 +47,7 @@
 #include "pt_denoise.h"
 #include "pt_variance.h"
 #include "pt_lightmix.h"
+#include "pt_film.h"
 #include "pthost.h"
 #include "../host/scene_check.h"
 
@@ -3894,6 +3896,168 @@ std::unique_ptr<pt_lightmix> lightmix_capture(pt_scene& s, const pt_profile& p, 
 
 }  // namespace
 
+// ------------------------------------------------------------------ progressive film (pt_film.h)
+// One allocation: the film's accum and moments, the pass buffers of the same strides, the err plane and the two block
+// arrays - each on a 256-byte boundary, every stride a multiple of 64 floats, the padding zero.
+struct pt_film {
+    int device = 0;
+    bool has_profile = false;
+    pt_profile profile{};
+    pt_opts opts{};
+    uint64_t n_local = 0, stride_a = 0, stride_m = 0, stride_e = 0, stride_b = 0, bytes = 0;
+    uint32_t n_blocks = 0, passes = 0, last_pass_samples = 0;
+    uint64_t samples = 0;
+    float* base = nullptr;
+    float *accum = nullptr, *moments = nullptr, *pass_accum = nullptr, *pass_moments = nullptr, *err = nullptr;
+    float *block_sum = nullptr, *block_max = nullptr;
+    ~pt_film() {
+        if (base) (void)hipFree(base);
+    }
+};
+
+namespace {
+
+std::unique_ptr<pt_film> film_alloc(int device, uint64_t n_local) {
+    auto up = [](uint64_t floats) { return (floats + 63u) & ~(uint64_t)63u; };
+    auto f = std::make_unique<pt_film>();
+    f->device = device;
+    f->n_local = n_local;
+    f->n_blocks = (uint32_t)((n_local + 255u) / 256u);
+    f->stride_a = up(3u * n_local);
+    f->stride_m = up(2u * n_local);
+    f->stride_e = up(n_local);
+    f->stride_b = up(f->n_blocks);
+    const uint64_t floats = 2u * (f->stride_a + f->stride_m) + f->stride_e + 2u * f->stride_b;
+    f->bytes = floats * sizeof(float);
+    HIP_CHECK(hipMalloc((void**)&f->base, f->bytes));
+    HIP_CHECK(hipMemset(f->base, 0, f->bytes));   // (the padding behind every plane stays zero)
+    float* p = f->base;
+    f->accum = p, p += f->stride_a;
+    f->moments = p, p += f->stride_m;
+    f->pass_accum = p, p += f->stride_a;
+    f->pass_moments = p, p += f->stride_m;
+    f->err = p, p += f->stride_e;
+    f->block_sum = p, p += f->stride_b;
+    f->block_max = p;
+    return f;
+}
+
+uint32_t film_merge_blocks(const pt_film& f) {
+    return (uint32_t)std::min<uint64_t>((std::max(f.stride_a, f.stride_m) / 4u + 255u) / 256u, FILM_MAX_BLOCKS);
+}
+
+void film_check_noise_args(const char* who, float lum_floor, double target) {
+    if (!(lum_floor > 0.f) || !std::isfinite(lum_floor)) fail(PT_ERR_INVALID, "%s: lum_floor must be positive and finite", who);
+    if (!(target >= 0.0) || !std::isfinite(target)) fail(PT_ERR_INVALID, "%s: target must be finite and not negative", who);
+}
+
+// What pt_film_add_pass and pt_film_add_planes refuse, before any device work.
+void film_check_samples(const char* who, const pt_film* film, uint32_t samples) {
+    if (samples < 1u) fail(PT_ERR_INVALID, "%s: a pass needs samples >= 1", who);
+    if (film->passes && (uint64_t)samples < 2u * (uint64_t)film->last_pass_samples)
+        fail(PT_ERR_INVALID, "%s: a pass of %u samples after one of %u (at least twice as many: an equal pass would repeat its seeds)",
+             who, samples, film->last_pass_samples);
+    if (film->samples + samples > (uint64_t)PT_FILM_MAX_SAMPLES)
+        fail(PT_ERR_INVALID, "%s: %llu samples in all, at most %u", who, (unsigned long long)(film->samples + samples),
+             (unsigned)PT_FILM_MAX_SAMPLES);
+}
+void film_check_pass(const char* who, const pt_film* film, const pt_scene* scene, uint32_t samples) {
+    if (!film || !scene) fail(PT_ERR_INVALID, "%s: null argument", who);
+    if (!film->has_profile) fail(PT_ERR_INVALID, "%s: a film made from planes has no profile to render with", who);
+    film_check_samples(who, film, samples);
+    if (scene->device != film->device)
+        fail(PT_ERR_INVALID, "%s: the scene is on device %d, the film on device %d", who, scene->device, film->device);
+}
+
+// film = film + pass buffers, then the counters
+void film_merge(pt_film& film, uint32_t samples) {
+    hipLaunchKernelGGL(k_film_merge, dim3(film_merge_blocks(film)), dim3(256), 0, 0, (float4*)film.accum,
+                       (const float4*)film.pass_accum, film.stride_a / 4u, (float4*)film.moments,
+                       (const float4*)film.pass_moments, film.stride_m / 4u);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    ++film.passes;
+    film.last_pass_samples = samples;
+    film.samples += samples;
+}
+
+void film_add_pass(pt_film& film, const pt_scene* scene, uint32_t samples) {
+    film_check_pass("pt_film_add_pass", &film, scene, samples);
+    HIP_CHECK(hipSetDevice(film.device));
+    pt_profile p = film.profile;
+    p.samples = samples;
+    FrameTaps taps;
+    taps.moments = (float2*)film.pass_moments;
+    render_device(render_state(scene), p, &film.opts, nullptr, film.pass_accum, nullptr, false, &taps);
+    HIP_CHECK(hipDeviceSynchronize());   // the frame is complete (and has not failed) before the film changes
+    film_merge(film, samples);
+}
+
+void film_noise_launch(const pt_film& film, float lum_floor, bool with_err) {
+    hipLaunchKernelGGL(k_film_noise, dim3(film.n_blocks), dim3(256), 0, 0, (const float2*)film.moments, (uint32_t)film.n_local,
+                       (uint32_t)film.samples, lum_floor, with_err ? film.err : (float*)nullptr, film.block_sum, film.block_max);
+    HIP_CHECK(hipGetLastError());
+}
+
+void film_noise(const pt_film& film, float lum_floor, double target, pt_film_noise_stats& out, float* err_host,
+                float* block_sum_host, float* block_max_host) {
+    film_check_noise_args("pt_film_noise", lum_floor, target);
+    if (film.samples < 2u) fail(PT_ERR_INVALID, "pt_film_noise: a sample variance needs a total of >= 2 samples (got %llu)", (unsigned long long)film.samples);
+    HIP_CHECK(hipSetDevice(film.device));
+    film_noise_launch(film, lum_floor, err_host != nullptr);
+    std::vector<float> sums(film.n_blocks);
+    HIP_CHECK(hipMemcpy(sums.data(), film.block_sum, film.n_blocks * sizeof(float), hipMemcpyDeviceToHost));   // (waits for the kernel)
+    if (block_sum_host) memcpy(block_sum_host, sums.data(), film.n_blocks * sizeof(float));
+    if (block_max_host) HIP_CHECK(hipMemcpy(block_max_host, film.block_max, film.n_blocks * sizeof(float), hipMemcpyDeviceToHost));
+    if (err_host) HIP_CHECK(hipMemcpy(err_host, film.err, film.n_local * sizeof(float), hipMemcpyDeviceToHost));
+    double S = 0.0, worst = 0.0;
+    uint32_t over = 0;
+    for (uint32_t b = 0; b < film.n_blocks; ++b) {
+        const uint64_t pixels = std::min<uint64_t>(256u, film.n_local - 256ull * b);
+        const double mean_b = (double)sums[b] / (double)pixels;
+        S = S + (double)sums[b];
+        if (b == 0 || mean_b > worst) worst = mean_b;
+        if (mean_b > target) ++over;
+    }
+    out.mean_error = S / (double)film.n_local;
+    out.max_block_error = worst;
+    out.fraction_over = (double)over / (double)film.n_blocks;
+    out.samples = film.samples;
+    out.n_blocks = film.n_blocks;
+    out.converged = out.mean_error <= target ? 1u : 0u;
+}
+
+void film_fill_info(const pt_film& film, pt_film_info& info) {
+    memset(&info, 0, sizeof info);
+    info.width = film.has_profile ? film.profile.width : 0u;
+    info.height = film.has_profile ? film.profile.height : 0u;
+    info.passes = film.passes;
+    info.last_pass_samples = film.last_pass_samples;
+    info.n_local = film.n_local;
+    info.samples = film.samples;
+    info.device_bytes = film.bytes;
+}
+
+void film_check_resolve(const char* who, const pt_film* film, int tonemap_type, const void* rgb8, const void* color) {
+    if (!film || (!rgb8 && !color)) fail(PT_ERR_INVALID, "%s: null argument", who);
+    if (tonemap_type < PT_TONEMAP_REINHARD || tonemap_type > PT_TONEMAP_ACES) fail(PT_ERR_INVALID, "%s: unknown tonemap %d", who, tonemap_type);
+    if (film->samples == 0) fail(PT_ERR_INVALID, "%s: the film holds no samples", who);
+}
+
+void film_resolve_launch(const pt_film& film, int tonemap_type, uint8_t* d_rgb8, float* d_color, hipStream_t stream) {
+    const uint64_t n_floats = 3u * film.n_local;
+    if (d_color) {
+        const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_floats + 255u) / 256u, FILM_MAX_BLOCKS);
+        hipLaunchKernelGGL(k_film_color, dim3(blocks), dim3(256), 0, stream, (const float*)film.accum, d_color, n_floats, (float)film.samples);
+    }
+    if (d_rgb8)
+        hipLaunchKernelGGL(k_postprocess, dim3(((uint32_t)film.n_local + 255u) / 256u), dim3(256), 0, stream, (const float*)film.accum,
+                           d_rgb8, (uint32_t)film.n_local, (uint32_t)film.samples, tonemap_type);
+    HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace
+
 // ==================================================================== C ABI
 extern "C" {
 
@@ -4232,6 +4396,206 @@ int pt_lightmix_apply(const pt_lightmix* mix, const float* colors, int tonemap, 
         HIP_CHECK(hipDeviceSynchronize());
         if (rgb8) d_rgb.fetch(rgb8, n);
         if (accum) d_acc.fetch(accum, n);
+    });
+}
+
+int pt_film_create(int device, const pt_profile* profile, const pt_opts* opts, pt_film** out) {
+    return guarded([&] {
+        if (!profile || !out) fail(PT_ERR_INVALID, "pt_film_create: null argument");
+        moments_check_opts("pt_film_create", opts);
+        pt_opts o;
+        normalise_opts(*profile, opts, o);
+        o.progress = nullptr;
+        o.progress_user = nullptr;
+        o.preview = nullptr;
+        o.preview_user = nullptr;
+        if (profile->brdf != PT_BRDF_COOK_TORRANCE) fail(PT_ERR_INVALID, "pt_film_create: unknown brdf %d", profile->brdf);
+        if (profile->tonemap < PT_TONEMAP_REINHARD || profile->tonemap > PT_TONEMAP_ACES) fail(PT_ERR_INVALID, "pt_film_create: unknown tonemap %d", profile->tonemap);
+        const uint64_t n_local = make_tile_map(*profile, o, o.shard_rank).n_local;
+        if (n_local == 0) fail(PT_ERR_INVALID, "pt_film_create: this rank has no pixels");
+        if (device >= 0) HIP_CHECK(hipSetDevice(device));
+        else HIP_CHECK(hipGetDevice(&device));
+        auto f = film_alloc(device, n_local);
+        f->has_profile = true;
+        f->profile = *profile;
+        f->profile.samples = 0;
+        f->opts = o;
+        *out = f.release();
+    });
+}
+
+int pt_film_create_from_planes(int device, uint64_t n_local, uint64_t samples, uint32_t last_pass_samples, const float* accum,
+                               const float* moments, pt_film** out) {
+    return guarded([&] {
+        if (!accum || !moments || !out) fail(PT_ERR_INVALID, "pt_film_create_from_planes: null argument");
+        if (!n_local || n_local >= (1ull << 31)) fail(PT_ERR_INVALID, "pt_film_create_from_planes: n_local must be in 1 .. 2^31 - 1");
+        if (!samples || samples > (uint64_t)PT_FILM_MAX_SAMPLES)
+            fail(PT_ERR_INVALID, "pt_film_create_from_planes: samples must be in 1 .. %u", (unsigned)PT_FILM_MAX_SAMPLES);
+        if (!last_pass_samples || last_pass_samples > samples)
+            fail(PT_ERR_INVALID, "pt_film_create_from_planes: last_pass_samples must be in 1 .. samples");
+        if (device >= 0) HIP_CHECK(hipSetDevice(device));
+        else HIP_CHECK(hipGetDevice(&device));
+        auto f = film_alloc(device, n_local);
+        HIP_CHECK(hipMemcpy(f->accum, accum, n_local * 12u, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(f->moments, moments, n_local * 8u, hipMemcpyHostToDevice));
+        f->passes = 1;
+        f->last_pass_samples = last_pass_samples;
+        f->samples = samples;
+        *out = f.release();
+    });
+}
+
+void pt_film_destroy(pt_film* film) { delete film; }
+
+int pt_film_reset(pt_film* film) {
+    return guarded([&] {
+        if (!film) fail(PT_ERR_INVALID, "pt_film_reset: null argument");
+        HIP_CHECK(hipSetDevice(film->device));
+        HIP_CHECK(hipMemset(film->accum, 0, film->stride_a * sizeof(float)));
+        HIP_CHECK(hipMemset(film->moments, 0, film->stride_m * sizeof(float)));
+        HIP_CHECK(hipDeviceSynchronize());
+        film->passes = 0;
+        film->last_pass_samples = 0;
+        film->samples = 0;
+    });
+}
+
+int pt_film_get_info(const pt_film* film, pt_film_info* info) {
+    return guarded([&] {
+        if (!film || !info) fail(PT_ERR_INVALID, "pt_film_get_info: null argument");
+        film_fill_info(*film, *info);
+    });
+}
+
+int pt_film_read(const pt_film* film, float* accum, float* moments) {
+    return guarded([&] {
+        if (!film) fail(PT_ERR_INVALID, "pt_film_read: null argument");
+        HIP_CHECK(hipSetDevice(film->device));
+        if (accum) HIP_CHECK(hipMemcpy(accum, film->accum, film->n_local * 12u, hipMemcpyDeviceToHost));
+        if (moments) HIP_CHECK(hipMemcpy(moments, film->moments, film->n_local * 8u, hipMemcpyDeviceToHost));
+    });
+}
+
+int pt_film_planes_device(const pt_film* film, void** d_accum, void** d_moments) {
+    return guarded([&] {
+        if (!film) fail(PT_ERR_INVALID, "pt_film_planes_device: null argument");
+        if (d_accum) *d_accum = film->accum;
+        if (d_moments) *d_moments = film->moments;
+    });
+}
+
+int pt_film_add_pass(pt_film* film, const pt_scene* scene, uint32_t samples) {
+    return guarded([&] {
+        film_check_pass("pt_film_add_pass", film, scene, samples);
+        film_add_pass(*film, scene, samples);
+    });
+}
+
+int pt_film_add_planes(pt_film* film, uint32_t samples, const float* accum, const float* moments) {
+    return guarded([&] {
+        if (!film || !accum || !moments) fail(PT_ERR_INVALID, "pt_film_add_planes: null argument");
+        film_check_samples("pt_film_add_planes", film, samples);
+        HIP_CHECK(hipSetDevice(film->device));
+        HIP_CHECK(hipMemcpy(film->pass_accum, accum, film->n_local * 12u, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(film->pass_moments, moments, film->n_local * 8u, hipMemcpyHostToDevice));
+        film_merge(*film, samples);
+    });
+}
+
+int pt_film_noise(const pt_film* film, float lum_floor, double target, pt_film_noise_stats* out, float* err_host,
+                  float* block_sum_host, float* block_max_host) {
+    return guarded([&] {
+        if (!film || !out) fail(PT_ERR_INVALID, "pt_film_noise: null argument");
+        pt_film_noise_stats st{};
+        film_noise(*film, lum_floor, target, st, err_host, block_sum_host, block_max_host);
+        *out = st;
+    });
+}
+
+int pt_film_resolve_device(const pt_film* film, int tonemap, void* d_rgb8, void* d_color, void* hip_stream) {
+    return guarded([&] {
+        film_check_resolve("pt_film_resolve_device", film, tonemap, d_rgb8, d_color);
+        HIP_CHECK(hipSetDevice(film->device));
+        film_resolve_launch(*film, tonemap, (uint8_t*)d_rgb8, (float*)d_color, (hipStream_t)hip_stream);
+    });
+}
+
+int pt_film_resolve(const pt_film* film, int tonemap, uint8_t* rgb8, float* color) {
+    return guarded([&] {
+        film_check_resolve("pt_film_resolve", film, tonemap, rgb8, color);
+        HIP_CHECK(hipSetDevice(film->device));
+        const size_t n = (size_t)film->n_local * 3u;
+        Staged<uint8_t> d_rgb(nullptr, n);
+        Staged<float> d_color(nullptr, n);
+        film_resolve_launch(*film, tonemap, rgb8 ? d_rgb.d : nullptr, color ? d_color.d : nullptr, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        if (rgb8) d_rgb.fetch(rgb8, n);
+        if (color) d_color.fetch(color, n);
+    });
+}
+
+int pt_film_render_until(pt_film* film, const pt_scene* scene, uint32_t first_pass_samples, uint64_t max_samples, float lum_floor,
+                         double target, pt_film_pass_fn on_pass, void* user, pt_film_noise_stats* out) {
+    return guarded([&] {
+        if (!film || !scene || !out) fail(PT_ERR_INVALID, "pt_film_render_until: null argument");
+        if (!film->has_profile) fail(PT_ERR_INVALID, "pt_film_render_until: a film made from planes has no profile to render with");
+        film_check_noise_args("pt_film_render_until", lum_floor, target);
+        if (first_pass_samples < 2u) fail(PT_ERR_INVALID, "pt_film_render_until: first_pass_samples must be >= 2 (a sample variance needs two)");
+        if (!film->passes && (uint64_t)first_pass_samples > max_samples)
+            fail(PT_ERR_INVALID, "pt_film_render_until: first_pass_samples %u exceeds max_samples %llu", first_pass_samples, (unsigned long long)max_samples);
+        if (scene->device != film->device)
+            fail(PT_ERR_INVALID, "pt_film_render_until: the scene is on device %d, the film on device %d", scene->device, film->device);
+        const uint64_t cap = std::min<uint64_t>(max_samples, (uint64_t)PT_FILM_MAX_SAMPLES);
+        pt_film_noise_stats st{};
+        bool measured = false;
+        for (;;) {
+            const uint64_t next = film->passes ? 2u * (uint64_t)film->last_pass_samples : (uint64_t)first_pass_samples;
+            if (film->samples + next > cap) break;
+            film_add_pass(*film, scene, (uint32_t)next);
+            film_noise(*film, lum_floor, target, st, nullptr, nullptr, nullptr);
+            measured = true;
+            if (on_pass) {
+                pt_film_info info;
+                film_fill_info(*film, info);
+                on_pass(&info, &st, user);
+            }
+            if (st.converged) break;
+        }
+        if (!measured) film_noise(*film, lum_floor, target, st, nullptr, nullptr, nullptr);   // (no pass fits: what the film holds)
+        *out = st;
+    });
+}
+
+int pt_film_kernel_times(const pt_film* film, float lum_floor, int with_err, uint32_t reps, float* ms_merge, float* ms_noise) {
+    return guarded([&] {
+        if (!film || !ms_merge || !ms_noise || !reps) fail(PT_ERR_INVALID, "pt_film_kernel_times: null argument");
+        if (film->samples < 2u) fail(PT_ERR_INVALID, "pt_film_kernel_times: the film's total must be >= 2");
+        film_check_noise_args("pt_film_kernel_times", lum_floor, 0.0);
+        HIP_CHECK(hipSetDevice(film->device));
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        struct Free {
+            hipEvent_t &a, &b;
+            ~Free() {
+                if (a) (void)hipEventDestroy(a);
+                if (b) (void)hipEventDestroy(b);
+            }
+        } guard{e0, e1};
+        HIP_CHECK(hipEventCreate(&e0));
+        HIP_CHECK(hipEventCreate(&e1));
+        for (uint32_t r = 0; r < 2u * reps; ++r) {
+            const bool merge = r < reps;
+            HIP_CHECK(hipEventRecord(e0, 0));
+            if (merge)   // the roles swapped: pass = pass + film (the pass buffers are scratch between passes)
+                hipLaunchKernelGGL(k_film_merge, dim3(film_merge_blocks(*film)), dim3(256), 0, 0, (float4*)film->pass_accum,
+                                   (const float4*)film->accum, film->stride_a / 4u, (float4*)film->pass_moments,
+                                   (const float4*)film->moments, film->stride_m / 4u);
+            else
+                film_noise_launch(*film, lum_floor, with_err != 0);
+            HIP_CHECK(hipEventRecord(e1, 0));
+            HIP_CHECK(hipEventSynchronize(e1));
+            HIP_CHECK(hipEventElapsedTime(merge ? &ms_merge[r] : &ms_noise[r - reps], e0, e1));
+        }
+        HIP_CHECK(hipGetLastError());
     });
 }
 

@@ -4,6 +4,7 @@
 //   path-tracer render <INPUT> [-o/--output <OUTPUT>] [-q/--quiet] [-v/--viewer]
 //                              [--debug-textures] [-p/--profile <PROFILE>] [--camera-path <CAMERAS>]
 //                              [--keyframes <FRAMES> [--light-mixer]]
+//                              [--noise-target <T> [--min-samples <N0>] [--max-samples <N>] [--noise-map <FILE.png>]]
 //       env OUTPUT (default render.png), env PROFILE
 //   path-tracer convert <INPUT> <OUTPUT>      (glTF 2.0 -> ISF, host/gltf_convert.cpp)
 //
@@ -18,8 +19,11 @@
 // --keyframes frames.json (a JSON array of frames, each with any of a camera, all lights, material factor edits: the scene
 // is uploaded once, frame i's edits are applied on top of frame i - 1's through pt_scene_set_camera / _set_lights /
 // _set_materials, and frame i is written as with --camera-path), --light-mixer (with --keyframes: frames whose only edit
-// is the colour of lights are mixed from the planes of one pt_lightmix capture instead of rendered).
+// is the colour of lights are mixed from the planes of one pt_lightmix capture instead of rendered),
+// --noise-target T (every frame is a progressive film, pt_film_render_until: passes of N0, 2 N0, 4 N0, ... samples until the
+// mean relative error of the pixels' mean luminance is <= T or the next pass would take the total above N).
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -65,6 +69,12 @@ void usage_render(FILE* f) {
           "      --denoise-iterations <N>  Filter passes of --denoise, pass i has step 2^i [0..8, default: the library's]\n"
           "      --denoise-variance   With --denoise: steer the filter's colour weight by the per-pixel variance of the frame's own\n"
           "                           samples (needs samples >= 2 in the profile)\n"
+          "      --noise-target <T>   Progressive film: add passes of N0, 2 N0, 4 N0, ... samples until the mean relative error of\n"
+          "                           the pixels' mean luminance is <= T or the next pass would exceed N samples in all (one\n"
+          "                           device, not with --light-mixer; -v prints one line per pass)\n"
+          "      --min-samples <N0>   First pass of --noise-target [>= 2, default: 8]\n"
+          "      --max-samples <N>    Sample budget of --noise-target [default: the profile's samples]\n"
+          "      --noise-map <FILE.png>  With --noise-target: write the per-pixel error as grey, white = 2 T and above\n"
           "  -h, --help               Print help\n",
           f);
 }
@@ -123,6 +133,20 @@ bool frame_pattern(const std::string& out, std::string& pre, int& width, std::st
     return true;
 }
 
+// --noise-target with -v: one line per pass
+void on_film_pass(const pt_film_info* info, const pt_film_noise_stats* noise, void* user) {
+    if (!*(const bool*)user) return;
+    fprintf(stderr, "film: pass %u: %u samples (%llu in all), noise %.6g, over target %.4f of the blocks\n", info->passes,
+            info->last_pass_samples, (unsigned long long)info->samples, noise->mean_error, noise->fraction_over);
+}
+
+// A whole non-negative decimal number that fits 32 bits, or die.
+uint32_t parse_u32(const std::string& v, const char* name) {
+    if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos)
+        die("error: invalid value '" + v + "' for '" + name + "': a whole number expected");
+    return (uint32_t)strtoul(v.c_str(), nullptr, 10);
+}
+
 void on_progress(uint32_t done, uint32_t total, void* user) {
     Progress* p = (Progress*)user;
     if (p->quiet) return;
@@ -140,6 +164,10 @@ int run_render(int argc, char** argv) {
     bool have_camera_path = false, have_keyframes = false;
     bool denoise = false, denoise_variance = false, light_mixer = false;
     int denoise_iterations = -1;
+    bool have_noise_target = false, have_min_samples = false, have_max_samples = false;
+    double noise_target = 0.0;
+    uint32_t min_samples = 8, max_samples = 0;
+    std::string noise_map;
     int device = 0;
     std::vector<int> devices;
     for (int i = 0; i < argc; ++i) {
@@ -179,6 +207,20 @@ int run_render(int argc, char** argv) {
                 die("error: invalid value '" + v + "' for '--denoise-iterations <N>': 0..8 expected");
             denoise_iterations = v[0] - '0';
         }
+        else if (a == "--noise-target" || a.rfind("--noise-target=", 0) == 0) {
+            std::string v = value("--noise-target <T>");
+            char* end = nullptr;
+            noise_target = strtod(v.c_str(), &end);
+            if (v.empty() || *end || !(noise_target > 0.0) || !std::isfinite(noise_target) || !((float)noise_target > 0.f))
+                die("error: invalid value '" + v + "' for '--noise-target <T>': a positive, finite number expected");
+            have_noise_target = true;
+        } else if (a == "--min-samples" || a.rfind("--min-samples=", 0) == 0) {
+            min_samples = parse_u32(value("--min-samples <N0>"), "--min-samples <N0>");
+            have_min_samples = true;
+        } else if (a == "--max-samples" || a.rfind("--max-samples=", 0) == 0) {
+            max_samples = parse_u32(value("--max-samples <N>"), "--max-samples <N>");
+            have_max_samples = true;
+        } else if (a == "--noise-map" || a.rfind("--noise-map=", 0) == 0) noise_map = value("--noise-map <FILE.png>");
         else if (a == "--camera-path" || a.rfind("--camera-path=", 0) == 0) {
             camera_path = value("--camera-path <CAMERAS>");
             have_camera_path = true;
@@ -225,11 +267,34 @@ int run_render(int argc, char** argv) {
     if (light_mixer && devices.size() > 1)
         die("error: the argument '--light-mixer' cannot be used with more than one device in '--devices <A,B,..>' (mixed frames "
             "are not gathered)");
+    if (!have_noise_target && (have_min_samples || have_max_samples || !noise_map.empty()))
+        die("error: '--min-samples <N0>', '--max-samples <N>' and '--noise-map <FILE.png>' need '--noise-target <T>'");
+    if (have_noise_target && light_mixer)
+        die("error: the argument '--noise-target <T>' cannot be used with '--light-mixer' (mixed frames have no samples to add to)");
+    if (have_noise_target && devices.size() > 1)
+        die("error: the argument '--noise-target <T>' cannot be used with more than one device in '--devices <A,B,..>' (the noise "
+            "figure is taken over the whole image on one device)");
+    if (have_noise_target && debug_textures) die("error: the argument '--noise-target <T>' cannot be used with '--debug-textures'");
+    if (!noise_map.empty()) {
+        std::string ext = noise_map.size() >= 4 ? noise_map.substr(noise_map.size() - 4) : "";
+        for (char& c : ext) c = (char)tolower(c);
+        if (ext != ".png") die("The image format could not be determined (only .png output is supported): " + noise_map);
+    }
 
     // Profile::load / Default (main.rs:33-36)
     pt_profile profile;
     if (pth_profile_load(have_profile ? profile_path.c_str() : nullptr, &profile) != PT_OK) die(pth_last_error());
-    if (denoise_variance && profile.samples < 2)
+    if (have_noise_target) {
+        if (!have_max_samples) max_samples = profile.samples;
+        if (min_samples < 2)
+            die("error: invalid value '" + std::to_string(min_samples) + "' for '--min-samples <N0>': at least 2 (a sample variance needs two samples)");
+        if (min_samples > max_samples)
+            die("error: '--min-samples <N0>' (" + std::to_string(min_samples) + ") exceeds the sample budget (" + std::to_string(max_samples) +
+                ": '--max-samples <N>' or the profile's samples)");
+        if (max_samples > (uint32_t)PT_FILM_MAX_SAMPLES)
+            die("error: invalid value '" + std::to_string(max_samples) + "' for '--max-samples <N>': at most " + std::to_string((uint32_t)PT_FILM_MAX_SAMPLES));
+    }
+    if (denoise_variance && !have_noise_target && profile.samples < 2)
         die("error: '--denoise-variance' needs a profile with samples >= 2 (a sample variance of " + std::to_string(profile.samples) +
             " sample does not exist)");
 
@@ -485,6 +550,51 @@ int run_render(int argc, char** argv) {
                pth_lights_differ_in_color_only(edits[f - 1].light.data(), (uint32_t)edits[f - 1].light.size(), edits[f].light.data(),
                                                (uint32_t)edits[f].light.size());
     };
+    // --noise-target: one film for the run; every frame starts it from zero passes
+    pt_film* film = nullptr;
+    if (have_noise_target && pt_film_create(device, &profile, &opts, &film) != PT_OK) die(pt_last_error());
+    const size_t n_pixels = (size_t)profile.width * profile.height;
+    auto render_film = [&](size_t f) {
+        if (f > 0 && pt_film_reset(film) != PT_OK) die(pt_last_error());
+        pt_film_noise_stats noise{};
+        if (pt_film_render_until(film, scene, min_samples, max_samples, PT_FILM_DEFAULT_LUM_FLOOR, noise_target, on_film_pass, &viewer,
+                                 &noise) != PT_OK)
+            die(pt_last_error());
+        pt_film_info info{};
+        if (pt_film_get_info(film, &info) != PT_OK) die(pt_last_error());
+        if (denoise) {   // the film's planes through the filter, samples = the film's total
+            std::vector<float> acc(n_pixels * 3), mom(n_pixels * 2), guides(n_pixels * PT_GUIDE_FLOATS);
+            if (pt_film_read(film, acc.data(), mom.data()) != PT_OK || pt_render_guides(scene, profile.width, profile.height, guides.data()) != PT_OK)
+                die(pt_last_error());
+            if ((denoise_variance ? pt_denoise_var(device, profile.width, profile.height, (uint32_t)info.samples, &dn, acc.data(), mom.data(),
+                                                   guides.data(), nullptr, rgb.data())
+                                  : pt_denoise(device, profile.width, profile.height, (uint32_t)info.samples, &dn, acc.data(), guides.data(),
+                                               nullptr, rgb.data())) != PT_OK)
+                die(pt_last_error());
+        } else if (pt_film_resolve(film, profile.tonemap, rgb.data(), nullptr) != PT_OK) {
+            die(pt_last_error());
+        }
+        if (!noise_map.empty()) {   // grey = as_u8(min(1, err / (2 T)) * 255)
+            std::vector<float> err(n_pixels);
+            if (pt_film_noise(film, PT_FILM_DEFAULT_LUM_FLOOR, noise_target, &noise, err.data(), nullptr, nullptr) != PT_OK) die(pt_last_error());
+            std::vector<uint8_t> grey(n_pixels * 3);
+            const float full = 2.0f * (float)noise_target;
+            for (size_t i = 0; i < n_pixels; ++i) {
+                const float v = fminf(1.0f, err[i] / full) * 255.0f;
+                const uint8_t g = !(v == v) || v <= 0.f ? 0 : (v >= 255.f ? 255 : (uint8_t)v);
+                grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = g;
+            }
+            std::string name = noise_map;
+            if (n_frames > 1) {   // one map per frame: the frame index goes in front of the extension
+                char num[32];
+                snprintf(num, sizeof num, "_%zu", f);
+                name = noise_map.substr(0, noise_map.size() - 4) + num + noise_map.substr(noise_map.size() - 4);
+            }
+            if (pth_png_write_rgb8(name.c_str(), profile.width, profile.height, grey.data()) != PT_OK) die(pth_last_error());
+        }
+        fprintf(stderr, "film: %u passes, %llu samples, noise %.6g, %s\n", info.passes, (unsigned long long)info.samples, noise.mean_error,
+                noise.converged ? "converged" : "max samples");
+    };
     pt_lightmix* mix = nullptr;
     bool mixer_on = light_mixer;
     size_t lights_of = 0, captures = 0, mixed = 0, rendered = 0;
@@ -515,6 +625,9 @@ int run_render(int argc, char** argv) {
             for (const pt_light& l : edits[f].light) colors.insert(colors.end(), l.color, l.color + 3);
             if (pt_lightmix_apply(mix, colors.data(), profile.tonemap, rgb.data(), nullptr) != PT_OK) die(pt_last_error());
             ++mixed;
+        } else if (film) {
+            render_film(f);
+            ++rendered;
         } else {
             if ((denoise_variance ? pt_render_denoised_var(scene, &profile, &opts, &dn, rgb.data(), nullptr)
                  : denoise        ? pt_render_denoised(scene, &profile, &opts, &dn, rgb.data(), nullptr)
@@ -536,6 +649,7 @@ int run_render(int argc, char** argv) {
     }
 
     if (mix) pt_lightmix_destroy(mix);
+    if (film) pt_film_destroy(film);
     if (light_mixer) fprintf(stderr, "light mixer: %zu captures, %zu mixed frames, %zu rendered frames\n", captures, mixed, rendered);
 
     if (stats) {

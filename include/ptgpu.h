@@ -594,6 +594,118 @@ int  pt_film_render_until(pt_film* film, const pt_scene* scene, uint32_t first_p
 int  pt_film_kernel_times(const pt_film* film, float lum_floor, int with_err, uint32_t reps, float* ms_merge, float* ms_noise);
 
 /* ------------------------------------------------------------------ */
+/* tile-list frames and the adaptive film                  */
+/* ------------------------------------------------------------------ */
+
+/* A tile-list frame renders the listed tiles of the frame (profile, opts) and nothing else - a region re-render, and what an
+ * adaptive film's later passes are made of.
+ *   tiles     n_tiles global tile numbers ty * tiles_x + tx of the tiling opts.tile_w x opts.tile_h (0: 32; the rules of
+ *             pt_opts), tiles_x = ceil(width / tile_w); STRICTLY ASCENDING.
+ *   outputs   packed: the tiles one after the other in list order, each row-major and clipped to the image - the packed order
+ *             of a shard.  pt_tiles_pixel_count gives the number of packed pixels (0 for a list or options that are refused),
+ *             pt_tiles_pixel_map (a host helper, no GPU) the global index x + y * width of every packed pixel.
+ *             rgb8 [n x 3 u8], accum [n x 3 f32], moments [n x 2 f32]; each may be NULL, not all of them.
+ *   contract  every packed pixel's accum, moments and rgb8 equal, bit for bit, those of the same global pixel in
+ *             pt_render_moments(scene, profile, opts) of the whole frame: the seed of a sample depends on the GLOBAL pixel index
+ *             and profile.samples only.  This holds for the default pipeline and for PT_FLAG_NO_GRIDS; with PT_FLAG_MEGAKERNEL for
+ *             accum and rgb8 (moments != NULL there: PT_ERR_UNSUPPORTED, as in pt_render_moments).
+ *   refusals  PT_ERR_INVALID before any device work, the outputs untouched: a null list or n_tiles == 0, a list that is not
+ *             strictly ascending, a tile number >= tiles_x * tiles_y, shard_count > 1, anything pt_render refuses.
+ * The host form blocks.  The device form copies the list before it returns and is asynchronous on hip_stream after that - but,
+ * UNLIKE pt_render_device, it may wait for the whole device and allocate when it is entered (the list's table is rewritten in
+ * place).  A tile-list frame leaves the scene's steady state alone: it is a first frame every time (unplanned, no frame cache
+ * read, written, keyed or counted), and the whole frames before and after it run what they would have run without it. */
+uint64_t pt_tiles_pixel_count(const pt_profile* profile, const pt_opts* opts, const uint32_t* tiles, uint32_t n_tiles);
+int  pt_tiles_pixel_map(const pt_profile* profile, const pt_opts* opts, const uint32_t* tiles, uint32_t n_tiles, uint32_t* out);
+int  pt_render_tiles(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, const uint32_t* tiles, uint32_t n_tiles,
+                     uint8_t* rgb8, float* accum, float* moments);   /* host */
+int  pt_render_tiles_device(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, const uint32_t* tiles,
+                            uint32_t n_tiles, void* d_rgb8, void* d_accum, void* d_moments, void* hip_stream);
+
+/* The adaptive film.  A film that has a profile and shard_count <= 1 may take TILE PASSES: a pass of `samples` samples over a
+ * list of tiles of the film's own tiling (its opts' tile size).  The first tile pass allocates a count plane - n_local u32,
+ * 256-byte aligned, filled with the film's uniform total - and the film is NON-UNIFORM from then on, until pt_film_reset.  A film
+ * that never takes a tile pass allocates nothing new, and every call above runs on it what it ran before.
+ *
+ * The rule for `samples` is the film's: at least twice the last pass's (whole or tile), info.samples + samples at most
+ * PT_FILM_MAX_SAMPLES - pixel i of a pass of a samples uses the seeds [i*a, i*a + a) whether or not its neighbours are rendered.
+ * info.samples of a non-uniform film is the LARGEST count (what a pixel has if it took every pass).
+ *
+ * pt_film_add_tile_pass renders the tile-list frame (pt_render_tiles_device) into the pass buffers, waits for it and only then
+ * merges: per pixel of the listed tiles   film = film + pass   on the 3 + 2 floats (one f32 addition each), count += samples.
+ * No other pixel is read or written.  A failure before the merge leaves the film as it was.  pt_film_add_tile_planes merges a
+ * pass rendered elsewhere (host planes in the packed order of pt_render_tiles for the list).  PT_ERR_INVALID before any device
+ * work: what pt_film_add_pass and pt_render_tiles refuse, a film without a profile, a sharded film.
+ * pt_film_read_counts: every pixel's count (a uniform film: its total everywhere).
+ *
+ * On a non-uniform film: pt_film_add_pass adds a whole frame - the tile pass that lists every tile; pt_film_read is unchanged;
+ * pt_film_reset makes the film uniform (and empty) again; pt_film_resolve / _device give color = accum / (float)count[p] and
+ * rgb8 = pt_render's post-processing with samples = count[p] (PT_ERR_INVALID while some tile holds no samples);
+ * pt_film_noise, pt_film_add_planes, pt_film_planes_device (and pt_film_render_until, pt_film_kernel_times, which are made of
+ * them) are PT_ERR_UNSUPPORTED and change nothing: their contracts assume one n.
+ *
+ * pt_film_tile_noise (uniform films too; the film needs a profile): all f32, one IEEE operation per step in this order,
+ * uncontracted, IEEE divide and sqrt (tests/film_adaptive_model.py restates it bit for bit):
+ *   per pixel p   pt_film_noise's err with n = count[p] (the uniform total on a uniform film)
+ *   per tile t    of clipped size cw x ch, its pixels numbered j = y * cw + x, P = cw * ch:
+ *                 for i in 0 .. 255:  v[i] = 0.f;  for j = i; j < P; j += 256:  v[i] = v[i] + err_j
+ *                 for stride = 128, 64, 32, 16, 8, 4, 2, 1:  for i < stride:  v[i] = v[i] + v[i + stride]
+ *                 tile_sum[t] = v[0];  tile_max[t]: the same steps with max in place of + (the largest err of the tile)
+ *                 (a full 16 x 16 tile: pt_film_noise's block, addition for addition)
+ *   on the host, in f64, t ascending:   mean_t = (double)tile_sum[t] / P;  mean_error = (sum of (double)tile_sum[t]) / n_local;
+ *                 max_tile_error = the largest mean_t;  over_tiles = tiles with mean_t > target;  converged = no such tile;
+ *                 samples = the largest count;  pixel_samples = the sum of every pixel's count
+ * err_host (n_local f32, image order), tile_sum_host and tile_max_host (n_tiles f32 each) may be NULL.  The tile arrays are
+ * allocated on first use.  PT_ERR_INVALID: what pt_film_noise refuses, a pixel with fewer than 2 samples, no profile, shards.
+ *
+ * pt_film_render_until_adaptive.  Loop: (1) the next pass has first_pass_samples (>= 2) on an empty film, 2 * last_pass_samples
+ * otherwise; (2) stop for budget if info.samples + that would exceed max_samples (or PT_FILM_MAX_SAMPLES); (3) render the pass
+ * over the active set - EVERY tile while the film is empty or info.samples < uniform_samples; a pass over every tile is
+ * pt_film_add_pass, so the film stays uniform for as long as that holds; (4) pt_film_tile_noise(lum_floor, target); (5) the
+ * candidates are the tiles with mean_t > target; (6) the next active set is the candidates, with dilate = 1 grown by their 8
+ * neighbours; (7) on_pass(info, noise, user) if set - noise.mean_error and .max_block_error are the tile figures, .fraction_over
+ * = over_tiles / n_tiles, .n_blocks = n_tiles, .converged = no candidate; (8) stop as converged when there is no candidate.
+ * out = the last tile statistics, out->active_tiles the tiles of the pass just rendered.  The selection is a pure function of the
+ * film's current planes: a tile that was dropped comes back only through dilation.  A film that already has passes (and
+ * info.samples >= uniform_samples) starts with step 4.  max_samples bounds the largest per-pixel count.
+ * uniform_samples (default 24) and dilate (default 1) are design choices, not measured optima: the variance of a few samples
+ * underestimates the error, and a hard tile edge in the sample density can show in the image. */
+typedef struct pt_film_tile_stats {
+    double mean_error;        /* sum of the tile sums / n_local                                    */
+    double max_tile_error;    /* largest tile_sum[t] / pixels of tile t                            */
+    uint64_t samples;         /* the largest per-pixel count                                       */
+    uint64_t pixel_samples;   /* the sum of every pixel's count                                    */
+    uint32_t n_tiles, over_tiles /* mean_t > target */, active_tiles /* pt_film_render_until_adaptive: of the last pass */,
+             converged /* over_tiles == 0 */;
+} pt_film_tile_stats;
+typedef struct pt_film_adaptive_info {
+    uint32_t uniform /* 1: no tile pass since the film was made or reset */, tile_w, tile_h, tiles_x, tiles_y, n_tiles, tile_passes,
+             last_pass_tiles /* tiles of the last pass (n_tiles: a whole frame; 0: no pass yet) */;
+    uint64_t min_samples, max_samples /* the smallest and the largest per-pixel count */, pixel_samples, device_bytes;
+} pt_film_adaptive_info;
+typedef struct pt_film_adaptive_params {
+    double target;
+    uint64_t max_samples;
+    float lum_floor;
+    uint32_t first_pass_samples, uniform_samples, dilate /* 0 or 1 */;
+} pt_film_adaptive_params;
+void pt_film_adaptive_params_default(pt_film_adaptive_params* params);   /* floor 0.01, target 0.02, first 8, uniform 24, dilate 1, max 512 */
+int  pt_film_add_tile_pass(pt_film* film, const pt_scene* scene, uint32_t samples, const uint32_t* tiles, uint32_t n_tiles);
+int  pt_film_add_tile_planes(pt_film* film, uint32_t samples, const uint32_t* tiles, uint32_t n_tiles,
+                             const float* accum /* host, packed */, const float* moments /* host, packed */);
+int  pt_film_read_counts(const pt_film* film, uint32_t* counts /* host, n_local */);
+int  pt_film_tile_noise(const pt_film* film, float lum_floor, double target, pt_film_tile_stats* out, float* err_host,
+                        float* tile_sum_host, float* tile_max_host);
+int  pt_film_get_adaptive_info(const pt_film* film, pt_film_adaptive_info* out);
+int  pt_film_render_until_adaptive(pt_film* film, const pt_scene* scene, const pt_film_adaptive_params* params,
+                                   pt_film_pass_fn on_pass, void* user, pt_film_tile_stats* out);
+/* Measurement, like pt_film_kernel_times, on a non-uniform film whose every pixel has >= 2 samples: ms_merge[r] =
+ * k_film_merge_tiles over every tile with a pass of zeros and zero samples (the pass buffers are scratch; the film's planes and
+ * counts keep their values), ms_noise[r] = k_film_tile_noise with the err plane, ms_resolve[r] = the u8 resolve with counts. */
+int  pt_film_adaptive_kernel_times(pt_film* film, float lum_floor, int tonemap, uint32_t reps, float* ms_merge, float* ms_noise,
+                                   float* ms_resolve);
+
+/* ------------------------------------------------------------------ */
 /* measurement                                                         */
 /* ------------------------------------------------------------------ */
 

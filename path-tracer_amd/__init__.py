@@ -165,6 +165,41 @@ class FilmNoise(C.Structure):
 FILM_PASS_FN = C.CFUNCTYPE(None, C.POINTER(FilmInfo), C.POINTER(FilmNoise), C.c_void_p)
 
 
+class FilmTileStats(C.Structure):
+    """pt_film_tile_stats: what pt_film_tile_noise makes of the film's moments and counts."""
+    _fields_ = [("mean_error", C.c_double), ("max_tile_error", C.c_double), ("samples", C.c_uint64),
+                ("pixel_samples", C.c_uint64), ("n_tiles", C.c_uint32), ("over_tiles", C.c_uint32),
+                ("active_tiles", C.c_uint32), ("converged", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class FilmAdaptiveInfo(C.Structure):
+    """pt_film_adaptive_info."""
+    _fields_ = [("uniform", C.c_uint32), ("tile_w", C.c_uint32), ("tile_h", C.c_uint32), ("tiles_x", C.c_uint32),
+                ("tiles_y", C.c_uint32), ("n_tiles", C.c_uint32), ("tile_passes", C.c_uint32), ("last_pass_tiles", C.c_uint32),
+                ("min_samples", C.c_uint64), ("max_samples", C.c_uint64), ("pixel_samples", C.c_uint64),
+                ("device_bytes", C.c_uint64)]
+
+
+class FilmAdaptiveParams(C.Structure):
+    """pt_film_adaptive_params."""
+    _fields_ = [("target", C.c_double), ("max_samples", C.c_uint64), ("lum_floor", C.c_float),
+                ("first_pass_samples", C.c_uint32), ("uniform_samples", C.c_uint32), ("dilate", C.c_uint32)]
+
+    @classmethod
+    def default(cls, **changes):
+        """pt_film_adaptive_params_default, with fields replaced by keyword."""
+        p = cls()
+        gpu_lib().pt_film_adaptive_params_default(C.byref(p))
+        for k, v in changes.items():
+            if k not in dict(cls._fields_):
+                raise TypeError(f"pt_film_adaptive_params has no field {k!r}")
+            setattr(p, k, v)
+        return p
+
+
 class Hit(C.Structure):
     _fields_ = [("prim", C.c_int32), ("flags", C.c_int32), ("dist", C.c_float), ("u", C.c_float),
                 ("v", C.c_float)]
@@ -269,7 +304,11 @@ GPU_SYMBOLS = ["pt_scene_create", "pt_scene_destroy", "pt_scene_set_camera", "pt
                "pt_lightmix_basis", "pt_lightmix_apply", "pt_lightmix_apply_device",
                "pt_film_create", "pt_film_create_from_planes", "pt_film_destroy", "pt_film_reset", "pt_film_get_info",
                "pt_film_read", "pt_film_planes_device", "pt_film_add_pass", "pt_film_add_planes", "pt_film_noise", "pt_film_resolve",
-               "pt_film_resolve_device", "pt_film_render_until", "pt_film_kernel_times"]
+               "pt_film_resolve_device", "pt_film_render_until", "pt_film_kernel_times",
+               "pt_tiles_pixel_count", "pt_tiles_pixel_map", "pt_render_tiles", "pt_render_tiles_device",
+               "pt_film_add_tile_pass", "pt_film_add_tile_planes", "pt_film_read_counts", "pt_film_tile_noise",
+               "pt_film_get_adaptive_info", "pt_film_render_until_adaptive", "pt_film_adaptive_params_default",
+               "pt_film_adaptive_kernel_times"]
 
 
 def host_lib():
@@ -446,6 +485,22 @@ def gpu_lib():
             L.pt_film_render_until.argtypes = [vp, vp, C.c_uint32, C.c_uint64, C.c_float, C.c_double, FILM_PASS_FN, vp,
                                                C.POINTER(FilmNoise)]
             L.pt_film_kernel_times.argtypes = [vp, C.c_float, C.c_int, C.c_uint32, vp, vp]
+        if hasattr(L, "pt_render_tiles"):   # (an A/B library of an earlier commit has no tile-list frames, no adaptive film)
+            L.pt_tiles_pixel_count.argtypes = [C.POINTER(Profile), C.POINTER(Opts), vp, C.c_uint32]
+            L.pt_tiles_pixel_count.restype = C.c_uint64
+            L.pt_tiles_pixel_map.argtypes = [C.POINTER(Profile), C.POINTER(Opts), vp, C.c_uint32, vp]
+            L.pt_render_tiles.argtypes = [vp, C.POINTER(Profile), C.POINTER(Opts), vp, C.c_uint32, vp, vp, vp]
+            L.pt_render_tiles_device.argtypes = [vp, C.POINTER(Profile), C.POINTER(Opts), vp, C.c_uint32, vp, vp, vp, vp]
+            L.pt_film_add_tile_pass.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32]
+            L.pt_film_add_tile_planes.argtypes = [vp, C.c_uint32, vp, C.c_uint32, vp, vp]
+            L.pt_film_read_counts.argtypes = [vp, vp]
+            L.pt_film_tile_noise.argtypes = [vp, C.c_float, C.c_double, C.POINTER(FilmTileStats), vp, vp, vp]
+            L.pt_film_get_adaptive_info.argtypes = [vp, C.POINTER(FilmAdaptiveInfo)]
+            L.pt_film_render_until_adaptive.argtypes = [vp, vp, C.POINTER(FilmAdaptiveParams), FILM_PASS_FN, vp,
+                                                        C.POINTER(FilmTileStats)]
+            L.pt_film_adaptive_params_default.argtypes = [C.POINTER(FilmAdaptiveParams)]
+            L.pt_film_adaptive_params_default.restype = None
+            L.pt_film_adaptive_kernel_times.argtypes = [vp, C.c_float, C.c_int, C.c_uint32, vp, vp, vp]
         L.pt_last_error.restype = C.c_char_p
         L.pt_version.restype = C.c_char_p
         _gpu = L
@@ -917,6 +972,30 @@ class GpuScene:
     def render_moments_device(self, profile, opts, d_rgb8, d_accum, d_moments, stream=0):
         check_gpu(self.lib.pt_render_moments_device(self.handle, C.byref(profile), C.byref(opts), d_rgb8, d_accum, d_moments, stream))
 
+    def render_tiles(self, profile, tiles, opts=None, want_moments=True):
+        """pt_render_tiles: (rgb8 [n, 3] uint8, accum [n, 3] float32, moments [n, 2] float32 or None) of the listed tiles
+        (global tile numbers, strictly ascending), packed in list order - tiles_pixel_map gives every packed pixel's
+        global index."""
+        import numpy as np
+        opts = opts or Opts.make()
+        t = _tile_list(tiles)
+        n = int(self.lib.pt_tiles_pixel_count(C.byref(profile), C.byref(opts), t.ctypes.data, len(t)))
+        rgb = np.empty((n, 3), np.uint8)
+        acc = np.empty((n, 3), np.float32)
+        mom = np.empty((n, 2), np.float32) if want_moments else None
+        check_gpu(self.lib.pt_render_tiles(self.handle, C.byref(profile), C.byref(opts), t.ctypes.data, len(t), rgb.ctypes.data,
+                                           acc.ctypes.data, mom.ctypes.data if want_moments else None))
+        return rgb, acc, mom
+
+    def render_tiles_device(self, profile, opts, tiles, d_rgb8, d_accum, d_moments, stream=0):
+        """pt_render_tiles_device: device pointers (any may be 0 / None, not all)."""
+        t = _tile_list(tiles)
+        check_gpu(self.lib.pt_render_tiles_device(self.handle, C.byref(profile), C.byref(opts), t.ctypes.data, len(t),
+                                                  d_rgb8 or None, d_accum or None, d_moments or None, stream))
+
+    tiles_pixel_count = staticmethod(lambda profile, tiles, opts=None: tiles_pixel_count(profile, tiles, opts))
+    tiles_pixel_map = staticmethod(lambda profile, tiles, opts=None: tiles_pixel_map(profile, tiles, opts))
+
     def render_samples(self, profile, opts=None):
         """pt_render_samples (test hook): [samples, n, 3] float32, the radiance of every sample of every packed pixel."""
         import numpy as np
@@ -1297,6 +1376,75 @@ class Film:
     def reset(self):
         check_gpu(self.lib.pt_film_reset(self.handle))
 
+    # ---- the adaptive film
+    def add_tile_pass(self, scene, samples, tiles):
+        """pt_film_add_tile_pass: a pass of `samples` samples over the listed tiles (global numbers, strictly ascending)."""
+        t = _tile_list(tiles)
+        check_gpu(self.lib.pt_film_add_tile_pass(self.handle, scene.handle, samples, t.ctypes.data, len(t)))
+
+    def add_tile_planes(self, accum, moments, samples, tiles):
+        """pt_film_add_tile_planes: a tile pass rendered elsewhere (GpuScene.render_tiles' packed accum and moments)."""
+        import numpy as np
+        t = _tile_list(tiles)
+        accum = np.ascontiguousarray(accum, np.float32)
+        moments = np.ascontiguousarray(moments, np.float32)
+        if accum.ndim != 2 or accum.shape[1] != 3 or moments.shape != (accum.shape[0], 2):
+            raise PtError(PT_ERR_INVALID, "Film.add_tile_planes: accum must be [n, 3] and moments [n, 2]")
+        check_gpu(self.lib.pt_film_add_tile_planes(self.handle, samples, t.ctypes.data, len(t), accum.ctypes.data,
+                                                   moments.ctypes.data))
+
+    def read_counts(self):
+        """pt_film_read_counts: every pixel's sample count [n_local] uint32."""
+        import numpy as np
+        counts = np.empty(int(self.info.n_local), np.uint32)
+        check_gpu(self.lib.pt_film_read_counts(self.handle, counts.ctypes.data))
+        return counts
+
+    @property
+    def adaptive_info(self):
+        i = FilmAdaptiveInfo()
+        check_gpu(self.lib.pt_film_get_adaptive_info(self.handle, C.byref(i)))
+        return i
+
+    def tile_noise(self, target, lum_floor=PT_FILM_DEFAULT_LUM_FLOOR, want_planes=False):
+        """pt_film_tile_noise: FilmTileStats; with want_planes (FilmTileStats, err [n_local], tile_sum [n_tiles],
+        tile_max [n_tiles])."""
+        import numpy as np
+        out = FilmTileStats()
+        if not want_planes:
+            check_gpu(self.lib.pt_film_tile_noise(self.handle, lum_floor, target, C.byref(out), None, None, None))
+            return out
+        n, nt = int(self.info.n_local), int(self.adaptive_info.n_tiles)
+        err, tsum, tmax = np.empty(n, np.float32), np.empty(nt, np.float32), np.empty(nt, np.float32)
+        check_gpu(self.lib.pt_film_tile_noise(self.handle, lum_floor, target, C.byref(out), err.ctypes.data, tsum.ctypes.data,
+                                              tmax.ctypes.data))
+        return out, err, tsum, tmax
+
+    def render_until_adaptive(self, scene, params, on_pass=None):
+        """pt_film_render_until_adaptive: doubling passes, the later ones over the tiles that are still above the target;
+        on_pass(FilmInfo, FilmNoise) after every pass (copies).  Returns the last FilmTileStats."""
+        out = FilmTileStats()
+        failure = []
+
+        def trampoline(info, noise, _user):
+            try:
+                on_pass(_copy(FilmInfo, info.contents), _copy(FilmNoise, noise.contents))
+            except BaseException as e:   # (an exception cannot cross the C frames: raised after the call)
+                failure.append(e)
+        cb = FILM_PASS_FN(trampoline) if on_pass is not None else C.cast(None, FILM_PASS_FN)
+        check_gpu(self.lib.pt_film_render_until_adaptive(self.handle, scene.handle, C.byref(params), cb, None, C.byref(out)))
+        if failure:
+            raise failure[0]
+        return out
+
+    def adaptive_kernel_times(self, lum_floor=PT_FILM_DEFAULT_LUM_FLOOR, tonemap=None, reps=20):
+        """pt_film_adaptive_kernel_times: ms of (k_film_merge_tiles, k_film_tile_noise, k_film_post_counts), [reps] each."""
+        import numpy as np
+        a, b, c = (np.zeros(reps, np.float32) for _ in range(3))
+        check_gpu(self.lib.pt_film_adaptive_kernel_times(self.handle, lum_floor, self._tonemap(tonemap), reps, a.ctypes.data,
+                                                         b.ctypes.data, c.ctypes.data))
+        return a, b, c
+
     def close(self):
         if self.handle:
             self.lib.pt_film_destroy(self.handle)
@@ -1349,6 +1497,29 @@ def denoise_var(width, height, samples, params, accum, moments, guides, device=0
 
 def denoise_var_scratch_bytes(width, height):
     return int(gpu_lib().pt_denoise_var_scratch_bytes(width, height))
+
+
+def _tile_list(tiles):
+    import numpy as np
+    return np.ascontiguousarray(tiles, np.uint32).reshape(-1)
+
+
+def tiles_pixel_count(profile, tiles, opts=None):
+    """pt_tiles_pixel_count: packed pixels of a tile list (0: a list or options that are refused)."""
+    opts = opts or Opts.make()
+    t = _tile_list(tiles)
+    return int(gpu_lib().pt_tiles_pixel_count(C.byref(profile), C.byref(opts), t.ctypes.data, len(t)))
+
+
+def tiles_pixel_map(profile, tiles, opts=None):
+    """pt_tiles_pixel_map: the global pixel index of every packed pixel of a tile list (no GPU needed)."""
+    import numpy as np
+    opts = opts or Opts.make()
+    t = _tile_list(tiles)
+    lib = gpu_lib()
+    out = np.empty(int(lib.pt_tiles_pixel_count(C.byref(profile), C.byref(opts), t.ctypes.data, len(t))), np.uint32)
+    check_gpu(lib.pt_tiles_pixel_map(C.byref(profile), C.byref(opts), t.ctypes.data, len(t), out.ctypes.data))
+    return out
 
 
 def local_pixel_map(profile, opts):

@@ -6,6 +6,14 @@
 //                  256 packed pixels
 //   k_film_color   color = accum / (float)n (pt_film_resolve's f32 output; the u8 output is k_postprocess's)
 //
+// The adaptive film: a film that has taken a pass over a list of tiles keeps a sample count per pixel.
+//
+//   k_film_merge_tiles     film = film + pass for the pixels of the listed tiles (the pass planes are packed in list order),
+//                          count = count + samples; no other pixel is read or written
+//   k_film_tile_noise      k_film_noise's figure with n = the pixel's own count, summed over every TILE of the image
+//   k_film_color_counts    color = accum / (float)count[p]
+//   k_film_post_counts     k_postprocess with samples = count[p]
+//
 // The planes are streamed as flat floats.  Every plane starts on a 256-byte boundary and its stride is a multiple of 64
 // floats (the padding is zero and stays zero: 0 + 0), so k_film_merge loads and stores whole float4s up to the padded end -
 // the planes are the film's own, no caller's buffer ends inside one.
@@ -84,4 +92,112 @@ __global__ __launch_bounds__(256) void k_film_color(const float* __restrict__ ac
                                                     uint64_t n_floats, float samples) {
     for (uint64_t k = (uint64_t)blockIdx.x * 256u + threadIdx.x; k < n_floats; k += (uint64_t)gridDim.x * 256u)
         color[k] = accum[k] / samples;
+}
+
+// ------------------------------------------------------------------ adaptive film
+// The tiling of an unsharded film: tile k = ty * tiles_x + tx covers the pixels [tx tile_w, ..) x [ty tile_h, ..) clipped to the
+// image - cw x ch of them, numbered j = y * cw + x.  The film's planes are in image order (p = x + y * width).
+struct FilmTiling {
+    uint32_t width, height, tile_w, tile_h, tiles_x;
+};
+struct FilmTile {
+    uint32_t x0, y0, cw, ch;
+    __device__ __forceinline__ uint32_t pixel(uint32_t j, uint32_t width) const { return (y0 + j / cw) * width + x0 + j % cw; }
+};
+__device__ __forceinline__ FilmTile film_tile(const FilmTiling& T, uint32_t k) {
+    FilmTile t;
+    t.x0 = (k % T.tiles_x) * T.tile_w;
+    t.y0 = (k / T.tiles_x) * T.tile_h;
+    t.cw = min(T.tile_w, T.width - t.x0);
+    t.ch = min(T.tile_h, T.height - t.y0);
+    return t;
+}
+
+// One workgroup per listed tile.  table: n_list + 1 packed offsets, then the n_list tile numbers (the table of the frame that
+// rendered the pass).  Pixel j of listed tile lt is packed pixel table[lt] + j of the pass planes.
+__global__ __launch_bounds__(256) void k_film_merge_tiles(const float* __restrict__ pass_accum, const float2* __restrict__ pass_mom,
+                                                          const uint32_t* __restrict__ table, uint32_t n_list, FilmTiling T,
+                                                          float* __restrict__ film_accum, float2* __restrict__ film_mom,
+                                                          uint32_t* __restrict__ count, uint32_t samples) {
+    const uint32_t lt = blockIdx.x;
+    const FilmTile t = film_tile(T, table[n_list + 1u + lt]);
+    const uint32_t off = table[lt], P = t.cw * t.ch;
+    for (uint32_t j = threadIdx.x; j < P; j += 256u) {
+        const size_t p = t.pixel(j, T.width), q = (size_t)off + j;
+        film_accum[3 * p] = film_accum[3 * p] + pass_accum[3 * q];
+        film_accum[3 * p + 1] = film_accum[3 * p + 1] + pass_accum[3 * q + 1];
+        film_accum[3 * p + 2] = film_accum[3 * p + 2] + pass_accum[3 * q + 2];
+        const float2 f = film_mom[p], m = pass_mom[q];
+        film_mom[p] = make_float2(f.x + m.x, f.y + m.y);
+        count[p] += samples;
+    }
+}
+
+// One workgroup per tile of the image.  n of pixel p: count[p], or the film's uniform total `n_uniform` where count is null.
+// Thread i adds the errors of the tile's pixels i, i + 256, ... to 0.f in that order; then k_film_noise's tree.  err (image
+// order) may be null.
+__global__ __launch_bounds__(256) void k_film_tile_noise(const float2* __restrict__ moments, const uint32_t* __restrict__ count,
+                                                         uint32_t n_uniform, FilmTiling T, float lum_floor, float* __restrict__ err,
+                                                         float* __restrict__ tile_sum, float* __restrict__ tile_max) {
+    __shared__ float vs[256];
+    __shared__ float vm[256];
+    const uint32_t i = threadIdx.x;
+    const FilmTile t = film_tile(T, blockIdx.x);
+    const uint32_t P = t.cw * t.ch;
+    float v = 0.f, w = 0.f;
+    for (uint32_t j = i; j < P; j += 256u) {
+        const size_t p = t.pixel(j, T.width);
+        const uint32_t n = count != nullptr ? count[p] : n_uniform;
+        const float2 m = moments[p];
+        const float N = (float)n;
+        const float mu = m.x / N;
+        const float e2 = m.y / N;
+        const float s2 = max_rs(0.f, e2 - mu * mu);
+        const float vL = s2 / (float)(n - 1u);
+        const float se = sqrtf(vL);
+        const float den = max_rs(mu, lum_floor);
+        const float e = se / den;
+        if (err != nullptr) err[p] = e;
+        v = v + e;
+        w = max_rs(w, e);
+    }
+    vs[i] = v;
+    vm[i] = w;
+    __syncthreads();
+    if (i < 128u) {
+        vs[i] = vs[i] + vs[i + 128u];
+        vm[i] = max_rs(vm[i], vm[i + 128u]);
+    }
+    __syncthreads();
+    if (i < 64u) {   // wave 0
+        float s = vs[i] + vs[i + 64u];
+        float m = max_rs(vm[i], vm[i + 64u]);
+#pragma unroll
+        for (int stride = 32; stride >= 1; stride >>= 1) {
+            s = s + __shfl_down(s, stride);
+            m = max_rs(m, __shfl_down(m, stride));
+        }
+        if (i == 0u) {
+            tile_sum[blockIdx.x] = s;
+            tile_max[blockIdx.x] = m;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_film_color_counts(const float* __restrict__ accum, const uint32_t* __restrict__ count,
+                                                           float* __restrict__ color, uint64_t n_floats) {
+    for (uint64_t k = (uint64_t)blockIdx.x * 256u + threadIdx.x; k < n_floats; k += (uint64_t)gridDim.x * 256u)
+        color[k] = accum[k] / (float)count[k / 3u];
+}
+
+// k_postprocess (pt_gpu.hip) with the pixel's own count for `samples`
+__global__ __launch_bounds__(256) void k_film_post_counts(const float* __restrict__ accum, const uint32_t* __restrict__ count,
+                                                          uint8_t* __restrict__ rgb8, uint32_t n, int tonemap_type) {
+    uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    f3 c = mk3(accum[3 * (size_t)i], accum[3 * (size_t)i + 1], accum[3 * (size_t)i + 2]) / (float)count[i];
+    c = tonemap(tonemap_type, c);
+    rgb8[3 * (size_t)i] = as_u8(pt_pow_inv_gamma(c.x) * 255.f);
+    rgb8[3 * (size_t)i + 1] = as_u8(pt_pow_inv_gamma(c.y) * 255.f);
+    rgb8[3 * (size_t)i + 2] = as_u8(pt_pow_inv_gamma(c.z) * 255.f);
 }

@@ -478,6 +478,36 @@ TileMap make_tile_map(const pt_profile& p, const pt_opts& o, uint32_t rank) {
     return m;
 }
 
+// The tile map of a tile-list frame (pt_render_tiles): the listed tiles in list order, packed one after the other -
+// what make_tile_map gives a rank, with the list in place of the rank rule.  PT_ERR_INVALID: a null or empty list, one that
+// is not strictly ascending, a tile number beyond the image's tiles, a sharded frame.
+TileMap make_tile_list_map(const char* who, const pt_profile& p, const pt_opts& o, const uint32_t* tiles, uint32_t n_tiles) {
+    if (!tiles || !n_tiles) fail(PT_ERR_INVALID, "%s: the tile list is empty", who);
+    if (o.shard_count > 1) fail(PT_ERR_INVALID, "%s: a tile list and shard_count %u exclude each other", who, o.shard_count);
+    TileMap m;
+    m.tile_w = o.tile_w;
+    m.tile_h = o.tile_h;
+    m.tiles_x = (p.width + o.tile_w - 1) / o.tile_w;
+    m.tiles_y = (p.height + o.tile_h - 1) / o.tile_h;
+    m.count = 1;
+    m.rank = 0;
+    uint64_t off = 0;
+    for (uint32_t lt = 0; lt < n_tiles; ++lt) {
+        const uint32_t k = tiles[lt];
+        if (k >= m.tiles_x * m.tiles_y) fail(PT_ERR_INVALID, "%s: tile %u of an image of %u x %u tiles", who, k, m.tiles_x, m.tiles_y);
+        if (lt && k <= tiles[lt - 1]) fail(PT_ERR_INVALID, "%s: the tile list is not strictly ascending (%u after %u)", who, k, tiles[lt - 1]);
+        const uint32_t tx = k % m.tiles_x, ty = k / m.tiles_x;
+        const uint32_t cw = std::min(o.tile_w, p.width - tx * o.tile_w), ch = std::min(o.tile_h, p.height - ty * o.tile_h);
+        m.tiles.push_back(k);
+        m.offsets.push_back((uint32_t)off);
+        off += (uint64_t)cw * ch;
+    }
+    m.n_local_tiles = n_tiles;
+    m.offsets.push_back((uint32_t)off);
+    m.n_local = off;
+    return m;
+}
+
 struct DeviceBuffer {
     void* p = nullptr;
     size_t bytes = 0;
@@ -611,6 +641,12 @@ struct pt_scene {
         std::map<std::vector<uint64_t>, std::unique_ptr<FrameStats>> stats;
         uint32_t mask_blocks = 0;   // blocks of the last frame's camera-grid cull table (0: no cull in that frame)
     } frame_state;
+    // A tile-list frame (pt_render_tiles) keeps out of all that: its counts go to a slot of its own, reset by every such frame
+    // (which waits for the device first: no copy into `host` and no `done` is in flight then), and its tile table - offsets, tile
+    // numbers, visiting order - to a buffer of its own, rewritten by every such frame (tile_tables is cached by a key that does
+    // not know the list)
+    std::unique_ptr<FrameStats> tile_frame_stats;
+    DeviceBuffer tile_list_table;
     DeviceBuffer stats_dev;
     // A frame cache: one value per work item that later frames of the same key read instead of computing it again.  The
     // mechanics they all share (frame_cache_frame, render_chunk): the plane is indexed by frame-global item g = batch x
@@ -746,6 +782,7 @@ struct pt_scene {
     ~pt_scene() {
         (void)hipSetDevice(device);
         frame_state.stats.clear();
+        tile_frame_stats.reset();
         for (void* p : allocations) (void)hipFree(p);
         for (hipEvent_t e : events) (void)hipEventDestroy(e);
         for (hipEvent_t e : {pipe.ev_shade, pipe.ev_shadow, pipe.ev_rng, pipe.ev_chunk, pipe.ev_trace, pipe.ev_wide, pipe.ev_exact, pipe.ev_exact_go})
@@ -2186,7 +2223,42 @@ struct Frame {
     bool bounce0_fused = false;
     uint32_t blocks64 = 0;   // 8x8 pixel blocks of the local tiles
     uint32_t batch = 0;      // samples per pass over the image
+    // a tile-list frame (pt_render_tiles): the tile map is the caller's list, the outputs are packed in list order; it leaves the
+    // scene's steady state - plans, frame caches, the count of frames before the escape masks - as it found it
+    bool tile_list = false;
 };
+
+// The tiles of a tile-list frame: global tile numbers, strictly ascending.
+struct TileList {
+    const uint32_t* tiles;
+    uint32_t n;
+};
+
+// The words of a frame's tile table: the packed offset of every local tile, their global tile numbers (tile_k_base), then -
+// morton - the order in which the wavefront integrator visits the local tiles
+std::vector<uint32_t> tile_table_words(const TileMap& tm, bool morton) {
+    std::vector<uint32_t> table(tm.offsets);
+    table.insert(table.end(), tm.tiles.begin(), tm.tiles.end());
+    if (morton) {
+        auto spread = [](uint32_t v) {   // bits of v to the even positions
+            uint64_t x = v;
+            x = (x | (x << 16)) & 0x0000ffff0000ffffull;
+            x = (x | (x << 8)) & 0x00ff00ff00ff00ffull;
+            x = (x | (x << 4)) & 0x0f0f0f0f0f0f0f0full;
+            x = (x | (x << 2)) & 0x3333333333333333ull;
+            x = (x | (x << 1)) & 0x5555555555555555ull;
+            return x;
+        };
+        std::vector<std::pair<uint64_t, uint32_t>> order(tm.n_local_tiles);
+        for (uint32_t lt = 0; lt < tm.n_local_tiles; ++lt) {
+            const uint32_t k = tm.tiles[lt];
+            order[lt] = {spread(k % tm.tiles_x) | (spread(k / tm.tiles_x) << 1), lt};
+        }
+        std::sort(order.begin(), order.end());
+        for (auto& e : order) table.push_back(e.second);
+    }
+    return table;
+}
 
 // The tile table of a sharded or Morton-ordered frame (cached per configuration: no host sync in steady state): the packed
 // offset of every local tile, their global tile numbers (tile_k_base), then - PT_TILE_ORDER=morton - the order in which
@@ -2199,26 +2271,7 @@ const uint32_t* tile_table(pt_scene& s, const pt_profile& p, const pt_opts& o, c
             HIP_CHECK(hipDeviceSynchronize());
             s.tile_tables.clear();
         }
-        std::vector<uint32_t> table(tm.offsets);
-        table.insert(table.end(), tm.tiles.begin(), tm.tiles.end());
-        if (morton) {
-            auto spread = [](uint32_t v) {   // bits of v to the even positions
-                uint64_t x = v;
-                x = (x | (x << 16)) & 0x0000ffff0000ffffull;
-                x = (x | (x << 8)) & 0x00ff00ff00ff00ffull;
-                x = (x | (x << 4)) & 0x0f0f0f0f0f0f0f0full;
-                x = (x | (x << 2)) & 0x3333333333333333ull;
-                x = (x | (x << 1)) & 0x5555555555555555ull;
-                return x;
-            };
-            std::vector<std::pair<uint64_t, uint32_t>> order(tm.n_local_tiles);
-            for (uint32_t lt = 0; lt < tm.n_local_tiles; ++lt) {
-                const uint32_t k = tm.tiles[lt];
-                order[lt] = {spread(k % tm.tiles_x) | (spread(k / tm.tiles_x) << 1), lt};
-            }
-            std::sort(order.begin(), order.end());
-            for (auto& e : order) table.push_back(e.second);
-        }
+        const std::vector<uint32_t> table = tile_table_words(tm, morton);
         auto buf = std::make_unique<DeviceBuffer>();
         buf->ensure(table.size() * 4);
         HIP_CHECK(hipMemcpy(buf->p, table.data(), table.size() * 4, hipMemcpyHostToDevice));   // (a fresh buffer: nobody reads it yet)
@@ -2228,20 +2281,27 @@ const uint32_t* tile_table(pt_scene& s, const pt_profile& p, const pt_opts& o, c
 }
 
 // Validation, the tile map, the escape masks, the counters, RenderParams, the pipeline, the sample batch and its staging
-// area.  false: this rank has no pixels.
-bool frame_setup(pt_scene& s, const pt_profile& p, const pt_opts* opts_in, void* d_accum, hipStream_t stream, Frame& f) {
+// area.  false: this rank has no pixels.  list: a tile-list frame's tiles (everything such a frame refuses is refused before
+// any device work; then it waits for the device - its table and its statistics slot are rewritten in place).
+bool frame_setup(pt_scene& s, const pt_profile& p, const pt_opts* opts_in, void* d_accum, hipStream_t stream, Frame& f,
+                 const TileList* list = nullptr) {
     pt_opts& o = f.o;
     normalise_opts(p, opts_in, o);
     if (p.samples == 0) fail(PT_ERR_INVALID, "profile.samples must be > 0");
     if (p.brdf != PT_BRDF_COOK_TORRANCE) fail(PT_ERR_INVALID, "unknown brdf %d", p.brdf);
     if (p.tonemap < 0 || p.tonemap > 2) fail(PT_ERR_INVALID, "unknown tonemap %d", p.tonemap);
+    f.tile_list = list != nullptr;
+    if (list) {
+        if (p.bounces > 4096u) fail(PT_ERR_INVALID, "profile.bounces %u is out of range (at most 4096)", p.bounces);
+        f.tm = make_tile_list_map("pt_render_tiles", p, o, list->tiles, list->n);
+    }
     HIP_CHECK(hipSetDevice(s.device));
     f.p = p;
-    f.tm = make_tile_map(p, o, o.shard_rank);
+    if (!list) f.tm = make_tile_map(p, o, o.shard_rank);
     const TileMap& tm = f.tm;
     if (tm.n_local == 0) return false;
     // escape masks: from the scene's (escape_after + 1)th frame of the default pipeline on (scene_upload has the reason)
-    if (s.escape_wanted && !s.escape_tried && !(o.flags & (PT_FLAG_NO_GRIDS | PT_FLAG_MEGAKERNEL))) {
+    if (!list && s.escape_wanted && !s.escape_tried && !(o.flags & (PT_FLAG_NO_GRIDS | PT_FLAG_MEGAKERNEL))) {
         if (s.frames_rendered >= s.escape_after) escape_masks_build(s);
         ++s.frames_rendered;
     }
@@ -2249,8 +2309,16 @@ bool frame_setup(pt_scene& s, const pt_profile& p, const pt_opts* opts_in, void*
     f.dev = s.dev;
     if (o.flags & PT_FLAG_NO_GRIDS) f.dev.escape = nullptr;
     uint32_t tile_order_base = 0, tile_k_base = 0;
-    if (o.shard_count > 1 || f.env.morton) {
+    if (list) {
+        HIP_CHECK(hipDeviceSynchronize());   // (the tile-list frame before this one may still read the table)
+        const std::vector<uint32_t> table = tile_table_words(tm, f.env.morton);
+        s.tile_list_table.ensure(table.size() * 4);
+        HIP_CHECK(hipMemcpy(s.tile_list_table.p, table.data(), table.size() * 4, hipMemcpyHostToDevice));
+        f.d_tiles = (const uint32_t*)s.tile_list_table.p;
+    } else if (o.shard_count > 1 || f.env.morton) {
         f.d_tiles = tile_table(s, p, o, tm, f.env.morton);
+    }
+    if (f.d_tiles) {
         tile_k_base = (uint32_t)tm.offsets.size();
         if (f.env.morton) tile_order_base = (uint32_t)(tm.offsets.size() + tm.tiles.size());
     }
@@ -2280,7 +2348,7 @@ bool frame_setup(pt_scene& s, const pt_profile& p, const pt_opts* opts_in, void*
     P.bounces = p.bounces;
     P.tonemap = p.tonemap;
     P.shard_rank = o.shard_rank;
-    P.shard_count = o.shard_count;
+    P.shard_count = list ? 2u : o.shard_count;   // (what the kernels read of it: > 1 - the outputs are packed by the tile table)
     P.tile_w = o.tile_w;
     P.tile_h = o.tile_h;
     P.tiles_x = tm.tiles_x;
@@ -2482,6 +2550,19 @@ WfFrame frame_plan(pt_scene& s, const Frame& f, const QueueEnv& qe) {
                                             o.flags & (PT_FLAG_NO_GRIDS | PT_FLAG_MEGAKERNEL | PT_FLAG_COUNTERS), (uint64_t)f.bounce0_fused, o.shard_rank, o.shard_count, o.tile_w, o.tile_h, f.batch, (uint64_t)wf.max_items};
     wf.cap_a = (uint32_t)std::min<uint64_t>(wf.max_items, std::max<uint64_t>(1u << 20, (uint64_t)(qe.first_gib * 1073741824.0) / wf.per_item) & ~63ull);
     if (s.wf_cap_ok) wf.cap_a = std::min(wf.cap_a, s.wf_cap_ok);
+    if (f.tile_list) {
+        // a first frame, every time: no plan is read or made, and no key another frame can meet is touched.  (frame_setup
+        // waited for the device: the counts of the tile-list frame before are home, nothing refers to the slot's event.)
+        if (!s.tile_frame_stats) s.tile_frame_stats = std::make_unique<pt_scene::FrameStats>();
+        pt_scene::FrameStats& own = *s.tile_frame_stats;
+        own.pending = own.valid = own.planned = own.stats_planned = own.plan_fresh = own.plan_failed = false;
+        own.stats_hit_loads = own.plan_hit_loads = 0;
+        wf.fs = &own;
+        wf.inline_at.assign(p.bounces + 2, 0);
+        wf.cap = wf.cap_a;
+        wf.cap_q[0] = wf.cap_q[1] = wf.cap_h = wf.cap_s = wf.cap_e = wf.cap;
+        return wf;
+    }
     auto& stats = s.frame_state.stats;
     if (!stats[stat_key]) {
         if (stats.size() > 64) {   // (a caller cycling through configurations: start over)
@@ -2594,6 +2675,7 @@ void queue_buffers(pt_scene& s, const Frame& f, const QueueEnv& qe, WfFrame& wf)
         wf.cap_q[0] = wf.cap_q[1] = wf.cap_h = wf.cap_s = wf.cap_e = wf.cap;
         std::fill(wf.inline_at.begin(), wf.inline_at.end(), 0);
     }
+    if (f.tile_list) return;   // (pt_scene_get_info goes on reporting the last whole frame)
     s.queue_bytes_last = w.queue[0].bytes + w.queue[1].bytes + w.hits.bytes + w.shadow.bytes + w.contrib.bytes + w.rng[0].bytes +
                          w.rng[1].bytes + w.draws.bytes + w.offgrid.bytes + w.exact[0].bytes + w.exact[1].bytes + w.deferred.bytes;
     s.queue_chunk_last = wf.cap;
@@ -3540,17 +3622,22 @@ struct FrameTaps {
 };
 
 // One frame of pt_render, pt_render_device and pt_render_gathered; taps: of pt_render_moments and pt_render_samples.
+// list: a tile-list frame (pt_render_tiles, pt_film_add_tile_pass).
 void render_device(pt_scene& s, const pt_profile& p, const pt_opts* opts_in, void* d_rgb8, void* d_accum,
-                   hipStream_t stream, bool allow_preview = false, const FrameTaps* taps = nullptr) {
+                   hipStream_t stream, bool allow_preview = false, const FrameTaps* taps = nullptr, const TileList* list = nullptr) {
     Frame f;
-    if (!frame_setup(s, p, opts_in, d_accum, stream, f)) return;
+    // (a tile-list frame refuses before any device work, and frame_setup waits for the device for it)
+    if (taps && list && opts_in && (opts_in->flags & PT_FLAG_MEGAKERNEL)) fail(PT_ERR_UNSUPPORTED, "this pipeline stages no samples");
+    if (!frame_setup(s, p, opts_in, d_accum, stream, f, list)) return;
     if (taps && !f.wavefront) fail(PT_ERR_UNSUPPORTED, "this pipeline stages no samples");
     const pt_opts& o = f.o;
     WfFrame wf;
     if (f.wavefront) {
         const QueueEnv qe = queue_env();
         wf = frame_plan(s, f, qe);
-        frame_caches(s, f, wf, stream);
+        // (a tile-list frame enters no cache: every pointer stays null - what a frame launches when every cache is out of use -
+        // and no last_key moves, so the next whole frame still follows its predecessor)
+        if (!f.tile_list) frame_caches(s, f, wf, stream);
         queue_buffers(s, f, qe, wf);
         stats_slots(s, f, wf);
         side_streams(s, f, wf);
@@ -3910,8 +3997,23 @@ struct pt_film {
     float* base = nullptr;
     float *accum = nullptr, *moments = nullptr, *pass_accum = nullptr, *pass_moments = nullptr, *err = nullptr;
     float *block_sum = nullptr, *block_max = nullptr;
+    // The adaptive film.  A film that has taken a tile pass is non-uniform: `count` (n_local u32, allocated by the
+    // first tile pass and filled with the uniform total) holds every pixel's samples, and `samples` is the largest of them.
+    // Every pass covers whole tiles of the film's own tiling, so a count per tile on the host says the same: tile_count is what
+    // the largest and the smallest count and their sum are read from.  `table`: the tile table of the pass being merged;
+    // `tile_sum` / `tile_max`: pt_film_tile_noise's arrays (allocated on first use).  A film that never takes a tile pass and
+    // is never asked for its tile noise allocates none of this.
+    uint32_t* count = nullptr;
+    float* tile_sum = nullptr;   // (tile_max = tile_sum + n_tiles)
+    DeviceBuffer table;
+    std::vector<uint64_t> tile_count;
+    uint64_t bytes_adaptive = 0;
+    uint32_t tile_passes = 0, last_pass_tiles = 0;   // (last_pass_tiles: of the last pass; 0: a whole frame, or no pass yet)
+    bool uniform() const { return count == nullptr; }
     ~pt_film() {
         if (base) (void)hipFree(base);
+        if (count) (void)hipFree(count);
+        if (tile_sum) (void)hipFree(tile_sum);
     }
 };
 
@@ -3978,6 +4080,7 @@ void film_merge(pt_film& film, uint32_t samples) {
     HIP_CHECK(hipDeviceSynchronize());
     ++film.passes;
     film.last_pass_samples = samples;
+    film.last_pass_tiles = 0;
     film.samples += samples;
 }
 
@@ -4027,6 +4130,139 @@ void film_noise(const pt_film& film, float lum_floor, double target, pt_film_noi
     out.converged = out.mean_error <= target ? 1u : 0u;
 }
 
+// ---- the adaptive film
+FilmTiling film_tiling(const pt_film& film) {
+    return FilmTiling{film.profile.width, film.profile.height, film.opts.tile_w, film.opts.tile_h,
+                      (film.profile.width + film.opts.tile_w - 1u) / film.opts.tile_w};
+}
+uint32_t film_n_tiles(const pt_film& film) {
+    const FilmTiling T = film_tiling(film);
+    return T.tiles_x * ((T.height + T.tile_h - 1u) / T.tile_h);
+}
+uint64_t film_tile_pixels(const FilmTiling& T, uint32_t k) {
+    const uint32_t x0 = (k % T.tiles_x) * T.tile_w, y0 = (k / T.tiles_x) * T.tile_h;
+    return (uint64_t)std::min(T.tile_w, T.width - x0) * std::min(T.tile_h, T.height - y0);
+}
+void film_check_tiled(const char* who, const pt_film* film) {
+    if (!film) fail(PT_ERR_INVALID, "%s: null argument", who);
+    if (!film->has_profile) fail(PT_ERR_INVALID, "%s: a film made from planes has no tiling", who);
+    if (film->opts.shard_count > 1) fail(PT_ERR_INVALID, "%s: a sharded film takes whole passes only (shard_count %u)", who, film->opts.shard_count);
+}
+void film_refuse_non_uniform(const char* who, const pt_film* film) {
+    if (film && !film->uniform()) fail(PT_ERR_UNSUPPORTED, "%s: the film has a sample count per pixel (pt_film_add_tile_pass); this call assumes one", who);
+}
+// What a tile pass refuses before any device work; returns the list's tile map.
+TileMap film_check_tile_pass(const char* who, const pt_film* film, uint32_t samples, const uint32_t* tiles, uint32_t n_tiles) {
+    film_check_tiled(who, film);
+    film_check_samples(who, film, samples);
+    return make_tile_list_map(who, film->profile, film->opts, tiles, n_tiles);
+}
+// The first tile pass: the count plane, filled with the uniform total; the table's buffer
+void film_make_non_uniform(pt_film& film) {
+    if (!film.uniform()) return;
+    const uint32_t n_tiles = film_n_tiles(film);
+    const size_t table_before = film.table.bytes;   // (the table's buffer outlives a pt_film_reset)
+    film.table.ensure((size_t)(2u * n_tiles + 1u) * 4u);
+    film.bytes_adaptive += film.table.bytes - table_before;
+    std::vector<uint32_t> fill((size_t)film.n_local, (uint32_t)film.samples);
+    uint32_t* d = nullptr;
+    HIP_CHECK(hipMalloc((void**)&d, (size_t)film.n_local * 4u));   // (256-byte aligned, as every hipMalloc)
+    if (hipMemcpy(d, fill.data(), fill.size() * 4u, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d);
+        fail(PT_ERR_DEVICE, "pt_film: the copy of the count plane failed");
+    }
+    film.count = d;
+    film.tile_count.assign(n_tiles, film.samples);
+    film.bytes_adaptive += (uint64_t)film.n_local * 4u;
+}
+// film = film + pass buffers over the listed tiles, then the counters
+void film_merge_tiles(pt_film& film, const TileMap& tm, uint32_t samples) {
+    film_make_non_uniform(film);
+    std::vector<uint32_t> table(tm.offsets);
+    table.insert(table.end(), tm.tiles.begin(), tm.tiles.end());
+    HIP_CHECK(hipMemcpy(film.table.p, table.data(), table.size() * 4u, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_film_merge_tiles, dim3(tm.n_local_tiles), dim3(256), 0, 0, (const float*)film.pass_accum,
+                       (const float2*)film.pass_moments, (const uint32_t*)film.table.p, tm.n_local_tiles, film_tiling(film),
+                       film.accum, (float2*)film.moments, film.count, samples);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    ++film.passes;
+    ++film.tile_passes;
+    film.last_pass_tiles = tm.n_local_tiles;
+    film.last_pass_samples = samples;
+    for (uint32_t k : tm.tiles) film.tile_count[k] += samples;
+    film.samples = *std::max_element(film.tile_count.begin(), film.tile_count.end());
+}
+void film_add_tile_pass(pt_film& film, const pt_scene* scene, uint32_t samples, const uint32_t* tiles, uint32_t n_tiles) {
+    const char* who = "pt_film_add_tile_pass";
+    if (!scene) fail(PT_ERR_INVALID, "%s: null argument", who);
+    const TileMap tm = film_check_tile_pass(who, &film, samples, tiles, n_tiles);
+    if (scene->device != film.device)
+        fail(PT_ERR_INVALID, "%s: the scene is on device %d, the film on device %d", who, scene->device, film.device);
+    HIP_CHECK(hipSetDevice(film.device));
+    pt_profile p = film.profile;
+    p.samples = samples;
+    FrameTaps taps;
+    taps.moments = (float2*)film.pass_moments;
+    const TileList list{tiles, n_tiles};
+    render_device(render_state(scene), p, &film.opts, nullptr, film.pass_accum, nullptr, false, &taps, &list);
+    HIP_CHECK(hipDeviceSynchronize());   // the frame is complete (and has not failed) before the film changes
+    film_merge_tiles(film, tm, samples);
+}
+// A whole frame on any film: a non-uniform one takes it as the tile pass that lists every tile
+void film_add_whole_pass(pt_film& film, const pt_scene* scene, uint32_t samples) {
+    if (film.uniform()) return film_add_pass(film, scene, samples);
+    film_check_pass("pt_film_add_pass", &film, scene, samples);
+    std::vector<uint32_t> all(film_n_tiles(film));
+    for (uint32_t k = 0; k < all.size(); ++k) all[k] = k;
+    film_add_tile_pass(film, scene, samples, all.data(), (uint32_t)all.size());
+}
+
+void film_tile_noise(const pt_film& film_c, float lum_floor, double target, pt_film_tile_stats& out, float* err_host,
+                     float* tile_sum_host, float* tile_max_host) {
+    const char* who = "pt_film_tile_noise";
+    film_check_tiled(who, &film_c);
+    film_check_noise_args(who, lum_floor, target);
+    pt_film& film = const_cast<pt_film&>(film_c);   // (the tile arrays are made on first use: scratch, not the film's contents)
+    const uint32_t n_tiles = film_n_tiles(film);
+    const uint64_t least = film.uniform() ? film.samples : *std::min_element(film.tile_count.begin(), film.tile_count.end());
+    if (least < 2u) fail(PT_ERR_INVALID, "%s: a sample variance needs >= 2 samples in every pixel (the fewest: %llu)", who, (unsigned long long)least);
+    HIP_CHECK(hipSetDevice(film.device));
+    if (!film.tile_sum) {
+        HIP_CHECK(hipMalloc((void**)&film.tile_sum, (size_t)n_tiles * 8u));
+        film.bytes_adaptive += (uint64_t)n_tiles * 8u;
+    }
+    float* tile_max = film.tile_sum + n_tiles;
+    const FilmTiling T = film_tiling(film);
+    hipLaunchKernelGGL(k_film_tile_noise, dim3(n_tiles), dim3(256), 0, 0, (const float2*)film.moments, (const uint32_t*)film.count,
+                       (uint32_t)film.samples, T, lum_floor, err_host ? film.err : (float*)nullptr, film.tile_sum, tile_max);
+    HIP_CHECK(hipGetLastError());
+    std::vector<float> sums(n_tiles);
+    HIP_CHECK(hipMemcpy(sums.data(), film.tile_sum, n_tiles * sizeof(float), hipMemcpyDeviceToHost));   // (waits for the kernel)
+    if (tile_sum_host) memcpy(tile_sum_host, sums.data(), n_tiles * sizeof(float));
+    if (tile_max_host) HIP_CHECK(hipMemcpy(tile_max_host, tile_max, n_tiles * sizeof(float), hipMemcpyDeviceToHost));
+    if (err_host) HIP_CHECK(hipMemcpy(err_host, film.err, film.n_local * sizeof(float), hipMemcpyDeviceToHost));
+    double S = 0.0, worst = 0.0;
+    uint32_t over = 0;
+    uint64_t pixel_samples = 0;
+    for (uint32_t t = 0; t < n_tiles; ++t) {
+        const uint64_t pixels = film_tile_pixels(T, t);
+        const double mean_t = (double)sums[t] / (double)pixels;
+        S = S + (double)sums[t];
+        if (t == 0 || mean_t > worst) worst = mean_t;
+        if (mean_t > target) ++over;
+        pixel_samples += pixels * (film.uniform() ? film.samples : film.tile_count[t]);
+    }
+    memset(&out, 0, sizeof out);
+    out.mean_error = S / (double)film.n_local;
+    out.max_tile_error = worst;
+    out.samples = film.samples;
+    out.pixel_samples = pixel_samples;
+    out.n_tiles = n_tiles;
+    out.over_tiles = over;
+    out.converged = over == 0u ? 1u : 0u;
+}
+
 void film_fill_info(const pt_film& film, pt_film_info& info) {
     memset(&info, 0, sizeof info);
     info.width = film.has_profile ? film.profile.width : 0u;
@@ -4035,17 +4271,31 @@ void film_fill_info(const pt_film& film, pt_film_info& info) {
     info.last_pass_samples = film.last_pass_samples;
     info.n_local = film.n_local;
     info.samples = film.samples;
-    info.device_bytes = film.bytes;
+    info.device_bytes = film.bytes + film.bytes_adaptive;
 }
 
 void film_check_resolve(const char* who, const pt_film* film, int tonemap_type, const void* rgb8, const void* color) {
     if (!film || (!rgb8 && !color)) fail(PT_ERR_INVALID, "%s: null argument", who);
     if (tonemap_type < PT_TONEMAP_REINHARD || tonemap_type > PT_TONEMAP_ACES) fail(PT_ERR_INVALID, "%s: unknown tonemap %d", who, tonemap_type);
     if (film->samples == 0) fail(PT_ERR_INVALID, "%s: the film holds no samples", who);
+    if (!film->uniform() && *std::min_element(film->tile_count.begin(), film->tile_count.end()) == 0)
+        fail(PT_ERR_INVALID, "%s: some tiles of the film hold no samples", who);
 }
 
 void film_resolve_launch(const pt_film& film, int tonemap_type, uint8_t* d_rgb8, float* d_color, hipStream_t stream) {
     const uint64_t n_floats = 3u * film.n_local;
+    if (!film.uniform()) {   // every pixel by its own count
+        if (d_color) {
+            const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_floats + 255u) / 256u, FILM_MAX_BLOCKS);
+            hipLaunchKernelGGL(k_film_color_counts, dim3(blocks), dim3(256), 0, stream, (const float*)film.accum,
+                               (const uint32_t*)film.count, d_color, n_floats);
+        }
+        if (d_rgb8)
+            hipLaunchKernelGGL(k_film_post_counts, dim3(((uint32_t)film.n_local + 255u) / 256u), dim3(256), 0, stream,
+                               (const float*)film.accum, (const uint32_t*)film.count, d_rgb8, (uint32_t)film.n_local, tonemap_type);
+        HIP_CHECK(hipGetLastError());
+        return;
+    }
     if (d_color) {
         const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_floats + 255u) / 256u, FILM_MAX_BLOCKS);
         hipLaunchKernelGGL(k_film_color, dim3(blocks), dim3(256), 0, stream, (const float*)film.accum, d_color, n_floats, (float)film.samples);
@@ -4173,6 +4423,70 @@ int pt_render(const pt_scene* scene, const pt_profile* profile, const pt_opts* o
         HIP_CHECK(hipDeviceSynchronize());
         if (rgb8) d_rgb.fetch(rgb8, n * 3);
         if (accum) d_acc.fetch(accum, n * 3);
+    });
+}
+
+uint64_t pt_tiles_pixel_count(const pt_profile* profile, const pt_opts* opts, const uint32_t* tiles, uint32_t n_tiles) {
+    uint64_t n = 0;
+    guarded([&] {
+        if (!profile) fail(PT_ERR_INVALID, "pt_tiles_pixel_count: null profile");
+        pt_opts o;
+        normalise_opts(*profile, opts, o);
+        n = make_tile_list_map("pt_tiles_pixel_count", *profile, o, tiles, n_tiles).n_local;
+    });
+    return n;
+}
+
+int pt_tiles_pixel_map(const pt_profile* profile, const pt_opts* opts, const uint32_t* tiles, uint32_t n_tiles, uint32_t* out) {
+    return guarded([&] {
+        if (!profile || !out) fail(PT_ERR_INVALID, "pt_tiles_pixel_map: null argument");
+        pt_opts o;
+        normalise_opts(*profile, opts, o);
+        const pt_profile& p = *profile;
+        const TileMap tm = make_tile_list_map("pt_tiles_pixel_map", p, o, tiles, n_tiles);
+        for (uint32_t lt = 0; lt < tm.n_local_tiles; ++lt) {
+            const uint32_t k = tm.tiles[lt];
+            const uint32_t tx = k % tm.tiles_x, ty = k / tm.tiles_x;
+            const uint32_t cw = std::min(o.tile_w, p.width - tx * o.tile_w), ch = std::min(o.tile_h, p.height - ty * o.tile_h);
+            for (uint32_t y = 0; y < ch; ++y)
+                for (uint32_t x = 0; x < cw; ++x)
+                    out[tm.offsets[lt] + y * cw + x] = (tx * o.tile_w + x) + (ty * o.tile_h + y) * p.width;
+        }
+    });
+}
+
+int pt_render_tiles_device(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, const uint32_t* tiles,
+                           uint32_t n_tiles, void* d_rgb8, void* d_accum, void* d_moments, void* hip_stream) {
+    return guarded([&] {
+        if (!scene || !profile || (!d_rgb8 && !d_accum && !d_moments)) fail(PT_ERR_INVALID, "pt_render_tiles_device: null argument");
+        const TileList list{tiles, n_tiles};
+        FrameTaps taps;
+        taps.moments = (float2*)d_moments;
+        render_device(render_state(scene), *profile, opts, d_rgb8, d_accum, (hipStream_t)hip_stream, false,
+                      d_moments ? &taps : nullptr, &list);
+    });
+}
+
+int pt_render_tiles(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, const uint32_t* tiles, uint32_t n_tiles,
+                    uint8_t* rgb8, float* accum, float* moments) {
+    return guarded([&] {
+        if (!scene || !profile || (!rgb8 && !accum && !moments)) fail(PT_ERR_INVALID, "pt_render_tiles: null argument");
+        pt_opts o;
+        normalise_opts(*profile, opts, o);
+        const uint64_t n = make_tile_list_map("pt_render_tiles", *profile, o, tiles, n_tiles).n_local;
+        if (moments) moments_check_opts("pt_render_tiles", opts);
+        HIP_CHECK(hipSetDevice(scene->device));
+        Staged<uint8_t> d_rgb(nullptr, n * 3);
+        Staged<float> d_acc(nullptr, n * 3);
+        Staged<float2> d_mom(nullptr, moments ? n : 0);
+        const TileList list{tiles, n_tiles};
+        FrameTaps taps;
+        taps.moments = d_mom.d;
+        render_device(render_state(scene), *profile, opts, d_rgb.d, d_acc.d, nullptr, false, moments ? &taps : nullptr, &list);
+        HIP_CHECK(hipDeviceSynchronize());
+        if (rgb8) d_rgb.fetch(rgb8, n * 3);
+        if (accum) d_acc.fetch(accum, n * 3);
+        if (moments) d_mom.fetch((float2*)moments, n);
     });
 }
 
@@ -4454,6 +4768,13 @@ int pt_film_reset(pt_film* film) {
         HIP_CHECK(hipMemset(film->accum, 0, film->stride_a * sizeof(float)));
         HIP_CHECK(hipMemset(film->moments, 0, film->stride_m * sizeof(float)));
         HIP_CHECK(hipDeviceSynchronize());
+        if (film->count) {   // uniform again: the count plane goes (the tile arrays and the table's buffer are scratch and stay)
+            (void)hipFree(film->count);
+            film->count = nullptr;
+            film->bytes_adaptive -= film->n_local * 4u;
+            film->tile_count.clear();
+        }
+        film->tile_passes = film->last_pass_tiles = 0;
         film->passes = 0;
         film->last_pass_samples = 0;
         film->samples = 0;
@@ -4479,6 +4800,7 @@ int pt_film_read(const pt_film* film, float* accum, float* moments) {
 int pt_film_planes_device(const pt_film* film, void** d_accum, void** d_moments) {
     return guarded([&] {
         if (!film) fail(PT_ERR_INVALID, "pt_film_planes_device: null argument");
+        film_refuse_non_uniform("pt_film_planes_device", film);
         if (d_accum) *d_accum = film->accum;
         if (d_moments) *d_moments = film->moments;
     });
@@ -4487,13 +4809,14 @@ int pt_film_planes_device(const pt_film* film, void** d_accum, void** d_moments)
 int pt_film_add_pass(pt_film* film, const pt_scene* scene, uint32_t samples) {
     return guarded([&] {
         film_check_pass("pt_film_add_pass", film, scene, samples);
-        film_add_pass(*film, scene, samples);
+        film_add_whole_pass(*film, scene, samples);
     });
 }
 
 int pt_film_add_planes(pt_film* film, uint32_t samples, const float* accum, const float* moments) {
     return guarded([&] {
         if (!film || !accum || !moments) fail(PT_ERR_INVALID, "pt_film_add_planes: null argument");
+        film_refuse_non_uniform("pt_film_add_planes", film);
         film_check_samples("pt_film_add_planes", film, samples);
         HIP_CHECK(hipSetDevice(film->device));
         HIP_CHECK(hipMemcpy(film->pass_accum, accum, film->n_local * 12u, hipMemcpyHostToDevice));
@@ -4506,6 +4829,7 @@ int pt_film_noise(const pt_film* film, float lum_floor, double target, pt_film_n
                   float* block_sum_host, float* block_max_host) {
     return guarded([&] {
         if (!film || !out) fail(PT_ERR_INVALID, "pt_film_noise: null argument");
+        film_refuse_non_uniform("pt_film_noise", film);
         pt_film_noise_stats st{};
         film_noise(*film, lum_floor, target, st, err_host, block_sum_host, block_max_host);
         *out = st;
@@ -4539,6 +4863,7 @@ int pt_film_render_until(pt_film* film, const pt_scene* scene, uint32_t first_pa
     return guarded([&] {
         if (!film || !scene || !out) fail(PT_ERR_INVALID, "pt_film_render_until: null argument");
         if (!film->has_profile) fail(PT_ERR_INVALID, "pt_film_render_until: a film made from planes has no profile to render with");
+        film_refuse_non_uniform("pt_film_render_until", film);
         film_check_noise_args("pt_film_render_until", lum_floor, target);
         if (first_pass_samples < 2u) fail(PT_ERR_INVALID, "pt_film_render_until: first_pass_samples must be >= 2 (a sample variance needs two)");
         if (!film->passes && (uint64_t)first_pass_samples > max_samples)
@@ -4570,6 +4895,7 @@ int pt_film_kernel_times(const pt_film* film, float lum_floor, int with_err, uin
     return guarded([&] {
         if (!film || !ms_merge || !ms_noise || !reps) fail(PT_ERR_INVALID, "pt_film_kernel_times: null argument");
         if (film->samples < 2u) fail(PT_ERR_INVALID, "pt_film_kernel_times: the film's total must be >= 2");
+        film_refuse_non_uniform("pt_film_kernel_times", film);
         film_check_noise_args("pt_film_kernel_times", lum_floor, 0.0);
         HIP_CHECK(hipSetDevice(film->device));
         hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -4594,6 +4920,204 @@ int pt_film_kernel_times(const pt_film* film, float lum_floor, int with_err, uin
             HIP_CHECK(hipEventRecord(e1, 0));
             HIP_CHECK(hipEventSynchronize(e1));
             HIP_CHECK(hipEventElapsedTime(merge ? &ms_merge[r] : &ms_noise[r - reps], e0, e1));
+        }
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+// ---- the adaptive film
+int pt_film_add_tile_pass(pt_film* film, const pt_scene* scene, uint32_t samples, const uint32_t* tiles, uint32_t n_tiles) {
+    return guarded([&] {
+        if (!film || !scene) fail(PT_ERR_INVALID, "pt_film_add_tile_pass: null argument");
+        film_add_tile_pass(*film, scene, samples, tiles, n_tiles);
+    });
+}
+
+int pt_film_add_tile_planes(pt_film* film, uint32_t samples, const uint32_t* tiles, uint32_t n_tiles, const float* accum,
+                            const float* moments) {
+    return guarded([&] {
+        if (!film || !accum || !moments) fail(PT_ERR_INVALID, "pt_film_add_tile_planes: null argument");
+        const TileMap tm = film_check_tile_pass("pt_film_add_tile_planes", film, samples, tiles, n_tiles);
+        HIP_CHECK(hipSetDevice(film->device));
+        HIP_CHECK(hipMemcpy(film->pass_accum, accum, tm.n_local * 12u, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(film->pass_moments, moments, tm.n_local * 8u, hipMemcpyHostToDevice));
+        film_merge_tiles(*film, tm, samples);
+    });
+}
+
+int pt_film_read_counts(const pt_film* film, uint32_t* counts) {
+    return guarded([&] {
+        if (!film || !counts) fail(PT_ERR_INVALID, "pt_film_read_counts: null argument");
+        if (film->uniform()) {
+            std::fill(counts, counts + film->n_local, (uint32_t)film->samples);
+            return;
+        }
+        HIP_CHECK(hipSetDevice(film->device));
+        HIP_CHECK(hipMemcpy(counts, film->count, film->n_local * 4u, hipMemcpyDeviceToHost));
+    });
+}
+
+int pt_film_tile_noise(const pt_film* film, float lum_floor, double target, pt_film_tile_stats* out, float* err_host,
+                       float* tile_sum_host, float* tile_max_host) {
+    return guarded([&] {
+        if (!film || !out) fail(PT_ERR_INVALID, "pt_film_tile_noise: null argument");
+        pt_film_tile_stats st{};
+        film_tile_noise(*film, lum_floor, target, st, err_host, tile_sum_host, tile_max_host);
+        *out = st;
+    });
+}
+
+int pt_film_get_adaptive_info(const pt_film* film, pt_film_adaptive_info* out) {
+    return guarded([&] {
+        if (!film || !out) fail(PT_ERR_INVALID, "pt_film_get_adaptive_info: null argument");
+        film_check_tiled("pt_film_get_adaptive_info", film);
+        const FilmTiling T = film_tiling(*film);
+        memset(out, 0, sizeof *out);
+        out->uniform = film->uniform() ? 1u : 0u;
+        out->tile_w = T.tile_w;
+        out->tile_h = T.tile_h;
+        out->tiles_x = T.tiles_x;
+        out->tiles_y = (T.height + T.tile_h - 1u) / T.tile_h;
+        out->n_tiles = out->tiles_x * out->tiles_y;
+        out->tile_passes = film->tile_passes;
+        out->last_pass_tiles = film->last_pass_tiles ? film->last_pass_tiles : film->passes ? out->n_tiles : 0u;
+        out->max_samples = film->samples;
+        out->min_samples = film->uniform() ? film->samples : *std::min_element(film->tile_count.begin(), film->tile_count.end());
+        for (uint32_t t = 0; t < out->n_tiles; ++t)
+            out->pixel_samples += film_tile_pixels(T, t) * (film->uniform() ? film->samples : film->tile_count[t]);
+        out->device_bytes = film->bytes + film->bytes_adaptive;
+    });
+}
+
+void pt_film_adaptive_params_default(pt_film_adaptive_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    p->lum_floor = PT_FILM_DEFAULT_LUM_FLOOR;
+    p->target = 0.02;
+    p->first_pass_samples = 8;
+    p->uniform_samples = 24;
+    p->dilate = 1;
+    p->max_samples = 512;
+}
+
+int pt_film_render_until_adaptive(pt_film* film, const pt_scene* scene, const pt_film_adaptive_params* params,
+                                  pt_film_pass_fn on_pass, void* user, pt_film_tile_stats* out) {
+    return guarded([&] {
+        const char* who = "pt_film_render_until_adaptive";
+        if (!film || !scene || !params || !out) fail(PT_ERR_INVALID, "%s: null argument", who);
+        film_check_tiled(who, film);
+        film_check_noise_args(who, params->lum_floor, params->target);
+        if (params->first_pass_samples < 2u) fail(PT_ERR_INVALID, "%s: first_pass_samples must be >= 2 (a sample variance needs two)", who);
+        if (params->dilate > 1u) fail(PT_ERR_INVALID, "%s: dilate must be 0 or 1", who);
+        if (!film->passes && (uint64_t)params->first_pass_samples > params->max_samples)
+            fail(PT_ERR_INVALID, "%s: first_pass_samples %u exceeds max_samples %llu", who, params->first_pass_samples, (unsigned long long)params->max_samples);
+        if (scene->device != film->device)
+            fail(PT_ERR_INVALID, "%s: the scene is on device %d, the film on device %d", who, scene->device, film->device);
+        const uint64_t cap = std::min<uint64_t>(params->max_samples, (uint64_t)PT_FILM_MAX_SAMPLES);
+        const FilmTiling T = film_tiling(*film);
+        const uint32_t n_tiles = film_n_tiles(*film), tiles_y = n_tiles / T.tiles_x;
+        std::vector<float> sums(n_tiles);
+        std::vector<uint32_t> active;   // the tiles of the next pass; empty: every tile
+        pt_film_tile_stats st{};
+        bool measured = false;
+        auto measure = [&](uint32_t rendered) {
+            film_tile_noise(*film, params->lum_floor, params->target, st, nullptr, sums.data(), nullptr);
+            st.active_tiles = rendered;
+            measured = true;
+            // the candidates - the tiles above the target - and, dilate: their 8 neighbours
+            std::vector<uint8_t> on(n_tiles, 0);
+            for (uint32_t t = 0; t < n_tiles; ++t) {
+                if (!((double)sums[t] / (double)film_tile_pixels(T, t) > params->target)) continue;
+                const int tx = (int)(t % T.tiles_x), ty = (int)(t / T.tiles_x), r = (int)params->dilate;
+                for (int y = std::max(0, ty - r); y <= std::min((int)tiles_y - 1, ty + r); ++y)
+                    for (int x = std::max(0, tx - r); x <= std::min((int)T.tiles_x - 1, tx + r); ++x) on[(uint32_t)y * T.tiles_x + (uint32_t)x] = 1;
+            }
+            active.clear();
+            for (uint32_t t = 0; t < n_tiles; ++t)
+                if (on[t]) active.push_back(t);
+        };
+        if (film->passes && film->samples >= 2u && film->samples >= params->uniform_samples) measure(0);   // (a film that has passes: its own active set)
+        for (;;) {
+            if (measured && st.converged) break;
+            const uint64_t next = film->passes ? 2u * (uint64_t)film->last_pass_samples : (uint64_t)params->first_pass_samples;
+            if (film->samples + next > cap) break;
+            const bool all = !measured || !film->passes || film->samples < params->uniform_samples || active.size() == n_tiles;
+            if (all) film_add_whole_pass(*film, scene, (uint32_t)next);
+            else film_add_tile_pass(*film, scene, (uint32_t)next, active.data(), (uint32_t)active.size());
+            measure(all ? n_tiles : (uint32_t)active.size());
+            if (on_pass) {
+                pt_film_info info;
+                film_fill_info(*film, info);
+                pt_film_noise_stats ns{};
+                ns.mean_error = st.mean_error;
+                ns.max_block_error = st.max_tile_error;
+                ns.fraction_over = (double)st.over_tiles / (double)n_tiles;
+                ns.samples = st.samples;
+                ns.n_blocks = n_tiles;
+                ns.converged = st.converged;
+                on_pass(&info, &ns, user);
+            }
+        }
+        if (!measured) film_tile_noise(*film, params->lum_floor, params->target, st, nullptr, nullptr, nullptr);   // (no pass fits: what the film holds)
+        *out = st;
+    });
+}
+
+int pt_film_adaptive_kernel_times(pt_film* film, float lum_floor, int tonemap, uint32_t reps, float* ms_merge, float* ms_noise,
+                                  float* ms_resolve) {
+    return guarded([&] {
+        const char* who = "pt_film_adaptive_kernel_times";
+        if (!film || !ms_merge || !ms_noise || !ms_resolve || !reps) fail(PT_ERR_INVALID, "%s: null argument", who);
+        film_check_tiled(who, film);
+        film_check_noise_args(who, lum_floor, 0.0);
+        film_check_resolve(who, film, tonemap, ms_resolve, nullptr);
+        if (film->uniform()) fail(PT_ERR_INVALID, "%s: the film has taken no tile pass", who);
+        if (*std::min_element(film->tile_count.begin(), film->tile_count.end()) < 2u) fail(PT_ERR_INVALID, "%s: every pixel needs >= 2 samples", who);
+        HIP_CHECK(hipSetDevice(film->device));
+        const uint32_t n_tiles = film_n_tiles(*film);
+        if (!film->tile_sum) {
+            HIP_CHECK(hipMalloc((void**)&film->tile_sum, (size_t)n_tiles * 8u));
+            film->bytes_adaptive += (uint64_t)n_tiles * 8u;
+        }
+        // the merge of a pass of zeros and zero samples over every tile: every load, addition and store of a real pass, and the
+        // film's planes as they were (x + 0 = x for every x a sum of radiances can be)
+        std::vector<uint32_t> all(n_tiles);
+        for (uint32_t k = 0; k < n_tiles; ++k) all[k] = k;
+        const TileMap tm = make_tile_list_map(who, film->profile, film->opts, all.data(), n_tiles);
+        std::vector<uint32_t> table(tm.offsets);
+        table.insert(table.end(), tm.tiles.begin(), tm.tiles.end());
+        HIP_CHECK(hipMemcpy(film->table.p, table.data(), table.size() * 4u, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(film->pass_accum, 0, film->stride_a * sizeof(float)));
+        HIP_CHECK(hipMemset(film->pass_moments, 0, film->stride_m * sizeof(float)));
+        Staged<uint8_t> d_rgb(nullptr, (size_t)film->n_local * 3u);
+        const FilmTiling T = film_tiling(*film);
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        struct Free {
+            hipEvent_t &a, &b;
+            ~Free() {
+                if (a) (void)hipEventDestroy(a);
+                if (b) (void)hipEventDestroy(b);
+            }
+        } guard{e0, e1};
+        HIP_CHECK(hipEventCreate(&e0));
+        HIP_CHECK(hipEventCreate(&e1));
+        for (uint32_t r = 0; r < 3u * reps; ++r) {
+            const uint32_t which = r / reps;
+            HIP_CHECK(hipEventRecord(e0, 0));
+            if (which == 0)
+                hipLaunchKernelGGL(k_film_merge_tiles, dim3(n_tiles), dim3(256), 0, 0, (const float*)film->pass_accum,
+                                   (const float2*)film->pass_moments, (const uint32_t*)film->table.p, n_tiles, T, film->accum,
+                                   (float2*)film->moments, film->count, 0u);
+            else if (which == 1)
+                hipLaunchKernelGGL(k_film_tile_noise, dim3(n_tiles), dim3(256), 0, 0, (const float2*)film->moments,
+                                   (const uint32_t*)film->count, (uint32_t)film->samples, T, lum_floor, film->err, film->tile_sum,
+                                   film->tile_sum + n_tiles);
+            else
+                hipLaunchKernelGGL(k_film_post_counts, dim3(((uint32_t)film->n_local + 255u) / 256u), dim3(256), 0, 0,
+                                   (const float*)film->accum, (const uint32_t*)film->count, d_rgb.d, (uint32_t)film->n_local, tonemap);
+            HIP_CHECK(hipEventRecord(e1, 0));
+            HIP_CHECK(hipEventSynchronize(e1));
+            HIP_CHECK(hipEventElapsedTime(which == 0 ? &ms_merge[r] : which == 1 ? &ms_noise[r - reps] : &ms_resolve[r - 2u * reps], e0, e1));
         }
         HIP_CHECK(hipGetLastError());
     });

@@ -4,7 +4,9 @@
 //   path-tracer render <INPUT> [-o/--output <OUTPUT>] [-q/--quiet] [-v/--viewer]
 //                              [--debug-textures] [-p/--profile <PROFILE>] [--camera-path <CAMERAS>]
 //                              [--keyframes <FRAMES> [--light-mixer]]
-//                              [--noise-target <T> [--min-samples <N0>] [--max-samples <N>] [--noise-map <FILE.png>]]
+//                              [--noise-target <T> [--min-samples <N0>] [--max-samples <N>] [--noise-map <FILE.png>]
+//                               [--adaptive [--adaptive-tile <N>] [--uniform-samples <U>] [--adaptive-dilate <0|1>]
+//                                [--sample-map <FILE.png>]]]
 //       env OUTPUT (default render.png), env PROFILE
 //   path-tracer convert <INPUT> <OUTPUT>      (glTF 2.0 -> ISF, host/gltf_convert.cpp)
 //
@@ -21,7 +23,9 @@
 // _set_materials, and frame i is written as with --camera-path), --light-mixer (with --keyframes: frames whose only edit
 // is the colour of lights are mixed from the planes of one pt_lightmix capture instead of rendered),
 // --noise-target T (every frame is a progressive film, pt_film_render_until: passes of N0, 2 N0, 4 N0, ... samples until the
-// mean relative error of the pixels' mean luminance is <= T or the next pass would take the total above N).
+// mean relative error of the pixels' mean luminance is <= T or the next pass would take the total above N),
+// --adaptive (with --noise-target: an adaptive film, pt_film_render_until_adaptive - once every pixel has U samples the
+// passes render only the N x N tiles whose mean error is still above T, and their neighbours; N bounds the largest count).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -75,6 +79,12 @@ void usage_render(FILE* f) {
           "      --min-samples <N0>   First pass of --noise-target [>= 2, default: 8]\n"
           "      --max-samples <N>    Sample budget of --noise-target [default: the profile's samples]\n"
           "      --noise-map <FILE.png>  With --noise-target: write the per-pixel error as grey, white = 2 T and above\n"
+          "      --adaptive           With --noise-target: later passes render only the tiles whose mean error is above T; the run\n"
+          "                           ends when no tile is, or at N samples in the busiest pixel (not with --denoise)\n"
+          "      --adaptive-tile <N>  Tile size of --adaptive [a multiple of 8 with N*N a multiple of 256, default: 32]\n"
+          "      --uniform-samples <U>  Every pass of --adaptive is a whole frame until every pixel has U samples [default: 24]\n"
+          "      --adaptive-dilate <0|1>  --adaptive also renders the 8 neighbours of a tile above T [default: 1]\n"
+          "      --sample-map <FILE.png>  With --adaptive: write the per-pixel sample count as grey, white = the largest\n"
           "  -h, --help               Print help\n",
           f);
 }
@@ -140,6 +150,20 @@ void on_film_pass(const pt_film_info* info, const pt_film_noise_stats* noise, vo
             info->last_pass_samples, (unsigned long long)info->samples, noise->mean_error, noise->fraction_over);
 }
 
+// --noise-target --adaptive with -v: one line per pass
+struct AdaptivePassCtx {
+    bool verbose;
+    pt_film* film;
+};
+void on_adaptive_pass(const pt_film_info* info, const pt_film_noise_stats* noise, void* user) {
+    const AdaptivePassCtx* ctx = (const AdaptivePassCtx*)user;
+    if (!ctx->verbose) return;
+    pt_film_adaptive_info ai{};
+    if (pt_film_get_adaptive_info(ctx->film, &ai) != PT_OK) return;
+    fprintf(stderr, "film: pass %u: %u samples, %u of %u tiles, noise %.6g\n", info->passes, info->last_pass_samples,
+            ai.last_pass_tiles, ai.n_tiles, noise->mean_error);
+}
+
 // A whole non-negative decimal number that fits 32 bits, or die.
 uint32_t parse_u32(const std::string& v, const char* name) {
     if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos)
@@ -167,7 +191,9 @@ int run_render(int argc, char** argv) {
     bool have_noise_target = false, have_min_samples = false, have_max_samples = false;
     double noise_target = 0.0;
     uint32_t min_samples = 8, max_samples = 0;
-    std::string noise_map;
+    std::string noise_map, sample_map;
+    bool adaptive = false, have_adaptive_tile = false, have_uniform_samples = false, have_adaptive_dilate = false;
+    uint32_t adaptive_tile = 32, uniform_samples = 0, adaptive_dilate = 1;
     int device = 0;
     std::vector<int> devices;
     for (int i = 0; i < argc; ++i) {
@@ -221,6 +247,19 @@ int run_render(int argc, char** argv) {
             max_samples = parse_u32(value("--max-samples <N>"), "--max-samples <N>");
             have_max_samples = true;
         } else if (a == "--noise-map" || a.rfind("--noise-map=", 0) == 0) noise_map = value("--noise-map <FILE.png>");
+        else if (a == "--adaptive") adaptive = true;
+        else if (a == "--adaptive-tile" || a.rfind("--adaptive-tile=", 0) == 0) {
+            adaptive_tile = parse_u32(value("--adaptive-tile <N>"), "--adaptive-tile <N>");
+            have_adaptive_tile = true;
+        } else if (a == "--uniform-samples" || a.rfind("--uniform-samples=", 0) == 0) {
+            uniform_samples = parse_u32(value("--uniform-samples <U>"), "--uniform-samples <U>");
+            have_uniform_samples = true;
+        } else if (a == "--adaptive-dilate" || a.rfind("--adaptive-dilate=", 0) == 0) {
+            std::string v = value("--adaptive-dilate <0|1>");
+            if (v != "0" && v != "1") die("error: invalid value '" + v + "' for '--adaptive-dilate <0|1>': 0 or 1 expected");
+            adaptive_dilate = v == "1" ? 1u : 0u;
+            have_adaptive_dilate = true;
+        } else if (a == "--sample-map" || a.rfind("--sample-map=", 0) == 0) sample_map = value("--sample-map <FILE.png>");
         else if (a == "--camera-path" || a.rfind("--camera-path=", 0) == 0) {
             camera_path = value("--camera-path <CAMERAS>");
             have_camera_path = true;
@@ -269,6 +308,23 @@ int run_render(int argc, char** argv) {
             "are not gathered)");
     if (!have_noise_target && (have_min_samples || have_max_samples || !noise_map.empty()))
         die("error: '--min-samples <N0>', '--max-samples <N>' and '--noise-map <FILE.png>' need '--noise-target <T>'");
+    if (adaptive && !have_noise_target) die("error: '--adaptive' needs '--noise-target <T>'");
+    if (!adaptive && (have_adaptive_tile || have_uniform_samples || have_adaptive_dilate || !sample_map.empty()))
+        die("error: '--adaptive-tile <N>', '--uniform-samples <U>', '--adaptive-dilate <0|1>' and '--sample-map <FILE.png>' need "
+            "'--noise-target <T> --adaptive'");
+    if (adaptive && denoise)
+        die("error: the argument '--adaptive' cannot be used with '--denoise' or '--denoise-variance' (the filters take one sample "
+            "count for the whole frame)");
+    if (adaptive && devices.size() > 1)
+        die("error: the argument '--adaptive' cannot be used with more than one device in '--devices <A,B,..>' (an adaptive film "
+            "lives on one device)");
+    if (adaptive && (adaptive_tile == 0 || adaptive_tile > 4096 || (adaptive_tile & 7u) || ((adaptive_tile * adaptive_tile) & 255u)))
+        die("error: invalid value '" + std::to_string(adaptive_tile) + "' for '--adaptive-tile <N>': a multiple of 8 with N*N a multiple of 256 expected");
+    if (!sample_map.empty()) {
+        std::string ext = sample_map.size() >= 4 ? sample_map.substr(sample_map.size() - 4) : "";
+        for (char& c : ext) c = (char)tolower(c);
+        if (ext != ".png") die("The image format could not be determined (only .png output is supported): " + sample_map);
+    }
     if (have_noise_target && light_mixer)
         die("error: the argument '--noise-target <T>' cannot be used with '--light-mixer' (mixed frames have no samples to add to)");
     if (have_noise_target && devices.size() > 1)
@@ -552,14 +608,41 @@ int run_render(int argc, char** argv) {
     };
     // --noise-target: one film for the run; every frame starts it from zero passes
     pt_film* film = nullptr;
-    if (have_noise_target && pt_film_create(device, &profile, &opts, &film) != PT_OK) die(pt_last_error());
+    pt_opts film_opts = opts;
+    if (adaptive) film_opts.tile_w = film_opts.tile_h = adaptive_tile;   // (the film's tiling is what its passes select by)
+    if (have_noise_target && pt_film_create(device, &profile, &film_opts, &film) != PT_OK) die(pt_last_error());
     const size_t n_pixels = (size_t)profile.width * profile.height;
+    // one frame's map, grey: the frame index goes in front of the extension when there are several
+    auto write_map = [&](const std::string& map, size_t f, const std::vector<uint8_t>& grey) {
+        std::string name = map;
+        if (n_frames > 1) {
+            char num[32];
+            snprintf(num, sizeof num, "_%zu", f);
+            name = map.substr(0, map.size() - 4) + num + map.substr(map.size() - 4);
+        }
+        if (pth_png_write_rgb8(name.c_str(), profile.width, profile.height, grey.data()) != PT_OK) die(pth_last_error());
+    };
+    auto to_grey = [](float v) { return (uint8_t)(!(v == v) || v <= 0.f ? 0 : (v >= 255.f ? 255 : (uint8_t)v)); };
     auto render_film = [&](size_t f) {
         if (f > 0 && pt_film_reset(film) != PT_OK) die(pt_last_error());
         pt_film_noise_stats noise{};
-        if (pt_film_render_until(film, scene, min_samples, max_samples, PT_FILM_DEFAULT_LUM_FLOOR, noise_target, on_film_pass, &viewer,
-                                 &noise) != PT_OK)
+        pt_film_tile_stats tiles{};
+        if (adaptive) {
+            pt_film_adaptive_params ap;
+            pt_film_adaptive_params_default(&ap);
+            ap.target = noise_target;
+            ap.first_pass_samples = min_samples;
+            ap.max_samples = max_samples;
+            if (have_uniform_samples) ap.uniform_samples = uniform_samples;
+            if (have_adaptive_dilate) ap.dilate = adaptive_dilate;
+            AdaptivePassCtx ctx{viewer, film};
+            if (pt_film_render_until_adaptive(film, scene, &ap, on_adaptive_pass, &ctx, &tiles) != PT_OK) die(pt_last_error());
+            noise.mean_error = tiles.mean_error;
+            noise.converged = tiles.converged;
+        } else if (pt_film_render_until(film, scene, min_samples, max_samples, PT_FILM_DEFAULT_LUM_FLOOR, noise_target, on_film_pass,
+                                        &viewer, &noise) != PT_OK) {
             die(pt_last_error());
+        }
         pt_film_info info{};
         if (pt_film_get_info(film, &info) != PT_OK) die(pt_last_error());
         if (denoise) {   // the film's planes through the filter, samples = the film's total
@@ -576,24 +659,29 @@ int run_render(int argc, char** argv) {
         }
         if (!noise_map.empty()) {   // grey = as_u8(min(1, err / (2 T)) * 255)
             std::vector<float> err(n_pixels);
-            if (pt_film_noise(film, PT_FILM_DEFAULT_LUM_FLOOR, noise_target, &noise, err.data(), nullptr, nullptr) != PT_OK) die(pt_last_error());
+            if ((adaptive ? pt_film_tile_noise(film, PT_FILM_DEFAULT_LUM_FLOOR, noise_target, &tiles, err.data(), nullptr, nullptr)
+                          : pt_film_noise(film, PT_FILM_DEFAULT_LUM_FLOOR, noise_target, &noise, err.data(), nullptr, nullptr)) != PT_OK)
+                die(pt_last_error());
             std::vector<uint8_t> grey(n_pixels * 3);
             const float full = 2.0f * (float)noise_target;
-            for (size_t i = 0; i < n_pixels; ++i) {
-                const float v = fminf(1.0f, err[i] / full) * 255.0f;
-                const uint8_t g = !(v == v) || v <= 0.f ? 0 : (v >= 255.f ? 255 : (uint8_t)v);
-                grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = g;
-            }
-            std::string name = noise_map;
-            if (n_frames > 1) {   // one map per frame: the frame index goes in front of the extension
-                char num[32];
-                snprintf(num, sizeof num, "_%zu", f);
-                name = noise_map.substr(0, noise_map.size() - 4) + num + noise_map.substr(noise_map.size() - 4);
-            }
-            if (pth_png_write_rgb8(name.c_str(), profile.width, profile.height, grey.data()) != PT_OK) die(pth_last_error());
+            for (size_t i = 0; i < n_pixels; ++i) grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = to_grey(fminf(1.0f, err[i] / full) * 255.0f);
+            write_map(noise_map, f, grey);
         }
-        fprintf(stderr, "film: %u passes, %llu samples, noise %.6g, %s\n", info.passes, (unsigned long long)info.samples, noise.mean_error,
-                noise.converged ? "converged" : "max samples");
+        if (!sample_map.empty()) {   // grey = as_u8(count / max_count * 255)
+            std::vector<uint32_t> counts(n_pixels);
+            if (pt_film_read_counts(film, counts.data()) != PT_OK) die(pt_last_error());
+            std::vector<uint8_t> grey(n_pixels * 3);
+            for (size_t i = 0; i < n_pixels; ++i)
+                grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = to_grey((float)counts[i] / (float)info.samples * 255.0f);
+            write_map(sample_map, f, grey);
+        }
+        if (adaptive)
+            fprintf(stderr, "film: %u passes, %llu samples, noise %.6g, %s, pixel-samples %llu of %llu\n", info.passes,
+                    (unsigned long long)info.samples, noise.mean_error, noise.converged ? "converged" : "max samples",
+                    (unsigned long long)tiles.pixel_samples, (unsigned long long)(info.n_local * info.samples));
+        else
+            fprintf(stderr, "film: %u passes, %llu samples, noise %.6g, %s\n", info.passes, (unsigned long long)info.samples, noise.mean_error,
+                    noise.converged ? "converged" : "max samples");
     };
     pt_lightmix* mix = nullptr;
     bool mixer_on = light_mixer;

@@ -706,6 +706,84 @@ int  pt_film_adaptive_kernel_times(pt_film* film, float lum_floor, int tonemap, 
                                    float* ms_resolve);
 
 /* ------------------------------------------------------------------ */
+/* film filter                                             */
+/* ------------------------------------------------------------------ */
+
+/* The a-trous filters on a film's own device planes, uniform or not, and the error figure of the filtered mean.  The film needs a
+ * profile and shard_count <= 1 (its planes are then in image order, width x height).  variance = 0 is pt_denoise's filter,
+ * variance = 1 pt_denoise_var's; params are theirs, with their rules.  guides: the planes of pt_render_guides for the film's view.
+ *
+ *   prep     exactly pt_denoise's / pt_denoise_var's prep with the pixel's own count for `samples`: N = (float)count[p], and the
+ *            divisor of the sample variance is (float)(count[p] - 1); count[p] is the film's total on a uniform film.
+ *   passes   theirs, unchanged.
+ *   finish   theirs: color [n_local x 3 f32] the filtered mean radiance, rgb8 its tone-mapped form (params->tonemap).
+ *   ferr     [n_local f32], variance = 1 only (variance = 0 with ferr != NULL: PT_ERR_INVALID).  All f32, one IEEE operation per
+ *            step in this order, uncontracted, IEEE divide and sqrt (tests/film_denoise_model.py restates it bit for bit):
+ *              a filtered pixel (depth >= 0, iterations > 0):   vf = v of the last pass (v = vacc / (wsum * wsum));
+ *                  if demodulating:  ld = lum(d);  vf = vf * (ld * ld);
+ *                  se = sqrt(vf);  den = max(lum(out), lum_floor);  ferr = se / den       (out: the pixel's color)
+ *              any other pixel (depth < 0, or iterations = 0):  pt_film_noise's err with n = count[p].
+ *   iterations = 0: color and rgb8 are pt_film_resolve's (params->tonemap), on any film.
+ *   On a uniform film color and rgb8 equal, bit for bit, pt_denoise_device / pt_denoise_var_device on pt_film_planes_device with
+ *   samples = info.samples.
+ *
+ * WHAT ferr IS NOT.  It is the standard error the filter's own weights would give the filtered mean if the taps were
+ * independent and the filter unbiased.  It ignores the filter's bias (blur across detail the guides do not see), and it
+ * ignores the correlation between neighbouring filtered pixels (after the first pass the taps share samples; v is propagated
+ * as if they did not, as in SVGF).  It is a stopping heuristic, not an error bound.
+ *
+ * PT_ERR_INVALID before any device work, the outputs untouched: a null film, params, guides / scene, or no output at all; a
+ * null scratch with iterations > 0; a film without a profile; a sharded film; a pixel with no samples; variance = 1 with a pixel
+ * below 2 samples; a scene on another device than the film's; what pt_denoise / pt_denoise_var refuse in params; a lum_floor
+ * that is not positive and finite; variance other than 0 or 1.
+ *
+ * pt_film_denoise_device takes the caller's scratch (pt_film_denoise_scratch_bytes, 256-byte aligned: the filter's planes, a
+ * ferr plane and two tile arrays; 0 for a film that is refused), allocates nothing and is asynchronous on hip_stream; each of
+ * d_out_color, d_out_rgb8, d_out_ferr may be NULL, not all.  The host forms render the guides from `scene` and block; their
+ * scratch (the same bytes and a plane of guides) is allocated inside the film by the first such call, counted in
+ * info.device_bytes from then on, kept by pt_film_reset and freed by pt_film_destroy.  A film that never calls them allocates
+ * nothing new.
+ *
+ * pt_film_tile_reduce_device (a test and measurement hook: the reduction pt_film_filtered_noise runs, on a plane of the caller's):
+ * pt_film_tile_noise's "per tile t" steps, word for word, over an error plane d_err [n_local f32,
+ * image order] that exists already, into d_tile_sum and d_tile_max [n_tiles f32 each]; asynchronous on hip_stream.
+ *
+ * pt_film_filtered_noise: the guides of `scene`, the variance filter, ferr, the tile reduction over ferr, then the host f64 step
+ * of pt_film_tile_noise (mean_t, mean_error, max_tile_error, over_tiles, converged, samples, pixel_samples).  ferr_host,
+ * tile_sum_host, tile_max_host may be NULL.  Refusals: pt_film_denoise's with variance = 1, and pt_film_tile_noise's target.
+ *
+ * pt_film_render_until_filtered is pt_film_render_until_adaptive's loop, step for step, with params->adaptive - except that step
+ * (4) is pt_film_filtered_noise(params->filter, lum_floor, target): tiles are selected by the error of the FILTERED image.  The
+ * guides are rendered once, when the function is entered (the film does not watch the scene).  The selection is a pure
+ * function of the film's planes, the guides and the parameters - the guides stay in the film's scratch for the whole call, so
+ * on_pass MUST NOT call pt_film_denoise, pt_film_filtered_noise or pt_film_denoise_kernel_times on this film (they render
+ * their own guides into the same plane); the device form with the caller's scratch, pt_film_read, pt_film_read_counts and
+ * pt_film_resolve are fine there.  Refusals, before any device work and before the scratch is made:
+ * pt_film_render_until_adaptive's, pt_denoise_var's parameter rules, and - on a film that is measured as it stands (it has
+ * uniform_samples already, or no pass fits the budget) - a pixel below 2 samples. */
+typedef struct pt_film_filtered_params {
+    pt_film_adaptive_params adaptive;
+    pt_denoise_params filter;
+} pt_film_filtered_params;
+void pt_film_filtered_params_default(pt_film_filtered_params* params);   /* adaptive defaults + pt_denoise_var defaults */
+uint64_t pt_film_denoise_scratch_bytes(const pt_film* film);
+int  pt_film_denoise_device(const pt_film* film, int variance /* 0 plain, 1 variance-guided */, const pt_denoise_params* params,
+                            float lum_floor, const void* d_guides, void* d_out_color, void* d_out_rgb8,
+                            void* d_out_ferr /* variance only, may be NULL */, void* d_scratch, void* hip_stream);
+int  pt_film_denoise(const pt_film* film, const pt_scene* scene /* guides are rendered from it */, int variance,
+                     const pt_denoise_params* params, float lum_floor, uint8_t* rgb8, float* color, float* ferr);   /* host */
+/* test / measurement hook */
+int  pt_film_tile_reduce_device(const pt_film* film, const void* d_err, void* d_tile_sum, void* d_tile_max, void* hip_stream);
+int  pt_film_filtered_noise(const pt_film* film, const pt_scene* scene, const pt_denoise_params* params, float lum_floor,
+                            double target, pt_film_tile_stats* out, float* ferr_host, float* tile_sum_host, float* tile_max_host);
+int  pt_film_render_until_filtered(pt_film* film, const pt_scene* scene, const pt_film_filtered_params* params,
+                                   pt_film_pass_fn on_pass, void* user, pt_film_tile_stats* out);
+/* Measurement, like the other *_times: the variance filter with ferr and the tile reduction on the null stream, HIP events
+ * between the stages; blocks.  ms_prep[r], ms_passes[r] (all passes), ms_finish[r] (finish + ferr), ms_reduce[r], reps each. */
+int  pt_film_denoise_kernel_times(const pt_film* film, const pt_scene* scene, const pt_denoise_params* params, float lum_floor,
+                                  uint32_t reps, float* ms_prep, float* ms_passes, float* ms_finish, float* ms_reduce);
+
+/* ------------------------------------------------------------------ */
 /* measurement                                                         */
 /* ------------------------------------------------------------------ */
 

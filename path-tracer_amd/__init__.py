@@ -200,6 +200,24 @@ class FilmAdaptiveParams(C.Structure):
         return p
 
 
+class FilmFilteredParams(C.Structure):
+    """pt_film_filtered_params: the adaptive loop's settings and the variance filter's."""
+    _fields_ = [("adaptive", FilmAdaptiveParams), ("filter", DenoiseParams)]
+
+    @classmethod
+    def default(cls, filter=None, **changes):
+        """pt_film_filtered_params_default; keywords replace fields of .adaptive, `filter` (a DenoiseParams) replaces .filter."""
+        p = cls()
+        gpu_lib().pt_film_filtered_params_default(C.byref(p))
+        for k, v in changes.items():
+            if k not in dict(FilmAdaptiveParams._fields_):
+                raise TypeError(f"pt_film_adaptive_params has no field {k!r}")
+            setattr(p.adaptive, k, v)
+        if filter is not None:
+            p.filter = filter
+        return p
+
+
 class Hit(C.Structure):
     _fields_ = [("prim", C.c_int32), ("flags", C.c_int32), ("dist", C.c_float), ("u", C.c_float),
                 ("v", C.c_float)]
@@ -308,7 +326,10 @@ GPU_SYMBOLS = ["pt_scene_create", "pt_scene_destroy", "pt_scene_set_camera", "pt
                "pt_tiles_pixel_count", "pt_tiles_pixel_map", "pt_render_tiles", "pt_render_tiles_device",
                "pt_film_add_tile_pass", "pt_film_add_tile_planes", "pt_film_read_counts", "pt_film_tile_noise",
                "pt_film_get_adaptive_info", "pt_film_render_until_adaptive", "pt_film_adaptive_params_default",
-               "pt_film_adaptive_kernel_times"]
+               "pt_film_adaptive_kernel_times",
+               "pt_film_filtered_params_default", "pt_film_denoise_scratch_bytes", "pt_film_denoise_device", "pt_film_denoise",
+               "pt_film_tile_reduce_device", "pt_film_filtered_noise", "pt_film_render_until_filtered",
+               "pt_film_denoise_kernel_times"]
 
 
 def host_lib():
@@ -501,6 +522,18 @@ def gpu_lib():
             L.pt_film_adaptive_params_default.argtypes = [C.POINTER(FilmAdaptiveParams)]
             L.pt_film_adaptive_params_default.restype = None
             L.pt_film_adaptive_kernel_times.argtypes = [vp, C.c_float, C.c_int, C.c_uint32, vp, vp, vp]
+        if hasattr(L, "pt_film_denoise"):   # (an A/B library of an earlier commit has no film filter)
+            L.pt_film_filtered_params_default.argtypes = [C.POINTER(FilmFilteredParams)]
+            L.pt_film_filtered_params_default.restype = None
+            L.pt_film_denoise_scratch_bytes.argtypes = [vp]
+            L.pt_film_denoise_scratch_bytes.restype = C.c_uint64
+            L.pt_film_denoise_device.argtypes = [vp, C.c_int, dp, C.c_float, vp, vp, vp, vp, vp, vp]
+            L.pt_film_denoise.argtypes = [vp, vp, C.c_int, dp, C.c_float, vp, vp, vp]
+            L.pt_film_tile_reduce_device.argtypes = [vp, vp, vp, vp, vp]
+            L.pt_film_filtered_noise.argtypes = [vp, vp, dp, C.c_float, C.c_double, C.POINTER(FilmTileStats), vp, vp, vp]
+            L.pt_film_render_until_filtered.argtypes = [vp, vp, C.POINTER(FilmFilteredParams), FILM_PASS_FN, vp,
+                                                        C.POINTER(FilmTileStats)]
+            L.pt_film_denoise_kernel_times.argtypes = [vp, vp, dp, C.c_float, C.c_uint32, vp, vp, vp, vp]
         L.pt_last_error.restype = C.c_char_p
         L.pt_version.restype = C.c_char_p
         _gpu = L
@@ -1444,6 +1477,71 @@ class Film:
         check_gpu(self.lib.pt_film_adaptive_kernel_times(self.handle, lum_floor, self._tonemap(tonemap), reps, a.ctypes.data,
                                                          b.ctypes.data, c.ctypes.data))
         return a, b, c
+
+    # ---- the film filter
+    def denoise_scratch_bytes(self):
+        return int(self.lib.pt_film_denoise_scratch_bytes(self.handle))
+
+    def denoise(self, scene, params, variance=True, lum_floor=PT_FILM_DEFAULT_LUM_FLOOR, want_ferr=False):
+        """pt_film_denoise: the a-trous filter (variance-guided, or plain) on the film's planes with guides rendered from a
+        GpuScene; (color [n_local, 3] float32, rgb8 [n_local, 3] uint8), with want_ferr (variance only) also ferr [n_local]."""
+        import numpy as np
+        n = int(self.info.n_local)
+        col, rgb = np.empty((n, 3), np.float32), np.empty((n, 3), np.uint8)
+        ferr = np.empty(n, np.float32) if want_ferr else None
+        check_gpu(self.lib.pt_film_denoise(self.handle, scene.handle, int(variance), C.byref(params), lum_floor, rgb.ctypes.data,
+                                           col.ctypes.data, ferr.ctypes.data if want_ferr else None))
+        return (col, rgb, ferr) if want_ferr else (col, rgb)
+
+    def denoise_device(self, params, variance, d_guides, d_color, d_rgb8, d_ferr, d_scratch, lum_floor=PT_FILM_DEFAULT_LUM_FLOOR,
+                       stream=0):
+        """pt_film_denoise_device: device pointers (outputs may be 0 / None, not all), asynchronous on `stream`."""
+        check_gpu(self.lib.pt_film_denoise_device(self.handle, int(variance), C.byref(params), lum_floor, d_guides, d_color or None,
+                                                  d_rgb8 or None, d_ferr or None, d_scratch or None, stream))
+
+    def tile_reduce_device(self, d_err, d_tile_sum, d_tile_max, stream=0):
+        """pt_film_tile_reduce_device: the tile sums and maxima of an error plane on the device."""
+        check_gpu(self.lib.pt_film_tile_reduce_device(self.handle, d_err, d_tile_sum, d_tile_max, stream))
+
+    def filtered_noise(self, scene, params, target, lum_floor=PT_FILM_DEFAULT_LUM_FLOOR, want_planes=False):
+        """pt_film_filtered_noise: FilmTileStats of the filtered image's error; with want_planes (FilmTileStats,
+        ferr [n_local], tile_sum [n_tiles], tile_max [n_tiles])."""
+        import numpy as np
+        out = FilmTileStats()
+        if not want_planes:
+            check_gpu(self.lib.pt_film_filtered_noise(self.handle, scene.handle, C.byref(params), lum_floor, target, C.byref(out),
+                                                      None, None, None))
+            return out
+        n, nt = int(self.info.n_local), int(self.adaptive_info.n_tiles)
+        ferr, tsum, tmax = np.empty(n, np.float32), np.empty(nt, np.float32), np.empty(nt, np.float32)
+        check_gpu(self.lib.pt_film_filtered_noise(self.handle, scene.handle, C.byref(params), lum_floor, target, C.byref(out),
+                                                  ferr.ctypes.data, tsum.ctypes.data, tmax.ctypes.data))
+        return out, ferr, tsum, tmax
+
+    def render_until_filtered(self, scene, params, on_pass=None):
+        """pt_film_render_until_filtered: render_until_adaptive with the tiles selected by the error of the filtered image
+        (params: FilmFilteredParams); on_pass(FilmInfo, FilmNoise) after every pass.  Returns the last FilmTileStats."""
+        out = FilmTileStats()
+        failure = []
+
+        def trampoline(info, noise, _user):
+            try:
+                on_pass(_copy(FilmInfo, info.contents), _copy(FilmNoise, noise.contents))
+            except BaseException as e:   # (an exception cannot cross the C frames: raised after the call)
+                failure.append(e)
+        cb = FILM_PASS_FN(trampoline) if on_pass is not None else C.cast(None, FILM_PASS_FN)
+        check_gpu(self.lib.pt_film_render_until_filtered(self.handle, scene.handle, C.byref(params), cb, None, C.byref(out)))
+        if failure:
+            raise failure[0]
+        return out
+
+    def denoise_kernel_times(self, scene, params, lum_floor=PT_FILM_DEFAULT_LUM_FLOOR, reps=20):
+        """pt_film_denoise_kernel_times: ms of (prep, all passes, finish + ferr, tile reduce), [reps] each."""
+        import numpy as np
+        t = [np.zeros(reps, np.float32) for _ in range(4)]
+        check_gpu(self.lib.pt_film_denoise_kernel_times(self.handle, scene.handle, C.byref(params), lum_floor, reps,
+                                                        *(a.ctypes.data for a in t)))
+        return tuple(t)
 
     def close(self):
         if self.handle:

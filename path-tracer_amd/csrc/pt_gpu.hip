@@ -48,6 +48,7 @@
 #include "pt_variance.h"
 #include "pt_lightmix.h"
 #include "pt_film.h"
+#include "pt_film_denoise.h"
 #include "pthost.h"
 #include "../host/scene_check.h"
 
@@ -3759,6 +3760,28 @@ bool dn_use_lds() {
     return !(e && *e == '0');
 }
 
+// The passes of pt_denoise over prepared planes; on return X holds the last pass's output.  ev: an event after every pass.
+void dn_passes(uint32_t width, uint32_t height, const pt_denoise_params& p, float4*& X, float4*& Y, const float4* U, const float2* G,
+               hipStream_t stream, hipEvent_t* ev, size_t& e) {
+    const dim3 grid((width + DN_TILE_W - 1u) / DN_TILE_W, (height + DN_TILE_H - 1u) / DN_TILE_H);
+    const bool lds = dn_use_lds();
+    for (uint32_t i = 0; i < p.iterations; ++i) {
+        DnParams P;
+        P.sigma_depth = p.sigma_depth;
+        const float sc = p.sigma_color * (1.0f / (float)(1u << i));
+        P.sc2 = sc * sc;
+        P.npow = p.normal_power_log2;
+        P.color_on = p.sigma_color != 0.f;
+        const int step = 1 << i;
+        if (lds && i == 0) hipLaunchKernelGGL(k_dn_pass<1>, grid, dim3(256), 0, stream, (const float4*)X, U, G, Y, (int)width, (int)height, step, P);
+        else if (lds && i == 1) hipLaunchKernelGGL(k_dn_pass<2>, grid, dim3(256), 0, stream, (const float4*)X, U, G, Y, (int)width, (int)height, step, P);
+        else hipLaunchKernelGGL(k_dn_pass<0>, grid, dim3(256), 0, stream, (const float4*)X, U, G, Y, (int)width, (int)height, step, P);
+        HIP_CHECK(hipGetLastError());
+        if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
+        std::swap(X, Y);
+    }
+}
+
 // prep, the passes and finish on `stream`; ev (measurement only): 2 + iterations + 1 events recorded between the stages
 void denoise_launch(uint32_t width, uint32_t height, uint32_t samples, const pt_denoise_params& p, const float* d_accum,
                     const float4* d_guides, float* d_out_color, uint8_t* d_out_rgb8, uint8_t* d_scratch, hipStream_t stream,
@@ -3783,27 +3806,28 @@ void denoise_launch(uint32_t width, uint32_t height, uint32_t samples, const pt_
     hipLaunchKernelGGL(k_dn_prep, dim3(blocks), dim3(256), 0, stream, d_accum, d_guides, width, height, samples, no_demod, X, U, G, D);
     HIP_CHECK(hipGetLastError());
     if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
-    const dim3 grid((width + DN_TILE_W - 1u) / DN_TILE_W, (height + DN_TILE_H - 1u) / DN_TILE_H);
-    const bool lds = dn_use_lds();
-    for (uint32_t i = 0; i < p.iterations; ++i) {
-        DnParams P;
-        P.sigma_depth = p.sigma_depth;
-        const float sc = p.sigma_color * (1.0f / (float)(1u << i));
-        P.sc2 = sc * sc;
-        P.npow = p.normal_power_log2;
-        P.color_on = p.sigma_color != 0.f;
-        const int step = 1 << i;
-        if (lds && i == 0) hipLaunchKernelGGL(k_dn_pass<1>, grid, dim3(256), 0, stream, (const float4*)X, (const float4*)U, (const float2*)G, Y, (int)width, (int)height, step, P);
-        else if (lds && i == 1) hipLaunchKernelGGL(k_dn_pass<2>, grid, dim3(256), 0, stream, (const float4*)X, (const float4*)U, (const float2*)G, Y, (int)width, (int)height, step, P);
-        else hipLaunchKernelGGL(k_dn_pass<0>, grid, dim3(256), 0, stream, (const float4*)X, (const float4*)U, (const float2*)G, Y, (int)width, (int)height, step, P);
-        HIP_CHECK(hipGetLastError());
-        if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
-        std::swap(X, Y);
-    }
+    dn_passes(width, height, p, X, Y, U, G, stream, ev, e);
     hipLaunchKernelGGL(k_dn_finish, dim3(blocks), dim3(256), 0, stream, (const float4*)X, (const float*)D, d_accum, samples, n, no_demod,
                        p.tonemap, d_out_color, d_out_rgb8);
     HIP_CHECK(hipGetLastError());
     if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
+}
+
+// The passes of pt_denoise_var over prepared planes, like dn_passes.
+void dnv_passes(uint32_t width, uint32_t height, const pt_denoise_params& p, float4*& X, float4*& Y, const float4* U, const float2* G,
+                hipStream_t stream, hipEvent_t* ev, size_t& e) {
+    const dim3 grid((width + DN_TILE_W - 1u) / DN_TILE_W, (height + DN_TILE_H - 1u) / DN_TILE_H);
+    DnvParams P;
+    P.sigma_depth = p.sigma_depth;
+    P.sigma_lum = p.sigma_color;
+    P.npow = p.normal_power_log2;
+    for (uint32_t i = 0; i < p.iterations; ++i) {
+        hipLaunchKernelGGL(k_dnv_pass, grid, dim3(256), 0, stream, (const float4*)X, U, G, Y,
+                           (int)width, (int)height, 1 << i, P);
+        HIP_CHECK(hipGetLastError());
+        if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
+        std::swap(X, Y);
+    }
 }
 
 // The variance-guided filter (pt_variance.h) on the planes of dn_scratch_layout: X / Y carry (x, v), U carries (u, z).
@@ -3831,18 +3855,7 @@ void denoise_var_launch(uint32_t width, uint32_t height, uint32_t samples, const
                        no_demod, X, U, G, D);
     HIP_CHECK(hipGetLastError());
     if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
-    const dim3 grid((width + DN_TILE_W - 1u) / DN_TILE_W, (height + DN_TILE_H - 1u) / DN_TILE_H);
-    DnvParams P;
-    P.sigma_depth = p.sigma_depth;
-    P.sigma_lum = p.sigma_color;
-    P.npow = p.normal_power_log2;
-    for (uint32_t i = 0; i < p.iterations; ++i) {
-        hipLaunchKernelGGL(k_dnv_pass, grid, dim3(256), 0, stream, (const float4*)X, (const float4*)U, (const float2*)G, Y,
-                           (int)width, (int)height, 1 << i, P);
-        HIP_CHECK(hipGetLastError());
-        if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
-        std::swap(X, Y);
-    }
+    dnv_passes(width, height, p, X, Y, U, G, stream, ev, e);
     // (an invalid pixel carries v = -1 in X.w: k_dn_finish's validity test)
     hipLaunchKernelGGL(k_dn_finish, dim3(blocks), dim3(256), 0, stream, (const float4*)X, (const float*)D, d_accum, samples, n, no_demod,
                        p.tonemap, d_out_color, d_out_rgb8);
@@ -4009,8 +4022,13 @@ struct pt_film {
     std::vector<uint64_t> tile_count;
     uint64_t bytes_adaptive = 0;
     uint32_t tile_passes = 0, last_pass_tiles = 0;   // (last_pass_tiles: of the last pass; 0: a whole frame, or no pass yet)
+    // The film filter: the scratch of pt_film_denoise_scratch_bytes and, behind it, a plane of guides - made by the
+    // first host call of the pt_film_denoise family, kept by pt_film_reset.
+    uint8_t* filter = nullptr;
+    uint64_t bytes_filter = 0;
     bool uniform() const { return count == nullptr; }
     ~pt_film() {
+        if (filter) (void)hipFree(filter);
         if (base) (void)hipFree(base);
         if (count) (void)hipFree(count);
         if (tile_sum) (void)hipFree(tile_sum);
@@ -4218,6 +4236,31 @@ void film_add_whole_pass(pt_film& film, const pt_scene* scene, uint32_t samples)
     film_add_tile_pass(film, scene, samples, all.data(), (uint32_t)all.size());
 }
 
+// The host step of pt_film_tile_noise: the statistics, in f64, of one tile sum per tile of the film.
+void film_tile_stats(const pt_film& film, const std::vector<float>& sums, double target, pt_film_tile_stats& out) {
+    const FilmTiling T = film_tiling(film);
+    const uint32_t n_tiles = (uint32_t)sums.size();
+    double S = 0.0, worst = 0.0;
+    uint32_t over = 0;
+    uint64_t pixel_samples = 0;
+    for (uint32_t t = 0; t < n_tiles; ++t) {
+        const uint64_t pixels = film_tile_pixels(T, t);
+        const double mean_t = (double)sums[t] / (double)pixels;
+        S = S + (double)sums[t];
+        if (t == 0 || mean_t > worst) worst = mean_t;
+        if (mean_t > target) ++over;
+        pixel_samples += pixels * (film.uniform() ? film.samples : film.tile_count[t]);
+    }
+    memset(&out, 0, sizeof out);
+    out.mean_error = S / (double)film.n_local;
+    out.max_tile_error = worst;
+    out.samples = film.samples;
+    out.pixel_samples = pixel_samples;
+    out.n_tiles = n_tiles;
+    out.over_tiles = over;
+    out.converged = over == 0u ? 1u : 0u;
+}
+
 void film_tile_noise(const pt_film& film_c, float lum_floor, double target, pt_film_tile_stats& out, float* err_host,
                      float* tile_sum_host, float* tile_max_host) {
     const char* who = "pt_film_tile_noise";
@@ -4242,25 +4285,7 @@ void film_tile_noise(const pt_film& film_c, float lum_floor, double target, pt_f
     if (tile_sum_host) memcpy(tile_sum_host, sums.data(), n_tiles * sizeof(float));
     if (tile_max_host) HIP_CHECK(hipMemcpy(tile_max_host, tile_max, n_tiles * sizeof(float), hipMemcpyDeviceToHost));
     if (err_host) HIP_CHECK(hipMemcpy(err_host, film.err, film.n_local * sizeof(float), hipMemcpyDeviceToHost));
-    double S = 0.0, worst = 0.0;
-    uint32_t over = 0;
-    uint64_t pixel_samples = 0;
-    for (uint32_t t = 0; t < n_tiles; ++t) {
-        const uint64_t pixels = film_tile_pixels(T, t);
-        const double mean_t = (double)sums[t] / (double)pixels;
-        S = S + (double)sums[t];
-        if (t == 0 || mean_t > worst) worst = mean_t;
-        if (mean_t > target) ++over;
-        pixel_samples += pixels * (film.uniform() ? film.samples : film.tile_count[t]);
-    }
-    memset(&out, 0, sizeof out);
-    out.mean_error = S / (double)film.n_local;
-    out.max_tile_error = worst;
-    out.samples = film.samples;
-    out.pixel_samples = pixel_samples;
-    out.n_tiles = n_tiles;
-    out.over_tiles = over;
-    out.converged = over == 0u ? 1u : 0u;
+    film_tile_stats(film, sums, target, out);
 }
 
 void film_fill_info(const pt_film& film, pt_film_info& info) {
@@ -4271,7 +4296,7 @@ void film_fill_info(const pt_film& film, pt_film_info& info) {
     info.last_pass_samples = film.last_pass_samples;
     info.n_local = film.n_local;
     info.samples = film.samples;
-    info.device_bytes = film.bytes + film.bytes_adaptive;
+    info.device_bytes = film.bytes + film.bytes_adaptive + film.bytes_filter;
 }
 
 void film_check_resolve(const char* who, const pt_film* film, int tonemap_type, const void* rgb8, const void* color) {
@@ -4304,6 +4329,193 @@ void film_resolve_launch(const pt_film& film, int tonemap_type, uint8_t* d_rgb8,
         hipLaunchKernelGGL(k_postprocess, dim3(((uint32_t)film.n_local + 255u) / 256u), dim3(256), 0, stream, (const float*)film.accum,
                            d_rgb8, (uint32_t)film.n_local, (uint32_t)film.samples, tonemap_type);
     HIP_CHECK(hipGetLastError());
+}
+
+// What the adaptive loops refuse before any device work (the null checks are the callers').
+void film_check_adaptive(const char* who, const pt_film* film, const pt_scene* scene, const pt_film_adaptive_params* params) {
+    film_check_tiled(who, film);
+    film_check_noise_args(who, params->lum_floor, params->target);
+    if (params->first_pass_samples < 2u) fail(PT_ERR_INVALID, "%s: first_pass_samples must be >= 2 (a sample variance needs two)", who);
+    if (params->dilate > 1u) fail(PT_ERR_INVALID, "%s: dilate must be 0 or 1", who);
+    if (!film->passes && (uint64_t)params->first_pass_samples > params->max_samples)
+        fail(PT_ERR_INVALID, "%s: first_pass_samples %u exceeds max_samples %llu", who, params->first_pass_samples, (unsigned long long)params->max_samples);
+    if (scene->device != film->device)
+        fail(PT_ERR_INVALID, "%s: the scene is on device %d, the film on device %d", who, scene->device, film->device);
+}
+
+// The loop of pt_film_render_until_adaptive (include/ptgpu.h, steps 1 - 8).  noise(st, sums): step 4 - the tile statistics of
+// what the film holds and, where sums is not null, the n_tiles tile sums the selection reads.
+template <class Noise>
+void film_adaptive_loop(pt_film* film, const pt_scene* scene, const pt_film_adaptive_params* params, pt_film_pass_fn on_pass,
+                        void* user, pt_film_tile_stats* out, Noise noise) {
+    const uint64_t cap = std::min<uint64_t>(params->max_samples, (uint64_t)PT_FILM_MAX_SAMPLES);
+    const FilmTiling T = film_tiling(*film);
+    const uint32_t n_tiles = film_n_tiles(*film), tiles_y = n_tiles / T.tiles_x;
+    std::vector<float> sums(n_tiles);
+    std::vector<uint32_t> active;   // the tiles of the next pass; empty: every tile
+    pt_film_tile_stats st{};
+    bool measured = false;
+    auto measure = [&](uint32_t rendered) {
+        noise(st, sums.data());
+        st.active_tiles = rendered;
+        measured = true;
+        // the candidates - the tiles above the target - and, dilate: their 8 neighbours
+        std::vector<uint8_t> on(n_tiles, 0);
+        for (uint32_t t = 0; t < n_tiles; ++t) {
+            if (!((double)sums[t] / (double)film_tile_pixels(T, t) > params->target)) continue;
+            const int tx = (int)(t % T.tiles_x), ty = (int)(t / T.tiles_x), r = (int)params->dilate;
+            for (int y = std::max(0, ty - r); y <= std::min((int)tiles_y - 1, ty + r); ++y)
+                for (int x = std::max(0, tx - r); x <= std::min((int)T.tiles_x - 1, tx + r); ++x) on[(uint32_t)y * T.tiles_x + (uint32_t)x] = 1;
+        }
+        active.clear();
+        for (uint32_t t = 0; t < n_tiles; ++t)
+            if (on[t]) active.push_back(t);
+    };
+    if (film->passes && film->samples >= 2u && film->samples >= params->uniform_samples) measure(0);   // (a film that has passes: its own active set)
+    for (;;) {
+        if (measured && st.converged) break;
+        const uint64_t next = film->passes ? 2u * (uint64_t)film->last_pass_samples : (uint64_t)params->first_pass_samples;
+        if (film->samples + next > cap) break;
+        const bool all = !measured || !film->passes || film->samples < params->uniform_samples || active.size() == n_tiles;
+        if (all) film_add_whole_pass(*film, scene, (uint32_t)next);
+        else film_add_tile_pass(*film, scene, (uint32_t)next, active.data(), (uint32_t)active.size());
+        measure(all ? n_tiles : (uint32_t)active.size());
+        if (on_pass) {
+            pt_film_info info;
+            film_fill_info(*film, info);
+            pt_film_noise_stats ns{};
+            ns.mean_error = st.mean_error;
+            ns.max_block_error = st.max_tile_error;
+            ns.fraction_over = (double)st.over_tiles / (double)n_tiles;
+            ns.samples = st.samples;
+            ns.n_blocks = n_tiles;
+            ns.converged = st.converged;
+            on_pass(&info, &ns, user);
+        }
+    }
+    if (!measured) noise(st, nullptr);   // (no pass fits: what the film holds)
+    *out = st;
+}
+
+// ---- the film filter (pt_film_denoise.h)
+struct FdnScratch {   // pt_film_denoise_scratch_bytes: the filter's planes, the ferr plane, the two tile arrays
+    DnScratch dn;
+    uint64_t ferr, tile_sum, tile_max, total;
+};
+FdnScratch fdn_scratch_layout(uint64_t n, uint32_t n_tiles) {
+    auto up = [](uint64_t v) { return (v + 255u) & ~(uint64_t)255u; };
+    FdnScratch L;
+    L.dn = dn_scratch_layout(n);
+    L.ferr = L.dn.total;
+    L.tile_sum = L.ferr + up(4u * n);
+    L.tile_max = L.tile_sum + up(4u * (uint64_t)n_tiles);
+    L.total = L.tile_max + up(4u * (uint64_t)n_tiles);
+    return L;
+}
+FdnScratch fdn_scratch_layout(const pt_film& film) { return fdn_scratch_layout(film.n_local, film_n_tiles(film)); }
+
+// What the pt_film_denoise family refuses before any device work (null pointers other than the film are the callers').
+void fdn_check(const char* who, const pt_film* film, int variance, const pt_denoise_params* p, float lum_floor, bool want_ferr) {
+    film_check_tiled(who, film);
+    if (variance != 0 && variance != 1) fail(PT_ERR_INVALID, "%s: variance must be 0 (plain) or 1 (variance-guided)", who);
+    if (!variance && want_ferr) fail(PT_ERR_INVALID, "%s: the plain filter carries no variance, so it has no ferr", who);
+    if (variance) dnv_check(who, p, film->profile.width, film->profile.height, 2u);
+    else {
+        dn_check_params(who, p);
+        dn_check_size(who, film->profile.width, film->profile.height);
+    }
+    film_check_noise_args(who, lum_floor, 0.0);
+    const uint64_t least = film->uniform() ? film->samples : *std::min_element(film->tile_count.begin(), film->tile_count.end());
+    if (least == 0) fail(PT_ERR_INVALID, "%s: some pixels of the film hold no samples", who);
+    if (variance && least < 2u) fail(PT_ERR_INVALID, "%s: a sample variance needs >= 2 samples in every pixel (the fewest: %llu)", who, (unsigned long long)least);
+}
+void fdn_check_scene(const char* who, const pt_film* film, const pt_scene* scene) {
+    if (scene->device != film->device)
+        fail(PT_ERR_INVALID, "%s: the scene is on device %d, the film on device %d", who, scene->device, film->device);
+}
+
+// prep, the passes and the finish on the film's planes; d_color, d_rgb8 and d_ferr (variance only) may be null.
+// ev (measurement only): 4 events - before prep, after prep, after the passes, after the finish.
+void fdn_launch(const pt_film& film, int variance, const pt_denoise_params& p, float lum_floor, const float4* d_guides,
+                float* d_color, uint8_t* d_rgb8, float* d_ferr, uint8_t* d_scratch, hipStream_t stream, hipEvent_t* ev = nullptr) {
+    const uint32_t width = film.profile.width, height = film.profile.height, n = width * height, blocks = (n + 255u) / 256u;
+    const uint32_t no_demod = p.flags & PT_DENOISE_NO_DEMODULATE;
+    const float2* mom = (const float2*)film.moments;
+    size_t e = 0;
+    if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
+    if (p.iterations == 0) {   // nothing is filtered: the film's resolve, and the raw error
+        if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
+        if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
+        if (d_color || d_rgb8) film_resolve_launch(film, p.tonemap, d_rgb8, d_color, stream);
+        if (d_ferr)
+            hipLaunchKernelGGL(k_fdn_finish, dim3(blocks), dim3(256), 0, stream, (const float4*)nullptr, (const float*)nullptr,
+                               (const float*)film.accum, mom, (const uint32_t*)film.count, (uint32_t)film.samples, n, no_demod,
+                               p.tonemap, lum_floor, (float*)nullptr, (uint8_t*)nullptr, d_ferr);
+        HIP_CHECK(hipGetLastError());
+        if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
+        return;
+    }
+    const DnScratch L = dn_scratch_layout(n);
+    float4* X = (float4*)(d_scratch + L.xa);
+    float4* Y = (float4*)(d_scratch + L.xb);
+    float4* U = (float4*)(d_scratch + L.u);
+    float2* G = (float2*)(d_scratch + L.g);
+    float* D = (float*)(d_scratch + L.d);
+    if (variance)
+        hipLaunchKernelGGL(k_fdn_prep<1>, dim3(blocks), dim3(256), 0, stream, (const float*)film.accum, mom, (const uint32_t*)film.count,
+                           (uint32_t)film.samples, d_guides, width, height, no_demod, X, U, G, D);
+    else
+        hipLaunchKernelGGL(k_fdn_prep<0>, dim3(blocks), dim3(256), 0, stream, (const float*)film.accum, mom, (const uint32_t*)film.count,
+                           (uint32_t)film.samples, d_guides, width, height, no_demod, X, U, G, D);
+    HIP_CHECK(hipGetLastError());
+    if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
+    size_t unused = 0;
+    if (variance) dnv_passes(width, height, p, X, Y, U, G, stream, nullptr, unused);
+    else dn_passes(width, height, p, X, Y, U, G, stream, nullptr, unused);
+    if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
+    if (variance)
+        hipLaunchKernelGGL(k_fdn_finish, dim3(blocks), dim3(256), 0, stream, (const float4*)X, (const float*)D, (const float*)film.accum,
+                           mom, (const uint32_t*)film.count, (uint32_t)film.samples, n, no_demod, p.tonemap, lum_floor, d_color,
+                           d_rgb8, d_ferr);
+    else   // (past the passes k_dn_finish reads neither accum nor samples)
+        hipLaunchKernelGGL(k_dn_finish, dim3(blocks), dim3(256), 0, stream, (const float4*)X, (const float*)D, (const float*)film.accum,
+                           (uint32_t)film.samples, n, no_demod, p.tonemap, d_color, d_rgb8);
+    HIP_CHECK(hipGetLastError());
+    if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
+}
+
+void fdn_tile_reduce_launch(const pt_film& film, const float* d_err, float* d_tile_sum, float* d_tile_max, hipStream_t stream) {
+    hipLaunchKernelGGL(k_film_tile_reduce, dim3(film_n_tiles(film)), dim3(256), 0, stream, d_err, film_tiling(film), d_tile_sum, d_tile_max);
+    HIP_CHECK(hipGetLastError());
+}
+
+// The host forms' scratch, made on first use: pt_film_denoise_scratch_bytes and a plane of guides behind it.
+uint8_t* film_filter_scratch(const pt_film& film_c) {
+    pt_film& film = const_cast<pt_film&>(film_c);   // (scratch, not the film's contents)
+    if (!film.filter) {
+        const uint64_t bytes = fdn_scratch_layout(film).total + 32u * film.n_local;
+        HIP_CHECK(hipMalloc((void**)&film.filter, bytes));
+        film.bytes_filter = bytes;
+    }
+    return film.filter;
+}
+float4* film_filter_guides(const pt_film& film) { return (float4*)(film_filter_scratch(film) + fdn_scratch_layout(film).total); }
+
+// Steps 2 - 5 of pt_film_filtered_noise over guides that are on the device already.
+void film_filtered_noise(const pt_film& film, const float4* d_guides, const pt_denoise_params& p, float lum_floor, double target,
+                         pt_film_tile_stats& out, float* ferr_host, float* tile_sum_host, float* tile_max_host) {
+    uint8_t* scratch = film_filter_scratch(film);
+    const FdnScratch L = fdn_scratch_layout(film);
+    const uint32_t n_tiles = film_n_tiles(film);
+    float *ferr = (float*)(scratch + L.ferr), *tile_sum = (float*)(scratch + L.tile_sum), *tile_max = (float*)(scratch + L.tile_max);
+    fdn_launch(film, 1, p, lum_floor, d_guides, nullptr, nullptr, ferr, scratch, nullptr);
+    fdn_tile_reduce_launch(film, ferr, tile_sum, tile_max, nullptr);
+    std::vector<float> sums(n_tiles);
+    HIP_CHECK(hipMemcpy(sums.data(), tile_sum, n_tiles * sizeof(float), hipMemcpyDeviceToHost));   // (waits for the kernels)
+    if (tile_sum_host) memcpy(tile_sum_host, sums.data(), n_tiles * sizeof(float));
+    if (tile_max_host) HIP_CHECK(hipMemcpy(tile_max_host, tile_max, n_tiles * sizeof(float), hipMemcpyDeviceToHost));
+    if (ferr_host) HIP_CHECK(hipMemcpy(ferr_host, ferr, film.n_local * sizeof(float), hipMemcpyDeviceToHost));
+    film_tile_stats(film, sums, target, out);
 }
 
 }  // namespace
@@ -4985,7 +5197,7 @@ int pt_film_get_adaptive_info(const pt_film* film, pt_film_adaptive_info* out) {
         out->min_samples = film->uniform() ? film->samples : *std::min_element(film->tile_count.begin(), film->tile_count.end());
         for (uint32_t t = 0; t < out->n_tiles; ++t)
             out->pixel_samples += film_tile_pixels(T, t) * (film->uniform() ? film->samples : film->tile_count[t]);
-        out->device_bytes = film->bytes + film->bytes_adaptive;
+        out->device_bytes = film->bytes + film->bytes_adaptive + film->bytes_filter;
     });
 }
 
@@ -5005,61 +5217,11 @@ int pt_film_render_until_adaptive(pt_film* film, const pt_scene* scene, const pt
     return guarded([&] {
         const char* who = "pt_film_render_until_adaptive";
         if (!film || !scene || !params || !out) fail(PT_ERR_INVALID, "%s: null argument", who);
-        film_check_tiled(who, film);
-        film_check_noise_args(who, params->lum_floor, params->target);
-        if (params->first_pass_samples < 2u) fail(PT_ERR_INVALID, "%s: first_pass_samples must be >= 2 (a sample variance needs two)", who);
-        if (params->dilate > 1u) fail(PT_ERR_INVALID, "%s: dilate must be 0 or 1", who);
-        if (!film->passes && (uint64_t)params->first_pass_samples > params->max_samples)
-            fail(PT_ERR_INVALID, "%s: first_pass_samples %u exceeds max_samples %llu", who, params->first_pass_samples, (unsigned long long)params->max_samples);
-        if (scene->device != film->device)
-            fail(PT_ERR_INVALID, "%s: the scene is on device %d, the film on device %d", who, scene->device, film->device);
-        const uint64_t cap = std::min<uint64_t>(params->max_samples, (uint64_t)PT_FILM_MAX_SAMPLES);
-        const FilmTiling T = film_tiling(*film);
-        const uint32_t n_tiles = film_n_tiles(*film), tiles_y = n_tiles / T.tiles_x;
-        std::vector<float> sums(n_tiles);
-        std::vector<uint32_t> active;   // the tiles of the next pass; empty: every tile
-        pt_film_tile_stats st{};
-        bool measured = false;
-        auto measure = [&](uint32_t rendered) {
-            film_tile_noise(*film, params->lum_floor, params->target, st, nullptr, sums.data(), nullptr);
-            st.active_tiles = rendered;
-            measured = true;
-            // the candidates - the tiles above the target - and, dilate: their 8 neighbours
-            std::vector<uint8_t> on(n_tiles, 0);
-            for (uint32_t t = 0; t < n_tiles; ++t) {
-                if (!((double)sums[t] / (double)film_tile_pixels(T, t) > params->target)) continue;
-                const int tx = (int)(t % T.tiles_x), ty = (int)(t / T.tiles_x), r = (int)params->dilate;
-                for (int y = std::max(0, ty - r); y <= std::min((int)tiles_y - 1, ty + r); ++y)
-                    for (int x = std::max(0, tx - r); x <= std::min((int)T.tiles_x - 1, tx + r); ++x) on[(uint32_t)y * T.tiles_x + (uint32_t)x] = 1;
-            }
-            active.clear();
-            for (uint32_t t = 0; t < n_tiles; ++t)
-                if (on[t]) active.push_back(t);
-        };
-        if (film->passes && film->samples >= 2u && film->samples >= params->uniform_samples) measure(0);   // (a film that has passes: its own active set)
-        for (;;) {
-            if (measured && st.converged) break;
-            const uint64_t next = film->passes ? 2u * (uint64_t)film->last_pass_samples : (uint64_t)params->first_pass_samples;
-            if (film->samples + next > cap) break;
-            const bool all = !measured || !film->passes || film->samples < params->uniform_samples || active.size() == n_tiles;
-            if (all) film_add_whole_pass(*film, scene, (uint32_t)next);
-            else film_add_tile_pass(*film, scene, (uint32_t)next, active.data(), (uint32_t)active.size());
-            measure(all ? n_tiles : (uint32_t)active.size());
-            if (on_pass) {
-                pt_film_info info;
-                film_fill_info(*film, info);
-                pt_film_noise_stats ns{};
-                ns.mean_error = st.mean_error;
-                ns.max_block_error = st.max_tile_error;
-                ns.fraction_over = (double)st.over_tiles / (double)n_tiles;
-                ns.samples = st.samples;
-                ns.n_blocks = n_tiles;
-                ns.converged = st.converged;
-                on_pass(&info, &ns, user);
-            }
-        }
-        if (!measured) film_tile_noise(*film, params->lum_floor, params->target, st, nullptr, nullptr, nullptr);   // (no pass fits: what the film holds)
-        *out = st;
+        film_check_adaptive(who, film, scene, params);
+        film_adaptive_loop(film, scene, params, on_pass, user, out,
+                           [&](pt_film_tile_stats& st, float* sums) {
+                               film_tile_noise(*film, params->lum_floor, params->target, st, nullptr, sums, nullptr);
+                           });
     });
 }
 
@@ -5120,6 +5282,143 @@ int pt_film_adaptive_kernel_times(pt_film* film, float lum_floor, int tonemap, u
             HIP_CHECK(hipEventElapsedTime(which == 0 ? &ms_merge[r] : which == 1 ? &ms_noise[r - reps] : &ms_resolve[r - 2u * reps], e0, e1));
         }
         HIP_CHECK(hipGetLastError());
+    });
+}
+
+// ---- the film filter
+uint64_t pt_film_denoise_scratch_bytes(const pt_film* film) {
+    if (!film || !film->has_profile || film->opts.shard_count > 1) return 0;
+    return fdn_scratch_layout(*film).total;
+}
+
+int pt_film_denoise_device(const pt_film* film, int variance, const pt_denoise_params* params, float lum_floor, const void* d_guides,
+                           void* d_out_color, void* d_out_rgb8, void* d_out_ferr, void* d_scratch, void* hip_stream) {
+    return guarded([&] {
+        const char* who = "pt_film_denoise_device";
+        if (!film || !params || !d_guides || (!d_out_color && !d_out_rgb8 && !d_out_ferr)) fail(PT_ERR_INVALID, "%s: null argument", who);
+        fdn_check(who, film, variance, params, lum_floor, d_out_ferr != nullptr);
+        if (!d_scratch && params->iterations) fail(PT_ERR_INVALID, "%s: null argument", who);
+        HIP_CHECK(hipSetDevice(film->device));
+        fdn_launch(*film, variance, *params, lum_floor, (const float4*)d_guides, (float*)d_out_color, (uint8_t*)d_out_rgb8,
+                   (float*)d_out_ferr, (uint8_t*)d_scratch, (hipStream_t)hip_stream);
+    });
+}
+
+int pt_film_denoise(const pt_film* film, const pt_scene* scene, int variance, const pt_denoise_params* params, float lum_floor,
+                    uint8_t* rgb8, float* color, float* ferr) {
+    return guarded([&] {
+        const char* who = "pt_film_denoise";
+        if (!film || !scene || !params || (!rgb8 && !color && !ferr)) fail(PT_ERR_INVALID, "%s: null argument", who);
+        fdn_check(who, film, variance, params, lum_floor, ferr != nullptr);
+        fdn_check_scene(who, film, scene);
+        HIP_CHECK(hipSetDevice(film->device));
+        const size_t n = (size_t)film->n_local;
+        uint8_t* scratch = film_filter_scratch(*film);
+        float4* d_guides = film_filter_guides(*film);
+        // only the planes that were asked for are staged (ferr: the scratch has a plane for it)
+        std::unique_ptr<Staged<uint8_t>> d_rgb;
+        std::unique_ptr<Staged<float>> d_color;
+        if (rgb8) d_rgb = std::make_unique<Staged<uint8_t>>(nullptr, n * 3);
+        if (color) d_color = std::make_unique<Staged<float>>(nullptr, n * 3);
+        float* d_ferr = ferr ? (float*)(scratch + fdn_scratch_layout(*film).ferr) : nullptr;
+        guides_launch(*scene, film->profile.width, film->profile.height, d_guides, nullptr);
+        fdn_launch(*film, variance, *params, lum_floor, d_guides, color ? d_color->d : nullptr, rgb8 ? d_rgb->d : nullptr, d_ferr,
+                   scratch, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        if (rgb8) d_rgb->fetch(rgb8, n * 3);
+        if (color) d_color->fetch(color, n * 3);
+        if (ferr) HIP_CHECK(hipMemcpy(ferr, d_ferr, n * sizeof(float), hipMemcpyDeviceToHost));
+    });
+}
+
+int pt_film_tile_reduce_device(const pt_film* film, const void* d_err, void* d_tile_sum, void* d_tile_max, void* hip_stream) {
+    return guarded([&] {
+        const char* who = "pt_film_tile_reduce_device";
+        if (!film || !d_err || !d_tile_sum || !d_tile_max) fail(PT_ERR_INVALID, "%s: null argument", who);
+        film_check_tiled(who, film);
+        HIP_CHECK(hipSetDevice(film->device));
+        fdn_tile_reduce_launch(*film, (const float*)d_err, (float*)d_tile_sum, (float*)d_tile_max, (hipStream_t)hip_stream);
+    });
+}
+
+int pt_film_filtered_noise(const pt_film* film, const pt_scene* scene, const pt_denoise_params* params, float lum_floor, double target,
+                           pt_film_tile_stats* out, float* ferr_host, float* tile_sum_host, float* tile_max_host) {
+    return guarded([&] {
+        const char* who = "pt_film_filtered_noise";
+        if (!film || !scene || !params || !out) fail(PT_ERR_INVALID, "%s: null argument", who);
+        fdn_check(who, film, 1, params, lum_floor, true);
+        film_check_noise_args(who, lum_floor, target);
+        fdn_check_scene(who, film, scene);
+        HIP_CHECK(hipSetDevice(film->device));
+        float4* d_guides = film_filter_guides(*film);
+        guides_launch(*scene, film->profile.width, film->profile.height, d_guides, nullptr);
+        pt_film_tile_stats st{};
+        film_filtered_noise(*film, d_guides, *params, lum_floor, target, st, ferr_host, tile_sum_host, tile_max_host);
+        *out = st;
+    });
+}
+
+void pt_film_filtered_params_default(pt_film_filtered_params* p) {
+    if (!p) return;
+    pt_film_adaptive_params_default(&p->adaptive);
+    pt_denoise_var_params_default(&p->filter);
+}
+
+int pt_film_render_until_filtered(pt_film* film, const pt_scene* scene, const pt_film_filtered_params* params,
+                                  pt_film_pass_fn on_pass, void* user, pt_film_tile_stats* out) {
+    return guarded([&] {
+        const char* who = "pt_film_render_until_filtered";
+        if (!film || !scene || !params || !out) fail(PT_ERR_INVALID, "%s: null argument", who);
+        const pt_film_adaptive_params& a = params->adaptive;
+        film_check_adaptive(who, film, scene, &a);
+        dnv_check(who, &params->filter, film->profile.width, film->profile.height, 2u);
+        // A film that is measured as it stands - it has its uniform samples, or no pass fits the budget - must pass the filter's
+        // count rule now, before the scratch is made and the guides are rendered; any other film takes a whole pass of >= 2 first.
+        const uint64_t next = film->passes ? 2u * (uint64_t)film->last_pass_samples : (uint64_t)a.first_pass_samples;
+        const bool measure_first = film->passes && film->samples >= 2u && film->samples >= a.uniform_samples;
+        const bool pass_fits = film->samples + next <= std::min<uint64_t>(a.max_samples, (uint64_t)PT_FILM_MAX_SAMPLES);
+        if (measure_first || !pass_fits) fdn_check(who, film, 1, &params->filter, a.lum_floor, true);
+        HIP_CHECK(hipSetDevice(film->device));
+        float4* d_guides = film_filter_guides(*film);   // rendered once: the film does not watch the scene
+        guides_launch(*scene, film->profile.width, film->profile.height, d_guides, nullptr);
+        film_adaptive_loop(film, scene, &a, on_pass, user, out, [&](pt_film_tile_stats& st, float* sums) {
+            fdn_check(who, film, 1, &params->filter, a.lum_floor, true);
+            film_filtered_noise(*film, d_guides, params->filter, a.lum_floor, a.target, st, nullptr, sums, nullptr);
+        });
+    });
+}
+
+int pt_film_denoise_kernel_times(const pt_film* film, const pt_scene* scene, const pt_denoise_params* params, float lum_floor,
+                                 uint32_t reps, float* ms_prep, float* ms_passes, float* ms_finish, float* ms_reduce) {
+    return guarded([&] {
+        const char* who = "pt_film_denoise_kernel_times";
+        if (!film || !scene || !params || !reps || !ms_prep || !ms_passes || !ms_finish || !ms_reduce) fail(PT_ERR_INVALID, "%s: null argument", who);
+        fdn_check(who, film, 1, params, lum_floor, true);
+        fdn_check_scene(who, film, scene);
+        HIP_CHECK(hipSetDevice(film->device));
+        uint8_t* scratch = film_filter_scratch(*film);
+        float4* d_guides = film_filter_guides(*film);
+        const FdnScratch L = fdn_scratch_layout(*film);
+        guides_launch(*scene, film->profile.width, film->profile.height, d_guides, nullptr);
+        std::vector<hipEvent_t> ev(5, nullptr);
+        struct Free {
+            std::vector<hipEvent_t>& e;
+            ~Free() {
+                for (hipEvent_t x : e)
+                    if (x) (void)hipEventDestroy(x);
+            }
+        } guard{ev};
+        for (hipEvent_t& x : ev) HIP_CHECK(hipEventCreate(&x));
+        for (uint32_t r = 0; r < reps; ++r) {
+            fdn_launch(*film, 1, *params, lum_floor, d_guides, nullptr, nullptr, (float*)(scratch + L.ferr), scratch, nullptr, ev.data());
+            fdn_tile_reduce_launch(*film, (const float*)(scratch + L.ferr), (float*)(scratch + L.tile_sum), (float*)(scratch + L.tile_max), nullptr);
+            HIP_CHECK(hipEventRecord(ev[4], nullptr));
+            HIP_CHECK(hipEventSynchronize(ev[4]));
+            HIP_CHECK(hipEventElapsedTime(&ms_prep[r], ev[0], ev[1]));
+            HIP_CHECK(hipEventElapsedTime(&ms_passes[r], ev[1], ev[2]));
+            HIP_CHECK(hipEventElapsedTime(&ms_finish[r], ev[2], ev[3]));
+            HIP_CHECK(hipEventElapsedTime(&ms_reduce[r], ev[3], ev[4]));
+        }
     });
 }
 

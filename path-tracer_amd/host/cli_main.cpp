@@ -6,7 +6,8 @@
 //                              [--keyframes <FRAMES> [--light-mixer]]
 //                              [--noise-target <T> [--min-samples <N0>] [--max-samples <N>] [--noise-map <FILE.png>]
 //                               [--adaptive [--adaptive-tile <N>] [--uniform-samples <U>] [--adaptive-dilate <0|1>]
-//                                [--sample-map <FILE.png>]]]
+//                                [--sample-map <FILE.png>]]
+//                               [--film-denoise <plain|variance> [--filtered-target]]]
 //       env OUTPUT (default render.png), env PROFILE
 //   path-tracer convert <INPUT> <OUTPUT>      (glTF 2.0 -> ISF, host/gltf_convert.cpp)
 //
@@ -25,7 +26,9 @@
 // --noise-target T (every frame is a progressive film, pt_film_render_until: passes of N0, 2 N0, 4 N0, ... samples until the
 // mean relative error of the pixels' mean luminance is <= T or the next pass would take the total above N),
 // --adaptive (with --noise-target: an adaptive film, pt_film_render_until_adaptive - once every pixel has U samples the
-// passes render only the N x N tiles whose mean error is still above T, and their neighbours; N bounds the largest count).
+// passes render only the N x N tiles whose mean error is still above T, and their neighbours; N bounds the largest count),
+// --film-denoise (with --noise-target: the finished film goes through pt_film_denoise in place of pt_film_resolve) and
+// --filtered-target (with --adaptive --film-denoise variance: pt_film_render_until_filtered - T is met by the filtered error).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -85,6 +88,11 @@ void usage_render(FILE* f) {
           "      --uniform-samples <U>  Every pass of --adaptive is a whole frame until every pixel has U samples [default: 24]\n"
           "      --adaptive-dilate <0|1>  --adaptive also renders the 8 neighbours of a tile above T [default: 1]\n"
           "      --sample-map <FILE.png>  With --adaptive: write the per-pixel sample count as grey, white = the largest\n"
+          "      --film-denoise <plain|variance>  With --noise-target: write the finished film, uniform or adaptive, filtered on the\n"
+          "                           device by the a-trous denoiser with every pixel's own sample count (--denoise-iterations\n"
+          "                           applies; one device, not with --denoise)\n"
+          "      --filtered-target    With --adaptive --film-denoise variance: T is met by the error of the FILTERED image - tiles\n"
+          "                           are selected by the variance the filter leaves; --noise-map then shows that error\n"
           "  -h, --help               Print help\n",
           f);
 }
@@ -194,6 +202,8 @@ int run_render(int argc, char** argv) {
     std::string noise_map, sample_map;
     bool adaptive = false, have_adaptive_tile = false, have_uniform_samples = false, have_adaptive_dilate = false;
     uint32_t adaptive_tile = 32, uniform_samples = 0, adaptive_dilate = 1;
+    std::string film_denoise;   // "", "plain" or "variance"
+    bool filtered_target = false;
     int device = 0;
     std::vector<int> devices;
     for (int i = 0; i < argc; ++i) {
@@ -248,6 +258,11 @@ int run_render(int argc, char** argv) {
             have_max_samples = true;
         } else if (a == "--noise-map" || a.rfind("--noise-map=", 0) == 0) noise_map = value("--noise-map <FILE.png>");
         else if (a == "--adaptive") adaptive = true;
+        else if (a == "--film-denoise" || a.rfind("--film-denoise=", 0) == 0) {
+            film_denoise = value("--film-denoise <plain|variance>");
+            if (film_denoise != "plain" && film_denoise != "variance")
+                die("error: invalid value '" + film_denoise + "' for '--film-denoise <plain|variance>': plain or variance expected");
+        } else if (a == "--filtered-target") filtered_target = true;
         else if (a == "--adaptive-tile" || a.rfind("--adaptive-tile=", 0) == 0) {
             adaptive_tile = parse_u32(value("--adaptive-tile <N>"), "--adaptive-tile <N>");
             have_adaptive_tile = true;
@@ -296,7 +311,7 @@ int run_render(int argc, char** argv) {
         }
     }
 
-    if (denoise_iterations >= 0 && !denoise) die("error: '--denoise-iterations <N>' needs '--denoise'");
+    if (denoise_iterations >= 0 && !denoise && film_denoise.empty()) die("error: '--denoise-iterations <N>' needs '--denoise'");
     if (denoise_variance && !denoise) die("error: '--denoise-variance' needs '--denoise'");
     if (denoise && devices.size() > 1)
         die("error: the argument '--denoise' cannot be used with more than one device in '--devices <A,B,..>' (the gathered "
@@ -315,6 +330,15 @@ int run_render(int argc, char** argv) {
     if (adaptive && denoise)
         die("error: the argument '--adaptive' cannot be used with '--denoise' or '--denoise-variance' (the filters take one sample "
             "count for the whole frame)");
+    if (!film_denoise.empty() && !have_noise_target) die("error: '--film-denoise <plain|variance>' needs '--noise-target <T>'");
+    if (!film_denoise.empty() && denoise)
+        die("error: the argument '--film-denoise <plain|variance>' cannot be used with '--denoise' (one filter per frame)");
+    if (!film_denoise.empty() && devices.size() > 1)
+        die("error: the argument '--film-denoise <plain|variance>' cannot be used with more than one device in '--devices <A,B,..>' "
+            "(the filter needs the whole film on one device)");
+    if (filtered_target && film_denoise == "plain")
+        die("error: the argument '--filtered-target' cannot be used with '--film-denoise plain' (the plain filter carries no variance)");
+    if (filtered_target && (!adaptive || film_denoise.empty())) die("error: '--filtered-target' needs '--adaptive --film-denoise variance'");
     if (adaptive && devices.size() > 1)
         die("error: the argument '--adaptive' cannot be used with more than one device in '--devices <A,B,..>' (an adaptive film "
             "lives on one device)");
@@ -592,7 +616,7 @@ int run_render(int argc, char** argv) {
     }
     std::vector<uint8_t> rgb((size_t)profile.width * profile.height * 3);
     pt_denoise_params dn;
-    if (denoise_variance) pt_denoise_var_params_default(&dn);
+    if (denoise_variance || film_denoise == "variance") pt_denoise_var_params_default(&dn);
     else pt_denoise_params_default(&dn);
     dn.tonemap = profile.tonemap;
     if (denoise_iterations >= 0) dn.iterations = (uint32_t)denoise_iterations;
@@ -636,7 +660,14 @@ int run_render(int argc, char** argv) {
             if (have_uniform_samples) ap.uniform_samples = uniform_samples;
             if (have_adaptive_dilate) ap.dilate = adaptive_dilate;
             AdaptivePassCtx ctx{viewer, film};
-            if (pt_film_render_until_adaptive(film, scene, &ap, on_adaptive_pass, &ctx, &tiles) != PT_OK) die(pt_last_error());
+            if (filtered_target) {   // tiles are selected by the error of the filtered image
+                pt_film_filtered_params fp;
+                fp.adaptive = ap;
+                fp.filter = dn;
+                if (pt_film_render_until_filtered(film, scene, &fp, on_adaptive_pass, &ctx, &tiles) != PT_OK) die(pt_last_error());
+            } else if (pt_film_render_until_adaptive(film, scene, &ap, on_adaptive_pass, &ctx, &tiles) != PT_OK) {
+                die(pt_last_error());
+            }
             noise.mean_error = tiles.mean_error;
             noise.converged = tiles.converged;
         } else if (pt_film_render_until(film, scene, min_samples, max_samples, PT_FILM_DEFAULT_LUM_FLOOR, noise_target, on_film_pass,
@@ -654,13 +685,17 @@ int run_render(int argc, char** argv) {
                                   : pt_denoise(device, profile.width, profile.height, (uint32_t)info.samples, &dn, acc.data(), guides.data(),
                                                nullptr, rgb.data())) != PT_OK)
                 die(pt_last_error());
+        } else if (!film_denoise.empty()) {   // the film's own planes through the filter on the device, every pixel by its count
+            if (pt_film_denoise(film, scene, film_denoise == "variance", &dn, PT_FILM_DEFAULT_LUM_FLOOR, rgb.data(), nullptr, nullptr) != PT_OK)
+                die(pt_last_error());
         } else if (pt_film_resolve(film, profile.tonemap, rgb.data(), nullptr) != PT_OK) {
             die(pt_last_error());
         }
         if (!noise_map.empty()) {   // grey = as_u8(min(1, err / (2 T)) * 255)
             std::vector<float> err(n_pixels);
-            if ((adaptive ? pt_film_tile_noise(film, PT_FILM_DEFAULT_LUM_FLOOR, noise_target, &tiles, err.data(), nullptr, nullptr)
-                          : pt_film_noise(film, PT_FILM_DEFAULT_LUM_FLOOR, noise_target, &noise, err.data(), nullptr, nullptr)) != PT_OK)
+            if ((filtered_target ? pt_film_filtered_noise(film, scene, &dn, PT_FILM_DEFAULT_LUM_FLOOR, noise_target, &tiles, err.data(), nullptr, nullptr)
+                 : adaptive      ? pt_film_tile_noise(film, PT_FILM_DEFAULT_LUM_FLOOR, noise_target, &tiles, err.data(), nullptr, nullptr)
+                                 : pt_film_noise(film, PT_FILM_DEFAULT_LUM_FLOOR, noise_target, &noise, err.data(), nullptr, nullptr)) != PT_OK)
                 die(pt_last_error());
             std::vector<uint8_t> grey(n_pixels * 3);
             const float full = 2.0f * (float)noise_target;
@@ -676,8 +711,9 @@ int run_render(int argc, char** argv) {
             write_map(sample_map, f, grey);
         }
         if (adaptive)
-            fprintf(stderr, "film: %u passes, %llu samples, noise %.6g, %s, pixel-samples %llu of %llu\n", info.passes,
-                    (unsigned long long)info.samples, noise.mean_error, noise.converged ? "converged" : "max samples",
+            fprintf(stderr, "film: %u passes, %llu samples, %s %.6g, %s, pixel-samples %llu of %llu\n", info.passes,
+                    (unsigned long long)info.samples, filtered_target ? "filtered noise" : "noise", noise.mean_error,
+                    noise.converged ? "converged" : "max samples",
                     (unsigned long long)tiles.pixel_samples, (unsigned long long)(info.n_local * info.samples));
         else
             fprintf(stderr, "film: %u passes, %llu samples, noise %.6g, %s\n", info.passes, (unsigned long long)info.samples, noise.mean_error,

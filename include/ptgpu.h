@@ -507,7 +507,8 @@ int  pt_lightmix_apply_device(const pt_lightmix* mix, const float* colors /* hos
  *   - seeds ARE shared between different pixels of different passes (pixel j of pass b and pixel ~ j*b/a of pass a).  That
  *     correlates the noise of two distant pixels and biases nothing.
  * No sample is rendered twice, so the doubling costs nothing.  Every pass is the first frame of its configuration (a new
- * `samples`): unplanned, no frame cache is keyed - the situation of a camera path.
+ * `samples`): unplanned, no frame cache is keyed - the situation of a camera path.  (A WINDOWED film - pt_film_create_windowed,
+ * further down - has neither caveat and no doubling rule: its passes are windows of one enumeration.)
  *
  * pt_film_create copies profile (its samples is ignored) and opts (the progress and preview callbacks are dropped) and allocates
  * on `device` (HIP ordinal, -1 = current): the film's accum and moments, pass buffers of the same size, one err plane (n_local
@@ -782,6 +783,94 @@ int  pt_film_render_until_filtered(pt_film* film, const pt_scene* scene, const p
  * between the stages; blocks.  ms_prep[r], ms_passes[r] (all passes), ms_finish[r] (finish + ferr), ms_reduce[r], reps each. */
 int  pt_film_denoise_kernel_times(const pt_film* film, const pt_scene* scene, const pt_denoise_params* params, float lum_floor,
                                   uint32_t reps, float* ms_prep, float* ms_passes, float* ms_finish, float* ms_reduce);
+
+/* ------------------------------------------------------------------ */
+/* window frames and windowed films                        */
+/* ------------------------------------------------------------------ */
+
+/* A window frame renders the samples [s0, s1) of the frame (profile, opts), 0 <= s0 < s1 <= N = profile.samples: sample s of
+ * pixel i uses the seed of pt_render(samples = N), whatever the windows are.  accum (and moments, where given) are IN-OUT: with
+ * s0 == 0 the sums start from zero and the buffers' contents are ignored; with s0 > 0 they hold the sums of [0, s0) and the call
+ * continues them sample by sample with the additions pt_render / pt_render_moments perform.
+ *   chaining   after any chain [0,a), [a,b), .., [y,N) on the same buffers accum, moments and rgb8 equal pt_render_moments(scene,
+ *              profile, opts) bit for bit.
+ *   prefixes   after a chain ending at k < N: accum is the in-order f32 running sum of the first k planes of pt_render_samples
+ *              for the N-sample profile, moments their luminance moments, rgb8 pt_render's post-processing of accum with
+ *              samples = k.
+ *   layout     tiles == NULL: the whole frame (n_tiles is ignored) - pt_render's buffers, shards in packed local order.
+ *              tiles != NULL: the rules, layout and refusals of pt_render_tiles; each packed pixel equals the same global pixel
+ *              of the whole-frame window.
+ *   pipelines  the default pipeline and PT_FLAG_NO_GRIDS: everything.  PT_FLAG_MEGAKERNEL: accum and rgb8 (its kernel carries
+ *              its sums the same way); moments != NULL there is PT_ERR_UNSUPPORTED, as in pt_render_moments.
+ *   refusals   PT_ERR_INVALID before any device work, the outputs untouched: s0 >= s1, s1 > N, a null accum, anything
+ *              pt_render / pt_render_tiles refuses.
+ * opts.sample_batch (and the staging budget) split a window into batches internally; that changes no bit.  The progress and
+ * preview callbacks of opts see the absolute sample numbers.  The host form blocks.  The device form is asynchronous on
+ * hip_stream but, like pt_render_tiles_device, may wait for the whole device and allocate when it is entered.
+ * A window frame leaves the scene's steady state alone, exactly as a tile-list frame does: it is a first frame every time
+ * (unplanned, no frame cache read, written, keyed or counted, the statistics slot of the tile-list frames), and the whole frames
+ * before and after it run what they would have run without it.  Planned or cached windows are not built: a film renders every
+ * sample once, and plans and caches pay only on the second rendering of the same items. */
+int  pt_render_window(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, uint32_t s0, uint32_t s1,
+                      const uint32_t* tiles /* NULL: the whole frame */, uint32_t n_tiles, uint8_t* rgb8, float* accum /* in-out */,
+                      float* moments /* in-out, may be NULL */);   /* host */
+int  pt_render_window_device(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, uint32_t s0, uint32_t s1,
+                             const uint32_t* tiles, uint32_t n_tiles, void* d_rgb8, void* d_accum, void* d_moments, void* hip_stream);
+
+/* A windowed film: every pass is a window of ONE enumeration of N = profile.samples samples per pixel (2 .. PT_FILM_MAX_SAMPLES),
+ * so a pixel at count c holds the sums of the samples [0, c) of pt_render(samples = N): pixel i uses only its own seeds
+ * [i*N, i*N + N), a window may have any length, and a film that reaches N everywhere equals pt_render_moments(N) bit for bit.
+ * Its planes mean what a film's planes mean (sums, moments, a count plane once it is non-uniform): pt_film_noise,
+ * pt_film_tile_noise, pt_film_resolve[_device], pt_film_read, pt_film_read_counts, pt_film_planes_device,
+ * pt_film_denoise[_device], pt_film_filtered_noise, pt_film_get_info / _adaptive_info and pt_film_reset work on it unchanged and
+ * follow the same uniform / non-uniform rules.  Mixing is PT_ERR_INVALID and changes nothing: pt_film_add_pass,
+ * pt_film_add_tile_pass, pt_film_add_planes, pt_film_add_tile_planes, pt_film_render_until, _adaptive and _filtered on a
+ * windowed film; the calls below (but pt_film_get_window_info and pt_film_window_params_default) on a film that is not.
+ *
+ * pt_film_add_window: the window [n, n + samples) of every pixel, n = info.samples; PT_ERR_INVALID when n + samples > N (a film
+ * at n == N is full).  The frame renders into the pass buffers, seeded with a copy of the film, and the film adopts them when
+ * it has completed: a failure leaves the film's planes and counters as they were.  Sharded films work.  On a non-uniform film it
+ * is the tile window that lists every tile.
+ * pt_film_add_tile_window (unsharded films): every listed tile t gets the window [count_t, count_t + samples) - counts are
+ * uniform inside a tile; PT_ERR_INVALID when any listed tile would pass N, and what pt_render_tiles refuses in the list.  The
+ * tiles are grouped by count, counts ascending; every group is gathered into a run of the pass buffers (k_film_gather_tiles),
+ * rendered there as one tile-list window frame, and when EVERY group's frame has completed the runs are written back and
+ * `samples` is added to the counts (k_film_scatter_tiles).  No pixel outside the list is read or written; a failure before the
+ * first write-back leaves the film as it was.  The first tile window makes the film non-uniform, as the first tile pass does.
+ *
+ * pt_film_render_until_windowed (unsharded films).  Loop: (1) the active tiles that are full (count == N) take no more; the
+ * next window has window_samples samples, clipped to N - the largest count among the rest; (2) stop for budget when none is
+ * left; (3) render the window over the active set - EVERY tile while the film is empty, while adaptive == 0 or while
+ * info.samples < uniform_samples; a window over every tile of a uniform film is pt_film_add_window; (4) pt_film_tile_noise;
+ * (5) - (7) the candidates, their dilation and on_pass as in pt_film_render_until_adaptive; (8) stop as converged when there is
+ * no candidate.  A film that has windows (every pixel >= 2 samples; adaptive: info.samples >= uniform_samples) starts with
+ * step 4.  A loop that runs out of budget with every tile active leaves the film equal to pt_render_moments(N), bit for bit.
+ * PT_ERR_INVALID before any device work: what pt_film_tile_noise refuses in lum_floor and target, window_samples < 1 (< 2 on an
+ * empty film: a sample variance needs two), dilate or adaptive above 1, a film that is not windowed, a sharded film, a scene on
+ * another device.  window_samples (default PT_FILM_DEFAULT_WINDOW_SAMPLES) is a design choice, not a measured optimum
+ * (DESIGN 4k): a short window stops closer to the target and pays a frame's fixed cost more often. */
+#define PT_FILM_DEFAULT_WINDOW_SAMPLES 32u
+typedef struct pt_film_window_info {
+    uint32_t windowed /* 0 / 1 */, enumeration /* N; 0: not windowed */, windows /* whole-frame windows since the film was made
+             or reset */, tile_windows;
+} pt_film_window_info;
+typedef struct pt_film_window_params {
+    double target;
+    float lum_floor;
+    uint32_t window_samples, adaptive /* 0: every window covers every tile; 1: the tiles above the target */, uniform_samples,
+             dilate /* 0 or 1 */;
+} pt_film_window_params;
+int  pt_film_create_windowed(int device, const pt_profile* profile /* samples = N */, const pt_opts* opts, pt_film** out);
+int  pt_film_add_window(pt_film* film, const pt_scene* scene, uint32_t samples);
+int  pt_film_add_tile_window(pt_film* film, const pt_scene* scene, uint32_t samples, const uint32_t* tiles, uint32_t n_tiles);
+int  pt_film_get_window_info(const pt_film* film, pt_film_window_info* out);
+void pt_film_window_params_default(pt_film_window_params* params);   /* floor 0.01, target 0.02, window 32, adaptive 1, uniform 24, dilate 1 */
+int  pt_film_render_until_windowed(pt_film* film, const pt_scene* scene, const pt_film_window_params* params,
+                                   pt_film_pass_fn on_pass, void* user, pt_film_tile_stats* out);
+/* Measurement, like the other *_times, on a non-uniform film: ms_gather[r] = k_film_gather_tiles over every tile into the pass
+ * buffers (scratch between passes), ms_scatter[r] = k_film_scatter_tiles writing the same values back with zero samples (the
+ * film's planes and counts keep their values). */
+int  pt_film_window_kernel_times(pt_film* film, uint32_t reps, float* ms_gather, float* ms_scatter);
 
 /* ------------------------------------------------------------------ */
 /* measurement                                                         */

@@ -218,6 +218,28 @@ class FilmFilteredParams(C.Structure):
         return p
 
 
+class FilmWindowInfo(C.Structure):
+    """pt_film_window_info."""
+    _fields_ = [("windowed", C.c_uint32), ("enumeration", C.c_uint32), ("windows", C.c_uint32), ("tile_windows", C.c_uint32)]
+
+
+class FilmWindowParams(C.Structure):
+    """pt_film_window_params."""
+    _fields_ = [("target", C.c_double), ("lum_floor", C.c_float), ("window_samples", C.c_uint32), ("adaptive", C.c_uint32),
+                ("uniform_samples", C.c_uint32), ("dilate", C.c_uint32)]
+
+    @classmethod
+    def default(cls, **changes):
+        """pt_film_window_params_default, with fields replaced by keyword."""
+        p = cls()
+        gpu_lib().pt_film_window_params_default(C.byref(p))
+        for k, v in changes.items():
+            if k not in dict(cls._fields_):
+                raise TypeError(f"pt_film_window_params has no field {k!r}")
+            setattr(p, k, v)
+        return p
+
+
 class Hit(C.Structure):
     _fields_ = [("prim", C.c_int32), ("flags", C.c_int32), ("dist", C.c_float), ("u", C.c_float),
                 ("v", C.c_float)]
@@ -329,7 +351,10 @@ GPU_SYMBOLS = ["pt_scene_create", "pt_scene_destroy", "pt_scene_set_camera", "pt
                "pt_film_adaptive_kernel_times",
                "pt_film_filtered_params_default", "pt_film_denoise_scratch_bytes", "pt_film_denoise_device", "pt_film_denoise",
                "pt_film_tile_reduce_device", "pt_film_filtered_noise", "pt_film_render_until_filtered",
-               "pt_film_denoise_kernel_times"]
+               "pt_film_denoise_kernel_times",
+               "pt_render_window", "pt_render_window_device", "pt_film_create_windowed", "pt_film_add_window",
+               "pt_film_add_tile_window", "pt_film_get_window_info", "pt_film_window_params_default",
+               "pt_film_render_until_windowed", "pt_film_window_kernel_times"]
 
 
 def host_lib():
@@ -534,6 +559,19 @@ def gpu_lib():
             L.pt_film_render_until_filtered.argtypes = [vp, vp, C.POINTER(FilmFilteredParams), FILM_PASS_FN, vp,
                                                         C.POINTER(FilmTileStats)]
             L.pt_film_denoise_kernel_times.argtypes = [vp, vp, dp, C.c_float, C.c_uint32, vp, vp, vp, vp]
+        if hasattr(L, "pt_render_window"):   # (an A/B library of an earlier commit has no windows)
+            L.pt_render_window.argtypes = [vp, C.POINTER(Profile), C.POINTER(Opts), C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp]
+            L.pt_render_window_device.argtypes = [vp, C.POINTER(Profile), C.POINTER(Opts), C.c_uint32, C.c_uint32, vp, C.c_uint32,
+                                                  vp, vp, vp, vp]
+            L.pt_film_create_windowed.argtypes = [C.c_int, C.POINTER(Profile), C.POINTER(Opts), C.POINTER(vp)]
+            L.pt_film_add_window.argtypes = [vp, vp, C.c_uint32]
+            L.pt_film_add_tile_window.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32]
+            L.pt_film_get_window_info.argtypes = [vp, C.POINTER(FilmWindowInfo)]
+            L.pt_film_window_params_default.argtypes = [C.POINTER(FilmWindowParams)]
+            L.pt_film_window_params_default.restype = None
+            L.pt_film_render_until_windowed.argtypes = [vp, vp, C.POINTER(FilmWindowParams), FILM_PASS_FN, vp,
+                                                        C.POINTER(FilmTileStats)]
+            L.pt_film_window_kernel_times.argtypes = [vp, C.c_uint32, vp, vp]
         L.pt_last_error.restype = C.c_char_p
         L.pt_version.restype = C.c_char_p
         _gpu = L
@@ -1026,6 +1064,36 @@ class GpuScene:
         check_gpu(self.lib.pt_render_tiles_device(self.handle, C.byref(profile), C.byref(opts), t.ctypes.data, len(t),
                                                   d_rgb8 or None, d_accum or None, d_moments or None, stream))
 
+    def render_window(self, profile, s0, s1, accum=None, moments=None, opts=None, tiles=None, want_moments=True):
+        """pt_render_window: the samples [s0, s1) of the frame (profile, opts), continuing the sums in accum [n, 3] and
+        moments [n, 2] (float32; ignored and may be None when s0 == 0).  tiles: a tile list (packed layout of render_tiles),
+        None the whole frame.  Returns (rgb8, accum, moments or None) - new arrays, the arguments are not written."""
+        import numpy as np
+        opts = opts or Opts.make()
+        t = _tile_list(tiles) if tiles is not None else None
+        if t is not None:
+            n = int(self.lib.pt_tiles_pixel_count(C.byref(profile), C.byref(opts), t.ctypes.data, len(t)))
+        else:
+            n = int(self.lib.pt_local_pixel_count(C.byref(profile), C.byref(opts)))
+        rgb = np.empty((n, 3), np.uint8)
+        acc = np.zeros((n, 3), np.float32) if accum is None else np.array(accum, np.float32, order="C")
+        mom = None
+        if want_moments:
+            mom = np.zeros((n, 2), np.float32) if moments is None else np.array(moments, np.float32, order="C")
+        if acc.shape != (n, 3) or (mom is not None and mom.shape != (n, 2)):
+            raise PtError(PT_ERR_INVALID, "render_window: accum must be [n, 3] and moments [n, 2]")
+        check_gpu(self.lib.pt_render_window(self.handle, C.byref(profile), C.byref(opts), s0, s1,
+                                            t.ctypes.data if t is not None else None, len(t) if t is not None else 0,
+                                            rgb.ctypes.data, acc.ctypes.data, mom.ctypes.data if mom is not None else None))
+        return rgb, acc, mom
+
+    def render_window_device(self, profile, opts, s0, s1, d_rgb8, d_accum, d_moments, tiles=None, stream=0):
+        """pt_render_window_device: device pointers (d_rgb8 and d_moments may be 0 / None); d_accum and d_moments are in-out."""
+        t = _tile_list(tiles) if tiles is not None else None
+        check_gpu(self.lib.pt_render_window_device(self.handle, C.byref(profile), C.byref(opts), s0, s1,
+                                                   t.ctypes.data if t is not None else None, len(t) if t is not None else 0,
+                                                   d_rgb8 or None, d_accum or None, d_moments or None, stream))
+
     tiles_pixel_count = staticmethod(lambda profile, tiles, opts=None: tiles_pixel_count(profile, tiles, opts))
     tiles_pixel_map = staticmethod(lambda profile, tiles, opts=None: tiles_pixel_map(profile, tiles, opts))
 
@@ -1477,6 +1545,58 @@ class Film:
         check_gpu(self.lib.pt_film_adaptive_kernel_times(self.handle, lum_floor, self._tonemap(tonemap), reps, a.ctypes.data,
                                                          b.ctypes.data, c.ctypes.data))
         return a, b, c
+
+    # ---- windowed films
+    @classmethod
+    def windowed(cls, profile, opts=None, device=0):
+        """pt_film_create_windowed: a film whose passes are windows of ONE enumeration of profile.samples samples."""
+        self = cls.__new__(cls)
+        self.lib = gpu_lib()
+        self.handle = C.c_void_p()
+        self.tonemap = profile.tonemap if profile is not None else TONEMAPS["FILMIC"]
+        check_gpu(self.lib.pt_film_create_windowed(device, C.byref(profile) if profile is not None else None,
+                                                   C.byref(opts) if opts is not None else None, C.byref(self.handle)))
+        return self
+
+    def add_window(self, scene, samples):
+        """pt_film_add_window: the next `samples` samples of the enumeration, for every pixel."""
+        check_gpu(self.lib.pt_film_add_window(self.handle, scene.handle, samples))
+
+    def add_tile_window(self, scene, samples, tiles):
+        """pt_film_add_tile_window: the next `samples` samples of every listed tile, each from its own count."""
+        t = _tile_list(tiles)
+        check_gpu(self.lib.pt_film_add_tile_window(self.handle, scene.handle, samples, t.ctypes.data, len(t)))
+
+    @property
+    def window_info(self):
+        i = FilmWindowInfo()
+        check_gpu(self.lib.pt_film_get_window_info(self.handle, C.byref(i)))
+        return i
+
+    def render_until_windowed(self, scene, params, on_pass=None):
+        """pt_film_render_until_windowed: windows of params.window_samples samples until no tile is above the target or the
+        active tiles hold the whole enumeration; on_pass(FilmInfo, FilmNoise) after every window (copies).  Returns the last
+        FilmTileStats."""
+        out = FilmTileStats()
+        failure = []
+
+        def trampoline(info, noise, _user):
+            try:
+                on_pass(_copy(FilmInfo, info.contents), _copy(FilmNoise, noise.contents))
+            except BaseException as e:   # (an exception cannot cross the C frames: raised after the call)
+                failure.append(e)
+        cb = FILM_PASS_FN(trampoline) if on_pass is not None else C.cast(None, FILM_PASS_FN)
+        check_gpu(self.lib.pt_film_render_until_windowed(self.handle, scene.handle, C.byref(params), cb, None, C.byref(out)))
+        if failure:
+            raise failure[0]
+        return out
+
+    def window_kernel_times(self, reps=20):
+        """pt_film_window_kernel_times: ms of (k_film_gather_tiles, k_film_scatter_tiles) over every tile, [reps] each."""
+        import numpy as np
+        a, b = np.zeros(reps, np.float32), np.zeros(reps, np.float32)
+        check_gpu(self.lib.pt_film_window_kernel_times(self.handle, reps, a.ctypes.data, b.ctypes.data))
+        return a, b
 
     # ---- the film filter (DESIGN 4j)
     def denoise_scratch_bytes(self):

@@ -49,6 +49,7 @@
 #include "pt_lightmix.h"
 #include "pt_film.h"
 #include "pt_film_denoise.h"
+#include "pt_film_window.h"
 #include "pthost.h"
 #include "../host/scene_check.h"
 
@@ -2227,12 +2228,24 @@ struct Frame {
     // a tile-list frame (pt_render_tiles): the tile map is the caller's list, the outputs are packed in list order; it leaves the
     // scene's steady state - plans, frame caches, the count of frames before the escape masks - as it found it
     bool tile_list = false;
+    // a window frame (pt_render_window): the samples [win_s0, win_s1) of the frame's enumeration, the sums carried
+    // in from the caller's buffers where win_s0 > 0; like a tile-list frame it keeps out of the scene's steady state
+    bool window = false;
+    uint32_t win_s0 = 0, win_s1 = 0;
+    bool detached() const { return tile_list || window; }   // a first frame every time: no plan, no frame cache
+    uint32_t first_sample() const { return window ? win_s0 : 0u; }
+    uint32_t end_sample() const { return window ? win_s1 : p.samples; }
 };
 
 // The tiles of a tile-list frame: global tile numbers, strictly ascending.
 struct TileList {
     const uint32_t* tiles;
     uint32_t n;
+};
+
+// The samples [s0, s1) of a window frame, 0 <= s0 < s1 <= profile.samples.
+struct SampleWindow {
+    uint32_t s0, s1;
 };
 
 // The words of a frame's tile table: the packed offset of every local tile, their global tile numbers (tile_k_base), then -
@@ -2285,13 +2298,21 @@ const uint32_t* tile_table(pt_scene& s, const pt_profile& p, const pt_opts& o, c
 // area.  false: this rank has no pixels.  list: a tile-list frame's tiles (everything such a frame refuses is refused before
 // any device work; then it waits for the device - its table and its statistics slot are rewritten in place).
 bool frame_setup(pt_scene& s, const pt_profile& p, const pt_opts* opts_in, void* d_accum, hipStream_t stream, Frame& f,
-                 const TileList* list = nullptr) {
+                 const TileList* list = nullptr, const SampleWindow* win = nullptr) {
     pt_opts& o = f.o;
     normalise_opts(p, opts_in, o);
     if (p.samples == 0) fail(PT_ERR_INVALID, "profile.samples must be > 0");
     if (p.brdf != PT_BRDF_COOK_TORRANCE) fail(PT_ERR_INVALID, "unknown brdf %d", p.brdf);
     if (p.tonemap < 0 || p.tonemap > 2) fail(PT_ERR_INVALID, "unknown tonemap %d", p.tonemap);
     f.tile_list = list != nullptr;
+    if (win) {
+        if (win->s0 >= win->s1 || win->s1 > p.samples)
+            fail(PT_ERR_INVALID, "pt_render_window: the window [%u, %u) of a frame of %u samples", win->s0, win->s1, p.samples);
+        if (!d_accum) fail(PT_ERR_INVALID, "pt_render_window: a window needs the accum buffer (its sums are carried there)");
+        f.window = true;
+        f.win_s0 = win->s0;
+        f.win_s1 = win->s1;
+    }
     if (list) {
         if (p.bounces > 4096u) fail(PT_ERR_INVALID, "profile.bounces %u is out of range (at most 4096)", p.bounces);
         f.tm = make_tile_list_map("pt_render_tiles", p, o, list->tiles, list->n);
@@ -2302,7 +2323,7 @@ bool frame_setup(pt_scene& s, const pt_profile& p, const pt_opts* opts_in, void*
     const TileMap& tm = f.tm;
     if (tm.n_local == 0) return false;
     // escape masks: from the scene's (escape_after + 1)th frame of the default pipeline on (scene_upload has the reason)
-    if (!list && s.escape_wanted && !s.escape_tried && !(o.flags & (PT_FLAG_NO_GRIDS | PT_FLAG_MEGAKERNEL))) {
+    if (!f.detached() && s.escape_wanted && !s.escape_tried && !(o.flags & (PT_FLAG_NO_GRIDS | PT_FLAG_MEGAKERNEL))) {
         if (s.frames_rendered >= s.escape_after) escape_masks_build(s);
         ++s.frames_rendered;
     }
@@ -2310,8 +2331,10 @@ bool frame_setup(pt_scene& s, const pt_profile& p, const pt_opts* opts_in, void*
     f.dev = s.dev;
     if (o.flags & PT_FLAG_NO_GRIDS) f.dev.escape = nullptr;
     uint32_t tile_order_base = 0, tile_k_base = 0;
+    // (the tile-list frame before this one may still read the table; the detached frame before this one may still write the
+    // statistics slot these frames share)
+    if (f.detached()) HIP_CHECK(hipDeviceSynchronize());
     if (list) {
-        HIP_CHECK(hipDeviceSynchronize());   // (the tile-list frame before this one may still read the table)
         const std::vector<uint32_t> table = tile_table_words(tm, f.env.morton);
         s.tile_list_table.ensure(table.size() * 4);
         HIP_CHECK(hipMemcpy(s.tile_list_table.p, table.data(), table.size() * 4, hipMemcpyHostToDevice));
@@ -2370,6 +2393,7 @@ bool frame_setup(pt_scene& s, const pt_profile& p, const pt_opts* opts_in, void*
     f.blocks64 = tm.n_local_tiles * (o.tile_w / 8u) * (o.tile_h / 8u);
     if (s.n_cu == 0) HIP_CHECK(hipDeviceGetAttribute(&s.n_cu, hipDeviceAttributeMultiprocessorCount, s.device));
     f.batch = o.sample_batch ? o.sample_batch : p.samples;
+    if (f.window) f.batch = std::min(f.batch, f.win_s1 - f.win_s0);
     f.alpha = s.dev.has_translucent != 0;
     if (f.wavefront) {
         uint64_t per_sample = tm.n_local * 12u;
@@ -2551,7 +2575,7 @@ WfFrame frame_plan(pt_scene& s, const Frame& f, const QueueEnv& qe) {
                                             o.flags & (PT_FLAG_NO_GRIDS | PT_FLAG_MEGAKERNEL | PT_FLAG_COUNTERS), (uint64_t)f.bounce0_fused, o.shard_rank, o.shard_count, o.tile_w, o.tile_h, f.batch, (uint64_t)wf.max_items};
     wf.cap_a = (uint32_t)std::min<uint64_t>(wf.max_items, std::max<uint64_t>(1u << 20, (uint64_t)(qe.first_gib * 1073741824.0) / wf.per_item) & ~63ull);
     if (s.wf_cap_ok) wf.cap_a = std::min(wf.cap_a, s.wf_cap_ok);
-    if (f.tile_list) {
+    if (f.detached()) {
         // a first frame, every time: no plan is read or made, and no key another frame can meet is touched.  (frame_setup
         // waited for the device: the counts of the tile-list frame before are home, nothing refers to the slot's event.)
         if (!s.tile_frame_stats) s.tile_frame_stats = std::make_unique<pt_scene::FrameStats>();
@@ -2676,7 +2700,7 @@ void queue_buffers(pt_scene& s, const Frame& f, const QueueEnv& qe, WfFrame& wf)
         wf.cap_q[0] = wf.cap_q[1] = wf.cap_h = wf.cap_s = wf.cap_e = wf.cap;
         std::fill(wf.inline_at.begin(), wf.inline_at.end(), 0);
     }
-    if (f.tile_list) return;   // (pt_scene_get_info goes on reporting the last whole frame)
+    if (f.detached()) return;   // (pt_scene_get_info goes on reporting the last whole frame)
     s.queue_bytes_last = w.queue[0].bytes + w.queue[1].bytes + w.hits.bytes + w.shadow.bytes + w.contrib.bytes + w.rng[0].bytes +
                          w.rng[1].bytes + w.draws.bytes + w.offgrid.bytes + w.exact[0].bytes + w.exact[1].bytes + w.deferred.bytes;
     s.queue_chunk_last = wf.cap;
@@ -2859,8 +2883,8 @@ void stats_slots(pt_scene& s, const Frame& f, WfFrame& wf) {
     pt_scene::FrameStats* fs = wf.fs;
     const uint32_t levels = f.p.bounces + 3;
     uint32_t n = 0;
-    for (uint32_t s0 = 0; s0 < f.p.samples; s0 += f.batch) {
-        const uint64_t tot = (uint64_t)f.blocks64 * 64u * std::min(f.batch, f.p.samples - s0);
+    for (uint32_t s0 = f.first_sample(); s0 < f.end_sample(); s0 += f.batch) {
+        const uint64_t tot = (uint64_t)f.blocks64 * 64u * std::min(f.batch, f.end_sample() - s0);
         n += (uint32_t)((tot + wf.cap - 1u) / wf.cap);
     }
     if (fs->pending) return;
@@ -3546,7 +3570,7 @@ void frame_readout(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, void*
     if (f.timing) HIP_CHECK(hipEventRecord(get_event(s, tl.ev++), stream));
     if (d_rgb8) {
         hipLaunchKernelGGL(k_postprocess, dim3(((uint32_t)f.tm.n_local + 255u) / 256u), dim3(256), 0, stream, f.accum,
-                           (uint8_t*)d_rgb8, (uint32_t)f.tm.n_local, p.samples, p.tonemap);
+                           (uint8_t*)d_rgb8, (uint32_t)f.tm.n_local, f.end_sample(), p.tonemap);
         HIP_CHECK(hipGetLastError());
     }
     if (f.timing) HIP_CHECK(hipEventRecord(get_event(s, tl.ev++), stream));
@@ -3623,13 +3647,15 @@ struct FrameTaps {
 };
 
 // One frame of pt_render, pt_render_device and pt_render_gathered; taps: of pt_render_moments and pt_render_samples.
-// list: a tile-list frame (pt_render_tiles, pt_film_add_tile_pass).
+// list: a tile-list frame (pt_render_tiles, pt_film_add_tile_pass).  win: a window frame (pt_render_window) - the batch loop
+// runs over its samples only, and the first batch carries the sums d_accum and taps->moments hold unless the window starts at 0.
 void render_device(pt_scene& s, const pt_profile& p, const pt_opts* opts_in, void* d_rgb8, void* d_accum,
-                   hipStream_t stream, bool allow_preview = false, const FrameTaps* taps = nullptr, const TileList* list = nullptr) {
+                   hipStream_t stream, bool allow_preview = false, const FrameTaps* taps = nullptr, const TileList* list = nullptr,
+                   const SampleWindow* win = nullptr) {
     Frame f;
-    // (a tile-list frame refuses before any device work, and frame_setup waits for the device for it)
-    if (taps && list && opts_in && (opts_in->flags & PT_FLAG_MEGAKERNEL)) fail(PT_ERR_UNSUPPORTED, "this pipeline stages no samples");
-    if (!frame_setup(s, p, opts_in, d_accum, stream, f, list)) return;
+    // (a tile-list or window frame refuses before any device work, and frame_setup waits for the device for it)
+    if (taps && (list || win) && opts_in && (opts_in->flags & PT_FLAG_MEGAKERNEL)) fail(PT_ERR_UNSUPPORTED, "this pipeline stages no samples");
+    if (!frame_setup(s, p, opts_in, d_accum, stream, f, list, win)) return;
     if (taps && !f.wavefront) fail(PT_ERR_UNSUPPORTED, "this pipeline stages no samples");
     const pt_opts& o = f.o;
     WfFrame wf;
@@ -3638,7 +3664,7 @@ void render_device(pt_scene& s, const pt_profile& p, const pt_opts* opts_in, voi
         wf = frame_plan(s, f, qe);
         // (a tile-list frame enters no cache: every pointer stays null - what a frame launches when every cache is out of use -
         // and no last_key moves, so the next whole frame still follows its predecessor)
-        if (!f.tile_list) frame_caches(s, f, wf, stream);
+        if (!f.detached()) frame_caches(s, f, wf, stream);
         queue_buffers(s, f, qe, wf);
         stats_slots(s, f, wf);
         side_streams(s, f, wf);
@@ -3647,9 +3673,9 @@ void render_device(pt_scene& s, const pt_profile& p, const pt_opts* opts_in, voi
     Timeline tl{s, f.timing, stream};
     wf.block_empty = camera_cull(s, f, stream);
     RenderParams P = f.P;
-    for (uint32_t s0 = 0; s0 < p.samples; s0 += f.batch) {
+    for (uint32_t s0 = f.first_sample(); s0 < f.end_sample(); s0 += f.batch) {
         P.sample_begin = s0;
-        P.sample_end = std::min(p.samples, s0 + f.batch);
+        P.sample_end = std::min(f.end_sample(), s0 + f.batch);
         const uint32_t nb = P.sample_end - P.sample_begin;
         pt_fastdiv_make(nb, P.div_batch);
         if (!f.wavefront) {
@@ -4026,6 +4052,10 @@ struct pt_film {
     // first host call of the pt_film_denoise family, kept by pt_film_reset.
     uint8_t* filter = nullptr;
     uint64_t bytes_filter = 0;
+    // A windowed film (pt_film_create_windowed): every pass is a window of ONE enumeration of enum_n samples per
+    // pixel, so a pixel at count c holds the sums of the samples [0, c) of pt_render(samples = enum_n).
+    bool windowed = false;
+    uint32_t enum_n = 0, windows = 0, tile_windows = 0;
     bool uniform() const { return count == nullptr; }
     ~pt_film() {
         if (filter) (void)hipFree(filter);
@@ -4073,6 +4103,7 @@ void film_check_noise_args(const char* who, float lum_floor, double target) {
 
 // What pt_film_add_pass and pt_film_add_planes refuse, before any device work.
 void film_check_samples(const char* who, const pt_film* film, uint32_t samples) {
+    if (film->windowed) fail(PT_ERR_INVALID, "%s: a windowed film takes windows only (pt_film_add_window)", who);
     if (samples < 1u) fail(PT_ERR_INVALID, "%s: a pass needs samples >= 1", who);
     if (film->passes && (uint64_t)samples < 2u * (uint64_t)film->last_pass_samples)
         fail(PT_ERR_INVALID, "%s: a pass of %u samples after one of %u (at least twice as many: an equal pass would repeat its seeds)",
@@ -4334,6 +4365,7 @@ void film_resolve_launch(const pt_film& film, int tonemap_type, uint8_t* d_rgb8,
 // What the adaptive loops refuse before any device work (the null checks are the callers').
 void film_check_adaptive(const char* who, const pt_film* film, const pt_scene* scene, const pt_film_adaptive_params* params) {
     film_check_tiled(who, film);
+    if (film->windowed) fail(PT_ERR_INVALID, "%s: a windowed film takes windows only (pt_film_render_until_windowed)", who);
     film_check_noise_args(who, params->lum_floor, params->target);
     if (params->first_pass_samples < 2u) fail(PT_ERR_INVALID, "%s: first_pass_samples must be >= 2 (a sample variance needs two)", who);
     if (params->dilate > 1u) fail(PT_ERR_INVALID, "%s: dilate must be 0 or 1", who);
@@ -4343,6 +4375,22 @@ void film_check_adaptive(const char* who, const pt_film* film, const pt_scene* s
         fail(PT_ERR_INVALID, "%s: the scene is on device %d, the film on device %d", who, scene->device, film->device);
 }
 
+// Steps 5 and 6 of the adaptive loops: the candidates - the tiles whose mean error is above the target - and, dilate: their 8
+// neighbours, ascending.
+void film_select_active(const FilmTiling& T, const std::vector<float>& sums, double target, uint32_t dilate, std::vector<uint32_t>& active) {
+    const uint32_t n_tiles = (uint32_t)sums.size(), tiles_y = n_tiles / T.tiles_x;
+    std::vector<uint8_t> on(n_tiles, 0);
+    for (uint32_t t = 0; t < n_tiles; ++t) {
+        if (!((double)sums[t] / (double)film_tile_pixels(T, t) > target)) continue;
+        const int tx = (int)(t % T.tiles_x), ty = (int)(t / T.tiles_x), r = (int)dilate;
+        for (int y = std::max(0, ty - r); y <= std::min((int)tiles_y - 1, ty + r); ++y)
+            for (int x = std::max(0, tx - r); x <= std::min((int)T.tiles_x - 1, tx + r); ++x) on[(uint32_t)y * T.tiles_x + (uint32_t)x] = 1;
+    }
+    active.clear();
+    for (uint32_t t = 0; t < n_tiles; ++t)
+        if (on[t]) active.push_back(t);
+}
+
 // The loop of pt_film_render_until_adaptive (include/ptgpu.h, steps 1 - 8).  noise(st, sums): step 4 - the tile statistics of
 // what the film holds and, where sums is not null, the n_tiles tile sums the selection reads.
 template <class Noise>
@@ -4350,7 +4398,7 @@ void film_adaptive_loop(pt_film* film, const pt_scene* scene, const pt_film_adap
                         void* user, pt_film_tile_stats* out, Noise noise) {
     const uint64_t cap = std::min<uint64_t>(params->max_samples, (uint64_t)PT_FILM_MAX_SAMPLES);
     const FilmTiling T = film_tiling(*film);
-    const uint32_t n_tiles = film_n_tiles(*film), tiles_y = n_tiles / T.tiles_x;
+    const uint32_t n_tiles = film_n_tiles(*film);
     std::vector<float> sums(n_tiles);
     std::vector<uint32_t> active;   // the tiles of the next pass; empty: every tile
     pt_film_tile_stats st{};
@@ -4359,17 +4407,7 @@ void film_adaptive_loop(pt_film* film, const pt_scene* scene, const pt_film_adap
         noise(st, sums.data());
         st.active_tiles = rendered;
         measured = true;
-        // the candidates - the tiles above the target - and, dilate: their 8 neighbours
-        std::vector<uint8_t> on(n_tiles, 0);
-        for (uint32_t t = 0; t < n_tiles; ++t) {
-            if (!((double)sums[t] / (double)film_tile_pixels(T, t) > params->target)) continue;
-            const int tx = (int)(t % T.tiles_x), ty = (int)(t / T.tiles_x), r = (int)params->dilate;
-            for (int y = std::max(0, ty - r); y <= std::min((int)tiles_y - 1, ty + r); ++y)
-                for (int x = std::max(0, tx - r); x <= std::min((int)T.tiles_x - 1, tx + r); ++x) on[(uint32_t)y * T.tiles_x + (uint32_t)x] = 1;
-        }
-        active.clear();
-        for (uint32_t t = 0; t < n_tiles; ++t)
-            if (on[t]) active.push_back(t);
+        film_select_active(T, sums, params->target, params->dilate, active);
     };
     if (film->passes && film->samples >= 2u && film->samples >= params->uniform_samples) measure(0);   // (a film that has passes: its own active set)
     for (;;) {
@@ -4394,6 +4432,187 @@ void film_adaptive_loop(pt_film* film, const pt_scene* scene, const pt_film_adap
         }
     }
     if (!measured) noise(st, nullptr);   // (no pass fits: what the film holds)
+    *out = st;
+}
+
+// ---- windowed films (pt_film_window.h)
+uint64_t film_count_of(const pt_film& film, uint32_t tile) { return film.uniform() ? film.samples : film.tile_count[tile]; }
+
+// What the window calls refuse before any device work.
+void film_check_window(const char* who, const pt_film* film, const pt_scene* scene, uint32_t samples) {
+    if (!film || !scene) fail(PT_ERR_INVALID, "%s: null argument", who);
+    if (!film->windowed) fail(PT_ERR_INVALID, "%s: the film is not windowed (pt_film_create_windowed)", who);
+    if (samples < 1u) fail(PT_ERR_INVALID, "%s: a window needs samples >= 1", who);
+    if (scene->device != film->device)
+        fail(PT_ERR_INVALID, "%s: the scene is on device %d, the film on device %d", who, scene->device, film->device);
+}
+
+// The frame's moments tap and the window [s0, s0 + samples) of the film's enumeration, rendered into (d_accum, d_moments) -
+// packed in list order where list is not null - which hold the sums of [0, s0).  Waits for the frame.
+void film_render_window(pt_film& film, const pt_scene* scene, uint32_t s0, uint32_t samples, const TileList* list, float* d_accum,
+                        float* d_moments) {
+    pt_profile p = film.profile;
+    p.samples = film.enum_n;
+    FrameTaps taps;
+    taps.moments = (float2*)d_moments;
+    const SampleWindow win{s0, s0 + samples};
+    render_device(render_state(scene), p, &film.opts, nullptr, d_accum, nullptr, false, &taps, list, &win);
+    HIP_CHECK(hipDeviceSynchronize());   // the frame is complete (and has not failed) before the film changes
+}
+
+// The tile window: every listed tile t continues at its own count.  The tiles are grouped by count, counts ascending; group g
+// is gathered to its own run of the pass buffers and rendered there as one tile-list window frame.  Only when every frame has
+// completed are the runs scattered back - a failure before that leaves the film as it was.
+void film_add_tile_window(pt_film& film, const pt_scene* scene, uint32_t samples, const uint32_t* tiles, uint32_t n_tiles) {
+    const char* who = "pt_film_add_tile_window";
+    film_check_window(who, &film, scene, samples);
+    film_check_tiled(who, &film);
+    const TileMap whole = make_tile_list_map(who, film.profile, film.opts, tiles, n_tiles);
+    std::map<uint64_t, std::vector<uint32_t>> groups;   // count -> its tiles, ascending both ways
+    for (uint32_t k : whole.tiles) {
+        const uint64_t c = film_count_of(film, k);
+        if (c + samples > film.enum_n)
+            fail(PT_ERR_INVALID, "%s: tile %u holds %llu samples, %u more would pass the enumeration's %u", who, k, (unsigned long long)c, samples, film.enum_n);
+        groups[c].push_back(k);
+    }
+    HIP_CHECK(hipSetDevice(film.device));
+    const size_t table_before = film.table.bytes;
+    film.table.ensure((size_t)(2u * film_n_tiles(film) + 1u) * 4u);
+    film.bytes_adaptive += film.table.bytes - table_before;
+    const FilmTiling T = film_tiling(film);
+    struct Run {
+        TileMap tm;
+        uint64_t off;   // the run's first packed pixel in the pass buffers
+    };
+    std::vector<Run> runs;
+    uint64_t off = 0;
+    auto upload = [&](const TileMap& tm) {
+        std::vector<uint32_t> table(tm.offsets);
+        table.insert(table.end(), tm.tiles.begin(), tm.tiles.end());
+        HIP_CHECK(hipMemcpy(film.table.p, table.data(), table.size() * 4u, hipMemcpyHostToDevice));
+    };
+    for (auto& g : groups) {
+        Run r{make_tile_list_map(who, film.profile, film.opts, g.second.data(), (uint32_t)g.second.size()), off};
+        float* pa = film.pass_accum + 3u * r.off;
+        float* pm = film.pass_moments + 2u * r.off;
+        upload(r.tm);
+        hipLaunchKernelGGL(k_film_gather_tiles, dim3(r.tm.n_local_tiles), dim3(256), 0, 0, (const float*)film.accum,
+                           (const float2*)film.moments, (const uint32_t*)film.table.p, r.tm.n_local_tiles, T, pa, (float2*)pm);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());   // (the table is rewritten by the next run)
+        const TileList list{g.second.data(), (uint32_t)g.second.size()};
+        film_render_window(film, scene, (uint32_t)g.first, samples, &list, pa, pm);
+        off += r.tm.n_local;
+        runs.push_back(std::move(r));
+    }
+    film_make_non_uniform(film);
+    for (const Run& r : runs) {
+        upload(r.tm);
+        hipLaunchKernelGGL(k_film_scatter_tiles, dim3(r.tm.n_local_tiles), dim3(256), 0, 0, (const float*)(film.pass_accum + 3u * r.off),
+                           (const float2*)(film.pass_moments + 2u * r.off), (const uint32_t*)film.table.p, r.tm.n_local_tiles, T,
+                           film.accum, (float2*)film.moments, film.count, samples);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        for (uint32_t k : r.tm.tiles) film.tile_count[k] += samples;
+    }
+    ++film.passes;
+    ++film.tile_passes;
+    ++film.tile_windows;
+    film.last_pass_tiles = n_tiles;
+    film.last_pass_samples = samples;
+    film.samples = *std::max_element(film.tile_count.begin(), film.tile_count.end());
+}
+
+// The whole-frame window [n, n + samples) of every pixel.  A uniform film renders it into the pass buffers, seeded with a
+// copy of the film, and adopts them on success; a non-uniform one takes the tile window that lists every tile.
+void film_add_window(pt_film& film, const pt_scene* scene, uint32_t samples) {
+    const char* who = "pt_film_add_window";
+    film_check_window(who, &film, scene, samples);
+    if (!film.uniform()) {
+        std::vector<uint32_t> all(film_n_tiles(film));
+        for (uint32_t k = 0; k < all.size(); ++k) all[k] = k;
+        return film_add_tile_window(film, scene, samples, all.data(), (uint32_t)all.size());
+    }
+    if (film.samples + samples > film.enum_n)
+        fail(PT_ERR_INVALID, "%s: the film holds %llu samples, %u more would pass the enumeration's %u", who, (unsigned long long)film.samples, samples, film.enum_n);
+    HIP_CHECK(hipSetDevice(film.device));
+    if (film.samples) {
+        HIP_CHECK(hipMemcpy(film.pass_accum, film.accum, film.stride_a * sizeof(float), hipMemcpyDeviceToDevice));
+        HIP_CHECK(hipMemcpy(film.pass_moments, film.moments, film.stride_m * sizeof(float), hipMemcpyDeviceToDevice));
+    }
+    film_render_window(film, scene, (uint32_t)film.samples, samples, nullptr, film.pass_accum, film.pass_moments);
+    HIP_CHECK(hipMemcpy(film.accum, film.pass_accum, film.n_local * 12u, hipMemcpyDeviceToDevice));
+    HIP_CHECK(hipMemcpy(film.moments, film.pass_moments, film.n_local * 8u, hipMemcpyDeviceToDevice));
+    HIP_CHECK(hipDeviceSynchronize());
+    ++film.passes;
+    ++film.windows;
+    film.last_pass_samples = samples;
+    film.last_pass_tiles = 0;
+    film.samples += samples;
+}
+
+void film_check_window_params(const char* who, const pt_film* film, const pt_scene* scene, const pt_film_window_params* params) {
+    if (!film->windowed) fail(PT_ERR_INVALID, "%s: the film is not windowed (pt_film_create_windowed)", who);
+    film_check_tiled(who, film);
+    film_check_noise_args(who, params->lum_floor, params->target);
+    if (params->window_samples < 1u) fail(PT_ERR_INVALID, "%s: window_samples must be >= 1", who);
+    if (!film->passes && params->window_samples < 2u)
+        fail(PT_ERR_INVALID, "%s: the first window needs >= 2 samples (a sample variance needs two)", who);
+    if (params->dilate > 1u) fail(PT_ERR_INVALID, "%s: dilate must be 0 or 1", who);
+    if (params->adaptive > 1u) fail(PT_ERR_INVALID, "%s: adaptive must be 0 or 1", who);
+    if (scene->device != film->device)
+        fail(PT_ERR_INVALID, "%s: the scene is on device %d, the film on device %d", who, scene->device, film->device);
+}
+
+// The loop of pt_film_render_until_windowed (include/ptgpu.h).
+void film_window_loop(pt_film* film, const pt_scene* scene, const pt_film_window_params* params, pt_film_pass_fn on_pass, void* user,
+                      pt_film_tile_stats* out) {
+    const FilmTiling T = film_tiling(*film);
+    const uint32_t n_tiles = film_n_tiles(*film), N = film->enum_n;
+    std::vector<float> sums(n_tiles);
+    std::vector<uint32_t> active, todo;
+    pt_film_tile_stats st{};
+    bool measured = false;
+    auto measure = [&](uint32_t rendered) {
+        film_tile_noise(*film, params->lum_floor, params->target, st, nullptr, sums.data(), nullptr);
+        st.active_tiles = rendered;
+        measured = true;
+        film_select_active(T, sums, params->target, params->dilate, active);
+    };
+    auto least = [&] { return film->uniform() ? film->samples : *std::min_element(film->tile_count.begin(), film->tile_count.end()); };
+    if (film->passes && least() >= 2u && (!params->adaptive || film->samples >= params->uniform_samples)) measure(0);
+    for (;;) {
+        if (measured && st.converged) break;
+        const bool all = !measured || !film->passes || !params->adaptive || film->samples < params->uniform_samples;
+        // the tiles of the next window: the active set without the tiles that are full; the window is clipped so that none passes N
+        todo.clear();
+        uint64_t most = 0;
+        for (uint32_t i = 0; i < (all ? n_tiles : (uint32_t)active.size()); ++i) {
+            const uint32_t t = all ? i : active[i];
+            const uint64_t c = film_count_of(*film, t);
+            if (c >= N) continue;
+            todo.push_back(t);
+            most = std::max(most, c);
+        }
+        if (todo.empty()) break;   // budget
+        const uint32_t w = (uint32_t)std::min<uint64_t>(params->window_samples, N - most);
+        if (film->uniform() && todo.size() == n_tiles) film_add_window(*film, scene, w);
+        else film_add_tile_window(*film, scene, w, todo.data(), (uint32_t)todo.size());
+        measure((uint32_t)todo.size());
+        if (on_pass) {
+            pt_film_info info;
+            film_fill_info(*film, info);
+            pt_film_noise_stats ns{};
+            ns.mean_error = st.mean_error;
+            ns.max_block_error = st.max_tile_error;
+            ns.fraction_over = (double)st.over_tiles / (double)n_tiles;
+            ns.samples = st.samples;
+            ns.n_blocks = n_tiles;
+            ns.converged = st.converged;
+            on_pass(&info, &ns, user);
+        }
+    }
+    if (!measured) film_tile_noise(*film, params->lum_floor, params->target, st, nullptr, nullptr, nullptr);   // (a full film that was never measured)
     *out = st;
 }
 
@@ -4702,6 +4921,50 @@ int pt_render_tiles(const pt_scene* scene, const pt_profile* profile, const pt_o
     });
 }
 
+int pt_render_window_device(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, uint32_t s0, uint32_t s1,
+                            const uint32_t* tiles, uint32_t n_tiles, void* d_rgb8, void* d_accum, void* d_moments, void* hip_stream) {
+    return guarded([&] {
+        if (!scene || !profile || !d_accum) fail(PT_ERR_INVALID, "pt_render_window_device: null argument");
+        if (d_moments) moments_check_opts("pt_render_window_device", opts);
+        const TileList list{tiles, n_tiles};
+        const SampleWindow win{s0, s1};
+        FrameTaps taps;
+        taps.moments = (float2*)d_moments;
+        render_device(render_state(scene), *profile, opts, d_rgb8, d_accum, (hipStream_t)hip_stream, false,
+                      d_moments ? &taps : nullptr, tiles ? &list : nullptr, &win);
+    });
+}
+
+int pt_render_window(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, uint32_t s0, uint32_t s1,
+                     const uint32_t* tiles, uint32_t n_tiles, uint8_t* rgb8, float* accum, float* moments) {
+    return guarded([&] {
+        const char* who = "pt_render_window";
+        if (!scene || !profile || !accum) fail(PT_ERR_INVALID, "%s: null argument", who);
+        if (s0 >= s1 || s1 > profile->samples)
+            fail(PT_ERR_INVALID, "%s: the window [%u, %u) of a frame of %u samples", who, s0, s1, profile->samples);
+        pt_opts o;
+        normalise_opts(*profile, opts, o);
+        const uint64_t n = tiles ? make_tile_list_map(who, *profile, o, tiles, n_tiles).n_local
+                                 : make_tile_map(*profile, o, o.shard_rank).n_local;
+        if (moments) moments_check_opts(who, opts);
+        HIP_CHECK(hipSetDevice(scene->device));
+        // (the carry: the sums of [0, s0) go in with the buffers; a window that starts at 0 overwrites them)
+        Staged<uint8_t> d_rgb(nullptr, n * 3);
+        Staged<float> d_acc(s0 ? accum : nullptr, n * 3);
+        Staged<float2> d_mom(s0 ? (const float2*)moments : nullptr, moments ? n : 0);
+        const TileList list{tiles, n_tiles};
+        const SampleWindow win{s0, s1};
+        FrameTaps taps;
+        taps.moments = d_mom.d;
+        render_device(render_state(scene), *profile, opts, d_rgb.d, d_acc.d, nullptr, false, moments ? &taps : nullptr,
+                      tiles ? &list : nullptr, &win);
+        HIP_CHECK(hipDeviceSynchronize());
+        if (rgb8) d_rgb.fetch(rgb8, n * 3);
+        d_acc.fetch(accum, n * 3);
+        if (moments) d_mom.fetch((float2*)moments, n);
+    });
+}
+
 int pt_debug_render(const pt_scene* scene, uint32_t width, uint32_t height, uint8_t* planes, int* any_hit) {
     return guarded([&] {
         if (!scene || !planes || !any_hit) fail(PT_ERR_INVALID, "pt_debug_render: null argument");
@@ -4987,6 +5250,7 @@ int pt_film_reset(pt_film* film) {
             film->tile_count.clear();
         }
         film->tile_passes = film->last_pass_tiles = 0;
+        film->windows = film->tile_windows = 0;
         film->passes = 0;
         film->last_pass_samples = 0;
         film->samples = 0;
@@ -5075,6 +5339,7 @@ int pt_film_render_until(pt_film* film, const pt_scene* scene, uint32_t first_pa
     return guarded([&] {
         if (!film || !scene || !out) fail(PT_ERR_INVALID, "pt_film_render_until: null argument");
         if (!film->has_profile) fail(PT_ERR_INVALID, "pt_film_render_until: a film made from planes has no profile to render with");
+        if (film->windowed) fail(PT_ERR_INVALID, "pt_film_render_until: a windowed film takes windows only (pt_film_render_until_windowed)");
         film_refuse_non_uniform("pt_film_render_until", film);
         film_check_noise_args("pt_film_render_until", lum_floor, target);
         if (first_pass_samples < 2u) fail(PT_ERR_INVALID, "pt_film_render_until: first_pass_samples must be >= 2 (a sample variance needs two)");
@@ -5222,6 +5487,113 @@ int pt_film_render_until_adaptive(pt_film* film, const pt_scene* scene, const pt
                            [&](pt_film_tile_stats& st, float* sums) {
                                film_tile_noise(*film, params->lum_floor, params->target, st, nullptr, sums, nullptr);
                            });
+    });
+}
+
+// ---- windowed films
+int pt_film_create_windowed(int device, const pt_profile* profile, const pt_opts* opts, pt_film** out) {
+    if (profile && out && (profile->samples < 2u || profile->samples > PT_FILM_MAX_SAMPLES))
+        return guarded([&] {
+            fail(PT_ERR_INVALID, "pt_film_create_windowed: the enumeration (profile.samples) must be in 2 .. %u (got %u)",
+                 (unsigned)PT_FILM_MAX_SAMPLES, profile->samples);
+        });
+    const int rc = pt_film_create(device, profile, opts, out);
+    if (rc == PT_OK) {
+        (*out)->windowed = true;
+        (*out)->enum_n = profile->samples;
+    }
+    return rc;
+}
+
+int pt_film_add_window(pt_film* film, const pt_scene* scene, uint32_t samples) {
+    return guarded([&] {
+        film_check_window("pt_film_add_window", film, scene, samples);
+        film_add_window(*film, scene, samples);
+    });
+}
+
+int pt_film_add_tile_window(pt_film* film, const pt_scene* scene, uint32_t samples, const uint32_t* tiles, uint32_t n_tiles) {
+    return guarded([&] {
+        film_check_window("pt_film_add_tile_window", film, scene, samples);
+        film_add_tile_window(*film, scene, samples, tiles, n_tiles);
+    });
+}
+
+int pt_film_get_window_info(const pt_film* film, pt_film_window_info* out) {
+    return guarded([&] {
+        if (!film || !out) fail(PT_ERR_INVALID, "pt_film_get_window_info: null argument");
+        memset(out, 0, sizeof *out);
+        out->windowed = film->windowed ? 1u : 0u;
+        out->enumeration = film->enum_n;
+        out->windows = film->windows;
+        out->tile_windows = film->tile_windows;
+    });
+}
+
+void pt_film_window_params_default(pt_film_window_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    p->lum_floor = PT_FILM_DEFAULT_LUM_FLOOR;
+    p->target = 0.02;
+    p->window_samples = PT_FILM_DEFAULT_WINDOW_SAMPLES;
+    p->adaptive = 1;
+    p->uniform_samples = 24;
+    p->dilate = 1;
+}
+
+int pt_film_render_until_windowed(pt_film* film, const pt_scene* scene, const pt_film_window_params* params, pt_film_pass_fn on_pass,
+                                  void* user, pt_film_tile_stats* out) {
+    return guarded([&] {
+        const char* who = "pt_film_render_until_windowed";
+        if (!film || !scene || !params || !out) fail(PT_ERR_INVALID, "%s: null argument", who);
+        film_check_window_params(who, film, scene, params);
+        film_window_loop(film, scene, params, on_pass, user, out);
+    });
+}
+
+int pt_film_window_kernel_times(pt_film* film, uint32_t reps, float* ms_gather, float* ms_scatter) {
+    return guarded([&] {
+        const char* who = "pt_film_window_kernel_times";
+        if (!film || !ms_gather || !ms_scatter || !reps) fail(PT_ERR_INVALID, "%s: null argument", who);
+        film_check_tiled(who, film);
+        if (film->uniform()) fail(PT_ERR_INVALID, "%s: the film has taken no tile window", who);
+        HIP_CHECK(hipSetDevice(film->device));
+        const uint32_t n_tiles = film_n_tiles(*film);
+        std::vector<uint32_t> all(n_tiles);
+        for (uint32_t k = 0; k < n_tiles; ++k) all[k] = k;
+        const TileMap tm = make_tile_list_map(who, film->profile, film->opts, all.data(), n_tiles);
+        std::vector<uint32_t> table(tm.offsets);
+        table.insert(table.end(), tm.tiles.begin(), tm.tiles.end());
+        HIP_CHECK(hipMemcpy(film->table.p, table.data(), table.size() * 4u, hipMemcpyHostToDevice));
+        const FilmTiling T = film_tiling(*film);
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        struct Free {
+            hipEvent_t &a, &b;
+            ~Free() {
+                if (a) (void)hipEventDestroy(a);
+                if (b) (void)hipEventDestroy(b);
+            }
+        } guard{e0, e1};
+        HIP_CHECK(hipEventCreate(&e0));
+        HIP_CHECK(hipEventCreate(&e1));
+        // gather every tile, then scatter what was gathered with zero samples: every load and store of a real tile window, and
+        // the film's planes and counts as they were
+        for (uint32_t r = 0; r < reps; ++r) {
+            HIP_CHECK(hipEventRecord(e0, 0));
+            hipLaunchKernelGGL(k_film_gather_tiles, dim3(n_tiles), dim3(256), 0, 0, (const float*)film->accum, (const float2*)film->moments,
+                               (const uint32_t*)film->table.p, n_tiles, T, film->pass_accum, (float2*)film->pass_moments);
+            HIP_CHECK(hipEventRecord(e1, 0));
+            HIP_CHECK(hipEventSynchronize(e1));
+            HIP_CHECK(hipEventElapsedTime(&ms_gather[r], e0, e1));
+            HIP_CHECK(hipEventRecord(e0, 0));
+            hipLaunchKernelGGL(k_film_scatter_tiles, dim3(n_tiles), dim3(256), 0, 0, (const float*)film->pass_accum,
+                               (const float2*)film->pass_moments, (const uint32_t*)film->table.p, n_tiles, T, film->accum,
+                               (float2*)film->moments, film->count, 0u);
+            HIP_CHECK(hipEventRecord(e1, 0));
+            HIP_CHECK(hipEventSynchronize(e1));
+            HIP_CHECK(hipEventElapsedTime(&ms_scatter[r], e0, e1));
+        }
+        HIP_CHECK(hipGetLastError());
     });
 }
 

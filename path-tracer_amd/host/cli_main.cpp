@@ -7,7 +7,8 @@
 //                              [--noise-target <T> [--min-samples <N0>] [--max-samples <N>] [--noise-map <FILE.png>]
 //                               [--adaptive [--adaptive-tile <N>] [--uniform-samples <U>] [--adaptive-dilate <0|1>]
 //                                [--sample-map <FILE.png>]]
-//                               [--film-denoise <plain|variance> [--filtered-target]]]
+//                               [--film-denoise <plain|variance> [--filtered-target]]
+//                               [--window-samples <W>]]
 //       env OUTPUT (default render.png), env PROFILE
 //   path-tracer convert <INPUT> <OUTPUT>      (glTF 2.0 -> ISF, host/gltf_convert.cpp)
 //
@@ -28,7 +29,10 @@
 // --adaptive (with --noise-target: an adaptive film, pt_film_render_until_adaptive - once every pixel has U samples the
 // passes render only the N x N tiles whose mean error is still above T, and their neighbours; N bounds the largest count),
 // --film-denoise (with --noise-target: the finished film goes through pt_film_denoise in place of pt_film_resolve) and
-// --filtered-target (with --adaptive --film-denoise variance: pt_film_render_until_filtered - T is met by the filtered error).
+// --filtered-target (with --adaptive --film-denoise variance: pt_film_render_until_filtered - T is met by the filtered error),
+// --window-samples W (with --noise-target: a windowed film, pt_film_render_until_windowed - windows of W samples of ONE
+// enumeration of N = --max-samples samples, so the frame is a prefix of the render with samples = N and, run to its budget,
+// that render byte for byte; T may be 0 here; --min-samples is refused, the first window has W samples).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -91,6 +95,10 @@ void usage_render(FILE* f) {
           "      --film-denoise <plain|variance>  With --noise-target: write the finished film, uniform or adaptive, filtered on the\n"
           "                           device by the a-trous denoiser with every pixel's own sample count (--denoise-iterations\n"
           "                           applies; one device, not with --denoise)\n"
+          "      --window-samples <W> With --noise-target: a windowed film - every pass adds the next W samples of ONE enumeration of\n"
+          "                           N = --max-samples samples (the active tiles only, with --adaptive), so the frame is a prefix of\n"
+          "                           the render with samples = N, and exactly that render when it runs to its budget; T may be 0\n"
+          "                           [>= 2; not with --min-samples or --filtered-target]\n"
           "      --filtered-target    With --adaptive --film-denoise variance: T is met by the error of the FILTERED image - tiles\n"
           "                           are selected by the variance the filter leaves; --noise-map then shows that error\n"
           "  -h, --help               Print help\n",
@@ -204,6 +212,9 @@ int run_render(int argc, char** argv) {
     uint32_t adaptive_tile = 32, uniform_samples = 0, adaptive_dilate = 1;
     std::string film_denoise;   // "", "plain" or "variance"
     bool filtered_target = false;
+    bool have_window_samples = false;
+    uint32_t window_samples = 0;
+    std::string noise_target_text;
     int device = 0;
     std::vector<int> devices;
     for (int i = 0; i < argc; ++i) {
@@ -247,8 +258,10 @@ int run_render(int argc, char** argv) {
             std::string v = value("--noise-target <T>");
             char* end = nullptr;
             noise_target = strtod(v.c_str(), &end);
-            if (v.empty() || *end || !(noise_target > 0.0) || !std::isfinite(noise_target) || !((float)noise_target > 0.f))
+            // (zero is a target only a windowed film takes - render the whole enumeration: checked once every flag is known)
+            if (v.empty() || *end || !(noise_target >= 0.0) || !std::isfinite(noise_target))
                 die("error: invalid value '" + v + "' for '--noise-target <T>': a positive, finite number expected");
+            noise_target_text = v;
             have_noise_target = true;
         } else if (a == "--min-samples" || a.rfind("--min-samples=", 0) == 0) {
             min_samples = parse_u32(value("--min-samples <N0>"), "--min-samples <N0>");
@@ -263,6 +276,10 @@ int run_render(int argc, char** argv) {
             if (film_denoise != "plain" && film_denoise != "variance")
                 die("error: invalid value '" + film_denoise + "' for '--film-denoise <plain|variance>': plain or variance expected");
         } else if (a == "--filtered-target") filtered_target = true;
+        else if (a == "--window-samples" || a.rfind("--window-samples=", 0) == 0) {
+            window_samples = parse_u32(value("--window-samples <W>"), "--window-samples <W>");
+            have_window_samples = true;
+        }
         else if (a == "--adaptive-tile" || a.rfind("--adaptive-tile=", 0) == 0) {
             adaptive_tile = parse_u32(value("--adaptive-tile <N>"), "--adaptive-tile <N>");
             have_adaptive_tile = true;
@@ -323,6 +340,16 @@ int run_render(int argc, char** argv) {
             "are not gathered)");
     if (!have_noise_target && (have_min_samples || have_max_samples || !noise_map.empty()))
         die("error: '--min-samples <N0>', '--max-samples <N>' and '--noise-map <FILE.png>' need '--noise-target <T>'");
+    if (have_noise_target && !have_window_samples && !(noise_target > 0.0 && (float)noise_target > 0.f))
+        die("error: invalid value '" + noise_target_text + "' for '--noise-target <T>': a positive, finite number expected");
+    if (have_window_samples && !have_noise_target) die("error: '--window-samples <W>' needs '--noise-target <T>'");
+    if (have_window_samples && window_samples < 2)
+        die("error: invalid value '" + std::to_string(window_samples) + "' for '--window-samples <W>': at least 2 (a sample variance needs two samples)");
+    if (have_window_samples && have_min_samples)
+        die("error: the argument '--window-samples <W>' cannot be used with '--min-samples <N0>' (the first window has W samples)");
+    if (have_window_samples && filtered_target)
+        die("error: the argument '--window-samples <W>' cannot be used with '--filtered-target' (the filtered selection is not built "
+            "for windows)");
     if (adaptive && !have_noise_target) die("error: '--adaptive' needs '--noise-target <T>'");
     if (!adaptive && (have_adaptive_tile || have_uniform_samples || have_adaptive_dilate || !sample_map.empty()))
         die("error: '--adaptive-tile <N>', '--uniform-samples <U>', '--adaptive-dilate <0|1>' and '--sample-map <FILE.png>' need "
@@ -366,6 +393,12 @@ int run_render(int argc, char** argv) {
     if (pth_profile_load(have_profile ? profile_path.c_str() : nullptr, &profile) != PT_OK) die(pth_last_error());
     if (have_noise_target) {
         if (!have_max_samples) max_samples = profile.samples;
+        if (have_window_samples) {
+            if (max_samples < 2)
+                die("error: '--window-samples <W>' needs an enumeration of at least 2 samples ('--max-samples <N>' or the profile's samples: " +
+                    std::to_string(max_samples) + ")");
+            min_samples = 2;   // (not a parameter of the windowed loop; keeps the checks below quiet)
+        }
         if (min_samples < 2)
             die("error: invalid value '" + std::to_string(min_samples) + "' for '--min-samples <N0>': at least 2 (a sample variance needs two samples)");
         if (min_samples > max_samples)
@@ -634,7 +667,11 @@ int run_render(int argc, char** argv) {
     pt_film* film = nullptr;
     pt_opts film_opts = opts;
     if (adaptive) film_opts.tile_w = film_opts.tile_h = adaptive_tile;   // (the film's tiling is what its passes select by)
-    if (have_noise_target && pt_film_create(device, &profile, &film_opts, &film) != PT_OK) die(pt_last_error());
+    pt_profile film_profile = profile;
+    if (have_window_samples) film_profile.samples = max_samples;   // the enumeration
+    if (have_noise_target && (have_window_samples ? pt_film_create_windowed(device, &film_profile, &film_opts, &film)
+                                                  : pt_film_create(device, &profile, &film_opts, &film)) != PT_OK)
+        die(pt_last_error());
     const size_t n_pixels = (size_t)profile.width * profile.height;
     // one frame's map, grey: the frame index goes in front of the extension when there are several
     auto write_map = [&](const std::string& map, size_t f, const std::vector<uint8_t>& grey) {
@@ -651,7 +688,19 @@ int run_render(int argc, char** argv) {
         if (f > 0 && pt_film_reset(film) != PT_OK) die(pt_last_error());
         pt_film_noise_stats noise{};
         pt_film_tile_stats tiles{};
-        if (adaptive) {
+        if (have_window_samples) {
+            pt_film_window_params wp;
+            pt_film_window_params_default(&wp);
+            wp.target = noise_target;
+            wp.window_samples = window_samples;
+            wp.adaptive = adaptive ? 1u : 0u;
+            if (have_uniform_samples) wp.uniform_samples = uniform_samples;
+            if (have_adaptive_dilate) wp.dilate = adaptive_dilate;
+            AdaptivePassCtx ctx{viewer, film};
+            if (pt_film_render_until_windowed(film, scene, &wp, on_adaptive_pass, &ctx, &tiles) != PT_OK) die(pt_last_error());
+            noise.mean_error = tiles.mean_error;
+            noise.converged = tiles.converged;
+        } else if (adaptive) {
             pt_film_adaptive_params ap;
             pt_film_adaptive_params_default(&ap);
             ap.target = noise_target;
@@ -694,7 +743,7 @@ int run_render(int argc, char** argv) {
         if (!noise_map.empty()) {   // grey = as_u8(min(1, err / (2 T)) * 255)
             std::vector<float> err(n_pixels);
             if ((filtered_target ? pt_film_filtered_noise(film, scene, &dn, PT_FILM_DEFAULT_LUM_FLOOR, noise_target, &tiles, err.data(), nullptr, nullptr)
-                 : adaptive      ? pt_film_tile_noise(film, PT_FILM_DEFAULT_LUM_FLOOR, noise_target, &tiles, err.data(), nullptr, nullptr)
+                 : adaptive || have_window_samples ? pt_film_tile_noise(film, PT_FILM_DEFAULT_LUM_FLOOR, noise_target, &tiles, err.data(), nullptr, nullptr)
                                  : pt_film_noise(film, PT_FILM_DEFAULT_LUM_FLOOR, noise_target, &noise, err.data(), nullptr, nullptr)) != PT_OK)
                 die(pt_last_error());
             std::vector<uint8_t> grey(n_pixels * 3);
@@ -710,7 +759,7 @@ int run_render(int argc, char** argv) {
                 grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = to_grey((float)counts[i] / (float)info.samples * 255.0f);
             write_map(sample_map, f, grey);
         }
-        if (adaptive)
+        if (adaptive || have_window_samples)
             fprintf(stderr, "film: %u passes, %llu samples, %s %.6g, %s, pixel-samples %llu of %llu\n", info.passes,
                     (unsigned long long)info.samples, filtered_target ? "filtered noise" : "noise", noise.mean_error,
                     noise.converged ? "converged" : "max samples",

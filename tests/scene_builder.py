@@ -96,12 +96,66 @@ def _unit(v):
     return v / np.linalg.norm(v)
 
 
+def _panel():
+    """The same triangle wound both ways side by side - one of the two is seen from its back; normals of length 0.5, 4 and 1."""
+    a, b, c = np.array([-1.9, 0.1, 0.2]), np.array([-1.2, 0.15, -0.9]), np.array([-1.6, 1.4, -0.3])
+    npn = [0.5 * _unit([1, 0.1, 0.6]), 4.0 * _unit([1, -0.1, 0.5]), _unit([0.9, 0.2, 0.7])]
+    tp = [np.array([0.11, 0.07]), np.array([2.3, -0.4]), np.array([0.9, 1.8])]
+    sh = np.array([0.0, 0.0, 1.25])
+    return [np.concatenate([np.concatenate([p, n, t]) for p, n, t in zip((a, b, c), npn, tp)]),
+            np.concatenate([np.concatenate([p + sh, n, t]) for p, n, t in zip((a, c, b), (npn[0], npn[2], npn[1]),
+                                                                            (tp[0], tp[2], tp[1]))])]
+
+
+def _terrace():
+    """The groups of `terrace`: what the escape masks (csrc/pt_escape.h) can answer, next to what they cannot.
+      floor  the ground y = 0 over [-2, 2] x [-2, 1.6] as 8 x 8 quads: small triangles, so that the origin set of most of them
+             is clear of everything that rises above the plane; vertex normals of length 1, tilted by up to 2 degrees (the
+             shaded origin sits 1e-5 x normal above the surface: inside [PT_ESC_H_LO, PT_ESC_H_HI])
+      box    a convex box floating 0.9 above the ground, normals outward and exactly axial: a flat top whose neighbours fall away
+      wall   a slab of 0.5 x 0.5 floating at y = 1.5 - high enough that neither the ground nor the box nor the ball counts as
+             "near and below" (r_near = 2 x the origin set's radius), so nearly its whole upper hemisphere is clear - with vertex
+             normals of length 1, 1, 4 and 0.5: where the interpolated normal is longer than the light grids' margin its paths
+             go through the shadow queue under a live light, and are ended by the masks under none
+      panel  the panel of `open`: vertex normals of length 0.5 and 4, standing on the ground - the ground triangles next to it
+             are left unexamined, as are those under the ball (a sphere has no mask)"""
+    g = {"floor": [], "box": []}
+    nx, nz, dx, dz = 8, 8, 0.5, 0.45
+    normal = lambda x, z: _unit([0.035 * np.sin(1.7 * x + 0.3), 1.0, 0.035 * np.cos(2.1 * z)])
+    for i in range(nx):
+        for j in range(nz):
+            x, z = -2.0 + i * dx, 1.6 - j * dz
+            n = [normal(x, z), normal(x + dx, z), normal(x + dx, z - dz), normal(x, z - dz)]
+            uv0 = (-2.5 + 1.3 * (x + 2.0) + 0.23 * (1.6 - z), -2.5 + 0.2 * (x + 2.0) + 1.45 * (1.6 - z))
+            g["floor"] += _quad((x, 0.0, z), (dx, 0, 0), (0, 0, -dz), n, uv0, (1.3 * dx, 0.2 * dx), (0.23 * dz, 1.45 * dz))
+    lo, hi = np.array([-1.1, 0.9, -0.1]), np.array([-0.6, 1.3, 0.4])
+    s = hi - lo
+    for axis in range(3):
+        a, b = (axis + 1) % 3, (axis + 2) % 3
+        for side in (0, 1):
+            p0 = lo.copy()
+            e1, e2, n = np.zeros(3), np.zeros(3), np.zeros(3)
+            e1[a], e2[b] = s[a], s[b]
+            if side:
+                p0[axis] = hi[axis]
+            else:
+                e1, e2 = e2, e1
+            n[axis] = 1.0 if side else -1.0
+            g["box"] += _quad(p0, e1, e2, [n] * 4, (0.03, 0.02), (0.9, 0.0), (0.0, 0.9))
+    ns = [_unit([0.03, 1, 0.02]), _unit([-0.05, 1, 0.0]), 4.0 * _unit([0.0, 1, -0.04]), 0.5 * _unit([0.04, 1, 0.04])]
+    g["wall"] = _quad((0.5, 1.5, 1.0), (0.5, 0, 0), (0, 0, -0.5), ns, (1.7, 0.13), (-2.3, 0.21), (0.17, 1.9))
+    g["panel"] = _panel()
+    return g
+
+
 GEOMETRIES = ("full", "open", "boxed", "spheres", "room")   # room: the closed box and the ball
+# not part of the matrix (cases()): the geometry whose escape masks prove misses (tests/test_masked_sequences.py)
+MASKED_GEOMETRIES = ("terrace",)
 
 
 def make_geometry(pta, geometry):
     """(triangles [n, 24], models): model k uses material k of MATERIALS (spheres-only: the ball alone, material 4)."""
-    groups = {}
+    groups = _terrace() if geometry == "terrace" else {}
     if geometry in ("full", "boxed", "room"):   # a closed box around it all, normals inward
         lo, hi = np.array([-3.1, -0.4, -3.3]), np.array([3.2, 4.3, 3.4])
         s = hi - lo
@@ -118,21 +172,14 @@ def make_geometry(pta, geometry):
                 n[axis] = -1.0 if side else 1.0
                 q += _quad(p0, e1, e2, [n] * 4, (0.03, 0.02), (0.9, 0.0), (0.0, 0.9))
         groups["box"] = q
-    if geometry not in ("spheres", "room"):
+    if geometry not in ("spheres", "room", "terrace"):
         # floor: vertex normals of length 0.5 and 4, not parallel; UVs scaled and rotated over [-2.5, 3.5]
         nf = [0.5 * _unit([0.05, 1, 0.02]), 4.0 * _unit([-0.04, 1, 0.03]), 0.5 * _unit([0.02, 1, -0.06]), 4.0 * _unit([0, 1, 0.05])]
         groups["floor"] = _quad((-2.0, 0.0, 1.5), (4.0, 0, 0), (0, 0, -3.5), nf, (-2.5, -2.5), (5.2, 0.8), (0.8, 5.2))
         # back wall: mirrored UVs (negative UV determinant)
         nw = [_unit([0.03, 0.02, 1]), _unit([-0.05, 0.0, 1]), 4.0 * _unit([0.0, -0.04, 1]), 0.5 * _unit([0.04, 0.04, 1])]
         groups["wall"] = _quad((-2.0, 0.0, -2.0), (4.0, 0, 0), (0, 2.5, 0), nw, (1.7, 0.13), (-2.3, 0.21), (0.17, 1.9))
-        # panel: the same triangle wound both ways side by side - one of the two is seen from its back
-        a, b, c = np.array([-1.9, 0.1, 0.2]), np.array([-1.2, 0.15, -0.9]), np.array([-1.6, 1.4, -0.3])
-        npn = [0.5 * _unit([1, 0.1, 0.6]), 4.0 * _unit([1, -0.1, 0.5]), _unit([0.9, 0.2, 0.7])]
-        tp = [np.array([0.11, 0.07]), np.array([2.3, -0.4]), np.array([0.9, 1.8])]
-        sh = np.array([0.0, 0.0, 1.25])
-        groups["panel"] = [np.concatenate([np.concatenate([p, n, t]) for p, n, t in zip((a, b, c), npn, tp)]),
-                           np.concatenate([np.concatenate([p + sh, n, t]) for p, n, t in zip((a, c, b), (npn[0], npn[2], npn[1]),
-                                                                                           (tp[0], tp[2], tp[1]))])]
+        groups["panel"] = _panel()
     if geometry == "full":   # a translucent sheet between the lights and the rest
         ns = [_unit([0, -1, 0])] * 4
         groups["sheet"] = _quad((-2.5, 2.2, 2.0), (5.0, 0, 0), (0, 0, -4.5), ns, (0.02, 0.04), (1.3, 0.0), (0.0, 1.1))

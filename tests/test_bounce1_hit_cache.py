@@ -12,10 +12,12 @@ lost on the way, a frame on another stream reading before the plane was zeroed. 
 - f32 accumulator and rgb8 - with the CPU oracle or with a PT_HIT1_CACHE=0 render of the same sequence, and every test
 reads the cache's own numbers (GpuScene.hit1_cache_stats): without them it would prove nothing.
 
-An item without a record is made by the study switch PT_HIT1_CACHE_HOLES.  The natural case - a path the escape masks ended
-at bounce 0 while the plane was filled, alive under another light - cannot be built from the builder's scenes: the masks of
-`open`, the one geometry with normals long enough for the shadow queue and a background that is not black, prove no miss
-at all (masked_casts is 0 in its instrumented frames under every light set), and nothing leaves the closed ones."""
+An item without a record is made here by the study switch PT_HIT1_CACHE_HOLES.  The natural case - a path the escape masks
+ended at bounce 0 while the plane was filled, alive under another light - cannot be built from the geometries of the shading
+matrix: the masks of `open`, the one of them with normals long enough for the shadow queue and a background that is not
+black, prove no miss at all (masked_casts is 0 in its instrumented frames under every light set), and nothing leaves the
+closed ones.  It is built in tests/test_masked_sequences.py, on the builder's `terrace` geometry (kept out of the matrix),
+whose masks do end paths: test_a_light_edit_revives_paths_the_masks_ended_while_the_planes_were_filled, no switch set."""
 import numpy as np
 import pytest
 

@@ -13,8 +13,9 @@ taking the other's records along.  Every frame here is compared bit for bit - f3
 oracle or with a render of the same sequence with the cache switched off, and every test reads both caches' numbers
 (GpuScene.hit1_cache_stats, hit2_cache_stats).
 
-An item without a record is made by the study switch PT_HIT2_CACHE_HOLES: the natural case cannot be built from the
-builder's scenes, for the reason given in tests/test_bounce1_hit_cache.py (the escape masks of `open` prove no miss)."""
+An item without a record is made here by the study switch PT_HIT2_CACHE_HOLES: the escape masks of `open` prove no miss (the
+reason given in tests/test_bounce1_hit_cache.py).  The natural case - a plane filled while the masks ended paths, read under
+lights that keep them alive - is tests/test_masked_sequences.py, on the builder's `terrace` geometry, without the switch."""
 import numpy as np
 import pytest
 

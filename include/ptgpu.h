@@ -987,12 +987,24 @@ int pt_get_hit1_fused_stats(const pt_scene* scene, uint64_t* launches, uint64_t*
  * loading launch found without a record (missing: never, by construction - a check), since the scene was made.  The frame
  * that stores the bounce-1 hits stores it, from the bounce-0 kernel that frame runs anyway; only frames that use the
  * bounce-1 hit cache use it; pt_scene_set_materials and pt_scene_set_camera re-key it (the allocation stays), light edits
- * keep it.  PT_CONT_CACHE=0 switches the cache off, PT_CONT_CACHE_GIB (8) is its budget; PT_CONT_ESCAPE=1 (default 0) lets the
+ * keep it.  PT_CONT_CACHE=0 switches the cache off, PT_CONT_CACHE_GIB (8) is its budget; PT_CONT_ESCAPE (default 1) lets the
  * loading launches take the escape-mask test's answer from the record too, where the scene's masks are those the records were
- * stored under; all three are read per frame.  The call
+ * stored under or refilled for (pt_get_cont_escape_stats); all three are read per frame.  The call
  * waits for the device.  The bytes are not part of pt_scene_info's queue_bytes or device_bytes. */
 int pt_get_cont_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* resets,
                             uint64_t* stores, uint64_t* loads, uint64_t* missing);
+/* The escape answers in those records (PT_CONT_ESCAPE).  Records stored before the scene's escape masks existed - a fresh view
+ * stores in its second frame, the masks are built before the third - get their answers from a launch of their own, chunk by
+ * chunk in the first frame that finds masks the records were not stored under: fill_launches and fill_items count those
+ * launches and the items they went over; flagged_launches the loading launches that were told the records have answers;
+ * fallback_lanes the lanes of such launches that ran the escape test themselves all the same (0 once the records are
+ * refilled), since the scene was made.  The call waits for the device. */
+int pt_get_cont_escape_stats(const pt_scene* scene, uint64_t* fill_launches, uint64_t* fill_items, uint64_t* flagged_launches,
+                             uint64_t* fallback_lanes);
+/* The state words of the first `count` cached continuation records (at most pt_get_cont_cache_stats' items_cached), one
+ * uint32 each: bit 0 - the record was written, bit 1 - it carries the escape test's answer, bit 2 - that answer.  A check
+ * for tests.  The call waits for the device. */
+int pt_scene_cont_states_copy(const pt_scene* scene, uint32_t* out, uint64_t count);
 /* The scene's cache of bounce-2 hits: the bounce-1 hit cache one bounce later - the bounce-2 ray is made from the bounce-1
  * hit, the material there and the item's random words, so it has the same key (view and material table, no light, no
  * bounce count) and the same rules, values and meaning of every field.  Only frames that use the bounce-1 hit cache and

@@ -332,7 +332,7 @@ HOST_SYMBOLS = ["pth_scene_load_isf", "pth_scene_free", "pth_scene_desc", "pth_s
 GPU_SYMBOLS = ["pt_scene_create", "pt_scene_destroy", "pt_scene_set_camera", "pt_scene_set_lights", "pt_scene_set_materials", "pt_prep_create", "pt_prep_destroy", "pt_scene_create_from_prep",
                "pt_comm_unique_id", "pt_comm_create", "pt_comm_create_all", "pt_comm_destroy", "pt_gather_tiles", "pt_render_gathered", "pt_local_pixel_count", "pt_local_pixel_map",
                "pt_render", "pt_render_device", "pt_debug_render", "pt_assemble_tiles", "pt_get_timing", "pt_get_counters",
-               "pt_scene_get_info", "pt_get_cull_stats", "pt_get_rng_cache_stats", "pt_get_hit_cache_stats", "pt_get_vis_cache_stats", "pt_get_hit1_cache_stats", "pt_get_hit1_fused_stats", "pt_get_cont_cache_stats", "pt_get_hit2_cache_stats", "pt_get_vis1_cache_stats", "pt_get_bounce1_fused_stats", "pt_get_bounce_hits_cache_stats", "pt_get_bounce_vis_cache_stats", "pt_get_bounce_fused_stats", "pt_kernel_occupancy", "pt_scene_escape_copy", "pt_escape_query", "pt_scene_grid_header", "pt_scene_grid_copy", "pt_trace_rays", "pt_trace_rays_wavefront",
+               "pt_scene_get_info", "pt_get_cull_stats", "pt_get_rng_cache_stats", "pt_get_hit_cache_stats", "pt_get_vis_cache_stats", "pt_get_hit1_cache_stats", "pt_get_hit1_fused_stats", "pt_get_cont_cache_stats", "pt_get_cont_escape_stats", "pt_scene_cont_states_copy", "pt_get_hit2_cache_stats", "pt_get_vis1_cache_stats", "pt_get_bounce1_fused_stats", "pt_get_bounce_hits_cache_stats", "pt_get_bounce_vis_cache_stats", "pt_get_bounce_fused_stats", "pt_kernel_occupancy", "pt_scene_escape_copy", "pt_escape_query", "pt_scene_grid_header", "pt_scene_grid_copy", "pt_trace_rays", "pt_trace_rays_wavefront",
                "pt_trace_rays_all", "pt_intersect_triangles",
                "pt_rng_words", "pt_eval_math", "pt_measure_copy_bandwidth", "pt_measure_gather_rate", "pt_last_error",
                "pt_version", "pt_render_guides", "pt_render_guides_device", "pt_denoise_params_default", "pt_denoise_scratch_bytes",
@@ -465,6 +465,9 @@ def gpu_lib():
             L.pt_get_hit1_fused_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 4
         if hasattr(L, "pt_get_cont_cache_stats"):
             L.pt_get_cont_cache_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 7
+        if hasattr(L, "pt_get_cont_escape_stats"):
+            L.pt_get_cont_escape_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 4
+            L.pt_scene_cont_states_copy.argtypes = [vp, vp, C.c_uint64]
         if hasattr(L, "pt_get_hit2_cache_stats"):
             L.pt_get_hit2_cache_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 7
         if hasattr(L, "pt_get_vis1_cache_stats"):
@@ -1175,6 +1178,21 @@ class GpuScene:
         loading launches, hit lanes of loading launches that found no record - always 0).  PT_CONT_CACHE=0 switches it off,
         PT_CONT_CACHE_GIB (default 8) is its budget.  Waits for the device."""
         return self._cache_stats(self.lib.pt_get_cont_cache_stats, 7)
+
+    def cont_escape_stats(self):
+        """The escape answers in the continuation records (PT_CONT_ESCAPE): (launches that refilled records stored before the
+        scene's masks existed, items they went over, loading launches told that the records have answers, lanes of such
+        launches that ran the escape test themselves - 0 once the records are refilled).  Waits for the device."""
+        return self._cache_stats(self.lib.pt_get_cont_escape_stats, 4)
+
+    def cont_states(self, count=None):
+        """The state words of the first `count` cached continuation records (default: all of them) as a uint32 array: bit 0
+        written, bit 1 the record carries the escape test's answer, bit 2 that answer.  Waits for the device."""
+        import numpy as np
+        n = int(self.cont_cache_stats()[2]) if count is None else int(count)
+        out = np.zeros(n, dtype=np.uint32)
+        check_gpu(self.lib.pt_scene_cont_states_copy(self.handle, out.ctypes.data_as(C.c_void_p), C.c_uint64(n)))
+        return out
 
     def hit2_cache_stats(self):
         """The scene's cache of bounce-2 hits: the fields of hit1_cache_stats.  Waits for the device."""

@@ -727,6 +727,13 @@ struct pt_scene {
     // or rebuilt; cont_escape_generation is the one the records were stored under - 0: none, or stored under more than one)
     FrameCache cont_cache;
     uint64_t escape_generation = 1, cont_escape_generation = 0;
+    // (records stored before the masks existed get their answers from k_cont_escape_fill, chunk by chunk in the first frame
+    // that finds masks the prefix was not stored under - render_chunk: [0, cont_fill_mark) has those of cont_fill_generation,
+    // and once that covers the prefix cont_escape_generation is the masks'.  cont_fill_launches / _items: those launches and
+    // the items they went over; cont_flagged_launches: loading launches told that the records have answers; the lanes of
+    // such launches that ran the test all the same are word 7 of hit1_unknown.  pt_get_cont_escape_stats)
+    uint64_t cont_fill_generation = 0, cont_fill_mark = 0;
+    uint64_t cont_fill_launches = 0, cont_fill_items = 0, cont_flagged_launches = 0;
     // The closest hits of the bounce-2 rays, same key: that ray is made from the bounce-1 hit, the material there and the
     // item's words - again no light, and the Russian roulette starts behind it - so what holds for bounce 1 holds one bounce
     // later.  In use in the frames hit1_cache serves that have a bounce 2; the record, the zeroing, the prefix, the counters
@@ -2725,7 +2732,7 @@ constexpr FrameCacheKind VIS_CACHE = {"PT_VIS_CACHE", "PT_VIS_CACHE_GIB", 1.0, 1
 // and, there being no device sync, every launch that reads the plane records the event too, not only those that write)
 constexpr FrameCacheKind HIT1_CACHE = {"PT_HIT1_CACHE", "PT_HIT1_CACHE_GIB", 8.0, 16u, ~0ull, true};
 #ifndef PT_CONT_ESCAPE_DEFAULT
-#define PT_CONT_ESCAPE_DEFAULT false   // (measured against the cache alone: profiles/r19_experiments.txt item 8)
+#define PT_CONT_ESCAPE_DEFAULT true   // (with the records refilled when the masks arrive: profiles/r20_experiments.txt item 2)
 #endif
 constexpr FrameCacheKind CONT_CACHE = {"PT_CONT_CACHE", "PT_CONT_CACHE_GIB", 8.0, 32u, ~0ull, true};   // (two planes of 16 B)
 constexpr FrameCacheKind HIT2_CACHE = {"PT_HIT2_CACHE", "PT_HIT2_CACHE_GIB", 8.0, 16u, ~0ull, true};
@@ -3413,7 +3420,35 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
         c.cont_plane = (uint4*)wf.cont_cache->buf.p + g0;
         c.cont_stride = (size_t)wf.cont_cache->stride;
     }
-    if (c.cont_mode == 2048 && wf.cont_escape && f.dev.escape && s.cont_escape_generation == s.escape_generation) c.cont_flags = 1u;
+    // The records' escape answers.  Masks the prefix was not stored under (built or rebuilt since): the part of this chunk below
+    // the marks of the camera hits and the continuations is refilled here, in front of the launch that loads it -
+    // k_cont_escape_fill, once per record and mask generation; chunks come in frame order, so the refilled part is a prefix too.
+    // Masks dropped: nothing to do - no flag without masks.  A translucent scene keys no continuation cache: no launch.
+    if (wf.cont_cache && wf.hit_cache && c.cached && wf.cont_escape && f.dev.escape && s.cont_escape_generation != s.escape_generation) {
+        if (s.cont_fill_generation != s.escape_generation) {
+            s.cont_fill_generation = s.escape_generation;
+            s.cont_fill_mark = 0;
+        }
+        const uint64_t below = std::min({g1, wf.cont_cache->mark, wf.hit_cache->mark});
+        if (g0 <= s.cont_fill_mark && below > s.cont_fill_mark) {
+            const uint32_t n = (uint32_t)(below - g0);
+            // (no stage of the timeline: it comes once per record and mask build, like the build itself)
+            hipLaunchKernelGGL(k_cont_escape_fill, dim3(std::max(1u, std::min((uint32_t)s.n_cu * 8u, (n + 255u) / 256u))), dim3(256), 0, c.st_main,
+                               f.dev, W, f.d_tiles, (const uint4*)c.rng_planes, (const uint4*)((uint4*)wf.hit_cache->buf.p + g0),
+                               (uint4*)wf.cont_cache->buf.p + g0, (size_t)wf.cont_cache->stride, n);
+            HIP_CHECK(hipGetLastError());
+            wf.cont_cache->touched(c.st_main);
+            s.cont_fill_mark = below;
+            ++s.cont_fill_launches;
+            s.cont_fill_items += n;
+        }
+        if (s.cont_fill_mark >= wf.cont_cache->mark) s.cont_escape_generation = s.escape_generation;
+    }
+    if (c.cont_mode == 2048 && wf.cont_escape && f.dev.escape &&
+        (s.cont_escape_generation == s.escape_generation || (s.cont_fill_generation == s.escape_generation && g1 <= s.cont_fill_mark))) {
+        c.cont_flags = 1u;
+        ++s.cont_flagged_launches;
+    }
     // the shadow visibility of bounces 1-4: indexed by the sample's slot in its batch's staging area, which any chunk of the
     // batch may hold - so the whole batch lies below the plane's stride, not the chunk alone
     for (uint32_t b = 1; b < WfFrame::HIT_BOUNCES; ++b) {
@@ -6243,6 +6278,33 @@ int pt_get_cont_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* it
         if (cache_stats({{bytes, fc.buf.bytes}, {items, fc.items}, {items_cached, fc.mark}, {resets, fc.counter[0]}, {stores, fc.counter[1]},
                          {loads, fc.counter[2]}, {missing, n[6]}}) != PT_OK)
             fail(PT_ERR_INVALID, "pt_get_cont_cache_stats: null argument");
+    });
+}
+int pt_get_cont_escape_stats(const pt_scene* scene, uint64_t* fill_launches, uint64_t* fill_items, uint64_t* flagged_launches,
+                             uint64_t* fallback_lanes) {
+    if (!scene) return PT_ERR_INVALID;
+    return guarded([&] {
+        uint64_t n[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // (pt_scene::hit1_unknown: word 7)
+        if (scene->hit1_unknown.p) {                // (synchronises, like pt_get_hit1_cache_stats)
+            HIP_CHECK(hipSetDevice(scene->device));
+            HIP_CHECK(hipDeviceSynchronize());
+            HIP_CHECK(hipMemcpy(n, scene->hit1_unknown.p, sizeof n, hipMemcpyDeviceToHost));
+        }
+        if (cache_stats({{fill_launches, scene->cont_fill_launches}, {fill_items, scene->cont_fill_items},
+                         {flagged_launches, scene->cont_flagged_launches}, {fallback_lanes, n[7]}}) != PT_OK)
+            fail(PT_ERR_INVALID, "pt_get_cont_escape_stats: null argument");
+    });
+}
+int pt_scene_cont_states_copy(const pt_scene* scene, uint32_t* out, uint64_t count) {
+    if (!scene || (!out && count)) return PT_ERR_INVALID;
+    return guarded([&] {
+        const pt_scene::FrameCache& fc = scene->cont_cache;
+        if (count > fc.mark) fail(PT_ERR_INVALID, "pt_scene_cont_states_copy: more records than the cache holds");
+        if (!count) return;
+        HIP_CHECK(hipSetDevice(scene->device));
+        HIP_CHECK(hipDeviceSynchronize());
+        // (word 3 of every record of plane 0)
+        HIP_CHECK(hipMemcpy2D(out, 4, (const uint32_t*)fc.buf.p + 3, 16, 4, (size_t)count, hipMemcpyDeviceToHost));
     });
 }
 int pt_get_hit2_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* items, uint64_t* items_cached, uint64_t* resets,

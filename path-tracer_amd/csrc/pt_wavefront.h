@@ -2287,6 +2287,41 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_
 #include "pt_wf_shade_body.h"
 }
 
+// The escape answers of records that were stored before the scene's masks existed (a fresh view stores its records in its
+// second frame, the masks are built before the third): items [0, n) of a chunk, all below the marks of the camera-hit and the
+// continuation planes.  For every record that was written (bit 0 of its state word) the lane rebuilds what the storing launch
+// had in registers when it asked - o and d from the cached words and the camera, the camera hit, make_surface, next_o; next_d
+// and next_thr are the record's own bits - and applies that launch's condition with the same operands and functions: the
+// state word it writes (one 4-byte store) is the one a launch storing under these masks would have written.  A record the
+// condition leaves out keeps its word: its bits 1 and 2 are clear whatever masks it was stored under.
+__global__ __launch_bounds__(256) void k_cont_escape_fill(DevScene S, WfParams W, const uint32_t* __restrict__ tile_offsets,
+                                                          const uint4* __restrict__ rng_planes, const uint4* __restrict__ hit_plane,
+                                                          uint4* __restrict__ cont_plane, size_t cont_stride, uint32_t n) {
+    if (S.escape == nullptr) return;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        const uint4 cont_d = cont_plane[i];
+        if ((cont_d.w & 1u) == 0u) continue;
+        const ItemRef it = decode_item(W.P, tile_offsets, W.item_base + i);
+        if (!it.valid) continue;
+        RawHit h;
+        if (!unpack_hit(hit_plane[i], h)) continue;
+        const uint4 cont_thr = cont_plane[cont_stride + i];
+        const f3 next_thr = mk3(__uint_as_float(cont_thr.x), __uint_as_float(cont_thr.y), __uint_as_float(cont_thr.z));
+        if (dot3(next_thr, next_thr) < 0.00001f) continue;
+        const uint4 w03 = rng_planes[i];
+        float sx, sy;
+        f3 o, d;
+        primary_screen(S, it.x, it.y, W.P.width, W.P.height, wf_rng_float(w03.x), wf_rng_float(w03.y), sx, sy);
+        primary_from_screen(S, sx, sy, o, d);
+        Surface surf;
+        make_surface(S, o, d, h, surf);
+        if (surf.sphere) continue;
+        const f3 next_o = surf.pos + surf.normal * 0.00001f;
+        const f3 next_d = mk3(__uint_as_float(cont_d.x), __uint_as_float(cont_d.y), __uint_as_float(cont_d.z));
+        ((uint32_t*)(cont_plane + i))[3] = 1u | 2u | (escape_proves_miss(S, PT_PRIM_INDEX(h.pid), next_o, next_d) ? 4u : 0u);
+    }
+}
+
 // The bounce-1 shade pass of an opaque, uninstrumented frame that reads the scene's bounce-1 shadow-visibility cache itself
 // (pt_gpu.hip FrameCache vis1_cache; GRIDX = 256, VIS1), and the bounce-2 hit cache as well (hit2_cache; GRIDX = 256 + 512,
 // NEXT1): k_wf_shade<false, false, false, 0> with three parameters more, for a chunk whose sample batch lies below the

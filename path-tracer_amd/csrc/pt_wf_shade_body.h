@@ -447,6 +447,12 @@
                     proven = known && (cont_d.w & 4u) != 0u;
                     if (wf_any(!known)) {
                         if (!known) proven = escape_proves_miss(S, PT_PRIM_INDEX(h.pid), next_o, next_d);
+                        // the lanes that ran the test although the launch was told the records have answers: counted
+                        // (next_ctr[7]; none once k_cont_escape_fill has been over the records)
+                        if ((cont_flags & 1u) != 0u) {
+                            const unsigned long long m = __ballot(!known);
+                            if (!known && wf_lane_rank(m) == 0u) atomicAdd(next_ctr + 7, (unsigned long long)__popcll(m));
+                        }
                     }
                 }
             }

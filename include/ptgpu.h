@@ -873,6 +873,87 @@ int  pt_film_render_until_windowed(pt_film* film, const pt_scene* scene, const p
 int  pt_film_window_kernel_times(pt_film* film, uint32_t reps, float* ms_gather, float* ms_scatter);
 
 /* ------------------------------------------------------------------ */
+/* sharded films                                           */
+/* ------------------------------------------------------------------ */
+
+/* A SHARD FILM is one rank's part of an adaptive or windowed film that opts->shard_count ranks hold together.  A film's tiling
+ * is its opts' tile size, which is the sharding's tile size too, so every tile of the film belongs whole to one rank - rank
+ * (tx + ty * s) % shard_count, the rule of pt_opts.  pt_film_create_shard makes the part of rank opts->shard_rank; windowed = 1:
+ * a windowed film of N = profile.samples (pt_film_create_windowed), 0: a film of doubling passes (pt_film_create); it refuses
+ * what they refuse.  The planes are in the packed local order of pt_local_pixel_map (profile, opts): the rank's tiles in
+ * ascending tile number, each row-major and clipped.  shard_count <= 1 is allowed: one rank holds every tile, in image order,
+ * and everything below is its N = 1 case.  pt_film_get_shard_info works on every film.
+ *
+ * TILE LISTS ARE GLOBAL on a shard film: the rules of pt_render_tiles, tile numbers of the image, any rank's tiles.  The rank
+ * renders and merges the listed tiles it holds and skips the others; host planes (pt_film_add_tile_planes) hold the rank's
+ * listed tiles only, packed in list order.  A list with none of the rank's tiles still counts as the pass: passes,
+ * last_pass_samples, tile_passes / tile_windows advance, and nothing is rendered or merged.  The film keeps the sample count of
+ * EVERY tile of the image, updated from the lists, so info.samples, adaptive_info.min_samples / max_samples / pixel_samples /
+ * n_tiles / tiles_x / tiles_y / last_pass_tiles are the whole film's on every rank; info.n_local and the planes are the rank's.
+ *   work            pt_film_add_pass, pt_film_add_window (whole frames: the sharded frame of pt_render, the film stays uniform),
+ *                   pt_film_add_tile_pass, pt_film_add_tile_planes, pt_film_add_tile_window (the rank's listed tiles, grouped by
+ *                   count), pt_film_add_planes, pt_film_read, pt_film_read_counts, pt_film_resolve[_device], pt_film_reset, the
+ *                   info calls, pt_film_adaptive_kernel_times and pt_film_window_kernel_times (the packed kernels over the rank's
+ *                   tiles).  A tile pass renders the rank's listed tiles as an UNSHARDED tile-list frame: its buffers come in
+ *                   list order, which is the film's own order for those tiles.
+ *   PT_ERR_INVALID  and nothing changes - their figures are defined over one device's planes: pt_film_tile_noise,
+ *                   pt_film_render_until, _adaptive, _windowed and _filtered, pt_film_denoise[_device],
+ *                   pt_film_denoise_kernel_times, pt_film_tile_reduce_device, pt_film_filtered_noise
+ *                   (pt_film_denoise_scratch_bytes: 0).
+ * The calls below marked (shard) are PT_ERR_INVALID on a film that is not a shard film.  Films of pt_film_create[_windowed] with
+ * shard_count > 1 are what they were: whole passes only.
+ *
+ * pt_film_shard_tile_noise (shard): pt_film_tile_noise's per-pixel and per-tile steps on the rank's tiles - a tile's sum and
+ * maximum are made from that tile's pixels only, addition for addition the steps of pt_film_tile_noise, so they do not depend on
+ * who holds the tile.  tile_sum and tile_max hold one entry per tile of the IMAGE; the entries of other ranks' tiles are +0.f.
+ * err_host (n_local f32, packed local order) may be NULL.  Refusals: pt_film_tile_noise's; "every pixel >= 2 samples" is checked
+ * over all tiles of the image.
+ * pt_film_tile_stats_from_sums (any film with a profile): the host f64 step of pt_film_tile_noise over a COMPLETE tile_sum array
+ * (n_tiles entries), n_local = width * height, the counts the film's.  On the sums of an unsharded film it equals that film's
+ * pt_film_tile_noise statistics field for field.
+ * pt_film_select_tiles (any film with a profile; no device work): steps 5 - 6 of the adaptive loops - the tiles with
+ * mean_t > target and, dilate = 1, their 8 neighbours, ascending, into tiles (room for n_tiles entries); *n_out their number.
+ *
+ * The exchange.  pt_film_exchange_fn is a blocking collective the host supplies: in, this rank's arrays; out, the element-wise
+ * combination over all ranks.  Unowned entries are +0.f and errors are not negative, so an element-wise sum, an element-wise
+ * maximum and "take the owner's" all give the same bits.  Every rank calls it once per measurement, in the same order.
+ * pt_film_exchange_comm (user: a pt_comm*) is a ready-made one over the library's communicator: one ncclAllGather of the two
+ * arrays, then the largest of every entry.
+ *
+ * pt_film_render_until_adaptive_sharded / _windowed_sharded (shard) are pt_film_render_until_adaptive / _windowed step for step
+ * - the same loop code - with step 4 = pt_film_shard_tile_noise, exchange, pt_film_tile_stats_from_sums.  Every decision is a
+ * pure function of the complete arrays and of the counts of all tiles, so the ranks take the same passes over the same lists and
+ * stop together without any other communication, and the shards, assembled, are the film the unsharded loop makes: accum,
+ * moments and counts bit for bit, the same statistics, the same stop.  exchange == NULL: shard_count <= 1 only.  A non-zero
+ * return of the exchange ends the loop with PT_ERR_DEVICE (the callback's code is in the message); the film keeps the passes
+ * merged so far.  Refusals: those of the unsharded loops.
+ *
+ * pt_film_assemble: `whole` - an empty or reset unsharded film of the same profile, tile size and kind (pt_film_create or
+ * pt_film_create_windowed with the same N) - receives the planes (and counts) of the n shard films of one sharded film in image
+ * order (k_film_import_shard) and their counters; shards on other devices are staged through the host.  shards: every rank of
+ * n == shard_count once, in any order, equal in every counter and in the tile counts.  Afterwards `whole` is an ordinary film
+ * (uniform if the shards are): resolve, tile noise, the filter, further passes or windows.  Any mismatch is PT_ERR_INVALID
+ * before any device work, `whole` untouched.  One process; shard planes do not travel between processes. */
+typedef struct pt_film_shard_info {
+    uint32_t shard /* 0 / 1 */, rank, count, n_tiles /* of the image */, own_tiles, _pad;
+    uint64_t n_pixels /* of the image */;
+} pt_film_shard_info;
+typedef int (*pt_film_exchange_fn)(float* tile_sum, float* tile_max, uint32_t n_tiles, void* user);
+int  pt_film_create_shard(int device, const pt_profile* profile, const pt_opts* opts, uint32_t windowed, pt_film** out);
+int  pt_film_get_shard_info(const pt_film* film, pt_film_shard_info* out);
+int  pt_film_shard_tile_noise(const pt_film* film, float lum_floor, float* tile_sum, float* tile_max, float* err_host);
+int  pt_film_tile_stats_from_sums(const pt_film* film, const float* tile_sum, double target, pt_film_tile_stats* out);
+int  pt_film_select_tiles(const pt_film* film, const float* tile_sum, double target, uint32_t dilate, uint32_t* tiles, uint32_t* n_out);
+int  pt_film_render_until_adaptive_sharded(pt_film* film, const pt_scene* scene, const pt_film_adaptive_params* params,
+                                           pt_film_exchange_fn exchange, void* exchange_user, pt_film_pass_fn on_pass, void* user,
+                                           pt_film_tile_stats* out);
+int  pt_film_render_until_windowed_sharded(pt_film* film, const pt_scene* scene, const pt_film_window_params* params,
+                                           pt_film_exchange_fn exchange, void* exchange_user, pt_film_pass_fn on_pass, void* user,
+                                           pt_film_tile_stats* out);
+int  pt_film_exchange_comm(float* tile_sum, float* tile_max, uint32_t n_tiles, void* user /* pt_comm* */);
+int  pt_film_assemble(pt_film* whole, const pt_film* const* shards, uint32_t n);
+
+/* ------------------------------------------------------------------ */
 /* measurement                                                         */
 /* ------------------------------------------------------------------ */
 

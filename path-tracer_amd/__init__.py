@@ -240,6 +240,16 @@ class FilmWindowParams(C.Structure):
         return p
 
 
+class FilmShardInfo(C.Structure):
+    """pt_film_shard_info."""
+    _fields_ = [("shard", C.c_uint32), ("rank", C.c_uint32), ("count", C.c_uint32), ("n_tiles", C.c_uint32),
+                ("own_tiles", C.c_uint32), ("_pad", C.c_uint32), ("n_pixels", C.c_uint64)]
+
+
+# pt_film_exchange_fn: int (float* tile_sum, float* tile_max, uint32_t n_tiles, void* user)
+FILM_EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_void_p)
+
+
 class Hit(C.Structure):
     _fields_ = [("prim", C.c_int32), ("flags", C.c_int32), ("dist", C.c_float), ("u", C.c_float),
                 ("v", C.c_float)]
@@ -354,7 +364,10 @@ GPU_SYMBOLS = ["pt_scene_create", "pt_scene_destroy", "pt_scene_set_camera", "pt
                "pt_film_denoise_kernel_times",
                "pt_render_window", "pt_render_window_device", "pt_film_create_windowed", "pt_film_add_window",
                "pt_film_add_tile_window", "pt_film_get_window_info", "pt_film_window_params_default",
-               "pt_film_render_until_windowed", "pt_film_window_kernel_times"]
+               "pt_film_render_until_windowed", "pt_film_window_kernel_times",
+               "pt_film_create_shard", "pt_film_get_shard_info", "pt_film_shard_tile_noise", "pt_film_tile_stats_from_sums",
+               "pt_film_select_tiles", "pt_film_render_until_adaptive_sharded", "pt_film_render_until_windowed_sharded",
+               "pt_film_exchange_comm", "pt_film_assemble"]
 
 
 def host_lib():
@@ -575,6 +588,18 @@ def gpu_lib():
             L.pt_film_render_until_windowed.argtypes = [vp, vp, C.POINTER(FilmWindowParams), FILM_PASS_FN, vp,
                                                         C.POINTER(FilmTileStats)]
             L.pt_film_window_kernel_times.argtypes = [vp, C.c_uint32, vp, vp]
+        if hasattr(L, "pt_film_create_shard"):   # (an A/B library of an earlier commit has no shard films)
+            L.pt_film_create_shard.argtypes = [C.c_int, C.POINTER(Profile), C.POINTER(Opts), C.c_uint32, C.POINTER(vp)]
+            L.pt_film_get_shard_info.argtypes = [vp, C.POINTER(FilmShardInfo)]
+            L.pt_film_shard_tile_noise.argtypes = [vp, C.c_float, vp, vp, vp]
+            L.pt_film_tile_stats_from_sums.argtypes = [vp, vp, C.c_double, C.POINTER(FilmTileStats)]
+            L.pt_film_select_tiles.argtypes = [vp, vp, C.c_double, C.c_uint32, vp, C.POINTER(C.c_uint32)]
+            L.pt_film_render_until_adaptive_sharded.argtypes = [vp, vp, C.POINTER(FilmAdaptiveParams), FILM_EXCHANGE_FN, vp,
+                                                                FILM_PASS_FN, vp, C.POINTER(FilmTileStats)]
+            L.pt_film_render_until_windowed_sharded.argtypes = [vp, vp, C.POINTER(FilmWindowParams), FILM_EXCHANGE_FN, vp,
+                                                                FILM_PASS_FN, vp, C.POINTER(FilmTileStats)]
+            L.pt_film_exchange_comm.argtypes = [vp, vp, C.c_uint32, vp]
+            L.pt_film_assemble.argtypes = [vp, C.POINTER(vp), C.c_uint32]
         L.pt_last_error.restype = C.c_char_p
         L.pt_version.restype = C.c_char_p
         _gpu = L
@@ -1615,6 +1640,102 @@ class Film:
         a, b = np.zeros(reps, np.float32), np.zeros(reps, np.float32)
         check_gpu(self.lib.pt_film_window_kernel_times(self.handle, reps, a.ctypes.data, b.ctypes.data))
         return a, b
+
+    # ---- sharded films
+    @classmethod
+    def shard(cls, profile, opts, windowed=False, device=0):
+        """pt_film_create_shard: the part of rank opts.shard_rank of a film that opts.shard_count ranks hold together
+        (windowed: a window film of profile.samples)."""
+        self = cls.__new__(cls)
+        self.lib = gpu_lib()
+        self.handle = C.c_void_p()
+        self.tonemap = profile.tonemap if profile is not None else TONEMAPS["FILMIC"]
+        check_gpu(self.lib.pt_film_create_shard(device, C.byref(profile) if profile is not None else None,
+                                                C.byref(opts) if opts is not None else None, int(windowed), C.byref(self.handle)))
+        return self
+
+    @property
+    def shard_info(self):
+        i = FilmShardInfo()
+        check_gpu(self.lib.pt_film_get_shard_info(self.handle, C.byref(i)))
+        return i
+
+    def shard_tile_noise(self, lum_floor=PT_FILM_DEFAULT_LUM_FLOOR, want_err=False):
+        """pt_film_shard_tile_noise: (tile_sum [n_tiles], tile_max [n_tiles]) of the image's tiles, 0 for other ranks' tiles;
+        with want_err (tile_sum, tile_max, err [n_local] in packed local order)."""
+        import numpy as np
+        nt = int(self.shard_info.n_tiles)
+        tsum, tmax = np.empty(nt, np.float32), np.empty(nt, np.float32)
+        err = np.empty(int(self.info.n_local), np.float32) if want_err else None
+        check_gpu(self.lib.pt_film_shard_tile_noise(self.handle, lum_floor, tsum.ctypes.data, tmax.ctypes.data,
+                                                    err.ctypes.data if want_err else None))
+        return (tsum, tmax, err) if want_err else (tsum, tmax)
+
+    def tile_stats_from_sums(self, tile_sum, target):
+        """pt_film_tile_stats_from_sums: FilmTileStats of a complete tile_sum array [n_tiles]."""
+        import numpy as np
+        tile_sum = np.ascontiguousarray(tile_sum, np.float32)
+        if tile_sum.shape != (int(self.shard_info.n_tiles),):
+            raise PtError(PT_ERR_INVALID, "Film.tile_stats_from_sums: tile_sum must be [n_tiles]")
+        out = FilmTileStats()
+        check_gpu(self.lib.pt_film_tile_stats_from_sums(self.handle, tile_sum.ctypes.data, target, C.byref(out)))
+        return out
+
+    def select_tiles(self, tile_sum, target, dilate=1):
+        """pt_film_select_tiles: the tiles above the target (dilate: and their 8 neighbours), ascending, uint32."""
+        import numpy as np
+        tile_sum = np.ascontiguousarray(tile_sum, np.float32)
+        nt = int(self.shard_info.n_tiles)
+        if tile_sum.shape != (nt,):
+            raise PtError(PT_ERR_INVALID, "Film.select_tiles: tile_sum must be [n_tiles]")
+        tiles, n = np.empty(nt, np.uint32), C.c_uint32()
+        check_gpu(self.lib.pt_film_select_tiles(self.handle, tile_sum.ctypes.data, target, dilate, tiles.ctypes.data, C.byref(n)))
+        return tiles[:n.value].copy()
+
+    def _render_until_sharded(self, fn, scene, params, exchange, on_pass):
+        import numpy as np
+        out = FilmTileStats()
+        failure = []
+
+        def trampoline(info, noise, _user):
+            try:
+                on_pass(_copy(FilmInfo, info.contents), _copy(FilmNoise, noise.contents))
+            except BaseException as e:   # (an exception cannot cross the C frames: raised after the call)
+                failure.append(e)
+
+        def exchange_trampoline(tile_sum, tile_max, n_tiles, _user):
+            try:   # the callback works on the two arrays in place; its return value is the C callback's (None: 0)
+                rc = exchange(np.ctypeslib.as_array(tile_sum, (n_tiles,)), np.ctypeslib.as_array(tile_max, (n_tiles,)))
+                return int(rc or 0)
+            except BaseException as e:
+                failure.append(e)
+                return -1
+        if isinstance(exchange, tuple):   # (a C callback and its user pointer, e.g. (lib.pt_film_exchange_comm, comm.handle))
+            ex, ex_user = C.cast(exchange[0], FILM_EXCHANGE_FN), exchange[1]
+        else:
+            ex = FILM_EXCHANGE_FN(exchange_trampoline) if exchange is not None else C.cast(None, FILM_EXCHANGE_FN)
+            ex_user = None
+        cb = FILM_PASS_FN(trampoline) if on_pass is not None else C.cast(None, FILM_PASS_FN)
+        rc = fn(self.handle, scene.handle, C.byref(params), ex, ex_user, cb, None, C.byref(out))
+        if failure:
+            raise failure[0]
+        check_gpu(rc)
+        return out
+
+    def render_until_adaptive_sharded(self, scene, params, exchange=None, on_pass=None):
+        """pt_film_render_until_adaptive_sharded on a shard film.  exchange(tile_sum, tile_max): a blocking collective over
+        the ranks that combines the two float32 arrays in place and returns 0 (or None), non-zero to end the loop with
+        PT_ERR_DEVICE; or a tuple (C function, user pointer); None: one rank.  Returns the last FilmTileStats."""
+        return self._render_until_sharded(self.lib.pt_film_render_until_adaptive_sharded, scene, params, exchange, on_pass)
+
+    def render_until_windowed_sharded(self, scene, params, exchange=None, on_pass=None):
+        """pt_film_render_until_windowed_sharded on a windowed shard film; the arguments of render_until_adaptive_sharded."""
+        return self._render_until_sharded(self.lib.pt_film_render_until_windowed_sharded, scene, params, exchange, on_pass)
+
+    def assemble(self, shards):
+        """pt_film_assemble: this empty unsharded film becomes the whole film of the shard films `shards` (every rank once)."""
+        handles = (C.c_void_p * len(shards))(*[f.handle for f in shards])
+        check_gpu(self.lib.pt_film_assemble(self.handle, handles, len(shards)))
 
     # ---- the film filter (DESIGN 4j)
     def denoise_scratch_bytes(self):

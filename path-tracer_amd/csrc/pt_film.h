@@ -113,17 +113,52 @@ __device__ __forceinline__ FilmTile film_tile(const FilmTiling& T, uint32_t k) {
     return t;
 }
 
+// The layout of a film's planes is the template parameter of the tile kernels' bodies: FilmTiling - image order, the unsharded
+// film - or FilmPacked - a shard film, whose planes hold the rank's own tiles one after the other: pixel j of tile
+// k is packed pixel base[k] + j (base: one entry per tile of the IMAGE, FILM_NOT_OWNED for another rank's tile).  The
+// image-order kernels are the bodies' FilmTiling instances, inlined: the code they were before the parameter existed.
+enum : uint32_t { FILM_NOT_OWNED = 0xffffffffu };
+struct FilmPacked {
+    FilmTiling T;
+    const uint32_t* base;
+};
+struct FilmSpan {   // where the pixels of one tile are: p(j), j < P
+    FilmTile t;
+    uint32_t width, base;
+    template <bool PACKED>
+    __device__ __forceinline__ size_t pixel(uint32_t j) const {
+        if constexpr (PACKED) return (size_t)base + j;
+        else return t.pixel(j, width);
+    }
+};
+__device__ __forceinline__ const FilmTiling& film_tiling_of(const FilmTiling& T) { return T; }
+__device__ __forceinline__ const FilmTiling& film_tiling_of(const FilmPacked& L) { return L.T; }
+template <class L>
+struct FilmLayoutIs;
+template <>
+struct FilmLayoutIs<FilmTiling> {
+    static constexpr bool packed = false;
+};
+template <>
+struct FilmLayoutIs<FilmPacked> {
+    static constexpr bool packed = true;
+};
+__device__ __forceinline__ FilmSpan film_span(const FilmTiling& T, uint32_t k) { return FilmSpan{film_tile(T, k), T.width, 0u}; }
+__device__ __forceinline__ FilmSpan film_span(const FilmPacked& L, uint32_t k) { return FilmSpan{film_tile(L.T, k), L.T.width, L.base[k]}; }
+
 // One workgroup per listed tile.  table: n_list + 1 packed offsets, then the n_list tile numbers (the table of the frame that
 // rendered the pass).  Pixel j of listed tile lt is packed pixel table[lt] + j of the pass planes.
-__global__ __launch_bounds__(256) void k_film_merge_tiles(const float* __restrict__ pass_accum, const float2* __restrict__ pass_mom,
-                                                          const uint32_t* __restrict__ table, uint32_t n_list, FilmTiling T,
-                                                          float* __restrict__ film_accum, float2* __restrict__ film_mom,
-                                                          uint32_t* __restrict__ count, uint32_t samples) {
+template <class Layout>
+__device__ __forceinline__ void film_merge_tiles_body(const float* __restrict__ pass_accum, const float2* __restrict__ pass_mom,
+                                                      const uint32_t* __restrict__ table, uint32_t n_list, const Layout& T,
+                                                      float* __restrict__ film_accum, float2* __restrict__ film_mom,
+                                                      uint32_t* __restrict__ count, uint32_t samples) {
+    constexpr bool PK = FilmLayoutIs<Layout>::packed;
     const uint32_t lt = blockIdx.x;
-    const FilmTile t = film_tile(T, table[n_list + 1u + lt]);
-    const uint32_t off = table[lt], P = t.cw * t.ch;
+    const FilmSpan t = film_span(T, table[n_list + 1u + lt]);
+    const uint32_t off = table[lt], P = t.t.cw * t.t.ch;
     for (uint32_t j = threadIdx.x; j < P; j += 256u) {
-        const size_t p = t.pixel(j, T.width), q = (size_t)off + j;
+        const size_t p = t.template pixel<PK>(j), q = (size_t)off + j;
         film_accum[3 * p] = film_accum[3 * p] + pass_accum[3 * q];
         film_accum[3 * p + 1] = film_accum[3 * p + 1] + pass_accum[3 * q + 1];
         film_accum[3 * p + 2] = film_accum[3 * p + 2] + pass_accum[3 * q + 2];
@@ -132,21 +167,45 @@ __global__ __launch_bounds__(256) void k_film_merge_tiles(const float* __restric
         count[p] += samples;
     }
 }
+__global__ __launch_bounds__(256) void k_film_merge_tiles(const float* __restrict__ pass_accum, const float2* __restrict__ pass_mom,
+                                                          const uint32_t* __restrict__ table, uint32_t n_list, FilmTiling T,
+                                                          float* __restrict__ film_accum, float2* __restrict__ film_mom,
+                                                          uint32_t* __restrict__ count, uint32_t samples) {
+    film_merge_tiles_body(pass_accum, pass_mom, table, n_list, T, film_accum, film_mom, count, samples);
+}
+__global__ __launch_bounds__(256) void k_film_merge_tiles_packed(const float* __restrict__ pass_accum, const float2* __restrict__ pass_mom,
+                                                                 const uint32_t* __restrict__ table, uint32_t n_list, FilmPacked T,
+                                                                 float* __restrict__ film_accum, float2* __restrict__ film_mom,
+                                                                 uint32_t* __restrict__ count, uint32_t samples) {
+    film_merge_tiles_body(pass_accum, pass_mom, table, n_list, T, film_accum, film_mom, count, samples);
+}
 
 // One workgroup per tile of the image.  n of pixel p: count[p], or the film's uniform total `n_uniform` where count is null.
 // Thread i adds the errors of the tile's pixels i, i + 256, ... to 0.f in that order; then k_film_noise's tree.  err (image
-// order) may be null.
-__global__ __launch_bounds__(256) void k_film_tile_noise(const float2* __restrict__ moments, const uint32_t* __restrict__ count,
-                                                         uint32_t n_uniform, FilmTiling T, float lum_floor, float* __restrict__ err,
-                                                         float* __restrict__ tile_sum, float* __restrict__ tile_max) {
+// order; the packed variant: the film's packed order) may be null.  A tile of another rank (packed variant only) gets the sum
+// and the maximum 0.f: nothing of it is read.
+template <class Layout>
+__device__ __forceinline__ void film_tile_noise_body(const float2* __restrict__ moments, const uint32_t* __restrict__ count,
+                                                     uint32_t n_uniform, const Layout& T, float lum_floor, float* __restrict__ err,
+                                                     float* __restrict__ tile_sum, float* __restrict__ tile_max) {
+    constexpr bool PK = FilmLayoutIs<Layout>::packed;
     __shared__ float vs[256];
     __shared__ float vm[256];
     const uint32_t i = threadIdx.x;
-    const FilmTile t = film_tile(T, blockIdx.x);
-    const uint32_t P = t.cw * t.ch;
+    const FilmSpan t = film_span(T, blockIdx.x);
+    if constexpr (PK) {
+        if (t.base == FILM_NOT_OWNED) {   // (the whole workgroup)
+            if (i == 0u) {
+                tile_sum[blockIdx.x] = 0.f;
+                tile_max[blockIdx.x] = 0.f;
+            }
+            return;
+        }
+    }
+    const uint32_t P = t.t.cw * t.t.ch;
     float v = 0.f, w = 0.f;
     for (uint32_t j = i; j < P; j += 256u) {
-        const size_t p = t.pixel(j, T.width);
+        const size_t p = t.template pixel<PK>(j);
         const uint32_t n = count != nullptr ? count[p] : n_uniform;
         const float2 m = moments[p];
         const float N = (float)n;
@@ -182,6 +241,16 @@ __global__ __launch_bounds__(256) void k_film_tile_noise(const float2* __restric
             tile_max[blockIdx.x] = m;
         }
     }
+}
+__global__ __launch_bounds__(256) void k_film_tile_noise(const float2* __restrict__ moments, const uint32_t* __restrict__ count,
+                                                         uint32_t n_uniform, FilmTiling T, float lum_floor, float* __restrict__ err,
+                                                         float* __restrict__ tile_sum, float* __restrict__ tile_max) {
+    film_tile_noise_body(moments, count, n_uniform, T, lum_floor, err, tile_sum, tile_max);
+}
+__global__ __launch_bounds__(256) void k_film_tile_noise_packed(const float2* __restrict__ moments, const uint32_t* __restrict__ count,
+                                                                uint32_t n_uniform, FilmPacked T, float lum_floor, float* __restrict__ err,
+                                                                float* __restrict__ tile_sum, float* __restrict__ tile_max) {
+    film_tile_noise_body(moments, count, n_uniform, T, lum_floor, err, tile_sum, tile_max);
 }
 
 __global__ __launch_bounds__(256) void k_film_color_counts(const float* __restrict__ accum, const uint32_t* __restrict__ count,

@@ -16,6 +16,7 @@
 //   k_guides, k_dn_*  pt_denoise.h: first-hit guide planes and the a-trous filter of denoised previews
 //   k_accumulate_moments, k_dnv_*  pt_variance.h: per-pixel sample moments and the variance-guided form of that filter
 //   k_film_*          pt_film.h: the progressive film - merging passes, the noise figure of its moments
+//   k_film_*_packed, k_film_import_shard   pt_film_shard.h: the tile kernels of shard films, and their way back to one device
 //   k_stream_copy     achievable-HBM yardstick of the roofline (pt_measure_copy_bandwidth)
 //   k_trace / k_trace_all / k_escape_query / k_isect / k_rng / k_math   parity-test hooks
 #include <hip/hip_runtime.h>
@@ -50,6 +51,7 @@
 #include "pt_film.h"
 #include "pt_film_denoise.h"
 #include "pt_film_window.h"
+#include "pt_film_shard.h"
 #include "pthost.h"
 #include "../host/scene_check.h"
 
@@ -4091,7 +4093,16 @@ struct pt_film {
     // pixel, so a pixel at count c holds the sums of the samples [0, c) of pt_render(samples = enum_n).
     bool windowed = false;
     uint32_t enum_n = 0, windows = 0, tile_windows = 0;
+    // A shard film (pt_film_create_shard): this rank's tiles of a film that opts.shard_count ranks hold together.
+    // tile_count, samples and the pass counters are the WHOLE film's (tile lists are global); the planes hold the own tiles.
+    // packed (shard_count > 1): the planes are in packed tile order and the FilmPacked kernels run; base_of[k] is the first
+    // packed pixel of tile k (FILM_NOT_OWNED: another rank's), base_dev the same on the device.  A one-rank shard film is in
+    // image order, like every unsharded film.
+    bool shard = false, packed = false;
+    std::vector<uint32_t> base_of;
+    DeviceBuffer base_dev;
     bool uniform() const { return count == nullptr; }
+    bool owns(uint32_t tile) const { return !packed || base_of[tile] != FILM_NOT_OWNED; }
     ~pt_film() {
         if (filter) (void)hipFree(filter);
         if (base) (void)hipFree(base);
@@ -4230,7 +4241,85 @@ uint64_t film_tile_pixels(const FilmTiling& T, uint32_t k) {
 void film_check_tiled(const char* who, const pt_film* film) {
     if (!film) fail(PT_ERR_INVALID, "%s: null argument", who);
     if (!film->has_profile) fail(PT_ERR_INVALID, "%s: a film made from planes has no tiling", who);
-    if (film->opts.shard_count > 1) fail(PT_ERR_INVALID, "%s: a sharded film takes whole passes only (shard_count %u)", who, film->opts.shard_count);
+    if (film->opts.shard_count > 1 && !film->shard) fail(PT_ERR_INVALID, "%s: a sharded film takes whole passes only (shard_count %u)", who, film->opts.shard_count);
+}
+// The calls whose figures are defined over one device's planes
+void film_refuse_shard(const char* who, const pt_film* film) {
+    if (film && film->shard) fail(PT_ERR_INVALID, "%s: a shard film holds a part of the image (pt_film_assemble makes the whole film)", who);
+}
+void film_check_shard(const char* who, const pt_film* film) {
+    if (!film) fail(PT_ERR_INVALID, "%s: null argument", who);
+    if (!film->shard) fail(PT_ERR_INVALID, "%s: the film is not a shard film (pt_film_create_shard)", who);
+}
+// The options of a film's tile-list frames and tile lists: a shard film's lists are global, its own tiles render unsharded
+pt_opts film_list_opts(const pt_film& film) {
+    pt_opts o = film.opts;
+    o.shard_rank = 0;
+    o.shard_count = 1;
+    return o;
+}
+FilmPacked film_packed(const pt_film& film) { return FilmPacked{film_tiling(film), (const uint32_t*)film.base_dev.p}; }
+// The listed tiles this film holds, in list order: the list itself unless the film is packed
+std::vector<uint32_t> film_own_tiles(const pt_film& film, const std::vector<uint32_t>& tiles) {
+    if (!film.packed) return tiles;
+    std::vector<uint32_t> own;
+    for (uint32_t k : tiles)
+        if (film.owns(k)) own.push_back(k);
+    return own;
+}
+std::vector<uint32_t> film_all_tiles(const pt_film& film) {
+    std::vector<uint32_t> all(film_n_tiles(film));
+    for (uint32_t k = 0; k < all.size(); ++k) all[k] = k;
+    return all;
+}
+// The tile map of the own tiles of a list (no tile: an empty map, nothing to launch)
+TileMap film_own_map(const char* who, const pt_film& film, const std::vector<uint32_t>& own) {
+    if (own.empty()) {
+        TileMap m{};
+        m.offsets.push_back(0u);
+        return m;
+    }
+    return make_tile_list_map(who, film.profile, film_list_opts(film), own.data(), (uint32_t)own.size());
+}
+void film_upload_table(pt_film& film, const TileMap& tm) {
+    std::vector<uint32_t> table(tm.offsets);
+    table.insert(table.end(), tm.tiles.begin(), tm.tiles.end());
+    HIP_CHECK(hipMemcpy(film.table.p, table.data(), table.size() * 4u, hipMemcpyHostToDevice));
+}
+// The four tile kernels on the film's layout.  n_list: the tiles of the uploaded table (> 0).
+void film_launch_merge_tiles(const pt_film& film, uint32_t n_list, const float* pa, const float* pm, uint32_t samples) {
+    if (film.packed)
+        hipLaunchKernelGGL(k_film_merge_tiles_packed, dim3(n_list), dim3(256), 0, 0, pa, (const float2*)pm, (const uint32_t*)film.table.p,
+                           n_list, film_packed(film), film.accum, (float2*)film.moments, film.count, samples);
+    else
+        hipLaunchKernelGGL(k_film_merge_tiles, dim3(n_list), dim3(256), 0, 0, pa, (const float2*)pm, (const uint32_t*)film.table.p, n_list,
+                           film_tiling(film), film.accum, (float2*)film.moments, film.count, samples);
+}
+void film_launch_gather_tiles(const pt_film& film, uint32_t n_list, float* pa, float* pm) {
+    if (film.packed)
+        hipLaunchKernelGGL(k_film_gather_tiles_packed, dim3(n_list), dim3(256), 0, 0, (const float*)film.accum, (const float2*)film.moments,
+                           (const uint32_t*)film.table.p, n_list, film_packed(film), pa, (float2*)pm);
+    else
+        hipLaunchKernelGGL(k_film_gather_tiles, dim3(n_list), dim3(256), 0, 0, (const float*)film.accum, (const float2*)film.moments,
+                           (const uint32_t*)film.table.p, n_list, film_tiling(film), pa, (float2*)pm);
+}
+void film_launch_scatter_tiles(const pt_film& film, uint32_t n_list, const float* pa, const float* pm, uint32_t samples) {
+    if (film.packed)
+        hipLaunchKernelGGL(k_film_scatter_tiles_packed, dim3(n_list), dim3(256), 0, 0, pa, (const float2*)pm, (const uint32_t*)film.table.p,
+                           n_list, film_packed(film), film.accum, (float2*)film.moments, film.count, samples);
+    else
+        hipLaunchKernelGGL(k_film_scatter_tiles, dim3(n_list), dim3(256), 0, 0, pa, (const float2*)pm, (const uint32_t*)film.table.p,
+                           n_list, film_tiling(film), film.accum, (float2*)film.moments, film.count, samples);
+}
+// One workgroup per tile of the IMAGE, on either layout
+void film_launch_tile_noise(const pt_film& film, float lum_floor, float* err, float* tile_sum, float* tile_max) {
+    const uint32_t n_tiles = film_n_tiles(film);
+    if (film.packed)
+        hipLaunchKernelGGL(k_film_tile_noise_packed, dim3(n_tiles), dim3(256), 0, 0, (const float2*)film.moments,
+                           (const uint32_t*)film.count, (uint32_t)film.samples, film_packed(film), lum_floor, err, tile_sum, tile_max);
+    else
+        hipLaunchKernelGGL(k_film_tile_noise, dim3(n_tiles), dim3(256), 0, 0, (const float2*)film.moments, (const uint32_t*)film.count,
+                           (uint32_t)film.samples, film_tiling(film), lum_floor, err, tile_sum, tile_max);
 }
 void film_refuse_non_uniform(const char* who, const pt_film* film) {
     if (film && !film->uniform()) fail(PT_ERR_UNSUPPORTED, "%s: the film has a sample count per pixel (pt_film_add_tile_pass); this call assumes one", who);
@@ -4239,7 +4328,7 @@ void film_refuse_non_uniform(const char* who, const pt_film* film) {
 TileMap film_check_tile_pass(const char* who, const pt_film* film, uint32_t samples, const uint32_t* tiles, uint32_t n_tiles) {
     film_check_tiled(who, film);
     film_check_samples(who, film, samples);
-    return make_tile_list_map(who, film->profile, film->opts, tiles, n_tiles);
+    return make_tile_list_map(who, film->profile, film_list_opts(*film), tiles, n_tiles);
 }
 // The first tile pass: the count plane, filled with the uniform total; the table's buffer
 void film_make_non_uniform(pt_film& film) {
@@ -4259,51 +4348,57 @@ void film_make_non_uniform(pt_film& film) {
     film.tile_count.assign(n_tiles, film.samples);
     film.bytes_adaptive += (uint64_t)film.n_local * 4u;
 }
-// film = film + pass buffers over the listed tiles, then the counters
-void film_merge_tiles(pt_film& film, const TileMap& tm, uint32_t samples) {
+// film = film + pass buffers over the tiles of tm - the listed tiles the film holds, which the pass buffers are packed by - then
+// the counters, which follow the whole list
+void film_merge_tiles(pt_film& film, const TileMap& tm, const std::vector<uint32_t>& listed, uint32_t samples) {
     film_make_non_uniform(film);
-    std::vector<uint32_t> table(tm.offsets);
-    table.insert(table.end(), tm.tiles.begin(), tm.tiles.end());
-    HIP_CHECK(hipMemcpy(film.table.p, table.data(), table.size() * 4u, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_film_merge_tiles, dim3(tm.n_local_tiles), dim3(256), 0, 0, (const float*)film.pass_accum,
-                       (const float2*)film.pass_moments, (const uint32_t*)film.table.p, tm.n_local_tiles, film_tiling(film),
-                       film.accum, (float2*)film.moments, film.count, samples);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
+    if (tm.n_local_tiles) {   // (a shard film that holds none of the list: the pass happened elsewhere)
+        film_upload_table(film, tm);
+        film_launch_merge_tiles(film, tm.n_local_tiles, film.pass_accum, film.pass_moments, samples);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+    }
     ++film.passes;
     ++film.tile_passes;
-    film.last_pass_tiles = tm.n_local_tiles;
+    film.last_pass_tiles = (uint32_t)listed.size();
     film.last_pass_samples = samples;
-    for (uint32_t k : tm.tiles) film.tile_count[k] += samples;
+    for (uint32_t k : listed) film.tile_count[k] += samples;
     film.samples = *std::max_element(film.tile_count.begin(), film.tile_count.end());
 }
 void film_add_tile_pass(pt_film& film, const pt_scene* scene, uint32_t samples, const uint32_t* tiles, uint32_t n_tiles) {
     const char* who = "pt_film_add_tile_pass";
     if (!scene) fail(PT_ERR_INVALID, "%s: null argument", who);
-    const TileMap tm = film_check_tile_pass(who, &film, samples, tiles, n_tiles);
+    const TileMap listed = film_check_tile_pass(who, &film, samples, tiles, n_tiles);
     if (scene->device != film.device)
         fail(PT_ERR_INVALID, "%s: the scene is on device %d, the film on device %d", who, scene->device, film.device);
     HIP_CHECK(hipSetDevice(film.device));
-    pt_profile p = film.profile;
-    p.samples = samples;
-    FrameTaps taps;
-    taps.moments = (float2*)film.pass_moments;
-    const TileList list{tiles, n_tiles};
-    render_device(render_state(scene), p, &film.opts, nullptr, film.pass_accum, nullptr, false, &taps, &list);
-    HIP_CHECK(hipDeviceSynchronize());   // the frame is complete (and has not failed) before the film changes
-    film_merge_tiles(film, tm, samples);
+    // a shard film renders the listed tiles it holds, as an unsharded tile-list frame: the pass buffers come in list order, which
+    // is the film's own order for those tiles
+    const std::vector<uint32_t> own = film_own_tiles(film, listed.tiles);
+    const TileMap tm = film.packed ? film_own_map(who, film, own) : listed;
+    if (!own.empty()) {
+        pt_profile p = film.profile;
+        p.samples = samples;
+        FrameTaps taps;
+        taps.moments = (float2*)film.pass_moments;
+        const TileList list{own.data(), (uint32_t)own.size()};
+        const pt_opts o = film_list_opts(film);
+        render_device(render_state(scene), p, &o, nullptr, film.pass_accum, nullptr, false, &taps, &list);
+        HIP_CHECK(hipDeviceSynchronize());   // the frame is complete (and has not failed) before the film changes
+    }
+    film_merge_tiles(film, tm, listed.tiles, samples);
 }
 // A whole frame on any film: a non-uniform one takes it as the tile pass that lists every tile
 void film_add_whole_pass(pt_film& film, const pt_scene* scene, uint32_t samples) {
     if (film.uniform()) return film_add_pass(film, scene, samples);
     film_check_pass("pt_film_add_pass", &film, scene, samples);
-    std::vector<uint32_t> all(film_n_tiles(film));
-    for (uint32_t k = 0; k < all.size(); ++k) all[k] = k;
+    const std::vector<uint32_t> all = film_all_tiles(film);
     film_add_tile_pass(film, scene, samples, all.data(), (uint32_t)all.size());
 }
 
 // The host step of pt_film_tile_noise: the statistics, in f64, of one tile sum per tile of the film.
 void film_tile_stats(const pt_film& film, const std::vector<float>& sums, double target, pt_film_tile_stats& out) {
+    const uint64_t n_pixels = (uint64_t)film.profile.width * film.profile.height;   // (n_local of an unsharded film; a shard film: the whole film's)
     const FilmTiling T = film_tiling(film);
     const uint32_t n_tiles = (uint32_t)sums.size();
     double S = 0.0, worst = 0.0;
@@ -4318,7 +4413,7 @@ void film_tile_stats(const pt_film& film, const std::vector<float>& sums, double
         pixel_samples += pixels * (film.uniform() ? film.samples : film.tile_count[t]);
     }
     memset(&out, 0, sizeof out);
-    out.mean_error = S / (double)film.n_local;
+    out.mean_error = S / (double)n_pixels;
     out.max_tile_error = worst;
     out.samples = film.samples;
     out.pixel_samples = pixel_samples;
@@ -4331,6 +4426,7 @@ void film_tile_noise(const pt_film& film_c, float lum_floor, double target, pt_f
                      float* tile_sum_host, float* tile_max_host) {
     const char* who = "pt_film_tile_noise";
     film_check_tiled(who, &film_c);
+    film_refuse_shard(who, &film_c);
     film_check_noise_args(who, lum_floor, target);
     pt_film& film = const_cast<pt_film&>(film_c);   // (the tile arrays are made on first use: scratch, not the film's contents)
     const uint32_t n_tiles = film_n_tiles(film);
@@ -4491,7 +4587,8 @@ void film_render_window(pt_film& film, const pt_scene* scene, uint32_t s0, uint3
     FrameTaps taps;
     taps.moments = (float2*)d_moments;
     const SampleWindow win{s0, s0 + samples};
-    render_device(render_state(scene), p, &film.opts, nullptr, d_accum, nullptr, false, &taps, list, &win);
+    const pt_opts o = list ? film_list_opts(film) : film.opts;
+    render_device(render_state(scene), p, &o, nullptr, d_accum, nullptr, false, &taps, list, &win);
     HIP_CHECK(hipDeviceSynchronize());   // the frame is complete (and has not failed) before the film changes
 }
 
@@ -4502,37 +4599,32 @@ void film_add_tile_window(pt_film& film, const pt_scene* scene, uint32_t samples
     const char* who = "pt_film_add_tile_window";
     film_check_window(who, &film, scene, samples);
     film_check_tiled(who, &film);
-    const TileMap whole = make_tile_list_map(who, film.profile, film.opts, tiles, n_tiles);
-    std::map<uint64_t, std::vector<uint32_t>> groups;   // count -> its tiles, ascending both ways
+    const pt_opts list_opts = film_list_opts(film);
+    const TileMap whole = make_tile_list_map(who, film.profile, list_opts, tiles, n_tiles);
+    std::map<uint64_t, std::vector<uint32_t>> groups;   // count -> its tiles (a shard film: the ones it holds), ascending both ways
     for (uint32_t k : whole.tiles) {
         const uint64_t c = film_count_of(film, k);
         if (c + samples > film.enum_n)
             fail(PT_ERR_INVALID, "%s: tile %u holds %llu samples, %u more would pass the enumeration's %u", who, k, (unsigned long long)c, samples, film.enum_n);
-        groups[c].push_back(k);
+        if (film.owns(k)) groups[c].push_back(k);
     }
     HIP_CHECK(hipSetDevice(film.device));
     const size_t table_before = film.table.bytes;
     film.table.ensure((size_t)(2u * film_n_tiles(film) + 1u) * 4u);
     film.bytes_adaptive += film.table.bytes - table_before;
-    const FilmTiling T = film_tiling(film);
     struct Run {
         TileMap tm;
         uint64_t off;   // the run's first packed pixel in the pass buffers
     };
     std::vector<Run> runs;
     uint64_t off = 0;
-    auto upload = [&](const TileMap& tm) {
-        std::vector<uint32_t> table(tm.offsets);
-        table.insert(table.end(), tm.tiles.begin(), tm.tiles.end());
-        HIP_CHECK(hipMemcpy(film.table.p, table.data(), table.size() * 4u, hipMemcpyHostToDevice));
-    };
+    auto upload = [&](const TileMap& tm) { film_upload_table(film, tm); };
     for (auto& g : groups) {
-        Run r{make_tile_list_map(who, film.profile, film.opts, g.second.data(), (uint32_t)g.second.size()), off};
+        Run r{make_tile_list_map(who, film.profile, list_opts, g.second.data(), (uint32_t)g.second.size()), off};
         float* pa = film.pass_accum + 3u * r.off;
         float* pm = film.pass_moments + 2u * r.off;
         upload(r.tm);
-        hipLaunchKernelGGL(k_film_gather_tiles, dim3(r.tm.n_local_tiles), dim3(256), 0, 0, (const float*)film.accum,
-                           (const float2*)film.moments, (const uint32_t*)film.table.p, r.tm.n_local_tiles, T, pa, (float2*)pm);
+        film_launch_gather_tiles(film, r.tm.n_local_tiles, pa, pm);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipDeviceSynchronize());   // (the table is rewritten by the next run)
         const TileList list{g.second.data(), (uint32_t)g.second.size()};
@@ -4543,13 +4635,13 @@ void film_add_tile_window(pt_film& film, const pt_scene* scene, uint32_t samples
     film_make_non_uniform(film);
     for (const Run& r : runs) {
         upload(r.tm);
-        hipLaunchKernelGGL(k_film_scatter_tiles, dim3(r.tm.n_local_tiles), dim3(256), 0, 0, (const float*)(film.pass_accum + 3u * r.off),
-                           (const float2*)(film.pass_moments + 2u * r.off), (const uint32_t*)film.table.p, r.tm.n_local_tiles, T,
-                           film.accum, (float2*)film.moments, film.count, samples);
+        film_launch_scatter_tiles(film, r.tm.n_local_tiles, film.pass_accum + 3u * r.off, film.pass_moments + 2u * r.off, samples);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipDeviceSynchronize());
         for (uint32_t k : r.tm.tiles) film.tile_count[k] += samples;
     }
+    for (uint32_t k : whole.tiles)   // (a shard film: the windows that other ranks render)
+        if (!film.owns(k)) film.tile_count[k] += samples;
     ++film.passes;
     ++film.tile_passes;
     ++film.tile_windows;
@@ -4564,8 +4656,7 @@ void film_add_window(pt_film& film, const pt_scene* scene, uint32_t samples) {
     const char* who = "pt_film_add_window";
     film_check_window(who, &film, scene, samples);
     if (!film.uniform()) {
-        std::vector<uint32_t> all(film_n_tiles(film));
-        for (uint32_t k = 0; k < all.size(); ++k) all[k] = k;
+        const std::vector<uint32_t> all = film_all_tiles(film);
         return film_add_tile_window(film, scene, samples, all.data(), (uint32_t)all.size());
     }
     if (film.samples + samples > film.enum_n)
@@ -4600,8 +4691,10 @@ void film_check_window_params(const char* who, const pt_film* film, const pt_sce
 }
 
 // The loop of pt_film_render_until_windowed (include/ptgpu.h).
+// noise(st, sums): as in film_adaptive_loop.
+template <class Noise>
 void film_window_loop(pt_film* film, const pt_scene* scene, const pt_film_window_params* params, pt_film_pass_fn on_pass, void* user,
-                      pt_film_tile_stats* out) {
+                      pt_film_tile_stats* out, Noise noise) {
     const FilmTiling T = film_tiling(*film);
     const uint32_t n_tiles = film_n_tiles(*film), N = film->enum_n;
     std::vector<float> sums(n_tiles);
@@ -4609,7 +4702,7 @@ void film_window_loop(pt_film* film, const pt_scene* scene, const pt_film_window
     pt_film_tile_stats st{};
     bool measured = false;
     auto measure = [&](uint32_t rendered) {
-        film_tile_noise(*film, params->lum_floor, params->target, st, nullptr, sums.data(), nullptr);
+        noise(st, sums.data());
         st.active_tiles = rendered;
         measured = true;
         film_select_active(T, sums, params->target, params->dilate, active);
@@ -4647,8 +4740,132 @@ void film_window_loop(pt_film* film, const pt_scene* scene, const pt_film_window
             on_pass(&info, &ns, user);
         }
     }
-    if (!measured) film_tile_noise(*film, params->lum_floor, params->target, st, nullptr, nullptr, nullptr);   // (a full film that was never measured)
+    if (!measured) noise(st, nullptr);   // (a full film that was never measured)
     *out = st;
+}
+
+// ---- sharded films (pt_film_shard.h)
+// This rank's tile sums and maxima: one entry per tile of the image, 0.f for the tiles of other ranks.  err_host: packed local.
+void film_shard_tile_noise(const pt_film& film_c, float lum_floor, float* tile_sum_host, float* tile_max_host, float* err_host) {
+    const char* who = "pt_film_shard_tile_noise";
+    film_check_shard(who, &film_c);
+    film_check_noise_args(who, lum_floor, 0.0);
+    pt_film& film = const_cast<pt_film&>(film_c);   // (the tile arrays are made on first use: scratch, not the film's contents)
+    const uint32_t n_tiles = film_n_tiles(film);
+    const uint64_t least = film.uniform() ? film.samples : *std::min_element(film.tile_count.begin(), film.tile_count.end());
+    if (least < 2u) fail(PT_ERR_INVALID, "%s: a sample variance needs >= 2 samples in every pixel (the fewest: %llu)", who, (unsigned long long)least);
+    HIP_CHECK(hipSetDevice(film.device));
+    if (!film.tile_sum) {
+        HIP_CHECK(hipMalloc((void**)&film.tile_sum, (size_t)n_tiles * 8u));
+        film.bytes_adaptive += (uint64_t)n_tiles * 8u;
+    }
+    film_launch_tile_noise(film, lum_floor, err_host ? film.err : (float*)nullptr, film.tile_sum, film.tile_sum + n_tiles);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    if (tile_sum_host) HIP_CHECK(hipMemcpy(tile_sum_host, film.tile_sum, n_tiles * sizeof(float), hipMemcpyDeviceToHost));
+    if (tile_max_host) HIP_CHECK(hipMemcpy(tile_max_host, film.tile_sum + n_tiles, n_tiles * sizeof(float), hipMemcpyDeviceToHost));
+    if (err_host) HIP_CHECK(hipMemcpy(err_host, film.err, film.n_local * sizeof(float), hipMemcpyDeviceToHost));
+}
+
+// Step 4 of the sharded loops: the local tile noise, the exchange, the host statistics of the complete array.
+struct ShardNoise {
+    const char* who;
+    pt_film* film;
+    float lum_floor;
+    double target;
+    pt_film_exchange_fn exchange;
+    void* exchange_user;
+    void operator()(pt_film_tile_stats& st, float* sums) const {
+        const uint32_t n_tiles = film_n_tiles(*film);
+        std::vector<float> s(n_tiles), m(n_tiles);
+        film_shard_tile_noise(*film, lum_floor, s.data(), m.data(), nullptr);
+        if (exchange) {
+            const int rc = exchange(s.data(), m.data(), n_tiles, exchange_user);
+            if (rc != 0) fail(PT_ERR_DEVICE, "%s: the exchange of the tile noise failed (the callback returned %d)", who, rc);
+        }
+        film_tile_stats(*film, s, target, st);
+        if (sums) memcpy(sums, s.data(), n_tiles * sizeof(float));
+    }
+};
+void film_check_sharded_loop(const char* who, const pt_film* film, pt_film_exchange_fn exchange) {
+    film_check_shard(who, film);
+    if (!exchange && film->opts.shard_count > 1)
+        fail(PT_ERR_INVALID, "%s: %u ranks hold the film, the loop needs an exchange", who, film->opts.shard_count);
+}
+
+// whole = the shards' planes in image order, and their counters.  Every refusal comes before any device work.
+void film_assemble(pt_film& whole, const pt_film* const* shards, uint32_t n) {
+    const char* who = "pt_film_assemble";
+    if (!whole.has_profile || whole.shard || whole.opts.shard_count > 1)
+        fail(PT_ERR_INVALID, "%s: the whole film must be an unsharded film with a profile (pt_film_create, pt_film_create_windowed)", who);
+    if (whole.passes || whole.samples || !whole.uniform()) fail(PT_ERR_INVALID, "%s: the whole film must be empty (pt_film_reset)", who);
+    if (!shards || !n) fail(PT_ERR_INVALID, "%s: null argument", who);
+    const pt_film* s0 = shards[0];
+    std::vector<uint8_t> seen(n, 0);
+    for (uint32_t i = 0; i < n; ++i) {
+        const pt_film* s = shards[i];
+        film_check_shard(who, s);
+        if (s->opts.shard_count != n) fail(PT_ERR_INVALID, "%s: %u shards of a film that %u ranks hold", who, n, s->opts.shard_count);
+        if (seen[s->opts.shard_rank]) fail(PT_ERR_INVALID, "%s: rank %u appears twice", who, s->opts.shard_rank);
+        seen[s->opts.shard_rank] = 1;   // (n distinct ranks below n: none is missing)
+        const pt_profile &a = s->profile, &b = whole.profile;
+        if (a.width != b.width || a.height != b.height || a.bounces != b.bounces || a.brdf != b.brdf || a.tonemap != b.tonemap)
+            fail(PT_ERR_INVALID, "%s: shard %u has another profile than the whole film", who, i);
+        if (s->opts.tile_w != whole.opts.tile_w || s->opts.tile_h != whole.opts.tile_h)
+            fail(PT_ERR_INVALID, "%s: shard %u has tiles of %u x %u, the whole film of %u x %u", who, i, s->opts.tile_w, s->opts.tile_h,
+                 whole.opts.tile_w, whole.opts.tile_h);
+        if (s->windowed != whole.windowed || s->enum_n != whole.enum_n)
+            fail(PT_ERR_INVALID, "%s: shard %u and the whole film differ in kind (windowed or not, the enumeration)", who, i);
+        if (s->passes != s0->passes || s->last_pass_samples != s0->last_pass_samples || s->samples != s0->samples ||
+            s->tile_passes != s0->tile_passes || s->last_pass_tiles != s0->last_pass_tiles || s->windows != s0->windows ||
+            s->tile_windows != s0->tile_windows || s->uniform() != s0->uniform() || s->tile_count != s0->tile_count)
+            fail(PT_ERR_INVALID, "%s: shard %u has other counters than shard 0 (they are not parts of one film)", who, i);
+    }
+    HIP_CHECK(hipSetDevice(whole.device));
+    const bool counts = !s0->uniform();
+    if (counts) film_make_non_uniform(whole);
+    const size_t table_before = whole.table.bytes;
+    whole.table.ensure((size_t)(2u * film_n_tiles(whole) + 1u) * 4u);
+    whole.bytes_adaptive += whole.table.bytes - table_before;
+    for (uint32_t i = 0; i < n; ++i) {
+        const pt_film& s = *shards[i];
+        const float *src_a = s.accum, *src_m = s.moments;
+        const uint32_t* src_c = s.count;
+        if (s.device != whole.device) {   // staged through the host into the whole film's pass buffers (counts: its err plane)
+            std::vector<float> ha(3u * s.n_local), hm(2u * s.n_local);
+            std::vector<uint32_t> hc(counts ? s.n_local : 0u);
+            HIP_CHECK(hipSetDevice(s.device));
+            HIP_CHECK(hipMemcpy(ha.data(), s.accum, ha.size() * 4u, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(hm.data(), s.moments, hm.size() * 4u, hipMemcpyDeviceToHost));
+            if (counts) HIP_CHECK(hipMemcpy(hc.data(), s.count, hc.size() * 4u, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipSetDevice(whole.device));
+            HIP_CHECK(hipMemcpy(whole.pass_accum, ha.data(), ha.size() * 4u, hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(whole.pass_moments, hm.data(), hm.size() * 4u, hipMemcpyHostToDevice));
+            if (counts) HIP_CHECK(hipMemcpy(whole.err, hc.data(), hc.size() * 4u, hipMemcpyHostToDevice));
+            src_a = whole.pass_accum, src_m = whole.pass_moments, src_c = counts ? (const uint32_t*)whole.err : nullptr;
+        }
+        if (!s.packed) {   // one rank: image order already
+            HIP_CHECK(hipMemcpy(whole.accum, src_a, s.n_local * 12u, hipMemcpyDeviceToDevice));
+            HIP_CHECK(hipMemcpy(whole.moments, src_m, s.n_local * 8u, hipMemcpyDeviceToDevice));
+            if (counts) HIP_CHECK(hipMemcpy(whole.count, src_c, s.n_local * 4u, hipMemcpyDeviceToDevice));
+        } else {
+            const TileMap tm = make_tile_map(s.profile, s.opts, s.opts.shard_rank);
+            film_upload_table(whole, tm);
+            hipLaunchKernelGGL(k_film_import_shard, dim3(tm.n_local_tiles), dim3(256), 0, 0, src_a, (const float2*)src_m, src_c,
+                               (const uint32_t*)whole.table.p, tm.n_local_tiles, film_tiling(whole), whole.accum, (float2*)whole.moments,
+                               counts ? whole.count : (uint32_t*)nullptr);
+            HIP_CHECK(hipGetLastError());
+        }
+        HIP_CHECK(hipDeviceSynchronize());   // (the table and the staging planes are rewritten by the next shard)
+    }
+    whole.passes = s0->passes;
+    whole.last_pass_samples = s0->last_pass_samples;
+    whole.samples = s0->samples;
+    whole.tile_passes = s0->tile_passes;
+    whole.last_pass_tiles = s0->last_pass_tiles;
+    whole.windows = s0->windows;
+    whole.tile_windows = s0->tile_windows;
+    if (counts) whole.tile_count = s0->tile_count;
 }
 
 // ---- the film filter (pt_film_denoise.h)
@@ -4671,6 +4888,7 @@ FdnScratch fdn_scratch_layout(const pt_film& film) { return fdn_scratch_layout(f
 // What the pt_film_denoise family refuses before any device work (null pointers other than the film are the callers').
 void fdn_check(const char* who, const pt_film* film, int variance, const pt_denoise_params* p, float lum_floor, bool want_ferr) {
     film_check_tiled(who, film);
+    film_refuse_shard(who, film);
     if (variance != 0 && variance != 1) fail(PT_ERR_INVALID, "%s: variance must be 0 (plain) or 1 (variance-guided)", who);
     if (!variance && want_ferr) fail(PT_ERR_INVALID, "%s: the plain filter carries no variance, so it has no ferr", who);
     if (variance) dnv_check(who, p, film->profile.width, film->profile.height, 2u);
@@ -5375,6 +5593,7 @@ int pt_film_render_until(pt_film* film, const pt_scene* scene, uint32_t first_pa
         if (!film || !scene || !out) fail(PT_ERR_INVALID, "pt_film_render_until: null argument");
         if (!film->has_profile) fail(PT_ERR_INVALID, "pt_film_render_until: a film made from planes has no profile to render with");
         if (film->windowed) fail(PT_ERR_INVALID, "pt_film_render_until: a windowed film takes windows only (pt_film_render_until_windowed)");
+        film_refuse_shard("pt_film_render_until", film);
         film_refuse_non_uniform("pt_film_render_until", film);
         film_check_noise_args("pt_film_render_until", lum_floor, target);
         if (first_pass_samples < 2u) fail(PT_ERR_INVALID, "pt_film_render_until: first_pass_samples must be >= 2 (a sample variance needs two)");
@@ -5449,11 +5668,14 @@ int pt_film_add_tile_planes(pt_film* film, uint32_t samples, const uint32_t* til
                             const float* moments) {
     return guarded([&] {
         if (!film || !accum || !moments) fail(PT_ERR_INVALID, "pt_film_add_tile_planes: null argument");
-        const TileMap tm = film_check_tile_pass("pt_film_add_tile_planes", film, samples, tiles, n_tiles);
+        const TileMap listed = film_check_tile_pass("pt_film_add_tile_planes", film, samples, tiles, n_tiles);
+        const TileMap tm = film->packed ? film_own_map("pt_film_add_tile_planes", *film, film_own_tiles(*film, listed.tiles)) : listed;
         HIP_CHECK(hipSetDevice(film->device));
-        HIP_CHECK(hipMemcpy(film->pass_accum, accum, tm.n_local * 12u, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(film->pass_moments, moments, tm.n_local * 8u, hipMemcpyHostToDevice));
-        film_merge_tiles(*film, tm, samples);
+        if (tm.n_local) {
+            HIP_CHECK(hipMemcpy(film->pass_accum, accum, tm.n_local * 12u, hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(film->pass_moments, moments, tm.n_local * 8u, hipMemcpyHostToDevice));
+        }
+        film_merge_tiles(*film, tm, listed.tiles, samples);
     });
 }
 
@@ -5517,6 +5739,7 @@ int pt_film_render_until_adaptive(pt_film* film, const pt_scene* scene, const pt
     return guarded([&] {
         const char* who = "pt_film_render_until_adaptive";
         if (!film || !scene || !params || !out) fail(PT_ERR_INVALID, "%s: null argument", who);
+        film_refuse_shard(who, film);
         film_check_adaptive(who, film, scene, params);
         film_adaptive_loop(film, scene, params, on_pass, user, out,
                            [&](pt_film_tile_stats& st, float* sums) {
@@ -5581,8 +5804,11 @@ int pt_film_render_until_windowed(pt_film* film, const pt_scene* scene, const pt
     return guarded([&] {
         const char* who = "pt_film_render_until_windowed";
         if (!film || !scene || !params || !out) fail(PT_ERR_INVALID, "%s: null argument", who);
+        film_refuse_shard(who, film);
         film_check_window_params(who, film, scene, params);
-        film_window_loop(film, scene, params, on_pass, user, out);
+        film_window_loop(film, scene, params, on_pass, user, out, [&](pt_film_tile_stats& st, float* sums) {
+            film_tile_noise(*film, params->lum_floor, params->target, st, nullptr, sums, nullptr);
+        });
     });
 }
 
@@ -5593,14 +5819,10 @@ int pt_film_window_kernel_times(pt_film* film, uint32_t reps, float* ms_gather, 
         film_check_tiled(who, film);
         if (film->uniform()) fail(PT_ERR_INVALID, "%s: the film has taken no tile window", who);
         HIP_CHECK(hipSetDevice(film->device));
-        const uint32_t n_tiles = film_n_tiles(*film);
-        std::vector<uint32_t> all(n_tiles);
-        for (uint32_t k = 0; k < n_tiles; ++k) all[k] = k;
-        const TileMap tm = make_tile_list_map(who, film->profile, film->opts, all.data(), n_tiles);
-        std::vector<uint32_t> table(tm.offsets);
-        table.insert(table.end(), tm.tiles.begin(), tm.tiles.end());
-        HIP_CHECK(hipMemcpy(film->table.p, table.data(), table.size() * 4u, hipMemcpyHostToDevice));
-        const FilmTiling T = film_tiling(*film);
+        // every tile the film holds (a shard film: its own, through the packed variants)
+        const TileMap tm = film_own_map(who, *film, film_own_tiles(*film, film_all_tiles(*film)));
+        const uint32_t n_tiles = tm.n_local_tiles;
+        film_upload_table(*film, tm);
         hipEvent_t e0 = nullptr, e1 = nullptr;
         struct Free {
             hipEvent_t &a, &b;
@@ -5615,15 +5837,12 @@ int pt_film_window_kernel_times(pt_film* film, uint32_t reps, float* ms_gather, 
         // the film's planes and counts as they were
         for (uint32_t r = 0; r < reps; ++r) {
             HIP_CHECK(hipEventRecord(e0, 0));
-            hipLaunchKernelGGL(k_film_gather_tiles, dim3(n_tiles), dim3(256), 0, 0, (const float*)film->accum, (const float2*)film->moments,
-                               (const uint32_t*)film->table.p, n_tiles, T, film->pass_accum, (float2*)film->pass_moments);
+            film_launch_gather_tiles(*film, n_tiles, film->pass_accum, film->pass_moments);
             HIP_CHECK(hipEventRecord(e1, 0));
             HIP_CHECK(hipEventSynchronize(e1));
             HIP_CHECK(hipEventElapsedTime(&ms_gather[r], e0, e1));
             HIP_CHECK(hipEventRecord(e0, 0));
-            hipLaunchKernelGGL(k_film_scatter_tiles, dim3(n_tiles), dim3(256), 0, 0, (const float*)film->pass_accum,
-                               (const float2*)film->pass_moments, (const uint32_t*)film->table.p, n_tiles, T, film->accum,
-                               (float2*)film->moments, film->count, 0u);
+            film_launch_scatter_tiles(*film, n_tiles, film->pass_accum, film->pass_moments, 0u);
             HIP_CHECK(hipEventRecord(e1, 0));
             HIP_CHECK(hipEventSynchronize(e1));
             HIP_CHECK(hipEventElapsedTime(&ms_scatter[r], e0, e1));
@@ -5650,16 +5869,12 @@ int pt_film_adaptive_kernel_times(pt_film* film, float lum_floor, int tonemap, u
         }
         // the merge of a pass of zeros and zero samples over every tile: every load, addition and store of a real pass, and the
         // film's planes as they were (x + 0 = x for every x a sum of radiances can be)
-        std::vector<uint32_t> all(n_tiles);
-        for (uint32_t k = 0; k < n_tiles; ++k) all[k] = k;
-        const TileMap tm = make_tile_list_map(who, film->profile, film->opts, all.data(), n_tiles);
-        std::vector<uint32_t> table(tm.offsets);
-        table.insert(table.end(), tm.tiles.begin(), tm.tiles.end());
-        HIP_CHECK(hipMemcpy(film->table.p, table.data(), table.size() * 4u, hipMemcpyHostToDevice));
+        // (every tile the film holds: a shard film's own, through the packed variants)
+        const TileMap tm = film_own_map(who, *film, film_own_tiles(*film, film_all_tiles(*film)));
+        film_upload_table(*film, tm);
         HIP_CHECK(hipMemset(film->pass_accum, 0, film->stride_a * sizeof(float)));
         HIP_CHECK(hipMemset(film->pass_moments, 0, film->stride_m * sizeof(float)));
         Staged<uint8_t> d_rgb(nullptr, (size_t)film->n_local * 3u);
-        const FilmTiling T = film_tiling(*film);
         hipEvent_t e0 = nullptr, e1 = nullptr;
         struct Free {
             hipEvent_t &a, &b;
@@ -5674,13 +5889,9 @@ int pt_film_adaptive_kernel_times(pt_film* film, float lum_floor, int tonemap, u
             const uint32_t which = r / reps;
             HIP_CHECK(hipEventRecord(e0, 0));
             if (which == 0)
-                hipLaunchKernelGGL(k_film_merge_tiles, dim3(n_tiles), dim3(256), 0, 0, (const float*)film->pass_accum,
-                                   (const float2*)film->pass_moments, (const uint32_t*)film->table.p, n_tiles, T, film->accum,
-                                   (float2*)film->moments, film->count, 0u);
+                film_launch_merge_tiles(*film, tm.n_local_tiles, film->pass_accum, film->pass_moments, 0u);
             else if (which == 1)
-                hipLaunchKernelGGL(k_film_tile_noise, dim3(n_tiles), dim3(256), 0, 0, (const float2*)film->moments,
-                                   (const uint32_t*)film->count, (uint32_t)film->samples, T, lum_floor, film->err, film->tile_sum,
-                                   film->tile_sum + n_tiles);
+                film_launch_tile_noise(*film, lum_floor, film->err, film->tile_sum, film->tile_sum + n_tiles);
             else
                 hipLaunchKernelGGL(k_film_post_counts, dim3(((uint32_t)film->n_local + 255u) / 256u), dim3(256), 0, 0,
                                    (const float*)film->accum, (const uint32_t*)film->count, d_rgb.d, (uint32_t)film->n_local, tonemap);
@@ -5692,9 +5903,114 @@ int pt_film_adaptive_kernel_times(pt_film* film, float lum_floor, int tonemap, u
     });
 }
 
+// ---- sharded films
+int pt_film_create_shard(int device, const pt_profile* profile, const pt_opts* opts, uint32_t windowed, pt_film** out) {
+    if (windowed > 1u) return guarded([&] { fail(PT_ERR_INVALID, "pt_film_create_shard: windowed must be 0 or 1"); });
+    const int rc = windowed ? pt_film_create_windowed(device, profile, opts, out) : pt_film_create(device, profile, opts, out);
+    if (rc != PT_OK) return rc;
+    const int rc_shard = guarded([&] {
+        pt_film& f = **out;
+        f.shard = true;
+        f.packed = f.opts.shard_count > 1;
+        if (!f.packed) return;
+        const TileMap tm = make_tile_map(f.profile, f.opts, f.opts.shard_rank);
+        f.base_of.assign(film_n_tiles(f), (uint32_t)FILM_NOT_OWNED);
+        for (uint32_t lt = 0; lt < tm.n_local_tiles; ++lt) f.base_of[tm.tiles[lt]] = tm.offsets[lt];
+        HIP_CHECK(hipSetDevice(f.device));
+        f.base_dev.ensure(f.base_of.size() * 4u);
+        f.bytes_adaptive += f.base_dev.bytes;
+        HIP_CHECK(hipMemcpy(f.base_dev.p, f.base_of.data(), f.base_of.size() * 4u, hipMemcpyHostToDevice));
+    });
+    if (rc_shard != PT_OK) {
+        delete *out;
+        *out = nullptr;
+    }
+    return rc_shard;
+}
+
+int pt_film_get_shard_info(const pt_film* film, pt_film_shard_info* out) {
+    return guarded([&] {
+        if (!film || !out) fail(PT_ERR_INVALID, "pt_film_get_shard_info: null argument");
+        memset(out, 0, sizeof *out);
+        out->shard = film->shard ? 1u : 0u;
+        out->rank = film->opts.shard_rank;
+        out->count = film->has_profile ? film->opts.shard_count : 0u;
+        if (!film->has_profile) return;
+        out->n_tiles = film_n_tiles(*film);
+        out->own_tiles = make_tile_map(film->profile, film->opts, film->opts.shard_rank).n_local_tiles;
+        out->n_pixels = (uint64_t)film->profile.width * film->profile.height;
+    });
+}
+
+int pt_film_shard_tile_noise(const pt_film* film, float lum_floor, float* tile_sum, float* tile_max, float* err_host) {
+    return guarded([&] {
+        if (!film || !tile_sum || !tile_max) fail(PT_ERR_INVALID, "pt_film_shard_tile_noise: null argument");
+        film_shard_tile_noise(*film, lum_floor, tile_sum, tile_max, err_host);
+    });
+}
+
+int pt_film_tile_stats_from_sums(const pt_film* film, const float* tile_sum, double target, pt_film_tile_stats* out) {
+    return guarded([&] {
+        const char* who = "pt_film_tile_stats_from_sums";
+        if (!film || !tile_sum || !out) fail(PT_ERR_INVALID, "%s: null argument", who);
+        if (!film->has_profile) fail(PT_ERR_INVALID, "%s: a film made from planes has no tiling", who);
+        film_check_noise_args(who, 1.f, target);
+        pt_film_tile_stats st{};
+        film_tile_stats(*film, std::vector<float>(tile_sum, tile_sum + film_n_tiles(*film)), target, st);
+        *out = st;
+    });
+}
+
+int pt_film_select_tiles(const pt_film* film, const float* tile_sum, double target, uint32_t dilate, uint32_t* tiles, uint32_t* n_out) {
+    return guarded([&] {
+        const char* who = "pt_film_select_tiles";
+        if (!film || !tile_sum || !tiles || !n_out) fail(PT_ERR_INVALID, "%s: null argument", who);
+        if (!film->has_profile) fail(PT_ERR_INVALID, "%s: a film made from planes has no tiling", who);
+        film_check_noise_args(who, 1.f, target);
+        if (dilate > 1u) fail(PT_ERR_INVALID, "%s: dilate must be 0 or 1", who);
+        std::vector<uint32_t> active;
+        film_select_active(film_tiling(*film), std::vector<float>(tile_sum, tile_sum + film_n_tiles(*film)), target, dilate, active);
+        std::copy(active.begin(), active.end(), tiles);
+        *n_out = (uint32_t)active.size();
+    });
+}
+
+int pt_film_render_until_adaptive_sharded(pt_film* film, const pt_scene* scene, const pt_film_adaptive_params* params,
+                                          pt_film_exchange_fn exchange, void* exchange_user, pt_film_pass_fn on_pass, void* user,
+                                          pt_film_tile_stats* out) {
+    return guarded([&] {
+        const char* who = "pt_film_render_until_adaptive_sharded";
+        if (!film || !scene || !params || !out) fail(PT_ERR_INVALID, "%s: null argument", who);
+        film_check_sharded_loop(who, film, exchange);
+        film_check_adaptive(who, film, scene, params);
+        film_adaptive_loop(film, scene, params, on_pass, user, out,
+                           ShardNoise{who, film, params->lum_floor, params->target, exchange, exchange_user});
+    });
+}
+
+int pt_film_render_until_windowed_sharded(pt_film* film, const pt_scene* scene, const pt_film_window_params* params,
+                                          pt_film_exchange_fn exchange, void* exchange_user, pt_film_pass_fn on_pass, void* user,
+                                          pt_film_tile_stats* out) {
+    return guarded([&] {
+        const char* who = "pt_film_render_until_windowed_sharded";
+        if (!film || !scene || !params || !out) fail(PT_ERR_INVALID, "%s: null argument", who);
+        film_check_sharded_loop(who, film, exchange);
+        film_check_window_params(who, film, scene, params);
+        film_window_loop(film, scene, params, on_pass, user, out,
+                         ShardNoise{who, film, params->lum_floor, params->target, exchange, exchange_user});
+    });
+}
+
+int pt_film_assemble(pt_film* whole, const pt_film* const* shards, uint32_t n) {
+    return guarded([&] {
+        if (!whole) fail(PT_ERR_INVALID, "pt_film_assemble: null argument");
+        film_assemble(*whole, shards, n);
+    });
+}
+
 // ---- the film filter
 uint64_t pt_film_denoise_scratch_bytes(const pt_film* film) {
-    if (!film || !film->has_profile || film->opts.shard_count > 1) return 0;
+    if (!film || !film->has_profile || film->opts.shard_count > 1 || film->shard) return 0;
     return fdn_scratch_layout(*film).total;
 }
 
@@ -5743,6 +6059,7 @@ int pt_film_tile_reduce_device(const pt_film* film, const void* d_err, void* d_t
         const char* who = "pt_film_tile_reduce_device";
         if (!film || !d_err || !d_tile_sum || !d_tile_max) fail(PT_ERR_INVALID, "%s: null argument", who);
         film_check_tiled(who, film);
+        film_refuse_shard(who, film);
         HIP_CHECK(hipSetDevice(film->device));
         fdn_tile_reduce_launch(*film, (const float*)d_err, (float*)d_tile_sum, (float*)d_tile_max, (hipStream_t)hip_stream);
     });
@@ -5777,6 +6094,7 @@ int pt_film_render_until_filtered(pt_film* film, const pt_scene* scene, const pt
         const char* who = "pt_film_render_until_filtered";
         if (!film || !scene || !params || !out) fail(PT_ERR_INVALID, "%s: null argument", who);
         const pt_film_adaptive_params& a = params->adaptive;
+        film_refuse_shard(who, film);
         film_check_adaptive(who, film, scene, &a);
         dnv_check(who, &params->filter, film->profile.width, film->profile.height, 2u);
         // A film that is measured as it stands - it has its uniform samples, or no pass fits the budget - must pass the filter's
@@ -6208,6 +6526,29 @@ int pt_render_gathered(const pt_scene* scene, pt_comm* comm, const pt_profile* p
         if (rc != PT_OK) throw GpuError{rc, g_err};
         HIP_CHECK(hipDeviceSynchronize());
         if (rgb8_frame) d_image.fetch(rgb8_frame, npix * 3);
+    });
+}
+
+int pt_film_exchange_comm(float* tile_sum, float* tile_max, uint32_t n_tiles, void* user) {
+    return guarded([&] {
+        pt_comm* comm = (pt_comm*)user;
+        if (!comm || !tile_sum || !tile_max || !n_tiles) fail(PT_ERR_INVALID, "pt_film_exchange_comm: null argument");
+        HIP_CHECK(hipSetDevice(comm->device));
+        // one exchange step: every rank contributes its two arrays; an entry's value is its owner's, every other rank's is
+        // +0.f, and errors are not negative - so the largest of an entry's values is the owner's, bit for bit
+        const size_t n = 2u * (size_t)n_tiles;
+        std::vector<float> mine(tile_sum, tile_sum + n_tiles), all(n * (size_t)comm->size);
+        mine.insert(mine.end(), tile_max, tile_max + n_tiles);
+        Staged<float> d_mine(mine.data(), n), d_all(nullptr, all.size());
+        RCCL_CHECK(rccl().AllGather(d_mine.d, d_all.d, n * sizeof(float), 0 /* ncclChar */, comm->comm, nullptr));
+        HIP_CHECK(hipDeviceSynchronize());
+        d_all.fetch(all.data(), all.size());
+        for (size_t i = 0; i < n; ++i) {
+            float v = all[i];
+            for (int r = 1; r < comm->size; ++r)
+                if (all[(size_t)r * n + i] > v) v = all[(size_t)r * n + i];
+            (i < n_tiles ? tile_sum[i] : tile_max[i - n_tiles]) = v;
+        }
     });
 }
 

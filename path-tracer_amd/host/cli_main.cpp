@@ -8,7 +8,8 @@
 //                               [--adaptive [--adaptive-tile <N>] [--uniform-samples <U>] [--adaptive-dilate <0|1>]
 //                                [--sample-map <FILE.png>]]
 //                               [--film-denoise <plain|variance> [--filtered-target]]
-//                               [--window-samples <W>]]
+//                               [--window-samples <W>]
+//                               [--film-devices <A,B,..>]]
 //       env OUTPUT (default render.png), env PROFILE
 //   path-tracer convert <INPUT> <OUTPUT>      (glTF 2.0 -> ISF, host/gltf_convert.cpp)
 //
@@ -32,7 +33,11 @@
 // --filtered-target (with --adaptive --film-denoise variance: pt_film_render_until_filtered - T is met by the filtered error),
 // --window-samples W (with --noise-target: a windowed film, pt_film_render_until_windowed - windows of W samples of ONE
 // enumeration of N = --max-samples samples, so the frame is a prefix of the render with samples = N and, run to its budget,
-// that render byte for byte; T may be 0 here; --min-samples is refused, the first window has W samples).
+// that render byte for byte; T may be 0 here; --min-samples is refused, the first window has W samples),
+// --film-devices A,B,.. (with --noise-target and --adaptive and/or --window-samples: the film is held by one shard film per entry
+// - pt_film_create_shard, one host thread, scene and shard film each; the sharded loops exchange their tile noise through a
+// barrier between the threads and take the same passes as the one-device loop; pt_film_assemble then makes the whole film on
+// the first listed device and everything after the loop - resolve, filter, maps, PNG - runs on it unchanged: the same bytes).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -99,6 +104,9 @@ void usage_render(FILE* f) {
           "                           N = --max-samples samples (the active tiles only, with --adaptive), so the frame is a prefix of\n"
           "                           the render with samples = N, and exactly that render when it runs to its budget; T may be 0\n"
           "                           [>= 2; not with --min-samples or --filtered-target]\n"
+          "      --film-devices <A,B,..>  With --noise-target and --adaptive and/or --window-samples: the film's tiles are shared by one\n"
+          "                           shard film per listed device (repeats allowed), the loop runs on all of them in lock-step and\n"
+          "                           the whole film is assembled on the first; the output is the one-device run's, byte for byte\n"
           "      --filtered-target    With --adaptive --film-denoise variance: T is met by the error of the FILTERED image - tiles\n"
           "                           are selected by the variance the filter leaves; --noise-map then shows that error\n"
           "  -h, --help               Print help\n",
@@ -216,7 +224,8 @@ int run_render(int argc, char** argv) {
     uint32_t window_samples = 0;
     std::string noise_target_text;
     int device = 0;
-    std::vector<int> devices;
+    std::vector<int> devices, film_devices;
+    bool have_film_devices = false;
     for (int i = 0; i < argc; ++i) {
         std::string a = argv[i];
         auto value = [&](const char* name) -> std::string {
@@ -309,6 +318,19 @@ int run_render(int argc, char** argv) {
                 devices.push_back(atoi(list.substr(p, q - p).c_str()));
                 p = q + 1;
             }
+        } else if (a == "--film-devices" || a.rfind("--film-devices=", 0) == 0) {
+            std::string list = value("--film-devices <A,B,..>");
+            film_devices.clear();
+            have_film_devices = true;
+            for (size_t p = 0; p <= list.size();) {
+                size_t q = list.find(',', p);
+                if (q == std::string::npos) q = list.size();
+                const std::string item = list.substr(p, q - p);
+                if (item.empty() || item.size() > 4 || item.find_first_not_of("0123456789") != std::string::npos)
+                    die("error: invalid value '" + list + "' for '--film-devices <A,B,..>': a list of device ordinals expected");
+                film_devices.push_back(atoi(item.c_str()));
+                p = q + 1;
+            }
         } else if (a == "--device" || a.rfind("--device=", 0) == 0) device = atoi(value("--device <N>").c_str());
         else if (a.size() > 1 && a[0] == '-' && a != "-")
             die("error: unexpected argument '" + a + "' found\n\nUsage: path-tracer render [OPTIONS] <INPUT>");
@@ -328,6 +350,21 @@ int run_render(int argc, char** argv) {
         }
     }
 
+    if (have_film_devices) {
+        auto with = [](const char* other, const char* why) {
+            die(std::string("error: the argument '--film-devices <A,B,..>' cannot be used with '") + other + "' (" + why + ")");
+        };
+        if (!have_noise_target) die("error: '--film-devices <A,B,..>' needs '--noise-target <T>'");
+        if (!adaptive && !have_window_samples)
+            die("error: '--film-devices <A,B,..>' needs '--adaptive' or '--window-samples <W>' (a sharded film is measured tile by tile)");
+        if (!devices.empty()) with("--devices <A,B,..>", "one list of devices per run");
+        if (filtered_target) with("--filtered-target", "the filter needs the whole image in every pass");
+        if (denoise) with("--denoise", "the finished film is filtered by '--film-denoise <plain|variance>'");
+        if (light_mixer) with("--light-mixer", "mixed frames have no samples to add to");
+        if (have_camera_path) with("--camera-path <CAMERAS>", "a sharded film renders one frame");
+        if (have_keyframes) with("--keyframes <FRAMES>", "a sharded film renders one frame");
+        device = film_devices[0];   // the whole film is assembled, resolved and filtered there
+    }
     if (denoise_iterations >= 0 && !denoise && film_denoise.empty()) die("error: '--denoise-iterations <N>' needs '--denoise'");
     if (denoise_variance && !denoise) die("error: '--denoise-variance' needs '--denoise'");
     if (denoise && devices.size() > 1)
@@ -684,11 +721,124 @@ int run_render(int argc, char** argv) {
         if (pth_png_write_rgb8(name.c_str(), profile.width, profile.height, grey.data()) != PT_OK) die(pth_last_error());
     };
     auto to_grey = [](float v) { return (uint8_t)(!(v == v) || v <= 0.f ? 0 : (v >= 255.f ? 255 : (uint8_t)v)); };
+    // --film-devices: one thread, scene and shard film per entry, the host work done once (pt_prep).  Two phases, as with
+    // --devices: every worker makes its scene and its shard film first, and the loop - whose exchange is a barrier between the
+    // workers - is entered only if ALL of them succeeded.  A failure inside the loop (the peers may be waiting in the barrier)
+    // ends the process with the message and exit code 2.  Then the shards are assembled into `film`.
+    struct FilmExchange {
+        std::mutex m;
+        std::condition_variable cv;
+        uint32_t n = 0, arrived = 0, generation = 0;
+        std::vector<float> acc_sum, acc_max, out_sum, out_max;
+        // every entry is its owner's value or +0.f, and errors are not negative: the largest is the owner's, bit for bit
+        static int call(float* tile_sum, float* tile_max, uint32_t n_tiles, void* user) {
+            FilmExchange& x = *(FilmExchange*)user;
+            std::unique_lock<std::mutex> lock(x.m);
+            if (x.arrived == 0) {
+                x.acc_sum.assign(n_tiles, 0.f);
+                x.acc_max.assign(n_tiles, 0.f);
+            }
+            if (x.acc_sum.size() != n_tiles) return 1;
+            for (uint32_t i = 0; i < n_tiles; ++i) {
+                if (tile_sum[i] > x.acc_sum[i]) x.acc_sum[i] = tile_sum[i];
+                if (tile_max[i] > x.acc_max[i]) x.acc_max[i] = tile_max[i];
+            }
+            if (++x.arrived == x.n) {
+                x.out_sum = x.acc_sum;
+                x.out_max = x.acc_max;
+                x.arrived = 0;
+                ++x.generation;
+                x.cv.notify_all();
+            } else {
+                const uint32_t g = x.generation;
+                x.cv.wait(lock, [&] { return x.generation != g; });
+            }
+            memcpy(tile_sum, x.out_sum.data(), n_tiles * sizeof(float));
+            memcpy(tile_max, x.out_max.data(), n_tiles * sizeof(float));
+            return 0;
+        }
+    };
+    auto render_film_sharded = [&](pt_film_tile_stats& tiles) {
+        const uint32_t n = (uint32_t)film_devices.size();
+        pt_prep* prep = nullptr;
+        if (pt_prep_create(pth_scene_desc(hscene), &prep) != PT_OK) die(pt_last_error());
+        std::vector<pt_film*> shards(n, nullptr);
+        std::vector<std::string> error(n);
+        std::vector<pt_film_tile_stats> outs(n);
+        FilmExchange exchange;
+        exchange.n = n;
+        std::mutex bar_mutex;
+        std::condition_variable bar_cv;
+        uint32_t arrived = 0, failed = 0;
+        auto worker = [&](uint32_t k) {
+            pt_scene* sc = nullptr;
+            auto check = [&](int rc) {   // (the message is thread-local: read it on this thread)
+                if (rc != PT_OK && error[k].empty()) error[k] = pt_last_error();
+                return rc == PT_OK;
+            };
+            pt_opts o = film_opts;
+            o.device = film_devices[k];
+            o.shard_rank = k;
+            o.shard_count = n;
+            o.progress = nullptr;
+            o.preview = nullptr;
+            const bool up = check(pt_scene_create_from_prep(prep, film_devices[k], &sc)) &&
+                            check(pt_film_create_shard(film_devices[k], &film_profile, &o, have_window_samples ? 1u : 0u, &shards[k]));
+            {   // barrier: all scenes and shard films are resident, or nobody enters the loop
+                std::unique_lock<std::mutex> lock(bar_mutex);
+                if (!up) ++failed;
+                if (++arrived == n) bar_cv.notify_all();
+                else bar_cv.wait(lock, [&] { return arrived == n; });
+            }
+            if (up && failed == 0) {
+                AdaptivePassCtx ctx{viewer && k == 0, shards[k]};   // (every rank sees the same passes: rank 0 prints them)
+                int rc;
+                if (have_window_samples) {
+                    pt_film_window_params wp;
+                    pt_film_window_params_default(&wp);
+                    wp.target = noise_target;
+                    wp.window_samples = window_samples;
+                    wp.adaptive = adaptive ? 1u : 0u;
+                    if (have_uniform_samples) wp.uniform_samples = uniform_samples;
+                    if (have_adaptive_dilate) wp.dilate = adaptive_dilate;
+                    rc = pt_film_render_until_windowed_sharded(shards[k], sc, &wp, FilmExchange::call, &exchange, on_adaptive_pass, &ctx, &outs[k]);
+                } else {
+                    pt_film_adaptive_params ap;
+                    pt_film_adaptive_params_default(&ap);
+                    ap.target = noise_target;
+                    ap.first_pass_samples = min_samples;
+                    ap.max_samples = max_samples;
+                    if (have_uniform_samples) ap.uniform_samples = uniform_samples;
+                    if (have_adaptive_dilate) ap.dilate = adaptive_dilate;
+                    rc = pt_film_render_until_adaptive_sharded(shards[k], sc, &ap, FilmExchange::call, &exchange, on_adaptive_pass, &ctx, &outs[k]);
+                }
+                if (!check(rc)) {
+                    fprintf(stderr, "Error: %s\n", error[k].c_str());   // (the peers may be inside the exchange: do not join them)
+                    fflush(stderr);
+                    _exit(2);
+                }
+            }
+            if (sc) pt_scene_destroy(sc);
+        };
+        std::vector<std::thread> threads;
+        for (uint32_t k = 0; k < n; ++k) threads.emplace_back(worker, k);
+        for (auto& t : threads) t.join();
+        pt_prep_destroy(prep);
+        for (uint32_t k = 0; k < n; ++k)
+            if (!error[k].empty()) die(error[k]);
+        if (pt_film_assemble(film, shards.data(), n) != PT_OK) die(pt_last_error());
+        for (pt_film* s : shards) pt_film_destroy(s);
+        tiles = outs[0];
+    };
     auto render_film = [&](size_t f) {
         if (f > 0 && pt_film_reset(film) != PT_OK) die(pt_last_error());
         pt_film_noise_stats noise{};
         pt_film_tile_stats tiles{};
-        if (have_window_samples) {
+        if (have_film_devices) {
+            render_film_sharded(tiles);
+            noise.mean_error = tiles.mean_error;
+            noise.converged = tiles.converged;
+        } else if (have_window_samples) {
             pt_film_window_params wp;
             pt_film_window_params_default(&wp);
             wp.target = noise_target;
@@ -837,11 +987,12 @@ int run_render(int argc, char** argv) {
                 // render = pt_render (kernels + the copy back); png = the output file
                 "{\"load_s\": %.3f, \"build_s\": %.3f, \"kd_build_s\": %.3f, \"grid_build_s\": %.3f, \"upload_s\": %.3f, "
                 "\"render_s\": %.3f, \"kernel_ms\": %.3f, \"png_s\": %.3f, \"total_s\": %.3f, \"msamples_per_s\": %.2f, "
-                "\"prims\": %llu, \"kd_nodes\": %llu, \"leaf_refs\": %llu, \"cam_grid_res\": %u, \"light_grids\": %u}\n",
+                "\"prims\": %llu, \"kd_nodes\": %llu, \"leaf_refs\": %llu, \"cam_grid_res\": %u, \"light_grids\": %u%s}\n",
                 sec(t0, t1), sec(t1, t2), (double)info.kd_build_seconds, (double)info.grid_build_seconds, (double)info.upload_seconds,
                 sec(t2, t3), (double)tm.integrate_ms, sec(t3, t4), sec(t0, t4), samples / sec(t2, t3) / 1e6,
                 (unsigned long long)info.n_prims, (unsigned long long)info.n_kd_nodes, (unsigned long long)info.n_leaf_refs,
-                info.cam_grid_res, info.light_grids);
+                info.cam_grid_res, info.light_grids,
+                have_film_devices ? (", \"film_devices\": " + std::to_string(film_devices.size())).c_str() : "");
     }
     pt_scene_destroy(scene);
     pth_scene_free(hscene);

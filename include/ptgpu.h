@@ -1082,6 +1082,17 @@ int pt_get_cont_cache_stats(const pt_scene* scene, uint64_t* bytes, uint64_t* it
  * refilled), since the scene was made.  The call waits for the device. */
 int pt_get_cont_escape_stats(const pt_scene* scene, uint64_t* fill_launches, uint64_t* fill_items, uint64_t* flagged_launches,
                              uint64_t* fallback_lanes);
+/* The lean variant of the loading bounce-0 launch (PT_B0_LEAN, default 1, read per frame).  A configuration - profile, options,
+ * chunking - whose last counted frame was a planned one in which every bounce-0 launch loaded camera hits, visibility,
+ * bounce-1 hits and continuations with the escape answers in the records, and in which no lane cast for a light, lacked a
+ * record, ran the escape test or wrote a shadow record, launches a variant of that kernel without any of that code, at more
+ * waves per SIMD (scenes without an orthographic light grid).  Any pt_scene_set_* call, a re-keyed cache or a moved mark, new
+ * or dropped escape masks, and an unplanned, counting or tile-list frame put the configuration back on the general variant
+ * until a frame has been counted clean again.  lean_launches / general_launches: the loading launches by variant;
+ * guard_trips: frames in which a lean launch met a lane it has no code for - it writes nothing for the lane and flags the
+ * frame, and the configuration's next render call fails with PT_ERR_DEVICE (never, by the rule above - a check) -, since the
+ * scene was made.  The call does not wait for the device. */
+int pt_get_b0_lean_stats(const pt_scene* scene, uint64_t* lean_launches, uint64_t* general_launches, uint64_t* guard_trips);
 /* The state words of the first `count` cached continuation records (at most pt_get_cont_cache_stats' items_cached), one
  * uint32 each: bit 0 - the record was written, bit 1 - it carries the escape test's answer, bit 2 - that answer.  A check
  * for tests.  The call waits for the device. */

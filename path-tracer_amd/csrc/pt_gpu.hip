@@ -228,8 +228,22 @@ __global__ __launch_bounds__(256) void k_assemble(const uint8_t* __restrict__ ga
 }
 
 // The counts of one chunk, gathered into one line of the frame's statistics (frame_plan, render_chunk).
-__global__ void k_wf_stats(const WfCounters* __restrict__ ctr, uint32_t levels, uint32_t* __restrict__ out) {
+// cold / lean_out (the lean bounce-0 variant's eligibility, frame_plan): the block of the bounce-1 hits' device counters and this
+// line's word behind the frame's lines - the workgroups of the loading bounce-0 launches that cast for a light ([8]) and their
+// lanes that found no continuation record ([6]) or ran the escape test themselves ([7]) since the last line was taken; [9]
+// keeps the sum that line saw.  No block: all ones, "not known".
+__global__ void k_wf_stats(const WfCounters* __restrict__ ctr, uint32_t levels, uint32_t* __restrict__ out,
+                           unsigned long long* __restrict__ cold, uint32_t* __restrict__ lean_out) {
     const uint32_t b = threadIdx.x;
+    if (b == 0) {
+        uint32_t since = 0xffffffffu;
+        if (cold) {
+            const unsigned long long sum = cold[6] + cold[7] + cold[8];
+            since = (uint32_t)min(sum - cold[9], 0xfffffffeull);
+            cold[9] = sum;
+        }
+        *lean_out = since;
+    }
     if (b >= levels) return;
     // (+ the records the bounce-0 kernel elided for the bounce-1 hit cache: the plan sizes queues, counts rays for the inline
     // rule and finds a chunk's last bounce as a frame that casts would - a plan outlives the frames that elide)
@@ -633,6 +647,14 @@ struct pt_scene {
         std::vector<uint8_t> plan_inline;
         std::vector<uint32_t> plan_last;   // per chunk of the plan: the last bounce that has a ray (later ones are not launched)
         bool plan_fresh = false, plan_failed = false;   // (failed: the device could not provide the plan's buffers)
+        // The lean bounce-0 variant (k_wf_shade_hits<2283 | 4096>).  lean: the last counted frame of the configuration was a
+        // planned one whose bounce-0 launches all loaded every cache with the escape answers in the records, and none of their
+        // lanes cast for a light, lacked a record, ran the escape test or wrote a shadow record; lean_sig: the state of the
+        // caches and masks it was counted under (lean_signature) - a frame under another state takes the general variant.
+        // stats_lean_ok, stats_sig: the same of the counts on their way.
+        bool lean = false, stats_lean_ok = false;
+        std::vector<uint64_t> lean_sig, stats_sig;
+        const uint32_t* cold_words() const { return host + (size_t)n_slots * levels * 4u; }   // one word per line, behind the lines
         ~FrameStats() {
             if (host) (void)hipHostFree(host);
             if (done) (void)hipEventDestroy(done);
@@ -736,6 +758,9 @@ struct pt_scene {
     // such launches that ran the test all the same are word 7 of hit1_unknown.  pt_get_cont_escape_stats)
     uint64_t cont_fill_generation = 0, cont_fill_mark = 0;
     uint64_t cont_fill_launches = 0, cont_fill_items = 0, cont_flagged_launches = 0;
+    // (the loading bounce-0 launches by variant - lean, k_wf_shade_hits<2283 | 4096>, and general - and the frames a lean launch
+    // flagged because it met a lane it does not contain the code for: none, ever.  pt_get_b0_lean_stats)
+    uint64_t b0_lean_launches = 0, b0_general_launches = 0, b0_lean_guard_trips = 0;
     // The closest hits of the bounce-2 rays, same key: that ray is made from the bounce-1 hit, the material there and the
     // item's words - again no light, and the Russian roulette starts behind it - so what holds for bounce 1 holds one bounce
     // later.  In use in the frames hit1_cache serves that have a bounce 2; the record, the zeroing, the prefix, the counters
@@ -2189,6 +2214,7 @@ struct QueueEnv {
     // lane of every wave slot of the device, per hardware queue: ~1.2 GB - when they are first launched, and dies if it cannot)
     double reserve_gib;
     double test_shrink;    // PT_PLAN_TEST_SHRINK, clamped to 0.01..1 (0: unset)
+    bool test_lean;        // PT_B0_LEAN_TEST_FORCE: the lean bounce-0 variant without asking whether the frame is eligible
 };
 
 QueueEnv queue_env() {
@@ -2199,6 +2225,7 @@ QueueEnv queue_env() {
     q.reserve_gib = env_num(getenv("PT_QUEUE_RESERVE_GIB"), 2.0);
     const char* shrink = getenv("PT_PLAN_TEST_SHRINK");
     q.test_shrink = shrink && *shrink ? std::min(1.0, std::max(0.01, atof(shrink))) : 0.0;
+    q.test_lean = env_bool(getenv("PT_B0_LEAN_TEST_FORCE"), false);
     return q;
 }
 
@@ -2461,6 +2488,9 @@ struct WfFrame {
     // PT_CONT_ESCAPE (read per frame): the loading launches use the escape test's recorded answer where the scene's masks are
     // those the records were stored under
     bool cont_escape = false;
+    // PT_B0_LEAN (read per frame): the loading bounce-0 launches of this frame take the lean variant (lean_frame);
+    // lean_forced: the test hook PT_B0_LEAN_TEST_FORCE - they take it whatever the counts said
+    bool lean = false, lean_forced = false;
     // PT_VIS1_FUSED (default 1), PT_HIT2_FUSED (default 0; both read per frame): the bounce-1 shade pass of a chunk whose batch has visibility bytes
     // adds the lights of known visibility itself (k_wf_shade_fused<256>); ... and, where the chunk loads its bounce-2 hits, reads
     // that plane itself too (<256 | 512>, the first switch on as well) - no k_wf_hits_load at bounce 2.  hits_next_wanted: this
@@ -2591,6 +2621,7 @@ WfFrame frame_plan(pt_scene& s, const Frame& f, const QueueEnv& qe) {
         pt_scene::FrameStats& own = *s.tile_frame_stats;
         own.pending = own.valid = own.planned = own.stats_planned = own.plan_fresh = own.plan_failed = false;
         own.stats_hit_loads = own.plan_hit_loads = 0;
+        own.lean = own.stats_lean_ok = false;
         wf.fs = &own;
         wf.inline_at.assign(p.bounces + 2, 0);
         wf.cap = wf.cap_a;
@@ -2611,12 +2642,25 @@ WfFrame frame_plan(pt_scene& s, const Frame& f, const QueueEnv& qe) {
         (void)hipGetLastError();   // (hipErrorNotReady is no error)
         if (q == hipSuccess) {
             fs->pending = false;
-            bool overflow = false;
+            bool overflow = false, guard = false;
+            // (the lean variant: a clean frame is one none of whose lines saw a cold lane or a bounce-0 shadow record)
+            bool clean = fs->planned && fs->stats_planned && fs->stats_lean_ok;
             for (uint32_t k = 0; k < fs->n_slots; ++k) {
                 overflow = overflow || fs->host[(size_t)k * fs->levels * 4 + 3] != 0u;
+                guard = guard || (fs->host[(size_t)k * fs->levels * 4 + 3] & 2u) != 0u;   // (bit 1: a lean launch met a cold lane)
+                clean = clean && fs->cold_words()[k] == 0u && fs->host[(size_t)k * fs->levels * 4 + 1] == 0u;
                 if (fs->planned && fs->stats_planned && k < fs->plan_last.size())   // (a ray at a bounce the plan did not launch)
                     for (uint32_t b = fs->plan_last[k] + 1u; b < fs->levels; ++b)
                         overflow = overflow || fs->host[((size_t)k * fs->levels + b) * 4] != 0u;
+            }
+            fs->lean = clean && !overflow;
+            fs->lean_sig = fs->stats_sig;
+            if (guard) {
+                // cannot happen (a configuration goes lean on counts that say no lane needs more): nothing was written for the lane
+                ++s.b0_lean_guard_trips;
+                fs->valid = fs->planned = false;
+                fail(PT_ERR_DEVICE, "internal error: a lean bounce-0 launch met a lane that needs the general variant; the previous "
+                                    "frame of this configuration is not to be trusted");
             }
             if (overflow) {
                 // cannot happen (the counts of a configuration do not change): a queue sized from them ran full
@@ -2733,6 +2777,9 @@ constexpr FrameCacheKind VIS_CACHE = {"PT_VIS_CACHE", "PT_VIS_CACHE_GIB", 1.0, 1
 // (zeroed AND a prefix: the memset of a new key also starts an empty prefix - frame_cache_frame resets the mark either way -
 // and, there being no device sync, every launch that reads the plane records the event too, not only those that write)
 constexpr FrameCacheKind HIT1_CACHE = {"PT_HIT1_CACHE", "PT_HIT1_CACHE_GIB", 8.0, 16u, ~0ull, true};
+#ifndef PT_B0_LEAN_DEFAULT
+#define PT_B0_LEAN_DEFAULT true   // (the lean bounce-0 variant: profiles/r21_experiments.txt)
+#endif
 #ifndef PT_CONT_ESCAPE_DEFAULT
 #define PT_CONT_ESCAPE_DEFAULT true   // (with the records refilled when the masks arrive: profiles/r20_experiments.txt item 2)
 #endif
@@ -2818,8 +2865,8 @@ void frame_caches(pt_scene& s, const Frame& f, WfFrame& wf, hipStream_t stream) 
     // (a counter block: the cache's unknown casts + the counts of the launches that read the plane themselves, pt_scene::hits_unknown)
     auto counter_block = [](DeviceBuffer& b) {
         if (b.p) return;
-        b.ensure(64);
-        HIP_CHECK(hipMemset(b.p, 0, 64));
+        b.ensure(128);   // (sixteen uint64: hit1_unknown uses ten)
+        HIP_CHECK(hipMemset(b.p, 0, 128));
     };
     {
         bool before = wf.hit_cache != nullptr, holes = false;
@@ -2900,7 +2947,7 @@ void stats_slots(pt_scene& s, const Frame& f, WfFrame& wf) {
     if (fs->n_slots != n || fs->levels != levels || !fs->host) {
         if (fs->host) (void)hipHostFree(fs->host);
         fs->host = nullptr;
-        HIP_CHECK(hipHostMalloc((void**)&fs->host, (size_t)n * levels * 16u));
+        HIP_CHECK(hipHostMalloc((void**)&fs->host, (size_t)n * levels * 16u + (size_t)n * 4u));   // (+ FrameStats::cold_words)
         fs->n_slots = n;
         fs->levels = levels;
     }
@@ -2909,8 +2956,34 @@ void stats_slots(pt_scene& s, const Frame& f, WfFrame& wf) {
     fs->stats_planned = wf.planned;
     fs->stats_hit_loads = 0;
     fs->first_item_of_slot.assign(n, 0u);
-    s.stats_dev.ensure((size_t)n * levels * 16u);
+    s.stats_dev.ensure((size_t)n * levels * 16u + (size_t)n * 4u);
     wf.stats_slots = n;
+}
+
+// The lean bounce-0 variant in this frame.  What a configuration's clean count was taken under: the keys and marks of the
+// caches the loading bounce-0 launch reads - words, camera hits, visibility, bounce-1 hits, continuations - and the masks'
+// generation.  Any scene edit drops the configuration's counts altogether (drop_frame_state), a re-key, a moved mark or new
+// masks change the signature: the frames behind it take the general variant until one of them has been counted clean again.
+// An unplanned, a counting or a detached frame takes the general variant and ends the configuration's eligibility.
+void lean_frame(pt_scene& s, const Frame& f, const QueueEnv& qe, WfFrame& wf) {
+    pt_scene::FrameStats* fs = wf.fs;
+    if (!fs) return;
+    std::vector<uint64_t> sig = {s.escape_generation};
+    for (const pt_scene::FrameCache* fc : {wf.rng_cache, wf.hit_cache, wf.vis_cache, wf.bounce_hits[1].cache, wf.cont_cache}) {
+        sig.push_back(fc ? 1u + fc->key.size() : 0u);
+        if (!fc) continue;
+        sig.insert(sig.end(), fc->key.begin(), fc->key.end());
+        sig.push_back(fc->mark);
+        sig.push_back(fc->stride);
+    }
+    const bool plain = wf.planned && !f.counting && !f.detached();
+    if (!plain) fs->lean = false;
+    wf.lean = env_bool(getenv("PT_B0_LEAN"), PT_B0_LEAN_DEFAULT) && plain && fs->lean && fs->lean_sig == sig;
+    wf.lean_forced = qe.test_lean;
+    if (wf.stats_slots) {
+        fs->stats_lean_ok = plain;
+        fs->stats_sig = std::move(sig);
+    }
 }
 
 // The side streams and the events between them, made by the first frame that needs them.
@@ -3020,6 +3093,7 @@ struct Chunk {
     uint4* cont_plane = nullptr;
     size_t cont_stride = 0;
     uint32_t cont_flags = 0;   // bit 0: the records' escape answers hold for the scene's masks (the loading variant's flag argument)
+    bool lean = false;         // the loading launch is the lean variant (k_wf_shade_hits<2283 | 4096>)
     // the scene's shadow-visibility caches of bounces 1-4, by bounce: the bytes of the chunk's sample batch, or null (k_og_shadow_vis)
     uint8_t* bounce_vis_plane[WfFrame::HIT_BOUNCES] = {};
     uint8_t* vis_plane_of(uint32_t bounce) const { return bounce < WfFrame::HIT_BOUNCES ? bounce_vis_plane[bounce] : nullptr; }
@@ -3234,7 +3308,8 @@ void shade_stage(pt_scene& s, const Frame& f, const WfFrame& wf, const Chunk& c,
         if (c.grid_mode == 3 && c.cached && c.hit_mode) {
             // GRIDX: 11 / 15 (orthographic branch) + 16 STORE / 32 LOAD + 64 VIS (LOAD only) + 128 NEXT (LOAD and VIS only)
             // + 1024 CONT_STORE (STORE, or LOAD and VIS) / 2048 CONT_LOAD (NEXT only)
-            switch ((s.grids.ortho ? 15 : 11) | c.hit_mode | (c.hit_mode == 32 && c.vis_plane ? 64 : 0) | (c.hit1_fused ? 128 : 0) | c.cont_mode) {
+            switch ((s.grids.ortho ? 15 : 11) | c.hit_mode | (c.hit_mode == 32 && c.vis_plane ? 64 : 0) | (c.hit1_fused ? 128 : 0) | c.cont_mode | (c.lean ? 4096 : 0)) {
+            case 235 | 2048 | 4096: launch_hits(std::integral_constant<int, 235 | 2048 | 4096>{}); break;
             case 27 | 1024: launch_hits(std::integral_constant<int, 27 | 1024>{}); break;
             case 31 | 1024: launch_hits(std::integral_constant<int, 31 | 1024>{}); break;
             case 107 | 1024: launch_hits(std::integral_constant<int, 107 | 1024>{}); break;
@@ -3451,6 +3526,14 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
         c.cont_flags = 1u;
         ++s.cont_flagged_launches;
     }
+    // the lean variant: a loading launch without the orthographic branch whose records answer the escape test (or a scene
+    // without masks: nobody asks), in a frame of a configuration that was counted clean; a counted frame with any other
+    // bounce-0 launch is not a clean one
+    {
+        const bool answered = c.cont_mode == 2048 && ((c.cont_flags & 1u) != 0u || !f.dev.escape);
+        c.lean = c.cont_mode == 2048 && !s.grids.ortho && ((wf.lean && answered) || wf.lean_forced);
+        if (wf.stats_slots && wf.stats_line < wf.stats_slots && !answered) wf.fs->stats_lean_ok = false;
+    }
     // the shadow visibility of bounces 1-4: indexed by the sample's slot in its batch's staging area, which any chunk of the
     // batch may hold - so the whole batch lies below the plane's stride, not the chunk alone
     for (uint32_t b = 1; b < WfFrame::HIT_BOUNCES; ++b) {
@@ -3562,6 +3645,7 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
         } else if (c.prim && c.cont_mode == 2048) {   // (no device sync before the planes are zeroed for a new key: the readers count)
             wf.cont_cache->touched(c.st_main);
             ++wf.cont_cache->counter[2];
+            ++(c.lean ? s.b0_lean_launches : s.b0_general_launches);
         }
         if (c.fused) {
             ++s.fused_launches(b);   // (by bounce: b1_fused_launches counts bounce 1's alone)
@@ -3587,7 +3671,8 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
     if (c.st_shadow != c.st_main) HIP_CHECK(hipStreamWaitEvent(c.st_main, pipe.ev_shadow, 0));
     if (wf.stats_slots && wf.stats_line < wf.stats_slots) {   // this chunk's counts: one line of the frame's statistics
         hipLaunchKernelGGL(k_wf_stats, dim3(1), dim3(64u * ((f.p.bounces + 3u + 63u) / 64u)), 0, c.st_main, (const WfCounters*)c.wctr,
-                           f.p.bounces + 3u, (uint32_t*)s.stats_dev.p + (size_t)wf.stats_line * (f.p.bounces + 3u) * 4u);
+                           f.p.bounces + 3u, (uint32_t*)s.stats_dev.p + (size_t)wf.stats_line * (f.p.bounces + 3u) * 4u,
+                           (unsigned long long*)s.hit1_unknown.p, (uint32_t*)s.stats_dev.p + (size_t)wf.stats_slots * (f.p.bounces + 3u) * 4u + wf.stats_line);
         HIP_CHECK(hipGetLastError());
         wf.fs->first_item_of_slot[wf.stats_line] = base;
         ++wf.stats_line;
@@ -3599,7 +3684,8 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
 void frame_readout(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, void* d_rgb8, hipStream_t stream) {
     const pt_profile& p = f.p;
     if (wf.stats_slots && wf.stats_line == wf.stats_slots) {
-        HIP_CHECK(hipMemcpyAsync(wf.fs->host, s.stats_dev.p, (size_t)wf.stats_slots * (p.bounces + 3u) * 16u, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipMemcpyAsync(wf.fs->host, s.stats_dev.p, (size_t)wf.stats_slots * (p.bounces + 3u) * 16u + (size_t)wf.stats_slots * 4u,
+                                 hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipEventRecord(wf.fs->done, stream));
         wf.fs->pending = true;
     }
@@ -3704,6 +3790,7 @@ void render_device(pt_scene& s, const pt_profile& p, const pt_opts* opts_in, voi
         if (!f.detached()) frame_caches(s, f, wf, stream);
         queue_buffers(s, f, qe, wf);
         stats_slots(s, f, wf);
+        lean_frame(s, f, qe, wf);
         side_streams(s, f, wf);
         wf.plan_last = (wf.planned && f.env.plan_skip) ? &wf.fs->plan_last : nullptr;
     }
@@ -6635,6 +6722,11 @@ int pt_get_cont_escape_stats(const pt_scene* scene, uint64_t* fill_launches, uin
                          {flagged_launches, scene->cont_flagged_launches}, {fallback_lanes, n[7]}}) != PT_OK)
             fail(PT_ERR_INVALID, "pt_get_cont_escape_stats: null argument");
     });
+}
+int pt_get_b0_lean_stats(const pt_scene* scene, uint64_t* lean_launches, uint64_t* general_launches, uint64_t* guard_trips) {
+    if (!scene) return PT_ERR_INVALID;
+    return cache_stats({{lean_launches, scene->b0_lean_launches}, {general_launches, scene->b0_general_launches},
+                        {guard_trips, scene->b0_lean_guard_trips}});
 }
 int pt_scene_cont_states_copy(const pt_scene* scene, uint32_t* out, uint64_t count) {
     if (!scene || (!out && count)) return PT_ERR_INVALID;

@@ -2264,8 +2264,14 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_
 #include "pt_wf_shade_body.h"
 }
 // (cont_plane: read only in this launch; not const, as the body's one name for it serves the storing variants too)
+// GRIDX | 4096, LEAN (without the orthographic branch only): the same launch for a frame that is known to need no shadow cast,
+// no escape test and no shadow record - the steady frame - with none of that compiled in (pt_wf_shade_body.h, LEAN): at
+// WF_SHADE_LEAN_WAVES waves per SIMD, 12 KiB of LDS.  The same parameters, so the same template: the bounds follow GRIDX.
+#ifndef WF_SHADE_LEAN_WAVES
+#define WF_SHADE_LEAN_WAVES 5
+#endif
 template <int GRIDX>
-__global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_shade_hits(DevScene S, WfParams W,
+__global__ __launch_bounds__(WF_SHADE_THREADS, (GRIDX & 4096) ? WF_SHADE_LEAN_WAVES : WF_SHADE_CACHED_WAVES) void k_wf_shade_hits(DevScene S, WfParams W,
                                                   const uint32_t* __restrict__ tile_offsets, const uint4* rng_planes,
                                                   uint4* __restrict__ hit_plane,
                                                   float4* __restrict__ queue_out, float4* __restrict__ shadow_q,
@@ -2276,7 +2282,8 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_
                                                   const uint4* __restrict__ next_plane, uint4* __restrict__ next_hits,
                                                   unsigned long long* __restrict__ next_ctr,
                                                   uint4* __restrict__ cont_plane, size_t cont_stride, uint32_t cont_flags) {
-    static_assert(GRIDX == (11 | 32 | 64 | 128 | 2048) || GRIDX == (15 | 32 | 64 | 128 | 2048), "LOAD, VIS, NEXT and CONT_LOAD of the cached opaque variants");
+    static_assert(GRIDX == (11 | 32 | 64 | 128 | 2048) || GRIDX == (15 | 32 | 64 | 128 | 2048) || GRIDX == (11 | 32 | 64 | 128 | 2048 | 4096),
+                  "LOAD, VIS, NEXT and CONT_LOAD of the cached opaque variants; LEAN without the orthographic branch");
     static_assert(wf_leading_args<WfShadeContLoadKernel>::scene_then_params,
                   "wf_opaque_arg: DevScene and WfParams must be the first two parameters of k_wf_shade_hits");
     constexpr bool ALPHA = false, COUNT = false, PRIMARY = true;

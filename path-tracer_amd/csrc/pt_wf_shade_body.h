@@ -45,6 +45,16 @@
     static_assert(!CONT_STORE || ((STORE || (LOAD && VIS)) && !NEXT), "the continuation is stored by the launch that runs while the bounce-1 hits are stored");
     static_assert(!CONT_LOAD || NEXT, "the continuation is loaded by the launches that read the bounce-1 hits themselves");
     static_assert(!(CONT_STORE && CONT_LOAD), "a launch stores the continuation or loads it");
+    // LEAN (k_wf_shade_hits<2283 | 4096>: the steady frame of a scene without the orthographic branch).  A frame whose caches
+    // answer everything makes no shadow cast, runs no escape test and writes no shadow record: this variant contains none of
+    // that - no og_light_blocked, no parking, no escape_proves_miss, no shadow-queue stores - and so needs neither the
+    // registers nor the LDS that hold the general variant at four waves per SIMD.  The host launches it only for a
+    // configuration whose last counted frame met no such lane (pt_gpu.hip, "lean"); a lane that would need any of it all the
+    // same - a COLD lane - writes nothing and raises bit 1 of ctr[0].overflow, which fails the configuration's next call.
+    // The records that are consumed behind the lights only (next_rec, cont_d, cont_thr: 48 of the step's 81 dense bytes per
+    // item) are fetched at the top of the step, as in the general variant, but wait in LDS, not in registers (sh_late).
+    constexpr bool LEAN = (GRIDX & 4096) != 0;
+    static_assert(!LEAN || (CONT_LOAD && !DIRL && PRIMARY), "the lean variant is a loading bounce-0 launch without the orthographic branch");
     uint4* rng_planes_out = const_cast<uint4*>(rng_planes);   // GRID == 3 writes plane 1 (nobody reads it before bounce 1)
     static_assert(GRID < 2 || PRIMARY, "the camera grid serves bounce 0");
     const bool list_pass = !PRIMARY && index_list != nullptr;
@@ -70,6 +80,9 @@
     // would stand, with its round trip, in front of the compaction's barrier)
     __shared__ uint32_t sh_cnt[NEXT ? 4 : 2][WF_SHADE_THREADS / 64];
     if (NEXT && threadIdx.x < WF_SHADE_THREADS / 64) sh_cnt[NEXT ? 3 : 0][threadIdx.x] = 0u;
+    // ([3][1], the general loading variants: set by any lane that casts for a light of unknown visibility - a word other
+    // threads write, so its zero must be there before the first of them can get that far)
+    if constexpr (CONT_LOAD && !LEAN) __syncthreads();
     __shared__ uint32_t sh_base[2];
     __shared__ uint32_t sh_oct[8][WF_SHADE_THREADS / 64], sh_oct_off[8][WF_SHADE_THREADS / 64];
     // (VIS1: what threads 0-3 counted over the launch's steps, each its own word - next-bounce records written, shadow records
@@ -84,7 +97,13 @@
     // thread - no barrier).  The accesses are volatile: a plain store would be forwarded to its load and the register kept.
     constexpr bool PARK = CACHED && !ALPHA && WF_SHADE_PARK;
     // (wf_opaque_arg reads S at offset 0 of the kernarg segment and W right behind it: the kernels below check that)
-    __shared__ uint32_t sh_park[PARK ? WF_PARK_SLOTS + (VIS ? 1u : 0u) + (NEXT ? 4u : 0u) : 1][WF_SHADE_THREADS];   // (VIS: + PK_VIS; NEXT: + PK_NEXT)
+    __shared__ uint32_t sh_park[(PARK && !LEAN) ? WF_PARK_SLOTS + (VIS ? 1u : 0u) + (NEXT ? 4u : 0u) : 1][WF_SHADE_THREADS];   // (VIS: + PK_VIS; NEXT: + PK_NEXT)
+    // (LEAN) the late records of the step, [plane][thread]: 0 next_rec, 1 cont_d, 2 cont_thr - every slot private to its thread,
+    // so no barrier; volatile, as the parking slots are: a plain store would be forwarded to its load and the registers kept
+    typedef uint32_t WfLateRec __attribute__((ext_vector_type(4)));
+    __shared__ WfLateRec sh_late[LEAN ? 3 : 1][LEAN ? WF_SHADE_THREADS : 1];
+    volatile __attribute__((address_space(3))) WfLateRec* const late = (volatile __attribute__((address_space(3))) WfLateRec*)&sh_late[0][LEAN ? threadIdx.x : 0u];
+    auto late_get = [&](uint32_t plane) -> uint4 { const WfLateRec v = late[plane * WF_SHADE_THREADS]; return make_uint4(v.x, v.y, v.z, v.w); };
     // (an LDS pointer by type: a volatile access through a generic pointer stays a flat access, one 64-bit address per slot)
     volatile __attribute__((address_space(3))) uint32_t* const park = (volatile __attribute__((address_space(3))) uint32_t*)&sh_park[0][threadIdx.x];
     auto park_u = [&](uint32_t slot, uint32_t v) { park[slot * WF_SHADE_THREADS] = v; };
@@ -128,6 +147,12 @@
         return wf_rng_float(word);
     };
     // (LOAD) the item's camera hit: a dense load that depends on nothing - its latency runs under decode_item and the ray set-up
+    // (LEAN) the three late records first: loads return in order, so when the step's last dense load - the item's words - is
+    // there, so are they, and the stores that put them into LDS (behind the ray set-up) wait for nothing of their own
+    uint4 late_next = make_uint4(0u, 0u, 0u, 0u), late_d = make_uint4(0u, 0u, 0u, 0u), late_thr = make_uint4(0u, 0u, 0u, 0u);
+    if constexpr (LEAN) {
+        if (live) late_next = next_plane[i], late_d = cont_plane[i], late_thr = cont_plane[cont_stride + i];
+    }
     uint4 cam_rec = make_uint4(0xffffffffu, 0u, 0u, 0u);
     if (LOAD && PRIMARY && live) cam_rec = hit_plane[i];
     // (VIS) the item's visibility byte, as dense and as independent: two bits per light - 0 unknown, 1 not blocked, 2 blocked
@@ -144,7 +169,9 @@
     // second read cost the launch 0.16 ms (8.29 against 8.13 ms).
     constexpr bool NEXT_WORD = NEXT && DIRL;
     uint4 next_rec = make_uint4(0u, 0u, 0u, 0u);
-    if constexpr (NEXT_WORD) {
+    if constexpr (LEAN) {
+        // (read from sh_late where it is used)
+    } else if constexpr (NEXT_WORD) {
         if (live) next_rec.x = ((const uint32_t*)next_plane)[4u * (size_t)i];
     } else if constexpr (NEXT) {
         if (live) next_rec = next_plane[i];
@@ -153,7 +180,7 @@
     // lanes whose camera record is a hit only, and with nontemporal loads: 0.04 and 0.09 ms of a 12.2 ms frame, inside the
     // spread of the runs, the second at 8 B of scratch - profiles/r19_experiments.txt item 3.)
     uint4 cont_d = make_uint4(0u, 0u, 0u, 0u), cont_thr = make_uint4(0u, 0u, 0u, 0u);
-    if constexpr (CONT_LOAD) {
+    if constexpr (CONT_LOAD && !LEAN) {
         if (live) cont_d = cont_plane[i], cont_thr = cont_plane[cont_stride + i];
     }
     if (PRIMARY && live) {  // entry i is work item i: the initial path state, built in place
@@ -165,6 +192,12 @@
             color = mk3(0.f, 0.f, 0.f);
             out_slot = (it.sample - 1u - W.P.sample_begin) * W.P.n_local + it.out_index;
             if (GRID >= 2) {   // ray_cast + alpha walk of the camera ray (mod.rs:182-205) through the camera grid
+                if constexpr (LEAN) {   // words 0 and 1 alone: the continuation is loaded, nothing draws from words 2 and 3
+                    const uint2 w01 = *(const uint2*)(rng_planes + i);
+                    float sx, sy;
+                    primary_screen(S, it.x, it.y, W.P.width, W.P.height, wf_rng_float(w01.x), wf_rng_float(w01.y), sx, sy);
+                    primary_from_screen(S, sx, sy, o, d);
+                } else
                 if (GRID == 3 && CACHED) {   // the same words, made once per item enumeration: one dense 16-byte load
                     const uint4 w03 = rng_planes[i];
                     float sx, sy;
@@ -230,6 +263,13 @@
             if (COUNT) n_new++;
         }
     }
+    if constexpr (LEAN) {   // (a lane reads its slots only where it is live and hit: those lanes stored them here)
+        if (live) {
+            late[0] = (WfLateRec){late_next.x, late_next.y, late_next.z, late_next.w};
+            late[WF_SHADE_THREADS] = (WfLateRec){late_d.x, late_d.y, late_d.z, late_d.w};
+            late[2u * WF_SHADE_THREADS] = (WfLateRec){late_thr.x, late_thr.y, late_thr.z, late_thr.w};
+        }
+    }
     if (!PRIMARY && live) {
         const float4* qr = wf_ray_rec(queue_in, i);
         const float4* qp = wf_path_rec(queue_in, W.qcap_in, i);
@@ -254,6 +294,7 @@
     }
     const uint32_t bounce = PRIMARY ? 0u : W.bounce, bounces = W.P.bounces;   // (PRIMARY: no Russian roulette code at all)
     bool to_shadow = false, survive = false;
+    bool cold = false;   // (LEAN) the lane needs what this variant does not contain
     bool inlined = false, ended_inline = false;   // (VIS1: the lights were added here; ... and the path ended for it)
     f3 term0 = mk3(0.f, 0.f, 0.f);
     Surface surf;
@@ -317,6 +358,9 @@
                     // full no LDS parking instruction is issued at all.
                     const uint32_t known = (vis >> (2u * li)) & 3u;
                     bool blocked = known == 2u;
+                    if constexpr (LEAN) {   // an unknown light: the lane is cold
+                        if (known == 0u) cold = true;
+                    } else
                     if (known == 0u) {
                         if (PARK) park_fixed(), park_3(PK_C, c), park_3(PK_COLOR, color), park_3(PK_TERM0, term0), park_u(PK_VIS, vis);
                         if (PARK && NEXT) park_u(PK_NEXT, next_rec.x), park_u(PK_NEXT + 1u, next_rec.y), park_u(PK_NEXT + 2u, next_rec.z), park_u(PK_NEXT + 3u, next_rec.w);
@@ -334,6 +378,11 @@
                             cont_d = make_uint4(again[0], again[1], again[2], again[3]);
                             again = (const volatile uint32_t*)(cont_plane + cont_stride + i);
                             cont_thr.x = again[0], cont_thr.y = again[1], cont_thr.z = again[2];
+                            // ... and leave a mark: a frame that made no such cast may take the lean variant next.  One word
+                            // of LDS per workgroup (sh_cnt[3][1]: nobody else's), added to the device's counter once, at the
+                            // end - an atomic per wave and cast on the one word made the frame that fills the visibility
+                            // plane 16 ms longer (157.9 -> 173.9 ms, profiles/r21_experiments.txt item 2)
+                            sh_cnt[NEXT ? 3 : 0][1] = 1u;
                         }
                         vis |= ((blocked ? 2u : 1u) << (2u * li)) | 0x100u;
                     }
@@ -350,7 +399,8 @@
                     if (!(rad.x == 0.f && rad.y == 0.f && rad.z == 0.f)) color = color + mul_ew(c, rad);
                 }
             } else if (!moot) {
-                to_shadow = true;
+                if constexpr (LEAN) cold = true;   // (a normal too long for the grids' margin: the lane would write a shadow record)
+                else to_shadow = true;
                 if constexpr (VIS1) {
                     // the light as k_og_shadow_vis would add it, should every live light of the record turn out known (bit 8,
                     // in the register only: one of them is not)
@@ -372,7 +422,7 @@
             }
         }
         if (COUNT && !inline_lights && !to_shadow) n_moot += S.n_lights;
-        if constexpr (VIS) {   // what this launch found out: one byte store per lane that cast; none once the plane is full
+        if constexpr (VIS && !LEAN) {   // what this launch found out: one byte store per lane that cast; none once the plane is full
             if (vis & 0x100u) vis_plane[i] = (uint8_t)vis;
         }
         bool ended = false;
@@ -381,10 +431,14 @@
             if (bounce < bounces) {   // what the storing launch computed here, bit for bit
                 next_o = surf.pos + surf.normal * 0.00001f;
                 draw += 2u;
+                if constexpr (LEAN) cont_d = late_get(1u), cont_thr = late_get(2u);   // (the thread's own slots, stored above)
                 next_d = mk3(__uint_as_float(cont_d.x), __uint_as_float(cont_d.y), __uint_as_float(cont_d.z));
                 next_thr = mk3(__uint_as_float(cont_thr.x), __uint_as_float(cont_thr.y), __uint_as_float(cont_thr.z));
                 // a hit lane without a record cannot occur below the mark: counted (next_ctr[6]; its zero throughput ends the path)
                 const bool missing = (cont_d.w & 1u) == 0u;
+                if constexpr (LEAN) {   // ... and cold
+                    if (missing) cold = true;
+                } else
                 if (wf_any(missing)) {
                     const unsigned long long m = __ballot(missing);
                     if (missing && wf_lane_rank(m) == 0u) atomicAdd(next_ctr + 6, (unsigned long long)__popcll(m));
@@ -445,6 +499,9 @@
                 } else {
                     const bool known = (cont_flags & 1u) != 0u && (cont_d.w & 2u) != 0u;
                     proven = known && (cont_d.w & 4u) != 0u;
+                    if constexpr (LEAN) {   // the test is needed and the record has no answer for these masks: cold
+                        if (!known) cold = true;
+                    } else
                     if (wf_any(!known)) {
                         if (!known) proven = escape_proves_miss(S, PT_PRIM_INDEX(h.pid), next_o, next_d);
                         // the lanes that ran the test although the launch was told the records have answers: counted
@@ -481,6 +538,16 @@
     // (below, with the other stores) IS the sample - no record, no slot, nothing for bounce 1 to read.  A to_shadow survivor
     // keeps its record whatever the cast found: the shadow kernel patches the colour and stages the miss.
     bool elided = false;
+    if constexpr (LEAN) {
+        // a cold lane writes nothing - no record, no sample, no count - and flags the frame (bit 1 of the word a full queue
+        // sets: the configuration's next call fails, pt_gpu.hip frame_plan)
+        if (cold) {
+            survive = false;
+            atomicOr(&ctr[0].overflow, 2u);
+        }
+        // (the word alone; the rest where the hit is written, behind the barriers)
+        if (survive) next_rec.x = *(volatile __attribute__((address_space(3))) uint32_t*)late;
+    }
     if constexpr (NEXT) {
         elided = survive && !to_shadow && next_rec.x == (0xffffffffu ^ WF_HIT1_FLIP);
         if (elided) survive = false;
@@ -567,6 +634,9 @@
         if (survive && !unknown) {
             const uint32_t word = next_rec.x ^ WF_HIT1_FLIP;
             ((uint32_t*)next_hits)[next_idx] = word;
+            if constexpr (LEAN) {
+                if (word != 0xffffffffu) next_rec = late_get(0u);
+            }
             if (NEXT_WORD && word != 0xffffffffu) {   // (volatile: a plain load is merged with the word's, and the record held)
                 const volatile uint32_t* rest = (const volatile uint32_t*)next_plane + 4u * (size_t)i;
                 next_rec.y = rest[1], next_rec.z = rest[2], next_rec.w = rest[3];
@@ -628,7 +698,7 @@
         }
     } else if ((NEXT || NEXT1) && elided) {   // the sample of a path whose next cast is known to miss
         wf_prestage_miss(staging, out_slot, color, next_thr, ld3(S.background));
-    } else if (live && hit && !survive) {  // no light can contribute and the path ends: the sample is complete
+    } else if (live && hit && !survive && !(LEAN && cold)) {  // no light can contribute and the path ends: the sample is complete
         float* out = staging + (size_t)out_slot * 3;
         out[0] = color.x;
         out[1] = color.y;
@@ -771,6 +841,11 @@
             atomicAdd(next_ctr + 2, (unsigned long long)sh_cnt[3][2]);
         }
         if (threadIdx.x == 0 && sh_cnt[3][0]) atomicAdd(next_ctr + 1, (unsigned long long)sh_cnt[3][0]);
+        // (CONT_LOAD) the workgroup cast for a light of unknown visibility: next_ctr[8] counts such workgroups.  (Written by the
+        // lanes that cast, in front of their step's barriers: visible to thread 1 here.)
+        if constexpr (CONT_LOAD && !LEAN) {
+            if (threadIdx.x == 1 && sh_cnt[3][1]) atomicAdd(next_ctr + 8, 1ull);
+        }
     }
     if constexpr (VIS1) {   // (threads 0-3: the words they alone wrote; next_ctr: pt_scene::hit2_unknown)
         const uint32_t mine_acc = threadIdx.x < 4u ? fused_acc[threadIdx.x] : 0u;

@@ -1272,6 +1272,70 @@ int pt_measure_copy_bandwidth(int device, uint64_t bytes, uint32_t reps, double*
 int pt_measure_gather_rate(int device, uint64_t table_bytes, uint32_t bytes_per_load, uint32_t loads_per_lane,
                            double* giga_loads_per_s);
 
+/* ------------------------------------------------------------------ */
+/* sample-coherent AOVs (no reference counterpart)          */
+/* ------------------------------------------------------------------ */
+
+/* Feature planes that are sample-coherent with the beauty frame: the pass replays, for every sample of the frame, the camera
+ * cast and the alpha walk of render_pixel (mod.rs:107-124, 182-205) - and nothing after them - and sums the features of the
+ * surfaces the walks stop at.  Every step is one f32 IEEE operation, uncontracted, in the order written.
+ *
+ * The sample record.  Pixel i (global index x + y*W), sample s = 1..N (N = profile.samples): the generator is
+ * StdRng::seed_from_u64(s + i*N); draws 0 and 1 are the jitter (r1, r2), the ray is primary_ray's; the surface is the one
+ * render_pixel shades at bounce 0: ray_cast, then the alpha walk with its draws taken from index 2 on (an entry of opacity
+ * >= 1 ends the walk, one of opacity > 0.001 ends it when its draw < opacity, and a walk that skips every entry keeps the
+ * last one; a walk of more than 14 draws goes on into ChaCha block 1).  16 f32:
+ *   [0..2]   unit shading normal: n = shading_normal; nn = (n.x*n.x + n.y*n.y) + n.z*n.z; n * (1/sqrt(nn)) when
+ *            0 < nn < inf, else 0 (the rule of pt_denoise's prep)
+ *   [3]      depth: the hit's `dist` (the sort key pt_trace_rays reports)
+ *   [4..6]   MaterialSample albedo            [7] 1.0 (coverage)
+ *   [8..10]  hit position (o + d*dist; spheres: o + d*t as Model::intersect computes it)
+ *   [11,12]  roughness (after the max(1e-4) clamp), metalness
+ *   [13]     lum(emissive) = (0.2126f*r + 0.7152f*g) + 0.0722f*b
+ *   [14]     global primitive index as int32 bits      [15] 1.0
+ * A sample without a surface: sixteen +0.0f, [14] = int32 -1.  Non-finite features propagate (outside the contract).
+ * aov_flags: PT_AOV_FIRST_ENTRY - the first list entry, no walk, no draws; PT_AOV_CENTRE - r1 = r2 = 0.5 instead of the
+ * jitter draws (the walk still draws from index 2).
+ *
+ * The pixel record, 16 f32:
+ *   [0..13]  the sum of the samples' floats 0..13 in a fixed order, a pure function of N: the samples are taken in blocks of
+ *            64 consecutive sample numbers; inside a block a missing sample is +0.0f and the 64 values are reduced by the
+ *            pairwise tree x[j] = x[2j] + x[2j+1], six levels; the total is the first block's sum, then + the next block's,
+ *            in block order (tests/aov_model.py reduce_records)
+ *   [14]     the primitive of the lowest-numbered covered sample (int32 bits, -1: none)
+ *   [15]     how many covered samples have that primitive, as a float ([15] < [7]: an edge pixel)
+ *
+ * pt_render_aov / _device: n_local x 16 f32 in the packed local order of pt_render (shard fields of opts as there: the
+ * global index goes into the seed).  Of the profile only width, height and samples are used; of opts the device, the shard
+ * fields and PT_FLAG_NO_GRIDS (the cast goes through the KD-tree instead of the camera grid: the same bits); the other flags,
+ * sample_batch and the callbacks are ignored.  The device form is asynchronous on hip_stream and allocates nothing (sharded:
+ * the scene's tile table, as pt_render_device); d_aov: 16-byte aligned.  They follow pt_scene_set_camera and the scene edits
+ * like pt_render_guides, read none of the scene's frame caches and leave its frame plan, caches and statistics untouched.
+ * pt_render_aov_samples (test hook): the sample records, N planes of n_local x 16 f32 (plane s - 1 = sample s), at most
+ * 256 MiB.  PT_ERR_INVALID before any device work: a null pointer, samples == 0, unknown flag bits, a rank without pixels,
+ * a misaligned d_aov, sample planes above 256 MiB. */
+enum { PT_AOV_FLOATS = 16, PT_AOV_FIRST_ENTRY = 1, PT_AOV_CENTRE = 2 };
+int pt_render_aov(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, uint32_t aov_flags,
+                  float* aov /* host, n_local x 16 */);
+int pt_render_aov_device(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, uint32_t aov_flags,
+                         void* d_aov, void* hip_stream);
+int pt_render_aov_samples(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, uint32_t aov_flags,
+                          float* records /* host, N x n_local x 16, <= 256 MiB */);
+
+/* Guides (PT_GUIDE_FLOATS per pixel, the layout of pt_render_guides) from pixel records r of a frame of `samples` samples.
+ * cov = r[7]; the pixel is valid iff cov > 0 and cov + cov >= (float)samples.  A valid pixel: normal = r[0..2] (left
+ * unnormalised: the filters' prep normalises it), depth = r[3] / cov, albedo = r[4..6] / (float)samples, prim = r[14].
+ * An invalid pixel is pt_render_guides' miss record: floats 0, depth -1.0f, prim -1.  The device form is asynchronous,
+ * allocates nothing and wants 16-byte aligned planes; device: HIP ordinal, -1 = current. */
+int pt_aov_guides(int device, uint64_t n_pixels, uint32_t samples, const float* aov, float* guides /* host */);
+int pt_aov_guides_device(int device, uint64_t n_pixels, uint32_t samples, const void* d_aov, void* d_guides, void* hip_stream);
+
+/* pt_render_denoised (variance = 0) / pt_render_denoised_var (variance != 0: a moments frame) with the guides of
+ * pt_render_aov + pt_aov_guides in place of pt_render_guides': frame, AOV pass, conversion and filter on one stream.  Their
+ * arguments, their rules; shard_count > 1 is PT_ERR_UNSUPPORTED. */
+int pt_render_denoised_aov(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts,
+                           const pt_denoise_params* params, int variance, uint32_t aov_flags, uint8_t* rgb8, float* color);
+
 const char* pt_last_error(void);
 const char* pt_version(void);
 

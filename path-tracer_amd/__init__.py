@@ -105,6 +105,7 @@ class Opts(C.Structure):
 
 
 PT_GUIDE_FLOATS = 8
+PT_AOV_FLOATS, PT_AOV_FIRST_ENTRY, PT_AOV_CENTRE = 16, 1, 2
 PT_DENOISE_NO_DEMODULATE = 1
 PT_DENOISE_STAGES = 10
 
@@ -367,7 +368,9 @@ GPU_SYMBOLS = ["pt_scene_create", "pt_scene_destroy", "pt_scene_set_camera", "pt
                "pt_film_render_until_windowed", "pt_film_window_kernel_times",
                "pt_film_create_shard", "pt_film_get_shard_info", "pt_film_shard_tile_noise", "pt_film_tile_stats_from_sums",
                "pt_film_select_tiles", "pt_film_render_until_adaptive_sharded", "pt_film_render_until_windowed_sharded",
-               "pt_film_exchange_comm", "pt_film_assemble"]
+               "pt_film_exchange_comm", "pt_film_assemble",
+               "pt_render_aov", "pt_render_aov_device", "pt_render_aov_samples", "pt_aov_guides", "pt_aov_guides_device",
+               "pt_render_denoised_aov"]
 
 
 def host_lib():
@@ -524,6 +527,13 @@ def gpu_lib():
         L.pt_denoise_var_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, dp, vp, vp, vp, vp, vp, vp, vp]
         L.pt_render_denoised_var.argtypes = [vp, C.POINTER(Profile), C.POINTER(Opts), dp, vp, vp]
         L.pt_denoise_var_stage_times.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, dp, vp, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "pt_render_aov"):   # (an A/B library of an earlier commit has no AOV pass)
+            L.pt_render_aov.argtypes = [vp, C.POINTER(Profile), C.POINTER(Opts), C.c_uint32, vp]
+            L.pt_render_aov_device.argtypes = [vp, C.POINTER(Profile), C.POINTER(Opts), C.c_uint32, vp, vp]
+            L.pt_render_aov_samples.argtypes = [vp, C.POINTER(Profile), C.POINTER(Opts), C.c_uint32, vp]
+            L.pt_aov_guides.argtypes = [C.c_int, C.c_uint64, C.c_uint32, vp, vp]
+            L.pt_aov_guides_device.argtypes = [C.c_int, C.c_uint64, C.c_uint32, vp, vp, vp]
+            L.pt_render_denoised_aov.argtypes = [vp, C.POINTER(Profile), C.POINTER(Opts), dp, C.c_int, C.c_uint32, vp, vp]
         if hasattr(L, "pt_lightmix_capture"):   # (an A/B library of an earlier commit has no light mixer)
             L.pt_lightmix_capture.argtypes = [vp, C.POINTER(Profile), C.POINTER(Opts), C.POINTER(vp)]
             L.pt_lightmix_create_from_planes.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, vp, vp, C.POINTER(vp)]
@@ -1148,6 +1158,43 @@ class GpuScene:
         col = np.empty((n, 3), np.float32)
         check_gpu(self.lib.pt_render_denoised_var(self.handle, C.byref(profile), C.byref(opts) if opts is not None else None,
                                                   C.byref(params) if params is not None else None, rgb.ctypes.data, col.ctypes.data))
+        return rgb, col
+
+    def render_aov(self, profile, opts=None, aov_flags=0):
+        """pt_render_aov: [n, 16] float32 pixel records (include/ptgpu.h) in the packed local order of render();
+        [:, 14].view(np.int32) is the primitive of the first covered sample."""
+        import numpy as np
+        opts = opts or Opts.make()
+        n = int(self.lib.pt_local_pixel_count(C.byref(profile), C.byref(opts)))
+        out = np.empty((n, PT_AOV_FLOATS), np.float32)
+        check_gpu(self.lib.pt_render_aov(self.handle, C.byref(profile), C.byref(opts), aov_flags, out.ctypes.data))
+        return out
+
+    def render_aov_device(self, profile, opts, d_aov, aov_flags=0, stream=0):
+        check_gpu(self.lib.pt_render_aov_device(self.handle, C.byref(profile), C.byref(opts) if opts is not None else None,
+                                                aov_flags, d_aov, stream))
+
+    def render_aov_samples(self, profile, opts=None, aov_flags=0):
+        """pt_render_aov_samples (test hook): [samples, n, 16] float32, the record of every sample of every packed pixel."""
+        import numpy as np
+        opts = opts or Opts.make()
+        n = int(self.lib.pt_local_pixel_count(C.byref(profile), C.byref(opts)))
+        if profile.samples * n * 64 > 256 << 20:
+            raise PtError(PT_ERR_INVALID, "render_aov_samples: the sample planes would exceed 256 MiB")
+        out = np.empty((profile.samples, n, PT_AOV_FLOATS), np.float32)
+        check_gpu(self.lib.pt_render_aov_samples(self.handle, C.byref(profile), C.byref(opts), aov_flags, out.ctypes.data))
+        return out
+
+    def render_denoised_aov(self, profile, params, variance=False, opts=None, aov_flags=0):
+        """pt_render_denoised_aov: render_denoised (variance: render_denoised_var) steered by the guides of the frame's own
+        samples (render_aov + aov_guides) instead of the pixel-centre guides."""
+        import numpy as np
+        n = profile.width * profile.height
+        rgb = np.empty((n, 3), np.uint8)
+        col = np.empty((n, 3), np.float32)
+        check_gpu(self.lib.pt_render_denoised_aov(self.handle, C.byref(profile), C.byref(opts) if opts is not None else None,
+                                                  C.byref(params) if params is not None else None, 1 if variance else 0,
+                                                  aov_flags, rgb.ctypes.data, col.ctypes.data))
         return rgb, col
 
     def lightmix_capture(self, profile, opts=None):
@@ -1860,6 +1907,19 @@ def denoise_var(width, height, samples, params, accum, moments, guides, device=0
                                        accum.ctypes.data, moments.ctypes.data, guides.ctypes.data, col.ctypes.data,
                                        rgb.ctypes.data))
     return col, rgb
+
+
+def aov_guides(samples, aov, device=0):
+    """pt_aov_guides on host arrays: aov [n, 16] float32 pixel records of a frame of `samples` samples (GpuScene.render_aov);
+    returns guides [n, 8] float32 in the layout of GpuScene.render_guides."""
+    import numpy as np
+    aov = np.ascontiguousarray(aov, np.float32)
+    if aov.size == 0 or aov.size % PT_AOV_FLOATS:
+        raise ValueError("aov_guides: aov must hold n * 16 floats")
+    n = aov.size // PT_AOV_FLOATS
+    guides = np.empty((n, PT_GUIDE_FLOATS), np.float32)
+    check_gpu(gpu_lib().pt_aov_guides(device, n, samples, aov.ctypes.data, guides.ctypes.data))
+    return guides
 
 
 def denoise_var_scratch_bytes(width, height):

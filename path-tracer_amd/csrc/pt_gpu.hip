@@ -17,6 +17,7 @@
 //   k_accumulate_moments, k_dnv_*  pt_variance.h: per-pixel sample moments and the variance-guided form of that filter
 //   k_film_*          pt_film.h: the progressive film - merging passes, the noise figure of its moments
 //   k_film_*_packed, k_film_import_shard   pt_film_shard.h: the tile kernels of shard films, and their way back to one device
+//   k_aov, k_aov_samples, k_aov_guides   pt_aov.h: sample-coherent feature planes (the samples' camera casts and alpha walks) and guides from them
 //   k_stream_copy     achievable-HBM yardstick of the roofline (pt_measure_copy_bandwidth)
 //   k_trace / k_trace_all / k_escape_query / k_isect / k_rng / k_math   parity-test hooks
 #include <hip/hip_runtime.h>
@@ -52,6 +53,7 @@
 #include "pt_film_denoise.h"
 #include "pt_film_window.h"
 #include "pt_film_shard.h"
+#include "pt_aov.h"
 #include "pthost.h"
 #include "../host/scene_check.h"
 
@@ -6445,6 +6447,175 @@ int pt_assemble_tiles(const pt_profile* profile, uint32_t shard_count, uint32_t 
                            (const uint8_t*)d_gathered, (uint8_t*)d_image, c.d, profile->width,
                            profile->height, on.tile_w, on.tile_h, c.tiles_x, slice_pixels, elem_bytes);
         HIP_CHECK(hipGetLastError());
+    });
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ sample-coherent AOVs (pt_aov.h)
+namespace {
+
+// What pt_render_aov* derive from their arguments; everything they refuse is refused here, before any device work.
+struct AovFrame {
+    AovParams A{};
+    TileMap tm;
+    pt_opts o{};
+    bool grid = false, alpha = false;
+};
+
+AovFrame aov_frame(const char* who, const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, uint32_t aov_flags,
+                   const void* out) {
+    if (!scene || !profile || !out) fail(PT_ERR_INVALID, "%s: null argument", who);
+    if (aov_flags & ~(uint32_t)(PT_AOV_FIRST_ENTRY | PT_AOV_CENTRE)) fail(PT_ERR_INVALID, "%s: unknown aov_flags 0x%x", who, aov_flags);
+    if ((uintptr_t)out & 15u) fail(PT_ERR_INVALID, "%s: the output must be 16-byte aligned", who);
+    AovFrame f;
+    normalise_opts(*profile, opts, f.o);
+    if (profile->samples == 0) fail(PT_ERR_INVALID, "%s: profile.samples must be > 0", who);
+    f.tm = make_tile_map(*profile, f.o, f.o.shard_rank);
+    if (f.tm.n_local == 0) fail(PT_ERR_INVALID, "%s: this rank has no pixels", who);
+    AovParams& A = f.A;
+    A.width = profile->width;
+    A.height = profile->height;
+    A.samples = profile->samples;
+    A.n_local = (uint32_t)f.tm.n_local;
+    A.flags = aov_flags;
+    while (A.log2_seg < 6u && (1u << A.log2_seg) < A.samples) ++A.log2_seg;
+    A.n_local_tiles = f.o.shard_count > 1 ? f.tm.n_local_tiles : 0u;
+    A.tile_w = f.o.tile_w;
+    A.tile_h = f.o.tile_h;
+    A.tiles_x = f.tm.tiles_x;
+    f.grid = !(f.o.flags & PT_FLAG_NO_GRIDS) && scene->dev.cam_grid.res != 0;
+    f.alpha = scene->dev.has_translucent != 0;
+    return f;
+}
+
+// The frame's tile table (sharded frames only: the scene's cached one, as pt_render_device takes it).
+const uint32_t* aov_tiles(const pt_scene* scene, const pt_profile& p, const AovFrame& f) {
+    if (f.o.shard_count <= 1) return nullptr;
+    return tile_table(render_state(scene), p, f.o, f.tm, render_env().morton);
+}
+
+void aov_launch(const pt_scene& s, const AovFrame& f, const uint32_t* d_tiles, float4* d_aov, hipStream_t stream) {
+    const uint64_t lanes = (uint64_t)f.A.n_local << f.A.log2_seg;
+    dispatch([&](auto alpha, auto grid) {
+        hipLaunchKernelGGL((k_aov<alpha, grid>), dim3((uint32_t)((lanes + 255u) / 256u)), dim3(256), 0, stream, s.dev, f.A, d_tiles, d_aov);
+    }, f.alpha, f.grid);
+    HIP_CHECK(hipGetLastError());
+}
+
+void aov_guides_check(const char* who, uint64_t n_pixels, uint32_t samples, const void* aov, const void* guides) {
+    if (!aov || !guides) fail(PT_ERR_INVALID, "%s: null argument", who);
+    if (!n_pixels || n_pixels >= (1ull << 31)) fail(PT_ERR_INVALID, "%s: n_pixels must be in 1 .. 2^31 - 1", who);
+    if (!samples) fail(PT_ERR_INVALID, "%s: samples is 0", who);
+}
+
+void aov_guides_launch(uint64_t n, uint32_t samples, const float4* d_aov, float4* d_guides, hipStream_t stream) {
+    hipLaunchKernelGGL(k_aov_guides, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, stream, d_aov, n, samples, d_guides);
+    HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" {
+
+int pt_render_aov_device(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, uint32_t aov_flags, void* d_aov,
+                         void* hip_stream) {
+    return guarded([&] {
+        const AovFrame f = aov_frame("pt_render_aov_device", scene, profile, opts, aov_flags, d_aov);
+        HIP_CHECK(hipSetDevice(scene->device));
+        aov_launch(*scene, f, aov_tiles(scene, *profile, f), (float4*)d_aov, (hipStream_t)hip_stream);
+    });
+}
+
+int pt_render_aov(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, uint32_t aov_flags, float* aov) {
+    return guarded([&] {
+        const AovFrame f = aov_frame("pt_render_aov", scene, profile, opts, aov_flags, (const void*)16);
+        if (!aov) fail(PT_ERR_INVALID, "pt_render_aov: null argument");
+        HIP_CHECK(hipSetDevice(scene->device));
+        const size_t n = f.tm.n_local;
+        Staged<float4> d_aov(nullptr, n * 4);
+        aov_launch(*scene, f, aov_tiles(scene, *profile, f), d_aov.d, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        d_aov.fetch((float4*)aov, n * 4);
+    });
+}
+
+int pt_render_aov_samples(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, uint32_t aov_flags, float* records) {
+    return guarded([&] {
+        const AovFrame f = aov_frame("pt_render_aov_samples", scene, profile, opts, aov_flags, (const void*)16);
+        if (!records) fail(PT_ERR_INVALID, "pt_render_aov_samples: null argument");
+        const uint64_t n = f.tm.n_local;
+        if ((uint64_t)profile->samples > (256ull << 20) / (n * 64u))
+            fail(PT_ERR_INVALID, "pt_render_aov_samples: %u planes of %llu pixels exceed 256 MiB", profile->samples, (unsigned long long)n);
+        HIP_CHECK(hipSetDevice(scene->device));
+        const uint64_t items = (uint64_t)profile->samples * n;
+        Staged<float4> d_rec(nullptr, items * 4);
+        const uint32_t* d_tiles = aov_tiles(scene, *profile, f);
+        dispatch([&](auto alpha, auto grid) {
+            hipLaunchKernelGGL((k_aov_samples<alpha, grid>), dim3((uint32_t)((items + 255u) / 256u)), dim3(256), 0, nullptr, scene->dev, f.A,
+                               d_tiles, d_rec.d);
+        }, f.alpha, f.grid);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        d_rec.fetch((float4*)records, items * 4);
+    });
+}
+
+int pt_aov_guides_device(int device, uint64_t n_pixels, uint32_t samples, const void* d_aov, void* d_guides, void* hip_stream) {
+    return guarded([&] {
+        aov_guides_check("pt_aov_guides_device", n_pixels, samples, d_aov, d_guides);
+        if (((uintptr_t)d_aov | (uintptr_t)d_guides) & 15u) fail(PT_ERR_INVALID, "pt_aov_guides_device: the planes must be 16-byte aligned");
+        if (device >= 0) HIP_CHECK(hipSetDevice(device));
+        aov_guides_launch(n_pixels, samples, (const float4*)d_aov, (float4*)d_guides, (hipStream_t)hip_stream);
+    });
+}
+
+int pt_aov_guides(int device, uint64_t n_pixels, uint32_t samples, const float* aov, float* guides) {
+    return guarded([&] {
+        aov_guides_check("pt_aov_guides", n_pixels, samples, aov, guides);
+        if (device >= 0) HIP_CHECK(hipSetDevice(device));
+        Staged<float4> d_aov((const float4*)aov, n_pixels * 4), d_guides(nullptr, n_pixels * 2);
+        aov_guides_launch(n_pixels, samples, d_aov.d, d_guides.d, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        d_guides.fetch((float4*)guides, n_pixels * 2);
+    });
+}
+
+int pt_render_denoised_aov(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, const pt_denoise_params* params,
+                           int variance, uint32_t aov_flags, uint8_t* rgb8, float* color) {
+    return guarded([&] {
+        const char* who = "pt_render_denoised_aov";
+        if (!scene || !profile) fail(PT_ERR_INVALID, "%s: null argument", who);
+        if (variance) {
+            dnv_check(who, params, profile->width, profile->height, profile->samples);
+            moments_check_opts(who, opts);
+        } else {
+            dn_check_params(who, params);
+        }
+        const AovFrame f = aov_frame(who, scene, profile, opts, aov_flags, (const void*)16);
+        if (f.o.shard_count > 1) fail(PT_ERR_UNSUPPORTED, "%s: the filter needs the whole image (shard_count %u)", who, f.o.shard_count);
+        HIP_CHECK(hipSetDevice(scene->device));
+        const uint32_t w = profile->width, h = profile->height;
+        const size_t n = (size_t)w * h;
+        Staged<uint8_t> d_rgb(nullptr, n * 3), d_scratch(nullptr, pt_denoise_scratch_bytes(w, h));
+        Staged<float> d_acc(nullptr, n * 3), d_color(nullptr, n * 3);
+        Staged<float2> d_mom(nullptr, variance ? n : 0);
+        Staged<float4> d_aov(nullptr, n * 4), d_guides(nullptr, n * 2);
+        FrameTaps taps;
+        taps.moments = d_mom.d;
+        // the raw frame (with its moments), then the AOV pass, the conversion and the filter behind it on the same stream
+        render_device(render_state(scene), *profile, opts, d_rgb.d, d_acc.d, nullptr, true, variance ? &taps : nullptr);
+        aov_launch(*scene, f, nullptr, d_aov.d, nullptr);
+        aov_guides_launch(n, profile->samples, d_aov.d, d_guides.d, nullptr);
+        if (variance)
+            denoise_var_launch(w, h, profile->samples, *params, d_acc.d, d_mom.d, d_guides.d, color ? d_color.d : nullptr,
+                               rgb8 ? d_rgb.d : nullptr, d_scratch.d, nullptr);
+        else
+            denoise_launch(w, h, profile->samples, *params, d_acc.d, d_guides.d, color ? d_color.d : nullptr, rgb8 ? d_rgb.d : nullptr,
+                           d_scratch.d, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        if (rgb8) d_rgb.fetch(rgb8, n * 3);
+        if (color) d_color.fetch(color, n * 3);
     });
 }
 

@@ -4,6 +4,7 @@
 //   path-tracer render <INPUT> [-o/--output <OUTPUT>] [-q/--quiet] [-v/--viewer]
 //                              [--debug-textures] [-p/--profile <PROFILE>] [--camera-path <CAMERAS>]
 //                              [--keyframes <FRAMES> [--light-mixer]]
+//                              [--denoise [--denoise-variance] [--denoise-guides <centre|samples>]] [--aov-dir <DIR>]
 //                              [--noise-target <T> [--min-samples <N0>] [--max-samples <N>] [--noise-map <FILE.png>]
 //                               [--adaptive [--adaptive-tile <N>] [--uniform-samples <U>] [--adaptive-dilate <0|1>]
 //                                [--sample-map <FILE.png>]]
@@ -47,7 +48,9 @@
 #include <condition_variable>
 #include <mutex>
 #include <thread>
+#include <sys/stat.h>
 #include <unistd.h>
+#include <utility>
 #include <vector>
 
 #include "ptgpu.h"
@@ -85,6 +88,11 @@ void usage_render(FILE* f) {
           "      --denoise-iterations <N>  Filter passes of --denoise, pass i has step 2^i [0..8, default: the library's]\n"
           "      --denoise-variance   With --denoise: steer the filter's colour weight by the per-pixel variance of the frame's own\n"
           "                           samples (needs samples >= 2 in the profile)\n"
+          "      --denoise-guides <centre|samples>  With --denoise: the guides of the pixel-centre ray's first hit, or the mean features\n"
+          "                           of the surfaces the frame's own samples shaded (their camera casts and alpha walks replayed)\n"
+          "                           [default: centre; samples: not with --noise-target]\n"
+          "      --aov-dir <DIR>      Write albedo.png, normal.png, depth.png and alpha.png of the frame's samples into DIR (created);\n"
+          "                           a single frame on one device (not with --camera-path, --keyframes, --noise-target or --devices)\n"
           "      --noise-target <T>   Progressive film: add passes of N0, 2 N0, 4 N0, ... samples until the mean relative error of\n"
           "                           the pixels' mean luminance is <= T or the next pass would exceed N samples in all (one\n"
           "                           device, not with --light-mixer; -v prints one line per pass)\n"
@@ -219,6 +227,8 @@ int run_render(int argc, char** argv) {
     bool adaptive = false, have_adaptive_tile = false, have_uniform_samples = false, have_adaptive_dilate = false;
     uint32_t adaptive_tile = 32, uniform_samples = 0, adaptive_dilate = 1;
     std::string film_denoise;   // "", "plain" or "variance"
+    std::string denoise_guides; // "", "centre" or "samples"
+    std::string aov_dir;
     bool filtered_target = false;
     bool have_window_samples = false;
     uint32_t window_samples = 0;
@@ -262,6 +272,14 @@ int run_render(int argc, char** argv) {
             if (v.empty() || v.size() > 1 || !isdigit((unsigned char)v[0]) || v[0] > '8')
                 die("error: invalid value '" + v + "' for '--denoise-iterations <N>': 0..8 expected");
             denoise_iterations = v[0] - '0';
+        }
+        else if (a == "--denoise-guides" || a.rfind("--denoise-guides=", 0) == 0) {
+            denoise_guides = value("--denoise-guides <centre|samples>");
+            if (denoise_guides != "centre" && denoise_guides != "samples")
+                die("error: invalid value '" + denoise_guides + "' for '--denoise-guides <centre|samples>': centre or samples expected");
+        } else if (a == "--aov-dir" || a.rfind("--aov-dir=", 0) == 0) {
+            aov_dir = value("--aov-dir <DIR>");
+            if (aov_dir.empty()) die("error: invalid value '' for '--aov-dir <DIR>': a directory name expected");
         }
         else if (a == "--noise-target" || a.rfind("--noise-target=", 0) == 0) {
             std::string v = value("--noise-target <T>");
@@ -367,6 +385,23 @@ int run_render(int argc, char** argv) {
     }
     if (denoise_iterations >= 0 && !denoise && film_denoise.empty()) die("error: '--denoise-iterations <N>' needs '--denoise'");
     if (denoise_variance && !denoise) die("error: '--denoise-variance' needs '--denoise'");
+    if (!denoise_guides.empty() && !film_denoise.empty())
+        die("error: the argument '--denoise-guides <centre|samples>' cannot be used with '--film-denoise <plain|variance>' (a film's "
+            "pixels have sample counts of their own)");
+    if (!denoise_guides.empty() && !denoise) die("error: '--denoise-guides <centre|samples>' needs '--denoise'");
+    if (denoise_guides == "samples" && have_noise_target)
+        die("error: the argument '--denoise-guides samples' cannot be used with '--noise-target <T>' (a film's pixels have sample "
+            "counts of their own)");
+    if (!aov_dir.empty()) {
+        auto with = [](const char* other, const char* why) {
+            die(std::string("error: the argument '--aov-dir <DIR>' cannot be used with '") + other + "' (" + why + ")");
+        };
+        if (have_camera_path) with("--camera-path <CAMERAS>", "the planes are written for a single frame");
+        if (have_keyframes) with("--keyframes <FRAMES>", "the planes are written for a single frame");
+        if (have_noise_target) with("--noise-target <T>", "a film's pixels have sample counts of their own");
+        if (devices.size() > 1) with("--devices <A,B,..>", "the planes are made on one device");
+        if (debug_textures) with("--debug-textures", "one set of feature images per run");
+    }
     if (denoise && devices.size() > 1)
         die("error: the argument '--denoise' cannot be used with more than one device in '--devices <A,B,..>' (the gathered "
             "multi-GPU frame is u8 only; the filter needs the f32 frame on one device)");
@@ -918,6 +953,40 @@ int run_render(int argc, char** argv) {
             fprintf(stderr, "film: %u passes, %llu samples, noise %.6g, %s\n", info.passes, (unsigned long long)info.samples, noise.mean_error,
                     noise.converged ? "converged" : "max samples");
     };
+    // --aov-dir: the frame's pixel records (pt_render_aov) as four images in the debug pass's conventions, as_u8(v * 255):
+    // albedo = sum / N, normal = the normalised sum * 0.5 + 0.5, depth = (sum / coverage) over the largest finite one,
+    // alpha = coverage / N; a pixel without coverage stays 0 in all of them
+    auto write_aov_planes = [&]() {
+        std::vector<float> aov(n_pixels * PT_AOV_FLOATS);
+        if (pt_render_aov(scene, &profile, &opts, 0u, aov.data()) != PT_OK) die(pt_last_error());
+        for (size_t p = 1; p <= aov_dir.size(); ++p)
+            if (p == aov_dir.size() || aov_dir[p] == '/') (void)mkdir(aov_dir.substr(0, p).c_str(), 0777);   // (existing: fine)
+        const float fn = (float)profile.samples;
+        float zmax = 0.f;
+        for (size_t i = 0; i < n_pixels; ++i) {
+            const float* r = &aov[i * PT_AOV_FLOATS];
+            const float z = r[3] / r[7];
+            if (r[7] > 0.f && std::isfinite(z) && z > zmax) zmax = z;
+        }
+        std::vector<uint8_t> albedo(n_pixels * 3, 0), normal(n_pixels * 3, 0), depth(n_pixels * 3, 0), alpha(n_pixels * 3, 0);
+        for (size_t i = 0; i < n_pixels; ++i) {
+            const float* r = &aov[i * PT_AOV_FLOATS];
+            if (!(r[7] > 0.f)) continue;
+            const float nn = (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
+            const float inv = nn > 0.f && nn < INFINITY ? 1.0f / sqrtf(nn) : 0.f;
+            for (int c = 0; c < 3; ++c) {
+                albedo[3 * i + c] = to_grey((r[4 + c] / fn) * 255.0f);
+                normal[3 * i + c] = to_grey(((r[c] * inv) * 0.5f + 0.5f) * 255.0f);
+                depth[3 * i + c] = to_grey(((r[3] / r[7]) / zmax) * 255.0f);
+                alpha[3 * i + c] = to_grey((r[7] / fn) * 255.0f);
+            }
+        }
+        const std::pair<const char*, const std::vector<uint8_t>*> files[] = {
+            {"albedo.png", &albedo}, {"normal.png", &normal}, {"depth.png", &depth}, {"alpha.png", &alpha}};
+        for (const auto& file : files)
+            if (pth_png_write_rgb8((aov_dir + "/" + file.first).c_str(), profile.width, profile.height, file.second->data()) != PT_OK)
+                die(pth_last_error());
+    };
     pt_lightmix* mix = nullptr;
     bool mixer_on = light_mixer;
     size_t lights_of = 0, captures = 0, mixed = 0, rendered = 0;
@@ -952,7 +1021,9 @@ int run_render(int argc, char** argv) {
             render_film(f);
             ++rendered;
         } else {
-            if ((denoise_variance ? pt_render_denoised_var(scene, &profile, &opts, &dn, rgb.data(), nullptr)
+            if ((denoise_guides == "samples"
+                     ? pt_render_denoised_aov(scene, &profile, &opts, &dn, denoise_variance ? 1 : 0, 0u, rgb.data(), nullptr)
+                 : denoise_variance ? pt_render_denoised_var(scene, &profile, &opts, &dn, rgb.data(), nullptr)
                  : denoise        ? pt_render_denoised(scene, &profile, &opts, &dn, rgb.data(), nullptr)
                                   : pt_render(scene, &profile, &opts, rgb.data(), nullptr)) != PT_OK)
                 die(pt_last_error());
@@ -968,6 +1039,7 @@ int run_render(int argc, char** argv) {
         for (char& c : ext) c = (char)tolower(c);
         if (ext != "png") die("The image format could not be determined (only .png output is supported): " + output);
         if (pth_png_write_rgb8(frame_name(f).c_str(), profile.width, profile.height, rgb.data()) != PT_OK) die(pth_last_error());
+        if (!aov_dir.empty()) write_aov_planes();
         t4 = std::chrono::steady_clock::now();
     }
 

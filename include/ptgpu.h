@@ -1093,6 +1093,20 @@ int pt_get_cont_escape_stats(const pt_scene* scene, uint64_t* fill_launches, uin
  * frame, and the configuration's next render call fails with PT_ERR_DEVICE (never, by the rule above - a check) -, since the
  * scene was made.  The call does not wait for the device. */
 int pt_get_b0_lean_stats(const pt_scene* scene, uint64_t* lean_launches, uint64_t* general_launches, uint64_t* guard_trips);
+/* The lean variant of the fused shade pass of bounces 1 and 2 (PT_B1_LEAN, default 1, read per frame; independent of
+ * PT_B0_LEAN).  A bounce whose shade pass adds the lights of known visibility itself, in a configuration whose last counted
+ * frame was a planned one that wrote at that bounce fewer shadow records than 1/64 of the records it shaded, launches a
+ * variant of that kernel without the shadow-record, sorting, exact-list, roulette and ChaCha code, at more waves per SIMD.  A
+ * queue entry it cannot shade - a light of unknown visibility, a normal too long for the light grids - it writes nothing for
+ * and appends to a list; a launch of the general kernel over that list follows on the same stream and shades the record
+ * whole, so eligibility decides speed only and the frame is the same bit for bit.  Any pt_scene_set_* call, a re-keyed cache
+ * or a moved mark, new or dropped escape masks, and an unplanned, counting or tile-list frame put the bounce back on the
+ * general variant until a frame has been counted again.  PT_B1_LEAN_TEST_FORCE=1 (a hook for tests) takes the lean variant
+ * wherever the plain fused pass would run at those bounces.  lean_launches_b1 / _b2: lean launches by bounce;
+ * general_launches: general fused launches at those bounces; handed_over: entries the list passes shaded, since the scene was
+ * made.  The call waits for the device. */
+int pt_get_b1_lean_stats(const pt_scene* scene, uint64_t* lean_launches_b1, uint64_t* lean_launches_b2, uint64_t* general_launches,
+                         uint64_t* handed_over);
 /* The state words of the first `count` cached continuation records (at most pt_get_cont_cache_stats' items_cached), one
  * uint32 each: bit 0 - the record was written, bit 1 - it carries the escape test's answer, bit 2 - that answer.  A check
  * for tests.  The call waits for the device. */

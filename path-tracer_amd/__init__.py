@@ -343,7 +343,7 @@ HOST_SYMBOLS = ["pth_scene_load_isf", "pth_scene_free", "pth_scene_desc", "pth_s
 GPU_SYMBOLS = ["pt_scene_create", "pt_scene_destroy", "pt_scene_set_camera", "pt_scene_set_lights", "pt_scene_set_materials", "pt_prep_create", "pt_prep_destroy", "pt_scene_create_from_prep",
                "pt_comm_unique_id", "pt_comm_create", "pt_comm_create_all", "pt_comm_destroy", "pt_gather_tiles", "pt_render_gathered", "pt_local_pixel_count", "pt_local_pixel_map",
                "pt_render", "pt_render_device", "pt_debug_render", "pt_assemble_tiles", "pt_get_timing", "pt_get_counters",
-               "pt_scene_get_info", "pt_get_cull_stats", "pt_get_rng_cache_stats", "pt_get_hit_cache_stats", "pt_get_vis_cache_stats", "pt_get_hit1_cache_stats", "pt_get_hit1_fused_stats", "pt_get_cont_cache_stats", "pt_get_cont_escape_stats", "pt_get_b0_lean_stats", "pt_scene_cont_states_copy", "pt_get_hit2_cache_stats", "pt_get_vis1_cache_stats", "pt_get_bounce1_fused_stats", "pt_get_bounce_hits_cache_stats", "pt_get_bounce_vis_cache_stats", "pt_get_bounce_fused_stats", "pt_kernel_occupancy", "pt_scene_escape_copy", "pt_escape_query", "pt_scene_grid_header", "pt_scene_grid_copy", "pt_trace_rays", "pt_trace_rays_wavefront",
+               "pt_scene_get_info", "pt_get_cull_stats", "pt_get_rng_cache_stats", "pt_get_hit_cache_stats", "pt_get_vis_cache_stats", "pt_get_hit1_cache_stats", "pt_get_hit1_fused_stats", "pt_get_cont_cache_stats", "pt_get_cont_escape_stats", "pt_get_b0_lean_stats", "pt_get_b1_lean_stats", "pt_scene_cont_states_copy", "pt_get_hit2_cache_stats", "pt_get_vis1_cache_stats", "pt_get_bounce1_fused_stats", "pt_get_bounce_hits_cache_stats", "pt_get_bounce_vis_cache_stats", "pt_get_bounce_fused_stats", "pt_kernel_occupancy", "pt_scene_escape_copy", "pt_escape_query", "pt_scene_grid_header", "pt_scene_grid_copy", "pt_trace_rays", "pt_trace_rays_wavefront",
                "pt_trace_rays_all", "pt_intersect_triangles",
                "pt_rng_words", "pt_eval_math", "pt_measure_copy_bandwidth", "pt_measure_gather_rate", "pt_last_error",
                "pt_version", "pt_render_guides", "pt_render_guides_device", "pt_denoise_params_default", "pt_denoise_scratch_bytes",
@@ -484,6 +484,9 @@ def gpu_lib():
         if hasattr(L, "pt_get_b0_lean_stats"):
             L.pt_get_b0_lean_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 3
             L.pt_get_b0_lean_stats.restype = C.c_int
+        if hasattr(L, "pt_get_b1_lean_stats"):
+            L.pt_get_b1_lean_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 4
+            L.pt_get_b1_lean_stats.restype = C.c_int
         if hasattr(L, "pt_get_cont_escape_stats"):
             L.pt_get_cont_escape_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 4
             L.pt_scene_cont_states_copy.argtypes = [vp, vp, C.c_uint64]
@@ -1266,6 +1269,14 @@ class GpuScene:
         bounce-0 launch loaded all its caches and no lane cast, lacked a record or wrote a shadow record; any scene edit,
         re-keyed cache or new masks put it back on the general variant until a frame has been counted clean again."""
         return self._cache_stats(self.lib.pt_get_b0_lean_stats, 3)
+
+    def b1_lean_stats(self):
+        """The lean variant of the fused shade pass of bounces 1 and 2 (PT_B1_LEAN): (lean launches at bounce 1, lean launches
+        at bounce 2, general fused launches at those bounces, queue entries the lean launches handed to the list pass behind
+        them).  A bounce goes lean after a planned frame that sent fewer than 1/64 of that bounce's shaded records to the
+        shadow queue; what a lean launch cannot shade the list pass shades, so results never depend on it.  Waits for the
+        device."""
+        return self._cache_stats(self.lib.pt_get_b1_lean_stats, 4)
 
     def cont_states(self, count=None):
         """The state words of the first `count` cached continuation records (default: all of them) as a uint32 array: bit 0

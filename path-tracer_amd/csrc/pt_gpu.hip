@@ -233,10 +233,13 @@ __global__ __launch_bounds__(256) void k_assemble(const uint8_t* __restrict__ ga
 // cold / lean_out (the lean bounce-0 variant's eligibility, frame_plan): the block of the bounce-1 hits' device counters and this
 // line's word behind the frame's lines - the workgroups of the loading bounce-0 launches that cast for a light ([8]) and their
 // lanes that found no continuation record ([6]) or ran the escape test themselves ([7]) since the last line was taken; [9]
-// keeps the sum that line saw.  No block: all ones, "not known".
+// keeps the sum that line saw.  No block: all ones, "not known".  shadow_out: this line's two words behind the cold words.
 __global__ void k_wf_stats(const WfCounters* __restrict__ ctr, uint32_t levels, uint32_t* __restrict__ out,
-                           unsigned long long* __restrict__ cold, uint32_t* __restrict__ lean_out) {
+                           unsigned long long* __restrict__ cold, uint32_t* __restrict__ lean_out, uint32_t* __restrict__ shadow_out) {
     const uint32_t b = threadIdx.x;
+    // (the lean shade pass of bounces 1 and 2: the shadow records written there, apart from those the fused pass inlined)
+    if ((b == 1 || b == 2) && b < levels) shadow_out[b - 1u] = ctr[b].shadow_count;
+    else if ((b == 1 || b == 2)) shadow_out[b - 1u] = 0u;
     if (b == 0) {
         uint32_t since = 0xffffffffu;
         if (cold) {
@@ -623,6 +626,9 @@ struct pt_scene {
         // the hits of queue 2 where the bounce-1 shade pass answers its survivors' casts from the bounce-2 hit cache itself: that
         // launch is still reading `hits`.  As long as queue 2 (20 B per record); like the cache it serves, not part of queue_bytes
         DeviceBuffer hits_next;
+        // the hand-over list of the lean shade pass of bounces 1 and 2 (k_wf_shade_fused<256 | 8192>): WF_HANDOVER_HEAD count
+        // words by bounce, zeroed once per chunk, then queue indices - as long as the longer queue.  Not part of queue_bytes either
+        DeviceBuffer handover;
         hipStream_t side = nullptr, side_wide = nullptr, side_exact = nullptr;
         hipEvent_t ev_shade = nullptr, ev_shadow = nullptr, ev_rng = nullptr, ev_chunk = nullptr, ev_trace = nullptr, ev_wide = nullptr,
                    ev_exact = nullptr, ev_exact_go = nullptr;
@@ -657,6 +663,15 @@ struct pt_scene {
         bool lean = false, stats_lean_ok = false;
         std::vector<uint64_t> lean_sig, stats_sig;
         const uint32_t* cold_words() const { return host + (size_t)n_slots * levels * 4u; }   // one word per line, behind the lines
+        // The lean shade pass of bounces 1 and 2 (k_wf_shade_fused<256 | 8192>), by bounce - 1.  b1_lean: the last counted frame
+        // of the configuration was a planned one that wrote at that bounce fewer shadow records than 1 / PT_B1_LEAN_SHARE of
+        // the records it shaded (shadow records + those whose lights the fused pass added itself); b1_sig: the state it was
+        // counted under (lean_sig's, plus that bounce's visibility and hit planes); stats_b1_sig: the same of the counts on
+        // their way.  shadow_words: two words per line behind the cold words - the shadow records written at bounces 1 and 2.
+        bool b1_lean[2] = {false, false}, stats_b1_ok = false;   // (stats_b1_ok: the counts on their way are a plain frame's)
+        std::vector<uint64_t> b1_sig[2], stats_b1_sig[2];
+        const uint32_t* shadow_words() const { return cold_words() + n_slots; }
+        static size_t host_bytes(uint32_t slots, uint32_t lv) { return (size_t)slots * lv * 16u + (size_t)slots * 12u; }
         ~FrameStats() {
             if (host) (void)hipHostFree(host);
             if (done) (void)hipEventDestroy(done);
@@ -763,6 +778,9 @@ struct pt_scene {
     // (the loading bounce-0 launches by variant - lean, k_wf_shade_hits<2283 | 4096>, and general - and the frames a lean launch
     // flagged because it met a lane it does not contain the code for: none, ever.  pt_get_b0_lean_stats)
     uint64_t b0_lean_launches = 0, b0_general_launches = 0, b0_lean_guard_trips = 0;
+    // (the fused shade launches of bounces 1 and 2 by variant - lean, k_wf_shade_fused<256 | 8192> with its list pass behind it,
+    // by bounce - 1, and general; the entries handed over are word 6 of those bounces' fused counter blocks.  pt_get_b1_lean_stats)
+    uint64_t b1_lean_launches[2] = {0, 0}, b1_general_launches = 0;
     // The closest hits of the bounce-2 rays, same key: that ray is made from the bounce-1 hit, the material there and the
     // item's words - again no light, and the Russian roulette starts behind it - so what holds for bounce 1 holds one bounce
     // later.  In use in the frames hit1_cache serves that have a bounce 2; the record, the zeroing, the prefix, the counters
@@ -2217,8 +2235,13 @@ struct QueueEnv {
     double reserve_gib;
     double test_shrink;    // PT_PLAN_TEST_SHRINK, clamped to 0.01..1 (0: unset)
     bool test_lean;        // PT_B0_LEAN_TEST_FORCE: the lean bounce-0 variant without asking whether the frame is eligible
+    bool test_lean1;       // PT_B1_LEAN_TEST_FORCE: the lean shade pass at bounces 1 and 2 wherever the plain fused pass would run
 };
 
+// The lean shade pass of bounces 1 and 2 is taken where the counted frame sent fewer than 1 / PT_B1_LEAN_SHARE of the bounce's
+// shaded records to the shadow queue: a handed-over record costs both passes
+// (a named constant, not a measurement: break-even lies near the lean launch's relative gain, 10-20 % - 1/64 is safely inside)
+constexpr uint64_t PT_B1_LEAN_SHARE = 64;
 QueueEnv queue_env() {
     QueueEnv q;
     q.first_gib = env_num(getenv("PT_QUEUE_GIB"), 8.0);
@@ -2228,6 +2251,7 @@ QueueEnv queue_env() {
     const char* shrink = getenv("PT_PLAN_TEST_SHRINK");
     q.test_shrink = shrink && *shrink ? std::min(1.0, std::max(0.01, atof(shrink))) : 0.0;
     q.test_lean = env_bool(getenv("PT_B0_LEAN_TEST_FORCE"), false);
+    q.test_lean1 = env_bool(getenv("PT_B1_LEAN_TEST_FORCE"), false);
     return q;
 }
 
@@ -2493,6 +2517,9 @@ struct WfFrame {
     // PT_B0_LEAN (read per frame): the loading bounce-0 launches of this frame take the lean variant (lean_frame);
     // lean_forced: the test hook PT_B0_LEAN_TEST_FORCE - they take it whatever the counts said
     bool lean = false, lean_forced = false;
+    // PT_B1_LEAN (read per frame): the plain fused shade pass of bounce b (1 or 2) takes the lean variant with its list pass
+    // (lean_frame); b1_lean_forced: the test hook PT_B1_LEAN_TEST_FORCE - it does whatever the counts said
+    bool b1_lean[3] = {false, false, false}, b1_lean_forced = false;
     // PT_VIS1_FUSED (default 1), PT_HIT2_FUSED (default 0; both read per frame): the bounce-1 shade pass of a chunk whose batch has visibility bytes
     // adds the lights of known visibility itself (k_wf_shade_fused<256>); ... and, where the chunk loads its bounce-2 hits, reads
     // that plane itself too (<256 | 512>, the first switch on as well) - no k_wf_hits_load at bounce 2.  hits_next_wanted: this
@@ -2624,6 +2651,7 @@ WfFrame frame_plan(pt_scene& s, const Frame& f, const QueueEnv& qe) {
         own.pending = own.valid = own.planned = own.stats_planned = own.plan_fresh = own.plan_failed = false;
         own.stats_hit_loads = own.plan_hit_loads = 0;
         own.lean = own.stats_lean_ok = false;
+        own.b1_lean[0] = own.b1_lean[1] = own.stats_b1_ok = false;
         wf.fs = &own;
         wf.inline_at.assign(p.bounces + 2, 0);
         wf.cap = wf.cap_a;
@@ -2657,6 +2685,17 @@ WfFrame frame_plan(pt_scene& s, const Frame& f, const QueueEnv& qe) {
             }
             fs->lean = clean && !overflow;
             fs->lean_sig = fs->stats_sig;
+            // (the lean shade pass of bounces 1 and 2: a handed-over record costs both passes, so the share of records the
+            // counted frame sent to the shadow queue must lie well inside the lean launch's relative gain)
+            for (uint32_t b = 1; b <= 2u; ++b) {
+                uint64_t shadow = 0, shaded = 0;
+                for (uint32_t k = 0; k < fs->n_slots && b < fs->levels; ++k) {
+                    shadow += fs->shadow_words()[2u * k + (b - 1u)];
+                    shaded += fs->host[((size_t)k * fs->levels + b) * 4 + 1];
+                }
+                fs->b1_lean[b - 1u] = fs->planned && fs->stats_planned && fs->stats_b1_ok && !overflow && shadow * PT_B1_LEAN_SHARE < shaded;
+                fs->b1_sig[b - 1u] = fs->stats_b1_sig[b - 1u];
+            }
             if (guard) {
                 // cannot happen (a configuration goes lean on counts that say no lane needs more): nothing was written for the lane
                 ++s.b0_lean_guard_trips;
@@ -2740,7 +2779,7 @@ void queue_buffers(pt_scene& s, const Frame& f, const QueueEnv& qe, WfFrame& wf)
             if (wf.planned) wf.fs->plan_fresh = false;
             break;
         }
-        for (DeviceBuffer* b : {&w.queue[0], &w.queue[1], &w.hits, &w.shadow, &w.contrib, &w.rng[0], &w.rng[1], &w.draws, &w.offgrid, &w.deferred, &w.exact[0], &w.exact[1], &w.block_mask, &w.hits_next})
+        for (DeviceBuffer* b : {&w.queue[0], &w.queue[1], &w.hits, &w.shadow, &w.contrib, &w.rng[0], &w.rng[1], &w.draws, &w.offgrid, &w.deferred, &w.exact[0], &w.exact[1], &w.block_mask, &w.hits_next, &w.handover})
             b->release();
         if (wf.planned) {   // (no room for the planned sizes: as a first frame)
             wf.planned = false;
@@ -2781,6 +2820,9 @@ constexpr FrameCacheKind VIS_CACHE = {"PT_VIS_CACHE", "PT_VIS_CACHE_GIB", 1.0, 1
 constexpr FrameCacheKind HIT1_CACHE = {"PT_HIT1_CACHE", "PT_HIT1_CACHE_GIB", 8.0, 16u, ~0ull, true};
 #ifndef PT_B0_LEAN_DEFAULT
 #define PT_B0_LEAN_DEFAULT true   // (the lean bounce-0 variant: profiles/r21_experiments.txt)
+#endif
+#ifndef PT_B1_LEAN_DEFAULT
+#define PT_B1_LEAN_DEFAULT true   // (the lean shade pass of bounces 1 and 2: profiles/r22_experiments.txt)
 #endif
 #ifndef PT_CONT_ESCAPE_DEFAULT
 #define PT_CONT_ESCAPE_DEFAULT true   // (with the records refilled when the masks arrive: profiles/r20_experiments.txt item 2)
@@ -2949,7 +2991,7 @@ void stats_slots(pt_scene& s, const Frame& f, WfFrame& wf) {
     if (fs->n_slots != n || fs->levels != levels || !fs->host) {
         if (fs->host) (void)hipHostFree(fs->host);
         fs->host = nullptr;
-        HIP_CHECK(hipHostMalloc((void**)&fs->host, (size_t)n * levels * 16u + (size_t)n * 4u));   // (+ FrameStats::cold_words)
+        HIP_CHECK(hipHostMalloc((void**)&fs->host, pt_scene::FrameStats::host_bytes(n, levels)));   // (+ FrameStats::cold_words, shadow_words)
         fs->n_slots = n;
         fs->levels = levels;
     }
@@ -2958,7 +3000,7 @@ void stats_slots(pt_scene& s, const Frame& f, WfFrame& wf) {
     fs->stats_planned = wf.planned;
     fs->stats_hit_loads = 0;
     fs->first_item_of_slot.assign(n, 0u);
-    s.stats_dev.ensure((size_t)n * levels * 16u + (size_t)n * 4u);
+    s.stats_dev.ensure(pt_scene::FrameStats::host_bytes(n, levels));
     wf.stats_slots = n;
 }
 
@@ -2982,8 +3024,31 @@ void lean_frame(pt_scene& s, const Frame& f, const QueueEnv& qe, WfFrame& wf) {
     if (!plain) fs->lean = false;
     wf.lean = env_bool(getenv("PT_B0_LEAN"), PT_B0_LEAN_DEFAULT) && plain && fs->lean && fs->lean_sig == sig;
     wf.lean_forced = qe.test_lean;
+    // The lean shade pass of bounces 1 and 2 (independent of PT_B0_LEAN): the same signature plus the keys and marks of that
+    // bounce's visibility and hit planes.  Eligibility is a matter of speed only - what the lean launch cannot shade it hands
+    // to the list pass behind it - so the test hook may force it on any frame.
+    const bool b1_on = env_bool(getenv("PT_B1_LEAN"), PT_B1_LEAN_DEFAULT);
+    if (!plain) fs->b1_lean[0] = fs->b1_lean[1] = false;
+    wf.b1_lean_forced = b1_on && qe.test_lean1;
+    for (uint32_t b = 1; b <= 2u; ++b) {
+        std::vector<uint64_t> sig_b = sig;
+        for (const pt_scene::FrameCache* fc : {(const pt_scene::FrameCache*)wf.bounce_vis[b], (const pt_scene::FrameCache*)wf.bounce_hits[b].cache}) {
+            sig_b.push_back(fc ? 1u + fc->key.size() : 0u);
+            if (!fc) continue;
+            sig_b.insert(sig_b.end(), fc->key.begin(), fc->key.end());
+            sig_b.push_back(fc->mark);
+            sig_b.push_back(fc->stride);
+        }
+        wf.b1_lean[b] = b1_on && plain && fs->b1_lean[b - 1u] && fs->b1_sig[b - 1u] == sig_b;
+        if (wf.stats_slots) fs->stats_b1_sig[b - 1u] = std::move(sig_b);
+    }
+    if (wf.b1_lean[1] || wf.b1_lean[2] || wf.b1_lean_forced) {   // (no room for the list: the general pass)
+        if (!s.pipe.handover.try_ensure(((size_t)std::max(wf.cap_q[0], wf.cap_q[1]) + WF_HANDOVER_HEAD) * 4u))
+            wf.b1_lean[1] = wf.b1_lean[2] = wf.b1_lean_forced = false;
+    }
     if (wf.stats_slots) {
         fs->stats_lean_ok = plain;
+        fs->stats_b1_ok = plain;
         fs->stats_sig = std::move(sig);
     }
 }
@@ -3104,6 +3169,9 @@ struct Chunk {
     int b1_fused = 0;
     // this bounce's shade pass is k_wf_shade_fused (bounce 1: b1_fused; bounces 2-4: 256, with that bounce's plane); 0: k_wf_shade
     int fused = 0;
+    // this bounce's fused pass (256 alone, bounce 1 or 2) is the lean variant, k_wf_shade_fused<256 | 8192>, with the list pass
+    // of the general body (<256 | 16384>) behind it
+    bool lean1 = false;
     uint4* hits = nullptr;   // the hit plane of this bounce's queue (WfPipe::hits; hits_next: see above), W.hcap records long
     float4 *q_in = nullptr, *q_out = nullptr;
     bool split_shade = false;   // the shade pass in two launches (PT_WF_SPLIT)
@@ -3304,7 +3372,18 @@ void shade_stage(pt_scene& s, const Frame& f, const WfFrame& wf, const Chunk& c,
     auto launch_shade = [&] {
         if (c.fused) {   // (bounces 1-4 of a chunk whose batch has that bounce's visibility bytes: render_chunk)
             if (c.fused & 512) launch_fused(std::integral_constant<int, 256 | 512>{});
-            else launch_fused(std::integral_constant<int, 256>{});
+            else if (c.lean1) {
+                // the lean variant lists what it cannot shade; the general body over that list follows at once - in front of
+                // this bounce's k_og_shadow_vis, the ev_shade record and the next bounce's k_wf_hits_load.  Always launched:
+                // a small grid that reads the count on the device
+                shade_list = (const uint32_t*)pipe.handover.p;
+                launch_fused(std::integral_constant<int, 256 | 8192>{});
+                const uint32_t whole = shade_grid;
+                shade_grid = std::min(shade_grid, (uint32_t)s.n_cu);
+                launch_fused(std::integral_constant<int, 256 | 16384>{});
+                shade_grid = whole;
+                shade_list = nullptr;
+            } else launch_fused(std::integral_constant<int, 256>{});
             return;
         }
         if (c.grid_mode == 3 && c.cached && c.hit_mode) {
@@ -3446,6 +3525,9 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
     W.walk_steps = f.env.walk ? f.env.walk : 20u;
     c.wctr = (WfCounters*)pipe.ctr.p;
     HIP_CHECK(hipMemsetAsync(c.wctr, 0, sizeof(WfCounters) * (f.p.bounces + 3), c.st_main));
+    // (the counts of the hand-over list, by bounce: a frame that may take the lean shade pass at bounce 1 or 2)
+    const bool lean1_frame = (wf.b1_lean[1] || wf.b1_lean[2] || wf.b1_lean_forced) && pipe.handover.p != nullptr;
+    if (lean1_frame) HIP_CHECK(hipMemsetAsync(pipe.handover.p, 0, WF_HANDOVER_HEAD * 4u, c.st_main));
     // The scene's frame caches, one prefix in the frame-global item g (chunk boundaries differ between a first frame and a
     // planned one: the prefix does not care); this chunk is [g0, g1)
     const uint64_t g0 = (uint64_t)(P.sample_begin / f.batch) * wf.items_per_batch + base, g1 = g0 + W.n_items;
@@ -3622,6 +3704,11 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
         } else if (c.grid_mode < 2) {
             trace_stage(s, f, c, tl);   // (grid_mode >= 2: k_wf_shade casts the camera rays itself)
         }
+        // The lean variant of the plain fused pass, bounces 1 and 2 (lean_frame: the counts say that next to no record of this
+        // bounce needs the shadow queue, or the test hook): a matter of speed only - the list pass shades what it leaves.
+        // (Not where the shade pass is split in two launches: the second one has a list of its own.)
+        c.lean1 = lean1_frame && c.fused == 256 && (b == 1u || b == 2u) && W.exact_shade_lists == 0u && !c.split_shade &&
+                  (wf.b1_lean[b] || wf.b1_lean_forced) && pipe.handover.bytes >= ((size_t)W.qcap_in + WF_HANDOVER_HEAD) * 4u;
         shade_stage(s, f, wf, c, tl);
         if (c.prim && c.hit_mode == 16) {   // the records are behind this launch: the prefix grows by the chunk
             wf.hit_cache->touched(c.st_main);
@@ -3649,6 +3736,7 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
             ++wf.cont_cache->counter[2];
             ++(c.lean ? s.b0_lean_launches : s.b0_general_launches);
         }
+        if (c.fused && (b == 1u || b == 2u)) ++(c.lean1 ? s.b1_lean_launches[b - 1u] : s.b1_general_launches);
         if (c.fused) {
             ++s.fused_launches(b);   // (by bounce: b1_fused_launches counts bounce 1's alone)
             if (c.fused & 512) wf.bounce_hits[2].cache->touched(c.st_main);   // (read here: its count of loads follows at bounce 2)
@@ -3674,7 +3762,8 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
     if (wf.stats_slots && wf.stats_line < wf.stats_slots) {   // this chunk's counts: one line of the frame's statistics
         hipLaunchKernelGGL(k_wf_stats, dim3(1), dim3(64u * ((f.p.bounces + 3u + 63u) / 64u)), 0, c.st_main, (const WfCounters*)c.wctr,
                            f.p.bounces + 3u, (uint32_t*)s.stats_dev.p + (size_t)wf.stats_line * (f.p.bounces + 3u) * 4u,
-                           (unsigned long long*)s.hit1_unknown.p, (uint32_t*)s.stats_dev.p + (size_t)wf.stats_slots * (f.p.bounces + 3u) * 4u + wf.stats_line);
+                           (unsigned long long*)s.hit1_unknown.p, (uint32_t*)s.stats_dev.p + (size_t)wf.stats_slots * (f.p.bounces + 3u) * 4u + wf.stats_line,
+                           (uint32_t*)s.stats_dev.p + (size_t)wf.stats_slots * ((f.p.bounces + 3u) * 4u + 1u) + 2u * wf.stats_line);
         HIP_CHECK(hipGetLastError());
         wf.fs->first_item_of_slot[wf.stats_line] = base;
         ++wf.stats_line;
@@ -3686,7 +3775,7 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
 void frame_readout(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, void* d_rgb8, hipStream_t stream) {
     const pt_profile& p = f.p;
     if (wf.stats_slots && wf.stats_line == wf.stats_slots) {
-        HIP_CHECK(hipMemcpyAsync(wf.fs->host, s.stats_dev.p, (size_t)wf.stats_slots * (p.bounces + 3u) * 16u + (size_t)wf.stats_slots * 4u,
+        HIP_CHECK(hipMemcpyAsync(wf.fs->host, s.stats_dev.p, pt_scene::FrameStats::host_bytes(wf.stats_slots, p.bounces + 3u),
                                  hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipEventRecord(wf.fs->done, stream));
         wf.fs->pending = true;
@@ -6898,6 +6987,25 @@ int pt_get_b0_lean_stats(const pt_scene* scene, uint64_t* lean_launches, uint64_
     if (!scene) return PT_ERR_INVALID;
     return cache_stats({{lean_launches, scene->b0_lean_launches}, {general_launches, scene->b0_general_launches},
                         {guard_trips, scene->b0_lean_guard_trips}});
+}
+int pt_get_b1_lean_stats(const pt_scene* scene, uint64_t* lean_launches_b1, uint64_t* lean_launches_b2, uint64_t* general_launches,
+                         uint64_t* handed_over) {
+    if (!scene) return PT_ERR_INVALID;
+    return guarded([&] {
+        uint64_t handed = 0;   // (word 6 of the fused counter blocks of bounces 1 and 2: pt_scene::hits_unknown(2), (3))
+        for (uint32_t b = 2; b <= 3u; ++b) {
+            const DeviceBuffer& block = scene->hits_unknown(b);
+            if (!block.p) continue;   // (synchronises, like pt_get_bounce1_fused_stats)
+            uint64_t n = 0;
+            HIP_CHECK(hipSetDevice(scene->device));
+            HIP_CHECK(hipDeviceSynchronize());
+            HIP_CHECK(hipMemcpy(&n, (const uint64_t*)block.p + 6, sizeof n, hipMemcpyDeviceToHost));
+            handed += n;
+        }
+        if (cache_stats({{lean_launches_b1, scene->b1_lean_launches[0]}, {lean_launches_b2, scene->b1_lean_launches[1]},
+                         {general_launches, scene->b1_general_launches}, {handed_over, handed}}) != PT_OK)
+            fail(PT_ERR_INVALID, "pt_get_b1_lean_stats: null argument");
+    });
 }
 int pt_scene_cont_states_copy(const pt_scene* scene, uint32_t* out, uint64_t count) {
     if (!scene || (!out && count)) return PT_ERR_INVALID;

@@ -1993,6 +1993,7 @@ PT_D bool wf_light_is_moot(const DevLight& L, f3 term, f3 surface_pos) {
 #define WF_SHADE_AGGREGATE 1  // bounces >= 1: retire the misses first, shade the hits 256 at a time (see the kernel)
 #endif
 #define WF_SHADE_SWEEP 4      // hit words per thread and step of the aggregation's sweep over the queue (one uint4)
+#define WF_HANDOVER_HEAD 16u  // the hand-over list of the lean later-bounce shade pass: count words by bounce in front of the entries
 #ifndef WF_SHADE_GRID_WAVES
 // ... for the variants that cast through origin grids inline: 3 (170 registers).  At 4 the fused bounce-0 kernel keeps
 // 132 B of its state per lane in scratch: 18.66 ms against 17.09 ms at 3 (and 21.3 ms at 2) on config 3.
@@ -2349,8 +2350,15 @@ __global__ __launch_bounds__(256) void k_cont_escape_fill(DevScene S, WfParams W
 // alone [1] next-bounce records written, unknown included (NEXT1), [2] survivors ended or elided here, [3] unknown, [4] records
 // whose lights were added here, [5] records deferred to the shadow queue.  What the launch leaves unwritten the frame plan
 // must still count: WfCounters::elided_count of the next bounce, inlined_count and exact_elided.
+// GRIDX | 8192, LEAN1: the same launch for bounces 1 and 2 of a frame that is known to write (nearly) no shadow record there -
+// the steady frame - with none of that compiled in (pt_wf_shade_body.h, LEAN1), at WF_SHADE_LEAN1_WAVES waves per SIMD; what it
+// cannot shade it lists in `index_list`.  GRIDX | 16384, HAND: the general body over that list, launched behind it.  The same
+// parameters, so the same template: the bounds follow GRIDX.
+#ifndef WF_SHADE_LEAN1_WAVES
+#define WF_SHADE_LEAN1_WAVES 5
+#endif
 template <int GRIDX>
-__global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES) void k_wf_shade_fused(DevScene S, WfParams W,
+__global__ __launch_bounds__(WF_SHADE_THREADS, (GRIDX & 8192) ? WF_SHADE_LEAN1_WAVES : WF_SHADE_WAVES) void k_wf_shade_fused(DevScene S, WfParams W,
                                                   const uint32_t* __restrict__ tile_offsets,
                                                   const float4* __restrict__ queue_in, const uint4* __restrict__ hits,
                                                   const uint4* rng_planes,
@@ -2361,7 +2369,8 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_WAVES) void k_wf_shade_f
                                                   uint32_t* __restrict__ exact_next, WfCounters* __restrict__ ctr,
                                                   const uint8_t* __restrict__ vis_bytes, const uint4* __restrict__ next_plane,
                                                   uint4* __restrict__ next_hits, unsigned long long* __restrict__ next_ctr) {
-    static_assert(GRIDX == 256 || GRIDX == (256 | 512), "VIS1, or VIS1 and NEXT1");
+    static_assert(GRIDX == 256 || GRIDX == (256 | 512) || GRIDX == (256 | 8192) || GRIDX == (256 | 16384),
+                  "VIS1, or VIS1 and NEXT1; LEAN1 and HAND with VIS1 alone");
     constexpr bool ALPHA = false, COUNT = false, PRIMARY = false;
     // (what this pass does not read)
     const uint32_t *const draws = nullptr, *const block_empty = nullptr;

@@ -55,17 +55,39 @@
     // item) are fetched at the top of the step, as in the general variant, but wait in LDS, not in registers (sh_late).
     constexpr bool LEAN = (GRIDX & 4096) != 0;
     static_assert(!LEAN || (CONT_LOAD && !DIRL && PRIMARY), "the lean variant is a loading bounce-0 launch without the orthographic branch");
+    // LEAN1 (k_wf_shade_fused<256 | 8192>: bounces 1 and 2 of a steady frame).  A frame whose visibility bytes are all known
+    // writes no shadow record at these bounces, sorts nothing, lists no ray for k_wf_trace_exact, plays no roulette and draws
+    // words 4-7 of the staged plane only: this variant contains none of the rest - no shadow or contribution record with its
+    // second lights loop, no second colour (a known light is added to `color` at once, with the operands `lit` receives in the
+    // general variant), no sorting option, no exact_shade_lists branch, no ChaCha block - and so runs at WF_SHADE_LEAN1_WAVES
+    // waves per SIMD.  A lane that needs any of it - a live light of unknown visibility, a normal too long for the grids, a
+    // draw beyond the staged words: a COLD lane - writes nothing and counts nothing; it appends its queue index to the
+    // hand-over list (one wf_reserve per wave on the list's own counter), and a launch of HAND, the general body over exactly
+    // those entries, follows on the same stream and shades the record whole.
+    // The list (`index_list` of both launches; the lean one writes it): sixteen count words by bounce, zeroed once per chunk,
+    // then the queue indices - as long as the bounce's queue, so it cannot overflow.  HAND reads the word and the hit of an
+    // entry from the chunk's own planes at the queue index.
+    constexpr bool LEAN1 = (GRIDX & 8192) != 0, HAND = (GRIDX & 16384) != 0;
+    static_assert(!(LEAN1 || HAND) || (VIS1 && !NEXT1), "the lean later-bounce variant and its list pass read the visibility bytes alone");
+    static_assert(!(LEAN1 && HAND), "a launch hands over or shades what was handed over");
+    uint32_t* const handover = (LEAN1 || HAND) ? const_cast<uint32_t*>(index_list) : nullptr;
     uint4* rng_planes_out = const_cast<uint4*>(rng_planes);   // GRID == 3 writes plane 1 (nobody reads it before bounce 1)
     static_assert(GRID < 2 || PRIMARY, "the camera grid serves bounce 0");
-    const bool list_pass = !PRIMARY && index_list != nullptr;
-    const uint32_t n_def = list_pass ? ctr[W.bounce].deferred_count : 0u;
-    const uint32_t n = PRIMARY ? W.n_items : list_pass ? n_def + (exact_list ? min(ctr[W.bounce].exact_count, W.ecap) : 0u) : min(ctr[W.bounce].queue_count, W.qcap_in);
+    const bool list_pass = !PRIMARY && !LEAN1 && index_list != nullptr;
+    const uint32_t n_def = HAND ? min(handover[W.bounce], W.qcap_in) : list_pass ? ctr[W.bounce].deferred_count : 0u;
+    // (HAND: the hand-over list alone - the bounce's exact list was shaded with the queue, by the launch that handed over)
+    const uint32_t n = PRIMARY ? W.n_items : list_pass ? n_def + ((!HAND && exact_list) ? min(ctr[W.bounce].exact_count, W.ecap) : 0u) : min(ctr[W.bounce].queue_count, W.qcap_in);
     // entry e of this launch: its queue record, the word of its hit, the hit
-    auto entry_index = [&](uint32_t e) -> uint32_t { return !list_pass ? e : e < n_def ? index_list[e] : exact_list[e - n_def]; };
+    auto entry_index = [&](uint32_t e) -> uint32_t {
+        if constexpr (HAND) return handover[WF_HANDOVER_HEAD + e];
+        return !list_pass ? e : e < n_def ? index_list[e] : exact_list[e - n_def];
+    };
     auto entry_word = [&](uint32_t e) -> uint32_t {
+        if constexpr (HAND) return wf_hit_word(hits, handover[WF_HANDOVER_HEAD + e]);
         return (!list_pass || e < n_def) ? wf_hit_word(hits, e) : wf_exact_words(exact_list, W.ecap)[e - n_def];
     };
     auto entry_hit = [&](uint32_t e, uint32_t i, RawHit& h) -> bool {
+        if constexpr (HAND) return wf_load_hit(hits, W.hcap, i, h);
         if (!list_pass) return wf_load_hit(hits, W.hcap, e, h);
         if (e < n_def) return wf_load_hit(hits, W.list_cap, e, h);
         const uint32_t x = wf_exact_words(exact_list, W.ecap)[e - n_def];
@@ -112,6 +134,13 @@
     auto unpark_u = [&](uint32_t slot) -> uint32_t { return park[slot * WF_SHADE_THREADS]; };
     auto unpark_f = [&](uint32_t slot) -> float { return __uint_as_float(park[slot * WF_SHADE_THREADS]); };
     auto unpark_3 = [&](uint32_t slot) -> f3 { const float x = unpark_f(slot), y = unpark_f(slot + 1u); return mk3(x, y, unpark_f(slot + 2u)); };
+    // (LEAN1) what the BRDF sample does not touch - out_slot, item, the colour, final by then, the new ray's origin and the
+    // primitive - waits in LDS across ct_sample and ct_eval_indirect, [slot][thread]: every slot private to its thread, so no
+    // barrier; volatile, as the slots above are.  These nine registers are what stands between the variant and
+    // WF_SHADE_LEAN1_WAVES waves without scratch (the first five alone: 12 B, profiles/r22_experiments.txt item 1).
+    constexpr uint32_t PARK1_SLOTS = 9u;
+    __shared__ uint32_t sh_park1[LEAN1 ? PARK1_SLOTS : 1][LEAN1 ? WF_SHADE_THREADS : 1];
+    volatile __attribute__((address_space(3))) uint32_t* const park1 = (volatile __attribute__((address_space(3))) uint32_t*)&sh_park1[0][LEAN1 ? threadIdx.x : 0u];
     // (Bounce 0 needs no hit aggregation like the later bounces' below: a wavefront is one 8x8 pixel block of one sample,
     // so its camera rays hit or miss together - collecting the hits of 256 items in LDS and shading them 256 at a time left
     // the instruction count and the 52 active lanes per instruction unchanged, profiles/r02_experiments.txt item 13.)
@@ -400,7 +429,17 @@
                 }
             } else if (!moot) {
                 if constexpr (LEAN) cold = true;   // (a normal too long for the grids' margin: the lane would write a shadow record)
-                else to_shadow = true;
+                else if constexpr (!LEAN1) to_shadow = true;
+                if constexpr (LEAN1) {
+                    // the light as the general variant adds it to `lit` - which starts as this colour -, added here: unknown
+                    // bits make the lane cold, and a cold lane's colour goes nowhere
+                    const uint32_t known = (vis >> (2u * li)) & 3u;
+                    if (known == 0u) cold = true;
+                    inlined = true;
+                    f3 rad = og_light_unshadowed<false>(S, li, surf.pos);
+                    if (known == 2u) rad = rad * 0.0f;
+                    if (!(rad.x == 0.f && rad.y == 0.f && rad.z == 0.f)) color = color + mul_ew(c, rad);
+                } else
                 if constexpr (VIS1) {
                     // the light as k_og_shadow_vis would add it, should every live light of the record turn out known (bit 8,
                     // in the register only: one of them is not)
@@ -412,6 +451,13 @@
                 }
             }
         }
+        if constexpr (LEAN1) {
+            // all of the record's lights, or none, here too: the general variant would send this record to the shadow queue for
+            // a normal too long for the grids' margin, so the lane is cold; so is one whose two draws are not both staged words
+            if (inlined && !(dot3(surf.normal, surf.normal) <= S.light_grid_max_normal2)) cold = true;
+            if (bounce < bounces && draw + 1u >= WF_RNG_STAGED) cold = true;
+            if (cold) inlined = false;
+        } else
         if constexpr (VIS1) {
             // all of the record's lights, or none: a partly added record would change the order of the additions.  A normal too
             // long for the grids' margin, or an unknown bit: the record goes to the shadow queue whole, as in k_wf_shade.
@@ -444,9 +490,14 @@
                     if (missing && wf_lane_rank(m) == 0u) atomicAdd(next_ctr + 6, (unsigned long long)__popcll(m));
                 }
             }
-        } else if (bounce < bounces) {
+        } else if (bounce < bounces && !(LEAN1 && cold)) {
             next_o = surf.pos + surf.normal * 0.00001f;
             float r1, r2;
+            if constexpr (LEAN1) {   // draws 2b+2 and 2b+3 of an opaque path: words 4-7 of the staged plane (any other lane is cold)
+                r1 = wf_rng_float(wf_rng_staged(rng_planes, W.cap, W.rng_first_plane, item, draw));
+                r2 = wf_rng_float(wf_rng_staged(rng_planes, W.cap, W.rng_first_plane, item, draw + 1u));
+                draw += 2u;
+            } else
             if (GRID == 3 && ALPHA) {
                 r1 = draw_b0(draw++);
                 r2 = draw_b0(draw++);
@@ -463,9 +514,23 @@
                 r1 = wf_rng_draw(rng, W, tile_offsets, rng_planes, item, draw++);
                 r2 = wf_rng_draw(rng, W, tile_offsets, rng_planes, item, draw++);
             }
+            if constexpr (LEAN1) {
+                park1[0] = out_slot, park1[WF_SHADE_THREADS] = item;
+                park1[2u * WF_SHADE_THREADS] = __float_as_uint(color.x), park1[3u * WF_SHADE_THREADS] = __float_as_uint(color.y);
+                park1[4u * WF_SHADE_THREADS] = __float_as_uint(color.z);
+                park1[5u * WF_SHADE_THREADS] = __float_as_uint(next_o.x), park1[6u * WF_SHADE_THREADS] = __float_as_uint(next_o.y);
+                park1[7u * WF_SHADE_THREADS] = __float_as_uint(next_o.z), park1[8u * WF_SHADE_THREADS] = h.pid;
+            }
             next_d = ct_sample(brdf, normal, view, r1, r2);
             f3 wgt = ct_eval_indirect(brdf, normal, view, next_d) / 1.0f;
             next_thr = mul_ew(thr, wgt);
+            if constexpr (LEAN1) {
+                out_slot = park1[0], item = park1[WF_SHADE_THREADS];
+                next_o.x = __uint_as_float(park1[5u * WF_SHADE_THREADS]), next_o.y = __uint_as_float(park1[6u * WF_SHADE_THREADS]);
+                next_o.z = __uint_as_float(park1[7u * WF_SHADE_THREADS]), h.pid = park1[8u * WF_SHADE_THREADS];
+                color.x = __uint_as_float(park1[2u * WF_SHADE_THREADS]), color.y = __uint_as_float(park1[3u * WF_SHADE_THREADS]);
+                color.z = __uint_as_float(park1[4u * WF_SHADE_THREADS]);
+            }
             if constexpr (CONT_STORE) {
                 // the escape test's answer for the lanes that will ask for it (not ended, a triangle, masks there): bit 1 - it
                 // was evaluated, with the masks that exist now -, bit 2 - the answer; the test below reads it from here
@@ -476,7 +541,10 @@
             }
         }
         if (dot3(next_thr, next_thr) < 0.00001f) ended = true;
-        if (!ended && bounce > 3) {
+        if constexpr (LEAN1) {   // (nothing of a cold lane's is asked of the masks)
+            if (cold) ended = true;
+        }
+        if (!LEAN1 && !ended && bounce > 3) {   // (LEAN1: bounces 1 and 2)
             float p = max_rs(max_rs(next_thr.x, next_thr.y), next_thr.z);
             next_thr = next_thr * (1.f / p);
             if (wf_rng_draw(rng, W, tile_offsets, rng_planes, item, draw++) > p) ended = true;
@@ -548,6 +616,18 @@
         // (the word alone; the rest where the hit is written, behind the barriers)
         if (survive) next_rec.x = *(volatile __attribute__((address_space(3))) uint32_t*)late;
     }
+    if constexpr (LEAN1) {
+        // a cold lane writes nothing - no record, no sample, no count - and hands its queue entry over.  (An entry is handed
+        // over once at most and the list is as long as the queue: the bound holds by construction and is checked all the same.)
+        if (cold) survive = false, inlined = false, ended_inline = false;
+        if (wf_any(cold)) {
+            const uint32_t slot = wf_reserve(handover + W.bounce, cold);
+            if (cold && slot < W.qcap_in) handover[WF_HANDOVER_HEAD + slot] = i;
+            else if (cold) ctr[0].overflow = 1u;
+            const unsigned long long m = __ballot(cold);
+            if (cold && wf_lane_rank(m) == 0u) atomicAdd(next_ctr + 6, (unsigned long long)__popcll(m));   // (pt_get_b1_lean_stats)
+        }
+    }
     if constexpr (NEXT) {
         elided = survive && !to_shadow && next_rec.x == (0xffffffffu ^ WF_HIT1_FLIP);
         if (elided) survive = false;
@@ -568,7 +648,7 @@
     const unsigned long long m_elided = NEXT ? __ballot(elided) : 0ull;
     const unsigned long long m_gone = VIS1 ? __ballot(elided || ended_inline) : 0ull, m_inlined = VIS1 ? __ballot(inlined) : 0ull;
     uint32_t oct = 0, oct_rank = 0;
-    if (W.sort_octants & 1u) {
+    if (!LEAN1 && (W.sort_octants & 1u)) {
         oct = (next_d.x < 0.f ? 1u : 0u) | (next_d.y < 0.f ? 2u : 0u) | (next_d.z < 0.f ? 4u : 0u);
 #pragma unroll
         for (uint32_t k = 0; k < 8u; ++k) {
@@ -601,7 +681,7 @@
         uint32_t total = 0;
         for (uint32_t k = 0; k < WF_SHADE_THREADS / 64; ++k) total += sh_cnt[1][k];
         fused_acc[threadIdx.x] += (total >> (10u * (threadIdx.x - 1u))) & 0x3ffu;
-    } else if ((W.sort_octants & 1u) && threadIdx.x >= 64u && threadIdx.x < 64u + 8u * (WF_SHADE_THREADS / 64)) {
+    } else if (!LEAN1 && (W.sort_octants & 1u) && threadIdx.x >= 64u && threadIdx.x < 64u + 8u * (WF_SHADE_THREADS / 64)) {
         // exclusive prefix of the (octant, wave) counts, octant-major
         const uint32_t e = threadIdx.x - 64u;
         uint32_t before = 0;
@@ -614,7 +694,7 @@
         next_idx += sh_cnt[0][k];
         sh_idx += VIS1 ? (sh_cnt[1][k] & 0x3ffu) : sh_cnt[1][k];
     }
-    if (W.sort_octants & 1u) next_idx = sh_base[0] + sh_oct_off[oct][wave] + oct_rank;
+    if (!LEAN1 && (W.sort_octants & 1u)) next_idx = sh_base[0] + sh_oct_off[oct][wave] + oct_rank;
     __syncthreads();  // sh_cnt / sh_base are rewritten by the next step
     // (the queues are sized by the records this very frame is known to produce, pt_gpu.hip FramePlan: a record beyond its
     // queue's end means that knowledge was wrong - nothing is written, the frame is flagged and rendered again with room)
@@ -653,7 +733,7 @@
                 atomicAdd(next_ctr + 3, (unsigned long long)__popcll(m));
             }
         }
-    } else if (W.exact_shade_lists) {   // (wave-uniform; 0.24 % of random directions)
+    } else if (!LEAN1 && W.exact_shade_lists) {   // (wave-uniform; 0.24 % of random directions)
         const bool listed = survive && slack_is_capped(__builtin_amdgcn_rcpf(next_d.x), __builtin_amdgcn_rcpf(next_d.y), __builtin_amdgcn_rcpf(next_d.z));
         if (wf_any(listed)) {
             const uint32_t slot = wf_reserve(&ctr[bounce + 1].exact_count, listed);
@@ -678,7 +758,7 @@
         if (!to_shadow) wf_prestage_miss(staging, out_slot, color, next_thr, ld3(S.background));
         if (W.use_entry) wf_entry_plane(queue_out, W.qcap_out)[next_idx] = S.prim_entry[PT_PRIM_INDEX(h.pid)];
     }
-    if (to_shadow) {
+    if (!LEAN1 && to_shadow) {
         float4* sq = shadow_q + (size_t)sh_idx * 4;
         sq[0] = make_float4(surf.pos.x, surf.pos.y, surf.pos.z, surf.normal.x);
         sq[1] = make_float4(surf.normal.y, surf.normal.z, surf.uv.x, surf.uv.y);
@@ -698,7 +778,7 @@
         }
     } else if ((NEXT || NEXT1) && elided) {   // the sample of a path whose next cast is known to miss
         wf_prestage_miss(staging, out_slot, color, next_thr, ld3(S.background));
-    } else if (live && hit && !survive && !(LEAN && cold)) {  // no light can contribute and the path ends: the sample is complete
+    } else if (live && hit && !survive && !((LEAN || LEAN1) && cold)) {  // no light can contribute and the path ends: the sample is complete
         float* out = staging + (size_t)out_slot * 3;
         out[0] = color.x;
         out[1] = color.y;
@@ -802,7 +882,7 @@
             have -= take;
             uint32_t mine = threadIdx.x < take ? agg[have + threadIdx.x] : 0u;
             __syncthreads();
-            if (W.sort_octants & 2u) {
+            if (!LEAN1 && (W.sort_octants & 2u)) {
                 // Material sorting (measured option, PT_WF_SORT=2): the 256 hits of a step are ordered by the model -
                 // i.e. the material - of the primitive they hit (8 classes, stable counting sort: ballot per class,
                 // mbcnt rank, prefix over classes and waves in LDS), so that a wavefront shades one material's

@@ -626,7 +626,7 @@ struct pt_scene {
         // the hits of queue 2 where the bounce-1 shade pass answers its survivors' casts from the bounce-2 hit cache itself: that
         // launch is still reading `hits`.  As long as queue 2 (20 B per record); like the cache it serves, not part of queue_bytes
         DeviceBuffer hits_next;
-        // the hand-over list of the lean shade pass of bounces 1 and 2 (k_wf_shade_fused<256 | 8192>): WF_HANDOVER_HEAD count
+        // the hand-over list of the lean shade pass of bounces 1 and 2 (k_wf_shade_fused<SB_VIS1 | SB_LEAN1>, code 8448): WF_HANDOVER_HEAD count
         // words by bounce, zeroed once per chunk, then queue indices - as long as the longer queue.  Not part of queue_bytes either
         DeviceBuffer handover;
         hipStream_t side = nullptr, side_wide = nullptr, side_exact = nullptr;
@@ -655,7 +655,7 @@ struct pt_scene {
         std::vector<uint8_t> plan_inline;
         std::vector<uint32_t> plan_last;   // per chunk of the plan: the last bounce that has a ray (later ones are not launched)
         bool plan_fresh = false, plan_failed = false;   // (failed: the device could not provide the plan's buffers)
-        // The lean bounce-0 variant (k_wf_shade_hits<2283 | 4096>).  lean: the last counted frame of the configuration was a
+        // The lean bounce-0 variant (k_wf_shade_hits<.. | SB_CONT_LOAD | SB_LEAN>, code 6379).  lean: the last counted frame of the configuration was a
         // planned one whose bounce-0 launches all loaded every cache with the escape answers in the records, and none of their
         // lanes cast for a light, lacked a record, ran the escape test or wrote a shadow record; lean_sig: the state of the
         // caches and masks it was counted under (lean_signature) - a frame under another state takes the general variant.
@@ -663,7 +663,7 @@ struct pt_scene {
         bool lean = false, stats_lean_ok = false;
         std::vector<uint64_t> lean_sig, stats_sig;
         const uint32_t* cold_words() const { return host + (size_t)n_slots * levels * 4u; }   // one word per line, behind the lines
-        // The lean shade pass of bounces 1 and 2 (k_wf_shade_fused<256 | 8192>), by bounce - 1.  b1_lean: the last counted frame
+        // The lean shade pass of bounces 1 and 2 (k_wf_shade_fused<SB_VIS1 | SB_LEAN1>, code 8448), by bounce - 1.  b1_lean: the last counted frame
         // of the configuration was a planned one that wrote at that bounce fewer shadow records than 1 / PT_B1_LEAN_SHARE of
         // the records it shaded (shadow records + those whose lights the fused pass added itself); b1_sig: the state it was
         // counted under (lean_sig's, plus that bounce's visibility and hit planes); stats_b1_sig: the same of the counts on
@@ -739,7 +739,7 @@ struct pt_scene {
     // materials, the light's colour or the bounces - so the frames of material and colour edits and of a steady state read
     // it instead of casting again.  One byte per item: two bits per light (scenes of at most four), 0 unknown / 1 not
     // blocked / 2 blocked.  No high-water mark: zero is "unknown", and the kernel that reads the plane casts for what it
-    // finds unknown and writes the answer back (k_wf_shade_hits<.. | 64>); a moved light or camera makes a new key (one
+    // finds unknown and writes the answer back (k_wf_shade_hits<.. | SB_VIS>); a moved light or camera makes a new key (one
     // memset, the allocation stays).  counter[0], [1]: times the plane was zeroed / launches of the variant.
     FrameCache vis_cache;
     // The closest hits of the bounce-1 rays of ONE view and ONE material table: in an opaque scene that ray is made from the
@@ -761,7 +761,7 @@ struct pt_scene {
     // throughput behind it: made from what the bounce-1 hits' key holds, so that key, its eligibility and its re-keying are
     // theirs.  Two planes of `stride` uint4 (pt_wf_shade_body.h CONT_STORE / CONT_LOAD), zeroed when they are keyed and filled
     // as a prefix with a mark of its own: by the bounce-0 launches of the chunks whose bounce-1 hits are stored in that frame
-    // (k_wf_shade_hits<.. | 1024>), read by the launches that read the bounce-1 hits themselves (<.. | 2048>).  A camera move
+    // (k_wf_shade_hits<.. | SB_CONT_STORE>), read by the launches that read the bounce-1 hits themselves (<.. | SB_CONT_LOAD>).  A camera move
     // resets the mark.  counter[0], [1], [2]: times the planes were zeroed / storing launches / loading launches; the hit
     // lanes a loading launch found without a record (none, ever) are word 6 of hit1_unknown.  pt_get_cont_cache_stats
     // (the escape test's answer in the records, PT_CONT_ESCAPE: escape_generation is bumped wherever the masks are built, dropped
@@ -775,10 +775,10 @@ struct pt_scene {
     // such launches that ran the test all the same are word 7 of hit1_unknown.  pt_get_cont_escape_stats)
     uint64_t cont_fill_generation = 0, cont_fill_mark = 0;
     uint64_t cont_fill_launches = 0, cont_fill_items = 0, cont_flagged_launches = 0;
-    // (the loading bounce-0 launches by variant - lean, k_wf_shade_hits<2283 | 4096>, and general - and the frames a lean launch
+    // (the loading bounce-0 launches by variant - lean, k_wf_shade_hits<.. | SB_LEAN> (6379), and general - and the frames a lean launch
     // flagged because it met a lane it does not contain the code for: none, ever.  pt_get_b0_lean_stats)
     uint64_t b0_lean_launches = 0, b0_general_launches = 0, b0_lean_guard_trips = 0;
-    // (the fused shade launches of bounces 1 and 2 by variant - lean, k_wf_shade_fused<256 | 8192> with its list pass behind it,
+    // (the fused shade launches of bounces 1 and 2 by variant - lean, k_wf_shade_fused<SB_VIS1 | SB_LEAN1> (8448) with its list pass behind it,
     // by bounce - 1, and general; the entries handed over are word 6 of those bounces' fused counter blocks.  pt_get_b1_lean_stats)
     uint64_t b1_lean_launches[2] = {0, 0}, b1_general_launches = 0;
     // The closest hits of the bounce-2 rays, same key: that ray is made from the bounce-1 hit, the material there and the
@@ -2507,7 +2507,7 @@ struct WfFrame {
     // the device counters of the fused shade launches of bounce b: behind the next bounce's counter of unknown casts
     unsigned long long* fused_ctr(uint32_t b) const { return b + 1u < HIT_BOUNCES ? bounce_hits[b + 1u].unknown : nullptr; }
     // PT_HIT1_FUSED (read per frame; 0: off): the bounce-0 kernel of a chunk that loads camera hits, visibility and bounce-1
-    // hits reads the bounce-1 plane itself (k_wf_shade_hits<.. | 128>) - no k_wf_hits_load at bounce 1
+    // hits reads the bounce-1 plane itself (k_wf_shade_hits<.. | SB_NEXT>) - no k_wf_hits_load at bounce 1
     bool hit1_fused = true;
     // the bounce-0 continuations (pt_scene::cont_cache), keyed like the bounce-1 hits; nullptr: not in use
     pt_scene::FrameCache* cont_cache = nullptr;
@@ -2521,8 +2521,8 @@ struct WfFrame {
     // (lean_frame); b1_lean_forced: the test hook PT_B1_LEAN_TEST_FORCE - it does whatever the counts said
     bool b1_lean[3] = {false, false, false}, b1_lean_forced = false;
     // PT_VIS1_FUSED (default 1), PT_HIT2_FUSED (default 0; both read per frame): the bounce-1 shade pass of a chunk whose batch has visibility bytes
-    // adds the lights of known visibility itself (k_wf_shade_fused<256>); ... and, where the chunk loads its bounce-2 hits, reads
-    // that plane itself too (<256 | 512>, the first switch on as well) - no k_wf_hits_load at bounce 2.  hits_next_wanted: this
+    // adds the lights of known visibility itself (k_wf_shade_fused<SB_VIS1>); ... and, where the chunk loads its bounce-2 hits, reads
+    // that plane itself too (<SB_VIS1 | SB_NEXT1>, the first switch on as well) - no k_wf_hits_load at bounce 2.  hits_next_wanted: this
     // frame may take the second, so queue_buffers provides WfPipe::hits_next
     bool hit2_fused = false, hits_next_wanted = false;   // (PT_VIS1_FUSED: vis_fused[1])
     uint32_t stats_line = 0, chunk_slot = 0;   // the frame's progress through its chunks
@@ -3138,39 +3138,39 @@ struct Chunk {
     // 3: the kernel computes the ChaCha block itself), 1 = shadow casts inside the shade kernel, 0 = none
     int grid_mode = 0;
     bool cached = false;   // the chunk's words are in the scene's word cache (rng_planes points there): GRID 3 reads them
-    // the scene's camera-hit cache (cached chunks only): 16 - the bounce-0 kernel stores the chunk's camera hits at hit_plane,
-    // 32 - it loads them instead of casting, 0 - neither
+    // the scene's camera-hit cache (cached chunks only): SB_STORE - the bounce-0 kernel stores the chunk's camera hits at
+    // hit_plane, SB_LOAD - it loads them instead of casting, 0 - neither
     int hit_mode = 0;
     uint4* hit_plane = nullptr;
     uint8_t* vis_plane = nullptr;   // the scene's shadow-visibility cache (chunks that load their hits only): the chunk's bytes, or null
-    // the scene's caches of later bounces' hits, by bounce (WfFrame::bounce_hits): 16 - k_wf_hits_store behind the bounce
-    // writes the chunk's records at `plane`, 32 - k_wf_hits_load takes the place of the bounce's casts, 0 - neither
+    // the scene's caches of later bounces' hits, by bounce (WfFrame::bounce_hits): SB_STORE - k_wf_hits_store behind the bounce
+    // writes the chunk's records at `plane`, SB_LOAD - k_wf_hits_load takes the place of the bounce's casts, 0 - neither
     struct BounceHits {
         int mode = 0;
         uint4* plane = nullptr;
     } bounce_hits[WfFrame::HIT_BOUNCES];
     int hits_mode(uint32_t bounce) const { return bounce < WfFrame::HIT_BOUNCES ? bounce_hits[bounce].mode : 0; }
-    // the bounce-0 kernel answers the bounce-1 casts from bounce_hits[1].plane itself (k_wf_shade_hits<.. | 128>): bounce 1
+    // the bounce-0 kernel answers the bounce-1 casts from bounce_hits[1].plane itself (k_wf_shade_hits<.. | SB_NEXT>): bounce 1
     // launches no k_wf_hits_load.  next_ctr: the cache's device counters (pt_scene::hit1_unknown)
     bool hit1_fused = false;
     unsigned long long* next_ctr = nullptr;
-    // the scene's cache of bounce-0 continuations: 1024 - the bounce-0 kernel stores the chunk's records at cont_plane (plane 1:
-    // cont_stride records behind), 2048 - it loads them instead of sampling the BRDF, 0 - neither
+    // the scene's cache of bounce-0 continuations: SB_CONT_STORE - the bounce-0 kernel stores the chunk's records at cont_plane
+    // (plane 1: cont_stride records behind), SB_CONT_LOAD - it loads them instead of sampling the BRDF, 0 - neither
     int cont_mode = 0;
     uint4* cont_plane = nullptr;
     size_t cont_stride = 0;
     uint32_t cont_flags = 0;   // bit 0: the records' escape answers hold for the scene's masks (the loading variant's flag argument)
-    bool lean = false;         // the loading launch is the lean variant (k_wf_shade_hits<2283 | 4096>)
+    bool lean = false;         // the loading launch is the lean variant (k_wf_shade_hits<.. | SB_LEAN>, code 6379)
     // the scene's shadow-visibility caches of bounces 1-4, by bounce: the bytes of the chunk's sample batch, or null (k_og_shadow_vis)
     uint8_t* bounce_vis_plane[WfFrame::HIT_BOUNCES] = {};
     uint8_t* vis_plane_of(uint32_t bounce) const { return bounce < WfFrame::HIT_BOUNCES ? bounce_vis_plane[bounce] : nullptr; }
-    // the bounce-1 shade pass reads bounce_vis_plane[1] itself (k_wf_shade_fused<256>), and bounce_hits[2].plane too (| 512): then bounce 2
+    // the bounce-1 shade pass reads bounce_vis_plane[1] itself (k_wf_shade_fused<SB_VIS1>), and bounce_hits[2].plane too (| SB_NEXT1): then bounce 2
     // launches no k_wf_hits_load and finds its hits in WfPipe::hits_next.  0: k_wf_shade.  Set at bounce 1, kept for bounce 2
     int b1_fused = 0;
-    // this bounce's shade pass is k_wf_shade_fused (bounce 1: b1_fused; bounces 2-4: 256, with that bounce's plane); 0: k_wf_shade
+    // this bounce's shade pass is k_wf_shade_fused (bounce 1: b1_fused; bounces 2-4: SB_VIS1, with that bounce's plane); 0: k_wf_shade
     int fused = 0;
-    // this bounce's fused pass (256 alone, bounce 1 or 2) is the lean variant, k_wf_shade_fused<256 | 8192>, with the list pass
-    // of the general body (<256 | 16384>) behind it
+    // this bounce's fused pass (SB_VIS1 alone, bounce 1 or 2) is the lean variant, k_wf_shade_fused<SB_VIS1 | SB_LEAN1> (8448), with
+    // the list pass of the general body (<SB_VIS1 | SB_HAND>, 16640) behind it
     bool lean1 = false;
     uint4* hits = nullptr;   // the hit plane of this bounce's queue (WfPipe::hits; hits_next: see above), W.hcap records long
     float4 *q_in = nullptr, *q_out = nullptr;
@@ -3257,7 +3257,7 @@ void trace_stage(pt_scene& s, const Frame& f, Chunk& c, Timeline& tl) {
     ++tl.launches;
 }
 
-// A bounce of a chunk whose hits one of the scene's hit caches holds (Chunk::bounce_hits, mode 32; `unknown`: that cache's
+// A bounce of a chunk whose hits one of the scene's hit caches holds (Chunk::bounce_hits, mode SB_LOAD; `unknown`: that cache's
 // counter), in place of trace_stage: k_wf_hits_load instead of k_wf_trace and k_wf_trace_wide, then k_wf_trace_exact for the
 // items without a record (normally none: the launch finds an empty list and returns).  All on the main stream, the shade pass
 // behind them unsplit: nothing is left that a second launch could run beside.  The shade pass before such a bounce listed no
@@ -3273,7 +3273,7 @@ void hits_load_stage(pt_scene& s, const Frame& f, Chunk& c, Timeline& tl, unsign
     W.split_deferred = 0u;
     W.exact_handover = f.env.exact;
     c.split_shade = false;
-    if (!(c.hit1_fused && b == 1u) && !((c.b1_fused & 512) && b == 2u)) {   // (... or whose bounce-1 shade pass did, bounce 2)
+    if (!(c.hit1_fused && b == 1u) && !((c.b1_fused & SB_NEXT1) && b == 2u)) {   // (... or whose bounce-1 shade pass did, bounce 2)
         const uint32_t grid = std::max(1u, std::min((uint32_t)s.n_cu * 16u, (W.qcap_in + 255u) / 256u));
         hipLaunchKernelGGL(k_wf_hits_load, dim3(grid), dim3(256), 0, c.st_main, W, (const float4*)c.q_in, c.hits,
                            (uint32_t*)pipe.exact[b & 1].p, c.wctr, (const uint4*)c.bounce_hits[b].plane, unknown);
@@ -3288,7 +3288,7 @@ void hits_load_stage(pt_scene& s, const Frame& f, Chunk& c, Timeline& tl, unsign
     ++tl.launches;
 }
 
-// Behind a bounce of a chunk that extends the prefix of one of the scene's hit caches (Chunk::bounce_hits, mode 16): the final
+// Behind a bounce of a chunk that extends the prefix of one of the scene's hit caches (Chunk::bounce_hits, mode SB_STORE): the final
 // hits of the bounce's queue to the plane.  On the main stream, before the next bounce's casts rewrite the chunk's hit plane,
 // the hand-over list and this bounce's exact list.  Only a chunk's first store is a stage of the timeline (PT_FLAG_TIMING): a
 // storing frame comes once per key, and its stage count stays one above a plain frame's whatever the number of planes.
@@ -3302,6 +3302,15 @@ void hits_store_stage(pt_scene& s, const Frame& f, const Chunk& c, Timeline& tl,
                        c.bounce_hits[c.b].plane, holes, holes ? (uint32_t)(g0 % holes) : 0u);
     HIP_CHECK(hipGetLastError());
     if (first) tl.end();
+}
+
+// launch(std::integral_constant<int, code>) for a code of one of the shade pass's tables (pt_wavefront.h WF_SHADE_*_CODES):
+// every listed variant is instantiated, a code that is not listed is an error.
+template <const auto& Codes, size_t I = 0, class F>
+void launch_variant(int code, F&& launch) {
+    if constexpr (I == std::size(Codes)) fail(PT_ERR_DEVICE, "internal error: no shade kernel for variant %d", code);
+    else if (code == Codes[I]) launch(std::integral_constant<int, Codes[I]>{});
+    else launch_variant<Codes, I + 1>(code, launch);
 }
 
 // k_wf_shade over the bounce's queue (split shade pass: then over the casts k_wf_trace_wide took meanwhile).
@@ -3330,16 +3339,16 @@ void shade_stage(pt_scene& s, const Frame& f, const WfFrame& wf, const Chunk& c,
                                (const uint32_t*)pipe.exact[b & 1].p, (const uint4*)c.hits, (uint32_t*)pipe.exact[(b + 1) & 1].p,
                                block_empty, c.wctr, f.gctr);
         };
-        if constexpr (G >= 8) dispatch([&](auto alpha) { go(alpha, std::false_type{}, std::true_type{}); }, f.alpha);
-        else if constexpr ((G & 3) >= 2) dispatch([&](auto alpha, auto count) { go(alpha, count, std::true_type{}); }, f.alpha, f.counting);
+        if constexpr ((G & SB_CACHED) != 0) dispatch([&](auto alpha) { go(alpha, std::false_type{}, std::true_type{}); }, f.alpha);
+        else if constexpr ((G & SB_GRID_MASK) >= 2) dispatch([&](auto alpha, auto count) { go(alpha, count, std::true_type{}); }, f.alpha, f.counting);
         else dispatch(go, f.alpha, f.counting, c.prim);
         HIP_CHECK(hipGetLastError());
     };
     // the cached opaque bounce-0 kernel with the camera-hit cache (k_wf_shade_hits): stores the chunk's hits or loads them;
-    // | 64, with the shadow-visibility cache (an overload with one parameter more): loads the hits, reads the chunk's
-    // visibility bytes and fills in the unknown; | 128, with the bounce-1 hit cache (three parameters more): answers the
-    // survivors' next casts from the chunk's records there; | 1024 / | 2048, with the continuation cache (two parameters
-    // more): stores the sampled direction and the throughput / loads them
+    // SB_VIS, with the shadow-visibility cache (an overload with one parameter more): loads the hits, reads the chunk's
+    // visibility bytes and fills in the unknown; SB_NEXT, with the bounce-1 hit cache (three parameters more): answers the
+    // survivors' next casts from the chunk's records there; SB_CONT_STORE / SB_CONT_LOAD, with the continuation cache (two
+    // parameters more, the loading variant's flags a third): stores the sampled direction and the throughput / loads them
     auto launch_hits = [&](auto grid) {
         constexpr int G = decltype(grid)::value;
         auto go = [&](auto... planes) {
@@ -3347,15 +3356,16 @@ void shade_stage(pt_scene& s, const Frame& f, const WfFrame& wf, const Chunk& c,
                                (const uint4*)c.rng_planes, c.hit_plane, c.q_out, (float4*)pipe.shadow.p, (float4*)pipe.contrib.p,
                                (float*)s.staging_buf.p, (uint32_t*)pipe.exact[(b + 1) & 1].p, block_empty, c.wctr, planes...);
         };
-        if constexpr (G & 2048) go(c.vis_plane, (const uint4*)c.bounce_hits[1].plane, (uint4*)pipe.hits.p, c.next_ctr, c.cont_plane, c.cont_stride, c.cont_flags);
-        else if constexpr ((G & 1024) && (G & 64)) go(c.vis_plane, c.cont_plane, c.cont_stride);
-        else if constexpr (G & 1024) go(c.cont_plane, c.cont_stride);
-        else if constexpr (G & 128) go(c.vis_plane, (const uint4*)c.bounce_hits[1].plane, (uint4*)pipe.hits.p, c.next_ctr);
-        else if constexpr (G & 64) go(c.vis_plane);
+        constexpr int taken = G & SB_PLANES;   // (the overload's plane bits)
+        if constexpr (taken == (SB_LOAD | SB_VIS | SB_NEXT | SB_CONT_LOAD)) go(c.vis_plane, (const uint4*)c.bounce_hits[1].plane, (uint4*)pipe.hits.p, c.next_ctr, c.cont_plane, c.cont_stride, c.cont_flags);
+        else if constexpr (taken == (SB_LOAD | SB_VIS | SB_CONT_STORE)) go(c.vis_plane, c.cont_plane, c.cont_stride);
+        else if constexpr (taken == (SB_STORE | SB_CONT_STORE)) go(c.cont_plane, c.cont_stride);
+        else if constexpr (taken == (SB_LOAD | SB_VIS | SB_NEXT)) go(c.vis_plane, (const uint4*)c.bounce_hits[1].plane, (uint4*)pipe.hits.p, c.next_ctr);
+        else if constexpr (taken == (SB_LOAD | SB_VIS)) go(c.vis_plane);
         else go();
         HIP_CHECK(hipGetLastError());
     };
-    // the bounce-1 shade pass that reads the bounce-1 visibility itself, | 512: and the bounce-2 hits (k_wf_shade_fused).  Stream
+    // the bounce-1 shade pass that reads the bounce-1 visibility itself, SB_NEXT1: and the bounce-2 hits (k_wf_shade_fused).  Stream
     // order: the bytes it reads on the main stream were written on the side stream by k_og_shadow_vis of an earlier chunk -
     // the chunk-end join of render_chunk put that behind this launch - or of an earlier frame, which the frame order (and, for a
     // frame on another stream, the cache's event) put there; chunks of one batch touch disjoint slots, and this launch
@@ -3366,58 +3376,28 @@ void shade_stage(pt_scene& s, const Frame& f, const WfFrame& wf, const Chunk& c,
                            (const float4*)c.q_in, shade_hits, (const uint4*)c.rng_planes, c.q_out, (float4*)pipe.shadow.p,
                            (float4*)pipe.contrib.p, (float*)s.staging_buf.p, shade_list, (const uint32_t*)pipe.exact[b & 1].p,
                            (const uint4*)c.hits, (uint32_t*)pipe.exact[(b + 1) & 1].p, c.wctr, (const uint8_t*)c.bounce_vis_plane[b],
-                           (const uint4*)c.bounce_hits[2].plane, (uint4*)pipe.hits_next.p, wf.fused_ctr(b));   // (the planes of | 512: bounce 1 only)
+                           (const uint4*)c.bounce_hits[2].plane, (uint4*)pipe.hits_next.p, wf.fused_ctr(b));   // (the planes of SB_NEXT1: bounce 1 only)
         HIP_CHECK(hipGetLastError());
     };
     auto launch_shade = [&] {
-        if (c.fused) {   // (bounces 1-4 of a chunk whose batch has that bounce's visibility bytes: render_chunk)
-            if (c.fused & 512) launch_fused(std::integral_constant<int, 256 | 512>{});
-            else if (c.lean1) {
-                // the lean variant lists what it cannot shade; the general body over that list follows at once - in front of
-                // this bounce's k_og_shadow_vis, the ev_shade record and the next bounce's k_wf_hits_load.  Always launched:
-                // a small grid that reads the count on the device
-                shade_list = (const uint32_t*)pipe.handover.p;
-                launch_fused(std::integral_constant<int, 256 | 8192>{});
-                const uint32_t whole = shade_grid;
-                shade_grid = std::min(shade_grid, (uint32_t)s.n_cu);
-                launch_fused(std::integral_constant<int, 256 | 16384>{});
-                shade_grid = whole;
-                shade_list = nullptr;
-            } else launch_fused(std::integral_constant<int, 256>{});
-            return;
-        }
-        if (c.grid_mode == 3 && c.cached && c.hit_mode) {
-            // GRIDX: 11 / 15 (orthographic branch) + 16 STORE / 32 LOAD + 64 VIS (LOAD only) + 128 NEXT (LOAD and VIS only)
-            // + 1024 CONT_STORE (STORE, or LOAD and VIS) / 2048 CONT_LOAD (NEXT only)
-            switch ((s.grids.ortho ? 15 : 11) | c.hit_mode | (c.hit_mode == 32 && c.vis_plane ? 64 : 0) | (c.hit1_fused ? 128 : 0) | c.cont_mode | (c.lean ? 4096 : 0)) {
-            case 235 | 2048 | 4096: launch_hits(std::integral_constant<int, 235 | 2048 | 4096>{}); break;
-            case 27 | 1024: launch_hits(std::integral_constant<int, 27 | 1024>{}); break;
-            case 31 | 1024: launch_hits(std::integral_constant<int, 31 | 1024>{}); break;
-            case 107 | 1024: launch_hits(std::integral_constant<int, 107 | 1024>{}); break;
-            case 111 | 1024: launch_hits(std::integral_constant<int, 111 | 1024>{}); break;
-            case 235 | 2048: launch_hits(std::integral_constant<int, 235 | 2048>{}); break;
-            case 239 | 2048: launch_hits(std::integral_constant<int, 239 | 2048>{}); break;
-            case 27: launch_hits(std::integral_constant<int, 27>{}); break;
-            case 43: launch_hits(std::integral_constant<int, 43>{}); break;
-            case 31: launch_hits(std::integral_constant<int, 31>{}); break;
-            case 47: launch_hits(std::integral_constant<int, 47>{}); break;
-            case 107: launch_hits(std::integral_constant<int, 107>{}); break;
-            case 111: launch_hits(std::integral_constant<int, 111>{}); break;
-            case 235: launch_hits(std::integral_constant<int, 235>{}); break;
-            default: launch_hits(std::integral_constant<int, 239>{}); break;
-            }
-            return;
-        }
-        switch (c.grid_mode == 0 ? 0 : c.grid_mode + (s.grids.ortho ? 4 : 0) + ((c.grid_mode == 3 && c.cached) ? 8 : 0)) {
-        case 0: launch(std::integral_constant<int, 0>{}); break;
-        case 1: launch(std::integral_constant<int, 1>{}); break;
-        case 2: launch(std::integral_constant<int, 2>{}); break;
-        case 3: launch(std::integral_constant<int, 3>{}); break;
-        case 5: launch(std::integral_constant<int, 5>{}); break;
-        case 6: launch(std::integral_constant<int, 6>{}); break;
-        case 11: launch(std::integral_constant<int, 11>{}); break;
-        case 15: launch(std::integral_constant<int, 15>{}); break;
-        default: launch(std::integral_constant<int, 7>{}); break;
+        const bool cached_b0 = c.grid_mode == 3 && c.cached;
+        if (c.fused && c.lean1) {   // (bounce 1 or 2, SB_VIS1 alone: render_chunk)
+            // the lean variant lists what it cannot shade; the general body over that list follows at once - in front of
+            // this bounce's k_og_shadow_vis, the ev_shade record and the next bounce's k_wf_hits_load.  Always launched:
+            // a small grid that reads the count on the device
+            shade_list = (const uint32_t*)pipe.handover.p;
+            launch_variant<WF_SHADE_FUSED_CODES>(wf_shade_fused_code((c.fused & SB_NEXT1) != 0, true, false), launch_fused);
+            const uint32_t whole = shade_grid;
+            shade_grid = std::min(shade_grid, (uint32_t)s.n_cu);
+            launch_variant<WF_SHADE_FUSED_CODES>(wf_shade_fused_code(false, false, true), launch_fused);
+            shade_grid = whole;
+            shade_list = nullptr;
+        } else if (c.fused) {   // (bounces 1-4 of a chunk whose batch has that bounce's visibility bytes: render_chunk)
+            launch_variant<WF_SHADE_FUSED_CODES>(wf_shade_fused_code((c.fused & SB_NEXT1) != 0, false, false), launch_fused);
+        } else if (cached_b0 && c.hit_mode) {
+            launch_variant<WF_SHADE_HITS_CODES>(wf_shade_hits_code(s.grids.ortho, c.hit_mode, c.vis_plane != nullptr, c.hit1_fused, c.cont_mode, c.lean), launch_hits);
+        } else {
+            launch_variant<WF_SHADE_CODES>(wf_shade_code(c.grid_mode, s.grids.ortho, cached_b0), launch);
         }
     };
     launch_shade();
@@ -3557,26 +3537,26 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
     if (c.cached) {
         // the camera hits: loaded by the bounce-0 kernel, or stored by it; anything else casts as before.  The shadow
         // visibility: a chunk that loads its hits and lies wholly below the plane's stride
-        c.hit_mode = reads(wf.hit_cache) ? 32 : extends(wf.hit_cache) ? 16 : 0;
+        c.hit_mode = reads(wf.hit_cache) ? SB_LOAD : extends(wf.hit_cache) ? SB_STORE : 0;
         if (c.hit_mode) c.hit_plane = (uint4*)wf.hit_cache->buf.p + g0;
-        if (c.hit_mode == 32 && wf.vis_cache && g1 <= wf.vis_cache->stride) c.vis_plane = (uint8_t*)wf.vis_cache->buf.p + g0;
+        if (c.hit_mode == SB_LOAD && wf.vis_cache && g1 <= wf.vis_cache->stride) c.vis_plane = (uint8_t*)wf.vis_cache->buf.p + g0;
     }
     // the later bounces' hits: loaded in place of the bounce's casts, or stored behind them; anything else casts as before
     for (uint32_t b = 1; b < WfFrame::HIT_BOUNCES; ++b) {
         const pt_scene::FrameCache* fc = wf.bounce_hits[b].cache;
         Chunk::BounceHits& bh = c.bounce_hits[b];
-        bh.mode = reads(fc) ? 32 : extends(fc) ? 16 : 0;
+        bh.mode = reads(fc) ? SB_LOAD : extends(fc) ? SB_STORE : 0;
         if (bh.mode) bh.plane = (uint4*)fc->buf.p + g0;
-        if (bh.mode == 32 && wf.stats_slots && wf.stats_line < wf.stats_slots) wf.fs->stats_hit_loads |= 1u << b;
+        if (bh.mode == SB_LOAD && wf.stats_slots && wf.stats_line < wf.stats_slots) wf.fs->stats_hit_loads |= 1u << b;
     }
     // ... and the bounce-1 hits by the bounce-0 kernel itself, where that loads the camera hits and the visibility too
-    c.hit1_fused = wf.hit1_fused && c.hit_mode == 32 && c.vis_plane != nullptr && c.hits_mode(1u) == 32;
+    c.hit1_fused = wf.hit1_fused && c.hit_mode == SB_LOAD && c.vis_plane != nullptr && c.hits_mode(1u) == SB_LOAD;
     c.next_ctr = wf.bounce_hits[1].unknown;
     // the continuations: loaded by the launch that reads the bounce-1 hits itself where the chunk lies below their mark too;
     // stored by the bounce-0 launch of a chunk whose bounce-1 hits are stored in this frame - one that stores its camera hits,
     // or loads them with the visibility - where the chunk is next above the mark and the budget has room for it
-    if (c.hit1_fused && reads(wf.cont_cache)) c.cont_mode = 2048;
-    else if (c.hits_mode(1u) == 16 && extends(wf.cont_cache) && (c.hit_mode == 16 || (c.hit_mode == 32 && c.vis_plane))) c.cont_mode = 1024;
+    if (c.hit1_fused && reads(wf.cont_cache)) c.cont_mode = SB_CONT_LOAD;
+    else if (c.hits_mode(1u) == SB_STORE && extends(wf.cont_cache) && (c.hit_mode == SB_STORE || (c.hit_mode == SB_LOAD && c.vis_plane))) c.cont_mode = SB_CONT_STORE;
     if (c.cont_mode) {
         c.cont_plane = (uint4*)wf.cont_cache->buf.p + g0;
         c.cont_stride = (size_t)wf.cont_cache->stride;
@@ -3605,7 +3585,7 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
         }
         if (s.cont_fill_mark >= wf.cont_cache->mark) s.cont_escape_generation = s.escape_generation;
     }
-    if (c.cont_mode == 2048 && wf.cont_escape && f.dev.escape &&
+    if (c.cont_mode == SB_CONT_LOAD && wf.cont_escape && f.dev.escape &&
         (s.cont_escape_generation == s.escape_generation || (s.cont_fill_generation == s.escape_generation && g1 <= s.cont_fill_mark))) {
         c.cont_flags = 1u;
         ++s.cont_flagged_launches;
@@ -3614,8 +3594,8 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
     // without masks: nobody asks), in a frame of a configuration that was counted clean; a counted frame with any other
     // bounce-0 launch is not a clean one
     {
-        const bool answered = c.cont_mode == 2048 && ((c.cont_flags & 1u) != 0u || !f.dev.escape);
-        c.lean = c.cont_mode == 2048 && !s.grids.ortho && ((wf.lean && answered) || wf.lean_forced);
+        const bool answered = c.cont_mode == SB_CONT_LOAD && ((c.cont_flags & 1u) != 0u || !f.dev.escape);
+        c.lean = c.cont_mode == SB_CONT_LOAD && !s.grids.ortho && ((wf.lean && answered) || wf.lean_forced);
         if (wf.stats_slots && wf.stats_line < wf.stats_slots && !answered) wf.fs->stats_lean_ok = false;
     }
     // the shadow visibility of bounces 1-4: indexed by the sample's slot in its batch's staging area, which any chunk of the
@@ -3683,21 +3663,21 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
         // known itself; ... and, where the chunk loads its bounce-2 hits, answers its survivors' casts from that plane.  A
         // scene with the orthographic branch takes k_wf_shade, and so does a frame with a sorting option (PT_WF_SORT): the
         // kernel keeps its counts in the LDS row those options write.
-        // Bounces 2-4 with a plane of their own: the same pass (256 alone: the next hits are k_wf_hits_load's), with that
+        // Bounces 2-4 with a plane of their own: the same pass (SB_VIS1 alone: the next hits are k_wf_hits_load's), with that
         // bounce's bytes and a counter block of that bounce's own (WfFrame::fused_ctr).
         c.fused = 0;
         if (b < WfFrame::HIT_BOUNCES && wf.vis_fused[b] && c.vis_plane_of(b) && c.grid_mode == 0 && f.use_light_grids && !f.alpha && !f.counting && !s.grids.ortho && f.env.sort == 0u)
-            c.fused = 256 | ((b == 1u && wf.hit2_fused && c.hits_mode(2u) == 32 && pipe.hits_next.bytes >= (size_t)W.qcap_out * 20u) ? 512 : 0);
+            c.fused = SB_VIS1 | ((b == 1u && wf.hit2_fused && c.hits_mode(2u) == SB_LOAD && pipe.hits_next.bytes >= (size_t)W.qcap_out * 20u) ? SB_NEXT1 : 0);
         if (b == 1u) c.b1_fused = c.fused;
         // (the hits of bounce 2 in such a chunk: a plane of their own, as long as the queue)
-        c.hits = (b == 2u && (c.b1_fused & 512)) ? (uint4*)pipe.hits_next.p : (uint4*)pipe.hits.p;
-        W.hcap = (b == 2u && (c.b1_fused & 512)) ? W.qcap_in : wf.cap_h;
+        c.hits = (b == 2u && (c.b1_fused & SB_NEXT1)) ? (uint4*)pipe.hits_next.p : (uint4*)pipe.hits.p;
+        W.hcap = (b == 2u && (c.b1_fused & SB_NEXT1)) ? W.qcap_in : wf.cap_h;
         // (a chunk that loads the next bounce's hits: the rays k_wf_trace would leave to k_wf_trace_exact have records like any
         // other, so this bounce's shade pass lists none of them - the exact list of the next bounce is k_wf_hits_load's, for
         // the items without one)
-        W.exact_shade_lists = (f.env.exact == 2u && c.hits_mode(b + 1u) != 32) ? 1u : 0u;
+        W.exact_shade_lists = (f.env.exact == 2u && c.hits_mode(b + 1u) != SB_LOAD) ? 1u : 0u;
         const int hits_mode = c.hits_mode(b);
-        if (hits_mode == 32) {
+        if (hits_mode == SB_LOAD) {
             hits_load_stage(s, f, c, tl, wf.bounce_hits[b].unknown);
             wf.bounce_hits[b].cache->touched(c.st_main);   // (no device sync before the plane is zeroed for a new key: the readers count)
             ++wf.bounce_hits[b].cache->counter[2];
@@ -3707,14 +3687,14 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
         // The lean variant of the plain fused pass, bounces 1 and 2 (lean_frame: the counts say that next to no record of this
         // bounce needs the shadow queue, or the test hook): a matter of speed only - the list pass shades what it leaves.
         // (Not where the shade pass is split in two launches: the second one has a list of its own.)
-        c.lean1 = lean1_frame && c.fused == 256 && (b == 1u || b == 2u) && W.exact_shade_lists == 0u && !c.split_shade &&
+        c.lean1 = lean1_frame && c.fused == SB_VIS1 && (b == 1u || b == 2u) && W.exact_shade_lists == 0u && !c.split_shade &&
                   (wf.b1_lean[b] || wf.b1_lean_forced) && pipe.handover.bytes >= ((size_t)W.qcap_in + WF_HANDOVER_HEAD) * 4u;
         shade_stage(s, f, wf, c, tl);
-        if (c.prim && c.hit_mode == 16) {   // the records are behind this launch: the prefix grows by the chunk
+        if (c.prim && c.hit_mode == SB_STORE) {   // the records are behind this launch: the prefix grows by the chunk
             wf.hit_cache->touched(c.st_main);
             wf.hit_cache->mark = g1;
             ++wf.hit_cache->counter[0];
-        } else if (c.prim && c.hit_mode == 32) {
+        } else if (c.prim && c.hit_mode == SB_LOAD) {
             ++wf.hit_cache->counter[1];
             if (c.hit1_fused) {   // (the bounce-1 plane is read here: its event and its count of loads follow at bounce 1)
                 wf.bounce_hits[1].cache->touched(c.st_main);
@@ -3725,13 +3705,13 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
                 ++wf.vis_cache->counter[1];
             }
         }
-        if (c.prim && c.cont_mode == 1024) {   // the records are behind this launch: the prefix grows by the chunk
+        if (c.prim && c.cont_mode == SB_CONT_STORE) {   // the records are behind this launch: the prefix grows by the chunk
             wf.cont_cache->touched(c.st_main);
             // (the masks this launch evaluated the escape test with: one generation for the whole prefix, or none)
             s.cont_escape_generation = (wf.cont_cache->mark == 0 || s.cont_escape_generation == s.escape_generation) ? s.escape_generation : 0;
             wf.cont_cache->mark = g1;
             ++wf.cont_cache->counter[1];
-        } else if (c.prim && c.cont_mode == 2048) {   // (no device sync before the planes are zeroed for a new key: the readers count)
+        } else if (c.prim && c.cont_mode == SB_CONT_LOAD) {   // (no device sync before the planes are zeroed for a new key: the readers count)
             wf.cont_cache->touched(c.st_main);
             ++wf.cont_cache->counter[2];
             ++(c.lean ? s.b0_lean_launches : s.b0_general_launches);
@@ -3739,14 +3719,14 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
         if (c.fused && (b == 1u || b == 2u)) ++(c.lean1 ? s.b1_lean_launches[b - 1u] : s.b1_general_launches);
         if (c.fused) {
             ++s.fused_launches(b);   // (by bounce: b1_fused_launches counts bounce 1's alone)
-            if (c.fused & 512) wf.bounce_hits[2].cache->touched(c.st_main);   // (read here: its count of loads follows at bounce 2)
+            if (c.fused & SB_NEXT1) wf.bounce_hits[2].cache->touched(c.st_main);   // (read here: its count of loads follows at bounce 2)
         }
         shadow_stage(s, f, c, tl);
         if (c.vis_plane_of(b) && c.grid_mode == 0) {   // (k_og_shadow_vis, on the side stream; any such launch may write the plane)
             wf.bounce_vis[b]->touched(c.st_shadow);
             ++wf.bounce_vis[b]->counter[1];
         }
-        if (hits_mode == 16) {   // the records are behind this launch: the prefix grows by the chunk
+        if (hits_mode == SB_STORE) {   // the records are behind this launch: the prefix grows by the chunk
             hits_store_stage(s, f, c, tl, wf.bounce_hits[b].holes, g0, !stored);
             stored = true;
             wf.bounce_hits[b].cache->touched(c.st_main);
@@ -3755,7 +3735,7 @@ void render_chunk(pt_scene& s, const Frame& f, WfFrame& wf, Timeline& tl, const 
         }
     }
     for (uint32_t b = b_end + 1u; b < WfFrame::HIT_BOUNCES; ++b)   // (a chunk without a ray at that bounce: nothing to store)
-        if (c.bounce_hits[b].mode == 16) wf.bounce_hits[b].cache->mark = g1;
+        if (c.bounce_hits[b].mode == SB_STORE) wf.bounce_hits[b].cache->mark = g1;
     // the next chunk clears the counters and reuses the queues, accumulate reads the staging area:
     // join the side stream
     if (c.st_shadow != c.st_main) HIP_CHECK(hipStreamWaitEvent(c.st_main, pipe.ev_shadow, 0));
@@ -7085,17 +7065,17 @@ int pt_kernel_occupancy(int device, int which, int* blocks_per_cu) {
         if (which == 0)
             HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_wf_shade<false, false, true, 3>, WF_SHADE_THREADS, 0));
         else if (which == 2)
-            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, (WfShadeHitsKernel)k_wf_shade_hits<(11 | 16)>, WF_SHADE_THREADS, 0));
+            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, (WfShadeHitsKernel)k_wf_shade_hits<(SB_B0_CACHED | SB_STORE)>, WF_SHADE_THREADS, 0));
         else if (which == 3)
-            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, (WfShadeHitsKernel)k_wf_shade_hits<(11 | 32)>, WF_SHADE_THREADS, 0));
+            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, (WfShadeHitsKernel)k_wf_shade_hits<(SB_B0_CACHED | SB_LOAD)>, WF_SHADE_THREADS, 0));
         else if (which == 4)
-            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, (WfShadeVisKernel)k_wf_shade_hits<(11 | 32 | 64)>, WF_SHADE_THREADS, 0));
+            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, (WfShadeVisKernel)k_wf_shade_hits<(SB_B0_CACHED | SB_LOAD | SB_VIS)>, WF_SHADE_THREADS, 0));
         else if (which == 6)
-            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, (WfShadeContLoadKernel)k_wf_shade_hits<(11 | 32 | 64 | 128 | 2048)>, WF_SHADE_THREADS, 0));
+            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, (WfShadeContLoadKernel)k_wf_shade_hits<(SB_B0_CACHED | SB_LOAD | SB_VIS | SB_NEXT | SB_CONT_LOAD)>, WF_SHADE_THREADS, 0));
         else if (which == 5)
-            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, (WfShadeVisKernel)k_wf_shade_hits<(15 | 32 | 64)>, WF_SHADE_THREADS, 0));
+            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, (WfShadeVisKernel)k_wf_shade_hits<(SB_B0_CACHED_DIRL | SB_LOAD | SB_VIS)>, WF_SHADE_THREADS, 0));
         else
-            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_wf_shade<false, false, true, 11>, WF_SHADE_THREADS, 0));
+            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_wf_shade<false, false, true, SB_B0_CACHED>, WF_SHADE_THREADS, 0));
     });
 }
 int pt_scene_get_info(const pt_scene* scene, pt_scene_info* out) {

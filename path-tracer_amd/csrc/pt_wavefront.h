@@ -142,7 +142,7 @@ struct WfCounters {  // one set per bounce level, zeroed once per chunk
     uint32_t deferred_count; // casts k_wf_trace left to k_wf_trace_wide in its drain phase
     uint32_t exact_count;    // casts k_wf_trace left to k_wf_trace_exact when it fetched them (slack_is_capped)
     // records of queue[b] that were never written: the bounce-0 kernel that reads the bounce-1 hit cache found the record's
-    // cast a miss behind a final colour (k_wf_shade_hits<.. | 128>).  A frame that casts writes queue_count + elided_count.
+    // cast a miss behind a final colour (k_wf_shade_hits<.. | SB_NEXT>).  A frame that casts writes queue_count + elided_count.
     uint32_t elided_count;
     // ... and what the bounce-1 shade pass that adds the known lights itself (k_wf_shade_fused) did not write: the survivors it
     // ended or elided count in elided_count of the next bounce; inlined_count - records of this bounce's shadow queue; of
@@ -2031,35 +2031,151 @@ enum : uint32_t { PK_BRDF = 0, PK_NORMAL = 11, PK_VIEW = 14, PK_UV = 17, PK_PID 
                   PK_COLOR = 26, PK_TERM0 = 29, WF_PARK_SLOTS = 32, PK_VIS = 32,   // (PK_VIS: the VIS variants' one slot more)
                   PK_NEXT = 33 };   // (PK_NEXT: the NEXT variants' four more - the item's bounce-1 hit record)
 static_assert(WF_PARK_SLOTS + 1u + 4u <= 39, "four workgroups of the bounce-0 kernel must fit a CU's LDS");
-// GRID (origin grids, pt_grid.h): 0 - none: direct light goes through the shadow queue and k_wf_shadow / k_og_shadow;
-// 1 - every light is a point light with a grid: get_light_info (mod.rs:281-333) is evaluated HERE, light after
-//     light, so a surface costs no shadow record, no contrib entries and no colour patch (190 B of queue traffic
-//     per shaded hit); only surfaces whose normal is too long for the grids' margin still take the queue;
-// 2 - (bounce 0) 1 + the camera ray is cast HERE through the camera grid: no hits[] round trip, and the 44 % of
-//     the samples that leave into the background never reach a second kernel;
-// 3 - (bounce 0) 2 + the item's ChaCha12 block is computed HERE instead of by k_wf_rng: the ~800 integer
-//     instructions per item run underneath the memory latency of the casts, and only the paths that go on write
-//     the words of bounces 1 and 2 (plane 1 of the RNG planes; a path has made at least four draws by then).
-// GRIDX = GRID + 4 * DIRL + 8 * CACHED; DIRL: some light is directional (orthographic grid branch of og_light_radiance
-// compiled in).  CACHED (GRID 3 only): words 0-7 of the item's block are READ from the scene's word cache (pt_gpu.hip
-// FrameCache rng_cache: rng_planes points at the chunk's first item there, W.cap is the cache's stride, W.rng_first_plane 0) - the raw
-// words, not the screen position: that depends on the camera, the words on the item enumeration alone.
-// + 16 * STORE + 32 * LOAD (CACHED, opaque, bounce 0 only; k_wf_shade_hits below): the scene's camera-hit cache (pt_gpu.hip
-// FrameCache hit_cache; hit_plane points at the chunk's first item there).  The closest hit of a camera ray depends on the item
-// enumeration, the camera and the geometry - not on the lights, the bounces or, in an opaque scene, the materials - so
-// STORE writes pack_hit of the cast's result for every item, and LOAD reads that record instead of casting: no og_cell on
-// the camera grid, no og_next_hit.  The ray itself is still derived: shading needs o and d.
-// + 64 * VIS (LOAD only; the second k_wf_shade_hits below): the scene's shadow-visibility cache (pt_gpu.hip FrameCache vis_cache;
-// vis_plane points at the chunk's first item there) - a light whose bits are known is not cast for.
-// + 128 * NEXT (LOAD and VIS only; the third k_wf_shade_hits below): the scene's bounce-1 hit cache (pt_gpu.hip FrameCache
-// hit1_cache; next_plane points at the chunk's first item there) - the survivors' next casts are answered here.
-// + 1024 * CONT_STORE (STORE, or LOAD and VIS, without NEXT) / + 2048 * CONT_LOAD (NEXT only; the last three k_wf_shade_hits
-// below): the scene's cache of bounce-0 continuations (pt_gpu.hip FrameCache cont_cache) - the sampled direction and the
-// throughput of the bounce-1 ray are written once per view and material table and read afterwards, not computed.
-// (S and W FIRST, in this order: the PARK variants read them again through the kernarg segment, wf_opaque_arg)
+// The variants of the shade pass: one code, GRIDX, made of the feature bits below.  k_wf_shade takes the codes of
+// WF_SHADE_CODES, the overloads of k_wf_shade_hits those of WF_SHADE_HITS_CODES, k_wf_shade_fused those of
+// WF_SHADE_FUSED_CODES: the tables say which variants exist, the functions behind them choose one, and the static_asserts
+// there prove that what the host can ask for is exactly what the tables hold (adding a variant: DESIGN.md, "A new shade variant").
+enum : int {
+    // GRID (origin grids, pt_grid.h): 0 - none: direct light goes through the shadow queue and k_wf_shadow / k_og_shadow;
+    // 1 - every light is a point light with a grid: get_light_info (mod.rs:281-333) is evaluated HERE, light after
+    //     light, so a surface costs no shadow record, no contrib entries and no colour patch (190 B of queue traffic
+    //     per shaded hit); only surfaces whose normal is too long for the grids' margin still take the queue;
+    // 2 - (bounce 0) 1 + the camera ray is cast HERE through the camera grid: no hits[] round trip, and the 44 % of
+    //     the samples that leave into the background never reach a second kernel;
+    // 3 - (bounce 0) 2 + the item's ChaCha12 block is computed HERE instead of by k_wf_rng: the ~800 integer
+    //     instructions per item run underneath the memory latency of the casts, and only the paths that go on write
+    //     the words of bounces 1 and 2 (plane 1 of the RNG planes; a path has made at least four draws by then).
+    SB_GRID_MASK = 3,
+    // DIRL: some light is directional (orthographic grid branch of og_light_radiance compiled in).
+    SB_DIRL = 4,
+    // CACHED (GRID 3 only): words 0-7 of the item's block are READ from the scene's word cache (pt_gpu.hip FrameCache
+    // rng_cache: rng_planes points at the chunk's first item there, W.cap is the cache's stride, W.rng_first_plane 0) - the raw
+    // words, not the screen position: that depends on the camera, the words on the item enumeration alone.
+    SB_CACHED = 8,
+    // STORE / LOAD (CACHED, opaque, bounce 0 only; k_wf_shade_hits below): the scene's camera-hit cache (pt_gpu.hip
+    // FrameCache hit_cache; hit_plane points at the chunk's first item there).  The closest hit of a camera ray depends on the item
+    // enumeration, the camera and the geometry - not on the lights, the bounces or, in an opaque scene, the materials - so
+    // STORE writes pack_hit of the cast's result for every item, and LOAD reads that record instead of casting: no og_cell on
+    // the camera grid, no og_next_hit.  The ray itself is still derived: shading needs o and d.
+    SB_STORE = 16,
+    SB_LOAD = 32,
+    // VIS (LOAD only; the second k_wf_shade_hits below): the scene's shadow-visibility cache (pt_gpu.hip FrameCache vis_cache;
+    // vis_plane points at the chunk's first item there) - a light whose bits are known is not cast for.
+    SB_VIS = 64,
+    // NEXT (LOAD and VIS only; the third k_wf_shade_hits below): the scene's bounce-1 hit cache (pt_gpu.hip FrameCache
+    // hit1_cache; next_plane points at the chunk's first item there) - the survivors' next casts are answered here.
+    SB_NEXT = 128,
+    // VIS1, NEXT1 (k_wf_shade_fused below): the later-bounce pass that reads its bounce's shadow-visibility bytes itself, and
+    // the next bounce's hit cache as well.
+    SB_VIS1 = 256,
+    SB_NEXT1 = 512,
+    // CONT_STORE (STORE, or LOAD and VIS, without NEXT) / CONT_LOAD (NEXT only; the last three k_wf_shade_hits below): the
+    // scene's cache of bounce-0 continuations (pt_gpu.hip FrameCache cont_cache) - the sampled direction and the throughput
+    // of the bounce-1 ray are written once per view and material table and read afterwards, not computed.
+    SB_CONT_STORE = 1024,
+    SB_CONT_LOAD = 2048,
+    // LEAN (CONT_LOAD without DIRL), LEAN1 / HAND (VIS1 alone): the steady frame's variants at five waves per SIMD, and the
+    // general body over what LEAN1 hands over (pt_wf_shade_body.h).
+    SB_LEAN = 4096,
+    SB_LEAN1 = 8192,
+    SB_HAND = 16384,
+    // the two bases of the cached opaque bounce-0 kernel, and the bits that say which planes a k_wf_shade_hits overload takes
+    SB_B0_CACHED = 3 | SB_CACHED,
+    SB_B0_CACHED_DIRL = SB_B0_CACHED | SB_DIRL,
+    SB_PLANES = SB_STORE | SB_LOAD | SB_VIS | SB_NEXT | SB_CONT_STORE | SB_CONT_LOAD,
+};
+// The variants that exist.  (The numbers are pinned below: the tests, DESIGN.md and profiles/ know the kernels by them.)
+constexpr int WF_SHADE_CODES[] = {0, 1, 2, 3, 1 | SB_DIRL, 2 | SB_DIRL, 3 | SB_DIRL, SB_B0_CACHED, SB_B0_CACHED_DIRL};
+constexpr int WF_SHADE_HITS_CODES[] = {
+    SB_B0_CACHED | SB_STORE, SB_B0_CACHED_DIRL | SB_STORE,
+    SB_B0_CACHED | SB_LOAD, SB_B0_CACHED_DIRL | SB_LOAD,
+    SB_B0_CACHED | SB_LOAD | SB_VIS, SB_B0_CACHED_DIRL | SB_LOAD | SB_VIS,
+    SB_B0_CACHED | SB_LOAD | SB_VIS | SB_NEXT, SB_B0_CACHED_DIRL | SB_LOAD | SB_VIS | SB_NEXT,
+    SB_B0_CACHED | SB_STORE | SB_CONT_STORE, SB_B0_CACHED_DIRL | SB_STORE | SB_CONT_STORE,
+    SB_B0_CACHED | SB_LOAD | SB_VIS | SB_CONT_STORE, SB_B0_CACHED_DIRL | SB_LOAD | SB_VIS | SB_CONT_STORE,
+    SB_B0_CACHED | SB_LOAD | SB_VIS | SB_NEXT | SB_CONT_LOAD, SB_B0_CACHED_DIRL | SB_LOAD | SB_VIS | SB_NEXT | SB_CONT_LOAD,
+    SB_B0_CACHED | SB_LOAD | SB_VIS | SB_NEXT | SB_CONT_LOAD | SB_LEAN};
+constexpr int WF_SHADE_FUSED_CODES[] = {SB_VIS1, SB_VIS1 | SB_NEXT1, SB_VIS1 | SB_LEAN1, SB_VIS1 | SB_HAND};
+template <int N>
+constexpr bool sb_same(const int (&a)[N], const int (&b)[N]) {
+    for (int k = 0; k < N; ++k)
+        if (a[k] != b[k]) return false;
+    return true;
+}
+template <int N>
+constexpr bool sb_listed(const int (&codes)[N], int code) {
+    for (int c : codes)
+        if (c == code) return true;
+    return false;
+}
+static_assert(sb_same(WF_SHADE_CODES, {0, 1, 2, 3, 5, 6, 7, 11, 15}), "the codes of k_wf_shade");
+static_assert(sb_same(WF_SHADE_HITS_CODES, {27, 31, 43, 47, 107, 111, 235, 239, 1051, 1055, 1131, 1135, 2283, 2287, 6379}), "the codes of k_wf_shade_hits");
+static_assert(sb_same(WF_SHADE_FUSED_CODES, {256, 768, 8448, 16640}), "the codes of k_wf_shade_fused");
+// What the host chooses a variant from, and what render_chunk (pt_gpu.hip) guarantees about it.  k_wf_shade: the grid mode,
+// the orthographic branch (no grid mode: no branch), the word cache (GRID 3 only).
+constexpr int wf_shade_code(int grid, bool ortho, bool cached) { return grid == 0 ? 0 : grid | (ortho ? SB_DIRL : 0) | (cached ? SB_CACHED : 0); }
+constexpr bool wf_shade_legal(int grid, bool cached) { return grid >= 0 && grid <= SB_GRID_MASK && (!cached || grid == 3); }
+// k_wf_shade_hits: hits - SB_STORE or SB_LOAD; cont - 0, SB_CONT_STORE or SB_CONT_LOAD.
+constexpr int wf_shade_hits_code(bool ortho, int hits, bool vis, bool next, int cont, bool lean) {
+    return (ortho ? SB_B0_CACHED_DIRL : SB_B0_CACHED) | hits | (vis ? SB_VIS : 0) | (next ? SB_NEXT : 0) | cont | (lean ? SB_LEAN : 0);
+}
+constexpr bool wf_shade_hits_legal(bool ortho, int hits, bool vis, bool next, int cont, bool lean) {
+    return (hits == SB_STORE || hits == SB_LOAD) && (!vis || hits == SB_LOAD) && (!next || (hits == SB_LOAD && vis)) &&
+           (cont == 0 || (cont == SB_CONT_LOAD && next) || (cont == SB_CONT_STORE && !next && (hits == SB_STORE || vis))) &&
+           (!lean || (cont == SB_CONT_LOAD && !ortho));
+}
+// k_wf_shade_fused: at most one of NEXT1, LEAN1 and HAND beside VIS1.
+constexpr int wf_shade_fused_code(bool next1, bool lean1, bool hand) { return SB_VIS1 | (next1 ? SB_NEXT1 : 0) | (lean1 ? SB_LEAN1 : 0) | (hand ? SB_HAND : 0); }
+constexpr bool wf_shade_fused_legal(bool next1, bool lean1, bool hand) { return (int)next1 + (int)lean1 + (int)hand <= 1; }
+// Input tuple t of each family: its code, or -1 where render_chunk cannot produce it.
+constexpr int wf_shade_tuple(int t) { return wf_shade_legal(t & 3, t & 8) ? wf_shade_code(t & 3, t & 4, t & 8) : -1; }
+constexpr int wf_shade_hits_tuple(int t) {
+    const int hits = (t & 16) ? SB_LOAD : SB_STORE, cont = t < 32 ? 0 : t < 64 ? SB_CONT_STORE : SB_CONT_LOAD;
+    return wf_shade_hits_legal(t & 1, hits, t & 2, t & 4, cont, t & 8) ? wf_shade_hits_code(t & 1, hits, t & 2, t & 4, cont, t & 8) : -1;
+}
+constexpr int wf_shade_fused_tuple(int t) { return wf_shade_fused_legal(t & 1, t & 2, t & 4) ? wf_shade_fused_code(t & 1, t & 2, t & 4) : -1; }
+// The number of legal tuples among [0, tuples) - or -1 where one of them maps to a code that is not listed, or a listed code
+// is the image of none.
+template <int N>
+constexpr int sb_legal_tuples(const int (&codes)[N], int tuples, int (*code_of)(int)) {
+    int legal = 0;
+    bool hit[N] = {};
+    for (int t = 0; t < tuples; ++t) {
+        const int code = code_of(t);
+        if (code < 0) continue;
+        if (!sb_listed(codes, code)) return -1;
+        for (int k = 0; k < N; ++k) hit[k] = hit[k] || codes[k] == code;
+        ++legal;
+    }
+    for (bool h : hit)
+        if (!h) return -1;
+    return legal;
+}
+static_assert(sb_legal_tuples(WF_SHADE_CODES, 16, wf_shade_tuple) == 10, "k_wf_shade: the legal inputs and the table (GRID 0 with and without the orthographic branch is one kernel)");
+static_assert(sb_legal_tuples(WF_SHADE_HITS_CODES, 96, wf_shade_hits_tuple) == 15, "k_wf_shade_hits: the legal inputs and the table");
+static_assert(sb_legal_tuples(WF_SHADE_FUSED_CODES, 8, wf_shade_fused_tuple) == 4, "k_wf_shade_fused: the legal inputs and the table");
 #define WF_HIT1_FLIP 0x10000000u   // bit 28 of a record's word in the later bounces' hit caches ("The bounce-1 hit cache" below)
+// What a kernel below does not have, under the names pt_wf_shade_body.h knows: the planes of the frame caches, group by group ...
+#define WF_SHADE_NO_VIS uint8_t* const vis_plane = nullptr;
+#define WF_SHADE_NO_NEXT                     \
+    const uint4* const next_plane = nullptr; \
+    uint4* const next_hits = nullptr;        \
+    unsigned long long* const next_ctr = nullptr;
+#define WF_SHADE_NO_CONT_FLAGS const uint32_t cont_flags = 0u;   // (the loading variant has them)
+#define WF_SHADE_NO_CONT               \
+    uint4* const cont_plane = nullptr; \
+    const size_t cont_stride = 0;      \
+    WF_SHADE_NO_CONT_FLAGS
+// ... and, k_wf_shade_hits, what bounce 0 of an opaque, uninstrumented frame does not read
+#define WF_SHADE_BOUNCE0_ONLY                                                                         \
+    constexpr bool ALPHA = false, COUNT = false, PRIMARY = true;                                      \
+    const float4* const queue_in = nullptr;                                                           \
+    const uint4 *const hits = nullptr, *const chunk_hits = nullptr;                                   \
+    const uint32_t *const draws = nullptr, *const index_list = nullptr, *const exact_list = nullptr; \
+    DevCounters* const gctr = nullptr;
+// (S and W FIRST, in this order: the PARK variants read them again through the kernarg segment, wf_opaque_arg)
 template <bool ALPHA, bool COUNT, bool PRIMARY, int GRIDX>
-__global__ __launch_bounds__(WF_SHADE_THREADS, GRIDX ? (ALPHA ? WF_SHADE_GRID_WAVES_ALPHA : GRIDX >= 8 ? WF_SHADE_CACHED_WAVES : WF_SHADE_GRID_WAVES) : WF_SHADE_WAVES) void k_wf_shade(DevScene S, WfParams W,
+__global__ __launch_bounds__(WF_SHADE_THREADS, GRIDX ? (ALPHA ? WF_SHADE_GRID_WAVES_ALPHA : (GRIDX & SB_CACHED) ? WF_SHADE_CACHED_WAVES : WF_SHADE_GRID_WAVES) : WF_SHADE_WAVES) void k_wf_shade(DevScene S, WfParams W,
                                                   const uint32_t* __restrict__ tile_offsets,
                                                   const float4* __restrict__ queue_in, const uint4* __restrict__ hits,
                                                   const uint4* rng_planes,
@@ -2071,92 +2187,58 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, GRIDX ? (ALPHA ? WF_SHADE_GRID_WA
                                                   uint32_t* __restrict__ exact_next,
                                                   const uint32_t* __restrict__ block_empty,
                                                   WfCounters* __restrict__ ctr, DevCounters* __restrict__ gctr) {
-    static_assert(GRIDX < 16, "the variants of the camera-hit cache are k_wf_shade_hits");
+    static_assert(sb_listed(WF_SHADE_CODES, GRIDX), "no such variant (those of the camera-hit cache are k_wf_shade_hits)");
     // wf_opaque_arg reads S at offset 0 of the kernarg segment and W right behind it: they must stay this kernel's first two
     // parameters, in this order (anything may follow them)
     static_assert(wf_leading_args<decltype(&k_wf_shade<ALPHA, COUNT, PRIMARY, GRIDX>)>::scene_then_params,
                   "wf_opaque_arg: DevScene and WfParams must be the first two parameters of k_wf_shade");
     uint4* const hit_plane = nullptr;   // (k_wf_shade_hits has one)
-    uint8_t* const vis_plane = nullptr;
-    const uint4* const next_plane = nullptr;   // (the third k_wf_shade_hits has these)
-    uint4* const next_hits = nullptr;
-    unsigned long long* const next_ctr = nullptr;
-    uint4* const cont_plane = nullptr;   // (the overloads with the continuation cache have these)
-    const size_t cont_stride = 0;
-    const uint32_t cont_flags = 0u;
+    WF_SHADE_NO_VIS WF_SHADE_NO_NEXT WF_SHADE_NO_CONT
 #include "pt_wf_shade_body.h"
 }
 
-// The cached opaque bounce-0 kernel with the scene's camera-hit cache: GRIDX = 11 or 15, + 16 (STORE) or + 32 (LOAD).  The
-// parameters bounce 0 does not read (queue_in, hits, draws, the lists) are gone; S and W stay first, see above.
+// The cached opaque bounce-0 kernel with the scene's camera-hit cache: SB_B0_CACHED or SB_B0_CACHED_DIRL, | SB_STORE or
+// | SB_LOAD.  The parameters bounce 0 does not read (queue_in, hits, draws, the lists) are gone; S and W stay first, see above.
+// Six overloads by the planes they take behind these twelve parameters; each says what it takes, what it lacks, and the body.
+#define WF_SHADE_HITS_PARAMS                                                                                                   \
+    DevScene S, WfParams W, const uint32_t* __restrict__ tile_offsets, const uint4* rng_planes, uint4* __restrict__ hit_plane, \
+        float4* __restrict__ queue_out, float4* __restrict__ shadow_q, float4* __restrict__ contrib,                           \
+        float* __restrict__ staging, uint32_t* __restrict__ exact_next, const uint32_t* __restrict__ block_empty,              \
+        WfCounters* __restrict__ ctr
+#define WF_SHADE_VIS_PARAMS uint8_t* __restrict__ vis_plane
+#define WF_SHADE_NEXT_PARAMS const uint4* __restrict__ next_plane, uint4* __restrict__ next_hits, unsigned long long* __restrict__ next_ctr
+#define WF_SHADE_CONT_PARAMS uint4* __restrict__ cont_plane, size_t cont_stride
+// (The overloads by their types: `k_wf_shade_hits<G>` alone names all of them where nothing is called.)
+typedef void (*WfShadeHitsKernel)(WF_SHADE_HITS_PARAMS);
+typedef void (*WfShadeVisKernel)(WF_SHADE_HITS_PARAMS, WF_SHADE_VIS_PARAMS);
+typedef void (*WfShadeNextKernel)(WF_SHADE_HITS_PARAMS, WF_SHADE_VIS_PARAMS, WF_SHADE_NEXT_PARAMS);
+typedef void (*WfShadeContStoreKernel)(WF_SHADE_HITS_PARAMS, WF_SHADE_CONT_PARAMS);
+typedef void (*WfShadeContStoreVisKernel)(WF_SHADE_HITS_PARAMS, WF_SHADE_VIS_PARAMS, WF_SHADE_CONT_PARAMS);
+typedef void (*WfShadeContLoadKernel)(WF_SHADE_HITS_PARAMS, WF_SHADE_VIS_PARAMS, WF_SHADE_NEXT_PARAMS, WF_SHADE_CONT_PARAMS, uint32_t cont_flags);
+static_assert(wf_leading_args<WfShadeHitsKernel>::scene_then_params,   // (one parameter list: checked once)
+              "wf_opaque_arg: DevScene and WfParams must be the first two parameters of k_wf_shade_hits");
 template <int GRIDX>
-__global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_shade_hits(DevScene S, WfParams W,
-                                                  const uint32_t* __restrict__ tile_offsets, const uint4* rng_planes,
-                                                  uint4* __restrict__ hit_plane,
-                                                  float4* __restrict__ queue_out, float4* __restrict__ shadow_q,
-                                                  float4* __restrict__ contrib, float* __restrict__ staging,
-                                                  uint32_t* __restrict__ exact_next,
-                                                  const uint32_t* __restrict__ block_empty,
-                                                  WfCounters* __restrict__ ctr) {
-    static_assert(GRIDX == (11 | 16) || GRIDX == (11 | 32) || GRIDX == (15 | 16) || GRIDX == (15 | 32), "STORE or LOAD of the cached opaque variants");
-    static_assert(wf_leading_args<decltype(&k_wf_shade_hits<GRIDX>)>::scene_then_params,
-                  "wf_opaque_arg: DevScene and WfParams must be the first two parameters of k_wf_shade_hits");
-    constexpr bool ALPHA = false, COUNT = false, PRIMARY = true;
-    // (what bounce 0 does not read)
-    const float4* const queue_in = nullptr;
-    const uint4 *const hits = nullptr, *const chunk_hits = nullptr;
-    const uint32_t *const draws = nullptr, *const index_list = nullptr, *const exact_list = nullptr;
-    DevCounters* const gctr = nullptr;
-    uint8_t* const vis_plane = nullptr;   // (the overload below has one)
-    const uint4* const next_plane = nullptr;   // (the third overload has these)
-    uint4* const next_hits = nullptr;
-    unsigned long long* const next_ctr = nullptr;
-    uint4* const cont_plane = nullptr;   // (the overloads with the continuation cache have these)
-    const size_t cont_stride = 0;
-    const uint32_t cont_flags = 0u;
+__global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_shade_hits(WF_SHADE_HITS_PARAMS) {
+    static_assert(sb_listed(WF_SHADE_HITS_CODES, GRIDX) && ((GRIDX & SB_PLANES) == SB_STORE || (GRIDX & SB_PLANES) == SB_LOAD),
+                  "STORE or LOAD of the cached opaque variants");
+    WF_SHADE_BOUNCE0_ONLY WF_SHADE_NO_VIS WF_SHADE_NO_NEXT WF_SHADE_NO_CONT
 #include "pt_wf_shade_body.h"
 }
 
-// ... and with the scene's shadow-visibility cache (pt_gpu.hip FrameCache vis_cache): GRIDX = 11 or 15, + 32 (LOAD) + 64 (VIS).  In an
+// ... and with the scene's shadow-visibility cache (pt_gpu.hip FrameCache vis_cache): | SB_LOAD | SB_VIS.  In an
 // opaque scene the answer of a bounce-0 shadow cast - og_blocked for one item and one light - depends on the camera hit,
 // the light's kind and position and the geometry: not on the materials, the light's colour or the bounces.  vis_plane
 // holds it, one byte per item of the chunk (two bits per light, zero: unknown); a lane casts for the lights it does not
 // know yet and writes its byte back, so the launch that fills the plane and those that read it are one kernel.  An
 // overload of its own, by the one parameter more: the kernels above keep their arguments, and their code, as they were.
-// (The two overloads by their types: `k_wf_shade_hits<G>` alone names both where nothing is called.)
-typedef void (*WfShadeHitsKernel)(DevScene, WfParams, const uint32_t*, const uint4*, uint4*, float4*, float4*, float4*, float*, uint32_t*,
-                                  const uint32_t*, WfCounters*);
-typedef void (*WfShadeVisKernel)(DevScene, WfParams, const uint32_t*, const uint4*, uint4*, float4*, float4*, float4*, float*, uint32_t*,
-                                 const uint32_t*, WfCounters*, uint8_t*);
 template <int GRIDX>
-__global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_shade_hits(DevScene S, WfParams W,
-                                                  const uint32_t* __restrict__ tile_offsets, const uint4* rng_planes,
-                                                  uint4* __restrict__ hit_plane,
-                                                  float4* __restrict__ queue_out, float4* __restrict__ shadow_q,
-                                                  float4* __restrict__ contrib, float* __restrict__ staging,
-                                                  uint32_t* __restrict__ exact_next,
-                                                  const uint32_t* __restrict__ block_empty,
-                                                  WfCounters* __restrict__ ctr, uint8_t* __restrict__ vis_plane) {
-    static_assert(GRIDX == (11 | 32 | 64) || GRIDX == (15 | 32 | 64), "LOAD and VIS of the cached opaque variants");
-    // (S and W first: wf_opaque_arg, as above)
-    static_assert(wf_leading_args<WfShadeVisKernel>::scene_then_params,
-                  "wf_opaque_arg: DevScene and WfParams must be the first two parameters of k_wf_shade_hits");
-    constexpr bool ALPHA = false, COUNT = false, PRIMARY = true;
-    const float4* const queue_in = nullptr;
-    const uint4 *const hits = nullptr, *const chunk_hits = nullptr;
-    const uint32_t *const draws = nullptr, *const index_list = nullptr, *const exact_list = nullptr;
-    DevCounters* const gctr = nullptr;
-    const uint4* const next_plane = nullptr;   // (the overload below has these)
-    uint4* const next_hits = nullptr;
-    unsigned long long* const next_ctr = nullptr;
-    uint4* const cont_plane = nullptr;   // (the overloads with the continuation cache have these)
-    const size_t cont_stride = 0;
-    const uint32_t cont_flags = 0u;
+__global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_shade_hits(WF_SHADE_HITS_PARAMS, WF_SHADE_VIS_PARAMS) {
+    static_assert(sb_listed(WF_SHADE_HITS_CODES, GRIDX) && (GRIDX & SB_PLANES) == (SB_LOAD | SB_VIS), "LOAD and VIS of the cached opaque variants");
+    WF_SHADE_BOUNCE0_ONLY WF_SHADE_NO_NEXT WF_SHADE_NO_CONT
 #include "pt_wf_shade_body.h"
 }
 
-// ... and with the scene's bounce-1 hit cache (pt_gpu.hip FrameCache hit1_cache): GRIDX = 11 or 15, + 32 (LOAD) + 64 (VIS) + 128
-// (NEXT), for a chunk that lies wholly below that cache's mark.  The kernel that makes the bounce-1 ray has the item's index in
+// ... and with the scene's bounce-1 hit cache (pt_gpu.hip FrameCache hit1_cache): | SB_LOAD | SB_VIS | SB_NEXT, for a chunk that lies wholly below that cache's mark.  The kernel that makes the bounce-1 ray has the item's index in
 // a register, and next_plane[i] is as dense a load as hit_plane[i]: it answers the cast where the ray is made.  A survivor
 // whose record says miss and whose colour is final (no shadow record) ENDS here - what wf_prestage_miss stages is its
 // sample, so it gets no queue record and no slot, and is counted in WfCounters::elided_count of the next bounce.  Every other
@@ -2166,31 +2248,10 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_
 // few unknown) only.  next_ctr: four uint64 on the device - [0] the cache's counter of unknown casts (k_wf_hits_load's), and
 // of these launches alone [1] records written, unknown included, [2] records elided, [3] unknown.
 // An overload again, by its three parameters more: the kernels above keep their arguments, and their code, as they were.
-typedef void (*WfShadeNextKernel)(DevScene, WfParams, const uint32_t*, const uint4*, uint4*, float4*, float4*, float4*, float*, uint32_t*,
-                                  const uint32_t*, WfCounters*, uint8_t*, const uint4*, uint4*, unsigned long long*);
 template <int GRIDX>
-__global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_shade_hits(DevScene S, WfParams W,
-                                                  const uint32_t* __restrict__ tile_offsets, const uint4* rng_planes,
-                                                  uint4* __restrict__ hit_plane,
-                                                  float4* __restrict__ queue_out, float4* __restrict__ shadow_q,
-                                                  float4* __restrict__ contrib, float* __restrict__ staging,
-                                                  uint32_t* __restrict__ exact_next,
-                                                  const uint32_t* __restrict__ block_empty,
-                                                  WfCounters* __restrict__ ctr, uint8_t* __restrict__ vis_plane,
-                                                  const uint4* __restrict__ next_plane, uint4* __restrict__ next_hits,
-                                                  unsigned long long* __restrict__ next_ctr) {
-    static_assert(GRIDX == (11 | 32 | 64 | 128) || GRIDX == (15 | 32 | 64 | 128), "LOAD, VIS and NEXT of the cached opaque variants");
-    // (S and W first: wf_opaque_arg, as above)
-    static_assert(wf_leading_args<WfShadeNextKernel>::scene_then_params,
-                  "wf_opaque_arg: DevScene and WfParams must be the first two parameters of k_wf_shade_hits");
-    constexpr bool ALPHA = false, COUNT = false, PRIMARY = true;
-    const float4* const queue_in = nullptr;
-    const uint4 *const hits = nullptr, *const chunk_hits = nullptr;
-    const uint32_t *const draws = nullptr, *const index_list = nullptr, *const exact_list = nullptr;
-    DevCounters* const gctr = nullptr;
-    uint4* const cont_plane = nullptr;   // (the overloads with the continuation cache have these)
-    const size_t cont_stride = 0;
-    const uint32_t cont_flags = 0u;
+__global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_shade_hits(WF_SHADE_HITS_PARAMS, WF_SHADE_VIS_PARAMS, WF_SHADE_NEXT_PARAMS) {
+    static_assert(sb_listed(WF_SHADE_HITS_CODES, GRIDX) && (GRIDX & SB_PLANES) == (SB_LOAD | SB_VIS | SB_NEXT), "LOAD, VIS and NEXT of the cached opaque variants");
+    WF_SHADE_BOUNCE0_ONLY WF_SHADE_NO_CONT
 #include "pt_wf_shade_body.h"
 }
 
@@ -2200,98 +2261,40 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_
 // of the bounce-1 hits, and the launches of one key compute it again and again only to look its cast up in next_plane.  Two
 // planes of uint4 by item keep it: the raw bits of next_d and a state word, the raw bits of next_thr (pt_wf_shade_body.h,
 // CONT_STORE / CONT_LOAD).  next_o is not kept: three multiply-adds on values the lights need anyway.
-// Storing, GRIDX | 1024: the bounce-0 kernel of a chunk whose bounce-1 hits are stored in this frame - the first two
-// overloads above, GRIDX 11 / 15 + 16 (a fresh view: the frame also stores its camera hits) or + 32 + 64 (a view whose
+// Storing, | SB_CONT_STORE: the bounce-0 kernel of a chunk whose bounce-1 hits are stored in this frame - the first two
+// overloads above, | SB_STORE (a fresh view: the frame also stores its camera hits) or | SB_LOAD | SB_VIS (a view whose
 // materials were edited), with the planes as two parameters more.
-// Loading, GRIDX | 2048: the third overload above with the same two parameters more, for a chunk that also lies below the
+// Loading, | SB_CONT_LOAD: the third overload above with the same two parameters more, for a chunk that also lies below the
 // continuation planes' mark.  A hit lane whose state word is zero cannot occur there; it is counted in next_ctr[6].
 // The escape test's answer (PT_CONT_ESCAPE): the storing launch records it where the scene has masks (bits 1 and 2 of the state
 // word); the loading launch uses it where cont_flags bit 0 says that the scene's masks are still those - a flag argument, set by
 // the host from the scene's mask generation - and the record has one, and runs the test itself for any other lane.
 // Overloads again, by their parameters: the kernels above keep their arguments, and their code, as they were.
-typedef void (*WfShadeContStoreKernel)(DevScene, WfParams, const uint32_t*, const uint4*, uint4*, float4*, float4*, float4*, float*, uint32_t*,
-                                       const uint32_t*, WfCounters*, uint4*, size_t);
-typedef void (*WfShadeContStoreVisKernel)(DevScene, WfParams, const uint32_t*, const uint4*, uint4*, float4*, float4*, float4*, float*,
-                                          uint32_t*, const uint32_t*, WfCounters*, uint8_t*, uint4*, size_t);
-typedef void (*WfShadeContLoadKernel)(DevScene, WfParams, const uint32_t*, const uint4*, uint4*, float4*, float4*, float4*, float*, uint32_t*,
-                                      const uint32_t*, WfCounters*, uint8_t*, const uint4*, uint4*, unsigned long long*, uint4*, size_t, uint32_t);
 template <int GRIDX>
-__global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_shade_hits(DevScene S, WfParams W,
-                                                  const uint32_t* __restrict__ tile_offsets, const uint4* rng_planes,
-                                                  uint4* __restrict__ hit_plane,
-                                                  float4* __restrict__ queue_out, float4* __restrict__ shadow_q,
-                                                  float4* __restrict__ contrib, float* __restrict__ staging,
-                                                  uint32_t* __restrict__ exact_next,
-                                                  const uint32_t* __restrict__ block_empty,
-                                                  WfCounters* __restrict__ ctr, uint4* __restrict__ cont_plane, size_t cont_stride) {
-    static_assert(GRIDX == (11 | 16 | 1024) || GRIDX == (15 | 16 | 1024), "STORE and CONT_STORE of the cached opaque variants");
-    const uint32_t cont_flags = 0u;   // (the loading variant has them)
-    // (S and W first: wf_opaque_arg, as above)
-    static_assert(wf_leading_args<WfShadeContStoreKernel>::scene_then_params,
-                  "wf_opaque_arg: DevScene and WfParams must be the first two parameters of k_wf_shade_hits");
-    constexpr bool ALPHA = false, COUNT = false, PRIMARY = true;
-    const float4* const queue_in = nullptr;
-    const uint4 *const hits = nullptr, *const chunk_hits = nullptr;
-    const uint32_t *const draws = nullptr, *const index_list = nullptr, *const exact_list = nullptr;
-    DevCounters* const gctr = nullptr;
-    uint8_t* const vis_plane = nullptr;
-    const uint4* const next_plane = nullptr;
-    uint4* const next_hits = nullptr;
-    unsigned long long* const next_ctr = nullptr;
+__global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_shade_hits(WF_SHADE_HITS_PARAMS, WF_SHADE_CONT_PARAMS) {
+    static_assert(sb_listed(WF_SHADE_HITS_CODES, GRIDX) && (GRIDX & SB_PLANES) == (SB_STORE | SB_CONT_STORE), "STORE and CONT_STORE of the cached opaque variants");
+    WF_SHADE_NO_CONT_FLAGS WF_SHADE_BOUNCE0_ONLY WF_SHADE_NO_VIS WF_SHADE_NO_NEXT
 #include "pt_wf_shade_body.h"
 }
 template <int GRIDX>
-__global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_shade_hits(DevScene S, WfParams W,
-                                                  const uint32_t* __restrict__ tile_offsets, const uint4* rng_planes,
-                                                  uint4* __restrict__ hit_plane,
-                                                  float4* __restrict__ queue_out, float4* __restrict__ shadow_q,
-                                                  float4* __restrict__ contrib, float* __restrict__ staging,
-                                                  uint32_t* __restrict__ exact_next,
-                                                  const uint32_t* __restrict__ block_empty,
-                                                  WfCounters* __restrict__ ctr, uint8_t* __restrict__ vis_plane,
-                                                  uint4* __restrict__ cont_plane, size_t cont_stride) {
-    static_assert(GRIDX == (11 | 32 | 64 | 1024) || GRIDX == (15 | 32 | 64 | 1024), "LOAD, VIS and CONT_STORE of the cached opaque variants");
-    const uint32_t cont_flags = 0u;   // (the loading variant has them)
-    static_assert(wf_leading_args<WfShadeContStoreVisKernel>::scene_then_params,
-                  "wf_opaque_arg: DevScene and WfParams must be the first two parameters of k_wf_shade_hits");
-    constexpr bool ALPHA = false, COUNT = false, PRIMARY = true;
-    const float4* const queue_in = nullptr;
-    const uint4 *const hits = nullptr, *const chunk_hits = nullptr;
-    const uint32_t *const draws = nullptr, *const index_list = nullptr, *const exact_list = nullptr;
-    DevCounters* const gctr = nullptr;
-    const uint4* const next_plane = nullptr;
-    uint4* const next_hits = nullptr;
-    unsigned long long* const next_ctr = nullptr;
+__global__ __launch_bounds__(WF_SHADE_THREADS, WF_SHADE_CACHED_WAVES) void k_wf_shade_hits(WF_SHADE_HITS_PARAMS, WF_SHADE_VIS_PARAMS, WF_SHADE_CONT_PARAMS) {
+    static_assert(sb_listed(WF_SHADE_HITS_CODES, GRIDX) && (GRIDX & SB_PLANES) == (SB_LOAD | SB_VIS | SB_CONT_STORE), "LOAD, VIS and CONT_STORE of the cached opaque variants");
+    WF_SHADE_NO_CONT_FLAGS WF_SHADE_BOUNCE0_ONLY WF_SHADE_NO_NEXT
 #include "pt_wf_shade_body.h"
 }
 // (cont_plane: read only in this launch; not const, as the body's one name for it serves the storing variants too)
-// GRIDX | 4096, LEAN (without the orthographic branch only): the same launch for a frame that is known to need no shadow cast,
+// | SB_LEAN (without the orthographic branch only): the same launch for a frame that is known to need no shadow cast,
 // no escape test and no shadow record - the steady frame - with none of that compiled in (pt_wf_shade_body.h, LEAN): at
 // WF_SHADE_LEAN_WAVES waves per SIMD, 12 KiB of LDS.  The same parameters, so the same template: the bounds follow GRIDX.
 #ifndef WF_SHADE_LEAN_WAVES
 #define WF_SHADE_LEAN_WAVES 5
 #endif
 template <int GRIDX>
-__global__ __launch_bounds__(WF_SHADE_THREADS, (GRIDX & 4096) ? WF_SHADE_LEAN_WAVES : WF_SHADE_CACHED_WAVES) void k_wf_shade_hits(DevScene S, WfParams W,
-                                                  const uint32_t* __restrict__ tile_offsets, const uint4* rng_planes,
-                                                  uint4* __restrict__ hit_plane,
-                                                  float4* __restrict__ queue_out, float4* __restrict__ shadow_q,
-                                                  float4* __restrict__ contrib, float* __restrict__ staging,
-                                                  uint32_t* __restrict__ exact_next,
-                                                  const uint32_t* __restrict__ block_empty,
-                                                  WfCounters* __restrict__ ctr, uint8_t* __restrict__ vis_plane,
-                                                  const uint4* __restrict__ next_plane, uint4* __restrict__ next_hits,
-                                                  unsigned long long* __restrict__ next_ctr,
-                                                  uint4* __restrict__ cont_plane, size_t cont_stride, uint32_t cont_flags) {
-    static_assert(GRIDX == (11 | 32 | 64 | 128 | 2048) || GRIDX == (15 | 32 | 64 | 128 | 2048) || GRIDX == (11 | 32 | 64 | 128 | 2048 | 4096),
+__global__ __launch_bounds__(WF_SHADE_THREADS, (GRIDX & SB_LEAN) ? WF_SHADE_LEAN_WAVES : WF_SHADE_CACHED_WAVES) void k_wf_shade_hits(
+    WF_SHADE_HITS_PARAMS, WF_SHADE_VIS_PARAMS, WF_SHADE_NEXT_PARAMS, WF_SHADE_CONT_PARAMS, uint32_t cont_flags) {
+    static_assert(sb_listed(WF_SHADE_HITS_CODES, GRIDX) && (GRIDX & SB_PLANES) == (SB_LOAD | SB_VIS | SB_NEXT | SB_CONT_LOAD),
                   "LOAD, VIS, NEXT and CONT_LOAD of the cached opaque variants; LEAN without the orthographic branch");
-    static_assert(wf_leading_args<WfShadeContLoadKernel>::scene_then_params,
-                  "wf_opaque_arg: DevScene and WfParams must be the first two parameters of k_wf_shade_hits");
-    constexpr bool ALPHA = false, COUNT = false, PRIMARY = true;
-    const float4* const queue_in = nullptr;
-    const uint4 *const hits = nullptr, *const chunk_hits = nullptr;
-    const uint32_t *const draws = nullptr, *const index_list = nullptr, *const exact_list = nullptr;
-    DevCounters* const gctr = nullptr;
+    WF_SHADE_BOUNCE0_ONLY
 #include "pt_wf_shade_body.h"
 }
 
@@ -2331,8 +2334,7 @@ __global__ __launch_bounds__(256) void k_cont_escape_fill(DevScene S, WfParams W
 }
 
 // The bounce-1 shade pass of an opaque, uninstrumented frame that reads the scene's bounce-1 shadow-visibility cache itself
-// (pt_gpu.hip FrameCache vis1_cache; GRIDX = 256, VIS1), and the bounce-2 hit cache as well (hit2_cache; GRIDX = 256 + 512,
-// NEXT1): k_wf_shade<false, false, false, 0> with three parameters more, for a chunk whose sample batch lies below the
+// (pt_gpu.hip FrameCache vis1_cache; SB_VIS1), and the bounce-2 hit cache as well (hit2_cache; SB_VIS1 | SB_NEXT1): k_wf_shade<false, false, false, 0> with three parameters more, for a chunk whose sample batch lies below the
 // visibility plane's stride (and, NEXT1, whose items all lie below the hit plane's mark), in a scene without the
 // orthographic branch.  Once the plane is full k_og_shadow_vis casts nothing: per record it reads what this kernel wrote
 // a moment before, looks up a byte this kernel can look up - the record's out_slot is in the queue record -, applies the
@@ -2350,15 +2352,15 @@ __global__ __launch_bounds__(256) void k_cont_escape_fill(DevScene S, WfParams W
 // alone [1] next-bounce records written, unknown included (NEXT1), [2] survivors ended or elided here, [3] unknown, [4] records
 // whose lights were added here, [5] records deferred to the shadow queue.  What the launch leaves unwritten the frame plan
 // must still count: WfCounters::elided_count of the next bounce, inlined_count and exact_elided.
-// GRIDX | 8192, LEAN1: the same launch for bounces 1 and 2 of a frame that is known to write (nearly) no shadow record there -
+// | SB_LEAN1: the same launch for bounces 1 and 2 of a frame that is known to write (nearly) no shadow record there -
 // the steady frame - with none of that compiled in (pt_wf_shade_body.h, LEAN1), at WF_SHADE_LEAN1_WAVES waves per SIMD; what it
-// cannot shade it lists in `index_list`.  GRIDX | 16384, HAND: the general body over that list, launched behind it.  The same
+// cannot shade it lists in `index_list`.  | SB_HAND: the general body over that list, launched behind it.  The same
 // parameters, so the same template: the bounds follow GRIDX.
 #ifndef WF_SHADE_LEAN1_WAVES
 #define WF_SHADE_LEAN1_WAVES 5
 #endif
 template <int GRIDX>
-__global__ __launch_bounds__(WF_SHADE_THREADS, (GRIDX & 8192) ? WF_SHADE_LEAN1_WAVES : WF_SHADE_WAVES) void k_wf_shade_fused(DevScene S, WfParams W,
+__global__ __launch_bounds__(WF_SHADE_THREADS, (GRIDX & SB_LEAN1) ? WF_SHADE_LEAN1_WAVES : WF_SHADE_WAVES) void k_wf_shade_fused(DevScene S, WfParams W,
                                                   const uint32_t* __restrict__ tile_offsets,
                                                   const float4* __restrict__ queue_in, const uint4* __restrict__ hits,
                                                   const uint4* rng_planes,
@@ -2369,17 +2371,14 @@ __global__ __launch_bounds__(WF_SHADE_THREADS, (GRIDX & 8192) ? WF_SHADE_LEAN1_W
                                                   uint32_t* __restrict__ exact_next, WfCounters* __restrict__ ctr,
                                                   const uint8_t* __restrict__ vis_bytes, const uint4* __restrict__ next_plane,
                                                   uint4* __restrict__ next_hits, unsigned long long* __restrict__ next_ctr) {
-    static_assert(GRIDX == 256 || GRIDX == (256 | 512) || GRIDX == (256 | 8192) || GRIDX == (256 | 16384),
-                  "VIS1, or VIS1 and NEXT1; LEAN1 and HAND with VIS1 alone");
+    static_assert(sb_listed(WF_SHADE_FUSED_CODES, GRIDX), "VIS1, or VIS1 and NEXT1; LEAN1 and HAND with VIS1 alone");
     constexpr bool ALPHA = false, COUNT = false, PRIMARY = false;
     // (what this pass does not read)
     const uint32_t *const draws = nullptr, *const block_empty = nullptr;
     DevCounters* const gctr = nullptr;
     uint4* const hit_plane = nullptr;
     uint8_t* const vis_plane = const_cast<uint8_t*>(vis_bytes);   // (the body's name for it; VIS1 only reads)
-    uint4* const cont_plane = nullptr;   // (the overloads with the continuation cache have these)
-    const size_t cont_stride = 0;
-    const uint32_t cont_flags = 0u;
+    WF_SHADE_NO_CONT
 #include "pt_wf_shade_body.h"
 }
 

@@ -1,7 +1,7 @@
 // The body of k_wf_shade and of k_wf_shade_hits (pt_wavefront.h), included inside both kernels: a function the two call would
 // be the plainer form, but inlined it compiles the existing variants to other code than the kernel's own text does (scratch
 // of eight variants moved by 4-8 B; profiles/r09_experiments.txt item 0), and those variants are tuned to the byte.
-// In scope: the template parameters ALPHA, COUNT, PRIMARY, GRIDX (as constants in k_wf_shade_hits) and the kernel's
+// In scope: the template parameters ALPHA, COUNT, PRIMARY, GRIDX (bits SB_*; constants in k_wf_shade_hits) and the kernel's
 // parameters - S, W, tile_offsets, queue_in, hits, rng_planes, draws, queue_out, shadow_q, contrib, staging, index_list,
 // exact_list, chunk_hits, exact_next, block_empty, ctr, gctr - and hit_plane, vis_plane, next_plane, next_hits, next_ctr,
 // cont_plane, cont_stride, cont_flags.
@@ -13,18 +13,18 @@
     // own plane (chunk_hits) at the queue index.  exact_next: the exact list of the NEXT bounce - a survivor whose new ray the
     // wavefront walker will not take (slack_is_capped) is listed here, where the ray is made, so that k_wf_trace_exact can
     // walk it while k_wf_trace is busy with the rest of the queue.
-    constexpr int GRID = GRIDX & 3;
-    constexpr bool DIRL = (GRIDX & 4) != 0;
-    constexpr bool CACHED = (GRIDX & 8) != 0;
-    constexpr bool STORE = (GRIDX & 16) != 0, LOAD = (GRIDX & 32) != 0;
-    static_assert(GRIDX != 4, "DIRL needs a grid mode");
+    constexpr int GRID = GRIDX & SB_GRID_MASK;
+    constexpr bool DIRL = (GRIDX & SB_DIRL) != 0;
+    constexpr bool CACHED = (GRIDX & SB_CACHED) != 0;
+    constexpr bool STORE = (GRIDX & SB_STORE) != 0, LOAD = (GRIDX & SB_LOAD) != 0;
+    static_assert(GRIDX != SB_DIRL, "DIRL needs a grid mode");
     static_assert(!(STORE || LOAD) || (CACHED && !ALPHA && !COUNT && PRIMARY), "the camera-hit cache serves the cached opaque bounce-0 kernel");
     static_assert(!(STORE && LOAD), "a launch stores the camera hits or loads them");
-    constexpr bool VIS = (GRIDX & 64) != 0;
+    constexpr bool VIS = (GRIDX & SB_VIS) != 0;
     static_assert(!VIS || LOAD, "the shadow-visibility cache serves the launches that load their camera hits");
     // NEXT: the launch reads the bounce-1 hit cache as well (next_plane: the chunk's records there) - a survivor whose record
     // says miss and whose colour is final ends here, the others get the word and the hit k_wf_hits_load would have copied
-    constexpr bool NEXT = (GRIDX & 128) != 0;
+    constexpr bool NEXT = (GRIDX & SB_NEXT) != 0;
     static_assert(!NEXT || (LOAD && VIS), "the bounce-1 hits are consumed by the launches that load camera hits and visibility");
     static_assert(!CACHED || (GRID == 3 && !COUNT), "the word cache serves the fused bounce-0 kernel");
     // VIS1, NEXT1 (k_wf_shade_fused: the opaque bounce-1 pass of a scene without the orthographic branch).  VIS1: the launch reads
@@ -32,8 +32,8 @@
     // known bits gets them added here, in light order, with the operands of k_og_shadow_vis, and writes no shadow record;
     // any other goes to the shadow queue whole.  NEXT1: the launch reads the bounce-2 hit cache as well (next_plane, by item),
     // as NEXT does one bounce earlier.
-    constexpr bool VIS1 = (GRIDX & 256) != 0, NEXT1 = (GRIDX & 512) != 0;
-    static_assert(!VIS1 || ((GRIDX & 255) == 0 && !ALPHA && !COUNT && !PRIMARY), "the bounce-1 visibility is read by the plain opaque later-bounce pass");
+    constexpr bool VIS1 = (GRIDX & SB_VIS1) != 0, NEXT1 = (GRIDX & SB_NEXT1) != 0;
+    static_assert(!VIS1 || ((GRIDX & (SB_VIS1 - 1)) == 0 && !ALPHA && !COUNT && !PRIMARY), "the bounce-1 visibility is read by the plain opaque later-bounce pass");
     static_assert(!NEXT1 || VIS1, "the bounce-2 hits are consumed by the launch that adds the lights itself");
     // CONT_STORE, CONT_LOAD (k_wf_shade_hits: the scene's cache of bounce-0 continuations, pt_gpu.hip FrameCache cont_cache;
     // cont_plane points at the chunk's first item of plane 0, plane 1 lies cont_stride records behind it).  Plane 0: the raw
@@ -41,11 +41,11 @@
     // escape_proves_miss was evaluated for the item with the masks that existed then; bit 2: its answer), plane 1: the raw bits of next_thr.  CONT_STORE: every hit lane writes
     // its two records behind ct_eval_indirect.  CONT_LOAD: the records are read at the top of the step, beside cam_rec, vis
     // and next_rec, and the launch contains no ct_sample, no ct_eval_indirect and no use of words 2 and 3.
-    constexpr bool CONT_STORE = (GRIDX & 1024) != 0, CONT_LOAD = (GRIDX & 2048) != 0;
+    constexpr bool CONT_STORE = (GRIDX & SB_CONT_STORE) != 0, CONT_LOAD = (GRIDX & SB_CONT_LOAD) != 0;
     static_assert(!CONT_STORE || ((STORE || (LOAD && VIS)) && !NEXT), "the continuation is stored by the launch that runs while the bounce-1 hits are stored");
     static_assert(!CONT_LOAD || NEXT, "the continuation is loaded by the launches that read the bounce-1 hits themselves");
     static_assert(!(CONT_STORE && CONT_LOAD), "a launch stores the continuation or loads it");
-    // LEAN (k_wf_shade_hits<2283 | 4096>: the steady frame of a scene without the orthographic branch).  A frame whose caches
+    // LEAN (k_wf_shade_hits<.. | SB_LEAN>, 6379: the steady frame of a scene without the orthographic branch).  A frame whose caches
     // answer everything makes no shadow cast, runs no escape test and writes no shadow record: this variant contains none of
     // that - no og_light_blocked, no parking, no escape_proves_miss, no shadow-queue stores - and so needs neither the
     // registers nor the LDS that hold the general variant at four waves per SIMD.  The host launches it only for a
@@ -53,9 +53,9 @@
     // same - a COLD lane - writes nothing and raises bit 1 of ctr[0].overflow, which fails the configuration's next call.
     // The records that are consumed behind the lights only (next_rec, cont_d, cont_thr: 48 of the step's 81 dense bytes per
     // item) are fetched at the top of the step, as in the general variant, but wait in LDS, not in registers (sh_late).
-    constexpr bool LEAN = (GRIDX & 4096) != 0;
+    constexpr bool LEAN = (GRIDX & SB_LEAN) != 0;
     static_assert(!LEAN || (CONT_LOAD && !DIRL && PRIMARY), "the lean variant is a loading bounce-0 launch without the orthographic branch");
-    // LEAN1 (k_wf_shade_fused<256 | 8192>: bounces 1 and 2 of a steady frame).  A frame whose visibility bytes are all known
+    // LEAN1 (k_wf_shade_fused<SB_VIS1 | SB_LEAN1>, 8448: bounces 1 and 2 of a steady frame).  A frame whose visibility bytes are all known
     // writes no shadow record at these bounces, sorts nothing, lists no ray for k_wf_trace_exact, plays no roulette and draws
     // words 4-7 of the staged plane only: this variant contains none of the rest - no shadow or contribution record with its
     // second lights loop, no second colour (a known light is added to `color` at once, with the operands `lit` receives in the
@@ -67,7 +67,7 @@
     // The list (`index_list` of both launches; the lean one writes it): sixteen count words by bounce, zeroed once per chunk,
     // then the queue indices - as long as the bounce's queue, so it cannot overflow.  HAND reads the word and the hit of an
     // entry from the chunk's own planes at the queue index.
-    constexpr bool LEAN1 = (GRIDX & 8192) != 0, HAND = (GRIDX & 16384) != 0;
+    constexpr bool LEAN1 = (GRIDX & SB_LEAN1) != 0, HAND = (GRIDX & SB_HAND) != 0;
     static_assert(!(LEAN1 || HAND) || (VIS1 && !NEXT1), "the lean later-bounce variant and its list pass read the visibility bytes alone");
     static_assert(!(LEAN1 && HAND), "a launch hands over or shades what was handed over");
     uint32_t* const handover = (LEAN1 || HAND) ? const_cast<uint32_t*>(index_list) : nullptr;

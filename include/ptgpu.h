@@ -1350,6 +1350,107 @@ int pt_aov_guides_device(int device, uint64_t n_pixels, uint32_t samples, const 
 int pt_render_denoised_aov(const pt_scene* scene, const pt_profile* profile, const pt_opts* opts,
                            const pt_denoise_params* params, int variance, uint32_t aov_flags, uint8_t* rgb8, float* color);
 
+/* ------------------------------------------------------------------ */
+/* temporal history (no reference counterpart)              */
+/* ------------------------------------------------------------------ */
+
+/* A history carries the sample sums of the frames of a camera path from view to view.  It is for one image size W x H,
+ * unsharded, on one device, and for a STATIC scene: the surface point a pixel's AOV record (pt_render_aov) holds is projected
+ * into the previous camera, the nearest pixel there (or one of its 2x2 footprint) gives its sums and its count when its
+ * surface agrees, and the new frame's sums are added.  It holds two sets of planes - accum (3 f32, sums of sample radiance),
+ * moments (2 f32, pt_render_moments' sums), count (u32), surf (2 x float4: (P.xyz, dist), (u.xyz, prim as int bits); no
+ * surface: (0,0,0,-1.f), (0,0,0,int -1)) - and one plane of guides (PT_GUIDE_FLOATS, pt_aov_guides of the newest frame).
+ * Every step is one f32 IEEE operation, uncontracted, in the order written (tests/history_model.py restates it bit for bit).
+ *
+ * View constants of a camera (host): c0..c3 = columns of `transform`, rows 0..2; A = (c0 c1 c2) in f64; cofactors C[i][j] as
+ * 2x2 determinants p*q - r*s; det = a00*C00 + a01*C01 + a02*C02 (0 or not finite: PT_ERR_INVALID); M[r][c] =
+ * (float)(C[c][r] / det); ty = tanf(fov / 2.f) (the host libm call of the scene's tan_half_fov); tx = ty * ((float)W /
+ * (float)H).
+ *
+ * pt_history_advance, a frame of N samples with AOV records r rendered from `camera`, per destination pixel p:
+ *   surface   cov = r[7]; valid iff cov > 0 && cov + cov >= (float)N (pt_aov_guides' rule).  P = r[8..10] / cov; dist =
+ *             r[3] / cov; nn = (nx*nx + ny*ny) + nz*nz; u = n * (1.f / sqrt(nn)) when 0 < nn < inf, else 0; prim = r[14].
+ *             surf[p] of the new view is written in either case (invalid: the no-surface record).
+ *   project   with the PREVIOUS view's constants: v = P - c3; qx = (M00*v.x + M01*v.y) + M02*v.z, qy, qz alike; w = -qz;
+ *             OUTSIDE when !(w > 0).  fx = ((qx / w / tx + 1.f) * 0.5f) * (float)W; fy = ((1.f - qy / w / ty) * 0.5f) *
+ *             (float)H; OUTSIDE when !(fx >= 0 && fx < (float)W && fy >= 0 && fy < (float)H) (in float: NaN and huge values
+ *             end here).  x0 = (int)floorf(fx), y0 alike.
+ *   taps      sx = (fx - (float)x0 >= 0.5f) ? 1 : -1, sy alike; (x0,y0), (x0+sx,y0), (x0,y0+sy), (x0+sx,y0+sy) in this
+ *             order, a tap outside the image skipped.  Tap q passes iff, in this order: 1. count_prev[q] > 0; 2.
+ *             surf_prev[q].dist >= 0; 3. (u.x*uq.x + u.y*uq.y) + u.z*uq.z >= normal_cos; 4. e = Pq - P, fabsf((e.x*u.x +
+ *             e.y*u.y) + e.z*u.z) <= plane_tol * dist.  The first tap that passes is the source.  No primitive test.
+ *   merge     a source q: c = count_prev[q] with its sums; if c > max_samples: f = (float)max_samples / (float)c, every
+ *             float of the sums times f, c = max_samples; accum[p] = A + a_frame[p], moments[p] = m + m_frame[p],
+ *             count[p] = c + N.  No source (no surface, OUTSIDE, no tap passes, an empty history): the frame's values, bits
+ *             unchanged, count[p] = N.
+ *   map       (optional, int32 per pixel) the source's pixel index, or -1 no surface, -2 OUTSIDE, -3..-6: which of the
+ *             tests 1-4 the PRIMARY tap (x0,y0) failed.
+ * The first frame after create / reset has no previous view: the new camera's constants stand for it and every count is 0.
+ * The guides of the new view come from the same records (pt_aov_guides).  The sets swap when the launch is enqueued.
+ * PT_ERR_INVALID before any device work: a null pointer (map excepted), N < 1, max_samples + N > PT_FILM_MAX_SAMPLES, a
+ * singular camera, misaligned device planes (16 bytes; d_map 4).  The host form takes planes in pt_render_moments' and
+ * pt_render_aov's unsharded layouts and blocks; the device form is asynchronous on hip_stream and allocates nothing.
+ *
+ * pt_history_add_frame renders the frame for the scene's CURRENT camera on the scene's device and advances: with j =
+ * frame_index % K (K = params.rotate, N = profile.samples), K == 1: pt_render_moments_device; K > 1:
+ * pt_render_window_device of profile.samples = K*N, [j*N, j*N + N) on zeroed buffers; then pt_render_aov_device (samples = N,
+ * flags 0) and pt_history_advance_device.  PT_FLAG_MEGAKERNEL and shard_count > 1: PT_ERR_UNSUPPORTED.  The history does not
+ * watch the scene: after a light, material or geometry edit the caller resets it (as with pt_film and pt_lightmix).
+ *
+ * pt_history_resolve: accum / (float)count and pt_render's post-processing, every pixel by its own count (the non-uniform
+ * film resolve).  pt_history_denoise: the film filter (pt_film_denoise: prep, passes, finish) on the history's planes, counts
+ * and its own guides; variance 0 plain, 1 variance-guided.  Refused (PT_ERR_INVALID): an empty history, variance = 1 with any
+ * count below 2, and what pt_film_denoise refuses of params and lum_floor.  The device forms are asynchronous on hip_stream
+ * (denoise: the scratch is the history's, made on the first call).
+ * pt_history_kernel_times: `reps` timings (ms) of k_hist_advance on the history's current planes (nothing is swapped). */
+typedef struct pt_history pt_history;
+typedef struct pt_history_params {
+    float normal_cos;       /* test 3 */
+    float plane_tol;        /* test 4, relative to the pixel's depth */
+    uint32_t max_samples;   /* the cap on a history count before a frame is added */
+    uint32_t rotate;        /* K of pt_history_add_frame, >= 1 */
+} pt_history_params;
+typedef struct pt_history_info {
+    uint32_t width, height;
+    uint32_t frames;          /* advances since create / reset */
+    uint32_t last_samples;    /* N of the last one */
+    uint32_t min_count, max_count;   /* bounds of the count plane (0, 0: empty) */
+    uint64_t device_bytes;
+    pt_history_params params;
+} pt_history_info;
+typedef struct pt_history_view {
+    float c3[3];
+    float M[9];   /* row-major */
+    float tx, ty;
+} pt_history_view;
+/* The best point of the grid of tools/measure_temporal_gain.py (tests/golden/temporal_gain.json: four golden scenes, 64x48,
+ * 4 spp, one degree of orbit a frame; max_samples = 4 frames x 4 spp). */
+#define PT_HISTORY_DEFAULT_NORMAL_COS 0.97f
+#define PT_HISTORY_DEFAULT_PLANE_TOL 0.01f
+#define PT_HISTORY_DEFAULT_MAX_SAMPLES 16u
+#define PT_HISTORY_DEFAULT_ROTATE 8u
+void pt_history_params_default(pt_history_params* params);
+int  pt_history_create(int device, uint32_t width, uint32_t height, const pt_history_params* params, pt_history** out);
+void pt_history_destroy(pt_history* hist);
+int  pt_history_reset(pt_history* hist);
+int  pt_history_get_info(const pt_history* hist, pt_history_info* out);
+int  pt_history_get_view(const pt_history* hist, int which /* 0 previous, 1 current */, pt_history_view* out);
+int  pt_history_advance(pt_history* hist, const pt_camera* camera, uint32_t samples, const float* accum, const float* moments,
+                        const float* aov, int32_t* map /* may be NULL */);   /* host */
+int  pt_history_advance_device(pt_history* hist, const pt_camera* camera, uint32_t samples, const void* d_accum,
+                               const void* d_moments, const void* d_aov, void* d_map, void* hip_stream);
+int  pt_history_add_frame(pt_history* hist, const pt_scene* scene, const pt_profile* profile, const pt_opts* opts,
+                          uint32_t frame_index);
+int  pt_history_read(const pt_history* hist, float* accum, float* moments, uint32_t* counts, float* surf /* n x 8 */,
+                     float* guides /* n x 8 */, int32_t* map /* of the last pt_history_add_frame */);   /* host, each may be NULL */
+int  pt_history_resolve(const pt_history* hist, int tonemap, uint8_t* rgb8, float* color);   /* host */
+int  pt_history_resolve_device(const pt_history* hist, int tonemap, void* d_rgb8, void* d_color, void* hip_stream);
+int  pt_history_denoise(const pt_history* hist, int variance, const pt_denoise_params* params, float lum_floor, uint8_t* rgb8,
+                        float* color);   /* host */
+int  pt_history_denoise_device(const pt_history* hist, int variance, const pt_denoise_params* params, float lum_floor,
+                               void* d_rgb8, void* d_color, void* hip_stream);
+int  pt_history_kernel_times(const pt_history* hist, uint32_t reps, float* ms_advance);
+
 const char* pt_last_error(void);
 const char* pt_version(void);
 

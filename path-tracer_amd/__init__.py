@@ -251,6 +251,33 @@ class FilmShardInfo(C.Structure):
 FILM_EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_void_p)
 
 
+class HistoryParams(C.Structure):
+    """pt_history_params: the reprojection tests, the cap and the window rotation of a History (include/ptgpu.h)."""
+    _fields_ = [("normal_cos", C.c_float), ("plane_tol", C.c_float), ("max_samples", C.c_uint32), ("rotate", C.c_uint32)]
+
+    @classmethod
+    def default(cls, **changes):
+        """pt_history_params_default, with fields replaced by keyword."""
+        p = cls()
+        gpu_lib().pt_history_params_default(C.byref(p))
+        for k, v in changes.items():
+            if k not in dict(cls._fields_):
+                raise TypeError(f"pt_history_params has no field {k!r}")
+            setattr(p, k, v)
+        return p
+
+
+class HistoryInfo(C.Structure):
+    """pt_history_info."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("frames", C.c_uint32), ("last_samples", C.c_uint32),
+                ("min_count", C.c_uint32), ("max_count", C.c_uint32), ("device_bytes", C.c_uint64), ("params", HistoryParams)]
+
+
+class HistoryView(C.Structure):
+    """pt_history_view: the constants of one camera for the history's image size (M row-major)."""
+    _fields_ = [("c3", C.c_float * 3), ("M", C.c_float * 9), ("tx", C.c_float), ("ty", C.c_float)]
+
+
 class Hit(C.Structure):
     _fields_ = [("prim", C.c_int32), ("flags", C.c_int32), ("dist", C.c_float), ("u", C.c_float),
                 ("v", C.c_float)]
@@ -370,7 +397,11 @@ GPU_SYMBOLS = ["pt_scene_create", "pt_scene_destroy", "pt_scene_set_camera", "pt
                "pt_film_select_tiles", "pt_film_render_until_adaptive_sharded", "pt_film_render_until_windowed_sharded",
                "pt_film_exchange_comm", "pt_film_assemble",
                "pt_render_aov", "pt_render_aov_device", "pt_render_aov_samples", "pt_aov_guides", "pt_aov_guides_device",
-               "pt_render_denoised_aov"]
+               "pt_render_denoised_aov",
+               "pt_history_params_default", "pt_history_create", "pt_history_destroy", "pt_history_reset", "pt_history_get_info",
+               "pt_history_get_view", "pt_history_advance", "pt_history_advance_device", "pt_history_add_frame", "pt_history_read",
+               "pt_history_resolve", "pt_history_resolve_device", "pt_history_denoise", "pt_history_denoise_device",
+               "pt_history_kernel_times"]
 
 
 def host_lib():
@@ -616,6 +647,24 @@ def gpu_lib():
                                                                 FILM_PASS_FN, vp, C.POINTER(FilmTileStats)]
             L.pt_film_exchange_comm.argtypes = [vp, vp, C.c_uint32, vp]
             L.pt_film_assemble.argtypes = [vp, C.POINTER(vp), C.c_uint32]
+        if hasattr(L, "pt_history_create"):   # (an A/B library of an earlier commit has no histories)
+            L.pt_history_params_default.argtypes = [C.POINTER(HistoryParams)]
+            L.pt_history_params_default.restype = None
+            L.pt_history_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(HistoryParams), C.POINTER(vp)]
+            L.pt_history_destroy.argtypes = [vp]
+            L.pt_history_destroy.restype = None
+            L.pt_history_reset.argtypes = [vp]
+            L.pt_history_get_info.argtypes = [vp, C.POINTER(HistoryInfo)]
+            L.pt_history_get_view.argtypes = [vp, C.c_int, C.POINTER(HistoryView)]
+            L.pt_history_advance.argtypes = [vp, C.POINTER(Camera), C.c_uint32, vp, vp, vp, vp]
+            L.pt_history_advance_device.argtypes = [vp, C.POINTER(Camera), C.c_uint32, vp, vp, vp, vp, vp]
+            L.pt_history_add_frame.argtypes = [vp, vp, C.POINTER(Profile), C.POINTER(Opts), C.c_uint32]
+            L.pt_history_read.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+            L.pt_history_resolve.argtypes = [vp, C.c_int, vp, vp]
+            L.pt_history_resolve_device.argtypes = [vp, C.c_int, vp, vp, vp]
+            L.pt_history_denoise.argtypes = [vp, C.c_int, C.POINTER(DenoiseParams), C.c_float, vp, vp]
+            L.pt_history_denoise_device.argtypes = [vp, C.c_int, C.POINTER(DenoiseParams), C.c_float, vp, vp, vp]
+            L.pt_history_kernel_times.argtypes = [vp, C.c_uint32, vp]
         L.pt_last_error.restype = C.c_char_p
         L.pt_version.restype = C.c_char_p
         _gpu = L
@@ -1873,6 +1922,123 @@ class Film:
     def close(self):
         if self.handle:
             self.lib.pt_film_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class History:
+    """pt_history: the sample sums of a camera path's frames, carried from view to view by projecting every pixel's AOV
+    surface point into the previous camera (include/ptgpu.h).  For a static scene; owns device memory."""
+
+    def __init__(self, width, height, params=None, device=0):
+        self.lib = gpu_lib()
+        self.handle = C.c_void_p()
+        self.width, self.height = int(width), int(height)
+        params = HistoryParams.default() if params is None else params
+        check_gpu(self.lib.pt_history_create(device, width, height, C.byref(params), C.byref(self.handle)))
+
+    @property
+    def info(self):
+        i = HistoryInfo()
+        check_gpu(self.lib.pt_history_get_info(self.handle, C.byref(i)))
+        return i
+
+    def view(self, which):
+        """pt_history_get_view: the HistoryView of the previous (0) or the current (1) camera."""
+        v = HistoryView()
+        check_gpu(self.lib.pt_history_get_view(self.handle, which, C.byref(v)))
+        return v
+
+    def reset(self):
+        check_gpu(self.lib.pt_history_reset(self.handle))
+
+    def advance(self, camera, samples, accum, moments, aov, want_map=False):
+        """pt_history_advance: a frame of `samples` samples rendered from `camera` (GpuScene.render_moments' accum [n, 3] and
+        moments [n, 2], GpuScene.render_aov's records [n, 16]) joins the history; with want_map the int32 map [n]."""
+        import numpy as np
+        n = self.width * self.height
+        accum = np.ascontiguousarray(accum, np.float32)
+        moments = np.ascontiguousarray(moments, np.float32)
+        aov = np.ascontiguousarray(aov, np.float32)
+        if accum.size != n * 3 or moments.size != n * 2 or aov.size != n * PT_AOV_FLOATS:
+            raise PtError(PT_ERR_INVALID, "History.advance: accum must be [n, 3], moments [n, 2] and aov [n, 16]")
+        cam = make_camera(camera)
+        hmap = np.empty(n, np.int32) if want_map else None
+        check_gpu(self.lib.pt_history_advance(self.handle, C.byref(cam) if cam is not None else None, samples, accum.ctypes.data,
+                                              moments.ctypes.data, aov.ctypes.data, hmap.ctypes.data if want_map else None))
+        return hmap
+
+    def advance_device(self, camera, samples, d_accum, d_moments, d_aov, d_map=None, stream=0):
+        """pt_history_advance_device: device pointers (d_map may be 0 / None), asynchronous on `stream`."""
+        cam = make_camera(camera)
+        check_gpu(self.lib.pt_history_advance_device(self.handle, C.byref(cam) if cam is not None else None, samples, d_accum,
+                                                     d_moments, d_aov, d_map or None, stream))
+
+    def add_frame(self, scene, profile, frame_index, opts=None):
+        """pt_history_add_frame: render the GpuScene's current view (profile.samples samples, the window frame_index % rotate
+        of the longer enumeration) with its AOV records and advance."""
+        check_gpu(self.lib.pt_history_add_frame(self.handle, scene.handle, C.byref(profile),
+                                                C.byref(opts) if opts is not None else None, frame_index))
+
+    def read(self):
+        """pt_history_read: (accum [n, 3], moments [n, 2], counts [n] uint32, surf [n, 8], guides [n, 8])."""
+        import numpy as np
+        n = self.width * self.height
+        acc, mom, cnt = np.empty((n, 3), np.float32), np.empty((n, 2), np.float32), np.empty(n, np.uint32)
+        surf, guides = np.empty((n, 8), np.float32), np.empty((n, PT_GUIDE_FLOATS), np.float32)
+        check_gpu(self.lib.pt_history_read(self.handle, acc.ctypes.data, mom.ctypes.data, cnt.ctypes.data, surf.ctypes.data,
+                                           guides.ctypes.data, None))
+        return acc, mom, cnt, surf, guides
+
+    def read_map(self):
+        """The int32 map [n] of the last add_frame (include/ptgpu.h: a source pixel, or -1 .. -6)."""
+        import numpy as np
+        hmap = np.empty(self.width * self.height, np.int32)
+        check_gpu(self.lib.pt_history_read(self.handle, None, None, None, None, None, hmap.ctypes.data))
+        return hmap
+
+    def resolve(self, tonemap="FILMIC"):
+        """pt_history_resolve: (rgb8 [n, 3] uint8, color [n, 3] float32 = accum / count)."""
+        import numpy as np
+        n = self.width * self.height
+        rgb, col = np.empty((n, 3), np.uint8), np.empty((n, 3), np.float32)
+        check_gpu(self.lib.pt_history_resolve(self.handle, TONEMAPS.get(tonemap, tonemap), rgb.ctypes.data, col.ctypes.data))
+        return rgb, col
+
+    def resolve_device(self, tonemap, d_rgb8, d_color, stream=0):
+        """pt_history_resolve_device: device pointers (either may be 0 / None), asynchronous on `stream`."""
+        check_gpu(self.lib.pt_history_resolve_device(self.handle, TONEMAPS.get(tonemap, tonemap), d_rgb8 or None, d_color or None,
+                                                     stream))
+
+    def denoise(self, params, variance=True, lum_floor=PT_FILM_DEFAULT_LUM_FLOOR):
+        """pt_history_denoise: the film filter on the history's planes, counts and guides; (color [n, 3], rgb8 [n, 3])."""
+        import numpy as np
+        n = self.width * self.height
+        col, rgb = np.empty((n, 3), np.float32), np.empty((n, 3), np.uint8)
+        check_gpu(self.lib.pt_history_denoise(self.handle, int(variance), C.byref(params) if params is not None else None,
+                                              lum_floor, rgb.ctypes.data, col.ctypes.data))
+        return col, rgb
+
+    def denoise_device(self, params, variance, d_rgb8, d_color, lum_floor=PT_FILM_DEFAULT_LUM_FLOOR, stream=0):
+        """pt_history_denoise_device: device pointers (either may be 0 / None), asynchronous on `stream`."""
+        check_gpu(self.lib.pt_history_denoise_device(self.handle, int(variance), C.byref(params), lum_floor, d_rgb8 or None,
+                                                     d_color or None, stream))
+
+    def kernel_times(self, reps=20):
+        """pt_history_kernel_times: ms of k_hist_advance, [reps]."""
+        import numpy as np
+        t = np.zeros(reps, np.float32)
+        check_gpu(self.lib.pt_history_kernel_times(self.handle, reps, t.ctypes.data))
+        return t
+
+    def close(self):
+        if self.handle:
+            self.lib.pt_history_destroy(self.handle)
             self.handle = C.c_void_p()
 
     def __del__(self):

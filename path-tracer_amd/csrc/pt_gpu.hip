@@ -18,6 +18,7 @@
 //   k_film_*          pt_film.h: the progressive film - merging passes, the noise figure of its moments
 //   k_film_*_packed, k_film_import_shard   pt_film_shard.h: the tile kernels of shard films, and their way back to one device
 //   k_aov, k_aov_samples, k_aov_guides   pt_aov.h: sample-coherent feature planes (the samples' camera casts and alpha walks) and guides from them
+//   k_hist_advance                       pt_history.h: a camera path's sums carried from view to view through the AOV positions
 //   k_stream_copy     achievable-HBM yardstick of the roofline (pt_measure_copy_bandwidth)
 //   k_trace / k_trace_all / k_escape_query / k_isect / k_rng / k_math   parity-test hooks
 #include <hip/hip_runtime.h>
@@ -54,6 +55,7 @@
 #include "pt_film_window.h"
 #include "pt_film_shard.h"
 #include "pt_aov.h"
+#include "pt_history.h"
 #include "pthost.h"
 #include "../host/scene_check.h"
 
@@ -4627,28 +4629,44 @@ void film_check_resolve(const char* who, const pt_film* film, int tonemap_type, 
         fail(PT_ERR_INVALID, "%s: some tiles of the film hold no samples", who);
 }
 
-void film_resolve_launch(const pt_film& film, int tonemap_type, uint8_t* d_rgb8, float* d_color, hipStream_t stream) {
-    const uint64_t n_floats = 3u * film.n_local;
-    if (!film.uniform()) {   // every pixel by its own count
+// The planes the resolve and the film filter read: a film's, or a temporal history's.  count == nullptr: every
+// pixel has `samples` samples.  width and height are the filter's (a film made from planes has neither).
+struct FilmPlanes {
+    const float* accum;
+    const float* moments;
+    const uint32_t* count;
+    uint32_t samples, width, height;
+    uint64_t n;
+};
+FilmPlanes film_planes(const pt_film& film) {
+    return {film.accum, film.moments, film.count, (uint32_t)film.samples, film.has_profile ? film.profile.width : 0u,
+            film.has_profile ? film.profile.height : 0u, film.n_local};
+}
+
+void film_resolve_launch(const FilmPlanes& film, int tonemap_type, uint8_t* d_rgb8, float* d_color, hipStream_t stream) {
+    const uint64_t n_floats = 3u * film.n;
+    if (film.count != nullptr) {   // every pixel by its own count
         if (d_color) {
             const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_floats + 255u) / 256u, FILM_MAX_BLOCKS);
-            hipLaunchKernelGGL(k_film_color_counts, dim3(blocks), dim3(256), 0, stream, (const float*)film.accum,
-                               (const uint32_t*)film.count, d_color, n_floats);
+            hipLaunchKernelGGL(k_film_color_counts, dim3(blocks), dim3(256), 0, stream, film.accum, film.count, d_color, n_floats);
         }
         if (d_rgb8)
-            hipLaunchKernelGGL(k_film_post_counts, dim3(((uint32_t)film.n_local + 255u) / 256u), dim3(256), 0, stream,
-                               (const float*)film.accum, (const uint32_t*)film.count, d_rgb8, (uint32_t)film.n_local, tonemap_type);
+            hipLaunchKernelGGL(k_film_post_counts, dim3(((uint32_t)film.n + 255u) / 256u), dim3(256), 0, stream, film.accum, film.count,
+                               d_rgb8, (uint32_t)film.n, tonemap_type);
         HIP_CHECK(hipGetLastError());
         return;
     }
     if (d_color) {
         const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_floats + 255u) / 256u, FILM_MAX_BLOCKS);
-        hipLaunchKernelGGL(k_film_color, dim3(blocks), dim3(256), 0, stream, (const float*)film.accum, d_color, n_floats, (float)film.samples);
+        hipLaunchKernelGGL(k_film_color, dim3(blocks), dim3(256), 0, stream, film.accum, d_color, n_floats, (float)film.samples);
     }
     if (d_rgb8)
-        hipLaunchKernelGGL(k_postprocess, dim3(((uint32_t)film.n_local + 255u) / 256u), dim3(256), 0, stream, (const float*)film.accum,
-                           d_rgb8, (uint32_t)film.n_local, (uint32_t)film.samples, tonemap_type);
+        hipLaunchKernelGGL(k_postprocess, dim3(((uint32_t)film.n + 255u) / 256u), dim3(256), 0, stream, film.accum, d_rgb8,
+                           (uint32_t)film.n, film.samples, tonemap_type);
     HIP_CHECK(hipGetLastError());
+}
+void film_resolve_launch(const pt_film& film, int tonemap_type, uint8_t* d_rgb8, float* d_color, hipStream_t stream) {
+    film_resolve_launch(film_planes(film), tonemap_type, d_rgb8, d_color, stream);
 }
 
 // What the adaptive loops refuse before any device work (the null checks are the callers').
@@ -5066,9 +5084,9 @@ void fdn_check_scene(const char* who, const pt_film* film, const pt_scene* scene
 
 // prep, the passes and the finish on the film's planes; d_color, d_rgb8 and d_ferr (variance only) may be null.
 // ev (measurement only): 4 events - before prep, after prep, after the passes, after the finish.
-void fdn_launch(const pt_film& film, int variance, const pt_denoise_params& p, float lum_floor, const float4* d_guides,
+void fdn_launch(const FilmPlanes& film, int variance, const pt_denoise_params& p, float lum_floor, const float4* d_guides,
                 float* d_color, uint8_t* d_rgb8, float* d_ferr, uint8_t* d_scratch, hipStream_t stream, hipEvent_t* ev = nullptr) {
-    const uint32_t width = film.profile.width, height = film.profile.height, n = width * height, blocks = (n + 255u) / 256u;
+    const uint32_t width = film.width, height = film.height, n = width * height, blocks = (n + 255u) / 256u;
     const uint32_t no_demod = p.flags & PT_DENOISE_NO_DEMODULATE;
     const float2* mom = (const float2*)film.moments;
     size_t e = 0;
@@ -5079,7 +5097,7 @@ void fdn_launch(const pt_film& film, int variance, const pt_denoise_params& p, f
         if (d_color || d_rgb8) film_resolve_launch(film, p.tonemap, d_rgb8, d_color, stream);
         if (d_ferr)
             hipLaunchKernelGGL(k_fdn_finish, dim3(blocks), dim3(256), 0, stream, (const float4*)nullptr, (const float*)nullptr,
-                               (const float*)film.accum, mom, (const uint32_t*)film.count, (uint32_t)film.samples, n, no_demod,
+                               film.accum, mom, film.count, film.samples, n, no_demod,
                                p.tonemap, lum_floor, (float*)nullptr, (uint8_t*)nullptr, d_ferr);
         HIP_CHECK(hipGetLastError());
         if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
@@ -5092,11 +5110,11 @@ void fdn_launch(const pt_film& film, int variance, const pt_denoise_params& p, f
     float2* G = (float2*)(d_scratch + L.g);
     float* D = (float*)(d_scratch + L.d);
     if (variance)
-        hipLaunchKernelGGL(k_fdn_prep<1>, dim3(blocks), dim3(256), 0, stream, (const float*)film.accum, mom, (const uint32_t*)film.count,
-                           (uint32_t)film.samples, d_guides, width, height, no_demod, X, U, G, D);
+        hipLaunchKernelGGL(k_fdn_prep<1>, dim3(blocks), dim3(256), 0, stream, film.accum, mom, film.count,
+                           film.samples, d_guides, width, height, no_demod, X, U, G, D);
     else
-        hipLaunchKernelGGL(k_fdn_prep<0>, dim3(blocks), dim3(256), 0, stream, (const float*)film.accum, mom, (const uint32_t*)film.count,
-                           (uint32_t)film.samples, d_guides, width, height, no_demod, X, U, G, D);
+        hipLaunchKernelGGL(k_fdn_prep<0>, dim3(blocks), dim3(256), 0, stream, film.accum, mom, film.count,
+                           film.samples, d_guides, width, height, no_demod, X, U, G, D);
     HIP_CHECK(hipGetLastError());
     if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
     size_t unused = 0;
@@ -5104,14 +5122,19 @@ void fdn_launch(const pt_film& film, int variance, const pt_denoise_params& p, f
     else dn_passes(width, height, p, X, Y, U, G, stream, nullptr, unused);
     if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
     if (variance)
-        hipLaunchKernelGGL(k_fdn_finish, dim3(blocks), dim3(256), 0, stream, (const float4*)X, (const float*)D, (const float*)film.accum,
-                           mom, (const uint32_t*)film.count, (uint32_t)film.samples, n, no_demod, p.tonemap, lum_floor, d_color,
+        hipLaunchKernelGGL(k_fdn_finish, dim3(blocks), dim3(256), 0, stream, (const float4*)X, (const float*)D, film.accum,
+                           mom, film.count, film.samples, n, no_demod, p.tonemap, lum_floor, d_color,
                            d_rgb8, d_ferr);
     else   // (past the passes k_dn_finish reads neither accum nor samples)
-        hipLaunchKernelGGL(k_dn_finish, dim3(blocks), dim3(256), 0, stream, (const float4*)X, (const float*)D, (const float*)film.accum,
-                           (uint32_t)film.samples, n, no_demod, p.tonemap, d_color, d_rgb8);
+        hipLaunchKernelGGL(k_dn_finish, dim3(blocks), dim3(256), 0, stream, (const float4*)X, (const float*)D, film.accum,
+                           film.samples, n, no_demod, p.tonemap, d_color, d_rgb8);
     HIP_CHECK(hipGetLastError());
     if (ev) HIP_CHECK(hipEventRecord(ev[e++], stream));
+}
+
+void fdn_launch(const pt_film& film, int variance, const pt_denoise_params& p, float lum_floor, const float4* d_guides,
+                float* d_color, uint8_t* d_rgb8, float* d_ferr, uint8_t* d_scratch, hipStream_t stream, hipEvent_t* ev = nullptr) {
+    fdn_launch(film_planes(film), variance, p, lum_floor, d_guides, d_color, d_rgb8, d_ferr, d_scratch, stream, ev);
 }
 
 void fdn_tile_reduce_launch(const pt_film& film, const float* d_err, float* d_tile_sum, float* d_tile_max, hipStream_t stream) {
@@ -6685,6 +6708,423 @@ int pt_render_denoised_aov(const pt_scene* scene, const pt_profile* profile, con
         HIP_CHECK(hipDeviceSynchronize());
         if (rgb8) d_rgb.fetch(rgb8, n * 3);
         if (color) d_color.fetch(color, n * 3);
+    });
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ temporal history (pt_history.h)
+// One allocation: two sets of planes (accum, moments, count, surf), the guides of the newest view, and the buffers
+// pt_history_add_frame renders into (accum, moments, AOV records) - each on a 256-byte boundary.
+struct pt_history {
+    int device = 0;
+    uint32_t width = 0, height = 0;
+    uint64_t n = 0, bytes = 0;
+    pt_history_params params{};
+    uint8_t* base = nullptr;
+    struct Set {
+        float* accum = nullptr;
+        float2* moments = nullptr;
+        uint32_t* count = nullptr;
+        float4* surf = nullptr;
+    } set[2];
+    int cur = 0;   // set[cur]: the current view; set[cur ^ 1]: the previous one (the next launch's output)
+    float4* guides = nullptr;
+    float *frame_accum = nullptr, *frame_aov = nullptr;
+    float2* frame_moments = nullptr;
+    int32_t* frame_map = nullptr;   // the map of the last pt_history_add_frame
+    HistView view[2]{};   // [0] previous, [1] current
+    uint32_t frames = 0, last_samples = 0;
+    uint8_t* filter = nullptr;   // the film filter's scratch, made on first use, kept by pt_history_reset
+    uint64_t bytes_filter = 0;
+    ~pt_history() {
+        if (filter) (void)hipFree(filter);
+        if (base) (void)hipFree(base);
+    }
+};
+
+namespace {
+
+void hist_check_params(const char* who, const pt_history_params* p) {
+    if (!p) fail(PT_ERR_INVALID, "%s: null parameters", who);
+    if (!(p->normal_cos >= -1.f && p->normal_cos <= 1.f)) fail(PT_ERR_INVALID, "%s: normal_cos must be in -1 .. 1", who);
+    if (!(p->plane_tol >= 0.f) || !std::isfinite(p->plane_tol)) fail(PT_ERR_INVALID, "%s: plane_tol must be finite and not negative", who);
+    if (p->max_samples < 1u || p->max_samples >= (uint32_t)PT_FILM_MAX_SAMPLES)
+        fail(PT_ERR_INVALID, "%s: max_samples %u outside 1 .. %u", who, p->max_samples, (unsigned)PT_FILM_MAX_SAMPLES - 1u);
+    if (p->rotate < 1u || p->rotate > 4096u) fail(PT_ERR_INVALID, "%s: rotate %u outside 1 .. 4096", who, p->rotate);
+}
+
+// The view constants of include/ptgpu.h from the columns of a transform and tan(fov / 2).
+HistView hist_view(const char* who, const float* c0, const float* c1, const float* c2, const float* c3, float ty, uint32_t width,
+                   uint32_t height) {
+    const double a[3][3] = {{c0[0], c1[0], c2[0]}, {c0[1], c1[1], c2[1]}, {c0[2], c1[2], c2[2]}};   // a[row][column]
+    double C[3][3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const int r0 = (i + 1) % 3, r1 = (i + 2) % 3, k0 = (j + 1) % 3, k1 = (j + 2) % 3;   // (cyclic: the sign is in the order)
+            C[i][j] = a[r0][k0] * a[r1][k1] - a[r0][k1] * a[r1][k0];
+        }
+    const double det = a[0][0] * C[0][0] + a[0][1] * C[0][1] + a[0][2] * C[0][2];
+    if (det == 0.0 || !std::isfinite(det)) fail(PT_ERR_INVALID, "%s: the camera transform is singular", who);
+    HistView v;
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) v.M[3 * r + c] = (float)(C[c][r] / det);
+    memcpy(v.c3, c3, 12);
+    v.ty = ty;
+    v.tx = ty * ((float)width / (float)height);
+    return v;
+}
+HistView hist_view(const char* who, const pt_camera& cam, uint32_t width, uint32_t height) {
+    const float* T = cam.transform;
+    return hist_view(who, T, T + 4, T + 8, T + 12, tanf(cam.fov / 2.f), width, height);
+}
+
+void hist_check_advance(const char* who, const pt_history* h, uint32_t samples) {
+    if (samples < 1u) fail(PT_ERR_INVALID, "%s: a frame needs samples >= 1", who);
+    if ((uint64_t)h->params.max_samples + samples > (uint64_t)PT_FILM_MAX_SAMPLES)
+        fail(PT_ERR_INVALID, "%s: max_samples %u + %u samples, at most %u", who, h->params.max_samples, samples, (unsigned)PT_FILM_MAX_SAMPLES);
+}
+
+HistArgs hist_args(const pt_history& h, const HistView& prev, uint32_t samples) {
+    HistArgs A;
+    A.prev = prev;
+    A.width = h.width;
+    A.height = h.height;
+    A.samples = samples;
+    A.max_samples = h.params.max_samples;
+    A.normal_cos = h.params.normal_cos;
+    A.plane_tol = h.params.plane_tol;
+    return A;
+}
+
+void hist_launch(const pt_history& h, const HistArgs& A, const pt_history::Set& from, const pt_history::Set& to, const float* d_accum,
+                 const float2* d_moments, const float4* d_aov, int32_t* d_map, hipStream_t stream) {
+    hipLaunchKernelGGL(k_hist_advance, dim3((uint32_t)((h.n + 255u) / 256u)), dim3(256), 0, stream, A, d_aov, d_accum, d_moments,
+                       (const float*)from.accum, (const float2*)from.moments, (const uint32_t*)from.count, (const float4*)from.surf,
+                       to.accum, to.moments, to.count, to.surf, d_map);
+    HIP_CHECK(hipGetLastError());
+}
+
+// The frame `view` of N samples joins the history: the launch, the guides of the new view, the swap.  Everything was checked.
+void hist_advance(pt_history& h, const HistView& view, uint32_t samples, const float* d_accum, const float2* d_moments,
+                  const float4* d_aov, int32_t* d_map, hipStream_t stream) {
+    const HistView prev = h.frames ? h.view[1] : view;   // (an empty history: every count is 0, no tap passes)
+    hist_launch(h, hist_args(h, prev, samples), h.set[h.cur], h.set[h.cur ^ 1], d_accum, d_moments, d_aov, d_map, stream);
+    aov_guides_launch(h.n, samples, d_aov, h.guides, stream);
+    h.cur ^= 1;
+    h.view[0] = prev;
+    h.view[1] = view;
+    h.frames += 1u;
+    h.last_samples = samples;
+}
+
+void hist_zero_counts(pt_history& h) {
+    for (auto& s : h.set) HIP_CHECK(hipMemsetAsync(s.count, 0, h.n * sizeof(uint32_t), nullptr));
+    HIP_CHECK(hipDeviceSynchronize());
+}
+
+FilmPlanes hist_planes(const pt_history& h) {
+    const pt_history::Set& s = h.set[h.cur];
+    return {s.accum, (const float*)s.moments, s.count, h.last_samples, h.width, h.height, h.n};
+}
+
+// The fewest samples a pixel holds.  Every advance leaves count >= N everywhere, so only a history whose last frame had one
+// sample needs its plane read (that read waits for the device).
+uint32_t hist_min_count(const pt_history& h, uint32_t* max_out = nullptr, bool exact = false) {
+    if (!h.frames) {
+        if (max_out) *max_out = 0u;
+        return 0u;
+    }
+    if (!exact && h.last_samples >= 2u) return h.last_samples;
+    std::vector<uint32_t> c(h.n);
+    HIP_CHECK(hipMemcpy(c.data(), h.set[h.cur].count, h.n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    const auto mm = std::minmax_element(c.begin(), c.end());
+    if (max_out) *max_out = *mm.second;
+    return *mm.first;
+}
+
+void hist_check_resolve(const char* who, const pt_history* h, int tonemap_type, const void* rgb8, const void* color) {
+    if (!h || (!rgb8 && !color)) fail(PT_ERR_INVALID, "%s: null argument", who);
+    if (tonemap_type < PT_TONEMAP_REINHARD || tonemap_type > PT_TONEMAP_ACES) fail(PT_ERR_INVALID, "%s: unknown tonemap %d", who, tonemap_type);
+    if (!h->frames) fail(PT_ERR_INVALID, "%s: the history holds no samples", who);
+}
+
+void hist_check_denoise(const char* who, const pt_history* h, int variance, const pt_denoise_params* p, float lum_floor, const void* rgb8,
+                        const void* color) {
+    if (!h || !p || (!rgb8 && !color)) fail(PT_ERR_INVALID, "%s: null argument", who);
+    if (variance != 0 && variance != 1) fail(PT_ERR_INVALID, "%s: variance must be 0 (plain) or 1 (variance-guided)", who);
+    if (variance) dnv_check(who, p, h->width, h->height, 2u);
+    else dn_check_params(who, p);
+    film_check_noise_args(who, lum_floor, 0.0);
+    if (!h->frames) fail(PT_ERR_INVALID, "%s: the history holds no samples", who);
+    if (variance) {
+        HIP_CHECK(hipSetDevice(h->device));
+        const uint32_t least = hist_min_count(*h);
+        if (least < 2u) fail(PT_ERR_INVALID, "%s: a sample variance needs >= 2 samples in every pixel (the fewest: %u)", who, least);
+    }
+}
+
+uint8_t* hist_filter_scratch(const pt_history& h_c) {
+    pt_history& h = const_cast<pt_history&>(h_c);   // (scratch, not the history's contents)
+    if (!h.filter) {
+        const uint64_t bytes = dn_scratch_layout(h.n).total;
+        HIP_CHECK(hipMalloc((void**)&h.filter, bytes));
+        h.bytes_filter = bytes;
+    }
+    return h.filter;
+}
+
+}  // namespace
+
+extern "C" {
+
+void pt_history_params_default(pt_history_params* p) {
+    if (!p) return;
+    p->normal_cos = PT_HISTORY_DEFAULT_NORMAL_COS;
+    p->plane_tol = PT_HISTORY_DEFAULT_PLANE_TOL;
+    p->max_samples = PT_HISTORY_DEFAULT_MAX_SAMPLES;
+    p->rotate = PT_HISTORY_DEFAULT_ROTATE;
+}
+
+int pt_history_create(int device, uint32_t width, uint32_t height, const pt_history_params* params, pt_history** out) {
+    return guarded([&] {
+        const char* who = "pt_history_create";
+        if (!out) fail(PT_ERR_INVALID, "%s: null argument", who);
+        *out = nullptr;
+        hist_check_params(who, params);
+        dn_check_size(who, width, height);
+        if ((uint64_t)width * height > (1ull << 28)) fail(PT_ERR_INVALID, "%s: image too large", who);
+        if (device >= 0) HIP_CHECK(hipSetDevice(device));
+        auto h = std::make_unique<pt_history>();
+        HIP_CHECK(hipGetDevice(&h->device));
+        h->width = width;
+        h->height = height;
+        h->n = (uint64_t)width * height;
+        h->params = *params;
+        auto up = [](uint64_t v) { return (v + 255u) & ~(uint64_t)255u; };
+        const uint64_t n = h->n, b_acc = up(12u * n), b_mom = up(8u * n), b_cnt = up(4u * n), b_surf = up(32u * n), b_aov = up(64u * n);
+        h->bytes = 2u * (b_acc + b_mom + b_cnt + b_surf) + b_surf /* guides */ + b_acc + b_mom + b_aov + b_cnt /* map */;
+        HIP_CHECK(hipMalloc((void**)&h->base, h->bytes));
+        HIP_CHECK(hipMemset(h->base, 0, h->bytes));
+        uint8_t* p = h->base;
+        for (auto& s : h->set) {
+            s.surf = (float4*)p, p += b_surf;
+            s.accum = (float*)p, p += b_acc;
+            s.moments = (float2*)p, p += b_mom;
+            s.count = (uint32_t*)p, p += b_cnt;
+        }
+        h->guides = (float4*)p, p += b_surf;
+        h->frame_aov = (float*)p, p += b_aov;
+        h->frame_accum = (float*)p, p += b_acc;
+        h->frame_moments = (float2*)p, p += b_mom;
+        h->frame_map = (int32_t*)p;
+        *out = h.release();
+    });
+}
+
+void pt_history_destroy(pt_history* hist) { delete hist; }
+
+int pt_history_reset(pt_history* hist) {
+    return guarded([&] {
+        if (!hist) fail(PT_ERR_INVALID, "pt_history_reset: null argument");
+        HIP_CHECK(hipSetDevice(hist->device));
+        hist_zero_counts(*hist);
+        hist->frames = 0;
+        hist->last_samples = 0;
+        hist->view[0] = hist->view[1] = HistView{};
+    });
+}
+
+int pt_history_get_info(const pt_history* hist, pt_history_info* out) {
+    return guarded([&] {
+        if (!hist || !out) fail(PT_ERR_INVALID, "pt_history_get_info: null argument");
+        memset(out, 0, sizeof *out);
+        out->width = hist->width;
+        out->height = hist->height;
+        out->frames = hist->frames;
+        out->last_samples = hist->last_samples;
+        if (hist->frames) {
+            HIP_CHECK(hipSetDevice(hist->device));
+            out->min_count = hist_min_count(*hist, &out->max_count, true);
+        }
+        out->device_bytes = hist->bytes + hist->bytes_filter;
+        out->params = hist->params;
+    });
+}
+
+int pt_history_get_view(const pt_history* hist, int which, pt_history_view* out) {
+    return guarded([&] {
+        if (!hist || !out) fail(PT_ERR_INVALID, "pt_history_get_view: null argument");
+        if (which != 0 && which != 1) fail(PT_ERR_INVALID, "pt_history_get_view: which must be 0 (previous) or 1 (current)");
+        if (!hist->frames) fail(PT_ERR_INVALID, "pt_history_get_view: the history has seen no frame");
+        static_assert(sizeof(pt_history_view) == sizeof(HistView), "pt_history_view is HistView");
+        memcpy(out, &hist->view[which], sizeof *out);
+    });
+}
+
+int pt_history_advance_device(pt_history* hist, const pt_camera* camera, uint32_t samples, const void* d_accum, const void* d_moments,
+                              const void* d_aov, void* d_map, void* hip_stream) {
+    return guarded([&] {
+        const char* who = "pt_history_advance_device";
+        if (!hist || !camera || !d_accum || !d_moments || !d_aov) fail(PT_ERR_INVALID, "%s: null argument", who);
+        hist_check_advance(who, hist, samples);
+        if ((((uintptr_t)d_accum | (uintptr_t)d_moments | (uintptr_t)d_aov) & 15u) || ((uintptr_t)d_map & 3u))
+            fail(PT_ERR_INVALID, "%s: the planes must be 16-byte aligned (the map: 4)", who);
+        const HistView view = hist_view(who, *camera, hist->width, hist->height);
+        HIP_CHECK(hipSetDevice(hist->device));
+        hist_advance(*hist, view, samples, (const float*)d_accum, (const float2*)d_moments, (const float4*)d_aov, (int32_t*)d_map,
+                     (hipStream_t)hip_stream);
+    });
+}
+
+int pt_history_advance(pt_history* hist, const pt_camera* camera, uint32_t samples, const float* accum, const float* moments,
+                       const float* aov, int32_t* map) {
+    return guarded([&] {
+        const char* who = "pt_history_advance";
+        if (!hist || !camera || !accum || !moments || !aov) fail(PT_ERR_INVALID, "%s: null argument", who);
+        hist_check_advance(who, hist, samples);
+        const HistView view = hist_view(who, *camera, hist->width, hist->height);
+        HIP_CHECK(hipSetDevice(hist->device));
+        const size_t n = hist->n;
+        // (the history's own frame buffers take the host planes)
+        HIP_CHECK(hipMemcpy(hist->frame_accum, accum, n * 12u, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(hist->frame_moments, moments, n * 8u, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(hist->frame_aov, aov, n * 64u, hipMemcpyHostToDevice));
+        Staged<int32_t> d_map(nullptr, map ? n : 0);
+        hist_advance(*hist, view, samples, hist->frame_accum, hist->frame_moments, (const float4*)hist->frame_aov, map ? d_map.d : nullptr,
+                     nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        if (map) d_map.fetch(map, n);
+    });
+}
+
+int pt_history_add_frame(pt_history* hist, const pt_scene* scene, const pt_profile* profile, const pt_opts* opts, uint32_t frame_index) {
+    return guarded([&] {
+        const char* who = "pt_history_add_frame";
+        if (!hist || !scene || !profile) fail(PT_ERR_INVALID, "%s: null argument", who);
+        if (profile->width != hist->width || profile->height != hist->height)
+            fail(PT_ERR_INVALID, "%s: a %ux%u frame for a %ux%u history", who, profile->width, profile->height, hist->width, hist->height);
+        if (scene->device != hist->device)
+            fail(PT_ERR_INVALID, "%s: the scene is on device %d, the history on device %d", who, scene->device, hist->device);
+        moments_check_opts(who, opts);
+        pt_opts o;
+        normalise_opts(*profile, opts, o);
+        if (o.shard_count > 1) fail(PT_ERR_UNSUPPORTED, "%s: a history holds the whole image (shard_count %u)", who, o.shard_count);
+        const uint32_t N = profile->samples, K = hist->params.rotate;
+        hist_check_advance(who, hist, N);
+        if ((uint64_t)K * N > (uint64_t)PT_FILM_MAX_SAMPLES) fail(PT_ERR_INVALID, "%s: rotate %u x %u samples, at most %u", who, K, N, (unsigned)PT_FILM_MAX_SAMPLES);
+        const DevScene& D = scene->dev;
+        const HistView view = hist_view(who, D.cam_c0, D.cam_c1, D.cam_c2, D.cam_c3, D.tan_half_fov, hist->width, hist->height);
+        const AovFrame f = aov_frame(who, scene, profile, opts, 0u, hist->frame_aov);
+        HIP_CHECK(hipSetDevice(hist->device));
+        FrameTaps taps;
+        taps.moments = hist->frame_moments;
+        if (K == 1u) {
+            render_device(render_state(scene), *profile, opts, nullptr, hist->frame_accum, nullptr, false, &taps);
+        } else {
+            const uint32_t j = frame_index % K;
+            pt_profile wide = *profile;
+            wide.samples = K * N;
+            const SampleWindow win{j * N, j * N + N};
+            HIP_CHECK(hipMemsetAsync(hist->frame_accum, 0, hist->n * 12u, nullptr));
+            HIP_CHECK(hipMemsetAsync(hist->frame_moments, 0, hist->n * 8u, nullptr));
+            render_device(render_state(scene), wide, opts, nullptr, hist->frame_accum, nullptr, false, &taps, nullptr, &win);
+        }
+        aov_launch(*scene, f, nullptr, (float4*)hist->frame_aov, nullptr);
+        hist_advance(*hist, view, N, hist->frame_accum, hist->frame_moments, (const float4*)hist->frame_aov, hist->frame_map, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+    });
+}
+
+int pt_history_read(const pt_history* hist, float* accum, float* moments, uint32_t* counts, float* surf, float* guides, int32_t* map) {
+    return guarded([&] {
+        if (!hist) fail(PT_ERR_INVALID, "pt_history_read: null argument");
+        HIP_CHECK(hipSetDevice(hist->device));
+        const pt_history::Set& s = hist->set[hist->cur];
+        const size_t n = hist->n;
+        if (accum) HIP_CHECK(hipMemcpy(accum, s.accum, n * 12u, hipMemcpyDeviceToHost));
+        if (moments) HIP_CHECK(hipMemcpy(moments, s.moments, n * 8u, hipMemcpyDeviceToHost));
+        if (counts) HIP_CHECK(hipMemcpy(counts, s.count, n * 4u, hipMemcpyDeviceToHost));
+        if (surf) HIP_CHECK(hipMemcpy(surf, s.surf, n * 32u, hipMemcpyDeviceToHost));
+        if (guides) HIP_CHECK(hipMemcpy(guides, hist->guides, n * 32u, hipMemcpyDeviceToHost));
+        if (map) HIP_CHECK(hipMemcpy(map, hist->frame_map, n * 4u, hipMemcpyDeviceToHost));
+    });
+}
+
+int pt_history_resolve_device(const pt_history* hist, int tonemap, void* d_rgb8, void* d_color, void* hip_stream) {
+    return guarded([&] {
+        hist_check_resolve("pt_history_resolve_device", hist, tonemap, d_rgb8, d_color);
+        HIP_CHECK(hipSetDevice(hist->device));
+        film_resolve_launch(hist_planes(*hist), tonemap, (uint8_t*)d_rgb8, (float*)d_color, (hipStream_t)hip_stream);
+    });
+}
+
+int pt_history_resolve(const pt_history* hist, int tonemap, uint8_t* rgb8, float* color) {
+    return guarded([&] {
+        hist_check_resolve("pt_history_resolve", hist, tonemap, rgb8, color);
+        HIP_CHECK(hipSetDevice(hist->device));
+        const size_t n = (size_t)hist->n * 3u;
+        Staged<uint8_t> d_rgb(nullptr, n);
+        Staged<float> d_color(nullptr, n);
+        film_resolve_launch(hist_planes(*hist), tonemap, rgb8 ? d_rgb.d : nullptr, color ? d_color.d : nullptr, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        if (rgb8) d_rgb.fetch(rgb8, n);
+        if (color) d_color.fetch(color, n);
+    });
+}
+
+int pt_history_denoise_device(const pt_history* hist, int variance, const pt_denoise_params* params, float lum_floor, void* d_rgb8,
+                              void* d_color, void* hip_stream) {
+    return guarded([&] {
+        hist_check_denoise("pt_history_denoise_device", hist, variance, params, lum_floor, d_rgb8, d_color);
+        HIP_CHECK(hipSetDevice(hist->device));
+        fdn_launch(hist_planes(*hist), variance, *params, lum_floor, hist->guides, (float*)d_color, (uint8_t*)d_rgb8, nullptr,
+                   hist_filter_scratch(*hist), (hipStream_t)hip_stream);
+    });
+}
+
+int pt_history_denoise(const pt_history* hist, int variance, const pt_denoise_params* params, float lum_floor, uint8_t* rgb8,
+                       float* color) {
+    return guarded([&] {
+        hist_check_denoise("pt_history_denoise", hist, variance, params, lum_floor, rgb8, color);
+        HIP_CHECK(hipSetDevice(hist->device));
+        const size_t n = (size_t)hist->n * 3u;
+        Staged<uint8_t> d_rgb(nullptr, rgb8 ? n : 0);
+        Staged<float> d_color(nullptr, color ? n : 0);
+        fdn_launch(hist_planes(*hist), variance, *params, lum_floor, hist->guides, color ? d_color.d : nullptr, rgb8 ? d_rgb.d : nullptr,
+                   nullptr, hist_filter_scratch(*hist), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        if (rgb8) d_rgb.fetch(rgb8, n);
+        if (color) d_color.fetch(color, n);
+    });
+}
+
+int pt_history_kernel_times(const pt_history* hist, uint32_t reps, float* ms_advance) {
+    return guarded([&] {
+        const char* who = "pt_history_kernel_times";
+        if (!hist || !ms_advance || !reps) fail(PT_ERR_INVALID, "%s: null argument", who);
+        if (!hist->frames) fail(PT_ERR_INVALID, "%s: the history holds no samples", who);
+        HIP_CHECK(hipSetDevice(hist->device));
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        struct Free {
+            hipEvent_t &a, &b;
+            ~Free() {
+                if (a) (void)hipEventDestroy(a);
+                if (b) (void)hipEventDestroy(b);
+            }
+        } guard{e0, e1};
+        HIP_CHECK(hipEventCreate(&e0));
+        HIP_CHECK(hipEventCreate(&e1));
+        // current set -> the other one (scratch between advances), with the frame buffers as they stand; no swap
+        const HistArgs A = hist_args(*hist, hist->view[1], std::max(1u, hist->last_samples));
+        for (uint32_t r = 0; r < reps; ++r) {
+            HIP_CHECK(hipEventRecord(e0, 0));
+            hist_launch(*hist, A, hist->set[hist->cur], hist->set[hist->cur ^ 1], hist->frame_accum, hist->frame_moments,
+                        (const float4*)hist->frame_aov, nullptr, nullptr);
+            HIP_CHECK(hipEventRecord(e1, 0));
+            HIP_CHECK(hipEventSynchronize(e1));
+            HIP_CHECK(hipEventElapsedTime(&ms_advance[r], e0, e1));
+        }
     });
 }
 

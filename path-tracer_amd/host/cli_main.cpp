@@ -11,6 +11,8 @@
 //                               [--film-denoise <plain|variance> [--filtered-target]]
 //                               [--window-samples <W>]
 //                               [--film-devices <A,B,..>]]
+//                              [--temporal [--temporal-frames <H>] [--temporal-rotate <K>] [--temporal-normal-cos <C>]
+//                               [--temporal-plane-tol <T>] [--temporal-map <FILE_%04d.png>]]
 //       env OUTPUT (default render.png), env PROFILE
 //   path-tracer convert <INPUT> <OUTPUT>      (glTF 2.0 -> ISF, host/gltf_convert.cpp)
 //
@@ -38,7 +40,11 @@
 // --film-devices A,B,.. (with --noise-target and --adaptive and/or --window-samples: the film is held by one shard film per entry
 // - pt_film_create_shard, one host thread, scene and shard film each; the sharded loops exchange their tile noise through a
 // barrier between the threads and take the same passes as the one-device loop; pt_film_assemble then makes the whole film on
-// the first listed device and everything after the loop - resolve, filter, maps, PNG - runs on it unchanged: the same bytes).
+// the first listed device and everything after the loop - resolve, filter, maps, PNG - runs on it unchanged: the same bytes),
+// --temporal (with --camera-path or --keyframes: one pt_history for the run - every frame is rendered by pt_history_add_frame,
+// joins the sums its pixels' surface points find in the previous view, and is written from the history: resolved, or with
+// --denoise filtered by pt_history_denoise; max_samples = H x the profile's samples; a keyframe that edits lights or materials
+// resets the history before its frame).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -117,6 +123,18 @@ void usage_render(FILE* f) {
           "                           the whole film is assembled on the first; the output is the one-device run's, byte for byte\n"
           "      --filtered-target    With --adaptive --film-denoise variance: T is met by the error of the FILTERED image - tiles\n"
           "                           are selected by the variance the filter leaves; --noise-map then shows that error\n"
+          "      --temporal           With --camera-path or --keyframes: keep a temporal history along the path - every frame's\n"
+          "                           samples join those its pixels' surface points find in the previous view (a static scene; a\n"
+          "                           keyframe that edits lights or materials starts the history afresh); with --denoise the\n"
+          "                           history is filtered with every pixel's own sample count (one device)\n"
+          "      --temporal-frames <H>  The history of a pixel is capped at H frames' samples [default: 4]\n"
+          "      --temporal-rotate <K>  Frame i renders the samples [jN, jN + N), j = i mod K, of an enumeration of K N samples, so\n"
+          "                           that still pixels do not see the same samples again [default: the library's]\n"
+          "      --temporal-normal-cos <C>  The least cosine between the normals of a pixel and its history [default: the library's]\n"
+          "      --temporal-plane-tol <T>  The largest distance of the history's point from the pixel's plane, relative to its depth\n"
+          "                           [default: the library's]\n"
+          "      --temporal-map <FILE_%04d.png>  Write where every pixel's history came from as grey: white a source, black no\n"
+          "                           surface, the greys between: outside the previous view, then the test that failed\n"
           "  -h, --help               Print help\n",
           f);
 }
@@ -236,6 +254,9 @@ int run_render(int argc, char** argv) {
     int device = 0;
     std::vector<int> devices, film_devices;
     bool have_film_devices = false;
+    bool temporal = false, have_temporal_frames = false, have_temporal_rotate = false;
+    uint32_t temporal_frames = 4, temporal_rotate = 0;
+    std::string temporal_normal_cos, temporal_plane_tol, temporal_map;
     for (int i = 0; i < argc; ++i) {
         std::string a = argv[i];
         auto value = [&](const char* name) -> std::string {
@@ -266,6 +287,18 @@ int run_render(int argc, char** argv) {
         else if (a == "--stats") stats = true;
         else if (a == "--denoise") denoise = true;
         else if (a == "--light-mixer") light_mixer = true;
+        else if (a == "--temporal") temporal = true;
+        else if (a == "--temporal-frames" || a.rfind("--temporal-frames=", 0) == 0) {
+            temporal_frames = parse_u32(value("--temporal-frames <H>"), "--temporal-frames <H>");
+            have_temporal_frames = true;
+        } else if (a == "--temporal-rotate" || a.rfind("--temporal-rotate=", 0) == 0) {
+            temporal_rotate = parse_u32(value("--temporal-rotate <K>"), "--temporal-rotate <K>");
+            have_temporal_rotate = true;
+        } else if (a == "--temporal-normal-cos" || a.rfind("--temporal-normal-cos=", 0) == 0)
+            temporal_normal_cos = value("--temporal-normal-cos <C>");
+        else if (a == "--temporal-plane-tol" || a.rfind("--temporal-plane-tol=", 0) == 0)
+            temporal_plane_tol = value("--temporal-plane-tol <T>");
+        else if (a == "--temporal-map" || a.rfind("--temporal-map=", 0) == 0) temporal_map = value("--temporal-map <FILE_%04d.png>");
         else if (a == "--denoise-variance") denoise_variance = true;
         else if (a == "--denoise-iterations" || a.rfind("--denoise-iterations=", 0) == 0) {
             std::string v = value("--denoise-iterations <N>");
@@ -383,6 +416,47 @@ int run_render(int argc, char** argv) {
         if (have_keyframes) with("--keyframes <FRAMES>", "a sharded film renders one frame");
         device = film_devices[0];   // the whole film is assembled, resolved and filtered there
     }
+    pt_history_params hist_params;
+    pt_history_params_default(&hist_params);
+    if (!temporal && (have_temporal_frames || have_temporal_rotate || !temporal_normal_cos.empty() || !temporal_plane_tol.empty() ||
+                      !temporal_map.empty()))
+        die("error: '--temporal-frames <H>', '--temporal-rotate <K>', '--temporal-normal-cos <C>', '--temporal-plane-tol <T>' and "
+            "'--temporal-map <FILE_%04d.png>' need '--temporal'");
+    if (temporal) {
+        auto with = [](const char* other, const char* why) {
+            die(std::string("error: the argument '--temporal' cannot be used with '") + other + "' (" + why + ")");
+        };
+        if (!have_camera_path && !have_keyframes) die("error: '--temporal' needs '--camera-path <CAMERAS>' or '--keyframes <FRAMES>'");
+        if (have_noise_target) with("--noise-target <T>", "a film adds samples to one view, a history carries them between views");
+        if (!film_denoise.empty()) with("--film-denoise <plain|variance>", "the history is filtered by '--denoise'");
+        if (have_film_devices) with("--film-devices <A,B,..>", "a history lives on one device");
+        if (light_mixer) with("--light-mixer", "mixed frames have no samples to add to");
+        if (!aov_dir.empty()) with("--aov-dir <DIR>", "the planes are written for a single frame");
+        if (!denoise_guides.empty()) with("--denoise-guides <centre|samples>", "a history is filtered with the guides of its own samples");
+        if (devices.size() > 1) with("--devices <A,B,..>", "a history lives on one device");
+        if (debug_textures) with("--debug-textures", "debug textures are one frame without samples");
+        auto number = [](const std::string& v, const char* name, float lo, float hi) {
+            char* end = nullptr;
+            const float x = strtof(v.c_str(), &end);
+            if (v.empty() || *end || !(x >= lo && x <= hi))
+                die("error: invalid value '" + v + "' for '" + name + "': a number in " + std::to_string(lo) + " .. " + std::to_string(hi) + " expected");
+            return x;
+        };
+        if (!temporal_normal_cos.empty()) hist_params.normal_cos = number(temporal_normal_cos, "--temporal-normal-cos <C>", -1.f, 1.f);
+        if (!temporal_plane_tol.empty()) hist_params.plane_tol = number(temporal_plane_tol, "--temporal-plane-tol <T>", 0.f, 1e6f);
+        if (have_temporal_rotate) {
+            if (temporal_rotate < 1 || temporal_rotate > 4096)
+                die("error: invalid value '" + std::to_string(temporal_rotate) + "' for '--temporal-rotate <K>': 1 .. 4096 expected");
+            hist_params.rotate = temporal_rotate;
+        }
+        if (temporal_frames < 1)
+            die("error: invalid value '" + std::to_string(temporal_frames) + "' for '--temporal-frames <H>': at least 1");
+        if (!temporal_map.empty()) {
+            std::string ext = temporal_map.size() >= 4 ? temporal_map.substr(temporal_map.size() - 4) : "";
+            for (char& c : ext) c = (char)tolower(c);
+            if (ext != ".png") die("The image format could not be determined (only .png output is supported): " + temporal_map);
+        }
+    }
     if (denoise_iterations >= 0 && !denoise && film_denoise.empty()) die("error: '--denoise-iterations <N>' needs '--denoise'");
     if (denoise_variance && !denoise) die("error: '--denoise-variance' needs '--denoise'");
     if (!denoise_guides.empty() && !film_denoise.empty())
@@ -479,6 +553,15 @@ int run_render(int argc, char** argv) {
         if (max_samples > (uint32_t)PT_FILM_MAX_SAMPLES)
             die("error: invalid value '" + std::to_string(max_samples) + "' for '--max-samples <N>': at most " + std::to_string((uint32_t)PT_FILM_MAX_SAMPLES));
     }
+    if (temporal) {
+        const uint64_t cap = (uint64_t)temporal_frames * profile.samples;
+        if (profile.samples < 1 || cap + profile.samples > (uint64_t)PT_FILM_MAX_SAMPLES ||
+            (uint64_t)hist_params.rotate * profile.samples > (uint64_t)PT_FILM_MAX_SAMPLES)
+            die("error: '--temporal-frames <H>' (" + std::to_string(temporal_frames) + ") and '--temporal-rotate <K>' (" +
+                std::to_string(hist_params.rotate) + ") times the profile's samples (" + std::to_string(profile.samples) +
+                ") must stay below " + std::to_string((uint32_t)PT_FILM_MAX_SAMPLES));
+        hist_params.max_samples = (uint32_t)cap;
+    }
     if (denoise_variance && !have_noise_target && profile.samples < 2)
         die("error: '--denoise-variance' needs a profile with samples >= 2 (a sample variance of " + std::to_string(profile.samples) +
             " sample does not exist)");
@@ -520,6 +603,20 @@ int run_render(int argc, char** argv) {
         char num[48];
         snprintf(num, sizeof num, "%0*zu", out_width, f);
         return out_pre + num + out_post;
+    };
+    std::string map_pre, map_post;
+    int map_width = 0;
+    bool map_field = false;
+    if (!temporal_map.empty()) {
+        map_field = frame_pattern(temporal_map, map_pre, map_width, map_post);
+        if ((have_camera_path ? cameras.size() : (size_t)n_keyframes) > 1 && !map_field)
+            die("error: the name '" + temporal_map + "' of '--temporal-map <FILE_%04d.png>' has no %d / %0Nd field for the frame index");
+    }
+    auto map_name = [&](size_t f) {
+        if (!map_field) return temporal_map;
+        char num[48];
+        snprintf(num, sizeof num, "%0*zu", map_width, f);
+        return map_pre + num + map_post;
     };
 
     auto t0 = std::chrono::steady_clock::now();
@@ -987,6 +1084,25 @@ int run_render(int argc, char** argv) {
             if (pth_png_write_rgb8((aov_dir + "/" + file.first).c_str(), profile.width, profile.height, file.second->data()) != PT_OK)
                 die(pth_last_error());
     };
+    // --temporal: one history for the run
+    pt_history* hist = nullptr;
+    if (temporal && pt_history_create(device, profile.width, profile.height, &hist_params, &hist) != PT_OK) die(pt_last_error());
+    auto render_temporal = [&](size_t f) {
+        if (f > 0 && (edits[f].lights || edits[f].materials) && pt_history_reset(hist) != PT_OK) die(pt_last_error());
+        if (pt_history_add_frame(hist, scene, &profile, &opts, (uint32_t)f) != PT_OK) die(pt_last_error());
+        if ((denoise ? pt_history_denoise(hist, denoise_variance ? 1 : 0, &dn, PT_FILM_DEFAULT_LUM_FLOOR, rgb.data(), nullptr)
+                     : pt_history_resolve(hist, profile.tonemap, rgb.data(), nullptr)) != PT_OK)
+            die(pt_last_error());
+        if (temporal_map.empty()) return;
+        std::vector<int32_t> src(n_pixels);
+        if (pt_history_read(hist, nullptr, nullptr, nullptr, nullptr, nullptr, src.data()) != PT_OK) die(pt_last_error());
+        std::vector<uint8_t> grey(n_pixels * 3);
+        for (size_t i = 0; i < n_pixels; ++i) {   // -1 black, -2 .. -6: 32, 64, 96, 128, 160, a source: white
+            const uint8_t g = src[i] >= 0 ? 255 : (uint8_t)(32 * (-src[i] - 1));
+            grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = g;
+        }
+        if (pth_png_write_rgb8(map_name(f).c_str(), profile.width, profile.height, grey.data()) != PT_OK) die(pth_last_error());
+    };
     pt_lightmix* mix = nullptr;
     bool mixer_on = light_mixer;
     size_t lights_of = 0, captures = 0, mixed = 0, rendered = 0;
@@ -1020,6 +1136,9 @@ int run_render(int argc, char** argv) {
         } else if (film) {
             render_film(f);
             ++rendered;
+        } else if (hist) {
+            render_temporal(f);
+            ++rendered;
         } else {
             if ((denoise_guides == "samples"
                      ? pt_render_denoised_aov(scene, &profile, &opts, &dn, denoise_variance ? 1 : 0, 0u, rgb.data(), nullptr)
@@ -1045,6 +1164,7 @@ int run_render(int argc, char** argv) {
 
     if (mix) pt_lightmix_destroy(mix);
     if (film) pt_film_destroy(film);
+    if (hist) pt_history_destroy(hist);
     if (light_mixer) fprintf(stderr, "light mixer: %zu captures, %zu mixed frames, %zu rendered frames\n", captures, mixed, rendered);
 
     if (stats) {
